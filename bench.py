@@ -10,9 +10,12 @@ Workload = BASELINE.json configs[1]: "ViT-B/16 encoder, 4k frames (chunk_size=16
 Frames are sharded by chunk, memory rows by rank; per-GPU work is fixed as N grows ("weak").
 
 Prints ONE JSON line (rank 0).  `value` = frame embeddings per second over all GPUs, inputs resident in HBM.
-Extra objects: `roofline` (dominant kernel, HIP-event timed inside the timed region) and, at N=1 only, `cpu_baseline`
+A plain run does only what that figure needs: set-up, --warmup steps, the --steps timed steps, the outputs of the last
+timed step (--dump-outputs DIR) and the line.  --full adds everything else: `roofline` (dominant kernel, HIP-event
+timed right after the timed region), the per-kernel breakdown, the one-stream A/B and, at N=1 only, `cpu_baseline`
 (the oracle on the host cores, bounded sample), `knn` (the kNN half of the metric on a 1M x 768 index), `streaming`
-(BASELINE configs[4]: 16 x 1080p chunks through one hipGraph) and `c3` (BASELINE configs[2]: CLIP-ViT-L/14-336 bf16).
+(BASELINE configs[4]: 16 x 1080p chunks through one hipGraph), `c3` (BASELINE configs[2]: CLIP-ViT-L/14-336 bf16) and
+the legs mfma_ceiling, rccl_world1, c4_rank_share and extractor.
 """
 import argparse
 import json
@@ -32,6 +35,7 @@ import torch.distributed as dist  # noqa: E402
 
 MFMA_PEAK_TFLOPS = 2500.0  # dense fp16/bf16, MI355X_MICROARCH.md "Peak BF16/FP16 MFMA ~2.5 PF dense"
 HBM_PEAK_GBPS = 8000.0     # MI355X_MICROARCH.md "HBM3E peak BW 8.0 TB/s spec"
+DUMP_LIMIT_BYTES = 60 << 20  # --dump-outputs array bytes: with the .npy headers the files stay under 64 MB
 
 
 def parse():
@@ -39,6 +43,13 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=16)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every figure beyond the headline: per-kernel breakdown, roofline, one-stream A/B and "
+                         "the legs (mfma_ceiling, rccl_world1, knn, c4_rank_share, extractor, streaming, c3, cpu_baseline); "
+                         "the --no-* options below skip single ones of them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (rank 0) as DIR/<name>.npy: embeddings (float32), "
+                         "topk_scores and topk_rows (float64)")
     ap.add_argument("--chunks-per-step", type=int, default=110,
                     help="chunks of 16 frames encoded per step per GPU (110 chunks = 1,760 frames = two encoder passes of "
                          "880, which the default two-stream schedule runs side by side; 55 = one pass, one stream)")
@@ -70,7 +81,8 @@ def parse():
     ap.add_argument("--c3-frames", type=int, default=2048 + 224, help="frames per timing of the C3 leg (rounded down "
                     "to whole encoder passes of 224 frames; BASELINE configs[2] names 32k frames)")
     ap.add_argument("--backend", default="nccl", help="nccl (= RCCL over xGMI); gloo only to rehearse N>1 on one GPU")
-    ap.add_argument("--no-profile", action="store_true", help="do not record per-kernel HIP events in the timed region")
+    ap.add_argument("--no-profile", action="store_true",
+                    help="with --full: do not repeat the timed steps with the dominant kernel's HIP events on")
     ap.add_argument("--dry-run", action="store_true", help="launcher self-test: rendezvous + barrier on the CPU (gloo), "
                     "rank 0 prints a stub line; no GPU work, nothing measured")
     ap.add_argument("--stream-rows", type=int, default=2_097_152, help="rolling memory rows of the C5 latency leg")
@@ -207,6 +219,23 @@ def pmc_traffic(kernel: str, shape: str, leg: str = "main"):
     return None, {"file": None, "kernel": kernel, "run_shape": shape, "note": "no committed PMC summary holds this kernel"}
 
 
+def dump_outputs(dirname: str, emb, scores, rows) -> None:
+    """--dump-outputs: the last timed step's embeddings [F, D] and top-k scores / rows [F, k] as float32 / float64 .npy
+    files (row ids are exact in float64).  Past DUMP_LIMIT_BYTES every array keeps the same seeded sample of queries,
+    whose indices go to sampled_queries.npy."""
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {"embeddings": emb.float().cpu().numpy(), "topk_scores": scores.double().cpu().numpy(),
+              "topk_rows": rows.double().cpu().numpy()}
+    n = arrays["embeddings"].shape[0]
+    keep = min(n, DUMP_LIMIT_BYTES // (sum(a[0].nbytes for a in arrays.values()) + 8))
+    if keep < n:
+        idx = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        arrays = {name: a[idx] for name, a in arrays.items()}
+        arrays["sampled_queries"] = idx.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def note(msg: str) -> None:
     """Progress line on stderr (rank 0's stdout carries exactly one JSON line)."""
     if int(os.environ.get("RANK", "0")) == 0:
@@ -266,7 +295,7 @@ def main():
     # ---- RCCL on this box, before this process touches the GPU: a child process runs dist.ShardedRetriever on a
     # one-rank "nccl" group with both all-gathers forced (tools/rccl_world1.py); a hang there is a timeout here
     rccl_world1 = None
-    if world == 1 and rank == 0 and not args.no_rccl_world1:
+    if args.full and world == 1 and rank == 0 and not args.no_rccl_world1:
         import subprocess
         note("rccl world-1 self-test (child process)")
         try:
@@ -323,30 +352,34 @@ def main():
         emb = enc.embed_frames(frames)                      # [F, D] fp16, L2-normalised
         scores, rows = retriever.search(emb, k)             # global top-k for this rank's F queries
         memory.append(emb)
-        return scores, rows
+        return emb, scores, rows
 
     note(f"main leg: {F} frames per step, {R}-row shard, world {world}")
     for i in range(args.warmup):
         step(i)
     torch.cuda.synchronize()
 
-    # per-kernel breakdown: ONE extra untimed step with every launch bracketed by HIP events (two event records cost
-    # ~7 us per launch here, 12 % of the step).  While per-kernel timing is on, the encoder's default schedule
+    # per-kernel breakdown (--full): ONE extra untimed step with every launch bracketed by HIP events (two event records
+    # cost ~7 us per launch here, 12 % of the step).  While per-kernel timing is on, the encoder's default schedule
     # (VM_SCHED_AUTO, include/vidmem.h) runs ONE stream: with two, a kernel's event duration includes its wait for the
-    # other stream's kernels.
+    # other stream's kernels.  A plain run takes the same step untimed and without events, so that the timed steps
+    # see the same frames and the same memory with and without --full (the two schedules give the same bits).
     mb_frames = enc.micro_batch(F)          # frames per encoder pass (csrc/encoder.hip, micro_batch_of)
     passes = -(-F // mb_frames)
     two_streams = passes >= 2 and args.schedule != "one_stream"   # what VM_SCHED_AUTO does with this step when timing is off
     per_step_events = passes * (7 * spec["layers"] + 8) + 16
-    ctx.profile_enable(per_step_events + 64)
-    step(args.warmup)
-    breakdown = ctx.profile_read()
-    # the two GEMM kernel instantiations, as rocprofv3 names them: the 16-bit-store epilogue (patch embed, QKV,
-    # attention projection, FC2) and the GELU epilogue (FC1)
-    kern_cats = {"gemm256p_kernel<f16, STORE16>": ("gemm_patch", "gemm_qkv", "gemm_resid"),
-                 "gemm256p_kernel<f16, GELU16>": ("gemm_act",)}
-    dom = max(kern_cats, key=lambda kname: sum(breakdown[c][0] for c in kern_cats[kname]))
-    ctx.profile_enable(0)
+    if args.full:
+        ctx.profile_enable(per_step_events + 64)
+        step(args.warmup)
+        breakdown = ctx.profile_read()
+        # the two GEMM kernel instantiations, as rocprofv3 names them: the 16-bit-store epilogue (patch embed, QKV,
+        # attention projection, FC2) and the GELU epilogue (FC1)
+        kern_cats = {"gemm256p_kernel<f16, STORE16>": ("gemm_patch", "gemm_qkv", "gemm_resid"),
+                     "gemm256p_kernel<f16, GELU16>": ("gemm_act",)}
+        dom = max(kern_cats, key=lambda kname: sum(breakdown[c][0] for c in kern_cats[kname]))
+        ctx.profile_enable(0)
+    else:
+        step(args.warmup)
 
     # ---- THE TIMED REGION: exactly args.steps steps of the product's default path (no per-kernel events) -------------
     if world > 1:
@@ -354,18 +387,20 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        step(args.warmup + 1 + i)
+        last = step(args.warmup + 1 + i)
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *last)
     uncert = retriever.uncertified_total()   # queries the fp32 scan could not certify; redone exhaustively in-step
 
     # ---- the dominant kernel's launch durations: the SAME steps again with its HIP events on (recorded on the launch
     # stream; the one-stream schedule, see above).  Also the A/B of the two schedules: same embeddings, bit for bit.
     one_stream = None
-    prof = breakdown
-    if not args.no_profile:
+    prof = breakdown if args.full else None
+    if args.full and not args.no_profile:
         ctx.profile_enable(args.steps * per_step_events + 64)
         ctx.profile_mask(list(kern_cats[dom]))
         torch.cuda.synchronize()
@@ -426,7 +461,7 @@ def main():
             "all-gathered on device tensors, result compared bit for bit with the local search.  One rank moves nothing "
             "over xGMI: the times are RCCL's per-collective overhead, not a link measurement"))
 
-    if rank == 0:
+    if rank == 0 and args.full:
         # ---- roofline of the dominant kernel (by total time inside the timed region) ------------------------
         T = enc.tokens
         H, M = spec["hidden"], spec["mlp"]
@@ -495,7 +530,7 @@ def main():
     # The chip lowers its clock under matrix load: the data sheet's 2.5 PFLOP/s is not what ANY kernel reaches on random
     # operands.  Three synthetic loops - registers only; + the GEMM tile's fragment reads; + its L2 -> LDS staging -
     # put a measured ceiling beside the fraction of the data-sheet peak.
-    if rank == 0 and world == 1 and not args.no_ceiling:
+    if args.full and rank == 0 and world == 1 and not args.no_ceiling:
         note("mfma ceiling leg")
         secs = args.ceiling_seconds
         names = ("registers_only", "with_fragment_reads", "with_fragment_reads_and_staging")
@@ -517,7 +552,7 @@ def main():
                                              "in this run on this GPU; frac stays achieved / the 2.5 PFLOP/s data sheet")
 
     # ---- kNN half of the metric: Q=16 queries/launch over a 1M x 768 index (single GPU part of every rank 0) ----
-    if rank == 0 and world == 1 and not args.no_knn:
+    if args.full and rank == 0 and world == 1 and not args.no_knn:
         note("knn leg")
         del frame_pool
         Mk = args.knn_rows
@@ -568,7 +603,7 @@ def main():
     # 1,048,576-row shard (dist.ShardedRetriever: all-gather queries -> local exhaustive top-k -> all-gather candidates
     # -> 8-part merge of its own 880).  Here the other ranks' queries are embeddings of other synthetic frames, the
     # other ranks' candidate lists are this shard's lists of their queries; nothing crosses a link.
-    if rank == 0 and world == 1 and not args.no_c4:
+    if args.full and rank == 0 and world == 1 and not args.no_c4:
         note("c4 rank-share leg")
         W4 = args.c4_world
         R4 = 1_048_576
@@ -651,7 +686,7 @@ def main():
     # (BASELINE configs[1] literally; reference loop src/pipeline/vlm_extractor.py:44-74).  `value` above batches 55
     # chunks per encoder call from frames resident in HBM; this leg drives the drop-in class from a file on the host:
     # frame reads, pinned staging, H2D, per-chunk top-k + append, JSON and metrics files included.
-    if rank == 0 and world == 1 and not args.no_extractor:
+    if args.full and rank == 0 and world == 1 and not args.no_extractor:
         note("extractor (plugin path) leg")
         import asyncio
         import tempfile
@@ -716,7 +751,7 @@ def main():
                         "are per clip, not per frame"}
 
     # ---- streaming leg (BASELINE configs[4]): 16 x 1080p frames per chunk, rolling 2M-row memory, one hipGraph ------
-    if rank == 0 and world == 1 and not args.no_streaming:
+    if args.full and rank == 0 and world == 1 and not args.no_streaming:
         note("streaming leg")
         from vidmem.streaming import StreamingSession
         Ms = args.stream_rows
@@ -843,7 +878,7 @@ def main():
         ring.close()
 
     # ---- BASELINE configs[2] leg: CLIP-ViT-L/14-336 bf16 encoder + top-20 over a 1M x 1024 bf16 index --------------
-    if rank == 0 and world == 1 and not args.no_c3:
+    if args.full and rank == 0 and world == 1 and not args.no_c3:
         note("c3 leg (CLIP-L/14-336 bf16)")
         del enc
         torch.cuda.empty_cache()
@@ -920,7 +955,7 @@ def main():
         mem3.close()
         del enc3, fr3
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         note("cpu baseline")
         out["cpu_baseline"] = cpu_baseline(spec, weights, mem_rows[:R].cpu().numpy(), k)
 

@@ -1,5 +1,5 @@
 """CPU: the configuration and timing-file shapes of the drop-in classes against the reference's own files
-(config/base_config.yaml is read where it lies under /root/reference when present; the metrics JSON shape restates
+(config/base_config.yaml is stored as tests/golden/reference_base_config.yaml; the metrics JSON shape restates
 src/core/metrics.py:9-66)."""
 import json
 import os
@@ -7,9 +7,8 @@ import textwrap
 from types import SimpleNamespace
 
 import numpy as np
-import pytest
 
-REF_YAML = "/root/reference/config/base_config.yaml"
+REF_YAML = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_base_config.yaml")
 
 
 def test_load_config_keeps_reference_keys_and_adds_sections(tmp_path):
@@ -34,7 +33,6 @@ def test_load_config_keeps_reference_keys_and_adds_sections(tmp_path):
     json.dumps(d)  # what process_video writes under metadata.config
 
 
-@pytest.mark.skipif(not os.path.exists(REF_YAML), reason="reference tree not present (GPU box)")
 def test_reference_yaml_loads_with_defaults_for_the_new_sections():
     from vidmem import config as C
     cfg = C.load_config(REF_YAML)

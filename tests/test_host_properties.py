@@ -80,3 +80,39 @@ def test_bench_launches_itself_for_n_gt_1():
     bad = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--dry-run"], cwd=root,
                          env=env2, capture_output=True, text=True, timeout=120)
     assert bad.returncode != 0
+
+
+def test_bench_dump_outputs_dtypes_and_size_cap(tmp_path):
+    """bench.py --dump-outputs: embeddings as float32, top-k scores and rows as float64, all exact; past the size cap
+    every array keeps the same seeded sample of queries (its indices in sampled_queries.npy) and the arrays stay
+    under the cap.  Run in a child process: importing bench.py sets environment defaults of its own."""
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    prog = r'''
+import sys, numpy as np, torch
+sys.path.insert(0, sys.argv[1])
+import bench
+g = torch.Generator().manual_seed(0)
+emb = torch.randn((300, 16), generator=g).half()
+scores = torch.rand((300, 4), generator=g, dtype=torch.float64)
+rows = torch.randint(0, 1 << 40, (300, 4), generator=g)
+bench.dump_outputs(sys.argv[2] + "/all", emb, scores, rows)
+bench.DUMP_LIMIT_BYTES = 4096
+bench.dump_outputs(sys.argv[2] + "/cut", emb, scores, rows)
+np.save(sys.argv[2] + "/inputs.npy", np.concatenate([emb.float().double().numpy(), scores.numpy(), rows.double().numpy()], 1))
+'''
+    out = subprocess.run([sys.executable, "-c", prog, root, str(tmp_path)], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr[-2000:]
+    inputs = np.load(tmp_path / "inputs.npy")
+    names = ("embeddings", "topk_scores", "topk_rows")
+    full = {n: np.load(tmp_path / "all" / f"{n}.npy") for n in names}
+    assert sorted(os.listdir(tmp_path / "all")) == sorted(f"{n}.npy" for n in names)
+    assert [full[n].dtype for n in names] == [np.float32, np.float64, np.float64]
+    assert np.array_equal(np.concatenate([full[n].astype(np.float64) for n in names], 1), inputs)
+    cut = {n: np.load(tmp_path / "cut" / f"{n}.npy") for n in names + ("sampled_queries",)}
+    idx = cut["sampled_queries"].astype(np.int64)
+    assert 0 < len(idx) < 300 and np.array_equal(idx, np.unique(idx))
+    assert np.array_equal(np.concatenate([cut[n].astype(np.float64) for n in names], 1), inputs[idx])
+    assert sum(a.nbytes for a in cut.values()) <= 4096

@@ -18,7 +18,7 @@ ZERO=1 $B/gemm_bench 173360 3072 768 1 20 2>&1 | grep -v amdgpu.ids | sed "s/^/t
 ZERO=1 $B/gemm_bench_poly 173360 3072 768 1 20 2>&1 | grep -v amdgpu.ids | sed "s/^/poly  ZERO: /"
 python -m pytest tests/test_encoder_gpu.py tests/test_dropin_gpu.py -q > $O/enc_tests.log 2>&1; trc=$?
 tail -5 $O/enc_tests.log; grep -h "rel err\|vs quant" $O/enc_tests.log | head -20
-L="--no-knn --no-c4 --no-extractor --no-streaming --no-c3 --no-cpu-baseline --no-ceiling --no-rccl-world1 --no-profile"
+L="--full --no-knn --no-c4 --no-extractor --no-streaming --no-c3 --no-cpu-baseline --no-ceiling --no-rccl-world1 --no-profile"
 for r in 1 2; do
   python bench.py $L --schedule one_stream > $O/b_one_$r.json 2>/dev/null && python tools/show_bench.py "one_stream 1760 r$r" < $O/b_one_$r.json | cut -c1-60
   python bench.py $L > $O/b_auto_$r.json 2>/dev/null && python tools/show_bench.py "auto 1760 r$r" < $O/b_auto_$r.json | cut -c1-60

@@ -6,6 +6,6 @@ O=gpurun_out/r4y; mkdir -p $O
 python -m pytest tests/test_encoder_gpu.py -q -x > $O/tests.log 2>&1; trc=$?
 tail -3 $O/tests.log
 [ $trc -ne 0 ] && exit $trc
-L="--no-knn --no-c4 --no-extractor --no-streaming --no-cpu-baseline --no-rccl-world1"
+L="--full --no-knn --no-c4 --no-extractor --no-streaming --no-cpu-baseline --no-rccl-world1"
 for r in 1 2; do python bench.py $L > $O/bench$r.json 2> $O/bench.err; python tools/benchsum2.py $O/bench$r.json | grep -E "^value|one-stream|roofline|mfma_ceiling|^c3:"; done
 exit 0
