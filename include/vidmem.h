@@ -129,6 +129,44 @@ int vm_encode_micro_batch(const vm_encoder *enc, int B);
 int vm_encode(vm_encoder *enc, const void *patches, int B, void *out_emb, int l2_normalise, void *workspace,
               size_t workspace_bytes, void *stream);
 
+/* ---- text encoder -------------------------------------------------------------------------------------
+ * CLIP's text transformer (ViT-L/14 family): puts a question into the joint text-image space of a CLIP image encoder
+ * built with its visual projection (proj_dim > 0), the counterpart of OpenAIEmbeddings.aembed_query(query) in
+ * HybridRetriever._vector_search_chunks (src/pipeline/retriever_hybrid.py:284-306).  Token + position embedding
+ * (fp32) -> layers pre-LN blocks with CAUSAL attention (the vision encoder's layer code) -> final LayerNorm of each
+ * sequence's pooled row -> projection (no bias) -> optional L2 -> cast.  The pooled row is the first position whose id
+ * is eot_id, or 0 when there is none (transformers' rule for eos_token_id != 2).  Token ids are clamped into
+ * [0, vocab) on the device; out_flags reports it. */
+typedef struct vm_text_encoder vm_text_encoder;
+typedef struct vm_text_encoder_desc {
+    int vocab;      /* 49408                                            */
+    int context;    /* 77 (at most 80)                                  */
+    int hidden;     /* 768 (% 256, <= 1024)                             */
+    int layers;     /* 12                                               */
+    int heads;      /* 12 (head dim must be 64)                         */
+    int mlp;        /* 3072                                             */
+    int act;        /* vm_act                                           */
+    int proj_dim;   /* 0: none, else text_projection rows (768)         */
+    int eot_id;     /* 49407                                            */
+    int dtype;      /* vm_dtype of GEMM operands and of the output      */
+    float ln_eps;
+} vm_text_encoder_desc;
+/* weights_host: array of DEVICE pointers, in this order (n = 5 + 12*layers):
+ *   0 tok_emb [vocab, hidden] f32   1 pos [context, hidden] f32   2 ln_final_g  3 ln_final_b (f32 [hidden])
+ *   4 proj_w [proj_dim, hidden] dtype (ignored if proj_dim == 0)
+ *   then per layer l, base = 5 + 12*l: the same 12 entries as vm_encoder_create's.  Copied during create. */
+int vm_text_encoder_create(vm_ctx *ctx, const vm_text_encoder_desc *desc, const void *const *weights_host,
+                           int n_weights, vm_text_encoder **out);
+void vm_text_encoder_destroy(vm_text_encoder *enc);
+int vm_text_encoder_out_dim(const vm_text_encoder *enc);   /* proj_dim ? proj_dim : hidden */
+size_t vm_text_encode_workspace_bytes(const vm_text_encoder *enc, int B, int T);
+/* token_ids: device int32 [B,T], 1 <= T <= context.  out_emb [B, out_dim] dtype.  out_flags: device int32 [B] or NULL,
+ * per sequence bit 0 = an id was out of range (clamped), bit 1 = no eot_id (row 0 pooled).  A sequence's embedding
+ * depends only on its ids up to its pooled row: not on B, T or the ids behind it.  Same conventions as vm_encode
+ * (no sync, no allocation, one stream, capturable). */
+int vm_text_encode(vm_text_encoder *enc, const int32_t *token_ids, int B, int T, void *out_emb, int l2_normalise,
+                   int32_t *out_flags, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- embedding memory ---------------------------------------------------------------------------------
  * Replaces the Chunk.embedding store: append = src/components/neo4j_handler.py:229-242
  * (MERGE ... SET c.embedding), bulk read-back = src/components/pre_llm_injector.py:390-412.

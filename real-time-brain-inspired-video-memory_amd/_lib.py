@@ -38,6 +38,8 @@ SYMBOLS = [
     "vm_topk_workspace_bytes", "vm_topk_cosine", "vm_topk_redo_workspace_bytes", "vm_topk_redo_flagged",
     "vm_topk_exact_workspace_bytes", "vm_topk_cosine_exact",
     "vm_cosine_exact", "vm_topk_select", "vm_topk_merge", "vm_profile_enable", "vm_profile_read", "vm_profile_mask", "vm_probe_mfma",
+    "vm_text_encoder_create", "vm_text_encoder_destroy", "vm_text_encoder_out_dim", "vm_text_encode_workspace_bytes",
+    "vm_text_encode",
 ]
 PROF_CATS = ["preprocess", "gemm_patch", "gemm_qkv", "gemm_act", "gemm_resid", "attention", "layernorm", "pool",
              "append", "topk_scan", "topk_finalize", "topk_exact", "topk_merge", "gemm_cls"]
@@ -53,6 +55,12 @@ class EncoderDesc(C.Structure):
     _fields_ = [(n, C.c_int) for n in
                 ("image", "patch", "hidden", "layers", "heads", "mlp", "act", "pre_ln", "patch_bias", "proj_dim",
                  "dtype")] + [("ln_eps", C.c_float)]
+
+
+class TextEncoderDesc(C.Structure):
+    _fields_ = [(n, C.c_int) for n in
+                ("vocab", "context", "hidden", "layers", "heads", "mlp", "act", "proj_dim", "eot_id", "dtype")] + \
+               [("ln_eps", C.c_float)]
 
 
 _lib: Optional[C.CDLL] = None
@@ -119,6 +127,11 @@ def lib() -> C.CDLL:
         "vm_profile_read": (i32, [vp, C.POINTER(f64), C.POINTER(i64)]),
         "vm_profile_mask": (i32, [vp, C.c_uint32]),
         "vm_probe_mfma": (i32, [vp, i32, i32, f64, C.POINTER(f64), vp]),
+        "vm_text_encoder_create": (i32, [vp, C.POINTER(TextEncoderDesc), C.POINTER(vp), i32, C.POINTER(vp)]),
+        "vm_text_encoder_destroy": (None, [vp]),
+        "vm_text_encoder_out_dim": (i32, [vp]),
+        "vm_text_encode_workspace_bytes": (sz, [vp, i32, i32]),
+        "vm_text_encode": (i32, [vp, vp, i32, i32, vp, i32, vp, vp, sz, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError here = header/library drift: fail loudly

@@ -14,6 +14,8 @@ Keys the hot path honours (same names and defaults as the reference where it has
 New:
   encoder: {arch, dtype, weights, seed, device, top_k, look_ahead_chunks}   which vision encoder stands where the remote VLM was
   memory:  {capacity, ring, dtype, snapshot}               the HBM-resident store that stands where Chunk.embedding was
+  text_encoder: {arch, dtype, weights, seed, device, tokenizer}   the question embedder of the retriever (arch null = none;
+           read through section(), so it never appears in a config that does not name it)
 """
 from __future__ import annotations
 
@@ -36,6 +38,14 @@ MEMORY_DEFAULTS: Dict[str, Any] = {
     "ring": False,           # True: rolling window, oldest rows overwritten
     "dtype": None,           # None = the encoder's dtype
     "snapshot": None,        # path of an EmbeddingMemory.snapshot to restore from / save to
+}
+TEXT_ENCODER_DEFAULTS: Dict[str, Any] = {
+    "arch": None,            # specs.TEXT_SPECS key (clip_l14_text); None = no text encoder is built
+    "dtype": "f16",          # f16 | bf16
+    "weights": None,         # .safetensors (a CLIPModel state dict) or .npz of named fp32 arrays; None = seeded synthetic
+    "seed": 42,
+    "device": 0,
+    "tokenizer": None,       # directory with CLIP's vocab.json + merges.txt (local files; text.clip_tokenizer)
 }
 VIDEO_DEFAULTS: Dict[str, Any] = {"chunk_size_seconds": 5.0, "frames_per_chunk": 5, "fps_target": None}
 EMBEDDER_DEFAULTS: Dict[str, Any] = {"top_k_chunk_with_batch_similarity": 3, "top_k_similar_batch": 2}

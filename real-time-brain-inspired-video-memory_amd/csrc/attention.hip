@@ -47,10 +47,12 @@ __device__ __forceinline__ uint16_t ctx_value(float o, float inv) {
 }
 
 // One 16-query tile against all keys of the (frame, head) staged in LDS: scores, softmax, P.V, context store.
-template <int DT, int NT, bool EXACT>
+// CAUSAL (text tower): keys after the lane's query row qrow are masked like keys past T, in every tile, so a row's
+// result does not depend on T or on anything behind it as long as the build (NT) is the same.
+template <int DT, int NT, bool EXACT, bool CAUSAL = false>
 __device__ __forceinline__ void attend_tile(const char *kl, const char *vl, typename vm_elem<DT>::vec8 qa,
                                             typename vm_elem<DT>::vec8 qb, int T, int lane, bool qvalid,
-                                            uint16_t *dst_row, int ctx_nt = 0) {
+                                            uint16_t *dst_row, int ctx_nt = 0, int qrow = 0) {
     using E = vm_elem<DT>;
     using vec8 = typename E::vec8;
     constexpr int NS = (NT + 1) / 2;  // 32-key steps of the PV product
@@ -69,7 +71,13 @@ __device__ __forceinline__ void attend_tile(const char *kl, const char *vl, type
         f32x4 a = f32x4{0.f, 0.f, 0.f, 0.f};
         a = E::mfma16(k0, qa, a);
         a = E::mfma16(k1, qb, a);
-        if (EXACT ? (kt == NT - 1) : (kt * 16 + 16 > T)) {
+        if (CAUSAL) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int key = kt * 16 + 4 * h + j;
+                a[j] = (key < T && key <= qrow) ? a[j] : -INFINITY;   // key 0 always passes: the row max is finite
+            }
+        } else if (EXACT ? (kt == NT - 1) : (kt * 16 + 16 > T)) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) a[j] = (kt * 16 + 4 * h + j < T) ? a[j] : -INFINITY;
         }
@@ -901,8 +909,8 @@ int launch_long(vm_ctx *ctx, const uint16_t *qkv, uint16_t *out, int B, int T, i
 }
 
 // NT = key tiles of 16 (13 for 197 tokens, 37 for 577).  EXACT: T > 16*(NT-1), so only the last tile has masked keys
-// and the mask is resolved at compile time for every other tile.
-template <int DT, int NT, bool EXACT, int OCC>
+// and the mask is resolved at compile time for every other tile.  CAUSAL: the text tower's mask (attend_tile).
+template <int DT, int NT, bool EXACT, int OCC, bool CAUSAL = false>
 __global__ void __launch_bounds__(256, OCC)
     attention_kernel(const uint16_t *__restrict__ qkv, uint16_t *__restrict__ ctx_out, int T, int heads, int qt_lim) {
     using E = vm_elem<DT>;
@@ -958,8 +966,8 @@ __global__ void __launch_bounds__(256, OCC)
         const vec8 qa = q0, qb = q1;
         if (qt + 4 < qt_lim) load_q(qt + 4, q0, q1);  // next tile's queries: their latency hides behind this tile
 
-        attend_tile<DT, NT, EXACT>(kl, vl, qa, qb, T, lane, qvalid,
-                                   ctx_out + ((size_t)b * T + (qvalid ? qtok : 0)) * H + head * 64);
+        attend_tile<DT, NT, EXACT, CAUSAL>(kl, vl, qa, qb, T, lane, qvalid,
+                                           ctx_out + ((size_t)b * T + (qvalid ? qtok : 0)) * H + head * 64, 0, qtok);
     }
 }
 
@@ -1072,10 +1080,10 @@ int launch_stream(vm_ctx *ctx, const uint16_t *qkv, uint16_t *out, int B, int T,
 }
 
 
-template <int DT, int NT, bool EXACT, int OCC = (NT <= 13 ? 2 : 1)>
+template <int DT, int NT, bool EXACT, int OCC = (NT <= 13 ? 2 : 1), bool CAUSAL = false>
 int launch(vm_ctx *ctx, const uint16_t *qkv, uint16_t *out, int B, int T, int heads, hipStream_t st, int qt_lim) {
     const size_t lds = (size_t)NT * 16 * 128 * 2;
-    auto kern = attention_kernel<DT, NT, EXACT, OCC>;
+    auto kern = attention_kernel<DT, NT, EXACT, OCC, CAUSAL>;
     static unsigned long long attr_set = 0;   // one bit per device
     if (!((attr_set >> (ctx->device & 63)) & 1ull)) {
         VM_HIP(ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -1088,8 +1096,13 @@ int launch(vm_ctx *ctx, const uint16_t *qkv, uint16_t *out, int B, int T, int he
 }
 
 template <int DT>
-int dispatch(vm_ctx *ctx, const uint16_t *qkv, uint16_t *out, int B, int T, int heads, hipStream_t st, int q_rows) {
+int dispatch(vm_ctx *ctx, const uint16_t *qkv, uint16_t *out, int B, int T, int heads, hipStream_t st, int q_rows,
+             int causal) {
     const int nt = (T + 15) / 16;
+    if (causal) {   // text tower (77 tokens): ONE build for every T <= 80, so a row's result cannot depend on T
+        if (nt > 5) return vm_fail(ctx, VM_ERR_UNSUPPORTED, "causal attention: %d tokens > 80", T);
+        return launch<DT, 5, false, 2, true>(ctx, qkv, out, B, T, heads, st, 5);
+    }
     const int ql = q_rows > 0 ? (q_rows + 15) / 16 : nt;  // query tiles wanted (clamped to the kernel's NT at launch)
     if (nt == 13) {  // ViT-B/16-224: 197 tokens
         return launch_stream<DT, 13, true>(ctx, qkv, out, B, T, heads, st, ql);
@@ -1105,7 +1118,7 @@ int dispatch(vm_ctx *ctx, const uint16_t *qkv, uint16_t *out, int B, int T, int 
 }  // namespace
 
 int vm_attention(vm_ctx *ctx, int dtype, const uint16_t *qkv, uint16_t *ctx_out, int B, int T, int heads,
-                 hipStream_t st, int q_rows) {
-    return dtype == VM_F16 ? dispatch<VM_F16>(ctx, qkv, ctx_out, B, T, heads, st, q_rows)
-                           : dispatch<VM_BF16>(ctx, qkv, ctx_out, B, T, heads, st, q_rows);
+                 hipStream_t st, int q_rows, int causal) {
+    return dtype == VM_F16 ? dispatch<VM_F16>(ctx, qkv, ctx_out, B, T, heads, st, q_rows, causal)
+                           : dispatch<VM_BF16>(ctx, qkv, ctx_out, B, T, heads, st, q_rows, causal);
 }

@@ -293,21 +293,26 @@ __global__ void __launch_bounds__(256) embed_kernel(const uint16_t *__restrict__
 
 // One block per frame: CLS row = x32 + delta16 (the last FC2 output), final LayerNorm (fp32), optional projection
 // W[proj_dim, H] (16-bit weights, 16-bit rounded input, fp32 accumulate), optional L2 normalisation, cast to 16 bit.
-template <int DT>
+// AT_ROW (text tower): the pooled row of sequence b is pool_row[b] instead of 0 (the trailing parameter keeps the
+// vision build's kernel arguments where they were).
+template <int DT, bool AT_ROW = false>
 __global__ void __launch_bounds__(256) pool_kernel(const float *__restrict__ x, const uint16_t *__restrict__ delta16,
                                                    const uint16_t *__restrict__ deltaB16,
                                                    const float *__restrict__ gamma, const float *__restrict__ beta,
                                                    float eps, const uint16_t *__restrict__ proj_w, int proj_dim, int l2,
-                                                   uint16_t *__restrict__ out, int T, int H) {
+                                                   uint16_t *__restrict__ out, int T, int H,
+                                                   const int32_t *__restrict__ pool_row = nullptr) {
     using E = vm_elem<DT>;
     extern __shared__ __attribute__((aligned(16))) float sh[];  // [H] row, then [out_dim] result
     __shared__ float red[8];
     float *y = sh;
     float *res = sh + H;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const float *row = x + (size_t)blockIdx.x * T * H;
-    const uint16_t *drow = delta16 + (size_t)blockIdx.x * T * H;
-    const uint16_t *erow = deltaB16 + (size_t)blockIdx.x * T * H;
+    size_t base = (size_t)blockIdx.x * T * H;
+    if constexpr (AT_ROW) base += (size_t)pool_row[blockIdx.x] * H;
+    const float *row = x + base;
+    const uint16_t *drow = delta16 + base;
+    const uint16_t *erow = deltaB16 + base;
     auto block_sum = [&](float v) {
         v = wave_sum(v);
         __syncthreads();
@@ -353,6 +358,46 @@ __global__ void __launch_bounds__(256) pool_kernel(const float *__restrict__ x, 
         inv = 1.f / fmaxf(nrm, 1e-12f);
     }
     for (int i = tid; i < od; i += 256) out[(size_t)blockIdx.x * od + i] = E::from_float(src[i] * inv);
+}
+
+// Token + position embedding of the text tower, one wave per token row:
+//   x32[b*T + t] = tok[clamp(ids[b*T + t], 0, vocab - 1)] + pos[t]   (fp32 table: no 16-bit storage point)
+// The wave of row t = 0 of each sequence also scans its ids: pool_row[b] = the first t with ids == eot_id, or 0 when
+// there is none (transformers' CLIPTextTransformer rule for eos_token_id != 2); flags[b] (optional) = bit 0: an id was
+// out of range and clamped, bit 1: no EOT.
+template <int VPL>
+__global__ void __launch_bounds__(256) text_embed_kernel(const int32_t *__restrict__ ids, const float *__restrict__ tok,
+                                                         const float *__restrict__ pos, int vocab, int eot_id,
+                                                         float *__restrict__ x32, int32_t *__restrict__ pool_row,
+                                                         int32_t *__restrict__ flags, int rows, int T, int H) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const int b = row / T, t = row - b * T;
+    int id = ids[row];
+    id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
+    const float4 *te = reinterpret_cast<const float4 *>(tok + (size_t)id * H);
+    const float4 *pe = reinterpret_cast<const float4 *>(pos + (size_t)t * H);
+    float4 *xr = reinterpret_cast<float4 *>(x32 + (size_t)row * H);
+#pragma unroll
+    for (int i = 0; i < VPL; ++i) {
+        const float4 e4 = te[lane + 64 * i], p4 = pe[lane + 64 * i];
+        xr[lane + 64 * i] = make_float4(e4.x + p4.x, e4.y + p4.y, e4.z + p4.z, e4.w + p4.w);
+    }
+    if (t != 0) return;
+    int first = T;
+    bool clamped = false;
+    for (int t0 = 0; t0 < T; t0 += 64) {   // wave-uniform loop
+        const int tt = t0 + lane;
+        const int v = tt < T ? ids[(size_t)b * T + tt] : 0;
+        const unsigned long long hit = __ballot(tt < T && v == eot_id);
+        if (hit && first == T) first = t0 + __ffsll((long long)hit) - 1;
+        clamped |= __any(tt < T && (v < 0 || v >= vocab)) != 0;
+    }
+    if (lane == 0) {
+        pool_row[b] = first < T ? first : 0;
+        if (flags) flags[b] = (clamped ? 1 : 0) | (first < T ? 0 : 2);
+    }
 }
 
 }  // namespace
@@ -427,13 +472,31 @@ int vm_embed(vm_ctx *ctx, int dtype, const uint16_t *patch16, const float *cls, 
 
 int vm_pool(vm_ctx *ctx, int dtype, const float *x, const uint16_t *delta16, const uint16_t *deltaB16,
             const float *gamma, const float *beta, float eps, const uint16_t *proj_w, int proj_dim, int l2, uint16_t *out,
-            int B, int T, int H, hipStream_t st) {
+            int B, int T, int H, hipStream_t st, const int32_t *pool_row) {
     const size_t lds = (size_t)(H + (proj_dim > 0 ? proj_dim : 0)) * 4;
     vm_prof_scope prof(ctx, VM_PROF_POOL, st);
-    if (dtype == VM_F16)
+    if (pool_row) {
+        if (dtype == VM_F16)
+            pool_kernel<VM_F16, true><<<B, 256, lds, st>>>(x, delta16, deltaB16, gamma, beta, eps, proj_w, proj_dim, l2, out, T, H, pool_row);
+        else
+            pool_kernel<VM_BF16, true><<<B, 256, lds, st>>>(x, delta16, deltaB16, gamma, beta, eps, proj_w, proj_dim, l2, out, T, H, pool_row);
+    } else if (dtype == VM_F16) {
         pool_kernel<VM_F16><<<B, 256, lds, st>>>(x, delta16, deltaB16, gamma, beta, eps, proj_w, proj_dim, l2, out, T, H);
-    else
+    } else {
         pool_kernel<VM_BF16><<<B, 256, lds, st>>>(x, delta16, deltaB16, gamma, beta, eps, proj_w, proj_dim, l2, out, T, H);
+    }
+    VM_LAUNCH_CHECK(ctx);
+    return VM_OK;
+}
+
+int vm_text_embed(vm_ctx *ctx, const int32_t *ids, const float *tok, const float *pos, int vocab, int eot_id,
+                  float *x32, int32_t *pool_row, int32_t *flags, int B, int T, int H, hipStream_t st) {
+    const int rows = B * T, blocks = (rows + 3) / 4;
+    if (H % 256 != 0) return vm_fail(ctx, VM_ERR_UNSUPPORTED, "row width %d", H);
+    vm_prof_scope prof(ctx, VM_PROF_LAYERNORM, st);   // the embedding stage's category, as vm_embed's
+#define TEMB(V) text_embed_kernel<V><<<blocks, 256, 0, st>>>(ids, tok, pos, vocab, eot_id, x32, pool_row, flags, rows, T, H)
+    VM_VPL_SWITCH(H, TEMB)
+#undef TEMB
     VM_LAUNCH_CHECK(ctx);
     return VM_OK;
 }
@@ -445,6 +508,27 @@ struct LayerW {
     float *ln1_g, *ln1_b, *qkv_b, *proj_b, *ln2_g, *ln2_b, *fc1_b, *fc2_b;
     uint16_t *qkv_w, *proj_w, *fc1_w, *fc2_w;
 };
+// Byte sizes of one layer's 12 weights in header order (vm_encoder_create, vm_text_encoder_create) ...
+static void layer_sizes(size_t H, size_t M, size_t lsz[12]) {
+    const size_t v[12] = {H * 4, H * 4, 3 * H * H * 2, 3 * H * 4, H * H * 2, H * 4,
+                          H * 4, H * 4, M * H * 2,     M * 4,     H * M * 2, H * 4};
+    for (int i = 0; i < 12; ++i) lsz[i] = v[i];
+}
+// ... and the layer's pointers into a weight blob at those offsets
+static void bind_layer(LayerW &w, char *b, const size_t o[12]) {
+    w.ln1_g = (float *)(b + o[0]);
+    w.ln1_b = (float *)(b + o[1]);
+    w.qkv_w = (uint16_t *)(b + o[2]);
+    w.qkv_b = (float *)(b + o[3]);
+    w.proj_w = (uint16_t *)(b + o[4]);
+    w.proj_b = (float *)(b + o[5]);
+    w.ln2_g = (float *)(b + o[6]);
+    w.ln2_b = (float *)(b + o[7]);
+    w.fc1_w = (uint16_t *)(b + o[8]);
+    w.fc1_b = (float *)(b + o[9]);
+    w.fc2_w = (uint16_t *)(b + o[10]);
+    w.fc2_b = (float *)(b + o[11]);
+}
 struct vm_encoder {
     vm_ctx *ctx;
     vm_encoder_desc d;
@@ -525,8 +609,8 @@ extern "C" int vm_encoder_create(vm_ctx *ctx, const vm_encoder_desc *desc, const
         size_t o[12];
     };
     LO *lo = new LO[d.layers];
-    const size_t lsz[12] = {H * 4, H * 4, 3 * H * H * 2, 3 * H * 4, H * H * 2, H * 4,
-                            H * 4, H * 4, M * H * 2,     M * 4,     H * M * 2, H * 4};
+    size_t lsz[12];
+    layer_sizes(H, M, lsz);
     for (int l = 0; l < d.layers; ++l)
         for (int i = 0; i < 12; ++i) lo[l].o[i] = take(lsz[i]);
     hipError_t er = hipMalloc((void **)&e->blob, total);
@@ -552,20 +636,7 @@ extern "C" int vm_encoder_create(vm_ctx *ctx, const vm_encoder_desc *desc, const
     e->layers = new LayerW[d.layers];
     for (int l = 0; l < d.layers && er == hipSuccess; ++l) {
         for (int i = 0; i < 12 && er == hipSuccess; ++i) er = copy(lo[l].o[i], wp[9 + 12 * l + i], lsz[i]);
-        LayerW &w = e->layers[l];
-        char *b = e->blob;
-        w.ln1_g = (float *)(b + lo[l].o[0]);
-        w.ln1_b = (float *)(b + lo[l].o[1]);
-        w.qkv_w = (uint16_t *)(b + lo[l].o[2]);
-        w.qkv_b = (float *)(b + lo[l].o[3]);
-        w.proj_w = (uint16_t *)(b + lo[l].o[4]);
-        w.proj_b = (float *)(b + lo[l].o[5]);
-        w.ln2_g = (float *)(b + lo[l].o[6]);
-        w.ln2_b = (float *)(b + lo[l].o[7]);
-        w.fc1_w = (uint16_t *)(b + lo[l].o[8]);
-        w.fc1_b = (float *)(b + lo[l].o[9]);
-        w.fc2_w = (uint16_t *)(b + lo[l].o[10]);
-        w.fc2_b = (float *)(b + lo[l].o[11]);
+        bind_layer(e->layers[l], e->blob, lo[l].o);
     }
     delete[] lo;
     if (er != hipSuccess) {
@@ -667,8 +738,7 @@ struct Ws {
     uint16_t *a16, *d16, *e16, *qkv16, *mlp16;   // LN out / attention ctx, projection out (+ patch rows), FC2 out, QKV, MLP hidden
     size_t bytes;
 };
-static Ws carve(const vm_encoder *e, int mb, void *base) {
-    const size_t rows = (size_t)mb * e->tokens, H = e->d.hidden, M = e->d.mlp;
+static Ws carve_rows(size_t rows, size_t H, size_t M, void *base) {
     Ws w;
     size_t off = 0;
     auto take = [&](size_t bytes) {
@@ -685,6 +755,103 @@ static Ws carve(const vm_encoder *e, int mb, void *base) {
     w.bytes = off;
     return w;
 }
+static Ws carve(const vm_encoder *e, int mb, void *base) {
+    return carve_rows((size_t)mb * e->tokens, e->d.hidden, e->d.mlp, base);
+}
+
+// ---- the per-layer stages of a pre-LN tower, shared by vm_encode (vision) and vm_text_encode (text) ----
+// One pass = nb sequences of T rows in one workspace.  pend_proj / pend_fc2: the previous layer's branch outputs, not
+// yet folded into x32 (the next LN1 or the pool folds them).
+struct Pass {
+    int b0, nb, rows;
+    Ws ws;
+    const uint16_t *pend_proj, *pend_fc2;
+};
+struct Tower {
+    vm_ctx *ctx;
+    int dt, H, heads, mlp, act_epi, layers, T;
+    float eps;
+    const LayerW *lw;
+    int cls_env;     // VM_ENC_OPT_LAST_LAYER bits (0 = every row of the last layer)
+    bool dual;       // two-stream schedule: low-register LayerNorms
+    int causal;      // text tower: causal attention
+    hipStream_t st;  // the stream the stages launch on
+    bool cls_only() const { return (cls_env & 1) != 0; }
+    int gemm16(const uint16_t *X, int ldx, const uint16_t *W, const float *bias, uint16_t *out, int M, int N, int K,
+               int epi, int cat, int ldo = 0, int head_major = 0, int hm_rows = 0, int hm_stride = 0) const {
+        GemmArgs g;
+        memset(&g, 0, sizeof(g));
+        g.X = X; g.W = W; g.bias = bias; g.out16 = out;
+        g.M = M; g.N = N; g.K = K; g.ldx = ldx; g.ldo = ldo ? ldo : N; g.prof_cat = cat; g.head_major = head_major;
+        g.hm_rows = hm_rows; g.hm_stride = hm_stride;
+        return vm_gemm(ctx, dt, g, epi, st);
+    }
+    int ln1(Pass &p, int l) const {
+        // x32 += proj(l-1) + fc2(l-1), written back once; a16 = LN1(x32)
+        // (last layer: only the CLS rows' folded sums are read again - by LN2 and the pool - so only they are written)
+        const LayerW &w = lw[l];
+        const int fold = p.pend_proj == nullptr ? 0 : (l == layers - 1 && cls_only() && T > 1 ? T : 1);
+        return vm_resid_layernorm(ctx, dt, p.ws.x32, p.pend_proj, p.pend_fc2, fold, w.ln1_g, w.ln1_b, eps, p.ws.a16,
+                                  p.rows, H, st, 1, dual ? 1 : 0);
+    }
+    int attn_block(Pass &p, int l) const {   // QKV, attention, projection
+        const LayerW &w = lw[l];
+        const Ws &ws = p.ws;
+        const int rows = p.rows, nb = p.nb;
+        const bool last_cls = l == layers - 1 && cls_only();
+        int r;
+        // head_major: q/k/v of one head as contiguous [rows, 64] blocks: attention streams whole KiB
+        if (last_cls && (cls_env & 2)) {
+            // last layer: keys and values of every row, but only the CLS rows' queries (see below): the K / V
+            // weight rows [H, 3H) write the k and v blocks, then a GEMM over the nb CLS rows (row stride T) writes
+            // each head's query into row b*T of its q block
+            r = gemm16(ws.a16, H, w.qkv_w + (size_t)H * H, w.qkv_b + H, ws.qkv16 + (size_t)heads * rows * 64, rows,
+                       2 * H, H, EPI_STORE16, VM_PROF_GEMM_QKV, 0, 1);
+            if (r == VM_OK)
+                r = gemm16(ws.a16, T * H, w.qkv_w, w.qkv_b, ws.qkv16, nb, H, H, EPI_STORE16, VM_PROF_GEMM_CLS, 0, 1, rows, T);
+        } else {
+            r = gemm16(ws.a16, H, w.qkv_w, w.qkv_b, ws.qkv16, rows, 3 * H, H, EPI_STORE16, VM_PROF_GEMM_QKV, 0, 1);
+        }
+        if (r != VM_OK) return r;
+        if ((r = vm_attention(ctx, dt, ws.qkv16, ws.a16, nb, T, heads, st, last_cls && (cls_env & 2) ? 1 : 0,
+                              causal)) != VM_OK)
+            return r;
+        if (last_cls) {
+            // LAST layer: the embedding is pooled from the CLS row alone (vm_pool), and behind the attention every
+            // row depends only on itself - so projection, LN2, FC1 and FC2 run on the nb CLS rows, addressed in
+            // place with a row stride of T rows (GEMM ldx / ldo, LN rstride).  The other rows' branch outputs were
+            // never read by anything; the CLS rows get the same values bit for bit (every GEMM tiling accumulates
+            // an output in the same MFMA order).  6.2 % of ViT-B/16's FLOPs, 3.5 % of CLIP-L/14-336's.
+            const int TH = T * H;
+            return gemm16(ws.a16, TH, w.proj_w, w.proj_b, ws.d16, nb, H, H, EPI_DELTA16, VM_PROF_GEMM_CLS, TH);
+        }
+        return gemm16(ws.a16, H, w.proj_w, w.proj_b, ws.d16, rows, H, H, EPI_DELTA16, VM_PROF_GEMM_RESID);
+    }
+    int ln2(Pass &p, int l) const {
+        // a16 = LN2(x32 + proj(l)); x32 itself is NOT rewritten here: the next LN1 (or the pool) folds both
+        const LayerW &w = lw[l];
+        const bool last_cls = l == layers - 1 && cls_only();
+        return vm_resid_layernorm(ctx, dt, p.ws.x32, p.ws.d16, nullptr, 0, w.ln2_g, w.ln2_b, eps, p.ws.a16,
+                                  last_cls ? p.nb : p.rows, H, st, last_cls ? T : 1, dual && !last_cls ? 1 : 0);
+    }
+    int mlp_block(Pass &p, int l) const {   // FC1 (+activation), FC2
+        const LayerW &w = lw[l];
+        const Ws &ws = p.ws;
+        const bool last_cls = l == layers - 1 && cls_only();
+        int r;
+        if (last_cls) {
+            const int TH = T * H;
+            if ((r = gemm16(ws.a16, TH, w.fc1_w, w.fc1_b, ws.mlp16, p.nb, mlp, H, act_epi, VM_PROF_GEMM_CLS)) != VM_OK) return r;
+            r = gemm16(ws.mlp16, mlp, w.fc2_w, w.fc2_b, ws.e16, p.nb, H, mlp, EPI_DELTA16, VM_PROF_GEMM_CLS, TH);
+        } else {
+            if ((r = gemm16(ws.a16, H, w.fc1_w, w.fc1_b, ws.mlp16, p.rows, mlp, H, act_epi, VM_PROF_GEMM_ACT)) != VM_OK) return r;
+            r = gemm16(ws.mlp16, mlp, w.fc2_w, w.fc2_b, ws.e16, p.rows, H, mlp, EPI_DELTA16, VM_PROF_GEMM_RESID);
+        }
+        p.pend_proj = ws.d16;
+        p.pend_fc2 = ws.e16;
+        return r;
+    }
+};
 
 extern "C" size_t vm_encode_workspace_bytes(const vm_encoder *e, int B) {
     if (!e || B <= 0) return 0;
@@ -714,7 +881,6 @@ extern "C" int vm_encode(vm_encoder *e, const void *patches, int B, void *out_em
     // VM_ENC_OPT_LAST_LAYER: bit 0 = projection / LN2 / MLP of the last layer on the CLS rows only, bit 1 = also only
     // the CLS rows' queries and query tile in its attention; 0 = everything on every row (same embeddings, tests)
     const int cls_env = e->cls_last;
-    const bool cls_only = (cls_env & 1) != 0;
 
     // Two-stream schedule (VM_ENC_OPT_SCHEDULE; the default for calls of two or more passes).  Consecutive micro-batch
     // passes of a call alternate between two internal streams (fork behind the caller's stream, join before returning;
@@ -727,11 +893,6 @@ extern "C" int vm_encode(vm_encoder *e, const void *patches, int B, void *out_em
     // by more than the LayerNorm time they cover.  With two streams a kernel's HIP-event (and rocprofv3) duration
     // includes the time it waits for the other stream's GEMM to leave the CUs, so VM_SCHED_AUTO falls back to ONE
     // stream while per-kernel timing is enabled on the context (vm_profile_enable > 0): same embeddings, clean timings.
-    struct Pass {
-        int b0, nb, rows;
-        Ws ws;
-        const uint16_t *pend_proj, *pend_fc2;   // branch outputs not yet folded into x32 (previous layer's)
-    };
     const bool timing = ctx->prof_ev != nullptr;
     const bool dual = B > mb && workspace_bytes >= 2 * ws0.bytes &&
                       (e->schedule == VM_SCHED_TWO_STREAMS || (e->schedule == VM_SCHED_AUTO && !timing));
@@ -742,93 +903,17 @@ extern "C" int vm_encode(vm_encoder *e, const void *patches, int B, void *out_em
         VM_HIP(ctx, hipEventRecord(e->ev_fork, st0));
         for (int i = 0; i < 2; ++i) VM_HIP(ctx, hipStreamWaitEvent(e->side[i], e->ev_fork, 0));
     }
-    GemmArgs g;
-    int g_head_major = 0, g_hm_rows = 0, g_hm_stride = 0;
-    auto gemm16 = [&](const uint16_t *X, int ldx, const uint16_t *W, const float *bias, uint16_t *out, int M, int N,
-                      int K, int epi, int cat, int ldo = 0) {
-        memset(&g, 0, sizeof(g));
-        g.X = X; g.W = W; g.bias = bias; g.out16 = out;
-        g.M = M; g.N = N; g.K = K; g.ldx = ldx; g.ldo = ldo ? ldo : N; g.prof_cat = cat; g.head_major = g_head_major;
-        g.hm_rows = g_hm_rows; g.hm_stride = g_hm_stride;
-        return vm_gemm(ctx, dt, g, epi, st);
-    };
-    // ---- the stages of one pass ----
+    Tower tw;
+    tw.ctx = ctx; tw.dt = dt; tw.H = H; tw.heads = d.heads; tw.mlp = d.mlp; tw.act_epi = act_epi; tw.layers = d.layers;
+    tw.T = T; tw.eps = d.ln_eps; tw.lw = e->layers; tw.cls_env = cls_env; tw.dual = dual; tw.causal = 0; tw.st = st;
+    // ---- the stages of one pass (the layer stages are Tower's) ----
     auto embed = [&](Pass &p) -> int {
         // patch embedding: [nb*P, patch_k] x [H, patch_k]^T (+bias) -> 16-bit rows; then x32 = rows + pos (+cls) [+pre-LN]
-        int r = gemm16((const uint16_t *)patches + (size_t)p.b0 * P * e->patch_k, e->patch_k, e->patch_w, e->patch_b,
-                       p.ws.d16, p.nb * P, H, e->patch_k, EPI_DELTA16, VM_PROF_GEMM_PATCH);
+        int r = tw.gemm16((const uint16_t *)patches + (size_t)p.b0 * P * e->patch_k, e->patch_k, e->patch_w, e->patch_b,
+                          p.ws.d16, p.nb * P, H, e->patch_k, EPI_DELTA16, VM_PROF_GEMM_PATCH);
         if (r != VM_OK) return r;
         p.pend_proj = p.pend_fc2 = nullptr;
         return vm_embed(ctx, dt, p.ws.d16, e->cls, e->pos, e->pre_g, e->pre_b, d.ln_eps, d.pre_ln, p.ws.x32, p.nb, T, H, st);
-    };
-    auto ln1 = [&](Pass &p, int l) -> int {
-        // x32 += proj(l-1) + fc2(l-1), written back once; a16 = LN1(x32)
-        // (last layer: only the CLS rows' folded sums are read again - by LN2 and the pool - so only they are written)
-        const LayerW &w = e->layers[l];
-        const int fold = p.pend_proj == nullptr ? 0 : (l == d.layers - 1 && cls_only && T > 1 ? T : 1);
-        return vm_resid_layernorm(ctx, dt, p.ws.x32, p.pend_proj, p.pend_fc2, fold, w.ln1_g, w.ln1_b, d.ln_eps, p.ws.a16,
-                                  p.rows, H, st, 1, dual ? 1 : 0);
-    };
-    auto attn_block = [&](Pass &p, int l) -> int {   // QKV, attention, projection
-        const LayerW &w = e->layers[l];
-        const Ws &ws = p.ws;
-        const int rows = p.rows, nb = p.nb;
-        const bool last_cls = l == d.layers - 1 && cls_only;
-        int r;
-        g_head_major = 1;  // q/k/v of one head as contiguous [rows, 64] blocks: attention streams whole KiB
-        if (last_cls && (cls_env & 2)) {
-            // last layer: keys and values of every row, but only the CLS rows' queries (see below): the K / V
-            // weight rows [H, 3H) write the k and v blocks, then a GEMM over the nb CLS rows (row stride T) writes
-            // each head's query into row b*T of its q block
-            r = gemm16(ws.a16, H, w.qkv_w + (size_t)H * H, w.qkv_b + H, ws.qkv16 + (size_t)d.heads * rows * 64, rows,
-                       2 * H, H, EPI_STORE16, VM_PROF_GEMM_QKV);
-            if (r == VM_OK) {
-                g_hm_rows = rows;
-                g_hm_stride = T;
-                r = gemm16(ws.a16, T * H, w.qkv_w, w.qkv_b, ws.qkv16, nb, H, H, EPI_STORE16, VM_PROF_GEMM_CLS);
-                g_hm_rows = g_hm_stride = 0;
-            }
-        } else {
-            r = gemm16(ws.a16, H, w.qkv_w, w.qkv_b, ws.qkv16, rows, 3 * H, H, EPI_STORE16, VM_PROF_GEMM_QKV);
-        }
-        g_head_major = 0;
-        if (r != VM_OK) return r;
-        if ((r = vm_attention(ctx, dt, ws.qkv16, ws.a16, nb, T, d.heads, st, last_cls && (cls_env & 2) ? 1 : 0)) != VM_OK)
-            return r;
-        if (last_cls) {
-            // LAST layer: the embedding is pooled from the CLS row alone (vm_pool), and behind the attention every
-            // row depends only on itself - so projection, LN2, FC1 and FC2 run on the nb CLS rows, addressed in
-            // place with a row stride of T rows (GEMM ldx / ldo, LN rstride).  The other rows' branch outputs were
-            // never read by anything; the CLS rows get the same values bit for bit (every GEMM tiling accumulates
-            // an output in the same MFMA order).  6.2 % of ViT-B/16's FLOPs, 3.5 % of CLIP-L/14-336's.
-            const int TH = T * H;
-            return gemm16(ws.a16, TH, w.proj_w, w.proj_b, ws.d16, nb, H, H, EPI_DELTA16, VM_PROF_GEMM_CLS, TH);
-        }
-        return gemm16(ws.a16, H, w.proj_w, w.proj_b, ws.d16, rows, H, H, EPI_DELTA16, VM_PROF_GEMM_RESID);
-    };
-    auto ln2 = [&](Pass &p, int l) -> int {
-        // a16 = LN2(x32 + proj(l)); x32 itself is NOT rewritten here: the next LN1 (or the pool) folds both
-        const LayerW &w = e->layers[l];
-        const bool last_cls = l == d.layers - 1 && cls_only;
-        return vm_resid_layernorm(ctx, dt, p.ws.x32, p.ws.d16, nullptr, 0, w.ln2_g, w.ln2_b, d.ln_eps, p.ws.a16,
-                                  last_cls ? p.nb : p.rows, H, st, last_cls ? T : 1, dual && !last_cls ? 1 : 0);
-    };
-    auto mlp_block = [&](Pass &p, int l) -> int {   // FC1 (+activation), FC2
-        const LayerW &w = e->layers[l];
-        const Ws &ws = p.ws;
-        const bool last_cls = l == d.layers - 1 && cls_only;
-        int r;
-        if (last_cls) {
-            const int TH = T * H;
-            if ((r = gemm16(ws.a16, TH, w.fc1_w, w.fc1_b, ws.mlp16, p.nb, d.mlp, H, act_epi, VM_PROF_GEMM_CLS)) != VM_OK) return r;
-            r = gemm16(ws.mlp16, d.mlp, w.fc2_w, w.fc2_b, ws.e16, p.nb, H, d.mlp, EPI_DELTA16, VM_PROF_GEMM_CLS, TH);
-        } else {
-            if ((r = gemm16(ws.a16, H, w.fc1_w, w.fc1_b, ws.mlp16, p.rows, d.mlp, H, act_epi, VM_PROF_GEMM_ACT)) != VM_OK) return r;
-            r = gemm16(ws.mlp16, d.mlp, w.fc2_w, w.fc2_b, ws.e16, p.rows, H, d.mlp, EPI_DELTA16, VM_PROF_GEMM_RESID);
-        }
-        p.pend_proj = ws.d16;
-        p.pend_fc2 = ws.e16;
-        return r;
     };
     auto pool = [&](Pass &p) -> int {
         uint16_t *dst = (uint16_t *)out_emb + (size_t)p.b0 * e->out_dim;
@@ -844,7 +929,7 @@ extern "C" int vm_encode(vm_encoder *e, const void *patches, int B, void *out_em
             A.nb = B - b0 < mb ? B - b0 : mb;
             A.rows = A.nb * T;
             A.ws = dual && (pass & 1) ? ws1 : ws0;
-            st = dual ? e->side[pass & 1] : st0;    // the stage lambdas launch on `st`
+            st = tw.st = dual ? e->side[pass & 1] : st0;    // the stages launch on `st`
             // developer experiment (VIDMEM_ENC_PHASE = n, measured null: DESIGN.md 4.6): the second stream starts behind
             // the n-th stage of the first pass's first layer instead of together with it
             static const int phase_env = (int)VM_DEV_ENV("ENC_PHASE", 0);
@@ -852,13 +937,13 @@ extern "C" int vm_encode(vm_encoder *e, const void *patches, int B, void *out_em
             if (dual && phase_env > 0 && pass == 1) (void)hipStreamWaitEvent(st, e->ev_phase, 0);
             VM_TRY(embed(A));
             for (int l = 0; l < d.layers; ++l) {
-                VM_TRY(ln1(A, l));
+                VM_TRY(tw.ln1(A, l));
                 if (mark && l == 0 && phase_env == 1) (void)hipEventRecord(e->ev_phase, st);
-                VM_TRY(attn_block(A, l));
+                VM_TRY(tw.attn_block(A, l));
                 if (mark && l == 0 && phase_env == 2) (void)hipEventRecord(e->ev_phase, st);
-                VM_TRY(ln2(A, l));
+                VM_TRY(tw.ln2(A, l));
                 if (mark && l == 0 && phase_env == 3) (void)hipEventRecord(e->ev_phase, st);
-                VM_TRY(mlp_block(A, l));
+                VM_TRY(tw.mlp_block(A, l));
                 if (mark && l == 0 && phase_env == 4) (void)hipEventRecord(e->ev_phase, st);
                 if (mark && l == 1 && phase_env == 5) (void)hipEventRecord(e->ev_phase, st);   // a layer and a half... (after layer 1's MLP)
             }
@@ -879,5 +964,150 @@ extern "C" int vm_encode(vm_encoder *e, const void *patches, int B, void *out_em
                 rc = vm_fail(ctx, VM_ERR_HIP, "vm_encode: joining the internal streams failed: %s", hipGetErrorString(he));
         }
     }
+    return rc;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// text tower (CLIP's text transformer): token + position embedding -> the same pre-LN layers with causal attention ->
+// final LayerNorm of each sequence's EOT row -> projection -> [L2] -> 16 bit.  One pass, one stream, every row of
+// every layer (the pooled row moves with the EOT, so the last layer's CLS-only trick does not apply).
+// ---------------------------------------------------------------------------------------------------------
+struct vm_text_encoder {
+    vm_ctx *ctx;
+    vm_text_encoder_desc d;
+    int out_dim;
+    char *blob;  // one device allocation holding every weight
+    float *tok, *pos, *ln_g, *ln_b;
+    uint16_t *proj_w;
+    LayerW *layers;
+};
+
+extern "C" int vm_text_encoder_create(vm_ctx *ctx, const vm_text_encoder_desc *desc, const void *const *wp, int n_weights,
+                                      vm_text_encoder **out) {
+    if (!ctx || !desc || !wp || !out) return VM_ERR_INVALID;
+    const vm_text_encoder_desc &d = *desc;
+    if (d.hidden % 256 != 0 || d.hidden > 1024 || d.heads * 64 != d.hidden)
+        return vm_fail(ctx, VM_ERR_UNSUPPORTED, "text hidden=%d heads=%d: need hidden %% 256 == 0, <= 1024, head dim 64",
+                       d.hidden, d.heads);
+    if (d.mlp % 128 != 0 || d.layers <= 0 || d.vocab <= 0 || d.context < 1 || d.context > 80)
+        return vm_fail(ctx, VM_ERR_UNSUPPORTED, "text tower: bad mlp/layers/vocab or context %d (1..80)", d.context);
+    if (d.dtype != VM_F16 && d.dtype != VM_BF16) return vm_fail(ctx, VM_ERR_INVALID, "bad dtype");
+    if (d.act != VM_ACT_GELU && d.act != VM_ACT_QUICK_GELU) return vm_fail(ctx, VM_ERR_INVALID, "bad act %d", d.act);
+    if (d.proj_dim < 0 || d.proj_dim % 8 != 0) return vm_fail(ctx, VM_ERR_UNSUPPORTED, "proj_dim %d", d.proj_dim);
+    if (n_weights != 5 + 12 * d.layers)
+        return vm_fail(ctx, VM_ERR_INVALID, "expected %d weight pointers, got %d", 5 + 12 * d.layers, n_weights);
+    VM_HIP(ctx, hipSetDevice(ctx->device));
+    vm_text_encoder *e = new vm_text_encoder();
+    memset(e, 0, sizeof(*e));
+    e->ctx = ctx;
+    e->d = d;
+    e->out_dim = d.proj_dim ? d.proj_dim : d.hidden;
+    const size_t H = d.hidden, M = d.mlp;
+    size_t total = 0;
+    auto take = [&](size_t bytes) {
+        size_t off = total;
+        total += vm_align_up(bytes, 256);
+        return off;
+    };
+    const size_t head_sz[5] = {(size_t)d.vocab * H * 4, (size_t)d.context * H * 4, H * 4, H * 4,
+                               (size_t)d.proj_dim * H * 2};
+    size_t head_off[5];
+    for (int i = 0; i < 5; ++i) head_off[i] = take(head_sz[i]);
+    size_t lsz[12];
+    layer_sizes(H, M, lsz);
+    struct LO {
+        size_t o[12];
+    };
+    LO *lo = new LO[d.layers];
+    for (int l = 0; l < d.layers; ++l)
+        for (int i = 0; i < 12; ++i) lo[l].o[i] = take(lsz[i]);
+    hipError_t er = hipMalloc((void **)&e->blob, total);
+    if (er != hipSuccess) {
+        delete[] lo;
+        delete e;
+        return vm_fail(ctx, VM_ERR_NOMEM, "text encoder weights: hipMalloc(%zu) failed", total);
+    }
+    auto copy = [&](size_t off, const void *src, size_t bytes) -> hipError_t {
+        if (bytes == 0) return hipSuccess;
+        if (!src) return hipErrorInvalidValue;
+        return hipMemcpy(e->blob + off, src, bytes, hipMemcpyDeviceToDevice);
+    };
+    for (int i = 0; i < 5 && er == hipSuccess; ++i) er = copy(head_off[i], wp[i], head_sz[i]);
+    e->layers = new LayerW[d.layers];
+    for (int l = 0; l < d.layers && er == hipSuccess; ++l) {
+        for (int i = 0; i < 12 && er == hipSuccess; ++i) er = copy(lo[l].o[i], wp[5 + 12 * l + i], lsz[i]);
+        bind_layer(e->layers[l], e->blob, lo[l].o);
+    }
+    delete[] lo;
+    if (er != hipSuccess) {
+        vm_text_encoder_destroy(e);
+        return vm_fail(ctx, VM_ERR_HIP, "text encoder weight copy failed: %s (null or short weight pointer?)",
+                       hipGetErrorString(er));
+    }
+    char *b = e->blob;
+    e->tok = (float *)(b + head_off[0]);
+    e->pos = (float *)(b + head_off[1]);
+    e->ln_g = (float *)(b + head_off[2]);
+    e->ln_b = (float *)(b + head_off[3]);
+    e->proj_w = d.proj_dim ? (uint16_t *)(b + head_off[4]) : nullptr;
+    *out = e;
+    return VM_OK;
+}
+
+extern "C" void vm_text_encoder_destroy(vm_text_encoder *e) {
+    if (!e) return;
+    if (e->blob) (void)hipFree(e->blob);
+    delete[] e->layers;
+    delete e;
+}
+
+extern "C" int vm_text_encoder_out_dim(const vm_text_encoder *e) { return e ? e->out_dim : 0; }
+
+// workspace: the layer stack's buffers for B*T rows, then the pooled row index per sequence (int32 [B])
+static size_t text_ws_layers(const vm_text_encoder *e, int B, int T) {
+    return carve_rows((size_t)B * T, e->d.hidden, e->d.mlp, nullptr).bytes;
+}
+
+extern "C" size_t vm_text_encode_workspace_bytes(const vm_text_encoder *e, int B, int T) {
+    if (!e || B <= 0 || T <= 0 || T > e->d.context) return 0;
+    return text_ws_layers(e, B, T) + vm_align_up((size_t)B * 4, 256);
+}
+
+extern "C" int vm_text_encode(vm_text_encoder *e, const int32_t *token_ids, int B, int T, void *out_emb,
+                              int l2_normalise, int32_t *out_flags, void *workspace, size_t workspace_bytes,
+                              void *stream) {
+    if (!e) return VM_ERR_INVALID;
+    vm_ctx *ctx = e->ctx;
+    const vm_text_encoder_desc &d = e->d;
+    if (!token_ids || !out_emb || B <= 0 || T < 1 || T > d.context)
+        return vm_fail(ctx, VM_ERR_INVALID, "vm_text_encode: bad arguments (B=%d, T=%d, context %d)", B, T, d.context);
+    const size_t need = vm_text_encode_workspace_bytes(e, B, T);
+    if (!workspace || workspace_bytes < need)
+        return vm_fail(ctx, VM_ERR_NOMEM, "vm_text_encode: workspace %zu < %zu", workspace_bytes, need);
+    if (((uintptr_t)workspace & 255) || ((uintptr_t)token_ids & 3) || ((uintptr_t)out_emb & 15))
+        return vm_fail(ctx, VM_ERR_INVALID, "vm_text_encode: workspace must be 256-byte, ids 4-byte, output 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    Pass p;
+    p.b0 = 0;
+    p.nb = B;
+    p.rows = B * T;
+    p.ws = carve_rows((size_t)p.rows, d.hidden, d.mlp, workspace);
+    p.pend_proj = p.pend_fc2 = nullptr;
+    int32_t *pool_row = (int32_t *)((char *)workspace + text_ws_layers(e, B, T));
+    Tower tw;
+    tw.ctx = ctx; tw.dt = d.dtype; tw.H = d.hidden; tw.heads = d.heads; tw.mlp = d.mlp;
+    tw.act_epi = d.act == VM_ACT_QUICK_GELU ? EPI_QGELU16 : EPI_GELU16; tw.layers = d.layers; tw.T = T;
+    tw.eps = d.ln_eps; tw.lw = e->layers; tw.cls_env = 0; tw.dual = false; tw.causal = 1; tw.st = st;
+    int rc = vm_text_embed(ctx, token_ids, e->tok, e->pos, d.vocab, d.eot_id, p.ws.x32, pool_row, out_flags, B, T,
+                           d.hidden, st);
+    for (int l = 0; l < d.layers && rc == VM_OK; ++l) {
+        if (rc == VM_OK) rc = tw.ln1(p, l);
+        if (rc == VM_OK) rc = tw.attn_block(p, l);
+        if (rc == VM_OK) rc = tw.ln2(p, l);
+        if (rc == VM_OK) rc = tw.mlp_block(p, l);
+    }
+    if (rc == VM_OK)
+        rc = vm_pool(ctx, d.dtype, p.ws.x32, p.pend_proj, p.pend_fc2, e->ln_g, e->ln_b, d.ln_eps, e->proj_w, d.proj_dim,
+                     l2_normalise, (uint16_t *)out_emb, B, T, d.hidden, st, pool_row);
     return rc;
 }

@@ -42,8 +42,9 @@ int vm_gemm(vm_ctx *ctx, int dtype, const GemmArgs &g, int epi, hipStream_t st);
 // ctx [B*T, H] 16-bit row-major; head dim 64.
 // q_rows > 0: only the first q_rows query rows of every frame are needed (rounded up to 16-row tiles; the other rows
 // of ctx_out are left untouched)
+// causal = 1: key j > query row i is masked (the text tower); T <= 80, always the same 5-tile build
 int vm_attention(vm_ctx *ctx, int dtype, const uint16_t *qkv, uint16_t *ctx_out, int B, int T, int heads,
-                 hipStream_t st, int q_rows = 0);
+                 hipStream_t st, int q_rows = 0, int causal = 0);
 
 // v = (x32[row] + delta16[row]) + deltaB16[row] (fp16 whatever `dtype`: EPI_DELTA16; either may be null);
 // x32[row] = v when write_x == 1, or when write_x = n > 1 and row % n == 0; out16[row] = LayerNorm(v) * gamma + beta
@@ -55,6 +56,11 @@ int vm_resid_layernorm(vm_ctx *ctx, int dtype, float *x32, const uint16_t *delta
 int vm_embed(vm_ctx *ctx, int dtype, const uint16_t *patch16, const float *cls, const float *pos, const float *pre_g,
              const float *pre_b, float eps, int pre_ln, float *x32, int B, int T, int H, hipStream_t st);
 // CLS row ((x32 + delta16) + deltaB16) -> final LayerNorm, optional projection, optional L2 normalisation, cast
+// pool_row (device int32 [B], may be null = row 0): the row of each sequence that is pooled (the text tower's EOT row)
 int vm_pool(vm_ctx *ctx, int dtype, const float *x, const uint16_t *delta16, const uint16_t *deltaB16,
             const float *gamma, const float *beta, float eps, const uint16_t *proj_w, int proj_dim, int l2, uint16_t *out,
-            int B, int T, int H, hipStream_t st);
+            int B, int T, int H, hipStream_t st, const int32_t *pool_row = nullptr);
+// x32[b*T + t] = tok[clamp(ids[b*T + t], 0, vocab-1)] + pos[t] (fp32); per sequence pool_row[b] = first t with
+// ids == eot_id, else 0; flags[b] (may be null) = bit 0: an id was clamped, bit 1: no EOT
+int vm_text_embed(vm_ctx *ctx, const int32_t *ids, const float *tok, const float *pos, int vocab, int eot_id,
+                  float *x32, int32_t *pool_row, int32_t *flags, int B, int T, int H, hipStream_t st);

@@ -117,14 +117,41 @@ def build_encoder(enc_cfg) -> FrameEncoder:
     from . import specs, synthetic
     spec = specs.SPECS[enc_cfg.arch]
     if enc_cfg.weights:
-        z = np.load(enc_cfg.weights, allow_pickle=False)
-        weights = {k: z[k] for k in z.files}
+        if str(enc_cfg.weights).endswith(".safetensors"):
+            from .text import load_weight_file   # a CLIPModel checkpoint (clip_l14_336_joint) or named arrays
+            weights = load_weight_file(str(enc_cfg.weights), "vision")
+        else:
+            z = np.load(enc_cfg.weights, allow_pickle=False)
+            weights = {k: z[k] for k in z.files}
         missing = set(synthetic.encoder_weight_shapes(spec)) - set(weights)
         if missing:
             raise ValueError(f"{enc_cfg.weights}: missing weight arrays {sorted(missing)[:4]}...")
     else:
         weights = synthetic.encoder_weights(spec, seed=int(enc_cfg.seed))
     return FrameEncoder(spec, weights, dtype=enc_cfg.dtype, device=int(enc_cfg.device))
+
+
+def build_text_embedder(config: Any, tokenizer=None):
+    """``config.text_encoder`` -> text.HipTextEmbedder, or None when its ``arch`` is null (the default: nothing is
+    built).  ``tokenizer``: a callable ``str -> list[int]``; default: text.clip_tokenizer(text_encoder.tokenizer)."""
+    from . import specs, synthetic
+    from .text import HipTextEmbedder, TextEncoder, clip_tokenizer, load_weight_file
+    tcfg = cfgmod.section(config, "text_encoder", cfgmod.TEXT_ENCODER_DEFAULTS)
+    if not tcfg.arch:
+        return None
+    spec = specs.TEXT_SPECS[tcfg.arch]
+    if tcfg.weights:
+        weights = load_weight_file(str(tcfg.weights), "text")
+        missing = set(synthetic.text_encoder_weight_shapes(spec)) - set(weights)
+        if missing:
+            raise ValueError(f"{tcfg.weights}: missing text weight arrays {sorted(missing)[:4]}...")
+    else:
+        weights = synthetic.text_encoder_weights(spec, seed=int(tcfg.seed))
+    if tokenizer is None:
+        if not tcfg.tokenizer:
+            raise ValueError("text_encoder.tokenizer: a directory with CLIP's vocab.json and merges.txt is required")
+        tokenizer = clip_tokenizer(str(tcfg.tokenizer))
+    return HipTextEmbedder(TextEncoder(spec, weights, dtype=tcfg.dtype, device=int(tcfg.device)), tokenizer)
 
 
 def build_memory(mem_cfg, encoder: FrameEncoder) -> EmbeddingMemory:

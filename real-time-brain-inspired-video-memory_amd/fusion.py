@@ -52,10 +52,12 @@ class HipHybridMixin:
 
     _hip: Optional[HipVectorSearch] = None
 
-    def attach_memory(self, memory, *, score_mode: int, min_score: float = 0.3, splitter=None):
-        """``score_mode`` is required: see similarity.HipVectorSearch (Neo4j's score mapping is unpinned)."""
-        self._hip = HipVectorSearch(memory, self.embedder, self.config, min_score=min_score, score_mode=score_mode,
-                                    splitter=splitter)
+    def attach_memory(self, memory, *, score_mode: int, min_score: float = 0.3, splitter=None, embedder=None):
+        """``score_mode`` is required: see similarity.HipVectorSearch (Neo4j's score mapping is unpinned).
+        ``embedder``: what embeds the questions (e.g. text.HipTextEmbedder); None = ``self.embedder``.  ValueError when
+        it states an ``out_dim`` other than ``memory.dim``."""
+        self._hip = HipVectorSearch(memory, self.embedder if embedder is None else embedder, self.config,
+                                    min_score=min_score, score_mode=score_mode, splitter=splitter)
         return self
 
     async def _vector_search_chunks(self, session, query):

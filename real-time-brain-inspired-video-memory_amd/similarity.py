@@ -125,6 +125,12 @@ class HipVectorSearch:
         ``_lib.VM_SCORE_UNIT_INTERVAL``; ``min_score`` (default: the reference's literal) is compared AFTER the mapping."""
         if score_mode not in (_lib.VM_SCORE_RAW, _lib.VM_SCORE_UNIT_INTERVAL):
             raise ValueError("score_mode must be VM_SCORE_RAW or VM_SCORE_UNIT_INTERVAL")
+        # an embedder that states its width (HipTextEmbedder, FrameEncoder-backed ones) must match the memory's rows: a
+        # text tower against a memory built without the joint projection (clip_l14_336: 1024-d) is a wiring error
+        out_dim = getattr(embedder, "out_dim", None)
+        if out_dim is not None and int(out_dim) != int(memory.dim):
+            raise ValueError(f"embedder out_dim {out_dim} != memory.dim {memory.dim}: build the memory with the matching "
+                             "image encoder (text questions: encoder.arch clip_l14_336_joint)")
         self.memory, self.embedder, self.config = memory, embedder, config
         self.min_score, self.score_mode, self.splitter = min_score, score_mode, splitter
 

@@ -14,7 +14,27 @@ CLIP_L14_336 = dict(
     ln_eps=1e-5, pre_ln=True, patch_bias=False, proj_dim=0,
     mean=(0.48145466, 0.4578275, 0.40821073), std=(0.26862954, 0.26130258, 0.27577711),
 )
-SPECS = {"vit_b16_224": VIT_B16_224, "clip_l14_336": CLIP_L14_336}
+# CLIP-L/14-336 with its visual projection: the 768-d image embedding of CLIP's joint text-image space, the one a
+# CLIP_L14_TEXT question embedding is compared with (clip_l14_336 stores the 1024-d post-LayerNorm CLS row instead)
+CLIP_L14_336_JOINT = dict(CLIP_L14_336, arch="clip_l14_336_joint", proj_dim=768)
+SPECS = {"vit_b16_224": VIT_B16_224, "clip_l14_336": CLIP_L14_336, "clip_l14_336_joint": CLIP_L14_336_JOINT}
+
+# CLIP's text transformer (the ViT-L/14 family's): causal pre-LN layers, pooled at the first EOT token, text_projection
+# into the joint space (csrc/encoder.hip vm_text_encode; text.TextEncoder)
+CLIP_L14_TEXT = dict(
+    arch="clip_l14_text", vocab=49408, context=77, hidden=768, layers=12, heads=12, mlp=3072, act="quick_gelu",
+    ln_eps=1e-5, proj_dim=768, eot_id=49407,
+)
+TEXT_SPECS = {"clip_l14_text": CLIP_L14_TEXT}
+
+
+def text_flops_per_sequence(spec, T: int = None) -> float:
+    """Algorithmic FLOPs of one sequence of T tokens (default: the context) through the text tower, every row of every
+    layer as vm_text_encode runs them (2 * MACs of the GEMMs, full QK^T / PV, the pooled row's projection)."""
+    H, L, M = spec["hidden"], spec["layers"], spec["mlp"]
+    n = spec["context"] if T is None else T
+    per_layer = 2 * n * H * 3 * H + 2 * 2 * n * n * H + 2 * n * H * H + 2 * 2 * n * H * M
+    return float(L * per_layer + 2 * H * spec.get("proj_dim", 0))
 
 # algorithmic FLOPs per frame (2 * MACs of the GEMMs and of QK^T / PV; SURVEY.md §8d).
 # executed=True: what vm_encode actually runs - the LAST layer's projection and MLP only on the CLS row, the one row the

@@ -67,6 +67,32 @@ def encoder_weights(spec: Dict, seed: int = 42, std: float = 0.02, tail: str = "
     return out
 
 
+def text_encoder_weight_shapes(spec: Dict) -> Dict[str, tuple]:
+    """Named arrays of a text tower (specs.TEXT_SPECS) in vm_text_encoder_create's order: tok_emb, pos, ln_g, ln_b,
+    proj_w (when proj_dim), then the vision encoder's 12 per-layer names."""
+    H, M = spec["hidden"], spec["mlp"]
+    shapes = {"tok_emb": (spec["vocab"], H), "pos": (spec["context"], H), "ln_g": (H,), "ln_b": (H,)}
+    if spec.get("proj_dim", 0):
+        shapes["proj_w"] = (spec["proj_dim"], H)
+    for l in range(spec["layers"]):
+        shapes.update({
+            f"l{l}.ln1_g": (H,), f"l{l}.ln1_b": (H,),
+            f"l{l}.qkv_w": (3 * H, H), f"l{l}.qkv_b": (3 * H,),
+            f"l{l}.proj_w": (H, H), f"l{l}.proj_b": (H,),
+            f"l{l}.ln2_g": (H,), f"l{l}.ln2_b": (H,),
+            f"l{l}.fc1_w": (M, H), f"l{l}.fc1_b": (M,),
+            f"l{l}.fc2_w": (H, M), f"l{l}.fc2_b": (H,),
+        })
+    return shapes
+
+
+def text_encoder_weights(spec: Dict, seed: int = 42, std: float = 0.02) -> Dict[str, np.ndarray]:
+    """fp32 master weights of a text tower, seeded like encoder_weights: everything ~ N(0, std^2), LayerNorm
+    gamma = 1 + N(0, std^2)."""
+    return {name: normal(seed, "text." + name, shape, std=std, mean=1.0 if name.endswith("_g") else 0.0)
+            for name, shape in text_encoder_weight_shapes(spec).items()}
+
+
 def frames_u8(seed: int, n: int, height: int, width: int) -> np.ndarray:
     """uint8 [n, H, W, 3] BGR frames, i.i.d. uniform 0..255 (what cv2.VideoCapture.read hands over,
     reference src/pipeline/vlm_extractor.py:110-117)."""
