@@ -188,6 +188,22 @@ int vm_memory_reset(vm_memory *mem, void *stream);
 int64_t vm_memory_sync(vm_memory *mem, void *stream);
 const void *vm_memory_rows(const vm_memory *mem); /* device pointer to the [capacity, D] row store          */
 
+/* ---- grouped memory -------------------------------------------------------------------------------------
+ * A grouped memory carries an int64 GROUP KEY per row.  A GROUP is a maximal run of consecutive row ids with equal keys
+ * (a key that comes back after other keys opens a new group): the frames of one video chunk, appended together
+ * (src/pipeline/vlm_extractor.py:44-74 stores one row per frame; ids {run}_{chunk}_{i}).  In a ring, a group whose
+ * oldest rows were overwritten is made of its surviving rows, also when it straddles the physical wrap.
+ * vm_memory_create_grouped allocates the key column (and a group-ordinal column) beside the rows.
+ * vm_memory_append_grouped: keys = device int64 [B]; the first row continues the group of the previous call when that
+ *   call was also grouped and ended with the same key.  Capturable like vm_memory_append (no allocation, no sync).
+ * vm_memory_append on a grouped memory makes every row its own group (key = -1 - row id; the next grouped call opens a
+ *   new group); it then runs one launch more than on a plain memory.  vm_memory_reset forgets the open group.
+ * vm_memory_group_keys: device pointer to the [capacity] key column (slot order, like vm_memory_rows), 0 if not grouped. */
+int vm_memory_create_grouped(vm_ctx *ctx, int64_t capacity_rows, int D, int dtype, int ring, vm_memory **out);
+int vm_memory_append_grouped(vm_memory *mem, const void *rows, int B, const int64_t *keys, int64_t *out_first_row_host,
+                             void *stream);
+const int64_t *vm_memory_group_keys(const vm_memory *mem);
+
 /* ---- cosine top-k over the memory ---------------------------------------------------------------------
  * Replaces PreLLMInjector._calculate_batch_similarities + _cosine_similarity
  * (src/components/pre_llm_injector.py:346-388) and the Cypher scan of HybridRetriever._vector_search_chunks
@@ -230,6 +246,28 @@ int vm_topk_cosine_exact(vm_memory *mem, const void *queries, int Q, int k, int 
                          double min_score, int score_mode, int64_t row_stride, int64_t row_offset,
                          double *out_scores, int64_t *out_rows, void *workspace, size_t workspace_bytes,
                          void *stream);
+/* Grouped top-k: the k best GROUPS of a grouped memory.  Take the exhaustive row ranking of vm_topk_cosine (score_mode
+ * mapping, > min_score filter, score descending, row id ascending), keep the first row of each group, return the first
+ * k.  Equivalently: a group's score is the exact max over its rows, its representative the lowest row id reaching it,
+ * groups ordered by (score desc, representative asc).  out_scores [Q,k] are the reference's fp64 values bit for bit,
+ * out_rows [Q,k] the representatives, out_keys [Q,k] int64 (may be NULL) their group keys; -1 / 0.0 / -1 padded.
+ * ALWAYS the exhaustive answer: an fp32 MFMA scan reduces scores to per-group fp32 maxima, the best k + slack groups are
+ * re-scored exactly, and a query whose result cannot be proven (vm_topk_cosine's bound 2 (D + 8) 2^-24 against the
+ * best rejected group's fp32 max, or more than 4096 candidate rows) is counted in *out_uncertified (may be NULL),
+ * marked in out_query_flags [Q] (vm_topk_flag; may be NULL) and redone exhaustively on the device inside the same call.
+ * Every row of a candidate group is re-scored, so groups of a few hundred rows or more (k = 10: an average above ~220)
+ * always take that exhaustive redo: exact, but at the cost of an exhaustive search.
+ * No host read-back, no allocation: capturable.  1 <= k <= 64, Q >= 1; VM_ERR_INVALID on a memory that is not grouped.
+ * Workspace: vm_topk_grouped_workspace_bytes (4 x Q x capacity bytes of per-group maxima plus a few MB). */
+size_t vm_topk_grouped_workspace_bytes(const vm_memory *mem, int Q, int k);
+int vm_topk_cosine_grouped(vm_memory *mem, const void *queries, int Q, int k, int use_min_score, double min_score,
+                           int score_mode, double *out_scores, int64_t *out_rows, int64_t *out_keys,
+                           int32_t *out_uncertified, int32_t *out_query_flags, void *workspace, size_t workspace_bytes,
+                           void *stream);
+/* The same contract, exhaustive only: every row scored exactly for every query (slow; tests, and a checker). */
+int vm_topk_cosine_grouped_exact(vm_memory *mem, const void *queries, int Q, int k, int use_min_score,
+                                 double min_score, int score_mode, double *out_scores, int64_t *out_rows,
+                                 int64_t *out_keys, void *workspace, size_t workspace_bytes, void *stream);
 /* All-pairs exact cosine, out [Q, S] fp64: the post-compression filter of
  * src/pipeline/retriever_hybrid.py:494-504 (query vs segment embeddings) and a checker for the scan.
  * rows [S, D] dtype need not live in a vm_memory.  dtype VM_F32 takes fp32 operands: an embedder that returns fp32

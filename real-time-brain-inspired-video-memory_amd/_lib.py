@@ -35,6 +35,8 @@ SYMBOLS = [
     "vm_encode_workspace_bytes", "vm_encode_micro_batch", "vm_encode",
     "vm_memory_create", "vm_memory_destroy", "vm_memory_append", "vm_memory_size", "vm_memory_capacity",
     "vm_memory_dim", "vm_memory_reset", "vm_memory_sync", "vm_memory_rows",
+    "vm_memory_create_grouped", "vm_memory_append_grouped", "vm_memory_group_keys",
+    "vm_topk_grouped_workspace_bytes", "vm_topk_cosine_grouped", "vm_topk_cosine_grouped_exact",
     "vm_topk_workspace_bytes", "vm_topk_cosine", "vm_topk_redo_workspace_bytes", "vm_topk_redo_flagged",
     "vm_topk_exact_workspace_bytes", "vm_topk_cosine_exact",
     "vm_cosine_exact", "vm_topk_select", "vm_topk_merge", "vm_profile_enable", "vm_profile_read", "vm_profile_mask", "vm_probe_mfma",
@@ -114,6 +116,12 @@ def lib() -> C.CDLL:
         "vm_memory_reset": (i32, [vp, vp]),
         "vm_memory_sync": (i64, [vp, vp]),
         "vm_memory_rows": (vp, [vp]),
+        "vm_memory_create_grouped": (i32, [vp, i64, i32, i32, i32, C.POINTER(vp)]),
+        "vm_memory_append_grouped": (i32, [vp, vp, i32, vp, C.POINTER(i64), vp]),
+        "vm_memory_group_keys": (vp, [vp]),
+        "vm_topk_grouped_workspace_bytes": (sz, [vp, i32, i32]),
+        "vm_topk_cosine_grouped": (i32, [vp, vp, i32, i32, i32, f64, i32, vp, vp, vp, vp, vp, vp, sz, vp]),
+        "vm_topk_cosine_grouped_exact": (i32, [vp, vp, i32, i32, i32, f64, i32, vp, vp, vp, vp, sz, vp]),
         "vm_topk_workspace_bytes": (sz, [vp, i32, i32]),
         "vm_topk_cosine": (i32, [vp, vp, i32, i32, i32, f64, i32, i64, i64, vp, vp, vp, vp, vp, sz, vp]),
         "vm_topk_redo_workspace_bytes": (sz, [vp, i32, i32]),

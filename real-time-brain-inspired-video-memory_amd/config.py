@@ -38,6 +38,7 @@ MEMORY_DEFAULTS: Dict[str, Any] = {
     "ring": False,           # True: rolling window, oldest rows overwritten
     "dtype": None,           # None = the encoder's dtype
     "snapshot": None,        # path of an EmbeddingMemory.snapshot to restore from / save to
+    "group_by": None,        # "chunk": a grouped memory (one group per video chunk) for distinct-chunk search; None = plain
 }
 TEXT_ENCODER_DEFAULTS: Dict[str, Any] = {
     "arch": None,            # specs.TEXT_SPECS key (clip_l14_text); None = no text encoder is built

@@ -42,6 +42,59 @@ __global__ void __launch_bounds__(128) memory_append_kernel(const uint16_t *__re
 
 __global__ void memory_bump_kernel(int64_t *d_total, int B) { *d_total += B; }
 
+// Grouped memories: key and group ordinal of every appended row (one block, launched between the row copy and the bump
+// so that it sees the same device row count).  A row opens a new group when its key differs from the previous row's -
+// for the first row of the call: from the last key of the previous call, unless that call was a plain append or there
+// was none (VM_GSTATE_OPEN == 0).  keys == null (plain append): every row is its own group, key = -1 - row id.
+// Ordinal of a row = groups opened before it minus one, from an inclusive block scan of the "opens" flags.
+__global__ void __launch_bounds__(256) memory_group_kernel(const int64_t *__restrict__ keys, int B, int64_t *__restrict__ gkey,
+                                                           int64_t *__restrict__ gord, int64_t *__restrict__ state,
+                                                           int64_t cap, int ring) {
+    __shared__ int scan[256];
+    const int tid = threadIdx.x;
+    const int64_t total = state[0];
+    int64_t groups = state[VM_GSTATE_GROUPS];
+    const int64_t last_key = state[VM_GSTATE_LAST_KEY];
+    const bool open = state[VM_GSTATE_OPEN] != 0;
+    for (int c0 = 0; c0 < B; c0 += 256) {
+        const int i = c0 + tid;
+        int64_t kv = 0;
+        int flag = 0;
+        if (i < B) {
+            kv = keys ? keys[i] : -1 - (total + i);
+            if (!keys)
+                flag = 1;
+            else if (i == 0)
+                flag = !(open && kv == last_key);
+            else
+                flag = keys[i - 1] != kv;
+        }
+        scan[tid] = flag;
+        __syncthreads();
+        for (int off = 1; off < 256; off <<= 1) {
+            const int v = tid >= off ? scan[tid - off] : 0;
+            __syncthreads();
+            scan[tid] += v;
+            __syncthreads();
+        }
+        if (i < B) {
+            const int64_t id = total + i;
+            const int64_t slot = ring ? id % cap : id;
+            if (slot < cap) {
+                gkey[slot] = kv;
+                gord[slot] = groups + scan[tid] - 1;
+            }
+        }
+        groups += scan[255];
+        __syncthreads();
+    }
+    if (tid == 0) {
+        state[VM_GSTATE_GROUPS] = groups;
+        state[VM_GSTATE_LAST_KEY] = keys ? keys[B - 1] : 0;
+        state[VM_GSTATE_OPEN] = keys ? 1 : 0;
+    }
+}
+
 extern "C" int vm_memory_create(vm_ctx *ctx, int64_t capacity_rows, int D, int dtype, int ring,
                                 vm_memory **out) {
     if (!ctx || !out) return VM_ERR_INVALID;
@@ -82,12 +135,32 @@ extern "C" void vm_memory_destroy(vm_memory *m) {
     if (m->norm64) (void)hipFree(m->norm64);
     if (m->rnorm32) (void)hipFree(m->rnorm32);
     if (m->d_total) (void)hipFree(m->d_total);
+    if (m->gkey) (void)hipFree(m->gkey);
+    if (m->gord) (void)hipFree(m->gord);
     delete m;
 }
 
-extern "C" int vm_memory_append(vm_memory *m, const void *rows, int B, int64_t *out_first_row_host,
-                                void *stream) {
-    if (!m) return VM_ERR_INVALID;
+extern "C" int vm_memory_create_grouped(vm_ctx *ctx, int64_t capacity_rows, int D, int dtype, int ring,
+                                        vm_memory **out) {
+    vm_memory *m = nullptr;
+    const int rc = vm_memory_create(ctx, capacity_rows, D, dtype, ring, &m);
+    if (rc != VM_OK) return rc;
+    const int64_t cap_pad = (capacity_rows + 63) / 64 * 64;
+    hipError_t e = hipMalloc((void **)&m->gkey, (size_t)cap_pad * 8);
+    if (e == hipSuccess) e = hipMalloc((void **)&m->gord, (size_t)cap_pad * 8);
+    if (e == hipSuccess) e = hipMemset(m->gkey, 0, (size_t)cap_pad * 8);
+    if (e == hipSuccess) e = hipMemset(m->gord, 0, (size_t)cap_pad * 8);
+    if (e != hipSuccess) {
+        vm_memory_destroy(m);
+        return vm_fail(ctx, VM_ERR_NOMEM, "group columns of a %lld-row memory: %s", (long long)capacity_rows,
+                       hipGetErrorString(e));
+    }
+    *out = m;
+    return VM_OK;
+}
+
+static int memory_append(vm_memory *m, const void *rows, int B, const int64_t *keys, int64_t *out_first_row_host,
+                         void *stream) {
     vm_ctx *ctx = m->ctx;
     if (B < 0 || (B > 0 && !rows)) return vm_fail(ctx, VM_ERR_INVALID, "vm_memory_append: bad arguments");
     if (out_first_row_host) *out_first_row_host = m->h_total;
@@ -105,11 +178,30 @@ extern "C" int vm_memory_append(vm_memory *m, const void *rows, int B, int64_t *
         memory_append_kernel<VM_BF16><<<B, 128, 0, st>>>((const uint16_t *)rows, B, m->D, m->rows, m->norm64,
                                                         m->rnorm32, m->d_total, m->cap, m->ring);
     VM_LAUNCH_CHECK(ctx);
+    if (m->gkey) {  // grouped memories only: a plain memory runs exactly the two launches above and below
+        memory_group_kernel<<<1, 256, 0, st>>>(keys, B, m->gkey, m->gord, m->d_total, m->cap, m->ring);
+        VM_LAUNCH_CHECK(ctx);
+    }
     memory_bump_kernel<<<1, 1, 0, st>>>(m->d_total, B);
     VM_LAUNCH_CHECK(ctx);
     m->h_total += B;
     return VM_OK;
 }
+
+extern "C" int vm_memory_append(vm_memory *m, const void *rows, int B, int64_t *out_first_row_host, void *stream) {
+    if (!m) return VM_ERR_INVALID;
+    return memory_append(m, rows, B, nullptr, out_first_row_host, stream);
+}
+
+extern "C" int vm_memory_append_grouped(vm_memory *m, const void *rows, int B, const int64_t *keys,
+                                        int64_t *out_first_row_host, void *stream) {
+    if (!m) return VM_ERR_INVALID;
+    if (!m->gkey) return vm_fail(m->ctx, VM_ERR_INVALID, "vm_memory_append_grouped: the memory is not grouped");
+    if (B > 0 && !keys) return vm_fail(m->ctx, VM_ERR_INVALID, "vm_memory_append_grouped: keys is null");
+    return memory_append(m, rows, B, keys, out_first_row_host, stream);
+}
+
+extern "C" const int64_t *vm_memory_group_keys(const vm_memory *m) { return m ? m->gkey : nullptr; }
 
 extern "C" int64_t vm_memory_size(const vm_memory *m) { return m ? m->h_total : 0; }
 extern "C" int64_t vm_memory_capacity(const vm_memory *m) { return m ? m->cap : 0; }

@@ -1,0 +1,1065 @@
+// Grouped cosine top-k: the k best GROUPS (video chunks) of a grouped memory, one hit per group (include/vidmem.h).
+//
+// The row ranking is vm_topk_cosine's (src/components/pre_llm_injector.py:346-388, retriever_hybrid.py:293-306); a
+// group's score is the exact max over its rows and its representative the lowest row id reaching that max.  Same
+// two-stage, certified design as topk.hip:
+//   table    : first age order of every live group (groups are runs of equal ordinals, memory.hip) + clears the maxima
+//   scan     : fp32 MFMA scores with the list scan's numerics (the same instruction over the same operand layout, then
+//              x 1/||row||), folded into per-(query, group) fp32 maxima with one atomic max per run of a 16-row tile
+//   select   : per query, the best M + 1 groups by (fp32 max desc, group asc): a cut from a sample of the maxima, a
+//              parallel compaction of every group at or above it, a block-wide selection (radix over all maxima if too many)
+//   finalize : every row of the best M groups re-scored exactly in fp64 (one rounding per product and per partial sum,
+//              left to right; norm64), exact group max + representative, ordered, k kept.  Certified when the exact
+//              k-th group score clears the (M+1)-th group's fp32 max / ||q|| by topk.hip's bound 2 (D + 8) 2^-24
+//   redo     : flagged queries (gap or candidate-row overflow) scored exhaustively, group-aligned row slices per
+//              block, segmented max in LDS, stable top-k per slice, merge.  Reads flags and counts on the device.
+// Every launch reads the row count from the device and sizes its grid from the capacity: capturable.
+#include "vm_internal.h"
+
+#include <climits>
+
+namespace {
+
+constexpr int GS_THREADS = 256;   // scan
+constexpr int SEL_THREADS = 1024; // select: cut and final sort (one block per query)
+constexpr int SEL_SAMPLE = 2048;  // groups whose fp32 maxima give each query's cut
+constexpr int SEL_CAP = 4096;     // groups at or above the cut a query keeps; more -> the full radix select
+constexpr int CMP_THREADS = 256;  // select: compaction
+constexpr int CMP_LCAP = 1024;    // hits one compaction block gathers in LDS
+constexpr int GF_THREADS = 512;   // finalize
+constexpr int GCMAX = 128;        // candidate groups per query kept by the select (M + 1 <= GCMAX)
+constexpr int GROWCAP = 4096;     // rows the finalize re-scores per query; more -> VM_FLAG_OVERFLOW, exhaustive redo
+constexpr int GR_THREADS = 256;   // redo
+constexpr int GR_CHUNK = 1024;    // rows scored per selection pass of the redo
+constexpr int GKMAX = 64;
+
+// order-preserving unsigned images (bigger key = bigger value; -0 folded into +0; 0 is below every image)
+__device__ __forceinline__ uint32_t okey32(float s) {
+    uint32_t u = __float_as_uint(s);
+    if (s == 0.f) u = 0;
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float dekey32(uint32_t k) {
+    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+__device__ __forceinline__ unsigned long long okey64(double d) {
+    unsigned long long u = (unsigned long long)__double_as_longlong(d);
+    if (d == 0.0) u = 0;
+    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
+__device__ __forceinline__ double dekey64(unsigned long long k) {
+    return __longlong_as_double((long long)((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k));
+}
+
+// live rows + the ordinal of the oldest live group + the number of live groups, from the device counters
+struct GView {
+    RingView rv;
+    int64_t ord0, ng;
+};
+__device__ __forceinline__ int64_t slot_of(const RingView &rv, int64_t o) {
+    const int64_t p = o + rv.head;
+    return p >= rv.cap ? p - rv.cap : p;
+}
+__device__ __forceinline__ GView group_view(const int64_t *d_total, int64_t cap, int ring, const int64_t *gord) {
+    GView g;
+    g.rv = ring_view(*d_total, cap, ring);
+    g.ord0 = 0;
+    g.ng = 0;
+    if (g.rv.n > 0) {
+        g.ord0 = gord[g.rv.head];
+        g.ng = gord[slot_of(g.rv, g.rv.n - 1)] - g.ord0 + 1;
+    }
+    return g;
+}
+
+// the exact reference cosine of the query staged in LDS (ql) and the row in slot p, strictly left to right
+template <int DT>
+__device__ __forceinline__ double exact_score(const uint16_t *ql, double qn, const uint16_t *__restrict__ mem,
+                                              const double *__restrict__ norm64, int64_t p, int D) {
+    using E = vm_elem<DT>;
+    const uint16_t *mv = mem + (size_t)p * D;
+    double dot = 0.0;
+    for (int i = 0; i < D; i += 32) {  // D is a multiple of 128; 4 row chunks in flight per step
+        uint4 b4[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) b4[u] = *reinterpret_cast<const uint4 *>(mv + i + 8 * u);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const uint4 a = *reinterpret_cast<const uint4 *>(ql + i + 8 * u);
+            const uint16_t *ae = reinterpret_cast<const uint16_t *>(&a);
+            const uint16_t *be = reinterpret_cast<const uint16_t *>(&b4[u]);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) dot = __dadd_rn(dot, __dmul_rn(E::to_double(ae[j]), E::to_double(be[j])));
+        }
+    }
+    const double mn = norm64[p];  // the reference's norm of the stored row, computed at append
+    return (qn == 0.0 || mn == 0.0) ? 0.0 : __ddiv_rn(dot, __dmul_rn(qn, mn));
+}
+
+template <int DT>
+__device__ __forceinline__ double exact_qnorm(const uint16_t *ql, int D) {
+    using E = vm_elem<DT>;
+    double nq = 0.0;
+    for (int i = 0; i < D; i += 8) {  // 16-byte LDS reads; the sum itself strictly left to right
+        const uint4 a = *reinterpret_cast<const uint4 *>(ql + i);
+        const uint16_t *ae = reinterpret_cast<const uint16_t *>(&a);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const double x = E::to_double(ae[j]);
+            nq = __dadd_rn(nq, __dmul_rn(x, x));
+        }
+    }
+    return __dsqrt_rn(nq);
+}
+
+__device__ __forceinline__ double shown_score(double e, int score_mode) {
+    return score_mode == VM_SCORE_UNIT_INTERVAL ? __ddiv_rn(__dadd_rn(1.0, e), 2.0) : e;
+}
+
+// ---- table -------------------------------------------------------------------------------------------------
+// first_o[g] = age order of the first live row of live group g (g = ordinal - ord0), first_o[ng] = n; F[0, Q*ng) = 0;
+// fill_flags: flags[0, Q) = 1 (the exhaustive-only entry point).  Grid-stride, any grid.
+__global__ void __launch_bounds__(256)
+    group_table_kernel(const int64_t *__restrict__ d_total, int64_t cap, int ring, const int64_t *__restrict__ gord,
+                       int Q, int *__restrict__ first_o, uint32_t *__restrict__ F, int32_t *__restrict__ flags,
+                       int fill_flags) {
+    const GView gv = group_view(d_total, cap, ring, gord);
+    const int64_t n = gv.rv.n;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    const int64_t t0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    for (int64_t o = t0; o <= n; o += stride) {
+        if (o == n) {
+            first_o[gv.ng] = (int)n;
+        } else {
+            const int64_t g = gord[slot_of(gv.rv, o)] - gv.ord0;
+            if (o == 0 || gord[slot_of(gv.rv, o - 1)] - gv.ord0 != g) first_o[g] = (int)o;
+        }
+    }
+    if (F)
+        for (int64_t i = t0; i < (int64_t)Q * gv.ng; i += stride) F[i] = 0;
+    if (fill_flags)
+        for (int64_t i = t0; i < Q; i += stride) flags[i] = 1;
+}
+
+// ---- scan --------------------------------------------------------------------------------------------------
+// grid (row blocks, query groups of QT*16).  The MFMA part is topk_scan_kernel's (topk.hip): 16-row tiles in physical
+// order, the row tile the A operand straight from global memory, the query tile the B operand from chunk-swizzled LDS,
+// acc[t][j] = <row tile*16 + 4h + j, query q0 + 16t + r16>, score = acc * rnorm32.  Instead of a candidate list, each
+// lane folds its 4 consecutive rows into runs of one group and raises F[q][group] with one atomic max per run.
+template <int DT, int QT>
+__global__ void __launch_bounds__(GS_THREADS)
+    group_scan_kernel(const uint16_t *__restrict__ mem, const float *__restrict__ rnorm,
+                      const int64_t *__restrict__ gord, const uint16_t *__restrict__ queries,
+                      const int64_t *__restrict__ d_total, int64_t cap, int ring, int D, int Q,
+                      uint32_t *__restrict__ F) {
+    using E = vm_elem<DT>;
+    using vec8 = typename E::vec8;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    uint4 *qlds = reinterpret_cast<uint4 *>(smem);
+    const int chunks = D / 8;
+    constexpr int nw = GS_THREADS / 64;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int r16 = lane & 15, h = lane >> 4;
+    const int q0 = blockIdx.y * (QT * 16);
+    for (int idx = tid; idx < QT * 16 * chunks; idx += GS_THREADS) {
+        const int q = idx / chunks, ci = idx - q * chunks;
+        uint4 v = make_uint4(0, 0, 0, 0);
+        if (q0 + q < Q) v = reinterpret_cast<const uint4 *>(queries + (size_t)(q0 + q) * D)[ci];
+        qlds[q * chunks + ((ci & ~15) | ((ci ^ q) & 15))] = v;
+    }
+    __syncthreads();
+    const GView gv = group_view(d_total, cap, ring, gord);
+    const int64_t n = gv.rv.n;
+    const int64_t ntiles = (n + 15) / 16;
+    const int ksteps = D / 32;
+    constexpr int LB = 8;
+    const uint4 *qrow = qlds + r16 * chunks;
+    const int tstride = 16 * chunks;
+    const int64_t tile_step = (int64_t)gridDim.x * nw;
+    for (int64_t tile = (int64_t)blockIdx.x * nw + wave; tile < ntiles; tile += tile_step) {
+        int64_t row = tile * 16 + r16;
+        if (row > n - 1) row = n - 1;  // tail lanes re-read the last row; their scores are masked below
+        const uint4 *src = reinterpret_cast<const uint4 *>(mem + (size_t)row * D) + h;
+        f32x4 acc[QT];
+#pragma unroll
+        for (int t = 0; t < QT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int s0 = 0; s0 < ksteps; s0 += LB) {
+            uint4 cur[LB];
+#pragma unroll
+            for (int u = 0; u < LB; ++u) cur[u] = src[(s0 + u < ksteps ? s0 + u : ksteps - 1) * 4];
+#pragma unroll
+            for (int u = 0; u < LB; ++u) {
+                if (s0 + u < ksteps) {
+                    const int ci = h + 4 * (s0 + u);
+                    const vec8 av = __builtin_bit_cast(vec8, cur[u]);
+                    const uint4 *qp = qrow + ((ci & ~15) | ((ci ^ r16) & 15));
+#pragma unroll
+                    for (int t = 0; t < QT; ++t) acc[t] = E::mfma16(av, __builtin_bit_cast(vec8, qp[t * tstride]), acc[t]);
+                }
+            }
+        }
+        const int64_t p0 = tile * 16 + 4 * h;
+        const float4 rn = *reinterpret_cast<const float4 *>(rnorm + p0);  // allocation is padded to 64 rows
+        const float rnv[4] = {rn.x, rn.y, rn.z, rn.w};
+        int gj[4];  // live group index (< cap < 2^31), -1 past the live rows
+#pragma unroll
+        for (int j = 0; j < 4; ++j) gj[j] = p0 + j < n ? (int)(gord[p0 + j] - gv.ord0) : -1;
+        // physical slot p holds age order p - head (mod cap); the ordinal does not care: groups are runs of slots too,
+        // except across the physical wrap, where the two halves still carry one ordinal
+#pragma unroll
+        for (int t = 0; t < QT; ++t) {
+            const int q = q0 + 16 * t + r16;
+            uint32_t *Fq = F + (size_t)q * gv.ng;
+            // Runs of one group among this lane's 4 rows.  Interior runs go straight to their atomic.  The first and
+            // the last run may go on in the lanes that hold the rows before / after (lane -+ 16, same query), so one
+            // atomic per run of the whole 16-row tile: the lane where the run starts adds what the next lanes hold.
+            int gF = -1, gL = -1, closed = 0;
+            uint32_t bF = 0, bL = 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (gj[j] < 0) continue;
+                const uint32_t key = okey32(acc[t][j] * rnv[j]);
+                if (gj[j] != gL) {
+                    if (gL >= 0) {  // the run before closes
+                        if (closed == 0) {
+                            gF = gL;
+                            bF = bL;
+                        } else if (q < Q) {
+                            atomicMax(Fq + gL, bL);
+                        }
+                        ++closed;
+                    }
+                    gL = gj[j];
+                    bL = key;
+                } else {
+                    bL = key > bL ? key : bL;
+                }
+            }
+            const int single = closed == 0;  // one run (or none): it is the first and the last
+            if (single) {
+                gF = gL;
+                bF = bL;
+            }
+            // neighbours, fetched by every lane (the four lanes of a query are all live or all idle together)
+            const int gLp = __shfl(gL, (lane - 16) & 63, 64);
+            int gFn[3], sn[3];
+            uint32_t bFn[3];
+#pragma unroll
+            for (int d = 1; d <= 3; ++d) {
+                gFn[d - 1] = __shfl(gF, (lane + 16 * d) & 63, 64);
+                bFn[d - 1] = __shfl(bF, (lane + 16 * d) & 63, 64);
+                sn[d - 1] = __shfl(single, (lane + 16 * d) & 63, 64);
+            }
+            if (q >= Q) continue;
+            const bool cont_in = h > 0 && gF >= 0 && gLp == gF;  // the first run started in an earlier lane
+            if (!single && !cont_in) atomicMax(Fq + gF, bF);
+            if (gL >= 0 && !(single && cont_in)) {
+                uint32_t total = bL;
+#pragma unroll
+                for (int d = 1; d <= 3; ++d) {
+                    if (h + d > 3 || gFn[d - 1] != gL) break;
+                    total = bFn[d - 1] > total ? bFn[d - 1] : total;
+                    if (!sn[d - 1]) break;
+                }
+                atomicMax(Fq + gL, total);
+            }
+        }
+    }
+}
+
+// ---- select ------------------------------------------------------------------------------------------------
+// Per query, the best take = min(M + 1, ng) groups by (fp32 max desc, group asc), as 64-bit composites
+// key << 32 | ~group (bigger = better, unique).  cut: the take-th best composite of a strided sample of SEL_SAMPLE groups
+// (all of them when there are fewer) - at least take groups reach it; compact: every group at or above the cut, from
+// many blocks; final: the take-th largest key among those (ties by group), the take best kept.  A query with more than SEL_CAP groups at its cut runs
+// the exact radix select below over all its groups instead (slow, any input).
+__device__ __forceinline__ unsigned long long composite(uint32_t key, int g) {
+    return ((unsigned long long)key << 32) | (unsigned long long)(0xffffffffu - (uint32_t)g);
+}
+
+// largest T with at least `need` of the block's values >= T (PER values per thread, SEL_THREADS threads; every thread
+// calls it): a bitwise search, one block-wide count per bit
+template <int PER>
+__device__ __forceinline__ uint32_t block_kth_u32(const uint32_t (&v)[PER], int need) {
+    __shared__ int wsum[SEL_THREADS / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t T = 0;
+    for (int bit = 31; bit >= 0; --bit) {
+        const uint32_t c = T | (1u << bit);
+        int cnt = 0;
+#pragma unroll
+        for (int j = 0; j < PER; ++j) cnt += v[j] >= c ? 1 : 0;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
+        if (lane == 0) wsum[wave] = cnt;
+        __syncthreads();
+        int tot = 0;
+#pragma unroll
+        for (int w = 0; w < SEL_THREADS / 64; ++w) tot += wsum[w];
+        __syncthreads();
+        if (tot >= need) T = c;
+    }
+    return T;
+}
+
+// One block per query: cut = key T << 32, T = the take-th largest fp32-max key of a strided sample of SEL_SAMPLE groups
+// (all of them when there are fewer).  At least take groups have a key >= T (ties at T included, whatever their group).
+__global__ void __launch_bounds__(SEL_THREADS)
+    group_cut_kernel(const int64_t *__restrict__ d_total, int64_t cap, int ring, const int64_t *__restrict__ gord,
+                     const uint32_t *__restrict__ F, int M1, unsigned long long *__restrict__ cut,
+                     int *__restrict__ ccount) {
+    constexpr int PER = SEL_SAMPLE / SEL_THREADS;
+    const int q = blockIdx.x, lane = threadIdx.x;
+    const GView gv = group_view(d_total, cap, ring, gord);
+    const int64_t ng = gv.ng;
+    const uint32_t *Fq = F + (size_t)q * ng;
+    const int cnt = (int)(ng < SEL_SAMPLE ? ng : SEL_SAMPLE);
+    uint32_t v[PER];
+#pragma unroll
+    for (int j = 0; j < PER; ++j) {
+        const int i = j * SEL_THREADS + lane;
+        v[j] = i < cnt ? Fq[ng <= SEL_SAMPLE ? i : (int64_t)i * ng / SEL_SAMPLE] : 0u;
+    }
+    const int take = cnt < M1 ? cnt : M1;
+    const uint32_t T = take > 0 ? block_kth_u32<PER>(v, take) : 0xffffffffu;
+    if (lane == 0) {
+        cut[q] = (unsigned long long)T << 32;
+        ccount[q] = 0;
+    }
+}
+
+// grid (slices, Q): wave-aggregated appends of every composite >= cut[q] to the query's buffer
+__global__ void __launch_bounds__(CMP_THREADS)
+    group_compact_kernel(const int64_t *__restrict__ d_total, int64_t cap, int ring, const int64_t *__restrict__ gord,
+                         const uint32_t *__restrict__ F, const unsigned long long *__restrict__ cut,
+                         int *__restrict__ ccount, unsigned long long *__restrict__ cbuf) {
+    // hits gather in LDS first: one global atomic per block (one per wave with hits on a single counter per query
+    // serialised behind each other: 0.29 ms at Q = 16 over 200 k groups)
+    __shared__ unsigned long long lbuf[CMP_LCAP];
+    __shared__ int lcnt, gbase;
+    const int q = blockIdx.y, lane = threadIdx.x & 63;
+    const GView gv = group_view(d_total, cap, ring, gord);
+    const int64_t ng = gv.ng;
+    const uint32_t *Fq = F + (size_t)q * ng;
+    const unsigned long long c0 = cut[q];
+    const int64_t stride = (int64_t)gridDim.x * CMP_THREADS;
+    if (threadIdx.x == 0) lcnt = 0;
+    __syncthreads();
+    for (int64_t base = (int64_t)blockIdx.x * CMP_THREADS; base < ng; base += stride) {  // uniform per wave
+        const int64_t g = base + threadIdx.x;
+        unsigned long long c = 0;
+        if (g < ng) c = composite(Fq[g], (int)g);
+        const bool hit = g < ng && c >= c0;
+        const unsigned long long bal = __ballot(hit);
+        if (bal) {
+            int pos0 = 0;
+            if (lane == 0) pos0 = atomicAdd(&lcnt, __popcll(bal));
+            pos0 = __shfl(pos0, 0, 64);
+            const int pos = pos0 + __popcll(bal & ((1ull << lane) - 1ull));
+            if (hit && pos < CMP_LCAP) lbuf[pos] = c;
+        }
+    }
+    __syncthreads();
+    const int nb = lcnt;
+    if (threadIdx.x == 0) gbase = nb ? atomicAdd(&ccount[q], nb > CMP_LCAP ? SEL_CAP + 1 : nb) : 0;  // >: radix path
+    __syncthreads();
+    if (nb > CMP_LCAP) return;
+    for (int i = threadIdx.x; i < nb; i += CMP_THREADS) {
+        const int pos = gbase + i;
+        if (pos < SEL_CAP) cbuf[(size_t)q * SEL_CAP + pos] = lbuf[i];
+    }
+}
+
+// One block per query: the best `take` = min(M + 1, ng) groups by (fp32 max desc, group asc) over ALL groups.  Four
+// 8-bit radix passes find the take-th largest key T; then one ordered pass collects every key > T and the first needed
+// keys == T.  The overflow path of the select.
+__device__ void radix_select_all(const uint32_t *__restrict__ Fq, int ng, int take, int *__restrict__ og,
+                                 uint32_t *__restrict__ ok) {
+    __shared__ int hist[256];
+    __shared__ uint32_t prefix_sh;
+    __shared__ int need_sh, wcnt[SEL_THREADS / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    uint32_t prefix = 0, mask = 0;
+    int need = take;
+    for (int shift = 24; shift >= 0; shift -= 8) {
+        for (int b = tid; b < 256; b += SEL_THREADS) hist[b] = 0;
+        __syncthreads();
+        for (int i = tid; i < ng; i += SEL_THREADS) {
+            const uint32_t v = Fq[i];
+            if ((v & mask) == prefix) atomicAdd(&hist[(v >> shift) & 255], 1);
+        }
+        __syncthreads();
+        if (tid == 0) {
+            int above = 0;
+            for (int b = 255; b >= 0; --b) {
+                if (above + hist[b] >= need) {
+                    need_sh = need - above;
+                    prefix_sh = prefix | ((uint32_t)b << shift);
+                    break;
+                }
+                above += hist[b];
+            }
+        }
+        __syncthreads();
+        prefix = prefix_sh;
+        need = need_sh;
+        mask |= 255u << shift;
+    }
+    // keys > T go to [0, take - need) in any order, keys == T to [take - need, take) in group order
+    const uint32_t T = prefix;
+    const int n_gt = take - need;
+    __shared__ int gt_pos;
+    if (tid == 0) gt_pos = 0;
+    __syncthreads();
+    int eq_base = 0;
+    for (int c0 = 0; c0 < ng; c0 += SEL_THREADS) {
+        const int i = c0 + tid;
+        const uint32_t v = i < ng ? Fq[i] : 0;
+        const bool gt = i < ng && v > T, eq = i < ng && v == T;
+        if (gt) {
+            const int pos = atomicAdd(&gt_pos, 1);
+            og[pos] = i;
+            ok[pos] = v;
+        }
+        const unsigned long long bal = __ballot(eq);
+        if (lane == 0) wcnt[wave] = __popcll(bal);
+        __syncthreads();
+        int before = eq_base, total = 0;
+        for (int w = 0; w < SEL_THREADS / 64; ++w) {
+            if (w < wave) before += wcnt[w];
+            total += wcnt[w];
+        }
+        before += __popcll(bal & ((1ull << lane) - 1ull));
+        if (eq && before < need) {
+            og[n_gt + before] = i;
+            ok[n_gt + before] = v;
+        }
+        eq_base += total;
+        const bool done = eq_base >= need && gt_pos == n_gt;  // uniform: read after the barrier below
+        __syncthreads();
+        if (done) break;
+    }
+}
+
+__global__ void __launch_bounds__(SEL_THREADS)
+    group_select_final_kernel(const int64_t *__restrict__ d_total, int64_t cap, int ring,
+                              const int64_t *__restrict__ gord, const uint32_t *__restrict__ F, int M1,
+                              const int *__restrict__ ccount, const unsigned long long *__restrict__ cbuf,
+                              int *__restrict__ cand_g, uint32_t *__restrict__ cand_k, int *__restrict__ cand_n) {
+    const int q = blockIdx.x, tid = threadIdx.x;
+    const GView gv = group_view(d_total, cap, ring, gord);
+    const int ng = (int)gv.ng;
+    int *og = cand_g + (size_t)q * GCMAX;
+    uint32_t *ok = cand_k + (size_t)q * GCMAX;
+    const int take = ng < M1 ? ng : M1;
+    if (tid == 0) cand_n[q] = take;
+    const int cnt = ccount[q];
+    if (cnt > SEL_CAP) {
+        radix_select_all(F + (size_t)q * ng, ng, take, og, ok);
+        return;
+    }
+    // the take-th largest key of the compacted list, then ties at that key by group
+    constexpr int PER = SEL_CAP / SEL_THREADS;
+    __shared__ int red[2][SEL_THREADS / 64];
+    __shared__ int npos;
+    const int lane = tid & 63, wave = tid >> 6;
+    uint32_t hi[PER], lo[PER];
+#pragma unroll
+    for (int j = 0; j < PER; ++j) {
+        const int i = j * SEL_THREADS + tid;
+        const unsigned long long c = i < cnt ? cbuf[(size_t)q * SEL_CAP + i] : 0ull;
+        hi[j] = (uint32_t)(c >> 32);
+        lo[j] = (uint32_t)c;  // ~group: bigger = lower group
+    }
+    const uint32_t T = block_kth_u32<PER>(hi, take);
+    int above = 0, equal = 0;
+#pragma unroll
+    for (int j = 0; j < PER; ++j) {
+        above += hi[j] > T ? 1 : 0;
+        equal += hi[j] == T ? 1 : 0;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        above += __shfl_xor(above, off, 64);
+        equal += __shfl_xor(equal, off, 64);
+    }
+    if (lane == 0) {
+        red[0][wave] = above;
+        red[1][wave] = equal;
+    }
+    if (tid == 0) npos = 0;
+    __syncthreads();
+    above = equal = 0;
+#pragma unroll
+    for (int w = 0; w < SEL_THREADS / 64; ++w) {
+        above += red[0][w];
+        equal += red[1][w];
+    }
+    const int need_eq = take - above;
+    uint32_t lo_cut = 0;  // keep the need_eq lowest groups among the keys == T
+    if (need_eq < equal) {
+        uint32_t le[PER];
+#pragma unroll
+        for (int j = 0; j < PER; ++j) le[j] = hi[j] == T ? lo[j] : 0u;
+        lo_cut = block_kth_u32<PER>(le, need_eq);  // uniform branch: every thread sees the same counts
+    }
+#pragma unroll
+    for (int j = 0; j < PER; ++j) {  // exactly take entries are kept; their order does not matter (finalize ranks)
+        const bool keep = hi[j] > T || (hi[j] == T && lo[j] >= lo_cut && (j * SEL_THREADS + tid) < cnt);
+        if (keep) {
+            const int pos = atomicAdd(&npos, 1);
+            og[pos] = (int)(0xffffffffu - lo[j]);
+            ok[pos] = hi[j];
+        }
+    }
+}
+
+// ---- finalize ----------------------------------------------------------------------------------------------
+// One block per query.  Ranks the take candidates by (fp32 key desc, group asc): the first nc = min(take, M) are
+// re-scored, the (M+1)-th (if any) bounds every rejected group.  Every row of a candidate group is scored exactly
+// (a row whose fp32 score is more than 2 eps below its group's fp32 max can not be the max, but the rows of a
+// candidate group are few and scoring them all needs no per-row fp32 score), exact max and lowest row reaching it by
+// LDS atomics, then the k best by (score desc, representative asc).
+template <int DT>
+__global__ void __launch_bounds__(GF_THREADS)
+    group_finalize_kernel(const uint16_t *__restrict__ mem, const double *__restrict__ norm64,
+                          const int64_t *__restrict__ gkey, const int64_t *__restrict__ gord,
+                          const uint16_t *__restrict__ queries, const int64_t *__restrict__ d_total, int64_t cap,
+                          int ring, int D, const int *__restrict__ first_o, const int *__restrict__ cand_g,
+                          const uint32_t *__restrict__ cand_k, const int *__restrict__ cand_n, int M, int k, int use_min,
+                          double min_score, int score_mode, double *__restrict__ out_scores,
+                          int64_t *__restrict__ out_rows, int64_t *__restrict__ out_keys, int *__restrict__ uncertified,
+                          int *__restrict__ flags, int *__restrict__ user_flags) {
+    extern __shared__ __attribute__((aligned(16))) char gf_dyn[];
+    uint16_t *ql = reinterpret_cast<uint16_t *>(gf_dyn);  // [D]
+    __shared__ int sg[GCMAX], ca[GCMAX], cpre[GCMAX + 1], rk[GCMAX], lg[GCMAX];
+    __shared__ uint32_t sk[GCMAX], lk[GCMAX];
+    __shared__ unsigned long long gmax[GCMAX];
+    __shared__ long long grep[GCMAX];
+    __shared__ double es[GROWCAP];
+    __shared__ uint8_t ec[GROWCAP];
+    __shared__ double qn_sh;
+    __shared__ int flag_sh;
+    const int q = blockIdx.x, tid = threadIdx.x;
+    const GView gv = group_view(d_total, cap, ring, gord);
+    const int C = cand_n[q];
+    const int nc = C < M ? C : M;
+    for (int i = tid; i < D / 8; i += GF_THREADS)
+        reinterpret_cast<uint4 *>(ql)[i] = reinterpret_cast<const uint4 *>(queries + (size_t)q * D)[i];
+    if (tid < C) {
+        lg[tid] = cand_g[(size_t)q * GCMAX + tid];
+        lk[tid] = cand_k[(size_t)q * GCMAX + tid];
+    }
+    if (tid == 0) flag_sh = VM_FLAG_CERTIFIED;
+    __syncthreads();
+    if (tid < C) {  // rank by (fp32 key desc, group asc)
+        const int g = lg[tid];
+        const uint32_t key = lk[tid];
+        int r = 0;
+        for (int j = 0; j < C; ++j) r += (lk[j] > key || (lk[j] == key && lg[j] < g)) ? 1 : 0;
+        sg[r] = g;
+        sk[r] = key;
+    }
+    __syncthreads();
+    if (tid < nc) {
+        const int a = first_o[sg[tid]];
+        ca[tid] = a;
+        cpre[tid + 1] = first_o[sg[tid] + 1] - a;  // length for now
+        gmax[tid] = 0;
+        grep[tid] = LLONG_MAX;
+    }
+    if (tid == 64) qn_sh = exact_qnorm<DT>(ql, D);  // the second wave; the prefix sum below is the first's
+    __syncthreads();
+    if (tid == 0) {
+        cpre[0] = 0;
+        for (int c = 0; c < nc; ++c) cpre[c + 1] += cpre[c];
+    }
+    __syncthreads();
+    const int R = cpre[nc];
+    const double qn = qn_sh;
+    if (R > GROWCAP) {  // uniform: too many candidate rows -> the exhaustive redo answers this query
+        for (int i = tid; i < k; i += GF_THREADS) {
+            out_scores[(size_t)q * k + i] = 0.0;
+            out_rows[(size_t)q * k + i] = -1;
+            if (out_keys) out_keys[(size_t)q * k + i] = -1;
+        }
+        if (tid == 0) {
+            flags[q] = VM_FLAG_OVERFLOW;
+            if (user_flags) user_flags[q] = VM_FLAG_OVERFLOW;
+            if (uncertified) atomicAdd(uncertified, 1);
+        }
+        return;
+    }
+    for (int r = tid; r < R; r += GF_THREADS) {
+        int lo = 0, hi = nc - 1;  // the candidate c with cpre[c] <= r < cpre[c + 1]
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (cpre[mid] <= r) lo = mid;
+            else hi = mid - 1;
+        }
+        const int64_t o = ca[lo] + (r - cpre[lo]);
+        const double e = exact_score<DT>(ql, qn, mem, norm64, slot_of(gv.rv, o), D);
+        es[r] = e;
+        ec[r] = (uint8_t)lo;
+        atomicMax(&gmax[lo], okey64(e));
+    }
+    __syncthreads();
+    for (int r = tid; r < R; r += GF_THREADS) {
+        const int c = ec[r];
+        if (okey64(es[r]) == gmax[c]) atomicMin(&grep[c], (long long)(ca[c] + (r - cpre[c])));
+    }
+    __syncthreads();
+    if (tid < nc) {
+        const double e = dekey64(gmax[tid]);
+        const long long o = grep[tid];
+        int r = 0;
+        for (int d = 0; d < nc; ++d) {
+            const double e2 = dekey64(gmax[d]);
+            r += (e2 > e || (e2 == e && grep[d] < o)) ? 1 : 0;
+        }
+        rk[tid] = r;
+        if (r < k) {
+            const double shown = shown_score(e, score_mode);
+            const bool pass = !use_min || shown > min_score;
+            out_scores[(size_t)q * k + r] = pass ? shown : 0.0;
+            out_rows[(size_t)q * k + r] = pass ? gv.rv.base + o : -1;
+            if (out_keys) out_keys[(size_t)q * k + r] = pass ? gkey[slot_of(gv.rv, o)] : -1;
+        }
+        // certification: the exact k-th group score against the best fp32 max of a group that never became a candidate
+        const int kth = (k < nc ? k : nc) - 1;
+        if (r == kth && C > M && qn != 0.0) {
+            const double eps = 2.0 * (double)(D + 8) * 5.9604644775390625e-08;  // 2*(D+8)*2^-24, topk.hip
+            const double reject = (double)dekey32(sk[M]) / qn + eps;
+            if (!(e > reject)) flag_sh = VM_FLAG_GAP;
+        }
+    }
+    for (int i = nc + tid; i < k; i += GF_THREADS) {
+        out_scores[(size_t)q * k + i] = 0.0;
+        out_rows[(size_t)q * k + i] = -1;
+        if (out_keys) out_keys[(size_t)q * k + i] = -1;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        flags[q] = flag_sh;
+        if (user_flags) user_flags[q] = flag_sh;
+        if (flag_sh && uncertified) atomicAdd(uncertified, 1);
+    }
+}
+
+// ---- redo --------------------------------------------------------------------------------------------------
+// k rounds of block-wide arg-best over n (score, order) candidates read through `get`, strictly after the previous
+// winner in (score desc, order asc) - topk_exact.hip's block_select for GR_THREADS threads.
+template <typename Get>
+__device__ __forceinline__ void gblock_select(int n, int k, Get get, double *out_s, int64_t *out_o, double *red_s,
+                                              int64_t *red_o) {
+    const int tid = threadIdx.x;
+    double prev_s = INFINITY;
+    int64_t prev_o = -1;
+    for (int r = 0; r < k; ++r) {
+        double bs = -INFINITY;
+        int64_t bo = -1;
+        for (int i = tid; i < n; i += GR_THREADS) {
+            double v;
+            int64_t o;
+            get(i, v, o);
+            if (o < 0) continue;
+            const bool after_prev = v < prev_s || (v == prev_s && o > prev_o);
+            const bool beats = bo < 0 || v > bs || (v == bs && o < bo);
+            if (after_prev && beats) {
+                bs = v;
+                bo = o;
+            }
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const double s2 = __shfl_xor(bs, off, 64);
+            const int64_t o2 = __shfl_xor(bo, off, 64);
+            if (o2 >= 0 && (bo < 0 || s2 > bs || (s2 == bs && o2 < bo))) {
+                bs = s2;
+                bo = o2;
+            }
+        }
+        __syncthreads();
+        if ((tid & 63) == 0) {
+            red_s[tid >> 6] = bs;
+            red_o[tid >> 6] = bo;
+        }
+        __syncthreads();
+        bs = red_s[0];
+        bo = red_o[0];
+#pragma unroll
+        for (int w = 1; w < GR_THREADS / 64; ++w) {
+            const double s2 = red_s[w];
+            const int64_t o2 = red_o[w];
+            if (o2 >= 0 && (bo < 0 || s2 > bs || (s2 == bs && o2 < bo))) {
+                bs = s2;
+                bo = o2;
+            }
+        }
+        if (tid == 0) {
+            out_s[r] = bo >= 0 ? bs : -INFINITY;
+            out_o[r] = bo;
+        }
+        prev_s = bs;
+        prev_o = bo;
+        if (bo < 0) {
+            for (int r2 = r + 1 + tid; r2 < k; r2 += GR_THREADS) {
+                out_s[r2] = -INFINITY;
+                out_o[r2] = -1;
+            }
+            break;
+        }
+    }
+    __syncthreads();
+}
+
+// grid = nblk.  Block b owns the groups whose first live row lies in its even slice [lo, hi) of age orders, so every
+// group is scored whole by one block (a group longer than a slice makes its block longer).  Per flagged query: rows in
+// chunks of GR_CHUNK, exact scores, per-chunk group max + lowest row by LDS atomics, the chunk's last group carried into
+// the next chunk, and a stable top-k of complete groups: part[(b * Q + q) * k + i] = {score, representative order}.
+template <int DT>
+__global__ void __launch_bounds__(GR_THREADS)
+    group_redo_scan_kernel(const uint16_t *__restrict__ queries, const uint16_t *__restrict__ mem,
+                           const double *__restrict__ norm64, const int64_t *__restrict__ gord,
+                           const int64_t *__restrict__ d_total, int64_t cap, int ring, int D, int Q, int k,
+                           const int *__restrict__ first_o, const int32_t *__restrict__ flags,
+                           double *__restrict__ part_s, int64_t *__restrict__ part_o) {
+    extern __shared__ __attribute__((aligned(16))) char gr_dyn[];
+    uint16_t *ql = reinterpret_cast<uint16_t *>(gr_dyn);  // [D]
+    __shared__ double sc[GR_CHUNK];
+    __shared__ short lidx[GR_CHUNK];
+    __shared__ unsigned long long gmax[GR_CHUNK];
+    __shared__ long long grep[GR_CHUNK];
+    __shared__ double run_s[GKMAX], new_s[GKMAX], red_s[GR_THREADS / 64];
+    __shared__ int64_t run_o[GKMAX], new_o[GKMAX], red_o[GR_THREADS / 64];
+    __shared__ double qn_sh, carry_s;
+    __shared__ int64_t carry_o, carry_g;
+    __shared__ int carry_live, r0_sh, r1_sh;
+    const int tid = threadIdx.x;
+    int any = 0;
+    for (int i = tid; i < Q; i += GR_THREADS) any |= flags[i];
+    if (!__syncthreads_or(any)) return;
+    const GView gv = group_view(d_total, cap, ring, gord);
+    const int64_t n = gv.rv.n;
+    if (tid == 0) {
+        const int64_t per = (n + gridDim.x - 1) / gridDim.x;
+        int64_t lo = (int64_t)blockIdx.x * per, hi = lo + per;
+        lo = lo < n ? lo : n;
+        hi = hi < n ? hi : n;
+        // first group whose first row is >= x: first_o is increasing over [0, ng] with first_o[ng] = n
+        auto lower = [&](int64_t x) {
+            int64_t a = 0, b = gv.ng;
+            while (a < b) {
+                const int64_t mid = (a + b) >> 1;
+                if (first_o[mid] < x) a = mid + 1;
+                else b = mid;
+            }
+            return first_o[a];
+        };
+        r0_sh = (int)lower(lo);
+        r1_sh = (int)lower(hi);
+    }
+    __syncthreads();
+    const int64_t r0 = r0_sh, r1 = r1_sh;
+    for (int q = 0; q < Q; ++q) {
+        if (flags[q] == 0) continue;  // uniform
+        __syncthreads();
+        for (int i = tid; i < D / 8; i += GR_THREADS)
+            reinterpret_cast<uint4 *>(ql)[i] = reinterpret_cast<const uint4 *>(queries + (size_t)q * D)[i];
+        if (tid < k) {
+            run_s[tid] = -INFINITY;
+            run_o[tid] = -1;
+        }
+        if (tid == 0) carry_live = 0;
+        __syncthreads();
+        if (tid == 0) qn_sh = exact_qnorm<DT>(ql, D);
+        __syncthreads();
+        const double qn = qn_sh;
+        for (int64_t c0 = r0; c0 < r1; c0 += GR_CHUNK) {
+            const int cn = (int)(r1 - c0 < GR_CHUNK ? r1 - c0 : GR_CHUNK);
+            const bool last_chunk = c0 + cn >= r1;
+            const int64_t gbase = gord[slot_of(gv.rv, c0)] - gv.ord0;
+            for (int i = tid; i < cn; i += GR_THREADS) {
+                gmax[i] = 0;
+                grep[i] = LLONG_MAX;
+            }
+            __syncthreads();
+            for (int i = tid; i < cn; i += GR_THREADS) {
+                const int64_t p = slot_of(gv.rv, c0 + i);
+                const double e = exact_score<DT>(ql, qn, mem, norm64, p, D);
+                const int li = (int)(gord[p] - gv.ord0 - gbase);
+                sc[i] = e;
+                lidx[i] = (short)li;
+                atomicMax(&gmax[li], okey64(e));
+            }
+            __syncthreads();
+            for (int i = tid; i < cn; i += GR_THREADS)
+                if (okey64(sc[i]) == gmax[lidx[i]]) atomicMin(&grep[lidx[i]], (long long)(c0 + i));
+            __syncthreads();
+            const int nl = lidx[cn - 1] + 1;
+            __shared__ int carry_cand;
+            if (tid == 0) {
+                carry_cand = 0;
+                if (carry_live) {
+                    if (carry_g == gbase) {  // the carried group goes on in this chunk: its earlier rows win ties
+                        if (okey64(carry_s) >= gmax[0]) {
+                            gmax[0] = okey64(carry_s);
+                            grep[0] = carry_o;
+                        }
+                    } else {
+                        carry_cand = 1;
+                    }
+                }
+            }
+            __syncthreads();
+            const int nloc = last_chunk ? nl : nl - 1;
+            const int ncar = carry_cand;
+            gblock_select(nloc + ncar + k, k,
+                          [&](int i, double &v, int64_t &o) {
+                              if (i < nloc) {
+                                  v = dekey64(gmax[i]);
+                                  o = grep[i];
+                              } else if (i < nloc + ncar) {
+                                  v = carry_s;
+                                  o = carry_o;
+                              } else {
+                                  v = run_s[i - nloc - ncar];
+                                  o = run_o[i - nloc - ncar];
+                              }
+                          },
+                          new_s, new_o, red_s, red_o);
+            if (tid < k) {
+                run_s[tid] = new_s[tid];
+                run_o[tid] = new_o[tid];
+            }
+            if (tid == 0) {
+                carry_live = last_chunk ? 0 : 1;
+                if (!last_chunk) {
+                    carry_s = dekey64(gmax[nl - 1]);
+                    carry_o = grep[nl - 1];
+                    carry_g = gbase + nl - 1;
+                }
+            }
+            __syncthreads();
+        }
+        if (tid < k) {
+            part_s[((size_t)blockIdx.x * Q + q) * k + tid] = run_s[tid];
+            part_o[((size_t)blockIdx.x * Q + q) * k + tid] = run_o[tid];
+        }
+    }
+}
+
+// grid = Q; unflagged queries exit at once.  Stable top-k over the nblk * k slice winners (each group lives in one
+// slice), then the output mapping of the fast path.
+__global__ void __launch_bounds__(GR_THREADS)
+    group_redo_merge_kernel(const double *__restrict__ part_s, const int64_t *__restrict__ part_o, int nblk, int Q,
+                            int k, const int32_t *__restrict__ flags, const int64_t *__restrict__ d_total, int64_t cap,
+                            int ring, const int64_t *__restrict__ gkey, int use_min, double min_score, int score_mode,
+                            double *__restrict__ out_scores, int64_t *__restrict__ out_rows,
+                            int64_t *__restrict__ out_keys) {
+    __shared__ double win_s[GKMAX], red_s[GR_THREADS / 64];
+    __shared__ int64_t win_o[GKMAX], red_o[GR_THREADS / 64];
+    const int q = blockIdx.x, tid = threadIdx.x;
+    if (flags[q] == 0) return;
+    const RingView rv = ring_view(*d_total, cap, ring);
+    gblock_select(nblk * k, k,
+                  [&](int i, double &v, int64_t &o) {
+                      const int b = i / k, e = i - b * k;
+                      v = part_s[((size_t)b * Q + q) * k + e];
+                      o = part_o[((size_t)b * Q + q) * k + e];
+                  },
+                  win_s, win_o, red_s, red_o);
+    if (tid < k) {
+        const int64_t o = win_o[tid];
+        double shown = win_s[tid];
+        bool ok = o >= 0;
+        if (ok) {
+            shown = shown_score(shown, score_mode);
+            if (use_min && !(shown > min_score)) ok = false;
+        }
+        out_scores[(size_t)q * k + tid] = ok ? shown : 0.0;
+        out_rows[(size_t)q * k + tid] = ok ? rv.base + o : -1;
+        if (out_keys) out_keys[(size_t)q * k + tid] = ok ? gkey[slot_of(rv, o)] : -1;
+    }
+}
+
+// ---- host --------------------------------------------------------------------------------------------------
+struct GPlan {
+    int M, qt, qgroups, nbx, nblk, tbl_blocks;
+    int cmp_slices;
+    size_t off_first, off_cg, off_ck, off_cn, off_flags, off_ps, off_po, off_cut, off_cc, off_cbuf, total;
+};
+
+GPlan group_plan(const vm_memory *m, int Q, int k) {
+    GPlan p;
+    p.M = k + (k / 4 > 8 ? k / 4 : 8);  // slack: near-ties between rank k and rank M are certified by the gap
+    p.qt = Q <= 16 ? 1 : 2;
+    p.qgroups = (Q + 16 * p.qt - 1) / (16 * p.qt);
+    const int64_t tiles = (m->cap + 15) / 16;
+    int64_t nbx = (tiles + GS_THREADS / 64 - 1) / (GS_THREADS / 64);
+    const int64_t lim = (int64_t)m->ctx->num_cus * 8;
+    p.nbx = (int)(nbx < lim ? (nbx < 1 ? 1 : nbx) : lim);
+    int64_t nb = (m->cap + GR_CHUNK - 1) / GR_CHUNK;
+    if (nb > m->ctx->num_cus) nb = m->ctx->num_cus;
+    p.nblk = nb < 1 ? 1 : (int)nb;
+    int64_t tb = (m->cap + 256) / 256;
+    p.tbl_blocks = (int)(tb < 1024 ? tb : 1024);
+    size_t off = vm_align_up((size_t)Q * (size_t)m->cap * 4, 256);  // F: [Q][live groups] fp32-max keys
+    p.off_first = off;
+    off += vm_align_up((size_t)(m->cap + 1) * 4, 256);
+    p.off_cg = off;
+    off += vm_align_up((size_t)Q * GCMAX * 4, 256);
+    p.off_ck = off;
+    off += vm_align_up((size_t)Q * GCMAX * 4, 256);
+    p.off_cn = off;
+    off += vm_align_up((size_t)Q * 4, 256);
+    p.off_flags = off;
+    off += vm_align_up((size_t)Q * 4, 256);
+    p.off_cut = off;
+    off += vm_align_up((size_t)Q * 8, 256);
+    p.off_cc = off;
+    off += vm_align_up((size_t)Q * 4, 256);
+    p.off_cbuf = off;
+    off += vm_align_up((size_t)Q * SEL_CAP * 8, 256);
+    int64_t sl = (m->cap + 8191) / 8192;
+    p.cmp_slices = (int)(sl < 1 ? 1 : (sl > 64 ? 64 : sl));
+    p.off_ps = off;
+    off += vm_align_up((size_t)p.nblk * Q * k * 8, 256);
+    p.off_po = off;
+    off += vm_align_up((size_t)p.nblk * Q * k * 8, 256);
+    p.total = off;
+    return p;
+}
+
+int group_check(vm_memory *m, const void *queries, int Q, int k, int score_mode, const double *out_scores,
+                const int64_t *out_rows, const void *workspace, size_t workspace_bytes, const char *who) {
+    vm_ctx *ctx = m->ctx;
+    if (!m->gkey) return vm_fail(ctx, VM_ERR_INVALID, "%s: the memory is not grouped (vm_memory_create_grouped)", who);
+    if (!queries || !out_scores || !out_rows || Q <= 0 || k <= 0)
+        return vm_fail(ctx, VM_ERR_INVALID, "%s: bad arguments", who);
+    if (k > GKMAX) return vm_fail(ctx, VM_ERR_UNSUPPORTED, "%s: k=%d > %d", who, k, GKMAX);
+    if (score_mode != VM_SCORE_RAW && score_mode != VM_SCORE_UNIT_INTERVAL)
+        return vm_fail(ctx, VM_ERR_INVALID, "bad score_mode %d", score_mode);
+    const size_t need = group_plan(m, Q, k).total;
+    if (!workspace || workspace_bytes < need)
+        return vm_fail(ctx, VM_ERR_NOMEM, "%s: workspace %zu < %zu", who, workspace_bytes, need);
+    if (((uintptr_t)workspace & 255) || ((uintptr_t)queries & 15))
+        return vm_fail(ctx, VM_ERR_INVALID, "%s: workspace must be 256-byte and queries 16-byte aligned", who);
+    return VM_OK;
+}
+
+template <int DT>
+int group_redo(vm_memory *m, const GPlan &p, const void *queries, int Q, int k, int use_min, double min_score,
+               int score_mode, double *out_scores, int64_t *out_rows, int64_t *out_keys, char *ws, hipStream_t st) {
+    vm_ctx *ctx = m->ctx;
+    vm_prof_scope prof(ctx, VM_PROF_TOPK_EXACT, st);
+    const int *first_o = (const int *)(ws + p.off_first);
+    const int32_t *flags = (const int32_t *)(ws + p.off_flags);
+    double *part_s = (double *)(ws + p.off_ps);
+    int64_t *part_o = (int64_t *)(ws + p.off_po);
+    group_redo_scan_kernel<DT><<<p.nblk, GR_THREADS, (size_t)m->D * 2, st>>>(
+        (const uint16_t *)queries, m->rows, m->norm64, m->gord, m->d_total, m->cap, m->ring, m->D, Q, k, first_o, flags,
+        part_s, part_o);
+    VM_LAUNCH_CHECK(ctx);
+    group_redo_merge_kernel<<<Q, GR_THREADS, 0, st>>>(part_s, part_o, p.nblk, Q, k, flags, m->d_total, m->cap, m->ring,
+                                                      m->gkey, use_min, min_score, score_mode, out_scores, out_rows,
+                                                      out_keys);
+    VM_LAUNCH_CHECK(ctx);
+    return VM_OK;
+}
+
+template <int DT, int QT>
+int group_scan(vm_memory *m, const GPlan &p, const void *queries, int Q, uint32_t *F, hipStream_t st) {
+    const size_t lds = (size_t)QT * 16 * m->D * 2;
+    auto kern = group_scan_kernel<DT, QT>;
+    if (lds > 65536) VM_HIP(m->ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    kern<<<dim3(p.nbx, p.qgroups), GS_THREADS, lds, st>>>(m->rows, m->rnorm32, m->gord, (const uint16_t *)queries,
+                                                         m->d_total, m->cap, m->ring, m->D, Q, F);
+    VM_LAUNCH_CHECK(m->ctx);
+    return VM_OK;
+}
+
+template <int DT>
+int group_topk(vm_memory *m, const void *queries, int Q, int k, int use_min, double min_score, int score_mode,
+               double *out_scores, int64_t *out_rows, int64_t *out_keys, int32_t *out_uncertified,
+               int32_t *out_query_flags, char *ws, hipStream_t st) {
+    vm_ctx *ctx = m->ctx;
+    const GPlan p = group_plan(m, Q, k);
+    uint32_t *F = (uint32_t *)ws;
+    int *first_o = (int *)(ws + p.off_first);
+    int *cand_g = (int *)(ws + p.off_cg);
+    uint32_t *cand_k = (uint32_t *)(ws + p.off_ck);
+    int *cand_n = (int *)(ws + p.off_cn);
+    int *flags = (int *)(ws + p.off_flags);
+    {
+        vm_prof_scope prof(ctx, VM_PROF_TOPK_SCAN, st);
+        group_table_kernel<<<p.tbl_blocks, 256, 0, st>>>(m->d_total, m->cap, m->ring, m->gord, Q, first_o, F, nullptr, 0);
+        VM_LAUNCH_CHECK(ctx);
+        const int rc = p.qt == 1 ? group_scan<DT, 1>(m, p, queries, Q, F, st) : group_scan<DT, 2>(m, p, queries, Q, F, st);
+        if (rc != VM_OK) return rc;
+    }
+    {
+        vm_prof_scope prof(ctx, VM_PROF_TOPK_FINALIZE, st);
+        unsigned long long *cut = (unsigned long long *)(ws + p.off_cut);
+        int *ccount = (int *)(ws + p.off_cc);
+        unsigned long long *cbuf = (unsigned long long *)(ws + p.off_cbuf);
+        group_cut_kernel<<<Q, SEL_THREADS, 0, st>>>(m->d_total, m->cap, m->ring, m->gord, F, p.M + 1, cut, ccount);
+        VM_LAUNCH_CHECK(ctx);
+        group_compact_kernel<<<dim3(p.cmp_slices, Q), CMP_THREADS, 0, st>>>(m->d_total, m->cap, m->ring, m->gord, F, cut,
+                                                                            ccount, cbuf);
+        VM_LAUNCH_CHECK(ctx);
+        group_select_final_kernel<<<Q, SEL_THREADS, 0, st>>>(m->d_total, m->cap, m->ring, m->gord, F, p.M + 1, ccount,
+                                                             cbuf, cand_g, cand_k, cand_n);
+        VM_LAUNCH_CHECK(ctx);
+        group_finalize_kernel<DT><<<Q, GF_THREADS, (size_t)m->D * 2, st>>>(
+            m->rows, m->norm64, m->gkey, m->gord, (const uint16_t *)queries, m->d_total, m->cap, m->ring, m->D, first_o,
+            cand_g, cand_k, cand_n, p.M, k, use_min, min_score, score_mode, out_scores, out_rows, out_keys,
+            out_uncertified, flags, out_query_flags);
+        VM_LAUNCH_CHECK(ctx);
+    }
+    return group_redo<DT>(m, p, queries, Q, k, use_min, min_score, score_mode, out_scores, out_rows, out_keys, ws, st);
+}
+
+}  // namespace
+
+extern "C" size_t vm_topk_grouped_workspace_bytes(const vm_memory *m, int Q, int k) {
+    if (!m || Q <= 0 || k <= 0 || k > GKMAX) return 0;
+    return group_plan(m, Q, k).total;
+}
+
+extern "C" int vm_topk_cosine_grouped(vm_memory *m, const void *queries, int Q, int k, int use_min_score,
+                                      double min_score, int score_mode, double *out_scores, int64_t *out_rows,
+                                      int64_t *out_keys, int32_t *out_uncertified, int32_t *out_query_flags,
+                                      void *workspace, size_t workspace_bytes, void *stream) {
+    if (!m) return VM_ERR_INVALID;
+    int rc = group_check(m, queries, Q, k, score_mode, out_scores, out_rows, workspace, workspace_bytes,
+                         "vm_topk_cosine_grouped");
+    if (rc != VM_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if (m->dtype == VM_F16)
+        return group_topk<VM_F16>(m, queries, Q, k, use_min_score, min_score, score_mode, out_scores, out_rows, out_keys,
+                                  out_uncertified, out_query_flags, (char *)workspace, st);
+    return group_topk<VM_BF16>(m, queries, Q, k, use_min_score, min_score, score_mode, out_scores, out_rows, out_keys,
+                               out_uncertified, out_query_flags, (char *)workspace, st);
+}
+
+extern "C" int vm_topk_cosine_grouped_exact(vm_memory *m, const void *queries, int Q, int k, int use_min_score,
+                                            double min_score, int score_mode, double *out_scores, int64_t *out_rows,
+                                            int64_t *out_keys, void *workspace, size_t workspace_bytes, void *stream) {
+    if (!m) return VM_ERR_INVALID;
+    int rc = group_check(m, queries, Q, k, score_mode, out_scores, out_rows, workspace, workspace_bytes,
+                         "vm_topk_cosine_grouped_exact");
+    if (rc != VM_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    vm_ctx *ctx = m->ctx;
+    const GPlan p = group_plan(m, Q, k);
+    char *ws = (char *)workspace;
+    group_table_kernel<<<p.tbl_blocks, 256, 0, st>>>(m->d_total, m->cap, m->ring, m->gord, Q, (int *)(ws + p.off_first),
+                                                     nullptr, (int32_t *)(ws + p.off_flags), 1);
+    VM_LAUNCH_CHECK(ctx);
+    if (m->dtype == VM_F16)
+        return group_redo<VM_F16>(m, p, queries, Q, k, use_min_score, min_score, score_mode, out_scores, out_rows,
+                                  out_keys, ws, st);
+    return group_redo<VM_BF16>(m, p, queries, Q, k, use_min_score, min_score, score_mode, out_scores, out_rows,
+                               out_keys, ws, st);
+}

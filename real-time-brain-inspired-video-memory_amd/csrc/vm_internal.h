@@ -11,9 +11,17 @@ struct vm_memory {
     uint16_t *rows;    // [cap_pad, D] 16-bit
     double *norm64;    // [cap_pad] exact reference norm of each stored row
     float *rnorm32;    // [cap_pad] 1/norm (0 for a zero row) for the fp32 scan
-    int64_t *d_total;  // device: rows appended so far (drives slots under graph replay)
+    int64_t *d_total;  // device: rows appended so far (drives slots under graph replay); 64 bytes, see VM_GSTATE_*
     int64_t h_total;   // host mirror
+    // grouped memories only (vm_memory_create_grouped; null otherwise)
+    int64_t *gkey;     // [cap_pad] group key of each slot (a plain append stores -1 - row id)
+    int64_t *gord;     // [cap_pad] group ordinal of each slot: groups ever opened before this row's group, so equal
+                       // ordinals = one group and ordinals rise by 0 or 1 from each row id to the next
 };
+
+// The 64-byte device block d_total points to: [0] row count, then the grouped append's state (zeroed with the row count
+// by vm_memory_reset, so a reset also forgets the open group).
+enum { VM_GSTATE_GROUPS = 1, VM_GSTATE_LAST_KEY = 2, VM_GSTATE_OPEN = 3 };
 
 // Logical view of the (ring) row store for a device-side row count: searchable rows n, physical slot of the oldest
 // row (head), row id of the oldest row (base).  Row of age order o (0 = oldest) sits in slot (o + head) % cap.

@@ -57,6 +57,12 @@ class ShardedRetriever:
         lo = self.rank * F
         return self._merge(s_all[:, lo:lo + F].contiguous(), r_all[:, lo:lo + F].contiguous())
 
+    def search_grouped(self, queries: torch.Tensor, k: int):
+        """Refused: a group (one chunk's frames) can span shards, so per-shard group maxima do not merge into the
+        global grouped answer.  Grouped search runs on one GPU (EmbeddingMemory.topk_grouped)."""
+        raise ValueError("grouped (distinct-chunk) search is not supported on a sharded memory: a group can span shards; "
+                         "use EmbeddingMemory.topk_grouped on a single-GPU grouped memory")
+
     def _all_gather(self, t: torch.Tensor) -> torch.Tensor:
         """Rank-major concatenation along dim 0.  RCCL gathers device tensors in place; under a gloo group (CPU tests,
         single-GPU rehearsal of the N>1 path) device tensors are staged through the host, since gloo has no device

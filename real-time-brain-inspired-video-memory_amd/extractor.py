@@ -157,11 +157,14 @@ def build_text_embedder(config: Any, tokenizer=None):
 def build_memory(mem_cfg, encoder: FrameEncoder) -> EmbeddingMemory:
     import os
     dtype = mem_cfg.dtype or encoder.dtype_name
+    group_by = getattr(mem_cfg, "group_by", None)
+    if group_by not in (None, "chunk"):
+        raise ValueError(f"memory.group_by must be null or 'chunk', got {group_by!r}")
     if mem_cfg.snapshot and os.path.exists(mem_cfg.snapshot):
         return EmbeddingMemory.restore(mem_cfg.snapshot, capacity=int(mem_cfg.capacity), ring=bool(mem_cfg.ring),
                                        device=encoder.device.index or 0)
     return EmbeddingMemory(int(mem_cfg.capacity), encoder.out_dim, dtype, ring=bool(mem_cfg.ring),
-                           device=encoder.device.index or 0)
+                           device=encoder.device.index or 0, grouped=group_by == "chunk")
 
 
 class FrameEmbeddingExtractor:
@@ -440,8 +443,12 @@ class FrameEmbeddingExtractor:
                             c["first"] = self.memory.append(emb, ids=ids, meta=c["meta"])
                     if batched:      # one append for the group: rows, ids and meta in chunk order
                         live = [c for c in chunks if c["nframes"]]
+                        # a grouped memory (memory.group_by: chunk) gets one key per chunk, per row; a single-chunk
+                        # append (below) is one new group by default
+                        group = ([k for c in live for k in [self.memory.new_group_key()] * c["nframes"]]
+                                 if getattr(self.memory, "grouped", False) else None)
                         first = self.memory.append(emb_all, ids=[i for c in live for i in c["ids"]],
-                                                   meta=[m for c in live for m in c["meta"]])
+                                                   meta=[m for c in live for m in c["meta"]], group=group)
                         for c in live:
                             c["first"] = first
                             first += c["nframes"]

@@ -52,12 +52,13 @@ class HipHybridMixin:
 
     _hip: Optional[HipVectorSearch] = None
 
-    def attach_memory(self, memory, *, score_mode: int, min_score: float = 0.3, splitter=None, embedder=None):
+    def attach_memory(self, memory, *, score_mode: int, min_score: float = 0.3, splitter=None, embedder=None,
+                      distinct: bool = False):
         """``score_mode`` is required: see similarity.HipVectorSearch (Neo4j's score mapping is unpinned).
         ``embedder``: what embeds the questions (e.g. text.HipTextEmbedder); None = ``self.embedder``.  ValueError when
-        it states an ``out_dim`` other than ``memory.dim``."""
+        it states an ``out_dim`` other than ``memory.dim``.  ``distinct=True``: one hit per chunk (grouped memory)."""
         self._hip = HipVectorSearch(memory, self.embedder if embedder is None else embedder, self.config,
-                                    min_score=min_score, score_mode=score_mode, splitter=splitter)
+                                    min_score=min_score, score_mode=score_mode, splitter=splitter, distinct=distinct)
         return self
 
     async def _vector_search_chunks(self, session, query):

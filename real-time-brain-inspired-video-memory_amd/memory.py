@@ -8,7 +8,10 @@ Reference behaviour mirrored here:
   * row order = append order (the reference's dict order comes from an unordered Cypher MATCH and is not
                deterministic; the build defines it).
 
-All arithmetic is in libvidmem.so (csrc/memory.hip, csrc/topk.hip, csrc/topk_exact.hip).
+Grouped memories (``grouped=True``) also keep one int64 group key per row: ``topk_grouped`` returns the k best groups
+(video chunks), one hit per group, instead of k frames of one moment (include/vidmem.h).
+
+All arithmetic is in libvidmem.so (csrc/memory.hip, csrc/topk.hip, csrc/topk_exact.hip, csrc/topk_group.hip).
 """
 from __future__ import annotations
 
@@ -26,7 +29,7 @@ def _torch_dtype(name: str):
 
 class EmbeddingMemory:
     def __init__(self, capacity: int, dim: int, dtype: str = "f16", ring: bool = False, device: int = 0,
-                 graph_uuid: Optional[str] = None):
+                 graph_uuid: Optional[str] = None, grouped: bool = False):
         self.ctx = _lib.Context.get(device)
         self.L = self.ctx.L
         self.device = torch.device("cuda", device)
@@ -36,6 +39,12 @@ class EmbeddingMemory:
         self.capacity = int(capacity)
         self.ring = bool(ring)
         self.graph_uuid = graph_uuid
+        self.grouped = bool(grouped)
+        self._next_group_key = 0    # above every key appended from host values (new_group_key)
+        self._last_keys_dev = None  # keys of the last grouped append when they were a device tensor (host: unknown)
+        self._gws = None            # grouped top-k workspace (vm_topk_grouped_workspace_bytes), grown on demand
+        self._gflags = None         # per-query flags of the last grouped call (device int32)
+        self._guncert = None        # queries the grouped fast path could not certify (device int32, accumulates)
         # Host tables: chunk id (reference pre_llm_injector.py:91) and {"time":..., "content":...} (for
         # _vector_search_chunks) of row (table_base + i).  table_base stays 0 unless a ring has wrapped far enough for
         # the slots of overwritten rows to be dropped (see _trim_tables); use id_of / meta_of for row -> entry.
@@ -43,8 +52,9 @@ class EmbeddingMemory:
         self.meta: List[Optional[dict]] = []
         self.table_base = 0
         h = C.c_void_p()
-        self.ctx.check(self.L.vm_memory_create(self.ctx.handle, self.capacity, self.dim, _lib.DTYPES[dtype],
-                                               1 if ring else 0, C.byref(h)))
+        create = self.L.vm_memory_create_grouped if self.grouped else self.L.vm_memory_create
+        self.ctx.check(create(self.ctx.handle, self.capacity, self.dim, _lib.DTYPES[dtype], 1 if ring else 0,
+                              C.byref(h)))
         self.handle = h
         self._scratch = TopkScratch(self.device)
 
@@ -78,20 +88,70 @@ class EmbeddingMemory:
             raise ValueError(f"embedding dimension {rows.shape[-1]} != memory dimension {self.dim}")
         return rows.to(device=self.device, dtype=self.dtype).contiguous()
 
-    def append(self, rows, ids: Optional[Sequence[str]] = None, meta: Optional[Sequence[dict]] = None) -> int:
+    def append(self, rows, ids: Optional[Sequence[str]] = None, meta: Optional[Sequence[dict]] = None,
+               group=None) -> int:
+        """Append rows; return the id of the first.  Grouped memories: ``group`` is one key for every row, or one key
+        per row (a sequence or an int64 tensor); omitted = this call is one new group (``new_group_key``, never equal to
+        the previous call's last key).  A group is a run of consecutive rows with equal keys, so a call whose first key
+        equals the previous call's last key continues that group.  A group is searched fast while a query's candidate
+        groups hold at most 4,096 rows together (k = 10: about 220 rows per group); larger groups, such as a whole video
+        appended in one call, are answered by the exhaustive search every time (exact, slower: DESIGN.md 11)."""
         t = self._as_rows(rows)
         B = t.shape[0]
         if ids is not None and len(ids) != B:
             raise ValueError("ids and rows differ in length")
+        keys = self._group_keys_for(B, group)
         first = C.c_int64(0)
-        self.ctx.check(self.L.vm_memory_append(self.handle, C.c_void_p(t.data_ptr()), B, C.byref(first),
-                                               _lib.current_stream_ptr()))
+        if keys is None:
+            self.ctx.check(self.L.vm_memory_append(self.handle, C.c_void_p(t.data_ptr()), B, C.byref(first),
+                                                   _lib.current_stream_ptr()))
+        else:
+            self.ctx.check(self.L.vm_memory_append_grouped(self.handle, C.c_void_p(t.data_ptr()), B,
+                                                           C.c_void_p(keys.data_ptr()), C.byref(first),
+                                                           _lib.current_stream_ptr()))
+            keys.record_stream(torch.cuda.current_stream())
         # the kernel reads `t` asynchronously: keep it alive until the stream has consumed it
         t.record_stream(torch.cuda.current_stream())
         self.ids.extend(list(ids) if ids is not None else [None] * B)
         self.meta.extend(list(meta) if meta is not None else [None] * B)
         self._trim_tables()
         return int(first.value)
+
+    def new_group_key(self) -> int:
+        """A key no earlier ``new_group_key`` call of this memory returned (and above every key appended so far from
+        host values): two videos in one memory never merge their chunk 0."""
+        key = self._next_group_key
+        self._next_group_key += 1
+        return key
+
+    def _group_keys_for(self, B: int, group) -> Optional[torch.Tensor]:
+        if not self.grouped:
+            if group is not None:
+                raise ValueError("group keys need a grouped memory (EmbeddingMemory(..., grouped=True))")
+            return None
+        if group is None:
+            # one NEW group: the key must differ from the previous call's last key, or the device would continue that
+            # group.  Host-given keys already raised the counter above it; device-given ones are read back here (one
+            # synchronising read - pass `group` explicitly inside a graph capture)
+            if self._last_keys_dev is not None and self._last_keys_dev.numel():
+                self._next_group_key = max(self._next_group_key, int(self._last_keys_dev[-1]) + 1)
+            group = self.new_group_key()
+        self._last_keys_dev = None
+        if isinstance(group, torch.Tensor) and group.dim() > 0:
+            keys = group.to(device=self.device, dtype=torch.int64).reshape(-1).contiguous()
+            self._last_keys_dev = keys
+        elif isinstance(group, (list, tuple)) or (hasattr(group, "shape") and len(getattr(group, "shape")) > 0):
+            vals = [int(x) for x in group]
+            if vals:
+                self._next_group_key = max(self._next_group_key, max(vals) + 1)
+            keys = torch.tensor(vals, dtype=torch.int64).to(self.device)
+        else:
+            key = int(group)
+            self._next_group_key = max(self._next_group_key, key + 1)
+            keys = torch.full((B,), key, dtype=torch.int64, device=self.device)
+        if keys.numel() != B:
+            raise ValueError(f"{keys.numel()} group keys for {B} rows")
+        return keys
 
     def _trim_tables(self) -> None:
         """A rolling window must not keep one table slot per row EVER appended: once a ring holds more than two
@@ -121,6 +181,8 @@ class EmbeddingMemory:
 
     def reset(self):
         self.ctx.check(self.L.vm_memory_reset(self.handle, _lib.current_stream_ptr()))
+        self._next_group_key = 0
+        self._last_keys_dev = None
         self.ids.clear()
         self.meta.clear()
         self.table_base = 0
@@ -183,6 +245,62 @@ class EmbeddingMemory:
         ws.record_stream(torch.cuda.current_stream())
         return scores, rows
 
+    def prepare_topk_grouped(self, Q: int, k: int) -> None:
+        """Size the grouped top-k workspace for (Q, k) now (before a graph capture: a capture must not allocate)."""
+        need = int(self.L.vm_topk_grouped_workspace_bytes(self.handle, int(Q), int(k)))
+        if self._gws is None or self._gws.numel() < need:
+            self._gws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
+        if self._gflags is None or self._gflags.numel() < Q:
+            self._gflags = torch.zeros(max(Q, 1), dtype=torch.int32, device=self.device)
+        if self._guncert is None:
+            self._guncert = torch.zeros(1, dtype=torch.int32, device=self.device)
+
+    def topk_grouped(self, queries, k: int, min_score: Optional[float] = None, score_mode: int = _lib.VM_SCORE_RAW,
+                     exact: bool = False) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """-> (scores [Q,k] float64, rows [Q,k] int64, keys [Q,k] int64): the k best GROUPS of a grouped memory.
+
+        The exhaustive row ranking of ``topk`` (score desc, row asc; score mapping and > min_score filter) with only the
+        first row of each group kept: a group scores the exact max over its rows, ``rows`` holds the lowest row id
+        reaching it, ``keys`` its group key; -1 / 0.0 / -1 padded.  Always the exhaustive answer: the fp32 fast path
+        redoes the queries it cannot certify on the device, in the same call (csrc/topk_group.hip).  ``exact=True``
+        scores every row exactly for every query (slow).  1 <= k <= 64.  The per-query flags of the last call (why a
+        query was redone, vm_topk_flag) are in ``last_group_flags``."""
+        if not self.grouped:
+            raise ValueError("topk_grouped needs a grouped memory (EmbeddingMemory(..., grouped=True))")
+        if not 1 <= int(k) <= 64:
+            raise ValueError(f"grouped top-k supports 1 <= k <= 64, got {k}")
+        q = self._as_rows(queries)
+        Q = q.shape[0]
+        self.prepare_topk_grouped(Q, k)
+        scores = torch.empty((Q, k), dtype=torch.float64, device=self.device)
+        rows = torch.empty((Q, k), dtype=torch.int64, device=self.device)
+        keys = torch.empty((Q, k), dtype=torch.int64, device=self.device)
+        st = _lib.current_stream_ptr()
+        use_min = 0 if min_score is None else 1
+        ms = 0.0 if min_score is None else float(min_score)
+        if exact:
+            self.ctx.check(self.L.vm_topk_cosine_grouped_exact(
+                self.handle, C.c_void_p(q.data_ptr()), Q, int(k), use_min, ms, int(score_mode),
+                C.c_void_p(scores.data_ptr()), C.c_void_p(rows.data_ptr()), C.c_void_p(keys.data_ptr()),
+                C.c_void_p(self._gws.data_ptr()), self._gws.numel(), st))
+        else:
+            self.ctx.check(self.L.vm_topk_cosine_grouped(
+                self.handle, C.c_void_p(q.data_ptr()), Q, int(k), use_min, ms, int(score_mode),
+                C.c_void_p(scores.data_ptr()), C.c_void_p(rows.data_ptr()), C.c_void_p(keys.data_ptr()),
+                C.c_void_p(self._guncert.data_ptr()), C.c_void_p(self._gflags.data_ptr()),
+                C.c_void_p(self._gws.data_ptr()), self._gws.numel(), st))
+        q.record_stream(torch.cuda.current_stream())
+        return scores, rows, keys
+
+    @property
+    def last_group_flags(self) -> Optional[torch.Tensor]:
+        return self._gflags
+
+    @property
+    def grouped_uncertified_count(self) -> int:
+        """Queries the grouped fast path redid exhaustively since this memory was created (synchronises)."""
+        return 0 if self._guncert is None else int(self._guncert.item())
+
     @property
     def uncertified_count(self) -> int:
         """Queries redone exhaustively since ``reset_uncertified`` on this memory's own scratch (one 4-byte
@@ -231,29 +349,48 @@ class EmbeddingMemory:
             phys = torch.cat([phys[head:], phys[:head]])
         return total - n, phys.cpu().numpy().view(np.uint16)
 
+    def group_keys_host(self):
+        """int64 [n]: the group key of every searchable row in row-id order (grouped memories; host copy)."""
+        import numpy as np
+        if not self.grouped:
+            raise ValueError("not a grouped memory")
+        total, n = len(self), self.searchable
+        keys = _tensor_from_ptr(self.L.vm_memory_group_keys(self.handle), (n,), torch.int64, self.device)
+        if self.ring and total > self.capacity:
+            head = total % self.capacity
+            keys = torch.cat([keys[head:], keys[:head]])
+        return keys.cpu().numpy().astype(np.int64)
+
     def snapshot(self, path: str) -> None:
         import json
         import numpy as np
         base, rows = self.rows_host()
         total = base + rows.shape[0]
+        extra = {"group_keys": self.group_keys_host()} if self.grouped else {}  # optional field: old files have none
         np.savez(path, rows=rows, dtype=self.dtype_name, dim=self.dim,
                  first_row_id=base, graph_uuid=self.graph_uuid or "",
                  ids=json.dumps([self.id_of(r) for r in range(base, total)]),
-                 meta=json.dumps([self.meta_of(r) for r in range(base, total)]))
+                 meta=json.dumps([self.meta_of(r) for r in range(base, total)]), **extra)
 
     @classmethod
     def restore(cls, path: str, capacity: Optional[int] = None, ring: bool = False, device: int = 0
                 ) -> "EmbeddingMemory":
-        """Row ids restart at 0 in the restored memory (ids / meta tables are restored in the same order)."""
+        """Row ids restart at 0 in the restored memory (ids / meta tables are restored in the same order).  A snapshot
+        of a grouped memory restores grouped, with its key column (a group cut by a ring's window keeps its rows)."""
         import json
         import numpy as np
         z = np.load(path, allow_pickle=False)
         rows = torch.from_numpy(z["rows"].view(np.int16))
         dtype = str(z["dtype"])
+        keys = z["group_keys"] if "group_keys" in z.files else None
         mem = cls(capacity or max(rows.shape[0], 1), int(z["dim"]), dtype, ring=ring, device=device,
-                  graph_uuid=str(z["graph_uuid"]) or None)
+                  graph_uuid=str(z["graph_uuid"]) or None, grouped=keys is not None)
         if rows.shape[0]:
-            mem.append(rows.view(_torch_dtype(dtype)), ids=json.loads(str(z["ids"])), meta=json.loads(str(z["meta"])))
+            group = None if keys is None else torch.from_numpy(keys.astype(np.int64))
+            mem.append(rows.view(_torch_dtype(dtype)), ids=json.loads(str(z["ids"])), meta=json.loads(str(z["meta"])),
+                       group=group)
+            if keys is not None and keys.size:
+                mem._next_group_key = max(0, int(keys.max()) + 1)
         return mem
 
     def id_of(self, row: int) -> Optional[str]:

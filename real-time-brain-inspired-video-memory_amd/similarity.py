@@ -49,14 +49,23 @@ def _length(e) -> int:
     return int(e.shape[-1]) if isinstance(e, torch.Tensor) else len(e)
 
 
-def batch_similarities(memory: EmbeddingMemory, chunk_embeddings: Sequence, top_k: int
+def _check_distinct(memory: EmbeddingMemory, distinct: bool) -> None:
+    if distinct and not getattr(memory, "grouped", False):
+        raise ValueError("distinct=True needs a grouped memory (EmbeddingMemory(..., grouped=True), memory.group_by: chunk)")
+
+
+def batch_similarities(memory: EmbeddingMemory, chunk_embeddings: Sequence, top_k: int, distinct: bool = False
                        ) -> List[List[Tuple[str, float]]]:
     """One batched top-k launch for every non-failed query; result re-threaded into the reference's list shape.
 
     A query whose length differs from the stored vectors' scores 0.0 against EVERY row in the reference
     (``_cosine_similarity``: ``if len(vec1) != len(vec2): return 0.0``, src/components/pre_llm_injector.py:378-379), and
     the stable descending sort (:369) then keeps memory order: the answer is the first ``top_k`` stored chunks, each
-    with score 0.0.  That is reproduced on the host (no arithmetic involved) instead of raising."""
+    with score 0.0.  That is reproduced on the host (no arithmetic involved) instead of raising.
+
+    ``distinct=True`` (grouped memories): at most one hit per group - the best frame of each of the ``top_k`` best
+    chunks (EmbeddingMemory.topk_grouped); the wrong-length rule above still lists the first rows."""
+    _check_distinct(memory, distinct)
     ok_idx = [i for i, e in enumerate(chunk_embeddings) if not isinstance(e, Exception) and e is not None]
     out: List[List[Tuple[str, float]]] = [[] for _ in chunk_embeddings]
     if not ok_idx or memory.searchable == 0 or top_k <= 0:
@@ -75,7 +84,10 @@ def batch_similarities(memory: EmbeddingMemory, chunk_embeddings: Sequence, top_
         q = torch.stack([chunk_embeddings[i] for i in ok_idx])
     else:
         q = torch.tensor([list(chunk_embeddings[i]) for i in ok_idx], dtype=torch.float32)
-    scores, rows = memory.topk(q, top_k)
+    if distinct:
+        scores, rows, _ = memory.topk_grouped(q, top_k)
+    else:
+        scores, rows = memory.topk(q, top_k)
     scores, rows = scores.cpu().tolist(), rows.cpu().tolist()
     for slot, i in enumerate(ok_idx):
         out[i] = [(memory.id_of(r), float(s)) for r, s in zip(rows[slot], scores[slot]) if r >= 0]
@@ -85,15 +97,18 @@ def batch_similarities(memory: EmbeddingMemory, chunk_embeddings: Sequence, top_
 class HipPreLLMSimilarity:
     """Mixin / stand-alone object for PreLLMInjector: set ``self.memory`` and ``self.embedder_config``."""
 
-    def __init__(self, memory: EmbeddingMemory, embedder_config: Any):
+    def __init__(self, memory: EmbeddingMemory, embedder_config: Any, distinct: bool = False):
+        _check_distinct(memory, distinct)
         self.memory = memory
         self.embedder_config = embedder_config
+        self.distinct = bool(distinct)
 
     async def _calculate_batch_similarities(self, chunk_embeddings, neo4j_handler=None
                                             ) -> List[List[Tuple[str, float]]]:
         try:
             return batch_similarities(self.memory, chunk_embeddings,
-                                      self.embedder_config.top_k_chunk_with_batch_similarity)
+                                      self.embedder_config.top_k_chunk_with_batch_similarity,
+                                      distinct=getattr(self, "distinct", False))
         except _lib.VidmemError as e:
             if e.code == _lib.VM_ERR_INVALID:
                 raise
@@ -116,13 +131,15 @@ class HipVectorSearch:
     """Mixin / stand-alone object for HybridRetriever's vector leg."""
 
     def __init__(self, memory: EmbeddingMemory, embedder: Any, config: Any, *, score_mode: int,
-                 min_score: float = 0.3, splitter: Optional[Callable[[str], List[str]]] = None):
+                 min_score: float = 0.3, splitter: Optional[Callable[[str], List[str]]] = None, distinct: bool = False):
         """``score_mode`` is REQUIRED (keyword): the reference filters on Neo4j's
         ``vector.similarity.cosine(...) > 0.3`` (src/pipeline/retriever_hybrid.py:296-298), a third-party function of an
         unpinned server image whose value may be the raw cosine or its [0,1] mapping (1+cos)/2 - with the literal 0.3
         meaning cos > 0.3 in one case and cos > -0.4 in the other.  Nothing in the reference pins it (parity unpinned,
         SURVEY.md 8 a10), so the integrator states which one their deployment had: ``_lib.VM_SCORE_RAW`` or
-        ``_lib.VM_SCORE_UNIT_INTERVAL``; ``min_score`` (default: the reference's literal) is compared AFTER the mapping."""
+        ``_lib.VM_SCORE_UNIT_INTERVAL``; ``min_score`` (default: the reference's literal) is compared AFTER the mapping.
+        ``distinct=True`` (grouped memory only, else ValueError): at most one hit per chunk - ``top_k_chunks`` distinct
+        chunks, each represented by its best frame (EmbeddingMemory.topk_grouped)."""
         if score_mode not in (_lib.VM_SCORE_RAW, _lib.VM_SCORE_UNIT_INTERVAL):
             raise ValueError("score_mode must be VM_SCORE_RAW or VM_SCORE_UNIT_INTERVAL")
         # an embedder that states its width (HipTextEmbedder, FrameEncoder-backed ones) must match the memory's rows: a
@@ -131,14 +148,20 @@ class HipVectorSearch:
         if out_dim is not None and int(out_dim) != int(memory.dim):
             raise ValueError(f"embedder out_dim {out_dim} != memory.dim {memory.dim}: build the memory with the matching "
                              "image encoder (text questions: encoder.arch clip_l14_336_joint)")
+        _check_distinct(memory, distinct)
         self.memory, self.embedder, self.config = memory, embedder, config
+        self.distinct = bool(distinct)
         self.min_score, self.score_mode, self.splitter = min_score, score_mode, splitter
 
     async def _vector_search_chunks(self, session, query) -> List[Dict[str, Any]]:
         try:
             query_embedding = await self.embedder.aembed_query(query)
-            scores, rows = self.memory.topk([query_embedding], self.config.top_k_chunks, min_score=self.min_score,
-                                            score_mode=self.score_mode)
+            if self.distinct:
+                scores, rows, _ = self.memory.topk_grouped([query_embedding], self.config.top_k_chunks,
+                                                           min_score=self.min_score, score_mode=self.score_mode)
+            else:
+                scores, rows = self.memory.topk([query_embedding], self.config.top_k_chunks, min_score=self.min_score,
+                                                score_mode=self.score_mode)
             chunks = []
             for r, s in zip(rows[0].cpu().tolist(), scores[0].cpu().tolist()):
                 if r < 0:
