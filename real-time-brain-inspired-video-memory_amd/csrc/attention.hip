@@ -20,8 +20,6 @@ namespace {
 
 typedef short s4v __attribute__((__vector_size__(4 * sizeof(short))));
 typedef __attribute__((address_space(3))) s4v *lds_s4v_ptr;
-typedef __attribute__((address_space(3))) void *lds_ptr_t;
-typedef const __attribute__((address_space(1))) void *gbl_ptr_t;
 typedef const __attribute__((address_space(3))) char *lds_cptr;   // 32-bit LDS byte address that stays one through asm
 
 // "Does any of the eight scores of a 32-key step exceed the row's reference?" as eight compares OR-ed on the scalar

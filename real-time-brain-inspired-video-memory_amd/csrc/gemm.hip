@@ -34,9 +34,6 @@ namespace {
 constexpr int BK = 64;
 constexpr int HALF_BYTES = 128 * BK * 2;  // 128 rows x 64 k, 16 KiB
 
-typedef __attribute__((address_space(3))) void *lds_ptr_t;
-typedef const __attribute__((address_space(1))) void *gbl_ptr_t;
-
 // x * sigmoid(1.702 x) with one v_exp_f32 and one v_rcp_f32 (the IEEE division sequence cost ~10 more instructions per
 // element; 1 ulp of the reciprocal is far below the 16-bit output's rounding)
 __device__ __forceinline__ float quick_gelu(float x) {
@@ -249,7 +246,6 @@ __device__ __forceinline__ void epilogue_row(const GemmArgs &g, const f32x4 (&a)
 // not get that wait)  The asm reads carry no dependency the compiler can see, hence the explicit
 // s_waitcnt lgkmcnt with the destination registers as "+v" operands before each first use.
 // ---------------------------------------------------------------------------------------------------------------
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 template <int OFF>
 __device__ __forceinline__ void lds_rd128(u32x4 &d, unsigned addr) {
@@ -557,11 +553,6 @@ __global__ void __launch_bounds__(512, 1) gemm256_kernel(GemmArgs g) {
 // the epilogue's stores are left in flight (counted vmcnt) while the next tile's MFMAs start, so neither the
 // prologue latency nor the output write-back leaves the matrix pipe idle between tiles.
 // ---------------------------------------------------------------------------------------------------------------
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
 template <int DT, int EPI, int ABL = 0>  // ABL (developer ablation): 8 = no global stores, 16 = no epilogue at all
 __global__ void __launch_bounds__(512, 1) gemm256p_kernel(GemmArgs g) {
     using E = vm_elem<DT>;

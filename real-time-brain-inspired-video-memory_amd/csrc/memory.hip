@@ -1,6 +1,7 @@
 // Embedding memory: resident [capacity, D] 16-bit rows + exact fp64 norms + fp32 reciprocal norms.
 // Replaces the Chunk.embedding property store of the reference
 // (src/components/neo4j_handler.py:229-242 append, src/components/pre_llm_injector.py:390-412 read-back).
+#include "topk_common.h"
 #include "vm_internal.h"
 
 // One block per appended row: coalesced 16-B copy of the row into its slot, then lane 0 accumulates the
@@ -23,18 +24,7 @@ __global__ void __launch_bounds__(128) memory_append_kernel(const uint16_t *__re
     uint4 *d4 = reinterpret_cast<uint4 *>(rows + (size_t)slot * D);
     for (int i = threadIdx.x; i < D / 8; i += blockDim.x) d4[i] = s4[i];
     if (threadIdx.x == 0) {
-        const uint16_t *s = src + (size_t)b * D;
-        double acc = 0.0;
-        for (int i = 0; i < D; i += 8) {
-            uint4 v = *reinterpret_cast<const uint4 *>(s + i);
-            const uint16_t *e = reinterpret_cast<const uint16_t *>(&v);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                double x = vm_elem<DT>::to_double(e[j]);
-                acc = __dadd_rn(acc, __dmul_rn(x, x));
-            }
-        }
-        double nrm = __dsqrt_rn(acc);
+        const double nrm = __dsqrt_rn(ref_sumsq<DT>(src + (size_t)b * D, D));
         norm64[slot] = nrm;
         rnorm32[slot] = nrm > 0.0 ? (float)(1.0 / nrm) : 0.0f;
     }

@@ -18,6 +18,7 @@
 //              The result is certified when the exact k-th score clears the best rejected fp32 score by more
 //              than the fp32 error bound; otherwise the query is counted in *uncertified and the caller runs
 //              the exhaustive kernel (topk_exact.hip).
+#include "topk_common.h"
 #include "vm_internal.h"
 
 #include <climits>
@@ -27,10 +28,6 @@ namespace {
 constexpr int SCAN_THREADS = 512;
 constexpr int FIN_THREADS = 256;
 constexpr int MAX_BLOCKS = 512;  // lists per query the finalize kernel accepts
-
-__device__ __forceinline__ bool better(float s1, int o1, float s2, int o2) {
-    return s1 > s2 || (s1 == s2 && o1 < o2);
-}
 
 // Sorted (best first) register list, branch-free insert with compile-time indices only.
 template <int KL>
@@ -506,6 +503,8 @@ __global__ void __launch_bounds__(FIN_THREADS)
     //    partial sums).  The TPC threads take interleaved 16-byte chunks and combine with shuffles.
     //  * otherwise (bf16, or large norms): one thread sums strictly left to right, as the reference does.
     // The query norm is handled the same way by the last wave's first TPC threads' neighbours (slot KL).
+    // The left-to-right branches, the guard and the score mapping below are topk_common.h's ref_dot, ref_sumsq,
+    // ref_cosine, shown_score and passes_min written out: called as helpers they change this kernel's instructions.
     const uint16_t *qv = ql;  // LDS copy of the query row
     // bf16 has no order-free fast path (its products span too many binades), so every candidate is summed strictly
     // left to right by one thread.  Fed from global memory that chain waits one load round trip per 32 elements
@@ -518,8 +517,7 @@ __global__ void __launch_bounds__(FIN_THREADS)
         const int cpr = D / 8;
         for (int idx = tid; idx < nfin * cpr; idx += FIN_THREADS) {
             const int c = idx / cpr, ch = idx - c * cpr;
-            int64_t p = fo[c] + rv.head;
-            if (p >= rv.cap) p -= rv.cap;
+            const int64_t p = slot_of(rv, fo[c]);
             *reinterpret_cast<uint4 *>(rows_l + (size_t)c * RS + ch * 8) =
                 *reinterpret_cast<const uint4 *>(mem + (size_t)p * D + ch * 8);
         }
@@ -530,7 +528,7 @@ __global__ void __launch_bounds__(FIN_THREADS)
     {
         const int c = tid / TPC, sub = tid % TPC;
         const bool live = c < nfin;
-        int64_t p = live ? fo[c] + rv.head : 0;
+        int64_t p = live ? fo[c] + rv.head : 0;  // slot_of written out, as the loops below
         if (p >= rv.cap) p -= rv.cap;
         const uint16_t *mv = STAGED ? rows_l + (size_t)(live ? c : 0) * RS : mem + (size_t)p * D;
         const bool any_order_exact = (DT == VM_F16) && live && (qnorm_fast * norm64[p] < 32.0);
@@ -601,9 +599,7 @@ __global__ void __launch_bounds__(FIN_THREADS)
     __syncthreads();
     const double qn = qnorm_sh;
     if (tid < nfin) {
-        int64_t p = fo[tid] + rv.head;
-        if (p >= rv.cap) p -= rv.cap;
-        const double mn = norm64[p];
+        const double mn = norm64[slot_of(rv, fo[tid])];
         // src/components/pre_llm_injector.py:385-388
         ex[tid] = (qn == 0.0 || mn == 0.0) ? 0.0 : __ddiv_rn(ex[tid], __dmul_rn(qn, mn));
     }
@@ -632,7 +628,7 @@ __global__ void __launch_bounds__(FIN_THREADS)
                 if (qflags) qflags[q] = VM_FLAG_OVERFLOW;
             } else if (!all_rows_are_candidates && qn != 0.0) {
                 const float bound_f32 = fs[KL - 1];  // best possible fp32 score of a rejected row (x 1/||q||)
-                const double eps = 2.0 * (double)(D + 8) * 5.9604644775390625e-08;  // 2*(D+8)*2^-24
+                const double eps = cert_eps(D);
                 const double reject = (double)bound_f32 / qn + eps;
                 if (!(e > reject)) {
                     if (uncertified) atomicAdd(uncertified, 1);
@@ -901,8 +897,7 @@ extern "C" int vm_topk_cosine(vm_memory *m, const void *queries, int Q, int k, i
         return vm_fail(ctx, VM_ERR_INVALID, "vm_topk_cosine: bad arguments (Q=%d k=%d)", Q, k);
     if (k > 58)
         return vm_fail(ctx, VM_ERR_UNSUPPORTED, "vm_topk_cosine: k=%d > 58; use vm_topk_cosine_exact", k);
-    if (score_mode != VM_SCORE_RAW && score_mode != VM_SCORE_UNIT_INTERVAL)
-        return vm_fail(ctx, VM_ERR_INVALID, "bad score_mode %d", score_mode);
+    if (int rc = vm_check_score_mode(ctx, score_mode)) return rc;
     const ScanPlan p = make_plan(m, Q, k);
     const size_t need = 2 * p.part_bytes + vm_align_up((size_t)p.q_pad * 8, 256) +
                         (p.emit ? vm_topk_emit_workspace_bytes(p.q_pad) : 0);

@@ -18,6 +18,7 @@
 //     select + rank count of the survivors), which topk.hip's finalize kernel re-scores exactly and certifies as
 //     before.  A query with more candidates than the buffer holds is marked and goes through the exhaustive redo
 //     (topk_exact.hip): never a wrong answer, only a slower one.
+#include "topk_common.h"
 #include "vm_internal.h"
 
 #include <climits>
@@ -34,32 +35,17 @@ constexpr int EM_WBUF = 128;       // entries of a wave's LDS emission buffer (f
 constexpr int CP_THREADS = 256;
 constexpr int CP_PER_THREAD = VM_EMIT_CAP / CP_THREADS;
 
-typedef __attribute__((address_space(3))) void *lds_ptr_t;
-typedef const __attribute__((address_space(1))) void *gbl_ptr_t;
-
-__device__ __forceinline__ bool better(float s1, int o1, float s2, int o2) {
-    return s1 > s2 || (s1 == s2 && o1 < o2);
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
 // LDS accesses of the hot loop are inline asm: hipcc (ROCm 7.2) puts `s_waitcnt vmcnt(0)` in front of every LDS
 // access it can see while an LDS-DMA is in flight (an LDS-DMA is a pending LDS write to its alias analysis), which
 // drained the three-tile prefetch once per tile (3 us per tile instead of 1).  The hand-placed counted waits below
 // order every read behind the DMA that feeds it: vmcnt before the tile's barrier, lgkmcnt before each MFMA batch.
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));  // a native vector: asm operands must be register values
+// No "memory" clobber, unlike topk_gscan.hip's lds_rd128: part of how this loop is scheduled (keep the two apart).
 template <int OFF>
 __device__ __forceinline__ void lds_read_b128(u32x4 &dst, unsigned addr) {
     asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF));
 }
 // wait for the batch (a, b, c, d): the statement names what it guards, so no consumer is scheduled above it
 #define VM_WAIT_LGKM4(N, a, b, c, d) asm volatile("s_waitcnt lgkmcnt(" #N ")" : "+v"(a), "+v"(b), "+v"(c), "+v"(d))
-__device__ __forceinline__ void lds_write_b32(unsigned addr, unsigned v) {
-    asm volatile("ds_write_b32 %0, %1" ::"v"(addr), "v"(v) : "memory");
-}
 
 // KS = D / 128.  STAGES tiles of [32 rows][D] 16-bit + 32 reciprocal norms each, then the emission buffers.
 // NG = 16-query groups per wave: 1 (<= 128 queries per superblock: HBM-bound) or 2 (<= 256: every A fragment read from

@@ -2,6 +2,7 @@
 // (src/components/pre_llm_injector.py:374-388: three left-to-right fp64 sums, sqrt, guards, one division),
 // then a stable top-k.  Used (a) as the fallback for queries the fast scan cannot certify, (b) for the
 // post-compression filter (src/pipeline/retriever_hybrid.py:494-504), (c) as an on-device checker.
+#include "topk_common.h"
 #include "vm_internal.h"
 
 namespace {
@@ -21,20 +22,11 @@ __global__ void __launch_bounds__(256)
     for (int i = threadIdx.x; i < D / 8; i += blockDim.x)
         reinterpret_cast<uint4 *>(ql)[i] = reinterpret_cast<const uint4 *>(qv)[i];
     __syncthreads();
-    if (threadIdx.x == 0) {
-        double nq = 0.0;
-        for (int i = 0; i < D; ++i) {
-            const double x = E::to_double(ql[i]);
-            nq = __dadd_rn(nq, __dmul_rn(x, x));
-        }
-        qnorm_sh = __dsqrt_rn(nq);
-    }
+    if (threadIdx.x == 0) qnorm_sh = __dsqrt_rn(ref_sumsq<DT>(ql, D));
     __syncthreads();
     const int64_t o = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (o >= n) return;
-    int64_t p = o + head;
-    if (p >= cap) p -= cap;
-    const uint16_t *mv = rows + (size_t)p * D;
+    const uint16_t *mv = rows + (size_t)slot_of(RingView{n, head, 0, cap}, o) * D;
     double dot = 0.0, nb = 0.0;
     for (int i = 0; i < D; i += 8) {
         const uint4 b = *reinterpret_cast<const uint4 *>(mv + i);
@@ -48,8 +40,7 @@ __global__ void __launch_bounds__(256)
             nb = __dadd_rn(nb, __dmul_rn(y, y));
         }
     }
-    const double qn = qnorm_sh, mn = __dsqrt_rn(nb);
-    out[(size_t)q * out_stride + o] = (qn == 0.0 || mn == 0.0) ? 0.0 : __ddiv_rn(dot, __dmul_rn(qn, mn));
+    out[(size_t)q * out_stride + o] = ref_cosine(dot, qnorm_sh, __dsqrt_rn(nb));
 }
 
 // fp32 operands (vm_cosine_exact, VM_F32): same arithmetic on the values as they are - every fp32 is exact in fp64.
@@ -69,7 +60,7 @@ __global__ void __launch_bounds__(256)
         nb = __dadd_rn(nb, __dmul_rn(y, y));
     }
     const double qn = __dsqrt_rn(na), mn = __dsqrt_rn(nb);
-    out[(size_t)q * n + o] = (qn == 0.0 || mn == 0.0) ? 0.0 : __ddiv_rn(dot, __dmul_rn(qn, mn));
+    out[(size_t)q * n + o] = ref_cosine(dot, qn, mn);
 }
 
 // One block per query: k rounds, each finds the best key strictly after the previous winner in
@@ -123,7 +114,7 @@ __global__ void __launch_bounds__(256)
         if (tid == 0) {
             double shown = prev_s;
             bool ok = prev_i >= 0;
-            if (ok) {
+            if (ok) {  // shown_score / passes_min (topk_common.h), written out: the helpers change this kernel
                 if (score_mode == VM_SCORE_UNIT_INTERVAL) shown = __ddiv_rn(__dadd_rn(1.0, prev_s), 2.0);
                 if (use_min && !(shown > min_score)) ok = false;
             }
@@ -149,73 +140,6 @@ constexpr int REDO_THREADS = 256;
 constexpr int REDO_CHUNK = 2048;  // scores held in LDS per selection pass
 constexpr int REDO_KMAX = 64;
 
-// k rounds of block-wide arg-best over `n` (score, order) candidates read through `get`, strictly after the
-// previous winner in (score desc, order asc): a stable top-k without sorting.  Winners go to out_s / out_o (LDS),
-// -inf / -1 padded.  All threads of the block must call it.
-template <typename Get>
-__device__ __forceinline__ void block_select(int n, int k, Get get, double *out_s, int64_t *out_o, double *red_s,
-                                             int64_t *red_o) {
-    const int tid = threadIdx.x;
-    double prev_s = INFINITY;
-    int64_t prev_o = -1;
-    for (int r = 0; r < k; ++r) {
-        double bs = -INFINITY;
-        int64_t bo = -1;
-        for (int i = tid; i < n; i += REDO_THREADS) {
-            double v;
-            int64_t o;
-            get(i, v, o);
-            if (o < 0) continue;
-            const bool after_prev = v < prev_s || (v == prev_s && o > prev_o);
-            const bool beats = bo < 0 || v > bs || (v == bs && o < bo);
-            if (after_prev && beats) {
-                bs = v;
-                bo = o;
-            }
-        }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const double s2 = __shfl_xor(bs, off, 64);
-            const int64_t o2 = __shfl_xor(bo, off, 64);
-            if (o2 >= 0 && (bo < 0 || s2 > bs || (s2 == bs && o2 < bo))) {
-                bs = s2;
-                bo = o2;
-            }
-        }
-        __syncthreads();  // previous round's readers of red_* are done
-        if ((tid & 63) == 0) {
-            red_s[tid >> 6] = bs;
-            red_o[tid >> 6] = bo;
-        }
-        __syncthreads();
-        bs = red_s[0];
-        bo = red_o[0];
-#pragma unroll
-        for (int w = 1; w < REDO_THREADS / 64; ++w) {
-            const double s2 = red_s[w];
-            const int64_t o2 = red_o[w];
-            if (o2 >= 0 && (bo < 0 || s2 > bs || (s2 == bs && o2 < bo))) {
-                bs = s2;
-                bo = o2;
-            }
-        }
-        if (tid == 0) {
-            out_s[r] = bo >= 0 ? bs : -INFINITY;
-            out_o[r] = bo;
-        }
-        prev_s = bs;
-        prev_o = bo;
-        if (bo < 0) {  // exhausted (uniform): pad the rest
-            for (int r2 = r + 1 + tid; r2 < k; r2 += REDO_THREADS) {
-                out_s[r2] = -INFINITY;
-                out_o[r2] = -1;
-            }
-            break;
-        }
-    }
-    __syncthreads();
-}
-
 // grid = nblk row blocks; every block walks all Q flags and, for each flagged query, scores its contiguous slice of
 // age orders exactly as the reference does (src/components/pre_llm_injector.py:374-388) and keeps the slice's
 // stable top-k: part[(block * Q + q) * k + i] = {score fp64, age order int64}.
@@ -225,7 +149,6 @@ __global__ void __launch_bounds__(REDO_THREADS)
                           const double *__restrict__ norm64, const int64_t *__restrict__ d_total, int64_t cap,
                           int ring, int D, int Q, int k, const int32_t *__restrict__ flags,
                           double *__restrict__ part_s, int64_t *__restrict__ part_o) {
-    using E = vm_elem<DT>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     uint16_t *ql = reinterpret_cast<uint16_t *>(smem);                       // [D]
     double *sc = reinterpret_cast<double *>(smem + (size_t)D * 2);           // [REDO_CHUNK]
@@ -253,38 +176,19 @@ __global__ void __launch_bounds__(REDO_THREADS)
             run_o[tid] = -1;
         }
         __syncthreads();
-        if (tid == 0) {
-            double nq = 0.0;
-            for (int i = 0; i < D; ++i) {
-                const double x = E::to_double(ql[i]);
-                nq = __dadd_rn(nq, __dmul_rn(x, x));
-            }
-            qnorm_sh = __dsqrt_rn(nq);
-        }
+        if (tid == 0) qnorm_sh = __dsqrt_rn(ref_sumsq<DT>(ql, D));
         __syncthreads();
         const double qn = qnorm_sh;
         for (int64_t c0 = lo; c0 < hi; c0 += REDO_CHUNK) {
             const int cn = (int)(hi - c0 < REDO_CHUNK ? hi - c0 : REDO_CHUNK);
             for (int i = tid; i < cn; i += REDO_THREADS) {
-                int64_t p = c0 + i + rv.head;
-                if (p >= rv.cap) p -= rv.cap;
-                const uint16_t *mv = rows + (size_t)p * D;
-                double dot = 0.0;
-                for (int e0 = 0; e0 < D; e0 += 8) {
-                    const uint4 b = *reinterpret_cast<const uint4 *>(mv + e0);
-                    const uint4 a = *reinterpret_cast<const uint4 *>(ql + e0);
-                    const uint16_t *ae = reinterpret_cast<const uint16_t *>(&a);
-                    const uint16_t *be = reinterpret_cast<const uint16_t *>(&b);
-#pragma unroll
-                    for (int j = 0; j < 8; ++j)
-                        dot = __dadd_rn(dot, __dmul_rn(E::to_double(ae[j]), E::to_double(be[j])));
-                }
-                const double mn = norm64[p];  // the reference's norm of the stored row, computed at append
-                sc[i] = (qn == 0.0 || mn == 0.0) ? 0.0 : __ddiv_rn(dot, __dmul_rn(qn, mn));
+                const int64_t p = slot_of(rv, c0 + i);
+                // norm64: the reference's norm of the stored row, computed at append
+                sc[i] = ref_cosine(ref_dot<DT>(ql, rows + (size_t)p * D, D), qn, norm64[p]);
             }
             __syncthreads();
             // candidates = this chunk's scores followed by the running list
-            block_select(cn + k, k,
+            block_select<REDO_THREADS>(cn + k, k,
                          [&](int i, double &v, int64_t &o) {
                              if (i < cn) {
                                  v = sc[i];
@@ -321,7 +225,7 @@ __global__ void __launch_bounds__(REDO_THREADS)
     const int q = blockIdx.x, tid = threadIdx.x;
     if (flags[q] == 0) return;
     const RingView rv = ring_view(*d_total, cap, ring);
-    block_select(nblk * k, k,
+    block_select<REDO_THREADS>(nblk * k, k,
                  [&](int i, double &v, int64_t &o) {
                      const int b = i / k, e = i - b * k;
                      v = part_s[((size_t)b * Q + q) * k + e];
@@ -332,7 +236,7 @@ __global__ void __launch_bounds__(REDO_THREADS)
         const int64_t o = win_o[tid];
         double shown = win_s[tid];
         bool ok = o >= 0;
-        if (ok) {
+        if (ok) {  // shown_score / passes_min (topk_common.h), written out: the helpers change this kernel
             if (score_mode == VM_SCORE_UNIT_INTERVAL) shown = __ddiv_rn(__dadd_rn(1.0, shown), 2.0);
             if (use_min && !(shown > min_score)) ok = false;
         }
@@ -443,8 +347,7 @@ extern "C" int vm_topk_redo_flagged(vm_memory *m, const void *queries, int Q, in
     if (!queries || !out_scores || !out_rows || !query_flags || Q <= 0 || k <= 0)
         return vm_fail(ctx, VM_ERR_INVALID, "vm_topk_redo_flagged: bad arguments");
     if (k > REDO_KMAX) return vm_fail(ctx, VM_ERR_UNSUPPORTED, "vm_topk_redo_flagged: k=%d > %d", k, REDO_KMAX);
-    if (score_mode != VM_SCORE_RAW && score_mode != VM_SCORE_UNIT_INTERVAL)
-        return vm_fail(ctx, VM_ERR_INVALID, "bad score_mode %d", score_mode);
+    if (int rc = vm_check_score_mode(ctx, score_mode)) return rc;
     const int nblk = redo_blocks(m);
     const size_t need = (size_t)nblk * Q * k * 16;
     if (!workspace || workspace_bytes < need)

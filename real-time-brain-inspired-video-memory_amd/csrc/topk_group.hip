@@ -14,6 +14,7 @@
 //   redo     : flagged queries (gap or candidate-row overflow) scored exhaustively, group-aligned row slices per
 //              block, segmented max in LDS, stable top-k per slice, merge.  Reads flags and counts on the device.
 // Every launch reads the row count from the device and sizes its grid from the capacity: capturable.
+#include "topk_common.h"
 #include "vm_internal.h"
 
 #include <climits>
@@ -56,10 +57,6 @@ struct GView {
     RingView rv;
     int64_t ord0, ng;
 };
-__device__ __forceinline__ int64_t slot_of(const RingView &rv, int64_t o) {
-    const int64_t p = o + rv.head;
-    return p >= rv.cap ? p - rv.cap : p;
-}
 __device__ __forceinline__ GView group_view(const int64_t *d_total, int64_t cap, int ring, const int64_t *gord) {
     GView g;
     g.rv = ring_view(*d_total, cap, ring);
@@ -72,7 +69,8 @@ __device__ __forceinline__ GView group_view(const int64_t *d_total, int64_t cap,
     return g;
 }
 
-// the exact reference cosine of the query staged in LDS (ql) and the row in slot p, strictly left to right
+// the exact reference cosine of the query staged in LDS (ql) and the row in slot p, strictly left to right.  The loops
+// here are topk_common.h's ref_dot and ref_sumsq written out: called as helpers they change the finalize's instructions.
 template <int DT>
 __device__ __forceinline__ double exact_score(const uint16_t *ql, double qn, const uint16_t *__restrict__ mem,
                                               const double *__restrict__ norm64, int64_t p, int D) {
@@ -93,7 +91,7 @@ __device__ __forceinline__ double exact_score(const uint16_t *ql, double qn, con
         }
     }
     const double mn = norm64[p];  // the reference's norm of the stored row, computed at append
-    return (qn == 0.0 || mn == 0.0) ? 0.0 : __ddiv_rn(dot, __dmul_rn(qn, mn));
+    return ref_cosine(dot, qn, mn);
 }
 
 template <int DT>
@@ -112,9 +110,6 @@ __device__ __forceinline__ double exact_qnorm(const uint16_t *ql, int D) {
     return __dsqrt_rn(nq);
 }
 
-__device__ __forceinline__ double shown_score(double e, int score_mode) {
-    return score_mode == VM_SCORE_UNIT_INTERVAL ? __ddiv_rn(__dadd_rn(1.0, e), 2.0) : e;
-}
 
 // ---- table -------------------------------------------------------------------------------------------------
 // first_o[g] = age order of the first live row of live group g (g = ordinal - ord0), first_o[ng] = n; F[0, Q*ng) = 0;
@@ -620,7 +615,7 @@ __global__ void __launch_bounds__(GF_THREADS)
         rk[tid] = r;
         if (r < k) {
             const double shown = shown_score(e, score_mode);
-            const bool pass = !use_min || shown > min_score;
+            const bool pass = passes_min(use_min, shown, min_score);
             out_scores[(size_t)q * k + r] = pass ? shown : 0.0;
             out_rows[(size_t)q * k + r] = pass ? gv.rv.base + o : -1;
             if (out_keys) out_keys[(size_t)q * k + r] = pass ? gkey[slot_of(gv.rv, o)] : -1;
@@ -628,7 +623,7 @@ __global__ void __launch_bounds__(GF_THREADS)
         // certification: the exact k-th group score against the best fp32 max of a group that never became a candidate
         const int kth = (k < nc ? k : nc) - 1;
         if (r == kth && C > M && qn != 0.0) {
-            const double eps = 2.0 * (double)(D + 8) * 5.9604644775390625e-08;  // 2*(D+8)*2^-24, topk.hip
+            const double eps = cert_eps(D);
             const double reject = (double)dekey32(sk[M]) / qn + eps;
             if (!(e > reject)) flag_sh = VM_FLAG_GAP;
         }
@@ -647,72 +642,6 @@ __global__ void __launch_bounds__(GF_THREADS)
 }
 
 // ---- redo --------------------------------------------------------------------------------------------------
-// k rounds of block-wide arg-best over n (score, order) candidates read through `get`, strictly after the previous
-// winner in (score desc, order asc) - topk_exact.hip's block_select for GR_THREADS threads.
-template <typename Get>
-__device__ __forceinline__ void gblock_select(int n, int k, Get get, double *out_s, int64_t *out_o, double *red_s,
-                                              int64_t *red_o) {
-    const int tid = threadIdx.x;
-    double prev_s = INFINITY;
-    int64_t prev_o = -1;
-    for (int r = 0; r < k; ++r) {
-        double bs = -INFINITY;
-        int64_t bo = -1;
-        for (int i = tid; i < n; i += GR_THREADS) {
-            double v;
-            int64_t o;
-            get(i, v, o);
-            if (o < 0) continue;
-            const bool after_prev = v < prev_s || (v == prev_s && o > prev_o);
-            const bool beats = bo < 0 || v > bs || (v == bs && o < bo);
-            if (after_prev && beats) {
-                bs = v;
-                bo = o;
-            }
-        }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const double s2 = __shfl_xor(bs, off, 64);
-            const int64_t o2 = __shfl_xor(bo, off, 64);
-            if (o2 >= 0 && (bo < 0 || s2 > bs || (s2 == bs && o2 < bo))) {
-                bs = s2;
-                bo = o2;
-            }
-        }
-        __syncthreads();
-        if ((tid & 63) == 0) {
-            red_s[tid >> 6] = bs;
-            red_o[tid >> 6] = bo;
-        }
-        __syncthreads();
-        bs = red_s[0];
-        bo = red_o[0];
-#pragma unroll
-        for (int w = 1; w < GR_THREADS / 64; ++w) {
-            const double s2 = red_s[w];
-            const int64_t o2 = red_o[w];
-            if (o2 >= 0 && (bo < 0 || s2 > bs || (s2 == bs && o2 < bo))) {
-                bs = s2;
-                bo = o2;
-            }
-        }
-        if (tid == 0) {
-            out_s[r] = bo >= 0 ? bs : -INFINITY;
-            out_o[r] = bo;
-        }
-        prev_s = bs;
-        prev_o = bo;
-        if (bo < 0) {
-            for (int r2 = r + 1 + tid; r2 < k; r2 += GR_THREADS) {
-                out_s[r2] = -INFINITY;
-                out_o[r2] = -1;
-            }
-            break;
-        }
-    }
-    __syncthreads();
-}
-
 // grid = nblk.  Block b owns the groups whose first live row lies in its even slice [lo, hi) of age orders, so every
 // group is scored whole by one block (a group longer than a slice makes its block longer).  Per flagged query: rows in
 // chunks of GR_CHUNK, exact scores, per-chunk group max + lowest row by LDS atomics, the chunk's last group carried into
@@ -814,7 +743,7 @@ __global__ void __launch_bounds__(GR_THREADS)
             __syncthreads();
             const int nloc = last_chunk ? nl : nl - 1;
             const int ncar = carry_cand;
-            gblock_select(nloc + ncar + k, k,
+            block_select<GR_THREADS>(nloc + ncar + k, k,
                           [&](int i, double &v, int64_t &o) {
                               if (i < nloc) {
                                   v = dekey64(gmax[i]);
@@ -862,7 +791,7 @@ __global__ void __launch_bounds__(GR_THREADS)
     const int q = blockIdx.x, tid = threadIdx.x;
     if (flags[q] == 0) return;
     const RingView rv = ring_view(*d_total, cap, ring);
-    gblock_select(nblk * k, k,
+    block_select<GR_THREADS>(nblk * k, k,
                   [&](int i, double &v, int64_t &o) {
                       const int b = i / k, e = i - b * k;
                       v = part_s[((size_t)b * Q + q) * k + e];
@@ -875,7 +804,7 @@ __global__ void __launch_bounds__(GR_THREADS)
         bool ok = o >= 0;
         if (ok) {
             shown = shown_score(shown, score_mode);
-            if (use_min && !(shown > min_score)) ok = false;
+            ok = passes_min(use_min, shown, min_score);
         }
         out_scores[(size_t)q * k + tid] = ok ? shown : 0.0;
         out_rows[(size_t)q * k + tid] = ok ? rv.base + o : -1;
@@ -938,8 +867,7 @@ int group_check(vm_memory *m, const void *queries, int Q, int k, int score_mode,
     if (!queries || !out_scores || !out_rows || Q <= 0 || k <= 0)
         return vm_fail(ctx, VM_ERR_INVALID, "%s: bad arguments", who);
     if (k > GKMAX) return vm_fail(ctx, VM_ERR_UNSUPPORTED, "%s: k=%d > %d", who, k, GKMAX);
-    if (score_mode != VM_SCORE_RAW && score_mode != VM_SCORE_UNIT_INTERVAL)
-        return vm_fail(ctx, VM_ERR_INVALID, "bad score_mode %d", score_mode);
+    if (int rc = vm_check_score_mode(ctx, score_mode)) return rc;
     const size_t need = group_plan(m, Q, k).total;
     if (!workspace || workspace_bytes < need)
         return vm_fail(ctx, VM_ERR_NOMEM, "%s: workspace %zu < %zu", who, workspace_bytes, need);

@@ -33,9 +33,6 @@ constexpr int GS_TAB = 2048;                   // per tile parity: 256 reciproca
 constexpr int GS_WBUF = 128;                   // entries of a wave's emission buffer
 constexpr int GS_LDS = GS_STAGE + 2 * GS_TAB + 8 * GS_WBUF * 12;
 
-typedef __attribute__((address_space(3))) void *lds_ptr_t;
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 struct GscanArgs {
     const uint16_t *mem;       // [cap_pad, D]
     const float *rnorm;        // [cap_pad]
@@ -52,10 +49,6 @@ struct GscanArgs {
     int QX;
 };
 
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 template <int OFF>
 __device__ __forceinline__ void lds_rd128(u32x4 &d, unsigned addr) {
     asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "n"(OFF) : "memory");
@@ -63,9 +56,6 @@ __device__ __forceinline__ void lds_rd128(u32x4 &d, unsigned addr) {
 template <int OFF>
 __device__ __forceinline__ void lds_rd32(unsigned &d, unsigned addr) {
     asm volatile("ds_read_b32 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "n"(OFF) : "memory");
-}
-__device__ __forceinline__ void lds_wr32(unsigned addr, unsigned v) {
-    asm volatile("ds_write_b32 %0, %1" ::"v"(addr), "v"(v) : "memory");
 }
 
 template <int DT>
@@ -263,9 +253,9 @@ __global__ void __launch_bounds__(512, 1) topk_gscan_kernel(GscanArgs g) {
                 if (pass) {
                     const int idx =
                         pending + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0));
-                    lds_wr32(eb0 + idx * 4, __builtin_bit_cast(unsigned, sc));
-                    lds_wr32(eb0 + (GS_WBUF + idx) * 4, (unsigned)o);
-                    lds_wr32(eb0 + (2 * GS_WBUF + idx) * 4, (unsigned)qj);
+                    lds_write_b32(eb0 + idx * 4, __builtin_bit_cast(unsigned, sc));
+                    lds_write_b32(eb0 + (GS_WBUF + idx) * 4, (unsigned)o);
+                    lds_write_b32(eb0 + (2 * GS_WBUF + idx) * 4, (unsigned)qj);
                 }
                 pending += __popcll(m);
             }

@@ -88,6 +88,26 @@ inline int vm_fail(vm_ctx *ctx, int code, const char *fmt, ...) {
 
 static inline size_t vm_align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
+// score_mode of the top-k entry points: VM_OK, or VM_ERR_INVALID for a value include/vidmem.h does not define
+inline int vm_check_score_mode(vm_ctx *ctx, int score_mode) {
+    if (score_mode != VM_SCORE_RAW && score_mode != VM_SCORE_UNIT_INTERVAL)
+        return vm_fail(ctx, VM_ERR_INVALID, "bad score_mode %d", score_mode);
+    return VM_OK;
+}
+
+// ---- inline-asm helpers of the LDS-DMA kernels (gemm, attention, topk_emit, topk_gscan) -------------------------
+typedef __attribute__((address_space(3))) void *lds_ptr_t;
+typedef const __attribute__((address_space(1))) void *gbl_ptr_t;
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));  // a native vector: asm operands must be register values
+
+template <int N>
+__device__ __forceinline__ void wait_vmcnt() {
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+__device__ __forceinline__ void lds_write_b32(unsigned addr, unsigned v) {
+    asm volatile("ds_write_b32 %0, %1" ::"v"(addr), "v"(v) : "memory");
+}
+
 // ---- 16-bit float helpers (device) ------------------------------------------------------------------------
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));

@@ -42,6 +42,11 @@ __host__ __device__ inline RingView ring_view(int64_t total, int64_t cap, int ri
     }
     return v;
 }
+// physical slot of the row of age order o (0 <= o < v.n)
+__host__ __device__ inline int64_t slot_of(const RingView &v, int64_t o) {
+    const int64_t p = o + v.head;
+    return p >= v.cap ? p - v.cap : p;
+}
 
 // The rows whose every score the cut cascade keeps in its first, DENSE pass: the NEWEST stored rows (at most 4,095 of
 // them, a whole number of 256-row panels plus the ragged end).  New rows are what a video's current frames resemble
