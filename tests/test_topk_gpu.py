@@ -13,6 +13,7 @@ import torch
 from oracle import cref
 from oracle import similarity_ref as S
 from tests.golden.make_similarity_golden import CASES, make_inputs
+from tests.topk_ref import oracle_rows_parallel as _oracle_rows_parallel
 
 pytestmark = pytest.mark.gpu
 
@@ -279,9 +280,9 @@ def test_sampled_cut_path_many_queries_bit_exact(M):
 
 
 def test_many_query_groups_bit_exact():
-    """Q = 200 at k = 10: four 64-query groups in one 1-D launch (groups of a row block renumbered onto one XCD),
-    sampled cut, cross-tile prefetch, network merges - the configuration bench.py's main leg and its Q=256 kNN batch
-    run, checked row for row and bit for bit against the C oracle."""
+    """Q = 200 at k = 10 over 70,000 x 128 rows: the emit cut cascade (csrc/topk_emit.hip) with two 16-query groups
+    per wave (NG = 2, more than 128 queries) and 8-fold pass limits - dense pass, [0, 32,768), the rest - checked row
+    for row and bit for bit against the C oracle."""
     rng = np.random.default_rng(33)
     D, M, Q, k = 128, 70_000, 200, 10
     m = torch.tensor(rng.standard_normal((M, D)), dtype=torch.float32).to(torch.float16)
@@ -359,7 +360,8 @@ def test_full_size_properties_1m_rows_bf16_k20():
     """BASELINE configs[2] size (1M x 1024 bf16, top-20): size-independent properties instead of an oracle pass -
     planted self-matches first with score 1, strictly ordered distinct rows, the returned scores are the exact
     reference cosines of the returned rows, sharding invariance (top-k(whole) == merge(top-k(halves))), agreement with
-    the exhaustive kernel on one query - for Q = 16 (list scan) and Q = 64 (emit scan)."""
+    the exhaustive kernel on one query - for Q = 16 and Q = 64, both on the emit cut cascade (k = 20 keeps 32-entry
+    lists, which vm_topk_emit_supported sends to the cascade at any query count)."""
     D, M, k = 1024, 1_000_000, 20
     g = torch.Generator(device="cuda").manual_seed(4321)
     from vidmem.memory import EmbeddingMemory, topk_merge
@@ -395,15 +397,6 @@ def test_full_size_properties_1m_rows_bf16_k20():
         s2, r2 = mem.topk(q[6:7], k, exact=True)
         assert np.array_equal(r2.cpu().numpy(), r_np[6:7]) and np.array_equal(s2.cpu().numpy(), s_np[6:7])
         assert mem.uncertified_count == 0
-
-
-def _oracle_rows_parallel(qbits, mbits, k, dtype, picks, threads=8):
-    """cref.cosine_topk for a subset of the queries, a few at a time on a thread pool (ctypes releases the GIL)."""
-    from concurrent.futures import ThreadPoolExecutor
-    groups = np.array_split(np.asarray(picks), threads)
-    with ThreadPoolExecutor(threads) as ex:
-        outs = list(ex.map(lambda g: cref.cosine_topk(qbits[g], mbits, k, dtype=dtype), groups))
-    return np.concatenate([o[0] for o in outs]), np.concatenate([o[1] for o in outs])
 
 
 def test_gemm_class_scan_7040_queries_bit_exact():
