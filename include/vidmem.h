@@ -204,6 +204,24 @@ int vm_memory_append_grouped(vm_memory *mem, const void *rows, int B, const int6
                              void *stream);
 const int64_t *vm_memory_group_keys(const vm_memory *mem);
 
+/* ---- tagged memory --------------------------------------------------------------------------------------
+ * A tagged memory carries one int64 TAG per row: which video a frame came from and when, so that one memory can hold
+ * many videos and a search can name the one it wants.  It replaces the per-graph predicate of the reference's two scans
+ * (src/pipeline/retriever_hybrid.py:295 `MATCH (c:Chunk {graph_uuid: $graph_uuid})`,
+ * src/components/pre_llm_injector.py:395-396 `WHERE c.graph_uuid = $graph_uuid`).  In a ring a row's tag lives and dies
+ * with its slot.  grouped != 0: the memory also carries group keys (vm_memory_create_grouped).
+ * vm_memory_append_tagged: tags = device int64 [B]; keys = device int64 [B] on a grouped memory (NULL there: every row
+ *   its own group, as vm_memory_append does), NULL otherwise.  Capturable like vm_memory_append (no allocation, no
+ *   sync); one launch more than on an untagged memory.
+ * vm_memory_append / vm_memory_append_grouped on a tagged memory store INT64_MIN: only a scope that starts at INT64_MIN
+ *   matches such a row.  On an untagged memory every call runs exactly the launches it ran before tags existed.
+ * vm_memory_tags: device pointer to the [capacity] tag column (slot order, like vm_memory_rows), 0 if not tagged. */
+int vm_memory_create_tagged(vm_ctx *ctx, int64_t capacity_rows, int D, int dtype, int ring, int grouped,
+                            vm_memory **out);
+int vm_memory_append_tagged(vm_memory *mem, const void *rows, int B, const int64_t *tags, const int64_t *keys,
+                            int64_t *out_first_row_host, void *stream);
+const int64_t *vm_memory_tags(const vm_memory *mem);
+
 /* ---- cosine top-k over the memory ---------------------------------------------------------------------
  * Replaces PreLLMInjector._calculate_batch_similarities + _cosine_similarity
  * (src/components/pre_llm_injector.py:346-388) and the Cypher scan of HybridRetriever._vector_search_chunks
@@ -268,6 +286,32 @@ int vm_topk_cosine_grouped(vm_memory *mem, const void *queries, int Q, int k, in
 int vm_topk_cosine_grouped_exact(vm_memory *mem, const void *queries, int Q, int k, int use_min_score,
                                  double min_score, int score_mode, double *out_scores, int64_t *out_rows,
                                  int64_t *out_keys, void *workspace, size_t workspace_bytes, void *stream);
+/* Scoped top-k: the k best rows of a tagged memory among those IN SCOPE.  scope_lo / scope_hi: device int64 [Q], one
+ * inclusive tag range per query (device arrays, so that a captured graph can be replayed with another window); row r is
+ * in query q's scope iff scope_lo[q] <= tag[r] <= scope_hi[q].  The result is the exhaustive row ranking of
+ * vm_topk_cosine (score_mode mapping, > min_score filter, score descending, row id ascending) over the in-scope rows
+ * only, first k: out_scores [Q,k] the reference's fp64 values bit for bit, out_rows [Q,k] global row ids
+ * (row_id * row_stride + row_offset), -1 / 0.0 padded.  An empty scope (lo > hi, or no live row matches) gives an
+ * all-padded row; with [INT64_MIN, INT64_MAX] the result equals vm_topk_cosine + vm_topk_redo_flagged.
+ * ALWAYS the exhaustive answer: an fp32 MFMA scan scores the 16-row tiles that hold an in-scope row (the others cost
+ * their 8-byte tags, their rows are not read), the best k + slack in-scope rows are re-scored exactly, and a query whose
+ * result cannot be proven (vm_topk_cosine's bound 2 (D + 8) 2^-24 against the best in-scope fp32 score that was not
+ * re-scored - out-of-scope rows never enter it -, or more than 8192 in-scope rows at the query's cut) is counted in
+ * *out_uncertified (may be NULL), marked in out_query_flags [Q] (vm_topk_flag; may be NULL) and redone exhaustively over
+ * its in-scope rows on the device inside the same call.
+ * No host read-back, no allocation: capturable.  1 <= k <= 64, Q >= 1; VM_ERR_INVALID on a memory that is not tagged.
+ * Workspace: vm_topk_scoped_workspace_bytes (4 x Q x capacity bytes of fp32 keys plus 64 KiB x Q and a few MB). */
+size_t vm_topk_scoped_workspace_bytes(const vm_memory *mem, int Q, int k);
+int vm_topk_cosine_scoped(vm_memory *mem, const void *queries, int Q, int k, const int64_t *scope_lo,
+                          const int64_t *scope_hi, int use_min_score, double min_score, int score_mode,
+                          int64_t row_stride, int64_t row_offset, double *out_scores, int64_t *out_rows,
+                          int32_t *out_uncertified, int32_t *out_query_flags, void *workspace, size_t workspace_bytes,
+                          void *stream);
+/* The same contract, exhaustive only: every in-scope pair scored exactly (slow; tests, and a checker). */
+int vm_topk_cosine_scoped_exact(vm_memory *mem, const void *queries, int Q, int k, const int64_t *scope_lo,
+                                const int64_t *scope_hi, int use_min_score, double min_score, int score_mode,
+                                int64_t row_stride, int64_t row_offset, double *out_scores, int64_t *out_rows,
+                                void *workspace, size_t workspace_bytes, void *stream);
 /* All-pairs exact cosine, out [Q, S] fp64: the post-compression filter of
  * src/pipeline/retriever_hybrid.py:494-504 (query vs segment embeddings) and a checker for the scan.
  * rows [S, D] dtype need not live in a vm_memory.  dtype VM_F32 takes fp32 operands: an embedder that returns fp32

@@ -37,6 +37,8 @@ SYMBOLS = [
     "vm_memory_dim", "vm_memory_reset", "vm_memory_sync", "vm_memory_rows",
     "vm_memory_create_grouped", "vm_memory_append_grouped", "vm_memory_group_keys",
     "vm_topk_grouped_workspace_bytes", "vm_topk_cosine_grouped", "vm_topk_cosine_grouped_exact",
+    "vm_memory_create_tagged", "vm_memory_append_tagged", "vm_memory_tags",
+    "vm_topk_scoped_workspace_bytes", "vm_topk_cosine_scoped", "vm_topk_cosine_scoped_exact",
     "vm_topk_workspace_bytes", "vm_topk_cosine", "vm_topk_redo_workspace_bytes", "vm_topk_redo_flagged",
     "vm_topk_exact_workspace_bytes", "vm_topk_cosine_exact",
     "vm_cosine_exact", "vm_topk_select", "vm_topk_merge", "vm_profile_enable", "vm_profile_read", "vm_profile_mask", "vm_probe_mfma",
@@ -122,6 +124,12 @@ def lib() -> C.CDLL:
         "vm_topk_grouped_workspace_bytes": (sz, [vp, i32, i32]),
         "vm_topk_cosine_grouped": (i32, [vp, vp, i32, i32, i32, f64, i32, vp, vp, vp, vp, vp, vp, sz, vp]),
         "vm_topk_cosine_grouped_exact": (i32, [vp, vp, i32, i32, i32, f64, i32, vp, vp, vp, vp, sz, vp]),
+        "vm_memory_create_tagged": (i32, [vp, i64, i32, i32, i32, i32, C.POINTER(vp)]),
+        "vm_memory_append_tagged": (i32, [vp, vp, i32, vp, vp, C.POINTER(i64), vp]),
+        "vm_memory_tags": (vp, [vp]),
+        "vm_topk_scoped_workspace_bytes": (sz, [vp, i32, i32]),
+        "vm_topk_cosine_scoped": (i32, [vp, vp, i32, i32, vp, vp, i32, f64, i32, i64, i64, vp, vp, vp, vp, vp, sz, vp]),
+        "vm_topk_cosine_scoped_exact": (i32, [vp, vp, i32, i32, vp, vp, i32, f64, i32, i64, i64, vp, vp, vp, sz, vp]),
         "vm_topk_workspace_bytes": (sz, [vp, i32, i32]),
         "vm_topk_cosine": (i32, [vp, vp, i32, i32, i32, f64, i32, i64, i64, vp, vp, vp, vp, vp, sz, vp]),
         "vm_topk_redo_workspace_bytes": (sz, [vp, i32, i32]),

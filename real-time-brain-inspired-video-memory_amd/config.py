@@ -39,6 +39,8 @@ MEMORY_DEFAULTS: Dict[str, Any] = {
     "dtype": None,           # None = the encoder's dtype
     "snapshot": None,        # path of an EmbeddingMemory.snapshot to restore from / save to
     "group_by": None,        # "chunk": a grouped memory (one group per video chunk) for distinct-chunk search; None = plain
+    "tag_by": None,          # "time": a tagged memory - every frame row carries (video, chunk start in ms), so a search can
+                             # name one video or a time window of it (memory.scope_of); None = untagged
 }
 TEXT_ENCODER_DEFAULTS: Dict[str, Any] = {
     "arch": None,            # specs.TEXT_SPECS key (clip_l14_text); None = no text encoder is built

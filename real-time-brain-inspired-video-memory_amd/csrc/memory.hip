@@ -4,6 +4,8 @@
 #include "topk_common.h"
 #include "vm_internal.h"
 
+#include <climits>
+
 // One block per appended row: coalesced 16-B copy of the row into its slot, then lane 0 accumulates the
 // reference's norm exactly: sqrt(sum(b*b)) with one rounding per product and per partial sum, left to right
 // (src/components/pre_llm_injector.py:383).  The slot comes from the DEVICE-side counter so a captured graph
@@ -85,6 +87,18 @@ __global__ void __launch_bounds__(256) memory_group_kernel(const int64_t *__rest
     }
 }
 
+// Tagged memories: the tag of every appended row, into the slot the row copy used (launched before the bump, so it
+// sees the same device row count).  tags == null (an append without tags): INT64_MIN.
+__global__ void __launch_bounds__(256) memory_tag_kernel(const int64_t *__restrict__ tags, int B,
+                                                         int64_t *__restrict__ tag, const int64_t *__restrict__ d_total,
+                                                         int64_t cap, int ring) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= B) return;
+    const int64_t id = *d_total + i;
+    const int64_t slot = ring ? id % cap : id;
+    if (slot < cap) tag[slot] = tags ? tags[i] : LLONG_MIN;
+}
+
 extern "C" int vm_memory_create(vm_ctx *ctx, int64_t capacity_rows, int D, int dtype, int ring,
                                 vm_memory **out) {
     if (!ctx || !out) return VM_ERR_INVALID;
@@ -127,6 +141,7 @@ extern "C" void vm_memory_destroy(vm_memory *m) {
     if (m->d_total) (void)hipFree(m->d_total);
     if (m->gkey) (void)hipFree(m->gkey);
     if (m->gord) (void)hipFree(m->gord);
+    if (m->tag) (void)hipFree(m->tag);
     delete m;
 }
 
@@ -149,8 +164,26 @@ extern "C" int vm_memory_create_grouped(vm_ctx *ctx, int64_t capacity_rows, int 
     return VM_OK;
 }
 
-static int memory_append(vm_memory *m, const void *rows, int B, const int64_t *keys, int64_t *out_first_row_host,
-                         void *stream) {
+extern "C" int vm_memory_create_tagged(vm_ctx *ctx, int64_t capacity_rows, int D, int dtype, int ring, int grouped,
+                                       vm_memory **out) {
+    vm_memory *m = nullptr;
+    const int rc = grouped ? vm_memory_create_grouped(ctx, capacity_rows, D, dtype, ring, &m)
+                           : vm_memory_create(ctx, capacity_rows, D, dtype, ring, &m);
+    if (rc != VM_OK) return rc;
+    const int64_t cap_pad = (capacity_rows + 63) / 64 * 64;
+    hipError_t e = hipMalloc((void **)&m->tag, (size_t)cap_pad * 8);
+    if (e == hipSuccess) e = hipMemset(m->tag, 0, (size_t)cap_pad * 8);
+    if (e != hipSuccess) {
+        vm_memory_destroy(m);
+        return vm_fail(ctx, VM_ERR_NOMEM, "tag column of a %lld-row memory: %s", (long long)capacity_rows,
+                       hipGetErrorString(e));
+    }
+    *out = m;
+    return VM_OK;
+}
+
+static int memory_append(vm_memory *m, const void *rows, int B, const int64_t *keys, const int64_t *tags,
+                         int64_t *out_first_row_host, void *stream) {
     vm_ctx *ctx = m->ctx;
     if (B < 0 || (B > 0 && !rows)) return vm_fail(ctx, VM_ERR_INVALID, "vm_memory_append: bad arguments");
     if (out_first_row_host) *out_first_row_host = m->h_total;
@@ -172,6 +205,10 @@ static int memory_append(vm_memory *m, const void *rows, int B, const int64_t *k
         memory_group_kernel<<<1, 256, 0, st>>>(keys, B, m->gkey, m->gord, m->d_total, m->cap, m->ring);
         VM_LAUNCH_CHECK(ctx);
     }
+    if (m->tag) {  // tagged memories only
+        memory_tag_kernel<<<(B + 255) / 256, 256, 0, st>>>(tags, B, m->tag, m->d_total, m->cap, m->ring);
+        VM_LAUNCH_CHECK(ctx);
+    }
     memory_bump_kernel<<<1, 1, 0, st>>>(m->d_total, B);
     VM_LAUNCH_CHECK(ctx);
     m->h_total += B;
@@ -180,7 +217,7 @@ static int memory_append(vm_memory *m, const void *rows, int B, const int64_t *k
 
 extern "C" int vm_memory_append(vm_memory *m, const void *rows, int B, int64_t *out_first_row_host, void *stream) {
     if (!m) return VM_ERR_INVALID;
-    return memory_append(m, rows, B, nullptr, out_first_row_host, stream);
+    return memory_append(m, rows, B, nullptr, nullptr, out_first_row_host, stream);
 }
 
 extern "C" int vm_memory_append_grouped(vm_memory *m, const void *rows, int B, const int64_t *keys,
@@ -188,8 +225,19 @@ extern "C" int vm_memory_append_grouped(vm_memory *m, const void *rows, int B, c
     if (!m) return VM_ERR_INVALID;
     if (!m->gkey) return vm_fail(m->ctx, VM_ERR_INVALID, "vm_memory_append_grouped: the memory is not grouped");
     if (B > 0 && !keys) return vm_fail(m->ctx, VM_ERR_INVALID, "vm_memory_append_grouped: keys is null");
-    return memory_append(m, rows, B, keys, out_first_row_host, stream);
+    return memory_append(m, rows, B, keys, nullptr, out_first_row_host, stream);
 }
+
+extern "C" int vm_memory_append_tagged(vm_memory *m, const void *rows, int B, const int64_t *tags, const int64_t *keys,
+                                       int64_t *out_first_row_host, void *stream) {
+    if (!m) return VM_ERR_INVALID;
+    if (!m->tag) return vm_fail(m->ctx, VM_ERR_INVALID, "vm_memory_append_tagged: the memory is not tagged");
+    if (B > 0 && !tags) return vm_fail(m->ctx, VM_ERR_INVALID, "vm_memory_append_tagged: tags is null");
+    if (keys && !m->gkey) return vm_fail(m->ctx, VM_ERR_INVALID, "vm_memory_append_tagged: keys on a memory that is not grouped");
+    return memory_append(m, rows, B, keys, tags, out_first_row_host, stream);
+}
+
+extern "C" const int64_t *vm_memory_tags(const vm_memory *m) { return m ? m->tag : nullptr; }
 
 extern "C" const int64_t *vm_memory_group_keys(const vm_memory *m) { return m ? m->gkey : nullptr; }
 

@@ -1,0 +1,731 @@
+// Scoped cosine top-k: the k best rows among those whose int64 TAG lies in the query's inclusive range [lo, hi]
+// (include/vidmem.h).  Replaces the per-graph predicate of the two scans the row search replaces
+// (src/pipeline/retriever_hybrid.py:295 `MATCH (c:Chunk {graph_uuid: $graph_uuid})`,
+// src/components/pre_llm_injector.py:395-396 `WHERE c.graph_uuid = $graph_uuid`): one memory holds many videos, a
+// query names the video or the time window it wants.
+//
+// The row ranking is vm_topk_cosine's, taken over the in-scope rows only.  Same two-stage, certified design as topk.hip
+// and topk_group.hip; a row is a group of one whose fp32 key is 0 when it is out of scope:
+//   scan     : per 16-row tile the wave first reads the tile's 16 tags and tests them against the scopes of its query
+//              tile; a tile with no (row, query) pair in scope is skipped WITHOUT reading its rows (8 bytes per row
+//              instead of 2 D) and only zeroes its keys.  Otherwise fp32 MFMA scores with the list scan's numerics (the
+//              same instruction over the same operand layout, then x 1/||row||), the per-pair mask applied again, one
+//              order-preserving key per (query, physical slot): F[q][slot], 0 = out of scope (below every score's key)
+//   select   : per query the best M + 1 in-scope rows by (fp32 key desc, age order asc): a cut from a strided sample of
+//              the keys, a parallel compaction of every in-scope row at or above it, a block-wide selection.  A query
+//              with more than SEL_CAP rows at its cut is flagged VM_FLAG_OVERFLOW
+//   finalize : the best M re-scored exactly (topk_common.h), ordered (score desc, row asc), filtered, k kept.  Certified
+//              when the scope holds at most M rows, or when the exact k-th score clears the (M+1)-th IN-SCOPE fp32
+//              score / ||q|| by cert_eps(D), strictly.  Out-of-scope rows have key 0 and never reach the certificate
+//   redo     : flagged queries scored exhaustively over their in-scope rows, slices of age orders per block, stable
+//              top-k per slice, merge.  Flags and counts are read on the device; near-empty when nothing is flagged.
+// Every launch reads the row count from the device and sizes its grid from the capacity: capturable.
+#include "topk_common.h"
+#include "vm_internal.h"
+
+#include <climits>
+
+namespace {
+
+constexpr int SS_THREADS = 256;    // scan
+constexpr int SEL_THREADS = 1024;  // cut and selection (one block per query)
+constexpr int SEL_SAMPLE = 16384;  // slots whose keys give each query's cut
+constexpr int SEL_CAP = 8192;      // rows at or above the cut a query keeps; more -> VM_FLAG_OVERFLOW
+constexpr int CMP_THREADS = 256;   // compaction
+constexpr int CMP_LCAP = 2048;     // hits one compaction block gathers in LDS before it flushes them
+constexpr int SF_THREADS = 256;    // finalize
+constexpr int SCMAX = 128;         // candidates per query kept by the select (M + 1 <= 81)
+constexpr int SR_THREADS = 256;    // redo
+constexpr int SR_CHUNK = 1024;     // rows scored per selection pass of the redo
+constexpr int SKMAX = 64;
+
+// order-preserving unsigned image of an fp32 score (bigger key = bigger value; -0 folded into +0; every image is > 0)
+__device__ __forceinline__ uint32_t okey32(float s) {
+    uint32_t u = __float_as_uint(s);
+    if (s == 0.f) u = 0;
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float dekey32(uint32_t k) {
+    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+__device__ __forceinline__ bool in_scope(int64_t tag, int64_t lo, int64_t hi) { return lo <= tag && tag <= hi; }
+// age order (0 = oldest) of the live row in physical slot p
+__device__ __forceinline__ int64_t order_of(const RingView &v, int64_t p) {
+    const int64_t o = p - v.head;
+    return o < 0 ? o + v.cap : o;
+}
+
+// ---- scan --------------------------------------------------------------------------------------------------
+// grid (row blocks, query groups of QT*16).  The MFMA part is topk_scan_kernel's (topk.hip): 16-row tiles in physical
+// order, the row tile the A operand straight from global memory, the query tile the B operand from chunk-swizzled LDS,
+// acc[t][j] = <row tile*16 + 4h + j, query q0 + 16t + r16>, score = acc * rnorm32.  F[q * fstride + slot] = key or 0.
+template <int DT, int QT>
+__global__ void __launch_bounds__(SS_THREADS)
+    scope_scan_kernel(const uint16_t *__restrict__ mem, const float *__restrict__ rnorm,
+                      const int64_t *__restrict__ tag, const uint16_t *__restrict__ queries,
+                      const int64_t *__restrict__ scope_lo, const int64_t *__restrict__ scope_hi,
+                      const int64_t *__restrict__ d_total, int64_t cap, int ring, int D, int Q, int64_t fstride,
+                      uint32_t *__restrict__ F) {
+    using E = vm_elem<DT>;
+    using vec8 = typename E::vec8;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    uint4 *qlds = reinterpret_cast<uint4 *>(smem);
+    __shared__ int64_t slo[QT * 16], shi[QT * 16];
+    const int chunks = D / 8;
+    constexpr int nw = SS_THREADS / 64;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int r16 = lane & 15, h = lane >> 4;
+    const int q0 = blockIdx.y * (QT * 16);
+    for (int idx = tid; idx < QT * 16 * chunks; idx += SS_THREADS) {
+        const int q = idx / chunks, ci = idx - q * chunks;
+        uint4 v = make_uint4(0, 0, 0, 0);
+        if (q0 + q < Q) v = reinterpret_cast<const uint4 *>(queries + (size_t)(q0 + q) * D)[ci];
+        qlds[q * chunks + ((ci & ~15) | ((ci ^ q) & 15))] = v;
+    }
+    if (tid < QT * 16) {  // queries past Q have the empty scope
+        const bool live = q0 + tid < Q;
+        slo[tid] = live ? scope_lo[q0 + tid] : LLONG_MAX;
+        shi[tid] = live ? scope_hi[q0 + tid] : LLONG_MIN;
+    }
+    __syncthreads();
+    const RingView rv = ring_view(*d_total, cap, ring);
+    const int64_t n = rv.n;
+    const int64_t ntiles = (n + 15) / 16;
+    const int ksteps = D / 32;
+    constexpr int LB = 8;
+    const uint4 *qrow = qlds + r16 * chunks;
+    const int tstride = 16 * chunks;
+    const int64_t tile_step = (int64_t)gridDim.x * nw;
+    for (int64_t tile = (int64_t)blockIdx.x * nw + wave; tile < ntiles; tile += tile_step) {
+        const int64_t p0 = tile * 16 + 4 * h;  // this lane's 4 slots (below cap_pad: the columns are padded to 64 rows)
+        // the tile's 16 tags before any row data: lane (r16, h) tests row r16 against queries 4h .. 4h+3 of each sub-tile
+        {
+            const int64_t trow = tile * 16 + r16;
+            bool hit = false;
+            if (trow < n) {
+                const int64_t tg = tag[trow];
+#pragma unroll
+                for (int t = 0; t < QT; ++t)
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) hit |= in_scope(tg, slo[16 * t + 4 * h + c], shi[16 * t + 4 * h + c]);
+            }
+            if (__ballot(hit) == 0ull) {  // wave-uniform: nothing of this tile is wanted; its rows are not read
+#pragma unroll
+                for (int t = 0; t < QT; ++t) {
+                    const int q = q0 + 16 * t + r16;
+                    if (q < Q) *reinterpret_cast<uint4 *>(F + (size_t)q * fstride + p0) = make_uint4(0, 0, 0, 0);
+                }
+                continue;
+            }
+        }
+        int64_t row = tile * 16 + r16;
+        if (row > n - 1) row = n - 1;  // tail lanes re-read the last row; their scores are masked below
+        const uint4 *src = reinterpret_cast<const uint4 *>(mem + (size_t)row * D) + h;
+        f32x4 acc[QT];
+#pragma unroll
+        for (int t = 0; t < QT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int s0 = 0; s0 < ksteps; s0 += LB) {
+            uint4 cur[LB];
+#pragma unroll
+            for (int u = 0; u < LB; ++u) cur[u] = src[(s0 + u < ksteps ? s0 + u : ksteps - 1) * 4];
+#pragma unroll
+            for (int u = 0; u < LB; ++u) {
+                if (s0 + u < ksteps) {
+                    const int ci = h + 4 * (s0 + u);
+                    const vec8 av = __builtin_bit_cast(vec8, cur[u]);
+                    const uint4 *qp = qrow + ((ci & ~15) | ((ci ^ r16) & 15));
+#pragma unroll
+                    for (int t = 0; t < QT; ++t) acc[t] = E::mfma16(av, __builtin_bit_cast(vec8, qp[t * tstride]), acc[t]);
+                }
+            }
+        }
+        const float4 rn = *reinterpret_cast<const float4 *>(rnorm + p0);
+        const float rnv[4] = {rn.x, rn.y, rn.z, rn.w};
+        int64_t tj[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) tj[j] = tag[p0 + j];
+#pragma unroll
+        for (int t = 0; t < QT; ++t) {
+            const int q = q0 + 16 * t + r16;
+            if (q >= Q) continue;
+            const int64_t lo = slo[16 * t + r16], hi = shi[16 * t + r16];
+            uint32_t key[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                key[j] = (p0 + j < n && in_scope(tj[j], lo, hi)) ? okey32(acc[t][j] * rnv[j]) : 0u;
+            *reinterpret_cast<uint4 *>(F + (size_t)q * fstride + p0) = make_uint4(key[0], key[1], key[2], key[3]);
+        }
+    }
+}
+
+// ---- select ------------------------------------------------------------------------------------------------
+// 64-bit composites key << 32 | ~order (bigger = better, unique)
+__device__ __forceinline__ unsigned long long composite(uint32_t key, int o) {
+    return ((unsigned long long)key << 32) | (unsigned long long)(0xffffffffu - (uint32_t)o);
+}
+
+// largest T with at least `need` of the block's values >= T (PER values per thread, SEL_THREADS threads; every thread
+// calls it): a bitwise search, one block-wide count per bit.  low_bit > 0 stops the search there: the result has its low
+// bits clear and is a lower bound of the exact value (still at least `need` values >= T)
+template <int PER>
+__device__ __forceinline__ uint32_t block_kth_u32(const uint32_t (&v)[PER], int need, int low_bit = 0) {
+    __shared__ int wsum[SEL_THREADS / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t T = 0;
+    for (int bit = 31; bit >= low_bit; --bit) {
+        const uint32_t c = T | (1u << bit);
+        int cnt = 0;
+#pragma unroll
+        for (int j = 0; j < PER; ++j) cnt += v[j] >= c ? 1 : 0;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
+        if (lane == 0) wsum[wave] = cnt;
+        __syncthreads();
+        int tot = 0;
+#pragma unroll
+        for (int w = 0; w < SEL_THREADS / 64; ++w) tot += wsum[w];
+        __syncthreads();
+        if (tot >= need) T = c;
+    }
+    return T;
+}
+
+// One block per query: cut[q] = the (M+1)-th largest key of a sample of SEL_SAMPLE slots, one per stride (all slots when
+// there are fewer), or 1 - every in-scope row - when the sample holds fewer than M + 1 in-scope rows.  At least
+// min(M + 1, in-scope rows) rows have a key >= the cut, and no out-of-scope row (key 0) has.
+__global__ void __launch_bounds__(SEL_THREADS)
+    scope_cut_kernel(const int64_t *__restrict__ d_total, int64_t cap, int ring, const uint32_t *__restrict__ F,
+                     int64_t fstride, int M1, uint32_t *__restrict__ cut, int *__restrict__ ccount) {
+    constexpr int PER = SEL_SAMPLE / SEL_THREADS;
+    const int q = blockIdx.x, tid = threadIdx.x;
+    const int64_t n = ring_view(*d_total, cap, ring).n;
+    const uint32_t *Fq = F + (size_t)q * fstride;
+    const int cnt = (int)(n < SEL_SAMPLE ? n : SEL_SAMPLE);
+    uint32_t v[PER];
+#pragma unroll
+    for (int j = 0; j < PER; ++j) {
+        const int i = j * SEL_THREADS + tid;
+        // one slot per stride, at a hashed offset inside it: a fixed stride of 64 slots would see one source only of
+        // two that alternate every 16 rows
+        int64_t p = i;
+        if (n > SEL_SAMPLE) p = (int64_t)i * n / SEL_SAMPLE + (int64_t)(((uint32_t)i * 2654435761u) >> 8) % (n / SEL_SAMPLE);
+        v[j] = i < cnt ? Fq[p] : 0u;
+    }
+    // the top 20 bits of the key are enough for a cut (a score resolution of 2^-11 relative): 20 counting steps, not 32.
+    // 0 when fewer than M1 sampled keys are in scope (every in-scope key is above 2^12)
+    const uint32_t T = block_kth_u32<PER>(v, M1, 12);
+    if (tid == 0) {
+        cut[q] = T ? T : 1u;
+        ccount[q] = 0;
+    }
+}
+
+// grid (slices, Q): every in-scope row with key >= cut[q] goes to the query's buffer as a composite.  Hits gather in
+// LDS and leave with one global atomic per flush.  ccount[q] ends as the exact number of hits; the buffer keeps the
+// first SEL_CAP.
+__global__ void __launch_bounds__(CMP_THREADS)
+    scope_compact_kernel(const int64_t *__restrict__ d_total, int64_t cap, int ring, const uint32_t *__restrict__ F,
+                         int64_t fstride, const uint32_t *__restrict__ cut, int *__restrict__ ccount,
+                         unsigned long long *__restrict__ cbuf) {
+    __shared__ unsigned long long lbuf[CMP_LCAP];
+    __shared__ int lcnt, gbase;
+    const int q = blockIdx.y, tid = threadIdx.x;
+    const RingView rv = ring_view(*d_total, cap, ring);
+    const int64_t n = rv.n;
+    const uint32_t *Fq = F + (size_t)q * fstride;
+    const uint32_t T = cut[q];
+    const int64_t stride = (int64_t)gridDim.x * CMP_THREADS * 4;
+    if (tid == 0) lcnt = 0;
+    __syncthreads();
+    int held_max = 0;  // block-uniform upper bound of the hits in lbuf
+    auto flush = [&]() {  // called by every thread
+        __syncthreads();  // every hit of the iterations so far is in lbuf and counted in lcnt
+        const int held = lcnt;
+        if (tid == 0 && held) gbase = atomicAdd(&ccount[q], held);
+        __syncthreads();
+        for (int i = tid; i < held; i += CMP_THREADS) {
+            const int pos = gbase + i;
+            if (pos < SEL_CAP) cbuf[(size_t)q * SEL_CAP + pos] = lbuf[i];
+        }
+        __syncthreads();
+        if (tid == 0) lcnt = 0;
+        held_max = 0;
+        __syncthreads();
+    };
+    for (int64_t base = (int64_t)blockIdx.x * CMP_THREADS * 4; base < n; base += stride) {  // uniform per block
+        const int64_t p = base + 4 * tid;  // 4 consecutive slots, 16-byte aligned (fstride is a multiple of 64)
+        uint4 k4 = make_uint4(0, 0, 0, 0);
+        if (p < n) k4 = *reinterpret_cast<const uint4 *>(Fq + p);
+        const uint32_t key[4] = {k4.x, k4.y, k4.z, k4.w};
+        int hits = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) hits += (p + j < n && key[j] >= T) ? 1 : 0;  // T >= 1: never an out-of-scope row
+        if (hits) {  // rare: one LDS atomic per thread with hits
+            int pos = atomicAdd(&lcnt, hits);  // pos + hits <= CMP_LCAP: flushed before it could fill
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (p + j < n && key[j] >= T) lbuf[pos++] = composite(key[j], (int)order_of(rv, p + j));
+        }
+        held_max += 4 * __syncthreads_count(hits != 0);
+        if (held_max > CMP_LCAP - 4 * CMP_THREADS) flush();
+    }
+    flush();
+}
+
+// One block per query: the best take = min(M + 1, hits) composites of the compacted list.  cand_n[q] = take, or -1 when
+// the list overflowed (the finalize flags the query for the exhaustive redo).
+__global__ void __launch_bounds__(SEL_THREADS)
+    scope_select_kernel(int M1, const int *__restrict__ ccount, const unsigned long long *__restrict__ cbuf,
+                        int *__restrict__ cand_o, uint32_t *__restrict__ cand_k, int *__restrict__ cand_n) {
+    const int q = blockIdx.x, tid = threadIdx.x;
+    int *oo = cand_o + (size_t)q * SCMAX;
+    uint32_t *ok = cand_k + (size_t)q * SCMAX;
+    const int cnt = ccount[q];
+    if (cnt > SEL_CAP || cnt == 0) {  // uniform
+        if (tid == 0) cand_n[q] = cnt ? -1 : 0;
+        return;
+    }
+    const int take = cnt < M1 ? cnt : M1;
+    if (tid == 0) cand_n[q] = take;
+    constexpr int PER = SEL_CAP / SEL_THREADS;
+    __shared__ int red[2][SEL_THREADS / 64];
+    __shared__ int npos;
+    const int lane = tid & 63, wave = tid >> 6;
+    uint32_t hi[PER], lo[PER];
+#pragma unroll
+    for (int j = 0; j < PER; ++j) {
+        const int i = j * SEL_THREADS + tid;
+        const unsigned long long c = i < cnt ? cbuf[(size_t)q * SEL_CAP + i] : 0ull;
+        hi[j] = (uint32_t)(c >> 32);
+        lo[j] = (uint32_t)c;  // ~order: bigger = older row
+    }
+    const uint32_t T = block_kth_u32<PER>(hi, take);  // >= 1: every list entry has a key >= 1, and take <= cnt
+    int above = 0, equal = 0;
+#pragma unroll
+    for (int j = 0; j < PER; ++j) {
+        above += hi[j] > T ? 1 : 0;
+        equal += hi[j] == T ? 1 : 0;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        above += __shfl_xor(above, off, 64);
+        equal += __shfl_xor(equal, off, 64);
+    }
+    if (lane == 0) {
+        red[0][wave] = above;
+        red[1][wave] = equal;
+    }
+    if (tid == 0) npos = 0;
+    __syncthreads();
+    above = equal = 0;
+#pragma unroll
+    for (int w = 0; w < SEL_THREADS / 64; ++w) {
+        above += red[0][w];
+        equal += red[1][w];
+    }
+    const int need_eq = take - above;
+    uint32_t lo_cut = 0;  // keep the need_eq oldest rows among the keys == T
+    if (need_eq < equal) {
+        uint32_t le[PER];
+#pragma unroll
+        for (int j = 0; j < PER; ++j) le[j] = hi[j] == T ? lo[j] : 0u;
+        lo_cut = block_kth_u32<PER>(le, need_eq);  // uniform branch: every thread sees the same counts
+    }
+#pragma unroll
+    for (int j = 0; j < PER; ++j) {  // exactly take entries are kept; their order does not matter (finalize ranks)
+        const bool keep = hi[j] > T || (hi[j] == T && lo[j] >= lo_cut);
+        if (keep) {
+            const int pos = atomicAdd(&npos, 1);
+            if (pos < SCMAX) {
+                oo[pos] = (int)(0xffffffffu - lo[j]);
+                ok[pos] = hi[j];
+            }
+        }
+    }
+}
+
+// ---- finalize ----------------------------------------------------------------------------------------------
+// One block per query.  Ranks the C candidates by (fp32 key desc, order asc): the first nc = min(C, M) are re-scored
+// exactly, the (M+1)-th (if any) bounds every other in-scope row.
+template <int DT>
+__global__ void __launch_bounds__(SF_THREADS)
+    scope_finalize_kernel(const uint16_t *__restrict__ mem, const double *__restrict__ norm64,
+                          const uint16_t *__restrict__ queries, const int64_t *__restrict__ d_total, int64_t cap,
+                          int ring, int D, const int *__restrict__ cand_o, const uint32_t *__restrict__ cand_k,
+                          const int *__restrict__ cand_n, int M, int k, int use_min, double min_score, int score_mode,
+                          int64_t row_stride, int64_t row_offset, double *__restrict__ out_scores,
+                          int64_t *__restrict__ out_rows, int *__restrict__ uncertified, int *__restrict__ flags,
+                          int *__restrict__ user_flags) {
+    extern __shared__ __attribute__((aligned(16))) char sf_dyn[];
+    uint16_t *ql = reinterpret_cast<uint16_t *>(sf_dyn);  // [D]
+    __shared__ int so[SCMAX], lo_[SCMAX];
+    __shared__ uint32_t sk[SCMAX], lk[SCMAX];
+    __shared__ double es[SCMAX];
+    __shared__ double qn_sh;
+    __shared__ int flag_sh;
+    const int q = blockIdx.x, tid = threadIdx.x;
+    const RingView rv = ring_view(*d_total, cap, ring);
+    const int C = cand_n[q];
+    if (C < 0) {  // uniform: more rows at the cut than the buffer holds -> the exhaustive redo answers this query
+        for (int i = tid; i < k; i += SF_THREADS) {
+            out_scores[(size_t)q * k + i] = 0.0;
+            out_rows[(size_t)q * k + i] = -1;
+        }
+        if (tid == 0) {
+            flags[q] = VM_FLAG_OVERFLOW;
+            if (user_flags) user_flags[q] = VM_FLAG_OVERFLOW;
+            if (uncertified) atomicAdd(uncertified, 1);
+        }
+        return;
+    }
+    const int nc = C < M ? C : M;
+    for (int i = tid; i < D / 8; i += SF_THREADS)
+        reinterpret_cast<uint4 *>(ql)[i] = reinterpret_cast<const uint4 *>(queries + (size_t)q * D)[i];
+    if (tid < C) {
+        lo_[tid] = cand_o[(size_t)q * SCMAX + tid];
+        lk[tid] = cand_k[(size_t)q * SCMAX + tid];
+    }
+    if (tid == 0) flag_sh = VM_FLAG_CERTIFIED;
+    __syncthreads();
+    if (tid < C) {  // rank by (fp32 key desc, order asc)
+        const int o = lo_[tid];
+        const uint32_t key = lk[tid];
+        int r = 0;
+        for (int j = 0; j < C; ++j) r += (lk[j] > key || (lk[j] == key && lo_[j] < o)) ? 1 : 0;
+        so[r] = o;
+        sk[r] = key;
+    }
+    if (tid == SF_THREADS - 1) qn_sh = __dsqrt_rn(ref_sumsq<DT>(ql, D));
+    __syncthreads();
+    const double qn = qn_sh;
+    if (tid < nc) {
+        const int64_t p = slot_of(rv, so[tid]);
+        es[tid] = ref_cosine(ref_dot<DT>(ql, mem + (size_t)p * D, D), qn, norm64[p]);
+    }
+    __syncthreads();
+    if (tid < nc) {
+        const double e = es[tid];
+        const int o = so[tid];
+        int r = 0;
+        for (int d = 0; d < nc; ++d) r += (es[d] > e || (es[d] == e && so[d] < o)) ? 1 : 0;
+        if (r < k) {
+            const double shown = shown_score(e, score_mode);
+            const bool pass = passes_min(use_min, shown, min_score);
+            out_scores[(size_t)q * k + r] = pass ? shown : 0.0;
+            out_rows[(size_t)q * k + r] = pass ? (rv.base + o) * row_stride + row_offset : -1;
+        }
+        // certification: the exact k-th score against the best fp32 score of an in-scope row that was not re-scored
+        const int kth = (k < nc ? k : nc) - 1;
+        if (r == kth && C > M && qn != 0.0) {
+            const double reject = (double)dekey32(sk[M]) / qn + cert_eps(D);
+            if (!(e > reject)) flag_sh = VM_FLAG_GAP;
+        }
+    }
+    for (int i = nc + tid; i < k; i += SF_THREADS) {
+        out_scores[(size_t)q * k + i] = 0.0;
+        out_rows[(size_t)q * k + i] = -1;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        flags[q] = flag_sh;
+        if (user_flags) user_flags[q] = flag_sh;
+        if (flag_sh && uncertified) atomicAdd(uncertified, 1);
+    }
+}
+
+// ---- redo --------------------------------------------------------------------------------------------------
+__global__ void scope_fill_flags_kernel(int32_t *__restrict__ flags, int Q) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < Q) flags[i] = 1;
+}
+
+// grid = nblk row blocks; every block walks all Q flags and, for each flagged query, scores the in-scope rows of its
+// contiguous slice of age orders exactly and keeps the slice's stable top-k:
+// part[(block * Q + q) * k + i] = {score fp64, age order int64}.  A chunk with no in-scope row costs its tags only.
+template <int DT>
+__global__ void __launch_bounds__(SR_THREADS)
+    scope_redo_scan_kernel(const uint16_t *__restrict__ queries, const uint16_t *__restrict__ rows,
+                           const double *__restrict__ norm64, const int64_t *__restrict__ tag,
+                           const int64_t *__restrict__ scope_lo, const int64_t *__restrict__ scope_hi,
+                           const int64_t *__restrict__ d_total, int64_t cap, int ring, int D, int Q, int k,
+                           const int32_t *__restrict__ flags, double *__restrict__ part_s,
+                           int64_t *__restrict__ part_o) {
+    extern __shared__ __attribute__((aligned(16))) char sr_dyn[];
+    uint16_t *ql = reinterpret_cast<uint16_t *>(sr_dyn);  // [D]
+    __shared__ double sc[SR_CHUNK];
+    __shared__ uint8_t live[SR_CHUNK];
+    __shared__ double run_s[SKMAX], new_s[SKMAX], red_s[SR_THREADS / 64];
+    __shared__ int64_t run_o[SKMAX], new_o[SKMAX], red_o[SR_THREADS / 64];
+    __shared__ double qnorm_sh;
+    const int tid = threadIdx.x;
+    int any = 0;
+    for (int i = tid; i < Q; i += SR_THREADS) any |= flags[i];
+    if (!__syncthreads_or(any)) return;
+    const RingView rv = ring_view(*d_total, cap, ring);
+    const int64_t per = (rv.n + gridDim.x - 1) / gridDim.x;
+    const int64_t lo = (int64_t)blockIdx.x * per;
+    const int64_t hi = lo + per < rv.n ? lo + per : rv.n;
+    for (int q = 0; q < Q; ++q) {
+        if (flags[q] == 0) continue;  // uniform
+        __syncthreads();
+        for (int i = tid; i < D / 8; i += SR_THREADS)
+            reinterpret_cast<uint4 *>(ql)[i] = reinterpret_cast<const uint4 *>(queries + (size_t)q * D)[i];
+        if (tid < k) {
+            run_s[tid] = -INFINITY;
+            run_o[tid] = -1;
+        }
+        __syncthreads();
+        if (tid == 0) qnorm_sh = __dsqrt_rn(ref_sumsq<DT>(ql, D));
+        __syncthreads();
+        const double qn = qnorm_sh;
+        const int64_t slo = scope_lo[q], shi = scope_hi[q];
+        for (int64_t c0 = lo; c0 < hi; c0 += SR_CHUNK) {
+            const int cn = (int)(hi - c0 < SR_CHUNK ? hi - c0 : SR_CHUNK);
+            int mine = 0;
+            for (int i = tid; i < cn; i += SR_THREADS) {
+                const int64_t p = slot_of(rv, c0 + i);
+                const bool in = in_scope(tag[p], slo, shi);
+                live[i] = in ? 1 : 0;
+                if (in) {
+                    sc[i] = ref_cosine(ref_dot<DT>(ql, rows + (size_t)p * D, D), qn, norm64[p]);
+                    mine = 1;
+                }
+            }
+            if (!__syncthreads_or(mine)) continue;  // uniform: nothing of this chunk is in scope
+            block_select<SR_THREADS>(cn + k, k,
+                                     [&](int i, double &v, int64_t &o) {
+                                         if (i < cn) {
+                                             v = sc[i];
+                                             o = live[i] ? c0 + i : -1;
+                                         } else {
+                                             v = run_s[i - cn];
+                                             o = run_o[i - cn];
+                                         }
+                                     },
+                                     new_s, new_o, red_s, red_o);
+            if (tid < k) {
+                run_s[tid] = new_s[tid];
+                run_o[tid] = new_o[tid];
+            }
+            __syncthreads();
+        }
+        if (tid < k) {
+            part_s[((size_t)blockIdx.x * Q + q) * k + tid] = run_s[tid];
+            part_o[((size_t)blockIdx.x * Q + q) * k + tid] = run_o[tid];
+        }
+    }
+}
+
+// grid = Q; a block whose query is not flagged exits at once.  Stable top-k over the nblk * k slice winners, then the
+// output mapping of the fast path.
+__global__ void __launch_bounds__(SR_THREADS)
+    scope_redo_merge_kernel(const double *__restrict__ part_s, const int64_t *__restrict__ part_o, int nblk, int Q,
+                            int k, const int32_t *__restrict__ flags, const int64_t *__restrict__ d_total, int64_t cap,
+                            int ring, int use_min, double min_score, int score_mode, int64_t row_stride,
+                            int64_t row_offset, double *__restrict__ out_scores, int64_t *__restrict__ out_rows) {
+    __shared__ double win_s[SKMAX], red_s[SR_THREADS / 64];
+    __shared__ int64_t win_o[SKMAX], red_o[SR_THREADS / 64];
+    const int q = blockIdx.x, tid = threadIdx.x;
+    if (flags[q] == 0) return;
+    const RingView rv = ring_view(*d_total, cap, ring);
+    block_select<SR_THREADS>(nblk * k, k,
+                             [&](int i, double &v, int64_t &o) {
+                                 const int b = i / k, e = i - b * k;
+                                 v = part_s[((size_t)b * Q + q) * k + e];
+                                 o = part_o[((size_t)b * Q + q) * k + e];
+                             },
+                             win_s, win_o, red_s, red_o);
+    if (tid < k) {
+        const int64_t o = win_o[tid];
+        double shown = win_s[tid];
+        bool ok = o >= 0;
+        if (ok) {
+            shown = shown_score(shown, score_mode);
+            ok = passes_min(use_min, shown, min_score);
+        }
+        out_scores[(size_t)q * k + tid] = ok ? shown : 0.0;
+        out_rows[(size_t)q * k + tid] = ok ? (rv.base + o) * row_stride + row_offset : -1;
+    }
+}
+
+// ---- host --------------------------------------------------------------------------------------------------
+struct SPlan {
+    int M, qt, qgroups, nbx, nblk, cmp_slices;
+    int64_t fstride;
+    size_t off_co, off_ck, off_cn, off_flags, off_cut, off_cc, off_cbuf, off_ps, off_po, total;
+};
+
+SPlan scope_plan(const vm_memory *m, int Q, int k) {
+    SPlan p;
+    p.M = k + (k / 4 > 8 ? k / 4 : 8);  // slack: near-ties between rank k and rank M are certified by the gap
+    p.qt = Q <= 16 ? 1 : 2;
+    p.qgroups = (Q + 16 * p.qt - 1) / (16 * p.qt);
+    const int64_t tiles = (m->cap + 15) / 16;
+    int64_t nbx = (tiles + SS_THREADS / 64 - 1) / (SS_THREADS / 64);
+    const int64_t lim = (int64_t)m->ctx->num_cus * 8;
+    p.nbx = (int)(nbx < lim ? (nbx < 1 ? 1 : nbx) : lim);
+    int64_t nb = (m->cap + SR_CHUNK - 1) / SR_CHUNK;
+    if (nb > m->ctx->num_cus) nb = m->ctx->num_cus;
+    p.nblk = nb < 1 ? 1 : (int)nb;
+    int64_t sl = (m->cap + 8191) / 8192;
+    p.cmp_slices = (int)(sl < 1 ? 1 : (sl > 64 ? 64 : sl));
+    p.fstride = (m->cap + 63) / 64 * 64;  // the columns' padding: a tail tile writes its 16 keys
+    size_t off = vm_align_up((size_t)Q * (size_t)p.fstride * 4, 256);  // F: [Q][slot] fp32 keys
+    p.off_co = off;
+    off += vm_align_up((size_t)Q * SCMAX * 4, 256);
+    p.off_ck = off;
+    off += vm_align_up((size_t)Q * SCMAX * 4, 256);
+    p.off_cn = off;
+    off += vm_align_up((size_t)Q * 4, 256);
+    p.off_flags = off;
+    off += vm_align_up((size_t)Q * 4, 256);
+    p.off_cut = off;
+    off += vm_align_up((size_t)Q * 4, 256);
+    p.off_cc = off;
+    off += vm_align_up((size_t)Q * 4, 256);
+    p.off_cbuf = off;
+    off += vm_align_up((size_t)Q * SEL_CAP * 8, 256);
+    p.off_ps = off;
+    off += vm_align_up((size_t)p.nblk * Q * k * 8, 256);
+    p.off_po = off;
+    off += vm_align_up((size_t)p.nblk * Q * k * 8, 256);
+    p.total = off;
+    return p;
+}
+
+int scope_check(vm_memory *m, const void *queries, int Q, int k, const int64_t *scope_lo, const int64_t *scope_hi,
+                int score_mode, const double *out_scores, const int64_t *out_rows, const void *workspace,
+                size_t workspace_bytes, const char *who) {
+    vm_ctx *ctx = m->ctx;
+    if (!m->tag) return vm_fail(ctx, VM_ERR_INVALID, "%s: the memory is not tagged (vm_memory_create_tagged)", who);
+    if (!queries || !scope_lo || !scope_hi || !out_scores || !out_rows || Q <= 0)
+        return vm_fail(ctx, VM_ERR_INVALID, "%s: bad arguments", who);
+    if (k < 1 || k > SKMAX) return vm_fail(ctx, VM_ERR_INVALID, "%s: k=%d outside [1, %d]", who, k, SKMAX);
+    if (int rc = vm_check_score_mode(ctx, score_mode)) return rc;
+    const size_t need = scope_plan(m, Q, k).total;
+    if (!workspace || workspace_bytes < need)
+        return vm_fail(ctx, VM_ERR_NOMEM, "%s: workspace %zu < %zu", who, workspace_bytes, need);
+    if (((uintptr_t)workspace & 255) || ((uintptr_t)queries & 15))
+        return vm_fail(ctx, VM_ERR_INVALID, "%s: workspace must be 256-byte and queries 16-byte aligned", who);
+    return VM_OK;
+}
+
+template <int DT>
+int scope_redo(vm_memory *m, const SPlan &p, const void *queries, int Q, int k, const int64_t *scope_lo,
+               const int64_t *scope_hi, int use_min, double min_score, int score_mode, int64_t row_stride,
+               int64_t row_offset, double *out_scores, int64_t *out_rows, char *ws, hipStream_t st) {
+    vm_ctx *ctx = m->ctx;
+    vm_prof_scope prof(ctx, VM_PROF_TOPK_EXACT, st);
+    const int32_t *flags = (const int32_t *)(ws + p.off_flags);
+    double *part_s = (double *)(ws + p.off_ps);
+    int64_t *part_o = (int64_t *)(ws + p.off_po);
+    scope_redo_scan_kernel<DT><<<p.nblk, SR_THREADS, (size_t)m->D * 2, st>>>(
+        (const uint16_t *)queries, m->rows, m->norm64, m->tag, scope_lo, scope_hi, m->d_total, m->cap, m->ring, m->D, Q,
+        k, flags, part_s, part_o);
+    VM_LAUNCH_CHECK(ctx);
+    scope_redo_merge_kernel<<<Q, SR_THREADS, 0, st>>>(part_s, part_o, p.nblk, Q, k, flags, m->d_total, m->cap, m->ring,
+                                                      use_min, min_score, score_mode, row_stride, row_offset,
+                                                      out_scores, out_rows);
+    VM_LAUNCH_CHECK(ctx);
+    return VM_OK;
+}
+
+template <int DT, int QT>
+int scope_scan(vm_memory *m, const SPlan &p, const void *queries, int Q, const int64_t *scope_lo,
+               const int64_t *scope_hi, uint32_t *F, hipStream_t st) {
+    const size_t lds = (size_t)QT * 16 * m->D * 2;
+    auto kern = scope_scan_kernel<DT, QT>;
+    if (lds > 65536 - 1024)
+        VM_HIP(m->ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    kern<<<dim3(p.nbx, p.qgroups), SS_THREADS, lds, st>>>(m->rows, m->rnorm32, m->tag, (const uint16_t *)queries,
+                                                         scope_lo, scope_hi, m->d_total, m->cap, m->ring, m->D, Q,
+                                                         p.fstride, F);
+    VM_LAUNCH_CHECK(m->ctx);
+    return VM_OK;
+}
+
+template <int DT>
+int scope_topk(vm_memory *m, const void *queries, int Q, int k, const int64_t *scope_lo, const int64_t *scope_hi,
+               int use_min, double min_score, int score_mode, int64_t row_stride, int64_t row_offset,
+               double *out_scores, int64_t *out_rows, int32_t *out_uncertified, int32_t *out_query_flags, char *ws,
+               hipStream_t st) {
+    vm_ctx *ctx = m->ctx;
+    const SPlan p = scope_plan(m, Q, k);
+    uint32_t *F = (uint32_t *)ws;
+    int *cand_o = (int *)(ws + p.off_co);
+    uint32_t *cand_k = (uint32_t *)(ws + p.off_ck);
+    int *cand_n = (int *)(ws + p.off_cn);
+    int *flags = (int *)(ws + p.off_flags);
+    {
+        vm_prof_scope prof(ctx, VM_PROF_TOPK_SCAN, st);
+        const int rc = p.qt == 1 ? scope_scan<DT, 1>(m, p, queries, Q, scope_lo, scope_hi, F, st)
+                                 : scope_scan<DT, 2>(m, p, queries, Q, scope_lo, scope_hi, F, st);
+        if (rc != VM_OK) return rc;
+    }
+    {
+        vm_prof_scope prof(ctx, VM_PROF_TOPK_FINALIZE, st);
+        uint32_t *cut = (uint32_t *)(ws + p.off_cut);
+        int *ccount = (int *)(ws + p.off_cc);
+        unsigned long long *cbuf = (unsigned long long *)(ws + p.off_cbuf);
+        scope_cut_kernel<<<Q, SEL_THREADS, 0, st>>>(m->d_total, m->cap, m->ring, F, p.fstride, p.M + 1, cut, ccount);
+        VM_LAUNCH_CHECK(ctx);
+        scope_compact_kernel<<<dim3(p.cmp_slices, Q), CMP_THREADS, 0, st>>>(m->d_total, m->cap, m->ring, F, p.fstride,
+                                                                            cut, ccount, cbuf);
+        VM_LAUNCH_CHECK(ctx);
+        scope_select_kernel<<<Q, SEL_THREADS, 0, st>>>(p.M + 1, ccount, cbuf, cand_o, cand_k, cand_n);
+        VM_LAUNCH_CHECK(ctx);
+        scope_finalize_kernel<DT><<<Q, SF_THREADS, (size_t)m->D * 2, st>>>(
+            m->rows, m->norm64, (const uint16_t *)queries, m->d_total, m->cap, m->ring, m->D, cand_o, cand_k, cand_n,
+            p.M, k, use_min, min_score, score_mode, row_stride, row_offset, out_scores, out_rows, out_uncertified, flags,
+            out_query_flags);
+        VM_LAUNCH_CHECK(ctx);
+    }
+    return scope_redo<DT>(m, p, queries, Q, k, scope_lo, scope_hi, use_min, min_score, score_mode, row_stride,
+                          row_offset, out_scores, out_rows, ws, st);
+}
+
+}  // namespace
+
+extern "C" size_t vm_topk_scoped_workspace_bytes(const vm_memory *m, int Q, int k) {
+    if (!m || Q <= 0 || k <= 0 || k > SKMAX) return 0;
+    return scope_plan(m, Q, k).total;
+}
+
+extern "C" int vm_topk_cosine_scoped(vm_memory *m, const void *queries, int Q, int k, const int64_t *scope_lo,
+                                     const int64_t *scope_hi, int use_min_score, double min_score, int score_mode,
+                                     int64_t row_stride, int64_t row_offset, double *out_scores, int64_t *out_rows,
+                                     int32_t *out_uncertified, int32_t *out_query_flags, void *workspace,
+                                     size_t workspace_bytes, void *stream) {
+    if (!m) return VM_ERR_INVALID;
+    int rc = scope_check(m, queries, Q, k, scope_lo, scope_hi, score_mode, out_scores, out_rows, workspace,
+                         workspace_bytes, "vm_topk_cosine_scoped");
+    if (rc != VM_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if (m->dtype == VM_F16)
+        return scope_topk<VM_F16>(m, queries, Q, k, scope_lo, scope_hi, use_min_score, min_score, score_mode, row_stride,
+                                  row_offset, out_scores, out_rows, out_uncertified, out_query_flags, (char *)workspace,
+                                  st);
+    return scope_topk<VM_BF16>(m, queries, Q, k, scope_lo, scope_hi, use_min_score, min_score, score_mode, row_stride,
+                               row_offset, out_scores, out_rows, out_uncertified, out_query_flags, (char *)workspace, st);
+}
+
+extern "C" int vm_topk_cosine_scoped_exact(vm_memory *m, const void *queries, int Q, int k, const int64_t *scope_lo,
+                                           const int64_t *scope_hi, int use_min_score, double min_score, int score_mode,
+                                           int64_t row_stride, int64_t row_offset, double *out_scores,
+                                           int64_t *out_rows, void *workspace, size_t workspace_bytes, void *stream) {
+    if (!m) return VM_ERR_INVALID;
+    int rc = scope_check(m, queries, Q, k, scope_lo, scope_hi, score_mode, out_scores, out_rows, workspace,
+                         workspace_bytes, "vm_topk_cosine_scoped_exact");
+    if (rc != VM_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    vm_ctx *ctx = m->ctx;
+    const SPlan p = scope_plan(m, Q, k);
+    char *ws = (char *)workspace;
+    scope_fill_flags_kernel<<<(Q + 255) / 256, 256, 0, st>>>((int32_t *)(ws + p.off_flags), Q);
+    VM_LAUNCH_CHECK(ctx);
+    if (m->dtype == VM_F16)
+        return scope_redo<VM_F16>(m, p, queries, Q, k, scope_lo, scope_hi, use_min_score, min_score, score_mode,
+                                  row_stride, row_offset, out_scores, out_rows, ws, st);
+    return scope_redo<VM_BF16>(m, p, queries, Q, k, scope_lo, scope_hi, use_min_score, min_score, score_mode, row_stride,
+                               row_offset, out_scores, out_rows, ws, st);
+}

@@ -17,6 +17,8 @@ struct vm_memory {
     int64_t *gkey;     // [cap_pad] group key of each slot (a plain append stores -1 - row id)
     int64_t *gord;     // [cap_pad] group ordinal of each slot: groups ever opened before this row's group, so equal
                        // ordinals = one group and ordinals rise by 0 or 1 from each row id to the next
+    // tagged memories only (vm_memory_create_tagged; null otherwise)
+    int64_t *tag;      // [cap_pad] tag of each slot (INT64_MIN for a row appended without one)
 };
 
 // The 64-byte device block d_total points to: [0] row count, then the grouped append's state (zeroed with the row count

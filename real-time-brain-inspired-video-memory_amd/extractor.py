@@ -38,7 +38,7 @@ import torch
 
 from . import config as cfgmod
 from .encoder import FrameEncoder
-from .memory import EmbeddingMemory
+from .memory import EmbeddingMemory, make_tag
 from .metrics import MetricsTracker, get_logger
 
 logger = get_logger("vidmem.extractor")
@@ -160,11 +160,14 @@ def build_memory(mem_cfg, encoder: FrameEncoder) -> EmbeddingMemory:
     group_by = getattr(mem_cfg, "group_by", None)
     if group_by not in (None, "chunk"):
         raise ValueError(f"memory.group_by must be null or 'chunk', got {group_by!r}")
+    tag_by = getattr(mem_cfg, "tag_by", None)
+    if tag_by not in (None, "time"):
+        raise ValueError(f"memory.tag_by must be null or 'time', got {tag_by!r}")
     if mem_cfg.snapshot and os.path.exists(mem_cfg.snapshot):
         return EmbeddingMemory.restore(mem_cfg.snapshot, capacity=int(mem_cfg.capacity), ring=bool(mem_cfg.ring),
                                        device=encoder.device.index or 0)
     return EmbeddingMemory(int(mem_cfg.capacity), encoder.out_dim, dtype, ring=bool(mem_cfg.ring),
-                           device=encoder.device.index or 0, grouped=group_by == "chunk")
+                           device=encoder.device.index or 0, grouped=group_by == "chunk", tagged=tag_by == "time")
 
 
 class FrameEmbeddingExtractor:
@@ -274,6 +277,10 @@ class FrameEmbeddingExtractor:
                                             video_cfg.frames_per_chunk)
             results = []
             result_lines: List[str] = []      # results[i] as JSON text (finish)
+            # a tagged memory (memory.tag_by: time): this video is one new source, every frame row of a chunk is tagged
+            # (source, the chunk's start in ms); the neighbour search below stays unscoped
+            tagged = bool(getattr(self.memory, "tagged", False))
+            source = self.memory.new_source() if tagged else None
             # Look-ahead groups (config.encoder.look_ahead_chunks, default 0 = auto, 1 = the reference's one chunk at a time,
             # :44-74): the frames of N consecutive chunks go through ONE encoder call - the encoder fills the chip only
             # from a few hundred frames up - and then every chunk of the group, in chunk order, gets its own top-k
@@ -439,16 +446,22 @@ class FrameEmbeddingExtractor:
                         created = time.strftime("%Y-%m-%dT%H:%M:%S+00:00", time.gmtime())   # Chunk.created_at of the export
                         c["ids"] = ids
                         c["meta"] = [{"time": time_str, "content": None, "batch_id": chunk_idx, "created_at": created}] * nframes
+                        tag_kw = {}
+                        if tagged:
+                            c["meta"][0]["source"] = source   # one dict for the chunk's rows
+                            c["tag"] = make_tag(source, int(start / fps * 1000.0))
+                            tag_kw = {"tag": c["tag"]}
                         if not batched:
-                            c["first"] = self.memory.append(emb, ids=ids, meta=c["meta"])
+                            c["first"] = self.memory.append(emb, ids=ids, meta=c["meta"], **tag_kw)
                     if batched:      # one append for the group: rows, ids and meta in chunk order
                         live = [c for c in chunks if c["nframes"]]
                         # a grouped memory (memory.group_by: chunk) gets one key per chunk, per row; a single-chunk
                         # append (below) is one new group by default
                         group = ([k for c in live for k in [self.memory.new_group_key()] * c["nframes"]]
                                  if getattr(self.memory, "grouped", False) else None)
+                        tag_kw = {"tag": [t for c in live for t in [c["tag"]] * c["nframes"]]} if tagged else {}
                         first = self.memory.append(emb_all, ids=[i for c in live for i in c["ids"]],
-                                                   meta=[m for c in live for m in c["meta"]], group=group)
+                                                   meta=[m for c in live for m in c["meta"]], group=group, **tag_kw)
                         for c in live:
                             c["first"] = first
                             first += c["nframes"]

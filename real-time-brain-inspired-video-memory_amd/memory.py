@@ -11,7 +11,12 @@ Reference behaviour mirrored here:
 Grouped memories (``grouped=True``) also keep one int64 group key per row: ``topk_grouped`` returns the k best groups
 (video chunks), one hit per group, instead of k frames of one moment (include/vidmem.h).
 
-All arithmetic is in libvidmem.so (csrc/memory.hip, csrc/topk.hip, csrc/topk_exact.hip, csrc/topk_group.hip).
+Tagged memories (``tagged=True``) keep one int64 tag per row - which video, and when (``make_tag``) - so that one memory
+holds many videos: ``topk_scoped`` ranks only the rows whose tag lies in the query's range (``scope_of``), the
+counterpart of the reference's ``{graph_uuid: $graph_uuid}`` predicate (include/vidmem.h).
+
+All arithmetic is in libvidmem.so (csrc/memory.hip, csrc/topk.hip, csrc/topk_exact.hip, csrc/topk_group.hip,
+csrc/topk_scope.hip).
 """
 from __future__ import annotations
 
@@ -23,13 +28,42 @@ import torch
 from . import _lib
 
 
+INT64_MIN, INT64_MAX = -(1 << 63), (1 << 63) - 1
+TAG_MS_BITS = 40                 # a tag = source << 40 | milliseconds
+TAG_MAX_MS = 1 << TAG_MS_BITS    # ~34.8 years of video per source
+TAG_MAX_SOURCE = 1 << 22
+SCOPE_ALL = (INT64_MIN, INT64_MAX)  # every row, untagged ones (INT64_MIN) included
+
+
+def make_tag(source: int, ms: int) -> int:
+    """The tag of a row of source (video) ``source`` at ``ms`` milliseconds: ``(source << 40) | ms``, with
+    0 <= ms < 2^40 and 0 <= source < 2^22.  Tags of one source are consecutive integers in time order, so one inclusive
+    range names a whole source or a time window of it (``scope_of``)."""
+    source, ms = int(source), int(ms)
+    if not 0 <= source < TAG_MAX_SOURCE:
+        raise ValueError(f"source {source} outside [0, 2^22)")
+    if not 0 <= ms < TAG_MAX_MS:
+        raise ValueError(f"ms {ms} outside [0, 2^40)")
+    return (source << TAG_MS_BITS) | ms
+
+
+def scope_of(source: int, t0_ms: Optional[int] = None, t1_ms: Optional[int] = None) -> Tuple[int, int]:
+    """The inclusive tag range ``(lo, hi)`` of source ``source`` between ``t0_ms`` and ``t1_ms`` (both inclusive;
+    ``None`` = from its start / to its end).  ``scope_of(3)`` is all of video 3:
+    ``(3 << 40, (3 << 40) | (2^40 - 1))``; ``scope_of(3, 180_000, 300_000)`` is video 3 between 180 s and 300 s.
+    ``t0_ms > t1_ms`` is a valid, empty scope."""
+    lo = make_tag(source, 0 if t0_ms is None else t0_ms)
+    hi = make_tag(source, TAG_MAX_MS - 1 if t1_ms is None else t1_ms)
+    return lo, hi
+
+
 def _torch_dtype(name: str):
     return {"f16": torch.float16, "bf16": torch.bfloat16}[name]
 
 
 class EmbeddingMemory:
     def __init__(self, capacity: int, dim: int, dtype: str = "f16", ring: bool = False, device: int = 0,
-                 graph_uuid: Optional[str] = None, grouped: bool = False):
+                 graph_uuid: Optional[str] = None, grouped: bool = False, tagged: bool = False):
         self.ctx = _lib.Context.get(device)
         self.L = self.ctx.L
         self.device = torch.device("cuda", device)
@@ -40,6 +74,11 @@ class EmbeddingMemory:
         self.ring = bool(ring)
         self.graph_uuid = graph_uuid
         self.grouped = bool(grouped)
+        self.tagged = bool(tagged)
+        self._next_source = 0       # new_source
+        self._sws = None            # scoped top-k workspace (vm_topk_scoped_workspace_bytes), grown on demand
+        self._sflags = None         # per-query flags of the last scoped call (device int32)
+        self._suncert = None        # queries the scoped fast path could not certify (device int32, accumulates)
         self._next_group_key = 0    # above every key appended from host values (new_group_key)
         self._last_keys_dev = None  # keys of the last grouped append when they were a device tensor (host: unknown)
         self._gws = None            # grouped top-k workspace (vm_topk_grouped_workspace_bytes), grown on demand
@@ -52,9 +91,13 @@ class EmbeddingMemory:
         self.meta: List[Optional[dict]] = []
         self.table_base = 0
         h = C.c_void_p()
-        create = self.L.vm_memory_create_grouped if self.grouped else self.L.vm_memory_create
-        self.ctx.check(create(self.ctx.handle, self.capacity, self.dim, _lib.DTYPES[dtype], 1 if ring else 0,
-                              C.byref(h)))
+        if self.tagged:
+            self.ctx.check(self.L.vm_memory_create_tagged(self.ctx.handle, self.capacity, self.dim, _lib.DTYPES[dtype],
+                                                          1 if ring else 0, 1 if self.grouped else 0, C.byref(h)))
+        else:  # exactly the calls an untagged memory made before tags existed
+            create = self.L.vm_memory_create_grouped if self.grouped else self.L.vm_memory_create
+            self.ctx.check(create(self.ctx.handle, self.capacity, self.dim, _lib.DTYPES[dtype], 1 if ring else 0,
+                                  C.byref(h)))
         self.handle = h
         self._scratch = TopkScratch(self.device)
 
@@ -89,20 +132,33 @@ class EmbeddingMemory:
         return rows.to(device=self.device, dtype=self.dtype).contiguous()
 
     def append(self, rows, ids: Optional[Sequence[str]] = None, meta: Optional[Sequence[dict]] = None,
-               group=None) -> int:
+               group=None, tag=None) -> int:
         """Append rows; return the id of the first.  Grouped memories: ``group`` is one key for every row, or one key
         per row (a sequence or an int64 tensor); omitted = this call is one new group (``new_group_key``, never equal to
         the previous call's last key).  A group is a run of consecutive rows with equal keys, so a call whose first key
         equals the previous call's last key continues that group.  A group is searched fast while a query's candidate
         groups hold at most 4,096 rows together (k = 10: about 220 rows per group); larger groups, such as a whole video
-        appended in one call, are answered by the exhaustive search every time (exact, slower: DESIGN.md 11)."""
+        appended in one call, are answered by the exhaustive search every time (exact, slower: DESIGN.md 11).
+
+        Tagged memories: ``tag`` is one int for every row, or one per row (a sequence or an int64 tensor; a device
+        tensor is passed through without a host read); omitted = the rows carry INT64_MIN, which only a scope that
+        starts at INT64_MIN matches."""
         t = self._as_rows(rows)
         B = t.shape[0]
         if ids is not None and len(ids) != B:
             raise ValueError("ids and rows differ in length")
         keys = self._group_keys_for(B, group)
+        tags = self._tags_for(B, tag)
         first = C.c_int64(0)
-        if keys is None:
+        if tags is not None:
+            self.ctx.check(self.L.vm_memory_append_tagged(self.handle, C.c_void_p(t.data_ptr()), B,
+                                                          C.c_void_p(tags.data_ptr()),
+                                                          C.c_void_p(keys.data_ptr() if keys is not None else 0),
+                                                          C.byref(first), _lib.current_stream_ptr()))
+            tags.record_stream(torch.cuda.current_stream())
+            if keys is not None:
+                keys.record_stream(torch.cuda.current_stream())
+        elif keys is None:
             self.ctx.check(self.L.vm_memory_append(self.handle, C.c_void_p(t.data_ptr()), B, C.byref(first),
                                                    _lib.current_stream_ptr()))
         else:
@@ -116,6 +172,27 @@ class EmbeddingMemory:
         self.meta.extend(list(meta) if meta is not None else [None] * B)
         self._trim_tables()
         return int(first.value)
+
+    def new_source(self) -> int:
+        """A source index no earlier ``new_source`` call of this memory returned: one per video (``make_tag``)."""
+        src = self._next_source
+        self._next_source += 1
+        return src
+
+    def _tags_for(self, B: int, tag) -> Optional[torch.Tensor]:
+        if tag is None:
+            return None
+        if not self.tagged:
+            raise ValueError("tags need a tagged memory (EmbeddingMemory(..., tagged=True))")
+        if isinstance(tag, torch.Tensor) and tag.dim() > 0:
+            tags = tag.to(device=self.device, dtype=torch.int64).reshape(-1).contiguous()
+        elif isinstance(tag, (list, tuple)) or (hasattr(tag, "shape") and len(getattr(tag, "shape")) > 0):
+            tags = torch.tensor([int(x) for x in tag], dtype=torch.int64).to(self.device)
+        else:
+            tags = torch.full((B,), int(tag), dtype=torch.int64, device=self.device)
+        if tags.numel() != B:
+            raise ValueError(f"{tags.numel()} tags for {B} rows")
+        return tags
 
     def new_group_key(self) -> int:
         """A key no earlier ``new_group_key`` call of this memory returned (and above every key appended so far from
@@ -182,6 +259,7 @@ class EmbeddingMemory:
     def reset(self):
         self.ctx.check(self.L.vm_memory_reset(self.handle, _lib.current_stream_ptr()))
         self._next_group_key = 0
+        self._next_source = 0
         self._last_keys_dev = None
         self.ids.clear()
         self.meta.clear()
@@ -292,6 +370,84 @@ class EmbeddingMemory:
         q.record_stream(torch.cuda.current_stream())
         return scores, rows, keys
 
+    def prepare_topk_scoped(self, Q: int, k: int) -> None:
+        """Size the scoped top-k workspace for (Q, k) now (before a graph capture: a capture must not allocate)."""
+        need = int(self.L.vm_topk_scoped_workspace_bytes(self.handle, int(Q), int(k)))
+        if self._sws is None or self._sws.numel() < need:
+            self._sws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
+        if self._sflags is None or self._sflags.numel() < Q:
+            self._sflags = torch.zeros(max(Q, 1), dtype=torch.int32, device=self.device)
+        if self._suncert is None:
+            self._suncert = torch.zeros(1, dtype=torch.int32, device=self.device)
+
+    def _scope_tensor(self, scope, Q: int) -> torch.Tensor:
+        """-> device int64 [2, Q] (row 0 = lo, row 1 = hi) from one (lo, hi), Q pairs, or an int64 [Q, 2] tensor (a
+        device tensor is not read on the host)."""
+        if isinstance(scope, torch.Tensor):
+            if scope.dtype != torch.int64 or scope.dim() != 2 or scope.shape[1] != 2:
+                raise ValueError("a scope tensor must be int64 [Q, 2]")
+            if scope.shape[0] != Q:
+                raise ValueError(f"{scope.shape[0]} scopes for {Q} queries")
+            return scope.to(self.device).t().contiguous()
+        pairs = list(scope)
+        if len(pairs) == 2 and not hasattr(pairs[0], "__len__"):
+            pairs = [pairs] * Q
+        if len(pairs) != Q:
+            raise ValueError(f"{len(pairs)} scopes for {Q} queries")
+        if any(len(p) != 2 for p in pairs):
+            raise ValueError("a scope is a pair (lo, hi)")
+        vals = [[int(p[0]) for p in pairs], [int(p[1]) for p in pairs]]
+        return torch.tensor(vals, dtype=torch.int64).to(self.device)
+
+    def topk_scoped(self, queries, k: int, scope, min_score: Optional[float] = None,
+                    score_mode: int = _lib.VM_SCORE_RAW, exact: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+        """-> (scores [Q,k] float64, rows [Q,k] int64): the k best rows of a tagged memory whose tag lies in the query's
+        scope, an inclusive range ``(lo, hi)``: one for all queries, a sequence of Q pairs, or an int64 ``[Q, 2]`` tensor
+        (``scope_of`` builds the range of a video or of a time window of it).
+
+        The exhaustive row ranking of ``topk`` (score desc, row asc; score mapping and > min_score filter) over the
+        in-scope rows only; -1 / 0.0 padded; an empty scope gives an all-padded row.  Always the exhaustive answer: the
+        fp32 fast path redoes the queries it cannot certify on the device, in the same call (csrc/topk_scope.hip).
+        ``exact=True`` scores every in-scope pair exactly (slow).  1 <= k <= 64.  The per-query flags of the last call
+        (why a query was redone, vm_topk_flag) are in ``last_scope_flags``."""
+        if not self.tagged:
+            raise ValueError("topk_scoped needs a tagged memory (EmbeddingMemory(..., tagged=True))")
+        if not 1 <= int(k) <= 64:
+            raise ValueError(f"scoped top-k supports 1 <= k <= 64, got {k}")
+        q = self._as_rows(queries)
+        Q = q.shape[0]
+        sc = self._scope_tensor(scope, Q)
+        self.prepare_topk_scoped(Q, k)
+        scores = torch.empty((Q, k), dtype=torch.float64, device=self.device)
+        rows = torch.empty((Q, k), dtype=torch.int64, device=self.device)
+        st = _lib.current_stream_ptr()
+        use_min = 0 if min_score is None else 1
+        ms = 0.0 if min_score is None else float(min_score)
+        lo, hi = C.c_void_p(sc[0].data_ptr()), C.c_void_p(sc[1].data_ptr())
+        if exact:
+            self.ctx.check(self.L.vm_topk_cosine_scoped_exact(
+                self.handle, C.c_void_p(q.data_ptr()), Q, int(k), lo, hi, use_min, ms, int(score_mode), 1, 0,
+                C.c_void_p(scores.data_ptr()), C.c_void_p(rows.data_ptr()),
+                C.c_void_p(self._sws.data_ptr()), self._sws.numel(), st))
+        else:
+            self.ctx.check(self.L.vm_topk_cosine_scoped(
+                self.handle, C.c_void_p(q.data_ptr()), Q, int(k), lo, hi, use_min, ms, int(score_mode), 1, 0,
+                C.c_void_p(scores.data_ptr()), C.c_void_p(rows.data_ptr()),
+                C.c_void_p(self._suncert.data_ptr()), C.c_void_p(self._sflags.data_ptr()),
+                C.c_void_p(self._sws.data_ptr()), self._sws.numel(), st))
+        q.record_stream(torch.cuda.current_stream())
+        sc.record_stream(torch.cuda.current_stream())
+        return scores, rows
+
+    @property
+    def last_scope_flags(self) -> Optional[torch.Tensor]:
+        return self._sflags
+
+    @property
+    def scoped_uncertified_count(self) -> int:
+        """Queries the scoped fast path redid exhaustively since this memory was created (synchronises)."""
+        return 0 if self._suncert is None else int(self._suncert.item())
+
     @property
     def last_group_flags(self) -> Optional[torch.Tensor]:
         return self._gflags
@@ -361,12 +517,26 @@ class EmbeddingMemory:
             keys = torch.cat([keys[head:], keys[:head]])
         return keys.cpu().numpy().astype(np.int64)
 
+    def tags_host(self):
+        """int64 [n]: the tag of every searchable row in row-id order (tagged memories; host copy)."""
+        import numpy as np
+        if not self.tagged:
+            raise ValueError("not a tagged memory")
+        total, n = len(self), self.searchable
+        tags = _tensor_from_ptr(self.L.vm_memory_tags(self.handle), (n,), torch.int64, self.device)
+        if self.ring and total > self.capacity:
+            head = total % self.capacity
+            tags = torch.cat([tags[head:], tags[:head]])
+        return tags.cpu().numpy().astype(np.int64)
+
     def snapshot(self, path: str) -> None:
         import json
         import numpy as np
         base, rows = self.rows_host()
         total = base + rows.shape[0]
         extra = {"group_keys": self.group_keys_host()} if self.grouped else {}  # optional field: old files have none
+        if self.tagged:
+            extra["tags"] = self.tags_host()  # optional too: files without it restore untagged
         np.savez(path, rows=rows, dtype=self.dtype_name, dim=self.dim,
                  first_row_id=base, graph_uuid=self.graph_uuid or "",
                  ids=json.dumps([self.id_of(r) for r in range(base, total)]),
@@ -376,19 +546,26 @@ class EmbeddingMemory:
     def restore(cls, path: str, capacity: Optional[int] = None, ring: bool = False, device: int = 0
                 ) -> "EmbeddingMemory":
         """Row ids restart at 0 in the restored memory (ids / meta tables are restored in the same order).  A snapshot
-        of a grouped memory restores grouped, with its key column (a group cut by a ring's window keeps its rows)."""
+        of a grouped memory restores grouped, with its key column (a group cut by a ring's window keeps its rows); one
+        of a tagged memory restores tagged, with its tags."""
         import json
         import numpy as np
         z = np.load(path, allow_pickle=False)
         rows = torch.from_numpy(z["rows"].view(np.int16))
         dtype = str(z["dtype"])
         keys = z["group_keys"] if "group_keys" in z.files else None
+        tags = z["tags"] if "tags" in z.files else None
+        tagged_kw = {} if tags is None else {"tagged": True}
         mem = cls(capacity or max(rows.shape[0], 1), int(z["dim"]), dtype, ring=ring, device=device,
-                  graph_uuid=str(z["graph_uuid"]) or None, grouped=keys is not None)
+                  graph_uuid=str(z["graph_uuid"]) or None, grouped=keys is not None, **tagged_kw)
         if rows.shape[0]:
             group = None if keys is None else torch.from_numpy(keys.astype(np.int64))
+            tag_kw = {} if tags is None else {"tag": torch.from_numpy(tags.astype(np.int64))}
             mem.append(rows.view(_torch_dtype(dtype)), ids=json.loads(str(z["ids"])), meta=json.loads(str(z["meta"])),
-                       group=group)
+                       group=group, **tag_kw)
+            if tags is not None and tags.size:  # sources handed out after a restore do not collide with stored ones
+                real = tags[tags >= 0]
+                mem._next_source = int(real.max() >> TAG_MS_BITS) + 1 if real.size else 0
             if keys is not None and keys.size:
                 mem._next_group_key = max(0, int(keys.max()) + 1)
         return mem

@@ -54,8 +54,17 @@ def _check_distinct(memory: EmbeddingMemory, distinct: bool) -> None:
         raise ValueError("distinct=True needs a grouped memory (EmbeddingMemory(..., grouped=True), memory.group_by: chunk)")
 
 
-def batch_similarities(memory: EmbeddingMemory, chunk_embeddings: Sequence, top_k: int, distinct: bool = False
-                       ) -> List[List[Tuple[str, float]]]:
+def _check_scope(memory: EmbeddingMemory, scope, distinct: bool) -> None:
+    if scope is None:
+        return
+    if distinct:
+        raise ValueError("scope together with distinct=True is not supported: the scoped search ranks rows, not groups")
+    if not getattr(memory, "tagged", False):
+        raise ValueError("scope needs a tagged memory (EmbeddingMemory(..., tagged=True), memory.tag_by: time)")
+
+
+def batch_similarities(memory: EmbeddingMemory, chunk_embeddings: Sequence, top_k: int, distinct: bool = False,
+                       scope=None) -> List[List[Tuple[str, float]]]:
     """One batched top-k launch for every non-failed query; result re-threaded into the reference's list shape.
 
     A query whose length differs from the stored vectors' scores 0.0 against EVERY row in the reference
@@ -64,8 +73,13 @@ def batch_similarities(memory: EmbeddingMemory, chunk_embeddings: Sequence, top_
     with score 0.0.  That is reproduced on the host (no arithmetic involved) instead of raising.
 
     ``distinct=True`` (grouped memories): at most one hit per group - the best frame of each of the ``top_k`` best
-    chunks (EmbeddingMemory.topk_grouped); the wrong-length rule above still lists the first rows."""
+    chunks (EmbeddingMemory.topk_grouped); the wrong-length rule above still lists the first rows.
+
+    ``scope`` (tagged memories): one inclusive tag range ``(lo, hi)`` for every query (memory.scope_of) - the
+    reference's ``{graph_uuid: $graph_uuid}`` predicate; only in-scope rows are ranked (EmbeddingMemory.topk_scoped), and
+    the wrong-length rule lists the first in-scope rows.  ``None`` = the whole memory, as before."""
     _check_distinct(memory, distinct)
+    _check_scope(memory, scope, distinct)
     ok_idx = [i for i, e in enumerate(chunk_embeddings) if not isinstance(e, Exception) and e is not None]
     out: List[List[Tuple[str, float]]] = [[] for _ in chunk_embeddings]
     if not ok_idx or memory.searchable == 0 or top_k <= 0:
@@ -73,7 +87,12 @@ def batch_similarities(memory: EmbeddingMemory, chunk_embeddings: Sequence, top_
     wrong = [i for i in ok_idx if _length(chunk_embeddings[i]) != memory.dim]
     if wrong:
         first_row = len(memory) - memory.searchable
-        zeros = [(memory.id_of(first_row + j), 0.0) for j in range(min(top_k, memory.searchable))]
+        if scope is None:
+            zeros = [(memory.id_of(first_row + j), 0.0) for j in range(min(top_k, memory.searchable))]
+        else:
+            tags = memory.tags_host()
+            hit = ((tags >= int(scope[0])) & (tags <= int(scope[1]))).nonzero()[0][:top_k]
+            zeros = [(memory.id_of(first_row + int(j)), 0.0) for j in hit]
         for i in wrong:
             out[i] = list(zeros)
         ok_idx = [i for i in ok_idx if i not in set(wrong)]
@@ -84,7 +103,9 @@ def batch_similarities(memory: EmbeddingMemory, chunk_embeddings: Sequence, top_
         q = torch.stack([chunk_embeddings[i] for i in ok_idx])
     else:
         q = torch.tensor([list(chunk_embeddings[i]) for i in ok_idx], dtype=torch.float32)
-    if distinct:
+    if scope is not None:
+        scores, rows = memory.topk_scoped(q, top_k, scope)
+    elif distinct:
         scores, rows, _ = memory.topk_grouped(q, top_k)
     else:
         scores, rows = memory.topk(q, top_k)
@@ -97,18 +118,23 @@ def batch_similarities(memory: EmbeddingMemory, chunk_embeddings: Sequence, top_
 class HipPreLLMSimilarity:
     """Mixin / stand-alone object for PreLLMInjector: set ``self.memory`` and ``self.embedder_config``."""
 
-    def __init__(self, memory: EmbeddingMemory, embedder_config: Any, distinct: bool = False):
+    def __init__(self, memory: EmbeddingMemory, embedder_config: Any, distinct: bool = False, scope=None):
+        """``scope``: an inclusive tag range ``(lo, hi)`` (memory.scope_of) every search of this object is restricted to
+        - the reference's ``WHERE c.graph_uuid = $graph_uuid`` (src/components/pre_llm_injector.py:395-396); tagged memory
+        only, not together with ``distinct``.  ``None`` = the whole memory."""
         _check_distinct(memory, distinct)
+        _check_scope(memory, scope, distinct)
         self.memory = memory
         self.embedder_config = embedder_config
         self.distinct = bool(distinct)
+        self.scope = scope
 
     async def _calculate_batch_similarities(self, chunk_embeddings, neo4j_handler=None
                                             ) -> List[List[Tuple[str, float]]]:
         try:
             return batch_similarities(self.memory, chunk_embeddings,
                                       self.embedder_config.top_k_chunk_with_batch_similarity,
-                                      distinct=getattr(self, "distinct", False))
+                                      distinct=getattr(self, "distinct", False), scope=getattr(self, "scope", None))
         except _lib.VidmemError as e:
             if e.code == _lib.VM_ERR_INVALID:
                 raise
@@ -131,7 +157,8 @@ class HipVectorSearch:
     """Mixin / stand-alone object for HybridRetriever's vector leg."""
 
     def __init__(self, memory: EmbeddingMemory, embedder: Any, config: Any, *, score_mode: int,
-                 min_score: float = 0.3, splitter: Optional[Callable[[str], List[str]]] = None, distinct: bool = False):
+                 min_score: float = 0.3, splitter: Optional[Callable[[str], List[str]]] = None, distinct: bool = False,
+                 scope=None):
         """``score_mode`` is REQUIRED (keyword): the reference filters on Neo4j's
         ``vector.similarity.cosine(...) > 0.3`` (src/pipeline/retriever_hybrid.py:296-298), a third-party function of an
         unpinned server image whose value may be the raw cosine or its [0,1] mapping (1+cos)/2 - with the literal 0.3
@@ -139,7 +166,10 @@ class HipVectorSearch:
         SURVEY.md 8 a10), so the integrator states which one their deployment had: ``_lib.VM_SCORE_RAW`` or
         ``_lib.VM_SCORE_UNIT_INTERVAL``; ``min_score`` (default: the reference's literal) is compared AFTER the mapping.
         ``distinct=True`` (grouped memory only, else ValueError): at most one hit per chunk - ``top_k_chunks`` distinct
-        chunks, each represented by its best frame (EmbeddingMemory.topk_grouped)."""
+        chunks, each represented by its best frame (EmbeddingMemory.topk_grouped).
+        ``scope``: an inclusive tag range ``(lo, hi)`` (memory.scope_of) the search is restricted to - the reference's
+        ``MATCH (c:Chunk {graph_uuid: $graph_uuid})`` (src/pipeline/retriever_hybrid.py:295); tagged memory only, not
+        together with ``distinct`` (ValueError).  ``None`` = the whole memory."""
         if score_mode not in (_lib.VM_SCORE_RAW, _lib.VM_SCORE_UNIT_INTERVAL):
             raise ValueError("score_mode must be VM_SCORE_RAW or VM_SCORE_UNIT_INTERVAL")
         # an embedder that states its width (HipTextEmbedder, FrameEncoder-backed ones) must match the memory's rows: a
@@ -149,14 +179,19 @@ class HipVectorSearch:
             raise ValueError(f"embedder out_dim {out_dim} != memory.dim {memory.dim}: build the memory with the matching "
                              "image encoder (text questions: encoder.arch clip_l14_336_joint)")
         _check_distinct(memory, distinct)
+        _check_scope(memory, scope, distinct)
         self.memory, self.embedder, self.config = memory, embedder, config
         self.distinct = bool(distinct)
+        self.scope = scope
         self.min_score, self.score_mode, self.splitter = min_score, score_mode, splitter
 
     async def _vector_search_chunks(self, session, query) -> List[Dict[str, Any]]:
         try:
             query_embedding = await self.embedder.aembed_query(query)
-            if self.distinct:
+            if getattr(self, "scope", None) is not None:
+                scores, rows = self.memory.topk_scoped([query_embedding], self.config.top_k_chunks, self.scope,
+                                                       min_score=self.min_score, score_mode=self.score_mode)
+            elif self.distinct:
                 scores, rows, _ = self.memory.topk_grouped([query_embedding], self.config.top_k_chunks,
                                                            min_score=self.min_score, score_mode=self.score_mode)
             else:
