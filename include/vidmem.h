@@ -182,8 +182,9 @@ int64_t vm_memory_capacity(const vm_memory *mem);
 int vm_memory_dim(const vm_memory *mem);
 int vm_memory_reset(vm_memory *mem, void *stream);
 /* Re-read the DEVICE row counter into the host mirror and return it (negative = vm_status).  Needed after hipGraph
- * replays of vm_memory_append (they advance only the device counter) and after a graph CAPTURE of it (which advanced
- * only the host mirror).  Synchronises `stream`; not capturable.  The reference has no counterpart (its store is a
+ * replays of vm_memory_append (they advance only the device counter), after a graph CAPTURE of it (which advanced
+ * only the host mirror) and after every vm_memory_append_novel, eager or replayed (how many rows it keeps is decided on
+ * the device, so it never advances the mirror).  Synchronises `stream`; not capturable.  The reference has no counterpart (its store is a
  * database, src/components/neo4j_handler.py:229-242); this is the price of the capturable append. */
 int64_t vm_memory_sync(vm_memory *mem, void *stream);
 const void *vm_memory_rows(const vm_memory *mem); /* device pointer to the [capacity, D] row store          */
@@ -221,6 +222,43 @@ int vm_memory_create_tagged(vm_ctx *ctx, int64_t capacity_rows, int D, int dtype
 int vm_memory_append_tagged(vm_memory *mem, const void *rows, int B, const int64_t *tags, const int64_t *keys,
                             int64_t *out_first_row_host, void *stream);
 const int64_t *vm_memory_tags(const vm_memory *mem);
+
+/* ---- novelty-gated append ------------------------------------------------------------------------------
+ * Store a row only when nothing resembles it: video is redundant, and a static shot appends rows that are one vector up
+ * to noise.  The reference has no counterpart (it stores one text embedding per chunk,
+ * src/components/neo4j_handler.py:229-242); decisions are taken on the reference cosine of vm_topk_cosine (fp64, one
+ * rounding per product and partial sum, left to right, zero-norm guard) on the 16-bit values, bit for bit.
+ * rows [B, D] dtype, 1 <= B <= 4096 (VM_ERR_UNSUPPORTED above; B = 0 is a no-op that writes *out_count = 0).
+ * known_scores / known_rows: what the caller already knows about each row - the best RAW cosine of rows[i] against
+ * whatever part of the memory it searched and the row that reached it (< 0: nothing found) - device arrays read at
+ * element i * known_stride, so column 0 of a [B, k] top-k result is passed in place; both NULL = nothing known (the gate
+ * is then among the batch only); one NULL and one not is VM_ERR_INVALID.  In row order:
+ *   suppressor(i) = known_rows[i]   if known_rows[i] >= 0 and known_scores[i] > threshold
+ *                 = row_of[j], j the LOWEST j < i with keep[j] and cosine(rows[i], rows[j]) > threshold, if there is one
+ *   keep[i]   = no suppressor           (`>` is strict, like use_min_score: a score equal to the threshold keeps the row)
+ *   row_of[i] = suppressor(i), or, when kept, the id rows[i] receives: (rows before the call) + (kept rows before i)
+ * The kept rows are appended in batch order exactly as vm_memory_append[_grouped|_tagged] appends that sub-batch: row
+ * bytes, norms, ring slots, tags (tags NULL on a tagged memory: INT64_MIN), group keys and ordinals (keys NULL on a
+ * grouped memory: every kept row its own group; a run of equal keys among the KEPT rows is one group and continues the
+ * previous call's open group under vm_memory_append_grouped's rule).  tags / keys on a memory without that column:
+ * VM_ERR_INVALID.  A call that keeps nothing leaves every column, the row counter and the group state untouched;
+ * threshold >= 2 keeps everything; a NaN threshold is VM_ERR_INVALID.
+ * With known_* = the exact top-1 of every row over the whole memory before the call, and no stored row overwritten
+ * during the call, the result equals the loop "search the memory as it stands, append one row iff its best score is not
+ * above the threshold".  In a ring that wraps inside the call the rule above holds as written.
+ * out_keep int32 [B] (0 / 1), out_row_of int64 [B], out_count int32 [1] (kept rows of THIS call, rewritten): device,
+ * each may be NULL.  No allocation, no synchronisation, no host read-back; launches are sized from B, the row counter
+ * is read on the device: capturable, e.g. {vm_topk_cosine, vm_topk_redo_flagged, vm_memory_append_novel} in one graph.
+ * Host mirror: the library cannot know the kept count, so vm_memory_size is NOT advanced - vm_memory_sync brings it in
+ * line.  On a memory that is not a ring the call is refused with VM_ERR_NOMEM when mirror + B exceeds the capacity (the
+ * worst case; the mirror must therefore be current); whatever the mirror said, no slot at or beyond the capacity is
+ * written and the counter never moves past it.
+ * Workspace: vm_novelty_workspace_bytes (B x 8 bytes of norms + B x ceil(B / 64) x 8 bytes of pair bits + 2 KiB). */
+size_t vm_novelty_workspace_bytes(const vm_memory *mem, int B);
+int vm_memory_append_novel(vm_memory *mem, const void *rows, int B, double threshold, const double *known_scores,
+                           const int64_t *known_rows, int64_t known_stride, const int64_t *tags, const int64_t *keys,
+                           int32_t *out_keep, int64_t *out_row_of, int32_t *out_count, void *workspace,
+                           size_t workspace_bytes, void *stream);
 
 /* ---- cosine top-k over the memory ---------------------------------------------------------------------
  * Replaces PreLLMInjector._calculate_batch_similarities + _cosine_similarity

@@ -13,7 +13,7 @@ Keys the hot path honours (same names and defaults as the reference where it has
   retrieval.top_k = 5, top_k_chunks = 8, compression_threshold = 0.7               src/core/config.py:70-86
 New:
   encoder: {arch, dtype, weights, seed, device, top_k, look_ahead_chunks}   which vision encoder stands where the remote VLM was
-  memory:  {capacity, ring, dtype, snapshot}               the HBM-resident store that stands where Chunk.embedding was
+  memory:  {capacity, ring, dtype, snapshot, group_by, tag_by, novelty_threshold}   the HBM-resident store that stands where Chunk.embedding was
   text_encoder: {arch, dtype, weights, seed, device, tokenizer}   the question embedder of the retriever (arch null = none;
            read through section(), so it never appears in a config that does not name it)
 """
@@ -41,6 +41,8 @@ MEMORY_DEFAULTS: Dict[str, Any] = {
     "group_by": None,        # "chunk": a grouped memory (one group per video chunk) for distinct-chunk search; None = plain
     "tag_by": None,          # "time": a tagged memory - every frame row carries (video, chunk start in ms), so a search can
                              # name one video or a time window of it (memory.scope_of); None = untagged
+    "novelty_threshold": None,  # a float: a frame is stored only when no stored frame and no earlier kept frame of its
+                             # chunk scores above it (EmbeddingMemory.append_novel); None = every frame is stored
 }
 TEXT_ENCODER_DEFAULTS: Dict[str, Any] = {
     "arch": None,            # specs.TEXT_SPECS key (clip_l14_text); None = no text encoder is built

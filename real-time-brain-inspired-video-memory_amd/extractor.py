@@ -15,6 +15,10 @@ Mirrors ``VLMExtractor`` (src/pipeline/vlm_extractor.py):
   * where the reference POSTs JPEGs to a remote VLM (:121-185), this encodes the frames on the GPU, retrieves the top-k
     most similar stored frames and appends the new embeddings to the memory.
 
+  * ``config.memory.novelty_threshold`` (default null): a frame is stored only when nothing resembles it
+    (EmbeddingMemory.append_novel); ``embedding_rows`` then lists the row that stands for each frame and every chunk
+    gains ``stored_frames``.
+
 ONE deliberate deviation, decided here and nowhere else: the reference shrinks frames taller than 720 rows with
 ``cv2.resize`` before JPEG-encoding them (:114-116) - a payload optimisation for the HTTP call.  This path has no
 payload: the preprocess kernel resamples the ORIGINAL frame to the encoder's input size in one bilinear pass
@@ -281,6 +285,13 @@ class FrameEmbeddingExtractor:
             # (source, the chunk's start in ms); the neighbour search below stays unscoped
             tagged = bool(getattr(self.memory, "tagged", False))
             source = self.memory.new_source() if tagged else None
+            # memory.novelty_threshold (default None = off): a frame is stored only when nothing resembles it
+            # (EmbeddingMemory.append_novel).  Every group then takes the chunk-by-chunk path below: the look-ahead
+            # group still goes through one encoder call, search and append run per chunk, and every chunk's append
+            # synchronises once (it reads which frames were kept) - the price of an offline clip; the streaming session
+            # is the real-time path.  A gated batched group search is not built.
+            tau = getattr(cfgmod.section(self.config, "memory", cfgmod.MEMORY_DEFAULTS), "novelty_threshold", None)
+            gated = tau is not None
             # Look-ahead groups (config.encoder.look_ahead_chunks, default 0 = auto, 1 = the reference's one chunk at a time,
             # :44-74): the frames of N consecutive chunks go through ONE encoder call - the encoder fills the chip only
             # from a few hundred frames up - and then every chunk of the group, in chunk order, gets its own top-k
@@ -360,6 +371,7 @@ class FrameEmbeddingExtractor:
                                                 for s, r in zip(s_row, r_row) if r >= 0])
                         off += n
                     chunk_time = group_time / len(live)
+                    gate_fields = {"stored_frames": c["stored"]} if gated else {}
                     results.append({
                         "time": c["time"],
                         "content": f"[{c['nframes']} frame embeddings]",
@@ -367,8 +379,11 @@ class FrameEmbeddingExtractor:
                         "processing_time": chunk_time,
                         "group_time": group_time,
                         "group_chunks": len(live),
-                        "embedding_rows": list(range(c["first"], c["first"] + c["nframes"])),
+                        # gated: the row that stands for each frame - its own, or the one that suppressed it
+                        "embedding_rows": (c["row_of"] if gated else
+                                           list(range(c["first"], c["first"] + c["nframes"]))),
                         "similar": similar,
+                        **gate_fields,
                     })
                     # serialised here, while the GPU works on the next group, not in one piece after the last one
                     result_lines.append(json.dumps(results[-1], default=str))
@@ -421,7 +436,7 @@ class FrameEmbeddingExtractor:
                     # One search for the whole group when that is provably the same thing: every chunk of the group still
                     # sees exactly "the memory before the group + the group's earlier chunks", i.e. no row of the memory is
                     # overwritten while the group is appended (not a ring, or a ring that does not wrap inside the group).
-                    batched = (len(grp) > 1 and emb_all is not None and self.top_k > 0 and emb_all.is_cuda and
+                    batched = (not gated and len(grp) > 1 and emb_all is not None and self.top_k > 0 and emb_all.is_cuda and
                                (not self.memory.ring or len(self.memory) + total <= self.memory.capacity))
                     if batched:
                         grp_s, grp_r = self._group_search(emb_all, counts)
@@ -451,7 +466,14 @@ class FrameEmbeddingExtractor:
                             c["meta"][0]["source"] = source   # one dict for the chunk's rows
                             c["tag"] = make_tag(source, int(start / fps * 1000.0))
                             tag_kw = {"tag": c["tag"]}
-                        if not batched:
+                        if gated:
+                            # the chunk's own search is what the gate knows about the memory; an unsearched chunk
+                            # (empty memory, top_k 0) lets append_novel search
+                            how = {"known": (scores, rows)} if c["searched"] else {"against": "memory"}
+                            nov = self.memory.append_novel(emb, tau, ids=ids, meta=c["meta"], **how, **tag_kw)
+                            c["row_of"] = [int(r) for r in nov.row_of.tolist()]
+                            c["stored"] = int(nov.kept)
+                        elif not batched:
                             c["first"] = self.memory.append(emb, ids=ids, meta=c["meta"], **tag_kw)
                     if batched:      # one append for the group: rows, ids and meta in chunk order
                         live = [c for c in chunks if c["nframes"]]

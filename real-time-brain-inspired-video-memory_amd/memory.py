@@ -16,12 +16,13 @@ holds many videos: ``topk_scoped`` ranks only the rows whose tag lies in the que
 counterpart of the reference's ``{graph_uuid: $graph_uuid}`` predicate (include/vidmem.h).
 
 All arithmetic is in libvidmem.so (csrc/memory.hip, csrc/topk.hip, csrc/topk_exact.hip, csrc/topk_group.hip,
-csrc/topk_scope.hip).
+csrc/topk_scope.hip, csrc/novelty.hip).
 """
 from __future__ import annotations
 
 import ctypes as C
-from typing import List, Optional, Sequence, Tuple
+import math
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -57,6 +58,17 @@ def scope_of(source: int, t0_ms: Optional[int] = None, t1_ms: Optional[int] = No
     return lo, hi
 
 
+NOVEL_MAX_ROWS = 4096            # rows per vm_memory_append_novel call
+
+
+class Novelty(NamedTuple):
+    """What ``append_novel`` decided: ``keep`` bool [B] and ``row_of`` int64 [B] on the device (the row that stands for
+    each frame: its own new id when kept, the row that suppressed it otherwise), ``kept`` the number of stored rows."""
+    keep: torch.Tensor
+    row_of: torch.Tensor
+    kept: int
+
+
 def _torch_dtype(name: str):
     return {"f16": torch.float16, "bf16": torch.bfloat16}[name]
 
@@ -84,6 +96,7 @@ class EmbeddingMemory:
         self._gws = None            # grouped top-k workspace (vm_topk_grouped_workspace_bytes), grown on demand
         self._gflags = None         # per-query flags of the last grouped call (device int32)
         self._guncert = None        # queries the grouped fast path could not certify (device int32, accumulates)
+        self._nscratch = None       # buffers of the gated append (NoveltyScratch), grown on demand
         # Host tables: chunk id (reference pre_llm_injector.py:91) and {"time":..., "content":...} (for
         # _vector_search_chunks) of row (table_base + i).  table_base stays 0 unless a ring has wrapped far enough for
         # the slots of overwritten rows to be dropped (see _trim_tables); use id_of / meta_of for row -> entry.
@@ -172,6 +185,163 @@ class EmbeddingMemory:
         self.meta.extend(list(meta) if meta is not None else [None] * B)
         self._trim_tables()
         return int(first.value)
+
+    # ---- novelty-gated append (include/vidmem.h vm_memory_append_novel) -----------------------------
+    def prepare_append_novel(self, B: int) -> "NoveltyScratch":
+        """Size this memory's own gated-append buffers for batches of up to ``B`` rows now (before a graph capture: a
+        capture must not allocate)."""
+        if self._nscratch is None or not self._nscratch.fits(self, B):
+            self._nscratch = NoveltyScratch.for_(self, B)
+        return self._nscratch
+
+    @staticmethod
+    def _check_threshold(threshold) -> float:
+        tau = float(threshold)
+        if math.isnan(tau):
+            raise ValueError("the novelty threshold is NaN")
+        return tau
+
+    def _known_pair(self, known, B: int):
+        """``known=(scores, rows)``, each [B] or [B, k] -> (scores, rows, stride): device float64 / int64 tensors whose
+        element i * stride is row i's best score / the row that reached it (column 0 of a top-k result, in place)."""
+        if not isinstance(known, (tuple, list)) or len(known) != 2:
+            raise ValueError("known must be a pair (scores, rows)")
+        ks, kr = known
+        if not isinstance(ks, torch.Tensor) or not isinstance(kr, torch.Tensor):
+            raise ValueError("known scores and rows must be tensors")
+        if ks.dim() not in (1, 2) or kr.shape != ks.shape:
+            raise ValueError("known scores and rows must both be [B] or [B, k]")
+        if ks.shape[0] != B:
+            raise ValueError(f"known results for {ks.shape[0]} rows, batch of {B}")
+        if ks.dim() == 2:
+            if ks.shape[1] < 1:
+                raise ValueError("known results with k = 0")
+            ks, kr = ks[:, 0], kr[:, 0]
+        ks = ks.to(device=self.device, dtype=torch.float64)
+        kr = kr.to(device=self.device, dtype=torch.int64)
+        if B > 1 and (ks.stride(0) != kr.stride(0) or ks.stride(0) < 1):
+            ks, kr = ks.contiguous(), kr.contiguous()
+        return ks, kr, (int(ks.stride(0)) if B > 1 else 1)
+
+    def enqueue_append_novel(self, rows, threshold, known=None, group=None, tag=None,
+                             scratch: Optional["NoveltyScratch"] = None
+                             ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """The capturable gated append -> (keep int32 [B] 0 / 1, row_of int64 [B], count int32 [1]): views of the
+        buffers of ``scratch`` (default: this memory's own, ``prepare_append_novel``), valid until the next call on it.
+
+        Enqueues ``vm_memory_append_novel`` on the current stream: nothing is read on the host, the id / meta tables and
+        the host row count are not touched - ``sync()`` afterwards brings them in line (rows get ``None`` entries, as
+        after replays of ``append``).  ``known=(scores, rows)``: ``[B]`` or ``[B, k]`` tensors of a search the caller
+        already ran (RAW scores, no ``min_score``); ``None`` = the gate is among the batch only.  At most 4,096 rows.
+        Inside a graph capture pass ``group`` / ``tag`` as device tensors (rewritten in place between replays) and a
+        ``scratch`` the session owns."""
+        tau = self._check_threshold(threshold)
+        t = self._as_rows(rows)
+        B = t.shape[0]
+        if B > NOVEL_MAX_ROWS:
+            raise ValueError(f"a gated append takes at most {NOVEL_MAX_ROWS} rows per call, got {B}")
+        ks = kr = None
+        stride = 1
+        if known is not None:
+            ks, kr, stride = self._known_pair(known, B)
+        keys = self._group_keys_for(B, group)
+        tags = self._tags_for(B, tag)
+        return self._append_novel_call(t, tau, ks, kr, stride, keys, tags, scratch)
+
+    def _append_novel_call(self, t, tau, ks, kr, stride, keys, tags, scratch):
+        B = t.shape[0]
+        if scratch is None:
+            scratch = self.prepare_append_novel(B)
+        elif not scratch.fits(self, B):
+            raise ValueError("caller-owned novelty scratch is too small for this batch")
+        ptr = lambda x: C.c_void_p(x.data_ptr() if x is not None else 0)
+        self.ctx.check(self.L.vm_memory_append_novel(
+            self.handle, ptr(t), B, tau, ptr(ks), ptr(kr), int(stride), ptr(tags), ptr(keys), ptr(scratch.keep),
+            ptr(scratch.row_of), ptr(scratch.count), ptr(scratch.ws), scratch.ws.numel(), _lib.current_stream_ptr()))
+        cur = torch.cuda.current_stream()
+        for x in (t, ks, kr, keys, tags):
+            if x is not None:
+                x.record_stream(cur)
+        return scratch.keep[:B], scratch.row_of[:B], scratch.count
+
+    def append_novel(self, rows, threshold, against="memory", known=None, ids: Optional[Sequence[str]] = None,
+                     meta: Optional[Sequence[dict]] = None, group=None, tag=None) -> Novelty:
+        """Append only the rows that nothing resembles -> ``Novelty(keep, row_of, kept)``.
+
+        In row order a row is dropped when a stored row scores above ``threshold`` against it (``against``), or an
+        earlier KEPT row of the batch does; a score equal to the threshold keeps the row.  Scores are the reference
+        cosine of ``topk``, bit for bit, so this equals the one-row-at-a-time loop "search, append iff the best score
+        is not above the threshold" (include/vidmem.h vm_memory_append_novel).
+
+        ``against``: ``"memory"`` (default) = ``topk(rows, 1)`` over everything stored, redo included (skipped on an
+        empty memory); a scope ``(lo, hi)`` / Q pairs / int64 ``[B, 2]`` tensor on a tagged memory =
+        ``topk_scoped(rows, 1, scope)`` ("new for this video", "new within the last minute"); ``None`` = among the
+        batch only.  ``known=(scores, rows)``: ``[B]`` or ``[B, k]`` tensors of a search the caller already ran, used
+        INSTEAD of ``against`` - they must be RAW scores of a search without ``min_score``: a mapped or filtered score
+        would be compared with the threshold as if it were the cosine.
+        ``ids`` / ``meta``: one entry per row of the batch; only the kept rows' entries are recorded.  ``group`` /
+        ``tag``: as in ``append``, per row of the batch; ``group=None`` on a grouped memory = the kept rows of this
+        call are one new group.
+
+        This form SYNCHRONISES once per call: it reads ``keep`` back to extend the id / meta tables and brings the row
+        count in line (``enqueue_append_novel`` is the form that does not).  Batches above 4,096 rows are walked in
+        slices of 4,096, each slice searched after the previous one was appended; with ``known`` or ``against=None``
+        such a batch is refused (later slices would not be compared with the earlier ones)."""
+        tau = self._check_threshold(threshold)
+        whole = isinstance(against, str) and against == "memory"
+        if known is not None and not whole:
+            raise ValueError("known replaces the search: give known or against, not both")
+        scope = None
+        if known is None and against is not None and not whole:
+            if isinstance(against, str):
+                raise ValueError(f"against must be 'memory', a scope or None, got {against!r}")
+            if not self.tagged:
+                raise ValueError("a scope needs a tagged memory (EmbeddingMemory(..., tagged=True))")
+            scope = against
+        t = self._as_rows(rows)
+        B = t.shape[0]
+        if ids is not None and len(ids) != B:
+            raise ValueError("ids and rows differ in length")
+        if meta is not None and len(meta) != B:
+            raise ValueError("meta and rows differ in length")
+        ks = kr = None
+        stride = 1
+        if known is not None:
+            ks, kr, stride = self._known_pair(known, B)
+        if B > NOVEL_MAX_ROWS and (known is not None or against is None):
+            raise ValueError(f"more than {NOVEL_MAX_ROWS} rows need against='memory' or a scope")
+        sc = self._scope_tensor(scope, B).t() if scope is not None else None     # [B, 2] view
+        keys = self._group_keys_for(B, group)
+        tags = self._tags_for(B, tag)
+        keep_parts, row_parts, kept = [], [], 0
+        for lo in range(0, B, NOVEL_MAX_ROWS):
+            hi = min(B, lo + NOVEL_MAX_ROWS)
+            part = t[lo:hi]
+            s_ks, s_kr, s_stride = ks, kr, stride
+            if known is None and against is not None and self.searchable:
+                if scope is None:
+                    s_ks, s_kr = self.topk(part, 1)
+                else:
+                    s_ks, s_kr = self.topk_scoped(part, 1, sc[lo:hi].contiguous())
+                s_ks, s_kr, s_stride = s_ks[:, 0], s_kr[:, 0], 1
+            keep_i, row_of, _ = self._append_novel_call(part, tau, s_ks, s_kr, s_stride,
+                                                        None if keys is None else keys[lo:hi],
+                                                        None if tags is None else tags[lo:hi], None)
+            keep = keep_i.ne(0)
+            row_of = row_of.clone()
+            picks = torch.nonzero(keep).flatten().tolist()      # the one synchronising read
+            self.ids.extend([ids[lo + i] for i in picks] if ids is not None else [None] * len(picks))
+            self.meta.extend([meta[lo + i] for i in picks] if meta is not None else [None] * len(picks))
+            self.sync()
+            keep_parts.append(keep)
+            row_parts.append(row_of)
+            kept += len(picks)
+        if not keep_parts:
+            return Novelty(torch.zeros(0, dtype=torch.bool, device=self.device),
+                           torch.zeros(0, dtype=torch.int64, device=self.device), 0)
+        if len(keep_parts) == 1:
+            return Novelty(keep_parts[0], row_parts[0], kept)
+        return Novelty(torch.cat(keep_parts), torch.cat(row_parts), kept)
 
     def new_source(self) -> int:
         """A source index no earlier ``new_source`` call of this memory returned: one per video (``make_tag``)."""
@@ -577,6 +747,28 @@ class EmbeddingMemory:
     def meta_of(self, row: int) -> Optional[dict]:
         i = row - self.table_base
         return self.meta[i] if 0 <= i < len(self.meta) else None
+
+
+class NoveltyScratch:
+    """Device buffers of the gated append for batches of up to ``B`` rows: the workspace (norms and pair bits), ``keep``
+    (int32), ``row_of`` (int64) and ``count`` (int32 [1]).  Like ``TopkScratch``, an owner keeps ONE instance per stream /
+    captured graph: a hipGraph bakes the addresses in."""
+
+    def __init__(self, device, B: int, ws_bytes: int):
+        self.B = int(B)
+        self.ws = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=device)
+        self.keep = torch.zeros(max(B, 1), dtype=torch.int32, device=device)
+        self.row_of = torch.zeros(max(B, 1), dtype=torch.int64, device=device)
+        self.count = torch.zeros(1, dtype=torch.int32, device=device)
+
+    def fits(self, memory: "EmbeddingMemory", B: int) -> bool:
+        return (self.B >= min(B, NOVEL_MAX_ROWS) and
+                self.ws.numel() >= int(memory.L.vm_novelty_workspace_bytes(memory.handle, int(min(B, NOVEL_MAX_ROWS)))))
+
+    @classmethod
+    def for_(cls, memory: "EmbeddingMemory", B: int) -> "NoveltyScratch":
+        B = max(1, min(int(B), NOVEL_MAX_ROWS))
+        return cls(memory.device, B, int(memory.L.vm_novelty_workspace_bytes(memory.handle, B)))
 
 
 class TopkScratch:
