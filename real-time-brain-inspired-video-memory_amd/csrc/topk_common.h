@@ -3,7 +3,8 @@
 // A top-k answer is the reference's bit for bit (src/components/pre_llm_injector.py:374-388): the fp64 cosine with one
 // rounding per product and per partial sum, summed strictly left to right, the zero-norm guard and one division;
 // results ordered by (score desc, row asc).  Each rule is defined here once; the row search (topk.hip), the exhaustive
-// kernels (topk_exact.hip), the grouped search (topk_group.hip) and the append's row norms (memory.hip) use it.
+// kernels (topk_exact.hip), the grouped and scoped searches (topk_group.hip, topk_scope.hip; their shared selection stage
+// is topk_select.h) and the append's row norms (memory.hip) use it.
 #pragma once
 #include "vm_common.h"
 

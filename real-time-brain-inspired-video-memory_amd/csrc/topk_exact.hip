@@ -2,6 +2,8 @@
 // (src/components/pre_llm_injector.py:374-388: three left-to-right fp64 sums, sqrt, guards, one division),
 // then a stable top-k.  Used (a) as the fallback for queries the fast scan cannot certify, (b) for the
 // post-compression filter (src/pipeline/retriever_hybrid.py:494-504), (c) as an on-device checker.
+// Also home of what the three redos share (vm_internal.h): the row-block count vm_topk_redo_blocks and the merge of the
+// slice winners vm_topk_redo_merge, called by the row redo here and by topk_group.hip and topk_scope.hip.
 #include "topk_common.h"
 #include "vm_internal.h"
 
@@ -213,13 +215,15 @@ __global__ void __launch_bounds__(REDO_THREADS)
 }
 
 // grid = Q; a block whose query is not flagged exits at once.  Stable top-k over the nblk * k slice winners,
-// then the same output mapping as the fast path (score mode, min_score, global row id, -1 / 0.0 padding).
+// then the same output mapping as the fast path (score mode, min_score, global row id, -1 / 0.0 padding).  The one merge
+// of the row, scoped and grouped redos; gkey / out_keys are the grouped search's (null otherwise).
 __global__ void __launch_bounds__(REDO_THREADS)
     topk_redo_merge_kernel(const double *__restrict__ part_s, const int64_t *__restrict__ part_o, int nblk, int Q,
                            int k, const int32_t *__restrict__ flags, const int64_t *__restrict__ d_total,
                            int64_t cap, int ring, int use_min, double min_score, int score_mode,
                            int64_t row_stride, int64_t row_offset, double *__restrict__ out_scores,
-                           int64_t *__restrict__ out_rows) {
+                           int64_t *__restrict__ out_rows, const int64_t *__restrict__ gkey,
+                           int64_t *__restrict__ out_keys) {
     __shared__ double win_s[REDO_KMAX], red_s[REDO_THREADS / 64];
     __shared__ int64_t win_o[REDO_KMAX], red_o[REDO_THREADS / 64];
     const int q = blockIdx.x, tid = threadIdx.x;
@@ -236,22 +240,34 @@ __global__ void __launch_bounds__(REDO_THREADS)
         const int64_t o = win_o[tid];
         double shown = win_s[tid];
         bool ok = o >= 0;
-        if (ok) {  // shown_score / passes_min (topk_common.h), written out: the helpers change this kernel
-            if (score_mode == VM_SCORE_UNIT_INTERVAL) shown = __ddiv_rn(__dadd_rn(1.0, shown), 2.0);
-            if (use_min && !(shown > min_score)) ok = false;
+        if (ok) {
+            shown = shown_score(shown, score_mode);
+            ok = passes_min(use_min, shown, min_score);
         }
         out_scores[(size_t)q * k + tid] = ok ? shown : 0.0;
         out_rows[(size_t)q * k + tid] = ok ? (rv.base + o) * row_stride + row_offset : -1;
+        if (out_keys) out_keys[(size_t)q * k + tid] = ok ? gkey[slot_of(rv, o)] : -1;
     }
 }
 
-int redo_blocks(const vm_memory *m) {
-    int64_t b = (m->cap + REDO_CHUNK - 1) / REDO_CHUNK;
+}  // namespace
+
+int vm_topk_redo_blocks(const vm_memory *m, int chunk) {
+    int64_t b = (m->cap + chunk - 1) / chunk;
     if (b > m->ctx->num_cus) b = m->ctx->num_cus;
     return b < 1 ? 1 : (int)b;
 }
 
-}  // namespace
+int vm_topk_redo_merge(vm_memory *m, const double *part_s, const int64_t *part_o, int nblk, int Q, int k,
+                       const int32_t *flags, int use_min, double min_score, int score_mode, int64_t row_stride,
+                       int64_t row_offset, double *out_scores, int64_t *out_rows, const int64_t *gkey,
+                       int64_t *out_keys, hipStream_t st) {
+    topk_redo_merge_kernel<<<Q, REDO_THREADS, 0, st>>>(part_s, part_o, nblk, Q, k, flags, m->d_total, m->cap, m->ring,
+                                                      use_min, min_score, score_mode, row_stride, row_offset,
+                                                      out_scores, out_rows, gkey, out_keys);
+    VM_LAUNCH_CHECK(m->ctx);
+    return VM_OK;
+}
 
 extern "C" int vm_cosine_exact(vm_ctx *ctx, const void *queries, int Q, const void *rows, int64_t S, int D,
                                int dtype, double *out, void *stream) {
@@ -335,7 +351,7 @@ extern "C" int vm_topk_select(vm_ctx *ctx, const double *scores, int Q, int64_t 
 
 extern "C" size_t vm_topk_redo_workspace_bytes(const vm_memory *m, int Q, int k) {
     if (!m || Q <= 0 || k <= 0 || k > REDO_KMAX) return 0;
-    return vm_align_up((size_t)redo_blocks(m) * Q * k * 16, 256);
+    return vm_align_up((size_t)vm_topk_redo_blocks(m, REDO_CHUNK) * Q * k * 16, 256);
 }
 
 extern "C" int vm_topk_redo_flagged(vm_memory *m, const void *queries, int Q, int k, int use_min_score,
@@ -348,7 +364,7 @@ extern "C" int vm_topk_redo_flagged(vm_memory *m, const void *queries, int Q, in
         return vm_fail(ctx, VM_ERR_INVALID, "vm_topk_redo_flagged: bad arguments");
     if (k > REDO_KMAX) return vm_fail(ctx, VM_ERR_UNSUPPORTED, "vm_topk_redo_flagged: k=%d > %d", k, REDO_KMAX);
     if (int rc = vm_check_score_mode(ctx, score_mode)) return rc;
-    const int nblk = redo_blocks(m);
+    const int nblk = vm_topk_redo_blocks(m, REDO_CHUNK);
     const size_t need = (size_t)nblk * Q * k * 16;
     if (!workspace || workspace_bytes < need)
         return vm_fail(ctx, VM_ERR_NOMEM, "vm_topk_redo_flagged: workspace %zu < %zu", workspace_bytes, need);
@@ -368,9 +384,6 @@ extern "C" int vm_topk_redo_flagged(vm_memory *m, const void *queries, int Q, in
             (const uint16_t *)queries, m->rows, m->norm64, m->d_total, m->cap, m->ring, m->D, Q, k, query_flags,
             part_s, part_o);
     VM_LAUNCH_CHECK(ctx);
-    topk_redo_merge_kernel<<<Q, REDO_THREADS, 0, st>>>(part_s, part_o, nblk, Q, k, query_flags, m->d_total, m->cap,
-                                                      m->ring, use_min_score, min_score, score_mode, row_stride,
-                                                      row_offset, out_scores, out_rows);
-    VM_LAUNCH_CHECK(ctx);
-    return VM_OK;
+    return vm_topk_redo_merge(m, part_s, part_o, nblk, Q, k, query_flags, use_min_score, min_score, score_mode, row_stride,
+                              row_offset, out_scores, out_rows, nullptr, nullptr, st);
 }

@@ -2,7 +2,8 @@
 //
 // The row ranking is vm_topk_cosine's (src/components/pre_llm_injector.py:346-388, retriever_hybrid.py:293-306); a
 // group's score is the exact max over its rows and its representative the lowest row id reaching that max.  Same
-// two-stage, certified design as topk.hip:
+// two-stage, certified design as topk.hip; the key images, the block-wide selection, the plan
+// scaffold and the argument check are topk_select.h's, shared with topk_scope.hip:
 //   table    : first age order of every live group (groups are runs of equal ordinals, memory.hip) + clears the maxima
 //   scan     : fp32 MFMA scores with the list scan's numerics (the same instruction over the same operand layout, then
 //              x 1/||row||), folded into per-(query, group) fp32 maxima with one atomic max per run of a 16-row tile
@@ -12,10 +13,10 @@
 //              left to right; norm64), exact group max + representative, ordered, k kept.  Certified when the exact
 //              k-th group score clears the (M+1)-th group's fp32 max / ||q|| by topk.hip's bound 2 (D + 8) 2^-24
 //   redo     : flagged queries (gap or candidate-row overflow) scored exhaustively, group-aligned row slices per
-//              block, segmented max in LDS, stable top-k per slice, merge.  Reads flags and counts on the device.
+//              block, segmented max in LDS, stable top-k per slice, then the one merge of every redo
+//              (vm_topk_redo_merge, topk_exact.hip).  Reads flags and counts on the device.
 // Every launch reads the row count from the device and sizes its grid from the capacity: capturable.
-#include "topk_common.h"
-#include "vm_internal.h"
+#include "topk_select.h"
 
 #include <climits>
 
@@ -34,15 +35,7 @@ constexpr int GR_THREADS = 256;   // redo
 constexpr int GR_CHUNK = 1024;    // rows scored per selection pass of the redo
 constexpr int GKMAX = 64;
 
-// order-preserving unsigned images (bigger key = bigger value; -0 folded into +0; 0 is below every image)
-__device__ __forceinline__ uint32_t okey32(float s) {
-    uint32_t u = __float_as_uint(s);
-    if (s == 0.f) u = 0;
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float dekey32(uint32_t k) {
-    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
+// order-preserving unsigned images of fp64 scores (okey32 / dekey32 of topk_select.h, one word wider)
 __device__ __forceinline__ unsigned long long okey64(double d) {
     unsigned long long u = (unsigned long long)__double_as_longlong(d);
     if (d == 0.0) u = 0;
@@ -264,38 +257,10 @@ __global__ void __launch_bounds__(GS_THREADS)
 
 // ---- select ------------------------------------------------------------------------------------------------
 // Per query, the best take = min(M + 1, ng) groups by (fp32 max desc, group asc), as 64-bit composites
-// key << 32 | ~group (bigger = better, unique).  cut: the take-th best composite of a strided sample of SEL_SAMPLE groups
-// (all of them when there are fewer) - at least take groups reach it; compact: every group at or above the cut, from
-// many blocks; final: the take-th largest key among those (ties by group), the take best kept.  A query with more than SEL_CAP groups at its cut runs
-// the exact radix select below over all its groups instead (slow, any input).
-__device__ __forceinline__ unsigned long long composite(uint32_t key, int g) {
-    return ((unsigned long long)key << 32) | (unsigned long long)(0xffffffffu - (uint32_t)g);
-}
-
-// largest T with at least `need` of the block's values >= T (PER values per thread, SEL_THREADS threads; every thread
-// calls it): a bitwise search, one block-wide count per bit
-template <int PER>
-__device__ __forceinline__ uint32_t block_kth_u32(const uint32_t (&v)[PER], int need) {
-    __shared__ int wsum[SEL_THREADS / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t T = 0;
-    for (int bit = 31; bit >= 0; --bit) {
-        const uint32_t c = T | (1u << bit);
-        int cnt = 0;
-#pragma unroll
-        for (int j = 0; j < PER; ++j) cnt += v[j] >= c ? 1 : 0;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
-        if (lane == 0) wsum[wave] = cnt;
-        __syncthreads();
-        int tot = 0;
-#pragma unroll
-        for (int w = 0; w < SEL_THREADS / 64; ++w) tot += wsum[w];
-        __syncthreads();
-        if (tot >= need) T = c;
-    }
-    return T;
-}
+// key << 32 | ~group (topk_select.h).  cut: the take-th best composite of a strided sample of SEL_SAMPLE groups (all of
+// them when there are fewer) - at least take groups reach it; compact: every group at or above the cut, from many
+// blocks; final: the take-th largest key among those (ties by group), the take best kept (select_best).  A query with
+// more than SEL_CAP groups at its cut runs the exact radix select below over all its groups instead (slow, any input).
 
 // One block per query: cut = key T << 32, T = the take-th largest fp32-max key of a strided sample of SEL_SAMPLE groups
 // (all of them when there are fewer).  At least take groups have a key >= T (ties at T included, whatever their group).
@@ -316,7 +281,7 @@ __global__ void __launch_bounds__(SEL_THREADS)
         v[j] = i < cnt ? Fq[ng <= SEL_SAMPLE ? i : (int64_t)i * ng / SEL_SAMPLE] : 0u;
     }
     const int take = cnt < M1 ? cnt : M1;
-    const uint32_t T = take > 0 ? block_kth_u32<PER>(v, take) : 0xffffffffu;
+    const uint32_t T = take > 0 ? block_kth_u32<SEL_THREADS>(v, take) : 0xffffffffu;
     if (lane == 0) {
         cut[q] = (unsigned long long)T << 32;
         ccount[q] = 0;
@@ -436,6 +401,7 @@ __device__ void radix_select_all(const uint32_t *__restrict__ Fq, int ng, int ta
     }
 }
 
+// One block per query: the best take groups of the compacted list, or of all groups when the list overflowed.
 __global__ void __launch_bounds__(SEL_THREADS)
     group_select_final_kernel(const int64_t *__restrict__ d_total, int64_t cap, int ring,
                               const int64_t *__restrict__ gord, const uint32_t *__restrict__ F, int M1,
@@ -453,60 +419,7 @@ __global__ void __launch_bounds__(SEL_THREADS)
         radix_select_all(F + (size_t)q * ng, ng, take, og, ok);
         return;
     }
-    // the take-th largest key of the compacted list, then ties at that key by group
-    constexpr int PER = SEL_CAP / SEL_THREADS;
-    __shared__ int red[2][SEL_THREADS / 64];
-    __shared__ int npos;
-    const int lane = tid & 63, wave = tid >> 6;
-    uint32_t hi[PER], lo[PER];
-#pragma unroll
-    for (int j = 0; j < PER; ++j) {
-        const int i = j * SEL_THREADS + tid;
-        const unsigned long long c = i < cnt ? cbuf[(size_t)q * SEL_CAP + i] : 0ull;
-        hi[j] = (uint32_t)(c >> 32);
-        lo[j] = (uint32_t)c;  // ~group: bigger = lower group
-    }
-    const uint32_t T = block_kth_u32<PER>(hi, take);
-    int above = 0, equal = 0;
-#pragma unroll
-    for (int j = 0; j < PER; ++j) {
-        above += hi[j] > T ? 1 : 0;
-        equal += hi[j] == T ? 1 : 0;
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        above += __shfl_xor(above, off, 64);
-        equal += __shfl_xor(equal, off, 64);
-    }
-    if (lane == 0) {
-        red[0][wave] = above;
-        red[1][wave] = equal;
-    }
-    if (tid == 0) npos = 0;
-    __syncthreads();
-    above = equal = 0;
-#pragma unroll
-    for (int w = 0; w < SEL_THREADS / 64; ++w) {
-        above += red[0][w];
-        equal += red[1][w];
-    }
-    const int need_eq = take - above;
-    uint32_t lo_cut = 0;  // keep the need_eq lowest groups among the keys == T
-    if (need_eq < equal) {
-        uint32_t le[PER];
-#pragma unroll
-        for (int j = 0; j < PER; ++j) le[j] = hi[j] == T ? lo[j] : 0u;
-        lo_cut = block_kth_u32<PER>(le, need_eq);  // uniform branch: every thread sees the same counts
-    }
-#pragma unroll
-    for (int j = 0; j < PER; ++j) {  // exactly take entries are kept; their order does not matter (finalize ranks)
-        const bool keep = hi[j] > T || (hi[j] == T && lo[j] >= lo_cut && (j * SEL_THREADS + tid) < cnt);
-        if (keep) {
-            const int pos = atomicAdd(&npos, 1);
-            og[pos] = (int)(0xffffffffu - lo[j]);
-            ok[pos] = hi[j];
-        }
-    }
+    select_best<SEL_THREADS, SEL_CAP, GCMAX>(cbuf + (size_t)q * SEL_CAP, cnt, take, og, ok);
 }
 
 // ---- finalize ----------------------------------------------------------------------------------------------
@@ -622,6 +535,7 @@ __global__ void __launch_bounds__(GF_THREADS)
         }
         // certification: the exact k-th group score against the best fp32 max of a group that never became a candidate
         const int kth = (k < nc ? k : nc) - 1;
+        // (clears_gap of topk_select.h written out: called as a helper it changes this kernel's instructions)
         if (r == kth && C > M && qn != 0.0) {
             const double eps = cert_eps(D);
             const double reject = (double)dekey32(sk[M]) / qn + eps;
@@ -778,102 +692,38 @@ __global__ void __launch_bounds__(GR_THREADS)
     }
 }
 
-// grid = Q; unflagged queries exit at once.  Stable top-k over the nblk * k slice winners (each group lives in one
-// slice), then the output mapping of the fast path.
-__global__ void __launch_bounds__(GR_THREADS)
-    group_redo_merge_kernel(const double *__restrict__ part_s, const int64_t *__restrict__ part_o, int nblk, int Q,
-                            int k, const int32_t *__restrict__ flags, const int64_t *__restrict__ d_total, int64_t cap,
-                            int ring, const int64_t *__restrict__ gkey, int use_min, double min_score, int score_mode,
-                            double *__restrict__ out_scores, int64_t *__restrict__ out_rows,
-                            int64_t *__restrict__ out_keys) {
-    __shared__ double win_s[GKMAX], red_s[GR_THREADS / 64];
-    __shared__ int64_t win_o[GKMAX], red_o[GR_THREADS / 64];
-    const int q = blockIdx.x, tid = threadIdx.x;
-    if (flags[q] == 0) return;
-    const RingView rv = ring_view(*d_total, cap, ring);
-    block_select<GR_THREADS>(nblk * k, k,
-                  [&](int i, double &v, int64_t &o) {
-                      const int b = i / k, e = i - b * k;
-                      v = part_s[((size_t)b * Q + q) * k + e];
-                      o = part_o[((size_t)b * Q + q) * k + e];
-                  },
-                  win_s, win_o, red_s, red_o);
-    if (tid < k) {
-        const int64_t o = win_o[tid];
-        double shown = win_s[tid];
-        bool ok = o >= 0;
-        if (ok) {
-            shown = shown_score(shown, score_mode);
-            ok = passes_min(use_min, shown, min_score);
-        }
-        out_scores[(size_t)q * k + tid] = ok ? shown : 0.0;
-        out_rows[(size_t)q * k + tid] = ok ? rv.base + o : -1;
-        if (out_keys) out_keys[(size_t)q * k + tid] = ok ? gkey[slot_of(rv, o)] : -1;
-    }
-}
-
 // ---- host --------------------------------------------------------------------------------------------------
-struct GPlan {
-    int M, qt, qgroups, nbx, nblk, tbl_blocks;
-    int cmp_slices;
+struct GPlan : TopkGeom {
+    int tbl_blocks;
     size_t off_first, off_cg, off_ck, off_cn, off_flags, off_ps, off_po, off_cut, off_cc, off_cbuf, total;
 };
 
 GPlan group_plan(const vm_memory *m, int Q, int k) {
     GPlan p;
-    p.M = k + (k / 4 > 8 ? k / 4 : 8);  // slack: near-ties between rank k and rank M are certified by the gap
-    p.qt = Q <= 16 ? 1 : 2;
-    p.qgroups = (Q + 16 * p.qt - 1) / (16 * p.qt);
-    const int64_t tiles = (m->cap + 15) / 16;
-    int64_t nbx = (tiles + GS_THREADS / 64 - 1) / (GS_THREADS / 64);
-    const int64_t lim = (int64_t)m->ctx->num_cus * 8;
-    p.nbx = (int)(nbx < lim ? (nbx < 1 ? 1 : nbx) : lim);
-    int64_t nb = (m->cap + GR_CHUNK - 1) / GR_CHUNK;
-    if (nb > m->ctx->num_cus) nb = m->ctx->num_cus;
-    p.nblk = nb < 1 ? 1 : (int)nb;
+    static_cast<TopkGeom &>(p) = vm_topk_geom(m, Q, k, GS_THREADS, GR_CHUNK);
     int64_t tb = (m->cap + 256) / 256;
     p.tbl_blocks = (int)(tb < 1024 ? tb : 1024);
-    size_t off = vm_align_up((size_t)Q * (size_t)m->cap * 4, 256);  // F: [Q][live groups] fp32-max keys
-    p.off_first = off;
-    off += vm_align_up((size_t)(m->cap + 1) * 4, 256);
-    p.off_cg = off;
-    off += vm_align_up((size_t)Q * GCMAX * 4, 256);
-    p.off_ck = off;
-    off += vm_align_up((size_t)Q * GCMAX * 4, 256);
-    p.off_cn = off;
-    off += vm_align_up((size_t)Q * 4, 256);
-    p.off_flags = off;
-    off += vm_align_up((size_t)Q * 4, 256);
-    p.off_cut = off;
-    off += vm_align_up((size_t)Q * 8, 256);
-    p.off_cc = off;
-    off += vm_align_up((size_t)Q * 4, 256);
-    p.off_cbuf = off;
-    off += vm_align_up((size_t)Q * SEL_CAP * 8, 256);
-    int64_t sl = (m->cap + 8191) / 8192;
-    p.cmp_slices = (int)(sl < 1 ? 1 : (sl > 64 ? 64 : sl));
-    p.off_ps = off;
-    off += vm_align_up((size_t)p.nblk * Q * k * 8, 256);
-    p.off_po = off;
-    off += vm_align_up((size_t)p.nblk * Q * k * 8, 256);
-    p.total = off;
+    WsBump ws;
+    ws.take((size_t)Q * (size_t)m->cap * 4);  // F at offset 0: [Q][live groups] fp32-max keys
+    p.off_first = ws.take((size_t)(m->cap + 1) * 4);
+    p.off_cg = ws.take((size_t)Q * GCMAX * 4);
+    p.off_ck = ws.take((size_t)Q * GCMAX * 4);
+    p.off_cn = ws.take((size_t)Q * 4);
+    p.off_flags = ws.take((size_t)Q * 4);
+    p.off_cut = ws.take((size_t)Q * 8);
+    p.off_cc = ws.take((size_t)Q * 4);
+    p.off_cbuf = ws.take((size_t)Q * SEL_CAP * 8);
+    p.off_ps = ws.take((size_t)p.nblk * Q * k * 8);
+    p.off_po = ws.take((size_t)p.nblk * Q * k * 8);
+    p.total = ws.off;
     return p;
 }
 
 int group_check(vm_memory *m, const void *queries, int Q, int k, int score_mode, const double *out_scores,
                 const int64_t *out_rows, const void *workspace, size_t workspace_bytes, const char *who) {
-    vm_ctx *ctx = m->ctx;
-    if (!m->gkey) return vm_fail(ctx, VM_ERR_INVALID, "%s: the memory is not grouped (vm_memory_create_grouped)", who);
-    if (!queries || !out_scores || !out_rows || Q <= 0 || k <= 0)
-        return vm_fail(ctx, VM_ERR_INVALID, "%s: bad arguments", who);
-    if (k > GKMAX) return vm_fail(ctx, VM_ERR_UNSUPPORTED, "%s: k=%d > %d", who, k, GKMAX);
-    if (int rc = vm_check_score_mode(ctx, score_mode)) return rc;
-    const size_t need = group_plan(m, Q, k).total;
-    if (!workspace || workspace_bytes < need)
-        return vm_fail(ctx, VM_ERR_NOMEM, "%s: workspace %zu < %zu", who, workspace_bytes, need);
-    if (((uintptr_t)workspace & 255) || ((uintptr_t)queries & 15))
-        return vm_fail(ctx, VM_ERR_INVALID, "%s: workspace must be 256-byte and queries 16-byte aligned", who);
-    return VM_OK;
+    return vm_topk_check(m, m->gkey ? nullptr : "grouped (vm_memory_create_grouped)",
+                         queries && out_scores && out_rows && Q > 0 && k > 0, queries, k, GKMAX, VM_ERR_UNSUPPORTED,
+                         score_mode, workspace, workspace_bytes, group_plan(m, Q, k).total, who);
 }
 
 template <int DT>
@@ -889,11 +739,8 @@ int group_redo(vm_memory *m, const GPlan &p, const void *queries, int Q, int k, 
         (const uint16_t *)queries, m->rows, m->norm64, m->gord, m->d_total, m->cap, m->ring, m->D, Q, k, first_o, flags,
         part_s, part_o);
     VM_LAUNCH_CHECK(ctx);
-    group_redo_merge_kernel<<<Q, GR_THREADS, 0, st>>>(part_s, part_o, p.nblk, Q, k, flags, m->d_total, m->cap, m->ring,
-                                                      m->gkey, use_min, min_score, score_mode, out_scores, out_rows,
-                                                      out_keys);
-    VM_LAUNCH_CHECK(ctx);
-    return VM_OK;
+    return vm_topk_redo_merge(m, part_s, part_o, p.nblk, Q, k, flags, use_min, min_score, score_mode, 1, 0, out_scores,
+                              out_rows, m->gkey, out_keys, st);
 }
 
 template <int DT, int QT>
@@ -964,11 +811,11 @@ extern "C" int vm_topk_cosine_grouped(vm_memory *m, const void *queries, int Q, 
                          "vm_topk_cosine_grouped");
     if (rc != VM_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
-    if (m->dtype == VM_F16)
-        return group_topk<VM_F16>(m, queries, Q, k, use_min_score, min_score, score_mode, out_scores, out_rows, out_keys,
-                                  out_uncertified, out_query_flags, (char *)workspace, st);
-    return group_topk<VM_BF16>(m, queries, Q, k, use_min_score, min_score, score_mode, out_scores, out_rows, out_keys,
-                               out_uncertified, out_query_flags, (char *)workspace, st);
+    return vm_by_dtype(m, [&](auto dt) {
+        return group_topk<decltype(dt)::value>(m, queries, Q, k, use_min_score, min_score, score_mode, out_scores,
+                                               out_rows, out_keys, out_uncertified, out_query_flags, (char *)workspace,
+                                               st);
+    });
 }
 
 extern "C" int vm_topk_cosine_grouped_exact(vm_memory *m, const void *queries, int Q, int k, int use_min_score,
@@ -985,9 +832,8 @@ extern "C" int vm_topk_cosine_grouped_exact(vm_memory *m, const void *queries, i
     group_table_kernel<<<p.tbl_blocks, 256, 0, st>>>(m->d_total, m->cap, m->ring, m->gord, Q, (int *)(ws + p.off_first),
                                                      nullptr, (int32_t *)(ws + p.off_flags), 1);
     VM_LAUNCH_CHECK(ctx);
-    if (m->dtype == VM_F16)
-        return group_redo<VM_F16>(m, p, queries, Q, k, use_min_score, min_score, score_mode, out_scores, out_rows,
-                                  out_keys, ws, st);
-    return group_redo<VM_BF16>(m, p, queries, Q, k, use_min_score, min_score, score_mode, out_scores, out_rows,
-                               out_keys, ws, st);
+    return vm_by_dtype(m, [&](auto dt) {
+        return group_redo<decltype(dt)::value>(m, p, queries, Q, k, use_min_score, min_score, score_mode, out_scores,
+                                               out_rows, out_keys, ws, st);
+    });
 }

@@ -5,7 +5,8 @@
 // query names the video or the time window it wants.
 //
 // The row ranking is vm_topk_cosine's, taken over the in-scope rows only.  Same two-stage, certified design as topk.hip
-// and topk_group.hip; a row is a group of one whose fp32 key is 0 when it is out of scope:
+// and topk_group.hip, with which it shares topk_select.h (key images, block-wide selection, gap
+// certificate, plan scaffold, argument check); a row is a group of one whose fp32 key is 0 when it is out of scope:
 //   scan     : per 16-row tile the wave first reads the tile's 16 tags and tests them against the scopes of its query
 //              tile; a tile with no (row, query) pair in scope is skipped WITHOUT reading its rows (8 bytes per row
 //              instead of 2 D) and only zeroes its keys.  Otherwise fp32 MFMA scores with the list scan's numerics (the
@@ -18,10 +19,10 @@
 //              when the scope holds at most M rows, or when the exact k-th score clears the (M+1)-th IN-SCOPE fp32
 //              score / ||q|| by cert_eps(D), strictly.  Out-of-scope rows have key 0 and never reach the certificate
 //   redo     : flagged queries scored exhaustively over their in-scope rows, slices of age orders per block, stable
-//              top-k per slice, merge.  Flags and counts are read on the device; near-empty when nothing is flagged.
+//              top-k per slice, then the one merge of every redo (vm_topk_redo_merge, topk_exact.hip).  Flags and
+//              counts are read on the device; near-empty when nothing is flagged.
 // Every launch reads the row count from the device and sizes its grid from the capacity: capturable.
-#include "topk_common.h"
-#include "vm_internal.h"
+#include "topk_select.h"
 
 #include <climits>
 
@@ -39,15 +40,6 @@ constexpr int SR_THREADS = 256;    // redo
 constexpr int SR_CHUNK = 1024;     // rows scored per selection pass of the redo
 constexpr int SKMAX = 64;
 
-// order-preserving unsigned image of an fp32 score (bigger key = bigger value; -0 folded into +0; every image is > 0)
-__device__ __forceinline__ uint32_t okey32(float s) {
-    uint32_t u = __float_as_uint(s);
-    if (s == 0.f) u = 0;
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float dekey32(uint32_t k) {
-    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
 __device__ __forceinline__ bool in_scope(int64_t tag, int64_t lo, int64_t hi) { return lo <= tag && tag <= hi; }
 // age order (0 = oldest) of the live row in physical slot p
 __device__ __forceinline__ int64_t order_of(const RingView &v, int64_t p) {
@@ -159,37 +151,7 @@ __global__ void __launch_bounds__(SS_THREADS)
 }
 
 // ---- select ------------------------------------------------------------------------------------------------
-// 64-bit composites key << 32 | ~order (bigger = better, unique)
-__device__ __forceinline__ unsigned long long composite(uint32_t key, int o) {
-    return ((unsigned long long)key << 32) | (unsigned long long)(0xffffffffu - (uint32_t)o);
-}
-
-// largest T with at least `need` of the block's values >= T (PER values per thread, SEL_THREADS threads; every thread
-// calls it): a bitwise search, one block-wide count per bit.  low_bit > 0 stops the search there: the result has its low
-// bits clear and is a lower bound of the exact value (still at least `need` values >= T)
-template <int PER>
-__device__ __forceinline__ uint32_t block_kth_u32(const uint32_t (&v)[PER], int need, int low_bit = 0) {
-    __shared__ int wsum[SEL_THREADS / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t T = 0;
-    for (int bit = 31; bit >= low_bit; --bit) {
-        const uint32_t c = T | (1u << bit);
-        int cnt = 0;
-#pragma unroll
-        for (int j = 0; j < PER; ++j) cnt += v[j] >= c ? 1 : 0;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
-        if (lane == 0) wsum[wave] = cnt;
-        __syncthreads();
-        int tot = 0;
-#pragma unroll
-        for (int w = 0; w < SEL_THREADS / 64; ++w) tot += wsum[w];
-        __syncthreads();
-        if (tot >= need) T = c;
-    }
-    return T;
-}
-
+// composites (topk_select.h) of key and age order: ties at one key go to the older row
 // One block per query: cut[q] = the (M+1)-th largest key of a sample of SEL_SAMPLE slots, one per stride (all slots when
 // there are fewer), or 1 - every in-scope row - when the sample holds fewer than M + 1 in-scope rows.  At least
 // min(M + 1, in-scope rows) rows have a key >= the cut, and no out-of-scope row (key 0) has.
@@ -213,7 +175,7 @@ __global__ void __launch_bounds__(SEL_THREADS)
     }
     // the top 20 bits of the key are enough for a cut (a score resolution of 2^-11 relative): 20 counting steps, not 32.
     // 0 when fewer than M1 sampled keys are in scope (every in-scope key is above 2^12)
-    const uint32_t T = block_kth_u32<PER>(v, M1, 12);
+    const uint32_t T = block_kth_u32<SEL_THREADS>(v, M1, 12);
     if (tid == 0) {
         cut[q] = T ? T : 1u;
         ccount[q] = 0;
@@ -287,61 +249,7 @@ __global__ void __launch_bounds__(SEL_THREADS)
     }
     const int take = cnt < M1 ? cnt : M1;
     if (tid == 0) cand_n[q] = take;
-    constexpr int PER = SEL_CAP / SEL_THREADS;
-    __shared__ int red[2][SEL_THREADS / 64];
-    __shared__ int npos;
-    const int lane = tid & 63, wave = tid >> 6;
-    uint32_t hi[PER], lo[PER];
-#pragma unroll
-    for (int j = 0; j < PER; ++j) {
-        const int i = j * SEL_THREADS + tid;
-        const unsigned long long c = i < cnt ? cbuf[(size_t)q * SEL_CAP + i] : 0ull;
-        hi[j] = (uint32_t)(c >> 32);
-        lo[j] = (uint32_t)c;  // ~order: bigger = older row
-    }
-    const uint32_t T = block_kth_u32<PER>(hi, take);  // >= 1: every list entry has a key >= 1, and take <= cnt
-    int above = 0, equal = 0;
-#pragma unroll
-    for (int j = 0; j < PER; ++j) {
-        above += hi[j] > T ? 1 : 0;
-        equal += hi[j] == T ? 1 : 0;
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        above += __shfl_xor(above, off, 64);
-        equal += __shfl_xor(equal, off, 64);
-    }
-    if (lane == 0) {
-        red[0][wave] = above;
-        red[1][wave] = equal;
-    }
-    if (tid == 0) npos = 0;
-    __syncthreads();
-    above = equal = 0;
-#pragma unroll
-    for (int w = 0; w < SEL_THREADS / 64; ++w) {
-        above += red[0][w];
-        equal += red[1][w];
-    }
-    const int need_eq = take - above;
-    uint32_t lo_cut = 0;  // keep the need_eq oldest rows among the keys == T
-    if (need_eq < equal) {
-        uint32_t le[PER];
-#pragma unroll
-        for (int j = 0; j < PER; ++j) le[j] = hi[j] == T ? lo[j] : 0u;
-        lo_cut = block_kth_u32<PER>(le, need_eq);  // uniform branch: every thread sees the same counts
-    }
-#pragma unroll
-    for (int j = 0; j < PER; ++j) {  // exactly take entries are kept; their order does not matter (finalize ranks)
-        const bool keep = hi[j] > T || (hi[j] == T && lo[j] >= lo_cut);
-        if (keep) {
-            const int pos = atomicAdd(&npos, 1);
-            if (pos < SCMAX) {
-                oo[pos] = (int)(0xffffffffu - lo[j]);
-                ok[pos] = hi[j];
-            }
-        }
-    }
+    select_best<SEL_THREADS, SEL_CAP, SCMAX>(cbuf + (size_t)q * SEL_CAP, cnt, take, oo, ok);
 }
 
 // ---- finalize ----------------------------------------------------------------------------------------------
@@ -416,10 +324,7 @@ __global__ void __launch_bounds__(SF_THREADS)
         }
         // certification: the exact k-th score against the best fp32 score of an in-scope row that was not re-scored
         const int kth = (k < nc ? k : nc) - 1;
-        if (r == kth && C > M && qn != 0.0) {
-            const double reject = (double)dekey32(sk[M]) / qn + cert_eps(D);
-            if (!(e > reject)) flag_sh = VM_FLAG_GAP;
-        }
+        if (r == kth && C > M && qn != 0.0 && !clears_gap(e, sk[M], qn, D)) flag_sh = VM_FLAG_GAP;
     }
     for (int i = nc + tid; i < k; i += SF_THREADS) {
         out_scores[(size_t)q * k + i] = 0.0;
@@ -516,98 +421,37 @@ __global__ void __launch_bounds__(SR_THREADS)
     }
 }
 
-// grid = Q; a block whose query is not flagged exits at once.  Stable top-k over the nblk * k slice winners, then the
-// output mapping of the fast path.
-__global__ void __launch_bounds__(SR_THREADS)
-    scope_redo_merge_kernel(const double *__restrict__ part_s, const int64_t *__restrict__ part_o, int nblk, int Q,
-                            int k, const int32_t *__restrict__ flags, const int64_t *__restrict__ d_total, int64_t cap,
-                            int ring, int use_min, double min_score, int score_mode, int64_t row_stride,
-                            int64_t row_offset, double *__restrict__ out_scores, int64_t *__restrict__ out_rows) {
-    __shared__ double win_s[SKMAX], red_s[SR_THREADS / 64];
-    __shared__ int64_t win_o[SKMAX], red_o[SR_THREADS / 64];
-    const int q = blockIdx.x, tid = threadIdx.x;
-    if (flags[q] == 0) return;
-    const RingView rv = ring_view(*d_total, cap, ring);
-    block_select<SR_THREADS>(nblk * k, k,
-                             [&](int i, double &v, int64_t &o) {
-                                 const int b = i / k, e = i - b * k;
-                                 v = part_s[((size_t)b * Q + q) * k + e];
-                                 o = part_o[((size_t)b * Q + q) * k + e];
-                             },
-                             win_s, win_o, red_s, red_o);
-    if (tid < k) {
-        const int64_t o = win_o[tid];
-        double shown = win_s[tid];
-        bool ok = o >= 0;
-        if (ok) {
-            shown = shown_score(shown, score_mode);
-            ok = passes_min(use_min, shown, min_score);
-        }
-        out_scores[(size_t)q * k + tid] = ok ? shown : 0.0;
-        out_rows[(size_t)q * k + tid] = ok ? (rv.base + o) * row_stride + row_offset : -1;
-    }
-}
-
 // ---- host --------------------------------------------------------------------------------------------------
-struct SPlan {
-    int M, qt, qgroups, nbx, nblk, cmp_slices;
+struct SPlan : TopkGeom {
     int64_t fstride;
     size_t off_co, off_ck, off_cn, off_flags, off_cut, off_cc, off_cbuf, off_ps, off_po, total;
 };
 
 SPlan scope_plan(const vm_memory *m, int Q, int k) {
     SPlan p;
-    p.M = k + (k / 4 > 8 ? k / 4 : 8);  // slack: near-ties between rank k and rank M are certified by the gap
-    p.qt = Q <= 16 ? 1 : 2;
-    p.qgroups = (Q + 16 * p.qt - 1) / (16 * p.qt);
-    const int64_t tiles = (m->cap + 15) / 16;
-    int64_t nbx = (tiles + SS_THREADS / 64 - 1) / (SS_THREADS / 64);
-    const int64_t lim = (int64_t)m->ctx->num_cus * 8;
-    p.nbx = (int)(nbx < lim ? (nbx < 1 ? 1 : nbx) : lim);
-    int64_t nb = (m->cap + SR_CHUNK - 1) / SR_CHUNK;
-    if (nb > m->ctx->num_cus) nb = m->ctx->num_cus;
-    p.nblk = nb < 1 ? 1 : (int)nb;
-    int64_t sl = (m->cap + 8191) / 8192;
-    p.cmp_slices = (int)(sl < 1 ? 1 : (sl > 64 ? 64 : sl));
+    static_cast<TopkGeom &>(p) = vm_topk_geom(m, Q, k, SS_THREADS, SR_CHUNK);
     p.fstride = (m->cap + 63) / 64 * 64;  // the columns' padding: a tail tile writes its 16 keys
-    size_t off = vm_align_up((size_t)Q * (size_t)p.fstride * 4, 256);  // F: [Q][slot] fp32 keys
-    p.off_co = off;
-    off += vm_align_up((size_t)Q * SCMAX * 4, 256);
-    p.off_ck = off;
-    off += vm_align_up((size_t)Q * SCMAX * 4, 256);
-    p.off_cn = off;
-    off += vm_align_up((size_t)Q * 4, 256);
-    p.off_flags = off;
-    off += vm_align_up((size_t)Q * 4, 256);
-    p.off_cut = off;
-    off += vm_align_up((size_t)Q * 4, 256);
-    p.off_cc = off;
-    off += vm_align_up((size_t)Q * 4, 256);
-    p.off_cbuf = off;
-    off += vm_align_up((size_t)Q * SEL_CAP * 8, 256);
-    p.off_ps = off;
-    off += vm_align_up((size_t)p.nblk * Q * k * 8, 256);
-    p.off_po = off;
-    off += vm_align_up((size_t)p.nblk * Q * k * 8, 256);
-    p.total = off;
+    WsBump ws;
+    ws.take((size_t)Q * (size_t)p.fstride * 4);  // F at offset 0: [Q][slot] fp32 keys
+    p.off_co = ws.take((size_t)Q * SCMAX * 4);
+    p.off_ck = ws.take((size_t)Q * SCMAX * 4);
+    p.off_cn = ws.take((size_t)Q * 4);
+    p.off_flags = ws.take((size_t)Q * 4);
+    p.off_cut = ws.take((size_t)Q * 4);
+    p.off_cc = ws.take((size_t)Q * 4);
+    p.off_cbuf = ws.take((size_t)Q * SEL_CAP * 8);
+    p.off_ps = ws.take((size_t)p.nblk * Q * k * 8);
+    p.off_po = ws.take((size_t)p.nblk * Q * k * 8);
+    p.total = ws.off;
     return p;
 }
 
 int scope_check(vm_memory *m, const void *queries, int Q, int k, const int64_t *scope_lo, const int64_t *scope_hi,
                 int score_mode, const double *out_scores, const int64_t *out_rows, const void *workspace,
                 size_t workspace_bytes, const char *who) {
-    vm_ctx *ctx = m->ctx;
-    if (!m->tag) return vm_fail(ctx, VM_ERR_INVALID, "%s: the memory is not tagged (vm_memory_create_tagged)", who);
-    if (!queries || !scope_lo || !scope_hi || !out_scores || !out_rows || Q <= 0)
-        return vm_fail(ctx, VM_ERR_INVALID, "%s: bad arguments", who);
-    if (k < 1 || k > SKMAX) return vm_fail(ctx, VM_ERR_INVALID, "%s: k=%d outside [1, %d]", who, k, SKMAX);
-    if (int rc = vm_check_score_mode(ctx, score_mode)) return rc;
-    const size_t need = scope_plan(m, Q, k).total;
-    if (!workspace || workspace_bytes < need)
-        return vm_fail(ctx, VM_ERR_NOMEM, "%s: workspace %zu < %zu", who, workspace_bytes, need);
-    if (((uintptr_t)workspace & 255) || ((uintptr_t)queries & 15))
-        return vm_fail(ctx, VM_ERR_INVALID, "%s: workspace must be 256-byte and queries 16-byte aligned", who);
-    return VM_OK;
+    return vm_topk_check(m, m->tag ? nullptr : "tagged (vm_memory_create_tagged)",
+                         queries && scope_lo && scope_hi && out_scores && out_rows && Q > 0, queries, k, SKMAX,
+                         VM_ERR_INVALID, score_mode, workspace, workspace_bytes, scope_plan(m, Q, k).total, who);
 }
 
 template <int DT>
@@ -623,11 +467,8 @@ int scope_redo(vm_memory *m, const SPlan &p, const void *queries, int Q, int k, 
         (const uint16_t *)queries, m->rows, m->norm64, m->tag, scope_lo, scope_hi, m->d_total, m->cap, m->ring, m->D, Q,
         k, flags, part_s, part_o);
     VM_LAUNCH_CHECK(ctx);
-    scope_redo_merge_kernel<<<Q, SR_THREADS, 0, st>>>(part_s, part_o, p.nblk, Q, k, flags, m->d_total, m->cap, m->ring,
-                                                      use_min, min_score, score_mode, row_stride, row_offset,
-                                                      out_scores, out_rows);
-    VM_LAUNCH_CHECK(ctx);
-    return VM_OK;
+    return vm_topk_redo_merge(m, part_s, part_o, p.nblk, Q, k, flags, use_min, min_score, score_mode, row_stride,
+                              row_offset, out_scores, out_rows, nullptr, nullptr, st);
 }
 
 template <int DT, int QT>
@@ -701,12 +542,11 @@ extern "C" int vm_topk_cosine_scoped(vm_memory *m, const void *queries, int Q, i
                          workspace_bytes, "vm_topk_cosine_scoped");
     if (rc != VM_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
-    if (m->dtype == VM_F16)
-        return scope_topk<VM_F16>(m, queries, Q, k, scope_lo, scope_hi, use_min_score, min_score, score_mode, row_stride,
-                                  row_offset, out_scores, out_rows, out_uncertified, out_query_flags, (char *)workspace,
-                                  st);
-    return scope_topk<VM_BF16>(m, queries, Q, k, scope_lo, scope_hi, use_min_score, min_score, score_mode, row_stride,
-                               row_offset, out_scores, out_rows, out_uncertified, out_query_flags, (char *)workspace, st);
+    return vm_by_dtype(m, [&](auto dt) {
+        return scope_topk<decltype(dt)::value>(m, queries, Q, k, scope_lo, scope_hi, use_min_score, min_score,
+                                               score_mode, row_stride, row_offset, out_scores, out_rows,
+                                               out_uncertified, out_query_flags, (char *)workspace, st);
+    });
 }
 
 extern "C" int vm_topk_cosine_scoped_exact(vm_memory *m, const void *queries, int Q, int k, const int64_t *scope_lo,
@@ -723,9 +563,8 @@ extern "C" int vm_topk_cosine_scoped_exact(vm_memory *m, const void *queries, in
     char *ws = (char *)workspace;
     scope_fill_flags_kernel<<<(Q + 255) / 256, 256, 0, st>>>((int32_t *)(ws + p.off_flags), Q);
     VM_LAUNCH_CHECK(ctx);
-    if (m->dtype == VM_F16)
-        return scope_redo<VM_F16>(m, p, queries, Q, k, scope_lo, scope_hi, use_min_score, min_score, score_mode,
-                                  row_stride, row_offset, out_scores, out_rows, ws, st);
-    return scope_redo<VM_BF16>(m, p, queries, Q, k, scope_lo, scope_hi, use_min_score, min_score, score_mode, row_stride,
-                               row_offset, out_scores, out_rows, ws, st);
+    return vm_by_dtype(m, [&](auto dt) {
+        return scope_redo<decltype(dt)::value>(m, p, queries, Q, k, scope_lo, scope_hi, use_min_score, min_score,
+                                               score_mode, row_stride, row_offset, out_scores, out_rows, ws, st);
+    });
 }

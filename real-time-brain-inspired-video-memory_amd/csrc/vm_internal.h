@@ -74,6 +74,17 @@ __host__ __device__ inline DenseRange dense_newest(const RingView &rv) {
     return r;
 }
 
+// ---- exhaustive redo (topk_exact.hip), shared by the row, grouped and scoped searches -------------------------------
+// row blocks of a redo scan that scores `chunk` rows per selection pass: the one definition of nblk
+int vm_topk_redo_blocks(const vm_memory *m, int chunk);
+// Merge of the redo scans' slice winners, part_s / part_o [nblk][Q][k] = {score, age order}, for the flagged queries:
+// stable top-k, score mapping, min_score, row id = (base + order) * row_stride + row_offset.  gkey / out_keys: null, or
+// the grouped search's key column and key output.
+int vm_topk_redo_merge(vm_memory *m, const double *part_s, const int64_t *part_o, int nblk, int Q, int k,
+                       const int32_t *flags, int use_min, double min_score, int score_mode, int64_t row_stride,
+                       int64_t row_offset, double *out_scores, int64_t *out_rows, const int64_t *gkey,
+                       int64_t *out_keys, hipStream_t st);
+
 // ---- emit-only many-query scan (topk_emit.hip), driven by topk.hip ---------------------------------------------
 constexpr int VM_EMIT_CAP = 4096;  // candidate slots per query; more -> the query is marked for the exhaustive redo
 bool vm_topk_emit_supported(const vm_memory *m, int Q, int KL);

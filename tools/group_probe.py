@@ -1,6 +1,6 @@
 """Grouped top-k against the row top-k of the same (Q, k), event-timed and warm, in one process.
 
-  python tools/group_probe.py [--iters 20] [--out profiles/group_probe.json]
+  python tools/group_probe.py [--iters 20] [--out profiles/group_probe.json] [--lib other/libvidmem.so]
 
 Cases: 1 M x 768 fp16 in groups of 16 and of 5, Q = 1 / 16 / 64, k = 10; 1 M x 1024 bf16 in groups of 16, Q = 1,
 k = 20.  Rows are clustered (a centre per group + small noise), queries are noisy copies of stored rows.  "row" =
@@ -16,7 +16,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import torch  # noqa: E402
 
-import vidmem  # noqa: E402,F401
+import vidmem  # noqa: E402
+import vidmem._lib  # noqa: E402
 from vidmem.memory import EmbeddingMemory  # noqa: E402
 
 HBM_PEAK = 8.0e12
@@ -81,7 +82,10 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--lib", default=None, help="another build of libvidmem.so to time (an A/B against a parent commit)")
     a = ap.parse_args()
+    if a.lib:
+        vidmem._lib.LIB_PATH = os.path.abspath(a.lib)
     recs = []
     recs += run_case(1 << 20, 768, 16, "f16", [1, 16, 64], 10, a.iters)
     recs += run_case(1 << 20, 768, 5, "f16", [1, 16, 64], 10, a.iters)

@@ -1,6 +1,6 @@
 """Scoped top-k against the row top-k, event-timed and warm, the variants alternating in one process.
 
-  python tools/scope_probe.py [--iters 20] [--out profiles/scope_probe.json]
+  python tools/scope_probe.py [--iters 20] [--out profiles/scope_probe.json] [--lib other/libvidmem.so]
 
 Memory: 1 M x 768 fp16 in 8 contiguous sources of 131,072 rows, clustered rows (a centre per 16 rows + small noise),
 queries noisy copies of stored in-scope rows; Q = 1 / 16 at k = 10, and 1 M x 1024 bf16 at Q = 1, k = 20.
@@ -19,7 +19,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import torch  # noqa: E402
 
-import vidmem  # noqa: E402,F401
+import vidmem  # noqa: E402
+import vidmem._lib  # noqa: E402
 from vidmem.memory import SCOPE_ALL, EmbeddingMemory, make_tag, scope_of  # noqa: E402
 
 from group_probe import TD, clustered  # noqa: E402
@@ -106,7 +107,10 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--lib", default=None, help="another build of libvidmem.so to time (an A/B against a parent commit)")
     a = ap.parse_args()
+    if a.lib:
+        vidmem._lib.LIB_PATH = os.path.abspath(a.lib)
     recs = []
     recs += run_case(1 << 20, 768, "f16", [1, 16], 10, a.iters)
     recs += run_case(1 << 20, 1024, "bf16", [1], 20, a.iters)
