@@ -260,6 +260,50 @@ int vm_memory_append_novel(vm_memory *mem, const void *rows, int B, double thres
                            int32_t *out_keep, int64_t *out_row_of, int32_t *out_count, void *workspace,
                            size_t workspace_bytes, void *stream);
 
+/* ---- erase: forget rows and compact the memory ------------------------------------------------------------
+ * Forget rows by tag (a whole video, a time window, several of them) or by row id (a search result), and close the
+ * gaps.  The reference has no counterpart (its store only ever MERGEs, src/components/neo4j_handler.py:229-242).
+ * vm_memory_erase_scoped: tagged memories only (VM_ERR_INVALID otherwise).  scope_lo / scope_hi: device int64
+ *   [n_scopes], n_scopes >= 1, inclusive tag ranges by vm_topk_cosine_scoped's rule; a row is erased iff its tag lies
+ *   in at least one range (lo > hi matches nothing).
+ * vm_memory_erase_rows: row_ids device int64 [n]; ids < 0 or >= the row count are ignored and duplicates are allowed,
+ *   so a [Q, k] top-k result with its -1 padding is passed in place.  n = 0 is a no-op: only *out_erased = 0 is written.
+ * Afterwards the memory holds the surviving rows in their old order, renumbered 0 .. n'-1, and every column over slots
+ * [0, n_old) is bit for bit what a FRESH memory of the same kind holds after one vm_memory_append[_grouped|_tagged] of
+ * the survivors with their stored tags and keys: row bytes, norms and reciprocal norms (moved, never recomputed), tags,
+ * group keys, group ordinals, the group state (groups opened, last key = the last survivor's, open iff a row is left)
+ * and the row counter n'.  The vacated slots [n', n_old) are zeroed in every column: forgetting means the bytes are
+ * gone.  Groups follow the definition above, a maximal run of equal keys: two groups with one key that become adjacent
+ * are ONE group afterwards; a group that loses rows keeps the rest.
+ * Keys written by a plain append (-1 - row id) keep their VALUE: after an erase they no longer equal -1 - id, and a
+ *   later plain append can write a key that a surviving row already carries (adjacent, the two would be one group).
+ *   A caller that mixes plain appends and erases on a grouped memory gives its rows keys of its own.
+ * out_new_row_of: device int64 [n_old] (sized for the capacity if the count is not known), old id -> new id, or -1 for
+ * an erased row.  out_erased: device int64 [1], rewritten on every call.  Either may be NULL.
+ * No allocation, no synchronisation, no host read-back; the row count is read on the device and launches are sized
+ * from the capacity and the workspace: capturable, e.g. {vm_memory_append_tagged, vm_memory_erase_scoped,
+ * vm_topk_cosine_scoped} in one graph whose window is rewritten between replays.  Launches grow with
+ * capacity / segment, not with the row count.
+ * Host mirror: the count is decided on the device, so vm_memory_size is NOT adjusted - vm_memory_sync brings it in
+ * line, as after vm_memory_append_novel (a non-ring memory refuses appends by the mirror: sync before appending into
+ * the reclaimed capacity).
+ * Rings: a ring that has not wrapped (at most `capacity` rows appended) is handled like a linear memory and goes on as
+ * a ring.  A ring that has wrapped is refused with VM_ERR_UNSUPPORTED by the mirror (mirror > capacity; the mirror must
+ * therefore be current); whatever the mirror said, when the DEVICE count exceeds the capacity nothing is touched and
+ * *out_erased = -1.
+ * Workspace: vm_memory_erase_workspace_bytes(mem, segment_rows): keep flags and their prefix (5 bytes x capacity), the
+ * per-chunk counts, and one SEGMENT of scratch for every column (segment_rows x (2 D + 28) bytes).  The rows move
+ * segment by segment through that scratch; segment_rows = 0 names the library's default (65,536 rows, or the capacity
+ * if smaller), other values are rounded up to a multiple of 256 and capped at the default.  The call derives its
+ * segment from workspace_bytes - the largest multiple of 256 rows that fits, at most the default; fewer than 256 rows
+ * of scratch is VM_ERR_NOMEM.  The result does not depend on the segment. */
+size_t vm_memory_erase_workspace_bytes(const vm_memory *mem, int64_t segment_rows);
+int vm_memory_erase_scoped(vm_memory *mem, const int64_t *scope_lo, const int64_t *scope_hi, int n_scopes,
+                           int64_t *out_new_row_of, int64_t *out_erased, void *workspace, size_t workspace_bytes,
+                           void *stream);
+int vm_memory_erase_rows(vm_memory *mem, const int64_t *row_ids, int64_t n, int64_t *out_new_row_of,
+                         int64_t *out_erased, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- cosine top-k over the memory ---------------------------------------------------------------------
  * Replaces PreLLMInjector._calculate_batch_similarities + _cosine_similarity
  * (src/components/pre_llm_injector.py:346-388) and the Cypher scan of HybridRetriever._vector_search_chunks

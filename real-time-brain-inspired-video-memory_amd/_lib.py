@@ -39,6 +39,7 @@ SYMBOLS = [
     "vm_topk_grouped_workspace_bytes", "vm_topk_cosine_grouped", "vm_topk_cosine_grouped_exact",
     "vm_memory_create_tagged", "vm_memory_append_tagged", "vm_memory_tags",
     "vm_novelty_workspace_bytes", "vm_memory_append_novel",
+    "vm_memory_erase_workspace_bytes", "vm_memory_erase_scoped", "vm_memory_erase_rows",
     "vm_topk_scoped_workspace_bytes", "vm_topk_cosine_scoped", "vm_topk_cosine_scoped_exact",
     "vm_topk_workspace_bytes", "vm_topk_cosine", "vm_topk_redo_workspace_bytes", "vm_topk_redo_flagged",
     "vm_topk_exact_workspace_bytes", "vm_topk_cosine_exact",
@@ -130,6 +131,9 @@ def lib() -> C.CDLL:
         "vm_memory_tags": (vp, [vp]),
         "vm_novelty_workspace_bytes": (sz, [vp, i32]),
         "vm_memory_append_novel": (i32, [vp, vp, i32, f64, vp, vp, i64, vp, vp, vp, vp, vp, vp, sz, vp]),
+        "vm_memory_erase_workspace_bytes": (sz, [vp, i64]),
+        "vm_memory_erase_scoped": (i32, [vp, vp, vp, i32, vp, vp, vp, sz, vp]),
+        "vm_memory_erase_rows": (i32, [vp, vp, i64, vp, vp, vp, sz, vp]),
         "vm_topk_scoped_workspace_bytes": (sz, [vp, i32, i32]),
         "vm_topk_cosine_scoped": (i32, [vp, vp, i32, i32, vp, vp, i32, f64, i32, i64, i64, vp, vp, vp, vp, vp, sz, vp]),
         "vm_topk_cosine_scoped_exact": (i32, [vp, vp, i32, i32, vp, vp, i32, f64, i32, i64, i64, vp, vp, vp, sz, vp]),

@@ -16,7 +16,10 @@ holds many videos: ``topk_scoped`` ranks only the rows whose tag lies in the que
 counterpart of the reference's ``{graph_uuid: $graph_uuid}`` predicate (include/vidmem.h).
 
 All arithmetic is in libvidmem.so (csrc/memory.hip, csrc/topk.hip, csrc/topk_exact.hip, csrc/topk_group.hip,
-csrc/topk_scope.hip, csrc/novelty.hip).
+csrc/topk_scope.hip, csrc/novelty.hip, csrc/erase.hip).
+
+``erase`` forgets rows - a whole video or time window by its tags, or rows by id - and compacts the memory in place, so
+that a non-ring memory that has filled up takes new rows again (include/vidmem.h).
 """
 from __future__ import annotations
 
@@ -69,6 +72,21 @@ class Novelty(NamedTuple):
     kept: int
 
 
+class Erased(NamedTuple):
+    """What ``erase`` did: ``count`` rows are gone; ``new_row_of`` int64 [rows before the call] on the device maps every
+    old row id to its new one, -1 for an erased row."""
+    count: int
+    new_row_of: torch.Tensor
+
+
+def _check_erase_selectors(rows, scope) -> None:
+    """``erase`` / ``enqueue_erase`` take exactly one selector."""
+    if rows is not None and scope is not None:
+        raise ValueError("erase takes rows or scope, not both")
+    if rows is None and scope is None:
+        raise ValueError("erase needs a selector: rows=... or scope=...")
+
+
 def _torch_dtype(name: str):
     return {"f16": torch.float16, "bf16": torch.bfloat16}[name]
 
@@ -97,6 +115,7 @@ class EmbeddingMemory:
         self._gflags = None         # per-query flags of the last grouped call (device int32)
         self._guncert = None        # queries the grouped fast path could not certify (device int32, accumulates)
         self._nscratch = None       # buffers of the gated append (NoveltyScratch), grown on demand
+        self._escratch = None       # buffers of erase (EraseScratch), made on demand
         # Host tables: chunk id (reference pre_llm_injector.py:91) and {"time":..., "content":...} (for
         # _vector_search_chunks) of row (table_base + i).  table_base stays 0 unless a ring has wrapped far enough for
         # the slots of overwritten rows to be dropped (see _trim_tables); use id_of / meta_of for row -> entry.
@@ -342,6 +361,100 @@ class EmbeddingMemory:
         if len(keep_parts) == 1:
             return Novelty(keep_parts[0], row_parts[0], kept)
         return Novelty(torch.cat(keep_parts), torch.cat(row_parts), kept)
+
+    # ---- erase (include/vidmem.h vm_memory_erase_scoped / vm_memory_erase_rows) ----------------------
+    def prepare_erase(self, segment_rows: int = 0) -> "EraseScratch":
+        """Size this memory's own erase buffers now (before a graph capture: a capture must not allocate).
+        ``segment_rows``: rows that move through the scratch at a time; 0 = the library's default."""
+        need = int(self.L.vm_memory_erase_workspace_bytes(self.handle, int(segment_rows)))
+        if self._escratch is None or self._escratch.ws.numel() != max(need, 256):
+            self._escratch = EraseScratch.for_(self, segment_rows)
+        return self._escratch
+
+    def _erase_scopes(self, scope) -> torch.Tensor:
+        """-> device int64 [2, n] (row 0 = lo, row 1 = hi) from one (lo, hi), a sequence of pairs, or an int64 [n, 2]
+        tensor (a device tensor is not read on the host)."""
+        if isinstance(scope, torch.Tensor):
+            if scope.dtype != torch.int64 or scope.dim() != 2 or scope.shape[1] != 2 or scope.shape[0] < 1:
+                raise ValueError("a scope tensor must be int64 [n, 2], n >= 1")
+            return scope.to(self.device).t().contiguous()
+        pairs = list(scope)
+        if len(pairs) == 2 and not hasattr(pairs[0], "__len__"):
+            pairs = [pairs]
+        if not pairs or any(len(p) != 2 for p in pairs):
+            raise ValueError("a scope is a pair (lo, hi), or a sequence of at least one pair")
+        vals = [[int(p[0]) for p in pairs], [int(p[1]) for p in pairs]]
+        return torch.tensor(vals, dtype=torch.int64).to(self.device)
+
+    def enqueue_erase(self, rows=None, scope=None, scratch: Optional["EraseScratch"] = None
+                      ) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The capturable erase -> (new_row_of int64 [capacity], erased int64 [1]): the buffers of ``scratch`` (default:
+        this memory's own, ``prepare_erase``), valid until the next call on it.  Entries of ``new_row_of`` at and beyond
+        the row count before the call are not written.
+
+        Enqueues ``vm_memory_erase_rows`` / ``vm_memory_erase_scoped`` on the current stream: nothing is read on the
+        host, the id / meta tables and the host row count are not touched - ``sync()`` afterwards brings the count in
+        line (the tables are then cut to it, not remapped: ``erase`` is the form that remaps them).  Inside a graph
+        capture pass ``scope`` as an int64 ``[n, 2]`` device tensor or ``rows`` as an int64 device tensor (rewritten in
+        place between replays) and a ``scratch`` the session owns."""
+        _check_erase_selectors(rows, scope)
+        if scope is not None and not self.tagged:
+            raise ValueError("erase by scope needs a tagged memory (EmbeddingMemory(..., tagged=True))")
+        if scratch is None:
+            scratch = self._escratch or self.prepare_erase()
+        ptr = lambda x: C.c_void_p(x.data_ptr())
+        st = _lib.current_stream_ptr()
+        if scope is not None:
+            sel = self._erase_scopes(scope)
+            self.ctx.check(self.L.vm_memory_erase_scoped(self.handle, ptr(sel[0]), ptr(sel[1]), sel.shape[1],
+                                                         ptr(scratch.new_row_of), ptr(scratch.erased), ptr(scratch.ws),
+                                                         scratch.ws.numel(), st))
+        else:
+            if isinstance(rows, torch.Tensor):
+                sel = rows.to(device=self.device, dtype=torch.int64).reshape(-1).contiguous()
+            else:
+                sel = torch.tensor([int(r) for r in rows], dtype=torch.int64).to(self.device)
+            self.ctx.check(self.L.vm_memory_erase_rows(self.handle, C.c_void_p(sel.data_ptr() if sel.numel() else 0),
+                                                       sel.numel(), ptr(scratch.new_row_of), ptr(scratch.erased),
+                                                       ptr(scratch.ws), scratch.ws.numel(), st))
+        sel.record_stream(torch.cuda.current_stream())
+        return scratch.new_row_of, scratch.erased
+
+    def erase(self, rows=None, scope=None) -> Erased:
+        """Forget rows and close the gaps -> ``Erased(count, new_row_of)``.
+
+        Exactly one selector: ``scope`` = one inclusive tag range ``(lo, hi)`` (``scope_of(3)``: all of video 3) or a
+        sequence of them, on a tagged memory - a row goes when its tag lies in at least one; ``rows`` = a sequence or
+        tensor of row ids, any shape - ids below 0 or beyond the end are ignored and duplicates are allowed, so the
+        ``rows`` of a top-k result are passed as they are.
+        The survivors keep their order and are renumbered 0 .. n'-1; everything the memory holds - rows, norms, tags,
+        group keys, groups - is then what a fresh memory would hold after one append of the survivors (two groups with
+        one key that become adjacent are one group), and the freed capacity takes new rows.  The id / meta tables are
+        remapped (``id_of(new) ==`` the old id) and ``len()`` follows.  Keys of rows that were appended without a
+        group keep their value (include/vidmem.h).
+        A ring that has wrapped is refused.  This form SYNCHRONISES once (``enqueue_erase`` is the form that does not)."""
+        _check_erase_selectors(rows, scope)
+        new_row_of, erased = self.enqueue_erase(rows=rows, scope=scope)
+        total = int(self.L.vm_memory_sync(self.handle, _lib.current_stream_ptr()))     # the one wait
+        if total < 0:
+            self.ctx.check(total)
+        count = int(erased.item())
+        if count < 0:
+            raise _lib.VidmemError(_lib.VM_ERR_UNSUPPORTED, "erase: the ring has wrapped (the host row count was stale)")
+        n_old = total + count
+        out = new_row_of[:n_old].clone() if count else torch.arange(n_old, dtype=torch.int64, device=self.device)
+        if count:
+            kept = torch.nonzero(out >= 0).flatten().tolist()
+            pad = [None] * max(0, n_old - self.table_base - len(self.ids))
+            ids, meta = self.ids + pad, self.meta + pad
+            self.ids = [ids[i - self.table_base] for i in kept]
+            self.meta = [meta[i - self.table_base] for i in kept]
+            self.table_base = 0
+        self.sync()
+        if self.grouped:   # what a later append(group=None) must not repeat: the last survivor's key (read only then)
+            keys = _tensor_from_ptr(self.L.vm_memory_group_keys(self.handle), (max(total, 1),), torch.int64, self.device)
+            self._last_keys_dev = keys[total - 1:total].clone() if total else None
+        return Erased(count, out)
 
     def new_source(self) -> int:
         """A source index no earlier ``new_source`` call of this memory returned: one per video (``make_tag``)."""
@@ -769,6 +882,22 @@ class NoveltyScratch:
     def for_(cls, memory: "EmbeddingMemory", B: int) -> "NoveltyScratch":
         B = max(1, min(int(B), NOVEL_MAX_ROWS))
         return cls(memory.device, B, int(memory.L.vm_novelty_workspace_bytes(memory.handle, B)))
+
+
+class EraseScratch:
+    """Device buffers of erase: the workspace (keep flags, their prefix, one segment of every column), ``new_row_of``
+    (int64 [capacity]) and ``erased`` (int64 [1]).  Like ``NoveltyScratch``, an owner keeps ONE instance per stream /
+    captured graph: a hipGraph bakes the addresses in."""
+
+    def __init__(self, device, capacity: int, ws_bytes: int):
+        self.ws = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=device)
+        self.new_row_of = torch.full((max(capacity, 1),), -1, dtype=torch.int64, device=device)
+        self.erased = torch.zeros(1, dtype=torch.int64, device=device)
+
+    @classmethod
+    def for_(cls, memory: "EmbeddingMemory", segment_rows: int = 0) -> "EraseScratch":
+        need = int(memory.L.vm_memory_erase_workspace_bytes(memory.handle, int(segment_rows)))
+        return cls(memory.device, memory.capacity, need)
 
 
 class TopkScratch:
