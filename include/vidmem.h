@@ -394,6 +394,46 @@ int vm_topk_cosine_scoped_exact(vm_memory *mem, const void *queries, int Q, int 
                                 const int64_t *scope_hi, int use_min_score, double min_score, int score_mode,
                                 int64_t row_stride, int64_t row_offset, double *out_scores, int64_t *out_rows,
                                 void *workspace, size_t workspace_bytes, void *stream);
+/* Range search: EVERY row above a threshold, in time order - "which frames of this video show X?" has no k.  The
+ * threshold is the reference's own notion of relevance (`vector.similarity.cosine(...) > 0.3`,
+ * src/pipeline/retriever_hybrid.py:296-298; `>= compression_threshold`, :494-504); this call returns all of what passes
+ * it, not the best 64.
+ * Hit rule: for query q a hit is a live row r that is in q's scope when scopes are given (scope_lo[q] <= tag[r] <=
+ *   scope_hi[q], vm_topk_cosine_scoped's rule) and whose shown score - the reference cosine of vm_topk_cosine, fp64 on the
+ *   stored 16-bit values, zero-norm guard, then the score_mode mapping - is STRICTLY above min_score, like use_min_score.
+ *   A zero row or a zero query scores 0.0 and is a hit iff the shown score of 0.0 is above min_score.
+ * Result: the hits in ASCENDING ROW ID: append order, oldest first in a ring, time order within a video.  The first
+ *   max_hits are written, out_rows [Q, max_hits] = row_id * row_stride + row_offset and out_scores [Q, max_hits] the
+ *   reference's fp64 values bit for bit; the rest is padded with -1 / 0.0.  out_counts[q] (device int64 [Q]) is the TOTAL
+ *   number of hits, also when it exceeds max_hits: the caller sees the truncation.  max_hits = 0 is a count-only call
+ *   (out_rows / out_scores may then be NULL).  The result depends on the memory, the query, its scope and the threshold
+ *   only: not on Q, the other queries of the call, the launch geometry or the workspace size.
+ * Scopes: scope_lo / scope_hi device int64 [Q], or both NULL = every live row, on any memory (plain, grouped, tagged,
+ *   ring).  Non-NULL scopes on an untagged memory, or one NULL and one not: VM_ERR_INVALID.  An empty scope (lo > hi, or
+ *   no live row matches) gives count 0.
+ * Thresholds: NaN is VM_ERR_INVALID; -inf, or anything below every score, returns every in-scope row; >= 2 returns none.
+ * ALWAYS the exhaustive answer, and there are no flags: the cut is known before the scan starts.  An fp32 MFMA scan bounds
+ *   each pair's exact cosine from above by (double)fp32_score / ||q|| + 2 (D + 8) 2^-24 (vm_topk_cosine's bound); a pair
+ *   whose bound's shown score is not above min_score is provably no hit and is dropped unscored, every other pair is
+ *   re-scored exactly and is a hit iff its exact shown score passes.  out_rescored[q] (device int64 [Q], may be NULL):
+ *   the pairs of query q that were scored exactly in this call (>= out_counts[q]; equal when no score lies within the
+ *   bound of the threshold).  Order comes from prefix sums over separate launches: deterministic, no atomics.
+ * No allocation, no synchronisation, no host read-back; the row count is read on the device and launches are sized from
+ * the capacity: capturable, and a replay after an append sees the new rows.  Calls are stream-ordered per handle.
+ * Workspace: vm_range_workspace_bytes(mem, Q) = with P = capacity rounded up to 64 rows and C = ceil(P / 4096) chunks,
+ *   Q x P / 8 bytes of candidate bits + Q x P / 8 bytes of hit bits + Q x P x 8 bytes of exact scores (written at
+ *   candidate slots only) + Q x C x 16 bytes of chunk counts and prefixes + Q x 12 bytes of cuts and query norms, each
+ *   array rounded up to 256 bytes: 8.25 bytes per (query, slot). */
+size_t vm_range_workspace_bytes(const vm_memory *mem, int Q);
+int vm_range_cosine(vm_memory *mem, const void *queries, int Q, double min_score, int score_mode,
+                    const int64_t *scope_lo, const int64_t *scope_hi, int64_t row_stride, int64_t row_offset,
+                    int64_t max_hits, int64_t *out_rows, double *out_scores, int64_t *out_counts,
+                    int64_t *out_rescored, void *workspace, size_t workspace_bytes, void *stream);
+/* The same contract, exhaustive only: every live in-scope pair scored exactly, no fp32 scan (slow; tests, and a checker). */
+int vm_range_cosine_exact(vm_memory *mem, const void *queries, int Q, double min_score, int score_mode,
+                          const int64_t *scope_lo, const int64_t *scope_hi, int64_t row_stride, int64_t row_offset,
+                          int64_t max_hits, int64_t *out_rows, double *out_scores, int64_t *out_counts,
+                          void *workspace, size_t workspace_bytes, void *stream);
 /* All-pairs exact cosine, out [Q, S] fp64: the post-compression filter of
  * src/pipeline/retriever_hybrid.py:494-504 (query vs segment embeddings) and a checker for the scan.
  * rows [S, D] dtype need not live in a vm_memory.  dtype VM_F32 takes fp32 operands: an embedder that returns fp32

@@ -16,10 +16,13 @@ holds many videos: ``topk_scoped`` ranks only the rows whose tag lies in the que
 counterpart of the reference's ``{graph_uuid: $graph_uuid}`` predicate (include/vidmem.h).
 
 All arithmetic is in libvidmem.so (csrc/memory.hip, csrc/topk.hip, csrc/topk_exact.hip, csrc/topk_group.hip,
-csrc/topk_scope.hip, csrc/novelty.hip, csrc/erase.hip).
+csrc/topk_scope.hip, csrc/novelty.hip, csrc/erase.hip, csrc/range.hip).
 
 ``erase`` forgets rows - a whole video or time window by its tags, or rows by id - and compacts the memory in place, so
 that a non-ring memory that has filled up takes new rows again (include/vidmem.h).
+
+``range_search`` returns EVERY row above a threshold, in time order, where the top-k searches return the best k;
+``moments`` turns those hits into ``(video, t0, t1, peak)`` runs (csrc/range.hip, include/vidmem.h).
 """
 from __future__ import annotations
 
@@ -79,6 +82,70 @@ class Erased(NamedTuple):
     new_row_of: torch.Tensor
 
 
+class RangeHits(NamedTuple):
+    """What ``enqueue_range`` returns, all on the device: ``counts`` int64 [Q] (the TOTAL hits of each query, also above
+    ``max_hits``), ``rows`` int64 [Q, max_hits] (-1 padded) and ``scores`` float64 [Q, max_hits] (0.0 padded)."""
+    counts: torch.Tensor
+    rows: torch.Tensor
+    scores: torch.Tensor
+
+
+class RangeResult(NamedTuple):
+    """One query's entry of ``range_search``: ``rows`` int64 and ``scores`` float64, trimmed to the hits that were
+    written, in ascending row id; ``count`` the query's total number of hits (``> len(rows)`` = cut by ``max_hits``)."""
+    rows: torch.Tensor
+    scores: torch.Tensor
+    count: int
+
+
+class Moment(NamedTuple):
+    """A run of hits of one source, close in time (``segment_moments``)."""
+    source: int
+    t0_ms: int
+    t1_ms: int
+    first_row: int
+    last_row: int
+    hits: int
+    peak_row: int
+    peak_score: float
+
+
+def segment_moments(rows, scores, tags, max_gap_ms) -> List[Moment]:
+    """One query's hits -> moments.  ``rows`` int64 [n] ascending, ``scores`` float64 [n], ``tags`` int64 [n] (the tag
+    of each hit row, ``make_tag``'s split: source = tag >> 40, milliseconds = the low 40 bits): numpy in, a list out.
+
+    Walks the hits in row order.  A run continues while the source stays the same and the milliseconds do not decrease
+    and grow by at most ``max_gap_ms``; anything else opens a new run.  Hits tagged INT64_MIN have no time and are left
+    out.  A run's peak is its highest score, the lowest row on ties.  Moments come back ordered by
+    (peak_score descending, first_row ascending), the order relation of every search here."""
+    import numpy as np
+    rows = np.asarray(rows, dtype=np.int64).reshape(-1)
+    scores = np.asarray(scores, dtype=np.float64).reshape(-1)
+    tags = np.asarray(tags, dtype=np.int64).reshape(-1)
+    if not (rows.shape == scores.shape == tags.shape):
+        raise ValueError("rows, scores and tags differ in length")
+    gap = int(max_gap_ms)
+    if gap < 0:
+        raise ValueError("max_gap_ms is negative")
+    timed = tags != INT64_MIN
+    rows, scores, tags = rows[timed], scores[timed], tags[timed]
+    if rows.size == 0:
+        return []
+    src = tags >> TAG_MS_BITS
+    ms = tags & (TAG_MAX_MS - 1)
+    step = ms[1:] - ms[:-1]
+    cut = (src[1:] != src[:-1]) | (step < 0) | (step > gap)
+    starts = np.concatenate([[0], np.nonzero(cut)[0] + 1])
+    ends = np.concatenate([starts[1:], [rows.size]])
+    out = []
+    for a, b in zip(starts.tolist(), ends.tolist()):
+        peak = a + int(np.argmax(scores[a:b]))     # argmax keeps the first = lowest row on ties
+        out.append(Moment(int(src[a]), int(ms[a]), int(ms[b - 1]), int(rows[a]), int(rows[b - 1]), b - a,
+                          int(rows[peak]), float(scores[peak])))
+    out.sort(key=lambda m: (-m.peak_score, m.first_row))
+    return out
+
+
 def _check_erase_selectors(rows, scope) -> None:
     """``erase`` / ``enqueue_erase`` take exactly one selector."""
     if rows is not None and scope is not None:
@@ -116,6 +183,8 @@ class EmbeddingMemory:
         self._guncert = None        # queries the grouped fast path could not certify (device int32, accumulates)
         self._nscratch = None       # buffers of the gated append (NoveltyScratch), grown on demand
         self._escratch = None       # buffers of erase (EraseScratch), made on demand
+        self._rscratch = None       # buffers of the range search (RangeScratch), grown on demand
+        self._rlast = None          # the scratch of the last range call (last_range_rescored)
         # Host tables: chunk id (reference pre_llm_injector.py:91) and {"time":..., "content":...} (for
         # _vector_search_chunks) of row (table_base + i).  table_base stays 0 unless a ring has wrapped far enough for
         # the slots of overwritten rows to be dropped (see _trim_tables); use id_of / meta_of for row -> entry.
@@ -722,6 +791,125 @@ class EmbeddingMemory:
         sc.record_stream(torch.cuda.current_stream())
         return scores, rows
 
+    # ---- range search (include/vidmem.h vm_range_cosine) ---------------------------------------------
+    def prepare_range(self, Q: int, max_hits: int) -> "RangeScratch":
+        """Size this memory's own range-search buffers for ``Q`` queries and ``max_hits`` hits each now (before a graph
+        capture: a capture must not allocate)."""
+        if self._rscratch is None or not self._rscratch.fits(self, Q, max_hits):
+            self._rscratch = RangeScratch.for_(self, Q, max_hits)
+        return self._rscratch
+
+    def _range_call(self, q: torch.Tensor, sc: Optional[torch.Tensor], min_score: float, score_mode: int,
+                    max_hits: int, scratch: Optional["RangeScratch"], exact: bool) -> RangeHits:
+        Q = q.shape[0]
+        if scratch is None:
+            scratch = self.prepare_range(Q, max_hits)
+        elif not scratch.fits(self, Q, max_hits):
+            raise ValueError("caller-owned range scratch is too small for this (Q, max_hits)")
+        rows = scratch.rows[:Q * max_hits].view(Q, max_hits)
+        scores = scratch.scores[:Q * max_hits].view(Q, max_hits)
+        ptr = lambda x: C.c_void_p(x.data_ptr() if x is not None and x.numel() else 0)
+        lo, hi = (ptr(sc[0]), ptr(sc[1])) if sc is not None else (C.c_void_p(0), C.c_void_p(0))
+        head = (self.handle, ptr(q), Q, float(min_score), int(score_mode), lo, hi, 1, 0, int(max_hits),
+                ptr(rows), ptr(scores), ptr(scratch.counts))
+        tail = (ptr(scratch.ws), scratch.ws.numel(), _lib.current_stream_ptr())
+        if exact:
+            self.ctx.check(self.L.vm_range_cosine_exact(*head, *tail))
+        else:
+            self.ctx.check(self.L.vm_range_cosine(*head, ptr(scratch.rescored), *tail))
+        cur = torch.cuda.current_stream()
+        q.record_stream(cur)
+        if sc is not None:
+            sc.record_stream(cur)
+        self._rlast = scratch
+        return RangeHits(scratch.counts[:Q], rows, scores)
+
+    def _range_args(self, queries, min_score, scope, score_mode):
+        ms = float(min_score)
+        if math.isnan(ms):
+            raise ValueError("the range threshold is NaN")
+        if score_mode not in (_lib.VM_SCORE_RAW, _lib.VM_SCORE_UNIT_INTERVAL):
+            raise ValueError("score_mode must be VM_SCORE_RAW or VM_SCORE_UNIT_INTERVAL")
+        if scope is not None and not self.tagged:
+            raise ValueError("a scope needs a tagged memory (EmbeddingMemory(..., tagged=True))")
+        q = self._as_rows(queries)
+        return q, (self._scope_tensor(scope, q.shape[0]) if scope is not None else None), ms
+
+    def enqueue_range(self, queries, min_score, scope=None, score_mode: int = _lib.VM_SCORE_RAW, max_hits: int = 1024,
+                      scratch: Optional["RangeScratch"] = None) -> RangeHits:
+        """The capturable range search -> ``RangeHits(counts, rows, scores)``: views of the buffers of ``scratch``
+        (default: this memory's own, ``prepare_range``), valid until the next range call on it.
+
+        Every row whose shown score is strictly above ``min_score``, in ascending row id (time order); the first
+        ``max_hits`` of each query are written, ``counts`` holds the full number.  ``scope``: what ``topk_scoped`` takes
+        (tagged memories; ``None`` = every live row, on any memory).  Enqueues ``vm_range_cosine`` on the current stream:
+        nothing is read on the host.  Inside a graph capture pass ``scope`` as an int64 ``[Q, 2]`` device tensor
+        (rewritten in place between replays) and a ``scratch`` the session owns, or call ``prepare_range`` first."""
+        if int(max_hits) < 0:
+            raise ValueError("max_hits is negative")
+        q, sc, ms = self._range_args(queries, min_score, scope, score_mode)
+        return self._range_call(q, sc, ms, score_mode, int(max_hits), scratch, False)
+
+    def range_search(self, queries, min_score, scope=None, score_mode: int = _lib.VM_SCORE_RAW,
+                     max_hits: Optional[int] = None, exact: bool = False) -> List[RangeResult]:
+        """Every row above a threshold -> one ``RangeResult(rows, scores, count)`` per query: the rows (int64, ascending
+        id = time order) whose shown score is strictly above ``min_score`` and their scores (float64, the reference's
+        values bit for bit), on the device.  Always the exhaustive answer (include/vidmem.h vm_range_cosine).
+
+        ``max_hits=None``: everything - a count-only call, ONE synchronising read of the counts, then the filling call
+        with the exact size.  With a ``max_hits`` only the first ``max_hits`` hits of each query are returned and
+        ``count`` still holds the query's full number, so a caller sees the truncation (one read of the counts too).
+        ``scope``: as in ``topk_scoped``, tagged memories only; ``None`` = every live row, on any memory.
+        ``exact=True`` scores every in-scope pair exactly instead of scanning first (slow; a checker).  The number of
+        pairs the last fast call scored exactly is in ``last_range_rescored``."""
+        q, sc, ms = self._range_args(queries, min_score, scope, score_mode)
+        Q = q.shape[0]
+        if max_hits is not None and int(max_hits) < 0:
+            raise ValueError("max_hits is negative")
+        if max_hits is None:
+            counts = self._range_call(q, sc, ms, score_mode, 0, None, exact).counts.cpu().tolist()   # the one wait
+            width = max(counts) if counts else 0
+            if width == 0:
+                return [RangeResult(torch.zeros(0, dtype=torch.int64, device=self.device),
+                                    torch.zeros(0, dtype=torch.float64, device=self.device), 0) for _ in range(Q)]
+            hits = self._range_call(q, sc, ms, score_mode, width, None, exact)
+        else:
+            hits = self._range_call(q, sc, ms, score_mode, int(max_hits), None, exact)
+            counts = hits.counts.cpu().tolist()
+        out = []
+        for i, c in enumerate(counts):
+            n = min(int(c), hits.rows.shape[1])
+            out.append(RangeResult(hits.rows[i, :n].clone(), hits.scores[i, :n].clone(), int(c)))
+        return out
+
+    @property
+    def last_range_rescored(self) -> Optional[torch.Tensor]:
+        """int64 per query: the pairs the last fast range call scored exactly (device tensor)."""
+        return None if self._rlast is None else self._rlast.rescored
+
+    def moments(self, queries, min_score, scope=None, max_gap_ms: int = 1000,
+                score_mode: int = _lib.VM_SCORE_RAW) -> List[List[Moment]]:
+        """``range_search`` then ``segment_moments``: per query the runs of hits of one video that lie at most
+        ``max_gap_ms`` apart, each with its first and last milliseconds and its peak - "one hit per event", ordered by
+        (peak score descending, first row ascending).  Tagged memories only; the hits' tags are gathered on the device
+        and read back once."""
+        if not self.tagged:
+            raise ValueError("moments needs a tagged memory (EmbeddingMemory(..., tagged=True))")
+        found = self.range_search(queries, min_score, scope=scope, score_mode=score_mode)
+        sizes = [int(f.rows.numel()) for f in found]
+        if sum(sizes) == 0:
+            return [[] for _ in found]
+        col = _tensor_from_ptr(self.L.vm_memory_tags(self.handle), (self.capacity,), torch.int64, self.device)
+        all_rows = torch.cat([f.rows for f in found])
+        packed = torch.stack([all_rows, col[all_rows % self.capacity],        # a row's slot, ring or not
+                              torch.cat([f.scores for f in found]).view(torch.int64)]).cpu().numpy()
+        out, at = [], 0
+        for n in sizes:
+            part = packed[:, at:at + n]
+            out.append(segment_moments(part[0], part[2].copy().view("float64"), part[1], max_gap_ms))
+            at += n
+        return out
+
     @property
     def last_scope_flags(self) -> Optional[torch.Tensor]:
         return self._sflags
@@ -882,6 +1070,30 @@ class NoveltyScratch:
     def for_(cls, memory: "EmbeddingMemory", B: int) -> "NoveltyScratch":
         B = max(1, min(int(B), NOVEL_MAX_ROWS))
         return cls(memory.device, B, int(memory.L.vm_novelty_workspace_bytes(memory.handle, B)))
+
+
+class RangeScratch:
+    """Device buffers of the range search for up to ``Q`` queries with ``max_hits`` hits each: the workspace (candidate
+    and hit bits, exact scores, chunk counts), ``counts`` and ``rescored`` (int64 [Q]) and the ``rows`` / ``scores``
+    outputs (Q x max_hits).  Like ``TopkScratch``, an owner keeps ONE instance per stream / captured graph: a hipGraph
+    bakes the addresses in."""
+
+    def __init__(self, device, Q: int, max_hits: int, ws_bytes: int):
+        self.Q, self.max_hits = int(Q), int(max_hits)
+        self.ws = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=device)
+        self.counts = torch.zeros(max(Q, 1), dtype=torch.int64, device=device)
+        self.rescored = torch.zeros(max(Q, 1), dtype=torch.int64, device=device)
+        self.rows = torch.full((max(Q * max_hits, 1),), -1, dtype=torch.int64, device=device)
+        self.scores = torch.zeros(max(Q * max_hits, 1), dtype=torch.float64, device=device)
+
+    def fits(self, memory: "EmbeddingMemory", Q: int, max_hits: int) -> bool:
+        return (self.counts.numel() >= Q and self.rows.numel() >= Q * max_hits and
+                self.ws.numel() >= int(memory.L.vm_range_workspace_bytes(memory.handle, int(Q))))
+
+    @classmethod
+    def for_(cls, memory: "EmbeddingMemory", Q: int, max_hits: int) -> "RangeScratch":
+        Q = max(1, int(Q))
+        return cls(memory.device, Q, int(max_hits), int(memory.L.vm_range_workspace_bytes(memory.handle, Q)))
 
 
 class EraseScratch:

@@ -153,6 +153,24 @@ def _zip_truncating_cosine(vec1, vec2) -> float:
     return dot_product / (mag1 * mag2)
 
 
+def frames_above(memory: EmbeddingMemory, query_embedding, min_score: float, *, score_mode: int, scope=None,
+                 max_hits: Optional[int] = None) -> List[Tuple[str, float]]:
+    """Every stored frame whose score against ``query_embedding`` is strictly above ``min_score`` as ``(id, score)``, in
+    time order (ascending row id) - the ``min_score`` leg of ``HipVectorSearch`` without the k
+    (``vector.similarity.cosine(...) > 0.3``, src/pipeline/retriever_hybrid.py:296-298, with no ``LIMIT``).
+
+    ``score_mode`` is a REQUIRED keyword for the reason ``HipVectorSearch`` gives: the threshold is compared after the
+    mapping, and nothing in the reference pins which mapping its server applied.  ``scope``: an inclusive tag range
+    (memory.scope_of), tagged memories only; ``max_hits``: keep the first ``max_hits`` frames only (``None`` = all).
+    Ids come from ``memory.id_of`` (``None`` for a row stored without one)."""
+    if score_mode not in (_lib.VM_SCORE_RAW, _lib.VM_SCORE_UNIT_INTERVAL):
+        raise ValueError("score_mode must be VM_SCORE_RAW or VM_SCORE_UNIT_INTERVAL")
+    _check_scope(memory, scope, False)
+    hit = memory.range_search([query_embedding] if not isinstance(query_embedding, torch.Tensor) else query_embedding,
+                              min_score, scope=scope, score_mode=score_mode, max_hits=max_hits)[0]
+    return [(memory.id_of(r), float(s)) for r, s in zip(hit.rows.cpu().tolist(), hit.scores.cpu().tolist())]
+
+
 class HipVectorSearch:
     """Mixin / stand-alone object for HybridRetriever's vector leg."""
 
