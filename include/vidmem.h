@@ -304,6 +304,65 @@ int vm_memory_erase_scoped(vm_memory *mem, const int64_t *scope_lo, const int64_
 int vm_memory_erase_rows(vm_memory *mem, const int64_t *row_ids, int64_t n, int64_t *out_new_row_of,
                          int64_t *out_erased, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- event segmentation: group frames by content, not by fixed chunk ---------------------------------------
+ * Cut the stored rows into EVENTS: maximal runs of consecutive row ids in which each frame resembles the one before it.
+ * The reference has no counterpart: it cuts a video every chunk_size_seconds (src/pipeline/vlm_extractor.py:38-46) and
+ * stores one text embedding per chunk (src/components/neo4j_handler.py:229-242).
+ * Live rows are the ids lo .. n-1 (lo = 0, or n - capacity in a wrapped ring).  For a live row r > lo, link(r) is the
+ * reference cosine of rows r-1 and r as in vm_topk_cosine - fp64 on the stored 16-bit values, one rounding per product
+ * and per partial sum, left to right, the stored fp64 norms (moved, never recomputed), a zero norm gives 0.0 - bit for
+ * bit; it is symmetric in its two rows.  link(lo) = 0.0.
+ * Row r OPENS an event iff
+ *   r == lo, or
+ *   !(link(r) > threshold)   (strict, like use_min_score and the novelty gate: a link equal to the threshold opens), or
+ *   on a tagged memory, with src = tag >> 40 and ms = tag & (2^40 - 1):
+ *     exactly one of tag[r-1], tag[r] is INT64_MIN, or
+ *     neither is INT64_MIN and src differs, or
+ *     neither is INT64_MIN, max_gap_ms >= 0, and ms[r] - ms[r-1] is negative or above max_gap_ms
+ *     (two INT64_MIN rows follow the score rule only).
+ * max_gap_ms < 0 switches the gap rule off (the source rule stays); max_gap_ms >= 0 on an untagged memory is
+ * VM_ERR_INVALID.  A NaN threshold is VM_ERR_INVALID; threshold >= 2 makes every row its own event; -inf leaves only
+ * the tag rules.
+ * Events are runs of consecutive row ids, as groups are: two videos appended in alternation cut each other's events at
+ * every switch.  Adjacent links chain: a slow pan whose neighbours all score 0.99 can end far from where it began -
+ * there is no drift guard and no cap on an event's length (long events send vm_topk_cosine_grouped to its exhaustive
+ * redo, see there; the novelty gate beside it keeps static scenes short).
+ * vm_memory_events: read-only, any memory (plain, grouped, tagged, ring).  out_links [n_live] (may be NULL): link(lo + i).
+ *   out_event_of [n_live] (may be NULL): the 0-based event index of row lo + i.  out_first_rows [max_events]: the first
+ *   row id of event e, -1 padded; NULL iff max_events == 0.  out_n_events [1]: the TOTAL number of events, also above
+ *   max_events.  All device pointers.
+ * vm_memory_regroup_events: rewrites the group columns, grouped memories only (VM_ERR_INVALID otherwise), so that the
+ *   grouped search returns one hit per event.  from_row: device int64 [1], or NULL = the whole memory.
+ *   Whole mode (from_row NULL or *from_row <= lo): for every live row, key = the row id of its event's first row,
+ *     ordinal = its event index (the oldest live row's event is 0); group state: groups = the event count, last key = the
+ *     last event's key, and the last event is CLOSED: a later keyed append opens a new group whatever its key, only a
+ *     tail regroup extends an event.  On a linear memory the two columns over [0, n) are bit for bit what a fresh
+ *     grouped memory holds after one vm_memory_append_grouped of the same rows with those keys.
+ *   Tail mode (lo < *from_row < n): rows below from_row are untouched; row from_row is judged against row from_row - 1
+ *     by the rule above: if it does not open an event it takes the key and ordinal of that row, whatever put them
+ *     there, otherwise its key is its own id and its ordinal the previous row's plus one; the rest follows from that
+ *     row.  Group state: groups = the last row's ordinal + 1, last key = the last row's key, closed.
+ *     *from_row >= n touches nothing and writes *out_n_events = 0.
+ *     Plain appends, each followed by a tail regroup from its first new row, leave exactly what one whole regroup
+ *     leaves at the end - on a linear memory or a ring that has not wrapped, with no erase in between.  In a wrapped
+ *     ring the first live event keeps the key it was formed with; a whole regroup would renumber it.
+ *   out_n_events [1] (may be NULL): the events opened among the rows the call covered.
+ * Both: no allocation, no synchronisation, no host read-back; the row count is read on the device and launches are sized
+ * from the capacity: capturable, and a replay after an append sees the new rows.  An empty memory writes
+ * *out_n_events = 0 and nothing else.  A workspace below vm_memory_events_workspace_bytes is refused with VM_ERR_NOMEM
+ * before any launch.  One exact pair per row, one pass over the rows (n x D x 2 bytes); the prefix sums run over
+ * separate launches, deterministic, no atomics: the result does not depend on launch geometry or workspace size.
+ * Workspace: one flag byte per slot + 16 bytes per 256 slots + 256 bytes, each array rounded up to 256 bytes.
+ * vm_memory_group_ordinals: device pointer to the [capacity] group-ordinal column (slot order, like
+ *   vm_memory_group_keys), 0 if not grouped. */
+size_t vm_memory_events_workspace_bytes(const vm_memory *mem);
+int vm_memory_events(vm_memory *mem, double threshold, int64_t max_gap_ms, double *out_links, int64_t *out_event_of,
+                     int64_t max_events, int64_t *out_first_rows, int64_t *out_n_events, void *workspace,
+                     size_t workspace_bytes, void *stream);
+int vm_memory_regroup_events(vm_memory *mem, double threshold, int64_t max_gap_ms, const int64_t *from_row,
+                             int64_t *out_n_events, void *workspace, size_t workspace_bytes, void *stream);
+const int64_t *vm_memory_group_ordinals(const vm_memory *mem);
+
 /* ---- cosine top-k over the memory ---------------------------------------------------------------------
  * Replaces PreLLMInjector._calculate_batch_similarities + _cosine_similarity
  * (src/components/pre_llm_injector.py:346-388) and the Cypher scan of HybridRetriever._vector_search_chunks

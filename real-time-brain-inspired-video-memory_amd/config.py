@@ -13,7 +13,8 @@ Keys the hot path honours (same names and defaults as the reference where it has
   retrieval.top_k = 5, top_k_chunks = 8, compression_threshold = 0.7               src/core/config.py:70-86
 New:
   encoder: {arch, dtype, weights, seed, device, top_k, look_ahead_chunks}   which vision encoder stands where the remote VLM was
-  memory:  {capacity, ring, dtype, snapshot, group_by, tag_by, novelty_threshold}   the HBM-resident store that stands where Chunk.embedding was
+  memory:  {capacity, ring, dtype, snapshot, group_by, tag_by, novelty_threshold, event_threshold, event_max_gap_ms}
+           the HBM-resident store that stands where Chunk.embedding was
   text_encoder: {arch, dtype, weights, seed, device, tokenizer}   the question embedder of the retriever (arch null = none;
            read through section(), so it never appears in a config that does not name it)
 """
@@ -38,11 +39,17 @@ MEMORY_DEFAULTS: Dict[str, Any] = {
     "ring": False,           # True: rolling window, oldest rows overwritten
     "dtype": None,           # None = the encoder's dtype
     "snapshot": None,        # path of an EmbeddingMemory.snapshot to restore from / save to
-    "group_by": None,        # "chunk": a grouped memory (one group per video chunk) for distinct-chunk search; None = plain
+    "group_by": None,        # "chunk": a grouped memory (one group per video chunk) for distinct-chunk search; "event": a
+                             # grouped memory whose groups are events - runs of frames that each resemble the one before
+                             # (EmbeddingMemory.regroup_events; needs event_threshold); None = plain
     "tag_by": None,          # "time": a tagged memory - every frame row carries (video, chunk start in ms), so a search can
                              # name one video or a time window of it (memory.scope_of); None = untagged
     "novelty_threshold": None,  # a float: a frame is stored only when no stored frame and no earlier kept frame of its
                              # chunk scores above it (EmbeddingMemory.append_novel); None = every frame is stored
+    "event_threshold": None,    # group_by "event": a frame continues the event of the frame before it while their
+                             # cosine is strictly above this float
+    "event_max_gap_ms": None,   # group_by "event" on a tagged memory: an int - a step backwards in time or of more than
+                             # this many milliseconds also opens an event; None = time never cuts
 }
 TEXT_ENCODER_DEFAULTS: Dict[str, Any] = {
     "arch": None,            # specs.TEXT_SPECS key (clip_l14_text); None = no text encoder is built

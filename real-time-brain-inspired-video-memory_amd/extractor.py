@@ -19,6 +19,11 @@ Mirrors ``VLMExtractor`` (src/pipeline/vlm_extractor.py):
     (EmbeddingMemory.append_novel); ``embedding_rows`` then lists the row that stands for each frame and every chunk
     gains ``stored_frames``.
 
+  * ``config.memory.group_by: event`` (with ``event_threshold``): the grouped memory's groups are EVENTS - runs of frames
+    that each resemble the one before - instead of chunks: after each look-ahead group's appends one tail regroup from the
+    group's first row is enqueued (EmbeddingMemory.enqueue_regroup_events).  The extractor's own searches are plain
+    ``topk``, so the output JSON is that of ``group_by: null`` except for the config echo.
+
 ONE deliberate deviation, decided here and nowhere else: the reference shrinks frames taller than 720 rows with
 ``cv2.resize`` before JPEG-encoding them (:114-116) - a payload optimisation for the HTTP call.  This path has no
 payload: the preprocess kernel resamples the ORIGINAL frame to the encoder's input size in one bilinear pass
@@ -158,12 +163,31 @@ def build_text_embedder(config: Any, tokenizer=None):
     return HipTextEmbedder(TextEncoder(spec, weights, dtype=tcfg.dtype, device=int(tcfg.device)), tokenizer)
 
 
+def event_rule(mem_cfg) -> Optional[Tuple[float, Optional[int]]]:
+    """``memory.group_by: event`` -> (event_threshold, event_max_gap_ms), ``None`` for any other ``group_by``.  The
+    threshold is required and a float; the gap is an int of milliseconds or null, and needs ``tag_by: time``."""
+    if getattr(mem_cfg, "group_by", None) != "event":
+        return None
+    tau = getattr(mem_cfg, "event_threshold", None)
+    if isinstance(tau, bool) or not isinstance(tau, (int, float)) or tau != tau:
+        raise ValueError(f"memory.group_by 'event' needs memory.event_threshold, a float; got {tau!r}")
+    gap = getattr(mem_cfg, "event_max_gap_ms", None)
+    if gap is not None:
+        if isinstance(gap, bool) or not isinstance(gap, int) or gap < 0:
+            raise ValueError(f"memory.event_max_gap_ms must be null or a non-negative int, got {gap!r}")
+        if getattr(mem_cfg, "tag_by", None) != "time":
+            raise ValueError("memory.event_max_gap_ms needs memory.tag_by: time")
+    return float(tau), gap
+
+
 def build_memory(mem_cfg, encoder: FrameEncoder) -> EmbeddingMemory:
     import os
     dtype = mem_cfg.dtype or encoder.dtype_name
     group_by = getattr(mem_cfg, "group_by", None)
-    if group_by not in (None, "chunk"):
-        raise ValueError(f"memory.group_by must be null or 'chunk', got {group_by!r}")
+    if group_by not in (None, "chunk", "event"):
+        raise ValueError(f"memory.group_by must be null, 'chunk' or 'event', got {group_by!r}")
+    if group_by == "event":
+        event_rule(mem_cfg)
     tag_by = getattr(mem_cfg, "tag_by", None)
     if tag_by not in (None, "time"):
         raise ValueError(f"memory.tag_by must be null or 'time', got {tag_by!r}")
@@ -171,7 +195,8 @@ def build_memory(mem_cfg, encoder: FrameEncoder) -> EmbeddingMemory:
         return EmbeddingMemory.restore(mem_cfg.snapshot, capacity=int(mem_cfg.capacity), ring=bool(mem_cfg.ring),
                                        device=encoder.device.index or 0)
     return EmbeddingMemory(int(mem_cfg.capacity), encoder.out_dim, dtype, ring=bool(mem_cfg.ring),
-                           device=encoder.device.index or 0, grouped=group_by == "chunk", tagged=tag_by == "time")
+                           device=encoder.device.index or 0, grouped=group_by in ("chunk", "event"),
+                           tagged=tag_by == "time")
 
 
 class FrameEmbeddingExtractor:
@@ -292,6 +317,11 @@ class FrameEmbeddingExtractor:
             # is the real-time path.  A gated batched group search is not built.
             tau = getattr(cfgmod.section(self.config, "memory", cfgmod.MEMORY_DEFAULTS), "novelty_threshold", None)
             gated = tau is not None
+            # memory.group_by: event - the groups of the memory are events, not chunks: the rows are appended as they
+            # come and one tail regroup from the look-ahead group's first row follows its appends
+            events = event_rule(cfgmod.section(self.config, "memory", cfgmod.MEMORY_DEFAULTS))
+            if events is not None and not getattr(self.memory, "grouped", False):
+                raise ValueError("memory.group_by 'event' needs a grouped memory")
             # Look-ahead groups (config.encoder.look_ahead_chunks, default 0 = auto, 1 = the reference's one chunk at a time,
             # :44-74): the frames of N consecutive chunks go through ONE encoder call - the encoder fills the chip only
             # from a few hundred frames up - and then every chunk of the group, in chunk order, gets its own top-k
@@ -433,6 +463,8 @@ class FrameEmbeddingExtractor:
                     credits.release()
                     chunks, dev_s, dev_r, off = [], [], [], 0
                     total = sum(counts)
+                    # id of the first row this group stores (gated: if it stores any)
+                    group_first = len(self.memory) if events is not None else 0
                     # One search for the whole group when that is provably the same thing: every chunk of the group still
                     # sees exactly "the memory before the group + the group's earlier chunks", i.e. no row of the memory is
                     # overwritten while the group is appended (not a ring, or a ring that does not wrap inside the group).
@@ -480,13 +512,15 @@ class FrameEmbeddingExtractor:
                         # a grouped memory (memory.group_by: chunk) gets one key per chunk, per row; a single-chunk
                         # append (below) is one new group by default
                         group = ([k for c in live for k in [self.memory.new_group_key()] * c["nframes"]]
-                                 if getattr(self.memory, "grouped", False) else None)
+                                 if getattr(self.memory, "grouped", False) and events is None else None)
                         tag_kw = {"tag": [t for c in live for t in [c["tag"]] * c["nframes"]]} if tagged else {}
                         first = self.memory.append(emb_all, ids=[i for c in live for i in c["ids"]],
                                                    meta=[m for c in live for m in c["meta"]], group=group, **tag_kw)
                         for c in live:
                             c["first"] = first
                             first += c["nframes"]
+                    if events is not None and total:
+                        self.memory.enqueue_regroup_events(events[0], events[1], from_row=group_first)
                     host_s = host_r = ev = None
                     if dev_s:
                         cat_s, cat_r = torch.cat(dev_s), torch.cat(dev_r)

@@ -16,13 +16,17 @@ holds many videos: ``topk_scoped`` ranks only the rows whose tag lies in the que
 counterpart of the reference's ``{graph_uuid: $graph_uuid}`` predicate (include/vidmem.h).
 
 All arithmetic is in libvidmem.so (csrc/memory.hip, csrc/topk.hip, csrc/topk_exact.hip, csrc/topk_group.hip,
-csrc/topk_scope.hip, csrc/novelty.hip, csrc/erase.hip, csrc/range.hip).
+csrc/topk_scope.hip, csrc/novelty.hip, csrc/erase.hip, csrc/range.hip, csrc/events.hip).
 
 ``erase`` forgets rows - a whole video or time window by its tags, or rows by id - and compacts the memory in place, so
 that a non-ring memory that has filled up takes new rows again (include/vidmem.h).
 
 ``range_search`` returns EVERY row above a threshold, in time order, where the top-k searches return the best k;
 ``moments`` turns those hits into ``(video, t0, t1, peak)`` runs (csrc/range.hip, include/vidmem.h).
+
+``events`` cuts the stored rows into events - maximal runs of consecutive rows in which each frame resembles the one
+before it - and ``regroup_events`` makes those events the groups of ``topk_grouped``: one hit per scene instead of one
+per fixed chunk (csrc/events.hip, include/vidmem.h).
 """
 from __future__ import annotations
 
@@ -146,6 +150,70 @@ def segment_moments(rows, scores, tags, max_gap_ms) -> List[Moment]:
     return out
 
 
+class EventsOut(NamedTuple):
+    """What ``enqueue_events`` returns, all on the device: ``count`` int64 [1] (the TOTAL number of events, also above
+    ``max_events``), ``first_rows`` int64 [max_events] (-1 padded), ``event_of`` int64 [capacity] (entries at and beyond
+    the live row count are not written) and ``links`` float64 [capacity] or ``None``."""
+    count: torch.Tensor
+    first_rows: torch.Tensor
+    event_of: torch.Tensor
+    links: Optional[torch.Tensor]
+
+
+class Events(NamedTuple):
+    """What ``events`` returns: ``first_rows`` int64 (the first row id of every event that was written, ascending),
+    ``event_of`` int64 [live rows] (the event index of each live row, oldest first), ``count`` the total number of
+    events (``> len(first_rows)`` = cut by ``max_events``) and ``links`` float64 [live rows] or ``None``."""
+    first_rows: torch.Tensor
+    event_of: torch.Tensor
+    count: int
+    links: Optional[torch.Tensor]
+
+
+class Event(NamedTuple):
+    """A run of consecutive rows that resemble each other (``segment_events``)."""
+    source: Optional[int]
+    t0_ms: Optional[int]
+    t1_ms: Optional[int]
+    first_row: int
+    last_row: int
+    rows: int
+
+
+def segment_events(first_rows, n_rows, base=0, tags=None) -> List[Event]:
+    """The events of a memory as a list, in row order.  ``first_rows`` int64 [E] ascending: the first row id of every
+    event (``events(...).first_rows``, complete); the live rows are the ids ``base .. base + n_rows - 1``; ``tags`` int64
+    [n_rows] or ``None``: the tag of each live row in row order (``tags_host()``; ``make_tag``'s split: source =
+    tag >> 40, milliseconds = the low 40 bits).  Event e runs from its first row to the row before the next event's
+    first.  ``source`` and ``t0_ms`` come from its first row's tag, ``t1_ms`` from its last row's; an untagged memory or
+    rows tagged INT64_MIN give ``None`` for all three (an event never mixes timed and untimed rows, nor two sources)."""
+    import numpy as np
+    first = np.asarray(first_rows, dtype=np.int64).reshape(-1)
+    n_rows, base = int(n_rows), int(base)
+    if n_rows < 0:
+        raise ValueError("n_rows is negative")
+    if first.size == 0:
+        if n_rows:
+            raise ValueError("live rows but no event: first_rows is incomplete")
+        return []
+    if first[0] != base or (np.diff(first) <= 0).any() or first[-1] >= base + n_rows:
+        raise ValueError("first_rows must start at base, ascend strictly and stay below base + n_rows")
+    if tags is not None:
+        tags = np.asarray(tags, dtype=np.int64).reshape(-1)
+        if tags.size != n_rows:
+            raise ValueError(f"{tags.size} tags for {n_rows} rows")
+    last = np.concatenate([first[1:] - 1, [base + n_rows - 1]])
+    out = []
+    for a, b in zip(first.tolist(), last.tolist()):
+        source = t0 = t1 = None
+        if tags is not None:
+            ta, tb = int(tags[a - base]), int(tags[b - base])
+            if ta != INT64_MIN and tb != INT64_MIN:
+                source, t0, t1 = ta >> TAG_MS_BITS, ta & (TAG_MAX_MS - 1), tb & (TAG_MAX_MS - 1)
+        out.append(Event(source, t0, t1, a, b, b - a + 1))
+    return out
+
+
 def _check_erase_selectors(rows, scope) -> None:
     """``erase`` / ``enqueue_erase`` take exactly one selector."""
     if rows is not None and scope is not None:
@@ -185,6 +253,7 @@ class EmbeddingMemory:
         self._escratch = None       # buffers of erase (EraseScratch), made on demand
         self._rscratch = None       # buffers of the range search (RangeScratch), grown on demand
         self._rlast = None          # the scratch of the last range call (last_range_rescored)
+        self._vscratch = None       # buffers of the event segmentation (EventsScratch), grown on demand
         # Host tables: chunk id (reference pre_llm_injector.py:91) and {"time":..., "content":...} (for
         # _vector_search_chunks) of row (table_base + i).  table_base stays 0 unless a ring has wrapped far enough for
         # the slots of overwritten rows to be dropped (see _trim_tables); use id_of / meta_of for row -> entry.
@@ -910,6 +979,102 @@ class EmbeddingMemory:
             at += n
         return out
 
+    # ---- event segmentation (include/vidmem.h vm_memory_events / vm_memory_regroup_events) -----------
+    def prepare_events(self, max_events: int = 0) -> "EventsScratch":
+        """Size this memory's own event buffers for ``max_events`` first rows now (before a graph capture: a capture
+        must not allocate)."""
+        if self._vscratch is None or not self._vscratch.fits(self, max_events):
+            self._vscratch = EventsScratch.for_(self, max_events)
+        return self._vscratch
+
+    def _events_args(self, threshold, max_gap_ms, regroup: bool = False) -> Tuple[float, int]:
+        """The argument rules of both calls, checked on the host before anything reaches the library."""
+        if regroup and not self.grouped:
+            raise ValueError("regroup_events needs a grouped memory (EmbeddingMemory(..., grouped=True))")
+        tau = float(threshold)
+        if math.isnan(tau):
+            raise ValueError("the event threshold is NaN")
+        gap = -1 if max_gap_ms is None else int(max_gap_ms)
+        if gap >= 0 and not self.tagged:
+            raise ValueError("max_gap_ms needs a tagged memory (EmbeddingMemory(..., tagged=True))")
+        return tau, (gap if gap >= 0 else -1)
+
+    def enqueue_events(self, threshold, max_gap_ms: Optional[int] = None, max_events: int = 1024,
+                       with_links: bool = False, scratch: Optional["EventsScratch"] = None) -> EventsOut:
+        """The capturable event segmentation -> ``EventsOut(count, first_rows, event_of, links)``: views of the buffers
+        of ``scratch`` (default: this memory's own, ``prepare_events``), valid until the next events call on it.
+
+        A row opens an event when it is the oldest live row, when its link - the reference cosine against the row
+        before it - is not strictly above ``threshold``, or, on a tagged memory, when the source changes, exactly one
+        of the two rows is untimed, or (``max_gap_ms`` given) the milliseconds step backwards or by more than
+        ``max_gap_ms``.  Enqueues ``vm_memory_events`` on the current stream: nothing is read on the host."""
+        tau, gap = self._events_args(threshold, max_gap_ms)
+        max_events = int(max_events)
+        if max_events < 0:
+            raise ValueError("max_events is negative")
+        if scratch is None:
+            scratch = self.prepare_events(max_events)
+        elif not scratch.fits(self, max_events):
+            raise ValueError("caller-owned events scratch is too small for this max_events")
+        ptr = lambda x: C.c_void_p(x.data_ptr() if x is not None else 0)
+        first = scratch.first_rows[:max_events] if max_events else None
+        links = scratch.links if with_links else None
+        self.ctx.check(self.L.vm_memory_events(self.handle, tau, gap, ptr(links), ptr(scratch.event_of), max_events,
+                                               ptr(first), ptr(scratch.count), ptr(scratch.ws), scratch.ws.numel(),
+                                               _lib.current_stream_ptr()))
+        return EventsOut(scratch.count, scratch.first_rows[:max_events], scratch.event_of, links)
+
+    def events(self, threshold, max_gap_ms: Optional[int] = None, max_events: Optional[int] = None,
+               with_links: bool = False) -> Events:
+        """Cut the stored rows into events -> ``Events(first_rows, event_of, count, links)`` on the device, trimmed to
+        what was written (``enqueue_events`` for the rule; ``segment_events`` turns the result into a list).
+
+        ``max_events=None``: every event - the call is sized for the live row count, the most events there can be.
+        With a ``max_events`` only the first ``max_events`` first rows are returned and ``count`` still holds the total.
+        This form SYNCHRONISES once (it reads the count); the host row count must be current (``sync()``).  Two videos
+        appended in alternation cut each other's events at every switch, and links chain: a slow pan is one event
+        however far it drifts."""
+        self._events_args(threshold, max_gap_ms)
+        if max_events is not None and int(max_events) < 0:
+            raise ValueError("max_events is negative")
+        n = self.searchable
+        width = n if max_events is None else int(max_events)
+        out = self.enqueue_events(threshold, max_gap_ms, width, with_links)
+        count = int(out.count.item()) if n else 0           # the one wait; an empty memory writes the count only
+        return Events(out.first_rows[:min(count, width)].clone(), out.event_of[:n].clone(), count,
+                      out.links[:n].clone() if with_links else None)
+
+    def enqueue_regroup_events(self, threshold, max_gap_ms: Optional[int] = None, from_row=None,
+                               scratch: Optional["EventsScratch"] = None) -> torch.Tensor:
+        """The capturable regroup -> the device int64 [1] count of events opened among the rows it covered (a buffer of
+        ``scratch``, default this memory's own).  Rewrites the group key and ordinal columns of a grouped memory so that
+        every event is one group: key = the row id of the event's first row.  ``from_row=None``: the whole memory;
+        an int or a device int64 [1] tensor (not read on the host): the rows from that id on - the row is judged against
+        its predecessor and continues that row's group when it does not open an event.  Plain appends, each followed
+        by a tail regroup from its first new row, leave what one whole regroup leaves, on a linear memory or a ring
+        that has not wrapped and with no erase in between.  Afterwards the last event is closed: a later keyed append
+        opens a new group whatever its key.  Enqueues ``vm_memory_regroup_events``: nothing is read on the host."""
+        tau, gap = self._events_args(threshold, max_gap_ms, regroup=True)
+        if scratch is None:
+            scratch = self.prepare_events(0)
+        frm = None
+        if from_row is not None:
+            if isinstance(from_row, torch.Tensor):
+                frm = from_row.to(device=self.device, dtype=torch.int64).reshape(-1)[:1].contiguous()
+            else:
+                frm = torch.tensor([int(from_row)], dtype=torch.int64).to(self.device)
+        self.ctx.check(self.L.vm_memory_regroup_events(self.handle, tau, gap, C.c_void_p(frm.data_ptr() if frm is not None else 0),
+                                                       C.c_void_p(scratch.count.data_ptr()), C.c_void_p(scratch.ws.data_ptr()),
+                                                       scratch.ws.numel(), _lib.current_stream_ptr()))
+        if frm is not None:
+            frm.record_stream(torch.cuda.current_stream())
+        self._last_keys_dev = None        # the keys are row ids now; the last event is closed on the device
+        return scratch.count
+
+    def regroup_events(self, threshold, max_gap_ms: Optional[int] = None, from_row=None) -> int:
+        """``enqueue_regroup_events`` and one synchronising read -> the number of events among the covered rows."""
+        return int(self.enqueue_regroup_events(threshold, max_gap_ms, from_row).item())
+
     @property
     def last_scope_flags(self) -> Optional[torch.Tensor]:
         return self._sflags
@@ -1070,6 +1235,28 @@ class NoveltyScratch:
     def for_(cls, memory: "EmbeddingMemory", B: int) -> "NoveltyScratch":
         B = max(1, min(int(B), NOVEL_MAX_ROWS))
         return cls(memory.device, B, int(memory.L.vm_novelty_workspace_bytes(memory.handle, B)))
+
+
+class EventsScratch:
+    """Device buffers of the event segmentation: the workspace (flags and chunk prefixes), ``count`` (int64 [1]),
+    ``first_rows`` (int64 [max_events]), ``event_of`` (int64 [capacity]) and ``links`` (float64 [capacity]).  Like
+    ``TopkScratch``, an owner keeps ONE instance per stream / captured graph: a hipGraph bakes the addresses in."""
+
+    def __init__(self, device, capacity: int, max_events: int, ws_bytes: int):
+        self.ws = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=device)
+        self.count = torch.zeros(1, dtype=torch.int64, device=device)
+        self.first_rows = torch.full((max(int(max_events), 1),), -1, dtype=torch.int64, device=device)
+        self.event_of = torch.zeros(max(capacity, 1), dtype=torch.int64, device=device)
+        self.links = torch.zeros(max(capacity, 1), dtype=torch.float64, device=device)
+
+    def fits(self, memory: "EmbeddingMemory", max_events: int) -> bool:
+        return (self.first_rows.numel() >= max_events and self.event_of.numel() >= memory.capacity and
+                self.ws.numel() >= int(memory.L.vm_memory_events_workspace_bytes(memory.handle)))
+
+    @classmethod
+    def for_(cls, memory: "EmbeddingMemory", max_events: int = 0) -> "EventsScratch":
+        return cls(memory.device, memory.capacity, int(max_events),
+                   int(memory.L.vm_memory_events_workspace_bytes(memory.handle)))
 
 
 class RangeScratch:
