@@ -172,7 +172,11 @@ int vm_text_encode(vm_text_encoder *enc, const int32_t *token_ids, int B, int T,
  * (MERGE ... SET c.embedding), bulk read-back = src/components/pre_llm_injector.py:390-412.
  * Rows are kept resident in HBM as [capacity, D] dtype, plus per row an exact fp64 norm and an fp32 reciprocal
  * norm.  Row id = append order (0,1,2,...).  ring=1: after `capacity` rows the oldest are overwritten; ids keep
- * counting, only the newest `capacity` ids are searchable. */
+ * counting, only the newest `capacity` ids are searchable.
+ * Any finite rows are accepted.  The searches' fp32 fast path applies while every stored row's norm is 0 or lies in
+ * [2^-40, 2^40] (a bf16 row can leave that interval, an fp16 row cannot); once a row outside it was appended, every
+ * search of this memory is answered exactly at exhaustive cost until vm_memory_reset - erasing or overwriting the row
+ * does not bring the fast path back.  Stored NaN / inf values are undefined, as in the reference. */
 int vm_memory_create(vm_ctx *ctx, int64_t capacity_rows, int D, int dtype, int ring, vm_memory **out);
 void vm_memory_destroy(vm_memory *mem);
 /* rows: [B, D] dtype.  *out_first_row_host (optional) receives the id of the first appended row. */
@@ -382,7 +386,10 @@ const int64_t *vm_memory_group_ordinals(const vm_memory *mem);
  * bound 2 (D + 8) 2^-24 - near-ties between rank k and rank k + slack, e.g. more than `slack` exact duplicates;
  * VM_FLAG_OVERFLOW = more candidates at or above a query's cut than its buffer holds).  Pass the flags
  * to vm_topk_redo_flagged on the same stream: the reference always returns the exhaustive answer
- * (src/components/pre_llm_injector.py:356-370), so the pair {vm_topk_cosine, vm_topk_redo_flagged} is the drop-in. */
+ * (src/components/pre_llm_injector.py:356-370), so the pair {vm_topk_cosine, vm_topk_redo_flagged} is the drop-in.
+ * Domain: the bound holds while the query's norm and every stored row's norm are 0 or lie in [2^-40, 2^40] (D <= 2048;
+ * vm_memory_create).  Outside it every query concerned is flagged VM_FLAG_GAP and vm_topk_redo_flagged answers it: exact,
+ * at exhaustive cost.  Stored NaN / inf values are undefined, as in the reference. */
 size_t vm_topk_workspace_bytes(const vm_memory *mem, int Q, int k);
 int vm_topk_cosine(vm_memory *mem, const void *queries, int Q, int k, int use_min_score, double min_score,
                    int score_mode, int64_t row_stride, int64_t row_offset, double *out_scores,
@@ -415,7 +422,9 @@ int vm_topk_cosine_exact(vm_memory *mem, const void *queries, int Q, int k, int 
  * best rejected group's fp32 max, or more than 4096 candidate rows) is counted in *out_uncertified (may be NULL),
  * marked in out_query_flags [Q] (vm_topk_flag; may be NULL) and redone exhaustively on the device inside the same call.
  * Every row of a candidate group is re-scored, so groups of a few hundred rows or more (k = 10: an average above ~220)
- * always take that exhaustive redo: exact, but at the cost of an exhaustive search.
+ * always take that exhaustive redo: exact, but at the cost of an exhaustive search.  So does every query whose norm, or
+ * a stored row's norm, is neither 0 nor in [2^-40, 2^40], the interval inside which the bound holds (vm_memory_create);
+ * stored NaN / inf values are undefined, as in the reference.
  * No host read-back, no allocation: capturable.  1 <= k <= 64, Q >= 1; VM_ERR_INVALID on a memory that is not grouped.
  * Workspace: vm_topk_grouped_workspace_bytes (4 x Q x capacity bytes of per-group maxima plus a few MB). */
 size_t vm_topk_grouped_workspace_bytes(const vm_memory *mem, int Q, int k);
@@ -439,7 +448,9 @@ int vm_topk_cosine_grouped_exact(vm_memory *mem, const void *queries, int Q, int
  * result cannot be proven (vm_topk_cosine's bound 2 (D + 8) 2^-24 against the best in-scope fp32 score that was not
  * re-scored - out-of-scope rows never enter it -, or more than 8192 in-scope rows at the query's cut) is counted in
  * *out_uncertified (may be NULL), marked in out_query_flags [Q] (vm_topk_flag; may be NULL) and redone exhaustively over
- * its in-scope rows on the device inside the same call.
+ * its in-scope rows on the device inside the same call.  So is every query whose norm, or a stored row's norm, is
+ * neither 0 nor in [2^-40, 2^40], the interval inside which the bound holds (vm_memory_create): exact, at exhaustive
+ * cost; stored NaN / inf values are undefined, as in the reference.
  * No host read-back, no allocation: capturable.  1 <= k <= 64, Q >= 1; VM_ERR_INVALID on a memory that is not tagged.
  * Workspace: vm_topk_scoped_workspace_bytes (4 x Q x capacity bytes of fp32 keys plus 64 KiB x Q and a few MB). */
 size_t vm_topk_scoped_workspace_bytes(const vm_memory *mem, int Q, int k);
@@ -477,6 +488,9 @@ int vm_topk_cosine_scoped_exact(vm_memory *mem, const void *queries, int Q, int 
  *   re-scored exactly and is a hit iff its exact shown score passes.  out_rescored[q] (device int64 [Q], may be NULL):
  *   the pairs of query q that were scored exactly in this call (>= out_counts[q]; equal when no score lies within the
  *   bound of the threshold).  Order comes from prefix sums over separate launches: deterministic, no atomics.
+ *   The bound holds while the query's norm and every stored row's norm are 0 or lie in [2^-40, 2^40] (vm_memory_create);
+ *   outside that interval every in-scope pair of the query is re-scored exactly (out_rescored[q] = its in-scope rows):
+ *   exact, at exhaustive cost.  Stored NaN / inf values are undefined, as in the reference.
  * No allocation, no synchronisation, no host read-back; the row count is read on the device and launches are sized from
  * the capacity: capturable, and a replay after an append sees the new rows.  Calls are stream-ordered per handle.
  * Workspace: vm_range_workspace_bytes(mem, Q) = with P = capacity rounded up to 64 rows and C = ceil(P / 4096) chunks,

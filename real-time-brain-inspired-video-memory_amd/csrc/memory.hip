@@ -9,14 +9,14 @@
 // One block per appended row: coalesced 16-B copy of the row into its slot, then lane 0 accumulates the
 // reference's norm exactly: sqrt(sum(b*b)) with one rounding per product and per partial sum, left to right
 // (src/components/pre_llm_injector.py:383).  The slot comes from the DEVICE-side counter so a captured graph
-// replays correctly.
+// replays correctly.  dom: the memory's domain word, &d_total[VM_GSTATE_OUTSIDE] (written, so not through d_total).
 template <int DT>
 __global__ void __launch_bounds__(128) memory_append_kernel(const uint16_t *__restrict__ src, int B, int D,
                                                             uint16_t *__restrict__ rows,
                                                             double *__restrict__ norm64,
                                                             float *__restrict__ rnorm32,
                                                             const int64_t *__restrict__ d_total, int64_t cap,
-                                                            int ring) {
+                                                            int ring, int64_t *dom) {
     const int b = blockIdx.x;
     const int64_t total = *d_total;
     int64_t id = total + b;
@@ -29,6 +29,8 @@ __global__ void __launch_bounds__(128) memory_append_kernel(const uint16_t *__re
         const double nrm = __dsqrt_rn(ref_sumsq<DT>(src + (size_t)b * D, D));
         norm64[slot] = nrm;
         rnorm32[slot] = nrm > 0.0 ? (float)(1.0 / nrm) : 0.0f;
+        // the certificate's sticky domain word (vm_internal.h VM_GSTATE_OUTSIDE; fp16 norms cannot leave the domain)
+        if (DT == VM_BF16 && cert_norm_outside(nrm)) *dom = 1;
     }
 }
 
@@ -196,10 +198,12 @@ static int memory_append(vm_memory *m, const void *rows, int B, const int64_t *k
     vm_prof_scope prof(ctx, VM_PROF_APPEND, st);
     if (m->dtype == VM_F16)
         memory_append_kernel<VM_F16><<<B, 128, 0, st>>>((const uint16_t *)rows, B, m->D, m->rows, m->norm64,
-                                                       m->rnorm32, m->d_total, m->cap, m->ring);
+                                                       m->rnorm32, m->d_total, m->cap, m->ring,
+                                                        m->d_total + VM_GSTATE_OUTSIDE);
     else
         memory_append_kernel<VM_BF16><<<B, 128, 0, st>>>((const uint16_t *)rows, B, m->D, m->rows, m->norm64,
-                                                        m->rnorm32, m->d_total, m->cap, m->ring);
+                                                        m->rnorm32, m->d_total, m->cap, m->ring,
+                                                        m->d_total + VM_GSTATE_OUTSIDE);
     VM_LAUNCH_CHECK(ctx);
     if (m->gkey) {  // grouped memories only: a plain memory runs exactly the two launches above and below
         memory_group_kernel<<<1, 256, 0, st>>>(keys, B, m->gkey, m->gord, m->d_total, m->cap, m->ring);

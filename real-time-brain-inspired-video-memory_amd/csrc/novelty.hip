@@ -203,7 +203,7 @@ __global__ void __launch_bounds__(128) novel_append_kernel(const uint16_t *__res
                                                            double *__restrict__ norm64, float *__restrict__ rnorm32,
                                                            int64_t *__restrict__ tagcol, int64_t cap, int ring,
                                                            int32_t *__restrict__ out_keep,
-                                                           int64_t *__restrict__ out_row_of) {
+                                                           int64_t *__restrict__ out_row_of, int64_t *dom) {
     __shared__ int best[2];
     const int l = blockIdx.x;
     const int w = l >> 6;
@@ -224,6 +224,7 @@ __global__ void __launch_bounds__(128) novel_append_kernel(const uint16_t *__res
             const double nrm = norm[l];
             norm64[slot] = nrm;
             rnorm32[slot] = nrm > 0.0 ? (float)(1.0 / nrm) : 0.0f;
+            if (DT == VM_BF16 && cert_norm_outside(nrm)) *dom = 1;   // as memory_append_kernel: the sticky domain word
             if (tagcol) tagcol[slot] = tags ? tags[l] : LLONG_MIN;
         }
         return;
@@ -378,11 +379,11 @@ extern "C" int vm_memory_append_novel(vm_memory *m, const void *rows, int B, dou
     if (m->dtype == VM_F16)
         novel_append_kernel<VM_F16><<<B, 128, 0, st>>>(src, B, D, W, ws.A, ws.hdr, ws.norm, known_rows, known_stride,
                                                       tags, m->rows, m->norm64, m->rnorm32, m->tag, m->cap, m->ring,
-                                                      out_keep, out_row_of);
+                                                      out_keep, out_row_of, m->d_total + VM_GSTATE_OUTSIDE);
     else
         novel_append_kernel<VM_BF16><<<B, 128, 0, st>>>(src, B, D, W, ws.A, ws.hdr, ws.norm, known_rows, known_stride,
                                                        tags, m->rows, m->norm64, m->rnorm32, m->tag, m->cap, m->ring,
-                                                       out_keep, out_row_of);
+                                                       out_keep, out_row_of, m->d_total + VM_GSTATE_OUTSIDE);
     VM_LAUNCH_CHECK(ctx);
     if (m->gkey) {
         novel_group_kernel<<<1, 256, 0, st>>>(keys, B, ws.hdr, m->gkey, m->gord, m->d_total, m->cap, m->ring);

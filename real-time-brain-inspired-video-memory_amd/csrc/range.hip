@@ -44,17 +44,24 @@ __device__ __forceinline__ bool is_hit(double shown, double min_score) { return 
 // shown_score is monotone, so is_hit of that bound being false settles it.  The candidate value (threshold - eps) x ||q||
 // is rounded DOWN to fp32 and then verified with the very predicate, stepping further down while it fails: a row just
 // below the cut is still a candidate, never the reverse.  A zero query scores 0.0 everywhere: all or nothing.
+// The bound holds inside the certificate's domain only (topk_common.h cert_eps).  A bf16 query whose norm lies outside
+// it, or a bf16 memory whose domain word is set (dom = &d_total[VM_GSTATE_OUTSIDE]: some stored row's norm does), gets
+// the cut NaN: every in-scope pair is a candidate and is settled exactly.  fp16 norms cannot leave the domain.
 template <int DT>
 __global__ void __launch_bounds__(64)
     range_cut_kernel(const uint16_t *__restrict__ queries, int Q, int D, double min_score, int score_mode,
-                     float *__restrict__ cut, double *__restrict__ qn_out) {
+                     float *__restrict__ cut, double *__restrict__ qn_out, const int64_t *dom) {
     const int q = blockIdx.x * 64 + threadIdx.x;
     if (q >= Q) return;
     const double qn = __dsqrt_rn(ref_sumsq<DT>(queries + (size_t)q * D, D));
     qn_out[q] = qn;
+    bool off_domain = false;
+    if constexpr (DT == VM_BF16) off_domain = *dom != 0 || cert_norm_outside(qn);
     float c;
     if (qn == 0.0) {
         c = is_hit(shown_score(0.0, score_mode), min_score) ? -INFINITY : INFINITY;
+    } else if (off_domain) {
+        c = NAN;  // no fp32 score is `at or below` a NaN cut - not even -inf, which an overflowed sum is: all candidates
     } else {
         const double eps = cert_eps(D);
         auto rejects = [&](float s) { return !is_hit(shown_score((double)s / qn + eps, score_mode), min_score); };
@@ -465,7 +472,7 @@ int range_run(vm_memory *m, bool fast, const void *queries, int Q, double min_sc
     {
         vm_prof_scope prof(ctx, fast ? VM_PROF_TOPK_SCAN : VM_PROF_TOPK_EXACT, st);
         range_cut_kernel<DT><<<(Q + 63) / 64, 64, 0, st>>>((const uint16_t *)queries, Q, m->D, min_score, score_mode,
-                                                          cut, qn);
+                                                          cut, qn, m->d_total + VM_GSTATE_OUTSIDE);
         VM_LAUNCH_CHECK(ctx);
         if (fast) {
             const bool scoped = scope_lo != nullptr;

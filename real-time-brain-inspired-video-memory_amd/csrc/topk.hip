@@ -626,6 +626,7 @@ __global__ void __launch_bounds__(FIN_THREADS)
             if (mark && mark[q]) {  // emit scan: candidate buffer overflowed / unranked ties -> exhaustive redo
                 if (uncertified) atomicAdd(uncertified, 1);
                 if (qflags) qflags[q] = VM_FLAG_OVERFLOW;
+                if constexpr (DT == VM_BF16) nqual = -1;  // flagged: the domain guard below leaves the query alone
             } else if (!all_rows_are_candidates && qn != 0.0) {
                 const float bound_f32 = fs[KL - 1];  // best possible fp32 score of a rejected row (x 1/||q||)
                 const double eps = cert_eps(D);
@@ -633,8 +634,22 @@ __global__ void __launch_bounds__(FIN_THREADS)
                 if (!(e > reject)) {
                     if (uncertified) atomicAdd(uncertified, 1);
                     if (qflags) qflags[q] = VM_FLAG_GAP;
+                    if constexpr (DT == VM_BF16) nqual = -1;
                 }
             }
+        }
+    }
+    // Domain of the certificate (topk_common.h cert_eps; bf16 only: fp16 norms cannot leave it, and the fp16 kernels
+    // above stay as they were measured).  A query whose norm, or a memory one of whose rows' norms (the sticky word
+    // beside the row count), lies outside is never certified: its fp32 scores may have over- or underflowed and a NaN
+    // score never became a candidate, so there may not even be a k-th candidate to speak for it.  Thread 0 flags what
+    // the certificate above let through (nqual, no longer needed as the list count, is -1 once the query is flagged).
+    if constexpr (DT == VM_BF16) {
+        __syncthreads();
+        if (tid == 0 && nqual != -1 && (uncertified || qflags) && rv.n > (int64_t)nfin &&
+            (d_total[VM_GSTATE_OUTSIDE] != 0 || cert_norm_outside(qn))) {
+            if (uncertified) atomicAdd(uncertified, 1);
+            if (qflags) qflags[q] = VM_FLAG_GAP;
         }
     }
 }

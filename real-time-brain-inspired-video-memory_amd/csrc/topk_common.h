@@ -66,7 +66,20 @@ __device__ __forceinline__ bool passes_min(int use_min, double shown, double min
 
 // Certification bound, DESIGN.md 4.1: an fp32-scanned score x 1/||q|| lies within 2 (D + 8) 2^-24 of the exact cosine,
 // so an exact k-th score above (best rejected fp32 score / ||q||) + cert_eps(D) is provably the k-th.
+// PRECONDITION ("Domain of the certificate"): the bound is a statement about fp32 arithmetic that neither
+// overflows nor underflows.  It holds when the query's norm and the norm of EVERY stored row are 0 or lie in
+// [2^-40, 2^40] (cert_norm_outside below) and D <= 2,048; a kernel that uses cert_eps must check that first and, outside,
+// treat the query as uncertified (the row, grouped and scoped searches: VM_FLAG_GAP -> the exhaustive redo; the range
+// search: every pair is a candidate).  Stored NaN / inf values are undefined, as in the reference.
 __device__ __forceinline__ double cert_eps(int D) { return 2.0 * (double)(D + 8) * 5.9604644775390625e-08; }
+
+// The norm interval of the certificate's domain.  fp16 norms cannot leave it (they lie in [2^-24, 2^22]); a bf16 norm
+// can.  A zero vector is inside: its fp32 score is an exact 0.  A NaN norm is outside.
+constexpr double VM_CERT_NORM_MIN = 9.094947017729282379150390625e-13;  // 2^-40
+constexpr double VM_CERT_NORM_MAX = 1099511627776.0;                    // 2^40
+__device__ __forceinline__ bool cert_norm_outside(double nrm) {
+    return nrm != 0.0 && !(nrm >= VM_CERT_NORM_MIN && nrm <= VM_CERT_NORM_MAX);
+}
 
 // the tie rule of the fp32 candidate lists: (score desc, age order asc)
 __device__ __forceinline__ bool better(float s1, int o1, float s2, int o2) {

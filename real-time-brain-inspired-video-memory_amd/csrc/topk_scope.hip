@@ -332,9 +332,15 @@ __global__ void __launch_bounds__(SF_THREADS)
     }
     __syncthreads();
     if (tid == 0) {
-        flags[q] = flag_sh;
-        if (user_flags) user_flags[q] = flag_sh;
-        if (flag_sh && uncertified) atomicAdd(uncertified, 1);
+        int f = flag_sh;
+        // domain of the certificate (topk_common.h cert_eps; bf16 only): outside it the in-call redo answers the query
+        if constexpr (DT == VM_BF16) {
+            if (f == VM_FLAG_CERTIFIED && rv.n > 0 && (d_total[VM_GSTATE_OUTSIDE] != 0 || cert_norm_outside(qn)))
+                f = VM_FLAG_GAP;
+        }
+        flags[q] = f;
+        if (user_flags) user_flags[q] = f;
+        if (f && uncertified) atomicAdd(uncertified, 1);
     }
 }
 

@@ -22,8 +22,12 @@ struct vm_memory {
 };
 
 // The 64-byte device block d_total points to: [0] row count, then the grouped append's state (zeroed with the row count
-// by vm_memory_reset, so a reset also forgets the open group).
-enum { VM_GSTATE_GROUPS = 1, VM_GSTATE_LAST_KEY = 2, VM_GSTATE_OPEN = 3 };
+// by vm_memory_reset, so a reset also forgets the open group), then [4] the certificate's domain word (bf16 memories):
+// nonzero once a row was appended whose norm lies outside the certificate's domain (topk_common.h cert_norm_outside).
+// The word is STICKY: the appends set it (memory.hip, novelty.hip), only vm_memory_reset clears it; an erase or a ring
+// overwrite that removes the offending row leaves it set (the searches stay exact, at exhaustive cost, until a reset),
+// and a restore rebuilds it because it appends.  The bf16 searches read it where they would use cert_eps.
+enum { VM_GSTATE_GROUPS = 1, VM_GSTATE_LAST_KEY = 2, VM_GSTATE_OPEN = 3, VM_GSTATE_OUTSIDE = 4 };
 
 // Logical view of the (ring) row store for a device-side row count: searchable rows n, physical slot of the oldest
 // row (head), row id of the oldest row (base).  Row of age order o (0 = oldest) sits in slot (o + head) % cap.

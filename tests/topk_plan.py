@@ -10,14 +10,14 @@ from __future__ import annotations
 from dataclasses import dataclass, field
 from typing import List, Optional, Tuple
 
-SAMPLE_ROWS = 16384       # topk.hip:675
+SAMPLE_ROWS = 16384       # topk.hip:690
 EMIT_CAP = 4096           # vm_internal.h:76 VM_EMIT_CAP (the dense pass's row budget, the first limit's unit)
 EM_QPB = 128              # topk_emit.hip:33 queries per superblock (16 per wave, 8 waves)
 MAX_K_FAST = 58           # topk.hip vm_topk_cosine: k > 58 -> vm_topk_cosine_exact
 
 
 def pick_kl(k: int) -> int:
-    """topk.hip:682: the per-lane list length, k + 2 / k + 4 / k + 6 of slack."""
+    """topk.hip:697: the per-lane list length, k + 2 / k + 4 / k + 6 of slack."""
     if k + 2 <= 8:
         return 8
     if k + 4 <= 16:
@@ -28,7 +28,7 @@ def pick_kl(k: int) -> int:
 
 
 def pick_qt(Q: int, KL: int, D: int) -> int:
-    """topk.hip:683-687: query tiles of 16 per scan block, QT * KL <= 64, the query tile within 144 KiB of LDS."""
+    """topk.hip:698-702: query tiles of 16 per scan block, QT * KL <= 64, the query tile within 144 KiB of LDS."""
     qt_max = min(64 // KL, 4)
     need = (Q + 15) // 16
     qt = 4 if need >= 4 and qt_max >= 4 else (2 if need >= 2 and qt_max >= 2 else 1)
@@ -54,12 +54,12 @@ def gscan_supported(Q: int, rows: int, D: int, num_cus: int) -> bool:
 
 
 def cut_growth(Q: int) -> int:
-    """topk.hip:795-797: the cascade's pass limits grow 32-fold for <= 128 queries (one superblock), 8-fold above."""
+    """topk.hip:810-812: the cascade's pass limits grow 32-fold for <= 128 queries (one superblock), 8-fold above."""
     return 32 if Q <= 128 else 8
 
 
 def pass_limits(Q: int, cap: int) -> List[Tuple[int, Optional[int]]]:
-    """topk.hip:804-815: the cascade's scan passes after the dense one, as [begin, limit) in physical slots; limit None
+    """topk.hip:819-830: the cascade's scan passes after the dense one, as [begin, limit) in physical slots; limit None
     = the last pass (INT64_MAX: up to the end of the stored rows).  The limits go 4096 g, 4096 g^2, ... and the pass
     that starts once a limit reaches the capacity is the last."""
     g = cut_growth(Q)
@@ -126,26 +126,26 @@ def plan(Q: int, k: int, D: int, dtype: str, cap: int, num_cus: int = 256) -> Pl
     KL = pick_kl(k)
     QT = pick_qt(Q, KL, D)
     p = Plan("list", dtype, D, KL=KL, QT=QT)
-    # topk.hip:720 make_plan: the emit cascade needs the emit set of D and a memory of >= 4 samples
+    # topk.hip:735 make_plan: the emit cascade needs the emit set of D and a memory of >= 4 samples
     if emit_supported(Q, KL, D, cap) and cap >= 4 * SAMPLE_ROWS:
         p.family = "cascade"
         p.KS = D // 128
         p.NG = 2 if p.KS <= 6 and Q > EM_QPB else 1     # topk_emit.hip:546-547 launch_emit_ng
-        p.passes.append(Pass(0, None, "dense"))           # topk.hip:806: pass 0 has no cut (never gscan)
+        p.passes.append(Pass(0, None, "dense"))           # topk.hip:821: pass 0 has no cut (never gscan)
         for begin, limit in pass_limits(Q, cap):
             rows = (cap if limit is None else min(cap, limit)) - begin
             gs = begin % 256 == 0 and gscan_supported(Q, rows, D, num_cus)   # topk_emit.hip:585-587
             p.passes.append(Pass(begin, limit, "gscan" if gs else "emit"))
         n = len(p.passes)
         # every pass: one scan launch (emit or gscan: VM_PROF_TOPK_SCAN) and one compact (VM_PROF_TOPK_FINALIZE,
-        # topk_emit.hip:606), then the final finalize (topk.hip:841)
+        # topk_emit.hip:606), then the final finalize (topk.hip:856)
         p.launches = {"topk_scan": n, "topk_finalize": n + 1}
-    elif QT >= 2 and cap >= 4 * SAMPLE_ROWS:              # topk.hip:819: the sampled pre-pass and its finalize
+    elif QT >= 2 and cap >= 4 * SAMPLE_ROWS:              # topk.hip:834: the sampled pre-pass and its finalize
         p.family = "list+prepass"
         p.launches = {"topk_scan": 2, "topk_finalize": 2}
     else:
         p.launches = {"topk_scan": 1, "topk_finalize": 1}
-    if dtype == "bf16":   # topk.hip:843-848: stage the KL candidate rows when they fit in 96 KiB beside the query
+    if dtype == "bf16":   # topk.hip:858-863: stage the KL candidate rows when they fit in 96 KiB beside the query
         p.staged = D * 2 + KL * (D + 8) * 2 <= 96 * 1024
     return p
 
