@@ -367,6 +367,49 @@ int vm_memory_regroup_events(vm_memory *mem, double threshold, int64_t max_gap_m
                              int64_t *out_n_events, void *workspace, size_t workspace_bytes, void *stream);
 const int64_t *vm_memory_group_ordinals(const vm_memory *mem);
 
+/* ---- group summaries: one centroid row and one key frame per group ------------------------------------------
+ * Turn every group of a grouped memory - a fixed chunk (vm_memory_append_grouped) or an event
+ * (vm_memory_regroup_events) - into ONE vector and ONE frame to show for it.  The reference stores one embedding per
+ * chunk (src/components/neo4j_handler.py:229-242) and searches those (src/pipeline/retriever_hybrid.py:293-306); a
+ * group's normalised mean embedding is that vector, and a second memory holding these rows has the reference's shape.
+ * Grouped memories only (VM_ERR_INVALID otherwise); read-only.  Live rows are the ids lo .. n-1 as in vm_memory_events.
+ * Live groups are numbered in row order: G(r) = ordinal[r] - ordinal[lo]; n_groups = G(n-1) + 1.  In a wrapped ring the
+ * oldest group consists of its surviving rows.
+ * first_group: device int64 [1], the first group g0 of the WINDOW; NULL = 0, a negative value = 0.  The call writes the
+ * groups g0 .. min(g0 + max_groups, n_groups) - 1 to the output slots 0 .. and pads the rest of max_groups.
+ * out_n_groups [1] (required): always the TOTAL number of live groups.  max_groups == 0 writes only the count (the
+ * other outputs may be NULL); g0 >= n_groups writes the count and the padding; an empty memory writes
+ * *out_n_groups = 0 and nothing else.
+ * Per group with live rows a .. b (row ids), each output device memory, each may be NULL independently:
+ *   out_first_rows int64 [max_groups]: a.  out_n_rows int64: b - a + 1.  out_keys int64: the group key of row a.
+ *     Padding: -1.
+ *   out_centroids [max_groups, D] of the memory's dtype, zero-padded - what vm_memory_append* accepts as it stands.
+ *     S_j = the fp64 sum of the stored 16-bit values x[r][j], r = a .. b strictly in row order, from 0.0, one rounding
+ *     per addition.  N = sqrt(sum_j S_j * S_j): one rounding per product and per partial sum, left to right in j, then a
+ *     correctly rounded square root.  N == 0 (also a group that cancels exactly): the all-zero row.  Otherwise
+ *     c_j = round16(S_j / N): one correctly rounded division, then ONE round-to-nearest-even from fp64 to the dtype
+ *     (never through fp32, which would round twice); subnormals and the sign of zero are kept.
+ *   out_key_rows int64 [max_groups], out_key_scores double [max_groups]: the KEY FRAME, the row of the group with the
+ *     highest score(r) = the reference cosine of vm_topk_cosine with the stored centroid row c as the query and row r
+ *     as the stored row (fp64 on the 16-bit values, left to right; the centroid's norm = sqrt of its sum of squares;
+ *     the row's norm = its STORED fp64 norm; a zero norm gives 0.0), always RAW; ties: the lowest row id.  The score
+ *     is that cosine bit for bit.  Padding: -1 and 0.0.  out_key_scores without out_key_rows is allowed; with both
+ *     NULL the second pass over the rows is not launched.
+ * No allocation, no synchronisation, no host read-back; the row count and *first_group are read on the device and
+ * launches are sized from the capacity and max_groups: capturable, and a replay after an append sees the new rows.
+ * Deterministic, no atomics: a group is summed by one workgroup in row order, so the result does not depend on launch
+ * geometry, workspace size, max_groups or the window a group is asked through.  Stored NaN / inf values are undefined,
+ * as elsewhere; no norm domain applies (no fp32 stage, no certificate, no redo).  D above 8,192: VM_ERR_UNSUPPORTED.
+ * A workspace below vm_memory_summaries_workspace_bytes is refused with VM_ERR_NOMEM before any launch.
+ * Workspace, with m = min(max_groups, capacity): 256 bytes + 8 (m + 1) bytes of group bounds + 8 bytes per slot of the
+ * capacity rounded up to 256 slots (scores) + 2 D m bytes (the centroids when out_centroids is NULL), each array
+ * rounded up to 256 bytes. */
+size_t vm_memory_summaries_workspace_bytes(const vm_memory *mem, int64_t max_groups);
+int vm_memory_summaries(vm_memory *mem, const int64_t *first_group, int64_t max_groups, void *out_centroids,
+                        int64_t *out_first_rows, int64_t *out_n_rows, int64_t *out_keys, int64_t *out_key_rows,
+                        double *out_key_scores, int64_t *out_n_groups, void *workspace, size_t workspace_bytes,
+                        void *stream);
+
 /* ---- cosine top-k over the memory ---------------------------------------------------------------------
  * Replaces PreLLMInjector._calculate_batch_similarities + _cosine_similarity
  * (src/components/pre_llm_injector.py:346-388) and the Cypher scan of HybridRetriever._vector_search_chunks

@@ -43,6 +43,7 @@ SYMBOLS = [
     "vm_topk_scoped_workspace_bytes", "vm_topk_cosine_scoped", "vm_topk_cosine_scoped_exact",
     "vm_range_workspace_bytes", "vm_range_cosine", "vm_range_cosine_exact",
     "vm_memory_events_workspace_bytes", "vm_memory_events", "vm_memory_regroup_events", "vm_memory_group_ordinals",
+    "vm_memory_summaries_workspace_bytes", "vm_memory_summaries",
     "vm_topk_workspace_bytes", "vm_topk_cosine", "vm_topk_redo_workspace_bytes", "vm_topk_redo_flagged",
     "vm_topk_exact_workspace_bytes", "vm_topk_cosine_exact",
     "vm_cosine_exact", "vm_topk_select", "vm_topk_merge", "vm_profile_enable", "vm_profile_read", "vm_profile_mask", "vm_probe_mfma",
@@ -146,6 +147,8 @@ def lib() -> C.CDLL:
         "vm_memory_events": (i32, [vp, f64, i64, vp, vp, i64, vp, vp, vp, sz, vp]),
         "vm_memory_regroup_events": (i32, [vp, f64, i64, vp, vp, vp, sz, vp]),
         "vm_memory_group_ordinals": (vp, [vp]),
+        "vm_memory_summaries_workspace_bytes": (sz, [vp, i64]),
+        "vm_memory_summaries": (i32, [vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
         "vm_topk_workspace_bytes": (sz, [vp, i32, i32]),
         "vm_topk_cosine": (i32, [vp, vp, i32, i32, i32, f64, i32, i64, i64, vp, vp, vp, vp, vp, sz, vp]),
         "vm_topk_redo_workspace_bytes": (sz, [vp, i32, i32]),

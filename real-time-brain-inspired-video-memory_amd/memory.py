@@ -16,7 +16,7 @@ holds many videos: ``topk_scoped`` ranks only the rows whose tag lies in the que
 counterpart of the reference's ``{graph_uuid: $graph_uuid}`` predicate (include/vidmem.h).
 
 All arithmetic is in libvidmem.so (csrc/memory.hip, csrc/topk.hip, csrc/topk_exact.hip, csrc/topk_group.hip,
-csrc/topk_scope.hip, csrc/novelty.hip, csrc/erase.hip, csrc/range.hip, csrc/events.hip).
+csrc/topk_scope.hip, csrc/novelty.hip, csrc/erase.hip, csrc/range.hip, csrc/events.hip, csrc/summary.hip).
 
 ``erase`` forgets rows - a whole video or time window by its tags, or rows by id - and compacts the memory in place, so
 that a non-ring memory that has filled up takes new rows again (include/vidmem.h).
@@ -27,6 +27,9 @@ that a non-ring memory that has filled up takes new rows again (include/vidmem.h
 ``events`` cuts the stored rows into events - maximal runs of consecutive rows in which each frame resembles the one
 before it - and ``regroup_events`` makes those events the groups of ``topk_grouped``: one hit per scene instead of one
 per fixed chunk (csrc/events.hip, include/vidmem.h).
+
+``summaries`` turns every group into one centroid row and one key frame, and ``consolidate`` appends those centroids to
+a second, small memory that every search runs on unchanged (csrc/summary.hip, include/vidmem.h).
 """
 from __future__ import annotations
 
@@ -180,6 +183,33 @@ class Event(NamedTuple):
     rows: int
 
 
+class SummariesOut(NamedTuple):
+    """What ``enqueue_summaries`` returns, all on the device, one entry per window slot: ``count`` int64 [1] (the TOTAL
+    number of live groups), ``first_rows`` / ``n_rows`` / ``keys`` int64 [max_groups] (-1 padded), ``centroids``
+    [max_groups, D] of the memory's dtype (zero-padded), and with key frames ``key_rows`` int64 (-1 padded) and
+    ``key_scores`` float64 (0.0 padded), else ``None``."""
+    count: torch.Tensor
+    first_rows: torch.Tensor
+    n_rows: torch.Tensor
+    keys: torch.Tensor
+    centroids: torch.Tensor
+    key_rows: Optional[torch.Tensor]
+    key_scores: Optional[torch.Tensor]
+
+
+class Summaries(NamedTuple):
+    """What ``summaries`` returns, trimmed to the groups that were written: per group its first row id, row count,
+    group key, centroid row, key frame (the stored row closest to the centroid) and that row's RAW cosine against the
+    centroid; ``count`` the total number of live groups."""
+    first_rows: torch.Tensor
+    n_rows: torch.Tensor
+    keys: torch.Tensor
+    centroids: torch.Tensor
+    key_rows: torch.Tensor
+    key_scores: torch.Tensor
+    count: int
+
+
 def segment_events(first_rows, n_rows, base=0, tags=None) -> List[Event]:
     """The events of a memory as a list, in row order.  ``first_rows`` int64 [E] ascending: the first row id of every
     event (``events(...).first_rows``, complete); the live rows are the ids ``base .. base + n_rows - 1``; ``tags`` int64
@@ -254,6 +284,7 @@ class EmbeddingMemory:
         self._rscratch = None       # buffers of the range search (RangeScratch), grown on demand
         self._rlast = None          # the scratch of the last range call (last_range_rescored)
         self._vscratch = None       # buffers of the event segmentation (EventsScratch), grown on demand
+        self._mscratch = None       # buffers of the group summaries (SummaryScratch), grown on demand
         # Host tables: chunk id (reference pre_llm_injector.py:91) and {"time":..., "content":...} (for
         # _vector_search_chunks) of row (table_base + i).  table_base stays 0 unless a ring has wrapped far enough for
         # the slots of overwritten rows to be dropped (see _trim_tables); use id_of / meta_of for row -> entry.
@@ -1075,6 +1106,110 @@ class EmbeddingMemory:
         """``enqueue_regroup_events`` and one synchronising read -> the number of events among the covered rows."""
         return int(self.enqueue_regroup_events(threshold, max_gap_ms, from_row).item())
 
+    # ---- group summaries (include/vidmem.h vm_memory_summaries, DESIGN.md 18) --------------------------------------
+    def prepare_summaries(self, max_groups: int) -> "SummaryScratch":
+        """Size this memory's own summary buffers for windows of ``max_groups`` groups now (before a graph capture: a
+        capture must not allocate)."""
+        max_groups = self._summary_args(0, max_groups)[1]
+        if self._mscratch is None or not self._mscratch.fits(self, max_groups):
+            self._mscratch = SummaryScratch.for_(self, max_groups)
+        return self._mscratch
+
+    def _summary_args(self, first_group, max_groups) -> Tuple[int, int]:
+        """The argument rules of the summary calls, checked on the host before anything reaches the library."""
+        if not self.grouped:
+            raise ValueError("summaries need a grouped memory (EmbeddingMemory(..., grouped=True))")
+        max_groups = int(max_groups)
+        if max_groups < 0:
+            raise ValueError("max_groups is negative")
+        if isinstance(first_group, torch.Tensor):
+            return first_group, max_groups
+        first_group = int(first_group)
+        if first_group < 0:
+            raise ValueError("first_group is negative")
+        return first_group, max_groups
+
+    def enqueue_summaries(self, first_group=0, max_groups: int = 1024, key_frames: bool = True,
+                          scratch: Optional["SummaryScratch"] = None) -> SummariesOut:
+        """The capturable group summaries -> ``SummariesOut``: views of the buffers of ``scratch`` (default: this
+        memory's own, ``prepare_summaries``), valid until the next summaries call on it.
+
+        Window slot i holds live group ``first_group + i`` (groups are numbered in row order, the oldest live group is
+        0): its first row id, row count, group key, centroid - the normalised fp64 mean of its rows, rounded once to
+        the memory's dtype - and, with ``key_frames``, the stored row closest to that centroid and its RAW cosine.
+        ``first_group``: an int, or a device int64 [1] tensor (not read on the host, so a captured graph can page).
+        Enqueues ``vm_memory_summaries`` on the current stream: nothing is read on the host."""
+        first_group, max_groups = self._summary_args(first_group, max_groups)
+        if scratch is None:
+            scratch = self.prepare_summaries(max_groups)
+        elif not scratch.fits(self, max_groups):
+            raise ValueError("caller-owned summary scratch is too small for this max_groups")
+        if isinstance(first_group, torch.Tensor):
+            frm = first_group.to(device=self.device, dtype=torch.int64).reshape(-1)[:1].contiguous()
+        else:
+            frm = torch.tensor([first_group], dtype=torch.int64).to(self.device)
+        ptr = lambda x: C.c_void_p(x.data_ptr() if x is not None else 0)
+        m = max_groups
+        out = SummariesOut(scratch.count, scratch.first_rows[:m], scratch.n_rows[:m], scratch.keys[:m],
+                           scratch.centroids[:m], scratch.key_rows[:m] if key_frames else None,
+                           scratch.key_scores[:m] if key_frames else None)
+        some = lambda x: x if m else None           # max_groups == 0: the count only
+        self.ctx.check(self.L.vm_memory_summaries(self.handle, ptr(frm), m, ptr(some(out.centroids)),
+                                                  ptr(some(out.first_rows)), ptr(some(out.n_rows)),
+                                                  ptr(some(out.keys)), ptr(some(out.key_rows)),
+                                                  ptr(some(out.key_scores)), ptr(scratch.count), ptr(scratch.ws),
+                                                  scratch.ws.numel(), _lib.current_stream_ptr()))
+        frm.record_stream(torch.cuda.current_stream())
+        return out
+
+    def summaries(self, first_group: int = 0, max_groups: Optional[int] = None) -> Summaries:
+        """One centroid row and one key frame per group -> ``Summaries(first_rows, n_rows, keys, centroids, key_rows,
+        key_scores, count)`` on the device, trimmed to the groups that were written (``enqueue_summaries`` for the
+        rule).  ``max_groups=None``: every group from ``first_group`` on - a count-only call, then one sized call.
+        ``count`` is always the total number of live groups.  This form SYNCHRONISES (it reads the count)."""
+        first_group, _ = self._summary_args(first_group, 0 if max_groups is None else max_groups)
+        if isinstance(first_group, torch.Tensor):
+            raise ValueError("summaries() takes first_group as an int; enqueue_summaries accepts a device tensor")
+        if max_groups is None:
+            total = int(self.enqueue_summaries(first_group, 0).count.item())
+            max_groups = max(total - first_group, 0)
+        out = self.enqueue_summaries(first_group, int(max_groups))
+        count = int(out.count.item())
+        m = max(0, min(count - first_group, int(max_groups)))
+        return Summaries(out.first_rows[:m].clone(), out.n_rows[:m].clone(), out.keys[:m].clone(),
+                         out.centroids[:m].clone(), out.key_rows[:m].clone(), out.key_scores[:m].clone(), count)
+
+    def consolidate(self, into: "EmbeddingMemory", first_group: int = 0, max_groups: Optional[int] = None
+                    ) -> Tuple[Summaries, int]:
+        """Append the centroids of the groups ``first_group ..`` to ``into``, a memory of the same ``dim`` and dtype ->
+        ``(Summaries, first row id in into)``.  A centroid carries the tag of its key row when both memories are
+        tagged and the source group's key when ``into`` is grouped; in ``into``'s id / meta tables it gets the id of
+        the key row and ``{"first_row", "last_row", "key_row", "key_score"}``.  Paging: a second call with
+        ``first_group`` = the first call's ``count`` adds only the groups that opened since (the last group of the
+        first call may still have been growing: consolidate closed groups, or erase and redo the last summary)."""
+        if not isinstance(into, EmbeddingMemory):
+            raise ValueError("consolidate needs an EmbeddingMemory to append to")
+        if into.dim != self.dim or into.dtype_name != self.dtype_name:
+            raise ValueError(f"consolidate: {self.dim} x {self.dtype_name} rows do not fit a memory of "
+                             f"{into.dim} x {into.dtype_name}")
+        s = self.summaries(first_group, max_groups)
+        m = int(s.first_rows.numel())
+        if m == 0:
+            return s, len(into)
+        first, nrow = s.first_rows.tolist(), s.n_rows.tolist()
+        krow, kscore = s.key_rows.tolist(), s.key_scores.tolist()
+        tag = None
+        if self.tagged and into.tagged:
+            total, n = len(self), self.searchable
+            tags = _tensor_from_ptr(self.L.vm_memory_tags(self.handle), (n,), torch.int64, self.device)
+            slots = s.key_rows % self.capacity if (self.ring and total > self.capacity) else s.key_rows
+            tag = tags[slots]
+        meta = [{"first_row": a, "last_row": a + c - 1, "key_row": k, "key_score": v}
+                for a, c, k, v in zip(first, nrow, krow, kscore)]
+        at = into.append(s.centroids, ids=[self.id_of(k) for k in krow], meta=meta,
+                         group=s.keys if into.grouped else None, tag=tag)
+        return s, at
+
     @property
     def last_scope_flags(self) -> Optional[torch.Tensor]:
         return self._sflags
@@ -1257,6 +1392,34 @@ class EventsScratch:
     def for_(cls, memory: "EmbeddingMemory", max_events: int = 0) -> "EventsScratch":
         return cls(memory.device, memory.capacity, int(max_events),
                    int(memory.L.vm_memory_events_workspace_bytes(memory.handle)))
+
+
+class SummaryScratch:
+    """Device buffers of the group summaries for windows of up to ``max_groups`` groups: the workspace (group bounds,
+    one score per slot), ``count`` (int64 [1]) and the per-group outputs.  Like ``TopkScratch``, an owner keeps ONE
+    instance per stream / captured graph: a hipGraph bakes the addresses in."""
+
+    def __init__(self, device, dim: int, dtype, max_groups: int, ws_bytes: int):
+        m = max(int(max_groups), 1)
+        self.max_groups = int(max_groups)
+        self.ws = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=device)
+        self.count = torch.zeros(1, dtype=torch.int64, device=device)
+        self.first_rows = torch.full((m,), -1, dtype=torch.int64, device=device)
+        self.n_rows = torch.full((m,), -1, dtype=torch.int64, device=device)
+        self.keys = torch.full((m,), -1, dtype=torch.int64, device=device)
+        self.key_rows = torch.full((m,), -1, dtype=torch.int64, device=device)
+        self.key_scores = torch.zeros(m, dtype=torch.float64, device=device)
+        self.centroids = torch.zeros((m, dim), dtype=dtype, device=device)
+
+    def fits(self, memory: "EmbeddingMemory", max_groups: int) -> bool:
+        return (self.max_groups >= max_groups and self.centroids.shape[1] == memory.dim and
+                self.centroids.dtype == memory.dtype and
+                self.ws.numel() >= int(memory.L.vm_memory_summaries_workspace_bytes(memory.handle, int(max_groups))))
+
+    @classmethod
+    def for_(cls, memory: "EmbeddingMemory", max_groups: int) -> "SummaryScratch":
+        ws_bytes = int(memory.L.vm_memory_summaries_workspace_bytes(memory.handle, int(max_groups)))
+        return cls(memory.device, memory.dim, memory.dtype, int(max_groups), ws_bytes)
 
 
 class RangeScratch:
