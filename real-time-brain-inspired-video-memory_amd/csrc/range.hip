@@ -9,8 +9,9 @@
 // is re-scored exactly (topk_common.h), and order comes from prefix sums over separate launches - no atomics, no
 // workgroup waits for another.
 //   cut      : per query the fp64 norm and one fp32 cut, conservative: a score <= cut is PROVABLY no hit
-//   scan     : the MFMA loop of topk_scope.hip (16-row tiles, the row tile the A operand from global memory, the query
-//              tile from chunk-swizzled LDS, x 1/||row||; a tile with no in-scope pair is skipped on its 16 tags).  One
+//   scan     : the shared tile scan (topk_tile_scan.h: 16-row tiles, the row tile the A operand from global memory, the
+//              query tile from chunk-swizzled LDS, x 1/||row||; a tile with no in-scope pair is skipped on its 16 tags)
+//              with the policy RangeScan below.  One
 //              BIT per (query, physical slot): in scope, live, and not at or below the cut.  16 bits per (query, tile),
 //              assembled across the four h lanes that hold a tile's rows for one query
 //   rescore  : grid (chunks of RC_CHUNK age orders, Q).  Each candidate bit becomes one exact shown score, stored at
@@ -20,20 +21,17 @@
 //              write (row id, score); the padding of [count, max_hits) is spread over the same blocks
 // The exhaustive entry replaces cut + scan by a mask kernel (every live in-scope pair is a candidate): it shares no
 // arithmetic with the scan.  Every launch reads the row count from the device and is sized from the capacity.
-#include "topk_select.h"
+#include "topk_tile_scan.h"
 
 #include <climits>
 #include <cmath>
 
 namespace {
 
-constexpr int RS_THREADS = 256;  // scan
 constexpr int RC_THREADS = 256;  // rescore, emit
 constexpr int RC_PER = 16;       // age orders per thread
 constexpr int RC_CHUNK = RC_THREADS * RC_PER;  // 4096 age orders = 64 hit words per block
 constexpr int RP_THREADS = 256;  // prefix (one block per query)
-
-__device__ __forceinline__ bool in_scope(int64_t tag, int64_t lo, int64_t hi) { return lo <= tag && tag <= hi; }
 
 // the hit rule on an exact cosine: shown score strictly above the threshold
 __device__ __forceinline__ bool is_hit(double shown, double min_score) { return passes_min(1, shown, min_score); }
@@ -74,122 +72,82 @@ __global__ void __launch_bounds__(64)
 }
 
 // ---- scan --------------------------------------------------------------------------------------------------
-// grid (row blocks, query groups of QT*16); topk_scope.hip's scan with another epilogue.  acc[t][j] = <row tile*16 + 4h
-// + j, query q0 + 16t + r16>; lane (r16, h) holds 4 of a tile's 16 pair bits for its query, the other 12 sit in lanes
-// r16 + 16 h'.  cand16[q * cstride16 + tile] = the tile's 16 bits (bit i = slot tile*16 + i).  SCOPED = false reads no
-// tags (every live row is in scope).
-template <int DT, int QT, bool SCOPED>
-__global__ void __launch_bounds__(RS_THREADS)
-    range_scan_kernel(const uint16_t *__restrict__ mem, const float *__restrict__ rnorm,
-                      const int64_t *__restrict__ tag, const uint16_t *__restrict__ queries,
-                      const int64_t *__restrict__ scope_lo, const int64_t *__restrict__ scope_hi,
-                      const float *__restrict__ cut, const int64_t *__restrict__ d_total, int64_t cap, int ring, int D,
-                      int Q, int64_t cstride16, uint16_t *__restrict__ cand16) {
-    using E = vm_elem<DT>;
-    using vec8 = typename E::vec8;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    uint4 *qlds = reinterpret_cast<uint4 *>(smem);
-    __shared__ int64_t slo[QT * 16], shi[QT * 16];
-    __shared__ float scut[QT * 16];
-    const int chunks = D / 8;
-    constexpr int nw = RS_THREADS / 64;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int r16 = lane & 15, h = lane >> 4;
-    const int q0 = blockIdx.y * (QT * 16);
-    for (int idx = tid; idx < QT * 16 * chunks; idx += RS_THREADS) {
-        const int q = idx / chunks, ci = idx - q * chunks;
-        uint4 v = make_uint4(0, 0, 0, 0);
-        if (q0 + q < Q) v = reinterpret_cast<const uint4 *>(queries + (size_t)(q0 + q) * D)[ci];
-        qlds[q * chunks + ((ci & ~15) | ((ci ^ q) & 15))] = v;
+// The range policy of the tile scan (topk_tile_scan.h): lane (r16, h) holds 4 of a tile's 16 pair bits for its query, the
+// other 12 sit in lanes r16 + 16 h'.  cand16[q * cstride16 + tile] = the tile's 16 bits (bit i = slot tile*16 + i).
+// SCOPED = false reads no tags (every live row is in scope) and skips no tile.
+template <int QT, bool SCOPED>
+struct RangeQState {  // 16-byte aligned as the scoped search's, for the same LDS loads
+    alignas(16) int64_t lo[QT * 16], hi[QT * 16];
+    float cut[QT * 16];
+};
+template <int QT>
+struct RangeQState<QT, false> {
+    float cut[QT * 16];
+};
+template <bool SCOPED>
+struct RangeScan {
+    struct Args {
+        const int64_t *tag, *scope_lo, *scope_hi;
+        const float *cut;
+        int64_t cstride16;
+        uint16_t *cand16;
+    };
+    template <int QT>
+    using QState = RangeQState<QT, SCOPED>;
+    struct View {};
+    template <class QS>
+    static __device__ __forceinline__ void load_query(QS &qs, const Args &a, int i, int q, bool live) {
+        if constexpr (SCOPED) {  // queries past Q have the empty scope and are never written
+            qs.lo[i] = live ? a.scope_lo[q] : LLONG_MAX;
+            qs.hi[i] = live ? a.scope_hi[q] : LLONG_MIN;
+        }
+        qs.cut[i] = live ? a.cut[q] : INFINITY;
     }
-    if (tid < QT * 16) {  // queries past Q have the empty scope and are never written
-        const bool live = q0 + tid < Q;
-        if (SCOPED) {
-            slo[tid] = live ? scope_lo[q0 + tid] : LLONG_MAX;
-            shi[tid] = live ? scope_hi[q0 + tid] : LLONG_MIN;
+    static __device__ __forceinline__ View view(const Args &, const RingView &) { return {}; }
+    template <int QT>
+    static __device__ __forceinline__ bool skip_tile(const QState<QT> &qs, const Args &a, const TileLane &l) {
+        if constexpr (SCOPED) {
+            if (tile_in_scope<QT>(a.tag, qs.lo, qs.hi, l)) return false;
+#pragma unroll
+            for (int t = 0; t < QT; ++t) {  // a skipped tile has no candidate
+                const int q = l.q0 + 16 * t + l.r16;
+                if (l.h == 0 && q < l.Q) a.cand16[(size_t)q * a.cstride16 + l.tile] = 0;
+            }
+            return true;
+        } else {
+            return false;
         }
-        scut[tid] = live ? cut[q0 + tid] : INFINITY;
     }
-    __syncthreads();
-    const RingView rv = ring_view(*d_total, cap, ring);
-    const int64_t n = rv.n;
-    const int64_t ntiles = (n + 15) / 16;
-    const int ksteps = D / 32;
-    constexpr int LB = 8;
-    const uint4 *qrow = qlds + r16 * chunks;
-    const int tstride = 16 * chunks;
-    const int64_t tile_step = (int64_t)gridDim.x * nw;
-    for (int64_t tile = (int64_t)blockIdx.x * nw + wave; tile < ntiles; tile += tile_step) {
-        const int64_t p0 = tile * 16 + 4 * h;  // this lane's 4 slots (below cap_pad: the columns are padded to 64 rows)
-        if (SCOPED) {  // the tile's 16 tags before any row data, as the scoped scan tests them
-            const int64_t trow = tile * 16 + r16;
-            bool hit = false;
-            if (trow < n) {
-                const int64_t tg = tag[trow];
-#pragma unroll
-                for (int t = 0; t < QT; ++t)
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) hit |= in_scope(tg, slo[16 * t + 4 * h + c], shi[16 * t + 4 * h + c]);
-            }
-            if (__ballot(hit) == 0ull) {  // wave-uniform: nothing of this tile is wanted; its rows are not read
-#pragma unroll
-                for (int t = 0; t < QT; ++t) {
-                    const int q = q0 + 16 * t + r16;
-                    if (h == 0 && q < Q) cand16[(size_t)q * cstride16 + tile] = 0;
-                }
-                continue;
-            }
-        }
-        int64_t row = tile * 16 + r16;
-        if (row > n - 1) row = n - 1;  // tail lanes re-read the last row; their bits are masked below
-        const uint4 *src = reinterpret_cast<const uint4 *>(mem + (size_t)row * D) + h;
-        f32x4 acc[QT];
-#pragma unroll
-        for (int t = 0; t < QT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-        for (int s0 = 0; s0 < ksteps; s0 += LB) {
-            uint4 cur[LB];
-#pragma unroll
-            for (int u = 0; u < LB; ++u) cur[u] = src[(s0 + u < ksteps ? s0 + u : ksteps - 1) * 4];
-#pragma unroll
-            for (int u = 0; u < LB; ++u) {
-                if (s0 + u < ksteps) {
-                    const int ci = h + 4 * (s0 + u);
-                    const vec8 av = __builtin_bit_cast(vec8, cur[u]);
-                    const uint4 *qp = qrow + ((ci & ~15) | ((ci ^ r16) & 15));
-#pragma unroll
-                    for (int t = 0; t < QT; ++t) acc[t] = E::mfma16(av, __builtin_bit_cast(vec8, qp[t * tstride]), acc[t]);
-                }
-            }
-        }
-        const float4 rn = *reinterpret_cast<const float4 *>(rnorm + p0);
-        const float rnv[4] = {rn.x, rn.y, rn.z, rn.w};
+    template <int QT>
+    static __device__ __forceinline__ void epilogue(const QState<QT> &qs, const Args &a, const View &,
+                                                    const TileLane &l, const float (&s)[QT][4]) {
         int64_t tj[4] = {0, 0, 0, 0};
-        if (SCOPED) {
+        if constexpr (SCOPED) {
 #pragma unroll
-            for (int j = 0; j < 4; ++j) tj[j] = tag[p0 + j];
+            for (int j = 0; j < 4; ++j) tj[j] = a.tag[l.p0() + j];
         }
 #pragma unroll
         for (int t = 0; t < QT; ++t) {
-            const int q = q0 + 16 * t + r16;  // past Q: cut = +inf and an empty scope, no bit; all 64 lanes shuffle
-            const float c = scut[16 * t + r16];
+            const int q = l.q0 + 16 * t + l.r16;  // past Q: cut = +inf and an empty scope, no bit; all 64 lanes shuffle
+            const float c = qs.cut[16 * t + l.r16];
             int64_t lo = 0, hi = 0;
-            if (SCOPED) {
-                lo = slo[16 * t + r16];
-                hi = shi[16 * t + r16];
+            if constexpr (SCOPED) {
+                lo = qs.lo[16 * t + l.r16];
+                hi = qs.hi[16 * t + l.r16];
             }
             uint32_t bits = 0;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                const bool in = p0 + j < n && (!SCOPED || in_scope(tj[j], lo, hi));
+                const bool in = l.p0() + j < l.n && (!SCOPED || in_scope(tj[j], lo, hi));
                 // `not at or below the cut`: a NaN score stays a candidate and is settled exactly
-                if (in && !(acc[t][j] * rnv[j] <= c)) bits |= 1u << (4 * h + j);
+                if (in && !(s[t][j] <= c)) bits |= 1u << (4 * l.h + j);
             }
             bits |= __shfl_xor(bits, 16, 64);
             bits |= __shfl_xor(bits, 32, 64);
-            if (h == 0 && q < Q) cand16[(size_t)q * cstride16 + tile] = (uint16_t)bits;
+            if (l.h == 0 && q < l.Q) a.cand16[(size_t)q * a.cstride16 + l.tile] = (uint16_t)bits;
         }
     }
-}
+};
 
 // ---- mask (exhaustive entry) -------------------------------------------------------------------------------
 // grid (words, Q): candidate word w of query q = the live, in-scope slots among [32 w, 32 w + 32).  No score is looked at.
@@ -389,10 +347,9 @@ __global__ void __launch_bounds__(RC_THREADS)
 }
 
 // ---- host --------------------------------------------------------------------------------------------------
-struct RPlan {
+struct RPlan : ScanGeom {
     int64_t cap_pad;  // the columns' padding (64 rows)
     int nch;          // chunks of RC_CHUNK age orders
-    int qt, qgroups, nbx;
     size_t off_hit, off_sc, off_ch, off_cc, off_cb, off_cut, off_qn, total;
 };
 
@@ -400,12 +357,7 @@ RPlan range_plan(const vm_memory *m, int Q) {
     RPlan p;
     p.cap_pad = (m->cap + 63) / 64 * 64;
     p.nch = (int)((p.cap_pad + RC_CHUNK - 1) / RC_CHUNK);
-    p.qt = Q <= 16 ? 1 : 2;
-    p.qgroups = (Q + 16 * p.qt - 1) / (16 * p.qt);
-    const int64_t tiles = p.cap_pad / 16;
-    const int64_t nbx = (tiles + RS_THREADS / 64 - 1) / (RS_THREADS / 64);
-    const int64_t lim = (int64_t)m->ctx->num_cus * 8;
-    p.nbx = (int)(nbx < lim ? nbx : lim);
+    static_cast<ScanGeom &>(p) = vm_scan_geom(m, Q, p.cap_pad / 16, TS_THREADS);  // the tiles of the padded columns
     WsBump ws;
     ws.take((size_t)Q * (size_t)p.cap_pad / 8);              // candidate bits at offset 0: [Q][physical slot]
     p.off_hit = ws.take((size_t)Q * (size_t)p.cap_pad / 8);  // hit bits [Q][age order]
@@ -439,20 +391,6 @@ int range_check(vm_memory *m, const void *queries, int Q, double min_score, int 
     return VM_OK;
 }
 
-template <int DT, int QT, bool SCOPED>
-int range_scan(vm_memory *m, const RPlan &p, const void *queries, int Q, const int64_t *scope_lo,
-               const int64_t *scope_hi, const float *cut, uint16_t *cand16, hipStream_t st) {
-    const size_t lds = (size_t)QT * 16 * m->D * 2;
-    auto kern = range_scan_kernel<DT, QT, SCOPED>;
-    if (lds > 65536 - 1024)
-        VM_HIP(m->ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    kern<<<dim3(p.nbx, p.qgroups), RS_THREADS, lds, st>>>(m->rows, m->rnorm32, m->tag, (const uint16_t *)queries,
-                                                         scope_lo, scope_hi, cut, m->d_total, m->cap, m->ring, m->D, Q,
-                                                         p.cap_pad / 16, cand16);
-    VM_LAUNCH_CHECK(m->ctx);
-    return VM_OK;
-}
-
 // fast = cut + scan, otherwise the mask; then rescore, prefix, emit
 template <int DT>
 int range_run(vm_memory *m, bool fast, const void *queries, int Q, double min_score, int score_mode,
@@ -475,15 +413,12 @@ int range_run(vm_memory *m, bool fast, const void *queries, int Q, double min_sc
                                                           cut, qn, m->d_total + VM_GSTATE_OUTSIDE);
         VM_LAUNCH_CHECK(ctx);
         if (fast) {
-            const bool scoped = scope_lo != nullptr;
+            const int64_t cstride16 = p.cap_pad / 16;
             uint16_t *c16 = (uint16_t *)ws;
-            int rc;
-            if (p.qt == 1)
-                rc = scoped ? range_scan<DT, 1, true>(m, p, queries, Q, scope_lo, scope_hi, cut, c16, st)
-                            : range_scan<DT, 1, false>(m, p, queries, Q, scope_lo, scope_hi, cut, c16, st);
-            else
-                rc = scoped ? range_scan<DT, 2, true>(m, p, queries, Q, scope_lo, scope_hi, cut, c16, st)
-                            : range_scan<DT, 2, false>(m, p, queries, Q, scope_lo, scope_hi, cut, c16, st);
+            const int rc = scope_lo ? vm_tile_scan<DT, RangeScan<true>>(
+                                          m, p, queries, Q, {m->tag, scope_lo, scope_hi, cut, cstride16, c16}, st)
+                                    : vm_tile_scan<DT, RangeScan<false>>(
+                                          m, p, queries, Q, {nullptr, nullptr, nullptr, cut, cstride16, c16}, st);
             if (rc != VM_OK) return rc;
         } else {
             range_mask_kernel<<<dim3((unsigned)((cstride32 + 255) / 256), Q), 256, 0, st>>>(

@@ -53,6 +53,8 @@ __device__ __forceinline__ SmWindow sm_window(const int64_t *d_total, int64_t ca
     s.rv = ring_view(*d_total, cap, ring);
     s.n_groups = 0;
     s.ord0 = 0;
+    // group_view (vm_internal.h) written out: it reads the oldest row's slot as rv.head, and with that every kernel of
+    // this file compiles to other instructions than the measured ones
     if (s.rv.n > 0) {
         s.ord0 = gord[slot_of(s.rv, 0)];
         s.n_groups = gord[slot_of(s.rv, s.rv.n - 1)] - s.ord0 + 1;

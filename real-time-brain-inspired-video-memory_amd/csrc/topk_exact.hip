@@ -2,8 +2,9 @@
 // (src/components/pre_llm_injector.py:374-388: three left-to-right fp64 sums, sqrt, guards, one division),
 // then a stable top-k.  Used (a) as the fallback for queries the fast scan cannot certify, (b) for the
 // post-compression filter (src/pipeline/retriever_hybrid.py:494-504), (c) as an on-device checker.
-// Also home of what the three redos share (vm_internal.h): the row-block count vm_topk_redo_blocks and the merge of the
-// slice winners vm_topk_redo_merge, called by the row redo here and by topk_group.hip and topk_scope.hip.
+// Also home of what the three redos share (vm_internal.h): the row-block count vm_topk_redo_blocks, the redo scan of rows
+// vm_topk_redo_scan (the row redo here and topk_scope.hip; the grouped one carries a group across chunks and is
+// topk_group.hip's own) and the merge of the slice winners vm_topk_redo_merge (all three).
 #include "topk_common.h"
 #include "vm_internal.h"
 
@@ -139,21 +140,34 @@ __global__ void __launch_bounds__(256)
 // no allocation, capturable into a hipGraph, and free (two near-empty launches) when no query is flagged.
 // ---------------------------------------------------------------------------------------------------------
 constexpr int REDO_THREADS = 256;
-constexpr int REDO_CHUNK = 2048;  // scores held in LDS per selection pass
 constexpr int REDO_KMAX = 64;
 
 // grid = nblk row blocks; every block walks all Q flags and, for each flagged query, scores its contiguous slice of
 // age orders exactly as the reference does (src/components/pre_llm_injector.py:374-388) and keeps the slice's
-// stable top-k: part[(block * Q + q) * k + i] = {score fp64, age order int64}.
-template <int DT>
+// stable top-k: part[(block * Q + q) * k + i] = {score fp64, age order int64}.  CHUNK scores are held in LDS per
+// selection pass.  The redo scan of the row search (SCOPED = false: every live row; the scores sit in dynamic LDS behind
+// the query) and of the scoped search (SCOPED = true: only the rows whose tag lies in the query's scope are scored and
+// may win, and a chunk with no in-scope row costs its tags only; the scores and the in-scope marks sit in static LDS).
+template <int DT, int CHUNK, bool SCOPED>
 __global__ void __launch_bounds__(REDO_THREADS)
     topk_redo_scan_kernel(const uint16_t *__restrict__ queries, const uint16_t *__restrict__ rows,
-                          const double *__restrict__ norm64, const int64_t *__restrict__ d_total, int64_t cap,
-                          int ring, int D, int Q, int k, const int32_t *__restrict__ flags,
-                          double *__restrict__ part_s, int64_t *__restrict__ part_o) {
+                          const double *__restrict__ norm64, const int64_t *__restrict__ tag,
+                          const int64_t *__restrict__ scope_lo, const int64_t *__restrict__ scope_hi,
+                          const int64_t *__restrict__ d_total, int64_t cap, int ring, int D, int Q, int k,
+                          const int32_t *__restrict__ flags, double *__restrict__ part_s,
+                          int64_t *__restrict__ part_o) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    uint16_t *ql = reinterpret_cast<uint16_t *>(smem);                       // [D]
-    double *sc = reinterpret_cast<double *>(smem + (size_t)D * 2);           // [REDO_CHUNK]
+    uint16_t *ql = reinterpret_cast<uint16_t *>(smem);  // [D]
+    double *sc;                                         // [CHUNK]
+    uint8_t *live = nullptr;                            // [CHUNK], SCOPED only: the row is in the query's scope
+    if constexpr (SCOPED) {
+        __shared__ double sc_sh[CHUNK];
+        __shared__ uint8_t live_sh[CHUNK];
+        sc = sc_sh;
+        live = live_sh;
+    } else {
+        sc = reinterpret_cast<double *>(smem + (size_t)D * 2);
+    }
     __shared__ double run_s[REDO_KMAX], new_s[REDO_KMAX], red_s[REDO_THREADS / 64];
     __shared__ int64_t run_o[REDO_KMAX], new_o[REDO_KMAX], red_o[REDO_THREADS / 64];
     __shared__ double qnorm_sh;
@@ -181,20 +195,39 @@ __global__ void __launch_bounds__(REDO_THREADS)
         if (tid == 0) qnorm_sh = __dsqrt_rn(ref_sumsq<DT>(ql, D));
         __syncthreads();
         const double qn = qnorm_sh;
-        for (int64_t c0 = lo; c0 < hi; c0 += REDO_CHUNK) {
-            const int cn = (int)(hi - c0 < REDO_CHUNK ? hi - c0 : REDO_CHUNK);
+        int64_t slo = 0, shi = 0;
+        if constexpr (SCOPED) {
+            slo = scope_lo[q];
+            shi = scope_hi[q];
+        }
+        for (int64_t c0 = lo; c0 < hi; c0 += CHUNK) {
+            const int cn = (int)(hi - c0 < CHUNK ? hi - c0 : CHUNK);
+            int mine = 0;
             for (int i = tid; i < cn; i += REDO_THREADS) {
                 const int64_t p = slot_of(rv, c0 + i);
-                // norm64: the reference's norm of the stored row, computed at append
-                sc[i] = ref_cosine(ref_dot<DT>(ql, rows + (size_t)p * D, D), qn, norm64[p]);
+                bool in = true;
+                if constexpr (SCOPED) {
+                    in = in_scope(tag[p], slo, shi);
+                    live[i] = in ? 1 : 0;
+                }
+                if (in) {
+                    // norm64: the reference's norm of the stored row, computed at append
+                    sc[i] = ref_cosine(ref_dot<DT>(ql, rows + (size_t)p * D, D), qn, norm64[p]);
+                    mine = 1;
+                }
             }
-            __syncthreads();
+            if constexpr (SCOPED) {
+                if (!__syncthreads_or(mine)) continue;  // uniform: nothing of this chunk is in scope
+            } else {
+                __syncthreads();
+            }
             // candidates = this chunk's scores followed by the running list
             block_select<REDO_THREADS>(cn + k, k,
                          [&](int i, double &v, int64_t &o) {
                              if (i < cn) {
                                  v = sc[i];
                                  o = c0 + i;
+                                 if constexpr (SCOPED) o = live[i] ? o : -1;
                              } else {
                                  v = run_s[i - cn];
                                  o = run_o[i - cn];
@@ -256,6 +289,29 @@ int vm_topk_redo_blocks(const vm_memory *m, int chunk) {
     int64_t b = (m->cap + chunk - 1) / chunk;
     if (b > m->ctx->num_cus) b = m->ctx->num_cus;
     return b < 1 ? 1 : (int)b;
+}
+
+template <int DT>
+static int redo_scan(vm_memory *m, const void *queries, int Q, int k, const int64_t *scope_lo, const int64_t *scope_hi,
+              const int32_t *flags, int nblk, double *part_s, int64_t *part_o, hipStream_t st) {
+    const size_t ql = (size_t)m->D * 2;
+    if (scope_lo)
+        topk_redo_scan_kernel<DT, VM_REDO_CHUNK_SCOPED, true><<<nblk, REDO_THREADS, ql, st>>>(
+            (const uint16_t *)queries, m->rows, m->norm64, m->tag, scope_lo, scope_hi, m->d_total, m->cap, m->ring, m->D,
+            Q, k, flags, part_s, part_o);
+    else
+        topk_redo_scan_kernel<DT, VM_REDO_CHUNK, false><<<nblk, REDO_THREADS, ql + (size_t)VM_REDO_CHUNK * 8, st>>>(
+            (const uint16_t *)queries, m->rows, m->norm64, nullptr, nullptr, nullptr, m->d_total, m->cap, m->ring, m->D,
+            Q, k, flags, part_s, part_o);
+    VM_LAUNCH_CHECK(m->ctx);
+    return VM_OK;
+}
+
+int vm_topk_redo_scan(vm_memory *m, const void *queries, int Q, int k, const int64_t *scope_lo,
+                      const int64_t *scope_hi, const int32_t *flags, int nblk, double *part_s, int64_t *part_o,
+                      hipStream_t st) {
+    return m->dtype == VM_F16 ? redo_scan<VM_F16>(m, queries, Q, k, scope_lo, scope_hi, flags, nblk, part_s, part_o, st)
+                              : redo_scan<VM_BF16>(m, queries, Q, k, scope_lo, scope_hi, flags, nblk, part_s, part_o, st);
 }
 
 int vm_topk_redo_merge(vm_memory *m, const double *part_s, const int64_t *part_o, int nblk, int Q, int k,
@@ -351,7 +407,7 @@ extern "C" int vm_topk_select(vm_ctx *ctx, const double *scores, int Q, int64_t 
 
 extern "C" size_t vm_topk_redo_workspace_bytes(const vm_memory *m, int Q, int k) {
     if (!m || Q <= 0 || k <= 0 || k > REDO_KMAX) return 0;
-    return vm_align_up((size_t)vm_topk_redo_blocks(m, REDO_CHUNK) * Q * k * 16, 256);
+    return vm_align_up((size_t)vm_topk_redo_blocks(m, VM_REDO_CHUNK) * Q * k * 16, 256);
 }
 
 extern "C" int vm_topk_redo_flagged(vm_memory *m, const void *queries, int Q, int k, int use_min_score,
@@ -364,7 +420,7 @@ extern "C" int vm_topk_redo_flagged(vm_memory *m, const void *queries, int Q, in
         return vm_fail(ctx, VM_ERR_INVALID, "vm_topk_redo_flagged: bad arguments");
     if (k > REDO_KMAX) return vm_fail(ctx, VM_ERR_UNSUPPORTED, "vm_topk_redo_flagged: k=%d > %d", k, REDO_KMAX);
     if (int rc = vm_check_score_mode(ctx, score_mode)) return rc;
-    const int nblk = vm_topk_redo_blocks(m, REDO_CHUNK);
+    const int nblk = vm_topk_redo_blocks(m, VM_REDO_CHUNK);
     const size_t need = (size_t)nblk * Q * k * 16;
     if (!workspace || workspace_bytes < need)
         return vm_fail(ctx, VM_ERR_NOMEM, "vm_topk_redo_flagged: workspace %zu < %zu", workspace_bytes, need);
@@ -374,16 +430,7 @@ extern "C" int vm_topk_redo_flagged(vm_memory *m, const void *queries, int Q, in
     vm_prof_scope prof(ctx, VM_PROF_TOPK_EXACT, st);
     double *part_s = (double *)workspace;
     int64_t *part_o = (int64_t *)((char *)workspace + (size_t)nblk * Q * k * 8);
-    const size_t lds = (size_t)m->D * 2 + (size_t)REDO_CHUNK * 8;
-    if (m->dtype == VM_F16)
-        topk_redo_scan_kernel<VM_F16><<<nblk, REDO_THREADS, lds, st>>>(
-            (const uint16_t *)queries, m->rows, m->norm64, m->d_total, m->cap, m->ring, m->D, Q, k, query_flags,
-            part_s, part_o);
-    else
-        topk_redo_scan_kernel<VM_BF16><<<nblk, REDO_THREADS, lds, st>>>(
-            (const uint16_t *)queries, m->rows, m->norm64, m->d_total, m->cap, m->ring, m->D, Q, k, query_flags,
-            part_s, part_o);
-    VM_LAUNCH_CHECK(ctx);
+    if (int rc = vm_topk_redo_scan(m, queries, Q, k, nullptr, nullptr, query_flags, nblk, part_s, part_o, st)) return rc;
     return vm_topk_redo_merge(m, part_s, part_o, nblk, Q, k, query_flags, use_min_score, min_score, score_mode, row_stride,
                               row_offset, out_scores, out_rows, nullptr, nullptr, st);
 }

@@ -3,7 +3,8 @@
 // The row ranking is vm_topk_cosine's (src/components/pre_llm_injector.py:346-388, retriever_hybrid.py:293-306); a
 // group's score is the exact max over its rows and its representative the lowest row id reaching that max.  Same
 // two-stage, certified design as topk.hip; the key images, the block-wide selection, the plan
-// scaffold and the argument check are topk_select.h's, shared with topk_scope.hip:
+// scaffold and the argument check are topk_select.h's, shared with topk_scope.hip; the scan is topk_tile_scan.h's, shared
+// with topk_scope.hip and range.hip (GroupScan below is its policy):
 //   table    : first age order of every live group (groups are runs of equal ordinals, memory.hip) + clears the maxima
 //   scan     : fp32 MFMA scores with the list scan's numerics (the same instruction over the same operand layout, then
 //              x 1/||row||), folded into per-(query, group) fp32 maxima with one atomic max per run of a 16-row tile
@@ -16,13 +17,12 @@
 //              block, segmented max in LDS, stable top-k per slice, then the one merge of every redo
 //              (vm_topk_redo_merge, topk_exact.hip).  Reads flags and counts on the device.
 // Every launch reads the row count from the device and sizes its grid from the capacity: capturable.
-#include "topk_select.h"
+#include "topk_tile_scan.h"
 
 #include <climits>
 
 namespace {
 
-constexpr int GS_THREADS = 256;   // scan
 constexpr int SEL_THREADS = 1024; // select: cut and final sort (one block per query)
 constexpr int SEL_SAMPLE = 2048;  // groups whose fp32 maxima give each query's cut
 constexpr int SEL_CAP = 4096;     // groups at or above the cut a query keeps; more -> the full radix select
@@ -43,23 +43,6 @@ __device__ __forceinline__ unsigned long long okey64(double d) {
 }
 __device__ __forceinline__ double dekey64(unsigned long long k) {
     return __longlong_as_double((long long)((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k));
-}
-
-// live rows + the ordinal of the oldest live group + the number of live groups, from the device counters
-struct GView {
-    RingView rv;
-    int64_t ord0, ng;
-};
-__device__ __forceinline__ GView group_view(const int64_t *d_total, int64_t cap, int ring, const int64_t *gord) {
-    GView g;
-    g.rv = ring_view(*d_total, cap, ring);
-    g.ord0 = 0;
-    g.ng = 0;
-    if (g.rv.n > 0) {
-        g.ord0 = gord[g.rv.head];
-        g.ng = gord[slot_of(g.rv, g.rv.n - 1)] - g.ord0 + 1;
-    }
-    return g;
 }
 
 // the exact reference cosine of the query staged in LDS (ql) and the row in slot p, strictly left to right.  The loops
@@ -111,7 +94,7 @@ __global__ void __launch_bounds__(256)
     group_table_kernel(const int64_t *__restrict__ d_total, int64_t cap, int ring, const int64_t *__restrict__ gord,
                        int Q, int *__restrict__ first_o, uint32_t *__restrict__ F, int32_t *__restrict__ flags,
                        int fill_flags) {
-    const GView gv = group_view(d_total, cap, ring, gord);
+    const GroupView gv = group_view(d_total, cap, ring, gord);
     const int64_t n = gv.rv.n;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     const int64_t t0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -130,74 +113,36 @@ __global__ void __launch_bounds__(256)
 }
 
 // ---- scan --------------------------------------------------------------------------------------------------
-// grid (row blocks, query groups of QT*16).  The MFMA part is topk_scan_kernel's (topk.hip): 16-row tiles in physical
-// order, the row tile the A operand straight from global memory, the query tile the B operand from chunk-swizzled LDS,
-// acc[t][j] = <row tile*16 + 4h + j, query q0 + 16t + r16>, score = acc * rnorm32.  Instead of a candidate list, each
-// lane folds its 4 consecutive rows into runs of one group and raises F[q][group] with one atomic max per run.
-template <int DT, int QT>
-__global__ void __launch_bounds__(GS_THREADS)
-    group_scan_kernel(const uint16_t *__restrict__ mem, const float *__restrict__ rnorm,
-                      const int64_t *__restrict__ gord, const uint16_t *__restrict__ queries,
-                      const int64_t *__restrict__ d_total, int64_t cap, int ring, int D, int Q,
-                      uint32_t *__restrict__ F) {
-    using E = vm_elem<DT>;
-    using vec8 = typename E::vec8;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    uint4 *qlds = reinterpret_cast<uint4 *>(smem);
-    const int chunks = D / 8;
-    constexpr int nw = GS_THREADS / 64;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int r16 = lane & 15, h = lane >> 4;
-    const int q0 = blockIdx.y * (QT * 16);
-    for (int idx = tid; idx < QT * 16 * chunks; idx += GS_THREADS) {
-        const int q = idx / chunks, ci = idx - q * chunks;
-        uint4 v = make_uint4(0, 0, 0, 0);
-        if (q0 + q < Q) v = reinterpret_cast<const uint4 *>(queries + (size_t)(q0 + q) * D)[ci];
-        qlds[q * chunks + ((ci & ~15) | ((ci ^ q) & 15))] = v;
+// The grouped policy of the tile scan (topk_tile_scan.h).  Instead of a key per row, each lane folds its 4 consecutive
+// rows into runs of one group and raises F[q * ng + group] with one atomic max per run.
+struct GroupScan {
+    struct Args {
+        const int64_t *gord;
+        uint32_t *F;
+    };
+    template <int QT>
+    struct QState {};
+    using View = GroupView;
+    template <class QS>
+    static __device__ __forceinline__ void load_query(QS &, const Args &, int, int, bool) {}
+    static __device__ __forceinline__ View view(const Args &a, const RingView &rv) { return group_view(rv, a.gord); }
+    template <int QT>
+    static __device__ __forceinline__ bool skip_tile(const QState<QT> &, const Args &, const TileLane &) {
+        return false;
     }
-    __syncthreads();
-    const GView gv = group_view(d_total, cap, ring, gord);
-    const int64_t n = gv.rv.n;
-    const int64_t ntiles = (n + 15) / 16;
-    const int ksteps = D / 32;
-    constexpr int LB = 8;
-    const uint4 *qrow = qlds + r16 * chunks;
-    const int tstride = 16 * chunks;
-    const int64_t tile_step = (int64_t)gridDim.x * nw;
-    for (int64_t tile = (int64_t)blockIdx.x * nw + wave; tile < ntiles; tile += tile_step) {
-        int64_t row = tile * 16 + r16;
-        if (row > n - 1) row = n - 1;  // tail lanes re-read the last row; their scores are masked below
-        const uint4 *src = reinterpret_cast<const uint4 *>(mem + (size_t)row * D) + h;
-        f32x4 acc[QT];
-#pragma unroll
-        for (int t = 0; t < QT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-        for (int s0 = 0; s0 < ksteps; s0 += LB) {
-            uint4 cur[LB];
-#pragma unroll
-            for (int u = 0; u < LB; ++u) cur[u] = src[(s0 + u < ksteps ? s0 + u : ksteps - 1) * 4];
-#pragma unroll
-            for (int u = 0; u < LB; ++u) {
-                if (s0 + u < ksteps) {
-                    const int ci = h + 4 * (s0 + u);
-                    const vec8 av = __builtin_bit_cast(vec8, cur[u]);
-                    const uint4 *qp = qrow + ((ci & ~15) | ((ci ^ r16) & 15));
-#pragma unroll
-                    for (int t = 0; t < QT; ++t) acc[t] = E::mfma16(av, __builtin_bit_cast(vec8, qp[t * tstride]), acc[t]);
-                }
-            }
-        }
-        const int64_t p0 = tile * 16 + 4 * h;
-        const float4 rn = *reinterpret_cast<const float4 *>(rnorm + p0);  // allocation is padded to 64 rows
-        const float rnv[4] = {rn.x, rn.y, rn.z, rn.w};
+    template <int QT>
+    static __device__ __forceinline__ void epilogue(const QState<QT> &, const Args &a, const View &gv,
+                                                    const TileLane &l, const float (&s)[QT][4]) {
+        const int lane = l.lane, h = l.h;
         int gj[4];  // live group index (< cap < 2^31), -1 past the live rows
 #pragma unroll
-        for (int j = 0; j < 4; ++j) gj[j] = p0 + j < n ? (int)(gord[p0 + j] - gv.ord0) : -1;
+        for (int j = 0; j < 4; ++j) gj[j] = l.p0() + j < l.n ? (int)(a.gord[l.p0() + j] - gv.ord0) : -1;
         // physical slot p holds age order p - head (mod cap); the ordinal does not care: groups are runs of slots too,
         // except across the physical wrap, where the two halves still carry one ordinal
 #pragma unroll
         for (int t = 0; t < QT; ++t) {
-            const int q = q0 + 16 * t + r16;
-            uint32_t *Fq = F + (size_t)q * gv.ng;
+            const int q = l.q0 + 16 * t + l.r16, Q = l.Q;
+            uint32_t *Fq = a.F + (size_t)q * gv.ng;
             // Runs of one group among this lane's 4 rows.  Interior runs go straight to their atomic.  The first and
             // the last run may go on in the lanes that hold the rows before / after (lane -+ 16, same query), so one
             // atomic per run of the whole 16-row tile: the lane where the run starts adds what the next lanes hold.
@@ -206,7 +151,7 @@ __global__ void __launch_bounds__(GS_THREADS)
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 if (gj[j] < 0) continue;
-                const uint32_t key = okey32(acc[t][j] * rnv[j]);
+                const uint32_t key = okey32(s[t][j]);
                 if (gj[j] != gL) {
                     if (gL >= 0) {  // the run before closes
                         if (closed == 0) {
@@ -253,7 +198,7 @@ __global__ void __launch_bounds__(GS_THREADS)
             }
         }
     }
-}
+};
 
 // ---- select ------------------------------------------------------------------------------------------------
 // Per query, the best take = min(M + 1, ng) groups by (fp32 max desc, group asc), as 64-bit composites
@@ -270,7 +215,7 @@ __global__ void __launch_bounds__(SEL_THREADS)
                      int *__restrict__ ccount) {
     constexpr int PER = SEL_SAMPLE / SEL_THREADS;
     const int q = blockIdx.x, lane = threadIdx.x;
-    const GView gv = group_view(d_total, cap, ring, gord);
+    const GroupView gv = group_view(d_total, cap, ring, gord);
     const int64_t ng = gv.ng;
     const uint32_t *Fq = F + (size_t)q * ng;
     const int cnt = (int)(ng < SEL_SAMPLE ? ng : SEL_SAMPLE);
@@ -298,7 +243,7 @@ __global__ void __launch_bounds__(CMP_THREADS)
     __shared__ unsigned long long lbuf[CMP_LCAP];
     __shared__ int lcnt, gbase;
     const int q = blockIdx.y, lane = threadIdx.x & 63;
-    const GView gv = group_view(d_total, cap, ring, gord);
+    const GroupView gv = group_view(d_total, cap, ring, gord);
     const int64_t ng = gv.ng;
     const uint32_t *Fq = F + (size_t)q * ng;
     const unsigned long long c0 = cut[q];
@@ -408,7 +353,7 @@ __global__ void __launch_bounds__(SEL_THREADS)
                               const int *__restrict__ ccount, const unsigned long long *__restrict__ cbuf,
                               int *__restrict__ cand_g, uint32_t *__restrict__ cand_k, int *__restrict__ cand_n) {
     const int q = blockIdx.x, tid = threadIdx.x;
-    const GView gv = group_view(d_total, cap, ring, gord);
+    const GroupView gv = group_view(d_total, cap, ring, gord);
     const int ng = (int)gv.ng;
     int *og = cand_g + (size_t)q * GCMAX;
     uint32_t *ok = cand_k + (size_t)q * GCMAX;
@@ -449,7 +394,7 @@ __global__ void __launch_bounds__(GF_THREADS)
     __shared__ double qn_sh;
     __shared__ int flag_sh;
     const int q = blockIdx.x, tid = threadIdx.x;
-    const GView gv = group_view(d_total, cap, ring, gord);
+    const GroupView gv = group_view(d_total, cap, ring, gord);
     const int C = cand_n[q];
     const int nc = C < M ? C : M;
     for (int i = tid; i < D / 8; i += GF_THREADS)
@@ -588,7 +533,7 @@ __global__ void __launch_bounds__(GR_THREADS)
     int any = 0;
     for (int i = tid; i < Q; i += GR_THREADS) any |= flags[i];
     if (!__syncthreads_or(any)) return;
-    const GView gv = group_view(d_total, cap, ring, gord);
+    const GroupView gv = group_view(d_total, cap, ring, gord);
     const int64_t n = gv.rv.n;
     if (tid == 0) {
         const int64_t per = (n + gridDim.x - 1) / gridDim.x;
@@ -706,7 +651,7 @@ struct GPlan : TopkGeom {
 
 GPlan group_plan(const vm_memory *m, int Q, int k) {
     GPlan p;
-    static_cast<TopkGeom &>(p) = vm_topk_geom(m, Q, k, GS_THREADS, GR_CHUNK);
+    static_cast<TopkGeom &>(p) = vm_topk_geom(m, Q, k, TS_THREADS, GR_CHUNK);
     int64_t tb = (m->cap + 256) / 256;
     p.tbl_blocks = (int)(tb < 1024 ? tb : 1024);
     WsBump ws;
@@ -749,17 +694,6 @@ int group_redo(vm_memory *m, const GPlan &p, const void *queries, int Q, int k, 
                               out_rows, m->gkey, out_keys, st);
 }
 
-template <int DT, int QT>
-int group_scan(vm_memory *m, const GPlan &p, const void *queries, int Q, uint32_t *F, hipStream_t st) {
-    const size_t lds = (size_t)QT * 16 * m->D * 2;
-    auto kern = group_scan_kernel<DT, QT>;
-    if (lds > 65536) VM_HIP(m->ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    kern<<<dim3(p.nbx, p.qgroups), GS_THREADS, lds, st>>>(m->rows, m->rnorm32, m->gord, (const uint16_t *)queries,
-                                                         m->d_total, m->cap, m->ring, m->D, Q, F);
-    VM_LAUNCH_CHECK(m->ctx);
-    return VM_OK;
-}
-
 template <int DT>
 int group_topk(vm_memory *m, const void *queries, int Q, int k, int use_min, double min_score, int score_mode,
                double *out_scores, int64_t *out_rows, int64_t *out_keys, int32_t *out_uncertified,
@@ -776,7 +710,7 @@ int group_topk(vm_memory *m, const void *queries, int Q, int k, int use_min, dou
         vm_prof_scope prof(ctx, VM_PROF_TOPK_SCAN, st);
         group_table_kernel<<<p.tbl_blocks, 256, 0, st>>>(m->d_total, m->cap, m->ring, m->gord, Q, first_o, F, nullptr, 0);
         VM_LAUNCH_CHECK(ctx);
-        const int rc = p.qt == 1 ? group_scan<DT, 1>(m, p, queries, Q, F, st) : group_scan<DT, 2>(m, p, queries, Q, F, st);
+        const int rc = vm_tile_scan<DT, GroupScan>(m, p, queries, Q, {m->gord, F}, st);
         if (rc != VM_OK) return rc;
     }
     {

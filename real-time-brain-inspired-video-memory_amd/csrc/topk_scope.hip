@@ -6,7 +6,8 @@
 //
 // The row ranking is vm_topk_cosine's, taken over the in-scope rows only.  Same two-stage, certified design as topk.hip
 // and topk_group.hip, with which it shares topk_select.h (key images, block-wide selection, gap
-// certificate, plan scaffold, argument check); a row is a group of one whose fp32 key is 0 when it is out of scope:
+// certificate, plan scaffold, argument check) and topk_tile_scan.h (the scan; ScopeScan below is its policy); a row is a
+// group of one whose fp32 key is 0 when it is out of scope:
 //   scan     : per 16-row tile the wave first reads the tile's 16 tags and tests them against the scopes of its query
 //              tile; a tile with no (row, query) pair in scope is skipped WITHOUT reading its rows (8 bytes per row
 //              instead of 2 D) and only zeroes its keys.  Otherwise fp32 MFMA scores with the list scan's numerics (the
@@ -19,16 +20,16 @@
 //              when the scope holds at most M rows, or when the exact k-th score clears the (M+1)-th IN-SCOPE fp32
 //              score / ||q|| by cert_eps(D), strictly.  Out-of-scope rows have key 0 and never reach the certificate
 //   redo     : flagged queries scored exhaustively over their in-scope rows, slices of age orders per block, stable
-//              top-k per slice, then the one merge of every redo (vm_topk_redo_merge, topk_exact.hip).  Flags and
+//              top-k per slice (vm_topk_redo_scan: the row redo's kernel with the tag predicate), then the one merge of
+//              every redo (vm_topk_redo_merge; both topk_exact.hip).  Flags and
 //              counts are read on the device; near-empty when nothing is flagged.
 // Every launch reads the row count from the device and sizes its grid from the capacity: capturable.
-#include "topk_select.h"
+#include "topk_tile_scan.h"
 
 #include <climits>
 
 namespace {
 
-constexpr int SS_THREADS = 256;    // scan
 constexpr int SEL_THREADS = 1024;  // cut and selection (one block per query)
 constexpr int SEL_SAMPLE = 16384;  // slots whose keys give each query's cut
 constexpr int SEL_CAP = 8192;      // rows at or above the cut a query keeps; more -> VM_FLAG_OVERFLOW
@@ -36,119 +37,57 @@ constexpr int CMP_THREADS = 256;   // compaction
 constexpr int CMP_LCAP = 2048;     // hits one compaction block gathers in LDS before it flushes them
 constexpr int SF_THREADS = 256;    // finalize
 constexpr int SCMAX = 128;         // candidates per query kept by the select (M + 1 <= 81)
-constexpr int SR_THREADS = 256;    // redo
-constexpr int SR_CHUNK = 1024;     // rows scored per selection pass of the redo
 constexpr int SKMAX = 64;
 
-__device__ __forceinline__ bool in_scope(int64_t tag, int64_t lo, int64_t hi) { return lo <= tag && tag <= hi; }
-// age order (0 = oldest) of the live row in physical slot p
-__device__ __forceinline__ int64_t order_of(const RingView &v, int64_t p) {
-    const int64_t o = p - v.head;
-    return o < 0 ? o + v.cap : o;
-}
-
 // ---- scan --------------------------------------------------------------------------------------------------
-// grid (row blocks, query groups of QT*16).  The MFMA part is topk_scan_kernel's (topk.hip): 16-row tiles in physical
-// order, the row tile the A operand straight from global memory, the query tile the B operand from chunk-swizzled LDS,
-// acc[t][j] = <row tile*16 + 4h + j, query q0 + 16t + r16>, score = acc * rnorm32.  F[q * fstride + slot] = key or 0.
-template <int DT, int QT>
-__global__ void __launch_bounds__(SS_THREADS)
-    scope_scan_kernel(const uint16_t *__restrict__ mem, const float *__restrict__ rnorm,
-                      const int64_t *__restrict__ tag, const uint16_t *__restrict__ queries,
-                      const int64_t *__restrict__ scope_lo, const int64_t *__restrict__ scope_hi,
-                      const int64_t *__restrict__ d_total, int64_t cap, int ring, int D, int Q, int64_t fstride,
-                      uint32_t *__restrict__ F) {
-    using E = vm_elem<DT>;
-    using vec8 = typename E::vec8;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    uint4 *qlds = reinterpret_cast<uint4 *>(smem);
-    __shared__ int64_t slo[QT * 16], shi[QT * 16];
-    const int chunks = D / 8;
-    constexpr int nw = SS_THREADS / 64;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int r16 = lane & 15, h = lane >> 4;
-    const int q0 = blockIdx.y * (QT * 16);
-    for (int idx = tid; idx < QT * 16 * chunks; idx += SS_THREADS) {
-        const int q = idx / chunks, ci = idx - q * chunks;
-        uint4 v = make_uint4(0, 0, 0, 0);
-        if (q0 + q < Q) v = reinterpret_cast<const uint4 *>(queries + (size_t)(q0 + q) * D)[ci];
-        qlds[q * chunks + ((ci & ~15) | ((ci ^ q) & 15))] = v;
+// The scoped policy of the tile scan (topk_tile_scan.h): four keys per lane, F[q * fstride + slot] = the order-preserving
+// key of the fp32 score, or 0 when the row is out of the query's scope or past the live rows.
+struct ScopeScan {
+    struct Args {
+        const int64_t *tag, *scope_lo, *scope_hi;
+        int64_t fstride;
+        uint32_t *F;
+    };
+    template <int QT>
+    struct QState {  // 16-byte aligned: the tag pre-test reads a lane's four scopes with two 16-byte LDS loads per array
+        alignas(16) int64_t lo[QT * 16], hi[QT * 16];
+    };
+    struct View {};
+    template <class QS>
+    static __device__ __forceinline__ void load_query(QS &qs, const Args &a, int i, int q, bool live) {
+        qs.lo[i] = live ? a.scope_lo[q] : LLONG_MAX;  // queries past Q have the empty scope
+        qs.hi[i] = live ? a.scope_hi[q] : LLONG_MIN;
     }
-    if (tid < QT * 16) {  // queries past Q have the empty scope
-        const bool live = q0 + tid < Q;
-        slo[tid] = live ? scope_lo[q0 + tid] : LLONG_MAX;
-        shi[tid] = live ? scope_hi[q0 + tid] : LLONG_MIN;
+    static __device__ __forceinline__ View view(const Args &, const RingView &) { return {}; }
+    template <int QT>
+    static __device__ __forceinline__ bool skip_tile(const QState<QT> &qs, const Args &a, const TileLane &l) {
+        if (tile_in_scope<QT>(a.tag, qs.lo, qs.hi, l)) return false;
+#pragma unroll
+        for (int t = 0; t < QT; ++t) {  // a skipped tile only zeroes its keys
+            const int q = l.q0 + 16 * t + l.r16;
+            if (q < l.Q) *reinterpret_cast<uint4 *>(a.F + (size_t)q * a.fstride + l.p0()) = make_uint4(0, 0, 0, 0);
+        }
+        return true;
     }
-    __syncthreads();
-    const RingView rv = ring_view(*d_total, cap, ring);
-    const int64_t n = rv.n;
-    const int64_t ntiles = (n + 15) / 16;
-    const int ksteps = D / 32;
-    constexpr int LB = 8;
-    const uint4 *qrow = qlds + r16 * chunks;
-    const int tstride = 16 * chunks;
-    const int64_t tile_step = (int64_t)gridDim.x * nw;
-    for (int64_t tile = (int64_t)blockIdx.x * nw + wave; tile < ntiles; tile += tile_step) {
-        const int64_t p0 = tile * 16 + 4 * h;  // this lane's 4 slots (below cap_pad: the columns are padded to 64 rows)
-        // the tile's 16 tags before any row data: lane (r16, h) tests row r16 against queries 4h .. 4h+3 of each sub-tile
-        {
-            const int64_t trow = tile * 16 + r16;
-            bool hit = false;
-            if (trow < n) {
-                const int64_t tg = tag[trow];
-#pragma unroll
-                for (int t = 0; t < QT; ++t)
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) hit |= in_scope(tg, slo[16 * t + 4 * h + c], shi[16 * t + 4 * h + c]);
-            }
-            if (__ballot(hit) == 0ull) {  // wave-uniform: nothing of this tile is wanted; its rows are not read
-#pragma unroll
-                for (int t = 0; t < QT; ++t) {
-                    const int q = q0 + 16 * t + r16;
-                    if (q < Q) *reinterpret_cast<uint4 *>(F + (size_t)q * fstride + p0) = make_uint4(0, 0, 0, 0);
-                }
-                continue;
-            }
-        }
-        int64_t row = tile * 16 + r16;
-        if (row > n - 1) row = n - 1;  // tail lanes re-read the last row; their scores are masked below
-        const uint4 *src = reinterpret_cast<const uint4 *>(mem + (size_t)row * D) + h;
-        f32x4 acc[QT];
-#pragma unroll
-        for (int t = 0; t < QT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-        for (int s0 = 0; s0 < ksteps; s0 += LB) {
-            uint4 cur[LB];
-#pragma unroll
-            for (int u = 0; u < LB; ++u) cur[u] = src[(s0 + u < ksteps ? s0 + u : ksteps - 1) * 4];
-#pragma unroll
-            for (int u = 0; u < LB; ++u) {
-                if (s0 + u < ksteps) {
-                    const int ci = h + 4 * (s0 + u);
-                    const vec8 av = __builtin_bit_cast(vec8, cur[u]);
-                    const uint4 *qp = qrow + ((ci & ~15) | ((ci ^ r16) & 15));
-#pragma unroll
-                    for (int t = 0; t < QT; ++t) acc[t] = E::mfma16(av, __builtin_bit_cast(vec8, qp[t * tstride]), acc[t]);
-                }
-            }
-        }
-        const float4 rn = *reinterpret_cast<const float4 *>(rnorm + p0);
-        const float rnv[4] = {rn.x, rn.y, rn.z, rn.w};
+    template <int QT>
+    static __device__ __forceinline__ void epilogue(const QState<QT> &qs, const Args &a, const View &,
+                                                    const TileLane &l, const float (&s)[QT][4]) {
         int64_t tj[4];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) tj[j] = tag[p0 + j];
+        for (int j = 0; j < 4; ++j) tj[j] = a.tag[l.p0() + j];
 #pragma unroll
         for (int t = 0; t < QT; ++t) {
-            const int q = q0 + 16 * t + r16;
-            if (q >= Q) continue;
-            const int64_t lo = slo[16 * t + r16], hi = shi[16 * t + r16];
+            const int q = l.q0 + 16 * t + l.r16;
+            if (q >= l.Q) continue;
+            const int64_t lo = qs.lo[16 * t + l.r16], hi = qs.hi[16 * t + l.r16];
             uint32_t key[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j)
-                key[j] = (p0 + j < n && in_scope(tj[j], lo, hi)) ? okey32(acc[t][j] * rnv[j]) : 0u;
-            *reinterpret_cast<uint4 *>(F + (size_t)q * fstride + p0) = make_uint4(key[0], key[1], key[2], key[3]);
+                key[j] = (l.p0() + j < l.n && in_scope(tj[j], lo, hi)) ? okey32(s[t][j]) : 0u;
+            *reinterpret_cast<uint4 *>(a.F + (size_t)q * a.fstride + l.p0()) = make_uint4(key[0], key[1], key[2], key[3]);
         }
     }
-}
+};
 
 // ---- select ------------------------------------------------------------------------------------------------
 // composites (topk_select.h) of key and age order: ties at one key go to the older row
@@ -350,83 +289,6 @@ __global__ void scope_fill_flags_kernel(int32_t *__restrict__ flags, int Q) {
     if (i < Q) flags[i] = 1;
 }
 
-// grid = nblk row blocks; every block walks all Q flags and, for each flagged query, scores the in-scope rows of its
-// contiguous slice of age orders exactly and keeps the slice's stable top-k:
-// part[(block * Q + q) * k + i] = {score fp64, age order int64}.  A chunk with no in-scope row costs its tags only.
-template <int DT>
-__global__ void __launch_bounds__(SR_THREADS)
-    scope_redo_scan_kernel(const uint16_t *__restrict__ queries, const uint16_t *__restrict__ rows,
-                           const double *__restrict__ norm64, const int64_t *__restrict__ tag,
-                           const int64_t *__restrict__ scope_lo, const int64_t *__restrict__ scope_hi,
-                           const int64_t *__restrict__ d_total, int64_t cap, int ring, int D, int Q, int k,
-                           const int32_t *__restrict__ flags, double *__restrict__ part_s,
-                           int64_t *__restrict__ part_o) {
-    extern __shared__ __attribute__((aligned(16))) char sr_dyn[];
-    uint16_t *ql = reinterpret_cast<uint16_t *>(sr_dyn);  // [D]
-    __shared__ double sc[SR_CHUNK];
-    __shared__ uint8_t live[SR_CHUNK];
-    __shared__ double run_s[SKMAX], new_s[SKMAX], red_s[SR_THREADS / 64];
-    __shared__ int64_t run_o[SKMAX], new_o[SKMAX], red_o[SR_THREADS / 64];
-    __shared__ double qnorm_sh;
-    const int tid = threadIdx.x;
-    int any = 0;
-    for (int i = tid; i < Q; i += SR_THREADS) any |= flags[i];
-    if (!__syncthreads_or(any)) return;
-    const RingView rv = ring_view(*d_total, cap, ring);
-    const int64_t per = (rv.n + gridDim.x - 1) / gridDim.x;
-    const int64_t lo = (int64_t)blockIdx.x * per;
-    const int64_t hi = lo + per < rv.n ? lo + per : rv.n;
-    for (int q = 0; q < Q; ++q) {
-        if (flags[q] == 0) continue;  // uniform
-        __syncthreads();
-        for (int i = tid; i < D / 8; i += SR_THREADS)
-            reinterpret_cast<uint4 *>(ql)[i] = reinterpret_cast<const uint4 *>(queries + (size_t)q * D)[i];
-        if (tid < k) {
-            run_s[tid] = -INFINITY;
-            run_o[tid] = -1;
-        }
-        __syncthreads();
-        if (tid == 0) qnorm_sh = __dsqrt_rn(ref_sumsq<DT>(ql, D));
-        __syncthreads();
-        const double qn = qnorm_sh;
-        const int64_t slo = scope_lo[q], shi = scope_hi[q];
-        for (int64_t c0 = lo; c0 < hi; c0 += SR_CHUNK) {
-            const int cn = (int)(hi - c0 < SR_CHUNK ? hi - c0 : SR_CHUNK);
-            int mine = 0;
-            for (int i = tid; i < cn; i += SR_THREADS) {
-                const int64_t p = slot_of(rv, c0 + i);
-                const bool in = in_scope(tag[p], slo, shi);
-                live[i] = in ? 1 : 0;
-                if (in) {
-                    sc[i] = ref_cosine(ref_dot<DT>(ql, rows + (size_t)p * D, D), qn, norm64[p]);
-                    mine = 1;
-                }
-            }
-            if (!__syncthreads_or(mine)) continue;  // uniform: nothing of this chunk is in scope
-            block_select<SR_THREADS>(cn + k, k,
-                                     [&](int i, double &v, int64_t &o) {
-                                         if (i < cn) {
-                                             v = sc[i];
-                                             o = live[i] ? c0 + i : -1;
-                                         } else {
-                                             v = run_s[i - cn];
-                                             o = run_o[i - cn];
-                                         }
-                                     },
-                                     new_s, new_o, red_s, red_o);
-            if (tid < k) {
-                run_s[tid] = new_s[tid];
-                run_o[tid] = new_o[tid];
-            }
-            __syncthreads();
-        }
-        if (tid < k) {
-            part_s[((size_t)blockIdx.x * Q + q) * k + tid] = run_s[tid];
-            part_o[((size_t)blockIdx.x * Q + q) * k + tid] = run_o[tid];
-        }
-    }
-}
-
 // ---- host --------------------------------------------------------------------------------------------------
 struct SPlan : TopkGeom {
     int64_t fstride;
@@ -435,7 +297,7 @@ struct SPlan : TopkGeom {
 
 SPlan scope_plan(const vm_memory *m, int Q, int k) {
     SPlan p;
-    static_cast<TopkGeom &>(p) = vm_topk_geom(m, Q, k, SS_THREADS, SR_CHUNK);
+    static_cast<TopkGeom &>(p) = vm_topk_geom(m, Q, k, TS_THREADS, VM_REDO_CHUNK_SCOPED);
     p.fstride = (m->cap + 63) / 64 * 64;  // the columns' padding: a tail tile writes its 16 keys
     WsBump ws;
     ws.take((size_t)Q * (size_t)p.fstride * 4);  // F at offset 0: [Q][slot] fp32 keys
@@ -460,7 +322,6 @@ int scope_check(vm_memory *m, const void *queries, int Q, int k, const int64_t *
                          VM_ERR_INVALID, score_mode, workspace, workspace_bytes, scope_plan(m, Q, k).total, who);
 }
 
-template <int DT>
 int scope_redo(vm_memory *m, const SPlan &p, const void *queries, int Q, int k, const int64_t *scope_lo,
                const int64_t *scope_hi, int use_min, double min_score, int score_mode, int64_t row_stride,
                int64_t row_offset, double *out_scores, int64_t *out_rows, char *ws, hipStream_t st) {
@@ -469,26 +330,9 @@ int scope_redo(vm_memory *m, const SPlan &p, const void *queries, int Q, int k, 
     const int32_t *flags = (const int32_t *)(ws + p.off_flags);
     double *part_s = (double *)(ws + p.off_ps);
     int64_t *part_o = (int64_t *)(ws + p.off_po);
-    scope_redo_scan_kernel<DT><<<p.nblk, SR_THREADS, (size_t)m->D * 2, st>>>(
-        (const uint16_t *)queries, m->rows, m->norm64, m->tag, scope_lo, scope_hi, m->d_total, m->cap, m->ring, m->D, Q,
-        k, flags, part_s, part_o);
-    VM_LAUNCH_CHECK(ctx);
+    if (int rc = vm_topk_redo_scan(m, queries, Q, k, scope_lo, scope_hi, flags, p.nblk, part_s, part_o, st)) return rc;
     return vm_topk_redo_merge(m, part_s, part_o, p.nblk, Q, k, flags, use_min, min_score, score_mode, row_stride,
                               row_offset, out_scores, out_rows, nullptr, nullptr, st);
-}
-
-template <int DT, int QT>
-int scope_scan(vm_memory *m, const SPlan &p, const void *queries, int Q, const int64_t *scope_lo,
-               const int64_t *scope_hi, uint32_t *F, hipStream_t st) {
-    const size_t lds = (size_t)QT * 16 * m->D * 2;
-    auto kern = scope_scan_kernel<DT, QT>;
-    if (lds > 65536 - 1024)
-        VM_HIP(m->ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    kern<<<dim3(p.nbx, p.qgroups), SS_THREADS, lds, st>>>(m->rows, m->rnorm32, m->tag, (const uint16_t *)queries,
-                                                         scope_lo, scope_hi, m->d_total, m->cap, m->ring, m->D, Q,
-                                                         p.fstride, F);
-    VM_LAUNCH_CHECK(m->ctx);
-    return VM_OK;
 }
 
 template <int DT>
@@ -505,8 +349,7 @@ int scope_topk(vm_memory *m, const void *queries, int Q, int k, const int64_t *s
     int *flags = (int *)(ws + p.off_flags);
     {
         vm_prof_scope prof(ctx, VM_PROF_TOPK_SCAN, st);
-        const int rc = p.qt == 1 ? scope_scan<DT, 1>(m, p, queries, Q, scope_lo, scope_hi, F, st)
-                                 : scope_scan<DT, 2>(m, p, queries, Q, scope_lo, scope_hi, F, st);
+        const int rc = vm_tile_scan<DT, ScopeScan>(m, p, queries, Q, {m->tag, scope_lo, scope_hi, p.fstride, F}, st);
         if (rc != VM_OK) return rc;
     }
     {
@@ -527,7 +370,7 @@ int scope_topk(vm_memory *m, const void *queries, int Q, int k, const int64_t *s
             out_query_flags);
         VM_LAUNCH_CHECK(ctx);
     }
-    return scope_redo<DT>(m, p, queries, Q, k, scope_lo, scope_hi, use_min, min_score, score_mode, row_stride,
+    return scope_redo(m, p, queries, Q, k, scope_lo, scope_hi, use_min, min_score, score_mode, row_stride,
                           row_offset, out_scores, out_rows, ws, st);
 }
 
@@ -569,8 +412,6 @@ extern "C" int vm_topk_cosine_scoped_exact(vm_memory *m, const void *queries, in
     char *ws = (char *)workspace;
     scope_fill_flags_kernel<<<(Q + 255) / 256, 256, 0, st>>>((int32_t *)(ws + p.off_flags), Q);
     VM_LAUNCH_CHECK(ctx);
-    return vm_by_dtype(m, [&](auto dt) {
-        return scope_redo<decltype(dt)::value>(m, p, queries, Q, k, scope_lo, scope_hi, use_min_score, min_score,
-                                               score_mode, row_stride, row_offset, out_scores, out_rows, ws, st);
-    });
+    return scope_redo(m, p, queries, Q, k, scope_lo, scope_hi, use_min_score, min_score, score_mode, row_stride,
+                      row_offset, out_scores, out_rows, ws, st);
 }

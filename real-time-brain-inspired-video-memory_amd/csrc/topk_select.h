@@ -133,24 +133,34 @@ struct WsBump {
     }
 };
 
-// the geometry both searches share
-struct TopkGeom {
+// The grid of a tile scan (topk_tile_scan.h): grid x = row blocks of scan_threads / 64 waves, one 16-row tile per wave
+// and step, at most 8 blocks per CU; grid y = query groups of qt 16-query tiles.  `tiles` is the caller's own count of
+// 16-row tiles of the capacity.
+struct ScanGeom {
+    int qt;       // 16-query tiles per scan block
+    int qgroups;  // scan grid y
+    int nbx;      // scan grid x
+};
+inline ScanGeom vm_scan_geom(const vm_memory *m, int Q, int64_t tiles, int scan_threads) {
+    ScanGeom g;
+    g.qt = Q <= 16 ? 1 : 2;
+    g.qgroups = (Q + 16 * g.qt - 1) / (16 * g.qt);
+    const int64_t nbx = (tiles + scan_threads / 64 - 1) / (scan_threads / 64);
+    const int64_t lim = (int64_t)m->ctx->num_cus * 8;
+    g.nbx = (int)(nbx < lim ? (nbx < 1 ? 1 : nbx) : lim);
+    return g;
+}
+
+// the geometry the grouped and the scoped search share
+struct TopkGeom : ScanGeom {
     int M;           // candidates re-scored exactly per query; the (M + 1)-th bounds the rest
-    int qt;          // 16-query tiles per scan block
-    int qgroups;     // scan grid y
-    int nbx;         // scan grid x
     int nblk;        // redo row blocks
     int cmp_slices;  // compaction grid x
 };
 inline TopkGeom vm_topk_geom(const vm_memory *m, int Q, int k, int scan_threads, int redo_chunk) {
     TopkGeom g;
+    static_cast<ScanGeom &>(g) = vm_scan_geom(m, Q, (m->cap + 15) / 16, scan_threads);
     g.M = k + (k / 4 > 8 ? k / 4 : 8);  // slack: near-ties between rank k and rank M are certified by the gap
-    g.qt = Q <= 16 ? 1 : 2;
-    g.qgroups = (Q + 16 * g.qt - 1) / (16 * g.qt);
-    const int64_t tiles = (m->cap + 15) / 16;
-    const int64_t nbx = (tiles + scan_threads / 64 - 1) / (scan_threads / 64);
-    const int64_t lim = (int64_t)m->ctx->num_cus * 8;
-    g.nbx = (int)(nbx < lim ? (nbx < 1 ? 1 : nbx) : lim);
     g.nblk = vm_topk_redo_blocks(m, redo_chunk);
     const int64_t sl = (m->cap + 8191) / 8192;
     g.cmp_slices = (int)(sl < 1 ? 1 : (sl > 64 ? 64 : sl));

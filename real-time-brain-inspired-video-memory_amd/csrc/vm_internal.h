@@ -54,6 +54,36 @@ __host__ __device__ inline int64_t slot_of(const RingView &v, int64_t o) {
     return p >= v.cap ? p - v.cap : p;
 }
 
+// age order (0 = oldest) of the live row in physical slot p
+__host__ __device__ inline int64_t order_of(const RingView &v, int64_t p) {
+    const int64_t o = p - v.head;
+    return o < 0 ? o + v.cap : o;
+}
+
+// tagged memories: a row is in a query's scope when its tag lies in the inclusive range [lo, hi]
+__host__ __device__ inline bool in_scope(int64_t tag, int64_t lo, int64_t hi) { return lo <= tag && tag <= hi; }
+
+// grouped memories: the live rows + the ordinal of the oldest live group + the number of live groups, from the device
+// counters.  Groups are runs of equal ordinals (gord above), so live group g = ordinal - ord0, 0 <= g < ng.
+struct GroupView {
+    RingView rv;
+    int64_t ord0, ng;
+};
+__device__ __forceinline__ GroupView group_view(const RingView &rv, const int64_t *gord) {
+    GroupView g;
+    g.rv = rv;
+    g.ord0 = 0;
+    g.ng = 0;
+    if (rv.n > 0) {
+        g.ord0 = gord[rv.head];
+        g.ng = gord[slot_of(rv, rv.n - 1)] - g.ord0 + 1;
+    }
+    return g;
+}
+__device__ __forceinline__ GroupView group_view(const int64_t *d_total, int64_t cap, int ring, const int64_t *gord) {
+    return group_view(ring_view(*d_total, cap, ring), gord);
+}
+
 // The rows whose every score the cut cascade keeps in its first, DENSE pass: the NEWEST stored rows (at most 4,095 of
 // them, a whole number of 256-row panels plus the ragged end).  New rows are what a video's current frames resemble
 // most - a scene lasts thousands of frames - so the first cut is high and the later passes emit little; with the
@@ -81,6 +111,15 @@ __host__ __device__ inline DenseRange dense_newest(const RingView &rv) {
 // ---- exhaustive redo (topk_exact.hip), shared by the row, grouped and scoped searches -------------------------------
 // row blocks of a redo scan that scores `chunk` rows per selection pass: the one definition of nblk
 int vm_topk_redo_blocks(const vm_memory *m, int chunk);
+// rows scored per selection pass by the redo scan of the row search and of the scoped search
+constexpr int VM_REDO_CHUNK = 2048, VM_REDO_CHUNK_SCOPED = 1024;
+// The redo scan of rows: for every flagged query, block b of nblk scores its slice of age orders exactly and leaves the
+// slice's stable top-k in part_s / part_o [nblk][Q][k].  scope_lo == null: every live row, nblk =
+// vm_topk_redo_blocks(m, VM_REDO_CHUNK); otherwise the rows whose tag lies in the query's [scope_lo, scope_hi] only,
+// nblk = vm_topk_redo_blocks(m, VM_REDO_CHUNK_SCOPED).  vm_topk_redo_merge follows.
+int vm_topk_redo_scan(vm_memory *m, const void *queries, int Q, int k, const int64_t *scope_lo,
+                      const int64_t *scope_hi, const int32_t *flags, int nblk, double *part_s, int64_t *part_o,
+                      hipStream_t st);
 // Merge of the redo scans' slice winners, part_s / part_o [nblk][Q][k] = {score, age order}, for the flagged queries:
 // stable top-k, score mapping, min_score, row id = (base + order) * row_stride + row_offset.  gkey / out_keys: null, or
 // the grouped search's key column and key output.

@@ -1,7 +1,7 @@
 """The range search against the two yardsticks the memory had before it, event-timed and warm, the variants alternating
 in one process.
 
-  python tools/range_probe.py [--rounds 3] [--out profiles/range_probe.json] [--quick]
+  python tools/range_probe.py [--rounds 3] [--out profiles/range_probe.json] [--quick] [--lib other/libvidmem.so]
 
 Memories: 1 M x 768 fp16 and 1 M x 1024 bf16, clusters of 16 rows, tagged as 16 contiguous sources.  Q in {1, 16, 64};
 queries = stored rows plus 0.1 noise.  Thresholds: taken from the exact scores of query 0 so that it has 16, 1,000 and
@@ -26,6 +26,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
 import vidmem  # noqa: E402, F401
+import vidmem._lib  # noqa: E402
 from vidmem.memory import EmbeddingMemory, _tensor_from_ptr  # noqa: E402
 
 from group_probe import TD, clustered  # noqa: E402
@@ -121,7 +122,10 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--out", default=None)
     ap.add_argument("--quick", action="store_true", help="the fp16 memory and Q in {1, 16} only")
+    ap.add_argument("--lib", default=None, help="another build of libvidmem.so to time (an A/B against a parent commit)")
     a = ap.parse_args()
+    if a.lib:
+        vidmem._lib.LIB_PATH = os.path.abspath(a.lib)
     qs = (1, 16) if a.quick else (1, 16, 64)
     recs = run_memory(1 << 20, 768, "f16", qs, a.rounds)
     if not a.quick:
