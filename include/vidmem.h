@@ -507,6 +507,43 @@ int vm_topk_cosine_scoped_exact(vm_memory *mem, const void *queries, int Q, int 
                                 const int64_t *scope_hi, int use_min_score, double min_score, int score_mode,
                                 int64_t row_stride, int64_t row_offset, double *out_scores, int64_t *out_rows,
                                 void *workspace, size_t workspace_bytes, void *stream);
+/* Scoped grouped top-k: the k best GROUPS of a tagged AND grouped memory among the rows IN SCOPE - "the k best scenes of
+ * video 7 between minute 10 and minute 20".  scope_lo / scope_hi: device int64 [Q], both required, inclusive tag ranges
+ * by vm_topk_cosine_scoped's rule (row r is in query q's scope iff scope_lo[q] <= tag[r] <= scope_hi[q]).
+ * Groups are what they are everywhere else: maximal runs of equal group ordinals over ALL live rows.  A scope does not
+ * redefine them: an out-of-scope row between two in-scope rows of one group does not split the group, and removing rows
+ * from view never merges two groups.
+ * Result for query q: take the exhaustive row ranking of vm_topk_cosine_scoped (in-scope live rows only, the raw
+ * reference cosine mapped by score_mode, the strict > min_score filter, raw score descending, row id ascending), keep the
+ * first row of each group, return the first k.  Equivalently: a group's score is the exact max over its IN-SCOPE rows,
+ * its representative the lowest in-scope row id reaching that max; a group with no in-scope row does not exist for this
+ * query.  out_scores [Q,k] are the reference's fp64 values bit for bit, out_rows [Q,k] row ids (no stride or offset, as
+ * in vm_topk_cosine_grouped), out_keys [Q,k] int64 (may be NULL) the representatives' group keys; 0.0 / -1 / -1 padded.
+ * Identities: with every scope [INT64_MIN, INT64_MAX] the three outputs equal vm_topk_cosine_grouped's; on a memory
+ * where every row is its own group, scores and rows equal vm_topk_cosine_scoped's with row_stride 1 and row_offset 0.
+ * ALWAYS the exhaustive answer, as with both parents: an fp32 MFMA scan of the 16-row tiles that hold an in-scope row
+ * reduces the in-scope scores to per-group fp32 maxima, the in-scope rows of the best k + slack groups are re-scored
+ * exactly, and a query whose result cannot be proven (vm_topk_cosine's bound 2 (D + 8) 2^-24 against the fp32 max over
+ * the in-scope rows of the best group that was not re-scored, or candidate groups of more than 4096 rows together - all
+ * their rows count, in scope or not) is counted in *out_uncertified (may be NULL), marked in out_query_flags [Q]
+ * (vm_topk_flag; may be NULL) and redone exhaustively over its in-scope rows on the device inside the same call.  So is
+ * every query whose norm, or a stored row's norm, is neither 0 nor in [2^-40, 2^40] (vm_memory_create).
+ * No host read-back, no allocation, no synchronisation; the row count and the scopes are read on the device and the
+ * grids are sized from the capacity: capturable, and a replay after an append or with rewritten scopes sees the new
+ * state.  1 <= k <= 64, Q >= 1; VM_ERR_INVALID on a memory that is not both tagged and grouped
+ * (vm_memory_create_tagged with grouped != 0), on a NULL scope array and on k outside its range; VM_ERR_NOMEM on an
+ * undersized workspace, before any launch.
+ * Workspace: vm_topk_grouped_scoped_workspace_bytes (4 x Q x capacity bytes of per-group maxima plus a few MB). */
+size_t vm_topk_grouped_scoped_workspace_bytes(const vm_memory *mem, int Q, int k);
+int vm_topk_cosine_grouped_scoped(vm_memory *mem, const void *queries, int Q, int k, const int64_t *scope_lo,
+                                  const int64_t *scope_hi, int use_min_score, double min_score, int score_mode,
+                                  double *out_scores, int64_t *out_rows, int64_t *out_keys, int32_t *out_uncertified,
+                                  int32_t *out_query_flags, void *workspace, size_t workspace_bytes, void *stream);
+/* The same contract, exhaustive only: every in-scope pair scored exactly (slow; tests, and a checker). */
+int vm_topk_cosine_grouped_scoped_exact(vm_memory *mem, const void *queries, int Q, int k, const int64_t *scope_lo,
+                                        const int64_t *scope_hi, int use_min_score, double min_score, int score_mode,
+                                        double *out_scores, int64_t *out_rows, int64_t *out_keys, void *workspace,
+                                        size_t workspace_bytes, void *stream);
 /* Range search: EVERY row above a threshold, in time order - "which frames of this video show X?" has no k.  The
  * threshold is the reference's own notion of relevance (`vector.similarity.cosine(...) > 0.3`,
  * src/pipeline/retriever_hybrid.py:296-298; `>= compression_threshold`, :494-504); this call returns all of what passes

@@ -58,7 +58,8 @@ class HipHybridMixin:
         ``embedder``: what embeds the questions (e.g. text.HipTextEmbedder); None = ``self.embedder``.  ValueError when
         it states an ``out_dim`` other than ``memory.dim``.  ``distinct=True``: one hit per chunk (grouped memory).
         ``scope``: an inclusive tag range (memory.scope_of) the vector leg is restricted to (tagged memory; the
-        reference's ``{graph_uuid: $graph_uuid}``, retriever_hybrid.py:295); not together with ``distinct``."""
+        reference's ``{graph_uuid: $graph_uuid}``, retriever_hybrid.py:295); together with ``distinct`` it needs a memory that
+        provides ``topk_grouped_scoped`` (a grouped and tagged EmbeddingMemory): one hit per chunk of the scope."""
         self._hip = HipVectorSearch(memory, self.embedder if embedder is None else embedder, self.config,
                                     min_score=min_score, score_mode=score_mode, splitter=splitter, distinct=distinct,
                                     scope=scope)

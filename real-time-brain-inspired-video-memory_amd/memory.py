@@ -279,6 +279,9 @@ class EmbeddingMemory:
         self._gws = None            # grouped top-k workspace (vm_topk_grouped_workspace_bytes), grown on demand
         self._gflags = None         # per-query flags of the last grouped call (device int32)
         self._guncert = None        # queries the grouped fast path could not certify (device int32, accumulates)
+        self._gsws = None           # scoped grouped top-k workspace (vm_topk_grouped_scoped_workspace_bytes)
+        self._gsflags = None        # per-query flags of the last scoped grouped call (device int32)
+        self._gsuncert = None       # queries the scoped grouped fast path could not certify (device int32, accumulates)
         self._nscratch = None       # buffers of the gated append (NoveltyScratch), grown on demand
         self._escratch = None       # buffers of erase (EraseScratch), made on demand
         self._rscratch = None       # buffers of the range search (RangeScratch), grown on demand
@@ -891,6 +894,63 @@ class EmbeddingMemory:
         sc.record_stream(torch.cuda.current_stream())
         return scores, rows
 
+    def prepare_topk_grouped_scoped(self, Q: int, k: int) -> None:
+        """Size the scoped grouped top-k workspace for (Q, k) now (before a graph capture: a capture must not allocate)."""
+        need = int(self.L.vm_topk_grouped_scoped_workspace_bytes(self.handle, int(Q), int(k)))
+        if self._gsws is None or self._gsws.numel() < need:
+            self._gsws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
+        if self._gsflags is None or self._gsflags.numel() < Q:
+            self._gsflags = torch.zeros(max(Q, 1), dtype=torch.int32, device=self.device)
+        if self._gsuncert is None:
+            self._gsuncert = torch.zeros(1, dtype=torch.int32, device=self.device)
+
+    def topk_grouped_scoped(self, queries, k: int, scope, min_score: Optional[float] = None,
+                            score_mode: int = _lib.VM_SCORE_RAW, exact: bool = False
+                            ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """-> (scores [Q,k] float64, rows [Q,k] int64, keys [Q,k] int64): the k best GROUPS of a tagged, grouped memory
+        among the rows whose tag lies in the query's scope - one hit per event within a video or a time window.
+        ``scope`` is ``topk_scoped``'s: one ``(lo, hi)`` for all queries, a sequence of Q pairs, or an int64 ``[Q, 2]``
+        tensor (``scope_of`` builds the range of a video or of a time window of it).
+
+        The exhaustive row ranking of ``topk_scoped`` (in-scope rows only; score desc, row asc; score mapping and
+        > min_score filter) with only the first row of each group kept: a group scores the exact max over its IN-SCOPE
+        rows, ``rows`` holds the lowest in-scope row id reaching it, ``keys`` its group key; -1 / 0.0 / -1 padded.  Groups
+        are the memory's own (runs over all live rows): a window that cuts an event in two neither splits it nor merges
+        its neighbours, and a group with no in-scope row is not returned.  Always the exhaustive answer: the fp32 fast
+        path redoes the queries it cannot certify on the device, in the same call (csrc/topk_group_scope.hip).
+        ``exact=True`` scores every in-scope pair exactly (slow).  1 <= k <= 64.  The per-query flags of the last call
+        (why a query was redone, vm_topk_flag) are in ``last_group_scope_flags``."""
+        if not (self.grouped and self.tagged):
+            raise ValueError("topk_grouped_scoped needs a grouped and tagged memory "
+                             "(EmbeddingMemory(..., grouped=True, tagged=True))")
+        if not 1 <= int(k) <= 64:
+            raise ValueError(f"scoped grouped top-k supports 1 <= k <= 64, got {k}")
+        q = self._as_rows(queries)
+        Q = q.shape[0]
+        sc = self._scope_tensor(scope, Q)
+        self.prepare_topk_grouped_scoped(Q, k)
+        scores = torch.empty((Q, k), dtype=torch.float64, device=self.device)
+        rows = torch.empty((Q, k), dtype=torch.int64, device=self.device)
+        keys = torch.empty((Q, k), dtype=torch.int64, device=self.device)
+        st = _lib.current_stream_ptr()
+        use_min = 0 if min_score is None else 1
+        ms = 0.0 if min_score is None else float(min_score)
+        lo, hi = C.c_void_p(sc[0].data_ptr()), C.c_void_p(sc[1].data_ptr())
+        if exact:
+            self.ctx.check(self.L.vm_topk_cosine_grouped_scoped_exact(
+                self.handle, C.c_void_p(q.data_ptr()), Q, int(k), lo, hi, use_min, ms, int(score_mode),
+                C.c_void_p(scores.data_ptr()), C.c_void_p(rows.data_ptr()), C.c_void_p(keys.data_ptr()),
+                C.c_void_p(self._gsws.data_ptr()), self._gsws.numel(), st))
+        else:
+            self.ctx.check(self.L.vm_topk_cosine_grouped_scoped(
+                self.handle, C.c_void_p(q.data_ptr()), Q, int(k), lo, hi, use_min, ms, int(score_mode),
+                C.c_void_p(scores.data_ptr()), C.c_void_p(rows.data_ptr()), C.c_void_p(keys.data_ptr()),
+                C.c_void_p(self._gsuncert.data_ptr()), C.c_void_p(self._gsflags.data_ptr()),
+                C.c_void_p(self._gsws.data_ptr()), self._gsws.numel(), st))
+        q.record_stream(torch.cuda.current_stream())
+        sc.record_stream(torch.cuda.current_stream())
+        return scores, rows, keys
+
     # ---- range search (include/vidmem.h vm_range_cosine, DESIGN.md 15) ---------------------------------------------
     def prepare_range(self, Q: int, max_hits: int) -> "RangeScratch":
         """Size this memory's own range-search buffers for ``Q`` queries and ``max_hits`` hits each now (before a graph
@@ -1218,6 +1278,15 @@ class EmbeddingMemory:
     def scoped_uncertified_count(self) -> int:
         """Queries the scoped fast path redid exhaustively since this memory was created (synchronises)."""
         return 0 if self._suncert is None else int(self._suncert.item())
+
+    @property
+    def last_group_scope_flags(self) -> Optional[torch.Tensor]:
+        return self._gsflags
+
+    @property
+    def group_scoped_uncertified_count(self) -> int:
+        """Queries the scoped grouped fast path redid exhaustively since this memory was created (synchronises)."""
+        return 0 if self._gsuncert is None else int(self._gsuncert.item())
 
     @property
     def last_group_flags(self) -> Optional[torch.Tensor]:

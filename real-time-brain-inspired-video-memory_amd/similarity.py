@@ -55,10 +55,14 @@ def _check_distinct(memory: EmbeddingMemory, distinct: bool) -> None:
 
 
 def _check_scope(memory: EmbeddingMemory, scope, distinct: bool) -> None:
+    """``scope`` together with ``distinct=True`` is accepted exactly when the memory object provides
+    ``topk_grouped_scoped`` (EmbeddingMemory does; the memory must then be grouped and tagged); any other memory object
+    is refused, because ``topk_scoped`` ranks rows and ``topk_grouped`` ranks groups of the whole memory."""
     if scope is None:
         return
-    if distinct:
-        raise ValueError("scope together with distinct=True is not supported: the scoped search ranks rows, not groups")
+    if distinct and not callable(getattr(memory, "topk_grouped_scoped", None)):
+        raise ValueError("scope together with distinct=True needs a memory that provides topk_grouped_scoped "
+                         "(EmbeddingMemory(..., grouped=True, tagged=True)): the scoped search ranks rows, not groups")
     if not getattr(memory, "tagged", False):
         raise ValueError("scope needs a tagged memory (EmbeddingMemory(..., tagged=True), memory.tag_by: time)")
 
@@ -77,7 +81,11 @@ def batch_similarities(memory: EmbeddingMemory, chunk_embeddings: Sequence, top_
 
     ``scope`` (tagged memories): one inclusive tag range ``(lo, hi)`` for every query (memory.scope_of) - the
     reference's ``{graph_uuid: $graph_uuid}`` predicate; only in-scope rows are ranked (EmbeddingMemory.topk_scoped), and
-    the wrong-length rule lists the first in-scope rows.  ``None`` = the whole memory, as before."""
+    the wrong-length rule lists the first in-scope rows.  ``None`` = the whole memory, as before.
+
+    ``distinct=True`` together with ``scope``: at most one hit per group among the in-scope rows
+    (EmbeddingMemory.topk_grouped_scoped) - accepted when the memory object provides that method, ValueError otherwise.
+    The wrong-length rule then lists the first in-scope row of each of the first ``top_k`` in-scope groups."""
     _check_distinct(memory, distinct)
     _check_scope(memory, scope, distinct)
     ok_idx = [i for i, e in enumerate(chunk_embeddings) if not isinstance(e, Exception) and e is not None]
@@ -91,7 +99,13 @@ def batch_similarities(memory: EmbeddingMemory, chunk_embeddings: Sequence, top_
             zeros = [(memory.id_of(first_row + j), 0.0) for j in range(min(top_k, memory.searchable))]
         else:
             tags = memory.tags_host()
-            hit = ((tags >= int(scope[0])) & (tags <= int(scope[1]))).nonzero()[0][:top_k]
+            hit = ((tags >= int(scope[0])) & (tags <= int(scope[1]))).nonzero()[0]
+            if distinct:  # every score is 0.0: the ranking keeps memory order, so each group shows its first in-scope row
+                keys = memory.group_keys_host()
+                starts = (keys[1:] != keys[:-1]).cumsum()            # group index of rows 1 .. n-1; row 0 is in group 0
+                gid = [0 if j == 0 else int(starts[j - 1]) for j in hit]
+                hit = [j for i, j in enumerate(hit) if i == 0 or gid[i] != gid[i - 1]]
+            hit = hit[:top_k]
             zeros = [(memory.id_of(first_row + int(j)), 0.0) for j in hit]
         for i in wrong:
             out[i] = list(zeros)
@@ -103,7 +117,9 @@ def batch_similarities(memory: EmbeddingMemory, chunk_embeddings: Sequence, top_
         q = torch.stack([chunk_embeddings[i] for i in ok_idx])
     else:
         q = torch.tensor([list(chunk_embeddings[i]) for i in ok_idx], dtype=torch.float32)
-    if scope is not None:
+    if scope is not None and distinct:
+        scores, rows, _ = memory.topk_grouped_scoped(q, top_k, scope)
+    elif scope is not None:
         scores, rows = memory.topk_scoped(q, top_k, scope)
     elif distinct:
         scores, rows, _ = memory.topk_grouped(q, top_k)
@@ -121,7 +137,9 @@ class HipPreLLMSimilarity:
     def __init__(self, memory: EmbeddingMemory, embedder_config: Any, distinct: bool = False, scope=None):
         """``scope``: an inclusive tag range ``(lo, hi)`` (memory.scope_of) every search of this object is restricted to
         - the reference's ``WHERE c.graph_uuid = $graph_uuid`` (src/components/pre_llm_injector.py:395-396); tagged memory
-        only, not together with ``distinct``.  ``None`` = the whole memory."""
+        only.  Together with ``distinct`` it needs a memory that provides ``topk_grouped_scoped`` (a grouped and tagged
+        EmbeddingMemory): one hit per group among the in-scope rows; ValueError otherwise.  ``None`` = the whole
+        memory."""
         _check_distinct(memory, distinct)
         _check_scope(memory, scope, distinct)
         self.memory = memory
@@ -186,8 +204,10 @@ class HipVectorSearch:
         ``distinct=True`` (grouped memory only, else ValueError): at most one hit per chunk - ``top_k_chunks`` distinct
         chunks, each represented by its best frame (EmbeddingMemory.topk_grouped).
         ``scope``: an inclusive tag range ``(lo, hi)`` (memory.scope_of) the search is restricted to - the reference's
-        ``MATCH (c:Chunk {graph_uuid: $graph_uuid})`` (src/pipeline/retriever_hybrid.py:295); tagged memory only, not
-        together with ``distinct`` (ValueError).  ``None`` = the whole memory."""
+        ``MATCH (c:Chunk {graph_uuid: $graph_uuid})`` (src/pipeline/retriever_hybrid.py:295); tagged memory only.
+        Together with ``distinct`` it needs a memory that provides ``topk_grouped_scoped`` (a grouped and tagged
+        EmbeddingMemory; ValueError otherwise): ``top_k_chunks`` distinct chunks of the scope, each represented by its
+        best in-scope frame.  ``None`` = the whole memory."""
         if score_mode not in (_lib.VM_SCORE_RAW, _lib.VM_SCORE_UNIT_INTERVAL):
             raise ValueError("score_mode must be VM_SCORE_RAW or VM_SCORE_UNIT_INTERVAL")
         # an embedder that states its width (HipTextEmbedder, FrameEncoder-backed ones) must match the memory's rows: a
@@ -206,7 +226,11 @@ class HipVectorSearch:
     async def _vector_search_chunks(self, session, query) -> List[Dict[str, Any]]:
         try:
             query_embedding = await self.embedder.aembed_query(query)
-            if getattr(self, "scope", None) is not None:
+            if getattr(self, "scope", None) is not None and self.distinct:
+                scores, rows, _ = self.memory.topk_grouped_scoped([query_embedding], self.config.top_k_chunks,
+                                                                  self.scope, min_score=self.min_score,
+                                                                  score_mode=self.score_mode)
+            elif getattr(self, "scope", None) is not None:
                 scores, rows = self.memory.topk_scoped([query_embedding], self.config.top_k_chunks, self.scope,
                                                        min_score=self.min_score, score_mode=self.score_mode)
             elif self.distinct:
