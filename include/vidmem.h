@@ -544,6 +544,51 @@ int vm_topk_cosine_grouped_scoped_exact(vm_memory *mem, const void *queries, int
                                         const int64_t *scope_hi, int use_min_score, double min_score, int score_mode,
                                         double *out_scores, int64_t *out_rows, int64_t *out_keys, void *workspace,
                                         size_t workspace_bytes, void *stream);
+/* Clip search: where does a SEQUENCE of frames occur in the memory - "have I seen these 16 frames before, and where?".
+ * The memory stores one row per frame in time order; the aligned counterpart of the reference's chunk-to-chunk link
+ * (src/components/pre_llm_injector.py:346-372, one vector per chunk) is a score per START ROW.
+ * clips [C, L, D] dtype, 1 <= L <= 16, C >= 1, 1 <= k <= 64, 1 <= min_sep <= 32 (VM_ERR_INVALID outside); any memory
+ * (plain, grouped, tagged, ring).
+ * Window: for a live start row r, window r is the rows r .. r+L-1 (live ids lo .. n-1 as in vm_memory_events).  It is
+ *   VALID iff all L rows are live and, on a tagged memory, no row r+1 .. r+L-1 has a TAG BREAK against its predecessor -
+ *   the tag part of vm_memory_events' opening rule: exactly one of the two tags is INT64_MIN; or neither is and the
+ *   sources differ; or neither is, max_gap_ms >= 0 and the clock step is negative or above max_gap_ms.  A window never
+ *   spans two videos.  max_gap_ms >= 0 on an untagged memory: VM_ERR_INVALID.
+ * Scope: scope_lo / scope_hi device int64 [C], or both NULL.  A window is IN SCOPE iff every one of its L rows is, by
+ *   vm_topk_cosine_scoped's rule.  Scopes on an untagged memory, or one NULL and one not: VM_ERR_INVALID.
+ * Score: W(r) = (e_0 + e_1 + ... + e_{L-1}) / L, e_i the raw reference cosine of clip frame i and row r+i (fp64 on the
+ *   stored 16-bit values, the stored norm, the zero-norm guard, as vm_topk_cosine); the sum starts from 0.0 and runs left
+ *   to right with one rounding per addition, then one correctly rounded division by (double)L.  L = 1 makes W the reference
+ *   cosine bit for bit.  The shown score is the score_mode mapping of W; the filter is strict > min_score on it.
+ * Peaks: a COMPETITOR of r is a valid, in-scope window r' != r with |r' - r| < min_sep; r is a PEAK iff it ranks before
+ *   every competitor in (raw W descending, start row ascending).  Two peaks are therefore at least min_sep rows apart;
+ *   min_sep = 1 makes every valid in-scope window a peak.  This is LOCAL-MAXIMUM suppression, not greedy suppression: in a
+ *   chain A > B > C whose neighbours are closer than min_sep only A is a peak (greedy would keep C as well).
+ * Result per clip: the peaks ranked by (raw W descending, start ascending), filtered, first k.  out_scores [C,k] the shown
+ *   fp64 values bit for bit, out_rows [C,k] the START row ids (no stride or offset: a row-sharded memory has no consecutive
+ *   rows); 0.0 / -1 padded.  It depends on the memory, the clip and its own arguments only: not on C, the other clips, the
+ *   launch geometry or the workspace size.
+ * ALWAYS the exhaustive answer: an fp32 MFMA scan scores every live row against the 16 C frames, each window's fp32 mean
+ *   lies within eps_w = 2 (D + 8) 2^-24 + 2^-23 of W, windows that a competitor exceeds by more than 2 eps_w are dropped
+ *   as provably no peaks, the best k + slack of the rest are re-scored exactly with their competitors, and a clip whose
+ *   result cannot be proven is counted in *out_uncertified (may be NULL; accumulates), marked in out_query_flags [C]
+ *   (vm_topk_flag; may be NULL) and redone exhaustively on the device inside the same call.  So is every clip with a frame
+ *   norm, or a stored row's norm, neither 0 nor in [2^-40, 2^40] (vm_memory_create).
+ * No allocation, no synchronisation, no host read-back; the row count and the scopes are read on the device and the grids
+ * are sized from the capacity: capturable.  An undersized workspace is refused with VM_ERR_NOMEM before any launch; a NaN
+ * min_score with use_min_score is VM_ERR_INVALID.
+ * Workspace: vm_topk_clip_workspace_bytes = 64 x C x capacity bytes of fp32 scores (16 columns per clip) + 16 x C x
+ *   capacity of window scores, keys and exact redo scores + 64 KiB x C and a few MB. */
+size_t vm_topk_clip_workspace_bytes(const vm_memory *mem, int C, int L, int k);
+int vm_topk_cosine_clip(vm_memory *mem, const void *clips, int C, int L, int k, int min_sep, int64_t max_gap_ms,
+                        const int64_t *scope_lo, const int64_t *scope_hi, int use_min_score, double min_score,
+                        int score_mode, double *out_scores, int64_t *out_rows, int32_t *out_uncertified,
+                        int32_t *out_query_flags, void *workspace, size_t workspace_bytes, void *stream);
+/* The same contract, exhaustive only: every valid in-scope window scored exactly (slow; tests, and a checker). */
+int vm_topk_cosine_clip_exact(vm_memory *mem, const void *clips, int C, int L, int k, int min_sep, int64_t max_gap_ms,
+                              const int64_t *scope_lo, const int64_t *scope_hi, int use_min_score, double min_score,
+                              int score_mode, double *out_scores, int64_t *out_rows, void *workspace,
+                              size_t workspace_bytes, void *stream);
 /* Range search: EVERY row above a threshold, in time order - "which frames of this video show X?" has no k.  The
  * threshold is the reference's own notion of relevance (`vector.similarity.cosine(...) > 0.3`,
  * src/pipeline/retriever_hybrid.py:296-298; `>= compression_threshold`, :494-504); this call returns all of what passes

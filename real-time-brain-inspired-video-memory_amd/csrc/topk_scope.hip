@@ -24,20 +24,12 @@
 //              every redo (vm_topk_redo_merge; both topk_exact.hip).  Flags and
 //              counts are read on the device; near-empty when nothing is flagged.
 // Every launch reads the row count from the device and sizes its grid from the capacity: capturable.
+#include "topk_scope_select.h"  // the select stage (cut, compaction, selection): shared with topk_clip.hip
 #include "topk_tile_scan.h"
 
 #include <climits>
 
 namespace {
-
-constexpr int SEL_THREADS = 1024;  // cut and selection (one block per query)
-constexpr int SEL_SAMPLE = 16384;  // slots whose keys give each query's cut
-constexpr int SEL_CAP = 8192;      // rows at or above the cut a query keeps; more -> VM_FLAG_OVERFLOW
-constexpr int CMP_THREADS = 256;   // compaction
-constexpr int CMP_LCAP = 2048;     // hits one compaction block gathers in LDS before it flushes them
-constexpr int SF_THREADS = 256;    // finalize
-constexpr int SCMAX = 128;         // candidates per query kept by the select (M + 1 <= 81)
-constexpr int SKMAX = 64;
 
 // ---- scan --------------------------------------------------------------------------------------------------
 // The scoped policy of the tile scan (topk_tile_scan.h): four keys per lane, F[q * fstride + slot] = the order-preserving
@@ -88,108 +80,6 @@ struct ScopeScan {
         }
     }
 };
-
-// ---- select ------------------------------------------------------------------------------------------------
-// composites (topk_select.h) of key and age order: ties at one key go to the older row
-// One block per query: cut[q] = the (M+1)-th largest key of a sample of SEL_SAMPLE slots, one per stride (all slots when
-// there are fewer), or 1 - every in-scope row - when the sample holds fewer than M + 1 in-scope rows.  At least
-// min(M + 1, in-scope rows) rows have a key >= the cut, and no out-of-scope row (key 0) has.
-__global__ void __launch_bounds__(SEL_THREADS)
-    scope_cut_kernel(const int64_t *__restrict__ d_total, int64_t cap, int ring, const uint32_t *__restrict__ F,
-                     int64_t fstride, int M1, uint32_t *__restrict__ cut, int *__restrict__ ccount) {
-    constexpr int PER = SEL_SAMPLE / SEL_THREADS;
-    const int q = blockIdx.x, tid = threadIdx.x;
-    const int64_t n = ring_view(*d_total, cap, ring).n;
-    const uint32_t *Fq = F + (size_t)q * fstride;
-    const int cnt = (int)(n < SEL_SAMPLE ? n : SEL_SAMPLE);
-    uint32_t v[PER];
-#pragma unroll
-    for (int j = 0; j < PER; ++j) {
-        const int i = j * SEL_THREADS + tid;
-        // one slot per stride, at a hashed offset inside it: a fixed stride of 64 slots would see one source only of
-        // two that alternate every 16 rows
-        int64_t p = i;
-        if (n > SEL_SAMPLE) p = (int64_t)i * n / SEL_SAMPLE + (int64_t)(((uint32_t)i * 2654435761u) >> 8) % (n / SEL_SAMPLE);
-        v[j] = i < cnt ? Fq[p] : 0u;
-    }
-    // the top 20 bits of the key are enough for a cut (a score resolution of 2^-11 relative): 20 counting steps, not 32.
-    // 0 when fewer than M1 sampled keys are in scope (every in-scope key is above 2^12)
-    const uint32_t T = block_kth_u32<SEL_THREADS>(v, M1, 12);
-    if (tid == 0) {
-        cut[q] = T ? T : 1u;
-        ccount[q] = 0;
-    }
-}
-
-// grid (slices, Q): every in-scope row with key >= cut[q] goes to the query's buffer as a composite.  Hits gather in
-// LDS and leave with one global atomic per flush.  ccount[q] ends as the exact number of hits; the buffer keeps the
-// first SEL_CAP.
-__global__ void __launch_bounds__(CMP_THREADS)
-    scope_compact_kernel(const int64_t *__restrict__ d_total, int64_t cap, int ring, const uint32_t *__restrict__ F,
-                         int64_t fstride, const uint32_t *__restrict__ cut, int *__restrict__ ccount,
-                         unsigned long long *__restrict__ cbuf) {
-    __shared__ unsigned long long lbuf[CMP_LCAP];
-    __shared__ int lcnt, gbase;
-    const int q = blockIdx.y, tid = threadIdx.x;
-    const RingView rv = ring_view(*d_total, cap, ring);
-    const int64_t n = rv.n;
-    const uint32_t *Fq = F + (size_t)q * fstride;
-    const uint32_t T = cut[q];
-    const int64_t stride = (int64_t)gridDim.x * CMP_THREADS * 4;
-    if (tid == 0) lcnt = 0;
-    __syncthreads();
-    int held_max = 0;  // block-uniform upper bound of the hits in lbuf
-    auto flush = [&]() {  // called by every thread
-        __syncthreads();  // every hit of the iterations so far is in lbuf and counted in lcnt
-        const int held = lcnt;
-        if (tid == 0 && held) gbase = atomicAdd(&ccount[q], held);
-        __syncthreads();
-        for (int i = tid; i < held; i += CMP_THREADS) {
-            const int pos = gbase + i;
-            if (pos < SEL_CAP) cbuf[(size_t)q * SEL_CAP + pos] = lbuf[i];
-        }
-        __syncthreads();
-        if (tid == 0) lcnt = 0;
-        held_max = 0;
-        __syncthreads();
-    };
-    for (int64_t base = (int64_t)blockIdx.x * CMP_THREADS * 4; base < n; base += stride) {  // uniform per block
-        const int64_t p = base + 4 * tid;  // 4 consecutive slots, 16-byte aligned (fstride is a multiple of 64)
-        uint4 k4 = make_uint4(0, 0, 0, 0);
-        if (p < n) k4 = *reinterpret_cast<const uint4 *>(Fq + p);
-        const uint32_t key[4] = {k4.x, k4.y, k4.z, k4.w};
-        int hits = 0;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) hits += (p + j < n && key[j] >= T) ? 1 : 0;  // T >= 1: never an out-of-scope row
-        if (hits) {  // rare: one LDS atomic per thread with hits
-            int pos = atomicAdd(&lcnt, hits);  // pos + hits <= CMP_LCAP: flushed before it could fill
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                if (p + j < n && key[j] >= T) lbuf[pos++] = composite(key[j], (int)order_of(rv, p + j));
-        }
-        held_max += 4 * __syncthreads_count(hits != 0);
-        if (held_max > CMP_LCAP - 4 * CMP_THREADS) flush();
-    }
-    flush();
-}
-
-// One block per query: the best take = min(M + 1, hits) composites of the compacted list.  cand_n[q] = take, or -1 when
-// the list overflowed (the finalize flags the query for the exhaustive redo).
-__global__ void __launch_bounds__(SEL_THREADS)
-    scope_select_kernel(int M1, const int *__restrict__ ccount, const unsigned long long *__restrict__ cbuf,
-                        int *__restrict__ cand_o, uint32_t *__restrict__ cand_k, int *__restrict__ cand_n) {
-    const int q = blockIdx.x, tid = threadIdx.x;
-    int *oo = cand_o + (size_t)q * SCMAX;
-    uint32_t *ok = cand_k + (size_t)q * SCMAX;
-    const int cnt = ccount[q];
-    if (cnt > SEL_CAP || cnt == 0) {  // uniform
-        if (tid == 0) cand_n[q] = cnt ? -1 : 0;
-        return;
-    }
-    const int take = cnt < M1 ? cnt : M1;
-    if (tid == 0) cand_n[q] = take;
-    select_best<SEL_THREADS, SEL_CAP, SCMAX>(cbuf + (size_t)q * SEL_CAP, cnt, take, oo, ok);
-}
 
 // ---- finalize ----------------------------------------------------------------------------------------------
 // One block per query.  Ranks the C candidates by (fp32 key desc, order asc): the first nc = min(C, M) are re-scored

@@ -284,6 +284,9 @@ class EmbeddingMemory:
         self._gsuncert = None       # queries the scoped grouped fast path could not certify (device int32, accumulates)
         self._nscratch = None       # buffers of the gated append (NoveltyScratch), grown on demand
         self._escratch = None       # buffers of erase (EraseScratch), made on demand
+        self._cscratch = None       # buffers of the clip search (ClipScratch), grown on demand
+        self._clast = None          # the scratch of the last clip call (last_clip_flags)
+        self._cuncert = None        # clips the clip search's fast path could not certify (device int32, accumulates)
         self._rscratch = None       # buffers of the range search (RangeScratch), grown on demand
         self._rlast = None          # the scratch of the last range call (last_range_rescored)
         self._vscratch = None       # buffers of the event segmentation (EventsScratch), grown on demand
@@ -951,6 +954,101 @@ class EmbeddingMemory:
         sc.record_stream(torch.cuda.current_stream())
         return scores, rows, keys
 
+    # ---- clip search (include/vidmem.h vm_topk_cosine_clip) -----------------------------------------
+    def prepare_topk_clip(self, C: int, L: int, k: int) -> "ClipScratch":
+        """Size this memory's own clip-search buffers for ``C`` clips of ``L`` frames and ``k`` hits each now (before a
+        graph capture: a capture must not allocate)."""
+        if self._cscratch is None or not self._cscratch.fits(self, C, L, k):
+            self._cscratch = ClipScratch.for_(self, C, L, k)
+        if self._cuncert is None:
+            self._cuncert = torch.zeros(1, dtype=torch.int32, device=self.device)
+        return self._cscratch
+
+    def _clip_args(self, clips, k, min_sep, scope, max_gap_ms, min_score, score_mode):
+        if not isinstance(clips, torch.Tensor):
+            clips = torch.tensor(clips, dtype=torch.float32)
+        if clips.dim() == 2:
+            clips = clips.unsqueeze(0)
+        if clips.dim() != 3 or clips.shape[-1] != self.dim:
+            raise ValueError(f"clips must be [C, L, {self.dim}] or [L, {self.dim}], got {tuple(clips.shape)}")
+        Cn, L = int(clips.shape[0]), int(clips.shape[1])
+        if Cn < 1:
+            raise ValueError("no clip")
+        if not 1 <= L <= 16:
+            raise ValueError(f"clip search supports 1 <= L <= 16 frames, got {L}")
+        if not 1 <= int(k) <= 64:
+            raise ValueError(f"clip search supports 1 <= k <= 64, got {k}")
+        sep = L if min_sep is None else int(min_sep)
+        if not 1 <= sep <= 32:
+            raise ValueError(f"clip search supports 1 <= min_sep <= 32, got {sep}")
+        if score_mode not in (_lib.VM_SCORE_RAW, _lib.VM_SCORE_UNIT_INTERVAL):
+            raise ValueError("score_mode must be VM_SCORE_RAW or VM_SCORE_UNIT_INTERVAL")
+        if (scope is not None or (max_gap_ms is not None and int(max_gap_ms) >= 0)) and not self.tagged:
+            raise ValueError("scope and max_gap_ms need a tagged memory (EmbeddingMemory(..., tagged=True))")
+        if min_score is not None and math.isnan(float(min_score)):
+            raise ValueError("min_score is NaN")
+        q = clips.to(device=self.device, dtype=self.dtype).contiguous()
+        sc = self._scope_tensor(scope, Cn) if scope is not None else None
+        gap = -1 if max_gap_ms is None else int(max_gap_ms)
+        return q, Cn, L, sep, sc, gap
+
+    def enqueue_topk_clip(self, clips, k: int, min_sep: Optional[int] = None, scope=None,
+                          max_gap_ms: Optional[int] = None, min_score: Optional[float] = None,
+                          score_mode: int = _lib.VM_SCORE_RAW, scratch: Optional["ClipScratch"] = None,
+                          exact: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The capturable clip search -> ``(scores [C,k] float64, rows [C,k] int64)``: views of the buffers of
+        ``scratch`` (default: this memory's own, ``prepare_topk_clip``), valid until the next clip call on it.  Arguments
+        as in ``topk_clip``.  Enqueues ``vm_topk_cosine_clip`` on the current stream: nothing is read on the host.
+        Inside a graph capture pass ``clips`` as a device tensor of the memory's dtype and ``scope`` as an int64
+        ``[C, 2]`` device tensor (both rewritten in place between replays) and a ``scratch`` the session owns, or call
+        ``prepare_topk_clip`` first."""
+        q, Cn, L, sep, sc, gap = self._clip_args(clips, k, min_sep, scope, max_gap_ms, min_score, score_mode)
+        k = int(k)
+        if scratch is None:
+            scratch = self.prepare_topk_clip(Cn, L, k)
+        elif not scratch.fits(self, Cn, L, k):
+            raise ValueError("caller-owned clip scratch is too small for this (C, L, k)")
+        if self._cuncert is None:
+            self._cuncert = torch.zeros(1, dtype=torch.int32, device=self.device)
+        scores = scratch.scores[:Cn * k].view(Cn, k)
+        rows = scratch.rows[:Cn * k].view(Cn, k)
+        ptr = lambda x: C.c_void_p(x.data_ptr())
+        lo, hi = (ptr(sc[0]), ptr(sc[1])) if sc is not None else (C.c_void_p(0), C.c_void_p(0))
+        use_min = 0 if min_score is None else 1
+        ms = 0.0 if min_score is None else float(min_score)
+        head = (self.handle, ptr(q), Cn, L, k, sep, gap, lo, hi, use_min, ms, int(score_mode), ptr(scores), ptr(rows))
+        tail = (ptr(scratch.ws), scratch.ws.numel(), _lib.current_stream_ptr())
+        if exact:
+            self.ctx.check(self.L.vm_topk_cosine_clip_exact(*head, *tail))
+        else:
+            self.ctx.check(self.L.vm_topk_cosine_clip(*head, ptr(self._cuncert), ptr(scratch.flags), *tail))
+        cur = torch.cuda.current_stream()
+        q.record_stream(cur)
+        if sc is not None:
+            sc.record_stream(cur)
+        self._clast = scratch
+        return scores, rows
+
+    def topk_clip(self, clips, k: int, min_sep: Optional[int] = None, scope=None, max_gap_ms: Optional[int] = None,
+                  min_score: Optional[float] = None, score_mode: int = _lib.VM_SCORE_RAW, exact: bool = False
+                  ) -> Tuple[torch.Tensor, torch.Tensor]:
+        """-> (scores [C,k] float64, rows [C,k] int64): where each clip - a SEQUENCE of L <= 16 frames, ``clips``
+        ``[C,L,D]`` or ``[L,D]`` - occurs in the memory.  ``rows`` are START row ids: window r is the rows r .. r+L-1 and
+        scores the mean of the L aligned reference cosines (frame i against row r+i; the fp64 values bit for bit).
+
+        A window must lie within the live rows and, on a tagged memory, within one video (no change of source inside;
+        ``max_gap_ms``: no clock step backwards or above it either); with ``scope`` (one ``(lo, hi)`` or C pairs, as
+        in ``topk_scoped``) every one of its rows must be in scope.  The k answers are PEAKS: windows that rank before
+        every other such window closer than ``min_sep`` rows (default: L, non-overlapping windows; 1 = every window), in
+        (score desc, start asc) - local-maximum suppression, so k answers are k moments, not k shifts of one.  Score
+        mapping and strict ``> min_score`` filter as in ``topk``; -1 / 0.0 padded.  Always the exhaustive answer: the
+        fp32 fast path redoes the clips it cannot certify on the device, in the same call (csrc/topk_clip.hip).
+        ``exact=True`` scores every window exactly (slow).  The per-clip flags of the last call are in
+        ``last_clip_flags``."""
+        scores, rows = self.enqueue_topk_clip(clips, k, min_sep=min_sep, scope=scope, max_gap_ms=max_gap_ms,
+                                              min_score=min_score, score_mode=score_mode, exact=exact)
+        return scores.clone(), rows.clone()
+
     # ---- range search (include/vidmem.h vm_range_cosine, DESIGN.md 15) ---------------------------------------------
     def prepare_range(self, Q: int, max_hits: int) -> "RangeScratch":
         """Size this memory's own range-search buffers for ``Q`` queries and ``max_hits`` hits each now (before a graph
@@ -1280,6 +1378,16 @@ class EmbeddingMemory:
         return 0 if self._suncert is None else int(self._suncert.item())
 
     @property
+    def last_clip_flags(self) -> Optional[torch.Tensor]:
+        """int32 per clip (vm_topk_flag): why the last fast clip call redid a clip, 0 = certified (device tensor)."""
+        return None if self._clast is None else self._clast.flags
+
+    @property
+    def clip_uncertified_count(self) -> int:
+        """Clips the clip search's fast path redid exhaustively since this memory was created (synchronises)."""
+        return 0 if self._cuncert is None else int(self._cuncert.item())
+
+    @property
     def last_group_scope_flags(self) -> Optional[torch.Tensor]:
         return self._gsflags
 
@@ -1513,6 +1621,29 @@ class RangeScratch:
     def for_(cls, memory: "EmbeddingMemory", Q: int, max_hits: int) -> "RangeScratch":
         Q = max(1, int(Q))
         return cls(memory.device, Q, int(max_hits), int(memory.L.vm_range_workspace_bytes(memory.handle, Q)))
+
+
+class ClipScratch:
+    """Device buffers of the clip search for up to ``C`` clips of ``L`` frames with ``k`` hits each: the workspace (query
+    tiles, fp32 score columns, window scores and keys, candidates, exact redo scores), ``flags`` (int32 [C]) and the
+    ``scores`` / ``rows`` outputs (C x k).  Like ``RangeScratch``, an owner keeps ONE instance per stream / captured
+    graph: a hipGraph bakes the addresses in."""
+
+    def __init__(self, device, C: int, k: int, ws_bytes: int):
+        self.C, self.k = int(C), int(k)
+        self.ws = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=device)
+        self.flags = torch.zeros(max(C, 1), dtype=torch.int32, device=device)
+        self.scores = torch.zeros(max(C * k, 1), dtype=torch.float64, device=device)
+        self.rows = torch.full((max(C * k, 1),), -1, dtype=torch.int64, device=device)
+
+    def fits(self, memory: "EmbeddingMemory", C: int, L: int, k: int) -> bool:
+        return (self.flags.numel() >= C and self.rows.numel() >= C * k and
+                self.ws.numel() >= int(memory.L.vm_topk_clip_workspace_bytes(memory.handle, int(C), int(L), int(k))))
+
+    @classmethod
+    def for_(cls, memory: "EmbeddingMemory", C: int, L: int, k: int) -> "ClipScratch":
+        need = int(memory.L.vm_topk_clip_workspace_bytes(memory.handle, int(C), int(L), int(k)))
+        return cls(memory.device, int(C), int(k), need)
 
 
 class EraseScratch:

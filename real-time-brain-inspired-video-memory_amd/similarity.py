@@ -131,6 +131,41 @@ def batch_similarities(memory: EmbeddingMemory, chunk_embeddings: Sequence, top_
     return out
 
 
+def clip_similarities(memory: EmbeddingMemory, chunks_of_frame_embeddings: Sequence, top_k: int,
+                      min_sep: Optional[int] = None, scope=None, max_gap_ms: Optional[int] = None
+                      ) -> List[List[Tuple[str, float]]]:
+    """The aligned counterpart of ``batch_similarities`` for a memory that stores one row per frame: each entry of
+    ``chunks_of_frame_embeddings`` is a chunk's frames in order (``[L, D]``, 1 <= L <= 16; tensor or lists), and its hits
+    are the stored moments it replays frame for frame (EmbeddingMemory.topk_clip: the mean of the L aligned cosines, one
+    hit per moment) - where ``batch_similarities`` on the same frames scores L independent queries and ignores order.
+
+    Returns the reference's list shape (src/components/pre_llm_injector.py:346-372): per chunk ``[(id, score), ...]``,
+    ``id = memory.id_of(start_row)``; an Exception or ``None`` entry yields ``[]`` (:357-359).
+    ``merge_batch_similarities`` consumes it unchanged.  Chunks of one length share one launch.  ``min_sep``, ``scope``
+    (one inclusive tag range for every chunk) and ``max_gap_ms`` as in ``topk_clip``."""
+    _check_scope(memory, scope, False)
+    out: List[List[Tuple[str, float]]] = [[] for _ in chunks_of_frame_embeddings]
+    if memory.searchable == 0 or top_k <= 0:
+        return out
+    by_len: Dict[int, List[int]] = {}
+    clips: Dict[int, torch.Tensor] = {}
+    for i, e in enumerate(chunks_of_frame_embeddings):
+        if isinstance(e, Exception) or e is None:
+            continue
+        t = e if isinstance(e, torch.Tensor) else torch.tensor([list(f) for f in e], dtype=torch.float32)
+        if t.dim() != 2 or t.shape[-1] != memory.dim:
+            raise ValueError(f"chunk {i}: frames must be [L, {memory.dim}], got {tuple(t.shape)}")
+        clips[i] = t
+        by_len.setdefault(int(t.shape[0]), []).append(i)
+    for L, idx in by_len.items():
+        q = torch.stack([clips[i].to(memory.device) for i in idx])
+        scores, rows = memory.topk_clip(q, top_k, min_sep=min_sep, scope=scope, max_gap_ms=max_gap_ms)
+        scores, rows = scores.cpu().tolist(), rows.cpu().tolist()
+        for slot, i in enumerate(idx):
+            out[i] = [(memory.id_of(r), float(s)) for r, s in zip(rows[slot], scores[slot]) if r >= 0]
+    return out
+
+
 class HipPreLLMSimilarity:
     """Mixin / stand-alone object for PreLLMInjector: set ``self.memory`` and ``self.embedder_config``."""
 
