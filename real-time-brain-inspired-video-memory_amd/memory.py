@@ -1518,12 +1518,19 @@ class EmbeddingMemory:
                 mem._next_group_key = max(0, int(keys.max()) + 1)
         return mem
 
+    def _table_index(self, row: int) -> int:
+        """The table slot of a LIVE row id, -1 for any other: a row a ring has overwritten has no entry any more, also
+        while its slot has not been trimmed yet (``_trim_tables`` drops them late, in batches)."""
+        if self.ring and row < len(self) - self.capacity:
+            return -1
+        return row - self.table_base
+
     def id_of(self, row: int) -> Optional[str]:
-        i = row - self.table_base
+        i = self._table_index(row)
         return self.ids[i] if 0 <= i < len(self.ids) else None
 
     def meta_of(self, row: int) -> Optional[dict]:
-        i = row - self.table_base
+        i = self._table_index(row)
         return self.meta[i] if 0 <= i < len(self.meta) else None
 
 

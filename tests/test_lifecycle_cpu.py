@@ -1,0 +1,374 @@
+"""CPU: the lifecycle harness (tests/lifecycle_ref.py) proved before it judges a kernel.
+
+1. the model against itself: provenance, two erases = one erase of the union, restored() = a fresh model of the window;
+2. the conditions both scripts must meet at every checkpoint, for both dtypes, from the reference alone;
+3. planted defects: a fake memory answers ``checkpoint`` from a second model instance; the unplanted fake passes, every
+   defect planted in that instance fails.
+"""
+from types import SimpleNamespace
+
+import numpy as np
+import pytest
+
+from oracle import cref
+from tests import clip_ref as CL
+from tests import erase_ref as E
+from tests import events_ref as V
+from tests import group_ref as G
+from tests import lifecycle_ref as LC
+from tests import scope_ref as S
+
+DTYPES = ["f16", "bf16"]
+SCRIPTS = {"linear": (LC.linear_script, 1600, False), "ring": (LC.ring_script, 600, True)}
+
+
+class Refused(Exception):
+    code = LC.VM_ERR_UNSUPPORTED
+
+
+def _norms(bits, dtype):
+    return np.linalg.norm(CL.from_bits(np.ascontiguousarray(bits), dtype).astype(np.float64), axis=1)
+
+
+class FakeMemory:
+    """The surface of ``EmbeddingMemory`` that the scripts and ``checkpoint`` use, answered from a ``Model`` of its own.
+    ``defect`` plants one way a real memory could go wrong."""
+
+    def __init__(self, model: LC.Model, defect=None):
+        self.m, self.defect = model, defect
+        self.ghost = None          # rows an erase left in the slots it vacated (defect "ghost")
+        self.stale = None          # the norms an erase left behind in slots [0, n') (defect "stale_norm")
+        self.memo = {}             # reader answers since the last mutation: checkpoint asks for both forms of each
+
+    # -- accessors
+    def __len__(self):
+        return self.m.total
+
+    @property
+    def searchable(self):
+        return self.m.total - self.m.base
+
+    def rows_host(self):
+        lo, live = self.m.window()
+        return lo + (self.defect == "ring_base" and self.m.wrapped), live.rows
+
+    def tags_host(self):
+        return self.m.window()[1].tags
+
+    def group_keys_host(self):
+        return self.m.window()[1].keys
+
+    def id_of(self, r):
+        return self.m.ids[r] if self.m.base <= r < self.m.total else None
+
+    def raw(self, n):
+        _, live = self.m.window()
+        out = []
+        for col in (live.rows, live.tags, live.keys, live.ords):
+            full = np.zeros((n,) + col.shape[1:], col.dtype)
+            full[:col.shape[0]] = col
+            out.append(full)
+        if self.ghost is not None:
+            k = live.rows.shape[0]
+            out[0][k:k + self.ghost.shape[0]] = self.ghost[:n - k]
+        return out
+
+    # -- mutators
+    def meta_of(self, r):
+        return None if self.id_of(r) is None else {"i": self.id_of(r)}
+
+    def append(self, rows, ids=None, meta=None, group=None, tag=None):
+        self.ghost = None
+        return self.m.append(rows, tag, group, ids)
+
+    def append_novel(self, rows, tau, ids=None, meta=None, group=None, tag=None):
+        known = None
+        if self.ghost is not None:                          # the search sees the rows that were not zeroed
+            lo, live = self.m.window()
+            known = LC.N.top1(rows, np.concatenate([live.rows, self.ghost]), self.m.dtype, base=lo)
+        n_ids = len(self.m.ids)
+        keep, row_of = self.m.append_novel(rows, tau, tag, group, ids, known=known)
+        if self.defect == "gated_ids":                      # the first ids of the batch, not the kept rows' ids
+            self.m.ids = self.m.ids[:n_ids] + list(ids)[:int(keep.sum())]
+        self.ghost = None
+        return SimpleNamespace(keep=keep, row_of=row_of, kept=int(keep.sum()))
+
+    def erase(self, rows=None, scope=None):
+        m = self.m
+        old = SimpleNamespace(rows=m.rows, tags=m.tags, ords=m.ords, ids=m.ids)
+        out = m.erase_rows(rows) if rows is not None else m.erase_scopes(scope)
+        if out is None:
+            raise Refused("erase: the ring has wrapped")
+        n, keep = m.total, out.new_row_of >= 0
+        if self.defect == "stale_norm" and out.count:
+            self.stale = _norms(old.rows[:n], m.dtype)
+        if self.defect == "tags_not_moved":
+            m.tags = old.tags[:n]
+        if self.defect == "ordinals_not_rederived":
+            m.ords = old.ords[keep]
+        if self.defect == "ghost":
+            self.ghost = old.rows[n:]
+        if self.defect == "ids_not_remapped":
+            m.ids = old.ids[:n]
+        return SimpleNamespace(count=out.count, new_row_of=out.new_row_of)
+
+    def regroup_events(self, threshold, max_gap_ms=None, from_row=None):
+        m = self.m
+        if from_row is None:
+            return m.regroup_whole(threshold, max_gap_ms)
+        if self.defect == "wrong_side" and m.wrapped and from_row % m.capacity == 0 and m.base < from_row < m.total:
+            # the predecessor of the row in slot 0 is read from the slot on the other side of the wrap - the oldest live
+            # row, which does not resemble it: the row opens an event where it should continue one.  The count it reports
+            # is the right one, so that only what the call left in the columns gives it away
+            lo, flags = m.flags(threshold, max_gap_ms)
+            count = int(flags[from_row - lo:].sum())
+            flags[from_row - lo] = True
+            out = V.regroup_tail(m.keys[lo:], m.ords[lo:], flags, from_row - lo, lo)
+            m.keys, m.ords = np.concatenate([m.keys[:lo], out.keys]), np.concatenate([m.ords[:lo], out.ordinals])
+            m.state = out.state
+            return count
+        return m.regroup_tail(threshold, max_gap_ms, from_row)
+
+    def reset(self):
+        last = self.m.state[1]
+        self.m.reset()
+        self.ghost = self.stale = None
+        if self.defect == "reset_keeps_open":
+            self.m.state = (0, last, 1)
+
+    # -- readers
+    def _once(self, fn, *args):
+        """``fn(*args)``, computed once while the model stands still (every mutation moves the total or the state)."""
+        key = (fn.__name__, self.m.total, self.m.state, self.stale is None) + tuple(
+            a.tobytes() if isinstance(a, np.ndarray) else repr(a) for a in args)
+        if key not in self.memo:
+            self.memo = {k: v for k, v in self.memo.items() if k[1:3] == key[1:3]}
+            self.memo[key] = fn(*args)
+        return self.memo[key]
+
+    def topk(self, q, k, min_score=None, exact=False):
+        return self._once(self._topk, q, k, min_score)
+
+    def _topk(self, q, k, min_score):
+        lo, live = self.m.window()
+        if self.stale is not None and live.rows.shape[0]:   # scores from the norms the erase left behind
+            scale = np.ones(live.rows.shape[0])
+            n = min(self.stale.size, scale.size)
+            scale[:n] = _norms(live.rows[:n], self.m.dtype) / np.where(self.stale[:n] > 0, self.stale[:n], 1.0)
+            scores = cref.cosine_matrix(np.ascontiguousarray(q), np.ascontiguousarray(live.rows), dtype=self.m.dtype) * scale
+            r, s = S.scoped_topk_from_scores(scores, live.tags, LC.SCOPE_ALL, k, min_score=min_score, base=lo)
+            return s, r
+        if min_score is not None:
+            r, s = cref.cosine_topk(np.ascontiguousarray(q), np.ascontiguousarray(live.rows), k, dtype=self.m.dtype,
+                                    min_score=min_score)
+            return s, np.where(r >= 0, r + lo, -1)
+        r, s = self.m.exp_topk(q, k)
+        return s, r
+
+    def topk_grouped(self, q, k, exact=False):
+        r, s, kk = self._once(self.m.exp_grouped, q, k)
+        return s, r, kk
+
+    def topk_scoped(self, q, k, scope, exact=False):
+        r, s = self._once(self.m.exp_scoped, q, scope, k)
+        return s, r
+
+    def topk_grouped_scoped(self, q, k, scope, exact=False):
+        r, s, kk = self._once(self.m.exp_grouped_scoped, q, scope, k)
+        return s, r, kk
+
+    def topk_clip(self, clips, k, exact=False):
+        r, s = self._once(self.m.exp_clip, clips, k)
+        return s, r
+
+    def range_search(self, q, min_score, scope=None, max_hits=None, exact=False):
+        return [SimpleNamespace(rows=r[:max_hits], scores=s[:max_hits], count=c)
+                for r, s, c in self._once(self.m.exp_range, q, min_score, scope)]
+
+    def events(self, threshold, max_gap_ms=None, with_links=False):
+        link, seg = self._once(self.m.exp_events, threshold, max_gap_ms)
+        return SimpleNamespace(first_rows=seg.first_rows, event_of=seg.event_of, count=seg.count, links=link)
+
+    def summaries(self):
+        s = self._once(self.m.exp_summaries)
+        return SimpleNamespace(count=int(s.first_rows.size), **s._asdict())
+
+    uncertified_count = grouped_uncertified_count = scoped_uncertified_count = 0
+    group_scoped_uncertified_count = clip_uncertified_count = 0
+
+
+class FakeIO:
+    """What ``checkpoint`` needs beside the memory's surface, for the fake."""
+    t = staticmethod(lambda bits: np.asarray(bits))
+    i64 = staticmethod(lambda x: np.asarray(x, np.int64))
+    bits = staticmethod(lambda x: np.asarray(x))
+    ordinals = staticmethod(lambda mem: mem.m.window()[1].ords)
+    raw = staticmethod(lambda mem, n: mem.raw(n))
+    restore = staticmethod(lambda mem, capacity: FakeMemory(mem.m.restored(capacity), mem.defect))
+
+
+def _driver(script, dtype, defect=None, hooks=()):
+    _, cap, ring = SCRIPTS[script]
+    D = LC.DIMS[dtype]
+    return LC.Driver(FakeMemory(LC.Model(D, dtype, cap, ring), defect), LC.Model(D, dtype, cap, ring), FakeIO, hooks)
+
+
+# ---- 1. the model against itself -------------------------------------------------------------------------------------
+def _filled(dtype="f16", n=300, capacity=400, ring=False):
+    bits, scene = LC.pool(dtype)
+    m = LC.Model(LC.DIMS[dtype], dtype, capacity, ring)
+    m.append(bits[:n], [LC.make_tag(i // 120, (i % 120) * LC.MS) for i in range(n)], 10_000 + scene[:n] % 5,
+             [f"r{i}" for i in range(n)], np.arange(n))
+    return m, bits
+
+
+def _state(m):
+    return (m.rows.tobytes(), m.tags.tolist(), m.keys.tolist(), m.ords.tolist(), m.ids, m.prov.tolist(), m.state)
+
+
+def test_two_erases_equal_one_erase_of_the_union():
+    a, _ = _filled()
+    b, _ = _filled()
+    first = a.erase_scopes([(LC.make_tag(1, 10 * LC.MS), LC.make_tag(1, 70 * LC.MS))])
+    second = a.erase_rows([0, 5, 140, 141, 200, -1, 999])
+    old_ids = np.nonzero(first.new_row_of >= 0)[0][[0, 5, 140, 141, 200]]
+    union = E.mask_of_scopes(b.tags, [(LC.make_tag(1, 10 * LC.MS), LC.make_tag(1, 70 * LC.MS))]) | E.mask_of_rows(300, old_ids)
+    once = b._erase(union)
+    assert first.count == 61 and second.count == 5 and once.count == 66
+    assert np.array_equal(E.compose(first.new_row_of, second.new_row_of), once.new_row_of)
+    assert _state(a) == _state(b)
+    assert a.used == 300 and a.total == 234 and a.state[2] == 1 and a.ords[-1] + 1 == a.state[0]
+
+
+def test_restored_equals_a_fresh_model_of_the_window():
+    for ring, cap in ((False, 400), (True, 256)):
+        m, bits = _filled(capacity=cap, ring=ring)
+        m.regroup_whole(LC.THRESHOLD, LC.GAP_MS)
+        lo, live = m.window()
+        assert lo == (44 if ring else 0)
+        fresh = LC.Model(m.D, m.dtype, 400)
+        fresh.append(live.rows, live.tags, live.keys, live.ids, live.prov)
+        back = m.restored(400)
+        assert _state(back) == _state(fresh) and back.state == (int(G.group_ids(live.keys)[-1]) + 1, int(live.keys[-1]), 1)
+        assert np.array_equal(back.ords, G.group_ids(live.keys)) and back.ids[0] == f"r{lo}"
+        assert np.array_equal(back.rows, bits[back.prov])
+
+
+def test_append_follows_the_open_group_rule_and_reset_forgets_it():
+    m, bits = _filled(n=20)
+    last = int(m.keys[-1])
+    groups = m.state[0]
+    m.append(bits[20:23], [0, 1, 2], [last, last, 7], ["a", "b", "c"])         # continues, then opens
+    assert m.ords[-3:].tolist() == [groups - 1, groups - 1, groups] and m.state == (groups + 1, 7, 1)
+    m.regroup_whole(2.0, -1)                                                    # every row its own event; closed
+    assert m.state == (23, 22, 0) and m.keys.tolist() == list(range(23))
+    m.append(bits[23:24], [3], [22], ["d"])                                     # the closed group's key opens a group
+    assert m.ords[-1] == 23 and m.state == (24, 22, 1)
+    m.reset()
+    m.append(bits[:2], [0, 1], [22, 22], ["e", "f"])
+    assert m.ords.tolist() == [0, 0] and m.state == (1, 22, 1) and m.total == 2 and m.used == 2
+
+
+# ---- 2. the conditions of the scripts ----------------------------------------------------------------------------------
+def _conditions(seen):
+    def hook(label, d, p, exp):
+        lo, live = d.model.window()
+        n = live.rows.shape[0]
+        at = f"[{d.dtype} {label}] "
+        seen.append((label, n))
+        # provenance: every live row is, bit for bit, the row it came from
+        assert (live.prov >= 0).all() and all(np.array_equal(live.rows[i], d.src[int(live.prov[i])]) for i in range(n)), at
+        assert len(live.ids) == n and len(set(live.ids)) == n
+        readers = [exp["topk"][0], exp["grouped"][0], exp["scoped"][0], exp["grouped_scoped"][0]]
+        if n == 0:          # the empty memory: padding and zero counts everywhere
+            assert all((r == -1).all() for r in readers) and all((c[0] == -1).all() for c in exp["clip"]), at
+            assert all(c == 0 for _, _, c in exp["range"]) and exp["events"][1].count == 0, at
+            assert exp["summaries"].first_rows.size == 0, at
+            return
+        # well-formed: the ordinals the device keeps are the runs of the keys, so the key-based oracles apply
+        assert np.array_equal(live.ords - live.ords[0], G.group_ids(live.keys)), at + "ordinals are not the runs of the keys"
+        assert (live.keys >= 0).all(), at + "a plain append's key"
+        full = [i for i in range(6) if all((r[i] >= 0).all() for r in readers)]
+        short = [i for i in range(6) if any((r[i] < 0).any() for r in readers)]
+        assert len(full) >= 3 and short, at + f"queries with k hits everywhere {full}, with fewer {short}"
+        for i, sc in enumerate(p.scopes):
+            if sc[0] > sc[1]:                                # the empty scope: only padding
+                assert (exp["scoped"][0][i] == -1).all() and (exp["grouped_scoped"][0][i] == -1).all(), at
+                assert exp["range"][i][2] == 0, at
+        counts = [c for _, _, c in exp["range"]]
+        assert sum(counts) > 0 and max(counts) < p.max_hits, at + f"range counts {counts}"
+        assert exp["events"][1].count > 1, at
+        assert all((c[0][0] >= 0).any() for c in exp["clip"]), at + "a clip without a hit"
+        if n % 16 == 0:
+            raise AssertionError(at + "a multiple of 16 live rows")
+        gone = d.gone is not None and not any(np.array_equal(d.src[d.gone], r) for r in live.rows)
+        if gone:            # the row that was erased or gated away does not come back with score 1
+            assert exp["topk"][1][3, 0] < 0.9999, at
+    return hook
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_linear_script_conditions_and_the_unplanted_fake(dtype):
+    seen = []
+    d = _driver("linear", dtype, hooks=[_conditions(seen)])
+    end = LC.linear_script(d)
+    labels = [s[0] for s in seen]
+    assert len(labels) == 13 and labels[0].startswith("1 ") and labels[-1].startswith("10 ")
+    assert all(0.2 <= g <= 0.8 for g in d.gated) and len(d.gated) == 2, d.gated
+    live = dict(seen)
+    assert live["4 append source 1, tail regroup"] > 512 and live["7 append_novel into vacated slots"] > 512
+    assert live["9 empty"] == 0 and max(live.values()) < 1600 and d.stored + end.stored < 1600
+    assert end.model.state[2] == 1 and end.model.ords[0] == 0          # step 10 opened a group
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_ring_script_conditions_and_the_unplanted_fake(dtype):
+    seen = []
+
+    def wrap_hook(label, d, p, exp):
+        m = d.model
+        if m.ring and m.total > 2 * m.capacity:
+            lo, live = m.window()
+            cap = m.capacity
+            assert m.keys[2 * cap - 1] == m.keys[2 * cap], "no group spans slots capacity - 1 and 0"
+            assert (2 * cap - 1) % cap == cap - 1 and (2 * cap) % cap == 0
+            assert live.keys[0] < lo, "the first live group is not a cut one"
+            seen.append(("wrapped twice", lo))
+
+    d = _driver("ring", dtype, hooks=[_conditions(seen), wrap_hook])
+    LC.ring_script(d)
+    labels = [s[0] for s in seen]
+    assert labels.count("wrapped twice") == 2 and "7 restored linear" in labels and labels[-1] == "8 reset, append"
+    assert all(0.2 <= g <= 0.8 for g in d.gated) and len(d.gated) == 1, d.gated
+    assert d.stored < 1600
+
+
+# ---- 3. planted defects ----------------------------------------------------------------------------------------------------
+DEFECTS = [("stale_norm", "linear", "default topk"), ("tags_not_moved", "linear", "tags_host"),
+           ("ghost", "linear", "past the live count"), ("ids_not_remapped", "linear", "id_of"),
+           ("gated_ids", "linear", "id_of"), ("reset_keeps_open", "linear", "raw ordinals"),
+           ("ordinals_not_rederived", "ring", "ordinals relative"), ("ring_base", "ring", "first live row"),
+           ("wrong_side", "ring", "group_keys_host")]
+
+
+@pytest.mark.parametrize("defect,script,message", DEFECTS, ids=[d[0] for d in DEFECTS])
+def test_planted_defect_fails_the_checkpoint(defect, script, message):
+    d = _driver(script, "f16", defect)
+    with pytest.raises(AssertionError) as e:
+        SCRIPTS[script][0](d)
+    assert message in str(e.value), str(e.value)[:300]
+    assert d.log, "the defect showed before the first checkpoint passed: the script did not get going"
+
+
+def test_ghost_rows_are_seen_by_the_next_gated_append():
+    """The vacated slot that was not zeroed: the next gated batch is suppressed by a row that no longer exists."""
+    m, bits = _filled(n=60, capacity=100)
+    fake = FakeMemory(m, "ghost")
+    clean, _ = _filled(n=60, capacity=100)
+    for mem in (fake, FakeMemory(clean)):
+        mem.erase(rows=list(range(40, 60)))
+    batch = LC.noisy(bits[55:58], "f16", 3, 0.02)
+    tags, keys, ids = [LC.make_tag(2, i) for i in range(3)], [1, 2, 3], ["x", "y", "z"]
+    got = fake.append_novel(batch, 0.99, ids=ids, group=keys, tag=tags)
+    want = FakeMemory(clean).append_novel(batch, 0.99, ids=ids, group=keys, tag=tags)
+    assert want.kept == 3 and got.kept == 0 and (got.row_of >= 40).all()
