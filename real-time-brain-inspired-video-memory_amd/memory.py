@@ -40,6 +40,9 @@ from typing import List, NamedTuple, Optional, Sequence, Tuple
 import torch
 
 from . import _lib
+from .scratch import (NOVEL_MAX_ROWS, ClipScratch, EraseScratch, EventsScratch, GroupedScopedTopkScratch,  # noqa: F401
+                      GroupedTopkScratch, NoveltyScratch, RangeScratch, ScopedTopkScratch, Scratch, SummaryScratch,
+                      TopkScratch)
 
 
 INT64_MIN, INT64_MAX = -(1 << 63), (1 << 63) - 1
@@ -69,9 +72,6 @@ def scope_of(source: int, t0_ms: Optional[int] = None, t1_ms: Optional[int] = No
     lo = make_tag(source, 0 if t0_ms is None else t0_ms)
     hi = make_tag(source, TAG_MAX_MS - 1 if t1_ms is None else t1_ms)
     return lo, hi
-
-
-NOVEL_MAX_ROWS = 4096            # rows per vm_memory_append_novel call
 
 
 class Novelty(NamedTuple):
@@ -256,6 +256,72 @@ def _torch_dtype(name: str):
     return {"f16": torch.float16, "bf16": torch.bfloat16}[name]
 
 
+def _ptr(x: Optional[torch.Tensor]) -> C.c_void_p:
+    """The address of a tensor for the library; the null pointer for ``None`` and for an empty tensor."""
+    return C.c_void_p(x.data_ptr() if x is not None and x.numel() else 0)
+
+
+def _min_score_args(min_score: Optional[float]) -> Tuple[int, float]:
+    """-> (use_min, min_score) as the searches take the optional strict ``> min_score`` filter."""
+    return (0, 0.0) if min_score is None else (1, float(min_score))
+
+
+def _keep_alive(*tensors) -> None:
+    """The library reads a call's inputs asynchronously: keep each one (``None`` skipped) until the current stream has
+    consumed it."""
+    cur = torch.cuda.current_stream()
+    for t in tensors:
+        if t is not None:
+            t.record_stream(cur)
+
+
+class _Search(NamedTuple):
+    """One of the four top-k searches as ``EmbeddingMemory._search`` runs it: its entries, the memory it needs and the
+    arguments it takes beyond (queries, k, min_score, score_mode)."""
+    words: str                   # the search in an error message
+    scratch: type                # its scratch kind (which names the sizing call)
+    fast: str                    # the fp32 scan with the exact redo of what it cannot certify
+    exact: Optional[str]         # every pair scored exactly
+    grouped: bool = False        # needs a grouped memory
+    tagged: bool = False         # needs a tagged memory
+    refusal: str = ""            # ... and says so in these words
+    max_k: int = 64              # 0 = the library's own rule
+    scoped: bool = False         # takes a (lo, hi) tag range per query
+    keyed: bool = False          # returns the group keys as a third output
+    strided: bool = False        # passes the (row_stride, row_offset) pair
+    redo: Optional[str] = None   # a separate second stage that redoes the flagged queries
+
+
+_PLAIN = _Search("top-k", TopkScratch, "vm_topk_cosine", None, max_k=0, strided=True, redo="vm_topk_redo_flagged")
+_GROUPED = _Search("grouped top-k", GroupedTopkScratch, "vm_topk_cosine_grouped", "vm_topk_cosine_grouped_exact",
+                   grouped=True, keyed=True,
+                   refusal="topk_grouped needs a grouped memory (EmbeddingMemory(..., grouped=True))")
+_SCOPED = _Search("scoped top-k", ScopedTopkScratch, "vm_topk_cosine_scoped", "vm_topk_cosine_scoped_exact",
+                  tagged=True, scoped=True, strided=True,
+                  refusal="topk_scoped needs a tagged memory (EmbeddingMemory(..., tagged=True))")
+_GROUPED_SCOPED = _Search("scoped grouped top-k", GroupedScopedTopkScratch, "vm_topk_cosine_grouped_scoped",
+                          "vm_topk_cosine_grouped_scoped_exact", grouped=True, tagged=True, scoped=True, keyed=True,
+                          refusal="topk_grouped_scoped needs a grouped and tagged memory "
+                                  "(EmbeddingMemory(..., grouped=True, tagged=True))")
+
+
+def _last_property(kind: type, name: str, what: str) -> property:
+    """``last_*``: a buffer of the scratch that the last call of ``kind`` on this memory used, its own or the caller's."""
+    def get(self) -> Optional[torch.Tensor]:
+        s = self._last.get(kind)
+        return None if s is None else getattr(s, name)
+    return property(get, doc=what + " (a device tensor of the scratch that call used; ``None`` before the first call).")
+
+
+def _count_property(kind: type, what: str) -> property:
+    """``*_uncertified_count``: the memory's counter of ``kind``, which counts on whichever scratch a call used."""
+    def get(self) -> int:
+        c = self._uncert.get(kind)
+        return 0 if c is None else int(c.item())
+    return property(get, doc=what + " redid exhaustively since this memory was created (one 4-byte read-back; "
+                                    "synchronises).")
+
+
 class EmbeddingMemory:
     def __init__(self, capacity: int, dim: int, dtype: str = "f16", ring: bool = False, device: int = 0,
                  graph_uuid: Optional[str] = None, grouped: bool = False, tagged: bool = False):
@@ -271,26 +337,9 @@ class EmbeddingMemory:
         self.grouped = bool(grouped)
         self.tagged = bool(tagged)
         self._next_source = 0       # new_source
-        self._sws = None            # scoped top-k workspace (vm_topk_scoped_workspace_bytes), grown on demand
-        self._sflags = None         # per-query flags of the last scoped call (device int32)
-        self._suncert = None        # queries the scoped fast path could not certify (device int32, accumulates)
         self._next_group_key = 0    # above every key appended from host values (new_group_key)
         self._last_keys_dev = None  # keys of the last grouped append when they were a device tensor (host: unknown)
-        self._gws = None            # grouped top-k workspace (vm_topk_grouped_workspace_bytes), grown on demand
-        self._gflags = None         # per-query flags of the last grouped call (device int32)
-        self._guncert = None        # queries the grouped fast path could not certify (device int32, accumulates)
-        self._gsws = None           # scoped grouped top-k workspace (vm_topk_grouped_scoped_workspace_bytes)
-        self._gsflags = None        # per-query flags of the last scoped grouped call (device int32)
-        self._gsuncert = None       # queries the scoped grouped fast path could not certify (device int32, accumulates)
-        self._nscratch = None       # buffers of the gated append (NoveltyScratch), grown on demand
-        self._escratch = None       # buffers of erase (EraseScratch), made on demand
-        self._cscratch = None       # buffers of the clip search (ClipScratch), grown on demand
-        self._clast = None          # the scratch of the last clip call (last_clip_flags)
-        self._cuncert = None        # clips the clip search's fast path could not certify (device int32, accumulates)
-        self._rscratch = None       # buffers of the range search (RangeScratch), grown on demand
-        self._rlast = None          # the scratch of the last range call (last_range_rescored)
-        self._vscratch = None       # buffers of the event segmentation (EventsScratch), grown on demand
-        self._mscratch = None       # buffers of the group summaries (SummaryScratch), grown on demand
+        self._init_scratch()
         # Host tables: chunk id (reference pre_llm_injector.py:91) and {"time":..., "content":...} (for
         # _vector_search_chunks) of row (table_base + i).  table_base stays 0 unless a ring has wrapped far enough for
         # the slots of overwritten rows to be dropped (see _trim_tables); use id_of / meta_of for row -> entry.
@@ -306,7 +355,33 @@ class EmbeddingMemory:
             self.ctx.check(create(self.ctx.handle, self.capacity, self.dim, _lib.DTYPES[dtype], 1 if ring else 0,
                                   C.byref(h)))
         self.handle = h
-        self._scratch = TopkScratch(self.device)
+
+    # ---- scratch: one owner rule for every kind (scratch.py) -----------------------------------------
+    def _init_scratch(self) -> None:
+        self._own = {}              # scratch kind -> this memory's own instance, made on first use, replaced to grow
+        self._last = {}             # scratch kind -> the scratch of the last call of that kind (last_*)
+        self._uncert = {}           # scratch kind -> device int32 [1]: what its fast path could not certify (accumulates)
+
+    def _resolve(self, kind: type, scratch: Optional[Scratch], *shape) -> Scratch:
+        """The scratch a call of ``shape`` uses.  ``scratch=None``: this memory's own of that kind, created on first use
+        and REPLACED by a new object when it does not fit (never resized: a captured graph may hold its addresses).  A
+        caller-owned one must fit."""
+        if scratch is None:
+            scratch = self._own.get(kind)
+            if scratch is None:
+                scratch = self._own[kind] = kind.for_(self, *shape)
+            elif not scratch.fits(self, *shape):
+                scratch = self._own[kind] = scratch.grown(self, *shape)     # sized for this call: it fits
+        elif not scratch.fits(self, *shape):
+            raise ValueError(f"caller-owned {kind.__name__} is too small for this call {shape}")
+        return scratch
+
+    def _counter(self, kind: type) -> torch.Tensor:
+        """The uncertified counter of a kind: the memory's, whichever scratch a call uses."""
+        c = self._uncert.get(kind)
+        if c is None:
+            c = self._uncert[kind] = torch.zeros(1, dtype=torch.int32, device=self.device)
+        return c
 
     def close(self):
         if getattr(self, "handle", None):
@@ -356,25 +431,15 @@ class EmbeddingMemory:
             raise ValueError("ids and rows differ in length")
         keys = self._group_keys_for(B, group)
         tags = self._tags_for(B, tag)
-        first = C.c_int64(0)
+        first, st = C.c_int64(0), _lib.current_stream_ptr()
         if tags is not None:
-            self.ctx.check(self.L.vm_memory_append_tagged(self.handle, C.c_void_p(t.data_ptr()), B,
-                                                          C.c_void_p(tags.data_ptr()),
-                                                          C.c_void_p(keys.data_ptr() if keys is not None else 0),
-                                                          C.byref(first), _lib.current_stream_ptr()))
-            tags.record_stream(torch.cuda.current_stream())
-            if keys is not None:
-                keys.record_stream(torch.cuda.current_stream())
+            rc = self.L.vm_memory_append_tagged(self.handle, _ptr(t), B, _ptr(tags), _ptr(keys), C.byref(first), st)
         elif keys is None:
-            self.ctx.check(self.L.vm_memory_append(self.handle, C.c_void_p(t.data_ptr()), B, C.byref(first),
-                                                   _lib.current_stream_ptr()))
+            rc = self.L.vm_memory_append(self.handle, _ptr(t), B, C.byref(first), st)
         else:
-            self.ctx.check(self.L.vm_memory_append_grouped(self.handle, C.c_void_p(t.data_ptr()), B,
-                                                           C.c_void_p(keys.data_ptr()), C.byref(first),
-                                                           _lib.current_stream_ptr()))
-            keys.record_stream(torch.cuda.current_stream())
-        # the kernel reads `t` asynchronously: keep it alive until the stream has consumed it
-        t.record_stream(torch.cuda.current_stream())
+            rc = self.L.vm_memory_append_grouped(self.handle, _ptr(t), B, _ptr(keys), C.byref(first), st)
+        self.ctx.check(rc)
+        _keep_alive(t, tags, keys)
         self.ids.extend(list(ids) if ids is not None else [None] * B)
         self.meta.extend(list(meta) if meta is not None else [None] * B)
         self._trim_tables()
@@ -384,9 +449,7 @@ class EmbeddingMemory:
     def prepare_append_novel(self, B: int) -> "NoveltyScratch":
         """Size this memory's own gated-append buffers for batches of up to ``B`` rows now (before a graph capture: a
         capture must not allocate)."""
-        if self._nscratch is None or not self._nscratch.fits(self, B):
-            self._nscratch = NoveltyScratch.for_(self, B)
-        return self._nscratch
+        return self._resolve(NoveltyScratch, None, int(B))
 
     @staticmethod
     def _check_threshold(threshold) -> float:
@@ -444,18 +507,11 @@ class EmbeddingMemory:
 
     def _append_novel_call(self, t, tau, ks, kr, stride, keys, tags, scratch):
         B = t.shape[0]
-        if scratch is None:
-            scratch = self.prepare_append_novel(B)
-        elif not scratch.fits(self, B):
-            raise ValueError("caller-owned novelty scratch is too small for this batch")
-        ptr = lambda x: C.c_void_p(x.data_ptr() if x is not None else 0)
+        scratch = self._resolve(NoveltyScratch, scratch, B)
         self.ctx.check(self.L.vm_memory_append_novel(
-            self.handle, ptr(t), B, tau, ptr(ks), ptr(kr), int(stride), ptr(tags), ptr(keys), ptr(scratch.keep),
-            ptr(scratch.row_of), ptr(scratch.count), ptr(scratch.ws), scratch.ws.numel(), _lib.current_stream_ptr()))
-        cur = torch.cuda.current_stream()
-        for x in (t, ks, kr, keys, tags):
-            if x is not None:
-                x.record_stream(cur)
+            self.handle, _ptr(t), B, tau, _ptr(ks), _ptr(kr), int(stride), _ptr(tags), _ptr(keys), _ptr(scratch.keep),
+            _ptr(scratch.row_of), _ptr(scratch.count), _ptr(scratch.ws), scratch.ws.numel(), _lib.current_stream_ptr()))
+        _keep_alive(t, ks, kr, keys, tags)
         return scratch.keep[:B], scratch.row_of[:B], scratch.count
 
     def append_novel(self, rows, threshold, against="memory", known=None, ids: Optional[Sequence[str]] = None,
@@ -504,7 +560,7 @@ class EmbeddingMemory:
             ks, kr, stride = self._known_pair(known, B)
         if B > NOVEL_MAX_ROWS and (known is not None or against is None):
             raise ValueError(f"more than {NOVEL_MAX_ROWS} rows need against='memory' or a scope")
-        sc = self._scope_tensor(scope, B).t() if scope is not None else None     # [B, 2] view
+        sc = self._scopes(scope, B).t() if scope is not None else None     # [B, 2] view
         keys = self._group_keys_for(B, group)
         tags = self._tags_for(B, tag)
         keep_parts, row_parts, kept = [], [], 0
@@ -541,25 +597,7 @@ class EmbeddingMemory:
     def prepare_erase(self, segment_rows: int = 0) -> "EraseScratch":
         """Size this memory's own erase buffers now (before a graph capture: a capture must not allocate).
         ``segment_rows``: rows that move through the scratch at a time; 0 = the library's default."""
-        need = int(self.L.vm_memory_erase_workspace_bytes(self.handle, int(segment_rows)))
-        if self._escratch is None or self._escratch.ws.numel() != max(need, 256):
-            self._escratch = EraseScratch.for_(self, segment_rows)
-        return self._escratch
-
-    def _erase_scopes(self, scope) -> torch.Tensor:
-        """-> device int64 [2, n] (row 0 = lo, row 1 = hi) from one (lo, hi), a sequence of pairs, or an int64 [n, 2]
-        tensor (a device tensor is not read on the host)."""
-        if isinstance(scope, torch.Tensor):
-            if scope.dtype != torch.int64 or scope.dim() != 2 or scope.shape[1] != 2 or scope.shape[0] < 1:
-                raise ValueError("a scope tensor must be int64 [n, 2], n >= 1")
-            return scope.to(self.device).t().contiguous()
-        pairs = list(scope)
-        if len(pairs) == 2 and not hasattr(pairs[0], "__len__"):
-            pairs = [pairs]
-        if not pairs or any(len(p) != 2 for p in pairs):
-            raise ValueError("a scope is a pair (lo, hi), or a sequence of at least one pair")
-        vals = [[int(p[0]) for p in pairs], [int(p[1]) for p in pairs]]
-        return torch.tensor(vals, dtype=torch.int64).to(self.device)
+        return self._resolve(EraseScratch, None, int(segment_rows))
 
     def enqueue_erase(self, rows=None, scope=None, scratch: Optional["EraseScratch"] = None
                       ) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -575,24 +613,19 @@ class EmbeddingMemory:
         _check_erase_selectors(rows, scope)
         if scope is not None and not self.tagged:
             raise ValueError("erase by scope needs a tagged memory (EmbeddingMemory(..., tagged=True))")
-        if scratch is None:
-            scratch = self._escratch or self.prepare_erase()
-        ptr = lambda x: C.c_void_p(x.data_ptr())
-        st = _lib.current_stream_ptr()
+        scratch = self._resolve(EraseScratch, scratch)     # any segment size serves: prepare_erase chooses one
+        tail = (_ptr(scratch.new_row_of), _ptr(scratch.erased), _ptr(scratch.ws), scratch.ws.numel(),
+                _lib.current_stream_ptr())
         if scope is not None:
-            sel = self._erase_scopes(scope)
-            self.ctx.check(self.L.vm_memory_erase_scoped(self.handle, ptr(sel[0]), ptr(sel[1]), sel.shape[1],
-                                                         ptr(scratch.new_row_of), ptr(scratch.erased), ptr(scratch.ws),
-                                                         scratch.ws.numel(), st))
+            sel = self._scopes(scope)
+            self.ctx.check(self.L.vm_memory_erase_scoped(self.handle, _ptr(sel[0]), _ptr(sel[1]), sel.shape[1], *tail))
         else:
             if isinstance(rows, torch.Tensor):
                 sel = rows.to(device=self.device, dtype=torch.int64).reshape(-1).contiguous()
             else:
                 sel = torch.tensor([int(r) for r in rows], dtype=torch.int64).to(self.device)
-            self.ctx.check(self.L.vm_memory_erase_rows(self.handle, C.c_void_p(sel.data_ptr() if sel.numel() else 0),
-                                                       sel.numel(), ptr(scratch.new_row_of), ptr(scratch.erased),
-                                                       ptr(scratch.ws), scratch.ws.numel(), st))
-        sel.record_stream(torch.cuda.current_stream())
+            self.ctx.check(self.L.vm_memory_erase_rows(self.handle, _ptr(sel), sel.numel(), *tail))
+        _keep_alive(sel)
         return scratch.new_row_of, scratch.erased
 
     def erase(self, rows=None, scope=None) -> Erased:
@@ -637,20 +670,34 @@ class EmbeddingMemory:
         self._next_source += 1
         return src
 
+    def _int64_column(self, value, B: int, what: str) -> Tuple[torch.Tensor, Optional[List[int]]]:
+        """One int for every row, one per row as a sequence, or an int64 tensor (a 0-dim one counts as one int; any other
+        is passed to the device without a host read) -> (device int64 [B], the values where the host knows them)."""
+        known = None
+        if isinstance(value, torch.Tensor) and value.dim() > 0:
+            col = value.to(device=self.device, dtype=torch.int64).reshape(-1).contiguous()
+        elif isinstance(value, (list, tuple)) or (hasattr(value, "shape") and len(value.shape) > 0):
+            known = [int(x) for x in value]
+            col = torch.tensor(known, dtype=torch.int64).to(self.device)
+        else:
+            known = [int(value)]
+            col = torch.full((B,), known[0], dtype=torch.int64, device=self.device)
+        if col.numel() != B:
+            raise ValueError(f"{col.numel()} {what} for {B} rows")
+        return col, known
+
+    def _int64_cell(self, value) -> torch.Tensor:
+        """An int, or a device tensor whose first element counts (not read on the host) -> device int64 [1]."""
+        if isinstance(value, torch.Tensor):
+            return value.to(device=self.device, dtype=torch.int64).reshape(-1)[:1].contiguous()
+        return torch.tensor([int(value)], dtype=torch.int64).to(self.device)
+
     def _tags_for(self, B: int, tag) -> Optional[torch.Tensor]:
         if tag is None:
             return None
         if not self.tagged:
             raise ValueError("tags need a tagged memory (EmbeddingMemory(..., tagged=True))")
-        if isinstance(tag, torch.Tensor) and tag.dim() > 0:
-            tags = tag.to(device=self.device, dtype=torch.int64).reshape(-1).contiguous()
-        elif isinstance(tag, (list, tuple)) or (hasattr(tag, "shape") and len(getattr(tag, "shape")) > 0):
-            tags = torch.tensor([int(x) for x in tag], dtype=torch.int64).to(self.device)
-        else:
-            tags = torch.full((B,), int(tag), dtype=torch.int64, device=self.device)
-        if tags.numel() != B:
-            raise ValueError(f"{tags.numel()} tags for {B} rows")
-        return tags
+        return self._int64_column(tag, B, "tags")[0]
 
     def new_group_key(self) -> int:
         """A key no earlier ``new_group_key`` call of this memory returned (and above every key appended so far from
@@ -671,21 +718,10 @@ class EmbeddingMemory:
             if self._last_keys_dev is not None and self._last_keys_dev.numel():
                 self._next_group_key = max(self._next_group_key, int(self._last_keys_dev[-1]) + 1)
             group = self.new_group_key()
-        self._last_keys_dev = None
-        if isinstance(group, torch.Tensor) and group.dim() > 0:
-            keys = group.to(device=self.device, dtype=torch.int64).reshape(-1).contiguous()
-            self._last_keys_dev = keys
-        elif isinstance(group, (list, tuple)) or (hasattr(group, "shape") and len(getattr(group, "shape")) > 0):
-            vals = [int(x) for x in group]
-            if vals:
-                self._next_group_key = max(self._next_group_key, max(vals) + 1)
-            keys = torch.tensor(vals, dtype=torch.int64).to(self.device)
-        else:
-            key = int(group)
-            self._next_group_key = max(self._next_group_key, key + 1)
-            keys = torch.full((B,), key, dtype=torch.int64, device=self.device)
-        if keys.numel() != B:
-            raise ValueError(f"{keys.numel()} group keys for {B} rows")
+        keys, known = self._int64_column(group, B, "group keys")
+        self._last_keys_dev = keys if known is None else None
+        if known:
+            self._next_group_key = max(self._next_group_key, max(known) + 1)
         return keys
 
     def _trim_tables(self) -> None:
@@ -710,9 +746,9 @@ class EmbeddingMemory:
         self._trim_tables()
         return total
 
-    def prepare_topk(self, Q: int, k: int) -> None:
+    def prepare_topk(self, Q: int, k: int) -> TopkScratch:
         """Size the shared top-k scratch for (Q, k) now, so a later eager call allocates nothing."""
-        self._scratch = self._scratch.fit(self, Q, k)
+        return self._resolve(TopkScratch, None, int(Q), int(k))
 
     def reset(self):
         self.ctx.check(self.L.vm_memory_reset(self.handle, _lib.current_stream_ptr()))
@@ -747,52 +783,67 @@ class EmbeddingMemory:
         ``scratch``: workspaces + flag / counter buffers owned by the caller (streaming sessions capture their
         addresses into a hipGraph); default = this memory's own, used by eager calls on the current stream.
         """
+        if not exact and k <= 58:
+            return self._search(_PLAIN, queries, k, None, min_score, score_mode, False, scratch,
+                                (row_stride, row_offset), redo)
         q = self._as_rows(queries)
         Q = q.shape[0]
         scores = torch.empty((Q, k), dtype=torch.float64, device=self.device)
         rows = torch.empty((Q, k), dtype=torch.int64, device=self.device)
-        st = _lib.current_stream_ptr()
-        use_min = 0 if min_score is None else 1
-        ms = 0.0 if min_score is None else float(min_score)
-        if not exact and k <= 58:
-            if scratch is None:
-                scratch = self._scratch = self._scratch.fit(self, Q, k)
-            elif not scratch.fits(self, Q, k):
-                raise ValueError("caller-owned top-k scratch is too small for this (Q, k)")
-            self.ctx.check(self.L.vm_topk_cosine(
-                self.handle, C.c_void_p(q.data_ptr()), Q, k, use_min, ms, int(score_mode), int(row_stride),
-                int(row_offset), C.c_void_p(scores.data_ptr()), C.c_void_p(rows.data_ptr()),
-                C.c_void_p(scratch.uncert.data_ptr()), C.c_void_p(scratch.flags.data_ptr()),
-                C.c_void_p(scratch.ws.data_ptr()), scratch.ws.numel(), st))
-            if redo:
-                self.ctx.check(self.L.vm_topk_redo_flagged(
-                    self.handle, C.c_void_p(q.data_ptr()), Q, k, use_min, ms, int(score_mode), int(row_stride),
-                    int(row_offset), C.c_void_p(scratch.flags.data_ptr()), C.c_void_p(scores.data_ptr()),
-                    C.c_void_p(rows.data_ptr()), C.c_void_p(scratch.redo_ws.data_ptr()), scratch.redo_ws.numel(),
-                    st))
-            q.record_stream(torch.cuda.current_stream())
-            return scores, rows
         need = int(self.L.vm_topk_exact_workspace_bytes(self.handle, Q, k))
         ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
         self.ctx.check(self.L.vm_topk_cosine_exact(
-            self.handle, C.c_void_p(q.data_ptr()), Q, k, use_min, ms, int(score_mode), int(row_stride),
-            int(row_offset), C.c_void_p(scores.data_ptr()), C.c_void_p(rows.data_ptr()),
-            C.c_void_p(ws.data_ptr()), ws.numel(), st))
-        ws.record_stream(torch.cuda.current_stream())
+            self.handle, _ptr(q), Q, k, *_min_score_args(min_score), int(score_mode), int(row_stride),
+            int(row_offset), _ptr(scores), _ptr(rows), _ptr(ws), ws.numel(), _lib.current_stream_ptr()))
+        _keep_alive(ws)
         return scores, rows
 
-    def prepare_topk_grouped(self, Q: int, k: int) -> None:
+    def _search(self, kind: _Search, queries, k, scope, min_score, score_mode, exact, scratch, stride=(1, 0),
+                redo=True) -> Tuple[torch.Tensor, ...]:
+        """The one body of ``topk``, ``topk_grouped``, ``topk_scoped`` and ``topk_grouped_scoped``.  The memory-kind and
+        ``k`` checks come before anything that needs a device."""
+        if (kind.grouped and not self.grouped) or (kind.tagged and not self.tagged):
+            raise ValueError(kind.refusal)
+        if kind.max_k and not 1 <= int(k) <= kind.max_k:
+            raise ValueError(f"{kind.words} supports 1 <= k <= {kind.max_k}, got {k}")
+        q = self._as_rows(queries)
+        Q, k = q.shape[0], int(k)
+        sc = self._scopes(scope, Q) if kind.scoped else None
+        s = self._resolve(kind.scratch, scratch, Q, k)
+        outs = [torch.empty((Q, k), dtype=dt, device=self.device)
+                for dt in (torch.float64, torch.int64, torch.int64)[:3 if kind.keyed else 2]]
+        head = [self.handle, _ptr(q), Q, k]
+        if kind.scoped:
+            head += [_ptr(sc[0]), _ptr(sc[1])]
+        head += [*_min_score_args(min_score), int(score_mode)]
+        if kind.strided:
+            head += [int(stride[0]), int(stride[1])]
+        outp = [_ptr(o) for o in outs]
+        st = _lib.current_stream_ptr()
+        if exact:
+            self.ctx.check(getattr(self.L, kind.exact)(*head, *outp, _ptr(s.ws), s.ws.numel(), st))
+        else:   # plain top-k counts on its scratch (a session reads its own), the others on the memory
+            uncert = s.uncert if kind is _PLAIN else self._counter(kind.scratch)
+            self.ctx.check(getattr(self.L, kind.fast)(*head, *outp, _ptr(uncert), _ptr(s.flags), _ptr(s.ws),
+                                                      s.ws.numel(), st))
+            if kind.redo and redo:
+                self.ctx.check(getattr(self.L, kind.redo)(*head, _ptr(s.flags), *outp, _ptr(s.redo_ws),
+                                                          s.redo_ws.numel(), st))
+        _keep_alive(q, sc)
+        self._last[kind.scratch] = s
+        return tuple(outs)
+
+    def _prepare_search(self, kind: _Search, Q: int, k: int) -> Scratch:
+        self._counter(kind.scratch)
+        return self._resolve(kind.scratch, None, int(Q), int(k))
+
+    def prepare_topk_grouped(self, Q: int, k: int) -> GroupedTopkScratch:
         """Size the grouped top-k workspace for (Q, k) now (before a graph capture: a capture must not allocate)."""
-        need = int(self.L.vm_topk_grouped_workspace_bytes(self.handle, int(Q), int(k)))
-        if self._gws is None or self._gws.numel() < need:
-            self._gws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
-        if self._gflags is None or self._gflags.numel() < Q:
-            self._gflags = torch.zeros(max(Q, 1), dtype=torch.int32, device=self.device)
-        if self._guncert is None:
-            self._guncert = torch.zeros(1, dtype=torch.int32, device=self.device)
+        return self._prepare_search(_GROUPED, Q, k)
 
     def topk_grouped(self, queries, k: int, min_score: Optional[float] = None, score_mode: int = _lib.VM_SCORE_RAW,
-                     exact: bool = False) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+                     exact: bool = False, scratch: Optional[GroupedTopkScratch] = None
+                     ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """-> (scores [Q,k] float64, rows [Q,k] int64, keys [Q,k] int64): the k best GROUPS of a grouped memory.
 
         The exhaustive row ranking of ``topk`` (score desc, row asc; score mapping and > min_score filter) with only the
@@ -800,65 +851,41 @@ class EmbeddingMemory:
         reaching it, ``keys`` its group key; -1 / 0.0 / -1 padded.  Always the exhaustive answer: the fp32 fast path
         redoes the queries it cannot certify on the device, in the same call (csrc/topk_group.hip).  ``exact=True``
         scores every row exactly for every query (slow).  1 <= k <= 64.  The per-query flags of the last call (why a
-        query was redone, vm_topk_flag) are in ``last_group_flags``."""
-        if not self.grouped:
-            raise ValueError("topk_grouped needs a grouped memory (EmbeddingMemory(..., grouped=True))")
-        if not 1 <= int(k) <= 64:
-            raise ValueError(f"grouped top-k supports 1 <= k <= 64, got {k}")
-        q = self._as_rows(queries)
-        Q = q.shape[0]
-        self.prepare_topk_grouped(Q, k)
-        scores = torch.empty((Q, k), dtype=torch.float64, device=self.device)
-        rows = torch.empty((Q, k), dtype=torch.int64, device=self.device)
-        keys = torch.empty((Q, k), dtype=torch.int64, device=self.device)
-        st = _lib.current_stream_ptr()
-        use_min = 0 if min_score is None else 1
-        ms = 0.0 if min_score is None else float(min_score)
-        if exact:
-            self.ctx.check(self.L.vm_topk_cosine_grouped_exact(
-                self.handle, C.c_void_p(q.data_ptr()), Q, int(k), use_min, ms, int(score_mode),
-                C.c_void_p(scores.data_ptr()), C.c_void_p(rows.data_ptr()), C.c_void_p(keys.data_ptr()),
-                C.c_void_p(self._gws.data_ptr()), self._gws.numel(), st))
-        else:
-            self.ctx.check(self.L.vm_topk_cosine_grouped(
-                self.handle, C.c_void_p(q.data_ptr()), Q, int(k), use_min, ms, int(score_mode),
-                C.c_void_p(scores.data_ptr()), C.c_void_p(rows.data_ptr()), C.c_void_p(keys.data_ptr()),
-                C.c_void_p(self._guncert.data_ptr()), C.c_void_p(self._gflags.data_ptr()),
-                C.c_void_p(self._gws.data_ptr()), self._gws.numel(), st))
-        q.record_stream(torch.cuda.current_stream())
-        return scores, rows, keys
+        query was redone, vm_topk_flag) are in ``last_group_flags``.  ``scratch``: as in ``topk`` - a
+        ``GroupedTopkScratch`` the caller owns (a graph capture), default this memory's own."""
+        return self._search(_GROUPED, queries, k, None, min_score, score_mode, exact, scratch)
 
-    def prepare_topk_scoped(self, Q: int, k: int) -> None:
+    def prepare_topk_scoped(self, Q: int, k: int) -> ScopedTopkScratch:
         """Size the scoped top-k workspace for (Q, k) now (before a graph capture: a capture must not allocate)."""
-        need = int(self.L.vm_topk_scoped_workspace_bytes(self.handle, int(Q), int(k)))
-        if self._sws is None or self._sws.numel() < need:
-            self._sws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
-        if self._sflags is None or self._sflags.numel() < Q:
-            self._sflags = torch.zeros(max(Q, 1), dtype=torch.int32, device=self.device)
-        if self._suncert is None:
-            self._suncert = torch.zeros(1, dtype=torch.int32, device=self.device)
+        return self._prepare_search(_SCOPED, Q, k)
 
-    def _scope_tensor(self, scope, Q: int) -> torch.Tensor:
-        """-> device int64 [2, Q] (row 0 = lo, row 1 = hi) from one (lo, hi), Q pairs, or an int64 [Q, 2] tensor (a
-        device tensor is not read on the host)."""
+    def _scopes(self, scope, n: Optional[int] = None) -> torch.Tensor:
+        """-> device int64 [2, n] (row 0 = lo, row 1 = hi) from one (lo, hi), a sequence of pairs, or an int64 [n, 2]
+        tensor (a device tensor is not read on the host).  ``n`` given: exactly ``n`` pairs, one pair standing for all
+        of them; ``n=None``: any number of pairs, at least one."""
         if isinstance(scope, torch.Tensor):
             if scope.dtype != torch.int64 or scope.dim() != 2 or scope.shape[1] != 2:
-                raise ValueError("a scope tensor must be int64 [Q, 2]")
-            if scope.shape[0] != Q:
-                raise ValueError(f"{scope.shape[0]} scopes for {Q} queries")
+                raise ValueError("a scope tensor must be int64 [n, 2]")
+            pairs, count = None, scope.shape[0]
+        else:
+            pairs = list(scope)
+            if len(pairs) == 2 and not hasattr(pairs[0], "__len__"):
+                pairs = [pairs] * (1 if n is None else n)
+            count = len(pairs)
+        if n is None and count < 1:
+            raise ValueError("0 scopes: at least one pair (lo, hi) is needed")
+        if n is not None and count != n:
+            raise ValueError(f"{count} scopes for {n} queries")
+        if pairs is None:
             return scope.to(self.device).t().contiguous()
-        pairs = list(scope)
-        if len(pairs) == 2 and not hasattr(pairs[0], "__len__"):
-            pairs = [pairs] * Q
-        if len(pairs) != Q:
-            raise ValueError(f"{len(pairs)} scopes for {Q} queries")
         if any(len(p) != 2 for p in pairs):
             raise ValueError("a scope is a pair (lo, hi)")
         vals = [[int(p[0]) for p in pairs], [int(p[1]) for p in pairs]]
         return torch.tensor(vals, dtype=torch.int64).to(self.device)
 
     def topk_scoped(self, queries, k: int, scope, min_score: Optional[float] = None,
-                    score_mode: int = _lib.VM_SCORE_RAW, exact: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+                    score_mode: int = _lib.VM_SCORE_RAW, exact: bool = False,
+                    scratch: Optional[ScopedTopkScratch] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """-> (scores [Q,k] float64, rows [Q,k] int64): the k best rows of a tagged memory whose tag lies in the query's
         scope, an inclusive range ``(lo, hi)``: one for all queries, a sequence of Q pairs, or an int64 ``[Q, 2]`` tensor
         (``scope_of`` builds the range of a video or of a time window of it).
@@ -867,48 +894,17 @@ class EmbeddingMemory:
         in-scope rows only; -1 / 0.0 padded; an empty scope gives an all-padded row.  Always the exhaustive answer: the
         fp32 fast path redoes the queries it cannot certify on the device, in the same call (csrc/topk_scope.hip).
         ``exact=True`` scores every in-scope pair exactly (slow).  1 <= k <= 64.  The per-query flags of the last call
-        (why a query was redone, vm_topk_flag) are in ``last_scope_flags``."""
-        if not self.tagged:
-            raise ValueError("topk_scoped needs a tagged memory (EmbeddingMemory(..., tagged=True))")
-        if not 1 <= int(k) <= 64:
-            raise ValueError(f"scoped top-k supports 1 <= k <= 64, got {k}")
-        q = self._as_rows(queries)
-        Q = q.shape[0]
-        sc = self._scope_tensor(scope, Q)
-        self.prepare_topk_scoped(Q, k)
-        scores = torch.empty((Q, k), dtype=torch.float64, device=self.device)
-        rows = torch.empty((Q, k), dtype=torch.int64, device=self.device)
-        st = _lib.current_stream_ptr()
-        use_min = 0 if min_score is None else 1
-        ms = 0.0 if min_score is None else float(min_score)
-        lo, hi = C.c_void_p(sc[0].data_ptr()), C.c_void_p(sc[1].data_ptr())
-        if exact:
-            self.ctx.check(self.L.vm_topk_cosine_scoped_exact(
-                self.handle, C.c_void_p(q.data_ptr()), Q, int(k), lo, hi, use_min, ms, int(score_mode), 1, 0,
-                C.c_void_p(scores.data_ptr()), C.c_void_p(rows.data_ptr()),
-                C.c_void_p(self._sws.data_ptr()), self._sws.numel(), st))
-        else:
-            self.ctx.check(self.L.vm_topk_cosine_scoped(
-                self.handle, C.c_void_p(q.data_ptr()), Q, int(k), lo, hi, use_min, ms, int(score_mode), 1, 0,
-                C.c_void_p(scores.data_ptr()), C.c_void_p(rows.data_ptr()),
-                C.c_void_p(self._suncert.data_ptr()), C.c_void_p(self._sflags.data_ptr()),
-                C.c_void_p(self._sws.data_ptr()), self._sws.numel(), st))
-        q.record_stream(torch.cuda.current_stream())
-        sc.record_stream(torch.cuda.current_stream())
-        return scores, rows
+        (why a query was redone, vm_topk_flag) are in ``last_scope_flags``.  ``scratch``: as in ``topk`` - a
+        ``ScopedTopkScratch`` the caller owns (a graph capture), default this memory's own."""
+        return self._search(_SCOPED, queries, k, scope, min_score, score_mode, exact, scratch)
 
-    def prepare_topk_grouped_scoped(self, Q: int, k: int) -> None:
+    def prepare_topk_grouped_scoped(self, Q: int, k: int) -> GroupedScopedTopkScratch:
         """Size the scoped grouped top-k workspace for (Q, k) now (before a graph capture: a capture must not allocate)."""
-        need = int(self.L.vm_topk_grouped_scoped_workspace_bytes(self.handle, int(Q), int(k)))
-        if self._gsws is None or self._gsws.numel() < need:
-            self._gsws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
-        if self._gsflags is None or self._gsflags.numel() < Q:
-            self._gsflags = torch.zeros(max(Q, 1), dtype=torch.int32, device=self.device)
-        if self._gsuncert is None:
-            self._gsuncert = torch.zeros(1, dtype=torch.int32, device=self.device)
+        return self._prepare_search(_GROUPED_SCOPED, Q, k)
 
     def topk_grouped_scoped(self, queries, k: int, scope, min_score: Optional[float] = None,
-                            score_mode: int = _lib.VM_SCORE_RAW, exact: bool = False
+                            score_mode: int = _lib.VM_SCORE_RAW, exact: bool = False,
+                            scratch: Optional[GroupedScopedTopkScratch] = None
                             ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """-> (scores [Q,k] float64, rows [Q,k] int64, keys [Q,k] int64): the k best GROUPS of a tagged, grouped memory
         among the rows whose tag lies in the query's scope - one hit per event within a video or a time window.
@@ -922,47 +918,16 @@ class EmbeddingMemory:
         its neighbours, and a group with no in-scope row is not returned.  Always the exhaustive answer: the fp32 fast
         path redoes the queries it cannot certify on the device, in the same call (csrc/topk_group_scope.hip).
         ``exact=True`` scores every in-scope pair exactly (slow).  1 <= k <= 64.  The per-query flags of the last call
-        (why a query was redone, vm_topk_flag) are in ``last_group_scope_flags``."""
-        if not (self.grouped and self.tagged):
-            raise ValueError("topk_grouped_scoped needs a grouped and tagged memory "
-                             "(EmbeddingMemory(..., grouped=True, tagged=True))")
-        if not 1 <= int(k) <= 64:
-            raise ValueError(f"scoped grouped top-k supports 1 <= k <= 64, got {k}")
-        q = self._as_rows(queries)
-        Q = q.shape[0]
-        sc = self._scope_tensor(scope, Q)
-        self.prepare_topk_grouped_scoped(Q, k)
-        scores = torch.empty((Q, k), dtype=torch.float64, device=self.device)
-        rows = torch.empty((Q, k), dtype=torch.int64, device=self.device)
-        keys = torch.empty((Q, k), dtype=torch.int64, device=self.device)
-        st = _lib.current_stream_ptr()
-        use_min = 0 if min_score is None else 1
-        ms = 0.0 if min_score is None else float(min_score)
-        lo, hi = C.c_void_p(sc[0].data_ptr()), C.c_void_p(sc[1].data_ptr())
-        if exact:
-            self.ctx.check(self.L.vm_topk_cosine_grouped_scoped_exact(
-                self.handle, C.c_void_p(q.data_ptr()), Q, int(k), lo, hi, use_min, ms, int(score_mode),
-                C.c_void_p(scores.data_ptr()), C.c_void_p(rows.data_ptr()), C.c_void_p(keys.data_ptr()),
-                C.c_void_p(self._gsws.data_ptr()), self._gsws.numel(), st))
-        else:
-            self.ctx.check(self.L.vm_topk_cosine_grouped_scoped(
-                self.handle, C.c_void_p(q.data_ptr()), Q, int(k), lo, hi, use_min, ms, int(score_mode),
-                C.c_void_p(scores.data_ptr()), C.c_void_p(rows.data_ptr()), C.c_void_p(keys.data_ptr()),
-                C.c_void_p(self._gsuncert.data_ptr()), C.c_void_p(self._gsflags.data_ptr()),
-                C.c_void_p(self._gsws.data_ptr()), self._gsws.numel(), st))
-        q.record_stream(torch.cuda.current_stream())
-        sc.record_stream(torch.cuda.current_stream())
-        return scores, rows, keys
+        (why a query was redone, vm_topk_flag) are in ``last_group_scope_flags``.  ``scratch``: as in ``topk`` - a
+        ``GroupedScopedTopkScratch`` the caller owns (a graph capture), default this memory's own."""
+        return self._search(_GROUPED_SCOPED, queries, k, scope, min_score, score_mode, exact, scratch)
 
     # ---- clip search (include/vidmem.h vm_topk_cosine_clip, DESIGN.md 20) -----------------------------------------
     def prepare_topk_clip(self, C: int, L: int, k: int) -> "ClipScratch":
         """Size this memory's own clip-search buffers for ``C`` clips of ``L`` frames and ``k`` hits each now (before a
         graph capture: a capture must not allocate)."""
-        if self._cscratch is None or not self._cscratch.fits(self, C, L, k):
-            self._cscratch = ClipScratch.for_(self, C, L, k)
-        if self._cuncert is None:
-            self._cuncert = torch.zeros(1, dtype=torch.int32, device=self.device)
-        return self._cscratch
+        self._counter(ClipScratch)
+        return self._resolve(ClipScratch, None, int(C), int(L), int(k))
 
     def _clip_args(self, clips, k, min_sep, scope, max_gap_ms, min_score, score_mode):
         if not isinstance(clips, torch.Tensor):
@@ -988,7 +953,7 @@ class EmbeddingMemory:
         if min_score is not None and math.isnan(float(min_score)):
             raise ValueError("min_score is NaN")
         q = clips.to(device=self.device, dtype=self.dtype).contiguous()
-        sc = self._scope_tensor(scope, Cn) if scope is not None else None
+        sc = self._scopes(scope, Cn) if scope is not None else None
         gap = -1 if max_gap_ms is None else int(max_gap_ms)
         return q, Cn, L, sep, sc, gap
 
@@ -1004,29 +969,20 @@ class EmbeddingMemory:
         ``prepare_topk_clip`` first."""
         q, Cn, L, sep, sc, gap = self._clip_args(clips, k, min_sep, scope, max_gap_ms, min_score, score_mode)
         k = int(k)
-        if scratch is None:
-            scratch = self.prepare_topk_clip(Cn, L, k)
-        elif not scratch.fits(self, Cn, L, k):
-            raise ValueError("caller-owned clip scratch is too small for this (C, L, k)")
-        if self._cuncert is None:
-            self._cuncert = torch.zeros(1, dtype=torch.int32, device=self.device)
+        scratch = self._resolve(ClipScratch, scratch, Cn, L, k)
         scores = scratch.scores[:Cn * k].view(Cn, k)
         rows = scratch.rows[:Cn * k].view(Cn, k)
-        ptr = lambda x: C.c_void_p(x.data_ptr())
-        lo, hi = (ptr(sc[0]), ptr(sc[1])) if sc is not None else (C.c_void_p(0), C.c_void_p(0))
-        use_min = 0 if min_score is None else 1
-        ms = 0.0 if min_score is None else float(min_score)
-        head = (self.handle, ptr(q), Cn, L, k, sep, gap, lo, hi, use_min, ms, int(score_mode), ptr(scores), ptr(rows))
-        tail = (ptr(scratch.ws), scratch.ws.numel(), _lib.current_stream_ptr())
+        lo, hi = (sc[0], sc[1]) if sc is not None else (None, None)
+        head = (self.handle, _ptr(q), Cn, L, k, sep, gap, _ptr(lo), _ptr(hi), *_min_score_args(min_score),
+                int(score_mode), _ptr(scores), _ptr(rows))
+        tail = (_ptr(scratch.ws), scratch.ws.numel(), _lib.current_stream_ptr())
         if exact:
             self.ctx.check(self.L.vm_topk_cosine_clip_exact(*head, *tail))
         else:
-            self.ctx.check(self.L.vm_topk_cosine_clip(*head, ptr(self._cuncert), ptr(scratch.flags), *tail))
-        cur = torch.cuda.current_stream()
-        q.record_stream(cur)
-        if sc is not None:
-            sc.record_stream(cur)
-        self._clast = scratch
+            self.ctx.check(self.L.vm_topk_cosine_clip(*head, _ptr(self._counter(ClipScratch)), _ptr(scratch.flags),
+                                                      *tail))
+        _keep_alive(q, sc)
+        self._last[ClipScratch] = scratch
         return scores, rows
 
     def topk_clip(self, clips, k: int, min_sep: Optional[int] = None, scope=None, max_gap_ms: Optional[int] = None,
@@ -1053,33 +1009,24 @@ class EmbeddingMemory:
     def prepare_range(self, Q: int, max_hits: int) -> "RangeScratch":
         """Size this memory's own range-search buffers for ``Q`` queries and ``max_hits`` hits each now (before a graph
         capture: a capture must not allocate)."""
-        if self._rscratch is None or not self._rscratch.fits(self, Q, max_hits):
-            self._rscratch = RangeScratch.for_(self, Q, max_hits)
-        return self._rscratch
+        return self._resolve(RangeScratch, None, int(Q), int(max_hits))
 
     def _range_call(self, q: torch.Tensor, sc: Optional[torch.Tensor], min_score: float, score_mode: int,
                     max_hits: int, scratch: Optional["RangeScratch"], exact: bool) -> RangeHits:
         Q = q.shape[0]
-        if scratch is None:
-            scratch = self.prepare_range(Q, max_hits)
-        elif not scratch.fits(self, Q, max_hits):
-            raise ValueError("caller-owned range scratch is too small for this (Q, max_hits)")
+        scratch = self._resolve(RangeScratch, scratch, Q, max_hits)
         rows = scratch.rows[:Q * max_hits].view(Q, max_hits)
         scores = scratch.scores[:Q * max_hits].view(Q, max_hits)
-        ptr = lambda x: C.c_void_p(x.data_ptr() if x is not None and x.numel() else 0)
-        lo, hi = (ptr(sc[0]), ptr(sc[1])) if sc is not None else (C.c_void_p(0), C.c_void_p(0))
-        head = (self.handle, ptr(q), Q, float(min_score), int(score_mode), lo, hi, 1, 0, int(max_hits),
-                ptr(rows), ptr(scores), ptr(scratch.counts))
-        tail = (ptr(scratch.ws), scratch.ws.numel(), _lib.current_stream_ptr())
+        lo, hi = (sc[0], sc[1]) if sc is not None else (None, None)
+        head = (self.handle, _ptr(q), Q, float(min_score), int(score_mode), _ptr(lo), _ptr(hi), 1, 0, int(max_hits),
+                _ptr(rows), _ptr(scores), _ptr(scratch.counts))
+        tail = (_ptr(scratch.ws), scratch.ws.numel(), _lib.current_stream_ptr())
         if exact:
             self.ctx.check(self.L.vm_range_cosine_exact(*head, *tail))
         else:
-            self.ctx.check(self.L.vm_range_cosine(*head, ptr(scratch.rescored), *tail))
-        cur = torch.cuda.current_stream()
-        q.record_stream(cur)
-        if sc is not None:
-            sc.record_stream(cur)
-        self._rlast = scratch
+            self.ctx.check(self.L.vm_range_cosine(*head, _ptr(scratch.rescored), *tail))
+        _keep_alive(q, sc)
+        self._last[RangeScratch] = scratch
         return RangeHits(scratch.counts[:Q], rows, scores)
 
     def _range_args(self, queries, min_score, scope, score_mode):
@@ -1091,7 +1038,7 @@ class EmbeddingMemory:
         if scope is not None and not self.tagged:
             raise ValueError("a scope needs a tagged memory (EmbeddingMemory(..., tagged=True))")
         q = self._as_rows(queries)
-        return q, (self._scope_tensor(scope, q.shape[0]) if scope is not None else None), ms
+        return q, (self._scopes(scope, q.shape[0]) if scope is not None else None), ms
 
     def enqueue_range(self, queries, min_score, scope=None, score_mode: int = _lib.VM_SCORE_RAW, max_hits: int = 1024,
                       scratch: Optional["RangeScratch"] = None) -> RangeHits:
@@ -1140,11 +1087,6 @@ class EmbeddingMemory:
             out.append(RangeResult(hits.rows[i, :n].clone(), hits.scores[i, :n].clone(), int(c)))
         return out
 
-    @property
-    def last_range_rescored(self) -> Optional[torch.Tensor]:
-        """int64 per query: the pairs the last fast range call scored exactly (device tensor)."""
-        return None if self._rlast is None else self._rlast.rescored
-
     def moments(self, queries, min_score, scope=None, max_gap_ms: int = 1000,
                 score_mode: int = _lib.VM_SCORE_RAW) -> List[List[Moment]]:
         """``range_search`` then ``segment_moments``: per query the runs of hits of one video that lie at most
@@ -1159,7 +1101,7 @@ class EmbeddingMemory:
             return [[] for _ in found]
         col = _tensor_from_ptr(self.L.vm_memory_tags(self.handle), (self.capacity,), torch.int64, self.device)
         all_rows = torch.cat([f.rows for f in found])
-        packed = torch.stack([all_rows, col[all_rows % self.capacity],        # a row's slot, ring or not
+        packed = torch.stack([all_rows, col[self._slots_of(all_rows)],
                               torch.cat([f.scores for f in found]).view(torch.int64)]).cpu().numpy()
         out, at = [], 0
         for n in sizes:
@@ -1172,9 +1114,7 @@ class EmbeddingMemory:
     def prepare_events(self, max_events: int = 0) -> "EventsScratch":
         """Size this memory's own event buffers for ``max_events`` first rows now (before a graph capture: a capture
         must not allocate)."""
-        if self._vscratch is None or not self._vscratch.fits(self, max_events):
-            self._vscratch = EventsScratch.for_(self, max_events)
-        return self._vscratch
+        return self._resolve(EventsScratch, None, int(max_events))
 
     def _events_args(self, threshold, max_gap_ms, regroup: bool = False) -> Tuple[float, int]:
         """The argument rules of both calls, checked on the host before anything reaches the library."""
@@ -1201,17 +1141,13 @@ class EmbeddingMemory:
         max_events = int(max_events)
         if max_events < 0:
             raise ValueError("max_events is negative")
-        if scratch is None:
-            scratch = self.prepare_events(max_events)
-        elif not scratch.fits(self, max_events):
-            raise ValueError("caller-owned events scratch is too small for this max_events")
-        ptr = lambda x: C.c_void_p(x.data_ptr() if x is not None else 0)
-        first = scratch.first_rows[:max_events] if max_events else None
+        scratch = self._resolve(EventsScratch, scratch, max_events)
+        first = scratch.first_rows[:max_events]
         links = scratch.links if with_links else None
-        self.ctx.check(self.L.vm_memory_events(self.handle, tau, gap, ptr(links), ptr(scratch.event_of), max_events,
-                                               ptr(first), ptr(scratch.count), ptr(scratch.ws), scratch.ws.numel(),
+        self.ctx.check(self.L.vm_memory_events(self.handle, tau, gap, _ptr(links), _ptr(scratch.event_of), max_events,
+                                               _ptr(first), _ptr(scratch.count), _ptr(scratch.ws), scratch.ws.numel(),
                                                _lib.current_stream_ptr()))
-        return EventsOut(scratch.count, scratch.first_rows[:max_events], scratch.event_of, links)
+        return EventsOut(scratch.count, first, scratch.event_of, links)
 
     def events(self, threshold, max_gap_ms: Optional[int] = None, max_events: Optional[int] = None,
                with_links: bool = False) -> Events:
@@ -1244,19 +1180,11 @@ class EmbeddingMemory:
         that has not wrapped and with no erase in between.  Afterwards the last event is closed: a later keyed append
         opens a new group whatever its key.  Enqueues ``vm_memory_regroup_events``: nothing is read on the host."""
         tau, gap = self._events_args(threshold, max_gap_ms, regroup=True)
-        if scratch is None:
-            scratch = self.prepare_events(0)
-        frm = None
-        if from_row is not None:
-            if isinstance(from_row, torch.Tensor):
-                frm = from_row.to(device=self.device, dtype=torch.int64).reshape(-1)[:1].contiguous()
-            else:
-                frm = torch.tensor([int(from_row)], dtype=torch.int64).to(self.device)
-        self.ctx.check(self.L.vm_memory_regroup_events(self.handle, tau, gap, C.c_void_p(frm.data_ptr() if frm is not None else 0),
-                                                       C.c_void_p(scratch.count.data_ptr()), C.c_void_p(scratch.ws.data_ptr()),
-                                                       scratch.ws.numel(), _lib.current_stream_ptr()))
-        if frm is not None:
-            frm.record_stream(torch.cuda.current_stream())
+        scratch = self._resolve(EventsScratch, scratch, 0)
+        frm = None if from_row is None else self._int64_cell(from_row)
+        self.ctx.check(self.L.vm_memory_regroup_events(self.handle, tau, gap, _ptr(frm), _ptr(scratch.count),
+                                                       _ptr(scratch.ws), scratch.ws.numel(), _lib.current_stream_ptr()))
+        _keep_alive(frm)
         self._last_keys_dev = None        # the keys are row ids now; the last event is closed on the device
         return scratch.count
 
@@ -1269,9 +1197,7 @@ class EmbeddingMemory:
         """Size this memory's own summary buffers for windows of ``max_groups`` groups now (before a graph capture: a
         capture must not allocate)."""
         max_groups = self._summary_args(0, max_groups)[1]
-        if self._mscratch is None or not self._mscratch.fits(self, max_groups):
-            self._mscratch = SummaryScratch.for_(self, max_groups)
-        return self._mscratch
+        return self._resolve(SummaryScratch, None, max_groups)
 
     def _summary_args(self, first_group, max_groups) -> Tuple[int, int]:
         """The argument rules of the summary calls, checked on the host before anything reaches the library."""
@@ -1298,26 +1224,18 @@ class EmbeddingMemory:
         ``first_group``: an int, or a device int64 [1] tensor (not read on the host, so a captured graph can page).
         Enqueues ``vm_memory_summaries`` on the current stream: nothing is read on the host."""
         first_group, max_groups = self._summary_args(first_group, max_groups)
-        if scratch is None:
-            scratch = self.prepare_summaries(max_groups)
-        elif not scratch.fits(self, max_groups):
-            raise ValueError("caller-owned summary scratch is too small for this max_groups")
-        if isinstance(first_group, torch.Tensor):
-            frm = first_group.to(device=self.device, dtype=torch.int64).reshape(-1)[:1].contiguous()
-        else:
-            frm = torch.tensor([first_group], dtype=torch.int64).to(self.device)
-        ptr = lambda x: C.c_void_p(x.data_ptr() if x is not None else 0)
+        scratch = self._resolve(SummaryScratch, scratch, max_groups)
+        frm = self._int64_cell(first_group)
         m = max_groups
         out = SummariesOut(scratch.count, scratch.first_rows[:m], scratch.n_rows[:m], scratch.keys[:m],
                            scratch.centroids[:m], scratch.key_rows[:m] if key_frames else None,
                            scratch.key_scores[:m] if key_frames else None)
-        some = lambda x: x if m else None           # max_groups == 0: the count only
-        self.ctx.check(self.L.vm_memory_summaries(self.handle, ptr(frm), m, ptr(some(out.centroids)),
-                                                  ptr(some(out.first_rows)), ptr(some(out.n_rows)),
-                                                  ptr(some(out.keys)), ptr(some(out.key_rows)),
-                                                  ptr(some(out.key_scores)), ptr(scratch.count), ptr(scratch.ws),
+        # max_groups == 0: the count only - the empty views give null pointers
+        self.ctx.check(self.L.vm_memory_summaries(self.handle, _ptr(frm), m, _ptr(out.centroids), _ptr(out.first_rows),
+                                                  _ptr(out.n_rows), _ptr(out.keys), _ptr(out.key_rows),
+                                                  _ptr(out.key_scores), _ptr(scratch.count), _ptr(scratch.ws),
                                                   scratch.ws.numel(), _lib.current_stream_ptr()))
-        frm.record_stream(torch.cuda.current_stream())
+        _keep_alive(frm)
         return out
 
     def summaries(self, first_group: int = 0, max_groups: Optional[int] = None) -> Summaries:
@@ -1358,61 +1276,42 @@ class EmbeddingMemory:
         krow, kscore = s.key_rows.tolist(), s.key_scores.tolist()
         tag = None
         if self.tagged and into.tagged:
-            total, n = len(self), self.searchable
-            tags = _tensor_from_ptr(self.L.vm_memory_tags(self.handle), (n,), torch.int64, self.device)
-            slots = s.key_rows % self.capacity if (self.ring and total > self.capacity) else s.key_rows
-            tag = tags[slots]
+            tags = _tensor_from_ptr(self.L.vm_memory_tags(self.handle), (self.capacity,), torch.int64, self.device)
+            tag = tags[self._slots_of(s.key_rows)]
         meta = [{"first_row": a, "last_row": a + c - 1, "key_row": k, "key_score": v}
                 for a, c, k, v in zip(first, nrow, krow, kscore)]
         at = into.append(s.centroids, ids=[self.id_of(k) for k in krow], meta=meta,
                          group=s.keys if into.grouped else None, tag=tag)
         return s, at
 
-    @property
-    def last_scope_flags(self) -> Optional[torch.Tensor]:
-        return self._sflags
-
-    @property
-    def scoped_uncertified_count(self) -> int:
-        """Queries the scoped fast path redid exhaustively since this memory was created (synchronises)."""
-        return 0 if self._suncert is None else int(self._suncert.item())
-
-    @property
-    def last_clip_flags(self) -> Optional[torch.Tensor]:
-        """int32 per clip (vm_topk_flag): why the last fast clip call redid a clip, 0 = certified (device tensor)."""
-        return None if self._clast is None else self._clast.flags
-
-    @property
-    def clip_uncertified_count(self) -> int:
-        """Clips the clip search's fast path redid exhaustively since this memory was created (synchronises)."""
-        return 0 if self._cuncert is None else int(self._cuncert.item())
-
-    @property
-    def last_group_scope_flags(self) -> Optional[torch.Tensor]:
-        return self._gsflags
-
-    @property
-    def group_scoped_uncertified_count(self) -> int:
-        """Queries the scoped grouped fast path redid exhaustively since this memory was created (synchronises)."""
-        return 0 if self._gsuncert is None else int(self._gsuncert.item())
-
-    @property
-    def last_group_flags(self) -> Optional[torch.Tensor]:
-        return self._gflags
-
-    @property
-    def grouped_uncertified_count(self) -> int:
-        """Queries the grouped fast path redid exhaustively since this memory was created (synchronises)."""
-        return 0 if self._guncert is None else int(self._guncert.item())
+    # ---- what the last call of a kind left, and what its fast path could not certify -------------------------------
+    last_flags = _last_property(TopkScratch, "flags", "int32 per query (vm_topk_flag): why the last fast `topk` call "
+                                "redid a query exhaustively, 0 = certified")
+    last_group_flags = _last_property(GroupedTopkScratch, "flags", "int32 per query (vm_topk_flag): why the last fast "
+                                      "`topk_grouped` call redid a query, 0 = certified")
+    last_scope_flags = _last_property(ScopedTopkScratch, "flags", "int32 per query (vm_topk_flag): why the last fast "
+                                      "`topk_scoped` call redid a query, 0 = certified")
+    last_group_scope_flags = _last_property(GroupedScopedTopkScratch, "flags", "int32 per query (vm_topk_flag): why the "
+                                            "last fast `topk_grouped_scoped` call redid a query, 0 = certified")
+    last_clip_flags = _last_property(ClipScratch, "flags", "int32 per clip (vm_topk_flag): why the last fast clip call "
+                                     "redid a clip, 0 = certified")
+    last_range_rescored = _last_property(RangeScratch, "rescored", "int64 per query: the pairs the last fast range call "
+                                         "scored exactly")
+    grouped_uncertified_count = _count_property(GroupedTopkScratch, "Queries the grouped fast path")
+    scoped_uncertified_count = _count_property(ScopedTopkScratch, "Queries the scoped fast path")
+    group_scoped_uncertified_count = _count_property(GroupedScopedTopkScratch, "Queries the scoped grouped fast path")
+    clip_uncertified_count = _count_property(ClipScratch, "Clips the clip search's fast path")
 
     @property
     def uncertified_count(self) -> int:
-        """Queries redone exhaustively since ``reset_uncertified`` on this memory's own scratch (one 4-byte
-        read-back; synchronises)."""
-        return int(self._scratch.uncert.item())
+        """Queries redone exhaustively since ``reset_uncertified`` on this memory's own top-k scratch."""
+        own = self._own.get(TopkScratch)
+        return 0 if own is None else int(own.uncert.item())
 
     def reset_uncertified(self) -> None:
-        self._scratch.uncert.zero_()
+        own = self._own.get(TopkScratch)
+        if own is not None:
+            own.uncert.zero_()
 
     def cosine_exact(self, queries, rows, as_f32: bool = False) -> torch.Tensor:
         """All-pairs reference cosine [Q,S] float64 between two row sets (neither needs to be stored).
@@ -1436,46 +1335,46 @@ class EmbeddingMemory:
         self.ctx.check(self.L.vm_cosine_exact(self.ctx.handle, C.c_void_p(q.data_ptr()), q.shape[0],
                                               C.c_void_p(r.data_ptr()), r.shape[0], dim, dt,
                                               C.c_void_p(out.data_ptr()), _lib.current_stream_ptr()))
-        q.record_stream(torch.cuda.current_stream())
-        r.record_stream(torch.cuda.current_stream())
+        _keep_alive(q, r)
         return out
 
     # ---- persistence: the reference's only durable store is the `embedding` list property
     # (src/components/neo4j_handler.py:229-242) and the export JSON (src/components/graph_exporter.py:61-67);
     # here: raw 16-bit rows in row-id order + the host id / meta tables, one .npz ------------------------------
+    def _in_row_order(self, column: torch.Tensor) -> torch.Tensor:
+        """A per-slot column over the searchable rows -> the same in row-id order: a ring that has wrapped keeps its
+        oldest row at slot ``total % capacity``."""
+        total = len(self)
+        if not (self.ring and total > self.capacity):
+            return column
+        head = total % self.capacity
+        return torch.cat([column[head:], column[:head]])
+
+    def _slots_of(self, rows: torch.Tensor) -> torch.Tensor:
+        """Row ids -> the slots that hold them, on every memory: a ring wraps, and elsewhere ids stay below capacity."""
+        return rows % self.capacity
+
     def rows_host(self):
         """(first_row_id, uint16 [n, D]): the searchable rows as raw 16-bit patterns in row-id order (host copy)."""
         import numpy as np
-        total, n = len(self), self.searchable
-        phys = self.rows_tensor().view(torch.int16)
-        if self.ring and total > self.capacity:  # oldest row sits at slot total % capacity
-            head = total % self.capacity
-            phys = torch.cat([phys[head:], phys[:head]])
-        return total - n, phys.cpu().numpy().view(np.uint16)
+        phys = self._in_row_order(self.rows_tensor().view(torch.int16))
+        return len(self) - phys.shape[0], phys.cpu().numpy().view(np.uint16)
 
     def group_keys_host(self):
         """int64 [n]: the group key of every searchable row in row-id order (grouped memories; host copy)."""
         import numpy as np
         if not self.grouped:
             raise ValueError("not a grouped memory")
-        total, n = len(self), self.searchable
-        keys = _tensor_from_ptr(self.L.vm_memory_group_keys(self.handle), (n,), torch.int64, self.device)
-        if self.ring and total > self.capacity:
-            head = total % self.capacity
-            keys = torch.cat([keys[head:], keys[:head]])
-        return keys.cpu().numpy().astype(np.int64)
+        keys = _tensor_from_ptr(self.L.vm_memory_group_keys(self.handle), (self.searchable,), torch.int64, self.device)
+        return self._in_row_order(keys).cpu().numpy().astype(np.int64)
 
     def tags_host(self):
         """int64 [n]: the tag of every searchable row in row-id order (tagged memories; host copy)."""
         import numpy as np
         if not self.tagged:
             raise ValueError("not a tagged memory")
-        total, n = len(self), self.searchable
-        tags = _tensor_from_ptr(self.L.vm_memory_tags(self.handle), (n,), torch.int64, self.device)
-        if self.ring and total > self.capacity:
-            head = total % self.capacity
-            tags = torch.cat([tags[head:], tags[:head]])
-        return tags.cpu().numpy().astype(np.int64)
+        tags = _tensor_from_ptr(self.L.vm_memory_tags(self.handle), (self.searchable,), torch.int64, self.device)
+        return self._in_row_order(tags).cpu().numpy().astype(np.int64)
 
     def snapshot(self, path: str) -> None:
         import json
@@ -1532,178 +1431,6 @@ class EmbeddingMemory:
     def meta_of(self, row: int) -> Optional[dict]:
         i = self._table_index(row)
         return self.meta[i] if 0 <= i < len(self.meta) else None
-
-
-class NoveltyScratch:
-    """Device buffers of the gated append for batches of up to ``B`` rows: the workspace (norms and pair bits), ``keep``
-    (int32), ``row_of`` (int64) and ``count`` (int32 [1]).  Like ``TopkScratch``, an owner keeps ONE instance per stream /
-    captured graph: a hipGraph bakes the addresses in."""
-
-    def __init__(self, device, B: int, ws_bytes: int):
-        self.B = int(B)
-        self.ws = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=device)
-        self.keep = torch.zeros(max(B, 1), dtype=torch.int32, device=device)
-        self.row_of = torch.zeros(max(B, 1), dtype=torch.int64, device=device)
-        self.count = torch.zeros(1, dtype=torch.int32, device=device)
-
-    def fits(self, memory: "EmbeddingMemory", B: int) -> bool:
-        return (self.B >= min(B, NOVEL_MAX_ROWS) and
-                self.ws.numel() >= int(memory.L.vm_novelty_workspace_bytes(memory.handle, int(min(B, NOVEL_MAX_ROWS)))))
-
-    @classmethod
-    def for_(cls, memory: "EmbeddingMemory", B: int) -> "NoveltyScratch":
-        B = max(1, min(int(B), NOVEL_MAX_ROWS))
-        return cls(memory.device, B, int(memory.L.vm_novelty_workspace_bytes(memory.handle, B)))
-
-
-class EventsScratch:
-    """Device buffers of the event segmentation: the workspace (flags and chunk prefixes), ``count`` (int64 [1]),
-    ``first_rows`` (int64 [max_events]), ``event_of`` (int64 [capacity]) and ``links`` (float64 [capacity]).  Like
-    ``TopkScratch``, an owner keeps ONE instance per stream / captured graph: a hipGraph bakes the addresses in."""
-
-    def __init__(self, device, capacity: int, max_events: int, ws_bytes: int):
-        self.ws = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=device)
-        self.count = torch.zeros(1, dtype=torch.int64, device=device)
-        self.first_rows = torch.full((max(int(max_events), 1),), -1, dtype=torch.int64, device=device)
-        self.event_of = torch.zeros(max(capacity, 1), dtype=torch.int64, device=device)
-        self.links = torch.zeros(max(capacity, 1), dtype=torch.float64, device=device)
-
-    def fits(self, memory: "EmbeddingMemory", max_events: int) -> bool:
-        return (self.first_rows.numel() >= max_events and self.event_of.numel() >= memory.capacity and
-                self.ws.numel() >= int(memory.L.vm_memory_events_workspace_bytes(memory.handle)))
-
-    @classmethod
-    def for_(cls, memory: "EmbeddingMemory", max_events: int = 0) -> "EventsScratch":
-        return cls(memory.device, memory.capacity, int(max_events),
-                   int(memory.L.vm_memory_events_workspace_bytes(memory.handle)))
-
-
-class SummaryScratch:
-    """Device buffers of the group summaries for windows of up to ``max_groups`` groups: the workspace (group bounds,
-    one score per slot), ``count`` (int64 [1]) and the per-group outputs.  Like ``TopkScratch``, an owner keeps ONE
-    instance per stream / captured graph: a hipGraph bakes the addresses in."""
-
-    def __init__(self, device, dim: int, dtype, max_groups: int, ws_bytes: int):
-        m = max(int(max_groups), 1)
-        self.max_groups = int(max_groups)
-        self.ws = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=device)
-        self.count = torch.zeros(1, dtype=torch.int64, device=device)
-        self.first_rows = torch.full((m,), -1, dtype=torch.int64, device=device)
-        self.n_rows = torch.full((m,), -1, dtype=torch.int64, device=device)
-        self.keys = torch.full((m,), -1, dtype=torch.int64, device=device)
-        self.key_rows = torch.full((m,), -1, dtype=torch.int64, device=device)
-        self.key_scores = torch.zeros(m, dtype=torch.float64, device=device)
-        self.centroids = torch.zeros((m, dim), dtype=dtype, device=device)
-
-    def fits(self, memory: "EmbeddingMemory", max_groups: int) -> bool:
-        return (self.max_groups >= max_groups and self.centroids.shape[1] == memory.dim and
-                self.centroids.dtype == memory.dtype and
-                self.ws.numel() >= int(memory.L.vm_memory_summaries_workspace_bytes(memory.handle, int(max_groups))))
-
-    @classmethod
-    def for_(cls, memory: "EmbeddingMemory", max_groups: int) -> "SummaryScratch":
-        ws_bytes = int(memory.L.vm_memory_summaries_workspace_bytes(memory.handle, int(max_groups)))
-        return cls(memory.device, memory.dim, memory.dtype, int(max_groups), ws_bytes)
-
-
-class RangeScratch:
-    """Device buffers of the range search for up to ``Q`` queries with ``max_hits`` hits each: the workspace (candidate
-    and hit bits, exact scores, chunk counts), ``counts`` and ``rescored`` (int64 [Q]) and the ``rows`` / ``scores``
-    outputs (Q x max_hits).  Like ``TopkScratch``, an owner keeps ONE instance per stream / captured graph: a hipGraph
-    bakes the addresses in."""
-
-    def __init__(self, device, Q: int, max_hits: int, ws_bytes: int):
-        self.Q, self.max_hits = int(Q), int(max_hits)
-        self.ws = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=device)
-        self.counts = torch.zeros(max(Q, 1), dtype=torch.int64, device=device)
-        self.rescored = torch.zeros(max(Q, 1), dtype=torch.int64, device=device)
-        self.rows = torch.full((max(Q * max_hits, 1),), -1, dtype=torch.int64, device=device)
-        self.scores = torch.zeros(max(Q * max_hits, 1), dtype=torch.float64, device=device)
-
-    def fits(self, memory: "EmbeddingMemory", Q: int, max_hits: int) -> bool:
-        return (self.counts.numel() >= Q and self.rows.numel() >= Q * max_hits and
-                self.ws.numel() >= int(memory.L.vm_range_workspace_bytes(memory.handle, int(Q))))
-
-    @classmethod
-    def for_(cls, memory: "EmbeddingMemory", Q: int, max_hits: int) -> "RangeScratch":
-        Q = max(1, int(Q))
-        return cls(memory.device, Q, int(max_hits), int(memory.L.vm_range_workspace_bytes(memory.handle, Q)))
-
-
-class ClipScratch:
-    """Device buffers of the clip search for up to ``C`` clips of ``L`` frames with ``k`` hits each: the workspace (query
-    tiles, fp32 score columns, window scores and keys, candidates, exact redo scores), ``flags`` (int32 [C]) and the
-    ``scores`` / ``rows`` outputs (C x k).  Like ``RangeScratch``, an owner keeps ONE instance per stream / captured
-    graph: a hipGraph bakes the addresses in."""
-
-    def __init__(self, device, C: int, k: int, ws_bytes: int):
-        self.C, self.k = int(C), int(k)
-        self.ws = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=device)
-        self.flags = torch.zeros(max(C, 1), dtype=torch.int32, device=device)
-        self.scores = torch.zeros(max(C * k, 1), dtype=torch.float64, device=device)
-        self.rows = torch.full((max(C * k, 1),), -1, dtype=torch.int64, device=device)
-
-    def fits(self, memory: "EmbeddingMemory", C: int, L: int, k: int) -> bool:
-        return (self.flags.numel() >= C and self.rows.numel() >= C * k and
-                self.ws.numel() >= int(memory.L.vm_topk_clip_workspace_bytes(memory.handle, int(C), int(L), int(k))))
-
-    @classmethod
-    def for_(cls, memory: "EmbeddingMemory", C: int, L: int, k: int) -> "ClipScratch":
-        need = int(memory.L.vm_topk_clip_workspace_bytes(memory.handle, int(C), int(L), int(k)))
-        return cls(memory.device, int(C), int(k), need)
-
-
-class EraseScratch:
-    """Device buffers of erase: the workspace (keep flags, their prefix, one segment of every column), ``new_row_of``
-    (int64 [capacity]) and ``erased`` (int64 [1]).  Like ``NoveltyScratch``, an owner keeps ONE instance per stream /
-    captured graph: a hipGraph bakes the addresses in."""
-
-    def __init__(self, device, capacity: int, ws_bytes: int):
-        self.ws = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=device)
-        self.new_row_of = torch.full((max(capacity, 1),), -1, dtype=torch.int64, device=device)
-        self.erased = torch.zeros(1, dtype=torch.int64, device=device)
-
-    @classmethod
-    def for_(cls, memory: "EmbeddingMemory", segment_rows: int = 0) -> "EraseScratch":
-        need = int(memory.L.vm_memory_erase_workspace_bytes(memory.handle, int(segment_rows)))
-        return cls(memory.device, memory.capacity, need)
-
-
-class TopkScratch:
-    """Device buffers one stream of top-k calls needs: the scan workspace, the redo workspace, the per-query flag
-    array and the uncertified counter.  An owner keeps ONE instance per stream / captured graph: a hipGraph bakes the
-    addresses in, so a scratch a capture has seen is never re-allocated (``fit`` returns a NEW object when it has to
-    grow and leaves the old buffers to whoever still references them)."""
-
-    def __init__(self, device, Q: int = 0, k: int = 0, ws_bytes: int = 0, redo_bytes: int = 0):
-        self.Q, self.k = int(Q), int(k)
-        self.ws = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=device)
-        self.redo_ws = torch.empty(max(redo_bytes, 256), dtype=torch.uint8, device=device)
-        self.flags = torch.zeros(max(Q, 1), dtype=torch.int32, device=device)
-        self.uncert = torch.zeros(1, dtype=torch.int32, device=device)
-
-    @staticmethod
-    def _need(memory: "EmbeddingMemory", Q: int, k: int):
-        return (int(memory.L.vm_topk_workspace_bytes(memory.handle, int(Q), int(k))),
-                int(memory.L.vm_topk_redo_workspace_bytes(memory.handle, int(Q), int(k))))
-
-    def fits(self, memory: "EmbeddingMemory", Q: int, k: int) -> bool:
-        ws, redo = self._need(memory, Q, k)
-        return self.ws.numel() >= ws and self.redo_ws.numel() >= redo and self.flags.numel() >= Q
-
-    def fit(self, memory: "EmbeddingMemory", Q: int, k: int) -> "TopkScratch":
-        if self.fits(memory, Q, k):
-            return self
-        ws, redo = self._need(memory, Q, k)
-        new = TopkScratch(self.ws.device, max(Q, self.flags.numel()), k, max(ws, self.ws.numel()),
-                          max(redo, self.redo_ws.numel()))
-        new.uncert.copy_(self.uncert)
-        return new
-
-    @classmethod
-    def for_(cls, memory: "EmbeddingMemory", Q: int, k: int) -> "TopkScratch":
-        ws, redo = cls._need(memory, Q, k)
-        return cls(memory.device, Q, k, ws, redo)
 
 
 def topk_select(ctx: "_lib.Context", scores: torch.Tensor, k: int, col_limit: Optional[torch.Tensor] = None,

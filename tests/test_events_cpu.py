@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from tests import events_ref as E
+from tests.host_memory import host_memory as _host_memory
 
 MIN = E.INT64_MIN
 
@@ -152,22 +153,6 @@ def test_build_memory_accepts_event_and_still_rejects_scene(monkeypatch):
 
 
 # ---- argument rules of the Python entries -----------------------------------------------------------------------------
-class _NoLibrary:
-    def __getattr__(self, name):
-        raise AssertionError(f"library call {name} before the arguments were checked")
-
-
-def _host_memory(grouped=False, tagged=False):
-    from vidmem.memory import EmbeddingMemory
-    mem = EmbeddingMemory.__new__(EmbeddingMemory)      # host rules only: no device handle
-    mem.grouped, mem.tagged, mem.capacity = grouped, tagged, 16
-    mem.L = mem.ctx = _NoLibrary()
-    mem.handle = None
-    mem.device = "cpu"
-    mem._vscratch = None
-    return mem
-
-
 def test_argument_errors_are_raised_without_a_library_call():
     plain, grouped, both = _host_memory(), _host_memory(grouped=True), _host_memory(grouped=True, tagged=True)
     for mem in (plain, grouped, both):

@@ -406,8 +406,7 @@ def test_refusals_launch_nothing():
         mem.topk_grouped_scoped(rows[:2], 3, [(0, 1), (0, 1), (0, 1)])
     # the C entry points themselves refuse too, and touch neither the outputs nor the counters
     L = mem.L
-    mem.prepare_topk_grouped_scoped(2, 3)
-    ws = mem._gsws
+    ws = mem.prepare_topk_grouped_scoped(2, 3).ws
     need = int(L.vm_topk_grouped_scoped_workspace_bytes(mem.handle, 2, 3))
     assert need > 0 and L.vm_topk_grouped_scoped_workspace_bytes(mem.handle, 2, 65) == 0
     sc = torch.zeros((2, 2), dtype=torch.int64, device="cuda")

@@ -326,14 +326,14 @@ def test_refusals():
     with pytest.raises(ValueError, match="tags"):
         mem.append(rows[:2], tag=[1, 2, 3])
     # the C entry points themselves refuse too
-    mem.prepare_topk_scoped(2, 3)
+    ws = mem.prepare_topk_scoped(2, 3).ws
     sc = torch.zeros((2, 2), dtype=torch.int64, device="cuda")
     out_s = torch.empty((2, 64), dtype=torch.float64, device="cuda")
     out_r = torch.empty((2, 64), dtype=torch.int64, device="cuda")
     p = lambda t: C.c_void_p(t.data_ptr())
     for handle, k in ((plain.handle, 3), (mem.handle, 0), (mem.handle, 65)):
         rc = mem.L.vm_topk_cosine_scoped(handle, p(rows), 2, k, p(sc[0]), p(sc[1]), 0, 0.0, 0, 1, 0, p(out_s), p(out_r),
-                                         None, None, p(mem._sws), mem._sws.numel(), _lib.current_stream_ptr())
+                                         None, None, p(ws), ws.numel(), _lib.current_stream_ptr())
         assert rc == _lib.VM_ERR_INVALID
     assert mem.L.vm_memory_append_tagged(plain.handle, p(rows), 2, p(sc[0]), None, None,
                                          _lib.current_stream_ptr()) == _lib.VM_ERR_INVALID

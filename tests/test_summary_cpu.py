@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from tests import summary_ref as S
+from tests.host_memory import host_memory as _host_memory
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FORMATS = {"f16": (10, 5), "bf16": (7, 8)}          # stored mantissa bits, exponent bits
@@ -167,23 +168,6 @@ def test_summarize_on_hand_made_groups():
 
 
 # ---- argument rules of the Python entries -----------------------------------------------------------------------------
-class _NoLibrary:
-    def __getattr__(self, name):
-        raise AssertionError(f"library call {name} before the arguments were checked")
-
-
-def _host_memory(grouped=False, tagged=False, dim=128, dtype="f16"):
-    from vidmem.memory import EmbeddingMemory
-    mem = EmbeddingMemory.__new__(EmbeddingMemory)      # host rules only: no device handle
-    mem.grouped, mem.tagged, mem.capacity = grouped, tagged, 16
-    mem.dim, mem.dtype_name = dim, dtype
-    mem.L = mem.ctx = _NoLibrary()
-    mem.handle = None
-    mem.device = "cpu"
-    mem._mscratch = None
-    return mem
-
-
 def test_argument_errors_are_raised_without_a_library_call():
     plain, grouped = _host_memory(), _host_memory(grouped=True)
     other = _host_memory(grouped=True)

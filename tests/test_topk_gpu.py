@@ -158,7 +158,7 @@ def test_the_shape_that_must_redo_near_ties_around_rank_k():
         mem.append(m)
         q = torch.stack([base, m[7]])                         # query 1 is an ordinary one
         s, r = mem.topk(q, k)
-        flags = mem._scratch.flags[:2].cpu().tolist()
+        flags = mem.last_flags[:2].cpu().tolist()
         want_r, want_s = cref.cosine_topk(_bits(q), _bits(m), k, dtype="f16")
         assert np.array_equal(r.cpu().numpy(), want_r) and np.array_equal(s.cpu().numpy(), want_s)
         assert flags[1] == 0

@@ -29,7 +29,7 @@ for kind in ("random", "noise-frame embeddings"):
     for copies in range(0, 3):
         mem.reset_uncertified()
         s, r = mem.topk(q, k)
-        flags = mem._scratch.flags[:880].clone()
+        flags = mem.last_flags[:880].clone()
         torch.cuda.synchronize()
         nf = int(flags.sum())
         print(f"{kind}: copies of the queries in memory: {copies}  redone {mem.uncertified_count} flagged {nf}  "

@@ -11,7 +11,7 @@ if len(sys.argv) > 1 and sys.argv[1] == "child":
         mem = EmbeddingMemory(M, D, "f16"); mem.append(m)
         mem.reset_uncertified()
         s, r = mem.topk(q, k, redo=False)
-        flagged = mem._scratch.flags[:Q].cpu().numpy()
+        flagged = mem.last_flags[:Q].cpu().numpy()
         s2, r2 = mem.topk(q, k, exact=True)
         bad = (r != r2).any(dim=1).cpu().numpy()
         print(f"EMIT={os.environ.get('VIDMEM_TOPK_EMIT','1')} D={D} M={M} Q={Q}: flagged {int(flagged.sum())}, wrong-without-redo {int(bad.sum())}, wrong&unflagged {int((bad & (flagged == 0)).sum())}", flush=True)

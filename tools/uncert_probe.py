@@ -30,7 +30,7 @@ flagged = []
 for c0 in range(0, NF, QC):
     q = emb[c0:c0 + QC]
     s, r = mem.topk(q, k)
-    fl = mem._scratch.flags[:q.shape[0]].clone()
+    fl = mem.last_flags[:q.shape[0]].clone()
     if int(fl.sum()):
         rows_now = len(mem)
         allrows = mem.rows_tensor()[:rows_now]
