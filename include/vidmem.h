@@ -507,6 +507,57 @@ int vm_topk_cosine_scoped_exact(vm_memory *mem, const void *queries, int Q, int 
                                 const int64_t *scope_hi, int use_min_score, double min_score, int score_mode,
                                 int64_t row_stride, int64_t row_offset, double *out_scores, int64_t *out_rows,
                                 void *workspace, size_t workspace_bytes, void *stream);
+/* Row masks and masked top-k: search any set of rows.  A MASK is a device array of W = vm_memory_mask_words(mem) 32-bit
+ * words (the capacity rounded up to 64 rows, / 32); several masks lie back to back, [n_masks][W].  The bit of row id r is
+ * bit s & 31 of word s >> 5 with s = r mod capacity: in a linear memory s = r, in a ring the physical slot the row lives
+ * in.  A bit whose slot holds no live row (past the row count, the padding, all of an empty memory) is ignored by every
+ * consumer, so ~mask is meaningful and safe; masks combine with & | ~ on the caller's side.  A mask is a statement about
+ * ROW IDS: an erase renumbers rows and a ring overwrites them, after which a mask is stale exactly as a stored row id
+ * is (the bit then names whichever row lives in the slot); nothing remaps it.
+ * vm_topk_cosine_masked: masks [n_masks][W]; mask_index: device int32 [Q], the mask each query uses, or NULL: mask 0
+ *   for every query when n_masks == 1, mask q for query q when n_masks == Q, VM_ERR_INVALID for any other n_masks.  An
+ *   index outside [0, n_masks) is the EMPTY mask (an all-padded row, never an out-of-range read).  At most 2^30 words of
+ *   masks per call (VM_ERR_UNSUPPORTED above).  The result is the exhaustive row ranking of vm_topk_cosine (reference
+ *   fp64 cosines bit for bit, score_mode mapping, > min_score filter, score descending, row id ascending) over the
+ *   selected live rows only, first k: out_scores [Q,k], out_rows [Q,k] global row ids (row_id * row_stride +
+ *   row_offset), -1 / 0.0 padded.  With every bit set the result equals vm_topk_cosine + vm_topk_redo_flagged; with the
+ *   mask of a tag range (vm_mask_from_scopes) it equals vm_topk_cosine_scoped.
+ *   ALWAYS the exhaustive answer, like the scoped search: an fp32 MFMA scan scores the 16-row tiles in which some query
+ *   selects a live row (the others cost 2 bytes of mask per query, their rows are not read), the best M = k + slack
+ *   selected rows are re-scored exactly, and a query is certified when its mask selects at most M rows or the exact k-th
+ *   score clears the (M+1)-th SELECTED fp32 score by vm_topk_cosine's bound 2 (D + 8) 2^-24 - unselected rows never
+ *   enter it.  Any other query (VM_FLAG_GAP; VM_FLAG_OVERFLOW: more than 8192 selected rows at the query's cut) is counted
+ *   in *out_uncertified (may be NULL), marked in out_query_flags [Q] (vm_topk_flag; may be NULL) and redone exhaustively
+ *   over its selected rows on the device inside the same call.  The bound's norm domain is vm_topk_cosine_scoped's.
+ *   Any memory: plain, grouped, tagged, ring.  No host read-back, no allocation: capturable; a replay sees a mask
+ *   rewritten in place and the rows appended since.  1 <= k <= 64, Q >= 1.
+ *   Workspace: vm_topk_masked_workspace_bytes (= the scoped search's: 4 x Q x capacity bytes of keys plus 64 KiB x Q
+ *   and a few MB). */
+int64_t vm_memory_mask_words(const vm_memory *mem);
+size_t vm_topk_masked_workspace_bytes(const vm_memory *mem, int Q, int k);
+int vm_topk_cosine_masked(vm_memory *mem, const void *queries, int Q, int k, const uint32_t *masks, int n_masks,
+                          const int32_t *mask_index, int use_min_score, double min_score, int score_mode,
+                          int64_t row_stride, int64_t row_offset, double *out_scores, int64_t *out_rows,
+                          int32_t *out_uncertified, int32_t *out_query_flags, void *workspace, size_t workspace_bytes,
+                          void *stream);
+/* The same contract, exhaustive only: every selected pair scored exactly (slow; tests, and a checker). */
+int vm_topk_cosine_masked_exact(vm_memory *mem, const void *queries, int Q, int k, const uint32_t *masks, int n_masks,
+                                const int32_t *mask_index, int use_min_score, double min_score, int score_mode,
+                                int64_t row_stride, int64_t row_offset, double *out_scores, int64_t *out_rows,
+                                void *workspace, size_t workspace_bytes, void *stream);
+/* The device-side mask builders; stream-ordered, no host read-back, capturable.  out_mask: one mask, W words.
+ * vm_mask_from_rows: sets the bit of every live row named in row_ids, device int64 [n] as any search wrote them
+ *   (row * row_stride + row_offset; row_stride >= 1).  -1 entries, ids not of that form and ids of rows that are not live
+ *   (never appended, or overwritten by a ring) are skipped; duplicates are fine.  clear_first != 0: the mask is zeroed
+ *   first; 0: the bits are ORed into what out_mask holds (atomically per word: the result does not depend on order).
+ * vm_mask_from_scopes: tagged memories only (VM_ERR_INVALID otherwise).  scope_lo / scope_hi: device int64 [n_ranges],
+ *   inclusive tag ranges by vm_topk_cosine_scoped's rule; a bit is set iff its slot holds a live row whose tag lies in
+ *   ANY of the ranges (vm_memory_erase_scoped's selector).  Writes every word of the mask (no atomics; a slot without a
+ *   live row gives 0); n_ranges == 0 gives the empty mask. */
+int vm_mask_from_rows(vm_memory *mem, const int64_t *row_ids, int64_t n, int64_t row_stride, int64_t row_offset,
+                      int clear_first, uint32_t *out_mask, void *stream);
+int vm_mask_from_scopes(vm_memory *mem, const int64_t *scope_lo, const int64_t *scope_hi, int n_ranges,
+                        uint32_t *out_mask, void *stream);
 /* Scoped grouped top-k: the k best GROUPS of a tagged AND grouped memory among the rows IN SCOPE - "the k best scenes of
  * video 7 between minute 10 and minute 20".  scope_lo / scope_hi: device int64 [Q], both required, inclusive tag ranges
  * by vm_topk_cosine_scoped's rule (row r is in query q's scope iff scope_lo[q] <= tag[r] <= scope_hi[q]).

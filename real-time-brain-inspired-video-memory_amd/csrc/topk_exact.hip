@@ -3,7 +3,7 @@
 // then a stable top-k.  Used (a) as the fallback for queries the fast scan cannot certify, (b) for the
 // post-compression filter (src/pipeline/retriever_hybrid.py:494-504), (c) as an on-device checker.
 // Also home of what the three redos share (vm_internal.h): the row-block count vm_topk_redo_blocks, the redo scan of rows
-// vm_topk_redo_scan (the row redo here and topk_scope.hip; the grouped one carries a group across chunks and is
+// vm_topk_redo_scan (the row redo here, topk_scope.hip and topk_mask.hip; the grouped one carries a group across chunks and is
 // topk_group.hip's own) and the merge of the slice winners vm_topk_redo_merge (all three).
 #include "topk_common.h"
 #include "vm_internal.h"
@@ -148,14 +148,18 @@ constexpr int REDO_KMAX = 64;
 // selection pass.  The redo scan of the row search (SCOPED = false: every live row; the scores sit in dynamic LDS behind
 // the query) and of the scoped search (SCOPED = true: only the rows whose tag lies in the query's scope are scored and
 // may win, and a chunk with no in-scope row costs its tags only; the scores and the in-scope marks sit in static LDS).
-template <int DT, int CHUNK, bool SCOPED>
+// REDO_MASKED is the scoped scan with another predicate: the bit of the row's slot in the query's mask (vm_internal.h
+// MaskSel) in place of the tag range.
+constexpr int REDO_ALL = 0, REDO_SCOPED = 1, REDO_MASKED = 2;
+template <int DT, int CHUNK, int PRED>
 __global__ void __launch_bounds__(REDO_THREADS)
     topk_redo_scan_kernel(const uint16_t *__restrict__ queries, const uint16_t *__restrict__ rows,
                           const double *__restrict__ norm64, const int64_t *__restrict__ tag,
                           const int64_t *__restrict__ scope_lo, const int64_t *__restrict__ scope_hi,
                           const int64_t *__restrict__ d_total, int64_t cap, int ring, int D, int Q, int k,
                           const int32_t *__restrict__ flags, double *__restrict__ part_s,
-                          int64_t *__restrict__ part_o) {
+                          int64_t *__restrict__ part_o, const MaskSel ms) {
+    constexpr bool SCOPED = PRED != REDO_ALL;  // a predicate selects the rows
     extern __shared__ __attribute__((aligned(16))) char smem[];
     uint16_t *ql = reinterpret_cast<uint16_t *>(smem);  // [D]
     double *sc;                                         // [CHUNK]
@@ -196,10 +200,12 @@ __global__ void __launch_bounds__(REDO_THREADS)
         __syncthreads();
         const double qn = qnorm_sh;
         int64_t slo = 0, shi = 0;
-        if constexpr (SCOPED) {
+        if constexpr (PRED == REDO_SCOPED) {
             slo = scope_lo[q];
             shi = scope_hi[q];
         }
+        int64_t moff = -1;
+        if constexpr (PRED == REDO_MASKED) moff = mask_offset(ms, q);
         for (int64_t c0 = lo; c0 < hi; c0 += CHUNK) {
             const int cn = (int)(hi - c0 < CHUNK ? hi - c0 : CHUNK);
             int mine = 0;
@@ -207,7 +213,8 @@ __global__ void __launch_bounds__(REDO_THREADS)
                 const int64_t p = slot_of(rv, c0 + i);
                 bool in = true;
                 if constexpr (SCOPED) {
-                    in = in_scope(tag[p], slo, shi);
+                    if constexpr (PRED == REDO_SCOPED) in = in_scope(tag[p], slo, shi);
+                    else in = mask_selects(ms.words, moff, p);
                     live[i] = in ? 1 : 0;
                 }
                 if (in) {
@@ -293,25 +300,30 @@ int vm_topk_redo_blocks(const vm_memory *m, int chunk) {
 
 template <int DT>
 static int redo_scan(vm_memory *m, const void *queries, int Q, int k, const int64_t *scope_lo, const int64_t *scope_hi,
-              const int32_t *flags, int nblk, double *part_s, int64_t *part_o, hipStream_t st) {
+              const int32_t *flags, int nblk, double *part_s, int64_t *part_o, hipStream_t st, const MaskSel *mask) {
     const size_t ql = (size_t)m->D * 2;
-    if (scope_lo)
-        topk_redo_scan_kernel<DT, VM_REDO_CHUNK_SCOPED, true><<<nblk, REDO_THREADS, ql, st>>>(
-            (const uint16_t *)queries, m->rows, m->norm64, m->tag, scope_lo, scope_hi, m->d_total, m->cap, m->ring, m->D,
-            Q, k, flags, part_s, part_o);
-    else
-        topk_redo_scan_kernel<DT, VM_REDO_CHUNK, false><<<nblk, REDO_THREADS, ql + (size_t)VM_REDO_CHUNK * 8, st>>>(
+    if (mask)
+        topk_redo_scan_kernel<DT, VM_REDO_CHUNK_SCOPED, REDO_MASKED><<<nblk, REDO_THREADS, ql, st>>>(
             (const uint16_t *)queries, m->rows, m->norm64, nullptr, nullptr, nullptr, m->d_total, m->cap, m->ring, m->D,
-            Q, k, flags, part_s, part_o);
+            Q, k, flags, part_s, part_o, *mask);
+    else if (scope_lo)
+        topk_redo_scan_kernel<DT, VM_REDO_CHUNK_SCOPED, REDO_SCOPED><<<nblk, REDO_THREADS, ql, st>>>(
+            (const uint16_t *)queries, m->rows, m->norm64, m->tag, scope_lo, scope_hi, m->d_total, m->cap, m->ring, m->D,
+            Q, k, flags, part_s, part_o, MaskSel{});
+    else
+        topk_redo_scan_kernel<DT, VM_REDO_CHUNK, REDO_ALL><<<nblk, REDO_THREADS, ql + (size_t)VM_REDO_CHUNK * 8, st>>>(
+            (const uint16_t *)queries, m->rows, m->norm64, nullptr, nullptr, nullptr, m->d_total, m->cap, m->ring, m->D,
+            Q, k, flags, part_s, part_o, MaskSel{});
     VM_LAUNCH_CHECK(m->ctx);
     return VM_OK;
 }
 
 int vm_topk_redo_scan(vm_memory *m, const void *queries, int Q, int k, const int64_t *scope_lo,
                       const int64_t *scope_hi, const int32_t *flags, int nblk, double *part_s, int64_t *part_o,
-                      hipStream_t st) {
-    return m->dtype == VM_F16 ? redo_scan<VM_F16>(m, queries, Q, k, scope_lo, scope_hi, flags, nblk, part_s, part_o, st)
-                              : redo_scan<VM_BF16>(m, queries, Q, k, scope_lo, scope_hi, flags, nblk, part_s, part_o, st);
+                      hipStream_t st, const MaskSel *mask) {
+    return m->dtype == VM_F16
+               ? redo_scan<VM_F16>(m, queries, Q, k, scope_lo, scope_hi, flags, nblk, part_s, part_o, st, mask)
+               : redo_scan<VM_BF16>(m, queries, Q, k, scope_lo, scope_hi, flags, nblk, part_s, part_o, st, mask);
 }
 
 int vm_topk_redo_merge(vm_memory *m, const double *part_s, const int64_t *part_o, int nblk, int Q, int k,

@@ -1,0 +1,266 @@
+// Masked cosine top-k: the k best rows among those a device BIT MASK selects (include/vidmem.h vm_topk_cosine_masked),
+// and the two device-side builders of such masks.  The row set is an operand: one bit per physical slot, built on the
+// host or on the device, combined with & | ~ by the caller, named per query.  Generalises the one predicate shape of the
+// scoped search (topk_scope.hip: one inclusive tag range per query) to any set: a metadata filter, the hits of another
+// search, an exclusion, a union of windows.
+//
+// The scoped search with another predicate, and built from the same parts:
+//   scan     : topk_tile_scan.h under the MaskScan policy below.  Per 16-row tile the wave first reads the tile's 16 mask
+//              bits of each of its queries (2 bytes per query, against the 128 bytes of tags of the scoped pre-test); a
+//              tile no query selects a live row of is skipped WITHOUT reading its rows and only zeroes its keys.
+//              Otherwise fp32 MFMA scores, F[q][slot] = okey32(score) for a selected live row, 0 for any other
+//   select   : topk_scope_select.h, unchanged: the best M + 1 selected rows by (fp32 key desc, age order asc)
+//   finalize : topk_scope_select.h's scope_finalize_kernel, unchanged: nothing in it is specific to scopes.  Certified
+//              when the mask selects at most M rows, or when the exact k-th score clears the (M+1)-th SELECTED fp32
+//              score / ||q|| by cert_eps(D), strictly.  Unselected rows have key 0 and never reach the certificate
+//   redo     : vm_topk_redo_scan with the mask predicate (topk_exact.hip), then vm_topk_redo_merge
+// A bit whose slot holds no live row is ignored everywhere: the scan and the redo visit live slots only.
+// Every launch reads the row count from the device and sizes its grid from the capacity: capturable.
+#include "topk_scope_select.h"
+#include "topk_tile_scan.h"
+
+namespace {
+
+// ---- scan --------------------------------------------------------------------------------------------------
+// The masked policy of the tile scan: four keys per lane, F[q * fstride + slot] = the order-preserving key of the fp32
+// score, or 0 when the query's mask does not select the slot or the slot is past the live rows.  A tile's 16 bits are
+// halfword tile & 1 of word tile >> 1 of the mask: halfword `tile` from the mask's first word (little endian).
+struct MaskScan {
+    struct Args {
+        MaskSel ms;
+        int64_t fstride;
+        uint32_t *F;
+    };
+    template <int QT>
+    struct QState {
+        int off[QT * 16];  // word offset of the query's mask, -1 = the empty mask (also: the query is past Q)
+    };
+    struct View {};
+    template <class QS>
+    static __device__ __forceinline__ void load_query(QS &qs, const Args &a, int i, int q, bool live) {
+        qs.off[i] = live ? (int)mask_offset(a.ms, q) : -1;
+    }
+    static __device__ __forceinline__ View view(const Args &, const RingView &) { return {}; }
+    // the 16 bits of `tile` in the mask at word offset off, the slots at and past n cleared
+    static __device__ __forceinline__ uint32_t tile_bits(const Args &a, int off, const TileLane &l) {
+        if (off < 0) return 0u;
+        // the tile is the same in every lane of a wave: what depends on it alone is scalar, so that nothing of it stays in
+        // VGPRs across the MFMA loop (without this: 84 VGPRs at QT = 2, against ScopeScan's 80)
+        const int tile = __builtin_amdgcn_readfirstlane((int)l.tile);
+        const int64_t left = l.n - (int64_t)tile * 16;  // >= 1: the scan visits tiles that hold a live slot
+        const uint32_t live = left < 16 ? (1u << left) - 1u : 0xffffu;
+        // a 32-bit byte offset from the masks' base (the host refuses more than 2^30 words of masks): one address VGPR
+        const uint32_t byte = (uint32_t)off * 4u + (uint32_t)tile * 2u;
+        const uint32_t b = *reinterpret_cast<const uint16_t *>(reinterpret_cast<const char *>(a.ms.words) + byte) & live;
+        return b;
+    }
+    template <int QT>
+    static __device__ __forceinline__ bool skip_tile(const QState<QT> &qs, const Args &a, const TileLane &l) {
+        // lane i < QT * 16 reads the tile's bits of block query i; wave-uniform: some query selects some live row
+        const uint32_t b = l.lane < QT * 16 ? tile_bits(a, qs.off[l.lane], l) : 0u;
+        if (__ballot(b != 0u) != 0ull) return false;
+#pragma unroll
+        for (int t = 0; t < QT; ++t) {  // a skipped tile only zeroes its keys
+            const int q = l.q0 + 16 * t + l.r16;
+            if (q < l.Q) *reinterpret_cast<uint4 *>(a.F + (size_t)q * a.fstride + l.p0()) = make_uint4(0, 0, 0, 0);
+        }
+        return true;
+    }
+    template <int QT>
+    static __device__ __forceinline__ void epilogue(const QState<QT> &qs, const Args &a, const View &,
+                                                    const TileLane &l, const float (&s)[QT][4]) {
+#pragma unroll
+        for (int t = 0; t < QT; ++t) {
+            const int q = l.q0 + 16 * t + l.r16;
+            if (q >= l.Q) continue;
+            const uint32_t b = tile_bits(a, qs.off[16 * t + l.r16], l) >> (4 * l.h);  // the lane's four slots
+            uint32_t key[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) key[j] = ((b >> j) & 1u) ? okey32(s[t][j]) : 0u;
+            *reinterpret_cast<uint4 *>(a.F + (size_t)q * a.fstride + l.p0()) = make_uint4(key[0], key[1], key[2], key[3]);
+        }
+    }
+};
+
+__global__ void mask_fill_flags_kernel(int32_t *__restrict__ flags, int Q) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < Q) flags[i] = 1;
+}
+
+// ---- builders ----------------------------------------------------------------------------------------------
+// Thread = one entry of row_ids: the bit of a live row's slot is ORed into the mask (the result does not depend on the
+// order of the atomics).  -1, an id that is not row * stride + offset, and a row that is not live are skipped.
+__global__ void __launch_bounds__(256)
+    mask_from_rows_kernel(const int64_t *__restrict__ row_ids, int64_t n, int64_t row_stride, int64_t row_offset,
+                          const int64_t *__restrict__ d_total, int64_t cap, int ring, uint32_t *__restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int64_t id = row_ids[i];
+    if (id < 0) return;
+    const int64_t d = id - row_offset;
+    if (d < 0 || d % row_stride != 0) return;
+    const int64_t r = d / row_stride;
+    const RingView rv = ring_view(*d_total, cap, ring);
+    if (r < rv.base || r >= rv.base + rv.n) return;
+    const int64_t s = r % cap;  // = slot_of(rv, r - rv.base): below W * 32
+    atomicOr(out + (s >> 5), 1u << (s & 31));
+}
+
+// Thread = one slot, a wave = two words of the mask; the grid covers all W * 32 slots, so every word is written and a
+// slot that holds no live row gives 0.
+__global__ void __launch_bounds__(256)
+    mask_from_scopes_kernel(const int64_t *__restrict__ tag, const int64_t *__restrict__ scope_lo,
+                            const int64_t *__restrict__ scope_hi, int n_ranges, const int64_t *__restrict__ d_total,
+                            int64_t cap, int ring, int64_t W, uint32_t *__restrict__ out) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= W * 32) return;  // wave-uniform: W * 32 is a multiple of 64
+    const int64_t n = ring_view(*d_total, cap, ring).n;
+    bool in = false;
+    if (p < n) {
+        const int64_t tg = tag[p];
+        for (int i = 0; i < n_ranges; ++i) in |= in_scope(tg, scope_lo[i], scope_hi[i]);
+    }
+    const unsigned long long b = __ballot(in);
+    const int lane = threadIdx.x & 63;
+    if (lane == 0) out[p >> 5] = (uint32_t)b;
+    if (lane == 32) out[p >> 5] = (uint32_t)(b >> 32);
+}
+
+// ---- host --------------------------------------------------------------------------------------------------
+int64_t mask_words(const vm_memory *m) { return (m->cap + 63) / 64 * 2; }
+
+int mask_check(vm_memory *m, const void *queries, int Q, int k, const uint32_t *masks, int n_masks,
+               const int32_t *mask_index, int score_mode, const double *out_scores, const int64_t *out_rows,
+               const void *workspace, size_t workspace_bytes, const char *who) {
+    const bool ok = queries && masks && out_scores && out_rows && Q > 0 && n_masks > 0 &&
+                    (mask_index || n_masks == 1 || n_masks == Q) && !((uintptr_t)masks & 3);
+    // the scan addresses a mask halfword by a 32-bit byte offset from `masks` (MaskScan::tile_bits)
+    if (ok && (int64_t)n_masks * mask_words(m) > ((int64_t)1 << 30))
+        return vm_fail(m->ctx, VM_ERR_UNSUPPORTED, "%s: more than 2^30 words of masks", who);
+    return vm_topk_check(m, nullptr, ok, queries, k, SKMAX, VM_ERR_INVALID, score_mode, workspace, workspace_bytes,
+                         scope_plan(m, Q, k).total, who);
+}
+
+int mask_redo(vm_memory *m, const SPlan &p, const void *queries, int Q, int k, const MaskSel &ms, int use_min,
+              double min_score, int score_mode, int64_t row_stride, int64_t row_offset, double *out_scores,
+              int64_t *out_rows, char *ws, hipStream_t st) {
+    vm_prof_scope prof(m->ctx, VM_PROF_TOPK_EXACT, st);
+    const int32_t *flags = (const int32_t *)(ws + p.off_flags);
+    double *part_s = (double *)(ws + p.off_ps);
+    int64_t *part_o = (int64_t *)(ws + p.off_po);
+    if (int rc = vm_topk_redo_scan(m, queries, Q, k, nullptr, nullptr, flags, p.nblk, part_s, part_o, st, &ms)) return rc;
+    return vm_topk_redo_merge(m, part_s, part_o, p.nblk, Q, k, flags, use_min, min_score, score_mode, row_stride,
+                              row_offset, out_scores, out_rows, nullptr, nullptr, st);
+}
+
+template <int DT>
+int mask_topk(vm_memory *m, const void *queries, int Q, int k, const MaskSel &ms, int use_min, double min_score,
+              int score_mode, int64_t row_stride, int64_t row_offset, double *out_scores, int64_t *out_rows,
+              int32_t *out_uncertified, int32_t *out_query_flags, char *ws, hipStream_t st) {
+    vm_ctx *ctx = m->ctx;
+    const SPlan p = scope_plan(m, Q, k);  // the scoped search's workspace: the same stages over the same key image
+    uint32_t *F = (uint32_t *)ws;
+    int *cand_o = (int *)(ws + p.off_co);
+    uint32_t *cand_k = (uint32_t *)(ws + p.off_ck);
+    int *cand_n = (int *)(ws + p.off_cn);
+    int *flags = (int *)(ws + p.off_flags);
+    {
+        vm_prof_scope prof(ctx, VM_PROF_TOPK_SCAN, st);
+        const int rc = vm_tile_scan<DT, MaskScan>(m, p, queries, Q, {ms, p.fstride, F}, st);
+        if (rc != VM_OK) return rc;
+    }
+    {
+        vm_prof_scope prof(ctx, VM_PROF_TOPK_FINALIZE, st);
+        uint32_t *cut = (uint32_t *)(ws + p.off_cut);
+        int *ccount = (int *)(ws + p.off_cc);
+        unsigned long long *cbuf = (unsigned long long *)(ws + p.off_cbuf);
+        scope_cut_kernel<<<Q, SEL_THREADS, 0, st>>>(m->d_total, m->cap, m->ring, F, p.fstride, p.M + 1, cut, ccount);
+        VM_LAUNCH_CHECK(ctx);
+        scope_compact_kernel<<<dim3(p.cmp_slices, Q), CMP_THREADS, 0, st>>>(m->d_total, m->cap, m->ring, F, p.fstride,
+                                                                            cut, ccount, cbuf);
+        VM_LAUNCH_CHECK(ctx);
+        scope_select_kernel<<<Q, SEL_THREADS, 0, st>>>(p.M + 1, ccount, cbuf, cand_o, cand_k, cand_n);
+        VM_LAUNCH_CHECK(ctx);
+        scope_finalize_kernel<DT><<<Q, SF_THREADS, (size_t)m->D * 2, st>>>(
+            m->rows, m->norm64, (const uint16_t *)queries, m->d_total, m->cap, m->ring, m->D, cand_o, cand_k, cand_n,
+            p.M, k, use_min, min_score, score_mode, row_stride, row_offset, out_scores, out_rows, out_uncertified, flags,
+            out_query_flags);
+        VM_LAUNCH_CHECK(ctx);
+    }
+    return mask_redo(m, p, queries, Q, k, ms, use_min, min_score, score_mode, row_stride, row_offset, out_scores,
+                     out_rows, ws, st);
+}
+
+}  // namespace
+
+extern "C" int64_t vm_memory_mask_words(const vm_memory *m) { return m ? mask_words(m) : 0; }
+
+extern "C" size_t vm_topk_masked_workspace_bytes(const vm_memory *m, int Q, int k) {
+    if (!m || Q <= 0 || k <= 0 || k > SKMAX) return 0;
+    return scope_plan(m, Q, k).total;
+}
+
+extern "C" int vm_topk_cosine_masked(vm_memory *m, const void *queries, int Q, int k, const uint32_t *masks,
+                                     int n_masks, const int32_t *mask_index, int use_min_score, double min_score,
+                                     int score_mode, int64_t row_stride, int64_t row_offset, double *out_scores,
+                                     int64_t *out_rows, int32_t *out_uncertified, int32_t *out_query_flags,
+                                     void *workspace, size_t workspace_bytes, void *stream) {
+    if (!m) return VM_ERR_INVALID;
+    int rc = mask_check(m, queries, Q, k, masks, n_masks, mask_index, score_mode, out_scores, out_rows, workspace,
+                        workspace_bytes, "vm_topk_cosine_masked");
+    if (rc != VM_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const MaskSel ms = {masks, mask_index, n_masks, mask_words(m)};
+    return vm_by_dtype(m, [&](auto dt) {
+        return mask_topk<decltype(dt)::value>(m, queries, Q, k, ms, use_min_score, min_score, score_mode, row_stride,
+                                              row_offset, out_scores, out_rows, out_uncertified, out_query_flags,
+                                              (char *)workspace, st);
+    });
+}
+
+extern "C" int vm_topk_cosine_masked_exact(vm_memory *m, const void *queries, int Q, int k, const uint32_t *masks,
+                                           int n_masks, const int32_t *mask_index, int use_min_score, double min_score,
+                                           int score_mode, int64_t row_stride, int64_t row_offset, double *out_scores,
+                                           int64_t *out_rows, void *workspace, size_t workspace_bytes, void *stream) {
+    if (!m) return VM_ERR_INVALID;
+    int rc = mask_check(m, queries, Q, k, masks, n_masks, mask_index, score_mode, out_scores, out_rows, workspace,
+                        workspace_bytes, "vm_topk_cosine_masked_exact");
+    if (rc != VM_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const SPlan p = scope_plan(m, Q, k);
+    char *ws = (char *)workspace;
+    mask_fill_flags_kernel<<<(Q + 255) / 256, 256, 0, st>>>((int32_t *)(ws + p.off_flags), Q);
+    VM_LAUNCH_CHECK(m->ctx);
+    const MaskSel ms = {masks, mask_index, n_masks, mask_words(m)};
+    return mask_redo(m, p, queries, Q, k, ms, use_min_score, min_score, score_mode, row_stride, row_offset, out_scores,
+                     out_rows, ws, st);
+}
+
+extern "C" int vm_mask_from_rows(vm_memory *m, const int64_t *row_ids, int64_t n, int64_t row_stride,
+                                 int64_t row_offset, int clear_first, uint32_t *out_mask, void *stream) {
+    if (!m) return VM_ERR_INVALID;
+    vm_ctx *ctx = m->ctx;
+    if (!out_mask || ((uintptr_t)out_mask & 3) || n < 0 || (n > 0 && !row_ids) || row_stride < 1)
+        return vm_fail(ctx, VM_ERR_INVALID, "vm_mask_from_rows: bad arguments");
+    hipStream_t st = (hipStream_t)stream;
+    if (clear_first) VM_HIP(ctx, hipMemsetAsync(out_mask, 0, (size_t)mask_words(m) * 4, st));
+    if (n == 0) return VM_OK;
+    mask_from_rows_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(row_ids, n, row_stride, row_offset, m->d_total,
+                                                                     m->cap, m->ring, out_mask);
+    VM_LAUNCH_CHECK(ctx);
+    return VM_OK;
+}
+
+extern "C" int vm_mask_from_scopes(vm_memory *m, const int64_t *scope_lo, const int64_t *scope_hi, int n_ranges,
+                                   uint32_t *out_mask, void *stream) {
+    if (!m) return VM_ERR_INVALID;
+    vm_ctx *ctx = m->ctx;
+    if (!m->tag) return vm_fail(ctx, VM_ERR_INVALID, "vm_mask_from_scopes: the memory is not tagged");
+    if (!out_mask || ((uintptr_t)out_mask & 3) || n_ranges < 0 || (n_ranges > 0 && (!scope_lo || !scope_hi)))
+        return vm_fail(ctx, VM_ERR_INVALID, "vm_mask_from_scopes: bad arguments");
+    const int64_t W = mask_words(m);
+    mask_from_scopes_kernel<<<(unsigned)((W * 32 + 255) / 256), 256, 0, (hipStream_t)stream>>>(
+        m->tag, scope_lo, scope_hi, n_ranges, m->d_total, m->cap, m->ring, W, out_mask);
+    VM_LAUNCH_CHECK(ctx);
+    return VM_OK;
+}

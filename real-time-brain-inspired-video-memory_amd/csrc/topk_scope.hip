@@ -24,7 +24,7 @@
 //              every redo (vm_topk_redo_merge; both topk_exact.hip).  Flags and
 //              counts are read on the device; near-empty when nothing is flagged.
 // Every launch reads the row count from the device and sizes its grid from the capacity: capturable.
-#include "topk_scope_select.h"  // the select stage (cut, compaction, selection): shared with topk_clip.hip
+#include "topk_scope_select.h"  // the select stage (cut, compaction, selection) and the finalize: shared
 #include "topk_tile_scan.h"
 
 #include <climits>
@@ -81,98 +81,6 @@ struct ScopeScan {
     }
 };
 
-// ---- finalize ----------------------------------------------------------------------------------------------
-// One block per query.  Ranks the C candidates by (fp32 key desc, order asc): the first nc = min(C, M) are re-scored
-// exactly, the (M+1)-th (if any) bounds every other in-scope row.
-template <int DT>
-__global__ void __launch_bounds__(SF_THREADS)
-    scope_finalize_kernel(const uint16_t *__restrict__ mem, const double *__restrict__ norm64,
-                          const uint16_t *__restrict__ queries, const int64_t *__restrict__ d_total, int64_t cap,
-                          int ring, int D, const int *__restrict__ cand_o, const uint32_t *__restrict__ cand_k,
-                          const int *__restrict__ cand_n, int M, int k, int use_min, double min_score, int score_mode,
-                          int64_t row_stride, int64_t row_offset, double *__restrict__ out_scores,
-                          int64_t *__restrict__ out_rows, int *__restrict__ uncertified, int *__restrict__ flags,
-                          int *__restrict__ user_flags) {
-    extern __shared__ __attribute__((aligned(16))) char sf_dyn[];
-    uint16_t *ql = reinterpret_cast<uint16_t *>(sf_dyn);  // [D]
-    __shared__ int so[SCMAX], lo_[SCMAX];
-    __shared__ uint32_t sk[SCMAX], lk[SCMAX];
-    __shared__ double es[SCMAX];
-    __shared__ double qn_sh;
-    __shared__ int flag_sh;
-    const int q = blockIdx.x, tid = threadIdx.x;
-    const RingView rv = ring_view(*d_total, cap, ring);
-    const int C = cand_n[q];
-    if (C < 0) {  // uniform: more rows at the cut than the buffer holds -> the exhaustive redo answers this query
-        for (int i = tid; i < k; i += SF_THREADS) {
-            out_scores[(size_t)q * k + i] = 0.0;
-            out_rows[(size_t)q * k + i] = -1;
-        }
-        if (tid == 0) {
-            flags[q] = VM_FLAG_OVERFLOW;
-            if (user_flags) user_flags[q] = VM_FLAG_OVERFLOW;
-            if (uncertified) atomicAdd(uncertified, 1);
-        }
-        return;
-    }
-    const int nc = C < M ? C : M;
-    for (int i = tid; i < D / 8; i += SF_THREADS)
-        reinterpret_cast<uint4 *>(ql)[i] = reinterpret_cast<const uint4 *>(queries + (size_t)q * D)[i];
-    if (tid < C) {
-        lo_[tid] = cand_o[(size_t)q * SCMAX + tid];
-        lk[tid] = cand_k[(size_t)q * SCMAX + tid];
-    }
-    if (tid == 0) flag_sh = VM_FLAG_CERTIFIED;
-    __syncthreads();
-    if (tid < C) {  // rank by (fp32 key desc, order asc)
-        const int o = lo_[tid];
-        const uint32_t key = lk[tid];
-        int r = 0;
-        for (int j = 0; j < C; ++j) r += (lk[j] > key || (lk[j] == key && lo_[j] < o)) ? 1 : 0;
-        so[r] = o;
-        sk[r] = key;
-    }
-    if (tid == SF_THREADS - 1) qn_sh = __dsqrt_rn(ref_sumsq<DT>(ql, D));
-    __syncthreads();
-    const double qn = qn_sh;
-    if (tid < nc) {
-        const int64_t p = slot_of(rv, so[tid]);
-        es[tid] = ref_cosine(ref_dot<DT>(ql, mem + (size_t)p * D, D), qn, norm64[p]);
-    }
-    __syncthreads();
-    if (tid < nc) {
-        const double e = es[tid];
-        const int o = so[tid];
-        int r = 0;
-        for (int d = 0; d < nc; ++d) r += (es[d] > e || (es[d] == e && so[d] < o)) ? 1 : 0;
-        if (r < k) {
-            const double shown = shown_score(e, score_mode);
-            const bool pass = passes_min(use_min, shown, min_score);
-            out_scores[(size_t)q * k + r] = pass ? shown : 0.0;
-            out_rows[(size_t)q * k + r] = pass ? (rv.base + o) * row_stride + row_offset : -1;
-        }
-        // certification: the exact k-th score against the best fp32 score of an in-scope row that was not re-scored
-        const int kth = (k < nc ? k : nc) - 1;
-        if (r == kth && C > M && qn != 0.0 && !clears_gap(e, sk[M], qn, D)) flag_sh = VM_FLAG_GAP;
-    }
-    for (int i = nc + tid; i < k; i += SF_THREADS) {
-        out_scores[(size_t)q * k + i] = 0.0;
-        out_rows[(size_t)q * k + i] = -1;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        int f = flag_sh;
-        // domain of the certificate (topk_common.h cert_eps; bf16 only): outside it the in-call redo answers the query
-        if constexpr (DT == VM_BF16) {
-            if (f == VM_FLAG_CERTIFIED && rv.n > 0 && (d_total[VM_GSTATE_OUTSIDE] != 0 || cert_norm_outside(qn)))
-                f = VM_FLAG_GAP;
-        }
-        flags[q] = f;
-        if (user_flags) user_flags[q] = f;
-        if (f && uncertified) atomicAdd(uncertified, 1);
-    }
-}
-
 // ---- redo --------------------------------------------------------------------------------------------------
 __global__ void scope_fill_flags_kernel(int32_t *__restrict__ flags, int Q) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -180,30 +88,6 @@ __global__ void scope_fill_flags_kernel(int32_t *__restrict__ flags, int Q) {
 }
 
 // ---- host --------------------------------------------------------------------------------------------------
-struct SPlan : TopkGeom {
-    int64_t fstride;
-    size_t off_co, off_ck, off_cn, off_flags, off_cut, off_cc, off_cbuf, off_ps, off_po, total;
-};
-
-SPlan scope_plan(const vm_memory *m, int Q, int k) {
-    SPlan p;
-    static_cast<TopkGeom &>(p) = vm_topk_geom(m, Q, k, TS_THREADS, VM_REDO_CHUNK_SCOPED);
-    p.fstride = (m->cap + 63) / 64 * 64;  // the columns' padding: a tail tile writes its 16 keys
-    WsBump ws;
-    ws.take((size_t)Q * (size_t)p.fstride * 4);  // F at offset 0: [Q][slot] fp32 keys
-    p.off_co = ws.take((size_t)Q * SCMAX * 4);
-    p.off_ck = ws.take((size_t)Q * SCMAX * 4);
-    p.off_cn = ws.take((size_t)Q * 4);
-    p.off_flags = ws.take((size_t)Q * 4);
-    p.off_cut = ws.take((size_t)Q * 4);
-    p.off_cc = ws.take((size_t)Q * 4);
-    p.off_cbuf = ws.take((size_t)Q * SEL_CAP * 8);
-    p.off_ps = ws.take((size_t)p.nblk * Q * k * 8);
-    p.off_po = ws.take((size_t)p.nblk * Q * k * 8);
-    p.total = ws.off;
-    return p;
-}
-
 int scope_check(vm_memory *m, const void *queries, int Q, int k, const int64_t *scope_lo, const int64_t *scope_hi,
                 int score_mode, const double *out_scores, const int64_t *out_rows, const void *workspace,
                 size_t workspace_bytes, const char *who) {

@@ -1,7 +1,8 @@
-// The fp32 MFMA tile scan of the grouped, scoped and range searches, written once: every live row
+// The fp32 MFMA tile scan of the grouped, scoped, masked and range searches, written once: every live row
 // against a tile of queries, with the list scan's numerics - topk_scan_kernel's (topk.hip) instruction over the same
 // operand layout, then x 1/||row|| - which is what cert_eps(D) (topk_common.h) is a statement about.  A search supplies
-// a POLICY for what differs, defined next to the rest of that search (topk_group.hip, topk_scope.hip, range.hip):
+// a POLICY for what differs, defined next to the rest of that search (topk_group.hip, topk_scope.hip, range.hip,
+// topk_mask.hip):
 //   struct Args                      what the policy reads and writes, passed to the kernel by value
 //   template <int QT> struct QState  per-query state of the block's QT * 16 queries in static LDS (empty: none)
 //   struct View                      what the policy derives once per thread from the live-row view

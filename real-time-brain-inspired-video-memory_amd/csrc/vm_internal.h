@@ -63,6 +63,24 @@ __host__ __device__ inline int64_t order_of(const RingView &v, int64_t p) {
 // tagged memories: a row is in a query's scope when its tag lies in the inclusive range [lo, hi]
 __host__ __device__ inline bool in_scope(int64_t tag, int64_t lo, int64_t hi) { return lo <= tag && tag <= hi; }
 
+// Row masks (include/vidmem.h vm_topk_cosine_masked): n_masks arrays of W 32-bit words, bit s & 31 of word s >> 5 = the
+// row in physical slot s.  index: null (one mask for every query, or mask q for query q) or the mask each query names.
+struct MaskSel {
+    const uint32_t *words;
+    const int32_t *index;
+    int n_masks;
+    int64_t W;
+};
+// word offset of query q's mask, -1 = the empty mask (an index outside [0, n_masks))
+__host__ __device__ inline int64_t mask_offset(const MaskSel &ms, int q) {
+    const int64_t i = ms.index ? ms.index[q] : (ms.n_masks == 1 ? 0 : q);
+    return i < 0 || i >= ms.n_masks ? -1 : i * ms.W;
+}
+// whether the mask at word offset off (-1: empty) selects physical slot p; a consumer tests p for liveness itself
+__host__ __device__ inline bool mask_selects(const uint32_t *words, int64_t off, int64_t p) {
+    return off >= 0 && ((words[off + (p >> 5)] >> (p & 31)) & 1u);
+}
+
 // grouped memories: the live rows + the ordinal of the oldest live group + the number of live groups, from the device
 // counters.  Groups are runs of equal ordinals (gord above), so live group g = ordinal - ord0, 0 <= g < ng.
 struct GroupView {
@@ -116,10 +134,11 @@ constexpr int VM_REDO_CHUNK = 2048, VM_REDO_CHUNK_SCOPED = 1024;
 // The redo scan of rows: for every flagged query, block b of nblk scores its slice of age orders exactly and leaves the
 // slice's stable top-k in part_s / part_o [nblk][Q][k].  scope_lo == null: every live row, nblk =
 // vm_topk_redo_blocks(m, VM_REDO_CHUNK); otherwise the rows whose tag lies in the query's [scope_lo, scope_hi] only,
-// nblk = vm_topk_redo_blocks(m, VM_REDO_CHUNK_SCOPED).  vm_topk_redo_merge follows.
+// nblk = vm_topk_redo_blocks(m, VM_REDO_CHUNK_SCOPED).  mask != null (scope_lo null): the rows the query's mask selects
+// only, the scoped scan's chunk and nblk.  vm_topk_redo_merge follows.
 int vm_topk_redo_scan(vm_memory *m, const void *queries, int Q, int k, const int64_t *scope_lo,
                       const int64_t *scope_hi, const int32_t *flags, int nblk, double *part_s, int64_t *part_o,
-                      hipStream_t st);
+                      hipStream_t st, const MaskSel *mask = nullptr);
 // Merge of the redo scans' slice winners, part_s / part_o [nblk][Q][k] = {score, age order}, for the flagged queries:
 // stable top-k, score mapping, min_score, row id = (base + order) * row_stride + row_offset.  gkey / out_keys: null, or
 // the grouped search's key column and key output.

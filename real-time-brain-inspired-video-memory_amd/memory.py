@@ -41,8 +41,8 @@ import torch
 
 from . import _lib
 from .scratch import (NOVEL_MAX_ROWS, ClipScratch, EraseScratch, EventsScratch, GroupedScopedTopkScratch,  # noqa: F401
-                      GroupedTopkScratch, NoveltyScratch, RangeScratch, ScopedTopkScratch, Scratch, SummaryScratch,
-                      TopkScratch)
+                      GroupedTopkScratch, MaskedTopkScratch, NoveltyScratch, RangeScratch, ScopedTopkScratch, Scratch,
+                      SummaryScratch, TopkScratch)
 
 
 INT64_MIN, INT64_MAX = -(1 << 63), (1 << 63) - 1
@@ -276,7 +276,7 @@ def _keep_alive(*tensors) -> None:
 
 
 class _Search(NamedTuple):
-    """One of the four top-k searches as ``EmbeddingMemory._search`` runs it: its entries, the memory it needs and the
+    """One of the five top-k searches as ``EmbeddingMemory._search`` runs it: its entries, the memory it needs and the
     arguments it takes beyond (queries, k, min_score, score_mode)."""
     words: str                   # the search in an error message
     scratch: type                # its scratch kind (which names the sizing call)
@@ -287,6 +287,7 @@ class _Search(NamedTuple):
     refusal: str = ""            # ... and says so in these words
     max_k: int = 64              # 0 = the library's own rule
     scoped: bool = False         # takes a (lo, hi) tag range per query
+    masked: bool = False         # takes row masks [n_masks, W] and the mask each query names
     keyed: bool = False          # returns the group keys as a third output
     strided: bool = False        # passes the (row_stride, row_offset) pair
     redo: Optional[str] = None   # a separate second stage that redoes the flagged queries
@@ -299,6 +300,8 @@ _GROUPED = _Search("grouped top-k", GroupedTopkScratch, "vm_topk_cosine_grouped"
 _SCOPED = _Search("scoped top-k", ScopedTopkScratch, "vm_topk_cosine_scoped", "vm_topk_cosine_scoped_exact",
                   tagged=True, scoped=True, strided=True,
                   refusal="topk_scoped needs a tagged memory (EmbeddingMemory(..., tagged=True))")
+_MASKED = _Search("masked top-k", MaskedTopkScratch, "vm_topk_cosine_masked", "vm_topk_cosine_masked_exact", masked=True,
+                  strided=True)
 _GROUPED_SCOPED = _Search("scoped grouped top-k", GroupedScopedTopkScratch, "vm_topk_cosine_grouped_scoped",
                           "vm_topk_cosine_grouped_scoped_exact", grouped=True, tagged=True, scoped=True, keyed=True,
                           refusal="topk_grouped_scoped needs a grouped and tagged memory "
@@ -800,21 +803,27 @@ class EmbeddingMemory:
 
     def _search(self, kind: _Search, queries, k, scope, min_score, score_mode, exact, scratch, stride=(1, 0),
                 redo=True) -> Tuple[torch.Tensor, ...]:
-        """The one body of ``topk``, ``topk_grouped``, ``topk_scoped`` and ``topk_grouped_scoped``.  The memory-kind and
-        ``k`` checks come before anything that needs a device."""
+        """The one body of ``topk``, ``topk_grouped``, ``topk_scoped``, ``topk_grouped_scoped`` and ``topk_masked``
+        (whose ``scope`` is the pair (mask, mask_index)).  The memory-kind, ``k`` and mask checks come before anything
+        that needs a device."""
         if (kind.grouped and not self.grouped) or (kind.tagged and not self.tagged):
             raise ValueError(kind.refusal)
         if kind.max_k and not 1 <= int(k) <= kind.max_k:
             raise ValueError(f"{kind.words} supports 1 <= k <= {kind.max_k}, got {k}")
+        masks = self._masks(scope[0]) if kind.masked else None
         q = self._as_rows(queries)
         Q, k = q.shape[0], int(k)
         sc = self._scopes(scope, Q) if kind.scoped else None
+        if kind.masked:
+            sc = self._mask_index(scope[1], masks.shape[0], Q)
         s = self._resolve(kind.scratch, scratch, Q, k)
         outs = [torch.empty((Q, k), dtype=dt, device=self.device)
                 for dt in (torch.float64, torch.int64, torch.int64)[:3 if kind.keyed else 2]]
         head = [self.handle, _ptr(q), Q, k]
         if kind.scoped:
             head += [_ptr(sc[0]), _ptr(sc[1])]
+        if kind.masked:
+            head += [_ptr(masks), masks.shape[0], _ptr(sc)]
         head += [*_min_score_args(min_score), int(score_mode)]
         if kind.strided:
             head += [int(stride[0]), int(stride[1])]
@@ -829,7 +838,7 @@ class EmbeddingMemory:
             if kind.redo and redo:
                 self.ctx.check(getattr(self.L, kind.redo)(*head, _ptr(s.flags), *outp, _ptr(s.redo_ws),
                                                           s.redo_ws.numel(), st))
-        _keep_alive(q, sc)
+        _keep_alive(q, sc, masks)
         self._last[kind.scratch] = s
         return tuple(outs)
 
@@ -921,6 +930,131 @@ class EmbeddingMemory:
         (why a query was redone, vm_topk_flag) are in ``last_group_scope_flags``.  ``scratch``: as in ``topk`` - a
         ``GroupedScopedTopkScratch`` the caller owns (a graph capture), default this memory's own."""
         return self._search(_GROUPED_SCOPED, queries, k, scope, min_score, score_mode, exact, scratch)
+
+    # ---- row masks and the masked search (include/vidmem.h vm_topk_cosine_masked, DESIGN.md 23) -------------------
+    @property
+    def mask_words(self) -> int:
+        """W: the 32-bit words of one row mask of this memory (``vm_memory_mask_words``: the capacity rounded up to 64
+        rows, / 32)."""
+        return (self.capacity + 63) // 64 * 2
+
+    def new_mask(self, n: int = 1) -> torch.Tensor:
+        """-> device int32 ``[n, W]``, all bits clear: ``n`` row masks.  The bit of row id ``r`` is bit ``s & 31`` of word
+        ``s >> 5`` with ``s = r % capacity``; bits of slots without a live row are ignored by every consumer, so masks
+        combine freely with ``& | ~``.  A mask speaks about ROW IDS: after an erase (which renumbers rows) or a ring
+        overwrite it is stale exactly as a stored row id is."""
+        return torch.zeros((int(n), self.mask_words), dtype=torch.int32, device=self.device)
+
+    def _masks(self, mask) -> torch.Tensor:
+        """-> contiguous device int32 ``[n_masks, W]`` from one mask ``[W]`` or several ``[n_masks, W]``; anything else is
+        refused before the library is called."""
+        if not isinstance(mask, torch.Tensor) or mask.dtype != torch.int32:
+            raise ValueError("a mask is an int32 tensor (EmbeddingMemory.new_mask)")
+        if mask.dim() not in (1, 2) or mask.shape[0] == 0:
+            raise ValueError(f"a mask is [W] or [n_masks, W] with n_masks >= 1, got {tuple(mask.shape)}")
+        if mask.shape[-1] != self.mask_words:
+            raise ValueError(f"mask width {mask.shape[-1]} != the {self.mask_words} words of this memory's masks")
+        return mask.reshape(-1, self.mask_words).to(self.device).contiguous()
+
+    def _mask_index(self, mask_index, n_masks: int, Q: int) -> Optional[torch.Tensor]:
+        """-> device int32 [Q] or ``None`` (one mask for all queries, or one per query)."""
+        if mask_index is None:
+            if n_masks not in (1, Q):
+                raise ValueError(f"{n_masks} masks for {Q} queries need a mask_index")
+            return None
+        if isinstance(mask_index, torch.Tensor):
+            if mask_index.dtype != torch.int32 or mask_index.dim() != 1:
+                raise ValueError("a mask_index tensor must be int32 [Q]")
+            idx = mask_index.to(self.device).contiguous()
+        else:
+            idx = torch.tensor([int(i) for i in mask_index], dtype=torch.int32).to(self.device)
+        if idx.shape[0] != Q:
+            raise ValueError(f"{idx.shape[0]} mask indices for {Q} queries")
+        return idx
+
+    def _one_mask(self, out) -> torch.Tensor:
+        """The mask a builder writes: ``out`` (one mask, ``[W]`` or ``[1, W]``, on the device) or a new one."""
+        if out is None:
+            return self.new_mask()[0]
+        if not isinstance(out, torch.Tensor) or out.dtype != torch.int32 or out.numel() != self.mask_words or \
+                out.device != self.device or not out.is_contiguous():
+            raise ValueError(f"out must be one contiguous device int32 mask of {self.mask_words} words")
+        return out
+
+    def mask_of_rows(self, rows, out: Optional[torch.Tensor] = None, clear: bool = True) -> torch.Tensor:
+        """-> the mask ``[W]`` of the live rows among ``rows``: a host sequence of row ids, or an int64 device tensor of
+        any shape as a search returned it (it is NOT read on the host; the call is stream-ordered and capturable).  -1
+        entries and ids of rows that are not live are skipped; duplicates are fine.  ``out``: the mask to write, default
+        a new one; ``clear=False`` ORs the rows into what ``out`` holds."""
+        if isinstance(rows, torch.Tensor):
+            if rows.dtype != torch.int64:
+                raise ValueError("row ids are int64")
+            ids = rows.to(self.device).contiguous().view(-1)
+        else:
+            ids = torch.tensor([int(r) for r in rows], dtype=torch.int64).to(self.device)
+        mask = self._one_mask(out)
+        self.ctx.check(self.L.vm_mask_from_rows(self.handle, _ptr(ids), ids.numel(), 1, 0, 1 if clear else 0, _ptr(mask),
+                                                _lib.current_stream_ptr()))
+        _keep_alive(ids)
+        return mask
+
+    def mask_of_scope(self, scope, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """-> the mask ``[W]`` of the live rows of a tagged memory whose tag lies in ANY of the given inclusive ranges:
+        one ``(lo, hi)``, a sequence of pairs, or an int64 ``[n, 2]`` tensor (``erase``'s selector).  Writes every word."""
+        if not self.tagged:
+            raise ValueError("mask_of_scope needs a tagged memory (EmbeddingMemory(..., tagged=True))")
+        sc = self._scopes(scope)
+        mask = self._one_mask(out)
+        self.ctx.check(self.L.vm_mask_from_scopes(self.handle, _ptr(sc[0]), _ptr(sc[1]), sc.shape[1], _ptr(mask),
+                                                  _lib.current_stream_ptr()))
+        _keep_alive(sc)
+        return mask
+
+    def _live_rows(self) -> range:
+        total = len(self)
+        return range(total - self.capacity if self.ring and total > self.capacity else 0,
+                     total if self.ring else min(total, self.capacity))
+
+    def mask_where(self, fn) -> torch.Tensor:
+        """-> the mask ``[W]`` of the live rows for which the host predicate ``fn(row, id, meta)`` holds (``id_of`` /
+        ``meta_of`` of the row): a metadata filter.  Built on the host, one upload."""
+        import numpy as np
+        bits = np.zeros(self.mask_words * 32, dtype=np.uint8)
+        for r in self._live_rows():
+            if fn(r, self.id_of(r), self.meta_of(r)):
+                bits[r % self.capacity] = 1
+        words = np.packbits(bits, bitorder="little").view(np.uint32).view(np.int32)
+        return torch.from_numpy(words.copy()).to(self.device)
+
+    def rows_of_mask(self, mask: torch.Tensor) -> List[int]:
+        """The live row ids one mask selects, ascending; decoded on the host (tests, debugging; synchronises)."""
+        import numpy as np
+        words = self._masks(mask)
+        if words.shape[0] != 1:
+            raise ValueError("rows_of_mask decodes one mask")
+        bits = np.unpackbits(words[0].cpu().numpy().view(np.uint8), bitorder="little")
+        return [r for r in self._live_rows() if bits[r % self.capacity]]
+
+    def prepare_topk_masked(self, Q: int, k: int) -> MaskedTopkScratch:
+        """Size the masked top-k workspace for (Q, k) now (before a graph capture: a capture must not allocate)."""
+        return self._prepare_search(_MASKED, Q, k)
+
+    def topk_masked(self, queries, k: int, mask, mask_index=None, min_score: Optional[float] = None,
+                    score_mode: int = _lib.VM_SCORE_RAW, exact: bool = False,
+                    scratch: Optional[MaskedTopkScratch] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """-> (scores [Q,k] float64, rows [Q,k] int64): the k best rows among those a row mask selects, on any memory.
+        ``mask``: int32 ``[W]`` (one mask for every query) or ``[n_masks, W]`` (``new_mask``, ``mask_of_rows``,
+        ``mask_of_scope``, ``mask_where``, and ``& | ~`` of them); ``mask_index``: the mask each query uses (Q ints or a
+        device int32 ``[Q]``), default mask 0 for all queries when there is one mask and mask q for query q when there are
+        Q.  An index outside ``[0, n_masks)`` is the empty mask.
+
+        The exhaustive row ranking of ``topk`` (score desc, row asc; score mapping and > min_score filter) over the
+        selected live rows only; -1 / 0.0 padded.  Always the exhaustive answer: the fp32 fast path redoes the queries it
+        cannot certify on the device, in the same call (csrc/topk_mask.hip).  ``exact=True`` scores every selected pair
+        exactly (slow).  1 <= k <= 64.  The per-query flags of the last call (why a query was redone, vm_topk_flag) are in
+        ``last_mask_flags``.  ``scratch``: as in ``topk`` - a ``MaskedTopkScratch`` the caller owns (a graph capture; a
+        replay sees the mask as it is then), default this memory's own."""
+        return self._search(_MASKED, queries, k, (mask, mask_index), min_score, score_mode, exact, scratch)
 
     # ---- clip search (include/vidmem.h vm_topk_cosine_clip, DESIGN.md 20) -----------------------------------------
     def prepare_topk_clip(self, C: int, L: int, k: int) -> "ClipScratch":
@@ -1297,6 +1431,9 @@ class EmbeddingMemory:
                                      "redid a clip, 0 = certified")
     last_range_rescored = _last_property(RangeScratch, "rescored", "int64 per query: the pairs the last fast range call "
                                          "scored exactly")
+    last_mask_flags = _last_property(MaskedTopkScratch, "flags", "int32 per query (vm_topk_flag): why the last fast masked "
+                                     "call redid a query, 0 = certified")
+    masked_uncertified_count = _count_property(MaskedTopkScratch, "Queries the masked fast path")
     grouped_uncertified_count = _count_property(GroupedTopkScratch, "Queries the grouped fast path")
     scoped_uncertified_count = _count_property(ScopedTopkScratch, "Queries the scoped fast path")
     group_scoped_uncertified_count = _count_property(GroupedScopedTopkScratch, "Queries the scoped grouped fast path")

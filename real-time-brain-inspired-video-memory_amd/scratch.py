@@ -106,7 +106,7 @@ class TopkScratch(Scratch):
 
 
 class _ScanScratch(Scratch):
-    """The workspace and the per-query ``flags`` (int32 [Q]) of a grouped and / or scoped top-k of up to (Q, k).  The
+    """The workspace and the per-query ``flags`` (int32 [Q]) of a grouped, scoped and / or masked top-k of up to (Q, k).  The
     uncertified counters of these searches are the memory's, whichever scratch a call used."""
 
     @staticmethod
@@ -120,6 +120,10 @@ class GroupedTopkScratch(_ScanScratch):
 
 class ScopedTopkScratch(_ScanScratch):
     workspaces = (("ws", "vm_topk_scoped_workspace_bytes"),)
+
+
+class MaskedTopkScratch(_ScanScratch):
+    workspaces = (("ws", "vm_topk_masked_workspace_bytes"),)
 
 
 class GroupedScopedTopkScratch(_ScanScratch):

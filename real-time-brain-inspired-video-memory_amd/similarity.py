@@ -67,8 +67,19 @@ def _check_scope(memory: EmbeddingMemory, scope, distinct: bool) -> None:
         raise ValueError("scope needs a tagged memory (EmbeddingMemory(..., tagged=True), memory.tag_by: time)")
 
 
+def _check_mask(mask, scope, distinct: bool) -> None:
+    """``mask`` (a row mask of the memory, EmbeddingMemory.topk_masked) stands alone: a scope is a mask already
+    (``mask_of_scope``, combined with ``&``), and the masked search ranks rows, not groups."""
+    if mask is None:
+        return
+    if scope is not None:
+        raise ValueError("mask and scope are mutually exclusive: combine them as mask & memory.mask_of_scope(scope)")
+    if distinct:
+        raise ValueError("mask and distinct=True are mutually exclusive: the masked search ranks rows, not groups")
+
+
 def batch_similarities(memory: EmbeddingMemory, chunk_embeddings: Sequence, top_k: int, distinct: bool = False,
-                       scope=None) -> List[List[Tuple[str, float]]]:
+                       scope=None, mask=None) -> List[List[Tuple[str, float]]]:
     """One batched top-k launch for every non-failed query; result re-threaded into the reference's list shape.
 
     A query whose length differs from the stored vectors' scores 0.0 against EVERY row in the reference
@@ -85,7 +96,12 @@ def batch_similarities(memory: EmbeddingMemory, chunk_embeddings: Sequence, top_
 
     ``distinct=True`` together with ``scope``: at most one hit per group among the in-scope rows
     (EmbeddingMemory.topk_grouped_scoped) - accepted when the memory object provides that method, ValueError otherwise.
-    The wrong-length rule then lists the first in-scope row of each of the first ``top_k`` in-scope groups."""
+    The wrong-length rule then lists the first in-scope row of each of the first ``top_k`` in-scope groups.
+
+    ``mask`` (any memory): one row mask for every query (EmbeddingMemory.new_mask / mask_of_rows / mask_where); only the
+    selected rows are ranked (EmbeddingMemory.topk_masked), and the wrong-length rule lists the first selected rows.
+    Mutually exclusive with ``scope`` and with ``distinct=True`` (ValueError)."""
+    _check_mask(mask, scope, distinct)
     _check_distinct(memory, distinct)
     _check_scope(memory, scope, distinct)
     ok_idx = [i for i, e in enumerate(chunk_embeddings) if not isinstance(e, Exception) and e is not None]
@@ -95,7 +111,9 @@ def batch_similarities(memory: EmbeddingMemory, chunk_embeddings: Sequence, top_
     wrong = [i for i in ok_idx if _length(chunk_embeddings[i]) != memory.dim]
     if wrong:
         first_row = len(memory) - memory.searchable
-        if scope is None:
+        if mask is not None:
+            zeros = [(memory.id_of(r), 0.0) for r in memory.rows_of_mask(mask)[:top_k]]
+        elif scope is None:
             zeros = [(memory.id_of(first_row + j), 0.0) for j in range(min(top_k, memory.searchable))]
         else:
             tags = memory.tags_host()
@@ -117,7 +135,9 @@ def batch_similarities(memory: EmbeddingMemory, chunk_embeddings: Sequence, top_
         q = torch.stack([chunk_embeddings[i] for i in ok_idx])
     else:
         q = torch.tensor([list(chunk_embeddings[i]) for i in ok_idx], dtype=torch.float32)
-    if scope is not None and distinct:
+    if mask is not None:
+        scores, rows = memory.topk_masked(q, top_k, mask)
+    elif scope is not None and distinct:
         scores, rows, _ = memory.topk_grouped_scoped(q, top_k, scope)
     elif scope is not None:
         scores, rows = memory.topk_scoped(q, top_k, scope)
@@ -169,25 +189,30 @@ def clip_similarities(memory: EmbeddingMemory, chunks_of_frame_embeddings: Seque
 class HipPreLLMSimilarity:
     """Mixin / stand-alone object for PreLLMInjector: set ``self.memory`` and ``self.embedder_config``."""
 
-    def __init__(self, memory: EmbeddingMemory, embedder_config: Any, distinct: bool = False, scope=None):
+    def __init__(self, memory: EmbeddingMemory, embedder_config: Any, distinct: bool = False, scope=None, mask=None):
         """``scope``: an inclusive tag range ``(lo, hi)`` (memory.scope_of) every search of this object is restricted to
         - the reference's ``WHERE c.graph_uuid = $graph_uuid`` (src/components/pre_llm_injector.py:395-396); tagged memory
         only.  Together with ``distinct`` it needs a memory that provides ``topk_grouped_scoped`` (a grouped and tagged
         EmbeddingMemory): one hit per group among the in-scope rows; ValueError otherwise.  ``None`` = the whole
-        memory."""
+        memory.  ``mask``: a row mask every search of this object is restricted to (``batch_similarities``); the object
+        keeps the tensor, so rewriting it in place changes the next search.  Not together with ``scope`` or
+        ``distinct``."""
+        _check_mask(mask, scope, distinct)
         _check_distinct(memory, distinct)
         _check_scope(memory, scope, distinct)
         self.memory = memory
         self.embedder_config = embedder_config
         self.distinct = bool(distinct)
         self.scope = scope
+        self.mask = mask
 
     async def _calculate_batch_similarities(self, chunk_embeddings, neo4j_handler=None
                                             ) -> List[List[Tuple[str, float]]]:
         try:
             return batch_similarities(self.memory, chunk_embeddings,
                                       self.embedder_config.top_k_chunk_with_batch_similarity,
-                                      distinct=getattr(self, "distinct", False), scope=getattr(self, "scope", None))
+                                      distinct=getattr(self, "distinct", False), scope=getattr(self, "scope", None),
+                                      mask=getattr(self, "mask", None))
         except _lib.VidmemError as e:
             if e.code == _lib.VM_ERR_INVALID:
                 raise
@@ -229,7 +254,7 @@ class HipVectorSearch:
 
     def __init__(self, memory: EmbeddingMemory, embedder: Any, config: Any, *, score_mode: int,
                  min_score: float = 0.3, splitter: Optional[Callable[[str], List[str]]] = None, distinct: bool = False,
-                 scope=None):
+                 scope=None, mask=None):
         """``score_mode`` is REQUIRED (keyword): the reference filters on Neo4j's
         ``vector.similarity.cosine(...) > 0.3`` (src/pipeline/retriever_hybrid.py:296-298), a third-party function of an
         unpinned server image whose value may be the raw cosine or its [0,1] mapping (1+cos)/2 - with the literal 0.3
@@ -242,7 +267,9 @@ class HipVectorSearch:
         ``MATCH (c:Chunk {graph_uuid: $graph_uuid})`` (src/pipeline/retriever_hybrid.py:295); tagged memory only.
         Together with ``distinct`` it needs a memory that provides ``topk_grouped_scoped`` (a grouped and tagged
         EmbeddingMemory; ValueError otherwise): ``top_k_chunks`` distinct chunks of the scope, each represented by its
-        best in-scope frame.  ``None`` = the whole memory."""
+        best in-scope frame.  ``None`` = the whole memory.
+        ``mask``: a row mask the search is restricted to (EmbeddingMemory.topk_masked: a metadata filter, the hits of
+        another search, an exclusion); any memory; not together with ``scope`` or ``distinct`` (ValueError)."""
         if score_mode not in (_lib.VM_SCORE_RAW, _lib.VM_SCORE_UNIT_INTERVAL):
             raise ValueError("score_mode must be VM_SCORE_RAW or VM_SCORE_UNIT_INTERVAL")
         # an embedder that states its width (HipTextEmbedder, FrameEncoder-backed ones) must match the memory's rows: a
@@ -251,17 +278,22 @@ class HipVectorSearch:
         if out_dim is not None and int(out_dim) != int(memory.dim):
             raise ValueError(f"embedder out_dim {out_dim} != memory.dim {memory.dim}: build the memory with the matching "
                              "image encoder (text questions: encoder.arch clip_l14_336_joint)")
+        _check_mask(mask, scope, distinct)
         _check_distinct(memory, distinct)
         _check_scope(memory, scope, distinct)
         self.memory, self.embedder, self.config = memory, embedder, config
         self.distinct = bool(distinct)
         self.scope = scope
+        self.mask = mask
         self.min_score, self.score_mode, self.splitter = min_score, score_mode, splitter
 
     async def _vector_search_chunks(self, session, query) -> List[Dict[str, Any]]:
         try:
             query_embedding = await self.embedder.aembed_query(query)
-            if getattr(self, "scope", None) is not None and self.distinct:
+            if getattr(self, "mask", None) is not None:
+                scores, rows = self.memory.topk_masked([query_embedding], self.config.top_k_chunks, self.mask,
+                                                       min_score=self.min_score, score_mode=self.score_mode)
+            elif getattr(self, "scope", None) is not None and self.distinct:
                 scores, rows, _ = self.memory.topk_grouped_scoped([query_embedding], self.config.top_k_chunks,
                                                                   self.scope, min_score=self.min_score,
                                                                   score_mode=self.score_mode)
