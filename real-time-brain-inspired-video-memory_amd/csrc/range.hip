@@ -76,8 +76,7 @@ __global__ void __launch_bounds__(64)
 // other 12 sit in lanes r16 + 16 h'.  cand16[q * cstride16 + tile] = the tile's 16 bits (bit i = slot tile*16 + i).
 // SCOPED = false reads no tags (every live row is in scope) and skips no tile.
 template <int QT, bool SCOPED>
-struct RangeQState {  // 16-byte aligned as the scoped search's, for the same LDS loads
-    alignas(16) int64_t lo[QT * 16], hi[QT * 16];
+struct RangeQState : TagQState<QT> {  // the scopes (topk_tile_scan.h), then the cuts
     float cut[QT * 16];
 };
 template <int QT>
@@ -97,10 +96,8 @@ struct RangeScan {
     struct View {};
     template <class QS>
     static __device__ __forceinline__ void load_query(QS &qs, const Args &a, int i, int q, bool live) {
-        if constexpr (SCOPED) {  // queries past Q have the empty scope and are never written
-            qs.lo[i] = live ? a.scope_lo[q] : LLONG_MAX;
-            qs.hi[i] = live ? a.scope_hi[q] : LLONG_MIN;
-        }
+        // queries past Q have the empty scope and are never written
+        if constexpr (SCOPED) load_tag_scope(qs, a.scope_lo, a.scope_hi, i, q, live);
         qs.cut[i] = live ? a.cut[q] : INFINITY;
     }
     static __device__ __forceinline__ View view(const Args &, const RingView &) { return {}; }

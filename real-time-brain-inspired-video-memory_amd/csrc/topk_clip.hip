@@ -97,15 +97,12 @@ struct ClipScan {
         float *S;
     };
     template <int QT>
-    struct QState {
-        alignas(16) int64_t lo[QT * 16], hi[QT * 16];
-    };
+    using QState = TagQState<QT>;
     struct View {};
     template <class QS>
     static __device__ __forceinline__ void load_query(QS &qs, const Args &a, int i, int q, bool live) {
         if (a.scope_lo) {
-            qs.lo[i] = live ? a.scope_lo[q >> 4] : LLONG_MAX;  // clips past C have the empty scope
-            qs.hi[i] = live ? a.scope_hi[q >> 4] : LLONG_MIN;
+            load_tag_scope(qs, a.scope_lo, a.scope_hi, i, q >> 4, live);  // clips past C have the empty scope
         } else {
             qs.lo[i] = LLONG_MIN;
             qs.hi[i] = LLONG_MAX;
@@ -339,11 +336,6 @@ __global__ void __launch_bounds__(SF_THREADS)
 }
 
 // ---- redo --------------------------------------------------------------------------------------------------
-__global__ void clip_fill_flags_kernel(int32_t *__restrict__ flags, int C) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < C) flags[i] = 1;
-}
-
 // grid (ceil(cap / CW_THREADS), C): W64[c][o] = the exact W of window o of a flagged clip, -inf when the window is not
 // valid or not in scope (indexed by age order)
 template <int DT>
@@ -597,7 +589,7 @@ template <int DT>
 int clip_exact(vm_memory *m, const ClipCall &a, char *ws, hipStream_t st) {
     const CPlan p = clip_plan(m, a.C, a.k);
     if (int rc = clip_pack<DT>(m, p, a, ws, st)) return rc;
-    clip_fill_flags_kernel<<<(a.C + 255) / 256, 256, 0, st>>>((int32_t *)(ws + p.off_flags), a.C);
+    fill_flags_kernel<<<(a.C + 255) / 256, 256, 0, st>>>((int32_t *)(ws + p.off_flags), a.C);
     VM_LAUNCH_CHECK(m->ctx);
     return clip_redo<DT>(m, p, a, ws, st);
 }

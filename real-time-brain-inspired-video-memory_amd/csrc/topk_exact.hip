@@ -145,21 +145,16 @@ constexpr int REDO_KMAX = 64;
 // grid = nblk row blocks; every block walks all Q flags and, for each flagged query, scores its contiguous slice of
 // age orders exactly as the reference does (src/components/pre_llm_injector.py:374-388) and keeps the slice's
 // stable top-k: part[(block * Q + q) * k + i] = {score fp64, age order int64}.  CHUNK scores are held in LDS per
-// selection pass.  The redo scan of the row search (SCOPED = false: every live row; the scores sit in dynamic LDS behind
-// the query) and of the scoped search (SCOPED = true: only the rows whose tag lies in the query's scope are scored and
-// may win, and a chunk with no in-scope row costs its tags only; the scores and the in-scope marks sit in static LDS).
-// REDO_MASKED is the scoped scan with another predicate: the bit of the row's slot in the query's mask (vm_internal.h
-// MaskSel) in place of the tag range.
-constexpr int REDO_ALL = 0, REDO_SCOPED = 1, REDO_MASKED = 2;
-template <int DT, int CHUNK, int PRED>
+// selection pass.  P = the row predicate (vm_internal.h).  NoScope: every live row, the scores sit in dynamic LDS behind
+// the query.  A scoped P (TagScope, MaskScope): only the rows it admits are scored and may win, and a chunk with none
+// costs its tags or mask words only; the scores and the in-scope marks sit in static LDS.
+template <int DT, int CHUNK, class P>
 __global__ void __launch_bounds__(REDO_THREADS)
     topk_redo_scan_kernel(const uint16_t *__restrict__ queries, const uint16_t *__restrict__ rows,
-                          const double *__restrict__ norm64, const int64_t *__restrict__ tag,
-                          const int64_t *__restrict__ scope_lo, const int64_t *__restrict__ scope_hi,
-                          const int64_t *__restrict__ d_total, int64_t cap, int ring, int D, int Q, int k,
-                          const int32_t *__restrict__ flags, double *__restrict__ part_s,
-                          int64_t *__restrict__ part_o, const MaskSel ms) {
-    constexpr bool SCOPED = PRED != REDO_ALL;  // a predicate selects the rows
+                          const double *__restrict__ norm64, const int64_t *__restrict__ d_total, int64_t cap, int ring,
+                          int D, int Q, int k, const int32_t *__restrict__ flags, double *__restrict__ part_s,
+                          int64_t *__restrict__ part_o, const P pred) {
+    constexpr bool SCOPED = P::scoped;  // a predicate selects the rows
     extern __shared__ __attribute__((aligned(16))) char smem[];
     uint16_t *ql = reinterpret_cast<uint16_t *>(smem);  // [D]
     double *sc;                                         // [CHUNK]
@@ -199,13 +194,7 @@ __global__ void __launch_bounds__(REDO_THREADS)
         if (tid == 0) qnorm_sh = __dsqrt_rn(ref_sumsq<DT>(ql, D));
         __syncthreads();
         const double qn = qnorm_sh;
-        int64_t slo = 0, shi = 0;
-        if constexpr (PRED == REDO_SCOPED) {
-            slo = scope_lo[q];
-            shi = scope_hi[q];
-        }
-        int64_t moff = -1;
-        if constexpr (PRED == REDO_MASKED) moff = mask_offset(ms, q);
+        const typename P::Q pq = pred.at(q);
         for (int64_t c0 = lo; c0 < hi; c0 += CHUNK) {
             const int cn = (int)(hi - c0 < CHUNK ? hi - c0 : CHUNK);
             int mine = 0;
@@ -213,8 +202,7 @@ __global__ void __launch_bounds__(REDO_THREADS)
                 const int64_t p = slot_of(rv, c0 + i);
                 bool in = true;
                 if constexpr (SCOPED) {
-                    if constexpr (PRED == REDO_SCOPED) in = in_scope(tag[p], slo, shi);
-                    else in = mask_selects(ms.words, moff, p);
+                    in = pq.in(p);
                     live[i] = in ? 1 : 0;
                 }
                 if (in) {
@@ -298,33 +286,27 @@ int vm_topk_redo_blocks(const vm_memory *m, int chunk) {
     return b < 1 ? 1 : (int)b;
 }
 
-template <int DT>
-static int redo_scan(vm_memory *m, const void *queries, int Q, int k, const int64_t *scope_lo, const int64_t *scope_hi,
-              const int32_t *flags, int nblk, double *part_s, int64_t *part_o, hipStream_t st, const MaskSel *mask) {
-    const size_t ql = (size_t)m->D * 2;
-    if (mask)
-        topk_redo_scan_kernel<DT, VM_REDO_CHUNK_SCOPED, REDO_MASKED><<<nblk, REDO_THREADS, ql, st>>>(
-            (const uint16_t *)queries, m->rows, m->norm64, nullptr, nullptr, nullptr, m->d_total, m->cap, m->ring, m->D,
-            Q, k, flags, part_s, part_o, *mask);
-    else if (scope_lo)
-        topk_redo_scan_kernel<DT, VM_REDO_CHUNK_SCOPED, REDO_SCOPED><<<nblk, REDO_THREADS, ql, st>>>(
-            (const uint16_t *)queries, m->rows, m->norm64, m->tag, scope_lo, scope_hi, m->d_total, m->cap, m->ring, m->D,
-            Q, k, flags, part_s, part_o, MaskSel{});
-    else
-        topk_redo_scan_kernel<DT, VM_REDO_CHUNK, REDO_ALL><<<nblk, REDO_THREADS, ql + (size_t)VM_REDO_CHUNK * 8, st>>>(
-            (const uint16_t *)queries, m->rows, m->norm64, nullptr, nullptr, nullptr, m->d_total, m->cap, m->ring, m->D,
-            Q, k, flags, part_s, part_o, MaskSel{});
+template <class P>
+int vm_topk_redo_scan(vm_memory *m, const void *queries, int Q, int k, const P &pred, const int32_t *flags, int nblk,
+                      double *part_s, int64_t *part_o, hipStream_t st) {
+    constexpr int CHUNK = P::scoped ? VM_REDO_CHUNK_SCOPED : VM_REDO_CHUNK;
+    // the unscoped scan keeps its scores in dynamic LDS behind the query, the scoped ones in static LDS
+    const size_t lds = (size_t)m->D * 2 + (P::scoped ? 0 : (size_t)CHUNK * 8);
+    auto launch = [&](auto kern) {
+        kern<<<nblk, REDO_THREADS, lds, st>>>((const uint16_t *)queries, m->rows, m->norm64, m->d_total, m->cap, m->ring,
+                                              m->D, Q, k, flags, part_s, part_o, pred);
+    };
+    if (m->dtype == VM_F16) launch(topk_redo_scan_kernel<VM_F16, CHUNK, P>);
+    else launch(topk_redo_scan_kernel<VM_BF16, CHUNK, P>);
     VM_LAUNCH_CHECK(m->ctx);
     return VM_OK;
 }
-
-int vm_topk_redo_scan(vm_memory *m, const void *queries, int Q, int k, const int64_t *scope_lo,
-                      const int64_t *scope_hi, const int32_t *flags, int nblk, double *part_s, int64_t *part_o,
-                      hipStream_t st, const MaskSel *mask) {
-    return m->dtype == VM_F16
-               ? redo_scan<VM_F16>(m, queries, Q, k, scope_lo, scope_hi, flags, nblk, part_s, part_o, st, mask)
-               : redo_scan<VM_BF16>(m, queries, Q, k, scope_lo, scope_hi, flags, nblk, part_s, part_o, st, mask);
-}
+template int vm_topk_redo_scan(vm_memory *, const void *, int, int, const NoScope &, const int32_t *, int, double *,
+                               int64_t *, hipStream_t);
+template int vm_topk_redo_scan(vm_memory *, const void *, int, int, const TagScope &, const int32_t *, int, double *,
+                               int64_t *, hipStream_t);
+template int vm_topk_redo_scan(vm_memory *, const void *, int, int, const MaskScope &, const int32_t *, int, double *,
+                               int64_t *, hipStream_t);
 
 int vm_topk_redo_merge(vm_memory *m, const double *part_s, const int64_t *part_o, int nblk, int Q, int k,
                        const int32_t *flags, int use_min, double min_score, int score_mode, int64_t row_stride,
@@ -442,7 +424,7 @@ extern "C" int vm_topk_redo_flagged(vm_memory *m, const void *queries, int Q, in
     vm_prof_scope prof(ctx, VM_PROF_TOPK_EXACT, st);
     double *part_s = (double *)workspace;
     int64_t *part_o = (int64_t *)((char *)workspace + (size_t)nblk * Q * k * 8);
-    if (int rc = vm_topk_redo_scan(m, queries, Q, k, nullptr, nullptr, query_flags, nblk, part_s, part_o, st)) return rc;
+    if (int rc = vm_topk_redo_scan(m, queries, Q, k, NoScope{}, query_flags, nblk, part_s, part_o, st)) return rc;
     return vm_topk_redo_merge(m, part_s, part_o, nblk, Q, k, query_flags, use_min_score, min_score, score_mode, row_stride,
                               row_offset, out_scores, out_rows, nullptr, nullptr, st);
 }

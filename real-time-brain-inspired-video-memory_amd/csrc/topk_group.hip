@@ -102,69 +102,21 @@ __global__ void __launch_bounds__(SEL_THREADS)
 }
 
 // ---- host --------------------------------------------------------------------------------------------------
-int group_check(vm_memory *m, const void *queries, int Q, int k, int score_mode, const double *out_scores,
-                const int64_t *out_rows, const void *workspace, size_t workspace_bytes, const char *who) {
+int group_check(vm_memory *m, const GroupCall &c, size_t workspace_bytes, const char *who) {
     return vm_topk_check(m, m->gkey ? nullptr : "grouped (vm_memory_create_grouped)",
-                         queries && out_scores && out_rows && Q > 0 && k > 0, queries, k, GKMAX, VM_ERR_UNSUPPORTED,
-                         score_mode, workspace, workspace_bytes, group_plan(m, Q, k).total, who);
+                         c.queries && c.out_scores && c.out_rows && c.Q > 0 && c.k > 0, c.queries, c.k, GKMAX,
+                         VM_ERR_UNSUPPORTED, c.score_mode, c.ws, workspace_bytes, group_plan(m, c.Q, c.k).total, who);
 }
 
-template <int DT>
-int group_redo(vm_memory *m, const GPlan &p, const void *queries, int Q, int k, int use_min, double min_score,
-               int score_mode, double *out_scores, int64_t *out_rows, int64_t *out_keys, char *ws, hipStream_t st) {
-    vm_ctx *ctx = m->ctx;
-    vm_prof_scope prof(ctx, VM_PROF_TOPK_EXACT, st);
-    const int *first_o = (const int *)(ws + p.off_first);
-    const int32_t *flags = (const int32_t *)(ws + p.off_flags);
-    double *part_s = (double *)(ws + p.off_ps);
-    int64_t *part_o = (int64_t *)(ws + p.off_po);
-    group_redo_scan_kernel<DT, NoScope><<<p.nblk, GR_THREADS, (size_t)m->D * 2, st>>>(
-        (const uint16_t *)queries, m->rows, m->norm64, m->gord, m->d_total, m->cap, m->ring, m->D, Q, k, first_o, flags,
-        part_s, part_o, NoScope{});
-    VM_LAUNCH_CHECK(ctx);
-    return vm_topk_redo_merge(m, part_s, part_o, p.nblk, Q, k, flags, use_min, min_score, score_mode, 1, 0, out_scores,
-                              out_rows, m->gkey, out_keys, st);
-}
-
-template <int DT>
-int group_topk(vm_memory *m, const void *queries, int Q, int k, int use_min, double min_score, int score_mode,
-               double *out_scores, int64_t *out_rows, int64_t *out_keys, int32_t *out_uncertified,
-               int32_t *out_query_flags, char *ws, hipStream_t st) {
-    vm_ctx *ctx = m->ctx;
-    const GPlan p = group_plan(m, Q, k);
-    uint32_t *F = (uint32_t *)ws;
-    int *first_o = (int *)(ws + p.off_first);
-    int *cand_g = (int *)(ws + p.off_cg);
-    uint32_t *cand_k = (uint32_t *)(ws + p.off_ck);
-    int *cand_n = (int *)(ws + p.off_cn);
-    int *flags = (int *)(ws + p.off_flags);
-    {
-        vm_prof_scope prof(ctx, VM_PROF_TOPK_SCAN, st);
-        group_table_kernel<<<p.tbl_blocks, 256, 0, st>>>(m->d_total, m->cap, m->ring, m->gord, Q, first_o, F, nullptr, 0);
-        VM_LAUNCH_CHECK(ctx);
-        const int rc = vm_tile_scan<DT, GroupScan>(m, p, queries, Q, {m->gord, F}, st);
-        if (rc != VM_OK) return rc;
-    }
-    {
-        vm_prof_scope prof(ctx, VM_PROF_TOPK_FINALIZE, st);
-        unsigned long long *cut = (unsigned long long *)(ws + p.off_cut);
-        int *ccount = (int *)(ws + p.off_cc);
-        unsigned long long *cbuf = (unsigned long long *)(ws + p.off_cbuf);
-        group_cut_kernel<<<Q, SEL_THREADS, 0, st>>>(m->d_total, m->cap, m->ring, m->gord, F, p.M + 1, cut, ccount);
-        VM_LAUNCH_CHECK(ctx);
-        group_compact_kernel<<<dim3(p.cmp_slices, Q), CMP_THREADS, 0, st>>>(m->d_total, m->cap, m->ring, m->gord, F, cut,
-                                                                            ccount, cbuf);
-        VM_LAUNCH_CHECK(ctx);
-        group_select_final_kernel<<<Q, SEL_THREADS, 0, st>>>(m->d_total, m->cap, m->ring, m->gord, F, p.M + 1, ccount,
-                                                             cbuf, cand_g, cand_k, cand_n);
-        VM_LAUNCH_CHECK(ctx);
-        group_finalize_kernel<DT, NoScope><<<Q, GF_THREADS, (size_t)m->D * 2, st>>>(
-            m->rows, m->norm64, m->gkey, m->gord, (const uint16_t *)queries, m->d_total, m->cap, m->ring, m->D, first_o,
-            cand_g, cand_k, cand_n, p.M, k, use_min, min_score, score_mode, out_scores, out_rows, out_keys,
-            out_uncertified, flags, out_query_flags, NoScope{});
-        VM_LAUNCH_CHECK(ctx);
-    }
-    return group_redo<DT>(m, p, queries, Q, k, use_min, min_score, score_mode, out_scores, out_rows, out_keys, ws, st);
+// both entry points: the fast form (topk_group_parts.h grouped_topk under GroupScan) or the exhaustive one
+int group_entry(vm_memory *m, const GroupCall &c, size_t workspace_bytes, bool exact, const char *who) {
+    if (!m) return VM_ERR_INVALID;
+    if (int rc = group_check(m, c, workspace_bytes, who)) return rc;
+    if (exact) return grouped_exact(m, c, NoScope{});
+    return vm_by_dtype(m, [&](auto dt) {
+        return grouped_topk<decltype(dt)::value, GroupScan, group_cut_kernel, group_select_final_kernel>(
+            m, c, {m->gord, nullptr}, NoScope{});
+    });
 }
 
 }  // namespace
@@ -178,34 +130,15 @@ extern "C" int vm_topk_cosine_grouped(vm_memory *m, const void *queries, int Q, 
                                       double min_score, int score_mode, double *out_scores, int64_t *out_rows,
                                       int64_t *out_keys, int32_t *out_uncertified, int32_t *out_query_flags,
                                       void *workspace, size_t workspace_bytes, void *stream) {
-    if (!m) return VM_ERR_INVALID;
-    int rc = group_check(m, queries, Q, k, score_mode, out_scores, out_rows, workspace, workspace_bytes,
-                         "vm_topk_cosine_grouped");
-    if (rc != VM_OK) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    return vm_by_dtype(m, [&](auto dt) {
-        return group_topk<decltype(dt)::value>(m, queries, Q, k, use_min_score, min_score, score_mode, out_scores,
-                                               out_rows, out_keys, out_uncertified, out_query_flags, (char *)workspace,
-                                               st);
-    });
+    const GroupCall c = {queries,  Q,        k,         use_min_score,   min_score,       score_mode, out_scores,
+                         out_rows, out_keys, out_uncertified, out_query_flags, (char *)workspace, (hipStream_t)stream};
+    return group_entry(m, c, workspace_bytes, false, "vm_topk_cosine_grouped");
 }
 
 extern "C" int vm_topk_cosine_grouped_exact(vm_memory *m, const void *queries, int Q, int k, int use_min_score,
                                             double min_score, int score_mode, double *out_scores, int64_t *out_rows,
                                             int64_t *out_keys, void *workspace, size_t workspace_bytes, void *stream) {
-    if (!m) return VM_ERR_INVALID;
-    int rc = group_check(m, queries, Q, k, score_mode, out_scores, out_rows, workspace, workspace_bytes,
-                         "vm_topk_cosine_grouped_exact");
-    if (rc != VM_OK) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    vm_ctx *ctx = m->ctx;
-    const GPlan p = group_plan(m, Q, k);
-    char *ws = (char *)workspace;
-    group_table_kernel<<<p.tbl_blocks, 256, 0, st>>>(m->d_total, m->cap, m->ring, m->gord, Q, (int *)(ws + p.off_first),
-                                                     nullptr, (int32_t *)(ws + p.off_flags), 1);
-    VM_LAUNCH_CHECK(ctx);
-    return vm_by_dtype(m, [&](auto dt) {
-        return group_redo<decltype(dt)::value>(m, p, queries, Q, k, use_min_score, min_score, score_mode, out_scores,
-                                               out_rows, out_keys, ws, st);
-    });
+    const GroupCall c = {queries,  Q,        k,       use_min_score, min_score,         score_mode, out_scores,
+                         out_rows, out_keys, nullptr, nullptr,       (char *)workspace, (hipStream_t)stream};
+    return group_entry(m, c, workspace_bytes, true, "vm_topk_cosine_grouped_exact");
 }

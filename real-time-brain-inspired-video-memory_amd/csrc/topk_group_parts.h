@@ -3,8 +3,10 @@
 //   moved unchanged   the tuning constants, the fp64 key images, the exact re-score, group_table_kernel,
 //                     group_compact_kernel, radix_select_all, the workspace plan
 //   moved and changed group_fold_runs (GroupScan's epilogue, its key now a functor), group_finalize_kernel and
-//                     group_redo_scan_kernel (a scope policy SC passed by value, used under `if constexpr (SC::scoped)`
-//                     only; the redo's LDS score array is `rs`, since `sc` is the policy)
+//                     group_redo_scan_kernel (a row predicate SC of vm_internal.h passed by value, used under
+//                     `if constexpr (SC::scoped)` only; the redo's LDS score array is `rs`, since `sc` is the predicate)
+//   the host driver   GroupCall, grouped_topk, grouped_redo, grouped_exact: a search brings its scan policy, its two
+//                     select kernels and its predicate
 // The anonymous namespace sits in a header: each of the two files compiles its own copy, so the library carries
 // group_table_kernel and group_compact_kernel twice.
 #pragma once
@@ -292,28 +294,12 @@ __device__ void radix_select_all(const uint32_t *__restrict__ Fq, int ng, int ta
     }
 }
 
-// ---- scope policy of the finalize and the redo --------------------------------------------------------------
-// What "row in slot p counts for query q" means: always (the grouped search), or the tag predicate of
-// vm_topk_cosine_scoped (the scoped grouped search).  Passed to the two kernels by value; every use of it sits under
-// `if constexpr (SC::scoped)`, so the grouped search's instantiations keep the instructions they had.
-struct NoScope {
-    static constexpr bool scoped = false;
-    struct Q {};
-    __device__ __forceinline__ Q at(int) const { return {}; }
-};
-struct TagScope {
-    static constexpr bool scoped = true;
-    const int64_t *tag, *lo, *hi;
-    struct Q {
-        const int64_t *tag;
-        int64_t lo, hi;
-        __device__ __forceinline__ bool in(int64_t p) const { return in_scope(tag[p], lo, hi); }
-    };
-    __device__ __forceinline__ Q at(int q) const { return {tag, lo[q], hi[q]}; }
-};
-constexpr int GF_OUT = 255;  // finalize: the candidate index of an out-of-scope row (candidates are < GCMAX)
-
 // ---- finalize ----------------------------------------------------------------------------------------------
+// SC, here and in the redo: the row predicate (vm_internal.h) - NoScope (the grouped search) or TagScope (the scoped
+// grouped search).  Passed to the two kernels by value; every use of it sits under `if constexpr (SC::scoped)`, so the
+// grouped search's instantiations keep the instructions they had.
+constexpr int GF_OUT = 255;  // the candidate index of an out-of-scope row (candidates are < GCMAX)
+
 // One block per query.  Ranks the take candidates by (fp32 key desc, group asc): the first nc = min(take, M) are
 // re-scored, the (M+1)-th (if any) bounds every rejected group.  Every row of a candidate group is scored exactly
 // (a row whose fp32 score is more than 2 eps below its group's fp32 max can not be the max, but the rows of a
@@ -635,6 +621,96 @@ GPlan group_plan(const vm_memory *m, int Q, int k) {
     p.off_po = ws.take((size_t)p.nblk * Q * k * 8);
     p.total = ws.off;
     return p;
+}
+
+// ---- host: the one driver of the two grouped searches -------------------------------------------------------
+// what every entry point of a grouped search is called with, past the operands of its predicate (vidmem.h: group
+// searches return row ids as they are, so row_stride = 1 and row_offset = 0)
+struct GroupCall {
+    const void *queries;
+    int Q, k, use_min;
+    double min_score;
+    int score_mode;
+    double *out_scores;
+    int64_t *out_rows, *out_keys;
+    int32_t *out_uncertified, *out_query_flags;  // null in the exhaustive-only entry points
+    char *ws;
+    hipStream_t stream;
+};
+
+// redo: flagged queries scored exhaustively, whole groups per block, then the one merge of every redo, with keys
+template <int DT, class SC>
+int grouped_redo(vm_memory *m, const GPlan &p, const GroupCall &c, const SC &sc) {
+    vm_ctx *ctx = m->ctx;
+    vm_prof_scope prof(ctx, VM_PROF_TOPK_EXACT, c.stream);
+    const int *first_o = (const int *)(c.ws + p.off_first);
+    const int32_t *flags = (const int32_t *)(c.ws + p.off_flags);
+    double *part_s = (double *)(c.ws + p.off_ps);
+    int64_t *part_o = (int64_t *)(c.ws + p.off_po);
+    group_redo_scan_kernel<DT, SC><<<p.nblk, GR_THREADS, (size_t)m->D * 2, c.stream>>>(
+        (const uint16_t *)c.queries, m->rows, m->norm64, m->gord, m->d_total, m->cap, m->ring, m->D, c.Q, c.k, first_o,
+        flags, part_s, part_o, sc);
+    VM_LAUNCH_CHECK(ctx);
+    return vm_topk_redo_merge(m, part_s, part_o, p.nblk, c.Q, c.k, flags, c.use_min, c.min_score, c.score_mode, 1, 0,
+                              c.out_scores, c.out_rows, m->gkey, c.out_keys, c.stream);
+}
+
+// table -> scan -> cut -> compact -> select -> finalize -> redo.  Scan: the tile-scan policy that raises the group maxima
+// (its Args have F, the plan's, filled in here); Cut / SelectFinal: the search's two select kernels, which differ in what
+// an empty group is (topk_group.hip, topk_group_scope.hip) and stay two because merged they compile to other
+// instructions; sc: the row predicate of the finalize and the redo.
+template <int DT, class Scan, auto Cut, auto SelectFinal, class SC>
+int grouped_topk(vm_memory *m, const GroupCall &c, typename Scan::Args a, const SC &sc) {
+    vm_ctx *ctx = m->ctx;
+    hipStream_t st = c.stream;
+    char *ws = c.ws;
+    const int Q = c.Q;
+    const GPlan p = group_plan(m, Q, c.k);
+    uint32_t *F = (uint32_t *)ws;
+    int *first_o = (int *)(ws + p.off_first);
+    int *cand_g = (int *)(ws + p.off_cg);
+    uint32_t *cand_k = (uint32_t *)(ws + p.off_ck);
+    int *cand_n = (int *)(ws + p.off_cn);
+    int *flags = (int *)(ws + p.off_flags);
+    {
+        vm_prof_scope prof(ctx, VM_PROF_TOPK_SCAN, st);
+        group_table_kernel<<<p.tbl_blocks, 256, 0, st>>>(m->d_total, m->cap, m->ring, m->gord, Q, first_o, F, nullptr, 0);
+        VM_LAUNCH_CHECK(ctx);
+        a.F = F;
+        const int rc = vm_tile_scan<DT, Scan>(m, p, c.queries, Q, a, st);
+        if (rc != VM_OK) return rc;
+    }
+    {
+        vm_prof_scope prof(ctx, VM_PROF_TOPK_FINALIZE, st);
+        unsigned long long *cut = (unsigned long long *)(ws + p.off_cut);
+        int *ccount = (int *)(ws + p.off_cc);
+        unsigned long long *cbuf = (unsigned long long *)(ws + p.off_cbuf);
+        Cut<<<Q, SEL_THREADS, 0, st>>>(m->d_total, m->cap, m->ring, m->gord, F, p.M + 1, cut, ccount);
+        VM_LAUNCH_CHECK(ctx);
+        group_compact_kernel<<<dim3(p.cmp_slices, Q), CMP_THREADS, 0, st>>>(m->d_total, m->cap, m->ring, m->gord, F, cut,
+                                                                            ccount, cbuf);
+        VM_LAUNCH_CHECK(ctx);
+        SelectFinal<<<Q, SEL_THREADS, 0, st>>>(m->d_total, m->cap, m->ring, m->gord, F, p.M + 1, ccount, cbuf, cand_g,
+                                               cand_k, cand_n);
+        VM_LAUNCH_CHECK(ctx);
+        group_finalize_kernel<DT, SC><<<Q, GF_THREADS, (size_t)m->D * 2, st>>>(
+            m->rows, m->norm64, m->gkey, m->gord, (const uint16_t *)c.queries, m->d_total, m->cap, m->ring, m->D, first_o,
+            cand_g, cand_k, cand_n, p.M, c.k, c.use_min, c.min_score, c.score_mode, c.out_scores, c.out_rows, c.out_keys,
+            c.out_uncertified, flags, c.out_query_flags, sc);
+        VM_LAUNCH_CHECK(ctx);
+    }
+    return grouped_redo<DT>(m, p, c, sc);
+}
+
+// the exhaustive-only entry point: the table with every query flagged, then the redo
+template <class SC>
+int grouped_exact(vm_memory *m, const GroupCall &c, const SC &sc) {
+    const GPlan p = group_plan(m, c.Q, c.k);
+    group_table_kernel<<<p.tbl_blocks, 256, 0, c.stream>>>(m->d_total, m->cap, m->ring, m->gord, c.Q,
+                                                         (int *)(c.ws + p.off_first), nullptr,
+                                                         (int32_t *)(c.ws + p.off_flags), 1);
+    VM_LAUNCH_CHECK(m->ctx);
+    return vm_by_dtype(m, [&](auto dt) { return grouped_redo<decltype(dt)::value>(m, p, c, sc); });
 }
 
 }  // namespace

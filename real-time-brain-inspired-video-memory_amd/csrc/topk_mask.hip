@@ -13,7 +13,7 @@
 //   finalize : topk_scope_select.h's scope_finalize_kernel, unchanged: nothing in it is specific to scopes.  Certified
 //              when the mask selects at most M rows, or when the exact k-th score clears the (M+1)-th SELECTED fp32
 //              score / ||q|| by cert_eps(D), strictly.  Unselected rows have key 0 and never reach the certificate
-//   redo     : vm_topk_redo_scan with the mask predicate (topk_exact.hip), then vm_topk_redo_merge
+//   redo     : vm_topk_redo_scan under the MaskScope predicate (vm_internal.h, topk_exact.hip), then vm_topk_redo_merge
 // A bit whose slot holds no live row is ignored everywhere: the scan and the redo visit live slots only.
 // Every launch reads the row count from the device and sizes its grid from the capacity: capturable.
 #include "topk_scope_select.h"
@@ -82,11 +82,6 @@ struct MaskScan {
     }
 };
 
-__global__ void mask_fill_flags_kernel(int32_t *__restrict__ flags, int Q) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < Q) flags[i] = 1;
-}
-
 // ---- builders ----------------------------------------------------------------------------------------------
 // Thread = one entry of row_ids: the bit of a live row's slot is ORed into the mask (the result does not depend on the
 // order of the atomics).  -1, an id that is not row * stride + offset, and a row that is not live are skipped.
@@ -129,66 +124,28 @@ __global__ void __launch_bounds__(256)
 // ---- host --------------------------------------------------------------------------------------------------
 int64_t mask_words(const vm_memory *m) { return (m->cap + 63) / 64 * 2; }
 
-int mask_check(vm_memory *m, const void *queries, int Q, int k, const uint32_t *masks, int n_masks,
-               const int32_t *mask_index, int score_mode, const double *out_scores, const int64_t *out_rows,
-               const void *workspace, size_t workspace_bytes, const char *who) {
-    const bool ok = queries && masks && out_scores && out_rows && Q > 0 && n_masks > 0 &&
-                    (mask_index || n_masks == 1 || n_masks == Q) && !((uintptr_t)masks & 3);
+int mask_check(vm_memory *m, const RowCall &c, const uint32_t *masks, int n_masks, const int32_t *mask_index,
+               size_t workspace_bytes, const char *who) {
+    const bool ok = c.queries && masks && c.out_scores && c.out_rows && c.Q > 0 && n_masks > 0 &&
+                    (mask_index || n_masks == 1 || n_masks == c.Q) && !((uintptr_t)masks & 3);
     // the scan addresses a mask halfword by a 32-bit byte offset from `masks` (MaskScan::tile_bits)
     if (ok && (int64_t)n_masks * mask_words(m) > ((int64_t)1 << 30))
         return vm_fail(m->ctx, VM_ERR_UNSUPPORTED, "%s: more than 2^30 words of masks", who);
-    return vm_topk_check(m, nullptr, ok, queries, k, SKMAX, VM_ERR_INVALID, score_mode, workspace, workspace_bytes,
-                         scope_plan(m, Q, k).total, who);
+    return vm_topk_check(m, nullptr, ok, c.queries, c.k, SKMAX, VM_ERR_INVALID, c.score_mode, c.ws, workspace_bytes,
+                         scope_plan(m, c.Q, c.k).total, who);
 }
 
-int mask_redo(vm_memory *m, const SPlan &p, const void *queries, int Q, int k, const MaskSel &ms, int use_min,
-              double min_score, int score_mode, int64_t row_stride, int64_t row_offset, double *out_scores,
-              int64_t *out_rows, char *ws, hipStream_t st) {
-    vm_prof_scope prof(m->ctx, VM_PROF_TOPK_EXACT, st);
-    const int32_t *flags = (const int32_t *)(ws + p.off_flags);
-    double *part_s = (double *)(ws + p.off_ps);
-    int64_t *part_o = (int64_t *)(ws + p.off_po);
-    if (int rc = vm_topk_redo_scan(m, queries, Q, k, nullptr, nullptr, flags, p.nblk, part_s, part_o, st, &ms)) return rc;
-    return vm_topk_redo_merge(m, part_s, part_o, p.nblk, Q, k, flags, use_min, min_score, score_mode, row_stride,
-                              row_offset, out_scores, out_rows, nullptr, nullptr, st);
-}
-
-template <int DT>
-int mask_topk(vm_memory *m, const void *queries, int Q, int k, const MaskSel &ms, int use_min, double min_score,
-              int score_mode, int64_t row_stride, int64_t row_offset, double *out_scores, int64_t *out_rows,
-              int32_t *out_uncertified, int32_t *out_query_flags, char *ws, hipStream_t st) {
-    vm_ctx *ctx = m->ctx;
-    const SPlan p = scope_plan(m, Q, k);  // the scoped search's workspace: the same stages over the same key image
-    uint32_t *F = (uint32_t *)ws;
-    int *cand_o = (int *)(ws + p.off_co);
-    uint32_t *cand_k = (uint32_t *)(ws + p.off_ck);
-    int *cand_n = (int *)(ws + p.off_cn);
-    int *flags = (int *)(ws + p.off_flags);
-    {
-        vm_prof_scope prof(ctx, VM_PROF_TOPK_SCAN, st);
-        const int rc = vm_tile_scan<DT, MaskScan>(m, p, queries, Q, {ms, p.fstride, F}, st);
-        if (rc != VM_OK) return rc;
-    }
-    {
-        vm_prof_scope prof(ctx, VM_PROF_TOPK_FINALIZE, st);
-        uint32_t *cut = (uint32_t *)(ws + p.off_cut);
-        int *ccount = (int *)(ws + p.off_cc);
-        unsigned long long *cbuf = (unsigned long long *)(ws + p.off_cbuf);
-        scope_cut_kernel<<<Q, SEL_THREADS, 0, st>>>(m->d_total, m->cap, m->ring, F, p.fstride, p.M + 1, cut, ccount);
-        VM_LAUNCH_CHECK(ctx);
-        scope_compact_kernel<<<dim3(p.cmp_slices, Q), CMP_THREADS, 0, st>>>(m->d_total, m->cap, m->ring, F, p.fstride,
-                                                                            cut, ccount, cbuf);
-        VM_LAUNCH_CHECK(ctx);
-        scope_select_kernel<<<Q, SEL_THREADS, 0, st>>>(p.M + 1, ccount, cbuf, cand_o, cand_k, cand_n);
-        VM_LAUNCH_CHECK(ctx);
-        scope_finalize_kernel<DT><<<Q, SF_THREADS, (size_t)m->D * 2, st>>>(
-            m->rows, m->norm64, (const uint16_t *)queries, m->d_total, m->cap, m->ring, m->D, cand_o, cand_k, cand_n,
-            p.M, k, use_min, min_score, score_mode, row_stride, row_offset, out_scores, out_rows, out_uncertified, flags,
-            out_query_flags);
-        VM_LAUNCH_CHECK(ctx);
-    }
-    return mask_redo(m, p, queries, Q, k, ms, use_min, min_score, score_mode, row_stride, row_offset, out_scores,
-                     out_rows, ws, st);
+// both entry points: the fast form (topk_scope_select.h key_image_topk under MaskScan; the scoped search's workspace, the
+// same stages over the same key image) or the exhaustive one
+int mask_entry(vm_memory *m, const RowCall &c, const uint32_t *masks, int n_masks, const int32_t *mask_index,
+               size_t workspace_bytes, bool exact, const char *who) {
+    if (!m) return VM_ERR_INVALID;
+    if (int rc = mask_check(m, c, masks, n_masks, mask_index, workspace_bytes, who)) return rc;
+    const MaskScope ms = {{masks, mask_index, n_masks, mask_words(m)}};
+    if (exact) return key_image_exact(m, c, ms);
+    return vm_by_dtype(m, [&](auto dt) {
+        return key_image_topk<decltype(dt)::value, MaskScan>(m, c, {ms.ms, 0, nullptr}, ms);
+    });
 }
 
 }  // namespace
@@ -205,35 +162,20 @@ extern "C" int vm_topk_cosine_masked(vm_memory *m, const void *queries, int Q, i
                                      int score_mode, int64_t row_stride, int64_t row_offset, double *out_scores,
                                      int64_t *out_rows, int32_t *out_uncertified, int32_t *out_query_flags,
                                      void *workspace, size_t workspace_bytes, void *stream) {
-    if (!m) return VM_ERR_INVALID;
-    int rc = mask_check(m, queries, Q, k, masks, n_masks, mask_index, score_mode, out_scores, out_rows, workspace,
-                        workspace_bytes, "vm_topk_cosine_masked");
-    if (rc != VM_OK) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    const MaskSel ms = {masks, mask_index, n_masks, mask_words(m)};
-    return vm_by_dtype(m, [&](auto dt) {
-        return mask_topk<decltype(dt)::value>(m, queries, Q, k, ms, use_min_score, min_score, score_mode, row_stride,
-                                              row_offset, out_scores, out_rows, out_uncertified, out_query_flags,
-                                              (char *)workspace, st);
-    });
+    const RowCall c = {queries,    Q,          k,          use_min_score, min_score,       score_mode,
+                       row_stride, row_offset, out_scores, out_rows,      out_uncertified, out_query_flags,
+                       (char *)workspace, (hipStream_t)stream};
+    return mask_entry(m, c, masks, n_masks, mask_index, workspace_bytes, false, "vm_topk_cosine_masked");
 }
 
 extern "C" int vm_topk_cosine_masked_exact(vm_memory *m, const void *queries, int Q, int k, const uint32_t *masks,
                                            int n_masks, const int32_t *mask_index, int use_min_score, double min_score,
                                            int score_mode, int64_t row_stride, int64_t row_offset, double *out_scores,
                                            int64_t *out_rows, void *workspace, size_t workspace_bytes, void *stream) {
-    if (!m) return VM_ERR_INVALID;
-    int rc = mask_check(m, queries, Q, k, masks, n_masks, mask_index, score_mode, out_scores, out_rows, workspace,
-                        workspace_bytes, "vm_topk_cosine_masked_exact");
-    if (rc != VM_OK) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    const SPlan p = scope_plan(m, Q, k);
-    char *ws = (char *)workspace;
-    mask_fill_flags_kernel<<<(Q + 255) / 256, 256, 0, st>>>((int32_t *)(ws + p.off_flags), Q);
-    VM_LAUNCH_CHECK(m->ctx);
-    const MaskSel ms = {masks, mask_index, n_masks, mask_words(m)};
-    return mask_redo(m, p, queries, Q, k, ms, use_min_score, min_score, score_mode, row_stride, row_offset, out_scores,
-                     out_rows, ws, st);
+    const RowCall c = {queries,    Q,          k,          use_min_score, min_score, score_mode,
+                       row_stride, row_offset, out_scores, out_rows,      nullptr,   nullptr,
+                       (char *)workspace, (hipStream_t)stream};
+    return mask_entry(m, c, masks, n_masks, mask_index, workspace_bytes, true, "vm_topk_cosine_masked_exact");
 }
 
 extern "C" int vm_mask_from_rows(vm_memory *m, const int64_t *row_ids, int64_t n, int64_t row_stride,

@@ -27,8 +27,6 @@
 #include "topk_scope_select.h"  // the select stage (cut, compaction, selection) and the finalize: shared
 #include "topk_tile_scan.h"
 
-#include <climits>
-
 namespace {
 
 // ---- scan --------------------------------------------------------------------------------------------------
@@ -41,14 +39,11 @@ struct ScopeScan {
         uint32_t *F;
     };
     template <int QT>
-    struct QState {  // 16-byte aligned: the tag pre-test reads a lane's four scopes with two 16-byte LDS loads per array
-        alignas(16) int64_t lo[QT * 16], hi[QT * 16];
-    };
+    using QState = TagQState<QT>;
     struct View {};
     template <class QS>
     static __device__ __forceinline__ void load_query(QS &qs, const Args &a, int i, int q, bool live) {
-        qs.lo[i] = live ? a.scope_lo[q] : LLONG_MAX;  // queries past Q have the empty scope
-        qs.hi[i] = live ? a.scope_hi[q] : LLONG_MIN;
+        load_tag_scope(qs, a.scope_lo, a.scope_hi, i, q, live);
     }
     static __device__ __forceinline__ View view(const Args &, const RingView &) { return {}; }
     template <int QT>
@@ -81,71 +76,24 @@ struct ScopeScan {
     }
 };
 
-// ---- redo --------------------------------------------------------------------------------------------------
-__global__ void scope_fill_flags_kernel(int32_t *__restrict__ flags, int Q) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < Q) flags[i] = 1;
-}
-
 // ---- host --------------------------------------------------------------------------------------------------
-int scope_check(vm_memory *m, const void *queries, int Q, int k, const int64_t *scope_lo, const int64_t *scope_hi,
-                int score_mode, const double *out_scores, const int64_t *out_rows, const void *workspace,
-                size_t workspace_bytes, const char *who) {
+int scope_check(vm_memory *m, const RowCall &c, const int64_t *scope_lo, const int64_t *scope_hi, size_t workspace_bytes,
+                const char *who) {
     return vm_topk_check(m, m->tag ? nullptr : "tagged (vm_memory_create_tagged)",
-                         queries && scope_lo && scope_hi && out_scores && out_rows && Q > 0, queries, k, SKMAX,
-                         VM_ERR_INVALID, score_mode, workspace, workspace_bytes, scope_plan(m, Q, k).total, who);
+                         c.queries && scope_lo && scope_hi && c.out_scores && c.out_rows && c.Q > 0, c.queries, c.k,
+                         SKMAX, VM_ERR_INVALID, c.score_mode, c.ws, workspace_bytes, scope_plan(m, c.Q, c.k).total, who);
 }
 
-int scope_redo(vm_memory *m, const SPlan &p, const void *queries, int Q, int k, const int64_t *scope_lo,
-               const int64_t *scope_hi, int use_min, double min_score, int score_mode, int64_t row_stride,
-               int64_t row_offset, double *out_scores, int64_t *out_rows, char *ws, hipStream_t st) {
-    vm_ctx *ctx = m->ctx;
-    vm_prof_scope prof(ctx, VM_PROF_TOPK_EXACT, st);
-    const int32_t *flags = (const int32_t *)(ws + p.off_flags);
-    double *part_s = (double *)(ws + p.off_ps);
-    int64_t *part_o = (int64_t *)(ws + p.off_po);
-    if (int rc = vm_topk_redo_scan(m, queries, Q, k, scope_lo, scope_hi, flags, p.nblk, part_s, part_o, st)) return rc;
-    return vm_topk_redo_merge(m, part_s, part_o, p.nblk, Q, k, flags, use_min, min_score, score_mode, row_stride,
-                              row_offset, out_scores, out_rows, nullptr, nullptr, st);
-}
-
-template <int DT>
-int scope_topk(vm_memory *m, const void *queries, int Q, int k, const int64_t *scope_lo, const int64_t *scope_hi,
-               int use_min, double min_score, int score_mode, int64_t row_stride, int64_t row_offset,
-               double *out_scores, int64_t *out_rows, int32_t *out_uncertified, int32_t *out_query_flags, char *ws,
-               hipStream_t st) {
-    vm_ctx *ctx = m->ctx;
-    const SPlan p = scope_plan(m, Q, k);
-    uint32_t *F = (uint32_t *)ws;
-    int *cand_o = (int *)(ws + p.off_co);
-    uint32_t *cand_k = (uint32_t *)(ws + p.off_ck);
-    int *cand_n = (int *)(ws + p.off_cn);
-    int *flags = (int *)(ws + p.off_flags);
-    {
-        vm_prof_scope prof(ctx, VM_PROF_TOPK_SCAN, st);
-        const int rc = vm_tile_scan<DT, ScopeScan>(m, p, queries, Q, {m->tag, scope_lo, scope_hi, p.fstride, F}, st);
-        if (rc != VM_OK) return rc;
-    }
-    {
-        vm_prof_scope prof(ctx, VM_PROF_TOPK_FINALIZE, st);
-        uint32_t *cut = (uint32_t *)(ws + p.off_cut);
-        int *ccount = (int *)(ws + p.off_cc);
-        unsigned long long *cbuf = (unsigned long long *)(ws + p.off_cbuf);
-        scope_cut_kernel<<<Q, SEL_THREADS, 0, st>>>(m->d_total, m->cap, m->ring, F, p.fstride, p.M + 1, cut, ccount);
-        VM_LAUNCH_CHECK(ctx);
-        scope_compact_kernel<<<dim3(p.cmp_slices, Q), CMP_THREADS, 0, st>>>(m->d_total, m->cap, m->ring, F, p.fstride,
-                                                                            cut, ccount, cbuf);
-        VM_LAUNCH_CHECK(ctx);
-        scope_select_kernel<<<Q, SEL_THREADS, 0, st>>>(p.M + 1, ccount, cbuf, cand_o, cand_k, cand_n);
-        VM_LAUNCH_CHECK(ctx);
-        scope_finalize_kernel<DT><<<Q, SF_THREADS, (size_t)m->D * 2, st>>>(
-            m->rows, m->norm64, (const uint16_t *)queries, m->d_total, m->cap, m->ring, m->D, cand_o, cand_k, cand_n,
-            p.M, k, use_min, min_score, score_mode, row_stride, row_offset, out_scores, out_rows, out_uncertified, flags,
-            out_query_flags);
-        VM_LAUNCH_CHECK(ctx);
-    }
-    return scope_redo(m, p, queries, Q, k, scope_lo, scope_hi, use_min, min_score, score_mode, row_stride,
-                          row_offset, out_scores, out_rows, ws, st);
+// both entry points: the fast form (topk_scope_select.h key_image_topk under ScopeScan) or the exhaustive one
+int scope_entry(vm_memory *m, const RowCall &c, const int64_t *scope_lo, const int64_t *scope_hi, size_t workspace_bytes,
+                bool exact, const char *who) {
+    if (!m) return VM_ERR_INVALID;
+    if (int rc = scope_check(m, c, scope_lo, scope_hi, workspace_bytes, who)) return rc;
+    const TagScope sc = {m->tag, scope_lo, scope_hi};
+    if (exact) return key_image_exact(m, c, sc);
+    return vm_by_dtype(m, [&](auto dt) {
+        return key_image_topk<decltype(dt)::value, ScopeScan>(m, c, {m->tag, scope_lo, scope_hi, 0, nullptr}, sc);
+    });
 }
 
 }  // namespace
@@ -160,32 +108,18 @@ extern "C" int vm_topk_cosine_scoped(vm_memory *m, const void *queries, int Q, i
                                      int64_t row_stride, int64_t row_offset, double *out_scores, int64_t *out_rows,
                                      int32_t *out_uncertified, int32_t *out_query_flags, void *workspace,
                                      size_t workspace_bytes, void *stream) {
-    if (!m) return VM_ERR_INVALID;
-    int rc = scope_check(m, queries, Q, k, scope_lo, scope_hi, score_mode, out_scores, out_rows, workspace,
-                         workspace_bytes, "vm_topk_cosine_scoped");
-    if (rc != VM_OK) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    return vm_by_dtype(m, [&](auto dt) {
-        return scope_topk<decltype(dt)::value>(m, queries, Q, k, scope_lo, scope_hi, use_min_score, min_score,
-                                               score_mode, row_stride, row_offset, out_scores, out_rows,
-                                               out_uncertified, out_query_flags, (char *)workspace, st);
-    });
+    const RowCall c = {queries,    Q,          k,          use_min_score, min_score,       score_mode,
+                       row_stride, row_offset, out_scores, out_rows,      out_uncertified, out_query_flags,
+                       (char *)workspace, (hipStream_t)stream};
+    return scope_entry(m, c, scope_lo, scope_hi, workspace_bytes, false, "vm_topk_cosine_scoped");
 }
 
 extern "C" int vm_topk_cosine_scoped_exact(vm_memory *m, const void *queries, int Q, int k, const int64_t *scope_lo,
                                            const int64_t *scope_hi, int use_min_score, double min_score, int score_mode,
                                            int64_t row_stride, int64_t row_offset, double *out_scores,
                                            int64_t *out_rows, void *workspace, size_t workspace_bytes, void *stream) {
-    if (!m) return VM_ERR_INVALID;
-    int rc = scope_check(m, queries, Q, k, scope_lo, scope_hi, score_mode, out_scores, out_rows, workspace,
-                         workspace_bytes, "vm_topk_cosine_scoped_exact");
-    if (rc != VM_OK) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    vm_ctx *ctx = m->ctx;
-    const SPlan p = scope_plan(m, Q, k);
-    char *ws = (char *)workspace;
-    scope_fill_flags_kernel<<<(Q + 255) / 256, 256, 0, st>>>((int32_t *)(ws + p.off_flags), Q);
-    VM_LAUNCH_CHECK(ctx);
-    return scope_redo(m, p, queries, Q, k, scope_lo, scope_hi, use_min_score, min_score, score_mode, row_stride,
-                      row_offset, out_scores, out_rows, ws, st);
+    const RowCall c = {queries,    Q,          k,          use_min_score, min_score, score_mode,
+                       row_stride, row_offset, out_scores, out_rows,      nullptr,   nullptr,
+                       (char *)workspace, (hipStream_t)stream};
+    return scope_entry(m, c, scope_lo, scope_hi, workspace_bytes, true, "vm_topk_cosine_scoped_exact");
 }

@@ -3,8 +3,9 @@
 // scoped search (topk_scope.hip: key 0 = out of scope) and shared, unchanged, with the clip search (topk_clip.hip: key 0 =
 // no valid, in-scope window that could be a peak starts in the slot) and the masked search (topk_mask.hip: key 0 = the
 // query's mask does not select the slot).  The scoped and the masked search also share what follows the selection: the
-// exact finalize with the gap certificate, and the workspace plan.  Each translation unit gets its own copy of the kernels
-// (anonymous namespace).
+// exact finalize with the gap certificate, the workspace plan and the host driver (RowCall, key_image_topk,
+// key_image_exact): a search brings its scan policy and its row predicate (vm_internal.h), nothing else.  Each translation
+// unit gets its own copy of the kernels (anonymous namespace).
 #pragma once
 #include "topk_select.h"
 #include "topk_tile_scan.h"  // TS_THREADS: the plan sizes the scan's grid
@@ -238,6 +239,90 @@ SPlan scope_plan(const vm_memory *m, int Q, int k) {
     p.off_po = ws.take((size_t)p.nblk * Q * k * 8);
     p.total = ws.off;
     return p;
+}
+
+// ---- host: the one driver of those searches ----------------------------------------------------------------
+// flags[0, n) = 1: every query (clip) is flagged, which is what makes a redo the exhaustive-only entry point
+__global__ void fill_flags_kernel(int32_t *__restrict__ flags, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) flags[i] = 1;
+}
+
+// what every entry point of a row search is called with, past the operands of its predicate
+struct RowCall {
+    const void *queries;
+    int Q, k, use_min;
+    double min_score;
+    int score_mode;
+    int64_t row_stride, row_offset;
+    double *out_scores;
+    int64_t *out_rows;
+    int32_t *out_uncertified, *out_query_flags;  // null in the exhaustive-only entry points
+    char *ws;
+    hipStream_t stream;
+};
+
+// redo: flagged queries scored exhaustively over the rows pred admits, then the one merge of every redo
+template <class P>
+int key_image_redo(vm_memory *m, const SPlan &p, const RowCall &c, const P &pred) {
+    vm_prof_scope prof(m->ctx, VM_PROF_TOPK_EXACT, c.stream);
+    const int32_t *flags = (const int32_t *)(c.ws + p.off_flags);
+    double *part_s = (double *)(c.ws + p.off_ps);
+    int64_t *part_o = (int64_t *)(c.ws + p.off_po);
+    if (int rc = vm_topk_redo_scan(m, c.queries, c.Q, c.k, pred, flags, p.nblk, part_s, part_o, c.stream)) return rc;
+    return vm_topk_redo_merge(m, part_s, part_o, p.nblk, c.Q, c.k, flags, c.use_min, c.min_score, c.score_mode,
+                              c.row_stride, c.row_offset, c.out_scores, c.out_rows, nullptr, nullptr, c.stream);
+}
+
+// scan -> cut -> compact -> select -> finalize -> redo.  Scan: the tile-scan policy that writes the key image (its Args
+// have fstride and F, which are the plan's and filled in here); pred: the same row set for the redo.
+template <int DT, class Scan, class P>
+int key_image_topk(vm_memory *m, const RowCall &c, typename Scan::Args a, const P &pred) {
+    vm_ctx *ctx = m->ctx;
+    hipStream_t st = c.stream;
+    char *ws = c.ws;
+    const int Q = c.Q;
+    const SPlan p = scope_plan(m, Q, c.k);
+    uint32_t *F = (uint32_t *)ws;
+    int *cand_o = (int *)(ws + p.off_co);
+    uint32_t *cand_k = (uint32_t *)(ws + p.off_ck);
+    int *cand_n = (int *)(ws + p.off_cn);
+    int *flags = (int *)(ws + p.off_flags);
+    {
+        vm_prof_scope prof(ctx, VM_PROF_TOPK_SCAN, st);
+        a.fstride = p.fstride;
+        a.F = F;
+        const int rc = vm_tile_scan<DT, Scan>(m, p, c.queries, Q, a, st);
+        if (rc != VM_OK) return rc;
+    }
+    {
+        vm_prof_scope prof(ctx, VM_PROF_TOPK_FINALIZE, st);
+        uint32_t *cut = (uint32_t *)(ws + p.off_cut);
+        int *ccount = (int *)(ws + p.off_cc);
+        unsigned long long *cbuf = (unsigned long long *)(ws + p.off_cbuf);
+        scope_cut_kernel<<<Q, SEL_THREADS, 0, st>>>(m->d_total, m->cap, m->ring, F, p.fstride, p.M + 1, cut, ccount);
+        VM_LAUNCH_CHECK(ctx);
+        scope_compact_kernel<<<dim3(p.cmp_slices, Q), CMP_THREADS, 0, st>>>(m->d_total, m->cap, m->ring, F, p.fstride,
+                                                                            cut, ccount, cbuf);
+        VM_LAUNCH_CHECK(ctx);
+        scope_select_kernel<<<Q, SEL_THREADS, 0, st>>>(p.M + 1, ccount, cbuf, cand_o, cand_k, cand_n);
+        VM_LAUNCH_CHECK(ctx);
+        scope_finalize_kernel<DT><<<Q, SF_THREADS, (size_t)m->D * 2, st>>>(
+            m->rows, m->norm64, (const uint16_t *)c.queries, m->d_total, m->cap, m->ring, m->D, cand_o, cand_k, cand_n,
+            p.M, c.k, c.use_min, c.min_score, c.score_mode, c.row_stride, c.row_offset, c.out_scores, c.out_rows,
+            c.out_uncertified, flags, c.out_query_flags);
+        VM_LAUNCH_CHECK(ctx);
+    }
+    return key_image_redo(m, p, c, pred);
+}
+
+// the exhaustive-only entry point: every query flagged, then the redo
+template <class P>
+int key_image_exact(vm_memory *m, const RowCall &c, const P &pred) {
+    const SPlan p = scope_plan(m, c.Q, c.k);
+    fill_flags_kernel<<<(c.Q + 255) / 256, 256, 0, c.stream>>>((int32_t *)(c.ws + p.off_flags), c.Q);
+    VM_LAUNCH_CHECK(m->ctx);
+    return key_image_redo(m, p, c, pred);
 }
 
 }  // namespace

@@ -15,6 +15,7 @@
 #pragma once
 #include "topk_select.h"
 
+#include <climits>
 #include <type_traits>
 
 constexpr int TS_THREADS = 256;
@@ -42,6 +43,19 @@ __device__ __forceinline__ bool tile_in_scope(const int64_t *__restrict__ tag, c
             for (int c = 0; c < 4; ++c) hit |= in_scope(tg, slo[16 * t + 4 * l.h + c], shi[16 * t + 4 * l.h + c]);
     }
     return __ballot(hit) != 0ull;
+}
+
+// The per-query state of a policy with tag scopes: the scopes of the block's QT * 16 queries.  16-byte aligned: the tag
+// pre-test reads a lane's four scopes with two 16-byte LDS loads per array.  A policy with more per-query state derives.
+template <int QT>
+struct TagQState {
+    alignas(16) int64_t lo[QT * 16], hi[QT * 16];
+};
+// entry i = the scope of query q; a query past Q (!live) has the empty scope
+template <class QS>
+__device__ __forceinline__ void load_tag_scope(QS &qs, const int64_t *lo, const int64_t *hi, int i, int q, bool live) {
+    qs.lo[i] = live ? lo[q] : LLONG_MAX;
+    qs.hi[i] = live ? hi[q] : LLONG_MIN;
 }
 
 // grid (row blocks, query groups of QT*16); dynamic LDS: the query tile, QT * 16 * D * 2 bytes.  16-row tiles in

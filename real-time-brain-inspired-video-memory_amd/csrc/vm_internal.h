@@ -81,6 +81,46 @@ __host__ __device__ inline bool mask_selects(const uint32_t *words, int64_t off,
     return off >= 0 && ((words[off + (p >> 5)] >> (p & 31)) & 1u);
 }
 
+// ---- row predicates -----------------------------------------------------------------------------------------
+// What "the row in physical slot p counts for query q" means, as a type handed to a kernel by value: always (NoScope), the
+// tag range of vm_topk_cosine_scoped (TagScope), the bit mask of vm_topk_cosine_masked (MaskScope).  A model has
+// `static constexpr bool scoped`, `Q at(int q) const` (what is per query, read once) and, when scoped, `bool
+// Q::in(int64_t p) const`; every use sits under `if constexpr (P::scoped)`, so a NoScope instantiation carries nothing
+// of it.  A consumer tests p for liveness itself.  The redo scans take one (topk_exact.hip, topk_group_parts.h), the
+// grouped finalize another, and the host drivers pass them through (topk_scope_select.h, topk_group_parts.h).
+struct NoScope {
+    static constexpr bool scoped = false;
+    struct Q {};
+    __device__ __forceinline__ Q at(int) const { return {}; }
+};
+struct TagScope {
+    static constexpr bool scoped = true;
+    const int64_t *tag, *lo, *hi;
+    struct Q {
+        const int64_t *tag;
+        int64_t lo, hi;
+        __device__ __forceinline__ bool in(int64_t p) const { return in_scope(tag[p], lo, hi); }
+    };
+    // The scopes are read through the constant address space (no kernel writes them).  The pointers arrive inside a
+    // by-value struct; the compiler does not prove the memory behind a pointer it loaded itself unwritten, as it does for a
+    // __restrict__ kernel argument, and the uniform loads lo[q] / hi[q] would be vector loads into six VGPRs, not scalar
+    // ones.
+    __device__ __forceinline__ Q at(int q) const {
+        typedef const __attribute__((address_space(4))) int64_t *scalar_ptr;
+        return {tag, ((scalar_ptr)lo)[q], ((scalar_ptr)hi)[q]};
+    }
+};
+struct MaskScope {
+    static constexpr bool scoped = true;
+    MaskSel ms;
+    struct Q {
+        const uint32_t *words;
+        int64_t off;
+        __device__ __forceinline__ bool in(int64_t p) const { return mask_selects(words, off, p); }
+    };
+    __device__ __forceinline__ Q at(int q) const { return {ms.words, mask_offset(ms, q)}; }
+};
+
 // grouped memories: the live rows + the ordinal of the oldest live group + the number of live groups, from the device
 // counters.  Groups are runs of equal ordinals (gord above), so live group g = ordinal - ord0, 0 <= g < ng.
 struct GroupView {
@@ -132,13 +172,13 @@ int vm_topk_redo_blocks(const vm_memory *m, int chunk);
 // rows scored per selection pass by the redo scan of the row search and of the scoped search
 constexpr int VM_REDO_CHUNK = 2048, VM_REDO_CHUNK_SCOPED = 1024;
 // The redo scan of rows: for every flagged query, block b of nblk scores its slice of age orders exactly and leaves the
-// slice's stable top-k in part_s / part_o [nblk][Q][k].  scope_lo == null: every live row, nblk =
-// vm_topk_redo_blocks(m, VM_REDO_CHUNK); otherwise the rows whose tag lies in the query's [scope_lo, scope_hi] only,
-// nblk = vm_topk_redo_blocks(m, VM_REDO_CHUNK_SCOPED).  mask != null (scope_lo null): the rows the query's mask selects
-// only, the scoped scan's chunk and nblk.  vm_topk_redo_merge follows.
-int vm_topk_redo_scan(vm_memory *m, const void *queries, int Q, int k, const int64_t *scope_lo,
-                      const int64_t *scope_hi, const int32_t *flags, int nblk, double *part_s, int64_t *part_o,
-                      hipStream_t st, const MaskSel *mask = nullptr);
+// slice's stable top-k in part_s / part_o [nblk][Q][k].  P = a row predicate (above): NoScope scores every live row in
+// chunks of VM_REDO_CHUNK, nblk = vm_topk_redo_blocks(m, VM_REDO_CHUNK); a scoped P only the rows it admits, in chunks of
+// VM_REDO_CHUNK_SCOPED, nblk = vm_topk_redo_blocks(m, VM_REDO_CHUNK_SCOPED).  Instantiated in topk_exact.hip for the three
+// predicates.  vm_topk_redo_merge follows.
+template <class P>
+int vm_topk_redo_scan(vm_memory *m, const void *queries, int Q, int k, const P &pred, const int32_t *flags, int nblk,
+                      double *part_s, int64_t *part_o, hipStream_t st);
 // Merge of the redo scans' slice winners, part_s / part_o [nblk][Q][k] = {score, age order}, for the flagged queries:
 // stable top-k, score mapping, min_score, row id = (base + order) * row_stride + row_offset.  gkey / out_keys: null, or
 // the grouped search's key column and key output.

@@ -1,7 +1,7 @@
 """Scoped grouped top-k against the grouped top-k, event-timed and warm, the two alternating in one process
 (DESIGN.md 19).
 
-  python tools/group_scope_probe.py [--iters 20] [--out run.json]
+  python tools/group_scope_probe.py [--iters 20] [--out run.json] [--lib other/libvidmem.so]
   python tools/group_scope_probe.py --merge profiles/group_scope_probe.json parent_a=pa.json new_a=na.json ...
 
 Memory: 1 M x 768 fp16 in groups of 16, clustered rows (a centre per group + small noise) - tools/group_probe.py's rows,
@@ -29,6 +29,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
 import vidmem  # noqa: E402,F401
+import vidmem._lib  # noqa: E402
 from vidmem.memory import SCOPE_ALL, EmbeddingMemory, scope_of  # noqa: E402
 
 from group_probe import TD, clustered  # noqa: E402
@@ -86,9 +87,12 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--lib", default=None, help="another build of libvidmem.so to time (an A/B against a parent commit)")
     ap.add_argument("--merge", nargs="+", metavar=("OUT", "NAME=RUN_JSON"), default=None,
                     help="no measurement: collect runs written with --out (and the parent's) into OUT")
     a = ap.parse_args()
+    if a.lib:
+        vidmem._lib.LIB_PATH = os.path.abspath(a.lib)
     if a.merge:
         runs = {name: json.load(open(path)) for name, path in (m.split("=", 1) for m in a.merge[1:])}
         device = next((r["device"] for r in runs.values() if "device" in r), None)

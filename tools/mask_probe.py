@@ -1,6 +1,6 @@
 """Masked top-k against the scoped and the row top-k of the same build, event-timed and warm.
 
-  python tools/mask_probe.py --rows 100000 [--iters 20] [--out profiles/mask_probe_100k.json]
+  python tools/mask_probe.py --rows 100000 [--iters 20] [--out profiles/mask_probe_100k.json] [--lib other/libvidmem.so]
 
 One process per memory size.  Memory: ``--rows`` x 768 fp16, clustered rows (a centre per 16 rows + small noise), tagged
 with tag = row id so that a contiguous selection is also one scope; queries are noisy copies of stored selected rows;
@@ -20,6 +20,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
 import vidmem  # noqa: F401,E402
+import vidmem._lib  # noqa: E402
 from vidmem.memory import EmbeddingMemory  # noqa: E402
 
 from group_probe import TD, clustered  # noqa: E402
@@ -43,7 +44,10 @@ def main():
     ap.add_argument("--rows", type=int, required=True)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--lib", default=None, help="another build of libvidmem.so to time (an A/B against a parent commit)")
     a = ap.parse_args()
+    if a.lib:
+        vidmem._lib.LIB_PATH = os.path.abspath(a.lib)
     n = a.rows
     rows = clustered(n, D, 16, DTYPE, seed=16)
     ids = torch.arange(n, device="cuda")
