@@ -558,6 +558,44 @@ int vm_mask_from_rows(vm_memory *mem, const int64_t *row_ids, int64_t n, int64_t
                       int clear_first, uint32_t *out_mask, void *stream);
 int vm_mask_from_scopes(vm_memory *mem, const int64_t *scope_lo, const int64_t *scope_hi, int n_ranges,
                         uint32_t *out_mask, void *stream);
+/* Span top-k: the k best rows among those whose ROW ID lies in the query's span.  Row ids are append order and append
+ * order is time, so a span is "the past before this frame": what a stored frame resembles in its own past, other than a
+ * moment ago (recall), or a causal limit per query.  row_lo / row_hi: device int64 [Q], both required (NULL is
+ * VM_ERR_INVALID), inclusive LOCAL row ids: append order, before the row_stride / row_offset mapping.  Row r counts for
+ * query q iff r is live and row_lo[q] <= r <= row_hi[q]; live means lo .. n - 1, with lo = n - capacity in a wrapped ring
+ * and 0 otherwise.  Ids inside a span that are not live are ignored: ids below the oldest row, ids at or past the row
+ * count, negative ids.  row_lo[q] > row_hi[q] is the EMPTY span and gives an all-padded result row; INT64_MIN .. INT64_MAX
+ * is every live row.  A span is a statement about ROW IDS and goes stale after an erase, exactly as a mask does; nothing
+ * remaps it.
+ * The result is the exhaustive row ranking of vm_topk_cosine (reference fp64 cosines bit for bit, score_mode mapping,
+ * strict > min_score filter, score descending, row id ascending) over the rows in the span only, first k: out_scores
+ * [Q,k], out_rows [Q,k] global row ids (row_id * row_stride + row_offset), -1 / 0.0 padded.
+ * Identities: with every span INT64_MIN .. INT64_MAX the result equals vm_topk_cosine + vm_topk_redo_flagged; on a tagged
+ * memory whose tags are the row ids it equals vm_topk_cosine_scoped for the same ranges; it equals
+ * vm_topk_cosine_masked with the mask of the span's rows (vm_mask_from_rows).
+ * ALWAYS the exhaustive answer, like the scoped search: an fp32 MFMA scan scores the 16-row tiles that hold a wanted row -
+ * whether a tile does follows from arithmetic on its row ids, so the test reads no memory and the rows of the other tiles
+ * are not read -, the best M = k + max(8, k/4) in-span rows are re-scored exactly, and a query is certified when its span
+ * holds at most M live rows or the exact k-th score clears the (M+1)-th IN-SPAN fp32 score by vm_topk_cosine's bound
+ * 2 (D + 8) 2^-24 - rows outside the span never enter it.  Any other query (VM_FLAG_GAP; VM_FLAG_OVERFLOW: more than
+ * 8192 in-span rows at the query's cut) is counted in *out_uncertified (may be NULL), marked in out_query_flags [Q]
+ * (vm_topk_flag; may be NULL) and redone exhaustively over its span on the device inside the same call.  The bound's norm
+ * domain is vm_topk_cosine_scoped's.
+ * Any memory: plain, grouped, tagged, ring.  No host read-back, no allocation, no synchronisation; the row count and the
+ * spans are read on the device and the grids are sized from the capacity: capturable, and a replay sees spans rewritten
+ * in place and the rows appended since.  1 <= k <= 64, Q >= 1; an undersized workspace is VM_ERR_NOMEM before any launch.
+ * Workspace: vm_topk_span_workspace_bytes (= the scoped search's: 4 x Q x capacity bytes of keys plus 64 KiB x Q and a
+ * few MB). */
+size_t vm_topk_span_workspace_bytes(const vm_memory *mem, int Q, int k);
+int vm_topk_cosine_span(vm_memory *mem, const void *queries, int Q, int k, const int64_t *row_lo, const int64_t *row_hi,
+                        int use_min_score, double min_score, int score_mode, int64_t row_stride, int64_t row_offset,
+                        double *out_scores, int64_t *out_rows, int32_t *out_uncertified, int32_t *out_query_flags,
+                        void *workspace, size_t workspace_bytes, void *stream);
+/* The same contract, exhaustive only: every in-span pair scored exactly (slow; tests, and a checker). */
+int vm_topk_cosine_span_exact(vm_memory *mem, const void *queries, int Q, int k, const int64_t *row_lo,
+                              const int64_t *row_hi, int use_min_score, double min_score, int score_mode,
+                              int64_t row_stride, int64_t row_offset, double *out_scores, int64_t *out_rows,
+                              void *workspace, size_t workspace_bytes, void *stream);
 /* Scoped grouped top-k: the k best GROUPS of a tagged AND grouped memory among the rows IN SCOPE - "the k best scenes of
  * video 7 between minute 10 and minute 20".  scope_lo / scope_hi: device int64 [Q], both required, inclusive tag ranges
  * by vm_topk_cosine_scoped's rule (row r is in query q's scope iff scope_lo[q] <= tag[r] <= scope_hi[q]).

@@ -3,8 +3,8 @@
 // then a stable top-k.  Used (a) as the fallback for queries the fast scan cannot certify, (b) for the
 // post-compression filter (src/pipeline/retriever_hybrid.py:494-504), (c) as an on-device checker.
 // Also home of what the three redos share (vm_internal.h): the row-block count vm_topk_redo_blocks, the redo scan of rows
-// vm_topk_redo_scan (the row redo here, topk_scope.hip and topk_mask.hip; the grouped one carries a group across chunks and is
-// topk_group.hip's own) and the merge of the slice winners vm_topk_redo_merge (all three).
+// vm_topk_redo_scan (the row redo here, topk_scope.hip, topk_mask.hip and topk_span.hip; the grouped one carries a group
+// across chunks and is topk_group.hip's own) and the merge of the slice winners vm_topk_redo_merge (all three).
 #include "topk_common.h"
 #include "vm_internal.h"
 
@@ -146,8 +146,8 @@ constexpr int REDO_KMAX = 64;
 // age orders exactly as the reference does (src/components/pre_llm_injector.py:374-388) and keeps the slice's
 // stable top-k: part[(block * Q + q) * k + i] = {score fp64, age order int64}.  CHUNK scores are held in LDS per
 // selection pass.  P = the row predicate (vm_internal.h).  NoScope: every live row, the scores sit in dynamic LDS behind
-// the query.  A scoped P (TagScope, MaskScope): only the rows it admits are scored and may win, and a chunk with none
-// costs its tags or mask words only; the scores and the in-scope marks sit in static LDS.
+// the query.  A scoped P (TagScope, MaskScope, RowSpan): only the rows it admits are scored and may win, and a chunk with
+// none costs its tags or mask words only (nothing under RowSpan); the scores and the in-scope marks sit in static LDS.
 template <int DT, int CHUNK, class P>
 __global__ void __launch_bounds__(REDO_THREADS)
     topk_redo_scan_kernel(const uint16_t *__restrict__ queries, const uint16_t *__restrict__ rows,
@@ -306,6 +306,8 @@ template int vm_topk_redo_scan(vm_memory *, const void *, int, int, const NoScop
 template int vm_topk_redo_scan(vm_memory *, const void *, int, int, const TagScope &, const int32_t *, int, double *,
                                int64_t *, hipStream_t);
 template int vm_topk_redo_scan(vm_memory *, const void *, int, int, const MaskScope &, const int32_t *, int, double *,
+                               int64_t *, hipStream_t);
+template int vm_topk_redo_scan(vm_memory *, const void *, int, int, const RowSpan &, const int32_t *, int, double *,
                                int64_t *, hipStream_t);
 
 int vm_topk_redo_merge(vm_memory *m, const double *part_s, const int64_t *part_o, int nblk, int Q, int k,

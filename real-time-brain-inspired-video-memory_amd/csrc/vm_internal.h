@@ -83,7 +83,8 @@ __host__ __device__ inline bool mask_selects(const uint32_t *words, int64_t off,
 
 // ---- row predicates -----------------------------------------------------------------------------------------
 // What "the row in physical slot p counts for query q" means, as a type handed to a kernel by value: always (NoScope), the
-// tag range of vm_topk_cosine_scoped (TagScope), the bit mask of vm_topk_cosine_masked (MaskScope).  A model has
+// tag range of vm_topk_cosine_scoped (TagScope), the bit mask of vm_topk_cosine_masked (MaskScope), the row-id span of
+// vm_topk_cosine_span (RowSpan, below them).  A model has
 // `static constexpr bool scoped`, `Q at(int q) const` (what is per query, read once) and, when scoped, `bool
 // Q::in(int64_t p) const`; every use sits under `if constexpr (P::scoped)`, so a NoScope instantiation carries nothing
 // of it.  A consumer tests p for liveness itself.  The redo scans take one (topk_exact.hip, topk_group_parts.h), the
@@ -119,6 +120,42 @@ struct MaskScope {
         __device__ __forceinline__ bool in(int64_t p) const { return mask_selects(words, off, p); }
     };
     __device__ __forceinline__ Q at(int q) const { return {ms.words, mask_offset(ms, q)}; }
+};
+
+// The row-id span [row_lo, row_hi] of vm_topk_cosine_span as inclusive bounds on the AGE ORDER, clamped to the live rows
+// [0, rv.n): ids below the oldest row, at or past the row count, or negative name no row.  lo > hi (here 1, 0): the span
+// is empty or holds no live row.  No sum or difference leaves the live ids, so INT64_MIN / INT64_MAX are safe bounds.
+struct OrderSpan {
+    int64_t lo, hi;
+};
+__host__ __device__ inline OrderSpan order_span(const RingView &rv, int64_t row_lo, int64_t row_hi) {
+    const int64_t first = rv.base, last = rv.base + rv.n - 1;
+    const int64_t lo = row_lo > first ? row_lo : first, hi = row_hi < last ? row_hi : last;
+    if (lo > hi) return {1, 0};
+    return {lo - first, hi - first};
+}
+// The span predicate: slot p counts for query q when the age order of its row lies within the query's bounds.  The one
+// predicate that reads no memory per row: at(q) reads the two bounds and the row count once - through the constant
+// address space, for TagScope's reason - and in(p) is arithmetic on the slot.
+struct RowSpan {
+    static constexpr bool scoped = true;
+    const int64_t *lo, *hi, *d_total;
+    int64_t cap;
+    int ring;
+    struct Q {
+        RingView rv;
+        int64_t lo, hi;  // age orders
+        __device__ __forceinline__ bool in(int64_t p) const {
+            const int64_t o = order_of(rv, p);
+            return lo <= o && o <= hi;
+        }
+    };
+    __device__ __forceinline__ Q at(int q) const {
+        typedef const __attribute__((address_space(4))) int64_t *scalar_ptr;
+        const RingView rv = ring_view(((scalar_ptr)d_total)[0], cap, ring);
+        const OrderSpan s = order_span(rv, ((scalar_ptr)lo)[q], ((scalar_ptr)hi)[q]);
+        return {rv, s.lo, s.hi};
+    }
 };
 
 // grouped memories: the live rows + the ordinal of the oldest live group + the number of live groups, from the device
@@ -174,7 +211,7 @@ constexpr int VM_REDO_CHUNK = 2048, VM_REDO_CHUNK_SCOPED = 1024;
 // The redo scan of rows: for every flagged query, block b of nblk scores its slice of age orders exactly and leaves the
 // slice's stable top-k in part_s / part_o [nblk][Q][k].  P = a row predicate (above): NoScope scores every live row in
 // chunks of VM_REDO_CHUNK, nblk = vm_topk_redo_blocks(m, VM_REDO_CHUNK); a scoped P only the rows it admits, in chunks of
-// VM_REDO_CHUNK_SCOPED, nblk = vm_topk_redo_blocks(m, VM_REDO_CHUNK_SCOPED).  Instantiated in topk_exact.hip for the three
+// VM_REDO_CHUNK_SCOPED, nblk = vm_topk_redo_blocks(m, VM_REDO_CHUNK_SCOPED).  Instantiated in topk_exact.hip for the four
 // predicates.  vm_topk_redo_merge follows.
 template <class P>
 int vm_topk_redo_scan(vm_memory *m, const void *queries, int Q, int k, const P &pred, const int32_t *flags, int nblk,

@@ -53,7 +53,7 @@ class HipHybridMixin:
     _hip: Optional[HipVectorSearch] = None
 
     def attach_memory(self, memory, *, score_mode: int, min_score: float = 0.3, splitter=None, embedder=None,
-                      distinct: bool = False, scope=None, mask=None):
+                      distinct: bool = False, scope=None, mask=None, span=None):
         """``score_mode`` is required: see similarity.HipVectorSearch (Neo4j's score mapping is unpinned).
         ``embedder``: what embeds the questions (e.g. text.HipTextEmbedder); None = ``self.embedder``.  ValueError when
         it states an ``out_dim`` other than ``memory.dim``.  ``distinct=True``: one hit per chunk (grouped memory).
@@ -61,10 +61,11 @@ class HipHybridMixin:
         reference's ``{graph_uuid: $graph_uuid}``, retriever_hybrid.py:295); together with ``distinct`` it needs a memory that
         provides ``topk_grouped_scoped`` (a grouped and tagged EmbeddingMemory): one hit per chunk of the scope.
         ``mask``: a row mask the vector leg is restricted to (EmbeddingMemory.topk_masked; any memory); not together with
-        ``scope`` or ``distinct``."""
+        ``scope`` or ``distinct``.  ``span``: one inclusive row-id range ``(lo, hi)``, ``None`` = open, the vector leg is
+        restricted to (EmbeddingMemory.topk_span; any memory); not together with ``scope``, ``mask`` or ``distinct``."""
         self._hip = HipVectorSearch(memory, self.embedder if embedder is None else embedder, self.config,
                                     min_score=min_score, score_mode=score_mode, splitter=splitter, distinct=distinct,
-                                    scope=scope, mask=mask)
+                                    scope=scope, mask=mask, span=span)
         return self
 
     async def _vector_search_chunks(self, session, query):

@@ -42,7 +42,7 @@ import torch
 from . import _lib
 from .scratch import (NOVEL_MAX_ROWS, ClipScratch, EraseScratch, EventsScratch, GroupedScopedTopkScratch,  # noqa: F401
                       GroupedTopkScratch, MaskedTopkScratch, NoveltyScratch, RangeScratch, ScopedTopkScratch, Scratch,
-                      SummaryScratch, TopkScratch)
+                      SpanTopkScratch, SummaryScratch, TopkScratch)
 
 
 INT64_MIN, INT64_MAX = -(1 << 63), (1 << 63) - 1
@@ -276,7 +276,7 @@ def _keep_alive(*tensors) -> None:
 
 
 class _Search(NamedTuple):
-    """One of the five top-k searches as ``EmbeddingMemory._search`` runs it: its entries, the memory it needs and the
+    """One of the six top-k searches as ``EmbeddingMemory._search`` runs it: its entries, the memory it needs and the
     arguments it takes beyond (queries, k, min_score, score_mode)."""
     words: str                   # the search in an error message
     scratch: type                # its scratch kind (which names the sizing call)
@@ -286,7 +286,8 @@ class _Search(NamedTuple):
     tagged: bool = False         # needs a tagged memory
     refusal: str = ""            # ... and says so in these words
     max_k: int = 64              # 0 = the library's own rule
-    scoped: bool = False         # takes a (lo, hi) tag range per query
+    scoped: bool = False         # takes a (lo, hi) pair per query: a tag range, or a row-id span
+    pairs: str = "scope"         # ... and calls it this in an error message
     masked: bool = False         # takes row masks [n_masks, W] and the mask each query names
     keyed: bool = False          # returns the group keys as a third output
     strided: bool = False        # passes the (row_stride, row_offset) pair
@@ -302,6 +303,8 @@ _SCOPED = _Search("scoped top-k", ScopedTopkScratch, "vm_topk_cosine_scoped", "v
                   refusal="topk_scoped needs a tagged memory (EmbeddingMemory(..., tagged=True))")
 _MASKED = _Search("masked top-k", MaskedTopkScratch, "vm_topk_cosine_masked", "vm_topk_cosine_masked_exact", masked=True,
                   strided=True)
+_SPAN = _Search("span top-k", SpanTopkScratch, "vm_topk_cosine_span", "vm_topk_cosine_span_exact", scoped=True,
+                pairs="span", strided=True)
 _GROUPED_SCOPED = _Search("scoped grouped top-k", GroupedScopedTopkScratch, "vm_topk_cosine_grouped_scoped",
                           "vm_topk_cosine_grouped_scoped_exact", grouped=True, tagged=True, scoped=True, keyed=True,
                           refusal="topk_grouped_scoped needs a grouped and tagged memory "
@@ -803,8 +806,8 @@ class EmbeddingMemory:
 
     def _search(self, kind: _Search, queries, k, scope, min_score, score_mode, exact, scratch, stride=(1, 0),
                 redo=True) -> Tuple[torch.Tensor, ...]:
-        """The one body of ``topk``, ``topk_grouped``, ``topk_scoped``, ``topk_grouped_scoped`` and ``topk_masked``
-        (whose ``scope`` is the pair (mask, mask_index)).  The memory-kind, ``k`` and mask checks come before anything
+        """The one body of ``topk``, ``topk_grouped``, ``topk_scoped``, ``topk_grouped_scoped``, ``topk_span`` (whose
+        ``scope`` is the row-id spans) and ``topk_masked`` (whose ``scope`` is the pair (mask, mask_index)).  The memory-kind, ``k`` and mask checks come before anything
         that needs a device."""
         if (kind.grouped and not self.grouped) or (kind.tagged and not self.tagged):
             raise ValueError(kind.refusal)
@@ -813,7 +816,7 @@ class EmbeddingMemory:
         masks = self._masks(scope[0]) if kind.masked else None
         q = self._as_rows(queries)
         Q, k = q.shape[0], int(k)
-        sc = self._scopes(scope, Q) if kind.scoped else None
+        sc = self._scopes(scope, Q, kind.pairs) if kind.scoped else None
         if kind.masked:
             sc = self._mask_index(scope[1], masks.shape[0], Q)
         s = self._resolve(kind.scratch, scratch, Q, k)
@@ -868,13 +871,13 @@ class EmbeddingMemory:
         """Size the scoped top-k workspace for (Q, k) now (before a graph capture: a capture must not allocate)."""
         return self._prepare_search(_SCOPED, Q, k)
 
-    def _scopes(self, scope, n: Optional[int] = None) -> torch.Tensor:
+    def _scopes(self, scope, n: Optional[int] = None, what: str = "scope") -> torch.Tensor:
         """-> device int64 [2, n] (row 0 = lo, row 1 = hi) from one (lo, hi), a sequence of pairs, or an int64 [n, 2]
         tensor (a device tensor is not read on the host).  ``n`` given: exactly ``n`` pairs, one pair standing for all
-        of them; ``n=None``: any number of pairs, at least one."""
+        of them; ``n=None``: any number of pairs, at least one.  ``what``: the word for a pair in an error message."""
         if isinstance(scope, torch.Tensor):
             if scope.dtype != torch.int64 or scope.dim() != 2 or scope.shape[1] != 2:
-                raise ValueError("a scope tensor must be int64 [n, 2]")
+                raise ValueError(f"a {what} tensor must be int64 [n, 2]")
             pairs, count = None, scope.shape[0]
         else:
             pairs = list(scope)
@@ -882,13 +885,13 @@ class EmbeddingMemory:
                 pairs = [pairs] * (1 if n is None else n)
             count = len(pairs)
         if n is None and count < 1:
-            raise ValueError("0 scopes: at least one pair (lo, hi) is needed")
+            raise ValueError(f"0 {what}s: at least one pair (lo, hi) is needed")
         if n is not None and count != n:
-            raise ValueError(f"{count} scopes for {n} queries")
+            raise ValueError(f"{count} {what}s for {n} queries")
         if pairs is None:
             return scope.to(self.device).t().contiguous()
         if any(len(p) != 2 for p in pairs):
-            raise ValueError("a scope is a pair (lo, hi)")
+            raise ValueError(f"a {what} is a pair (lo, hi)")
         vals = [[int(p[0]) for p in pairs], [int(p[1]) for p in pairs]]
         return torch.tensor(vals, dtype=torch.int64).to(self.device)
 
@@ -1055,6 +1058,96 @@ class EmbeddingMemory:
         ``last_mask_flags``.  ``scratch``: as in ``topk`` - a ``MaskedTopkScratch`` the caller owns (a graph capture; a
         replay sees the mask as it is then), default this memory's own."""
         return self._search(_MASKED, queries, k, (mask, mask_index), min_score, score_mode, exact, scratch)
+
+    # ---- row-id spans and recall links (include/vidmem.h vm_topk_cosine_span, DESIGN.md 25) ------------------------
+    def prepare_topk_span(self, Q: int, k: int) -> SpanTopkScratch:
+        """Size the span top-k workspace for (Q, k) now (before a graph capture: a capture must not allocate)."""
+        return self._prepare_search(_SPAN, Q, k)
+
+    @staticmethod
+    def _open_spans(span):
+        """``span`` as ``_scopes`` takes it: a tensor as it is (checked there), host pairs with ``None`` bounds opened."""
+        if isinstance(span, torch.Tensor):
+            return span
+        def opened(p):
+            if not hasattr(p, "__len__") or len(p) != 2:
+                raise ValueError("a span is a pair (lo, hi)")
+            return (INT64_MIN if p[0] is None else int(p[0]), INT64_MAX if p[1] is None else int(p[1]))
+        pairs = list(span)
+        if len(pairs) == 2 and not hasattr(pairs[0], "__len__"):
+            return opened(pairs)
+        return [opened(p) for p in pairs]
+
+    def topk_span(self, queries, k: int, span, min_score: Optional[float] = None, score_mode: int = _lib.VM_SCORE_RAW,
+                  exact: bool = False, scratch: Optional[SpanTopkScratch] = None, stride: Tuple[int, int] = (1, 0)
+                  ) -> Tuple[torch.Tensor, torch.Tensor]:
+        """-> (scores [Q,k] float64, rows [Q,k] int64): the k best rows among those whose ROW ID lies in the query's span,
+        on any memory.  Row ids are append order, so a span is a stretch of time: "the past before this frame".
+        ``span``: one inclusive ``(lo, hi)`` for all queries, a sequence of Q pairs, or a device int64 ``[Q, 2]`` tensor
+        (not read on the host; a captured call sees it rewritten in place).  ``None`` as a bound means open.  The ids
+        are this memory's own (before ``stride``); ids that name no live row are ignored, ``lo > hi`` is the empty span.
+
+        The exhaustive row ranking of ``topk`` (score desc, row asc; score mapping and > min_score filter) over the rows
+        in the span only; -1 / 0.0 padded.  Always the exhaustive answer: the fp32 fast path redoes the queries it cannot
+        certify on the device, in the same call (csrc/topk_span.hip).  ``exact=True`` scores every in-span pair exactly
+        (slow).  1 <= k <= 64.  ``stride``: ``(row_stride, row_offset)`` of the returned ids, as in ``topk``.  The
+        per-query flags of the last call are in ``last_span_flags``.  ``scratch``: as in ``topk`` - a ``SpanTopkScratch``
+        the caller owns (a graph capture), default this memory's own.  A span speaks about row ids: after an erase it is
+        stale exactly as a mask is."""
+        return self._search(_SPAN, queries, k, self._open_spans(span), min_score, score_mode, exact, scratch, stride)
+
+    def recall_links(self, first_row: Optional[int] = None, n_rows: Optional[int] = None, k: int = 10, min_gap: int = 1,
+                     max_back: Optional[int] = None, exclude_group: bool = False, min_score: Optional[float] = None,
+                     score_mode: int = _lib.VM_SCORE_RAW, block: int = 256, exact: bool = False
+                     ) -> Tuple[torch.Tensor, torch.Tensor]:
+        """-> (scores [n_rows,k] float64, rows [n_rows,k] int64): for each stored row, its k best matches in ITS OWN PAST.
+        Query i is the stored row ``r = first_row + i`` (default: every live row) and its span is
+        ``[r - max_back, r - min_gap]``, open below when ``max_back`` is ``None``; ``min_gap >= 1`` keeps the row itself
+        and its nearest temporal neighbours out.  ``exclude_group=True`` (grouped memories only): the span also ends no
+        later than the row before the first row of r's own group, so a row never links into its own chunk or event.
+        Rows with an empty past come back all-padded (-1 / 0.0).
+
+        Everything is built on the device and searched with ``topk_span``, in pages of ``block`` consecutive rows: a
+        page's spans end below its last row, so the tiles behind it are skipped for free and a whole-memory pass scores
+        about half the pairs.  One page needs ``4 x block x capacity`` bytes of workspace plus the fixed part.  Reads the
+        host row count: after captured appends call ``sync()`` first."""
+        k, min_gap, block = int(k), int(min_gap), int(block)
+        if min_gap < 1:
+            raise ValueError(f"recall_links needs min_gap >= 1 (a row always matches itself), got {min_gap}")
+        if max_back is not None and int(max_back) < 0:
+            raise ValueError(f"max_back must be >= 0 or None, got {max_back}")
+        if block < 1:
+            raise ValueError(f"block must be >= 1, got {block}")
+        if not 1 <= k <= 64:
+            raise ValueError(f"span top-k supports 1 <= k <= 64, got {k}")
+        if exclude_group and not self.grouped:
+            raise ValueError("exclude_group=True needs a grouped memory (EmbeddingMemory(..., grouped=True))")
+        total, n = len(self), self.searchable
+        base = total - n
+        first = base if first_row is None else int(first_row)
+        count = total - first if n_rows is None else int(n_rows)
+        if first < base or count < 0 or first + count > total:
+            raise ValueError(f"rows {first} .. {first + count - 1} are not all live ({base} .. {total - 1} are)")
+        scores = torch.zeros((count, k), dtype=torch.float64, device=self.device)
+        rows = torch.full((count, k), -1, dtype=torch.int64, device=self.device)
+        if count == 0:
+            return scores, rows
+        table = self.rows_tensor()
+        if exclude_group:      # ordinals rise by 0 or 1 from each row to the next: a group's first row by bisection
+            col = _tensor_from_ptr(self.L.vm_memory_group_ordinals(self.handle), (n,), torch.int64, self.device)
+            ords = self._in_row_order(col).contiguous()
+        for b0 in range(0, count, block):
+            r = torch.arange(first + b0, first + min(b0 + block, count), dtype=torch.int64, device=self.device)
+            hi = r - min_gap
+            lo = torch.full_like(r, INT64_MIN) if max_back is None else r - int(max_back)
+            if exclude_group:
+                group_first = base + torch.searchsorted(ords, ords[r - base])
+                hi = torch.minimum(hi, group_first - 1)
+            s, got = self.topk_span(table[self._slots_of(r)], k, torch.stack([lo, hi], dim=1), min_score=min_score,
+                                    score_mode=score_mode, exact=exact)
+            scores[b0:b0 + r.numel()] = s
+            rows[b0:b0 + r.numel()] = got
+        return scores, rows
 
     # ---- clip search (include/vidmem.h vm_topk_cosine_clip, DESIGN.md 20) -----------------------------------------
     def prepare_topk_clip(self, C: int, L: int, k: int) -> "ClipScratch":
@@ -1434,6 +1527,9 @@ class EmbeddingMemory:
     last_mask_flags = _last_property(MaskedTopkScratch, "flags", "int32 per query (vm_topk_flag): why the last fast masked "
                                      "call redid a query, 0 = certified")
     masked_uncertified_count = _count_property(MaskedTopkScratch, "Queries the masked fast path")
+    last_span_flags = _last_property(SpanTopkScratch, "flags", "int32 per query (vm_topk_flag): why the last fast "
+                                     "`topk_span` call redid a query, 0 = certified")
+    span_uncertified_count = _count_property(SpanTopkScratch, "Queries the span fast path")
     grouped_uncertified_count = _count_property(GroupedTopkScratch, "Queries the grouped fast path")
     scoped_uncertified_count = _count_property(ScopedTopkScratch, "Queries the scoped fast path")
     group_scoped_uncertified_count = _count_property(GroupedScopedTopkScratch, "Queries the scoped grouped fast path")

@@ -106,7 +106,7 @@ class TopkScratch(Scratch):
 
 
 class _ScanScratch(Scratch):
-    """The workspace and the per-query ``flags`` (int32 [Q]) of a grouped, scoped and / or masked top-k of up to (Q, k).  The
+    """The workspace and the per-query ``flags`` (int32 [Q]) of a grouped, scoped, masked or span top-k of up to (Q, k).  The
     uncertified counters of these searches are the memory's, whichever scratch a call used."""
 
     @staticmethod
@@ -124,6 +124,10 @@ class ScopedTopkScratch(_ScanScratch):
 
 class MaskedTopkScratch(_ScanScratch):
     workspaces = (("ws", "vm_topk_masked_workspace_bytes"),)
+
+
+class SpanTopkScratch(_ScanScratch):
+    workspaces = (("ws", "vm_topk_span_workspace_bytes"),)
 
 
 class GroupedScopedTopkScratch(_ScanScratch):

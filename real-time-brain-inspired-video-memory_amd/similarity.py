@@ -78,8 +78,32 @@ def _check_mask(mask, scope, distinct: bool) -> None:
         raise ValueError("mask and distinct=True are mutually exclusive: the masked search ranks rows, not groups")
 
 
+def _check_span(span, scope, mask, distinct: bool) -> None:
+    """``span`` (one inclusive row-id range ``(lo, hi)`` for every query, ``None`` = open; EmbeddingMemory.topk_span)
+    stands alone: a scope and a mask are other ways to choose rows, and the span search ranks rows, not groups."""
+    if span is None:
+        return
+    if scope is not None:
+        raise ValueError("span and scope are mutually exclusive: a span names row ids, a scope tags")
+    if mask is not None:
+        raise ValueError("span and mask are mutually exclusive: set the span's rows in the mask (memory.mask_of_rows)")
+    if distinct:
+        raise ValueError("span and distinct=True are mutually exclusive: the span search ranks rows, not groups")
+    if isinstance(span, torch.Tensor) or not hasattr(span, "__len__") or len(span) != 2 or \
+            any(hasattr(b, "__len__") for b in span):
+        raise ValueError("span is one pair (lo, hi) of row ids for every query; None is an open bound")
+
+
+def _span_rows(memory: EmbeddingMemory, span) -> range:
+    """The live row ids one span holds, ascending."""
+    last = len(memory) - 1
+    first = last - memory.searchable + 1
+    return range(first if span[0] is None else max(first, int(span[0])),
+                 (last if span[1] is None else min(last, int(span[1]))) + 1)
+
+
 def batch_similarities(memory: EmbeddingMemory, chunk_embeddings: Sequence, top_k: int, distinct: bool = False,
-                       scope=None, mask=None) -> List[List[Tuple[str, float]]]:
+                       scope=None, mask=None, span=None) -> List[List[Tuple[str, float]]]:
     """One batched top-k launch for every non-failed query; result re-threaded into the reference's list shape.
 
     A query whose length differs from the stored vectors' scores 0.0 against EVERY row in the reference
@@ -100,7 +124,12 @@ def batch_similarities(memory: EmbeddingMemory, chunk_embeddings: Sequence, top_
 
     ``mask`` (any memory): one row mask for every query (EmbeddingMemory.new_mask / mask_of_rows / mask_where); only the
     selected rows are ranked (EmbeddingMemory.topk_masked), and the wrong-length rule lists the first selected rows.
-    Mutually exclusive with ``scope`` and with ``distinct=True`` (ValueError)."""
+    Mutually exclusive with ``scope`` and with ``distinct=True`` (ValueError).
+
+    ``span`` (any memory): one inclusive row-id range ``(lo, hi)`` for every query, ``None`` = an open bound - a stretch
+    of the memory's time; only the rows in it are ranked (EmbeddingMemory.topk_span), and the wrong-length rule lists the
+    first in-span rows.  Mutually exclusive with ``scope``, ``mask`` and ``distinct=True`` (ValueError)."""
+    _check_span(span, scope, mask, distinct)
     _check_mask(mask, scope, distinct)
     _check_distinct(memory, distinct)
     _check_scope(memory, scope, distinct)
@@ -111,7 +140,9 @@ def batch_similarities(memory: EmbeddingMemory, chunk_embeddings: Sequence, top_
     wrong = [i for i in ok_idx if _length(chunk_embeddings[i]) != memory.dim]
     if wrong:
         first_row = len(memory) - memory.searchable
-        if mask is not None:
+        if span is not None:
+            zeros = [(memory.id_of(r), 0.0) for r in _span_rows(memory, span)[:top_k]]
+        elif mask is not None:
             zeros = [(memory.id_of(r), 0.0) for r in memory.rows_of_mask(mask)[:top_k]]
         elif scope is None:
             zeros = [(memory.id_of(first_row + j), 0.0) for j in range(min(top_k, memory.searchable))]
@@ -135,7 +166,9 @@ def batch_similarities(memory: EmbeddingMemory, chunk_embeddings: Sequence, top_
         q = torch.stack([chunk_embeddings[i] for i in ok_idx])
     else:
         q = torch.tensor([list(chunk_embeddings[i]) for i in ok_idx], dtype=torch.float32)
-    if mask is not None:
+    if span is not None:
+        scores, rows = memory.topk_span(q, top_k, span)
+    elif mask is not None:
         scores, rows = memory.topk_masked(q, top_k, mask)
     elif scope is not None and distinct:
         scores, rows, _ = memory.topk_grouped_scoped(q, top_k, scope)
@@ -149,6 +182,22 @@ def batch_similarities(memory: EmbeddingMemory, chunk_embeddings: Sequence, top_
     for slot, i in enumerate(ok_idx):
         out[i] = [(memory.id_of(r), float(s)) for r, s in zip(rows[slot], scores[slot]) if r >= 0]
     return out
+
+
+def recall_links(memory: EmbeddingMemory, first_row: Optional[int] = None, n_rows: Optional[int] = None, top_k: int = 10,
+                 min_gap: int = 1, max_back: Optional[int] = None, exclude_group: bool = False,
+                 min_score: Optional[float] = None, score_mode: int = _lib.VM_SCORE_RAW, block: int = 256
+                 ) -> List[List[Tuple[str, float]]]:
+    """What each stored row resembles in its own past, in the reference's list shape: entry i belongs to the stored row
+    ``first_row + i`` (default: every live row) and holds ``[(id, score), ...]`` of its ``top_k`` best matches among the
+    rows at least ``min_gap`` and at most ``max_back`` (``None``: any distance) before it - the links a temporal
+    consolidation pass would add between disconnected nodes.  Arguments as in ``EmbeddingMemory.recall_links``; ids come
+    from ``memory.id_of``; a row with an empty past, or none above ``min_score``, yields ``[]``."""
+    scores, rows = memory.recall_links(first_row, n_rows, k=top_k, min_gap=min_gap, max_back=max_back,
+                                       exclude_group=exclude_group, min_score=min_score, score_mode=score_mode,
+                                       block=block)
+    return [[(memory.id_of(r), float(s)) for r, s in zip(rr, ss) if r >= 0]
+            for rr, ss in zip(rows.cpu().tolist(), scores.cpu().tolist())]
 
 
 def clip_similarities(memory: EmbeddingMemory, chunks_of_frame_embeddings: Sequence, top_k: int,
@@ -189,14 +238,17 @@ def clip_similarities(memory: EmbeddingMemory, chunks_of_frame_embeddings: Seque
 class HipPreLLMSimilarity:
     """Mixin / stand-alone object for PreLLMInjector: set ``self.memory`` and ``self.embedder_config``."""
 
-    def __init__(self, memory: EmbeddingMemory, embedder_config: Any, distinct: bool = False, scope=None, mask=None):
+    def __init__(self, memory: EmbeddingMemory, embedder_config: Any, distinct: bool = False, scope=None, mask=None,
+                 span=None):
         """``scope``: an inclusive tag range ``(lo, hi)`` (memory.scope_of) every search of this object is restricted to
         - the reference's ``WHERE c.graph_uuid = $graph_uuid`` (src/components/pre_llm_injector.py:395-396); tagged memory
         only.  Together with ``distinct`` it needs a memory that provides ``topk_grouped_scoped`` (a grouped and tagged
         EmbeddingMemory): one hit per group among the in-scope rows; ValueError otherwise.  ``None`` = the whole
         memory.  ``mask``: a row mask every search of this object is restricted to (``batch_similarities``); the object
         keeps the tensor, so rewriting it in place changes the next search.  Not together with ``scope`` or
-        ``distinct``."""
+        ``distinct``.  ``span``: one inclusive row-id range ``(lo, hi)``, ``None`` = open, every search of this object is
+        restricted to (EmbeddingMemory.topk_span); not together with ``scope``, ``mask`` or ``distinct``."""
+        _check_span(span, scope, mask, distinct)
         _check_mask(mask, scope, distinct)
         _check_distinct(memory, distinct)
         _check_scope(memory, scope, distinct)
@@ -205,6 +257,7 @@ class HipPreLLMSimilarity:
         self.distinct = bool(distinct)
         self.scope = scope
         self.mask = mask
+        self.span = span
 
     async def _calculate_batch_similarities(self, chunk_embeddings, neo4j_handler=None
                                             ) -> List[List[Tuple[str, float]]]:
@@ -212,7 +265,7 @@ class HipPreLLMSimilarity:
             return batch_similarities(self.memory, chunk_embeddings,
                                       self.embedder_config.top_k_chunk_with_batch_similarity,
                                       distinct=getattr(self, "distinct", False), scope=getattr(self, "scope", None),
-                                      mask=getattr(self, "mask", None))
+                                      mask=getattr(self, "mask", None), span=getattr(self, "span", None))
         except _lib.VidmemError as e:
             if e.code == _lib.VM_ERR_INVALID:
                 raise
@@ -254,7 +307,7 @@ class HipVectorSearch:
 
     def __init__(self, memory: EmbeddingMemory, embedder: Any, config: Any, *, score_mode: int,
                  min_score: float = 0.3, splitter: Optional[Callable[[str], List[str]]] = None, distinct: bool = False,
-                 scope=None, mask=None):
+                 scope=None, mask=None, span=None):
         """``score_mode`` is REQUIRED (keyword): the reference filters on Neo4j's
         ``vector.similarity.cosine(...) > 0.3`` (src/pipeline/retriever_hybrid.py:296-298), a third-party function of an
         unpinned server image whose value may be the raw cosine or its [0,1] mapping (1+cos)/2 - with the literal 0.3
@@ -269,7 +322,10 @@ class HipVectorSearch:
         EmbeddingMemory; ValueError otherwise): ``top_k_chunks`` distinct chunks of the scope, each represented by its
         best in-scope frame.  ``None`` = the whole memory.
         ``mask``: a row mask the search is restricted to (EmbeddingMemory.topk_masked: a metadata filter, the hits of
-        another search, an exclusion); any memory; not together with ``scope`` or ``distinct`` (ValueError)."""
+        another search, an exclusion); any memory; not together with ``scope`` or ``distinct`` (ValueError).
+        ``span``: one inclusive row-id range ``(lo, hi)``, ``None`` = open, the search is restricted to
+        (EmbeddingMemory.topk_span: a stretch of the memory's time); any memory; not together with ``scope``, ``mask`` or
+        ``distinct`` (ValueError)."""
         if score_mode not in (_lib.VM_SCORE_RAW, _lib.VM_SCORE_UNIT_INTERVAL):
             raise ValueError("score_mode must be VM_SCORE_RAW or VM_SCORE_UNIT_INTERVAL")
         # an embedder that states its width (HipTextEmbedder, FrameEncoder-backed ones) must match the memory's rows: a
@@ -278,6 +334,7 @@ class HipVectorSearch:
         if out_dim is not None and int(out_dim) != int(memory.dim):
             raise ValueError(f"embedder out_dim {out_dim} != memory.dim {memory.dim}: build the memory with the matching "
                              "image encoder (text questions: encoder.arch clip_l14_336_joint)")
+        _check_span(span, scope, mask, distinct)
         _check_mask(mask, scope, distinct)
         _check_distinct(memory, distinct)
         _check_scope(memory, scope, distinct)
@@ -285,12 +342,16 @@ class HipVectorSearch:
         self.distinct = bool(distinct)
         self.scope = scope
         self.mask = mask
+        self.span = span
         self.min_score, self.score_mode, self.splitter = min_score, score_mode, splitter
 
     async def _vector_search_chunks(self, session, query) -> List[Dict[str, Any]]:
         try:
             query_embedding = await self.embedder.aembed_query(query)
-            if getattr(self, "mask", None) is not None:
+            if getattr(self, "span", None) is not None:
+                scores, rows = self.memory.topk_span([query_embedding], self.config.top_k_chunks, self.span,
+                                                     min_score=self.min_score, score_mode=self.score_mode)
+            elif getattr(self, "mask", None) is not None:
                 scores, rows = self.memory.topk_masked([query_embedding], self.config.top_k_chunks, self.mask,
                                                        min_score=self.min_score, score_mode=self.score_mode)
             elif getattr(self, "scope", None) is not None and self.distinct:
