@@ -596,6 +596,47 @@ int vm_topk_cosine_span_exact(vm_memory *mem, const void *queries, int Q, int k,
                               const int64_t *row_hi, int use_min_score, double min_score, int score_mode,
                               int64_t row_stride, int64_t row_offset, double *out_scores, int64_t *out_rows,
                               void *workspace, size_t workspace_bytes, void *stream);
+/* Mixed-query top-k: the k best rows by a WEIGHTED SUM OF COSINES.  A mixed query c is J term vectors and J weights:
+ * text plus picture in a joint space, relevance feedback (positive and negative terms), the mean over a few examples.
+ * terms: [C, J, D] device vectors in the memory's dtype, 1 <= J <= 16; weights: [C, J] device fp64 (on the device, like
+ * scopes and spans: a captured graph replays with rewritten weights).  masks: NULL = every live row (n_masks and
+ * mask_index are then ignored); otherwise masks, n_masks and mask_index mean exactly what they mean in
+ * vm_topk_cosine_masked, one mask per mixed query (mask_index [C]; NULL: n_masks == 1 or n_masks == C).
+ * Score of row r for query c:  W(c, r) = sum_j w[c][j] * e_j(r),  e_j(r) = the raw reference cosine of term j and row r
+ * (vm_topk_cosine's fp64 value; 0.0 when either norm is zero), the sum started at 0.0 and taken j = 0 .. J-1 left to
+ * right, one rounding per product and one per addition, never fused.  So J = 1, w = 1.0 gives the reference cosine bit
+ * for bit (the result equals vm_topk_cosine / vm_topk_cosine_masked), and appended terms of weight 0.0 change no bit.
+ * Result: the live rows the mask selects ranked by (W descending, row id ascending), those with W > min_score kept when
+ * use_min_score != 0 (strict; the scores are raw only: the unit-interval mapping has no meaning outside [-1, 1]), first k:
+ * out_scores [C,k] the fp64 W bit for bit, out_rows [C,k] global row ids (row_id * row_stride + row_offset), 0.0 / -1
+ * padded.  The result of a query depends on the memory, its own terms, weights and mask and the arguments only, not on
+ * the other queries of the call.  Non-finite weights are undefined, as stored NaN is.
+ * ALWAYS the exhaustive answer: the fp32 MFMA tile scan scores the J terms as the 16 columns of one query tile and sums
+ * them, scaled by fl32(w_j / ||term_j||), into ONE fp32 score B per (query, row); the best M = k + max(8, k/4) selected
+ * rows are re-scored exactly, and a query is certified when its mask selects at most M rows or the exact k-th W clears
+ * the (M+1)-th scanned score by eps_mix = A (2 (D + 8) 2^-24 + 2^-21), A = sum_j |w_j|, strictly.  The bound holds when
+ * every nonzero |w_j| lies in [2^-20, 2^20] and every term and stored norm is 0 or in [2^-40, 2^40]; outside, and for any
+ * other query (VM_FLAG_GAP; VM_FLAG_OVERFLOW: more than 8192 selected rows at the query's cut), the query is counted in
+ * *out_uncertified (may be NULL), marked in out_query_flags [C] (vm_topk_flag; may be NULL) and redone exhaustively over
+ * its selected rows on the device inside the same call.
+ * Any memory: plain, grouped, tagged, ring.  No host read-back, no allocation, no synchronisation: capturable; a replay
+ * sees weights, terms and masks rewritten in place and the rows appended since.  1 <= k <= 64, C >= 1.  VM_ERR_INVALID
+ * (with a vm_last_error text) for J outside [1, 16], k outside [1, 64], NULL terms, weights or outputs, a workspace
+ * below vm_topk_mix_workspace_bytes, masks that are not 4-byte aligned or whose count fits no rule above; the workspace
+ * must be 256-byte, terms 16-byte and weights 8-byte aligned.
+ * Workspace: vm_topk_mix_workspace_bytes (4 x C x capacity bytes of keys, 32 x D bytes of packed terms per query, plus
+ * 64 KiB x C and a few MB). */
+size_t vm_topk_mix_workspace_bytes(const vm_memory *mem, int C, int k);
+int vm_topk_cosine_mix(vm_memory *mem, const void *terms, const double *weights, int C, int J, int k,
+                       const uint32_t *masks, int n_masks, const int32_t *mask_index, int use_min_score,
+                       double min_score, int64_t row_stride, int64_t row_offset, double *out_scores, int64_t *out_rows,
+                       int32_t *out_uncertified, int32_t *out_query_flags, void *workspace, size_t workspace_bytes,
+                       void *stream);
+/* The same contract, exhaustive only: every selected (query, row) pair scored exactly (slow; tests, and a checker). */
+int vm_topk_cosine_mix_exact(vm_memory *mem, const void *terms, const double *weights, int C, int J, int k,
+                             const uint32_t *masks, int n_masks, const int32_t *mask_index, int use_min_score,
+                             double min_score, int64_t row_stride, int64_t row_offset, double *out_scores,
+                             int64_t *out_rows, void *workspace, size_t workspace_bytes, void *stream);
 /* Scoped grouped top-k: the k best GROUPS of a tagged AND grouped memory among the rows IN SCOPE - "the k best scenes of
  * video 7 between minute 10 and minute 20".  scope_lo / scope_hi: device int64 [Q], both required, inclusive tag ranges
  * by vm_topk_cosine_scoped's rule (row r is in query q's scope iff scope_lo[q] <= tag[r] <= scope_hi[q]).

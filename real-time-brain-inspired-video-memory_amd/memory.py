@@ -41,8 +41,8 @@ import torch
 
 from . import _lib
 from .scratch import (NOVEL_MAX_ROWS, ClipScratch, EraseScratch, EventsScratch, GroupedScopedTopkScratch,  # noqa: F401
-                      GroupedTopkScratch, MaskedTopkScratch, NoveltyScratch, RangeScratch, ScopedTopkScratch, Scratch,
-                      SpanTopkScratch, SummaryScratch, TopkScratch)
+                      GroupedTopkScratch, MaskedTopkScratch, MixTopkScratch, NoveltyScratch, RangeScratch,
+                      ScopedTopkScratch, Scratch, SpanTopkScratch, SummaryScratch, TopkScratch)
 
 
 INT64_MIN, INT64_MAX = -(1 << 63), (1 << 63) - 1
@@ -1149,6 +1149,82 @@ class EmbeddingMemory:
             rows[b0:b0 + r.numel()] = got
         return scores, rows
 
+    # ---- mixed-query search (include/vidmem.h vm_topk_cosine_mix) -----------------------------------
+    def prepare_topk_mix(self, C: int, J: int, k: int) -> MixTopkScratch:
+        """Size the mixed top-k workspace for ``C`` mixed queries of ``J`` terms and ``k`` hits each now (before a graph
+        capture: a capture must not allocate).  The workspace does not depend on ``J``: a query's terms always fill
+        one 16-column tile."""
+        if not 1 <= int(J) <= 16:
+            raise ValueError(f"mixed top-k supports 1 <= J <= 16 terms, got {J}")
+        self._counter(MixTopkScratch)
+        return self._resolve(MixTopkScratch, None, int(C), int(k))
+
+    def _mix_terms(self, terms) -> torch.Tensor:
+        """-> contiguous device ``[C, J, D]`` in the memory's dtype from ``[C, J, D]`` or ``[J, D]`` (one query)."""
+        if not isinstance(terms, torch.Tensor):
+            terms = torch.tensor(terms, dtype=torch.float32)
+        if terms.dim() == 2:
+            terms = terms.unsqueeze(0)
+        if terms.dim() != 3 or terms.shape[-1] != self.dim:
+            raise ValueError(f"terms must be [C, J, {self.dim}] or [J, {self.dim}], got {tuple(terms.shape)}")
+        if terms.shape[0] < 1:
+            raise ValueError("no mixed query")
+        if not 1 <= terms.shape[1] <= 16:
+            raise ValueError(f"mixed top-k supports 1 <= J <= 16 terms, got {terms.shape[1]}")
+        return terms.to(device=self.device, dtype=self.dtype).contiguous()
+
+    def _mix_weights(self, weights, Cn: int, J: int) -> torch.Tensor:
+        """-> contiguous device float64 ``[C, J]`` from a tensor, a nested list, or one list of J shared by all C."""
+        w = weights if isinstance(weights, torch.Tensor) else torch.tensor(weights, dtype=torch.float64)
+        if w.dim() == 1:
+            w = w.unsqueeze(0).expand(Cn, -1)
+        if tuple(w.shape) != (Cn, J):
+            raise ValueError(f"weights must be [{Cn}, {J}] or one list of {J}, got {tuple(w.shape)}")
+        return w.to(device=self.device, dtype=torch.float64).contiguous()
+
+    def topk_mix(self, terms, weights, k: int, mask=None, mask_index=None, min_score: Optional[float] = None,
+                 exact: bool = False, scratch: Optional[MixTopkScratch] = None, stride: Tuple[int, int] = (1, 0)
+                 ) -> Tuple[torch.Tensor, torch.Tensor]:
+        """-> (scores [C,k] float64, rows [C,k] int64): the k best rows by a WEIGHTED SUM OF COSINES, on any memory.
+        ``terms``: ``[C, J, D]`` (or ``[J, D]`` for one query), J <= 16 vectors per mixed query; ``weights``: a float64
+        tensor ``[C, J]``, a nested list, or one list of J shared by all C - positive, negative or zero.  The score of
+        row r is ``W = sum_j w_j * cos(term_j, r)``: the reference's fp64 cosines, summed left to right from 0.0 with one
+        rounding per product and per addition, so ``J = 1, w = 1`` is ``topk`` bit for bit and zero-weight terms change
+        nothing.  ``mask`` / ``mask_index``: as in ``topk_masked`` with one mask per mixed query, default every live
+        row; an exclusion is ``~mask_of_rows(rows_already_shown)``.
+
+        Ranked by (W desc, row id asc), the optional strict ``W > min_score`` filter on the raw sum (there is no score
+        mapping: W is not confined to [-1, 1]), -1 / 0.0 padded; ``stride``: the ``(row_stride, row_offset)`` of the
+        returned ids.  Always the exhaustive answer: the fp32 fast path redoes the queries it cannot certify on the
+        device, in the same call (csrc/topk_mix.hip).  ``exact=True`` scores every selected pair exactly (slow).  The
+        per-query flags of the last fast call are in ``last_mix_flags``.  ``scratch``: as in ``topk`` - a
+        ``MixTopkScratch`` the caller owns (a graph capture: pass ``terms``, ``weights`` and ``mask`` as device tensors
+        of their final dtype and rewrite them in place between replays), default this memory's own."""
+        if not 1 <= int(k) <= 64:
+            raise ValueError(f"mixed top-k supports 1 <= k <= 64, got {k}")
+        if min_score is not None and math.isnan(float(min_score)):
+            raise ValueError("min_score is NaN")
+        masks = self._masks(mask) if mask is not None else None
+        if masks is None and mask_index is not None:
+            raise ValueError("a mask_index needs a mask")
+        q = self._mix_terms(terms)
+        Cn, J, k = int(q.shape[0]), int(q.shape[1]), int(k)
+        w = self._mix_weights(weights, Cn, J)
+        idx = self._mask_index(mask_index, masks.shape[0], Cn) if masks is not None else None
+        s = self._resolve(MixTopkScratch, scratch, Cn, k)
+        scores = torch.empty((Cn, k), dtype=torch.float64, device=self.device)
+        rows = torch.empty((Cn, k), dtype=torch.int64, device=self.device)
+        head = (self.handle, _ptr(q), _ptr(w), Cn, J, k, _ptr(masks), 0 if masks is None else masks.shape[0], _ptr(idx),
+                *_min_score_args(min_score), int(stride[0]), int(stride[1]), _ptr(scores), _ptr(rows))
+        tail = (_ptr(s.ws), s.ws.numel(), _lib.current_stream_ptr())
+        if exact:
+            self.ctx.check(self.L.vm_topk_cosine_mix_exact(*head, *tail))
+        else:
+            self.ctx.check(self.L.vm_topk_cosine_mix(*head, _ptr(self._counter(MixTopkScratch)), _ptr(s.flags), *tail))
+        _keep_alive(q, w, masks, idx)
+        self._last[MixTopkScratch] = s
+        return scores, rows
+
     # ---- clip search (include/vidmem.h vm_topk_cosine_clip, DESIGN.md 20) -----------------------------------------
     def prepare_topk_clip(self, C: int, L: int, k: int) -> "ClipScratch":
         """Size this memory's own clip-search buffers for ``C`` clips of ``L`` frames and ``k`` hits each now (before a
@@ -1530,6 +1606,9 @@ class EmbeddingMemory:
     last_span_flags = _last_property(SpanTopkScratch, "flags", "int32 per query (vm_topk_flag): why the last fast "
                                      "`topk_span` call redid a query, 0 = certified")
     span_uncertified_count = _count_property(SpanTopkScratch, "Queries the span fast path")
+    last_mix_flags = _last_property(MixTopkScratch, "flags", "int32 per mixed query (vm_topk_flag): why the last fast "
+                                    "`topk_mix` call redid a query, 0 = certified")
+    mix_uncertified_count = _count_property(MixTopkScratch, "Mixed queries the mixed fast path")
     grouped_uncertified_count = _count_property(GroupedTopkScratch, "Queries the grouped fast path")
     scoped_uncertified_count = _count_property(ScopedTopkScratch, "Queries the scoped fast path")
     group_scoped_uncertified_count = _count_property(GroupedScopedTopkScratch, "Queries the scoped grouped fast path")

@@ -106,7 +106,7 @@ class TopkScratch(Scratch):
 
 
 class _ScanScratch(Scratch):
-    """The workspace and the per-query ``flags`` (int32 [Q]) of a grouped, scoped, masked or span top-k of up to (Q, k).  The
+    """The workspace and the per-query ``flags`` (int32 [Q]) of a grouped, scoped, masked, span or mixed top-k of up to (Q, k).  The
     uncertified counters of these searches are the memory's, whichever scratch a call used."""
 
     @staticmethod
@@ -128,6 +128,12 @@ class MaskedTopkScratch(_ScanScratch):
 
 class SpanTopkScratch(_ScanScratch):
     workspaces = (("ws", "vm_topk_span_workspace_bytes"),)
+
+
+class MixTopkScratch(_ScanScratch):
+    """The mixed-query top-k for up to ``C`` mixed queries (of up to 16 terms each) and ``k``."""
+
+    workspaces = (("ws", "vm_topk_mix_workspace_bytes"),)
 
 
 class GroupedScopedTopkScratch(_ScanScratch):

@@ -235,6 +235,53 @@ def clip_similarities(memory: EmbeddingMemory, chunks_of_frame_embeddings: Seque
     return out
 
 
+MIX_MAX_TERMS = 16   # terms of one mixed query (EmbeddingMemory.topk_mix)
+
+
+def feedback_terms(query, positives: Sequence = (), negatives: Sequence = (), alpha: float = 1.0, beta: float = 0.75,
+                   gamma: float = 0.15) -> Tuple[torch.Tensor, List[float]]:
+    """Rocchio relevance feedback as one mixed query -> ``(terms [J, D], weights [J])`` for ``EmbeddingMemory.topk_mix``
+    / ``mix_similarities``: the query with weight ``alpha``, each positive example with ``beta / len(positives)``, each
+    negative one with ``-gamma / len(negatives)``, in that order.  Where the textbook form adds the vectors and searches
+    with their sum, the mixed search ranks by the weighted sum of the COSINES: every example counts by its direction,
+    whatever its length, and the score is a defined fp64 value.  Vectors are ``[D]`` tensors or float sequences (stored
+    rows, hits of an earlier search, fresh embeddings).  Pure host code.  ``ValueError`` above 16 terms, for vectors of
+    different lengths and for a non-finite coefficient."""
+    positives, negatives = list(positives), list(negatives)
+    J = 1 + len(positives) + len(negatives)
+    if J > MIX_MAX_TERMS:
+        raise ValueError(f"feedback_terms: {J} terms, a mixed query holds at most {MIX_MAX_TERMS}")
+    for name, v in (("alpha", alpha), ("beta", beta), ("gamma", gamma)):
+        if not torch.isfinite(torch.tensor(float(v))):
+            raise ValueError(f"feedback_terms: {name} = {v} is not finite")
+    vecs = [v.detach().cpu() if isinstance(v, torch.Tensor) else torch.tensor([float(x) for x in v], dtype=torch.float32)
+            for v in [query, *positives, *negatives]]
+    for i, v in enumerate(vecs):
+        if v.dim() != 1 or v.shape != vecs[0].shape:
+            raise ValueError(f"feedback_terms: term {i} has shape {tuple(v.shape)}, the query {tuple(vecs[0].shape)}")
+    if len({v.dtype for v in vecs}) > 1:
+        vecs = [v.to(torch.float32) for v in vecs]
+    weights = [float(alpha)] + [float(beta) / len(positives) for _ in positives] \
+        + [-float(gamma) / len(negatives) for _ in negatives]
+    return torch.stack(vecs), weights
+
+
+def mix_similarities(memory: EmbeddingMemory, terms, weights, top_k: int, mask=None,
+                     min_score: Optional[float] = None) -> List[List[Tuple[str, float]]]:
+    """``EmbeddingMemory.topk_mix`` in the reference's list shape (src/components/pre_llm_injector.py:346-372), as
+    ``clip_similarities`` returns it: per mixed query ``[(id, score), ...]``, ``id = memory.id_of(row)``, the score the
+    weighted sum of cosines; ``merge_batch_similarities`` consumes it unchanged.  ``terms``: ``[C, J, D]`` or ``[J, D]``
+    (one query), ``weights``: ``[C, J]`` or one list of J (``feedback_terms`` returns a matching pair); ``mask``: one row
+    mask for every query or one per query - ``~memory.mask_of_rows(rows_already_shown)`` keeps earlier hits out."""
+    t = terms if isinstance(terms, torch.Tensor) else torch.tensor(terms, dtype=torch.float32)
+    n = 1 if t.dim() == 2 else int(t.shape[0])
+    if memory.searchable == 0 or top_k <= 0:
+        return [[] for _ in range(n)]
+    scores, rows = memory.topk_mix(t, weights, top_k, mask=mask, min_score=min_score)
+    return [[(memory.id_of(r), float(s)) for r, s in zip(rr, ss) if r >= 0]
+            for rr, ss in zip(rows.cpu().tolist(), scores.cpu().tolist())]
+
+
 class HipPreLLMSimilarity:
     """Mixin / stand-alone object for PreLLMInjector: set ``self.memory`` and ``self.embedder_config``."""
 
