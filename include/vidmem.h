@@ -637,6 +637,51 @@ int vm_topk_cosine_mix_exact(vm_memory *mem, const void *terms, const double *we
                              const uint32_t *masks, int n_masks, const int32_t *mask_index, int use_min_score,
                              double min_score, int64_t row_stride, int64_t row_offset, double *out_scores,
                              int64_t *out_rows, void *workspace, size_t workspace_bytes, void *stream);
+/* Diverse top-k: maximal marginal relevance (MMR).  The k answers of a query are picked one after another from a POOL of
+ * its best rows, and each pick pays for its resemblance to the rows picked before it, so that near-identical frames - a
+ * static camera, a replayed scene, one shot in two uploads - do not fill the k places.
+ * queries: [Q, D] in the memory's dtype; 1 <= k <= pool <= 64; lam: device fp64 [Q] (on the device, like weights, scopes
+ * and spans: a captured graph replays with rewritten values).  masks: NULL = every live row (n_masks and mask_index are
+ * then ignored); otherwise masks, n_masks and mask_index mean exactly what they mean in vm_topk_cosine_masked.
+ * The pool of query q: the exhaustive ranking of vm_topk_cosine over the live rows the mask selects, those with
+ * e > min_score kept when use_min_score != 0 (strict, on the raw cosine; there is no score mode), first `pool` entries:
+ * rows r_0 .. r_{np-1}, np <= pool, e_i the raw reference cosine bit for bit, ordered (e descending, row id ascending).
+ * The greedy pick, in fp64 with one rounding per operation, never fused:  mu = 1.0 - lam;  sim(i, j) = the reference
+ * cosine BETWEEN stored rows r_i and r_j (the dot of vm_topk_cosine's arithmetic over the two rows, divided by the product
+ * of their stored fp64 norms; 0.0 when either norm is 0), which is symmetric bit for bit.  Step 0 takes r_0, with
+ * red = 0.0.  At step t >= 1 every unpicked i has red_i = the maximum (plain >, from 0.0) of sim(i, s) over the picked s
+ * and the value  v_i = (lam * e_i) - (mu * red_i);  the largest v_i wins, ties - -0.0 against +0.0 included - go to the
+ * smaller row id.  min(k, np) picks are made.
+ * Outputs, in pick order: out_rows [Q,k] global row ids (row_id * row_stride + row_offset), out_scores [Q,k] the
+ * relevance e of each pick, out_mmr [Q,k] the v at which it was picked (step 0: (lam * e_0) - (mu * 0.0)); -1 / 0.0 / 0.0
+ * padded.  Consequences: lam = 1.0 gives the rows and scores of vm_topk_cosine (or _masked), first k, bit for bit,
+ * whatever the pool; pool == k only reorders the top k; the result of a query depends on the memory, its own query, lam
+ * and mask and the arguments only, not on the other queries of the call.  A finite lam outside [0, 1] is still defined by
+ * the formula; a non-finite lam is undefined, as stored NaN is.
+ * The pool stage IS vm_topk_cosine_masked (or, without masks, vm_topk_cosine_span with the open span) with k = pool:
+ * always the exhaustive answer, its uncertified queries counted in *out_uncertified (may be NULL), marked in
+ * out_query_flags [Q] (vm_topk_flag; may be NULL) and redone inside the call.  Then one kernel scores the pool's pairs
+ * and one wave per query picks.  Any memory: plain, grouped, tagged, ring.  No host read-back, no allocation, no
+ * synchronisation: capturable; a replay sees lam, queries and masks rewritten in place and the rows appended since.
+ * VM_ERR_INVALID (with a vm_last_error text) for k or pool outside [1, 64], k > pool, Q < 1, NULL queries, lam or
+ * outputs (all three are required), row_stride < 1, masks that are not 4-byte aligned or whose count fits no rule of the
+ * masked search, misaligned workspace (256 bytes), queries (16) or lam (8); VM_ERR_NOMEM for a workspace below
+ * vm_topk_diverse_workspace_bytes; VM_ERR_UNSUPPORTED above 2^30 words of masks or D > 5,120.  All before any launch,
+ * with the outputs untouched.
+ * Workspace: vm_topk_diverse_workspace_bytes(mem, Q, pool) (the masked search's for k = pool, plus 32 KiB x Q of pair
+ * cosines and the pool); 0 for arguments out of range. */
+size_t vm_topk_diverse_workspace_bytes(const vm_memory *mem, int Q, int pool);
+int vm_topk_cosine_diverse(vm_memory *mem, const void *queries, int Q, int k, int pool, const double *lam,
+                           const uint32_t *masks, int n_masks, const int32_t *mask_index, int use_min_score,
+                           double min_score, int64_t row_stride, int64_t row_offset, double *out_scores,
+                           int64_t *out_rows, double *out_mmr, int32_t *out_uncertified, int32_t *out_query_flags,
+                           void *workspace, size_t workspace_bytes, void *stream);
+/* The same contract with the exhaustive-only pool: every selected pair scored exactly (slow; tests, and a checker). */
+int vm_topk_cosine_diverse_exact(vm_memory *mem, const void *queries, int Q, int k, int pool, const double *lam,
+                                 const uint32_t *masks, int n_masks, const int32_t *mask_index, int use_min_score,
+                                 double min_score, int64_t row_stride, int64_t row_offset, double *out_scores,
+                                 int64_t *out_rows, double *out_mmr, void *workspace, size_t workspace_bytes,
+                                 void *stream);
 /* Scoped grouped top-k: the k best GROUPS of a tagged AND grouped memory among the rows IN SCOPE - "the k best scenes of
  * video 7 between minute 10 and minute 20".  scope_lo / scope_hi: device int64 [Q], both required, inclusive tag ranges
  * by vm_topk_cosine_scoped's rule (row r is in query q's scope iff scope_lo[q] <= tag[r] <= scope_hi[q]).

@@ -40,8 +40,8 @@ from typing import List, NamedTuple, Optional, Sequence, Tuple
 import torch
 
 from . import _lib
-from .scratch import (NOVEL_MAX_ROWS, ClipScratch, EraseScratch, EventsScratch, GroupedScopedTopkScratch,  # noqa: F401
-                      GroupedTopkScratch, MaskedTopkScratch, MixTopkScratch, NoveltyScratch, RangeScratch,
+from .scratch import (NOVEL_MAX_ROWS, ClipScratch, DiverseTopkScratch, EraseScratch, EventsScratch,  # noqa: F401
+                      GroupedScopedTopkScratch, GroupedTopkScratch, MaskedTopkScratch, MixTopkScratch, NoveltyScratch, RangeScratch,
                       ScopedTopkScratch, Scratch, SpanTopkScratch, SummaryScratch, TopkScratch)
 
 
@@ -1225,6 +1225,102 @@ class EmbeddingMemory:
         self._last[MixTopkScratch] = s
         return scores, rows
 
+    # ---- diverse search (include/vidmem.h vm_topk_cosine_diverse) ------------------------------------
+    @staticmethod
+    def _diverse_pool(k, pool) -> Tuple[int, int]:
+        """-> (k, pool) of a diverse call, the default pool ``min(64, max(k, 4 k))`` filled in; refused when they are not
+        ``1 <= k <= pool <= 64``."""
+        k = int(k)
+        pool = min(64, max(k, 4 * k)) if pool is None else int(pool)
+        if not 1 <= k <= 64:
+            raise ValueError(f"diverse top-k supports 1 <= k <= 64, got {k}")
+        if pool > 64:
+            raise ValueError(f"diverse top-k supports pool <= 64, got {pool}")
+        if k > pool:
+            raise ValueError(f"diverse top-k needs k <= pool, got k={k}, pool={pool}")
+        return k, pool
+
+    def prepare_topk_diverse(self, Q: int, k: int, pool: Optional[int] = None) -> DiverseTopkScratch:
+        """Size the diverse top-k workspace for ``Q`` queries, ``k`` picks and a pool of ``pool`` rows each now (before a
+        graph capture: a capture must not allocate).  The workspace depends on ``Q`` and ``pool`` only."""
+        k, pool = self._diverse_pool(k, pool)
+        self._counter(DiverseTopkScratch)
+        return self._resolve(DiverseTopkScratch, None, int(Q), pool)
+
+    def _diverse_lam(self, lam, Q: int) -> torch.Tensor:
+        """-> contiguous device float64 ``[Q]``.  A device float64 tensor passes through unread (a captured call sees it
+        rewritten in place); a float or Q floats are checked to lie in [0, 1] here."""
+        if isinstance(lam, torch.Tensor) and lam.is_cuda:
+            if lam.dtype != torch.float64 or tuple(lam.shape) != (Q,):
+                raise ValueError(f"a device lam must be float64 [{Q}], got {lam.dtype} {tuple(lam.shape)}")
+            return lam.to(self.device).contiguous()
+        vals = lam.tolist() if isinstance(lam, torch.Tensor) else lam
+        vals = [float(v) for v in vals] if hasattr(vals, "__len__") else [float(vals)] * Q
+        if len(vals) != Q:
+            raise ValueError(f"{len(vals)} values of lam for {Q} queries")
+        for v in vals:
+            if not 0.0 <= v <= 1.0:     # NaN included
+                raise ValueError(f"lam must lie in [0, 1], got {v}")
+        return torch.tensor(vals, dtype=torch.float64).to(self.device)
+
+    def topk_diverse(self, queries, k: int, pool: Optional[int] = None, lam=0.5, mask=None, mask_index=None,
+                     min_score: Optional[float] = None, exact: bool = False,
+                     scratch: Optional[DiverseTopkScratch] = None, stride: Tuple[int, int] = (1, 0)
+                     ) -> Tuple[torch.Tensor, torch.Tensor]:
+        """-> (scores [Q,k] float64, rows [Q,k] int64): k DIVERSE hits per query by maximal marginal relevance, on any
+        memory.  The pool is the query's ``pool`` best rows (``topk``'s ranking over the rows ``mask`` selects, strict
+        ``> min_score`` on the raw cosine; default ``pool = min(64, max(k, 4 k))``).  The first pick is the best row; each
+        later pick is the unpicked pool row with the largest ``lam * e - (1 - lam) * max sim(row, picked)``, ``e`` its
+        cosine with the query and ``sim`` the reference cosine between two STORED rows, every operation rounded once in
+        fp64, ties to the smaller row id (include/vidmem.h).  ``lam = 1`` is ``topk`` / ``topk_masked`` bit for bit,
+        ``lam = 0`` cares for spread alone after the first pick.  Rows come in PICK order with their relevance ``e`` as
+        score, -1 / 0.0 padded; the value each was picked at is in ``last_diverse_mmr``.
+
+        ``lam``: a float, Q floats, or a device float64 ``[Q]`` tensor, which is passed through unread.  A host value
+        outside [0, 1], ``k > pool`` or ``pool > 64`` raises ``ValueError`` before the library is called.  ``mask`` /
+        ``mask_index``: as in ``topk_masked``, default every live row.  ``stride``: the ``(row_stride, row_offset)`` of the
+        returned ids.  The pool is always the exhaustive answer (its fast path redoes what it cannot certify on the
+        device; ``last_diverse_flags``, ``diverse_uncertified_count``); ``exact=True`` scores every selected pair exactly
+        (slow).  ``scratch``: as in ``topk`` - a ``DiverseTopkScratch`` the caller owns (a graph capture: pass
+        ``queries``, ``lam`` and ``mask`` as device tensors of their final dtype and rewrite them in place between
+        replays), default this memory's own."""
+        k, pool = self._diverse_pool(k, pool)
+        if min_score is not None and math.isnan(float(min_score)):
+            raise ValueError("min_score is NaN")
+        masks = self._masks(mask) if mask is not None else None
+        if masks is None and mask_index is not None:
+            raise ValueError("a mask_index needs a mask")
+        q = self._as_rows(queries)
+        Q = int(q.shape[0])
+        lm = self._diverse_lam(lam, Q)
+        idx = self._mask_index(mask_index, masks.shape[0], Q) if masks is not None else None
+        s = self._resolve(DiverseTopkScratch, scratch, Q, pool)
+        scores = torch.empty((Q, k), dtype=torch.float64, device=self.device)
+        rows = torch.empty((Q, k), dtype=torch.int64, device=self.device)
+        head = (self.handle, _ptr(q), Q, k, pool, _ptr(lm), _ptr(masks), 0 if masks is None else masks.shape[0],
+                _ptr(idx), *_min_score_args(min_score), int(stride[0]), int(stride[1]), _ptr(scores), _ptr(rows),
+                _ptr(s.mmr))
+        tail = (_ptr(s.ws), s.ws.numel(), _lib.current_stream_ptr())
+        if exact:
+            self.ctx.check(self.L.vm_topk_cosine_diverse_exact(*head, *tail))
+        else:
+            self.ctx.check(self.L.vm_topk_cosine_diverse(*head, _ptr(self._counter(DiverseTopkScratch)), _ptr(s.flags),
+                                                         *tail))
+        _keep_alive(q, lm, masks, idx)
+        self._last[DiverseTopkScratch] = s
+        self._last_diverse_shape = (Q, k)
+        return scores, rows
+
+    @property
+    def last_diverse_mmr(self) -> Optional[torch.Tensor]:
+        """float64 ``[Q, k]``: the value ``lam * e - (1 - lam) * red`` at which each row of the last ``topk_diverse``
+        call was picked, 0.0 padded (a view of the scratch that call used; ``None`` before the first call)."""
+        s = self._last.get(DiverseTopkScratch)
+        if s is None:
+            return None
+        Q, k = self._last_diverse_shape
+        return s.mmr[:Q * k].view(Q, k)
+
     # ---- clip search (include/vidmem.h vm_topk_cosine_clip, DESIGN.md 20) -----------------------------------------
     def prepare_topk_clip(self, C: int, L: int, k: int) -> "ClipScratch":
         """Size this memory's own clip-search buffers for ``C`` clips of ``L`` frames and ``k`` hits each now (before a
@@ -1609,6 +1705,9 @@ class EmbeddingMemory:
     last_mix_flags = _last_property(MixTopkScratch, "flags", "int32 per mixed query (vm_topk_flag): why the last fast "
                                     "`topk_mix` call redid a query, 0 = certified")
     mix_uncertified_count = _count_property(MixTopkScratch, "Mixed queries the mixed fast path")
+    last_diverse_flags = _last_property(DiverseTopkScratch, "flags", "int32 per query (vm_topk_flag): why the pool stage "
+                                        "of the last fast `topk_diverse` call redid a query, 0 = certified")
+    diverse_uncertified_count = _count_property(DiverseTopkScratch, "Queries the diverse search's pool stage")
     grouped_uncertified_count = _count_property(GroupedTopkScratch, "Queries the grouped fast path")
     scoped_uncertified_count = _count_property(ScopedTopkScratch, "Queries the scoped fast path")
     group_scoped_uncertified_count = _count_property(GroupedScopedTopkScratch, "Queries the scoped grouped fast path")

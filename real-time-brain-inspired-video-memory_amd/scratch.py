@@ -106,7 +106,7 @@ class TopkScratch(Scratch):
 
 
 class _ScanScratch(Scratch):
-    """The workspace and the per-query ``flags`` (int32 [Q]) of a grouped, scoped, masked, span or mixed top-k of up to (Q, k).  The
+    """The workspace and the per-query ``flags`` (int32 [Q]) of a grouped, scoped, masked, span, mixed or diverse top-k of up to (Q, k).  The
     uncertified counters of these searches are the memory's, whichever scratch a call used."""
 
     @staticmethod
@@ -134,6 +134,17 @@ class MixTopkScratch(_ScanScratch):
     """The mixed-query top-k for up to ``C`` mixed queries (of up to 16 terms each) and ``k``."""
 
     workspaces = (("ws", "vm_topk_mix_workspace_bytes"),)
+
+
+class DiverseTopkScratch(_ScanScratch):
+    """The diverse (MMR) top-k for up to ``Q`` queries and a pool of ``pool`` rows each; also ``mmr`` (float64
+    [Q x pool]): the value at which each row of the last call was picked."""
+
+    workspaces = (("ws", "vm_topk_diverse_workspace_bytes"),)
+
+    @staticmethod
+    def _buffers(Q, pool):
+        return (("flags", torch.int32, _rows(Q), 0), ("mmr", torch.float64, _rows(Q * pool), 0.0))
 
 
 class GroupedScopedTopkScratch(_ScanScratch):

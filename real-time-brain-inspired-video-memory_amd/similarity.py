@@ -282,6 +282,21 @@ def mix_similarities(memory: EmbeddingMemory, terms, weights, top_k: int, mask=N
             for rr, ss in zip(rows.cpu().tolist(), scores.cpu().tolist())]
 
 
+def diverse_similarities(memory: EmbeddingMemory, queries, top_k: int, pool: Optional[int] = None, lam=0.5, mask=None,
+                         min_score: Optional[float] = None) -> List[List[Tuple[str, float]]]:
+    """``EmbeddingMemory.topk_diverse`` in the reference's list shape, as ``mix_similarities`` returns it: per query
+    ``[(id, score), ...]`` in PICK order, ``id = memory.id_of(row)``, the score the row's cosine with the query.  What a
+    vector store calls ``max_marginal_relevance_search(k, fetch_k, lambda_mult)``: ``top_k`` context slots that are not
+    spent on near-identical frames.  ``mask``: one row mask for every query or one per query."""
+    q = queries if isinstance(queries, torch.Tensor) else torch.tensor(queries, dtype=torch.float32)
+    n = 1 if q.dim() == 1 else int(q.shape[0])
+    if memory.searchable == 0 or top_k <= 0:
+        return [[] for _ in range(n)]
+    scores, rows = memory.topk_diverse(q, top_k, pool=pool, lam=lam, mask=mask, min_score=min_score)
+    return [[(memory.id_of(r), float(s)) for r, s in zip(rr, ss) if r >= 0]
+            for rr, ss in zip(rows.cpu().tolist(), scores.cpu().tolist())]
+
+
 class HipPreLLMSimilarity:
     """Mixin / stand-alone object for PreLLMInjector: set ``self.memory`` and ``self.embedder_config``."""
 
