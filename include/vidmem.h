@@ -511,7 +511,9 @@ int vm_topk_cosine_scoped_exact(vm_memory *mem, const void *queries, int Q, int 
  * words (the capacity rounded up to 64 rows, / 32); several masks lie back to back, [n_masks][W].  The bit of row id r is
  * bit s & 31 of word s >> 5 with s = r mod capacity: in a linear memory s = r, in a ring the physical slot the row lives
  * in.  A bit whose slot holds no live row (past the row count, the padding, all of an empty memory) is ignored by every
- * consumer, so ~mask is meaningful and safe; masks combine with & | ~ on the caller's side.  A mask is a statement about
+ * consumer, so ~mask is meaningful and safe; masks combine with & | ~ on the caller's side.  That holds after
+ * vm_memory_reset and after an erase as well, whatever the slots past the live count still hold (a reset leaves the
+ * columns as they are): only the row count decides which bits count.  A mask is a statement about
  * ROW IDS: an erase renumbers rows and a ring overwrites them, after which a mask is stale exactly as a stored row id
  * is (the bit then names whichever row lives in the slot); nothing remaps it.
  * vm_topk_cosine_masked: masks [n_masks][W]; mask_index: device int32 [Q], the mask each query uses, or NULL: mask 0

@@ -2,14 +2,21 @@
 
 Every feature of the memory has its own oracle; this file composes them into ONE model that is carried through a whole
 life - keyed, tagged and gated appends, erases, whole and tail regroups, the ring overwrite, reset, snapshot / restore -
-and says after every step what all nine readers must return (torch only where the existing data generators use it,
-``pool`` and ``noisy``).  It defines no cosine and no ranking of its own: every
+and says after every step what all fourteen readers must return (torch only where the existing data generators use it,
+``pool`` and ``noisy``).  The readers: ``topk``, ``topk_grouped``, ``topk_scoped``, ``topk_grouped_scoped``, ``topk_clip``,
+``range_search``, ``events``, ``summaries``, each top-k one with an exact form, and the five whose operands speak about row
+ids and slots - ``topk_masked``, ``topk_span``, ``topk_mix``, ``topk_diverse`` (with ``last_diverse_mmr``) and
+``recall_links`` - fed by the mask builders ``mask_of_rows``, ``mask_of_scope``, ``mask_where`` and read back through
+``rows_of_mask``.  It defines no cosine and no ranking of its own: every
 mutator restates the header's rule by calling the oracle that already states it (novelty_ref.gate, erase_ref.erase,
-events_ref.regroup / regroup_tail), every expectation is the feature's own oracle over the live window.
+events_ref.regroup / regroup_tail), every expectation is the feature's own oracle over the live window (mask_ref,
+span_ref, mix_ref and diverse_ref for the five newer readers).
 
 ``Model``       the state, in row-id order, and the mutators.
 ``checkpoint``  compares an ``EmbeddingMemory`` (or anything with its surface) with the model through the public
-                accessors and all nine readers, each top-k reader in its default and its ``exact`` form; bit equality.
+                accessors and all fourteen readers, each top-k reader in its default and its ``exact`` form; bit equality.
+                Where a feature's own oracle condition says that the fast path must certify a query of the masked, span,
+                mixed or diverse search, its flag of the default call must be 0: the redo may not hide a broken scan.
 ``Driver``      applies one step to the model and to the memory, compares what the step returns, builds the probes.
 ``linear_script`` / ``ring_script``  the two lives of tests/test_lifecycle_gpu.py; tests/test_lifecycle_cpu.py runs the
                 same scripts against a fake memory, proves the conditions they must meet and plants defects.
@@ -23,13 +30,17 @@ import numpy as np
 
 from oracle import cref
 from tests import clip_ref as CL
+from tests import diverse_ref as DR
 from tests import erase_ref as E
 from tests import events_ref as V
 from tests import group_ref as G
 from tests import group_scope_ref as GS
+from tests import mask_ref as MR
+from tests import mix_ref as XR
 from tests import novelty_ref as N
 from tests import range_ref as R
 from tests import scope_ref as S
+from tests import span_ref as SP
 from tests import summary_ref as M
 
 INT64_MIN, INT64_MAX = -(1 << 63), (1 << 63) - 1
@@ -41,6 +52,13 @@ MAX_HITS = 64
 THRESHOLD, GAP_MS = 0.5, 2000  # the events / regroup arguments of both scripts
 DIMS = {"f16": 128, "bf16": 256}
 VM_ERR_UNSUPPORTED = -4                # include/vidmem.h vm_status
+MASK_INDEX = (0, 1, 2, 3, 4, -1)       # the mask of each probe query: (a) .. (d), the carried exclusion, -1 = the empty mask
+MASK_INDEX2 = (5, 4, -1, 2, 1, 3)      # a second masked search: the carried complement, every query under another mask
+WEIGHTS = [[1.0, 0.0, 0.0]] + [[1.0, 0.5, -0.25]] * 5         # the mixed queries: C = 6, J = 3
+POOL, LAM = 16, (1.0, 0.5, 0.5, 0.3, 0.7, 0.0)                # the diverse search: k = 5 of a pool of 16
+LINK_ROWS, LINK_K, LINK_GAP, LINK_BLOCK = 300, 3, 2, 128      # recall links of the newest 300 rows: pages of 128, 128, 44
+LINK_CALLS = ((None, True), (200, False))                     # (max_back, exclude_group)
+DOMAIN = (2.0 ** -40, 2.0 ** 40)       # the norms inside which the fp32 stage's bound holds (include/vidmem.h)
 
 
 def make_tag(source, ms):
@@ -61,6 +79,12 @@ class Probes(NamedTuple):
     scopes: list           # six (lo, hi)
     clips: list            # uint16 [1, L, D] each
     range_min: float
+    mask_scopes: list      # mask (b): two tag ranges, one source and a window, in one mask_of_scope call
+    carried: tuple         # the model's words of the previous checkpoint's exclusion mask and of its complement, or None
+    spans: list            # six (lo, hi) in row ids, None = open
+    carried_span: tuple    # (lo + 10, total - 10) of the previous checkpoint, or None
+    terms: np.ndarray      # uint16 [6, 3, D]: the mixed queries
+    links: tuple           # (first_row, n_rows) of the recall links
     k: int = K
     max_hits: int = MAX_HITS
     threshold: float = THRESHOLD
@@ -70,10 +94,14 @@ class Probes(NamedTuple):
 class Model:
     """Rows, tags, keys, ordinals, ids and provenance of every row appended since the last reset or erase renumbering,
     in row-id order; ``state`` = (groups opened, last key, open); ``used`` = slots a linear memory has written since the
-    last reset (an erase zeroes what it vacates, a reset promises nothing about the columns)."""
+    last reset (an erase zeroes what it vacates, a reset promises nothing about the columns); ``written`` = slots written
+    since the memory was created, which a reset does not forget: what may still lie under a mask bit or inside a span;
+    ``outside`` = the sticky word of vm_memory_create: a row whose norm is neither 0 nor in [2^-40, 2^40] was appended
+    since the last reset, so every search is answered by the exhaustive redo."""
 
     def __init__(self, D, dtype, capacity, ring=False):
         self.D, self.dtype, self.capacity, self.ring = int(D), dtype, int(capacity), bool(ring)
+        self.written = 0
         self.reset()
 
     # ---- state ---------------------------------------------------------------------------------------------------
@@ -86,6 +114,7 @@ class Model:
         self.ids = []
         self.state = (0, 0, 0)
         self.used = 0
+        self.outside = False
 
     @property
     def total(self):
@@ -127,6 +156,8 @@ class Model:
         self.state = (groups + int(flags.sum()), int(keys[-1]), 1)
         if not self.ring:
             self.used = max(self.used, self.total)
+        self.written = max(self.written, min(self.total, self.capacity))
+        self.outside = self.outside or not in_domain(rows, self.dtype).all()
         return first
 
     def known(self, batch):
@@ -240,13 +271,111 @@ class Model:
         lo, live = self.window()
         return M.summarize(live.rows, live.keys, self.dtype, lo)
 
+    def exp_masked(self, q, sel, k):
+        lo, live = self.window()
+        return MR.masked_topk(q, live.rows, sel, k, dtype=self.dtype, base=lo)
+
+    def exp_span(self, q, spans, k):
+        lo, live = self.window()
+        return SP.span_topk(q, live.rows, spans, k, dtype=self.dtype, base=lo)
+
+    def exp_mix(self, terms, weights, sel, k):
+        lo, live = self.window()
+        return XR.mix_topk(terms, weights, live.rows, sel, k, dtype=self.dtype, base=lo)
+
+    def exp_diverse(self, q, sel, k, pool, lam):
+        lo, live = self.window()
+        return DR.diverse_topk(q, live.rows, sel, k, pool, list(lam), dtype=self.dtype, base=lo)
+
+    def exp_links(self, first, count, k, min_gap, max_back, exclude_group):
+        """span_ref.links_ref wants ``group_of`` as the group of every live row in row order, indexed by r - base, and
+        only compares neighbours: the model's ordinals as they are, a cut first group included."""
+        lo, live = self.window()
+        return _links(live.rows.tobytes(), live.ords.tobytes() if exclude_group else None, self.D, self.dtype, lo, k, first,
+                      count, min_gap, max_back)
+
+    def mask_selections(self, p: Probes, shown):
+        """bool [6, n]: what the six masks of a checkpoint select among the live rows, from the model alone.  (a) all
+        ones: every live row; (b) mask_of_scope: by the tags; (c) ~mask_of_rows(shown): the live rows that are not in
+        ``shown``; (d) mask_where: by the ids; (e) the carried exclusion mask and its complement: the header's staleness
+        rule - the bit names whichever row lives in the slot now (mask_ref.selected of the old words)."""
+        lo, live = self.window()
+        n = live.rows.shape[0]
+        ids = lo + np.arange(n, dtype=np.int64)
+        shown = np.asarray(shown, np.int64)
+        sels = [np.ones(n, bool), E.mask_of_scopes(live.tags, p.mask_scopes).astype(bool).reshape(n),
+                ~np.isin(ids, shown[shown >= 0]),
+                np.array([where(lo + i, name, {"i": name}) for i, name in enumerate(live.ids)], bool).reshape(n)]
+        for words in p.carried or (None, None):
+            sels.append(np.zeros(n, bool) if words is None else MR.selected(words, lo, n, self.capacity))
+        return np.stack(sels)
+
     def expect(self, p: Probes):
-        return {"topk": self.exp_topk(p.queries, p.k), "grouped": self.exp_grouped(p.queries, p.k),
-                "scoped": self.exp_scoped(p.queries, p.scopes, p.k),
-                "grouped_scoped": self.exp_grouped_scoped(p.queries, p.scopes, p.k),
-                "clip": [self.exp_clip(c, p.k) for c in p.clips],
-                "range": self.exp_range(p.queries, p.range_min, p.scopes),
-                "events": self.exp_events(p.threshold, p.gap_ms), "summaries": self.exp_summaries()}
+        lo, live = self.window()
+        n = live.rows.shape[0]
+        q, k = p.queries, p.k
+        exp = {"topk": self.exp_topk(q, k), "grouped": self.exp_grouped(q, k),
+               "scoped": self.exp_scoped(q, p.scopes, k),
+               "grouped_scoped": self.exp_grouped_scoped(q, p.scopes, k),
+               "clip": [self.exp_clip(c, k) for c in p.clips],
+               "range": self.exp_range(q, p.range_min, p.scopes),
+               "events": self.exp_events(p.threshold, p.gap_ms), "summaries": self.exp_summaries()}
+        sels = self.mask_selections(p, exp["topk"][0])
+        pick = lambda index: np.stack([sels[i] if 0 <= i < len(sels) else np.zeros(n, bool) for i in index])
+        sel, sel2 = pick(MASK_INDEX), pick(MASK_INDEX2)
+        span_sets = {"span": p.spans}
+        if p.carried_span is not None:
+            span_sets["span_carried"] = [p.carried_span] * 6
+        exp["mask_rows"] = [lo + np.nonzero(s)[0] for s in sels]
+        exp["sel"] = sel
+        exp["masked"], exp["masked2"] = self.exp_masked(q, sel, k), self.exp_masked(q, sel2, k)
+        for name, spans in span_sets.items():
+            exp[name] = self.exp_span(q, spans, k)
+        exp["mix"], exp["mix_masked"] = self.exp_mix(p.terms, WEIGHTS, None, k), self.exp_mix(p.terms, WEIGHTS, sel, k)
+        exp["diverse"] = self.exp_diverse(q, sel, k, POOL, LAM)
+        exp["links"] = [self.exp_links(*p.links, LINK_K, LINK_GAP, back, own) for back, own in LINK_CALLS]
+        # where the fast path must certify: each feature's own condition, on the oracle's scores (never on the device's)
+        must = {name: [False] * 6 for name in ("masked", "masked2", "mix", "mix_masked", "diverse", *span_sets)}
+        if n and not self.outside:
+            sc = cref.cosine_matrix(np.ascontiguousarray(q), np.ascontiguousarray(live.rows), dtype=self.dtype)
+            e = cref.cosine_matrix(np.ascontiguousarray(p.terms.reshape(-1, self.D)), np.ascontiguousarray(live.rows),
+                                   dtype=self.dtype).reshape(6, -1, n)
+            W = np.stack([XR.mix_scores(e[c], WEIGHTS[c]) for c in range(6)])
+            best = lambda scores, s: np.sort(scores[s])[::-1]
+            q_in = in_domain(q, self.dtype)
+            t_in = in_domain(p.terms.reshape(-1, self.D), self.dtype).reshape(6, -1).all(axis=1)
+            spans_sel = {name: SP.selection(spans, 6, lo, n) for name, spans in span_sets.items()}
+            for i in range(6):
+                for name, s in (("masked", sel), ("masked2", sel2), *spans_sel.items()):   # mask_ref.gap_ok at any k
+                    must[name][i] = bool(q_in[i] and s[i].any() and SP.gap_ok(best(sc[i], s[i]), self.D, k))
+                must["diverse"][i] = bool(q_in[i] and sel[i].any() and DR.flag0_ok(best(sc[i], sel[i]), POOL, self.D))
+                for name, s in (("mix", np.ones(n, bool)), ("mix_masked", sel[i])):
+                    must[name][i] = bool(t_in[i] and s.any() and XR.flag0_ok(best(W[i], s), k, self.D, XR.abs_sum(WEIGHTS[i])))
+        exp["must_certify"] = must
+        return exp
+
+
+@functools.lru_cache(maxsize=8)
+def _links(rows, ords, D, dtype, lo, k, first, count, min_gap, max_back):
+    """span_ref.links_ref, a pure function of the window's bytes: 300 restricted rankings, computed once for the model and
+    for whoever answers from an equal model (tests/test_lifecycle_cpu.py's fake)."""
+    out = SP.links_ref(np.frombuffer(rows, np.uint16).reshape(-1, D), lo, k, first=first, count=count, min_gap=min_gap,
+                       max_back=max_back, group_of=None if ords is None else np.frombuffer(ords, np.int64), dtype=dtype)
+    for a in out:
+        a.setflags(write=False)
+    return out
+
+
+def where(row, id, meta):
+    """The ``mask_where`` predicate of the probes, over the id string and ``meta["i"]``: the provenance index parsed
+    from the id (``s<batch>_p<index>``) is odd, and the metadata is that row's own."""
+    return meta["i"] == id and int(id.rsplit("_p", 1)[1]) % 2 == 1
+
+
+def in_domain(bits, dtype):
+    """bool per row: the norm is 0 or lies in the certificate's domain."""
+    nrm = np.linalg.norm(CL.from_bits(np.ascontiguousarray(bits), dtype).astype(np.float64), axis=-1)
+    return (nrm == 0) | ((nrm >= DOMAIN[0]) & (nrm <= DOMAIN[1]))
 
 
 # ---- checkpoint --------------------------------------------------------------------------------------------------------
@@ -265,14 +394,48 @@ def _same(got, want, what):
 
 
 UNCERT = ("uncertified_count", "grouped_uncertified_count", "scoped_uncertified_count",
-          "group_scoped_uncertified_count", "clip_uncertified_count")
+          "group_scoped_uncertified_count", "clip_uncertified_count", "masked_uncertified_count", "span_uncertified_count",
+          "mix_uncertified_count", "diverse_uncertified_count")
 
 
-def checkpoint(mem, model: Model, p: Probes, io, exp=None, label=""):
-    """``mem`` against ``model``: the accessors, then the nine readers; -> the ``*_uncertified_count`` of every reader.
-    ``io`` carries what is not part of the memory's surface: ``t(bits)`` (bit patterns -> what the memory takes as
-    rows), ``ordinals(mem)`` (the ordinal column of the live rows in row-id order, vm_memory_group_ordinals) and
-    ``raw(mem, n)`` (rows, tags, keys, ordinals over slots [0, n) in slot order)."""
+def _pair(got_s, got_r, want, what):
+    """One (scores, rows) answer against the oracle's (rows, scores)."""
+    _same(got_r, want[0], what + " rows")
+    assert _bits_equal(got_s, want[1]), what + " scores (bit-exact bar)"
+
+
+def _certified(flags, must, what):
+    """The flag-0 demand: the fast path may not leave to the redo a query that its own oracle condition says it must
+    certify (the redo would hide a broken scan)."""
+    flags = _np(flags)[:len(must)]
+    bad = [i for i, m in enumerate(must) if m and flags[i] != 0]
+    assert not bad, f"{what}: queries {bad} must be certified by the fast path, flags {flags.tolist()}"
+
+
+def _masks(mem, io, p: Probes, exp, shown, carry, at):
+    """The six masks of a checkpoint, built on ``mem``: -> the stacked masks ``[6, W]`` and the exclusion mask with its
+    complement for the next checkpoint to carry.  ``rows_of_mask`` of every one must be the model's selection."""
+    none = mem.new_mask()[0]
+    excl = ~mem.mask_of_rows(shown)
+    built = [~mem.new_mask()[0], mem.mask_of_scope(list(p.mask_scopes)), excl, mem.mask_where(where),
+             *((none, none) if carry.get("masks") is None else carry["masks"])]
+    names = ("all ones", "mask_of_scope", "~mask_of_rows", "mask_where", "carried ~mask_of_rows", "carried mask_of_rows")
+    for name, m, want in zip(names, built, exp["mask_rows"]):
+        got = np.asarray(mem.rows_of_mask(m), np.int64)
+        assert np.array_equal(got, want), f"{at}rows_of_mask of the {name} mask: {got.tolist()} != {want.tolist()}"
+    carry["built"] = (excl, ~excl)
+    return io.stack(built)
+
+
+def checkpoint(mem, model: Model, p: Probes, io, exp=None, label="", carry=None):
+    """``mem`` against ``model``: the accessors, then the fourteen readers; -> the ``*_uncertified_count`` of every
+    reader.  ``io`` carries what is not part of the memory's surface: ``t(bits)`` (bit patterns -> what the memory takes
+    as rows), ``ordinals(mem)`` (the ordinal column of the live rows in row-id order, vm_memory_group_ordinals),
+    ``raw(mem, n)`` (rows, tags, keys, ordinals over slots [0, n) in slot order), ``stack(masks)``, ``f64(x)`` and
+    ``i64d(x)`` (what the memory takes as stacked masks, as a device fp64 and as a device int64 tensor).  ``carry``: a
+    dict; ``carry["masks"]`` are the previous checkpoint's exclusion mask and its complement as this memory built them
+    (searched again now, stale), ``carry["built"]`` receives this checkpoint's."""
+    carry = {} if carry is None else carry
     exp = model.expect(p) if exp is None else exp
     lo, live = model.window()
     n = live.rows.shape[0]
@@ -301,10 +464,20 @@ def checkpoint(mem, model: Model, p: Probes, io, exp=None, label=""):
             assert np.array_equal(col[:n], want), f"{at}raw {name} of the live slots differ"
             assert not col[n:].any(), f"{at}raw {name}: a slot past the live count is not zero"
 
-    q = io.t(p.queries)
+    # identities the model owes before any device answer counts: the all-ones mask, the (1, 0, 0) weights and lam = 1
+    # change nothing
+    assert MASK_INDEX[0] == 0 and WEIGHTS[0] == [1.0, 0.0, 0.0] and LAM[0] == 1.0
+    for name in ("masked", "mix", "mix_masked"):
+        assert np.array_equal(exp[name][0][0], exp["topk"][0][0]) and _bits_equal(exp[name][1][0], exp["topk"][1][0]), \
+            f"{at}model: query 0 of {name} is not topk's"
+    assert np.array_equal(exp["diverse"][0][0], exp["masked"][0][0]) and _bits_equal(exp["diverse"][1][0], exp["masked"][1][0]), \
+        at + "model: lam = 1 is not topk_masked"
+    must = exp["must_certify"]
+    q, terms, lam, shown = io.t(p.queries), io.t(p.terms), io.f64(LAM), None
     for exact in (False, True):
         form = f"{at}{'exact' if exact else 'default'} "
         s, r = mem.topk(q, p.k, exact=exact)
+        shown = shown if exact else r                   # the default form's rows, as returned: the exclusion mask's operand
         _same(r, exp["topk"][0], form + "topk rows")
         assert _bits_equal(s, exp["topk"][1]), form + "topk scores (bit-exact bar)"
         s, r, kk = mem.topk_grouped(q, p.k, exact=exact)
@@ -330,6 +503,34 @@ def checkpoint(mem, model: Model, p: Probes, io, exp=None, label=""):
             assert h.count == want_c[i], f"{form}range_search count of query {i}: {h.count} != {want_c[i]}"
             _same(h.rows, want_r[i, :w], form + f"range_search rows of query {i}")
             assert _bits_equal(h.scores, want_s[i, :w]), form + f"range_search scores of query {i}"
+        # ---- the readers whose operands speak about row ids and slots
+        if not exact:
+            masks = _masks(mem, io, p, exp, shown, carry, at)
+        fast = (lambda flags, name: None) if exact else \
+            (lambda flags, name: _certified(getattr(mem, flags), must[name], f"{form}{name} ({flags})"))
+        for name, index in (("masked", MASK_INDEX), ("masked2", MASK_INDEX2)):
+            s, r = mem.topk_masked(q, p.k, masks, mask_index=list(index), exact=exact)
+            _pair(s, r, exp[name], form + f"topk_masked mask_index={list(index)}")
+            fast("last_mask_flags", name)
+        for name, spans in (("span", p.spans), ("span_carried", p.carried_span and [p.carried_span] * 6)):
+            if spans is None:
+                continue
+            for given in (spans, io.i64d([[INT64_MIN if a is None else a, INT64_MAX if b is None else b] for a, b in spans])):
+                s, r = mem.topk_span(q, p.k, given, exact=exact)
+                _pair(s, r, exp[name], form + f"topk_span {name} {'host pairs' if given is spans else 'device tensor'}")
+                fast("last_span_flags", name)
+        for name, kw in (("mix", {}), ("mix_masked", {"mask": masks, "mask_index": list(MASK_INDEX)})):
+            s, r = mem.topk_mix(terms, WEIGHTS, p.k, exact=exact, **kw)
+            _pair(s, r, exp[name], form + f"topk_mix {name}")
+            fast("last_mix_flags", name)
+        s, r = mem.topk_diverse(q, p.k, pool=POOL, lam=lam, mask=masks, mask_index=list(MASK_INDEX), exact=exact)
+        assert _bits_equal(mem.last_diverse_mmr, exp["diverse"][2]), form + "topk_diverse last_diverse_mmr"
+        _pair(s, r, exp["diverse"], form + "topk_diverse")
+        fast("last_diverse_flags", "diverse")
+        for (back, own), want in zip(LINK_CALLS, exp["links"]):
+            s, r = mem.recall_links(p.links[0], p.links[1], k=LINK_K, min_gap=LINK_GAP, max_back=back, exclude_group=own,
+                                    block=LINK_BLOCK, exact=exact)
+            _pair(s, r, want, form + f"recall_links max_back={back} exclude_group={own}")
     link, seg = exp["events"]
     ev = mem.events(p.threshold, max_gap_ms=p.gap_ms, with_links=True)
     assert ev.count == seg.count, f"{at}events count {ev.count} != {seg.count}"
@@ -406,6 +607,10 @@ class Driver:
         self.seq = 0
         self.stored = 0                  # rows that ever became live
         self.restored = []               # the drivers ``restore`` made: their memories are the caller's to close
+        self.carry = {}                  # the last checkpoint's exclusion masks (the memory's, and the model's words) and
+                                         # span: searched again, stale, after the next mutation; a restored memory is a
+                                         # new object and starts without them, a reset or an erase keeps them
+        self.last_erase = None           # new_row_of of the erase since the last checkpoint
 
     # -- data
     def take(self, n):
@@ -490,6 +695,7 @@ class Driver:
 
     def _erased(self, before_prov, out, got):
         assert got.count == out.count, f"erase count {got.count} != {out.count}"
+        self.last_erase = np.array(out.new_row_of)
         _same(got.new_row_of, out.new_row_of, "erase new_row_of")
         gone = np.nonzero(out.new_row_of < 0)[0]
         if gone.size:
@@ -574,7 +780,16 @@ class Driver:
             sc = cref.cosine_matrix(np.ascontiguousarray(q), np.ascontiguousarray(live.rows), dtype=self.dtype)
             eighth = [np.sort(sc[i][S.scope_mask(live.tags, *scopes[i])])[::-1] for i in range(6)]
             range_min = max(float(e[7]) for e in eighth if e.size > 7)
-        return Probes(q, scopes, clips, range_min)
+        total = self.model.total
+        spans = [(None, None), (None, lo + n // 2), (lo - 5, lo + 20), (total - 3, total + 10), (7, 3), (total - 1, total - 1)]
+        # a mixed query: the probe query, the next one, and a row far from it - the row that is gone when there is one
+        lost = self.overwritten if self.overwritten is not None else self.gone
+        far = [np.array(self.src[lost]) if lost is not None else live.rows[int(np.argmin(sc[c]))] if n else spare[c]
+               for c in range(6)]
+        terms = np.stack([np.stack([q[c], q[(c + 1) % 6], far[c]]) for c in range(6)])
+        w = min(n, LINK_ROWS)
+        return Probes(q, scopes, clips, range_min, mask_scopes=[one, window], carried=self.carry.get("words"), spans=spans,
+                      carried_span=self.carry.get("span"), terms=terms, links=(total - w, w))
 
     def check(self, label):
         n = self.model.total - self.model.base
@@ -583,7 +798,13 @@ class Driver:
         exp = self.model.expect(p)
         for hook in self.hooks:
             hook(label, self, p, exp)
-        self.log.append((label, checkpoint(self.mem, self.model, p, self.io, exp, label)))
+        carry = {"masks": self.carry.get("masks")}
+        self.log.append((label, checkpoint(self.mem, self.model, p, self.io, exp, label, carry)))
+        shown = exp["topk"][0]
+        words = MR.pack_rows(shown[shown >= 0], self.model.capacity)         # mask_of_rows of the rows shown, by the model
+        self.carry = {"masks": carry["built"], "words": (~words, words),
+                      "span": (self.model.base + 10, self.model.total - 10)}
+        self.last_erase = None
 
 
 # ---- the two scripts ---------------------------------------------------------------------------------------------------------

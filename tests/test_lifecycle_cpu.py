@@ -1,10 +1,15 @@
 """CPU: the lifecycle harness (tests/lifecycle_ref.py) proved before it judges a kernel.
 
 1. the model against itself: provenance, two erases = one erase of the union, restored() = a fresh model of the window;
-2. the conditions both scripts must meet at every checkpoint, for both dtypes, from the reference alone;
-3. planted defects: a fake memory answers ``checkpoint`` from a second model instance; the unplanted fake passes, every
-   defect planted in that instance fails.
+2. the conditions both scripts must meet at every checkpoint, for both dtypes, from the reference alone - those of the
+   nine older readers, and that the probes of the five newer ones (``topk_masked``, ``topk_span``, ``topk_mix``,
+   ``topk_diverse``, ``recall_links``, fed by ``mask_of_rows`` / ``mask_of_scope`` / ``mask_where``) are not vacuous: the
+   masks select some and not all, a stale mask is not a remapped one, dead slots lie under the all-ones mask after a
+   reset, the ring cuts a span, W and lam change a ranking, ``exclude_group`` changes a link;
+3. planted defects: a fake memory answers ``checkpoint`` from a second model instance, all fourteen readers and the mask
+   builders in numpy; the unplanted fake passes, every defect planted in that instance fails with its reader's name.
 """
+import weakref
 from types import SimpleNamespace
 
 import numpy as np
@@ -12,11 +17,15 @@ import pytest
 
 from oracle import cref
 from tests import clip_ref as CL
+from tests import diverse_ref as DR
 from tests import erase_ref as E
 from tests import events_ref as V
 from tests import group_ref as G
 from tests import lifecycle_ref as LC
+from tests import mask_ref as MR
+from tests import mix_ref as XR
 from tests import scope_ref as S
+from tests import span_ref as SP
 
 DTYPES = ["f16", "bf16"]
 SCRIPTS = {"linear": (LC.linear_script, 1600, False), "ring": (LC.ring_script, 600, True)}
@@ -30,12 +39,29 @@ def _norms(bits, dtype):
     return np.linalg.norm(CL.from_bits(np.ascontiguousarray(bits), dtype).astype(np.float64), axis=1)
 
 
+class _Mask(np.ndarray):
+    """A row mask of the fake memory: int32 words, so that ``~ & |`` work as on the device tensor.  Every one made is
+    remembered weakly: the defect "mask_remapped" has to find the masks a caller kept."""
+    made = []
+
+    def __array_finalize__(self, obj):
+        _Mask.made = [r for r in _Mask.made if r() is not None] + [weakref.ref(self)]
+
+
+STALE_NORMS = ("stale_norm", "mix_stale_norm", "diverse_stale_norm")
+
+
 class FakeMemory:
     """The surface of ``EmbeddingMemory`` that the scripts and ``checkpoint`` use, answered from a ``Model`` of its own.
     ``defect`` plants one way a real memory could go wrong."""
 
     def __init__(self, model: LC.Model, defect=None):
         self.m, self.defect = model, defect
+        self.W = MR.mask_words(model.capacity)
+        self.slots = np.zeros((model.capacity, model.D), np.uint16)    # the rows of a linear memory that never zeroes a
+                                   # slot: what lies under the bits beyond the live count (defect "mask_sees_dead_slots")
+        self.old_ids = None        # the ids before the last erase (defect "where_ids_stale")
+        self.last_diverse_mmr = None   # of the last topk_diverse call
         self.ghost = None          # rows an erase left in the slots it vacated (defect "ghost")
         self.stale = None          # the norms an erase left behind in slots [0, n') (defect "stale_norm")
         self.memo = {}             # reader answers since the last mutation: checkpoint asks for both forms of each
@@ -77,9 +103,16 @@ class FakeMemory:
     def meta_of(self, r):
         return None if self.id_of(r) is None else {"i": self.id_of(r)}
 
+    def _sync(self):
+        """The live rows into their slots; whatever lay behind them stays."""
+        if not self.m.ring:
+            self.slots[:self.m.total] = self.m.rows
+
     def append(self, rows, ids=None, meta=None, group=None, tag=None):
-        self.ghost = None
-        return self.m.append(rows, tag, group, ids)
+        self.ghost = self.old_ids = None
+        first = self.m.append(rows, tag, group, ids)
+        self._sync()
+        return first
 
     def append_novel(self, rows, tau, ids=None, meta=None, group=None, tag=None):
         known = None
@@ -90,7 +123,8 @@ class FakeMemory:
         keep, row_of = self.m.append_novel(rows, tau, tag, group, ids, known=known)
         if self.defect == "gated_ids":                      # the first ids of the batch, not the kept rows' ids
             self.m.ids = self.m.ids[:n_ids] + list(ids)[:int(keep.sum())]
-        self.ghost = None
+        self.ghost = self.old_ids = None
+        self._sync()
         return SimpleNamespace(keep=keep, row_of=row_of, kept=int(keep.sum()))
 
     def erase(self, rows=None, scope=None):
@@ -100,8 +134,20 @@ class FakeMemory:
         if out is None:
             raise Refused("erase: the ring has wrapped")
         n, keep = m.total, out.new_row_of >= 0
-        if self.defect == "stale_norm" and out.count:
+        if self.defect in STALE_NORMS and out.count:
             self.stale = _norms(old.rows[:n], m.dtype)
+        if self.defect == "where_ids_stale":
+            self.old_ids = old.ids
+        if self.defect == "mask_remapped":                  # every mask anybody holds follows its rows
+            seen = set()
+            for ref in _Mask.made:
+                mask = ref()
+                if mask is None or mask.shape != (self.W,) or mask.__array_interface__["data"][0] in seen:
+                    continue
+                seen.add(mask.__array_interface__["data"][0])
+                was = np.nonzero(MR.selected(np.array(mask).view(np.uint32), 0, keep.size, m.capacity))[0]
+                mask[...] = MR.pack_rows(out.new_row_of[was][keep[was]], m.capacity).view(np.int32)
+        self._sync()
         if self.defect == "tags_not_moved":
             m.tags = old.tags[:n]
         if self.defect == "ordinals_not_rederived":
@@ -132,7 +178,7 @@ class FakeMemory:
     def reset(self):
         last = self.m.state[1]
         self.m.reset()
-        self.ghost = self.stale = None
+        self.ghost = self.stale = self.old_ids = None
         if self.defect == "reset_keeps_open":
             self.m.state = (0, last, 1)
 
@@ -151,10 +197,8 @@ class FakeMemory:
 
     def _topk(self, q, k, min_score):
         lo, live = self.m.window()
-        if self.stale is not None and live.rows.shape[0]:   # scores from the norms the erase left behind
-            scale = np.ones(live.rows.shape[0])
-            n = min(self.stale.size, scale.size)
-            scale[:n] = _norms(live.rows[:n], self.m.dtype) / np.where(self.stale[:n] > 0, self.stale[:n], 1.0)
+        if self.defect == "stale_norm" and self.stale is not None and live.rows.shape[0]:
+            scale = self._stale_scale()                     # scores from the norms the erase left behind
             scores = cref.cosine_matrix(np.ascontiguousarray(q), np.ascontiguousarray(live.rows), dtype=self.m.dtype) * scale
             r, s = S.scoped_topk_from_scores(scores, live.tags, LC.SCOPE_ALL, k, min_score=min_score, base=lo)
             return s, r
@@ -193,8 +237,110 @@ class FakeMemory:
         s = self._once(self.m.exp_summaries)
         return SimpleNamespace(count=int(s.first_rows.size), **s._asdict())
 
+    def _stale_scale(self):
+        """Per live row: its norm over the norm the erase left in its slot."""
+        _, live = self.m.window()
+        scale = np.ones(live.rows.shape[0])
+        n = min(self.stale.size, scale.size)
+        scale[:n] = _norms(live.rows[:n], self.m.dtype) / np.where(self.stale[:n] > 0, self.stale[:n], 1.0)
+        return scale
+
+    # -- masks: int32 words [W] as on the device
+    def _mask(self, ids):
+        return MR.pack_rows(ids, self.m.capacity).view(np.int32).view(_Mask)
+
+    def new_mask(self, n=1):
+        return np.zeros((n, self.W), np.int32).view(_Mask)
+
+    def mask_of_rows(self, rows):
+        ids = np.asarray(rows, np.int64).ravel()
+        return self._mask(ids[(ids >= self.m.base) & (ids < self.m.total)])
+
+    def mask_of_scope(self, scope):
+        lo, live = self.m.window()
+        return self._mask(lo + np.nonzero(E.mask_of_scopes(live.tags, scope))[0])
+
+    def mask_where(self, fn):
+        ids = self.m.ids if self.old_ids is None else self.old_ids      # defect "where_ids_stale": the ids before the erase
+        return self._mask([r for r in range(self.m.base, self.m.total) if fn(r, ids[r], {"i": ids[r]})])
+
+    def _selection(self, mask, mask_index, Q):
+        lo, live = self.m.window()
+        words = np.array(mask).view(np.uint32).reshape(-1, self.W)
+        return MR.selection(words, mask_index, Q, lo, live.rows.shape[0], self.m.capacity)
+
+    def rows_of_mask(self, mask):
+        return (self.m.base + np.nonzero(self._selection(mask, None, 1)[0])[0]).tolist()
+
+    # -- the readers whose operands speak about row ids and slots
+    def topk_masked(self, q, k, mask, mask_index=None, exact=False):
+        return self._once(self._topk_masked, q, k, np.array(mask), mask_index)
+
+    def _topk_masked(self, q, k, mask, mask_index):
+        lo, live = self.m.window()
+        rows, sel = live.rows, self._selection(mask, mask_index, q.shape[0])
+        n, hi = rows.shape[0], self.m.written
+        if self.defect == "mask_sees_dead_slots" and not self.m.ring and hi > n:   # bits past the live count count too
+            rows = self.slots[:hi]
+            sel = MR.selection(mask.view(np.uint32).reshape(-1, self.W), mask_index, q.shape[0], 0, hi, self.m.capacity)
+        r, s = MR.masked_topk(q, rows, sel, k, dtype=self.m.dtype, base=lo)
+        return s, r
+
+    def topk_span(self, q, k, span, exact=False):
+        pairs = [tuple(int(x) for x in p) for p in span] if isinstance(span, np.ndarray) else list(span)
+        return self._once(self._topk_span, q, k, SP.pairs(pairs, q.shape[0]))
+
+    def _topk_span(self, q, k, pairs):
+        lo, live = self.m.window()
+        if self.defect == "span_by_slot" and self.m.wrapped:                # the bounds compared with the slot
+            slot = (lo + np.arange(live.rows.shape[0])) % self.m.capacity
+            sel = np.stack([(slot >= a) & (slot <= b) for a, b in pairs])
+            r, s = MR.masked_topk(q, live.rows, sel, k, dtype=self.m.dtype, base=lo)
+        else:
+            r, s = self.m.exp_span(q, pairs, k)
+        return s, r
+
+    def topk_mix(self, terms, weights, k, mask=None, mask_index=None, exact=False):
+        return self._once(self._topk_mix, terms, weights, k, None if mask is None else np.array(mask), mask_index)
+
+    def _topk_mix(self, terms, weights, k, mask, mask_index):
+        lo, live = self.m.window()
+        sel = None if mask is None else self._selection(mask, mask_index, terms.shape[0])
+        scores = XR.mix_scores_loop
+        if self.defect == "mix_stale_norm" and self.stale is not None and live.rows.shape[0]:
+            scale = self._stale_scale()
+            scores = lambda e, w: XR.mix_scores_loop(e * scale, w)
+        r, s = XR.mix_topk(terms, weights, live.rows, sel, k, dtype=self.m.dtype, base=lo, scores=scores)
+        return s, r
+
+    def topk_diverse(self, q, k, pool=None, lam=0.5, mask=None, mask_index=None, exact=False):
+        s, r, self.last_diverse_mmr = self._once(self._topk_diverse, q, k, pool, np.asarray(lam), np.array(mask), mask_index)
+        return s, r
+
+    def _topk_diverse(self, q, k, pool, lam, mask, mask_index):
+        lo, live = self.m.window()
+        sim = None
+        if self.defect == "diverse_stale_norm" and self.stale is not None and live.rows.shape[0]:
+            scale = self._stale_scale()
+            sim = DR.sim_matrix(live.rows, self.m.dtype) * scale[:, None] * scale[None, :]
+        r, s, v = DR.diverse_topk(q, live.rows, self._selection(mask, mask_index, q.shape[0]), k, pool, list(lam),
+                                  dtype=self.m.dtype, base=lo, sim=sim)
+        return s, r, v
+
+    def recall_links(self, first_row, n_rows, k=10, min_gap=1, max_back=None, exclude_group=False, block=256, exact=False):
+        aged = self.m.wrapped or self.m.total < self.m.used                 # the links go wrong on an aged memory only:
+        own = exclude_group and not (aged and self.defect == "links_own_group")     # a wrapped ring, or after an erase
+        r, s = self._once(self.m.exp_links, first_row, n_rows, k, min_gap, max_back, own)
+        done = n_rows // block * block
+        if aged and self.defect == "links_page_edge" and done < n_rows:     # the last, ragged page is never searched
+            r, s = r.copy(), s.copy()
+            r[done:], s[done:] = -1, 0.0
+        return s, r
+
+    last_mask_flags = last_span_flags = last_mix_flags = last_diverse_flags = np.zeros(6, np.int32)
     uncertified_count = grouped_uncertified_count = scoped_uncertified_count = 0
     group_scoped_uncertified_count = clip_uncertified_count = 0
+    masked_uncertified_count = span_uncertified_count = mix_uncertified_count = diverse_uncertified_count = 0
 
 
 class FakeIO:
@@ -202,6 +348,9 @@ class FakeIO:
     t = staticmethod(lambda bits: np.asarray(bits))
     i64 = staticmethod(lambda x: np.asarray(x, np.int64))
     bits = staticmethod(lambda x: np.asarray(x))
+    stack = staticmethod(lambda masks: np.stack([np.asarray(m) for m in masks]))
+    f64 = staticmethod(lambda x: np.asarray(x, np.float64))
+    i64d = staticmethod(lambda x: np.asarray(x, np.int64))
     ordinals = staticmethod(lambda mem: mem.m.window()[1].ords)
     raw = staticmethod(lambda mem, n: mem.raw(n))
     restore = staticmethod(lambda mem, capacity: FakeMemory(mem.m.restored(capacity), mem.defect))
@@ -270,12 +419,80 @@ def test_append_follows_the_open_group_rule_and_reset_forgets_it():
 
 
 # ---- 2. the conditions of the scripts ----------------------------------------------------------------------------------
-def _conditions(seen):
+ONCE = ("stale mask differs from a remapped one", "W ranks other rows than term 0", "a lam < 1 query leaves its pool's first k",
+        "a link row with an empty past, or live rows before the window", "exclude_group changes a link",
+        "the flag-0 demand is made of every reader")
+
+
+def _new_reader_conditions(label, d, p, exp, once, at):
+    """The probes of the masked, span, mixed and diverse searches and of the recall links are not vacuous: from the
+    oracle's values alone.  ``once`` counts what has to hold at least once per script."""
+    m = d.model
+    lo, live = m.window()
+    n, k, total = live.rows.shape[0], p.k, m.total
+    sels, sel = [r.size for r in exp["mask_rows"]], exp["sel"]
+    if n == 0:
+        assert all(c == 0 for c in sels) and not sel.any(), at
+        for name in ("masked", "masked2", "span", "mix", "mix_masked", "diverse"):
+            assert (exp[name][0] == -1).all() and not exp[name][1].any(), at + name
+        assert not exp["diverse"][2].any() and all(r.shape == (0, LC.LINK_K) for r, _ in exp["links"]), at
+        assert not any(any(v) for v in exp["must_certify"].values()), at
+        return
+    # masks (b), (c), (d): each selects at least k rows, so its query's answer is full, and not every live row ((b), one
+    # source and a window, only where two sources are live); among the six queries at least one has k selected rows and at
+    # least one (the empty mask) fewer
+    sources = np.unique(live.tags >> LC.MS_BITS).size
+    assert sels[0] == n and all(k <= c < n + (i == 0 and sources == 1) for i, c in enumerate(sels[1:4])), \
+        at + f"the masks select {sels} of {n} rows, {sources} sources"
+    per_query = sel.sum(axis=1)
+    assert (per_query >= k).any() and (per_query < k).any(), at + f"rows selected per query {per_query.tolist()}"
+    assert (exp["masked"][0][:4] >= 0).all() and (exp["masked"][0][5] == -1).all(), at
+    if d.last_erase is not None and p.carried is not None:      # stale: the bit names whichever row lives in the slot now
+        new = d.last_erase
+        for words, stale in zip(p.carried, exp["mask_rows"][4:]):
+            was = np.nonzero(MR.selected(words, 0, new.size, m.capacity))[0]
+            remapped = np.sort(new[was][new[was] >= 0])
+            once["stale mask differs from a remapped one"] += not np.array_equal(remapped, stale)
+    if label in ("9 append after erase-to-empty", "10 reset, append", "8 reset, append"):
+        assert m.written > n, at + "no slot beyond the live count was ever written: the all-ones mask covers nothing dead"
+    # spans
+    span_rows = exp["span"][0]
+    assert np.array_equal(span_rows[0], exp["topk"][0][0]), at + "the open span is not topk"
+    assert (span_rows[4] == -1).all() and span_rows[5].tolist() == [total - 1] + [-1] * (k - 1), at
+    assert (span_rows[1] <= lo + n // 2).all() and (span_rows[2][span_rows[2] >= 0] <= lo + 20).all(), at
+    assert sorted(span_rows[3][span_rows[3] >= 0]) == list(range(max(lo, total - 3), total)), at
+    if m.wrapped:           # ids lo - 5 .. lo - 1 named rows once; the ring has overwritten them: the span is cut by base
+        assert lo - 5 >= 0 and p.spans[2][0] == lo - 5 < lo and (span_rows[2] >= lo).all(), at
+        by_slot = [r for r in range(lo, total) if p.spans[2][0] <= r % m.capacity <= p.spans[2][1]]
+        assert by_slot != list(range(lo, lo + 21)), at + "the span by slots is the span by row ids"
+    # mixed, diverse, links
+    once["W ranks other rows than term 0"] += any(not np.array_equal(exp["mix"][0][c], exp["topk"][0][c]) for c in range(1, 6))
+    once["a lam < 1 query leaves its pool's first k"] += any(
+        set(exp["diverse"][0][i]) != set(exp["masked"][0][i]) for i in range(1, 5))
+    assert all(set(exp["diverse"][0][i]) - {-1} <= set(m.exp_masked(p.queries, sel, LC.POOL)[0][i]) for i in range(6)), at
+    first, count = p.links
+    assert count == min(n, LC.LINK_ROWS) and first + count == total and first >= lo, at
+    once["a link row with an empty past, or live rows before the window"] += bool(
+        (exp["links"][0][0] == -1).all(axis=1).any() or first > lo)
+    plain = m.exp_links(first, count, LC.LINK_K, LC.LINK_GAP, None, False)
+    once["exclude_group changes a link"] += not np.array_equal(plain[0], exp["links"][0][0])
+    must = exp["must_certify"]
+    assert not (must["masked"][5] or must["mix_masked"][5] or must["diverse"][5] or must["span"][4]), at + "an empty query"
+    if m.outside:
+        assert not any(any(v) for v in must.values()), at + "the sticky word is set: every query goes to the redo"
+    once["the flag-0 demand is made of every reader"] += all(any(v) for name, v in must.items())
+
+
+def _conditions(seen, once=None):
+    once = {} if once is None else once
+    once.update({name: 0 for name in ONCE})
+
     def hook(label, d, p, exp):
         lo, live = d.model.window()
         n = live.rows.shape[0]
         at = f"[{d.dtype} {label}] "
         seen.append((label, n))
+        _new_reader_conditions(label, d, p, exp, once, at)
         # provenance: every live row is, bit for bit, the row it came from
         assert (live.prov >= 0).all() and all(np.array_equal(live.rows[i], d.src[int(live.prov[i])]) for i in range(n)), at
         assert len(live.ids) == n and len(set(live.ids)) == n
@@ -309,9 +526,10 @@ def _conditions(seen):
 
 @pytest.mark.parametrize("dtype", DTYPES)
 def test_linear_script_conditions_and_the_unplanted_fake(dtype):
-    seen = []
-    d = _driver("linear", dtype, hooks=[_conditions(seen)])
+    seen, once = [], {}
+    d = _driver("linear", dtype, hooks=[_conditions(seen, once)])
     end = LC.linear_script(d)
+    assert all(once[name] >= 1 for name in ONCE), once
     labels = [s[0] for s in seen]
     assert len(labels) == 13 and labels[0].startswith("1 ") and labels[-1].startswith("10 ")
     assert all(0.2 <= g <= 0.8 for g in d.gated) and len(d.gated) == 2, d.gated
@@ -333,10 +551,19 @@ def test_ring_script_conditions_and_the_unplanted_fake(dtype):
             assert m.keys[2 * cap - 1] == m.keys[2 * cap], "no group spans slots capacity - 1 and 0"
             assert (2 * cap - 1) % cap == cap - 1 and (2 * cap) % cap == 0
             assert live.keys[0] < lo, "the first live group is not a cut one"
+            # links_ref's group_of: the model's ordinals as they are and the runs of the keys cut the same spans, and a
+            # row of the cut group has no past outside its group
+            first, count = p.links
+            by_ords = SP.link_spans(lo, m.total - lo, lo, LC.LINK_GAP, None, live.ords)
+            assert by_ords == SP.link_spans(lo, m.total - lo, lo, LC.LINK_GAP, None, G.group_ids(live.keys))
+            assert live.ords[1] == live.ords[0] and by_ords[1][1] == lo - 1
+            assert by_ords[first - lo:] == SP.link_spans(first, count, lo, LC.LINK_GAP, None, live.ords)
             seen.append(("wrapped twice", lo))
 
-    d = _driver("ring", dtype, hooks=[_conditions(seen), wrap_hook])
+    once = {}
+    d = _driver("ring", dtype, hooks=[_conditions(seen, once), wrap_hook])
     LC.ring_script(d)
+    assert all(once[name] >= 1 for name in ONCE), once
     labels = [s[0] for s in seen]
     assert labels.count("wrapped twice") == 2 and "7 restored linear" in labels and labels[-1] == "8 reset, append"
     assert all(0.2 <= g <= 0.8 for g in d.gated) and len(d.gated) == 1, d.gated
@@ -348,7 +575,12 @@ DEFECTS = [("stale_norm", "linear", "default topk"), ("tags_not_moved", "linear"
            ("ghost", "linear", "past the live count"), ("ids_not_remapped", "linear", "id_of"),
            ("gated_ids", "linear", "id_of"), ("reset_keeps_open", "linear", "raw ordinals"),
            ("ordinals_not_rederived", "ring", "ordinals relative"), ("ring_base", "ring", "first live row"),
-           ("wrong_side", "ring", "group_keys_host")]
+           ("wrong_side", "ring", "group_keys_host"),
+           ("mask_sees_dead_slots", "linear", "topk_masked"), ("mask_remapped", "linear", "carried"),
+           ("where_ids_stale", "linear", "mask_where"), ("span_by_slot", "ring", "topk_span"),
+           ("mix_stale_norm", "linear", "topk_mix"), ("diverse_stale_norm", "linear", "last_diverse_mmr"),
+           ("links_own_group", "linear", "recall_links max_back=None exclude_group=True"),
+           ("links_page_edge", "ring", "recall_links")]
 
 
 @pytest.mark.parametrize("defect,script,message", DEFECTS, ids=[d[0] for d in DEFECTS])

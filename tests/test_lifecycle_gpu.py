@@ -2,12 +2,18 @@
 
 Two scripts - a linear memory of 1,600 rows and a ring of 600, grouped and tagged - apply every mutator in turn: keyed,
 tagged and gated appends, erases by scope and by rows, whole and tail regroups, the ring overwrite, reset, snapshot /
-restore.  After every step ``lifecycle_ref.checkpoint`` compares the accessors, the raw columns and all nine readers -
-each top-k reader in its default and its exact form - with the model: rows, keys and fp64 score bits equal.
-tests/test_lifecycle_cpu.py proves the scripts' conditions and that the checkpoint fails on planted defects.
+restore.  After every step ``lifecycle_ref.checkpoint`` compares the accessors, the raw columns and all fourteen readers
+- ``topk``, ``topk_grouped``, ``topk_scoped``, ``topk_grouped_scoped``, ``topk_clip``, ``range_search``, ``events``,
+``summaries``, ``topk_masked``, ``topk_span``, ``topk_mix``, ``topk_diverse`` with ``last_diverse_mmr`` and
+``recall_links``, the mask builders ``mask_of_rows`` / ``mask_of_scope`` / ``mask_where`` through ``rows_of_mask``; each
+top-k reader in its default and its exact form - with the model: rows, keys and fp64 score bits equal.  The masks are
+all ones, a scope mask, the exclusion of the rows just shown, a metadata filter and the previous checkpoint's exclusion
+mask searched again, stale, after the mutation; the spans include one carried over in the same way.  Where a feature's
+own oracle condition says that the fast path of the masked, span, mixed or diverse search must certify a query, its flag
+must be 0.  tests/test_lifecycle_cpu.py proves the scripts' conditions and that the checkpoint fails on planted defects.
 
-Measured on one MI355X (profiles/lifecycle.json): 0.3 - 0.8 s per script and dtype, 1.1 s for the first
-case under pytest, which builds the data pools.
+Measured on one MI355X (profiles/lifecycle.json): 1.0 - 2.3 s per script and dtype (0.3 - 0.8 s with the
+nine readers of the parent commit, same session), 3.3 s for the first case under pytest, which builds the data pools.
 """
 import time
 
@@ -40,6 +46,20 @@ class IO:
     @staticmethod
     def bits(t):
         return t.contiguous().view(torch.int16).cpu().numpy().view(np.uint16)
+
+    @staticmethod
+    def stack(masks):
+        """Masks ``[W]`` -> one device tensor ``[n_masks, W]``."""
+        return torch.stack(list(masks))
+
+    @staticmethod
+    def f64(x):
+        return torch.tensor(list(x), dtype=torch.float64).cuda()
+
+    @staticmethod
+    def i64d(x):
+        """-> device int64 tensor (the spans as ``[Q, 2]``)."""
+        return torch.tensor(x, dtype=torch.int64).cuda()
 
     @staticmethod
     def _col(mem, fn, n, width=None):
