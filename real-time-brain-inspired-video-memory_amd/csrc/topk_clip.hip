@@ -5,8 +5,8 @@
 // window closer than min_sep rows (local-maximum suppression, not greedy), so k answers are k moments, not k shifts of one.
 //
 // Two-stage and certified like the other searches, with which it shares topk_tile_scan.h (the scan; ClipScan is its
-// policy), topk_scope_select.h (cut, compaction, selection over one key per slot, 0 = absent), the reference arithmetic of
-// topk_common.h and vm_topk_redo_merge:
+// policy), topk_key_image.hip (vm_key_image_select of topk_scope_select.h: cut, compaction, selection over one key per
+// slot, 0 = absent), the reference arithmetic of topk_common.h and vm_topk_redo_merge:
 //   pack     : each clip -> one zero-padded 16-query tile [C][16][D] + the exact fp64 norm of every frame
 //   scan     : fp32 MFMA scores of every live row against the 16 C frames, S[16 c + i][slot] (a tile with no row in a
 //              scope of the block's clips costs its tags only and writes nothing: its scores are never read)
@@ -432,10 +432,8 @@ __global__ void __launch_bounds__(CW_THREADS)
 }
 
 // ---- host --------------------------------------------------------------------------------------------------
-struct CPlan : TopkGeom {
-    int64_t fstride;
-    size_t off_qt, off_qn, off_S, off_bf, off_key, off_co, off_ck, off_cn, off_cw, off_cp, off_flags, off_cut, off_cc,
-        off_cbuf, off_w64, off_ps, off_po, total;
+struct CPlan : SelectPlan {  // the select stage's arrays are its base's
+    size_t off_qt, off_qn, off_S, off_bf, off_key, off_cw, off_cp, off_flags, off_w64, off_ps, off_po, total;
 };
 
 CPlan clip_plan(const vm_memory *m, int C, int k) {
@@ -556,22 +554,13 @@ int clip_topk(vm_memory *m, const ClipCall &a, int32_t *out_uncertified, int32_t
     }
     {
         vm_prof_scope prof(ctx, VM_PROF_TOPK_FINALIZE, st);
-        uint32_t *cut = (uint32_t *)(ws + p.off_cut);
-        int *ccount = (int *)(ws + p.off_cc);
-        unsigned long long *cbuf = (unsigned long long *)(ws + p.off_cbuf);
         const dim3 wgrid((unsigned)((m->cap + CW_THREADS - 1) / CW_THREADS), a.C);
         clip_window_kernel<<<wgrid, CW_THREADS, 0, st>>>(m->d_total, m->cap, m->ring, m->tag, a.scope_lo, a.scope_hi,
                                                         a.max_gap_ms, a.L, S, p.fstride, qn, Bf);
         VM_LAUNCH_CHECK(ctx);
         clip_peak_kernel<<<wgrid, CW_THREADS, 0, st>>>(m->d_total, m->cap, m->ring, m->D, a.min_sep, Bf, p.fstride, key);
         VM_LAUNCH_CHECK(ctx);
-        scope_cut_kernel<<<a.C, SEL_THREADS, 0, st>>>(m->d_total, m->cap, m->ring, key, p.fstride, p.M + 1, cut, ccount);
-        VM_LAUNCH_CHECK(ctx);
-        scope_compact_kernel<<<dim3(p.cmp_slices, a.C), CMP_THREADS, 0, st>>>(m->d_total, m->cap, m->ring, key,
-                                                                              p.fstride, cut, ccount, cbuf);
-        VM_LAUNCH_CHECK(ctx);
-        scope_select_kernel<<<a.C, SEL_THREADS, 0, st>>>(p.M + 1, ccount, cbuf, cand_o, cand_k, cand_n);
-        VM_LAUNCH_CHECK(ctx);
+        if (int rc = vm_key_image_select(m, p, key, a.C, ws, st)) return rc;
         clip_rescore_kernel<DT><<<dim3(p.M + 1, a.C), CW_THREADS, 0, st>>>(
             m->rows, m->norm64, qt, qn, m->d_total, m->cap, m->ring, m->D, a.L, a.min_sep, Bf, p.fstride, cand_o, cand_n,
             cand_w, cand_p);
@@ -589,8 +578,7 @@ template <int DT>
 int clip_exact(vm_memory *m, const ClipCall &a, char *ws, hipStream_t st) {
     const CPlan p = clip_plan(m, a.C, a.k);
     if (int rc = clip_pack<DT>(m, p, a, ws, st)) return rc;
-    fill_flags_kernel<<<(a.C + 255) / 256, 256, 0, st>>>((int32_t *)(ws + p.off_flags), a.C);
-    VM_LAUNCH_CHECK(m->ctx);
+    if (int rc = vm_fill_flags(m, (int32_t *)(ws + p.off_flags), a.C, st)) return rc;
     return clip_redo<DT>(m, p, a, ws, st);
 }
 

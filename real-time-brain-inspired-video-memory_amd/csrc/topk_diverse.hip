@@ -15,9 +15,7 @@
 //            (v desc, row id asc) and one coalesced read of the winner's row of S
 // Every launch reads the row count from the device and is sized from the arguments: no allocation, no synchronisation, no
 // host read-back - capturable.
-#include "topk_common.h"
-#include "topk_select.h"
-#include "vm_internal.h"
+#include "topk_scope_select.h"  // vm_key_image_plan: the pool search's workspace
 
 namespace {
 
@@ -143,18 +141,15 @@ __global__ void __launch_bounds__(64)
 }
 
 // ---- host --------------------------------------------------------------------------------------------------
-int64_t diverse_mask_words(const vm_memory *m) { return (m->cap + 63) / 64 * 2; }
-
-// the pool search's workspace (topk_scope_select.h scope_plan for k = pool, as both searches report it; at offset 0), then
-// the pool, the open span and S
+// the pool search's workspace (topk_scope_select.h vm_key_image_plan for k = pool, the masked and the span search's alike;
+// at offset 0), then the pool, the open span and S
 struct DPlan {
     size_t pool_total, off_prow, off_pe, off_lo, off_hi, off_S, total;
 };
 
 DPlan diverse_plan(const vm_memory *m, int Q, int pool) {
     DPlan p;
-    const size_t masked = vm_topk_masked_workspace_bytes(m, Q, pool), span = vm_topk_span_workspace_bytes(m, Q, pool);
-    p.pool_total = masked > span ? masked : span;
+    p.pool_total = vm_key_image_plan(m, Q, pool).total;
     WsBump ws;
     ws.off = vm_align_up(p.pool_total, 256);
     p.off_prow = ws.take((size_t)Q * pool * 8);
@@ -198,13 +193,8 @@ int diverse_check(vm_memory *m, const DiverseCall &c, const char *who) {
     if (!c.queries || !c.lam) return vm_fail(ctx, VM_ERR_INVALID, "%s: null queries or lam", who);
     if (!c.out_scores || !c.out_rows || !c.out_mmr) return vm_fail(ctx, VM_ERR_INVALID, "%s: null outputs", who);
     if (c.row_stride < 1) return vm_fail(ctx, VM_ERR_INVALID, "%s: row_stride=%lld < 1", who, (long long)c.row_stride);
-    if (c.masks) {  // mask_check's rules (topk_mask.hip)
-        if ((uintptr_t)c.masks & 3) return vm_fail(ctx, VM_ERR_INVALID, "%s: masks must be 4-byte aligned", who);
-        if (c.n_masks < 1 || !(c.mask_index || c.n_masks == 1 || c.n_masks == c.Q))
-            return vm_fail(ctx, VM_ERR_INVALID, "%s: %d masks for %d queries need a mask_index", who, c.n_masks, c.Q);
-        if ((int64_t)c.n_masks * diverse_mask_words(m) > ((int64_t)1 << 30))
-            return vm_fail(ctx, VM_ERR_UNSUPPORTED, "%s: more than 2^30 words of masks", who);
-    }
+    if (c.masks)
+        if (int rc = mask_operand_check(m, c.masks, c.n_masks, c.mask_index, c.Q, who)) return rc;
     if ((size_t)DV_TILE * m->D * 2 > DV_LDS_MAX)
         return vm_fail(ctx, VM_ERR_UNSUPPORTED, "%s: D=%d: a tile of %d rows does not fit the LDS", who, m->D, DV_TILE);
     const size_t need = diverse_plan(m, c.Q, c.pool).total;

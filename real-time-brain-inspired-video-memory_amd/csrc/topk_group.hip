@@ -4,8 +4,9 @@
 // group's score is the exact max over its rows and its representative the lowest row id reaching that max.  Same
 // two-stage, certified design as topk.hip; the key images, the block-wide selection, the plan
 // scaffold and the argument check are topk_select.h's, shared with topk_scope.hip; the scan is topk_tile_scan.h's, shared
-// with topk_scope.hip and range.hip (GroupScan below is its policy); the table, the run folding, the compaction, the radix
-// select, the finalize, the redo scan and the plan live in topk_group_parts.h, shared with topk_group_scope.hip:
+// with topk_scope.hip and range.hip (GroupScan below is its policy); the run folding, the radix select, the finalize, the
+// redo scan and the plan live in topk_group_parts.h, the table and the compaction in topk_group_parts.hip, all shared with
+// topk_group_scope.hip:
 //   table    : first age order of every live group (groups are runs of equal ordinals, memory.hip) + clears the maxima
 //   scan     : fp32 MFMA scores with the list scan's numerics (the same instruction over the same operand layout, then
 //              x 1/||row||), folded into per-(query, group) fp32 maxima with one atomic max per run of a 16-row tile

@@ -1,18 +1,28 @@
 // What the grouped search (topk_group.hip) and the scoped grouped search (topk_group_scope.hip) share beyond
 // topk_select.h, all of it from topk_group.hip:
-//   moved unchanged   the tuning constants, the fp64 key images, the exact re-score, group_table_kernel,
-//                     group_compact_kernel, radix_select_all, the workspace plan
+//   moved unchanged   the tuning constants, the fp64 key images, the exact re-score, radix_select_all, the workspace
+//                     plan; group_table_kernel and group_compact_kernel, which are no templates: compiled once, in
+//                     topk_group_parts.hip, and reached through the two launchers declared below
 //   moved and changed group_fold_runs (GroupScan's epilogue, its key now a functor), group_finalize_kernel and
 //                     group_redo_scan_kernel (a row predicate SC of vm_internal.h passed by value, used under
 //                     `if constexpr (SC::scoped)` only; the redo's LDS score array is `rs`, since `sc` is the predicate)
 //   the host driver   GroupCall, grouped_topk, grouped_redo, grouped_exact: a search brings its scan policy, its two
 //                     select kernels and its predicate
-// The anonymous namespace sits in a header: each of the two files compiles its own copy, so the library carries
-// group_table_kernel and group_compact_kernel twice.
+// What stays in the anonymous namespace here is a template, or inlined into one: each is instantiated in one unit only.
+// topk_scope_select.h reuses constant names with other values (SEL_CAP): no unit may include both headers.
 #pragma once
 #include "topk_tile_scan.h"
 
 #include <climits>
+
+// ---- table and compaction (topk_group_parts.hip) ------------------------------------------------------------------
+// first_o[g] = age order of the first live row of live group g, first_o[ng] = n; F (if not null): F[0, Q * ng) = 0;
+// fill_flags: flags[0, Q) = 1 (the exhaustive-only entry point)
+int vm_group_table(vm_memory *m, int blocks, int Q, int *first_o, uint32_t *F, int32_t *flags, int fill_flags,
+                   hipStream_t st);
+// grid (slices, Q): every group whose composite is >= cut[q] goes to the query's buffer; ccount[q] > SEL_CAP: radix path
+int vm_group_compact(vm_memory *m, int slices, int Q, const uint32_t *F, const unsigned long long *cut, int *ccount,
+                     unsigned long long *cbuf, hipStream_t st);
 
 namespace {
 
@@ -79,31 +89,6 @@ __device__ __forceinline__ double exact_qnorm(const uint16_t *ql, int D) {
     return __dsqrt_rn(nq);
 }
 
-
-// ---- table -------------------------------------------------------------------------------------------------
-// first_o[g] = age order of the first live row of live group g (g = ordinal - ord0), first_o[ng] = n; F[0, Q*ng) = 0;
-// fill_flags: flags[0, Q) = 1 (the exhaustive-only entry point).  Grid-stride, any grid.
-__global__ void __launch_bounds__(256)
-    group_table_kernel(const int64_t *__restrict__ d_total, int64_t cap, int ring, const int64_t *__restrict__ gord,
-                       int Q, int *__restrict__ first_o, uint32_t *__restrict__ F, int32_t *__restrict__ flags,
-                       int fill_flags) {
-    const GroupView gv = group_view(d_total, cap, ring, gord);
-    const int64_t n = gv.rv.n;
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    const int64_t t0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    for (int64_t o = t0; o <= n; o += stride) {
-        if (o == n) {
-            first_o[gv.ng] = (int)n;
-        } else {
-            const int64_t g = gord[slot_of(gv.rv, o)] - gv.ord0;
-            if (o == 0 || gord[slot_of(gv.rv, o - 1)] - gv.ord0 != g) first_o[g] = (int)o;
-        }
-    }
-    if (F)
-        for (int64_t i = t0; i < (int64_t)Q * gv.ng; i += stride) F[i] = 0;
-    if (fill_flags)
-        for (int64_t i = t0; i < Q; i += stride) flags[i] = 1;
-}
 
 // ---- scan: run folding ------------------------------------------------------------------------------------------
 // The epilogue of the grouped tile-scan policies.  Instead of a key per row, each lane folds its 4 consecutive rows into
@@ -180,49 +165,7 @@ __device__ __forceinline__ void group_fold_runs(const int64_t *gord, uint32_t *F
     }
 }
 
-// ---- select: compaction and the radix path ----------------------------------------------------------------------
-// grid (slices, Q): wave-aggregated appends of every composite >= cut[q] to the query's buffer
-__global__ void __launch_bounds__(CMP_THREADS)
-    group_compact_kernel(const int64_t *__restrict__ d_total, int64_t cap, int ring, const int64_t *__restrict__ gord,
-                         const uint32_t *__restrict__ F, const unsigned long long *__restrict__ cut,
-                         int *__restrict__ ccount, unsigned long long *__restrict__ cbuf) {
-    // hits gather in LDS first: one global atomic per block (one per wave with hits on a single counter per query
-    // serialised behind each other: 0.29 ms at Q = 16 over 200 k groups)
-    __shared__ unsigned long long lbuf[CMP_LCAP];
-    __shared__ int lcnt, gbase;
-    const int q = blockIdx.y, lane = threadIdx.x & 63;
-    const GroupView gv = group_view(d_total, cap, ring, gord);
-    const int64_t ng = gv.ng;
-    const uint32_t *Fq = F + (size_t)q * ng;
-    const unsigned long long c0 = cut[q];
-    const int64_t stride = (int64_t)gridDim.x * CMP_THREADS;
-    if (threadIdx.x == 0) lcnt = 0;
-    __syncthreads();
-    for (int64_t base = (int64_t)blockIdx.x * CMP_THREADS; base < ng; base += stride) {  // uniform per wave
-        const int64_t g = base + threadIdx.x;
-        unsigned long long c = 0;
-        if (g < ng) c = composite(Fq[g], (int)g);
-        const bool hit = g < ng && c >= c0;
-        const unsigned long long bal = __ballot(hit);
-        if (bal) {
-            int pos0 = 0;
-            if (lane == 0) pos0 = atomicAdd(&lcnt, __popcll(bal));
-            pos0 = __shfl(pos0, 0, 64);
-            const int pos = pos0 + __popcll(bal & ((1ull << lane) - 1ull));
-            if (hit && pos < CMP_LCAP) lbuf[pos] = c;
-        }
-    }
-    __syncthreads();
-    const int nb = lcnt;
-    if (threadIdx.x == 0) gbase = nb ? atomicAdd(&ccount[q], nb > CMP_LCAP ? SEL_CAP + 1 : nb) : 0;  // >: radix path
-    __syncthreads();
-    if (nb > CMP_LCAP) return;
-    for (int i = threadIdx.x; i < nb; i += CMP_THREADS) {
-        const int pos = gbase + i;
-        if (pos < SEL_CAP) cbuf[(size_t)q * SEL_CAP + pos] = lbuf[i];
-    }
-}
-
+// ---- select: the radix path ----------------------------------------------------------------------------------------
 // One block per query: the best `take` = min(M + 1, ng) groups by (fp32 max desc, group asc) over ALL groups.  Four
 // 8-bit radix passes find the take-th largest key T; then one ordered pass collects every key > T and the first needed
 // keys == T.  The overflow path of the select.
@@ -674,8 +617,7 @@ int grouped_topk(vm_memory *m, const GroupCall &c, typename Scan::Args a, const 
     int *flags = (int *)(ws + p.off_flags);
     {
         vm_prof_scope prof(ctx, VM_PROF_TOPK_SCAN, st);
-        group_table_kernel<<<p.tbl_blocks, 256, 0, st>>>(m->d_total, m->cap, m->ring, m->gord, Q, first_o, F, nullptr, 0);
-        VM_LAUNCH_CHECK(ctx);
+        if (int rc = vm_group_table(m, p.tbl_blocks, Q, first_o, F, nullptr, 0, st)) return rc;
         a.F = F;
         const int rc = vm_tile_scan<DT, Scan>(m, p, c.queries, Q, a, st);
         if (rc != VM_OK) return rc;
@@ -687,9 +629,7 @@ int grouped_topk(vm_memory *m, const GroupCall &c, typename Scan::Args a, const 
         unsigned long long *cbuf = (unsigned long long *)(ws + p.off_cbuf);
         Cut<<<Q, SEL_THREADS, 0, st>>>(m->d_total, m->cap, m->ring, m->gord, F, p.M + 1, cut, ccount);
         VM_LAUNCH_CHECK(ctx);
-        group_compact_kernel<<<dim3(p.cmp_slices, Q), CMP_THREADS, 0, st>>>(m->d_total, m->cap, m->ring, m->gord, F, cut,
-                                                                            ccount, cbuf);
-        VM_LAUNCH_CHECK(ctx);
+        if (int rc = vm_group_compact(m, p.cmp_slices, Q, F, cut, ccount, cbuf, st)) return rc;
         SelectFinal<<<Q, SEL_THREADS, 0, st>>>(m->d_total, m->cap, m->ring, m->gord, F, p.M + 1, ccount, cbuf, cand_g,
                                                cand_k, cand_n);
         VM_LAUNCH_CHECK(ctx);
@@ -706,10 +646,9 @@ int grouped_topk(vm_memory *m, const GroupCall &c, typename Scan::Args a, const 
 template <class SC>
 int grouped_exact(vm_memory *m, const GroupCall &c, const SC &sc) {
     const GPlan p = group_plan(m, c.Q, c.k);
-    group_table_kernel<<<p.tbl_blocks, 256, 0, c.stream>>>(m->d_total, m->cap, m->ring, m->gord, c.Q,
-                                                         (int *)(c.ws + p.off_first), nullptr,
-                                                         (int32_t *)(c.ws + p.off_flags), 1);
-    VM_LAUNCH_CHECK(m->ctx);
+    if (int rc = vm_group_table(m, p.tbl_blocks, c.Q, (int *)(c.ws + p.off_first), nullptr,
+                                (int32_t *)(c.ws + p.off_flags), 1, c.stream))
+        return rc;
     return vm_by_dtype(m, [&](auto dt) { return grouped_redo<decltype(dt)::value>(m, p, c, sc); });
 }
 

@@ -9,8 +9,9 @@
 //              bits of each of its queries (2 bytes per query, against the 128 bytes of tags of the scoped pre-test); a
 //              tile no query selects a live row of is skipped WITHOUT reading its rows and only zeroes its keys.
 //              Otherwise fp32 MFMA scores, F[q][slot] = okey32(score) for a selected live row, 0 for any other
-//   select   : topk_scope_select.h, unchanged: the best M + 1 selected rows by (fp32 key desc, age order asc)
-//   finalize : topk_scope_select.h's scope_finalize_kernel, unchanged: nothing in it is specific to scopes.  Certified
+//   select   : topk_key_image.hip, through topk_scope_select.h: the best M + 1 selected rows by (fp32 key desc, age order
+//              asc)
+//   finalize : topk_key_image.hip's scope_finalize_kernel: nothing in it is specific to scopes.  Certified
 //              when the mask selects at most M rows, or when the exact k-th score clears the (M+1)-th SELECTED fp32
 //              score / ||q|| by cert_eps(D), strictly.  Unselected rows have key 0 and never reach the certificate
 //   redo     : vm_topk_redo_scan under the MaskScope predicate (vm_internal.h, topk_exact.hip), then vm_topk_redo_merge
@@ -122,17 +123,15 @@ __global__ void __launch_bounds__(256)
 }
 
 // ---- host --------------------------------------------------------------------------------------------------
-int64_t mask_words(const vm_memory *m) { return (m->cap + 63) / 64 * 2; }
-
+// the mask operand's rules are vm_internal.h's; a misaligned or miscounted one is a bad argument here, with the others
 int mask_check(vm_memory *m, const RowCall &c, const uint32_t *masks, int n_masks, const int32_t *mask_index,
                size_t workspace_bytes, const char *who) {
     const bool ok = c.queries && masks && c.out_scores && c.out_rows && c.Q > 0 && n_masks > 0 &&
                     (mask_index || n_masks == 1 || n_masks == c.Q) && !((uintptr_t)masks & 3);
-    // the scan addresses a mask halfword by a 32-bit byte offset from `masks` (MaskScan::tile_bits)
-    if (ok && (int64_t)n_masks * mask_words(m) > ((int64_t)1 << 30))
-        return vm_fail(m->ctx, VM_ERR_UNSUPPORTED, "%s: more than 2^30 words of masks", who);
+    if (ok)
+        if (int rc = mask_limit_check(m, n_masks, who)) return rc;
     return vm_topk_check(m, nullptr, ok, c.queries, c.k, SKMAX, VM_ERR_INVALID, c.score_mode, c.ws, workspace_bytes,
-                         scope_plan(m, c.Q, c.k).total, who);
+                         vm_key_image_plan(m, c.Q, c.k).total, who);
 }
 
 // both entry points: the fast form (topk_scope_select.h key_image_topk under MaskScan; the scoped search's workspace, the
@@ -154,7 +153,7 @@ extern "C" int64_t vm_memory_mask_words(const vm_memory *m) { return m ? mask_wo
 
 extern "C" size_t vm_topk_masked_workspace_bytes(const vm_memory *m, int Q, int k) {
     if (!m || Q <= 0 || k <= 0 || k > SKMAX) return 0;
-    return scope_plan(m, Q, k).total;
+    return vm_key_image_plan(m, Q, k).total;
 }
 
 extern "C" int vm_topk_cosine_masked(vm_memory *m, const void *queries, int Q, int k, const uint32_t *masks,

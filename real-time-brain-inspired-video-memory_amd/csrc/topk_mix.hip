@@ -10,7 +10,7 @@
 //              sixteen MFMA columns that a one-vector query leaves empty hold the terms; the epilogue scales each
 //              column by its coefficient and sums the 16 lanes that hold one row's 16 scores, so only one key column per
 //              mixed query reaches memory: F[c][slot] = okey32(B) for a selected live row, 0 for any other
-//   select   : topk_scope_select.h, unchanged, with Q = C
+//   select   : topk_key_image.hip's vm_key_image_select, with Q = C
 //   finalize : mix_finalize_kernel: the exact W of the best M candidates; certified when at most M rows are selected
 //              or the exact k-th W clears dekey32(key of the (M+1)-th) + eps_mix(D, A), strictly
 //   redo     : mix_redo_scan_kernel (topk_redo_scan_kernel's structure, every admitted row scored exactly), then
@@ -390,9 +390,7 @@ __global__ void __launch_bounds__(MIX_THREADS)
 }
 
 // ---- host --------------------------------------------------------------------------------------------------
-int64_t mix_mask_words(const vm_memory *m) { return (m->cap + 63) / 64 * 2; }
-
-// scope_plan for C key rows, then what the pack leaves: the packed tiles, the coefficients, the term norms, A and the
+// vm_key_image_plan for C key rows, then what the pack leaves: the packed tiles, the coefficients, the term norms, A and the
 // domain flags
 struct MPlan : SPlan {
     ScanGeom scan;  // the tile scan's grid: 16 C columns
@@ -401,7 +399,7 @@ struct MPlan : SPlan {
 
 MPlan mix_plan(const vm_memory *m, int C, int k) {
     MPlan p;
-    static_cast<SPlan &>(p) = scope_plan(m, C, k);
+    static_cast<SPlan &>(p) = vm_key_image_plan(m, C, k);
     p.scan = vm_scan_geom(m, C * MIX_J, (m->cap + 15) / 16, TS_THREADS);
     WsBump ws;
     ws.off = p.total;
@@ -434,14 +432,8 @@ int mix_check(vm_memory *m, const MixCall &c, const char *who) {
     if (!c.queries || !c.weights) return vm_fail(ctx, VM_ERR_INVALID, "%s: null terms or weights", who);
     if (!c.out_scores || !c.out_rows) return vm_fail(ctx, VM_ERR_INVALID, "%s: null outputs", who);
     if (c.row_stride < 1) return vm_fail(ctx, VM_ERR_INVALID, "%s: row_stride=%lld < 1", who, (long long)c.row_stride);
-    if (c.masks) {  // mask_check's rules (topk_mask.hip), one mask per mixed query
-        if ((uintptr_t)c.masks & 3) return vm_fail(ctx, VM_ERR_INVALID, "%s: masks must be 4-byte aligned", who);
-        if (c.n_masks < 1 || !(c.mask_index || c.n_masks == 1 || c.n_masks == c.Q))
-            return vm_fail(ctx, VM_ERR_INVALID, "%s: %d masks for %d queries need a mask_index", who, c.n_masks, c.Q);
-        // the scan addresses a mask halfword by a 32-bit byte offset from `masks` (MixScan::tile_bits)
-        if ((int64_t)c.n_masks * mix_mask_words(m) > ((int64_t)1 << 30))
-            return vm_fail(ctx, VM_ERR_UNSUPPORTED, "%s: more than 2^30 words of masks", who);
-    }
+    if (c.masks)  // one mask per mixed query
+        if (int rc = mask_operand_check(m, c.masks, c.n_masks, c.mask_index, c.Q, who)) return rc;
     const size_t need = mix_plan(m, c.Q, c.k).mix_total;
     if (!c.ws || c.ws_bytes < need) return vm_fail(ctx, VM_ERR_INVALID, "%s: workspace %zu < %zu", who, c.ws_bytes, need);
     if (((uintptr_t)c.ws & 255) || ((uintptr_t)c.queries & 15) || ((uintptr_t)c.weights & 7))
@@ -503,12 +495,9 @@ int mix_run(vm_memory *m, const MixCall &c, bool exact) {
     const int C = c.Q;
     const MPlan p = mix_plan(m, C, c.k);
     const MixBufs b = mix_bufs(p, ws);
-    const MaskSel ms = {c.masks, c.mask_index, c.n_masks, mix_mask_words(m)};
+    const MaskSel ms = {c.masks, c.mask_index, c.n_masks, mask_words(m)};
     if (!exact) {
         uint32_t *F = (uint32_t *)ws;
-        int *cand_o = (int *)(ws + p.off_co);
-        uint32_t *cand_k = (uint32_t *)(ws + p.off_ck);
-        int *cand_n = (int *)(ws + p.off_cn);
         {
             vm_prof_scope prof(ctx, VM_PROF_TOPK_SCAN, st);
             if (int rc = mix_pack<DT>(m, c, b)) return rc;
@@ -517,29 +506,20 @@ int mix_run(vm_memory *m, const MixCall &c, bool exact) {
         }
         {
             vm_prof_scope prof(ctx, VM_PROF_TOPK_FINALIZE, st);
-            uint32_t *cut = (uint32_t *)(ws + p.off_cut);
-            int *ccount = (int *)(ws + p.off_cc);
-            unsigned long long *cbuf = (unsigned long long *)(ws + p.off_cbuf);
-            scope_cut_kernel<<<C, SEL_THREADS, 0, st>>>(m->d_total, m->cap, m->ring, F, p.fstride, p.M + 1, cut, ccount);
-            VM_LAUNCH_CHECK(ctx);
-            scope_compact_kernel<<<dim3(p.cmp_slices, C), CMP_THREADS, 0, st>>>(m->d_total, m->cap, m->ring, F,
-                                                                                p.fstride, cut, ccount, cbuf);
-            VM_LAUNCH_CHECK(ctx);
-            scope_select_kernel<<<C, SEL_THREADS, 0, st>>>(p.M + 1, ccount, cbuf, cand_o, cand_k, cand_n);
-            VM_LAUNCH_CHECK(ctx);
+            if (int rc = vm_key_image_select(m, p, F, C, ws, st)) return rc;
             const size_t lds = (size_t)c.J * m->D * 2;
             auto kern = mix_finalize_kernel<DT>;
             if (int rc = mix_lds_attr(m, kern, lds)) return rc;
             kern<<<C, MIX_THREADS, lds, st>>>(m->rows, m->norm64, b.tiles, c.weights, b.qn, b.A, b.dom, m->d_total,
-                                              m->cap, m->ring, m->D, c.J, cand_o, cand_k, cand_n, p.M, c.k, c.use_min,
-                                              c.min_score, c.row_stride, c.row_offset, c.out_scores, c.out_rows,
+                                              m->cap, m->ring, m->D, c.J, (const int *)(ws + p.off_co),
+                                              (const uint32_t *)(ws + p.off_ck), (const int *)(ws + p.off_cn), p.M, c.k,
+                                              c.use_min, c.min_score, c.row_stride, c.row_offset, c.out_scores, c.out_rows,
                                               c.out_uncertified, b.flags, c.out_query_flags);
             VM_LAUNCH_CHECK(ctx);
         }
     } else {
         if (int rc = mix_pack<DT>(m, c, b)) return rc;
-        fill_flags_kernel<<<(C + 255) / 256, 256, 0, st>>>(b.flags, C);
-        VM_LAUNCH_CHECK(ctx);
+        if (int rc = vm_fill_flags(m, b.flags, C, st)) return rc;
     }
     if (c.masks) return mix_redo<DT>(m, p, c, b, MaskScope{ms});
     return mix_redo<DT>(m, p, c, b, NoScope{});

@@ -24,7 +24,7 @@
 //              every redo (vm_topk_redo_merge; both topk_exact.hip).  Flags and
 //              counts are read on the device; near-empty when nothing is flagged.
 // Every launch reads the row count from the device and sizes its grid from the capacity: capturable.
-#include "topk_scope_select.h"  // the select stage (cut, compaction, selection) and the finalize: shared
+#include "topk_scope_select.h"  // the select stage (cut, compaction, selection) and the finalize: topk_key_image.hip
 #include "topk_tile_scan.h"
 
 namespace {
@@ -81,7 +81,7 @@ int scope_check(vm_memory *m, const RowCall &c, const int64_t *scope_lo, const i
                 const char *who) {
     return vm_topk_check(m, m->tag ? nullptr : "tagged (vm_memory_create_tagged)",
                          c.queries && scope_lo && scope_hi && c.out_scores && c.out_rows && c.Q > 0, c.queries, c.k,
-                         SKMAX, VM_ERR_INVALID, c.score_mode, c.ws, workspace_bytes, scope_plan(m, c.Q, c.k).total, who);
+                         SKMAX, VM_ERR_INVALID, c.score_mode, c.ws, workspace_bytes, vm_key_image_plan(m, c.Q, c.k).total, who);
 }
 
 // both entry points: the fast form (topk_scope_select.h key_image_topk under ScopeScan) or the exhaustive one
@@ -100,7 +100,7 @@ int scope_entry(vm_memory *m, const RowCall &c, const int64_t *scope_lo, const i
 
 extern "C" size_t vm_topk_scoped_workspace_bytes(const vm_memory *m, int Q, int k) {
     if (!m || Q <= 0 || k <= 0 || k > SKMAX) return 0;
-    return scope_plan(m, Q, k).total;
+    return vm_key_image_plan(m, Q, k).total;
 }
 
 extern "C" int vm_topk_cosine_scoped(vm_memory *m, const void *queries, int Q, int k, const int64_t *scope_lo,

@@ -1,252 +1,33 @@
-// The select stage over one fp32 key per (query, physical slot), key 0 = "not a candidate": the cut from a strided sample,
-// the parallel compaction of every slot at or above it and the block-wide selection of the best M + 1.  Written for the
-// scoped search (topk_scope.hip: key 0 = out of scope) and shared, unchanged, with the clip search (topk_clip.hip: key 0 =
-// no valid, in-scope window that could be a peak starts in the slot) and the masked search (topk_mask.hip: key 0 = the
-// query's mask does not select the slot).  The scoped and the masked search also share what follows the selection: the
-// exact finalize with the gap certificate, the workspace plan and the host driver (RowCall, key_image_topk,
-// key_image_exact): a search brings its scan policy and its row predicate (vm_internal.h), nothing else.  Each translation
-// unit gets its own copy of the kernels (anonymous namespace).
+// The interface of the select stage over one fp32 key per (query, physical slot), key 0 = "not a candidate": the cut from a
+// strided sample, the parallel compaction of every slot at or above it and the block-wide selection of the best M + 1.
+// Written for the scoped search (topk_scope.hip: key 0 = out of scope) and shared, unchanged, with the clip search
+// (topk_clip.hip: key 0 = no valid, in-scope window that could be a peak starts in the slot), the masked, the span and the
+// mixed search (topk_mask.hip, topk_span.hip, topk_mix.hip).  The scoped, the masked and the span search also share what
+// follows the selection: the exact finalize with the gap certificate, the workspace plan and the host driver (RowCall,
+// key_image_topk, key_image_exact): a search brings its scan policy and its row predicate (vm_internal.h), nothing else.
+// The kernels and their launches are compiled once, in topk_key_image.hip; here are the constants, the two
+// structs and the declarations another unit needs, and the host templates that have to see a scan policy or a predicate.
+// topk_group_parts.h reuses constant names with other values (SEL_CAP): no unit may include both headers.
 #pragma once
 #include "topk_select.h"
 #include "topk_tile_scan.h"  // TS_THREADS: the plan sizes the scan's grid
 
-namespace {
-
-constexpr int SEL_THREADS = 1024;  // cut and selection (one block per query)
-constexpr int SEL_SAMPLE = 16384;  // slots whose keys give each query's cut
-constexpr int SEL_CAP = 8192;      // rows at or above the cut a query keeps; more -> VM_FLAG_OVERFLOW
-constexpr int CMP_THREADS = 256;   // compaction
-constexpr int CMP_LCAP = 2048;     // hits one compaction block gathers in LDS before it flushes them
-constexpr int SF_THREADS = 256;    // finalize
-constexpr int SCMAX = 128;         // candidates per query kept by the select (M + 1 <= 81)
+constexpr int SEL_CAP = 8192;    // rows at or above the cut a query keeps; more -> VM_FLAG_OVERFLOW
+constexpr int SF_THREADS = 256;  // finalize
+constexpr int SCMAX = 128;       // candidates per query kept by the select (M + 1 <= 81)
 constexpr int SKMAX = 64;
 
-// ---- select ------------------------------------------------------------------------------------------------
-// composites (topk_select.h) of key and age order: ties at one key go to the older row
-// One block per query: cut[q] = the (M+1)-th largest key of a sample of SEL_SAMPLE slots, one per stride (all slots when
-// there are fewer), or 1 - every in-scope row - when the sample holds fewer than M + 1 in-scope rows.  At least
-// min(M + 1, in-scope rows) rows have a key >= the cut, and no out-of-scope row (key 0) has.
-__global__ void __launch_bounds__(SEL_THREADS)
-    scope_cut_kernel(const int64_t *__restrict__ d_total, int64_t cap, int ring, const uint32_t *__restrict__ F,
-                     int64_t fstride, int M1, uint32_t *__restrict__ cut, int *__restrict__ ccount) {
-    constexpr int PER = SEL_SAMPLE / SEL_THREADS;
-    const int q = blockIdx.x, tid = threadIdx.x;
-    const int64_t n = ring_view(*d_total, cap, ring).n;
-    const uint32_t *Fq = F + (size_t)q * fstride;
-    const int cnt = (int)(n < SEL_SAMPLE ? n : SEL_SAMPLE);
-    uint32_t v[PER];
-#pragma unroll
-    for (int j = 0; j < PER; ++j) {
-        const int i = j * SEL_THREADS + tid;
-        // one slot per stride, at a hashed offset inside it: a fixed stride of 64 slots would see one source only of
-        // two that alternate every 16 rows
-        int64_t p = i;
-        if (n > SEL_SAMPLE) p = (int64_t)i * n / SEL_SAMPLE + (int64_t)(((uint32_t)i * 2654435761u) >> 8) % (n / SEL_SAMPLE);
-        v[j] = i < cnt ? Fq[p] : 0u;
-    }
-    // the top 20 bits of the key are enough for a cut (a score resolution of 2^-11 relative): 20 counting steps, not 32.
-    // 0 when fewer than M1 sampled keys are in scope (every in-scope key is above 2^12)
-    const uint32_t T = block_kth_u32<SEL_THREADS>(v, M1, 12);
-    if (tid == 0) {
-        cut[q] = T ? T : 1u;
-        ccount[q] = 0;
-    }
-}
-
-// grid (slices, Q): every in-scope row with key >= cut[q] goes to the query's buffer as a composite.  Hits gather in
-// LDS and leave with one global atomic per flush.  ccount[q] ends as the exact number of hits; the buffer keeps the
-// first SEL_CAP.
-__global__ void __launch_bounds__(CMP_THREADS)
-    scope_compact_kernel(const int64_t *__restrict__ d_total, int64_t cap, int ring, const uint32_t *__restrict__ F,
-                         int64_t fstride, const uint32_t *__restrict__ cut, int *__restrict__ ccount,
-                         unsigned long long *__restrict__ cbuf) {
-    __shared__ unsigned long long lbuf[CMP_LCAP];
-    __shared__ int lcnt, gbase;
-    const int q = blockIdx.y, tid = threadIdx.x;
-    const RingView rv = ring_view(*d_total, cap, ring);
-    const int64_t n = rv.n;
-    const uint32_t *Fq = F + (size_t)q * fstride;
-    const uint32_t T = cut[q];
-    const int64_t stride = (int64_t)gridDim.x * CMP_THREADS * 4;
-    if (tid == 0) lcnt = 0;
-    __syncthreads();
-    int held_max = 0;  // block-uniform upper bound of the hits in lbuf
-    auto flush = [&]() {  // called by every thread
-        __syncthreads();  // every hit of the iterations so far is in lbuf and counted in lcnt
-        const int held = lcnt;
-        if (tid == 0 && held) gbase = atomicAdd(&ccount[q], held);
-        __syncthreads();
-        for (int i = tid; i < held; i += CMP_THREADS) {
-            const int pos = gbase + i;
-            if (pos < SEL_CAP) cbuf[(size_t)q * SEL_CAP + pos] = lbuf[i];
-        }
-        __syncthreads();
-        if (tid == 0) lcnt = 0;
-        held_max = 0;
-        __syncthreads();
-    };
-    for (int64_t base = (int64_t)blockIdx.x * CMP_THREADS * 4; base < n; base += stride) {  // uniform per block
-        const int64_t p = base + 4 * tid;  // 4 consecutive slots, 16-byte aligned (fstride is a multiple of 64)
-        uint4 k4 = make_uint4(0, 0, 0, 0);
-        if (p < n) k4 = *reinterpret_cast<const uint4 *>(Fq + p);
-        const uint32_t key[4] = {k4.x, k4.y, k4.z, k4.w};
-        int hits = 0;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) hits += (p + j < n && key[j] >= T) ? 1 : 0;  // T >= 1: never an out-of-scope row
-        if (hits) {  // rare: one LDS atomic per thread with hits
-            int pos = atomicAdd(&lcnt, hits);  // pos + hits <= CMP_LCAP: flushed before it could fill
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                if (p + j < n && key[j] >= T) lbuf[pos++] = composite(key[j], (int)order_of(rv, p + j));
-        }
-        held_max += 4 * __syncthreads_count(hits != 0);
-        if (held_max > CMP_LCAP - 4 * CMP_THREADS) flush();
-    }
-    flush();
-}
-
-// One block per query: the best take = min(M + 1, hits) composites of the compacted list.  cand_n[q] = take, or -1 when
-// the list overflowed (the finalize flags the query for the exhaustive redo).
-__global__ void __launch_bounds__(SEL_THREADS)
-    scope_select_kernel(int M1, const int *__restrict__ ccount, const unsigned long long *__restrict__ cbuf,
-                        int *__restrict__ cand_o, uint32_t *__restrict__ cand_k, int *__restrict__ cand_n) {
-    const int q = blockIdx.x, tid = threadIdx.x;
-    int *oo = cand_o + (size_t)q * SCMAX;
-    uint32_t *ok = cand_k + (size_t)q * SCMAX;
-    const int cnt = ccount[q];
-    if (cnt > SEL_CAP || cnt == 0) {  // uniform
-        if (tid == 0) cand_n[q] = cnt ? -1 : 0;
-        return;
-    }
-    const int take = cnt < M1 ? cnt : M1;
-    if (tid == 0) cand_n[q] = take;
-    select_best<SEL_THREADS, SEL_CAP, SCMAX>(cbuf + (size_t)q * SEL_CAP, cnt, take, oo, ok);
-}
-
-// ---- finalize ----------------------------------------------------------------------------------------------
-// One block per query.  Ranks the C candidates by (fp32 key desc, order asc): the first nc = min(C, M) are re-scored
-// exactly, the (M+1)-th (if any) bounds every other in-scope row.  "In scope" = has a nonzero key: nothing here knows
-// whether a tag range or a mask bit made it so.
-template <int DT>
-__global__ void __launch_bounds__(SF_THREADS)
-    scope_finalize_kernel(const uint16_t *__restrict__ mem, const double *__restrict__ norm64,
-                          const uint16_t *__restrict__ queries, const int64_t *__restrict__ d_total, int64_t cap,
-                          int ring, int D, const int *__restrict__ cand_o, const uint32_t *__restrict__ cand_k,
-                          const int *__restrict__ cand_n, int M, int k, int use_min, double min_score, int score_mode,
-                          int64_t row_stride, int64_t row_offset, double *__restrict__ out_scores,
-                          int64_t *__restrict__ out_rows, int *__restrict__ uncertified, int *__restrict__ flags,
-                          int *__restrict__ user_flags) {
-    extern __shared__ __attribute__((aligned(16))) char sf_dyn[];
-    uint16_t *ql = reinterpret_cast<uint16_t *>(sf_dyn);  // [D]
-    __shared__ int so[SCMAX], lo_[SCMAX];
-    __shared__ uint32_t sk[SCMAX], lk[SCMAX];
-    __shared__ double es[SCMAX];
-    __shared__ double qn_sh;
-    __shared__ int flag_sh;
-    const int q = blockIdx.x, tid = threadIdx.x;
-    const RingView rv = ring_view(*d_total, cap, ring);
-    const int C = cand_n[q];
-    if (C < 0) {  // uniform: more rows at the cut than the buffer holds -> the exhaustive redo answers this query
-        for (int i = tid; i < k; i += SF_THREADS) {
-            out_scores[(size_t)q * k + i] = 0.0;
-            out_rows[(size_t)q * k + i] = -1;
-        }
-        if (tid == 0) {
-            flags[q] = VM_FLAG_OVERFLOW;
-            if (user_flags) user_flags[q] = VM_FLAG_OVERFLOW;
-            if (uncertified) atomicAdd(uncertified, 1);
-        }
-        return;
-    }
-    const int nc = C < M ? C : M;
-    for (int i = tid; i < D / 8; i += SF_THREADS)
-        reinterpret_cast<uint4 *>(ql)[i] = reinterpret_cast<const uint4 *>(queries + (size_t)q * D)[i];
-    if (tid < C) {
-        lo_[tid] = cand_o[(size_t)q * SCMAX + tid];
-        lk[tid] = cand_k[(size_t)q * SCMAX + tid];
-    }
-    if (tid == 0) flag_sh = VM_FLAG_CERTIFIED;
-    __syncthreads();
-    if (tid < C) {  // rank by (fp32 key desc, order asc)
-        const int o = lo_[tid];
-        const uint32_t key = lk[tid];
-        int r = 0;
-        for (int j = 0; j < C; ++j) r += (lk[j] > key || (lk[j] == key && lo_[j] < o)) ? 1 : 0;
-        so[r] = o;
-        sk[r] = key;
-    }
-    if (tid == SF_THREADS - 1) qn_sh = __dsqrt_rn(ref_sumsq<DT>(ql, D));
-    __syncthreads();
-    const double qn = qn_sh;
-    if (tid < nc) {
-        const int64_t p = slot_of(rv, so[tid]);
-        es[tid] = ref_cosine(ref_dot<DT>(ql, mem + (size_t)p * D, D), qn, norm64[p]);
-    }
-    __syncthreads();
-    if (tid < nc) {
-        const double e = es[tid];
-        const int o = so[tid];
-        int r = 0;
-        for (int d = 0; d < nc; ++d) r += (es[d] > e || (es[d] == e && so[d] < o)) ? 1 : 0;
-        if (r < k) {
-            const double shown = shown_score(e, score_mode);
-            const bool pass = passes_min(use_min, shown, min_score);
-            out_scores[(size_t)q * k + r] = pass ? shown : 0.0;
-            out_rows[(size_t)q * k + r] = pass ? (rv.base + o) * row_stride + row_offset : -1;
-        }
-        // certification: the exact k-th score against the best fp32 score of an in-scope row that was not re-scored
-        const int kth = (k < nc ? k : nc) - 1;
-        if (r == kth && C > M && qn != 0.0 && !clears_gap(e, sk[M], qn, D)) flag_sh = VM_FLAG_GAP;
-    }
-    for (int i = nc + tid; i < k; i += SF_THREADS) {
-        out_scores[(size_t)q * k + i] = 0.0;
-        out_rows[(size_t)q * k + i] = -1;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        int f = flag_sh;
-        // domain of the certificate (topk_common.h cert_eps; bf16 only): outside it the in-call redo answers the query
-        if constexpr (DT == VM_BF16) {
-            if (f == VM_FLAG_CERTIFIED && rv.n > 0 && (d_total[VM_GSTATE_OUTSIDE] != 0 || cert_norm_outside(qn)))
-                f = VM_FLAG_GAP;
-        }
-        flags[q] = f;
-        if (user_flags) user_flags[q] = f;
-        if (f && uncertified) atomicAdd(uncertified, 1);
-    }
-}
-
-// ---- host: the workspace of a search that keeps F[q][slot], selects and finalizes (scoped, masked) ------------------
-struct SPlan : TopkGeom {
+// ---- host: the workspace ---------------------------------------------------------------------------------------
+// what the select stage reads of a plan: the geometry, the key image's row stride and where its arrays lie
+struct SelectPlan : TopkGeom {
     int64_t fstride;
-    size_t off_co, off_ck, off_cn, off_flags, off_cut, off_cc, off_cbuf, off_ps, off_po, total;
+    size_t off_co, off_ck, off_cn, off_cut, off_cc, off_cbuf;
 };
-
-SPlan scope_plan(const vm_memory *m, int Q, int k) {
-    SPlan p;
-    static_cast<TopkGeom &>(p) = vm_topk_geom(m, Q, k, TS_THREADS, VM_REDO_CHUNK_SCOPED);
-    p.fstride = (m->cap + 63) / 64 * 64;  // the columns' padding: a tail tile writes its 16 keys
-    WsBump ws;
-    ws.take((size_t)Q * (size_t)p.fstride * 4);  // F at offset 0: [Q][slot] fp32 keys
-    p.off_co = ws.take((size_t)Q * SCMAX * 4);
-    p.off_ck = ws.take((size_t)Q * SCMAX * 4);
-    p.off_cn = ws.take((size_t)Q * 4);
-    p.off_flags = ws.take((size_t)Q * 4);
-    p.off_cut = ws.take((size_t)Q * 4);
-    p.off_cc = ws.take((size_t)Q * 4);
-    p.off_cbuf = ws.take((size_t)Q * SEL_CAP * 8);
-    p.off_ps = ws.take((size_t)p.nblk * Q * k * 8);
-    p.off_po = ws.take((size_t)p.nblk * Q * k * 8);
-    p.total = ws.off;
-    return p;
-}
-
-// ---- host: the one driver of those searches ----------------------------------------------------------------
-// flags[0, n) = 1: every query (clip) is flagged, which is what makes a redo the exhaustive-only entry point
-__global__ void fill_flags_kernel(int32_t *__restrict__ flags, int n) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) flags[i] = 1;
-}
+// the workspace of a search that keeps F[q][slot] at offset 0, selects and finalizes (scoped, masked, span, mixed)
+struct SPlan : SelectPlan {
+    size_t off_flags, off_ps, off_po, total;
+};
+SPlan vm_key_image_plan(const vm_memory *m, int Q, int k);
 
 // what every entry point of a row search is called with, past the operands of its predicate
 struct RowCall {
@@ -262,6 +43,16 @@ struct RowCall {
     hipStream_t stream;
 };
 
+// ---- host: the launches (topk_key_image.hip) -------------------------------------------------------------------
+// cut -> compact -> select over the key image F [Q][p.fstride]: per key row the best p.M + 1 slots by (key desc, age
+// order asc) into cand_o / cand_k / cand_n at the plan's offsets in ws
+int vm_key_image_select(vm_memory *m, const SelectPlan &p, const uint32_t *F, int Q, char *ws, hipStream_t st);
+// the exact finalize of the candidates with the gap certificate, for the memory's dtype
+int vm_key_image_finalize(vm_memory *m, const SPlan &p, const RowCall &c);
+// flags[0, n) = 1: every query (clip) is flagged, which is what makes a redo the exhaustive-only entry point
+int vm_fill_flags(vm_memory *m, int32_t *flags, int n, hipStream_t st);
+
+// ---- host: the one driver of those searches ----------------------------------------------------------------
 // redo: flagged queries scored exhaustively over the rows pred admits, then the one merge of every redo
 template <class P>
 int key_image_redo(vm_memory *m, const SPlan &p, const RowCall &c, const P &pred) {
@@ -278,40 +69,19 @@ int key_image_redo(vm_memory *m, const SPlan &p, const RowCall &c, const P &pred
 // have fstride and F, which are the plan's and filled in here); pred: the same row set for the redo.
 template <int DT, class Scan, class P>
 int key_image_topk(vm_memory *m, const RowCall &c, typename Scan::Args a, const P &pred) {
-    vm_ctx *ctx = m->ctx;
-    hipStream_t st = c.stream;
-    char *ws = c.ws;
-    const int Q = c.Q;
-    const SPlan p = scope_plan(m, Q, c.k);
-    uint32_t *F = (uint32_t *)ws;
-    int *cand_o = (int *)(ws + p.off_co);
-    uint32_t *cand_k = (uint32_t *)(ws + p.off_ck);
-    int *cand_n = (int *)(ws + p.off_cn);
-    int *flags = (int *)(ws + p.off_flags);
+    const SPlan p = vm_key_image_plan(m, c.Q, c.k);
+    uint32_t *F = (uint32_t *)c.ws;
     {
-        vm_prof_scope prof(ctx, VM_PROF_TOPK_SCAN, st);
+        vm_prof_scope prof(m->ctx, VM_PROF_TOPK_SCAN, c.stream);
         a.fstride = p.fstride;
         a.F = F;
-        const int rc = vm_tile_scan<DT, Scan>(m, p, c.queries, Q, a, st);
+        const int rc = vm_tile_scan<DT, Scan>(m, p, c.queries, c.Q, a, c.stream);
         if (rc != VM_OK) return rc;
     }
     {
-        vm_prof_scope prof(ctx, VM_PROF_TOPK_FINALIZE, st);
-        uint32_t *cut = (uint32_t *)(ws + p.off_cut);
-        int *ccount = (int *)(ws + p.off_cc);
-        unsigned long long *cbuf = (unsigned long long *)(ws + p.off_cbuf);
-        scope_cut_kernel<<<Q, SEL_THREADS, 0, st>>>(m->d_total, m->cap, m->ring, F, p.fstride, p.M + 1, cut, ccount);
-        VM_LAUNCH_CHECK(ctx);
-        scope_compact_kernel<<<dim3(p.cmp_slices, Q), CMP_THREADS, 0, st>>>(m->d_total, m->cap, m->ring, F, p.fstride,
-                                                                            cut, ccount, cbuf);
-        VM_LAUNCH_CHECK(ctx);
-        scope_select_kernel<<<Q, SEL_THREADS, 0, st>>>(p.M + 1, ccount, cbuf, cand_o, cand_k, cand_n);
-        VM_LAUNCH_CHECK(ctx);
-        scope_finalize_kernel<DT><<<Q, SF_THREADS, (size_t)m->D * 2, st>>>(
-            m->rows, m->norm64, (const uint16_t *)c.queries, m->d_total, m->cap, m->ring, m->D, cand_o, cand_k, cand_n,
-            p.M, c.k, c.use_min, c.min_score, c.score_mode, c.row_stride, c.row_offset, c.out_scores, c.out_rows,
-            c.out_uncertified, flags, c.out_query_flags);
-        VM_LAUNCH_CHECK(ctx);
+        vm_prof_scope prof(m->ctx, VM_PROF_TOPK_FINALIZE, c.stream);
+        if (int rc = vm_key_image_select(m, p, F, c.Q, c.ws, c.stream)) return rc;
+        if (int rc = vm_key_image_finalize(m, p, c)) return rc;
     }
     return key_image_redo(m, p, c, pred);
 }
@@ -319,10 +89,7 @@ int key_image_topk(vm_memory *m, const RowCall &c, typename Scan::Args a, const 
 // the exhaustive-only entry point: every query flagged, then the redo
 template <class P>
 int key_image_exact(vm_memory *m, const RowCall &c, const P &pred) {
-    const SPlan p = scope_plan(m, c.Q, c.k);
-    fill_flags_kernel<<<(c.Q + 255) / 256, 256, 0, c.stream>>>((int32_t *)(c.ws + p.off_flags), c.Q);
-    VM_LAUNCH_CHECK(m->ctx);
+    const SPlan p = vm_key_image_plan(m, c.Q, c.k);
+    if (int rc = vm_fill_flags(m, (int32_t *)(c.ws + p.off_flags), c.Q, c.stream)) return rc;
     return key_image_redo(m, p, c, pred);
 }
-
-}  // namespace

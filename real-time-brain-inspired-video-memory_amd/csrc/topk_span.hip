@@ -9,8 +9,8 @@
 //              of tags in the scoped search, 2 bytes of mask per query in the masked one).  A tile no query wants is
 //              skipped without reading its rows and only zeroes its keys.  Otherwise fp32 MFMA scores,
 //              F[q][slot] = okey32(score) for a live row in the query's span, 0 for any other
-//   select   : topk_scope_select.h, unchanged
-//   finalize : topk_scope_select.h's scope_finalize_kernel, unchanged.  Certified when the span holds at most M live rows,
+//   select   : topk_key_image.hip, through topk_scope_select.h
+//   finalize : topk_key_image.hip's scope_finalize_kernel.  Certified when the span holds at most M live rows,
 //              or when the exact k-th score clears the (M+1)-th IN-SPAN fp32 score / ||q|| by cert_eps(D), strictly.  Rows
 //              outside the span have key 0 and never reach the certificate
 //   redo     : vm_topk_redo_scan under the RowSpan predicate (topk_exact.hip), then vm_topk_redo_merge
@@ -116,7 +116,7 @@ struct SpanScan {
 int span_check(vm_memory *m, const RowCall &c, const int64_t *row_lo, const int64_t *row_hi, size_t workspace_bytes,
                const char *who) {
     return vm_topk_check(m, nullptr, c.queries && row_lo && row_hi && c.out_scores && c.out_rows && c.Q > 0, c.queries,
-                         c.k, SKMAX, VM_ERR_INVALID, c.score_mode, c.ws, workspace_bytes, scope_plan(m, c.Q, c.k).total,
+                         c.k, SKMAX, VM_ERR_INVALID, c.score_mode, c.ws, workspace_bytes, vm_key_image_plan(m, c.Q, c.k).total,
                          who);
 }
 
@@ -138,7 +138,7 @@ int span_entry(vm_memory *m, const RowCall &c, const int64_t *row_lo, const int6
 
 extern "C" size_t vm_topk_span_workspace_bytes(const vm_memory *m, int Q, int k) {
     if (!m || Q <= 0 || k <= 0 || k > SKMAX) return 0;
-    return scope_plan(m, Q, k).total;
+    return vm_key_image_plan(m, Q, k).total;
 }
 
 extern "C" int vm_topk_cosine_span(vm_memory *m, const void *queries, int Q, int k, const int64_t *row_lo,

@@ -71,6 +71,23 @@ struct MaskSel {
     int n_masks;
     int64_t W;
 };
+// W of a memory: one bit per slot, in whole 64-bit pieces
+inline int64_t mask_words(const vm_memory *m) { return (m->cap + 63) / 64 * 2; }
+// The rules of a mask operand for Q queries, the same in every search that takes one.  The scans address a mask halfword
+// by a 32-bit byte offset from `masks` (MaskScan::tile_bits, MixScan::tile_bits): at most 2^30 words of masks.  The masked
+// search reports a misaligned or miscounted operand with its other arguments and uses the word limit alone.
+inline int mask_limit_check(const vm_memory *m, int n_masks, const char *who) {
+    if ((int64_t)n_masks * mask_words(m) > ((int64_t)1 << 30))
+        return vm_fail(m->ctx, VM_ERR_UNSUPPORTED, "%s: more than 2^30 words of masks", who);
+    return VM_OK;
+}
+inline int mask_operand_check(const vm_memory *m, const uint32_t *masks, int n_masks, const int32_t *mask_index, int Q,
+                              const char *who) {
+    if ((uintptr_t)masks & 3) return vm_fail(m->ctx, VM_ERR_INVALID, "%s: masks must be 4-byte aligned", who);
+    if (n_masks < 1 || !(mask_index || n_masks == 1 || n_masks == Q))
+        return vm_fail(m->ctx, VM_ERR_INVALID, "%s: %d masks for %d queries need a mask_index", who, n_masks, Q);
+    return mask_limit_check(m, n_masks, who);
+}
 // word offset of query q's mask, -1 = the empty mask (an index outside [0, n_masks))
 __host__ __device__ inline int64_t mask_offset(const MaskSel &ms, int q) {
     const int64_t i = ms.index ? ms.index[q] : (ms.n_masks == 1 ? 0 : q);

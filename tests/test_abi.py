@@ -153,3 +153,30 @@ def test_gemm_leaves_room_for_the_layernorm(built, tmp_path):
         if 2 * alloc(v) + ln_alloc > 512:
             over.append((k, v))
     assert not over, f"GEMM instantiations that no longer leave {ln_alloc} registers per SIMD: {over}"
+
+
+def test_no_kernel_is_compiled_twice(built, tmp_path):
+    """Every kernel symbol is defined in one gfx950 code object of libvidmem.so, the whole library over.  A kernel in a
+    header's anonymous namespace is compiled again by every translation unit that includes the header: five copies of
+    the key-image select stage and two of the grouped table and compaction were in the library that way,
+    and a per-kernel profile of one stage was spread over as many symbols.  Kernels that are identical under different
+    symbols inside one unit are not this test's business."""
+    objdump = "/opt/rocm/lib/llvm/bin/llvm-objdump"
+    readelf = "/opt/rocm/lib/llvm/bin/llvm-readelf"
+    if not (os.path.exists(objdump) and os.path.exists(readelf)):
+        pytest.skip("llvm tools of the ROCm image not found")
+    import shutil
+    so = str(tmp_path / "libvidmem.so")
+    shutil.copy(built.LIB_PATH, so)
+    subprocess.check_call([objdump, "--offloading", so], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, cwd=str(tmp_path))
+    units = {}
+    for f in sorted(os.listdir(tmp_path)):
+        if "gfx950" not in f:
+            continue
+        notes = subprocess.run([readelf, "--notes", str(tmp_path / f)], capture_output=True, text=True).stdout
+        for sym in re.findall(r"^\s*\.symbol:\s*(\S+)\.kd\s*$", notes, flags=re.M):   # one per kernel, none per argument
+            units.setdefault(sym, []).append(f)
+    n_units = len({f for fs in units.values() for f in fs})
+    assert n_units >= 20 and len(units) >= 300, (n_units, len(units))   # the whole library, the encoder's units included
+    twice = {s: fs for s, fs in units.items() if len(fs) > 1}
+    assert not twice, f"kernels defined in more than one code object: {twice}"

@@ -155,3 +155,52 @@ def test_renamed_and_changed_kernels_pair_by_base_name():
     assert pairs[("_Z4scanILi0ELi1EEvPi", "_Z4scanILi0E3TagEvPi")]["lines"] == 0
     assert pairs[("_Z4scanILi1ELi1EEvPi", "_Z4scanILi1E3TagEvPi")]["lines"] == 0
     assert pairs[(None, "_Z5otherPi")]["status"] == "only_b" and len(recs) == 3
+
+
+def test_pooled_compare_follows_kernels_between_units():
+    """Side A: cut_kernel in three units, move_kernel in another; side B: each once, in a new unit, move_kernel unchanged,
+    scan with another instruction, one new kernel."""
+    cut = ["s_load_dword s2, s[0:1], 0x0", "v_mov_b32_e32 v0, 1", "s_endpgm"]
+    move = ["v_mov_b32_e32 v0, 2", "s_endpgm"]
+    own = {u: {f"_Z3{u}Pi": ["v_mov_b32_e32 v0, 3", "s_endpgm"]} for u in ("aaa", "bbb", "ccc")}
+    side_a = [("aaa", {"_Z10cut_kernelPi": cut, **own["aaa"]}, {"_Z10cut_kernelPi": {"vgpr": 4}}),
+              ("bbb", {"_Z10cut_kernelPi": list(cut), **own["bbb"]}, {}),
+              ("ccc", {"_Z10cut_kernelPi": list(cut), **own["ccc"],
+                       "_Z4scanILi0EEvPi": ["s_load_dword s2, s[0:1], 0x8", "v_nop", "s_endpgm"]},
+               {"_Z4scanILi0EEvPi": {"vgpr": 8}}),
+              ("ddd", {"_Z11move_kernelPi": move}, {})]
+    side_b = [("aaa", own["aaa"], {}), ("bbb", own["bbb"], {}),
+              ("ccc", {**own["ccc"], "_Z4scanILi0EEvPi": ["s_load_dword s2, s[0:1], 0x8", "v_nop", "v_nop", "s_endpgm"]},
+               {"_Z4scanILi0EEvPi": {"vgpr": 9}}),
+              ("once", {"_Z10cut_kernelPi": list(cut), "_Z11move_kernelPi": list(move), "_Z10new_kernelPi": ["s_endpgm"]}, {})]
+    recs, surplus = KD.compare_pooled(side_a, side_b)
+    by_b = {r["b"]: r for r in recs}
+    assert len(recs) == 7
+    c = by_b["_Z10cut_kernelPi"]
+    assert c["status"] == "identical" and c["unit"] == "once" and c["a_units"] == ["aaa", "bbb", "ccc"]
+    mv = by_b["_Z11move_kernelPi"]
+    assert mv["status"] == "identical" and mv["unit"] == "once" and mv["a_units"] == ["ddd"]
+    sc = by_b["_Z4scanILi0EEvPi"]
+    assert sc["status"] == "differs" and sc["lines"] == 1 and sc["a"] == "_Z4scanILi0EEvPi"
+    assert sc["counts"] == {"a": {"instructions": 3, "vgpr": 8}, "b": {"instructions": 4, "vgpr": 9}}
+    assert by_b["_Z10new_kernelPi"]["status"] == "only_b" and by_b["_Z10new_kernelPi"]["a"] is None
+    assert all(by_b[f"_Z3{u}Pi"]["status"] == "identical" for u in own)
+    # what A holds and B does not: two of the three copies of cut_kernel, and the scan's former instructions
+    assert surplus == [{"symbol": "_Z10cut_kernelPi", "instructions": 3, "copies_a": 3, "copies_b": 1,
+                        "units": ["aaa", "bbb", "ccc"]},
+                       {"symbol": "_Z4scanILi0EEvPi", "instructions": 3, "copies_a": 1, "copies_b": 0, "units": ["ccc"]}]
+    text = KD.report_pooled(side_a, side_b, recs, surplus)
+    assert "A: 8 kernels in 4 code objects, 6 distinct" in text and "B: 7 kernels in 4 code objects, 7 distinct" in text
+    assert "B against A: 5 identical, 0 identical under another name, 1 differ, 1 only in B" in text
+    assert "A holds 3 copies that B does not hold, 9 instructions" in text
+    assert "3 -> 1  _Z10cut_kernelPi" in text
+
+
+def test_pooled_compare_finds_a_kernel_under_another_symbol():
+    body = ["v_mov_b32_e32 v1, 1", "s_endpgm"]
+    recs, surplus = KD.compare_pooled([("u0", {"_ZN12_GLOBAL__N_123scope_fill_flags_kernelEPii": body}, {})],
+                                      [("u1", {"_ZN12_GLOBAL__N_117fill_flags_kernelEPii": list(body)}, {})])
+    assert [(r["status"], r["a"], r["a_units"]) for r in recs] == [
+        ("renamed", "_ZN12_GLOBAL__N_123scope_fill_flags_kernelEPii", ["u0"])]
+    assert [(s["symbol"], s["copies_a"], s["copies_b"]) for s in surplus] == [
+        ("_ZN12_GLOBAL__N_123scope_fill_flags_kernelEPii", 1, 0)]

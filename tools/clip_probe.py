@@ -1,6 +1,6 @@
 """Clip search against the row top-k of the same frames, event-timed and warm, alternating in one process.
 
-  python tools/clip_probe.py [--iters 20] [--rows 1048576] [--out profiles/clip_probe.json]
+  python tools/clip_probe.py [--iters 20] [--rows 1048576] [--out profiles/clip_probe.json] [--lib other/libvidmem.so]
 
 Memory: 1 M x 768 fp16 of scene-structured rows (scenes of 24 - 40 rows, row = normalise(scene centre + 0.5 x unit noise)).
 Clips: C in {1, 16} of L = 16 consecutive stored rows plus 0.1 x unit noise, k = 10, min_sep = 16.
@@ -18,6 +18,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
 import vidmem  # noqa: E402,F401
+import vidmem._lib  # noqa: E402
 from vidmem.memory import EmbeddingMemory  # noqa: E402
 
 from scope_probe import alternate, fill  # noqa: E402
@@ -46,7 +47,10 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--rows", type=int, default=1 << 20)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--lib", default=None, help="another build of libvidmem.so to time")
     a = ap.parse_args()
+    if a.lib:
+        vidmem._lib.LIB_PATH = os.path.abspath(a.lib)
     n, D, L, k, sep = a.rows, 768, 16, 10, 16
     rows = scene_rows(n, D, 5)
     mem = fill(EmbeddingMemory(n, D, "f16"), rows)

@@ -19,7 +19,12 @@ A kernel only in A and one only in B that differ are reported as one differing p
 function's name without namespace, template arguments and signature); among several, the pairs with the fewest differing
 lines.  The tool only compares: it looks for no particular instruction.
 
-parse_disassembly, parse_notes and compare work on text and have no subprocess in them (tests/test_kernel_diff_cpu.py).
+``--pooled``: for two builds whose kernels moved between translation units (the sides may hold different numbers of code
+objects).  Every kernel of B, whatever unit holds it, is looked up among all kernels of A: identical under its symbol,
+identical under another, differing from its closest A kernel of the same base name, or only in B.  Then, per (symbol,
+instructions), the copies A holds and B no longer does.
+
+parse_disassembly, parse_notes, compare and compare_pooled work on text and have no subprocess in them (tests/test_kernel_diff_cpu.py).
 """
 import argparse
 import difflib
@@ -175,6 +180,82 @@ def report(unit, recs):
     return "\n".join(lines)
 
 
+def compare_pooled(side_a, side_b):
+    """The comparison for two builds whose kernels moved between translation units: every kernel of a side is pooled,
+    whatever unit holds it.  side_*: [(unit, disassembly, notes)].  Returns (recs, surplus).  recs, one per kernel of B
+    and unit that holds it: "status" ("identical": a kernel of A has these instructions under this symbol; "renamed":
+    under another symbol; "differs": from its closest A kernel of the same base name, with "counts" and "lines" as in
+    compare; "only_b"), "unit", "b", "a" and "a_units".  surplus, one per (symbol, instructions) that A holds more often
+    than B: "symbol", "instructions", "copies_a", "copies_b", "units" (A's)."""
+    by_sym, by_body, copies_b = {}, {}, {}
+    for unit, dis, notes in side_a:
+        for s, ins in dis.items():
+            by_sym.setdefault(s, []).append((unit, ins, notes.get(s, {})))
+            by_body.setdefault(tuple(ins), []).append((unit, s))
+    recs = []
+    for unit, dis, notes in side_b:
+        for s, ins in dis.items():
+            copies_b[s, tuple(ins)] = copies_b.get((s, tuple(ins)), 0) + 1
+            rec = {"unit": unit, "b": s, "a": None, "a_units": []}
+            same = [u for u, i, _ in by_sym.get(s, []) if i == ins]
+            if same:
+                rec.update(status="identical", a=s, a_units=same)
+            elif tuple(ins) in by_body:
+                sa = by_body[tuple(ins)][0][1]
+                rec.update(status="renamed", a=sa, a_units=[u for u, x in by_body[tuple(ins)] if x == sa])
+            else:
+                near = [(differing_lines(normalise(ia), normalise(ins)), sa, ua, ia, na)
+                        for sa, held in by_sym.items() if base_name(sa) == base_name(s) for ua, ia, na in held]
+                if near:
+                    lines, sa, ua, ia, na = min(near, key=lambda t: t[0])
+                    rec.update(status="differs", a=sa, a_units=[ua], lines=lines,
+                               counts={"a": dict(instructions=len(ia), **na),
+                                       "b": dict(instructions=len(ins), **notes.get(s, {}))})
+                else:
+                    rec["status"] = "only_b"
+            recs.append(rec)
+    surplus = []
+    for s, held in by_sym.items():
+        for body in dict.fromkeys(tuple(i) for _, i, _ in held):
+            units = [u for u, i, _ in held if tuple(i) == body]
+            if len(units) > copies_b.get((s, body), 0):
+                surplus.append({"symbol": s, "instructions": len(body), "copies_a": len(units),
+                                "copies_b": copies_b.get((s, body), 0), "units": units})
+    return recs, surplus
+
+
+def report_pooled(side_a, side_b, recs, surplus):
+    """The pooled comparison as text."""
+    def held(side):
+        bodies = [(s, tuple(i)) for _, dis, _ in side for s, i in dis.items()]
+        return f"{len(bodies)} kernels in {len(side)} code objects, {len(set(bodies))} distinct"
+    n = {k: sum(r["status"] == k for r in recs) for k in ("identical", "renamed", "differs", "only_b")}
+    lines = [f"== pooled\nA: {held(side_a)}\nB: {held(side_b)}",
+             f"B against A: {n['identical']} identical, {n['renamed']} identical under another name, "
+             f"{n['differs']} differ, {n['only_b']} only in B"]
+    for r in recs:
+        src = f"  [{r['unit']} <- A: {', '.join(r['a_units'])}]"
+        if r["status"] == "identical":
+            lines.append(f"  identical            {r['b']}{src}")
+        elif r["status"] == "renamed":
+            lines.append(f"  identical (renamed)  {r['a']}\n                    -> {r['b']}{src}")
+        elif r["status"] == "differs":
+            lines.append(f"  differs              {r['a']}" + ("" if r["a"] == r["b"] else f"\n                    -> {r['b']}")
+                         + src)
+            for key in ("instructions", "sgpr", "vgpr", "lds", "scratch"):
+                lines.append(f"      {key:<13}{r['counts']['a'].get(key, '?')} -> {r['counts']['b'].get(key, '?')}")
+            lines.append(f"      differing lines, s_load offsets normalised: {r['lines']}")
+        else:
+            lines.append(f"  only in B            {r['b']}  [{r['unit']}]")
+    gone = sum(s["copies_a"] - s["copies_b"] for s in surplus)
+    ins = sum((s["copies_a"] - s["copies_b"]) * s["instructions"] for s in surplus)
+    lines.append(f"A holds {gone} copies that B does not hold, {ins} instructions")
+    for s in surplus:
+        lines.append(f"  {s['copies_a']} -> {s['copies_b']}  {s['symbol']}  ({s['instructions']} instructions; A: "
+                     f"{', '.join(s['units'])})")
+    return "\n".join(lines)
+
+
 # ---- the subprocess half ---------------------------------------------------------------------------------------------
 def read_code_object(path):
     dis = subprocess.check_output([os.path.join(LLVM, "llvm-objdump"), "-d", "--no-show-raw-insn", "--no-leading-addr",
@@ -213,6 +294,8 @@ def main():
     ap.add_argument("b", help="the same of side B")
     ap.add_argument("--files", nargs="*", default=None, help="with directories: the .hip files to compare, without suffix")
     ap.add_argument("--names", nargs=2, default=None, metavar=("A", "B"), help="what the report calls the two sides")
+    ap.add_argument("--pooled", action="store_true",
+                    help="compare all kernels of A with all kernels of B, whatever unit holds them (kernels that moved)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     with tempfile.TemporaryDirectory() as tmp:
@@ -229,11 +312,21 @@ def main():
                 units.append((name + ".hip", pa, pb))
         else:
             ua, ub = library_code_objects(args.a, tmp, "a"), library_code_objects(args.b, tmp, "b")
-            if len(ua) != len(ub):
-                sys.exit(f"kernel_diff: {len(ua)} code objects in A, {len(ub)} in B")
-            units = [(na, pa, pb) for (na, pa), (_, pb) in zip(ua, ub)]
+            if args.pooled:
+                units = []
+            elif len(ua) != len(ub):
+                sys.exit(f"kernel_diff: {len(ua)} code objects in A, {len(ub)} in B (--pooled compares such builds)")
+            else:
+                units = [(na, pa, pb) for (na, pa), (_, pb) in zip(ua, ub)]
         na, nb = args.names or (args.a, args.b)
         text = [f"A = {na}\nB = {nb}"]
+        if args.pooled:
+            if os.path.isdir(args.a):
+                ua, ub = [(n, pa) for n, pa, _ in units], [(n, pb) for n, _, pb in units]
+            side_a = [(n, *read_code_object(p)) for n, p in ua]
+            side_b = [(n, *read_code_object(p)) for n, p in ub]
+            text.append(report_pooled(side_a, side_b, *compare_pooled(side_a, side_b)))
+            units = []
         for name, pa, pb in units:
             text.append(report(name, compare(*read_code_object(pa), *read_code_object(pb))))
     text = "\n\n".join(text) + "\n"

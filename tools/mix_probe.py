@@ -1,6 +1,6 @@
 """Mixed-query top-k against the masked top-k, event-timed and warm.
 
-  python tools/mix_probe.py [--rows 1000000] [--iters 20] [--out profiles/mix_probe.json] [--root other/checkout]
+  python tools/mix_probe.py [--rows 1000000] [--iters 20] [--out profiles/mix_probe.json] [--root other/checkout | --lib other/libvidmem.so]
 
 One process.  Memory: ``--rows`` x 768 fp16 scene-structured rows (a centre per 16 rows + small noise), k = 10.  In the
 same process, taking turns: ``EmbeddingMemory.topk_mix`` at (C, J) = (1, 1), (1, 4), (1, 16), (16, 4) (vm_topk_cosine_mix,
@@ -33,10 +33,14 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--root", default=None, help="another built checkout to import vidmem from (an A/B against a parent "
                     "commit)")
+    ap.add_argument("--lib", default=None, help="another build of libvidmem.so with this tree's ABI to time")
     a = ap.parse_args()
     sys.path.insert(0, os.path.abspath(a.root) if a.root else HERE)
     import torch
     import vidmem  # noqa: F401
+    import vidmem._lib
+    if a.lib:
+        vidmem._lib.LIB_PATH = os.path.abspath(a.lib)
     from vidmem.memory import EmbeddingMemory
     from group_probe import TD, clustered          # these find vidmem already imported
     from mask_probe import timed
