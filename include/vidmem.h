@@ -813,12 +813,17 @@ int vm_range_cosine_exact(vm_memory *mem, const void *queries, int Q, double min
  * src/pipeline/retriever_hybrid.py:494-504 (query vs segment embeddings) and a checker for the scan.
  * rows [S, D] dtype need not live in a vm_memory.  dtype VM_F32 takes fp32 operands: an embedder that returns fp32
  * values (every OpenAI-compatible server does) is then scored on its UN-rounded vectors, as the reference scores them
- * (:497), so `>= compression_threshold` decisions cannot flip on a 16-bit rounding. */
+ * (:497), so `>= compression_threshold` decisions cannot flip on a 16-bit rounding.
+ * 16-bit operands: D a multiple of 8 (VM_ERR_UNSUPPORTED otherwise), any S; VM_F32: any D >= 1.  S == 0 is VM_OK and
+ * writes nothing (rows and out may then be null, as the address of an empty device tensor is). */
 int vm_cosine_exact(vm_ctx *ctx, const void *queries, int Q, const void *rows, int64_t S, int D, int dtype,
                     double *out, void *stream);
 /* The k best columns of every row of an all-pairs score matrix (vm_cosine_exact's output), by the order relation of
  * vm_topk_cosine: (score descending, column ascending).  scores [Q,S] fp64; col_limit (device int64 [Q], may be NULL):
- * query q ranks only columns < col_limit[q].  out_rows = row_base + column, -1 / 0.0 padded.  With vm_cosine_exact
+ * query q ranks only columns < col_limit[q].  col_limit is clamped to [0, S]: a negative limit admits no column (all
+ * -1 / 0.0), a limit above S admits all S, NULL means S for every query.  Equal scores (+0.0 and -0.0 are equal) come out
+ * in column order and every returned score keeps the bits of its own entry; +-inf entries rank like any other value; NaN
+ * is undefined, as in the reference.  k may exceed S.  out_rows = row_base + column, -1 / 0.0 padded.  With vm_cosine_exact
  * and vm_topk_merge this ranks the frames of a look-ahead group against the group's own EARLIER chunks, rows that are
  * about to be appended: what the reference's chunk-by-chunk loop would have stored by the time each chunk is searched
  * (src/pipeline/vlm_extractor.py:44-74; the same stable sort as src/components/pre_llm_injector.py:369). */
@@ -826,7 +831,10 @@ int vm_topk_select(vm_ctx *ctx, const double *scores, int Q, int64_t S, const in
                    int64_t row_base, double *out_scores, int64_t *out_rows, void *stream);
 /* Merge `parts` per-shard results (each [Q,k], sorted as above, -1 padded) into the global top-k:
  * the step after the RCCL all-gather (and the cross-query max-merge input of pre_llm_injector.py:238-249).
- * scores [parts,Q,k] fp64, rows [parts,Q,k] int64. */
+ * scores [parts,Q,k] fp64, rows [parts,Q,k] int64.  Entries with row < 0 are padding and are dropped; the rest is ordered
+ * by (score descending, row ascending) and the first k are kept, -1 / 0.0 padded.  Callers merge DISJOINT row sets (the
+ * shards of a memory; the memory and a look-ahead group): the merge does not de-duplicate.  A (score, row) pair that
+ * occurs in two parts comes out twice, the copies adjacent, the earlier part's first. */
 int vm_topk_merge(vm_ctx *ctx, const double *scores, const int64_t *rows, int parts, int Q, int k,
                   double *out_scores, int64_t *out_rows, void *stream);
 

@@ -323,7 +323,8 @@ int vm_topk_redo_merge(vm_memory *m, const double *part_s, const int64_t *part_o
 
 extern "C" int vm_cosine_exact(vm_ctx *ctx, const void *queries, int Q, const void *rows, int64_t S, int D,
                                int dtype, double *out, void *stream) {
-    if (!ctx || !queries || !out || Q <= 0 || S < 0 || (S > 0 && !rows))
+    // S == 0: out [Q, 0] holds nothing, and an empty device tensor's address is null - neither rows nor out is needed
+    if (!ctx || !queries || Q <= 0 || S < 0 || (S > 0 && (!rows || !out)))
         return vm_fail(ctx, VM_ERR_INVALID, "vm_cosine_exact: bad arguments");
     if (S == 0) return VM_OK;
     dim3 grid((unsigned)((S + 255) / 256), Q);
