@@ -60,7 +60,19 @@ int vm_abi_version(void);
  * out_S x out_S, BGR->RGB, x*(1/(255*std)) - mean/std, cast to `dtype`.
  * layout CHW    : out [B,3,S,S]
  * layout PATCHES: out [B,(S/patch)^2,k_pad], k index = c*patch*patch + py*patch + px, zero-padded to k_pad
- *                 (the patch-embed GEMM's A operand; k_pad = vm_encoder_patch_k(enc)). */
+ *                 (the patch-embed GEMM's A operand; k_pad = vm_encoder_patch_k(enc)).
+ * The value of one output element, every operation in fp32 and rounded once (no fused multiply-add), d = ox or oy,
+ * n = W or H:   scale = (float)n / (float)out_S;  src = max(scale * (d + 0.5f) - 0.5f, 0);  i0 = min(floor(src), n - 1);
+ * i1 = min(i0 + 1, n - 1);  lam = src - i0;  top = (1 - lx) * p[y0][x0] + lx * p[y0][x1], bot likewise on row y1,
+ * val = (1 - ly) * top + ly * bot;  out = (dtype)(val * a + b) with a = 1.0f / (255.0f * std[c]), b = -mean[c] / std[c]
+ * and the cast rounding to nearest even, subnormals kept.  oracle/frames_ref.py preprocess_ref is this expression, and
+ * the output equals it bit for bit (tests/test_preprocess_gpu.py).
+ * Alignment: frames may start at ANY byte address (a view into a larger buffer; frames already at out_S x out_S are read
+ * in 8-byte words only when the pointer is 8-byte aligned, the result is the same either way).  out must be 16-byte
+ * aligned: it is written in 16-byte pieces.
+ * Returns VM_ERR_INVALID for a null ctx / frames / mean / std / out, B, H or W <= 0, a dtype other than VM_F16 / VM_BF16,
+ * an unknown layout, PATCHES with patch <= 0, out_S % patch != 0, k_pad % 8 != 0 or k_pad < 3 * patch * patch, a std[c]
+ * that is not > 0, or a misaligned out; VM_ERR_UNSUPPORTED for out_S <= 0 or out_S % 8 != 0.  Nothing is enqueued then. */
 int vm_preprocess(vm_ctx *ctx, const uint8_t *frames_hwc_bgr, int B, int H, int W, const float mean_host[3],
                   const float std_host[3], int out_S, int dtype, int layout, int patch, int k_pad, void *out,
                   void *stream);

@@ -10,6 +10,12 @@
       to a remote service as JPEG, :121-128): bilinear, half-pixel centres, no antialias, edge clamp
       (== torch.nn.functional.interpolate(mode="bilinear", align_corners=False), cross-checked in
       tests/test_frames_oracle.py), BGR->RGB, x*(1/(255*std)) - mean/std in fp32, round to fp16/bf16.
+      Its expression IS the definition of vm_preprocess (include/vidmem.h states it operation by operation): every
+      operation in fp32 and rounded once, no fused multiply-add - scale = n_in / n_out, src = max(scale * (d + 0.5) - 0.5, 0),
+      i0 = min(floor(src), n_in - 1), i1 = min(i0 + 1, n_in - 1), lam = src - i0; top = (1 - lx) * p00 + lx * p01, bot
+      likewise, val = (1 - ly) * top + ly * bot, out = val * a + b with a = 1 / (255 * std), b = -mean / std; then one
+      round-to-nearest-even cast that keeps subnormals.  The device output equals it bit for bit
+      (tests/test_preprocess_gpu.py; tests/preprocess_ref.py restates it per element and bounds it against float64).
 """
 from __future__ import annotations
 

@@ -146,7 +146,8 @@ struct PreArgs {
     const uint8_t *src;
     void *dst;
     int B, H, W, S, patch, k_pad, layout;
-    float ax, ay;  // source/dest scale (W/S, H/S) in fp32
+    int src_aligned8;  // ((uintptr_t)src & 7) == 0: the identity fast path may read the frames as uint2
+    float ax, ay;      // source/dest scale (W/S, H/S) in fp32
     float a[3], b[3];
 };
 
@@ -190,11 +191,13 @@ __global__ void __launch_bounds__(256) preprocess_kernel(PreArgs p0) {
         }
         const uint8_t *frame = p.src + (size_t)b * p.H * p.W * 3;
         uint16_t o8[8];
-        if (PATCH == 16 && p.H == p.S && p.W == p.S) {
+        if (PATCH == 16 && p.H == p.S && p.W == p.S && p.src_aligned8) {
             // Frames already at the encoder's size (the bench's 224 x 224 input): the bilinear weights are exactly
             // (1, 0), so the result is the source pixel itself - same value, same roundings as the general path below.
-            // The 8 outputs of a chunk are 8 consecutive pixels of one channel: 24 contiguous, 8-byte aligned bytes
-            // instead of 32 single-byte gathers.
+            // The 8 outputs of a chunk are 8 consecutive pixels of one channel: 24 contiguous bytes instead of 32
+            // single-byte gathers.  Their offset in the buffer, b * S * S * 3 + (oy * S + ox) * 3 with 8 | ox and 8 | S,
+            // is a multiple of 8, so they are 8-byte aligned exactly when the caller's pointer is (src_aligned8, set
+            // by the host); a frame pointer at any other byte takes the byte loads of the general path.
             constexpr int chunks = KPAD / 8;
             const int patch_idx = (int)(r / chunks);
             const int k0 = (int)(r - (int64_t)patch_idx * chunks) * 8;
@@ -274,6 +277,7 @@ extern "C" int vm_preprocess(vm_ctx *ctx, const uint8_t *frames, int B, int H, i
         return vm_fail(ctx, VM_ERR_INVALID, "vm_preprocess: bad arguments");
     if (out_S <= 0 || out_S % 8 != 0) return vm_fail(ctx, VM_ERR_UNSUPPORTED, "out_S=%d must be a multiple of 8", out_S);
     if (dtype != VM_F16 && dtype != VM_BF16) return vm_fail(ctx, VM_ERR_INVALID, "bad dtype %d", dtype);
+    if ((uintptr_t)out & 15) return vm_fail(ctx, VM_ERR_INVALID, "vm_preprocess: out must be 16-byte aligned");
     PreArgs p;
     p.src = frames;
     p.dst = out;
@@ -282,6 +286,7 @@ extern "C" int vm_preprocess(vm_ctx *ctx, const uint8_t *frames, int B, int H, i
     p.W = W;
     p.S = out_S;
     p.layout = layout;
+    p.src_aligned8 = ((uintptr_t)frames & 7) == 0;
     p.patch = 0;
     p.k_pad = 0;
     if (layout == VM_LAYOUT_PATCHES) {

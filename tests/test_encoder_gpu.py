@@ -14,6 +14,7 @@ import torch
 
 from oracle import frames_ref as F
 from oracle import vit_ref as V
+from tests import preprocess_ref as PR
 
 pytestmark = pytest.mark.gpu
 
@@ -91,16 +92,19 @@ def test_preprocess_matches_oracle(hw, dtype):
     frames = syn.frames_u8(1234, 2, hw[0], hw[1])
     ft = torch.from_numpy(frames).cuda()
     for layout in ("chw", "patches"):
-        got = enc.preprocess(ft, layout=layout).float().cpu().numpy()
+        got = enc.preprocess(ft, layout=layout)
         want = F.preprocess_ref(frames, spec["image"], spec["mean"], spec["std"], layout=layout,
                                 patch=spec["patch"], k_pad=enc.patch_k)
-        want16 = torch.from_numpy(want).to(TD[dtype]).float().numpy()
-        # same fp32 expression on both sides; allow one 16-bit rounding flip
-        ulp = 2.0 ** (-10 if dtype == "f16" else -7)
-        assert np.abs(got - want16).max() <= ulp * max(1.0, np.abs(want16).max()), (hw, layout)
-        assert (got == want16).mean() > 0.999
+        assert tuple(got.shape) == want.shape and got.dtype == TD[dtype]
+        # same fp32 expression and the same cast on both sides: the bit patterns are equal, signed zeros and f16
+        # subnormals included (tests/test_preprocess_gpu.py runs the whole case table this way)
+        bits = got.contiguous().view(torch.int16).cpu().numpy()
+        want_bits = PR.bits16(want.reshape(-1), dtype).reshape(want.shape)
+        assert np.array_equal(want_bits, torch.from_numpy(want).to(TD[dtype]).view(torch.int16).numpy())
+        differ = bits != want_bits
+        assert not differ.any(), (hw, layout, int(differ.sum()), np.argwhere(differ)[:4].tolist())
         if layout == "patches":
-            assert (got[..., 3 * spec["patch"] ** 2:] == 0).all()
+            assert not bits[..., 3 * spec["patch"] ** 2:].any()  # pad columns: the +0 pattern
 
 
 def test_preprocess_identity_is_exact():
