@@ -651,6 +651,76 @@ int vm_topk_cosine_mix_exact(vm_memory *mem, const void *terms, const double *we
                              const uint32_t *masks, int n_masks, const int32_t *mask_index, int use_min_score,
                              double min_score, int64_t row_stride, int64_t row_offset, double *out_scores,
                              int64_t *out_rows, void *workspace, size_t workspace_bytes, void *stream);
+/* Biased top-k: the k best rows by COSINE PLUS A PER-ROW PRIOR.  A preference that is not a filter: recency, a decaying
+ * or reinforced strength per stored frame, an importance weight from metadata, a boost for the rows another retrieval leg
+ * found.  The best k rows of cos + prior do not follow from the best k rows of cos, however large a pool is fetched.
+ * The bias column: a device array of S = vm_memory_bias_stride(mem) fp32 values, S = 32 x vm_memory_mask_words (the
+ * capacity rounded up to 64); several columns lie back to back as [n_bias][S], 16-byte aligned.  Entry s belongs to the
+ * row in physical slot s = row_id mod capacity - the masks' rule exactly -, an entry whose slot holds no live row is ignored
+ * by every consumer, and a column speaks about ROW IDS: it goes stale after an erase or a ring overwrite, as a mask does.
+ * bias_index: device int32 [Q] or NULL.  NULL: column 0 serves every query when n_bias == 1, column q serves query q when
+ * n_bias == Q; any other count with a NULL index is VM_ERR_INVALID.  An index outside [0, n_bias) is the ZERO column, never
+ * an out-of-range read.  bias_weight: device fp64 [Q] (beta_q; on the device, like the mixed weights: a captured graph
+ * replays with rewritten weights), or NULL for 1.0 for every query.  More than 2^30 bias values in one call are
+ * VM_ERR_UNSUPPORTED (the mask limit's answer), so that offsets stay 32-bit.
+ * Score of row r for query q:  S(q, r) = e(q, r) + beta_q * b[slot(r)],  e = the raw reference cosine (vm_topk_cosine's
+ * fp64 value; 0.0 when either norm is zero), b widened exactly to fp64, one fp64 rounding for the product and one for the
+ * sum, never fused.  masks: NULL = every live row (n_masks and mask_index are then ignored); otherwise masks, n_masks and
+ * mask_index mean exactly what they mean in vm_topk_cosine_masked.
+ * Result: the live rows the mask selects ranked by (S descending, row id ascending), those with S > min_score kept when
+ * use_min_score != 0 (strict; raw only: S is not confined to [-1, 1], so there is no score_mode), first k: out_scores [Q,k]
+ * the fp64 S bit for bit, out_rows [Q,k] global row ids (row_id * row_stride + row_offset), 0.0 / -1 padded.  The result of a
+ * query depends on the memory, its own vector, column, weight and mask and the arguments only, not on the other queries of
+ * the call.  Non-finite bias values or weights are undefined, as stored NaN is.
+ * Identities: beta_q = 0, or a column of zeros, gives vm_topk_cosine + vm_topk_redo_flagged bit for bit, and with a mask
+ * vm_topk_cosine_masked: the reference cosine is never -0.0 (its dot product starts at +0.0, a zero norm gives 0.0), and
+ * e + (+-0.0) = e for every other e.
+ * ALWAYS the exhaustive answer, like the masked search: the fp32 MFMA tile scan computes, one query per column,
+ * B = fl32(fl32(fl32(1 / ||q||) * s) + fl32(fl32(beta) * b)) per selected live row from its fp32 score s and one 4-byte bias
+ * value read next to the row; the best M = k + max(8, k/4) selected rows by B are re-scored exactly, and a query is certified
+ * when its mask selects at most M live rows or the exact k-th S is strictly above B* + eps_bias(D, B*), B* the (M+1)-th
+ * scanned score and eps_bias(D, B) = 2 (D + 8) 2^-24 + 2^-21 + 2^-22 |B|.  The bound holds when |beta| is 0 or lies in
+ * [2^-20, 2^20], every selected row's |b| <= 2^40 and the query's and every stored norm is 0 or in [2^-40, 2^40]; outside,
+ * and for any other query (VM_FLAG_GAP; VM_FLAG_OVERFLOW: more than 8192 selected rows at the query's cut), the query is
+ * counted in *out_uncertified (may be NULL), marked in out_query_flags [Q] (vm_topk_flag; may be NULL) and redone
+ * exhaustively over its selected rows on the device inside the same call.
+ * Any memory: plain, grouped, tagged, ring.  No host read-back, no allocation, no synchronisation: every launch reads the
+ * row count on the device and sizes its grid from the capacity, so the call is capturable; a replay sees bias values,
+ * weights, indices, queries and masks rewritten in place and the rows appended since.  1 <= k <= 64, Q >= 1.
+ * VM_ERR_INVALID (with a vm_last_error text) for k outside [1, 64], Q < 1, NULL queries, bias or outputs, row_stride < 1,
+ * a bias that is not 16-byte aligned or whose count fits no rule above, the mask operand's refusals of
+ * vm_topk_cosine_mix, a workspace below vm_topk_bias_workspace_bytes; the workspace must be 256-byte, queries 16-byte and
+ * bias_weight 8-byte aligned.  All before any launch, with the outputs untouched.
+ * Workspace: vm_topk_bias_workspace_bytes (the masked search's plus five small per-query arrays); 0 for arguments out of
+ * range. */
+int64_t vm_memory_bias_stride(const vm_memory *mem);
+size_t vm_topk_bias_workspace_bytes(const vm_memory *mem, int Q, int k);
+int vm_topk_cosine_biased(vm_memory *mem, const void *queries, int Q, int k, const float *bias, int n_bias,
+                          const int32_t *bias_index, const double *bias_weight, const uint32_t *masks, int n_masks,
+                          const int32_t *mask_index, int use_min_score, double min_score, int64_t row_stride,
+                          int64_t row_offset, double *out_scores, int64_t *out_rows, int32_t *out_uncertified,
+                          int32_t *out_query_flags, void *workspace, size_t workspace_bytes, void *stream);
+/* The same contract, exhaustive only: every selected (query, row) pair scored exactly (slow; tests, and a checker). */
+int vm_topk_cosine_biased_exact(vm_memory *mem, const void *queries, int Q, int k, const float *bias, int n_bias,
+                                const int32_t *bias_index, const double *bias_weight, const uint32_t *masks,
+                                int n_masks, const int32_t *mask_index, int use_min_score, double min_score,
+                                int64_t row_stride, int64_t row_offset, double *out_scores, int64_t *out_rows,
+                                void *workspace, size_t workspace_bytes, void *stream);
+/* The device-side bias builders; stream-ordered, no host read-back, capturable.  out_bias: ONE column, S fp32 values,
+ * 16-byte aligned.
+ * vm_bias_from_rows: stores values[i] (device fp32 [n]) in the slot of every live row named in row_ids, device int64 [n] as
+ *   any search wrote them (row * row_stride + row_offset; row_stride >= 1).  -1 entries, ids not of that form and ids of
+ *   rows that are not live are skipped: vm_mask_from_rows's rules.  clear_first != 0: the column is zeroed first; 0: the
+ *   other entries keep what they hold.  Duplicates that carry DIFFERENT values leave one of them, which one is not
+ *   defined (plain stores race); duplicates with one value are fine.
+ * vm_bias_from_tags: tagged memories only (VM_ERR_INVALID otherwise).  Linear recency: a live slot with tag t != INT64_MIN
+ *   gets b = (float)(per_ms * (double)d), d = (t & (2^40 - 1)) - t_ref_ms exact in int64 and in fp64, one fp64 rounding for
+ *   the product, then round to nearest even to fp32.  Untagged live rows and slots without a live row get `fill`.  Writes
+ *   all S entries.  per_ms = 1e-6: a frame loses 0.06 of score per minute of age; any other shape of decay is the
+ *   caller's own expression over the column. */
+int vm_bias_from_rows(vm_memory *mem, const int64_t *row_ids, const float *values, int64_t n, int64_t row_stride,
+                      int64_t row_offset, int clear_first, float *out_bias, void *stream);
+int vm_bias_from_tags(vm_memory *mem, int64_t t_ref_ms, double per_ms, float fill, float *out_bias, void *stream);
 /* Diverse top-k: maximal marginal relevance (MMR).  The k answers of a query are picked one after another from a POOL of
  * its best rows, and each pick pays for its resemblance to the rows picked before it, so that near-identical frames - a
  * static camera, a replayed scene, one shot in two uploads - do not fill the k places.

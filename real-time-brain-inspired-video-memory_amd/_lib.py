@@ -46,6 +46,8 @@ SYMBOLS = [
     "vm_mask_from_rows", "vm_mask_from_scopes",
     "vm_topk_span_workspace_bytes", "vm_topk_cosine_span", "vm_topk_cosine_span_exact",
     "vm_topk_mix_workspace_bytes", "vm_topk_cosine_mix", "vm_topk_cosine_mix_exact",
+    "vm_memory_bias_stride", "vm_topk_bias_workspace_bytes", "vm_topk_cosine_biased", "vm_topk_cosine_biased_exact",
+    "vm_bias_from_rows", "vm_bias_from_tags",
     "vm_topk_diverse_workspace_bytes", "vm_topk_cosine_diverse", "vm_topk_cosine_diverse_exact",
     "vm_topk_clip_workspace_bytes", "vm_topk_cosine_clip", "vm_topk_cosine_clip_exact",
     "vm_range_workspace_bytes", "vm_range_cosine", "vm_range_cosine_exact",
@@ -159,6 +161,12 @@ def lib() -> C.CDLL:
         "vm_topk_mix_workspace_bytes": (sz, [vp, i32, i32]),
         "vm_topk_cosine_mix": (i32, [vp, vp, vp, i32, i32, i32, vp, i32, vp, i32, f64, i64, i64, vp, vp, vp, vp, vp, sz, vp]),
         "vm_topk_cosine_mix_exact": (i32, [vp, vp, vp, i32, i32, i32, vp, i32, vp, i32, f64, i64, i64, vp, vp, vp, sz, vp]),
+        "vm_memory_bias_stride": (i64, [vp]),
+        "vm_topk_bias_workspace_bytes": (sz, [vp, i32, i32]),
+        "vm_topk_cosine_biased": (i32, [vp, vp, i32, i32, vp, i32, vp, vp, vp, i32, vp, i32, f64, i64, i64, vp, vp, vp, vp, vp, sz, vp]),
+        "vm_topk_cosine_biased_exact": (i32, [vp, vp, i32, i32, vp, i32, vp, vp, vp, i32, vp, i32, f64, i64, i64, vp, vp, vp, sz, vp]),
+        "vm_bias_from_rows": (i32, [vp, vp, vp, i64, i64, i64, i32, vp, vp]),
+        "vm_bias_from_tags": (i32, [vp, i64, f64, C.c_float, vp, vp]),
         "vm_topk_diverse_workspace_bytes": (sz, [vp, i32, i32]),
         "vm_topk_cosine_diverse": (i32, [vp, vp, i32, i32, i32, vp, vp, i32, vp, i32, f64, i64, i64, vp, vp, vp, vp, vp, vp, sz, vp]),
         "vm_topk_cosine_diverse_exact": (i32, [vp, vp, i32, i32, i32, vp, vp, i32, vp, i32, f64, i64, i64, vp, vp, vp, vp, sz, vp]),

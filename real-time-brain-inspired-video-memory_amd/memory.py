@@ -40,7 +40,7 @@ from typing import List, NamedTuple, Optional, Sequence, Tuple
 import torch
 
 from . import _lib
-from .scratch import (NOVEL_MAX_ROWS, ClipScratch, DiverseTopkScratch, EraseScratch, EventsScratch,  # noqa: F401
+from .scratch import (NOVEL_MAX_ROWS, BiasTopkScratch, ClipScratch, DiverseTopkScratch, EraseScratch, EventsScratch,  # noqa: F401
                       GroupedScopedTopkScratch, GroupedTopkScratch, MaskedTopkScratch, MixTopkScratch, NoveltyScratch, RangeScratch,
                       ScopedTopkScratch, Scratch, SpanTopkScratch, SummaryScratch, TopkScratch)
 
@@ -1225,6 +1225,172 @@ class EmbeddingMemory:
         self._last[MixTopkScratch] = s
         return scores, rows
 
+    # ---- biased search: cosine plus a per-row prior (include/vidmem.h vm_topk_cosine_biased) --------
+    @property
+    def bias_stride(self) -> int:
+        """S: the fp32 entries of one bias column of this memory (``vm_memory_bias_stride``: the capacity rounded up to
+        64 rows, = 32 x ``mask_words``)."""
+        return self.mask_words * 32
+
+    def new_bias(self, n: int = 1) -> torch.Tensor:
+        """-> device float32 zeros ``[n, S]``: ``n`` bias columns.  The entry of row id ``r`` is entry ``r % capacity``;
+        entries of slots without a live row are ignored by every consumer, so a column may be filled by any torch
+        expression.  A column speaks about ROW IDS: after an erase or a ring overwrite it is stale exactly as a mask
+        is."""
+        return torch.zeros((int(n), self.bias_stride), dtype=torch.float32, device=self.device)
+
+    def _biases(self, bias) -> torch.Tensor:
+        """-> contiguous device float32 ``[n_bias, S]`` from one column ``[S]`` or several ``[n_bias, S]``: a device
+        tensor of that form is passed through untouched, anything else is refused before the library is called."""
+        if not isinstance(bias, torch.Tensor) or bias.dtype != torch.float32:
+            raise ValueError("a bias is a float32 tensor (EmbeddingMemory.new_bias)")
+        if bias.dim() not in (1, 2) or bias.shape[0] == 0:
+            raise ValueError(f"a bias is [S] or [n_bias, S] with n_bias >= 1, got {tuple(bias.shape)}")
+        if bias.shape[-1] != self.bias_stride:
+            raise ValueError(f"bias width {bias.shape[-1]} != the {self.bias_stride} entries of this memory's columns")
+        if bias.device != self.device:
+            raise ValueError(f"the bias is on {bias.device}, the memory on {self.device}")
+        return bias.reshape(-1, self.bias_stride).contiguous()
+
+    def _bias_index(self, bias_index, n_bias: int, Q: int) -> Optional[torch.Tensor]:
+        """-> device int32 [Q] or ``None`` (one column for all queries, or one per query)."""
+        if bias_index is None:
+            if n_bias not in (1, Q):
+                raise ValueError(f"{n_bias} bias columns for {Q} queries need a bias_index")
+            return None
+        if isinstance(bias_index, torch.Tensor):
+            if bias_index.dtype != torch.int32 or bias_index.dim() != 1:
+                raise ValueError("a bias_index tensor must be int32 [Q]")
+            idx = bias_index.to(self.device).contiguous()
+        else:
+            idx = torch.tensor([int(i) for i in bias_index], dtype=torch.int32).to(self.device)
+        if idx.shape[0] != Q:
+            raise ValueError(f"{idx.shape[0]} bias indices for {Q} queries")
+        return idx
+
+    def _bias_weight(self, weight, Q: int) -> Optional[torch.Tensor]:
+        """-> device float64 [Q] or ``None`` (1.0 for every query) from a tensor, one number or Q numbers."""
+        if weight is None:
+            return None
+        if isinstance(weight, torch.Tensor):
+            if weight.dtype != torch.float64 or weight.dim() != 1:
+                raise ValueError("a weight tensor must be float64 [Q]")
+            w = weight.to(self.device).contiguous()
+        else:
+            vals = [float(weight)] * Q if not hasattr(weight, "__len__") else [float(x) for x in weight]
+            w = torch.tensor(vals, dtype=torch.float64).to(self.device)
+        if w.shape[0] != Q:
+            raise ValueError(f"{w.shape[0]} weights for {Q} queries")
+        return w
+
+    def _one_bias(self, out) -> torch.Tensor:
+        """The column a builder writes: ``out`` (one column, ``[S]`` or ``[1, S]``, on the device) or a new one."""
+        if out is None:
+            return self.new_bias()[0]
+        if not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.numel() != self.bias_stride or \
+                out.device != self.device or not out.is_contiguous():
+            raise ValueError(f"out must be one contiguous device float32 column of {self.bias_stride} entries")
+        return out
+
+    def bias_of_rows(self, rows, values, out: Optional[torch.Tensor] = None, clear: bool = True) -> torch.Tensor:
+        """-> the column ``[S]`` that holds ``values[i]`` for every live row ``rows[i]``: a prior from the hits of another
+        search or of another retrieval leg.  ``rows``: a host sequence of row ids, or an int64 device tensor of any shape
+        as a search returned it (NOT read on the host; stream-ordered and capturable); ``values``: as many float32
+        values (a device tensor, a host sequence, or one number for all).  -1 entries and ids of rows that are not live
+        are skipped; of duplicates that carry different values one stays.  ``out``: the column to write, default a new
+        one; ``clear=False`` leaves the other entries of ``out`` as they are."""
+        if isinstance(rows, torch.Tensor):
+            if rows.dtype != torch.int64:
+                raise ValueError("row ids are int64")
+            ids = rows.to(self.device).contiguous().view(-1)
+        else:
+            ids = torch.tensor([int(r) for r in rows], dtype=torch.int64).to(self.device)
+        if isinstance(values, torch.Tensor):
+            if values.dtype != torch.float32:
+                raise ValueError("bias values are float32")
+            vals = values.to(self.device).contiguous().view(-1)
+        elif hasattr(values, "__len__"):
+            vals = torch.tensor([float(v) for v in values], dtype=torch.float32).to(self.device)
+        else:
+            vals = torch.full((ids.numel(),), float(values), dtype=torch.float32, device=self.device)
+        if vals.numel() != ids.numel():
+            raise ValueError(f"{vals.numel()} values for {ids.numel()} rows")
+        col = self._one_bias(out)
+        self.ctx.check(self.L.vm_bias_from_rows(self.handle, _ptr(ids), _ptr(vals), ids.numel(), 1, 0, 1 if clear else 0,
+                                                _ptr(col), _lib.current_stream_ptr()))
+        _keep_alive(ids, vals)
+        return col
+
+    def bias_of_age(self, now_ms: int, per_ms: float, fill: float = 0.0, out: Optional[torch.Tensor] = None
+                    ) -> torch.Tensor:
+        """-> the column ``[S]`` of linear recency on a tagged memory: a live row tagged with ``ms`` milliseconds gets
+        ``float32(per_ms * (ms - now_ms))`` - with ``per_ms = 1e-6`` a frame loses 0.06 of score per minute of age -,
+        untagged rows and slots without a live row get ``fill``.  Writes every entry; any other shape of decay is a
+        torch expression over the result."""
+        if not self.tagged:
+            raise ValueError("bias_of_age needs a tagged memory (EmbeddingMemory(..., tagged=True))")
+        col = self._one_bias(out)
+        self.ctx.check(self.L.vm_bias_from_tags(self.handle, int(now_ms), float(per_ms), float(fill), _ptr(col),
+                                                _lib.current_stream_ptr()))
+        return col
+
+    def prepare_topk_biased(self, Q: int, k: int) -> BiasTopkScratch:
+        """Size the biased top-k workspace for (Q, k) now (before a graph capture: a capture must not allocate)."""
+        self._counter(BiasTopkScratch)
+        return self._resolve(BiasTopkScratch, None, int(Q), int(k))
+
+    def topk_biased(self, queries, k: int, bias, weight=None, bias_index=None, mask=None, mask_index=None,
+                    min_score: Optional[float] = None, exact: bool = False, scratch: Optional[BiasTopkScratch] = None,
+                    stride: Tuple[int, int] = (1, 0)) -> Tuple[torch.Tensor, torch.Tensor]:
+        """-> (scores [Q,k] float64, rows [Q,k] int64): the k best rows by COSINE PLUS A PER-ROW PRIOR, on any memory.
+        ``bias``: float32 ``[S]`` (one column for every query) or ``[n_bias, S]`` (``new_bias``, ``bias_of_rows``,
+        ``bias_of_age``, or any torch expression); ``bias_index``: the column each query uses (Q ints or a device int32
+        ``[Q]``), default column 0 for all queries when there is one and column q for query q when there are Q; an index
+        outside ``[0, n_bias)`` is the zero column.  ``weight``: beta per query - one number, Q numbers or a device
+        float64 ``[Q]`` -, default 1.0.  The score of row r is ``S = cos(q, r) + beta * bias[r % capacity]``: the
+        reference's fp64 cosine, the bias widened exactly, one rounding for the product and one for the sum, so
+        ``beta = 0`` or a column of zeros is ``topk`` (with a mask: ``topk_masked``) bit for bit.  ``mask`` /
+        ``mask_index``: as in ``topk_masked``, default every live row.
+
+        Ranked by (S desc, row id asc), the optional strict ``S > min_score`` filter on the raw sum (there is no score
+        mapping: S is not confined to [-1, 1]), -1 / 0.0 padded; ``stride``: the ``(row_stride, row_offset)`` of the
+        returned ids.  Always the exhaustive answer: the fp32 fast path redoes the queries it cannot certify on the
+        device, in the same call (csrc/topk_bias.hip).  ``exact=True`` scores every selected pair exactly (slow).  The
+        per-query flags of the last fast call are in ``last_bias_flags``.  ``scratch``: as in ``topk`` - a
+        ``BiasTopkScratch`` the caller owns (a graph capture: pass ``queries``, ``bias``, ``weight``, ``bias_index`` and
+        ``mask`` as device tensors of their final dtype and rewrite them in place between replays), default this
+        memory's own."""
+        if not 1 <= int(k) <= 64:
+            raise ValueError(f"biased top-k supports 1 <= k <= 64, got {k}")
+        if min_score is not None and math.isnan(float(min_score)):
+            raise ValueError("min_score is NaN")
+        cols = self._biases(bias)
+        masks = self._masks(mask) if mask is not None else None
+        if masks is None and mask_index is not None:
+            raise ValueError("a mask_index needs a mask")
+        q = self._as_rows(queries)
+        Q, k = int(q.shape[0]), int(k)
+        if Q < 1:
+            raise ValueError("no query")
+        bidx = self._bias_index(bias_index, cols.shape[0], Q)
+        w = self._bias_weight(weight, Q)
+        idx = self._mask_index(mask_index, masks.shape[0], Q) if masks is not None else None
+        s = self._resolve(BiasTopkScratch, scratch, Q, k)
+        scores = torch.empty((Q, k), dtype=torch.float64, device=self.device)
+        rows = torch.empty((Q, k), dtype=torch.int64, device=self.device)
+        head = (self.handle, _ptr(q), Q, k, _ptr(cols), cols.shape[0], _ptr(bidx), _ptr(w), _ptr(masks),
+                0 if masks is None else masks.shape[0], _ptr(idx), *_min_score_args(min_score), int(stride[0]),
+                int(stride[1]), _ptr(scores), _ptr(rows))
+        tail = (_ptr(s.ws), s.ws.numel(), _lib.current_stream_ptr())
+        if exact:
+            self.ctx.check(self.L.vm_topk_cosine_biased_exact(*head, *tail))
+        else:
+            self.ctx.check(self.L.vm_topk_cosine_biased(*head, _ptr(self._counter(BiasTopkScratch)), _ptr(s.flags),
+                                                        *tail))
+        _keep_alive(q, cols, bidx, w, masks, idx)
+        self._last[BiasTopkScratch] = s
+        return scores, rows
+
     # ---- diverse search (include/vidmem.h vm_topk_cosine_diverse, DESIGN.md 27) ------------------------------------
     @staticmethod
     def _diverse_pool(k, pool) -> Tuple[int, int]:
@@ -1705,6 +1871,9 @@ class EmbeddingMemory:
     last_mix_flags = _last_property(MixTopkScratch, "flags", "int32 per mixed query (vm_topk_flag): why the last fast "
                                     "`topk_mix` call redid a query, 0 = certified")
     mix_uncertified_count = _count_property(MixTopkScratch, "Mixed queries the mixed fast path")
+    last_bias_flags = _last_property(BiasTopkScratch, "flags", "int32 per query (vm_topk_flag): why the last fast "
+                                     "`topk_biased` call redid a query, 0 = certified")
+    bias_uncertified_count = _count_property(BiasTopkScratch, "Queries the biased fast path")
     last_diverse_flags = _last_property(DiverseTopkScratch, "flags", "int32 per query (vm_topk_flag): why the pool stage "
                                         "of the last fast `topk_diverse` call redid a query, 0 = certified")
     diverse_uncertified_count = _count_property(DiverseTopkScratch, "Queries the diverse search's pool stage")

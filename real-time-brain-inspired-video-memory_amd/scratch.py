@@ -106,7 +106,7 @@ class TopkScratch(Scratch):
 
 
 class _ScanScratch(Scratch):
-    """The workspace and the per-query ``flags`` (int32 [Q]) of a grouped, scoped, masked, span, mixed or diverse top-k of up to (Q, k).  The
+    """The workspace and the per-query ``flags`` (int32 [Q]) of a grouped, scoped, masked, span, mixed, biased or diverse top-k of up to (Q, k).  The
     uncertified counters of these searches are the memory's, whichever scratch a call used."""
 
     @staticmethod
@@ -134,6 +134,12 @@ class MixTopkScratch(_ScanScratch):
     """The mixed-query top-k for up to ``C`` mixed queries (of up to 16 terms each) and ``k``."""
 
     workspaces = (("ws", "vm_topk_mix_workspace_bytes"),)
+
+
+class BiasTopkScratch(_ScanScratch):
+    """The biased top-k (cosine plus a per-row prior) for up to ``Q`` queries and ``k``."""
+
+    workspaces = (("ws", "vm_topk_bias_workspace_bytes"),)
 
 
 class DiverseTopkScratch(_ScanScratch):

@@ -282,6 +282,22 @@ def mix_similarities(memory: EmbeddingMemory, terms, weights, top_k: int, mask=N
             for rr, ss in zip(rows.cpu().tolist(), scores.cpu().tolist())]
 
 
+def biased_similarities(memory: EmbeddingMemory, queries, bias, weight, top_k: int, mask=None,
+                        min_score: Optional[float] = None) -> List[List[Tuple[str, float]]]:
+    """``EmbeddingMemory.topk_biased`` in the reference's list shape, as ``mix_similarities`` returns it: per query
+    ``[(id, score), ...]``, ``id = memory.id_of(row)``, the score the cosine plus ``weight`` times the row's bias.
+    ``bias``: one column for every query or one per query (``memory.bias_of_age`` for recency, ``memory.bias_of_rows``
+    for a boost of the rows another retrieval leg found); ``weight``: one number, one per query, or ``None`` for 1.0;
+    ``mask``: one row mask for every query or one per query."""
+    q = queries if isinstance(queries, torch.Tensor) else torch.tensor(queries, dtype=torch.float32)
+    n = 1 if q.dim() == 1 else int(q.shape[0])
+    if memory.searchable == 0 or top_k <= 0:
+        return [[] for _ in range(n)]
+    scores, rows = memory.topk_biased(q, top_k, bias, weight=weight, mask=mask, min_score=min_score)
+    return [[(memory.id_of(r), float(s)) for r, s in zip(rr, ss) if r >= 0]
+            for rr, ss in zip(rows.cpu().tolist(), scores.cpu().tolist())]
+
+
 def diverse_similarities(memory: EmbeddingMemory, queries, top_k: int, pool: Optional[int] = None, lam=0.5, mask=None,
                          min_score: Optional[float] = None) -> List[List[Tuple[str, float]]]:
     """``EmbeddingMemory.topk_diverse`` in the reference's list shape, as ``mix_similarities`` returns it: per query
