@@ -651,6 +651,59 @@ int vm_topk_cosine_mix_exact(vm_memory *mem, const void *terms, const double *we
                              const uint32_t *masks, int n_masks, const int32_t *mask_index, int use_min_score,
                              double min_score, int64_t row_stride, int64_t row_offset, double *out_scores,
                              int64_t *out_rows, void *workspace, size_t workspace_bytes, void *stream);
+/* Any/all top-k: the k best rows by the MAXIMUM or the MINIMUM OF WEIGHTED COSINES over the terms of a fold query.
+ * VM_FOLD_MAX ("any", OR): rows that resemble any frame of a chunk / any of a few questions - the score by which the
+ * reference links a new batch to stored chunks (the maximum per stored id over the batch's result lists).  VM_FOLD_MIN
+ * ("all", AND): rows whose WORST term is best - text and example picture at once; a weighted sum cannot say that, one
+ * strong term carries a row.
+ * terms, weights, C, J, masks, n_masks, mask_index, the min-score pair, row_stride / row_offset, the outputs, the flags, the
+ * workspace and the stream mean exactly what they mean in vm_topk_cosine_mix; one mask per fold query.
+ * Score of row r for query c, with p_j = w[c][j] * e_j(r) (one fp64 rounding) and e_j(r) the raw reference cosine of term j
+ * and row r (vm_topk_cosine's fp64 value; 0.0 when either norm is zero):
+ *     acc = p_0, arg = 0;  for j = 1 .. J-1:  if p_j > acc (max) / p_j < acc (min):  acc = p_j, arg = j
+ *     F(c, r) = acc,  T(c, r) = arg
+ * The compare is strict: the first term wins a tie, and +0.0 is never replaced by -0.0 (nor -0.0 by +0.0).  The padding
+ * columns J .. 15 of the query tile never take part.  A ZERO WEIGHT IS NOT NEUTRAL here, unlike in vm_topk_cosine_mix: its
+ * product +-0.0 takes part in the maximum / minimum like any other value.  So J = 1, w = 1.0 gives the reference cosine
+ * bit for bit (the result equals vm_topk_cosine / vm_topk_cosine_masked), permuting the terms with their weights changes no
+ * row and no score bit (only T) - with ONE exception: where a row's products tie as zeros of both signs (a zero weight, or a
+ * cosine that is exactly 0.0), the first of them in term order gives F its sign, so a permutation can turn a +0.0 score into
+ * -0.0 or back; the value, the ranking and every nonzero score are unaffected - and appending a copy of a term with its
+ * weight changes nothing at all.
+ * Result: the live rows the mask selects ranked by (F DESCENDING, row id ascending) for BOTH ops, those with F > min_score
+ * kept when use_min_score != 0 (strict, on the raw value), first k: out_scores [C,k] the fp64 F bit for bit, out_rows [C,k]
+ * global row ids (row_id * row_stride + row_offset), 0.0 / -1 padded; out_terms: int32 [C,k] or NULL, T of each returned row
+ * (which frame of the chunk linked, which question matched), -1 where the row is -1.  The result of a query depends on the
+ * memory, its own terms, weights and mask and the arguments only, not on the other queries of the call.  Non-finite weights
+ * are undefined, as stored NaN is.
+ * ALWAYS the exhaustive answer: the fp32 MFMA tile scan scores the J terms as the 16 columns of one query tile, scales
+ * column j by fl32(w_j / ||term_j||) and takes the maximum / minimum over the J columns into ONE fp32 score B per (query,
+ * row); the best M = k + max(8, k/4) selected rows are re-scored exactly, and a query is certified when its mask selects at
+ * most M rows or the exact k-th F clears the (M+1)-th scanned score by eps_fold = A (2 (D + 8) 2^-24 + 2^-21),
+ * A = max_j |w_j|, strictly (max and min move by no more than their most-moved argument).  The bound holds when every
+ * nonzero |w_j| lies in [2^-20, 2^20] and every term and stored norm is 0 or in [2^-40, 2^40]; outside, and for any other
+ * query (VM_FLAG_GAP; VM_FLAG_OVERFLOW: more than 8192 selected rows at the query's cut), the query is counted in
+ * *out_uncertified (may be NULL), marked in out_query_flags [C] (vm_topk_flag; may be NULL) and redone exhaustively over its
+ * selected rows on the device inside the same call.
+ * Any memory: plain, grouped, tagged, ring.  No host read-back, no allocation, no synchronisation: every launch reads the
+ * row count on the device and sizes its grid from the capacity, so the call is capturable; a replay sees weights, terms and
+ * masks rewritten in place and the rows appended since.  1 <= k <= 64, 1 <= C <= 2^20.  VM_ERR_INVALID (with a vm_last_error
+ * text) for an op that is no vm_fold_op and for everything vm_topk_cosine_mix refuses, before any launch, with the outputs
+ * untouched; the workspace must be 256-byte, terms 16-byte and weights 8-byte aligned.
+ * Workspace: vm_topk_fold_workspace_bytes (= the mixed search's); 0 for arguments out of range. */
+enum vm_fold_op { VM_FOLD_MAX = 0, VM_FOLD_MIN = 1 };
+size_t vm_topk_fold_workspace_bytes(const vm_memory *mem, int C, int k);
+int vm_topk_cosine_fold(vm_memory *mem, const void *terms, const double *weights, int C, int J, int k, int op,
+                        const uint32_t *masks, int n_masks, const int32_t *mask_index, int use_min_score,
+                        double min_score, int64_t row_stride, int64_t row_offset, double *out_scores, int64_t *out_rows,
+                        int32_t *out_terms, int32_t *out_uncertified, int32_t *out_query_flags, void *workspace,
+                        size_t workspace_bytes, void *stream);
+/* The same contract, exhaustive only: every selected (query, row) pair scored exactly (slow; tests, and a checker). */
+int vm_topk_cosine_fold_exact(vm_memory *mem, const void *terms, const double *weights, int C, int J, int k, int op,
+                              const uint32_t *masks, int n_masks, const int32_t *mask_index, int use_min_score,
+                              double min_score, int64_t row_stride, int64_t row_offset, double *out_scores,
+                              int64_t *out_rows, int32_t *out_terms, void *workspace, size_t workspace_bytes,
+                              void *stream);
 /* Biased top-k: the k best rows by COSINE PLUS A PER-ROW PRIOR.  A preference that is not a filter: recency, a decaying
  * or reinforced strength per stored frame, an importance weight from metadata, a boost for the rows another retrieval leg
  * found.  The best k rows of cos + prior do not follow from the best k rows of cos, however large a pool is fetched.

@@ -22,6 +22,7 @@ VM_ACT_GELU, VM_ACT_QUICK_GELU = 0, 1
 VM_LAYOUT_CHW, VM_LAYOUT_PATCHES = 0, 1
 VM_SCORE_RAW, VM_SCORE_UNIT_INTERVAL = 0, 1
 VM_FLAG_CERTIFIED, VM_FLAG_GAP, VM_FLAG_OVERFLOW = 0, 1, 3       # vm_topk_flag: why a query went to the exhaustive redo
+VM_FOLD_MAX, VM_FOLD_MIN = 0, 1                                  # vm_fold_op: any (OR) / all (AND) of the terms
 VM_ENC_OPT_SCHEDULE, VM_ENC_OPT_MICRO_BATCH, VM_ENC_OPT_LAST_LAYER = 0, 1, 2
 VM_SCHED_AUTO, VM_SCHED_ONE_STREAM, VM_SCHED_TWO_STREAMS = 0, 1, 2
 SCHEDULES = {"auto": VM_SCHED_AUTO, "one_stream": VM_SCHED_ONE_STREAM, "two_streams": VM_SCHED_TWO_STREAMS}
@@ -46,6 +47,7 @@ SYMBOLS = [
     "vm_mask_from_rows", "vm_mask_from_scopes",
     "vm_topk_span_workspace_bytes", "vm_topk_cosine_span", "vm_topk_cosine_span_exact",
     "vm_topk_mix_workspace_bytes", "vm_topk_cosine_mix", "vm_topk_cosine_mix_exact",
+    "vm_topk_fold_workspace_bytes", "vm_topk_cosine_fold", "vm_topk_cosine_fold_exact",
     "vm_memory_bias_stride", "vm_topk_bias_workspace_bytes", "vm_topk_cosine_biased", "vm_topk_cosine_biased_exact",
     "vm_bias_from_rows", "vm_bias_from_tags",
     "vm_topk_diverse_workspace_bytes", "vm_topk_cosine_diverse", "vm_topk_cosine_diverse_exact",
@@ -161,6 +163,9 @@ def lib() -> C.CDLL:
         "vm_topk_mix_workspace_bytes": (sz, [vp, i32, i32]),
         "vm_topk_cosine_mix": (i32, [vp, vp, vp, i32, i32, i32, vp, i32, vp, i32, f64, i64, i64, vp, vp, vp, vp, vp, sz, vp]),
         "vm_topk_cosine_mix_exact": (i32, [vp, vp, vp, i32, i32, i32, vp, i32, vp, i32, f64, i64, i64, vp, vp, vp, sz, vp]),
+        "vm_topk_fold_workspace_bytes": (sz, [vp, i32, i32]),
+        "vm_topk_cosine_fold": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, i32, vp, i32, f64, i64, i64, vp, vp, vp, vp, vp, vp, sz, vp]),
+        "vm_topk_cosine_fold_exact": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, i32, vp, i32, f64, i64, i64, vp, vp, vp, vp, sz, vp]),
         "vm_memory_bias_stride": (i64, [vp]),
         "vm_topk_bias_workspace_bytes": (sz, [vp, i32, i32]),
         "vm_topk_cosine_biased": (i32, [vp, vp, i32, i32, vp, i32, vp, vp, vp, i32, vp, i32, f64, i64, i64, vp, vp, vp, vp, vp, sz, vp]),

@@ -16,11 +16,21 @@
 //   redo     : mix_redo_scan_kernel (topk_redo_scan_kernel's structure, every admitted row scored exactly), then
 //              vm_topk_redo_merge as it is
 // Every launch reads the row count from the device and sizes its grid from the capacity: capturable.
+//
+// The any/all search (vm_topk_cosine_fold) is the same route with another reduction over the terms: the
+// MAXIMUM or the MINIMUM of the weighted cosines, F(c, r) = max_j / min_j fl64(w_j * e_j(r)) by a strict compare taken
+// j = 0 .. J-1, T(c, r) = the first term that attains it.  Every kernel here takes the reduction as the template
+// parameter OP (MIX_OP_SUM, VM_FOLD_MAX, VM_FOLD_MIN); the sum instantiations are the mixed search's kernels as they were.
+// What differs: the pack's magnitude A is max |w_j|, not the sum; the scan policy FoldScan keeps the padding columns
+// J .. 15 out of the reduction (a zero column must not vote) and reduces with max / min, which is exact, so the bound
+// eps_fold = A (cert_eps(D) + 2^-21) needs A = max |w_j| only; a zero weight is NOT neutral (its product +-0.0 takes
+// part); and one small kernel after either path writes T of the returned rows (fold_terms_kernel).
 #include "topk_scope_select.h"
 #include "topk_tile_scan.h"
 
 namespace {
 
+constexpr int MIX_OP_SUM = 2;      // the template parameter OP: the sum, or a vm_fold_op; never a caller's value
 constexpr int MIX_J = 16;          // terms per mixed query = columns of one query tile
 constexpr int MIX_THREADS = 256;   // pack, finalize, redo
 constexpr double MIX_W_MIN = 9.5367431640625e-07;  // 2^-20: the weight domain of the bound, |w| in [2^-20, 2^20] or 0
@@ -32,10 +42,33 @@ constexpr double MIX_W_MAX = 1048576.0;            // 2^20
 __device__ __forceinline__ double eps_mix(int D, double A) {
     return __dmul_rn(A, __dadd_rn(cert_eps(D), 4.76837158203125e-07));
 }
+// The fold's bound is the same expression with A = max |w_j|: column j's scaled score lies within
+// |w_j| (cert_eps(D) + 2^-23 (1 + small)) of w_j e_j - the coefficient's rounding and the product's, 2^-24 relative each on
+// a magnitude of at most |w_j| (1 + cert_eps) -, and max and min move by no more than their most-moved argument and round
+// nothing.  2^-21 leaves a factor of four over the two roundings.
+__device__ __forceinline__ double eps_fold(int D, double A) { return eps_mix(D, A); }
+
+// The fold over the J products w_j * e_j: a strict compare taken left to right, so the first term wins a tie and a zero
+// of one sign is never replaced by the other.  e(j): the exact cosine of term j, from LDS (finalize, the winning term) or
+// computed as the loop goes (redo).  -> F, and T in arg.  The one statement of the defining compare.
+template <int OP, class E>
+__device__ __forceinline__ double fold_terms(const double *w, E e, int J, int &arg) {
+    double acc = __dmul_rn(w[0], e(0));
+    arg = 0;
+    for (int j = 1; j < J; ++j) {
+        const double p = __dmul_rn(w[j], e(j));
+        if (OP == VM_FOLD_MAX ? p > acc : p < acc) {
+            acc = p;
+            arg = j;
+        }
+    }
+    return acc;
+}
 
 // ---- pack --------------------------------------------------------------------------------------------------
 // One block per mixed query.  tiles [C][16][D]: the J terms, then zero columns.  coef / qn [C][16], A / dom [C].
-template <int DT>
+// A: the sum of the |w_j| (the mixed search), their maximum (a fold).
+template <int DT, int OP>
 __global__ void __launch_bounds__(MIX_THREADS)
     mix_pack_kernel(const uint16_t *__restrict__ terms, const double *__restrict__ weights, int J, int D,
                     uint16_t *__restrict__ tiles, float *__restrict__ coef, double *__restrict__ qn,
@@ -64,7 +97,8 @@ __global__ void __launch_bounds__(MIX_THREADS)
         double s = 0.0;
         int b = 0;
         for (int j = 0; j < MIX_J; ++j) {
-            s = __dadd_rn(s, aw[j]);
+            if constexpr (OP == MIX_OP_SUM) s = __dadd_rn(s, aw[j]);
+            else s = aw[j] > s ? aw[j] : s;  // the padding entries are 0.0
             b |= bad[j];
         }
         A[c] = s;
@@ -177,34 +211,89 @@ struct MixScan {
                 v[j] += row_ror<2>(v[j]);
                 v[j] += row_ror<1>(v[j]);
             }
-            if (l.r16 == 0) {
-                const uint32_t b = tile_bits(a, tile_off(a, l, t), l) >> (4 * l.h);  // four slots
-                uint32_t key[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) key[j] = ((b >> j) & 1u) ? okey32(v[j]) : 0u;
-                store_keys(a, l, t, u32x4{key[0], key[1], key[2], key[3]});
-            }
+            if (l.r16 == 0) store_selected(a, l, t, v);
         }
+    }
+    // lane r16 == 0 of each h: the keys of the lane's four reduced scores, 0 where the mask does not select the slot
+    static __device__ __forceinline__ void store_selected(const Args &a, const TileLane &l, int t, const float (&v)[4]) {
+        const uint32_t b = tile_bits(a, tile_off(a, l, t), l) >> (4 * l.h);  // four slots
+        uint32_t key[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) key[j] = ((b >> j) & 1u) ? okey32(v[j]) : 0u;
+        store_keys(a, l, t, u32x4{key[0], key[1], key[2], key[3]});
+    }
+};
+
+// The fold policy of the tile scan: MixScan's state, masks, skip and stores, with the maximum (VM_FOLD_MAX) or minimum
+// (VM_FOLD_MIN) over the query's J columns in place of the sum.  J is a kernel argument: uniform.  The padding columns
+// J .. 15 hold zero vectors and would score 0; they take the reduction's neutral element BEFORE it, so they never vote.
+// max / min of two floats is exact and commutes: after the four rotations every lane of a row holds the same bits.
+template <int OP>
+struct FoldScan : MixScan {
+    struct Args : MixScan::Args {
+        int J;
+    };
+    // pad: what a column adds to its scaled score before the reduction - -0.0 for a term (x + -0.0 = x for every x, either
+    // zero included), the neutral element for a padding column, whose scaled score is the exact 0 of a zero vector.
+    // From LDS like the coefficient: as a select on r16 < J the same thing costs four VGPRs across the MFMA loop
+    // (84 at QT = 2, a wave per SIMD less than the mixed scan's 80).
+    template <int QT>
+    struct QState : MixScan::QState<QT> {
+        float pad[QT * 16];
+    };
+    template <class QS>
+    static __device__ __forceinline__ void load_query(QS &qs, const Args &a, int i, int q, bool live) {
+        MixScan::load_query(qs, a, i, q, live);
+        qs.pad[i] = (i & 15) < a.J ? -0.f : (OP == VM_FOLD_MAX ? -INFINITY : INFINITY);
+    }
+    template <int QT>
+    static __device__ __forceinline__ void epilogue(const QState<QT> &qs, const Args &a, const View &,
+                                                    const TileLane &l, const float (&s)[QT][4]) {
+#pragma unroll
+        for (int t = 0; t < QT; ++t) {
+            if (l.q0 + 16 * t >= l.Q) continue;  // uniform
+            const float cf = qs.coef[16 * t + l.r16], pad = qs.pad[16 * t + l.r16];
+            float v[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[j] = cf * s[t][j] + pad;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                v[j] = fold2(v[j], row_ror<8>(v[j]));
+                v[j] = fold2(v[j], row_ror<4>(v[j]));
+                v[j] = fold2(v[j], row_ror<2>(v[j]));
+                v[j] = fold2(v[j], row_ror<1>(v[j]));
+            }
+            if (l.r16 == 0) store_selected(a, l, t, v);
+        }
+    }
+    static __device__ __forceinline__ float fold2(float x, float y) {
+        return OP == VM_FOLD_MAX ? fmaxf(x, y) : fminf(x, y);
     }
 };
 
 // ---- the exact score -----------------------------------------------------------------------------------------
 // W of the row in slot p for the J terms in tl [J][D] (LDS): sum from 0.0, left to right, one rounding per product and
-// per addition
-template <int DT>
+// per addition.  A fold: F of that row, fold_terms with the cosines computed as it goes.
+template <int DT, int OP>
 __device__ __forceinline__ double mix_exact(const uint16_t *tl, const double *w, const double *qn, int J, int D,
                                             const uint16_t *row, double rown) {
-    double acc = 0.0;
-    for (int j = 0; j < J; ++j)
-        acc = __dadd_rn(acc, __dmul_rn(w[j], ref_cosine(ref_dot<DT>(tl + (size_t)j * D, row, D), qn[j], rown)));
-    return acc;
+    if constexpr (OP == MIX_OP_SUM) {
+        double acc = 0.0;
+        for (int j = 0; j < J; ++j)
+            acc = __dadd_rn(acc, __dmul_rn(w[j], ref_cosine(ref_dot<DT>(tl + (size_t)j * D, row, D), qn[j], rown)));
+        return acc;
+    } else {
+        int arg;
+        return fold_terms<OP>(
+            w, [&](int j) { return ref_cosine(ref_dot<DT>(tl + (size_t)j * D, row, D), qn[j], rown); }, J, arg);
+    }
 }
 
 // ---- finalize ----------------------------------------------------------------------------------------------
 // One block per mixed query; dynamic LDS: the J terms.  Ranks the C candidates by (fp32 key desc, order asc): the first
 // nc = min(C, M) get their exact W - one (candidate, term) cosine per thread and step, then one left-to-right sum per
-// candidate -, the (M+1)-th (if any) bounds every other selected row.
-template <int DT>
+// candidate (a fold: one fold_terms) -, the (M+1)-th (if any) bounds every other selected row.  Asum: the pack's A.
+template <int DT, int OP>
 __global__ void __launch_bounds__(MIX_THREADS)
     mix_finalize_kernel(const uint16_t *__restrict__ mem, const double *__restrict__ norm64,
                         const uint16_t *__restrict__ tiles, const double *__restrict__ weights,
@@ -267,9 +356,14 @@ __global__ void __launch_bounds__(MIX_THREADS)
     }
     __syncthreads();
     if (tid < nc) {
-        double acc = 0.0;
-        for (int j = 0; j < J; ++j) acc = __dadd_rn(acc, __dmul_rn(wl[j], ec[tid * MIX_J + j]));
-        es[tid] = acc;
+        if constexpr (OP == MIX_OP_SUM) {
+            double acc = 0.0;
+            for (int j = 0; j < J; ++j) acc = __dadd_rn(acc, __dmul_rn(wl[j], ec[tid * MIX_J + j]));
+            es[tid] = acc;
+        } else {
+            int arg;
+            es[tid] = fold_terms<OP>(wl, [&](int j) { return ec[tid * MIX_J + j]; }, J, arg);
+        }
     }
     __syncthreads();
     if (tid < nc) {
@@ -284,7 +378,9 @@ __global__ void __launch_bounds__(MIX_THREADS)
         }
         // certification: the exact k-th W against the best scanned score of a selected row that was not re-scored
         const int kth = (k < nc ? k : nc) - 1;
-        if (r == kth && C > M && !(e > __dadd_rn((double)dekey32(sk[M]), eps_mix(D, Asum[q])))) flag_sh = VM_FLAG_GAP;
+        if (r == kth && C > M &&
+            !(e > __dadd_rn((double)dekey32(sk[M]), OP == MIX_OP_SUM ? eps_mix(D, Asum[q]) : eps_fold(D, Asum[q]))))
+            flag_sh = VM_FLAG_GAP;
     }
     for (int i = nc + tid; i < k; i += MIX_THREADS) {
         out_scores[(size_t)q * k + i] = 0.0;
@@ -311,7 +407,7 @@ constexpr int MIX_CHUNK = VM_REDO_CHUNK_SCOPED;
 // topk_redo_scan_kernel's structure (topk_exact.hip) with the mixed score: grid = nblk row blocks; every block walks all
 // C flags and, for each flagged query, scores its slice of age orders exactly - the rows pred admits - and keeps the
 // slice's stable top-k: part[(block * C + c) * k + i] = {W fp64, age order int64}.  Dynamic LDS: the J terms.
-template <int DT, class P>
+template <int DT, int OP, class P>
 __global__ void __launch_bounds__(MIX_THREADS)
     mix_redo_scan_kernel(const uint16_t *__restrict__ tiles, const double *__restrict__ weights,
                          const double *__restrict__ qn, const uint16_t *__restrict__ rows,
@@ -359,7 +455,7 @@ __global__ void __launch_bounds__(MIX_THREADS)
                 if constexpr (SCOPED) in = pq.in(p);
                 live[i] = in ? 1 : 0;
                 if (in) {
-                    sc[i] = mix_exact<DT>(tl, wl, ql, J, D, rows + (size_t)p * D, norm64[p]);
+                    sc[i] = mix_exact<DT, OP>(tl, wl, ql, J, D, rows + (size_t)p * D, norm64[p]);
                     mine = 1;
                 }
             }
@@ -386,6 +482,52 @@ __global__ void __launch_bounds__(MIX_THREADS)
             part_s[((size_t)blockIdx.x * C + q) * k + tid] = run_s[tid];
             part_o[((size_t)blockIdx.x * C + q) * k + tid] = run_o[tid];
         }
+    }
+}
+
+// ---- the winning term ----------------------------------------------------------------------------------------
+// T of the rows a fold returned, after either path (finalize or redo merge wrote out_rows in this stream): one block per
+// query, one (returned row, term) cosine per thread and step, then fold_terms per row.  A row id is mapped back through
+// row_stride / row_offset; -1 stays -1, and an id that is no live row (none is written by this call) gives -1, never a
+// read outside the store.  Dynamic LDS: the J terms.
+template <int DT, int OP>
+__global__ void __launch_bounds__(MIX_THREADS)
+    fold_terms_kernel(const uint16_t *__restrict__ mem, const double *__restrict__ norm64,
+                      const uint16_t *__restrict__ tiles, const double *__restrict__ weights,
+                      const double *__restrict__ qn, const int64_t *__restrict__ d_total, int64_t cap, int ring, int D,
+                      int J, int k, int64_t row_stride, int64_t row_offset, const int64_t *__restrict__ out_rows,
+                      int *__restrict__ out_terms) {
+    extern __shared__ __attribute__((aligned(16))) char ft_dyn[];
+    uint16_t *tl = reinterpret_cast<uint16_t *>(ft_dyn);  // [J][D]
+    __shared__ double ec[SKMAX * MIX_J];
+    __shared__ int64_t ord[SKMAX];
+    __shared__ double wl[MIX_J], ql[MIX_J];
+    const int q = blockIdx.x, tid = threadIdx.x;
+    const RingView rv = ring_view(*d_total, cap, ring);
+    for (int i = tid; i < J * (D / 8); i += MIX_THREADS)
+        reinterpret_cast<uint4 *>(tl)[i] = reinterpret_cast<const uint4 *>(tiles + (size_t)q * MIX_J * D)[i];
+    if (tid < k) {
+        const int64_t id = out_rows[(size_t)q * k + tid];
+        const int64_t o = id < 0 ? -1 : (id - row_offset) / row_stride - rv.base;
+        ord[tid] = (o >= 0 && o < rv.n) ? o : -1;
+    }
+    if (tid >= MIX_THREADS - MIX_J) {
+        const int j = tid - (MIX_THREADS - MIX_J);
+        wl[j] = j < J ? weights[(size_t)q * J + j] : 0.0;
+        ql[j] = qn[q * MIX_J + j];
+    }
+    __syncthreads();
+    for (int i = tid; i < k * J; i += MIX_THREADS) {  // (returned row, term) pairs
+        const int cd = i / J, j = i - cd * J;
+        if (ord[cd] < 0) continue;
+        const int64_t p = slot_of(rv, ord[cd]);
+        ec[cd * MIX_J + j] = ref_cosine(ref_dot<DT>(tl + (size_t)j * D, mem + (size_t)p * D, D), ql[j], norm64[p]);
+    }
+    __syncthreads();
+    if (tid < k) {
+        int arg = -1;
+        if (ord[tid] >= 0) fold_terms<OP>(wl, [&](int j) { return ec[tid * MIX_J + j]; }, J, arg);
+        out_terms[(size_t)q * k + tid] = arg;
     }
 }
 
@@ -420,12 +562,17 @@ struct MixCall : RowCall {
     int n_masks;
     const int32_t *mask_index;
     size_t ws_bytes;
+    bool fold;           // false: the mixed search (the sum), op is not read
+    int op;              // a fold's vm_fold_op, as the caller gave it
+    int32_t *out_terms;  // a fold's T [C][k], or null
 };
 
 constexpr int MIX_C_MAX = 1 << 20;  // 16 C columns and the workspace offsets stay far inside 32 bits of queries
 
 int mix_check(vm_memory *m, const MixCall &c, const char *who) {
     vm_ctx *ctx = m->ctx;
+    if (c.fold && c.op != VM_FOLD_MAX && c.op != VM_FOLD_MIN)
+        return vm_fail(ctx, VM_ERR_INVALID, "%s: op=%d is no vm_fold_op", who, c.op);
     if (c.J < 1 || c.J > MIX_J) return vm_fail(ctx, VM_ERR_INVALID, "%s: J=%d outside [1, %d]", who, c.J, MIX_J);
     if (c.k < 1 || c.k > SKMAX) return vm_fail(ctx, VM_ERR_INVALID, "%s: k=%d outside [1, %d]", who, c.k, SKMAX);
     if (c.Q < 1 || c.Q > MIX_C_MAX) return vm_fail(ctx, VM_ERR_INVALID, "%s: C=%d outside [1, %d]", who, c.Q, MIX_C_MAX);
@@ -454,9 +601,9 @@ MixBufs mix_bufs(const MPlan &p, char *ws) {
             (double *)(ws + p.off_A),       (int *)(ws + p.off_dom),    (int *)(ws + p.off_flags)};
 }
 
-template <int DT>
+template <int DT, int OP>
 int mix_pack(vm_memory *m, const MixCall &c, const MixBufs &b) {
-    mix_pack_kernel<DT><<<c.Q, MIX_THREADS, 0, c.stream>>>((const uint16_t *)c.queries, c.weights, c.J, m->D, b.tiles,
+    mix_pack_kernel<DT, OP><<<c.Q, MIX_THREADS, 0, c.stream>>>((const uint16_t *)c.queries, c.weights, c.J, m->D, b.tiles,
                                                          b.coef, b.qn, b.A, b.dom);
     VM_LAUNCH_CHECK(m->ctx);
     return VM_OK;
@@ -471,13 +618,13 @@ int mix_lds_attr(vm_memory *m, K kern, size_t lds) {
     return VM_OK;
 }
 
-template <int DT, class P>
+template <int DT, int OP, class P>
 int mix_redo(vm_memory *m, const MPlan &p, const MixCall &c, const MixBufs &b, const P &pred) {
     vm_prof_scope prof(m->ctx, VM_PROF_TOPK_EXACT, c.stream);
     double *part_s = (double *)(c.ws + p.off_ps);
     int64_t *part_o = (int64_t *)(c.ws + p.off_po);
     const size_t lds = (size_t)c.J * m->D * 2;
-    auto kern = mix_redo_scan_kernel<DT, P>;
+    auto kern = mix_redo_scan_kernel<DT, OP, P>;
     if (int rc = mix_lds_attr(m, kern, lds)) return rc;
     kern<<<p.nblk, MIX_THREADS, lds, c.stream>>>(b.tiles, c.weights, b.qn, m->rows, m->norm64, m->d_total, m->cap,
                                                  m->ring, m->D, c.Q, c.J, c.k, b.flags, part_s, part_o, pred);
@@ -486,8 +633,25 @@ int mix_redo(vm_memory *m, const MPlan &p, const MixCall &c, const MixBufs &b, c
                               c.row_stride, c.row_offset, c.out_scores, c.out_rows, nullptr, nullptr, c.stream);
 }
 
-// pack -> scan -> cut -> compact -> select -> finalize -> redo, or (exact) pack -> every query flagged -> redo
-template <int DT>
+// a fold's T of the rows the call returned, when the caller wants it
+template <int DT, int OP>
+int fold_terms_out(vm_memory *m, const MixCall &c, const MixBufs &b) {
+    if constexpr (OP != MIX_OP_SUM) {
+        if (!c.out_terms) return VM_OK;
+        const size_t lds = (size_t)c.J * m->D * 2;
+        auto kern = fold_terms_kernel<DT, OP>;
+        if (int rc = mix_lds_attr(m, kern, lds)) return rc;
+        kern<<<c.Q, MIX_THREADS, lds, c.stream>>>(m->rows, m->norm64, b.tiles, c.weights, b.qn, m->d_total, m->cap,
+                                                  m->ring, m->D, c.J, c.k, c.row_stride, c.row_offset, c.out_rows,
+                                                  c.out_terms);
+        VM_LAUNCH_CHECK(m->ctx);
+    }
+    return VM_OK;
+}
+
+// pack -> scan -> cut -> compact -> select -> finalize -> redo, or (exact) pack -> every query flagged -> redo; a fold
+// then writes its T
+template <int DT, int OP>
 int mix_run(vm_memory *m, const MixCall &c, bool exact) {
     vm_ctx *ctx = m->ctx;
     hipStream_t st = c.stream;
@@ -500,15 +664,20 @@ int mix_run(vm_memory *m, const MixCall &c, bool exact) {
         uint32_t *F = (uint32_t *)ws;
         {
             vm_prof_scope prof(ctx, VM_PROF_TOPK_SCAN, st);
-            if (int rc = mix_pack<DT>(m, c, b)) return rc;
-            const MixScan::Args a = {ms, b.coef, p.fstride, F};
-            if (int rc = vm_tile_scan<DT, MixScan>(m, p.scan, b.tiles, C * MIX_J, a, st)) return rc;
+            if (int rc = mix_pack<DT, OP>(m, c, b)) return rc;
+            if constexpr (OP == MIX_OP_SUM) {
+                const MixScan::Args a = {ms, b.coef, p.fstride, F};
+                if (int rc = vm_tile_scan<DT, MixScan>(m, p.scan, b.tiles, C * MIX_J, a, st)) return rc;
+            } else {
+                const typename FoldScan<OP>::Args a = {{ms, b.coef, p.fstride, F}, c.J};
+                if (int rc = vm_tile_scan<DT, FoldScan<OP>>(m, p.scan, b.tiles, C * MIX_J, a, st)) return rc;
+            }
         }
         {
             vm_prof_scope prof(ctx, VM_PROF_TOPK_FINALIZE, st);
             if (int rc = vm_key_image_select(m, p, F, C, ws, st)) return rc;
             const size_t lds = (size_t)c.J * m->D * 2;
-            auto kern = mix_finalize_kernel<DT>;
+            auto kern = mix_finalize_kernel<DT, OP>;
             if (int rc = mix_lds_attr(m, kern, lds)) return rc;
             kern<<<C, MIX_THREADS, lds, st>>>(m->rows, m->norm64, b.tiles, c.weights, b.qn, b.A, b.dom, m->d_total,
                                               m->cap, m->ring, m->D, c.J, (const int *)(ws + p.off_co),
@@ -518,17 +687,21 @@ int mix_run(vm_memory *m, const MixCall &c, bool exact) {
             VM_LAUNCH_CHECK(ctx);
         }
     } else {
-        if (int rc = mix_pack<DT>(m, c, b)) return rc;
+        if (int rc = mix_pack<DT, OP>(m, c, b)) return rc;
         if (int rc = vm_fill_flags(m, b.flags, C, st)) return rc;
     }
-    if (c.masks) return mix_redo<DT>(m, p, c, b, MaskScope{ms});
-    return mix_redo<DT>(m, p, c, b, NoScope{});
+    if (int rc = c.masks ? mix_redo<DT, OP>(m, p, c, b, MaskScope{ms}) : mix_redo<DT, OP>(m, p, c, b, NoScope{})) return rc;
+    return fold_terms_out<DT, OP>(m, c, b);
 }
 
 int mix_entry(vm_memory *m, const MixCall &c, bool exact, const char *who) {
     if (!m) return VM_ERR_INVALID;
     if (int rc = mix_check(m, c, who)) return rc;
-    return vm_by_dtype(m, [&](auto dt) { return mix_run<decltype(dt)::value>(m, c, exact); });
+    return vm_by_dtype(m, [&](auto dt) {
+        constexpr int DT = decltype(dt)::value;
+        if (!c.fold) return mix_run<DT, MIX_OP_SUM>(m, c, exact);
+        return c.op == VM_FOLD_MAX ? mix_run<DT, VM_FOLD_MAX>(m, c, exact) : mix_run<DT, VM_FOLD_MIN>(m, c, exact);
+    });
 }
 
 }  // namespace
@@ -545,7 +718,7 @@ extern "C" int vm_topk_cosine_mix(vm_memory *m, const void *terms, const double 
                                   void *workspace, size_t workspace_bytes, void *stream) {
     const MixCall c = {{terms, C, k, use_min_score, min_score, VM_SCORE_RAW, row_stride, row_offset, out_scores, out_rows,
                         out_uncertified, out_query_flags, (char *)workspace, (hipStream_t)stream},
-                       weights, J, masks, n_masks, mask_index, workspace_bytes};
+                       weights, J, masks, n_masks, mask_index, workspace_bytes, false, 0, nullptr};
     return mix_entry(m, c, false, "vm_topk_cosine_mix");
 }
 
@@ -556,6 +729,32 @@ extern "C" int vm_topk_cosine_mix_exact(vm_memory *m, const void *terms, const d
                                         void *stream) {
     const MixCall c = {{terms, C, k, use_min_score, min_score, VM_SCORE_RAW, row_stride, row_offset, out_scores, out_rows,
                         nullptr, nullptr, (char *)workspace, (hipStream_t)stream},
-                       weights, J, masks, n_masks, mask_index, workspace_bytes};
+                       weights, J, masks, n_masks, mask_index, workspace_bytes, false, 0, nullptr};
     return mix_entry(m, c, true, "vm_topk_cosine_mix_exact");
+}
+
+extern "C" size_t vm_topk_fold_workspace_bytes(const vm_memory *m, int C, int k) {
+    return vm_topk_mix_workspace_bytes(m, C, k);
+}
+
+extern "C" int vm_topk_cosine_fold(vm_memory *m, const void *terms, const double *weights, int C, int J, int k, int op,
+                                   const uint32_t *masks, int n_masks, const int32_t *mask_index, int use_min_score,
+                                   double min_score, int64_t row_stride, int64_t row_offset, double *out_scores,
+                                   int64_t *out_rows, int32_t *out_terms, int32_t *out_uncertified,
+                                   int32_t *out_query_flags, void *workspace, size_t workspace_bytes, void *stream) {
+    const MixCall c = {{terms, C, k, use_min_score, min_score, VM_SCORE_RAW, row_stride, row_offset, out_scores, out_rows,
+                        out_uncertified, out_query_flags, (char *)workspace, (hipStream_t)stream},
+                       weights, J, masks, n_masks, mask_index, workspace_bytes, true, op, out_terms};
+    return mix_entry(m, c, false, "vm_topk_cosine_fold");
+}
+
+extern "C" int vm_topk_cosine_fold_exact(vm_memory *m, const void *terms, const double *weights, int C, int J, int k,
+                                         int op, const uint32_t *masks, int n_masks, const int32_t *mask_index,
+                                         int use_min_score, double min_score, int64_t row_stride, int64_t row_offset,
+                                         double *out_scores, int64_t *out_rows, int32_t *out_terms, void *workspace,
+                                         size_t workspace_bytes, void *stream) {
+    const MixCall c = {{terms, C, k, use_min_score, min_score, VM_SCORE_RAW, row_stride, row_offset, out_scores, out_rows,
+                        nullptr, nullptr, (char *)workspace, (hipStream_t)stream},
+                       weights, J, masks, n_masks, mask_index, workspace_bytes, true, op, out_terms};
+    return mix_entry(m, c, true, "vm_topk_cosine_fold_exact");
 }

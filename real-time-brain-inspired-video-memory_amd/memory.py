@@ -41,6 +41,7 @@ import torch
 
 from . import _lib
 from .scratch import (NOVEL_MAX_ROWS, BiasTopkScratch, ClipScratch, DiverseTopkScratch, EraseScratch, EventsScratch,  # noqa: F401
+                      FoldTopkScratch,
                       GroupedScopedTopkScratch, GroupedTopkScratch, MaskedTopkScratch, MixTopkScratch, NoveltyScratch, RangeScratch,
                       ScopedTopkScratch, Scratch, SpanTopkScratch, SummaryScratch, TopkScratch)
 
@@ -1225,6 +1226,71 @@ class EmbeddingMemory:
         self._last[MixTopkScratch] = s
         return scores, rows
 
+    # ---- any/all search: the max or min of weighted cosines (include/vidmem.h vm_topk_cosine_fold) ----
+    def prepare_topk_fold(self, C: int, J: int, k: int) -> FoldTopkScratch:
+        """Size the any/all top-k workspace for ``C`` fold queries of ``J`` terms and ``k`` hits each now (before a graph
+        capture: a capture must not allocate).  The workspace does not depend on ``J``: a query's terms always fill
+        one 16-column tile."""
+        if not 1 <= int(J) <= 16:
+            raise ValueError(f"any/all top-k supports 1 <= J <= 16 terms, got {J}")
+        self._counter(FoldTopkScratch)
+        return self._resolve(FoldTopkScratch, None, int(C), int(k))
+
+    def topk_fold(self, terms, k: int, op: str = "max", weights=None, mask=None, mask_index=None,
+                  min_score: Optional[float] = None, exact: bool = False, scratch: Optional[FoldTopkScratch] = None,
+                  stride: Tuple[int, int] = (1, 0)) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """-> (scores [C,k] float64, rows [C,k] int64, terms_idx [C,k] int32): the k best rows by the MAXIMUM
+        (``op="max"``, any / OR) or the MINIMUM (``op="min"``, all / AND) of the weighted cosines over a query's terms,
+        on any memory.  ``terms``: ``[C, J, D]`` (or ``[J, D]`` for one query), J <= 16; ``weights``: as in ``topk_mix``,
+        ``None`` = all 1.0.  The score of row r is ``F = max_j / min_j (w_j * cos(term_j, r))`` over the reference's fp64
+        cosines, one rounding per product, a strict compare taken j = 0 .. J-1: the first term wins a tie, and
+        ``terms_idx`` names it (which frame linked, which question matched; -1 where the row is -1).  ``J = 1, w = 1`` is
+        ``topk`` bit for bit; a permutation of the terms changes only ``terms_idx`` (and the sign of a score that is a
+        zero: products that tie as +0.0 and -0.0 give F the sign of the first); a repeated term changes nothing.  A
+        ZERO WEIGHT IS NOT NEUTRAL, unlike in ``topk_mix``: its product +-0.0 takes part in the max / min.
+
+        Ranked by (F DESCENDING, row id ascending) for both ops - ``"min"`` returns the rows whose worst term is best -,
+        the optional strict ``F > min_score`` filter on the raw value, -1 / 0.0 padded; ``mask`` / ``mask_index``,
+        ``stride``, ``exact`` and ``scratch`` (a ``FoldTopkScratch``) as in ``topk_mix``.  Always the exhaustive answer:
+        the fp32 fast path redoes the queries it cannot certify on the device, in the same call (csrc/topk_mix.hip); the
+        per-query flags of the last fast call are in ``last_fold_flags``."""
+        if op not in ("max", "min"):
+            raise ValueError(f"op must be 'max' or 'min', got {op!r}")
+        if not 1 <= int(k) <= 64:
+            raise ValueError(f"any/all top-k supports 1 <= k <= 64, got {k}")
+        if min_score is not None and math.isnan(float(min_score)):
+            raise ValueError("min_score is NaN")
+        masks = self._masks(mask) if mask is not None else None
+        if masks is None and mask_index is not None:
+            raise ValueError("a mask_index needs a mask")
+        q = self._mix_terms(terms)
+        Cn, J, k = int(q.shape[0]), int(q.shape[1]), int(k)
+        w = self._mix_weights([1.0] * J if weights is None else weights, Cn, J)
+        idx = self._mask_index(mask_index, masks.shape[0], Cn) if masks is not None else None
+        s = self._resolve(FoldTopkScratch, scratch, Cn, k)
+        scores = torch.empty((Cn, k), dtype=torch.float64, device=self.device)
+        rows = torch.empty((Cn, k), dtype=torch.int64, device=self.device)
+        which = torch.empty((Cn, k), dtype=torch.int32, device=self.device)
+        head = (self.handle, _ptr(q), _ptr(w), Cn, J, k, _lib.VM_FOLD_MAX if op == "max" else _lib.VM_FOLD_MIN,
+                _ptr(masks), 0 if masks is None else masks.shape[0], _ptr(idx), *_min_score_args(min_score),
+                int(stride[0]), int(stride[1]), _ptr(scores), _ptr(rows), _ptr(which))
+        tail = (_ptr(s.ws), s.ws.numel(), _lib.current_stream_ptr())
+        if exact:
+            self.ctx.check(self.L.vm_topk_cosine_fold_exact(*head, *tail))
+        else:
+            self.ctx.check(self.L.vm_topk_cosine_fold(*head, _ptr(self._counter(FoldTopkScratch)), _ptr(s.flags), *tail))
+        _keep_alive(q, w, masks, idx)
+        self._last[FoldTopkScratch] = s
+        return scores, rows, which
+
+    def topk_any(self, terms, k: int, **kw) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """``topk_fold(terms, k, op="max", ...)``: the rows that resemble ANY term."""
+        return self.topk_fold(terms, k, op="max", **kw)
+
+    def topk_all(self, terms, k: int, **kw) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """``topk_fold(terms, k, op="min", ...)``: the rows that resemble ALL terms (ranked by their worst one)."""
+        return self.topk_fold(terms, k, op="min", **kw)
+
     # ---- biased search: cosine plus a per-row prior (include/vidmem.h vm_topk_cosine_biased, DESIGN.md 31) --------
     @property
     def bias_stride(self) -> int:
@@ -1871,6 +1937,9 @@ class EmbeddingMemory:
     last_mix_flags = _last_property(MixTopkScratch, "flags", "int32 per mixed query (vm_topk_flag): why the last fast "
                                     "`topk_mix` call redid a query, 0 = certified")
     mix_uncertified_count = _count_property(MixTopkScratch, "Mixed queries the mixed fast path")
+    last_fold_flags = _last_property(FoldTopkScratch, "flags", "int32 per fold query (vm_topk_flag): why the last fast "
+                                     "`topk_fold` call redid a query, 0 = certified")
+    fold_uncertified_count = _count_property(FoldTopkScratch, "Fold queries the any/all fast path")
     last_bias_flags = _last_property(BiasTopkScratch, "flags", "int32 per query (vm_topk_flag): why the last fast "
                                      "`topk_biased` call redid a query, 0 = certified")
     bias_uncertified_count = _count_property(BiasTopkScratch, "Queries the biased fast path")

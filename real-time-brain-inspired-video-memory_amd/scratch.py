@@ -136,6 +136,12 @@ class MixTopkScratch(_ScanScratch):
     workspaces = (("ws", "vm_topk_mix_workspace_bytes"),)
 
 
+class FoldTopkScratch(_ScanScratch):
+    """The any/all top-k for up to ``C`` fold queries (of up to 16 terms each) and ``k``."""
+
+    workspaces = (("ws", "vm_topk_fold_workspace_bytes"),)
+
+
 class BiasTopkScratch(_ScanScratch):
     """The biased top-k (cosine plus a per-row prior) for up to ``Q`` queries and ``k``."""
 
