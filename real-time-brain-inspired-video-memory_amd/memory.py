@@ -312,6 +312,26 @@ _GROUPED_SCOPED = _Search("scoped grouped top-k", GroupedScopedTopkScratch, "vm_
                                   "(EmbeddingMemory(..., grouped=True, tagged=True))")
 
 
+class _Scored(NamedTuple):
+    """One of the four searches that rank by a score of their own (mixed, any/all, biased, diverse) as
+    ``EmbeddingMemory._scored`` runs it.  Their entries share the middle and the end of the argument list - the masks, the
+    ``min_score`` pair, the stride, the outputs, the counter and the flags of the fast entry, the workspace - and differ in
+    the operands before it, which each public method normalises itself."""
+    words: str                          # the search in an error message
+    scratch: type                       # its scratch kind (which names the sizing call)
+    fast: str                           # the fp32 scan with the exact redo of what it cannot certify
+    exact: str                          # every selected pair scored exactly
+    third: Optional[torch.dtype] = None  # a third output [n, k] of this dtype after scores and rows
+    scratch_out: Optional[str] = None   # ... or a buffer of the scratch that the library writes there
+
+
+_MIX = _Scored("mixed top-k", MixTopkScratch, "vm_topk_cosine_mix", "vm_topk_cosine_mix_exact")
+_FOLD = _Scored("any/all top-k", FoldTopkScratch, "vm_topk_cosine_fold", "vm_topk_cosine_fold_exact", third=torch.int32)
+_BIASED = _Scored("biased top-k", BiasTopkScratch, "vm_topk_cosine_biased", "vm_topk_cosine_biased_exact")
+_DIVERSE = _Scored("diverse top-k", DiverseTopkScratch, "vm_topk_cosine_diverse", "vm_topk_cosine_diverse_exact",
+                   scratch_out="mmr")
+
+
 def _last_property(kind: type, name: str, what: str) -> property:
     """``last_*``: a buffer of the scratch that the last call of ``kind`` on this memory used, its own or the caller's."""
     def get(self) -> Optional[torch.Tensor]:
@@ -850,6 +870,40 @@ class EmbeddingMemory:
         self._counter(kind.scratch)
         return self._resolve(kind.scratch, None, int(Q), int(k))
 
+    def _scored(self, kind: _Scored, k, operands, mask, mask_index, min_score, exact, scratch, stride, first=None,
+                sized_by=None) -> Tuple[torch.Tensor, ...]:
+        """The one body of ``topk_mix``, ``topk_fold``, ``topk_biased`` and ``topk_diverse``.  ``first`` (optional) runs
+        after the ``k`` and ``min_score`` checks and before the mask is looked at; ``operands(what first returned)`` runs
+        after the mask checks and returns ``(n, front, keep)``: the number of queries, the entry's arguments between the
+        memory and the masks, and the tensors among them to keep alive.  ``sized_by``: what the scratch is sized by in
+        place of ``k`` (the diverse search's pool).  Every check comes before anything that needs a device."""
+        if not 1 <= int(k) <= 64:
+            raise ValueError(f"{kind.words} supports 1 <= k <= 64, got {k}")
+        if min_score is not None and math.isnan(float(min_score)):
+            raise ValueError("min_score is NaN")
+        early = first() if first is not None else None
+        masks = self._masks(mask) if mask is not None else None
+        if masks is None and mask_index is not None:
+            raise ValueError("a mask_index needs a mask")
+        n, front, keep = operands(early)
+        k = int(k)
+        idx = self._mask_index(mask_index, masks.shape[0], n) if masks is not None else None
+        s = self._resolve(kind.scratch, scratch, n, k if sized_by is None else sized_by)
+        outs = [torch.empty((n, k), dtype=dt, device=self.device)
+                for dt in (torch.float64, torch.int64, kind.third) if dt is not None]
+        head = [self.handle, *front, _ptr(masks), 0 if masks is None else masks.shape[0], _ptr(idx),
+                *_min_score_args(min_score), int(stride[0]), int(stride[1]), *(_ptr(o) for o in outs)]
+        if kind.scratch_out:
+            head.append(_ptr(getattr(s, kind.scratch_out)))
+        tail = (_ptr(s.ws), s.ws.numel(), _lib.current_stream_ptr())
+        if exact:
+            self.ctx.check(getattr(self.L, kind.exact)(*head, *tail))
+        else:
+            self.ctx.check(getattr(self.L, kind.fast)(*head, _ptr(self._counter(kind.scratch)), _ptr(s.flags), *tail))
+        _keep_alive(*keep, masks, idx)
+        self._last[kind.scratch] = s
+        return tuple(outs)
+
     def prepare_topk_grouped(self, Q: int, k: int) -> GroupedTopkScratch:
         """Size the grouped top-k workspace for (Q, k) now (before a graph capture: a capture must not allocate)."""
         return self._prepare_search(_GROUPED, Q, k)
@@ -1157,8 +1211,7 @@ class EmbeddingMemory:
         one 16-column tile."""
         if not 1 <= int(J) <= 16:
             raise ValueError(f"mixed top-k supports 1 <= J <= 16 terms, got {J}")
-        self._counter(MixTopkScratch)
-        return self._resolve(MixTopkScratch, None, int(C), int(k))
+        return self._prepare_search(_MIX, C, k)
 
     def _mix_terms(self, terms) -> torch.Tensor:
         """-> contiguous device ``[C, J, D]`` in the memory's dtype from ``[C, J, D]`` or ``[J, D]`` (one query)."""
@@ -1201,30 +1254,12 @@ class EmbeddingMemory:
         per-query flags of the last fast call are in ``last_mix_flags``.  ``scratch``: as in ``topk`` - a
         ``MixTopkScratch`` the caller owns (a graph capture: pass ``terms``, ``weights`` and ``mask`` as device tensors
         of their final dtype and rewrite them in place between replays), default this memory's own."""
-        if not 1 <= int(k) <= 64:
-            raise ValueError(f"mixed top-k supports 1 <= k <= 64, got {k}")
-        if min_score is not None and math.isnan(float(min_score)):
-            raise ValueError("min_score is NaN")
-        masks = self._masks(mask) if mask is not None else None
-        if masks is None and mask_index is not None:
-            raise ValueError("a mask_index needs a mask")
-        q = self._mix_terms(terms)
-        Cn, J, k = int(q.shape[0]), int(q.shape[1]), int(k)
-        w = self._mix_weights(weights, Cn, J)
-        idx = self._mask_index(mask_index, masks.shape[0], Cn) if masks is not None else None
-        s = self._resolve(MixTopkScratch, scratch, Cn, k)
-        scores = torch.empty((Cn, k), dtype=torch.float64, device=self.device)
-        rows = torch.empty((Cn, k), dtype=torch.int64, device=self.device)
-        head = (self.handle, _ptr(q), _ptr(w), Cn, J, k, _ptr(masks), 0 if masks is None else masks.shape[0], _ptr(idx),
-                *_min_score_args(min_score), int(stride[0]), int(stride[1]), _ptr(scores), _ptr(rows))
-        tail = (_ptr(s.ws), s.ws.numel(), _lib.current_stream_ptr())
-        if exact:
-            self.ctx.check(self.L.vm_topk_cosine_mix_exact(*head, *tail))
-        else:
-            self.ctx.check(self.L.vm_topk_cosine_mix(*head, _ptr(self._counter(MixTopkScratch)), _ptr(s.flags), *tail))
-        _keep_alive(q, w, masks, idx)
-        self._last[MixTopkScratch] = s
-        return scores, rows
+        def operands(_):
+            q = self._mix_terms(terms)
+            Cn, J = int(q.shape[0]), int(q.shape[1])
+            w = self._mix_weights(weights, Cn, J)
+            return Cn, (_ptr(q), _ptr(w), Cn, J, int(k)), (q, w)
+        return self._scored(_MIX, k, operands, mask, mask_index, min_score, exact, scratch, stride)
 
     # ---- any/all search: the max or min of weighted cosines (include/vidmem.h vm_topk_cosine_fold, DESIGN.md 32) ----
     def prepare_topk_fold(self, C: int, J: int, k: int) -> FoldTopkScratch:
@@ -1233,8 +1268,7 @@ class EmbeddingMemory:
         one 16-column tile."""
         if not 1 <= int(J) <= 16:
             raise ValueError(f"any/all top-k supports 1 <= J <= 16 terms, got {J}")
-        self._counter(FoldTopkScratch)
-        return self._resolve(FoldTopkScratch, None, int(C), int(k))
+        return self._prepare_search(_FOLD, C, k)
 
     def topk_fold(self, terms, k: int, op: str = "max", weights=None, mask=None, mask_index=None,
                   min_score: Optional[float] = None, exact: bool = False, scratch: Optional[FoldTopkScratch] = None,
@@ -1256,32 +1290,12 @@ class EmbeddingMemory:
         per-query flags of the last fast call are in ``last_fold_flags``."""
         if op not in ("max", "min"):
             raise ValueError(f"op must be 'max' or 'min', got {op!r}")
-        if not 1 <= int(k) <= 64:
-            raise ValueError(f"any/all top-k supports 1 <= k <= 64, got {k}")
-        if min_score is not None and math.isnan(float(min_score)):
-            raise ValueError("min_score is NaN")
-        masks = self._masks(mask) if mask is not None else None
-        if masks is None and mask_index is not None:
-            raise ValueError("a mask_index needs a mask")
-        q = self._mix_terms(terms)
-        Cn, J, k = int(q.shape[0]), int(q.shape[1]), int(k)
-        w = self._mix_weights([1.0] * J if weights is None else weights, Cn, J)
-        idx = self._mask_index(mask_index, masks.shape[0], Cn) if masks is not None else None
-        s = self._resolve(FoldTopkScratch, scratch, Cn, k)
-        scores = torch.empty((Cn, k), dtype=torch.float64, device=self.device)
-        rows = torch.empty((Cn, k), dtype=torch.int64, device=self.device)
-        which = torch.empty((Cn, k), dtype=torch.int32, device=self.device)
-        head = (self.handle, _ptr(q), _ptr(w), Cn, J, k, _lib.VM_FOLD_MAX if op == "max" else _lib.VM_FOLD_MIN,
-                _ptr(masks), 0 if masks is None else masks.shape[0], _ptr(idx), *_min_score_args(min_score),
-                int(stride[0]), int(stride[1]), _ptr(scores), _ptr(rows), _ptr(which))
-        tail = (_ptr(s.ws), s.ws.numel(), _lib.current_stream_ptr())
-        if exact:
-            self.ctx.check(self.L.vm_topk_cosine_fold_exact(*head, *tail))
-        else:
-            self.ctx.check(self.L.vm_topk_cosine_fold(*head, _ptr(self._counter(FoldTopkScratch)), _ptr(s.flags), *tail))
-        _keep_alive(q, w, masks, idx)
-        self._last[FoldTopkScratch] = s
-        return scores, rows, which
+        def operands(_):
+            q = self._mix_terms(terms)
+            Cn, J = int(q.shape[0]), int(q.shape[1])
+            w = self._mix_weights([1.0] * J if weights is None else weights, Cn, J)
+            return Cn, (_ptr(q), _ptr(w), Cn, J, int(k), _lib.VM_FOLD_MAX if op == "max" else _lib.VM_FOLD_MIN), (q, w)
+        return self._scored(_FOLD, k, operands, mask, mask_index, min_score, exact, scratch, stride)
 
     def topk_any(self, terms, k: int, **kw) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """``topk_fold(terms, k, op="max", ...)``: the rows that resemble ANY term."""
@@ -1402,8 +1416,7 @@ class EmbeddingMemory:
 
     def prepare_topk_biased(self, Q: int, k: int) -> BiasTopkScratch:
         """Size the biased top-k workspace for (Q, k) now (before a graph capture: a capture must not allocate)."""
-        self._counter(BiasTopkScratch)
-        return self._resolve(BiasTopkScratch, None, int(Q), int(k))
+        return self._prepare_search(_BIASED, Q, k)
 
     def topk_biased(self, queries, k: int, bias, weight=None, bias_index=None, mask=None, mask_index=None,
                     min_score: Optional[float] = None, exact: bool = False, scratch: Optional[BiasTopkScratch] = None,
@@ -1426,36 +1439,16 @@ class EmbeddingMemory:
         ``BiasTopkScratch`` the caller owns (a graph capture: pass ``queries``, ``bias``, ``weight``, ``bias_index`` and
         ``mask`` as device tensors of their final dtype and rewrite them in place between replays), default this
         memory's own."""
-        if not 1 <= int(k) <= 64:
-            raise ValueError(f"biased top-k supports 1 <= k <= 64, got {k}")
-        if min_score is not None and math.isnan(float(min_score)):
-            raise ValueError("min_score is NaN")
-        cols = self._biases(bias)
-        masks = self._masks(mask) if mask is not None else None
-        if masks is None and mask_index is not None:
-            raise ValueError("a mask_index needs a mask")
-        q = self._as_rows(queries)
-        Q, k = int(q.shape[0]), int(k)
-        if Q < 1:
-            raise ValueError("no query")
-        bidx = self._bias_index(bias_index, cols.shape[0], Q)
-        w = self._bias_weight(weight, Q)
-        idx = self._mask_index(mask_index, masks.shape[0], Q) if masks is not None else None
-        s = self._resolve(BiasTopkScratch, scratch, Q, k)
-        scores = torch.empty((Q, k), dtype=torch.float64, device=self.device)
-        rows = torch.empty((Q, k), dtype=torch.int64, device=self.device)
-        head = (self.handle, _ptr(q), Q, k, _ptr(cols), cols.shape[0], _ptr(bidx), _ptr(w), _ptr(masks),
-                0 if masks is None else masks.shape[0], _ptr(idx), *_min_score_args(min_score), int(stride[0]),
-                int(stride[1]), _ptr(scores), _ptr(rows))
-        tail = (_ptr(s.ws), s.ws.numel(), _lib.current_stream_ptr())
-        if exact:
-            self.ctx.check(self.L.vm_topk_cosine_biased_exact(*head, *tail))
-        else:
-            self.ctx.check(self.L.vm_topk_cosine_biased(*head, _ptr(self._counter(BiasTopkScratch)), _ptr(s.flags),
-                                                        *tail))
-        _keep_alive(q, cols, bidx, w, masks, idx)
-        self._last[BiasTopkScratch] = s
-        return scores, rows
+        def operands(cols):
+            q = self._as_rows(queries)
+            Q = int(q.shape[0])
+            if Q < 1:
+                raise ValueError("no query")
+            bidx = self._bias_index(bias_index, cols.shape[0], Q)
+            w = self._bias_weight(weight, Q)
+            return Q, (_ptr(q), Q, int(k), _ptr(cols), cols.shape[0], _ptr(bidx), _ptr(w)), (q, cols, bidx, w)
+        return self._scored(_BIASED, k, operands, mask, mask_index, min_score, exact, scratch, stride,
+                            first=lambda: self._biases(bias))
 
     # ---- diverse search (include/vidmem.h vm_topk_cosine_diverse, DESIGN.md 27) ------------------------------------
     @staticmethod
@@ -1476,8 +1469,7 @@ class EmbeddingMemory:
         """Size the diverse top-k workspace for ``Q`` queries, ``k`` picks and a pool of ``pool`` rows each now (before a
         graph capture: a capture must not allocate).  The workspace depends on ``Q`` and ``pool`` only."""
         k, pool = self._diverse_pool(k, pool)
-        self._counter(DiverseTopkScratch)
-        return self._resolve(DiverseTopkScratch, None, int(Q), pool)
+        return self._prepare_search(_DIVERSE, Q, pool)
 
     def _diverse_lam(self, lam, Q: int) -> torch.Tensor:
         """-> contiguous device float64 ``[Q]``.  A device float64 tensor passes through unread (a captured call sees it
@@ -1517,30 +1509,15 @@ class EmbeddingMemory:
         ``queries``, ``lam`` and ``mask`` as device tensors of their final dtype and rewrite them in place between
         replays), default this memory's own."""
         k, pool = self._diverse_pool(k, pool)
-        if min_score is not None and math.isnan(float(min_score)):
-            raise ValueError("min_score is NaN")
-        masks = self._masks(mask) if mask is not None else None
-        if masks is None and mask_index is not None:
-            raise ValueError("a mask_index needs a mask")
-        q = self._as_rows(queries)
-        Q = int(q.shape[0])
-        lm = self._diverse_lam(lam, Q)
-        idx = self._mask_index(mask_index, masks.shape[0], Q) if masks is not None else None
-        s = self._resolve(DiverseTopkScratch, scratch, Q, pool)
-        scores = torch.empty((Q, k), dtype=torch.float64, device=self.device)
-        rows = torch.empty((Q, k), dtype=torch.int64, device=self.device)
-        head = (self.handle, _ptr(q), Q, k, pool, _ptr(lm), _ptr(masks), 0 if masks is None else masks.shape[0],
-                _ptr(idx), *_min_score_args(min_score), int(stride[0]), int(stride[1]), _ptr(scores), _ptr(rows),
-                _ptr(s.mmr))
-        tail = (_ptr(s.ws), s.ws.numel(), _lib.current_stream_ptr())
-        if exact:
-            self.ctx.check(self.L.vm_topk_cosine_diverse_exact(*head, *tail))
-        else:
-            self.ctx.check(self.L.vm_topk_cosine_diverse(*head, _ptr(self._counter(DiverseTopkScratch)), _ptr(s.flags),
-                                                         *tail))
-        _keep_alive(q, lm, masks, idx)
-        self._last[DiverseTopkScratch] = s
-        self._last_diverse_shape = (Q, k)
+
+        def operands(_):
+            q = self._as_rows(queries)
+            Q = int(q.shape[0])
+            lm = self._diverse_lam(lam, Q)
+            return Q, (_ptr(q), Q, k, pool, _ptr(lm)), (q, lm)
+        scores, rows = self._scored(_DIVERSE, k, operands, mask, mask_index, min_score, exact, scratch, stride,
+                                    sized_by=pool)
+        self._last_diverse_shape = (scores.shape[0], k)
         return scores, rows
 
     @property

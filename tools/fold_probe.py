@@ -1,6 +1,6 @@
 """Any/all top-k against the two-step linking and against the mixed top-k, warm.
 
-  python tools/fold_probe.py [--rows 100000 1000000] [--iters 20] [--out profiles/fold_probe.json]
+  python tools/fold_probe.py [--rows 100000 1000000] [--iters 20] [--out profiles/fold_probe.json] [--root other/checkout | --lib other/libvidmem.so]
 
 One process; one run per value of ``--rows``, one after the other, each on a memory of its own: ``rows`` x 768 fp16
 scene-structured rows (a centre per 16 rows + small noise), one id per row.  ``--out`` holds ``{"tool", "runs": [one object
@@ -19,6 +19,9 @@ per run]}``.
 
 Every variant is timed twice, taking turns; both means are kept: the spread between a variant's two runs is the margin of a
 comparison.
+
+``--root`` / ``--lib``: another built checkout, or another build of the library with this tree's ABI, to time instead
+(mix_probe.py's options: an A/B against a parent commit, one process per side).
 """
 import argparse
 import json
@@ -37,14 +40,21 @@ def main():
     ap.add_argument("--rows", type=int, nargs="+", default=[100_000, 1_000_000])
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--root", default=None, help="another built checkout to import vidmem from (an A/B against a parent "
+                    "commit)")
+    ap.add_argument("--lib", default=None, help="another build of libvidmem.so with this tree's ABI to time")
     a = ap.parse_args()
-    sys.path.insert(0, HERE)
+    sys.path.insert(0, os.path.abspath(a.root) if a.root else HERE)
     import vidmem  # noqa: F401
+    import vidmem._lib
+    if a.lib:
+        vidmem._lib.LIB_PATH = os.path.abspath(a.lib)
     runs = [run(n, a.iters) for n in a.rows]
     if a.out:
         os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
         with open(a.out, "w") as f:
-            json.dump({"tool": "tools/fold_probe.py", "runs": runs}, f, indent=1)
+            json.dump({"tool": "tools/fold_probe.py", "root": a.root or "this tree", "lib": a.lib or "its own",
+                       "runs": runs}, f, indent=1)
 
 
 def run(n, iters):
