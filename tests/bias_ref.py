@@ -23,11 +23,11 @@ import numpy as np
 
 from oracle import cref
 from tests import mask_ref as MR
+from tests import mix_ref as XR
+from tests.scored_ref import DTS, NQ, rank_pair, scan_selections, slack_m  # noqa: F401
 
 QS = (1, 17, 33)                    # QT = 1, QT = 2 with a ragged second tile, and a second query group
 KS = (1, 5)
-DTS = ((128, "f16"), (128, "bf16"), (384, "f16"), (384, "bf16"))
-NQ = 33
 SETS = ("zero", "age", "boost", "wide", "big")
 BETAS = (1.0, 0.0, -0.5, 0.3, 2.0 ** -12)
 W_MIN, W_MAX, B_MAX = 2.0 ** -20, 2.0 ** 20, 2.0 ** 40      # the domain of the bound: |beta| (or 0), and |b|
@@ -38,11 +38,6 @@ INT64_MIN = -(1 << 63)
 def bias_stride(capacity: int) -> int:
     """S: the entries of one column, the capacity rounded up to 64 (= 32 x mask_ref.mask_words)."""
     return (capacity + 63) // 64 * 64
-
-
-def slack_m(k: int) -> int:
-    """M: the candidates re-scored exactly (vm_topk_geom); rank M + 1 bounds the rest."""
-    return k + max(k // 4, 8)
 
 
 def eps_bias(D: int, B: float) -> float:
@@ -150,10 +145,10 @@ def flag0_ok(best_first, k: int, D: int) -> bool:
 
 def margin(best_first, k: int, D: int) -> float:
     """(rank k - rank M + 1) / eps_bias, inf when there is no rank M + 1."""
-    M1 = slack_m(k) + 1
-    if best_first.size < M1:
+    pair = rank_pair(best_first, k)
+    if pair is None:
         return np.inf
-    hi, lo = float(best_first[k - 1]), float(best_first[M1 - 1])
+    hi, lo = float(pair[0]), float(pair[1])
     return (hi - lo) / eps_bias(D, max(abs(hi), abs(lo)))
 
 
@@ -169,15 +164,6 @@ def scan_scores(D, dtype, shape):
         b = row_bias(cols[si:si + 1], None, 1, base, n, cap or total)[0]
         for beta in BETAS:
             out[si, beta] = np.stack([bias_scores_loop(live[q], beta, b) for q in range(NQ)])
-    return out
-
-
-def scan_selections(Q, shape, base, n):
-    """name -> bool [Q, n]: 'none' (no mask) and every set of mask_ref.mask_sets(Q, shape)."""
-    total, cap = MR.SHAPES[shape]
-    out = {"none": np.ones((Q, n), dtype=bool)}
-    for name, (masks, index) in MR.mask_sets(Q, shape).items():
-        out[name] = MR.selection(masks, index, Q, base, n, cap or total)
     return out
 
 
@@ -216,13 +202,9 @@ E2E_D, E2E_N, E2E_FRAME_MS = 128, 60, 1000
 
 def e2e_videos(seed=29):
     """uint16 [2 N, D] fp16 bit patterns: two "videos" of N frames, each a slow drift, so a frame resembles its temporal
-    neighbours most (mix_ref.e2e_videos' construction with another seed)."""
-    rng = np.random.default_rng(seed)
-
-    def video(n):
-        x = rng.standard_normal((1, E2E_D)) + np.cumsum(0.35 * rng.standard_normal((n, E2E_D)), axis=0)
-        return x / np.linalg.norm(x, axis=1, keepdims=True)
-    return np.ascontiguousarray(np.concatenate([video(E2E_N), video(E2E_N)]).astype(np.float16)).view(np.uint16)
+    neighbours most: mix_ref.e2e_videos with another seed."""
+    assert (E2E_D, E2E_N) == (XR.E2E_D, XR.E2E_N)
+    return XR.e2e_videos(seed)
 
 
 def e2e_tags() -> np.ndarray:

@@ -36,6 +36,7 @@ from tests import scope_ref as S
 from tests import span_ref as SP
 from tests import summary_ref as M
 from tests import events_ref as V
+from tests.support import to_bits
 
 NOISE_SCALE, NOISE_BOUND, FLOOR, SPACING = 0.05, 0.06, 0.5, 0.05
 FAMILIES, LEVELS, GROUP, MS_BITS = 16, 9, 8, 40
@@ -105,12 +106,6 @@ def hoods(L: Layout):
     return out
 
 
-def to_bits(x, dtype=DTYPE) -> np.ndarray:
-    if dtype == "f16":
-        return np.ascontiguousarray(np.asarray(x, np.float32).astype(np.float16)).view(np.uint16)
-    return CL.to_bits(np.asarray(x, np.float32), dtype)
-
-
 def from_bits(b, dtype=DTYPE) -> np.ndarray:
     if dtype == "f16":
         return np.ascontiguousarray(b).view(np.float16).astype(np.float64)
@@ -160,7 +155,7 @@ def noisy_copy(bits, seed, noise=0.05) -> np.ndarray:
     assert not x[..., h:].any()
     e = np.zeros_like(x)
     e[..., :h] = noise * _unit(np.random.default_rng(2000 + seed).standard_normal(x[..., :h].shape))
-    return to_bits(x + e)
+    return to_bits(x + e, DTYPE)
 
 
 def first_half_only(bits) -> bool:
@@ -550,7 +545,7 @@ def fresh_rows(L: Layout, seed=99) -> np.ndarray:
     basis = base_queries(L)
     x = np.random.default_rng(seed).standard_normal((3, h))
     x, _ = np.linalg.qr((x - (x @ basis.T) @ basis).T)
-    return to_bits(np.concatenate([x.T, np.zeros((3, h))], axis=1))
+    return to_bits(np.concatenate([x.T, np.zeros((3, h))], axis=1), DTYPE)
 
 
 def mix_terms(L: Layout, seed=40):

@@ -21,6 +21,8 @@ import functools
 import numpy as np
 
 from oracle import cref
+from tests.domain_ref import cert_eps
+from tests.support import to_bits  # noqa: F401  (CL.to_bits for the other refs)
 
 INT64_MIN, INT64_MAX = -(1 << 63), (1 << 63) - 1
 MS_BITS = 40
@@ -29,7 +31,7 @@ MS_MASK = (1 << MS_BITS) - 1
 
 def eps_w(D: int) -> float:
     """cert_eps(D) + 2^-23 (csrc/topk_clip.hip clip_eps_w)."""
-    return 2.0 * (D + 8) * 2.0 ** -24 + 2.0 ** -23
+    return cert_eps(D) + 2.0 ** -23
 
 
 def scope_arrays(scopes, C):
@@ -243,13 +245,6 @@ def margin(clips, rows, k, min_sep, dtype="f16", tags=None, scopes=None, max_gap
 
 
 # ---- test data: a scene-structured "video" ---------------------------------------------------------------------------
-def to_bits(x: np.ndarray, dtype: str) -> np.ndarray:
-    """fp32 values -> the uint16 bit patterns of their round-to-nearest f16 / bf16 images."""
-    import torch
-    t = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(torch.float16 if dtype == "f16" else torch.bfloat16)
-    return t.contiguous().view(torch.int16).numpy().view(np.uint16).copy()
-
-
 def _unit(x):
     return x / np.linalg.norm(x, axis=-1, keepdims=True)
 

@@ -16,6 +16,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from oracle import cref
+from tests.support import to_bits
 
 # ---------------------------------------------------------------------------------------------------------------------
 # bit patterns
@@ -23,15 +24,6 @@ from oracle import cref
 THREADS = min(8, os.cpu_count() or 1)                  # the oracle's thread pool
 MAX_FINITE = {"f16": 0x7BFF, "bf16": 0x7F7F}          # 65504, 3.3895e38
 SUBNORMAL_MASK = {"f16": 0x03FF, "bf16": 0x007F}      # exponent field 0, any mantissa
-
-
-def to_bits(x: np.ndarray, dtype: str) -> np.ndarray:
-    """fp32/fp64 values -> uint16 bit patterns of ``dtype``, round to nearest even (no NaN / inf in these tests)."""
-    if dtype == "f16":
-        return np.ascontiguousarray(x, dtype=np.float32).astype(np.float16).view(np.uint16)
-    u = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32).astype(np.uint64)
-    u = u + 0x7FFF + ((u >> 16) & 1)
-    return (u >> 16).astype(np.uint16)
 
 
 def unit_bits(rng: np.random.Generator, n: int, D: int, dtype: str) -> np.ndarray:

@@ -22,8 +22,9 @@ import numpy as np
 
 from oracle import cref
 from tests import mask_ref as MR
+from tests import scored_ref
+from tests.scored_ref import DTS, rank_pair, slack_m  # noqa: F401
 
-DTS = ((128, "f16"), (128, "bf16"), (384, "f16"), (384, "bf16"))
 QS = (1, 16, 17, 33)
 K_POOL = ((1, 1), (5, 5), (5, 8), (5, 16), (5, 64), (17, 33), (64, 64))
 POOLS = (5, 8, 16, 64)              # the pools of precondition (i)
@@ -37,11 +38,6 @@ def lam_vector(Q: int):
 
 def per_query(lam, Q: int):
     return [float(x) for x in lam] if hasattr(lam, "__len__") else [float(lam)] * Q
-
-
-def slack_m(k: int) -> int:
-    """M: the candidates the pool search re-scores exactly (vm_topk_geom); rank M + 1 bounds the rest."""
-    return k + max(k // 4, 8)
 
 
 def sim_matrix(rows, dtype="f16") -> np.ndarray:
@@ -152,19 +148,16 @@ def diverse_topk_arrays(queries, rows, sel, k, pool, lam, dtype="f16", min_score
 # ---- the scan test's cases and preconditions ------------------------------------------------------------------------------
 def scan_selections(Q, shape, base, n):
     """name -> (masks, index, bool [Q, n]): 'none' (no mask) and every set of mask_ref.mask_sets."""
-    total, cap = MR.SHAPES[shape]
-    out = {"none": (None, None, np.ones((Q, n), dtype=bool))}
-    for name, (masks, index) in MR.mask_sets(Q, shape).items():
-        out[name] = (masks, index, MR.selection(masks, index, Q, base, n, cap or total))
-    return out
+    operands = {"none": (None, None), **MR.mask_sets(Q, shape)}
+    return {name: (*operands[name], sel) for name, sel in scored_ref.scan_selections(Q, shape, base, n).items()}
 
 
 def flag0_ok(best_first, pool: int, D: int) -> bool:
     """best_first: one query's exact selected scores, descending.  True when the pool search (k = pool) must certify the
     query itself: rank ``pool`` and rank M + 1 are more than 4 x cert_eps(D) apart, or fewer than M + 1 rows are
     selected."""
-    M1 = slack_m(pool) + 1
-    return best_first.size < M1 or bool(best_first[pool - 1] - best_first[M1 - 1] > 4 * MR.cert_eps(D))
+    pair = rank_pair(best_first, pool)
+    return pair is None or bool(pair[0] - pair[1] > 4 * MR.cert_eps(D))
 
 
 # ---- the end-to-end test's data -------------------------------------------------------------------------------------------

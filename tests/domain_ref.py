@@ -30,7 +30,7 @@ from typing import List, Optional, Tuple
 import numpy as np
 import torch
 
-TD = {"f16": torch.float16, "bf16": torch.bfloat16}
+from tests.support import TD, bits  # noqa: F401  (DR.bits for the tests)
 
 
 def cert_eps(D: int) -> float:
@@ -40,10 +40,6 @@ def cert_eps(D: int) -> float:
 
 # the norm interval of the certificate's domain (csrc/topk_common.h VM_CERT_NORM_MIN / MAX)
 NORM_MIN, NORM_MAX = 2.0 ** -40, 2.0 ** 40
-
-
-def bits(t: torch.Tensor) -> np.ndarray:
-    return t.contiguous().view(torch.int16).cpu().numpy().view(np.uint16)
 
 
 def scaled(rows16: torch.Tensor, exps) -> Tuple[torch.Tensor, bool]:

@@ -119,7 +119,7 @@ def scene_flags(sizes) -> np.ndarray:
 
 
 # The three planted-scene data sets of the tests: name -> (dtype, D, scenes, size seed, data seed).  Ragged scene sizes
-# 1 - 23 (tests/test_group_topk_gpu._sizes) that add up to 4864, 1808 and 3542 rows.
+# 1 - 23 (tests/support.group_sizes) that add up to 4864, 1808 and 3542 rows.
 SETS = {"f16_768": ("f16", 768, 390, 1, 101), "bf16_1024": ("bf16", 1024, 151, 34, 102),
         "f16_128": ("f16", 128, 296, 3, 103)}
 
@@ -129,9 +129,9 @@ def dataset(name):
     """(dtype, row bits uint16 [n, D], scene sizes, links [n]) of one set: made on the CPU (the same bytes with and
     without a GPU), once per process, never modified."""
     import torch
-    from tests.test_group_topk_gpu import _sizes, clustered
+    from tests.support import clustered, group_sizes
     dtype, D, scenes, size_seed, seed = SETS[name]
-    sizes = _sizes(scenes, "ragged", size_seed)
+    sizes = group_sizes(scenes, "ragged", size_seed)
     rows, _ = clustered(sizes, D, dtype, seed=seed, device="cpu")
     bits = rows.contiguous().view(torch.int16).numpy().view(np.uint16)
     bits.setflags(write=False)

@@ -553,14 +553,14 @@ def checkpoint(mem, model: Model, p: Probes, io, exp=None, label="", carry=None)
 @functools.lru_cache(maxsize=None)
 def pool(dtype):
     """(row bits uint16 [P, D], scene index [P]) of one dtype, made on the CPU once per process and never modified:
-    planted scenes of ragged sizes 1 - 23 (tests/test_group_topk_gpu.clustered, noise 0.3: rows of one scene score about
+    planted scenes of ragged sizes 1 - 23 (tests/support.clustered, noise 0.3: rows of one scene score about
     0.92 against each other, rows of two scenes about 0).  f16: every row scaled by 2^u, u uniform in [-2, 2], so the
     row norms spread over a factor of 16 and a norm left on the wrong row shows (tests/test_erase_gpu._data); bf16:
     unit rows."""
     import torch
-    from tests.test_group_topk_gpu import _sizes, clustered
+    from tests.support import clustered, group_sizes
     D = DIMS[dtype]
-    sizes = _sizes(330, "ragged", 11 if dtype == "f16" else 12)
+    sizes = group_sizes(330, "ragged", 11 if dtype == "f16" else 12)
     rows, gid = clustered(sizes, D, "f16" if dtype == "f16" else "bf16", seed=201 if dtype == "f16" else 202, noise=0.3,
                           device="cpu")
     x = rows.float().numpy()

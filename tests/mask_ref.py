@@ -22,11 +22,13 @@ import functools
 import numpy as np
 
 from oracle import cref
+from tests.domain_ref import cert_eps  # noqa: F401  (the certificate's bound; MR.cert_eps for the tests and the other refs)
+from tests.support import bits, clustered, queries_near
 
 K, M1 = 1, 10                       # the scan test's k, and the rank M + 1 = k + 8 + 1 that bounds the rows not re-scored
 QS = (1, 16, 17, 33)
 SHAPES = {"n17": (17, None), "n33": (33, None), "n47": (47, None), "ring40": (57, 40)}   # rows appended, ring capacity
-CLUSTERS = (5, 3, 4, 1, 2)          # tests/test_tile_scan_gpu.py's: at most 5 rows resemble one another
+CLUSTERS = (5, 3, 4, 1, 2)          # cluster sizes, repeated: at most 5 rows resemble one another
 FULL = 0xFFFFFFFF
 
 
@@ -112,16 +114,10 @@ def masked_topk_matrix(queries, rows, sel, k, dtype="f16", score_mode=0, min_sco
 
 
 # ---- the scan test's data and masks ---------------------------------------------------------------------------------
-def cert_eps(D: int) -> float:
-    """The certificate's bound (include/vidmem.h vm_topk_cosine): 2 (D + 8) 2^-24."""
-    return 2.0 * (D + 8) * 2.0 ** -24
-
-
 @functools.lru_cache(maxsize=None)
 def host_dataset(D, dtype, shape):
-    """tests/test_tile_scan_gpu.py's ``dataset`` without its upload: (rows, queries, base, oracle score matrix
-    [33, live rows]) of one shape, from the same generators and seeds, on the host."""
-    from tests.test_group_topk_gpu import _bits, clustered, queries_near
+    """The data of the scan tests, made once on the host (tests/tile_scan_data.py uploads it): (rows, queries, base,
+    oracle score matrix [33, live rows]) of one shape."""
     total, cap = SHAPES[shape]
     sizes, left = [], total
     while left:
@@ -130,8 +126,14 @@ def host_dataset(D, dtype, shape):
     rows, _ = clustered(sizes, D, dtype, seed=D + total, device="cpu")
     base = total - cap if cap else 0
     q = queries_near(rows[base:].contiguous(), max(QS), D + total + 1, dtype)
-    live = cref.cosine_matrix(_bits(q), _bits(rows[base:]), dtype=dtype)
+    live = cref.cosine_matrix(bits(q), bits(rows[base:]), dtype=dtype)
     return rows, q, base, live
+
+
+def host_case(D=128, dtype="f16", shape="n47"):
+    """``host_dataset`` as the oracles take it: (bit patterns of the live rows, of the queries, base, score matrix)."""
+    rows, q, base, live = host_dataset(D, dtype, shape)
+    return bits(rows[base:]), bits(q), base, live
 
 
 def mask_sets(Q: int, shape: str):

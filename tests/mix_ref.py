@@ -23,14 +23,9 @@ import numpy as np
 
 from oracle import cref
 from tests import mask_ref as MR
+from tests.scored_ref import CS, DTS, JS, KS, NQ, W_MAX, W_MIN, rank_pair, scan_selections, slack_m, term_rows  # noqa: F401
 
-CS = (1, 2, 3)                      # QT = 1, QT = 2, and a second query group with one live tile
-JS = (1, 2, 5, 16)
-KS = (1, 5)
-DTS = ((128, "f16"), (128, "bf16"), (384, "f16"), (384, "bf16"))
-NQ = 33                             # queries of the tile-scan dataset: term j of query c is dataset query (c J + j) % 33
 WEIGHT_SETS = ("one", "mean", "feedback", "wide")
-W_MIN, W_MAX = 2.0 ** -20, 2.0 ** 20     # the weight domain of the bound
 
 
 def weights_of(name: str, J: int):
@@ -44,15 +39,6 @@ def weights_of(name: str, J: int):
     if name == "wide":
         return [(-1.0) ** j * 2.0 ** ((j % 5) - 2) for j in range(J)]
     raise KeyError(name)
-
-
-def term_rows(c: int, J: int):
-    return [(c * J + j) % NQ for j in range(J)]
-
-
-def slack_m(k: int) -> int:
-    """M: the candidates re-scored exactly (vm_topk_geom); rank M + 1 bounds the rest."""
-    return k + max(k // 4, 8)
 
 
 def eps_mix(D: int, A: float) -> float:
@@ -119,23 +105,14 @@ def flag0_ok(best_first, k: int, D: int, A: float) -> bool:
     """best_first: one query's exact selected W, descending.  True when rank k and rank M + 1 are more than
     4 x eps_mix(D, A) apart, or when there is no rank M + 1 (everything is re-scored exactly): the fast path must then
     certify the query."""
-    M1 = slack_m(k) + 1
-    return best_first.size < M1 or bool(best_first[k - 1] - best_first[M1 - 1] > 4 * eps_mix(D, A))
+    pair = rank_pair(best_first, k)
+    return pair is None or bool(pair[0] - pair[1] > 4 * eps_mix(D, A))
 
 
 def margin(best_first, k: int, D: int, A: float) -> float:
     """(rank k - rank M + 1) / eps_mix, inf when there is no rank M + 1."""
-    M1 = slack_m(k) + 1
-    return np.inf if best_first.size < M1 else float((best_first[k - 1] - best_first[M1 - 1]) / eps_mix(D, A))
-
-
-def scan_selections(C, shape, base, n):
-    """name -> bool [C, n]: 'none' (no mask) and every set of mask_ref.mask_sets(C, shape)."""
-    total, cap = MR.SHAPES[shape]
-    out = {"none": np.ones((C, n), dtype=bool)}
-    for name, (masks, index) in MR.mask_sets(C, shape).items():
-        out[name] = MR.selection(masks, index, C, base, n, cap or total)
-    return out
+    pair = rank_pair(best_first, k)
+    return np.inf if pair is None else float((pair[0] - pair[1]) / eps_mix(D, A))
 
 
 # ---- the end-to-end test's data ---------------------------------------------------------------------------------------

@@ -21,16 +21,9 @@ from __future__ import annotations
 import numpy as np
 
 from oracle import cref
+from tests.support import to_bits
 
 INT64_MIN = -(1 << 63)
-
-
-def to_bits(x32: np.ndarray, dtype: str) -> np.ndarray:
-    """fp32 values -> uint16 bit patterns of the 16-bit type (round to nearest even, as torch rounds)."""
-    import torch
-    t = torch.from_numpy(np.ascontiguousarray(x32, dtype=np.float32))
-    t = t.to(torch.float16 if dtype == "f16" else torch.bfloat16)
-    return t.view(torch.int16).numpy().view(np.uint16).copy()
 
 
 def clip(n: int, C: int, D: int, sigma: float, dtype: str, seed: int = 5) -> np.ndarray:

@@ -10,14 +10,10 @@ from __future__ import annotations
 import numpy as np
 
 from oracle import cref
+from tests.domain_ref import cert_eps  # noqa: F401  (the fp32 scan's error bound on a cosine; R.cert_eps for the tests)
 from tests.scope_ref import scope_arrays, scope_mask
 
 INT64_MIN, INT64_MAX = -(1 << 63), (1 << 63) - 1
-
-
-def cert_eps(D: int) -> float:
-    """The fp32 scan's error bound on a cosine (csrc/topk_common.h cert_eps): 2 (D + 8) 2^-24."""
-    return 2.0 * (D + 8) * 2.0 ** -24
 
 
 def shown(raw, score_mode=0):

@@ -171,9 +171,9 @@ def scan_precondition(D, dtype, shape) -> int:
 
 def link_scores(D, dtype, shape):
     """(rows uint16 [n,D] in row order, base, the oracle's score matrix [n, n] of the live rows against themselves)."""
-    from tests.test_group_topk_gpu import _bits
+    from tests.support import bits
     rows, _, base, _ = MR.host_dataset(D, dtype, shape)
-    live = np.ascontiguousarray(_bits(rows[base:]))
+    live = np.ascontiguousarray(bits(rows[base:]))
     return live, base, cref.cosine_matrix(live, live, dtype=dtype)
 
 

@@ -14,19 +14,14 @@ import torch
 from oracle import cref
 from tests import bias_ref as BR
 from tests import mask_ref as MR
+from tests.support import same_arrays
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _case(D=128, dtype="f16", shape="n47"):
-    from tests.test_group_topk_gpu import _bits
-    rows, q, base, live = MR.host_dataset(D, dtype, shape)
     total, cap = MR.SHAPES[shape]
-    return _bits(rows[base:]), _bits(q), base, live, cap or total
-
-
-def _same(a, b):
-    return np.array_equal(a[0], b[0]) and np.array_equal(a[1].view(np.int64), b[1].view(np.int64))
+    return (*MR.host_case(D, dtype, shape), cap or total)
 
 
 def _bits64(x):
@@ -52,7 +47,7 @@ def test_loop_and_array_statements_agree_bit_for_bit(D, dtype):
     betas = [BR.query_case(i)[1] for i in range(33)]
     sel = MR.selection(*MR.mask_sets(33, "ring40")["alternating"], 33, base, rows.shape[0], cap)
     for k in (1, 5, 64):
-        assert _same(BR.bias_topk(q, rows, cols, index, betas, sel, k, dtype, base=base, capacity=cap),
+        assert same_arrays(BR.bias_topk(q, rows, cols, index, betas, sel, k, dtype, base=base, capacity=cap),
                      BR.bias_topk(q, rows, cols, index, betas, sel, k, dtype, base=base, capacity=cap,
                                   scores=BR.bias_scores))
 
@@ -69,17 +64,17 @@ def test_zero_weight_and_zero_column_are_the_row_oracle(D, dtype):
             want = cref.cosine_topk(q4, rows, k, dtype=dtype, min_score=cut)
             for beta in (0.0, -0.0):                                # beta = 0: whatever the column holds
                 got = BR.bias_topk(q4, rows, big_col, None, [beta] * 4, None, k, dtype, min_score=cut, capacity=cap)
-                assert _same(got, want), (k, cut, beta)
+                assert same_arrays(got, want), (k, cut, beta)
             for beta in (1.0, -0.5, 2.0 ** 20):                     # a column of zeros: whatever the weight
                 got = BR.bias_topk(q4, rows, zero_col, None, [beta] * 4, None, k, dtype, min_score=cut, capacity=cap)
-                assert _same(got, want), (k, cut, beta)
+                assert same_arrays(got, want), (k, cut, beta)
             got = BR.bias_topk(q4, rows, big_col, [7, -1, 1, 5], None, None, k, dtype, min_score=cut, capacity=cap)
-            assert _same(got, want), "an index outside [0, n_bias) is the zero column"
+            assert same_arrays(got, want), "an index outside [0, n_bias) is the zero column"
         masks, index = MR.mask_sets(4, "n47")["alternating"]
         sel = MR.selection(masks, index, 4, base, n, cap)
         want = MR.masked_topk(q4, rows, sel, k, dtype=dtype, base=base)
-        assert _same(BR.bias_topk(q4, rows, big_col, None, [0.0] * 4, sel, k, dtype, base=base, capacity=cap), want)
-        assert _same(BR.bias_topk(q4, rows, zero_col, None, [0.3] * 4, sel, k, dtype, base=base, capacity=cap), want)
+        assert same_arrays(BR.bias_topk(q4, rows, big_col, None, [0.0] * 4, sel, k, dtype, base=base, capacity=cap), want)
+        assert same_arrays(BR.bias_topk(q4, rows, zero_col, None, [0.3] * 4, sel, k, dtype, base=base, capacity=cap), want)
 
 
 def test_the_reference_cosine_is_never_minus_zero_and_adding_a_zero_changes_no_other_value():
@@ -191,7 +186,7 @@ def test_the_bound_holds_for_the_epilogues_fp32_steps(D, dtype):
 # ---- the Python layer, before the library is called ---------------------------------------------------------------------
 def test_python_refusals_and_scratch():
     from tests.host_memory import host_memory
-    from tests.test_scratch_cpu import SizingLibrary
+    from tests.host_memory import SizingLibrary
     from vidmem import memory as M
     mem = host_memory(capacity=100)
     S = mem.bias_stride

@@ -1,7 +1,7 @@
 """GPU: the biased top-k (vm_topk_cosine_biased, csrc/topk_bias.hip) and its two builders against tests/bias_ref.py.
 
 Bar: rows, fp64 score bits and padding identical to statement (A) of the oracle, for the fast and the ``exact=True``
-entry.  The scan test runs the shapes at which the shared tile scan can go wrong (tests/test_tile_scan_gpu.py's data) for
+entry.  The scan test runs the shapes at which the shared tile scan can go wrong (tests/tile_scan_data.py) for
 every (Q, bias set, weight, mask set, k) of tests/bias_ref.py and demands flag 0 wherever the oracle's scores allow it: the
 redo would hide a broken scan.  That they allow it is asserted from the oracle's scores before any search, and proven
 without a GPU in tests/test_bias_cpu.py.
@@ -12,15 +12,11 @@ import torch
 
 from tests import bias_ref as BR
 from tests import mask_ref as MR
-from tests.test_group_topk_gpu import _bits, clustered, queries_near
-from tests.test_mask_gpu import dev_mask, plain_memory
-from tests.test_tile_scan_gpu import dataset
+from tests.support import (bits, check_entries, clustered, dev_bias, dev_mask, plain_memory, queries_near, redone, same_result,
+                           scan_memory)
+from tests.tile_scan_data import dataset
 
 pytestmark = pytest.mark.gpu
-
-
-def dev_bias(cols) -> torch.Tensor:
-    return torch.from_numpy(np.ascontiguousarray(cols, dtype=np.float32)).cuda()
 
 
 def want_of(mem, q, cols, bindex, betas, k, dtype, masks=None, index=None, **kw):
@@ -28,7 +24,7 @@ def want_of(mem, q, cols, bindex, betas, k, dtype, masks=None, index=None, **kw)
     base, host_rows = mem.rows_host()
     Q = q.shape[0]
     sel = None if masks is None else MR.selection(masks, index, Q, base, host_rows.shape[0], mem.capacity)
-    return BR.bias_topk(_bits(q), host_rows, cols, bindex, betas, sel, k, dtype=dtype, base=base, capacity=mem.capacity,
+    return BR.bias_topk(bits(q), host_rows, cols, bindex, betas, sel, k, dtype=dtype, base=base, capacity=mem.capacity,
                         **kw)
 
 
@@ -36,34 +32,22 @@ def check(mem, q, cols, bindex, betas, k, dtype, masks=None, index=None, certifi
           dcols=None, dmask=None, **kw):
     """Fast and exact entry against (A) (``want``: (A) computed by the caller).  certified: None, or bool per query - the
     fast path must have answered those queries itself (flag 0)."""
-    Q = q.shape[0]
-    want_r, want_s = want or want_of(mem, q, cols, bindex, betas, k, dtype, masks, index, **kw)
+    want = want or want_of(mem, q, cols, bindex, betas, k, dtype, masks, index, **kw)
     b = dcols if dcols is not None else dev_bias(cols)
     m = dmask if dmask is not None else (None if masks is None else dev_mask(masks))
-    out = None
-    for exact in (False, True):
+
+    def call(exact):
         s, r = mem.topk_biased(q, k, b, weight=betas, bias_index=bindex, mask=m, mask_index=index, exact=exact, **kw)
-        got_r, got_s = r.cpu().numpy(), s.cpu().numpy()
-        if not exact:
-            flags = mem.last_bias_flags[:Q].cpu().numpy()
-            out = (got_r, got_s, flags)
-        assert np.array_equal(got_r, want_r), (label, exact, np.argwhere(got_r != want_r)[:5], got_r[:2], want_r[:2])
-        assert np.array_equal(got_s.view(np.int64), want_s.view(np.int64)), f"{label}: scores differ (bit-exact) exact={exact}"
-        if certified is not None and not exact:
-            assert (flags[np.asarray(certified)] == 0).all(), f"{label}: the scan left queries to the redo: {flags}"
-    return out
+        return r, s
+    return check_entries(call, lambda: mem.last_bias_flags[:q.shape[0]], want, certified, label)
 
 
 # ---- 1. the scan ------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("shape", list(MR.SHAPES))
 @pytest.mark.parametrize("D,dtype", BR.DTS)
 def test_scan(D, dtype, shape):
-    rows, q_all, base, live = dataset(D, dtype, shape)
-    hrows, hq, hbase, hlive = MR.host_dataset(D, dtype, shape)
-    assert hbase == base and np.array_equal(_bits(rows), _bits(hrows)) and np.array_equal(_bits(q_all), _bits(hq))
-    total, cap = MR.SHAPES[shape]
-    mem = plain_memory(rows, dtype, capacity=cap, ring=cap is not None, step=19)
-    assert mem.rows_host()[0] == base and mem.bias_stride == BR.bias_stride(mem.capacity)
+    mem, q_all, base, live, total, cap = scan_memory(D, dtype, shape)
+    assert mem.bias_stride == BR.bias_stride(mem.capacity)
     n = live.shape[1]
     cols = BR.set_columns(base, n, mem.capacity)            # NaN in the slots without a live row: ignored
     dcols = dev_bias(cols)
@@ -104,10 +88,6 @@ def test_scan(D, dtype, shape):
 
 
 # ---- 2. identities on the device --------------------------------------------------------------------------------------
-def _same(a, b):
-    return torch.equal(a[1], b[1]) and np.array_equal(a[0].cpu().numpy().view(np.int64), b[0].cpu().numpy().view(np.int64))
-
-
 @pytest.mark.parametrize("dtype", ["f16", "bf16"])
 def test_identities(dtype):
     rows, _ = clustered([5] * 200, 384, dtype, seed=21)
@@ -121,11 +101,11 @@ def test_identities(dtype):
         for exact in (False, True):
             plain, masked = mem.topk(q, k), mem.topk_masked(q, k, mask)
             # beta = 0 whatever the column holds, and a column of zeros whatever the weight: the reference cosine
-            assert _same(mem.topk_biased(q, k, noise, weight=0.0, exact=exact), plain), (k, exact)
-            assert _same(mem.topk_biased(q, k, zero, weight=-0.5, exact=exact), plain), (k, exact)
-            assert _same(mem.topk_biased(q, k, noise, bias_index=[-1] * 16, exact=exact), plain), (k, exact)
-            assert _same(mem.topk_biased(q, k, noise, weight=0.0, mask=mask, exact=exact), masked), (k, exact)
-            assert _same(mem.topk_biased(q, k, zero, mask=mask, exact=exact), masked), (k, exact)
+            assert same_result(mem.topk_biased(q, k, noise, weight=0.0, exact=exact), plain), (k, exact)
+            assert same_result(mem.topk_biased(q, k, zero, weight=-0.5, exact=exact), plain), (k, exact)
+            assert same_result(mem.topk_biased(q, k, noise, bias_index=[-1] * 16, exact=exact), plain), (k, exact)
+            assert same_result(mem.topk_biased(q, k, noise, weight=0.0, mask=mask, exact=exact), masked), (k, exact)
+            assert same_result(mem.topk_biased(q, k, zero, mask=mask, exact=exact), masked), (k, exact)
     # a query's result is the same alone and inside a batch
     cols = torch.cat([noise, 0.1 * noise.flip(1), zero])
     betas = [(1.0, -0.5, 0.3)[i % 3] for i in range(16)]
@@ -136,22 +116,15 @@ def test_identities(dtype):
         s16, r16 = mem.topk_biased(q, 10, cols, weight=betas, bias_index=bindex, mask=masks, mask_index=mindex, exact=exact)
         for i in (0, 1, 5, 15):
             one = mem.topk_biased(q[i:i + 1], 10, cols[bindex[i]], weight=betas[i], mask=masks[mindex[i]], exact=exact)
-            assert _same(one, (s16[i:i + 1], r16[i:i + 1])), (i, exact)
+            assert same_result(one, (s16[i:i + 1], r16[i:i + 1])), (i, exact)
     check(mem, q, cols.cpu().numpy(), bindex, betas, 10, dtype, masks.cpu().numpy().view(np.uint32), mindex, label="batch")
     mem.close()
 
 
 # ---- 3. what must go to the redo and still be exact -------------------------------------------------------------------
 def _redone(mem, q, cols, bindex, betas, k, dtype, label, flag=None, **kw):
-    from vidmem import _lib
-    before = mem.bias_uncertified_count
-    got_r, got_s, flags = check(mem, q, cols, bindex, betas, k, dtype, label=label, **kw)
-    assert (flags != 0).all(), (label, flags)
-    if flag is not None:
-        assert (flags == flag).all(), (label, flags)
-    assert flags[0] in (_lib.VM_FLAG_GAP, _lib.VM_FLAG_OVERFLOW)
-    assert mem.bias_uncertified_count == before + q.shape[0], label
-    return got_r, got_s
+    return redone(lambda: check(mem, q, cols, bindex, betas, k, dtype, label=label, **kw), lambda: mem.bias_uncertified_count,
+                  q.shape[0], label, flag)
 
 
 def test_redo_cases():

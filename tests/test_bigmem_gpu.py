@@ -26,38 +26,27 @@ import torch
 from tests import bigmem_ref as B
 from tests import diverse_ref as DR
 from tests import novelty_ref as NV
+from tests import support
 from tests import topk_plan as TP
+from tests.support import bits, from_bits, np_of
 
 pytestmark = pytest.mark.gpu
 
 L = B.BIG
 CAP = L.N + L.spare
-TD = {"f16": torch.float16, "bf16": torch.bfloat16}
 REPORT = {"layout": L._asdict(), "bytes_of_rows": L.N * L.D * 2, "tests": {}}
-
-
-def _t(bits, dtype="f16"):
-    return torch.from_numpy(np.ascontiguousarray(bits).view(np.int16)).view(TD[dtype]).cuda()
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int16).cpu().numpy().view(np.uint16)
-
-
-def _np(x):
-    return x.cpu().numpy() if hasattr(x, "cpu") else np.asarray(x)
 
 
 def _pair(got_s, got_r, want, what):
     """(scores, rows) of the memory against (rows, scores) of the oracle."""
-    r, s = _np(got_r), np.ascontiguousarray(_np(got_s), np.float64)
+    r, s = np_of(got_r), np.ascontiguousarray(np_of(got_s), np.float64)
     assert np.array_equal(r, want[0]), f"{what} rows: first difference at query {int(np.argmax((r != want[0]).any(1)))}: " \
                                        f"{r[(r != want[0]).any(1)][:2].tolist()} != {want[0][(r != want[0]).any(1)][:2].tolist()}"
     assert np.array_equal(s.view(np.int64), np.ascontiguousarray(want[1]).view(np.int64)), what + " scores (bit-exact bar)"
 
 
 def _flags0(flags, Q, what):
-    f = _np(flags)[:Q]
+    f = np_of(flags)[:Q]
     assert not f.any(), f"{what}: the fast path left queries {np.flatnonzero(f).tolist()[:8]} to the redo, flags {f[f != 0][:8]}"
 
 
@@ -126,7 +115,7 @@ def _gather(mem, column, rows):
 
 def _read_back(mem, model, what):
     slots = torch.from_numpy(model.gid % mem.capacity).cuda()
-    assert np.array_equal(_bits(mem.rows_tensor()[slots]), model.rows), what + ": rows_tensor differs at the sites"
+    assert np.array_equal(bits(mem.rows_tensor()[slots]), model.rows), what + ": rows_tensor differs at the sites"
     assert np.array_equal(_gather(mem, "keys", model.gid), model.keys), what + ": group keys differ at the sites"
     assert np.array_equal(_gather(mem, "tags", model.gid), model.tags), what + ": tags differ at the sites"
 
@@ -139,19 +128,7 @@ def test_append_read_back(st):
     for b in (L.b1, L.b2):      # planted bits on both sides of each boundary
         plant = B.planted_rows(L)
         for r in (b - 1, b):
-            assert np.array_equal(_bits(mem.rows_tensor()[r]), plant[r]), r
-
-
-def _launches(mem, fn):
-    ctx = mem.ctx
-    ctx.profile_mask(None)
-    ctx.profile_enable(256)
-    try:
-        out = fn()
-        prof = ctx.profile_read()
-    finally:
-        ctx.profile_enable(0)
-    return out, {c: prof[c][1] for c in ("topk_scan", "topk_finalize", "topk_exact")}
+            assert np.array_equal(bits(mem.rows_tensor()[r]), plant[r]), r
 
 
 # Q -> (family, kinds of the cascade's passes after the dense one).  256 x 256 tiles: 160 queries have enough of them only
@@ -170,13 +147,13 @@ def _plain(mem, model, Q, what=""):
     if Q >= 160:        # the last pass begins exactly at byte offset 2^32
         assert (plan.passes[-1].begin, plan.passes[-1].limit) == (L.b2, None), plan.passes
     scratch = TopkScratch.for_(mem, Q, B.K)
-    (s, r), launches = _launches(mem, lambda: mem.topk(_t(q, dtype), B.K, redo=False, scratch=scratch))
+    (s, r), launches = support.launches(mem, lambda: mem.topk(from_bits(q, dtype), B.K, redo=False, scratch=scratch))
     assert (launches["topk_scan"], launches["topk_finalize"]) == (plan.launches["topk_scan"], plan.launches["topk_finalize"]), \
         (plan.family, launches, plan.launches)
     _flags0(scratch.flags, Q, f"{what}topk Q={Q} redo=False")
     _pair(s, r, want, f"{what}topk Q={Q} redo=False")
     mem.reset_uncertified()
-    s, r = mem.topk(_t(q, dtype), B.K)
+    s, r = mem.topk(from_bits(q, dtype), B.K)
     _pair(s, r, want, f"{what}topk Q={Q}")
     _flags0(mem._last[TopkScratch].flags, Q, f"{what}topk Q={Q}")
     assert mem.uncertified_count == 0
@@ -193,9 +170,9 @@ def test_topk(st, Q):
 def test_topk_exact_and_exhaustive(st):
     mem, model = st.mem, st.model
     q = B.queries(L, 4, 4)
-    s, r = mem.topk(_t(q), B.K, exact=True)
+    s, r = mem.topk(from_bits(q), B.K, exact=True)
     _pair(s, r, model.topk(q, B.K), "topk exact")
-    (s, r), launches = _launches(mem, lambda: mem.topk(_t(q), 59, min_score=B.RANGE_MIN))
+    (s, r), launches = support.launches(mem, lambda: mem.topk(from_bits(q), 59, min_score=B.RANGE_MIN))
     assert launches["topk_scan"] == 0 and launches["topk_exact"] >= 1, launches
     want = model.topk(q, 59, min_score=B.RANGE_MIN)
     assert ((want[0] >= 0).sum(1) == [B.LEVELS + 1, B.LEVELS + 1, B.LEVELS, B.LEVELS]).all()
@@ -209,14 +186,14 @@ def _both(call, want, flags, Q, what, keys=None):
         form = what + (" exact" if exact else "")
         _pair(out[0], out[1], want, form)
         if keys is not None:
-            assert np.array_equal(_np(out[2]), keys), form + " keys"
+            assert np.array_equal(np_of(out[2]), keys), form + " keys"
         if not exact:
             _flags0(flags(), Q, form)
 
 
 def _scoped_and_grouped(mem, model, what=""):
     q = B.queries(L, 16, 7)
-    tq = _t(q)
+    tq = from_bits(q)
     want = model.grouped(q, B.K)
     _both(lambda e: mem.topk_grouped(tq, B.K, exact=e), want, lambda: mem.last_group_flags, 16, what + "grouped", want[2])
     for name, (scope, k, gk) in B.scope_cases(L).items():
@@ -240,12 +217,12 @@ def test_masked(st):
     q = B.queries(L, 16, 8)
     ids = B.mask_rows(L)
     mask = mem.mask_of_rows(ids)
-    _both(lambda e: mem.topk_masked(_t(q), B.K, mask, exact=e), model.masked(q, model.sel_of_rows(ids, 16), B.K),
+    _both(lambda e: mem.topk_masked(from_bits(q), B.K, mask, exact=e), model.masked(q, model.sel_of_rows(ids, 16), B.K),
           lambda: mem.last_mask_flags, 16, "masked mask_of_rows")
     scope, k, _ = B.scope_cases(L)["sources above b2"]
     mask = mem.mask_of_scope(scope)
     assert not bool(mask[:L.b2 // 32].any()) and bool(mask[L.b2 // 32:].any())      # no bit below row 2^21
-    _both(lambda e: mem.topk_masked(_t(q), k, mask, exact=e), model.masked(q, model.sel_of_scope(scope, 16), k),
+    _both(lambda e: mem.topk_masked(from_bits(q), k, mask, exact=e), model.masked(q, model.sel_of_scope(scope, 16), k),
           lambda: mem.last_mask_flags, 16, "masked mask_of_scope")
 
 
@@ -253,7 +230,7 @@ def _spans(mem, model, what=""):
     q = B.queries(L, 16, 8)
     for name, (fam, spans, k) in B.span_cases(L).items():
         qq = q[list(fam)]
-        _both(lambda e: mem.topk_span(_t(qq), k, spans, exact=e), model.span(qq, spans, k), lambda: mem.last_span_flags,
+        _both(lambda e: mem.topk_span(from_bits(qq), k, spans, exact=e), model.span(qq, spans, k), lambda: mem.last_span_flags,
               len(fam), f"{what}span {name}")
 
 
@@ -267,7 +244,7 @@ def _range(mem, model, what=""):
     for sc in (None, [scope] * 16):
         want = model.range(q, B.RANGE_MIN, sc)
         for exact in (False, True):
-            hits = mem.range_search(_t(q), B.RANGE_MIN, scope=sc, max_hits=64, exact=exact)
+            hits = mem.range_search(from_bits(q), B.RANGE_MIN, scope=sc, max_hits=64, exact=exact)
             for f, (h, w) in enumerate(zip(hits, want)):
                 form = f"{what}range {'scoped ' if sc else ''}{'exact ' if exact else ''}query {f}"
                 assert h.count == w[2] <= 64, f"{form}: {h.count} hits, want {w[2]}"       # never truncated
@@ -286,10 +263,10 @@ def _clip(mem, model, clips, k, min_sep, gap, min_score, what):
     """One clip search, fast and exact; where the oracle's margin condition holds the fast path must certify the clip."""
     want = model.clip(clips, k, min_sep, min_score, max_gap_ms=-1 if gap is None else gap)
     for exact in (False, True):
-        s, r = mem.topk_clip(_t(clips), k, min_sep=min_sep, max_gap_ms=gap, min_score=min_score, exact=exact)
+        s, r = mem.topk_clip(from_bits(clips), k, min_sep=min_sep, max_gap_ms=gap, min_score=min_score, exact=exact)
         _pair(s, r, want, what + (" exact" if exact else ""))
         if not exact:
-            flags = _np(mem.last_clip_flags)[:clips.shape[0]]
+            flags = np_of(mem.last_clip_flags)[:clips.shape[0]]
             bad = np.flatnonzero(want[2] & (flags != 0))
             assert bad.size == 0, f"{what}: the fast path left clips {bad.tolist()} to the redo, flags {flags.tolist()}"
     return want
@@ -316,7 +293,7 @@ def test_clip(st, min_sep, gap):
 def test_mix(st):
     mem, model = st.mem, st.model
     terms, w = B.mix_terms(L), [B.MIX_W] * 16
-    _both(lambda e: mem.topk_mix(_t(terms), w, B.MIX_K, exact=e), model.mix(terms, w, B.MIX_K), lambda: mem.last_mix_flags,
+    _both(lambda e: mem.topk_mix(from_bits(terms), w, B.MIX_K, exact=e), model.mix(terms, w, B.MIX_K), lambda: mem.last_mix_flags,
           16, "mix")
 
 
@@ -325,9 +302,9 @@ def test_diverse(st):
     q, lam = B.queries(L, 16, 10), DR.lam_vector(16)
     want = model.diverse(q, B.DIV_K, B.POOL, lam)
     for exact in (False, True):
-        s, r = mem.topk_diverse(_t(q), B.DIV_K, pool=B.POOL, lam=lam, exact=exact)
+        s, r = mem.topk_diverse(from_bits(q), B.DIV_K, pool=B.POOL, lam=lam, exact=exact)
         _pair(s, r, want, "diverse" + (" exact" if exact else ""))
-        assert np.array_equal(_np(mem.last_diverse_mmr).view(np.int64), want[2].view(np.int64)), "diverse mmr"
+        assert np.array_equal(np_of(mem.last_diverse_mmr).view(np.int64), want[2].view(np.int64)), "diverse mmr"
         if not exact:
             _flags0(mem.last_diverse_flags, 16, "diverse")
     picked = want[0]
@@ -344,9 +321,9 @@ def test_summaries(st):
         at = np.searchsorted(ref.keys, np.arange(g0, g0 + 4))
         assert np.array_equal(ref.keys[at], np.arange(g0, g0 + 4))          # whole groups of the neighbourhoods
         for name in ("first_rows", "n_rows", "keys", "key_rows"):
-            assert np.array_equal(_np(getattr(sm, name)), getattr(ref, name)[at]), f"summaries at group {g0}: {name}"
-        assert np.array_equal(_bits(sm.centroids), ref.centroids[at]), f"summaries at group {g0}: centroids"
-        assert np.array_equal(_np(sm.key_scores).view(np.int64), ref.key_scores[at].view(np.int64)), "summaries key_scores"
+            assert np.array_equal(np_of(getattr(sm, name)), getattr(ref, name)[at]), f"summaries at group {g0}: {name}"
+        assert np.array_equal(bits(sm.centroids), ref.centroids[at]), f"summaries at group {g0}: centroids"
+        assert np.array_equal(np_of(sm.key_scores).view(np.int64), ref.key_scores[at].view(np.int64)), "summaries key_scores"
 
 
 def test_events(st):
@@ -390,16 +367,16 @@ def test_append_novel(st):
     assert keep.tolist() == [False, True] * 3 and row_of[1::2].tolist() == [n0, n0 + 1, n0 + 2]
     ids = n0 + np.arange(3)
     tags = B.tag_of(L, ids) + B.LATE_MS                                   # the stored rows come 5 ms late
-    got = mem.append_novel(_t(batch), 0.8, group=torch.from_numpy(np.repeat(ids // B.GROUP, 2)).cuda(),
+    got = mem.append_novel(from_bits(batch), 0.8, group=torch.from_numpy(np.repeat(ids // B.GROUP, 2)).cuda(),
                            tag=torch.from_numpy(np.repeat(tags, 2)).cuda())
-    assert got.kept == 3 and _np(got.keep).tolist() == keep.tolist()
-    assert _np(got.row_of).tolist() == row_of.tolist()
+    assert got.kept == 3 and np_of(got.keep).tolist() == keep.tolist()
+    assert np_of(got.row_of).tolist() == row_of.tolist()
     assert len(mem) == n0 + 3
     model.append(batch[1::2], ids // B.GROUP, tags)
     _read_back(mem, model, "append_novel")
-    s, r = mem.topk(_t(batch[1::2]), 1)
+    s, r = mem.topk(from_bits(batch[1::2]), 1)
     _pair(s, r, model.topk(batch[1::2], 1), "the rows just stored")
-    assert _np(r)[:, 0].tolist() == ids.tolist()
+    assert np_of(r)[:, 0].tolist() == ids.tolist()
     # a clip across the old tail, past 4 GiB: found without max_gap_ms, no window once the 6 ms step exceeds it
     clip = B.noisy_copy(np.concatenate([model.rows[model.at(n0 - 2):model.at(n0 - 1) + 1], batch[1:5:2]]), 60)[None]
     for gap, found in ((None, True), (1, False), (B.LATE_MS + 1, True)):
@@ -442,7 +419,7 @@ def test_ring(st):
         assert want[0][0, 0] == B.members(L, 0)[0] and want[0][1, 0] == B.members(L, 1)[0]
     q = B.queries(L, 16, 7)
     for name, (scope, k, _) in B.scope_cases(L).items():
-        _both(lambda e: mem.topk_scoped(_t(q), k, scope, exact=e), model.scoped(q, scope, k), lambda: mem.last_scope_flags, 16,
+        _both(lambda e: mem.topk_scoped(from_bits(q), k, scope, exact=e), model.scoped(q, scope, k), lambda: mem.last_scope_flags, 16,
               f"ring: scoped {name}")
     _spans(mem, model, "ring: ")
     want = _range(mem, model, "ring: ")
@@ -463,5 +440,5 @@ def test_bf16(st):
         _plain(mem, model, Q, "bf16: ")
     q = B.queries(L, 16, 7, dtype="bf16")
     for name, (scope, k, _) in B.scope_cases(L).items():
-        _both(lambda e: mem.topk_scoped(_t(q, "bf16"), k, scope, exact=e), model.scoped(q, scope, k),
+        _both(lambda e: mem.topk_scoped(from_bits(q, "bf16"), k, scope, exact=e), model.scoped(q, scope, k),
               lambda: mem.last_scope_flags, 16, f"bf16: scoped {name}")

@@ -6,7 +6,8 @@ import pytest
 import torch
 
 from tests import clip_ref as R
-from tests.test_clip_gpu import MS, contiguous_tags, dev, make_memory, scope_of
+from tests.search_checks import make_memory
+from tests.support import MS, contiguous_tags, from_bits, scope_of
 
 pytestmark = pytest.mark.gpu
 
@@ -18,7 +19,7 @@ def test_clip_similarities_ids_and_scores_match_the_oracle():
     tags = contiguous_tags(n, 3)
     mem = make_memory(rows[:0], "f16", tags=tags[:0], capacity=n)
     ids = [f"frame-{i}" for i in range(n)]
-    mem.append(dev(rows, "f16"), ids=ids, tag=torch.as_tensor(tags).cuda())
+    mem.append(from_bits(rows, "f16"), ids=ids, tag=torch.as_tensor(tags).cuda())
     c16 = R.clips_from(rows, "f16", [100, 900], 16, 1)
     c5 = R.clips_from(rows, "f16", [640], 5, 2)
     vals16, vals5 = R.from_bits(c16, "f16"), R.from_bits(c5, "f16")

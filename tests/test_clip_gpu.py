@@ -22,12 +22,11 @@ import torch
 
 from tests import clip_ref as R
 from tests import domain_ref
+from tests.search_checks import make_memory
+from tests.support import ALL, MS, contiguous_tags, from_bits, scope_of
 
 pytestmark = pytest.mark.gpu
 
-TD = {"f16": torch.float16, "bf16": torch.bfloat16}
-ALL = (R.INT64_MIN, R.INT64_MAX)
-MS = 33
 
 # (D, L, min_sep, k, dtype) at 4,000 rows, C = 5 (odd: the two-clips-per-block scan sees a ragged last pair)
 PARITY = [(768, 16, 16, 10, "f16"), (768, 16, 1, 10, "f16"), (1024, 8, 8, 10, "f16"), (128, 3, 32, 10, "f16"),
@@ -44,25 +43,6 @@ def parity_case(D, L, min_sep, k, dtype):
 def size_case(n, D, L):
     rows = R.scene_video(n, D, "f16", 200 + D)
     return rows, R.clips_from(rows, "f16", R.pick_starts(n, L, 2, n), L, 3)
-
-
-def dev(bits, dtype):
-    return torch.from_numpy(np.array(bits).view(np.int16)).view(TD[dtype]).cuda()
-
-
-def make_memory(bits, dtype, tags=None, capacity=None, ring=False, grouped=False, step=65536):
-    from vidmem.memory import EmbeddingMemory
-    n, D = bits.shape
-    mem = EmbeddingMemory(capacity or max(n, 16), D, dtype, ring=ring, grouped=grouped, tagged=tags is not None)
-    rows = dev(bits, dtype)
-    tg = None if tags is None else torch.as_tensor(np.asarray(tags, dtype=np.int64)).cuda()
-    step = min(step, mem.capacity)
-    for c0 in range(0, n, step):
-        if tg is None:
-            mem.append(rows[c0:c0 + step])
-        else:
-            mem.append(rows[c0:c0 + step], tag=tg[c0:c0 + step])
-    return mem
 
 
 def same(got_r, got_s, want_r, want_s, what=""):
@@ -82,7 +62,7 @@ def check(mem, clips, k, min_sep, dtype, scopes=None, max_gap_ms=None, min_score
                            min_score=min_score, base=base)
     out = None
     for exact in (False, True):
-        s, r = mem.topk_clip(dev(clips, dtype), k, min_sep=min_sep, scope=scopes, max_gap_ms=max_gap_ms,
+        s, r = mem.topk_clip(from_bits(clips, dtype), k, min_sep=min_sep, scope=scopes, max_gap_ms=max_gap_ms,
                              min_score=min_score, score_mode=score_mode, exact=exact)
         got_r, got_s = r.cpu().numpy(), s.cpu().numpy()
         if not exact:
@@ -101,7 +81,7 @@ def test_one_frame_clip_equals_topk(D):
     rows = R.scene_video(4000, D, "f16", 100 + D)
     mem = make_memory(rows, "f16")
     clips = R.clips_from(rows, "f16", R.pick_starts(4000, 1, 5, 1), 1, 2)
-    q = dev(clips, "f16")
+    q = from_bits(clips, "f16")
     s0, r0 = mem.topk(q[:, 0].contiguous(), 10)
     for exact in (False, True):
         s1, r1 = mem.topk_clip(q, 10, min_sep=1, exact=exact)
@@ -134,16 +114,6 @@ def test_selection_at_size_certified(n, D, L, min_sep):
 
 
 # ---- 4. tags ----------------------------------------------------------------------------------------------------------
-def contiguous_tags(n, sources):
-    per = n // sources
-    i = np.arange(n, dtype=np.int64)
-    return ((i // per) << 40) | ((i % per) * MS)
-
-
-def scope_of(source, t0=None, t1=None):
-    return (int(source) << 40) | (0 if t0 is None else t0), (int(source) << 40) | ((1 << 40) - 1 if t1 is None else t1)
-
-
 def test_tags_no_window_spans_two_videos():
     n, L = 2000, 16
     rows = R.scene_video(n, 128, "f16", 31)
@@ -241,13 +211,13 @@ def test_fewer_rows_than_frames_and_exactly_one_window():
     mem = EmbeddingMemory(128, 128, "f16")
     got_r, got_s, _ = check(mem, clips, 3, 8, "f16", label="n = 0")
     assert (got_r == -1).all()
-    mem.append(dev(rows[:7], "f16"))
+    mem.append(from_bits(rows[:7], "f16"))
     got_r, got_s, _ = check(mem, clips, 3, 8, "f16", label="n < L")
     assert (got_r == -1).all() and (got_s == 0.0).all()
-    mem.append(dev(rows[7:8], "f16"))
+    mem.append(from_bits(rows[7:8], "f16"))
     got_r, _, _ = check(mem, clips, 3, 8, "f16", label="n == L")
     assert got_r[0].tolist() == [0, -1, -1]
-    mem.append(dev(rows[8:100], "f16"))
+    mem.append(from_bits(rows[8:100], "f16"))
     got_r, _, _ = check(mem, clips, 10, 32, "f16", label="fewer than k peaks")
     assert 0 < (got_r[0] >= 0).sum() < 10
 
@@ -279,7 +249,7 @@ def test_zero_frames_static_scene_and_min_score():
 def test_domain_row_outside_the_certificate_is_flagged_and_exact():
     n, L = 2000, 8
     bits = R.scene_video(n, 128, "bf16", 47)
-    rows = dev(bits, "bf16")
+    rows = from_bits(bits, "bf16")
     big, exact = domain_ref.scaled(rows[1234:1235], [50])            # norm 2^50: outside [2^-40, 2^40]
     assert exact
     rows[1234] = big[0]
@@ -297,7 +267,7 @@ def test_domain_row_outside_the_certificate_is_flagged_and_exact():
 def test_a_clip_alone_equals_the_clip_in_a_batch():
     rows, clips = parity_case(768, 16, 16, 10, "f16")
     mem = make_memory(rows, "f16")
-    q = dev(clips, "f16")
+    q = from_bits(clips, "f16")
     s5, r5 = mem.topk_clip(q, 10)
     for c in range(5):
         s1, r1 = mem.topk_clip(q[c:c + 1].contiguous(), 10)
@@ -349,7 +319,7 @@ def test_argument_errors():
     assert rc == _lib.VM_ERR_NOMEM and (s == 7.0).all() and (r == 7).all()            # refused before any launch
     for bad in ((2, 0, 5), (2, 17, 5), (0, 8, 5), (2, 8, 0), (2, 8, 65)):
         assert int(mem.L.vm_topk_clip_workspace_bytes(mem.handle, *bad)) == 0
-    q = dev(R.clips_from(rows, "f16", [5], 8, 1), "f16")
+    q = from_bits(R.clips_from(rows, "f16", [5], 8, 1), "f16")
     with pytest.raises(ValueError):
         mem.topk_clip(q, 5, scope=ALL)
     with pytest.raises(ValueError):
@@ -369,7 +339,7 @@ def test_graph_capture_append_and_clip_search_replayed():
     from vidmem.memory import EmbeddingMemory
     L, k, B, Cn = 8, 4, 128, 3
     bits = R.scene_video(1024, 128, "f16", 61)
-    rows = dev(bits, "f16")
+    rows = from_bits(bits, "f16")
     mem = EmbeddingMemory(2048, 128, "f16", tagged=True)
     mem.append(rows[:256], tag=torch.arange(256, device="cuda") * MS)                # source 0
     scratch = mem.prepare_topk_clip(Cn, L, k)
@@ -394,7 +364,7 @@ def test_graph_capture_append_and_clip_search_replayed():
         tg.copy_(((rep + 1) << 40) + torch.arange(B, device="cuda") * MS)
         starts = [n_new - L, 100, 252]                 # the newest rows; source 0; across the first boundary
         clips = R.clips_from(bits, "f16", starts, L, 70 + rep)
-        q.copy_(dev(clips, "f16"))
+        q.copy_(from_bits(clips, "f16"))
         windows = [scope_of(rep + 1), scope_of(0, MS * 10, MS * 200), ALL]
         scope.copy_(torch.tensor(windows, dtype=torch.int64))
         graph.replay()

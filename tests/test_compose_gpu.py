@@ -29,11 +29,12 @@ import pytest
 import torch
 
 from tests import compose_ref as R
+from tests import support
 from tests import topk_plan as TP
+from tests.support import TD
 
 pytestmark = pytest.mark.gpu
 
-TD = {"f16": torch.float16, "bf16": torch.bfloat16}
 APPENDS = (311, 1024, 97, 2048, 5)            # uneven append sizes, cycled
 REDONE = {}                                   # section -> most queries one fast-path call redid exhaustively
 
@@ -325,7 +326,6 @@ def test_sharded_ring_shards_after_every_append():
 def test_sharded_retrieval_on_the_cascade():
     """The strided mapping on the emit cascade at stride 8: shards of capacity 65,536 (launches are sized from the
     capacity), and one call's scan / finalize launch counts are the plan's."""
-    from tests.test_topk_paths_gpu import _launches
     c = R.cascade_case()
     k, Q = R.CASCADE_K, R.CASCADE_Q
     plan = TP.plan(Q, k, c.D, c.dtype, R.CASCADE_CAP, torch.cuda.get_device_properties(0).multi_processor_count)
@@ -335,7 +335,7 @@ def test_sharded_retrieval_on_the_cascade():
     seen = []
 
     def counted(mem, call):
-        out, launches = _launches(mem, call)
+        out, launches = support.launches(mem, call)
         seen.append((launches["topk_scan"], launches["topk_finalize"]))
         return out
 

@@ -16,10 +16,7 @@ from tests import mask_ref as MR
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _case(D=128, dtype="f16", shape="n47"):
-    from tests.test_group_topk_gpu import _bits
-    rows, q, base, live = MR.host_dataset(D, dtype, shape)
-    return _bits(rows[base:]), _bits(q), base, live
+_case = MR.host_case
 
 
 def _same(a, b):
@@ -115,7 +112,7 @@ def test_a_pool_larger_than_the_selected_rows_pads():
 # ---- the Python layer, before the library is called ------------------------------------------------------------------------
 def test_python_refusals_and_scratch():
     from tests.host_memory import host_memory
-    from tests.test_scratch_cpu import SizingLibrary
+    from tests.host_memory import SizingLibrary
     from vidmem import memory as M
     mem = host_memory(capacity=100)
     q = torch.zeros((2, mem.dim))
@@ -200,7 +197,6 @@ def test_scan_preconditions(D, dtype):
     """(i) Without a mask no query of the scan test is left to the redo: at k = pool, rank ``pool`` and rank M + 1 of the
     oracle's scores are more than 4 x cert_eps(D) apart, or fewer than M + 1 rows are live.  (ii) The test is not vacuous:
     at lam = 0.5, k = 5 the picks differ from plain top-5 for at least half of the 33 queries of every shape and pool."""
-    from tests.test_group_topk_gpu import _bits
     for shape in MR.SHAPES:
         rows, q, base, live = _case(D, dtype, shape)
         sim = DR.sim_matrix(rows, dtype)

@@ -2,7 +2,7 @@
 
 Bar: rows, fp64 relevance bits, fp64 mmr bits and padding identical to statement (A) of the oracle, for the fast and the
 ``exact=True`` entry.  There is no tolerance: the contract fixes every rounding.  The scan test runs the shapes at which
-the shared tile scan can go wrong (tests/test_tile_scan_gpu.py's data) and demands flag 0 wherever the oracle's scores
+the shared tile scan can go wrong (tests/tile_scan_data.py) and demands flag 0 wherever the oracle's scores
 allow it - without a mask, everywhere: the redo would hide a broken scan.  That they allow it, and that the picks differ
 from plain top-k at all, is proven without a GPU in tests/test_diverse_cpu.py.
 """
@@ -12,9 +12,8 @@ import torch
 
 from tests import diverse_ref as DR
 from tests import mask_ref as MR
-from tests.test_group_topk_gpu import _bits, clustered, queries_near
-from tests.test_mask_gpu import dev_mask, plain_memory
-from tests.test_tile_scan_gpu import dataset
+from tests.support import bits, check_entries, clustered, dev_mask, plain_memory, queries_near, same_result, scan_memory
+from tests.tile_scan_data import dataset
 
 pytestmark = pytest.mark.gpu
 
@@ -24,30 +23,22 @@ def want_of(mem, q, k, pool, lam, dtype, masks=None, index=None, **kw):
     base, host_rows = mem.rows_host()
     sel = None if masks is None else MR.selection(masks, index, q.shape[0], base, host_rows.shape[0], mem.capacity)
     sim = DR.sim_matrix(host_rows, dtype) if host_rows.shape[0] <= 128 else None    # else pool by pool
-    return DR.diverse_topk(_bits(q), host_rows, sel, k, pool, lam, dtype=dtype, base=base, sim=sim, **kw)
+    return DR.diverse_topk(bits(q), host_rows, sel, k, pool, lam, dtype=dtype, base=base, sim=sim, **kw)
 
 
 def check(mem, q, k, pool, lam, dtype, masks=None, index=None, certified=None, label="", want=None, lam_dev=None, **kw):
     """Fast and exact entry against (A) (``want``: (A) computed by the caller).  certified: None, or bool per query - the
     pool stage must have answered those queries itself (flag 0).  lam_dev: the device tensor to pass in place of lam."""
     Q = q.shape[0]
-    want_r, want_s, want_v = want or want_of(mem, q, k, pool, lam, dtype, masks, index, **kw)
+    want = want or want_of(mem, q, k, pool, lam, dtype, masks, index, **kw)
+    assert all(w.shape == (Q, k) for w in want), f"{label}: the oracle's outputs are not [Q, k]"
     m = None if masks is None else (masks if isinstance(masks, torch.Tensor) else dev_mask(masks))
-    out = None
-    for exact in (False, True):
+
+    def call(exact):
         s, r = mem.topk_diverse(q, k, pool=pool, lam=lam if lam_dev is None else lam_dev, mask=m, mask_index=index,
                                 exact=exact, **kw)
-        got_r, got_s, got_v = r.cpu().numpy(), s.cpu().numpy(), mem.last_diverse_mmr.cpu().numpy()
-        assert got_r.shape == got_s.shape == got_v.shape == (Q, k)
-        if not exact:
-            flags = mem.last_diverse_flags[:Q].cpu().numpy()
-            out = (got_r, got_s, got_v, flags)
-        assert np.array_equal(got_r, want_r), (label, exact, np.argwhere(got_r != want_r)[:5], got_r[:2], want_r[:2])
-        assert np.array_equal(got_s.view(np.int64), want_s.view(np.int64)), f"{label}: scores differ (bit-exact) exact={exact}"
-        assert np.array_equal(got_v.view(np.int64), want_v.view(np.int64)), f"{label}: mmr differs (bit-exact) exact={exact}"
-        if certified is not None and not exact:
-            assert (flags[np.asarray(certified)] == 0).all(), f"{label}: the scan left queries to the redo: {flags}"
-    return out
+        return r, s, mem.last_diverse_mmr
+    return check_entries(call, lambda: mem.last_diverse_flags[:Q], want, certified, label)
 
 
 # ---- 1. the scan ------------------------------------------------------------------------------------------------------
@@ -56,9 +47,8 @@ class _Oracle:
     selection comes from one cref.cosine_topk call for all 33 queries, the pairs from one cref.cosine_matrix call."""
 
     def __init__(self, D, dtype, shape):
-        rows, q, self.base, self.live = MR.host_dataset(D, dtype, shape)
+        self.rows, self.q, self.base, self.live = MR.host_case(D, dtype, shape)
         self.dtype = dtype
-        self.rows, self.q = _bits(rows[self.base:]), _bits(q)
         self.sim = DR.sim_matrix(self.rows, dtype)
         self.pools, self.picks = {}, {}
 
@@ -86,12 +76,10 @@ class _Oracle:
 @pytest.mark.parametrize("shape", list(MR.SHAPES))
 @pytest.mark.parametrize("D,dtype", DR.DTS)
 def test_scan(D, dtype, shape):
-    rows, q_all, base, live = dataset(D, dtype, shape)
+    mem, q_all, base, live, total, cap = scan_memory(D, dtype, shape)
+    rows = dataset(D, dtype, shape)[0]
     ora = _Oracle(D, dtype, shape)
-    assert ora.base == base and np.array_equal(_bits(rows[base:]), ora.rows) and np.array_equal(_bits(q_all), ora.q)
-    total, cap = MR.SHAPES[shape]
-    mem = plain_memory(rows, dtype, capacity=cap, ring=cap is not None, step=19)
-    assert mem.rows_host()[0] == base
+    assert ora.base == base and np.array_equal(bits(rows[base:]), ora.rows) and np.array_equal(bits(q_all), ora.q)
     n = live.shape[1]
     differ = 0
     for Q in DR.QS:
@@ -119,10 +107,6 @@ def test_scan(D, dtype, shape):
 
 
 # ---- 2. identities on the device --------------------------------------------------------------------------------------
-def _same(a, b):
-    return torch.equal(a[1], b[1]) and np.array_equal(a[0].cpu().numpy().view(np.int64), b[0].cpu().numpy().view(np.int64))
-
-
 @pytest.mark.parametrize("dtype", ["f16", "bf16"])
 def test_identities(dtype):
     rows, _ = clustered([5] * 200, 384, dtype, seed=21)
@@ -134,11 +118,11 @@ def test_identities(dtype):
         for exact in (False, True):
             for pool in (k, 64):
                 got = mem.topk_diverse(q, k, pool=pool, lam=1.0, exact=exact)
-                assert _same(got, mem.topk(q, k)), (k, pool, exact)
+                assert same_result(got, mem.topk(q, k)), (k, pool, exact)
                 assert np.array_equal(mem.last_diverse_mmr.cpu().numpy().view(np.int64),
                                       got[0].cpu().numpy().view(np.int64))             # 1.0 e - 0.0 red = e
                 got = mem.topk_diverse(q, k, pool=pool, lam=1.0, mask=mask, exact=exact)
-                assert _same(got, mem.topk_masked(q, k, mask)), (k, pool, exact)
+                assert same_result(got, mem.topk_masked(q, k, mask)), (k, pool, exact)
     # a query's result is the same alone and inside a batch of 33
     lam = DR.lam_vector(33)
     masks = torch.cat([mask, ~mask])
@@ -148,7 +132,7 @@ def test_identities(dtype):
         v33 = mem.last_diverse_mmr.clone()
         for c in (0, 15, 16, 32):
             s1, r1 = mem.topk_diverse(q[c], 10, pool=40, lam=lam[c], mask=masks[index[c]], exact=exact)
-            assert _same((s1, r1), (s33[c:c + 1], r33[c:c + 1])), (c, exact)
+            assert same_result((s1, r1), (s33[c:c + 1], r33[c:c + 1])), (c, exact)
             assert torch.equal(mem.last_diverse_mmr.view(torch.int64), v33[c:c + 1].view(torch.int64))
     check(mem, q, 10, 40, lam, dtype, masks.cpu().numpy().view(np.uint32), index, label="batch of 33")
     # pool == k only reorders the top k

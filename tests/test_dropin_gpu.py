@@ -17,12 +17,9 @@ import torch
 from oracle import cref
 from oracle import frames_ref as F
 from oracle import vit_ref as V
+from tests.support import bits
 
 pytestmark = pytest.mark.gpu
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int16).cpu().numpy().view(np.uint16)
 
 
 def rel(a, b):
@@ -63,7 +60,7 @@ def test_extractor_from_config_alone_and_neighbours_against_the_oracle(tmp_path,
         if first == 0:
             assert res["similar"] == []
             continue
-        want_r, want_s = cref.cosine_topk(_bits(stored[first:first + 6]), _bits(stored[:first]), 3, dtype="f16")
+        want_r, want_s = cref.cosine_topk(bits(stored[first:first + 6]), bits(stored[:first]), 3, dtype="f16")
         want = [[[f"{run_id}_{r // 6}_{r % 6}", float(s)] for r, s in zip(rq, sq) if r >= 0]
                 for rq, sq in zip(want_r, want_s)]
         assert res["similar"] == want                             # ids by the reference's scheme, fp64 scores bit for bit

@@ -15,10 +15,10 @@ import torch
 from oracle import frames_ref as F
 from oracle import vit_ref as V
 from tests import preprocess_ref as PR
+from tests.support import TD
 
 pytestmark = pytest.mark.gpu
 
-TD = {"f16": torch.float16, "bf16": torch.bfloat16}
 # Bars.  north_star: embeddings within 1e-3 relative of the CPU path.
 #   fp16: 1e-3, against BOTH oracles (same storage points; plain fp32).
 #   bf16: 1e-3 is below what ANY implementation with bf16 matrix operands can reach - tests/golden/bf16_floor.py prices

@@ -17,19 +17,13 @@ from oracle import cref
 from tests import erase_ref as E
 from tests import group_ref as G
 from tests import scope_ref as S
+from tests.support import MS, TD, from_bits
 
 pytestmark = pytest.mark.gpu
 
 N, CAP, SEG = 2000, 2100, 256
 SHAPES = [("f16", 128), ("bf16", 768)]
 KINDS = ["plain", "tagged", "grouped", "tagged_grouped"]
-TD = {"f16": torch.float16, "bf16": torch.bfloat16}
-MS = 33
-
-
-def _t(bits, dtype):
-    """uint16 bit patterns -> device tensor of the memory dtype."""
-    return torch.from_numpy(np.ascontiguousarray(bits).view(np.int16)).view(TD[dtype]).cuda()
 
 
 @functools.lru_cache(maxsize=None)
@@ -61,7 +55,7 @@ def _fill(mem, cols: E.Columns, dtype):
     if mem.tagged:
         kw["tag"] = torch.from_numpy(np.array(cols.tags))
     if cols.rows.shape[0]:
-        mem.append(_t(cols.rows, dtype), **kw)
+        mem.append(from_bits(cols.rows, dtype), **kw)
     return mem
 
 
@@ -99,7 +93,7 @@ def _check_searches(mem, cols: E.Columns, dtype, qbits, base=0):
     """topk / topk_grouped / topk_scoped of ``mem`` against the oracle over ``cols`` (the rows ``mem`` should hold)."""
     if cols.rows.shape[0] == 0:
         return
-    q = _t(qbits, dtype)
+    q = from_bits(qbits, dtype)
     want_r, want_s = cref.cosine_topk(np.ascontiguousarray(qbits), np.ascontiguousarray(cols.rows), 10, dtype=dtype)
     s, r = mem.topk(q, 10)
     assert np.array_equal(r.cpu().numpy(), np.where(want_r >= 0, want_r + base, -1))
@@ -128,7 +122,7 @@ def _check_against_fresh(mem, kind, dtype, model: E.ErasedModel, n_used, qbits):
     assert np.array_equal(_raw(mem, n_used)[0][:n_new].view(np.uint16), model.cols.rows)
     assert not _raw(mem, n_used)[0][n_new:].any()                 # forgetting means the bytes are gone
     if n_new:
-        q = _t(qbits, dtype)
+        q = from_bits(qbits, dtype)
         mem.reset_uncertified()
         for a, b in zip(mem.topk(q, 10), fresh.topk(q, 10)):
             assert torch.equal(a, b)
@@ -205,7 +199,7 @@ def test_groups_merge_when_the_group_between_them_goes():
     keys = np.array([4] * 10 + [9] * 10 + [4] * 10, np.int64)                 # A B A
     cols = E.Columns(bits[:30], None, keys)
     mem = _fill(_memory("grouped", 64, D, dtype), cols, dtype)
-    q = _t(bits[[2, 25]], dtype)
+    q = from_bits(bits[[2, 25]], dtype)
     assert set(mem.topk_grouped(q, 3)[2][0].tolist()) == {4, 9}
     assert mem.topk_grouped(q, 3)[2][0].tolist().count(4) == 2                # two groups with key 4
     new_row_of, erased = _erase(mem, rows=list(range(10, 20)))
@@ -223,10 +217,10 @@ def test_erasing_the_last_row_leaves_the_group_before_it_open():
     mem = _fill(_memory("grouped", 64, D, dtype), cols, dtype)
     new_row_of, erased = _erase(mem, rows=[5])
     assert erased == 1 and new_row_of.tolist() == [0, 1, 2, 3, 4, -1]
-    mem.append(_t(bits[6:9], dtype), group=torch.tensor([1, 1, 3]))           # continues group 1, then opens group 3
+    mem.append(from_bits(bits[6:9], dtype), group=torch.tensor([1, 1, 3]))           # continues group 1, then opens group 3
     want = E.Columns(np.concatenate([bits[:5], bits[6:9]]), None, np.array([1] * 7 + [3], np.int64))
     fresh = _fill(_memory("grouped", 64, D, dtype), want, dtype)
-    q = _t(bits[[0, 7, 8]], dtype)
+    q = from_bits(bits[[0, 7, 8]], dtype)
     got = mem.topk_grouped(q, 4)
     for a, b in zip(got, fresh.topk_grouped(q, 4)):
         assert torch.equal(a, b)
@@ -241,7 +235,7 @@ def test_rows_form_takes_a_padded_topk_result_and_an_empty_list():
     cols = _columns("tagged_grouped", dtype, D)
     qbits = _data(dtype, D)[3]
     mem = _fill(_memory("tagged_grouped", CAP, D, dtype), cols, dtype)
-    s, r = mem.topk(_t(qbits, dtype), 10, min_score=0.1)
+    s, r = mem.topk(from_bits(qbits, dtype), 10, min_score=0.1)
     assert r.shape == (5, 10) and (r == -1).any() and (r >= 0).any()          # a padded result
     ids = torch.cat([r, r[:2], torch.full((1, 10), N + 7, dtype=torch.int64, device="cuda")])       # duplicates, past the end
     out = mem.erase(rows=ids)
@@ -283,12 +277,12 @@ def test_erase_reclaims_the_capacity_of_a_full_memory():
     cols = E.Columns(bits[:cap], tags, None)
     mem = _fill(_memory("tagged", cap, D, dtype), cols, dtype)
     with pytest.raises(_lib.VidmemError) as e:
-        mem.append(_t(bits[cap:cap + 1], dtype), tag=make_tag(9, 0))
+        mem.append(from_bits(bits[cap:cap + 1], dtype), tag=make_tag(9, 0))
     assert e.value.code == _lib.VM_ERR_NOMEM
     out = mem.erase(scope=[scope_of(1), scope_of(2), scope_of(4)])           # 300 rows
     assert out.count == 300 and len(mem) == cap - 300
     new_tags = np.array([make_tag(9, i * MS) for i in range(300)], np.int64)
-    assert mem.append(_t(bits[1000:1300], dtype), tag=torch.from_numpy(new_tags)) == cap - 300
+    assert mem.append(from_bits(bits[1000:1300], dtype), tag=torch.from_numpy(new_tags)) == cap - 300
     assert len(mem) == cap
     model = E.erase(cols, E.mask_of_scopes(tags, [scope_of(1), scope_of(2), scope_of(4)]))
     want = E.Columns(np.concatenate([model.cols.rows, bits[1000:1300]]), np.concatenate([model.cols.tags, new_tags]), None)
@@ -302,12 +296,12 @@ def test_ring_below_its_capacity_erases_and_then_wraps():
     bits, _, _, _ = _data(dtype, D)
     tags = np.arange(400, dtype=np.int64) * 3
     mem = _memory("tagged", cap, D, dtype, ring=True)
-    mem.append(_t(bits[:200], dtype), tag=torch.from_numpy(tags[:200]))
+    mem.append(from_bits(bits[:200], dtype), tag=torch.from_numpy(tags[:200]))
     drop = E.mask_of_rows(200, range(40, 90))
     new_row_of, erased = _erase(mem, rows=torch.arange(40, 90))
     model = E.erase(E.Columns(bits[:200], tags[:200], None), drop)
     assert erased == 50 and np.array_equal(new_row_of, model.new_row_of) and len(mem) == 150
-    mem.append(_t(bits[200:400], dtype), tag=torch.from_numpy(tags[200:400]))           # 350 rows: the ring wraps
+    mem.append(from_bits(bits[200:400], dtype), tag=torch.from_numpy(tags[200:400]))           # 350 rows: the ring wraps
     assert len(mem) == 350 and mem.searchable == cap
     all_rows = np.concatenate([model.cols.rows, bits[200:400]])
     all_tags = np.concatenate([model.cols.tags, tags[200:400]])
@@ -321,9 +315,9 @@ def test_wrapped_ring_is_refused_and_the_device_guards_a_stale_mirror():
     dtype, D, cap = "f16", 128, 64
     bits, _, _, _ = _data(dtype, D)
     mem = _memory("tagged_grouped", cap, D, dtype, ring=True)
-    mem.append(_t(bits[:60], dtype), tag=torch.arange(60), group=torch.arange(60) // 4)
+    mem.append(from_bits(bits[:60], dtype), tag=torch.arange(60), group=torch.arange(60) // 4)
     # 20 more rows through the gated append, which does not advance the host mirror: the device wraps, the mirror says 60
-    mem.enqueue_append_novel(_t(bits[60:80], dtype), 2.0, tag=torch.arange(60, 80).cuda(),
+    mem.enqueue_append_novel(from_bits(bits[60:80], dtype), 2.0, tag=torch.arange(60, 80).cuda(),
                              group=(torch.arange(60, 80) // 4).cuda())
     assert len(mem) == 60
     before = _raw(mem, cap)
@@ -382,10 +376,10 @@ def test_capture_append_erase_older_than_and_scoped_search_in_one_graph():
         T = t_of(30 + 70 * rep)                                               # 31, 70, 70 rows older than T
         windows = [(T + 1, S.INT64_MAX), (t_of(lo), t_of(lo + B)), (0, T), (S.INT64_MIN, S.INT64_MAX)]
         qb = np.stack([bits[50 + 70 * rep], bits[lo + 1], bits[3], bits[lo + B - 1]])
-        rows_in.copy_(_t(bits[lo:lo + B], dtype))
+        rows_in.copy_(from_bits(bits[lo:lo + B], dtype))
         tags_in.copy_(torch.from_numpy(new_tags))
         older.copy_(torch.tensor([[t_of(0), T]]))
-        q_in.copy_(_t(qb, dtype))
+        q_in.copy_(from_bits(qb, dtype))
         window.copy_(torch.tensor(windows, dtype=torch.int64))
         graph.replay()
         torch.cuda.synchronize()
@@ -410,7 +404,7 @@ def test_erase_remaps_the_tables_and_an_erased_memory_round_trips(tmp_path):
     qbits = _data(dtype, D)[3]
     mem = _memory("tagged_grouped", CAP, D, dtype)
     kw = {"group": torch.from_numpy(np.array(cols.keys)), "tag": torch.from_numpy(np.array(cols.tags))}
-    mem.append(_t(cols.rows, dtype), ids=[f"c_{i}" for i in range(N)], meta=[{"i": i} for i in range(N)], **kw)
+    mem.append(from_bits(cols.rows, dtype), ids=[f"c_{i}" for i in range(N)], meta=[{"i": i} for i in range(N)], **kw)
     with pytest.raises(ValueError):
         mem.erase()
     with pytest.raises(ValueError):
@@ -432,7 +426,7 @@ def test_erase_remaps_the_tables_and_an_erased_memory_round_trips(tmp_path):
     mem.snapshot(path)
     back = EmbeddingMemory.restore(path, capacity=CAP)
     assert back.tagged and back.grouped and len(back) == len(mem) and back.ids == mem.ids
-    q = _t(qbits, dtype)
+    q = from_bits(qbits, dtype)
     for a, b in zip(mem.topk(q, 10) + mem.topk_grouped(q, 10) + mem.topk_scoped(q, 10, scope_of(3)),
                     back.topk(q, 10) + back.topk_grouped(q, 10) + back.topk_scoped(q, 10, scope_of(3))):
         assert torch.equal(a, b)

@@ -13,40 +13,16 @@ from oracle import cref
 from tests import events_ref as E
 from tests import group_ref as G
 from tests.novelty_feed import threshold_between
+from tests.search_checks import e2e_extractor, scene_clip
+from tests.support import Embedder, bits
 
 pytestmark = pytest.mark.gpu
 
 LENGTHS = [7, 3, 12, 1, 9, 6, 2, 11, 4, 5]          # frames per scene: 60 frames, cuts inside and between chunks of 5
 
 
-def _bits(t):
-    return t.contiguous().view(torch.int16).cpu().numpy().view(np.uint16)
-
-
-def scene_clip(seed, lengths, H, W, block=16):
-    """-> (frames uint8 [n, H, W, 3], owner int [n]): every scene is one image of random colour blocks shown
-    ``lengths[i]`` times in a row, each showing with its own +-1 of pixel noise (tests/novelty_feed.py's frames)."""
-    rng = np.random.default_rng(seed)
-    blocks = rng.integers(0, 256, size=(len(lengths), H // block, W // block, 3), dtype=np.uint8)
-    src = np.kron(blocks, np.ones((1, block, block, 1), np.uint8))
-    frames, owner = [], []
-    for i, n in enumerate(lengths):
-        for _ in range(n):
-            noise = rng.integers(-1, 2, size=src[i].shape)
-            frames.append(np.clip(src[i].astype(np.int16) + noise, 0, 255).astype(np.uint8))
-            owner.append(i)
-    return np.stack(frames), np.array(owner)
-
-
 def _run(tmp_path, clip, enc, memory_cfg, look_ahead, tag):
-    from vidmem import config as C
-    from vidmem.extractor import FrameEmbeddingExtractor
-    cfg = C.from_dict({
-        "video": {"chunk_size_seconds": 1.0, "frames_per_chunk": 5},
-        "encoder": {"arch": "vit_b16_2l", "dtype": "f16", "seed": 3, "top_k": 4, "look_ahead_chunks": look_ahead},
-        "memory": {"capacity": 512, **memory_cfg},
-    })
-    ex = FrameEmbeddingExtractor(cfg, encoder=enc)
+    ex = e2e_extractor(enc, memory_cfg, look_ahead)
     out = json.load(open(asyncio.run(ex.process_video(str(clip), str(tmp_path / f"out_{tag}.json")))))
     rid = out["metadata"]["run_id"]
     res = [{**r, "processing_time": None, "group_time": None, "group_chunks": None,
@@ -56,14 +32,6 @@ def _run(tmp_path, clip, enc, memory_cfg, look_ahead, tag):
     for key in ("group_by", "event_threshold"):           # the config echo
         out["metadata"]["config"]["memory"].pop(key)
     return ex, res, out["metadata"], rid
-
-
-class _Embedder:
-    def __init__(self, vec):
-        self.vec = vec
-
-    async def aembed_query(self, text):
-        return self.vec
 
 
 def test_group_by_event_changes_no_output_and_groups_are_the_scenes(tmp_path, monkeypatch):
@@ -103,10 +71,10 @@ def test_group_by_event_changes_no_output_and_groups_are_the_scenes(tmp_path, mo
     rows = mem.rows_tensor()
     noise = torch.randn(rows.shape[1], device="cuda", generator=torch.Generator("cuda").manual_seed(1))
     q16 = (rows[15].float() + 0.02 * noise).to(torch.float16)
-    vs = HipVectorSearch(mem, _Embedder(q16.double().cpu().tolist()), SimpleNamespace(top_k_chunks=4),
+    vs = HipVectorSearch(mem, Embedder(q16.double().cpu().tolist()), SimpleNamespace(top_k_chunks=4),
                          min_score=-1.0, score_mode=_lib.VM_SCORE_RAW, distinct=True)
     hits = asyncio.run(vs._vector_search_chunks(None, "q"))
-    want_r, want_s, _ = G.grouped_topk(_bits(q16[None]), stored, want.keys, 4, min_score=-1.0)
+    want_r, want_s, _ = G.grouped_topk(bits(q16[None]), stored, want.keys, 4, min_score=-1.0)
     assert [c["id"] for c in hits] == [mem.id_of(int(r)) for r in want_r[0]]
     assert [c["score"] for c in hits] == want_s[0].tolist()
     scenes = [int(owner[int(r)]) for r in want_r[0]]

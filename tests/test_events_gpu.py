@@ -13,71 +13,27 @@ import torch
 
 from tests import events_ref as E
 from tests import group_ref as G
+from tests.search_checks import RING_CAP, SENT_I, SENT_LINK, events_ws_need, ptr, raw_append_memory, raw_regroup
+from tests.support import from_bits, same_bits
 
 pytestmark = pytest.mark.gpu
-
-TD = {"f16": torch.float16, "bf16": torch.bfloat16}
-SENT_LINK, SENT_I = 123.0, -7          # what the output buffers hold before a call
-RING_CAP = {"f16_768": 3019, "bf16_1024": 1123, "f16_128": 2203}       # primes below n
-
-
-def _t(bits, dtype):
-    """uint16 bit patterns -> device tensor of the memory dtype."""
-    return torch.from_numpy(np.array(bits, copy=True).view(np.int16)).view(TD[dtype]).cuda()
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr() if t is not None else 0)
-
-
-def memory(bits, dtype, capacity=None, ring=False, grouped=False, tags=None, step=1000):
-    """A memory that was appended ``bits`` through the C entries with keys NULL (a grouped memory then holds the plain
-    append's columns: every row its own group), with ``tags`` if given."""
-    from vidmem import _lib
-    from vidmem.memory import EmbeddingMemory
-    n = bits.shape[0]
-    mem = EmbeddingMemory(capacity or max(n, 1), bits.shape[1], dtype, ring=ring, grouped=grouped, tagged=tags is not None)
-    step = min(step, mem.capacity)
-    first = C.c_int64(0)
-    for c0 in range(0, n, step):
-        rows = _t(bits[c0:c0 + step], dtype)
-        if tags is None:
-            rc = mem.L.vm_memory_append(mem.handle, _p(rows), rows.shape[0], C.byref(first), _lib.current_stream_ptr())
-        else:
-            tg = torch.from_numpy(np.ascontiguousarray(tags[c0:c0 + step])).cuda()
-            rc = mem.L.vm_memory_append_tagged(mem.handle, _p(rows), rows.shape[0], _p(tg), None, C.byref(first),
-                                               _lib.current_stream_ptr())
-        mem.ctx.check(rc)
-        torch.cuda.synchronize()
-    mem.sync()
-    return mem
-
-
-def ws_need(mem):
-    need = int(mem.L.vm_memory_events_workspace_bytes(mem.handle))
-    assert 0 < need <= 2 * mem.capacity + (1 << 14), need
-    return need
 
 
 def raw_events(mem, threshold, gap=-1, max_events=0, links=True, event_of=True, ws_bytes=None, room=3):
     """One call of the C entry on sentinel-filled buffers ``room`` entries longer than the capacity / ``max_events`` ->
     (rc, links, event_of, first_rows, count) as numpy arrays (the whole buffers, sentinels included)."""
     from vidmem import _lib
-    need = ws_need(mem)
+    need = events_ws_need(mem)
     ws = torch.empty(max(need if ws_bytes is None else ws_bytes, 256), dtype=torch.uint8, device="cuda")
     lk = torch.full((mem.capacity + room,), SENT_LINK, dtype=torch.float64, device="cuda")
     ev = torch.full((mem.capacity + room,), SENT_I, dtype=torch.int64, device="cuda")
     fr = torch.full((max_events + room,), SENT_I, dtype=torch.int64, device="cuda")
     cnt = torch.full((1,), SENT_I, dtype=torch.int64, device="cuda")
-    rc = mem.L.vm_memory_events(mem.handle, float(threshold), int(gap), _p(lk if links else None),
-                                _p(ev if event_of else None), int(max_events), _p(fr if max_events else None), _p(cnt),
-                                _p(ws), need if ws_bytes is None else ws_bytes, _lib.current_stream_ptr())
+    rc = mem.L.vm_memory_events(mem.handle, float(threshold), int(gap), ptr(lk if links else None),
+                                ptr(ev if event_of else None), int(max_events), ptr(fr if max_events else None), ptr(cnt),
+                                ptr(ws), need if ws_bytes is None else ws_bytes, _lib.current_stream_ptr())
     torch.cuda.synchronize()
     return rc, lk.cpu().numpy(), ev.cpu().numpy(), fr.cpu().numpy(), int(cnt.item())
-
-
-def same_bits(a, b):
-    return np.array_equal(np.asarray(a, np.float64).view(np.int64), np.asarray(b, np.float64).view(np.int64))
 
 
 def check_events(mem, link, flags, base, threshold, gap=-1, max_events=None, label=""):
@@ -114,21 +70,6 @@ def live_columns(mem):
     return k, o
 
 
-def raw_regroup(mem, threshold, gap=-1, from_row=None, ws_bytes=None):
-    """-> (rc, count); ``from_row``: None, an int (copied to the device) or a device tensor."""
-    from vidmem import _lib
-    need = ws_need(mem)
-    ws = torch.empty(max(need if ws_bytes is None else ws_bytes, 256), dtype=torch.uint8, device="cuda")
-    cnt = torch.full((1,), SENT_I, dtype=torch.int64, device="cuda")
-    frm = None
-    if from_row is not None:
-        frm = from_row if isinstance(from_row, torch.Tensor) else torch.tensor([int(from_row)], dtype=torch.int64).cuda()
-    rc = mem.L.vm_memory_regroup_events(mem.handle, float(threshold), int(gap), _p(frm), _p(cnt), _p(ws),
-                                        need if ws_bytes is None else ws_bytes, _lib.current_stream_ptr())
-    torch.cuda.synchronize()
-    return rc, int(cnt.item())
-
-
 # ---- 1. the three data sets, fresh and wrapped -------------------------------------------------------------------------
 @pytest.mark.parametrize("ring", [False, True], ids=["fresh", "ring"])
 @pytest.mark.parametrize("name", list(E.SETS))
@@ -136,7 +77,7 @@ def test_planted_scenes(name, ring):
     dtype, bits, sizes, link_all = E.dataset(name)
     n = bits.shape[0]
     cap = RING_CAP[name] if ring else None
-    mem = memory(bits, dtype, capacity=cap, ring=ring, grouped=True)
+    mem = raw_append_memory(bits, dtype, capacity=cap, ring=ring, grouped=True)
     lo = n - cap if ring else 0
     base, host = mem.rows_host()
     assert base == lo and np.array_equal(host, bits[lo:])
@@ -169,7 +110,7 @@ def test_planted_scenes(name, ring):
         k, o = live_columns(mem)
         assert np.array_equal(k, want_re.keys) and np.array_equal(o, want_re.ordinals), (name, ring, frm)
     # one hit per scene
-    q = _t(bits[[lo + 3, n // 2 + lo // 2, n - 1]], dtype)
+    q = from_bits(bits[[lo + 3, n // 2 + lo // 2, n - 1]], dtype)
     want_r, want_s, want_k = G.grouped_topk(bits[[lo + 3, n // 2 + lo // 2, n - 1]], bits[lo:], want_re.keys, 10,
                                             dtype=dtype, base=lo)
     s, r, kk = mem.topk_grouped(q, 10)
@@ -182,7 +123,7 @@ def test_planted_scenes(name, ring):
 @pytest.mark.parametrize("n", [0, 1, 2, 3, 63, 64, 65, 127, 128, 129, 255, 256, 257, 1023, 1024, 1025])
 def test_small_sizes(n):
     dtype, bits, _, link_all = E.dataset("f16_128")
-    mem = memory(bits[:n], dtype, capacity=max(n, 16), grouped=True)
+    mem = raw_append_memory(bits[:n], dtype, capacity=max(n, 16), grouped=True)
     if n == 0:          # an empty memory writes the count and nothing else
         rc, lk, ev, fr, cnt = raw_events(mem, 0.5, max_events=4)
         assert rc == 0 and cnt == 0
@@ -219,7 +160,7 @@ def test_threshold_at_a_link_and_special_rows():
     link = E.links(bits, dtype)
     assert link[z] == 0.0 and link[z + 1] == 0.0 and abs(link[d + 1] - 1.0) < 1e-9
     print(f"link of two identical rows: {link[d + 1]!r}")
-    mem = memory(bits, dtype)
+    mem = raw_append_memory(bits, dtype)
     r = inside[5] + 1
     tau = float(link[r])
     assert 0.9 < tau < 1.0
@@ -259,7 +200,7 @@ def test_tag_clauses():
     tags = (src << 40) | ms
     tags[d + 2:d + 6] = MIN                   # INT64_MIN mixed in: in, two score-rule rows, out
     tags[e + 1] = MIN                         # a single untimed row: in and out
-    mem = memory(bits, dtype, tags=tags, grouped=True)
+    mem = raw_append_memory(bits, dtype, tags=tags, grouped=True)
     for gap in (-1, 1000, 40, 39, 0):
         flags = E.opens(link, 0.5, tags, gap)
         assert flags[a + 3] and flags[d + 2] and not flags[d + 3] and flags[d + 6] and flags[e + 1] and flags[e + 2]
@@ -284,7 +225,7 @@ def test_tag_clauses():
     at = [x for x in evs if x.first_row == a + 3][0]
     assert at.source == 1 and at.t0_ms == (a + 3) * 40
     # a gap on an untagged memory
-    plain = memory(bits[:64], dtype, grouped=True)
+    plain = raw_append_memory(bits[:64], dtype, grouped=True)
     rc, lk, ev, fr, cnt = raw_events(plain, 0.5, gap=0, max_events=4)
     assert rc == _lib.VM_ERR_INVALID and cnt == SENT_I and (ev == SENT_I).all()
     assert raw_regroup(plain, 0.5, gap=1000)[0] == _lib.VM_ERR_INVALID
@@ -301,7 +242,7 @@ def test_regroup_linear_equals_a_fresh_keyed_append_and_the_group_state():
     bits, link = bits_ro[:n], link_all[:n]
     flags = E.opens(link, 0.5)
     want = E.regroup(flags)
-    mem = memory(bits, dtype, capacity=n + 8, grouped=True)
+    mem = raw_append_memory(bits, dtype, capacity=n + 8, grouped=True)
     k0, o0 = columns(mem, n)
     assert np.array_equal(k0, -1 - np.arange(n)) and np.array_equal(o0, np.arange(n))      # the plain append's columns
     assert raw_regroup(mem, 0.5) == (0, want.state[0])
@@ -310,27 +251,27 @@ def test_regroup_linear_equals_a_fresh_keyed_append_and_the_group_state():
     assert np.array_equal(mem.group_keys_host(), want.keys)
     assert not k[n:].any() and not o[n:].any()
     fresh = EmbeddingMemory(n + 8, bits.shape[1], dtype, grouped=True)
-    fresh.append(_t(bits, dtype), group=torch.from_numpy(want.keys))
+    fresh.append(from_bits(bits, dtype), group=torch.from_numpy(want.keys))
     fk, fo = columns(fresh)
     assert np.array_equal(fk, k) and np.array_equal(fo, o)
     qb = bits[[5, 700, 1499, 33]]
     want_r, want_s, want_k = G.grouped_topk(qb, bits, want.keys, 10, dtype=dtype)
     for m in (mem, fresh):
-        s, r, kk = m.topk_grouped(_t(qb, dtype), 10)
+        s, r, kk = m.topk_grouped(from_bits(qb, dtype), 10)
         assert np.array_equal(r.cpu().numpy(), want_r) and np.array_equal(kk.cpu().numpy(), want_k)
         assert same_bits(s.cpu().numpy(), want_s)
     scene_of = want.ordinals[want_r[want_r >= 0]]
     assert all(len(set(row)) == len(row) for row in scene_of.reshape(4, -1).tolist())      # one hit per scene
     # the last event is closed: a keyed append with its key still opens a new group ...
     last_key, last_ord = int(want.keys[-1]), int(want.ordinals[-1])
-    mem.append(_t(bits_ro[n:n + 1], dtype), group=last_key)
-    fresh.append(_t(bits_ro[n:n + 1], dtype), group=last_key)
+    mem.append(from_bits(bits_ro[n:n + 1], dtype), group=last_key)
+    fresh.append(from_bits(bits_ro[n:n + 1], dtype), group=last_key)
     k, o = columns(mem)
     assert (k[n], o[n]) == (last_key, last_ord + 1)
     assert columns(fresh)[1][n] == last_ord                       # where the group was open it was continued
     # ... and a plain append continues the ordinals without a hole
     first = C.c_int64(0)
-    mem.ctx.check(mem.L.vm_memory_append(mem.handle, _p(_t(bits_ro[n + 1:n + 3], dtype)), 2, C.byref(first),
+    mem.ctx.check(mem.L.vm_memory_append(mem.handle, ptr(from_bits(bits_ro[n + 1:n + 3], dtype)), 2, C.byref(first),
                                          _lib.current_stream_ptr()))
     torch.cuda.synchronize()
     k, o = columns(mem)
@@ -338,7 +279,7 @@ def test_regroup_linear_equals_a_fresh_keyed_append_and_the_group_state():
     assert k[n + 1:n + 3].tolist() == [-1 - (n + 1), -1 - (n + 2)]
     # the Python entry returns the count; a memory that is not grouped is refused
     assert mem.regroup_events(0.5) == int(E.opens(E.links(bits_ro[:n + 3], dtype), 0.5).sum())
-    plain = memory(bits[:64], dtype)
+    plain = raw_append_memory(bits[:64], dtype)
     before = raw_events(plain, 0.5, max_events=8)
     assert raw_regroup(plain, 0.5) == (_lib.VM_ERR_INVALID, SENT_I)
     with pytest.raises(ValueError, match="grouped"):
@@ -354,7 +295,7 @@ def test_regroup_after_erase():
     starts = np.concatenate([[0], np.cumsum(sizes)])
     mid = [i for i, (s, z) in enumerate(zip(starts, sizes)) if 200 < s and s + z < 400 and z >= 3][0]
     gone = list(range(int(starts[mid]), int(starts[mid] + sizes[mid])))            # a whole middle scene
-    mem = memory(bits_ro[:n], dtype, grouped=True)
+    mem = raw_append_memory(bits_ro[:n], dtype, grouped=True)
     assert mem.erase(rows=gone).count == len(gone)
     keep = np.ones(n, bool)
     keep[gone] = False
@@ -370,7 +311,7 @@ def test_regroup_after_erase():
     # erasing the rows BETWEEN two halves of one scene joins them
     big = [i for i, (s, z) in enumerate(zip(starts, sizes)) if z >= 9 and s + z < 200][0]
     cut = list(range(int(starts[big]) + 2, int(starts[big]) + 5))
-    mem2 = memory(bits_ro[:n], dtype, grouped=True)
+    mem2 = raw_append_memory(bits_ro[:n], dtype, grouped=True)
     mem2.erase(rows=cut)
     keep = np.ones(n, bool)
     keep[cut] = False
@@ -396,7 +337,7 @@ def test_tail_regroups_equal_one_whole_regroup(ring):
     frm_dev = torch.zeros(1, dtype=torch.int64, device="cuda")
     while at < n:
         end = min(n, at + int(rng.integers(1, 41)))
-        mem.append(_t(bits[at:end], dtype))                    # default group: one key per call - overwritten below
+        mem.append(from_bits(bits[at:end], dtype))                    # default group: one key per call - overwritten below
         if calls % 2:
             frm_dev.fill_(at)
             rc, cnt = raw_regroup(mem, 0.5, from_row=frm_dev)
@@ -415,10 +356,10 @@ def test_tail_regroups_equal_one_whole_regroup(ring):
         k2, o2 = columns(mem)
         assert np.array_equal(k2, k) and np.array_equal(o2, o)
     # the state: the last event is closed, so its own key opens a new group
-    mem.append(_t(bits_ro[n:n + 1], dtype), group=int(want.keys[-1]))
+    mem.append(from_bits(bits_ro[n:n + 1], dtype), group=int(want.keys[-1]))
     assert columns(mem)[1][n] == want.ordinals[-1] + 1
     # one whole regroup of another memory leaves the same columns; from_row <= lo is whole mode
-    other = memory(bits, dtype, capacity=n + 30, ring=ring, grouped=True)
+    other = raw_append_memory(bits, dtype, capacity=n + 30, ring=ring, grouped=True)
     for frm in (None, 0, -3):
         assert raw_regroup(other, 2.0) == (0, n)               # every row its own event in between
         assert raw_regroup(other, 0.5, from_row=frm) == (0, want.state[0])
@@ -439,8 +380,8 @@ def test_short_workspace_is_refused_and_the_workspace_size_does_not_matter():
     from vidmem import _lib
     dtype, bits_ro, _, link_all = E.dataset("bf16_1024")
     n = 777
-    mem = memory(bits_ro[:n], dtype, grouped=True)
-    need = ws_need(mem)
+    mem = raw_append_memory(bits_ro[:n], dtype, grouped=True)
+    need = events_ws_need(mem)
     rc, lk, ev, fr, cnt = raw_events(mem, 0.5, max_events=8, ws_bytes=need - 1)
     assert rc == _lib.VM_ERR_NOMEM and cnt == SENT_I
     assert (lk == SENT_LINK).all() and (ev == SENT_I).all() and (fr == SENT_I).all()
@@ -461,9 +402,9 @@ def test_graph_capture_append_and_events_replayed():
     dtype, bits_ro, _, link_all = E.dataset("f16_768")
     B, H = 128, 64
     mem = EmbeddingMemory(1024, 768, dtype)
-    mem.append(_t(bits_ro[:256], dtype))
+    mem.append(from_bits(bits_ro[:256], dtype))
     scratch = mem.prepare_events(H)
-    src = _t(bits_ro[256:256 + B], dtype).clone()
+    src = from_bits(bits_ro[256:256 + B], dtype).clone()
     torch.cuda.synchronize()
     s = torch.cuda.Stream()
     s.wait_stream(torch.cuda.current_stream())
@@ -477,7 +418,7 @@ def test_graph_capture_append_and_events_replayed():
     assert len(mem) == 256
     for rep in range(3):
         n = 256 + (rep + 1) * B
-        src.copy_(_t(bits_ro[n - B:n], dtype))
+        src.copy_(from_bits(bits_ro[n - B:n], dtype))
         graph.replay()
         torch.cuda.synchronize()
         assert mem.sync() == n

@@ -14,22 +14,12 @@ import torch
 from oracle import cref
 from tests import fold_ref as FR
 from tests import mask_ref as MR
+from tests.support import same_arrays, same_bits
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _case(D=128, dtype="f16", shape="n47"):
-    from tests.test_group_topk_gpu import _bits
-    rows, q, base, live = MR.host_dataset(D, dtype, shape)
-    return _bits(rows[base:]), _bits(q), base, live
-
-
-def _same(a, b):
-    return np.array_equal(a[0], b[0]) and np.array_equal(a[1].view(np.int64), b[1].view(np.int64))
-
-
-def _bits_equal(a, b):
-    return np.array_equal(np.asarray(a, dtype=np.float64).view(np.int64), np.asarray(b, dtype=np.float64).view(np.int64))
+_case = MR.host_case
 
 
 # ---- the oracle -----------------------------------------------------------------------------------------------------------
@@ -43,7 +33,7 @@ def test_loop_and_array_statements_agree_bit_for_bit(D, dtype):
                 for c in range(3):
                     e = live[FR.term_rows(c, J)]
                     (fa, ta), (fb, tb) = FR.fold_scores_loop(e, w, op), FR.fold_scores(e, w, op)
-                    assert _bits_equal(fa, fb) and np.array_equal(ta, tb), (op, J, wname, c)
+                    assert same_bits(fa, fb) and np.array_equal(ta, tb), (op, J, wname, c)
                     assert ta.dtype == np.int32 and ta.min() >= 0 and ta.max() < J
         terms = q[[FR.term_rows(c, 5) for c in range(3)]]
         ws = [FR.weights_of("signed", 5)] * 3
@@ -51,7 +41,7 @@ def test_loop_and_array_statements_agree_bit_for_bit(D, dtype):
         for k in (1, 5, 64):
             a = FR.fold_topk(terms, ws, rows, sel, k, op, dtype, base=base)
             b = FR.fold_topk(terms, ws, rows, sel, k, op, dtype, base=base, scores=FR.fold_scores)
-            assert _same(a, b) and np.array_equal(a[2], b[2])
+            assert same_arrays(a, b) and np.array_equal(a[2], b[2])
             assert ((a[2] == -1) == (a[0] == -1)).all()
 
 
@@ -63,19 +53,19 @@ def test_one_term_of_weight_one_is_the_row_oracle(D, dtype):
     for op in FR.OPS:
         for k in (1, 5, 20):
             r, s = cref.cosine_topk(q[:4], rows, k, dtype=dtype)
-            assert _same(FR.fold_topk(terms, ws, rows, None, k, op, dtype), (r, s))
+            assert same_arrays(FR.fold_topk(terms, ws, rows, None, k, op, dtype), (r, s))
             for cut in (0.2, -0.1):
                 r, s = cref.cosine_topk(q[:4], rows, k, dtype=dtype, min_score=cut)
-                assert _same(FR.fold_topk(terms, ws, rows, None, k, op, dtype, min_score=cut), (r, s))
+                assert same_arrays(FR.fold_topk(terms, ws, rows, None, k, op, dtype, min_score=cut), (r, s))
             masks, index = MR.mask_sets(4, "n47")["alternating"]
             sel = MR.selection(masks, index, 4, base, rows.shape[0], 47)
-            assert _same(FR.fold_topk(terms, ws, rows, sel, k, op, dtype, base=base),
+            assert same_arrays(FR.fold_topk(terms, ws, rows, sel, k, op, dtype, base=base),
                          MR.masked_topk(q[:4], rows, sel, k, dtype=dtype, base=base))
     # unit weights: F is the element-wise maximum (minimum) of the J exact score rows
     for J in (2, 5, 16):
         e = live[FR.term_rows(1, J)]
-        assert _bits_equal(FR.fold_scores_loop(e, [1.0] * J, "max")[0], e.max(axis=0))
-        assert _bits_equal(FR.fold_scores_loop(e, [1.0] * J, "min")[0], e.min(axis=0))
+        assert same_bits(FR.fold_scores_loop(e, [1.0] * J, "max")[0], e.max(axis=0))
+        assert same_bits(FR.fold_scores_loop(e, [1.0] * J, "min")[0], e.min(axis=0))
 
 
 def test_permutation_duplicate_and_batch_identities():
@@ -88,13 +78,13 @@ def test_permutation_duplicate_and_batch_identities():
                 F, T = FR.fold_scores_loop(e, w, op)
                 perm = rng.permutation(J)
                 Fp, Tp = FR.fold_scores_loop(e[perm], [w[i] for i in perm], op)
-                assert _bits_equal(F, Fp)                                       # no score bit changes, so no row does
+                assert same_bits(F, Fp)                                       # no score bit changes, so no row does
                 p = np.asarray(w)[:, None] * e
-                assert _bits_equal(p[perm][Tp, np.arange(e.shape[1])], F) and _bits_equal(p[T, np.arange(e.shape[1])], F)   # only T moves
+                assert same_bits(p[perm][Tp, np.arange(e.shape[1])], F) and same_bits(p[T, np.arange(e.shape[1])], F)   # only T moves
                 if J < 16:                                                      # a copy of a term with its weight: nothing
                     for d in range(J):
                         Fd, Td = FR.fold_scores_loop(np.concatenate([e, e[d:d + 1]]), w + [w[d]], op)
-                        assert _bits_equal(F, Fd) and np.array_equal(T, Td)
+                        assert same_bits(F, Fd) and np.array_equal(T, Td)
         # a query alone equals the same query inside a batch
         terms = q[[FR.term_rows(c, 5) for c in range(3)]]
         ws = [FR.weights_of(n, 5) for n in FR.WEIGHT_SETS]
@@ -102,7 +92,7 @@ def test_permutation_duplicate_and_batch_identities():
         r, s, t = FR.fold_topk(terms, ws, rows, sel, 5, op, "bf16")
         for c in range(3):
             r1, s1, t1 = FR.fold_topk(terms[c:c + 1], ws[c:c + 1], rows, sel[c:c + 1], 5, op, "bf16")
-            assert _same((r1, s1), (r[c:c + 1], s[c:c + 1])) and np.array_equal(t1, t[c:c + 1])
+            assert same_arrays((r1, s1), (r[c:c + 1], s[c:c + 1])) and np.array_equal(t1, t[c:c + 1])
 
 
 def test_signed_zeros_and_zero_weights():
@@ -112,7 +102,7 @@ def test_signed_zeros_and_zero_weights():
     n = e.shape[1]
     # a zero weight is not neutral: its product +-0.0 takes part
     F, T = FR.fold_scores_loop(e[:2], [1.0, 0.0], "max")
-    assert _bits_equal(np.abs(F), np.maximum(e[0], 0.0)) and (F >= 0).all() and ((T == 1) == (e[0] < 0)).all()
+    assert same_bits(np.abs(F), np.maximum(e[0], 0.0)) and (F >= 0).all() and ((T == 1) == (e[0] < 0)).all()
     F, T = FR.fold_scores_loop(e[:2], [1.0, 0.0], "min")
     assert (F <= 0).all() and ((T == 1) == (e[0] > 0)).all()
     # the one exception to "a permutation changes no score bit": products that tie as zeros of both signs give F the sign
@@ -133,7 +123,7 @@ def test_signed_zeros_and_zero_weights():
             assert (F == 0.0).all() and (T == 0).all()
             assert np.array_equal(np.signbit(F), np.signbit(np.float64(w[0]) * e[0]))
             Fb, Tb = FR.fold_scores(e, w, op)
-            assert _bits_equal(F, Fb) and np.array_equal(T, Tb)
+            assert same_bits(F, Fb) and np.array_equal(T, Tb)
         terms = q[[FR.term_rows(c, 3) for c in range(2)]]
         sel = np.zeros((2, n), dtype=bool)
         sel[:, 3::2] = True
@@ -275,7 +265,7 @@ def test_linked_similarities_on_an_exact_tie_orders_by_row_id_where_the_referenc
 # ---- the Python layer, before the library is called ------------------------------------------------------------------------
 def test_python_refusals_and_scratch():
     from tests.host_memory import host_memory
-    from tests.test_scratch_cpu import SizingLibrary
+    from tests.host_memory import SizingLibrary
     from vidmem import memory as M
     mem = host_memory(capacity=100)
     t = torch.zeros((2, 3, mem.dim))
@@ -391,7 +381,7 @@ def _changes(scorer, cases):
         keep = np.ones((1, e.shape[1]), dtype=bool) if sel is None else sel[None]
         a = MR.masked_topk_from_scores(F[None], keep, k)
         b = MR.masked_topk_from_scores(np.asarray(G, dtype=np.float64)[None], keep, k)
-        if not _same(a, b) or not np.array_equal(FR.terms_of_rows(T[None], a[0]), FR.terms_of_rows(np.asarray(U)[None], b[0])):
+        if not same_arrays(a, b) or not np.array_equal(FR.terms_of_rows(T[None], a[0]), FR.terms_of_rows(np.asarray(U)[None], b[0])):
             return True
     return False
 
@@ -458,7 +448,7 @@ def test_planted_defects_change_results_the_gpu_cases_compare():
     zeros = [(e, [0.0, 0.0, 0.0], op, None, 5) for op in FR.OPS]                               # "all zero"
     assert _changes(_not_strict, twice) and _changes(_not_strict, zeros)
     F, _ = _not_strict(e, [0.0, 0.0, 0.0], "max")
-    assert not _bits_equal(F, FR.fold_scores_loop(e, [0.0, 0.0, 0.0], "max")[0])                # the sign bit alone
+    assert not same_bits(F, FR.fold_scores_loop(e, [0.0, 0.0, 0.0], "max")[0])                # the sign bit alone
     # 4. T of the last instead of the first tied term (the scores are right)
     assert _changes(_last_tied_term, twice) and not _changes(_last_tied_term, scan)
     # 5. the minimum ranked ascending: the worst rows first
@@ -472,7 +462,7 @@ def test_planted_defects_change_results_the_gpu_cases_compare():
     F, T = FR.fold_scores_loop(live[FR.term_rows(1, 5)], FR.weights_of("signed", 5), "max")
     right = MR.masked_topk_from_scores(F[None], sels[1:2], 5)
     wrong = MR.masked_topk_from_scores(F[None], sels[0:1], 5)
-    assert not _same(right, wrong) and not set(right[0][0]) & set(wrong[0][0])
+    assert not same_arrays(right, wrong) and not set(right[0][0]) & set(wrong[0][0])
     # 8. A = the SUM of the |w_j| where the bound states their maximum: the certificate asks for sixteen times the gap
     # with sixteen unit weights, and a query the test demands flag 0 for (more than 4 eps_fold(max) between rank k and
     # rank M + 1) can no longer be certified once the gap is at most eps(sum) - eps(max): the scanned rank M + 1 may sit

@@ -2,7 +2,7 @@
 
 Bar: rows, fp64 score bits, the winning term T and padding identical to statement (A) of the oracle, for the fast and the
 ``exact=True`` entry and both ops.  The scan test runs the shapes at which the shared tile scan can go wrong
-(tests/test_tile_scan_gpu.py's data) for every (op, C, J, weight set, mask set, k) of tests/fold_ref.py and demands flag 0
+(tests/tile_scan_data.py) for every (op, C, J, weight set, mask set, k) of tests/fold_ref.py and demands flag 0
 wherever the oracle's scores allow it: the redo would hide a broken scan.  That they allow it is asserted from the
 oracle's scores before any search, and proven without a GPU in tests/test_fold_cpu.py.
 """
@@ -12,44 +12,12 @@ import torch
 
 from tests import fold_ref as FR
 from tests import mask_ref as MR
-from tests.test_group_topk_gpu import _bits, clustered, queries_near
-from tests.test_mask_gpu import dev_mask, plain_memory
-from tests.test_tile_scan_gpu import dataset
+from tests.search_checks import fold_check as check
+from tests.search_checks import fold_want as want_of
+from tests.support import bits, clustered, dev_mask, plain_memory, queries_near, redone, same_result, scan_memory
+from tests.tile_scan_data import dataset
 
 pytestmark = pytest.mark.gpu
-
-
-def want_of(mem, terms, weights, k, op, dtype, masks=None, index=None, **kw):
-    """Statement (A) for the memory as it is: terms [C,J,D] on the device, weights [C][J], masks / index host arrays."""
-    base, host_rows = mem.rows_host()
-    C = terms.shape[0]
-    sel = None if masks is None else MR.selection(masks, index, C, base, host_rows.shape[0], mem.capacity)
-    return FR.fold_topk(_bits(terms), weights, host_rows, sel, k, op, dtype=dtype, base=base, **kw)
-
-
-def per_query(weights, C):
-    return [list(weights)] * C if not isinstance(weights[0], (list, tuple)) else [list(w) for w in weights]
-
-
-def check(mem, terms, weights, k, op, dtype, masks=None, index=None, certified=None, label="", want=None, **kw):
-    """Fast and exact entry against (A) (``want``: (A) computed by the caller).  certified: None, or bool per query - the
-    fast path must have answered those queries itself (flag 0)."""
-    C = terms.shape[0]
-    want_r, want_s, want_t = want or want_of(mem, terms, per_query(weights, C), k, op, dtype, masks, index, **kw)
-    m = None if masks is None else (masks if isinstance(masks, torch.Tensor) else dev_mask(masks))
-    out = None
-    for exact in (False, True):
-        s, r, t = mem.topk_fold(terms, k, op=op, weights=weights, mask=m, mask_index=index, exact=exact, **kw)
-        got_r, got_s, got_t = r.cpu().numpy(), s.cpu().numpy(), t.cpu().numpy()
-        if not exact:
-            flags = mem.last_fold_flags[:C].cpu().numpy()
-            out = (got_r, got_s, flags)
-        assert np.array_equal(got_r, want_r), (label, op, exact, np.argwhere(got_r != want_r)[:5], got_r[:2], want_r[:2])
-        assert np.array_equal(got_s.view(np.int64), want_s.view(np.int64)), f"{label} {op}: scores differ (bit-exact) exact={exact}"
-        assert got_t.dtype == np.int32 and np.array_equal(got_t, want_t), (label, op, exact, got_t[:2], want_t[:2])
-        if certified is not None and not exact:
-            assert (flags[np.asarray(certified)] == 0).all(), f"{label} {op}: the scan left queries to the redo: {flags}"
-    return out
 
 
 # ---- 1. the scan ------------------------------------------------------------------------------------------------------
@@ -57,12 +25,7 @@ def check(mem, terms, weights, k, op, dtype, masks=None, index=None, certified=N
 @pytest.mark.parametrize("shape", list(MR.SHAPES))
 @pytest.mark.parametrize("D,dtype", FR.DTS)
 def test_scan(D, dtype, shape, op):
-    rows, q_all, base, live = dataset(D, dtype, shape)
-    hrows, hq, hbase, hlive = MR.host_dataset(D, dtype, shape)
-    assert hbase == base and np.array_equal(_bits(rows), _bits(hrows)) and np.array_equal(_bits(q_all), _bits(hq))
-    total, cap = MR.SHAPES[shape]
-    mem = plain_memory(rows, dtype, capacity=cap, ring=cap is not None, step=19)
-    assert mem.rows_host()[0] == base
+    mem, q_all, base, live, total, cap = scan_memory(D, dtype, shape)
     n = live.shape[1]
     demanded = cases = 0
     for C in FR.CS:
@@ -96,10 +59,6 @@ def test_scan(D, dtype, shape, op):
 
 
 # ---- 2. identities on the device --------------------------------------------------------------------------------------
-def _same(a, b):
-    return torch.equal(a[1], b[1]) and np.array_equal(a[0].cpu().numpy().view(np.int64), b[0].cpu().numpy().view(np.int64))
-
-
 @pytest.mark.parametrize("dtype", ["f16", "bf16"])
 def test_identities(dtype):
     rows, _ = clustered([5] * 200, 384, dtype, seed=21)
@@ -111,10 +70,10 @@ def test_identities(dtype):
             # J = 1, w = 1: the reference cosine bit for bit
             for exact in (False, True):
                 got = mem.topk_fold(q[:, None, :], k, op=op, exact=exact)
-                assert _same(got, mem.topk(q, k)), (op, k, exact)
+                assert same_result(got, mem.topk(q, k)), (op, k, exact)
                 assert (got[2][got[1] >= 0] == 0).all()
                 got = mem.topk_fold(q[:, None, :], k, op=op, mask=mask, exact=exact)
-                assert _same(got, mem.topk_masked(q, k, mask)), (op, k, exact)
+                assert same_result(got, mem.topk_masked(q, k, mask)), (op, k, exact)
             t = q[:15].reshape(3, 5, -1).contiguous()
             w = [1.0, 0.5, -0.5, 2.0, 1.0]
             perm = [3, 0, 4, 2, 1]
@@ -122,12 +81,12 @@ def test_identities(dtype):
                 a = mem.topk_fold(t, k, op=op, weights=w, mask=mask, exact=exact)
                 # permuting the terms with their weights changes no score bit and no row, only T
                 b = mem.topk_fold(t[:, perm].contiguous(), k, op=op, weights=[w[i] for i in perm], mask=mask, exact=exact)
-                assert _same(a, b), (op, k, exact)
+                assert same_result(a, b), (op, k, exact)
                 assert (a[1] >= 0).all() and torch.equal(torch.tensor(perm, device="cuda")[b[2].long()].int(), a[2])
                 # appending a copy of a term with its weight changes nothing at all
                 d = mem.topk_fold(torch.cat([t, t[:, 1:2]], dim=1).contiguous(), k, op=op, weights=w + [w[1]], mask=mask,
                                   exact=exact)
-                assert _same(a, d) and torch.equal(a[2], d[2]), (op, k, exact)
+                assert same_result(a, d) and torch.equal(a[2], d[2]), (op, k, exact)
         # a query's result is the same alone and inside a batch of 3
         terms = q[:15].reshape(3, 5, -1).contiguous()
         ws = [FR.weights_of(nm, 5) for nm in FR.WEIGHT_SETS]
@@ -136,7 +95,7 @@ def test_identities(dtype):
             s3, r3, t3 = mem.topk_fold(terms, 10, op=op, weights=ws, mask=masks, exact=exact)
             for c in range(3):
                 s1, r1, t1 = mem.topk_fold(terms[c], 10, op=op, weights=[ws[c]], mask=masks[c], exact=exact)
-                assert _same((s1, r1), (s3[c:c + 1], r3[c:c + 1])) and torch.equal(t1, t3[c:c + 1]), (op, c, exact)
+                assert same_result((s1, r1), (s3[c:c + 1], r3[c:c + 1])) and torch.equal(t1, t3[c:c + 1]), (op, c, exact)
         check(mem, terms, ws, 10, op, dtype, masks.cpu().numpy().view(np.uint32), label="batch of 3")
     # max with unit weights against the J plain searches: the best fold score is the best of the J best cosines
     s, r, t = mem.topk_any(q[:5][None].contiguous(), 1)
@@ -147,15 +106,8 @@ def test_identities(dtype):
 
 # ---- 3. what must go to the redo and still be exact -------------------------------------------------------------------
 def _redone(mem, terms, weights, k, op, dtype, label, flag=None, **kw):
-    from vidmem import _lib
-    before = mem.fold_uncertified_count
-    got_r, got_s, flags = check(mem, terms, weights, k, op, dtype, label=label, **kw)
-    assert (flags != 0).all(), (label, flags)
-    if flag is not None:
-        assert (flags == flag).all(), (label, flags)
-    assert flags[0] in (_lib.VM_FLAG_GAP, _lib.VM_FLAG_OVERFLOW)
-    assert mem.fold_uncertified_count == before + terms.shape[0], label
-    return got_r, got_s
+    return redone(lambda: check(mem, terms, weights, k, op, dtype, label=label, **kw), lambda: mem.fold_uncertified_count,
+                  terms.shape[0], label, flag)
 
 
 @pytest.mark.parametrize("op", FR.OPS)
@@ -176,7 +128,7 @@ def test_redo_cases(op):
     # (rank 5 and rank 14 lie more than 4 eps_fold apart) - so the flag is 0 and the counter stands still
     from oracle import cref
     twice = torch.stack([q[:2], q[:2]], dim=1).contiguous()
-    F = cref.cosine_matrix(_bits(q[:2]), mem.rows_host()[1], dtype="f16")
+    F = cref.cosine_matrix(bits(q[:2]), mem.rows_host()[1], dtype="f16")
     ok = [FR.flag0_ok(np.sort(F[c])[::-1], 5, 128, 1.0) for c in range(2)]
     assert all(ok), "precondition: identical terms"
     before = mem.fold_uncertified_count
@@ -210,10 +162,10 @@ def test_certificate_uses_the_largest_weight():
     """Sixteen copies of one term with unit weights: A = max |w_j| = 1, their sum is 16.  Rank 1 and rank M + 1 are more
     than 4 eps_fold(D, 1) apart, so the query must be certified; with the sum as A the certificate would ask for a gap
     of eps_fold(D, 16) and leave it to the redo (tests/test_fold_cpu.py, defect 8)."""
-    bits, term, gap = FR.certificate_gap_case()
-    D = bits.shape[1]
+    row_bits, term, gap = FR.certificate_gap_case()
+    D = row_bits.shape[1]
     assert 4 * FR.eps_fold(D, 1.0) < gap <= FR.eps_fold(D, 16.0) - FR.eps_fold(D, 1.0)
-    rows = torch.from_numpy(bits.view(np.int16)).view(torch.float16).cuda()
+    rows = torch.from_numpy(row_bits.view(np.int16)).view(torch.float16).cuda()
     mem = plain_memory(rows, "f16")
     terms = rows[0].expand(1, 16, -1).contiguous()
     for op in FR.OPS:
@@ -273,7 +225,7 @@ def test_arguments():
         assert (got_r[1:] == -1).all() and (got_r[0] >= 0).all()
         plain = check(mem, terms, ws, 7, op, "bf16", label="stride 1")
         base, host_rows = mem.rows_host()
-        wr, wscore, wt = FR.fold_topk(_bits(terms), ws, host_rows, None, 7, op, dtype="bf16")
+        wr, wscore, wt = FR.fold_topk(bits(terms), ws, host_rows, None, 7, op, dtype="bf16")
         for exact in (False, True):
             s, r, t = mem.topk_fold(terms, 7, op=op, weights=ws, stride=(3, 1), exact=exact)
             assert np.array_equal(r.cpu().numpy(), wr * 3 + 1) and np.array_equal(t.cpu().numpy(), wt)
@@ -389,7 +341,7 @@ def test_linked_similarities_against_the_reference_merge():
     mem.ids = [f"chunk-{i}" for i in range(len(mem))]
     ids = list(mem.ids)
     q = queries_near(rows, 40, 8, "f16")
-    cos = cref.cosine_matrix(_bits(q), _bits(rows), dtype="f16")
+    cos = cref.cosine_matrix(bits(q), bits(rows), dtype="f16")
     mask = dev_mask(MR.pack_rows(range(0, 120, 2), mem.capacity)[None])
     sel = MR.selected(MR.pack_rows(range(0, 120, 2), mem.capacity), 0, 120, mem.capacity)
     for Q, k_each, k_final in ((1, 5, 5), (3, 10, 4), (7, 10, 10), (16, 10, 10), (17, 8, 8), (40, 10, 3)):
@@ -414,7 +366,7 @@ def test_linked_similarities_against_the_reference_merge():
     # fold_similarities: the list shape of the fold itself
     t = q[:6].reshape(2, 3, -1).contiguous()
     for op in FR.OPS:
-        wr, wscore, _ = FR.fold_topk(_bits(t), [[1.0, 0.5, 2.0]] * 2, _bits(rows), None, 4, op)
+        wr, wscore, _ = FR.fold_topk(bits(t), [[1.0, 0.5, 2.0]] * 2, bits(rows), None, 4, op)
         got = fold_similarities(mem, t, 4, op=op, weights=[1.0, 0.5, 2.0])
         assert got == [[(ids[r], float(s)) for r, s in zip(rr, ss)] for rr, ss in zip(wr, wscore)]
     mem.close()

@@ -9,23 +9,14 @@ import pytest
 import torch
 
 from tests import group_ref as G
+from tests.search_checks import e2e_extractor
+from tests.support import Embedder, bits
 
 pytestmark = pytest.mark.gpu
 
 
-def _bits(t):
-    return t.contiguous().view(torch.int16).cpu().numpy().view(np.uint16)
-
-
 def _run(tmp_path, clip, enc, group_by, look_ahead, tag):
-    from vidmem import config as C
-    from vidmem.extractor import FrameEmbeddingExtractor
-    cfg = C.from_dict({
-        "video": {"chunk_size_seconds": 1.0, "frames_per_chunk": 5},
-        "encoder": {"arch": "vit_b16_2l", "dtype": "f16", "seed": 3, "top_k": 4, "look_ahead_chunks": look_ahead},
-        "memory": {"capacity": 512, "group_by": group_by},
-    })
-    ex = FrameEmbeddingExtractor(cfg, encoder=enc)
+    ex = e2e_extractor(enc, {"group_by": group_by}, look_ahead)
     out = json.load(open(asyncio.run(ex.process_video(str(clip), str(tmp_path / f"out_{tag}.json")))))
     rid = out["metadata"]["run_id"]
     res = [{**r, "processing_time": None, "group_time": None, "group_chunks": None,
@@ -34,14 +25,6 @@ def _run(tmp_path, clip, enc, group_by, look_ahead, tag):
     out["metadata"].pop("run_id")
     out["metadata"]["config"]["memory"].pop("group_by")
     return ex, res, out["metadata"], rid
-
-
-class _Embedder:
-    def __init__(self, vec):
-        self.vec = vec
-
-    async def aembed_query(self, text):
-        return self.vec
 
 
 @pytest.mark.parametrize("look_ahead", [1, 4])
@@ -69,10 +52,10 @@ def test_group_by_chunk_changes_no_output_and_search_is_distinct(tmp_path, monke
     noise = torch.randn(stored.shape[1], device="cuda", generator=torch.Generator("cuda").manual_seed(1))
     q = stored[7].float() + 0.02 * noise
     q16 = q.to(torch.float16)
-    vs = HipVectorSearch(mem, _Embedder(q16.double().cpu().tolist()), SimpleNamespace(top_k_chunks=3),
+    vs = HipVectorSearch(mem, Embedder(q16.double().cpu().tolist()), SimpleNamespace(top_k_chunks=3),
                          min_score=-1.0, score_mode=_lib.VM_SCORE_RAW, distinct=True)
     got = asyncio.run(vs._vector_search_chunks(None, "q"))
-    want_r, want_s, _ = G.grouped_topk(_bits(q16[None]), _bits(stored), keys, 3, min_score=-1.0)
+    want_r, want_s, _ = G.grouped_topk(bits(q16[None]), bits(stored), keys, 3, min_score=-1.0)
     assert [c["id"] for c in got] == [mem.id_of(int(r)) for r in want_r[0]]
     assert [c["score"] for c in got] == want_s[0].tolist()
     got_batches = [int(c["id"].split("_")[-2]) for c in got]

@@ -13,22 +13,12 @@ from oracle import cref
 from tests import group_ref as G
 from tests import group_scope_ref as GS
 from tests.novelty_feed import threshold_between
-from tests.test_events_e2e_gpu import _Embedder, _bits, scene_clip
+from tests.search_checks import e2e_extractor, scene_clip
+from tests.support import Embedder, bits
 
 pytestmark = pytest.mark.gpu
 
 LENGTHS = [[7, 3, 12, 1, 9, 8], [6, 2, 11, 4, 5, 2]]     # frames per scene of the two clips: 40 and 30 frames
-
-
-def _extractor(enc, memory_cfg):
-    from vidmem import config as C
-    from vidmem.extractor import FrameEmbeddingExtractor
-    cfg = C.from_dict({
-        "video": {"chunk_size_seconds": 1.0, "frames_per_chunk": 5},
-        "encoder": {"arch": "vit_b16_2l", "dtype": "f16", "seed": 3, "top_k": 4, "look_ahead_chunks": 4},
-        "memory": {"capacity": 512, **memory_cfg},
-    })
-    return FrameEmbeddingExtractor(cfg, encoder=enc)
 
 
 def _process(ex, clip, path):
@@ -48,13 +38,13 @@ def test_one_frame_per_scene_of_one_video(tmp_path, monkeypatch):
         np.savez(clips[i], frames=frames, fps=np.float64(5.0))      # 5 frames per one-second chunk: every frame is picked
         owner.append(own + (owner[-1][-1] + 1 if owner else 0))
     owner = np.concatenate(owner)
-    ex0 = _extractor(None, {})
+    ex0 = e2e_extractor(None, {})
     for i, clip in enumerate(clips):
         _process(ex0, clip, tmp_path / f"plain{i}.json")
     stored = ex0.memory.rows_host()[1]
     assert stored.shape[0] == owner.size == 70
     tau = threshold_between(cref.cosine_matrix(stored, stored), owner)          # from the reference's own scores
-    ex = _extractor(ex0.encoder, {"tag_by": "time", "group_by": "event", "event_threshold": tau})
+    ex = e2e_extractor(ex0.encoder, {"tag_by": "time", "group_by": "event", "event_threshold": tau})
     rids = [_process(ex, clip, tmp_path / f"event{i}.json") for i, clip in enumerate(clips)]
     mem = ex.memory
     assert mem.tagged and mem.grouped and np.array_equal(mem.rows_host()[1], stored)
@@ -66,24 +56,24 @@ def test_one_frame_per_scene_of_one_video(tmp_path, monkeypatch):
     rows = mem.rows_tensor()
     noise = torch.randn(rows.shape[1], device="cuda", generator=torch.Generator("cuda").manual_seed(1))
     q16 = (rows[15].float() + 0.02 * noise).to(torch.float16)
-    emb = _Embedder(q16.double().cpu().tolist())
+    emb = Embedder(q16.double().cpu().tolist())
     cfg = SimpleNamespace(top_k_chunks=4)
     vs = HipVectorSearch(mem, emb, cfg, min_score=-1.0, score_mode=_lib.VM_SCORE_RAW, distinct=True, scope=scope_of(1))
     hits = asyncio.run(vs._vector_search_chunks(None, "q"))
-    want_r, want_s, _ = GS.group_scoped_topk(_bits(q16[None]), stored, keys, tags, scope_of(1), 4, min_score=-1.0)
+    want_r, want_s, _ = GS.group_scoped_topk(bits(q16[None]), stored, keys, tags, scope_of(1), 4, min_score=-1.0)
     assert [c["id"] for c in hits] == [mem.id_of(int(r)) for r in want_r[0]]
     assert [c["score"] for c in hits] == want_s[0].tolist()
     assert len(hits) == 4 and all(c["id"].startswith(rids[1]) for c in hits)
     assert len({int(owner[int(r)]) for r in want_r[0]}) == 4                    # one frame per scene
     whole = HipVectorSearch(mem, emb, cfg, min_score=-1.0, score_mode=_lib.VM_SCORE_RAW, distinct=True)
-    best = G.grouped_topk(_bits(q16[None]), stored, keys, 1)[0][0, 0]           # without a scope clip 0's scene 2 wins
+    best = G.grouped_topk(bits(q16[None]), stored, keys, 1)[0][0, 0]           # without a scope clip 0's scene 2 wins
     assert asyncio.run(whole._vector_search_chunks(None, "q"))[0]["id"] == mem.id_of(int(best)) and owner[best] == 2
 
     # a window of clip 0 that cuts scene 2 (rows 10 .. 21) in two: seconds 3 to 5 are rows 15 .. 29
     win = scope_of(0, 3000, 5000)
     vs = HipVectorSearch(mem, emb, cfg, min_score=-1.0, score_mode=_lib.VM_SCORE_RAW, distinct=True, scope=win)
     hits = asyncio.run(vs._vector_search_chunks(None, "q"))
-    want_r, want_s, _ = GS.group_scoped_topk(_bits(q16[None]), stored, keys, tags, win, 4, min_score=-1.0)
+    want_r, want_s, _ = GS.group_scoped_topk(bits(q16[None]), stored, keys, tags, win, 4, min_score=-1.0)
     assert want_r[0, 3] == -1                      # three scenes have a frame in the window: the fourth hit is padding
     assert [c["id"] for c in hits] == [mem.id_of(int(r)) for r in want_r[0, :3]]
     assert [c["score"] for c in hits] == want_s[0, :3].tolist()
@@ -91,7 +81,7 @@ def test_one_frame_per_scene_of_one_video(tmp_path, monkeypatch):
 
     # the pre-LLM similarity, the same way; a wrong-length query lists the first in-scope row of the first in-scope scenes
     sims = batch_similarities(mem, [q16, [0.0] * 5, rows[50]], 3, distinct=True, scope=scope_of(1))
-    want_r, want_s, _ = GS.group_scoped_topk(_bits(torch.stack([q16, rows[50]])), stored, keys, tags, scope_of(1), 3)
+    want_r, want_s, _ = GS.group_scoped_topk(bits(torch.stack([q16, rows[50]])), stored, keys, tags, scope_of(1), 3)
     assert [i for i, _ in sims[0]] == [mem.id_of(int(r)) for r in want_r[0]]
     assert [s for _, s in sims[0]] == want_s[0].tolist()
     assert [i for i, _ in sims[2]] == [mem.id_of(int(r)) for r in want_r[1]] and sims[2][0][0] == mem.id_of(50)

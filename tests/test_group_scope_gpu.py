@@ -22,9 +22,8 @@ from tests import group_ref as G
 from tests import group_scope_ref as GS
 from tests import range_ref as R
 from tests import scope_ref as S
-from tests.test_group_topk_gpu import TD, _bits, clustered, queries_near
-from tests.test_scope_topk_gpu import ALL, MS, contiguous_tags, make_tag, mixed_scopes, scope_of
-from tests.test_tile_scan_gpu import CLUSTERS, K, M1, QS, SHAPES, gap_ok, scope_sets, tags_of
+from tests.support import ALL, MS, bits, clustered, contiguous_tags, make_tag, mixed_scopes, queries_near, scope_of
+from tests.tile_scan_data import CLUSTERS, K, QS, SHAPES, gap_ok, scope_sets, tags_of
 
 pytestmark = pytest.mark.gpu
 
@@ -68,7 +67,7 @@ def compare(mem, q, k, scopes, want, min_score=None, score_mode=0, certified=Fal
 def check(mem, q, k, dtype, scopes, **kw):
     """`compare` with the reference computed from what the memory holds."""
     base, host_rows = mem.rows_host()
-    want = GS.group_scoped_topk(_bits(q), host_rows, mem.group_keys_host(), mem.tags_host(), scopes, k, dtype=dtype,
+    want = GS.group_scoped_topk(bits(q), host_rows, mem.group_keys_host(), mem.tags_host(), scopes, k, dtype=dtype,
                                 score_mode=kw.get("score_mode", 0), min_score=kw.get("min_score"), base=base)
     return compare(mem, q, k, scopes, want, **kw)
 
@@ -86,7 +85,7 @@ def dataset(D, dtype, shape):
     rows, _ = clustered(sizes, D, dtype, seed=seed, device="cpu")
     base = total - cap if cap else 0
     q = queries_near(rows[base:].contiguous(), max(QS), seed + 1, dtype)
-    live = R.cref.cosine_matrix(_bits(q), _bits(rows[base:]), dtype=dtype)
+    live = R.cref.cosine_matrix(bits(q), bits(rows[base:]), dtype=dtype)
     return rows, q, base, sizes, live
 
 
@@ -378,7 +377,7 @@ def test_graph_capture_append_and_search_replayed_with_new_windows():
         torch.cuda.synchronize()
         assert mem.sync() == first + B
         base, host_rows = mem.rows_host()
-        want = GS.group_scoped_topk(_bits(q), host_rows, mem.group_keys_host(), mem.tags_host(), windows, k, base=base)
+        want = GS.group_scoped_topk(bits(q), host_rows, mem.group_keys_host(), mem.tags_host(), windows, k, base=base)
         assert np.array_equal(out_r.cpu().numpy(), want[0]) and np.array_equal(out_k.cpu().numpy(), want[2])
         assert np.array_equal(out_s.cpu().numpy().view(np.int64), want[1].view(np.int64))
         assert (out_r[0] >= first).all() and (out_r[3] == -1).all()

@@ -8,95 +8,39 @@ import pytest
 import torch
 
 from tests import group_ref as G
+from tests.search_checks import grouped_check
+from tests.support import clustered, group_sizes, grouped_memory, queries_near
 
 pytestmark = pytest.mark.gpu
-
-TD = {"f16": torch.float16, "bf16": torch.bfloat16}
-
-
-def _bits(t: torch.Tensor) -> np.ndarray:
-    return t.contiguous().view(torch.int16).cpu().numpy().view(np.uint16)
-
-
-def _sizes(n_groups, size, seed):
-    if size == "ragged":
-        rng = np.random.default_rng(seed)
-        return [int(x) for x in rng.integers(1, 24, n_groups)]
-    return [size] * n_groups
-
-
-def clustered(sizes, D, dtype, seed, noise=0.05, device="cuda"):
-    """Rows of len(sizes) groups; group g = a random centre + small per-row noise (one scene, consecutive frames)."""
-    g = torch.Generator(device=device).manual_seed(seed)
-    n = int(sum(sizes))
-    centres = torch.randn(len(sizes), D, generator=g, device=device)
-    gid = torch.repeat_interleave(torch.arange(len(sizes), device=device), torch.tensor(sizes, device=device))
-    rows = centres[gid] + noise * torch.randn(n, D, generator=g, device=device)
-    rows = rows / rows.norm(dim=1, keepdim=True)
-    return rows.to(TD[dtype]), gid
-
-
-def grouped_memory(rows, sizes, dtype, capacity=None, ring=False, keys=None):
-    from vidmem.memory import EmbeddingMemory
-    mem = EmbeddingMemory(capacity or max(rows.shape[0], 16), rows.shape[1], dtype, ring=ring, grouped=True)
-    off = 0
-    for i, s in enumerate(sizes):
-        mem.append(rows[off:off + s], group=None if keys is None else keys[i])
-        off += s
-    return mem
-
-
-def queries_near(rows, Q, seed, dtype):
-    g = torch.Generator(device=rows.device).manual_seed(seed)
-    pick = torch.randint(0, rows.shape[0], (Q,), generator=g, device=rows.device)
-    q = rows[pick].float() + 0.1 * torch.randn(Q, rows.shape[1], generator=g, device=rows.device)
-    return q.to(TD[dtype])
-
-
-def check(mem, q, k, dtype, min_score=None, score_mode=0, exact=False, certified=False):
-    """certified=True: also require that the fast path answered every query (no flag, no exhaustive redo)."""
-    s, r, kk = mem.topk_grouped(q, k, min_score=min_score, score_mode=score_mode, exact=exact)
-    if certified:
-        flags = mem.last_group_flags[:q.shape[0]].cpu().numpy()
-        assert (flags == 0).all(), f"fast path flagged {int((flags != 0).sum())} of {q.shape[0]} queries: {flags[:8]}"
-    base, host_rows = mem.rows_host()
-    keys = mem.group_keys_host()
-    want_r, want_s, want_k = G.grouped_topk(_bits(q), host_rows, keys, k, dtype=dtype, score_mode=score_mode,
-                                            min_score=min_score, base=base)
-    got_r, got_s, got_k = r.cpu().numpy(), s.cpu().numpy(), kk.cpu().numpy()
-    assert np.array_equal(got_r, want_r), (np.argwhere(got_r != want_r)[:5], got_r[:2], want_r[:2])
-    assert np.array_equal(got_k, want_k)
-    assert np.array_equal(got_s.view(np.int64), want_s.view(np.int64)), "scores differ (bit-exact bar)"
-    return got_r, got_s, got_k
 
 
 @pytest.mark.parametrize("dtype", ["f16", "bf16"])
 @pytest.mark.parametrize("D", [768, 1024])
 @pytest.mark.parametrize("size", [1, 5, 16, "ragged"])
 def test_group_sizes(dtype, D, size):
-    sizes = _sizes(600 if size != 1 else 4000, size, seed=D)
+    sizes = group_sizes(600 if size != 1 else 4000, size, seed=D)
     rows, _ = clustered(sizes, D, dtype, seed=7 + D)
     mem = grouped_memory(rows, sizes, dtype)
-    check(mem, queries_near(rows, 16, 3, dtype), 10, dtype, certified=True)
+    grouped_check(mem, queries_near(rows, 16, 3, dtype), 10, dtype, certified=True)
 
 
 @pytest.mark.parametrize("k", [1, 10, 64])
 @pytest.mark.parametrize("Q", [1, 16, 64, 300])
 def test_k_and_q(k, Q):
-    sizes = _sizes(800, 5, 0)
+    sizes = group_sizes(800, 5, 0)
     rows, _ = clustered(sizes, 768, "f16", seed=11)
     mem = grouped_memory(rows, sizes, "f16")
-    check(mem, queries_near(rows, Q, Q + k, "f16"), k, "f16", certified=True)
+    grouped_check(mem, queries_near(rows, Q, Q + k, "f16"), k, "f16", certified=True)
 
 
 @pytest.mark.parametrize("score_mode", [0, 1])
 def test_min_score(score_mode):
-    sizes = _sizes(500, "ragged", 4)
+    sizes = group_sizes(500, "ragged", 4)
     rows, _ = clustered(sizes, 768, "bf16", seed=12)
     mem = grouped_memory(rows, sizes, "bf16")
     q = queries_near(rows, 16, 5, "bf16")
     cut = 0.3 if score_mode == 0 else 0.65
-    _, s, _ = check(mem, q, 64, "bf16", min_score=cut, score_mode=score_mode, certified=True)
+    _, s, _ = grouped_check(mem, q, 64, "bf16", min_score=cut, score_mode=score_mode, certified=True)
     assert (s == 0.0).any() and (s > cut).any()  # the filter cut some lists short
 
 
@@ -110,7 +54,7 @@ def test_ties_lower_representative_wins():
     sizes = [5] * 8
     mem = grouped_memory(rows, sizes, "f16")
     q = rows[1:2].clone()
-    r, s, k = check(mem, q, 5, "f16")
+    r, s, k = grouped_check(mem, q, 5, "f16")
     assert r[0, :3].tolist() == [1, 12, 27] and s[0, 0] == s[0, 1] == s[0, 2]
     assert k[0, :3].tolist() == [0, 2, 5]
 
@@ -118,7 +62,7 @@ def test_ties_lower_representative_wins():
 def test_reappearing_key_is_a_new_group():
     rows, _ = clustered([4, 4, 4], 768, "f16", seed=3)
     mem = grouped_memory(rows, [4, 4, 4], "f16", keys=[7, 8, 7])
-    r, _, k = check(mem, rows[:1].clone(), 3, "f16")
+    r, _, k = grouped_check(mem, rows[:1].clone(), 3, "f16")
     assert k[0].tolist().count(7) == 2  # key 7 is two groups
 
 
@@ -129,25 +73,25 @@ def test_ring_wrap_and_overwritten_group():
     keys = mem.group_keys_host()
     assert len(keys) == 500 and keys[0] == keys[5] != keys[6]  # rows 15-20: the surviving part of the group of 14-20
     # rows 497-503 (group 71) straddle the physical wrap: slots 497-499 and 0-3
-    check(mem, torch.stack([rows[499], rows[500], rows[15]]).contiguous(), 5, "f16")
-    check(mem, queries_near(rows[15:].contiguous(), 16, 2, "f16"), 10, "f16", certified=True)
+    grouped_check(mem, torch.stack([rows[499], rows[500], rows[15]]).contiguous(), 5, "f16")
+    grouped_check(mem, queries_near(rows[15:].contiguous(), 16, 2, "f16"), 10, "f16", certified=True)
 
 
 def test_one_group_of_10k_rows():
     sizes = [300, 10000, 300] + [7] * 200
     rows, _ = clustered(sizes, 768, "f16", seed=5, noise=0.02)
     mem = grouped_memory(rows, sizes, "f16")
-    check(mem, queries_near(rows, 16, 1, "f16"), 10, "f16")
-    check(mem, rows[500:501].clone(), 3, "f16")
+    grouped_check(mem, queries_near(rows, 16, 1, "f16"), 10, "f16")
+    grouped_check(mem, rows[500:501].clone(), 3, "f16")
 
 
 def test_exact_variant_and_fast_path_agree():
-    sizes = _sizes(400, 16, 0)
+    sizes = group_sizes(400, 16, 0)
     rows, _ = clustered(sizes, 1024, "bf16", seed=2)
     mem = grouped_memory(rows, sizes, "bf16")
     q = queries_near(rows, 16, 8, "bf16")
-    a = check(mem, q, 20, "bf16", certified=True)
-    b = check(mem, q, 20, "bf16", exact=True)
+    a = grouped_check(mem, q, 20, "bf16", certified=True)
+    b = grouped_check(mem, q, 20, "bf16", exact=True)
     assert all(np.array_equal(x, y) for x, y in zip(a, b))
 
 
@@ -200,7 +144,7 @@ def test_one_million_clustered_rows_redo_path():
         rows[g * 625 * 16 + 3] = planted
     mem = grouped_memory_bulk(rows, 16)
     q = torch.stack([planted, rows[777], rows[500000], rows[999999]]).contiguous()
-    check(mem, q, 10, "f16")
+    grouped_check(mem, q, 10, "f16")
     flags = mem.last_group_flags[:4].cpu().numpy()
     assert flags[0] != 0 and (flags != 0).sum() >= 1
     assert mem.grouped_uncertified_count > 0
@@ -252,7 +196,7 @@ def test_graph_capture_replays_eager_result():
 
 def test_snapshot_restore_keeps_groups(tmp_path):
     from vidmem.memory import EmbeddingMemory
-    sizes = _sizes(100, "ragged", 6)
+    sizes = group_sizes(100, "ragged", 6)
     rows, _ = clustered(sizes, 768, "f16", seed=8)
     mem = grouped_memory(rows, sizes, "f16")
     q = queries_near(rows, 8, 3, "f16")
@@ -286,7 +230,7 @@ def test_select_overflow_path_on_a_million_tied_groups():
     mem = grouped_memory_bulk(rows, 1)
     q = torch.zeros((2, 768), dtype=torch.float16, device="cuda")
     q[1] = rows[4242]
-    r, s, _ = check(mem, q, 20, "f16")
+    r, s, _ = grouped_check(mem, q, 20, "f16")
     assert r[0].tolist() == list(range(20)) and (s[0] == 0.0).all()
     assert r[1, 0] == 4242
 

@@ -22,10 +22,10 @@ import pytest
 import torch
 
 from tests import lifecycle_ref as LC
+from tests.support import TD, bits
 
 pytestmark = pytest.mark.gpu
 
-TD = {"f16": torch.float16, "bf16": torch.bfloat16}
 SEG = 256                                  # erase segments of 256 rows: three and more per erase
 
 
@@ -43,9 +43,7 @@ class IO:
     def i64(x):
         return torch.from_numpy(np.ascontiguousarray(x, dtype=np.int64))
 
-    @staticmethod
-    def bits(t):
-        return t.contiguous().view(torch.int16).cpu().numpy().view(np.uint16)
+    bits = staticmethod(bits)
 
     @staticmethod
     def stack(masks):

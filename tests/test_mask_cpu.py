@@ -9,8 +9,7 @@ import pytest
 import torch
 
 from tests import mask_ref as MR
-from tests.host_memory import host_memory
-from tests.test_scratch_cpu import SizingLibrary, _buffers
+from tests.host_memory import host_memory, owner_rule_holds
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -103,22 +102,9 @@ def test_packing_of_a_ring_of_40_after_57_rows():
     assert sel[0].sum() == 4 and sel[1].sum() == 36 and not sel[2].any() and not sel[3].any()
 
 
-# ---- the scratch owner rule for the new kind (tests/test_scratch_cpu.py's stand-in sizing library) -------------------
+# ---- the scratch owner rule for the new kind (tests/host_memory.py's stand-in sizing library) -------------------
 def test_masked_scratch_follows_the_owner_rule():
-    from vidmem import memory as M
-    mem = host_memory(capacity=16, library=SizingLibrary())
-    first = mem.prepare_topk_masked(4, 10)
-    assert isinstance(first, M.MaskedTopkScratch) and first.fits(mem, 4, 10)
-    assert first.ws.numel() == 1000 + 64 * 14 and first.flags.dtype == torch.int32 and (first.flags == 0).all()
-    assert set(_buffers(first)) == {"ws", "flags"}
-    before = _buffers(first)
-    assert mem.prepare_topk_masked(4, 10) is first and mem._resolve(M.MaskedTopkScratch, None, 2, 5) is first
-    grown = mem.prepare_topk_masked(64, 32)
-    assert grown is not first and grown.fits(mem, 64, 32) and _buffers(first) == before   # replaced, never resized
-    with pytest.raises(ValueError, match="too small"):
-        mem._resolve(M.MaskedTopkScratch, M.MaskedTopkScratch.for_(mem, 4, 10), 64, 32)
-    theirs = M.MaskedTopkScratch.for_(mem, 64, 32)
-    assert mem._resolve(M.MaskedTopkScratch, theirs, 64, 32) is theirs
+    mem = owner_rule_holds("MaskedTopkScratch", "prepare_topk_masked")
     assert mem.last_mask_flags is None and mem.masked_uncertified_count == 0
 
 

@@ -9,7 +9,7 @@ import pytest
 import torch
 
 from tests import mask_ref as MR
-from tests.test_group_topk_gpu import _bits, clustered, queries_near
+from tests.support import Embedder, bits, clustered, queries_near
 
 pytestmark = pytest.mark.gpu
 
@@ -38,7 +38,7 @@ def test_search_within_the_results_of_a_range_search(world):
     mem, rows, host, _ = world
     qx = (rows[805].float() + 0.02 * torch.randn(D, device="cuda", generator=torch.Generator("cuda").manual_seed(1)))
     qx = qx.to(torch.float16)[None].contiguous()
-    x = MR.cref.cosine_matrix(_bits(qx), host)[0]
+    x = MR.cref.cosine_matrix(bits(qx), host)[0]
     srt = np.sort(x)[::-1]
     gaps = srt[10:200] - srt[11:201]                 # tau in the widest gap that leaves 11 .. 200 hits
     i = 10 + int(np.argmax(gaps))
@@ -51,7 +51,7 @@ def test_search_within_the_results_of_a_range_search(world):
     m = mem.mask_of_rows(hits.rows)
     s, r = mem.topk_masked(qy, 10, m)
     assert mem.rows_of_mask(m) == hit.nonzero()[0].tolist()
-    _same(s, r, *MR.masked_topk(_bits(qy), host, np.tile(hit, (3, 1)), 10))
+    _same(s, r, *MR.masked_topk(bits(qy), host, np.tile(hit, (3, 1)), 10))
     assert hit[r.cpu().numpy()].all()
 
 
@@ -59,7 +59,7 @@ def test_next_page_by_excluding_the_rows_returned_so_far(world):
     mem, rows, host, q = world
     Q, k = 2, 10
     q = q[:Q].contiguous()
-    want_r, want_s = MR.cref.cosine_topk(_bits(q), host, 3 * k)
+    want_r, want_s = MR.cref.cosine_topk(bits(q), host, 3 * k)
     mask = ~mem.new_mask(Q)                          # one mask per query: everything
     pages = []
     for page in range(3):
@@ -80,16 +80,8 @@ def test_metadata_filter(world):
     sel = np.arange(N) % 4 == 3
     assert mem.rows_of_mask(m) == sel.nonzero()[0].tolist()
     s, r = mem.topk_masked(q, 20, m, min_score=0.05)
-    _same(s, r, *MR.masked_topk(_bits(q), host, np.tile(sel, (q.shape[0], 1)), 20, min_score=0.05))
+    _same(s, r, *MR.masked_topk(bits(q), host, np.tile(sel, (q.shape[0], 1)), 20, min_score=0.05))
     assert all(mem.meta_of(int(x))["camera"] == 3 for x in r.flatten().tolist() if x >= 0)
-
-
-class _Embedder:
-    def __init__(self, vec):
-        self.vec = vec
-
-    async def aembed_query(self, text):
-        return self.vec
 
 
 def test_adapters_take_a_mask(world):
@@ -99,17 +91,17 @@ def test_adapters_take_a_mask(world):
     sel = (np.arange(N) % 4 == 1) & (np.arange(N) >= 100)
     m = mem.mask_where(lambda row, id_, meta: meta["camera"] == 1 and row >= 100)
     q16 = q[0]
-    vs = HipVectorSearch(mem, _Embedder(q16.double().cpu().tolist()), SimpleNamespace(top_k_chunks=6), min_score=-1.0,
+    vs = HipVectorSearch(mem, Embedder(q16.double().cpu().tolist()), SimpleNamespace(top_k_chunks=6), min_score=-1.0,
                          score_mode=_lib.VM_SCORE_RAW, mask=m)
     got = asyncio.run(vs._vector_search_chunks(None, "q"))
-    want_r, want_s = MR.masked_topk(_bits(q16[None]), host, sel[None], 6, min_score=-1.0)
+    want_r, want_s = MR.masked_topk(bits(q16[None]), host, sel[None], 6, min_score=-1.0)
     assert [c["id"] for c in got] == [f"frame{int(r)}" for r in want_r[0]] and len(got) == 6
     assert [c["score"] for c in got] == want_s[0].tolist()
     assert [c["content"] for c in got] == [f"c{int(r)}" for r in want_r[0]]
     # the pre-LLM similarity; a wrong-length query lists the first selected rows, a failed one nothing
     sim = HipPreLLMSimilarity(mem, SimpleNamespace(top_k_chunk_with_batch_similarity=3), mask=m)
     got = asyncio.run(sim._calculate_batch_similarities([q16, [0.0] * 5, RuntimeError("embedder"), rows[50]]))
-    want_r, want_s = MR.masked_topk(_bits(torch.stack([q16, rows[50]])), host, np.tile(sel, (2, 1)), 3)
+    want_r, want_s = MR.masked_topk(bits(torch.stack([q16, rows[50]])), host, np.tile(sel, (2, 1)), 3)
     assert got[0] == [(f"frame{int(r)}", float(s)) for r, s in zip(want_r[0], want_s[0])]
     assert got[3] == [(f"frame{int(r)}", float(s)) for r, s in zip(want_r[1], want_s[1])]
     assert got[1] == [("frame101", 0.0), ("frame105", 0.0), ("frame109", 0.0)] and got[2] == []

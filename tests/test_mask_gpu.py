@@ -1,7 +1,7 @@
 """GPU: row masks and the masked top-k (vm_topk_cosine_masked, csrc/topk_mask.hip) against tests/mask_ref.py.
 
 Bar: rows, fp64 score bits and padding identical to statement (A) of the oracle, for the fast and the ``exact=True``
-entry.  The scan test runs the shapes at which the shared tile scan can go wrong (tests/test_tile_scan_gpu.py's data) under
+entry.  The scan test runs the shapes at which the shared tile scan can go wrong (tests/tile_scan_data.py) under
 every mask set of tests/mask_ref.py and demands flag 0 of every query: the redo would hide a broken scan.  That the data
 allows it is asserted from the oracle's scores before any search, and proven without a GPU in tests/test_mask_cpu.py.
 """
@@ -11,49 +11,28 @@ import torch
 
 from tests import mask_ref as MR
 from tests import scope_ref as S
-from tests.test_group_topk_gpu import _bits, clustered, queries_near
-from tests.test_scope_topk_gpu import ALL, contiguous_tags, scope_of, tagged_memory
-from tests.test_tile_scan_gpu import dataset
+from tests.support import (ALL, bits, check_entries, clustered, contiguous_tags, dev_mask, plain_memory, planted_duplicates,
+                           queries_near, scan_memory, scope_of, tagged_memory)
 
 pytestmark = pytest.mark.gpu
-
-
-def dev_mask(words) -> torch.Tensor:
-    return torch.from_numpy(np.ascontiguousarray(words, dtype=np.uint32).view(np.int32)).cuda()
-
-
-def plain_memory(rows, dtype, capacity=None, ring=False, step=65536, **kind):
-    from vidmem.memory import EmbeddingMemory
-    mem = EmbeddingMemory(capacity or max(rows.shape[0], 16), rows.shape[1], dtype, ring=ring, **kind)
-    step = min(step, mem.capacity)
-    for c0 in range(0, rows.shape[0], step):
-        mem.append(rows[c0:c0 + step])
-    return mem
 
 
 def want_of(mem, q, k, dtype, masks, index, **kw):
     """Statement (A) for the memory as it is: masks / index as the call takes them (host arrays)."""
     base, host_rows = mem.rows_host()
     sel = MR.selection(masks, index, q.shape[0], base, host_rows.shape[0], mem.capacity)
-    return MR.masked_topk(_bits(q), host_rows, sel, k, dtype=dtype, base=base, **kw)
+    return MR.masked_topk(bits(q), host_rows, sel, k, dtype=dtype, base=base, **kw)
 
 
 def check(mem, q, k, dtype, masks, index=None, certified=False, label="", **kw):
     """Fast and exact entry against (A).  certified=True: the fast path answered every query (flag 0)."""
-    want_r, want_s = want_of(mem, q, k, dtype, masks, index, **kw)
     m = dev_mask(masks)
-    out = None
-    for exact in (False, True):
+
+    def call(exact):
         s, r = mem.topk_masked(q, k, m, mask_index=index, exact=exact, **kw)
-        got_r, got_s = r.cpu().numpy(), s.cpu().numpy()
-        if not exact:
-            flags = mem.last_mask_flags[:q.shape[0]].cpu().numpy()
-            out = (got_r, got_s, flags)
-        assert np.array_equal(got_r, want_r), (label, exact, np.argwhere(got_r != want_r)[:5], got_r[:2], want_r[:2])
-        assert np.array_equal(got_s.view(np.int64), want_s.view(np.int64)), f"{label}: scores differ (bit-exact) exact={exact}"
-        if certified and not exact:
-            assert (flags == 0).all(), f"{label}: the scan left queries to the redo: {flags}"
-    return out
+        return r, s
+    return check_entries(call, lambda: mem.last_mask_flags[:q.shape[0]], want_of(mem, q, k, dtype, masks, index, **kw),
+                         certified or None, label)
 
 
 # ---- 1. the scan ------------------------------------------------------------------------------------------------------
@@ -61,12 +40,8 @@ def check(mem, q, k, dtype, masks, index=None, certified=False, label="", **kw):
 @pytest.mark.parametrize("D,dtype", [(128, "f16"), (128, "bf16"), (384, "f16"), (384, "bf16")])
 def test_scan(D, dtype, shape):
     MR.scan_precondition(D, dtype, shape)            # from oracle scores, before any search
-    rows, q_all, base, live = dataset(D, dtype, shape)
-    hrows, hq, hbase, hlive = MR.host_dataset(D, dtype, shape)
-    assert hbase == base and np.array_equal(_bits(rows), _bits(hrows)) and np.array_equal(_bits(q_all), _bits(hq))
-    total, cap = MR.SHAPES[shape]
-    mem = plain_memory(rows, dtype, capacity=cap, ring=cap is not None, step=19)
-    assert mem.rows_host()[0] == base and mem.mask_words == mem.L.vm_memory_mask_words(mem.handle) == 2
+    mem, q_all, base, live, total, cap = scan_memory(D, dtype, shape)
+    assert mem.mask_words == mem.L.vm_memory_mask_words(mem.handle) == 2
     n = live.shape[1]
     for Q in MR.QS:
         q = q_all[:Q].contiguous()
@@ -114,25 +89,16 @@ def test_mask_of_scope_equals_topk_scoped_and_full_mask_equals_topk():
     m = mem.mask_of_scope(two)
     union = S.scope_mask(tags, *two[0]) | S.scope_mask(tags, *two[1])
     assert mem.rows_of_mask(m) == union.nonzero()[0].tolist() and union.sum() == 500 + 151
-    want_r, want_s = MR.masked_topk(_bits(q), mem.rows_host()[1], np.tile(union, (16, 1)), 10)
+    want_r, want_s = MR.masked_topk(bits(q), mem.rows_host()[1], np.tile(union, (16, 1)), 10)
     s1, r1 = mem.topk_masked(q, 10, m)
     assert np.array_equal(r1.cpu().numpy(), want_r)
     assert np.array_equal(s1.cpu().numpy().view(np.int64), want_s.view(np.int64))
 
 
 # ---- 3. the redo --------------------------------------------------------------------------------------------------------
-def _planted(n_dup_step=24):
-    rows = torch.randn(3000, 768, device="cuda", generator=torch.Generator("cuda").manual_seed(2)).to(torch.float16)
-    planted = rows[5].clone()
-    dup = list(range(1010, 1970, n_dup_step))          # 40 copies: k = 10 keeps 18 candidates
-    for r in dup:
-        rows[r] = planted
-    return rows, planted, dup
-
-
 def test_more_duplicates_than_slack_inside_the_mask_is_flagged_and_redone():
     from vidmem import _lib
-    rows, planted, dup = _planted()
+    rows, planted, dup = planted_duplicates()
     mem = plain_memory(rows, "f16")
     inside = MR.pack_rows(range(1000, 2000), mem.capacity)[None]
     before = mem.masked_uncertified_count
@@ -142,12 +108,12 @@ def test_more_duplicates_than_slack_inside_the_mask_is_flagged_and_redone():
 
 
 def test_the_same_duplicates_outside_the_mask_leave_flag_zero():
-    rows, planted, dup = _planted()
+    rows, planted, dup = planted_duplicates()
     mem = plain_memory(rows, "f16")
     keep = [r for r in range(3000) if r not in set(dup) and r != 5]
     outside = MR.pack_rows(keep, mem.capacity)[None]
     q = planted[None].contiguous()
-    exact = np.sort(MR.cref.cosine_matrix(_bits(q), mem.rows_host()[1])[0][keep])[::-1]
+    exact = np.sort(MR.cref.cosine_matrix(bits(q), mem.rows_host()[1])[0][keep])[::-1]
     assert exact[9] - exact[18] > 4 * MR.cert_eps(768), "precondition: rank k and rank M + 1 too close in the oracle"
     before = mem.masked_uncertified_count
     got_r, _, flags = check(mem, q, 10, "f16", outside, certified=True, label="ties outside")

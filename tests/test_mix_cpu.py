@@ -12,18 +12,12 @@ import torch
 from oracle import cref
 from tests import mask_ref as MR
 from tests import mix_ref as XR
+from tests.support import same_arrays
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _case(D=128, dtype="f16", shape="n47"):
-    from tests.test_group_topk_gpu import _bits
-    rows, q, base, live = MR.host_dataset(D, dtype, shape)
-    return _bits(rows[base:]), _bits(q), base, live
-
-
-def _same(a, b):
-    return np.array_equal(a[0], b[0]) and np.array_equal(a[1].view(np.int64), b[1].view(np.int64))
+_case = MR.host_case
 
 
 # ---- the oracle -----------------------------------------------------------------------------------------------------------
@@ -41,7 +35,7 @@ def test_loop_and_array_statements_agree_bit_for_bit(D, dtype):
     ws = [XR.weights_of("feedback", 5)] * 3
     sel = MR.selection(*MR.mask_sets(3, "n47")["alternating"], 3, base, rows.shape[0], 47)
     for k in (1, 5, 64):
-        assert _same(XR.mix_topk(terms, ws, rows, sel, k, dtype, base=base),
+        assert same_arrays(XR.mix_topk(terms, ws, rows, sel, k, dtype, base=base),
                      XR.mix_topk(terms, ws, rows, sel, k, dtype, base=base, scores=XR.mix_scores))
 
 
@@ -52,13 +46,13 @@ def test_one_term_of_weight_one_is_the_row_oracle(D, dtype):
     ws = [[1.0]] * 4
     for k in (1, 5, 20):
         r, s = cref.cosine_topk(q[:4], rows, k, dtype=dtype)
-        assert _same(XR.mix_topk(terms, ws, rows, None, k, dtype), (r, s))
+        assert same_arrays(XR.mix_topk(terms, ws, rows, None, k, dtype), (r, s))
         for cut in (0.2, -0.1):
             r, s = cref.cosine_topk(q[:4], rows, k, dtype=dtype, min_score=cut)
-            assert _same(XR.mix_topk(terms, ws, rows, None, k, dtype, min_score=cut), (r, s))
+            assert same_arrays(XR.mix_topk(terms, ws, rows, None, k, dtype, min_score=cut), (r, s))
         masks, index = MR.mask_sets(4, "n47")["alternating"]
         sel = MR.selection(masks, index, 4, base, rows.shape[0], 47)
-        assert _same(XR.mix_topk(terms, ws, rows, sel, k, dtype, base=base),
+        assert same_arrays(XR.mix_topk(terms, ws, rows, sel, k, dtype, base=base),
                      MR.masked_topk(q[:4], rows, sel, k, dtype=dtype, base=base))
 
 
@@ -70,7 +64,7 @@ def test_zero_weight_padding_is_bit_neutral():
         t16 = np.concatenate([t3, q[None, 10:23].repeat(3, axis=0)], axis=1)
         assert t16.shape[1] == 16
         for k in (1, 5):
-            assert _same(XR.mix_topk(t3, [w3] * 3, rows, None, k, "bf16"),
+            assert same_arrays(XR.mix_topk(t3, [w3] * 3, rows, None, k, "bf16"),
                          XR.mix_topk(t16, [w3 + [0.0] * 13] * 3, rows, None, k, "bf16"))
     e = live[XR.term_rows(0, 16)]
     w = XR.weights_of("wide", 5)
@@ -87,7 +81,7 @@ def test_permuting_the_queries_permutes_the_results():
     r, s = XR.mix_topk(terms, ws, rows, sel, 5)
     perm = [2, 0, 1]
     rp, sp = XR.mix_topk(terms[perm], [ws[i] for i in perm], rows, sel[perm], 5)
-    assert _same((rp, sp), (r[perm], s[perm]))
+    assert same_arrays((rp, sp), (r[perm], s[perm]))
 
 
 def test_eps_mix_restated():
@@ -133,7 +127,7 @@ def test_feedback_terms_weights_and_errors():
 # ---- the Python layer, before the library is called ------------------------------------------------------------------------
 def test_python_refusals_and_scratch():
     from tests.host_memory import host_memory
-    from tests.test_scratch_cpu import SizingLibrary
+    from tests.host_memory import SizingLibrary
     from vidmem import memory as M
     mem = host_memory(capacity=100)
     t = torch.zeros((2, 3, mem.dim))

@@ -1,7 +1,7 @@
 """GPU: the mixed-query top-k (vm_topk_cosine_mix, csrc/topk_mix.hip) against tests/mix_ref.py.
 
 Bar: rows, fp64 score bits and padding identical to statement (A) of the oracle, for the fast and the ``exact=True``
-entry.  The scan test runs the shapes at which the shared tile scan can go wrong (tests/test_tile_scan_gpu.py's data) for
+entry.  The scan test runs the shapes at which the shared tile scan can go wrong (tests/tile_scan_data.py) for
 every (C, J, weight set, mask set, k) of tests/mix_ref.py and demands flag 0 wherever the oracle's scores allow it: the
 redo would hide a broken scan.  That they allow it is asserted from the oracle's scores before any search, and proven
 without a GPU in tests/test_mix_cpu.py.
@@ -12,55 +12,19 @@ import torch
 
 from tests import mask_ref as MR
 from tests import mix_ref as XR
-from tests.test_group_topk_gpu import _bits, clustered, queries_near
-from tests.test_mask_gpu import dev_mask, plain_memory
-from tests.test_tile_scan_gpu import dataset
+from tests.search_checks import mix_check as check
+from tests.search_checks import mix_want as want_of
+from tests.support import bits, clustered, dev_mask, plain_memory, queries_near, redone, same_result, scan_memory
+from tests.tile_scan_data import dataset
 
 pytestmark = pytest.mark.gpu
-
-
-def want_of(mem, terms, weights, k, dtype, masks=None, index=None, **kw):
-    """Statement (A) for the memory as it is: terms [C,J,D] on the device, weights [C][J], masks / index host arrays."""
-    base, host_rows = mem.rows_host()
-    C = terms.shape[0]
-    sel = None if masks is None else MR.selection(masks, index, C, base, host_rows.shape[0], mem.capacity)
-    return XR.mix_topk(_bits(terms), weights, host_rows, sel, k, dtype=dtype, base=base, **kw)
-
-
-def per_query(weights, C):
-    return [list(weights)] * C if not isinstance(weights[0], (list, tuple)) else [list(w) for w in weights]
-
-
-def check(mem, terms, weights, k, dtype, masks=None, index=None, certified=None, label="", want=None, **kw):
-    """Fast and exact entry against (A) (``want``: (A) computed by the caller).  certified: None, or bool per query - the
-    fast path must have answered those queries itself (flag 0)."""
-    C = terms.shape[0]
-    want_r, want_s = want or want_of(mem, terms, per_query(weights, C), k, dtype, masks, index, **kw)
-    m = None if masks is None else (masks if isinstance(masks, torch.Tensor) else dev_mask(masks))
-    out = None
-    for exact in (False, True):
-        s, r = mem.topk_mix(terms, weights, k, mask=m, mask_index=index, exact=exact, **kw)
-        got_r, got_s = r.cpu().numpy(), s.cpu().numpy()
-        if not exact:
-            flags = mem.last_mix_flags[:C].cpu().numpy()
-            out = (got_r, got_s, flags)
-        assert np.array_equal(got_r, want_r), (label, exact, np.argwhere(got_r != want_r)[:5], got_r[:2], want_r[:2])
-        assert np.array_equal(got_s.view(np.int64), want_s.view(np.int64)), f"{label}: scores differ (bit-exact) exact={exact}"
-        if certified is not None and not exact:
-            assert (flags[np.asarray(certified)] == 0).all(), f"{label}: the scan left queries to the redo: {flags}"
-    return out
 
 
 # ---- 1. the scan ------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("shape", list(MR.SHAPES))
 @pytest.mark.parametrize("D,dtype", XR.DTS)
 def test_scan(D, dtype, shape):
-    rows, q_all, base, live = dataset(D, dtype, shape)
-    hrows, hq, hbase, hlive = MR.host_dataset(D, dtype, shape)
-    assert hbase == base and np.array_equal(_bits(rows), _bits(hrows)) and np.array_equal(_bits(q_all), _bits(hq))
-    total, cap = MR.SHAPES[shape]
-    mem = plain_memory(rows, dtype, capacity=cap, ring=cap is not None, step=19)
-    assert mem.rows_host()[0] == base
+    mem, q_all, base, live, total, cap = scan_memory(D, dtype, shape)
     n = live.shape[1]
     demanded = cases = 0
     for C in XR.CS:
@@ -93,10 +57,6 @@ def test_scan(D, dtype, shape):
 
 
 # ---- 2. identities on the device --------------------------------------------------------------------------------------
-def _same(a, b):
-    return torch.equal(a[1], b[1]) and np.array_equal(a[0].cpu().numpy().view(np.int64), b[0].cpu().numpy().view(np.int64))
-
-
 @pytest.mark.parametrize("dtype", ["f16", "bf16"])
 def test_identities(dtype):
     rows, _ = clustered([5] * 200, 384, dtype, seed=21)
@@ -107,9 +67,9 @@ def test_identities(dtype):
         # J = 1, w = 1: the reference cosine bit for bit
         for exact in (False, True):
             got = mem.topk_mix(q[:, None, :], [1.0], k, exact=exact)
-            assert _same(got, mem.topk(q, k)), (k, exact)
+            assert same_result(got, mem.topk(q, k)), (k, exact)
             got = mem.topk_mix(q[:, None, :], [1.0], k, mask=mask, exact=exact)
-            assert _same(got, mem.topk_masked(q, k, mask)), (k, exact)
+            assert same_result(got, mem.topk_masked(q, k, mask)), (k, exact)
     # zero-weight padding from J = 3 to J = 16 changes no bit
     t3 = q[:15].reshape(5, 3, -1).contiguous()
     t16 = torch.cat([t3, q[None, :13].expand(5, -1, -1)], dim=1).contiguous()
@@ -117,7 +77,7 @@ def test_identities(dtype):
         for exact in (False, True):
             a = mem.topk_mix(t3, w3, 10, mask=mask, exact=exact)
             b = mem.topk_mix(t16, w3 + [0.0] * 13, 10, mask=mask, exact=exact)
-            assert _same(a, b), (w3, exact)
+            assert same_result(a, b), (w3, exact)
     # a query's result is the same alone and inside a batch of 3
     terms = q[:15].reshape(3, 5, -1).contiguous()
     ws = [XR.weights_of(nm, 5) for nm in ("mean", "feedback", "wide")]
@@ -126,22 +86,15 @@ def test_identities(dtype):
         s3, r3 = mem.topk_mix(terms, ws, 10, mask=masks, exact=exact)
         for c in range(3):
             s1, r1 = mem.topk_mix(terms[c], [ws[c]], 10, mask=masks[c], exact=exact)
-            assert _same((s1, r1), (s3[c:c + 1], r3[c:c + 1])), (c, exact)
+            assert same_result((s1, r1), (s3[c:c + 1], r3[c:c + 1])), (c, exact)
     check(mem, terms, ws, 10, dtype, masks.cpu().numpy().view(np.uint32), label="batch of 3")
     mem.close()
 
 
 # ---- 3. what must go to the redo and still be exact -------------------------------------------------------------------
 def _redone(mem, terms, weights, k, dtype, label, flag=None, **kw):
-    from vidmem import _lib
-    before = mem.mix_uncertified_count
-    got_r, got_s, flags = check(mem, terms, weights, k, dtype, label=label, **kw)
-    assert (flags != 0).all(), (label, flags)
-    if flag is not None:
-        assert (flags == flag).all(), (label, flags)
-    assert flags[0] in (_lib.VM_FLAG_GAP, _lib.VM_FLAG_OVERFLOW)
-    assert mem.mix_uncertified_count == before + terms.shape[0], label
-    return got_r, got_s
+    return redone(lambda: check(mem, terms, weights, k, dtype, label=label, **kw), lambda: mem.mix_uncertified_count,
+                  terms.shape[0], label, flag)
 
 
 def test_redo_cases():
@@ -235,7 +188,7 @@ def test_arguments():
     assert (got_r[1:] == -1).all() and (got_r[0] >= 0).all()
     plain = check(mem, terms, ws, 7, "bf16", label="stride 1")
     base, host_rows = mem.rows_host()
-    wr, wscore = XR.mix_topk(_bits(terms), ws, host_rows, None, 7, dtype="bf16")
+    wr, wscore = XR.mix_topk(bits(terms), ws, host_rows, None, 7, dtype="bf16")
     for exact in (False, True):
         s, r = mem.topk_mix(terms, ws, 7, stride=(3, 1), exact=exact)
         assert np.array_equal(r.cpu().numpy(), wr * 3 + 1) and np.array_equal(s.cpu().numpy().view(np.int64), wscore.view(np.int64))

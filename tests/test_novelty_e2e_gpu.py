@@ -11,23 +11,10 @@ import torch
 from oracle import cref
 from tests import novelty_ref as N
 from tests.novelty_feed import feed, threshold_between
+from tests.search_checks import e2e_extractor
+from tests.support import bits
 
 pytestmark = pytest.mark.gpu
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int16).cpu().numpy().view(np.uint16)
-
-
-def _extractor(enc, tau, look_ahead):
-    from vidmem import config as C
-    from vidmem.extractor import FrameEmbeddingExtractor
-    cfg = C.from_dict({
-        "video": {"chunk_size_seconds": 1.0, "frames_per_chunk": 5},
-        "encoder": {"arch": "vit_b16_2l", "dtype": "f16", "seed": 3, "top_k": 4, "look_ahead_chunks": look_ahead},
-        "memory": {"capacity": 512, "novelty_threshold": tau},
-    })
-    return FrameEmbeddingExtractor(cfg, encoder=enc)
 
 
 def _process(ex, clip, path):
@@ -48,12 +35,12 @@ def test_gated_extractor_look_ahead_1_and_4_alike(tmp_path, monkeypatch):
     frames, owner = frames[:120], owner[:120]
     clip = tmp_path / "clip.npz"
     np.savez(clip, frames=frames, fps=np.float64(5.0))        # 5 frames per one-second chunk: every frame is picked
-    ex_off = _extractor(None, None, 1)
+    ex_off = e2e_extractor(None, {"novelty_threshold": None}, 1)
     enc = ex_off.encoder
     all_emb = enc.embed_frames(torch.from_numpy(frames).cuda())
-    emb_bits = _bits(all_emb)
+    emb_bits = bits(all_emb)
     tau = threshold_between(cref.cosine_matrix(emb_bits, emb_bits), owner)
-    ex1, ex4 = _extractor(enc, tau, 1), _extractor(enc, tau, 4)
+    ex1, ex4 = (e2e_extractor(enc, {"novelty_threshold": tau}, la) for la in (1, 4))
     res1, rid1 = _process(ex1, clip, tmp_path / "la1.json")
     res4, rid4 = _process(ex4, clip, tmp_path / "la4.json")
     assert res1 == res4 and len(res1) == 24

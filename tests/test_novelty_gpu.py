@@ -9,18 +9,13 @@ import pytest
 import torch
 
 from tests import novelty_ref as N
+from tests.support import from_bits
 
 pytestmark = pytest.mark.gpu
 
 SEQUENCE = (16, 17, 1, 300, 16, 250, 600)
 SHAPES = [("f16", 768), ("bf16", 1024)]
 KINDS = ["plain", "grouped", "tagged", "tagged_grouped"]
-
-
-def _t(bits, dtype):
-    """uint16 bit patterns -> device tensor of the memory dtype."""
-    tt = torch.float16 if dtype == "f16" else torch.bfloat16
-    return torch.from_numpy(np.ascontiguousarray(bits).view(np.int16)).view(tt).cuda()
 
 
 def _memory(kind, cap, D, dtype, ring=False):
@@ -46,7 +41,7 @@ def _assert_same_memory(mem, model, kind, dtype, queries):
             kw["group"] = torch.from_numpy(model.keys[lo:lo + step].copy())
         if ref.tagged:
             kw["tag"] = torch.from_numpy(model.tags[lo:lo + step].copy())
-        ref.append(_t(model.rows[lo:lo + step], dtype), **kw)
+        ref.append(from_bits(model.rows[lo:lo + step], dtype), **kw)
     assert len(mem) == len(ref) == model.total
     base, rows = mem.rows_host()
     base_r, rows_r = ref.rows_host()
@@ -57,7 +52,7 @@ def _assert_same_memory(mem, model, kind, dtype, queries):
     if mem.grouped:
         assert np.array_equal(mem.group_keys_host(), ref.group_keys_host())
         assert np.array_equal(mem.group_keys_host(), model.keys[base:])
-    q = _t(queries, dtype)
+    q = from_bits(queries, dtype)
     for a, b in zip(mem.topk(q, 10), ref.topk(q, 10)):
         assert torch.equal(a, b)
     if mem.grouped:
@@ -92,7 +87,7 @@ def test_recipe_sequence(dtype, D, kind, sigma, tau):
         idx = np.arange(off, off + B, dtype=np.int64)
         keys = idx // 16 if "grouped" in kind else None           # runs of 16 frames: groups continue across calls
         tags = np.array([make_tag(0, int(i) * 33) for i in idx], np.int64) if "tagged" in kind else None
-        bt = _t(batch, dtype)
+        bt = from_bits(batch, dtype)
         want_ks, want_kr = model.known(batch)
         if mem.searchable == 0:
             known = None
@@ -126,7 +121,7 @@ def test_single_large_batch_into_an_empty_memory(dtype, D, B):
     want_keep, want_row_of = N.gate(x, 0.9, dtype, 0)
     _in_band(want_keep)
     mem = _memory("plain", B, D, dtype)
-    keep, row_of, count = _gated(mem, _t(x, dtype), 0.9)
+    keep, row_of, count = _gated(mem, from_bits(x, dtype), 0.9)
     assert np.array_equal(keep, want_keep) and np.array_equal(row_of, want_row_of)
     assert count == int(want_keep.sum()) == len(mem)
     model = N.GatedMemory(D, dtype)
@@ -181,7 +176,7 @@ def test_threshold_planted_on_a_score(dtype, D):
     assert 0.5 < tau < 1.0
     for t, want in ((tau, [True, True]), (float(np.nextafter(tau, -np.inf)), [True, False])):
         mem = _memory("plain", 16, D, dtype)
-        keep, row_of, count = _gated(mem, _t(pair, dtype), t)
+        keep, row_of, count = _gated(mem, from_bits(pair, dtype), t)
         assert keep.tolist() == want and count == sum(want)
         assert row_of.tolist() == ([0, 1] if want[1] else [0, 0])
         assert np.array_equal(keep, N.gate(pair, t, dtype, 0)[0])
@@ -190,8 +185,8 @@ def test_threshold_planted_on_a_score(dtype, D):
     kr = torch.tensor([5], dtype=torch.int64, device="cuda")
     for t, want in ((tau, True), (float(np.nextafter(tau, -np.inf)), False)):
         mem = _memory("plain", 16, D, dtype, ring=True)
-        mem.append(_t(x[8:16], dtype))
-        keep, row_of, count = _gated(mem, _t(x[:1], dtype), t, known=(ks, kr))
+        mem.append(from_bits(x[8:16], dtype))
+        keep, row_of, count = _gated(mem, from_bits(x[:1], dtype), t, known=(ks, kr))
         assert keep.tolist() == [want] and row_of.tolist() == [8 if want else 5] and count == int(want)
         assert len(mem) == 8 + int(want)
 
@@ -210,25 +205,25 @@ def test_duplicates_zero_rows_and_a_batch_that_keeps_nothing():
     assert want_keep.tolist() == [True, True, False, True, False, True, False, True, False]
     assert want_row_of.tolist() == [3, 4, 4, 5, 4, 6, 4, 7, 4]       # every duplicate names the first one's new id
     mem = _memory("grouped", 64, D, dtype)
-    mem.append(_t(u[3:6], dtype), group=[7, 7, 9])
-    keep, row_of, count = _gated(mem, _t(batch, dtype), 0.5, group=torch.full((9,), 9, dtype=torch.int64).cuda())
+    mem.append(from_bits(u[3:6], dtype), group=[7, 7, 9])
+    keep, row_of, count = _gated(mem, from_bits(batch, dtype), 0.5, group=torch.full((9,), 9, dtype=torch.int64).cuda())
     assert np.array_equal(keep, want_keep) and np.array_equal(row_of, want_row_of) and count == 5
     # a batch that keeps nothing: counter, columns and group state untouched ...
     before = (mem.rows_host()[1].copy(), mem.group_keys_host().copy())
-    s, r = mem.topk(_t(u[:3], dtype), 1)
-    keep, row_of, count = _gated(mem, _t(u[:3], dtype), 0.5, known=(s, r),
+    s, r = mem.topk(from_bits(u[:3], dtype), 1)
+    keep, row_of, count = _gated(mem, from_bits(u[:3], dtype), 0.5, known=(s, r),
                                  group=torch.full((3,), 11, dtype=torch.int64).cuda())
     assert keep.tolist() == [False] * 3 and count == 0 and len(mem) == 8
     assert row_of.tolist() == [3, 4, 6]
     assert np.array_equal(mem.rows_host()[1], before[0]) and np.array_equal(mem.group_keys_host(), before[1])
     # ... so a grouped append with the previous key still continues the open group (key 9: rows 2 and 3..7 and the new one)
-    mem.append(_t(u[3:4], dtype), group=9)
+    mem.append(from_bits(u[3:4], dtype), group=9)
     model = N.GatedMemory(D, dtype)
     model.rows = np.concatenate([u[3:6], batch[want_keep], u[3:4]])
     model.keys = np.array([7, 7, 9, 9, 9, 9, 9, 9, 9], np.int64)
     model.tags = np.zeros(9, np.int64)
     _assert_same_memory(mem, model, "grouped", dtype, u)
-    sg, rg, kg = mem.topk_grouped(_t(u[3:4], dtype), 3)
+    sg, rg, kg = mem.topk_grouped(from_bits(u[3:4], dtype), 3)
     assert kg[0, 0].item() in (7, 9) and len(set(kg[0].tolist()) - {-1}) == 2       # two groups in all
 
 
@@ -243,14 +238,14 @@ def test_threshold_2_is_plain_append_and_minus_2_keeps_one_row(kind):
         kw = {"group": torch.arange(100).cuda() // 7, "tag": torch.arange(100).cuda() * 5}
     for lo, hi in ((0, 37), (37, 100)):
         sub = {k: v[lo:hi] for k, v in kw.items()}
-        keep, row_of, count = _gated(mem, _t(x[lo:hi], dtype), 2.0, **sub)
+        keep, row_of, count = _gated(mem, from_bits(x[lo:hi], dtype), 2.0, **sub)
         assert keep.all() and count == hi - lo and row_of.tolist() == list(range(lo, hi))
     model.rows = x
     model.keys = np.arange(100, dtype=np.int64) // 7 if kw else -1 - np.arange(100, dtype=np.int64)
     model.tags = np.arange(100, dtype=np.int64) * 5
     _assert_same_memory(mem, model, kind, dtype, x[[0, 50, 99]])       # bit-identical to the plain appends
     empty = _memory(kind, 256, D, dtype)
-    keep, row_of, count = _gated(empty, _t(x, dtype), -2.0)
+    keep, row_of, count = _gated(empty, from_bits(x, dtype), -2.0)
     assert keep.tolist() == [True] + [False] * 99 and count == 1 and (row_of == 0).all() and len(empty) == 1
 
 
@@ -264,7 +259,7 @@ def test_ring_that_wraps_inside_the_call_and_an_overwritten_known_row():
         batch = x[off:off + B]
         tags = np.arange(off, off + B, dtype=np.int64)
         known = model.known(batch)                  # describes the memory BEFORE the call, as the definition says
-        bt = _t(batch, dtype)
+        bt = from_bits(batch, dtype)
         dev_known = mem.topk(bt, 1) if mem.searchable else None
         want_keep, want_row_of = model.append_novel(batch, 0.9, known=known, tags=tags)
         _in_band(want_keep)
@@ -280,7 +275,7 @@ def test_ring_that_wraps_inside_the_call_and_an_overwritten_known_row():
     assert known[1][-1] == base and known[0][-1] > 0.99
     want_keep, want_row_of = model.append_novel(batch, 0.9, known=known)
     assert not want_keep[-1] and want_row_of[-1] == base and want_keep.sum() > 1
-    bt = _t(batch, dtype)
+    bt = from_bits(batch, dtype)
     keep, row_of, count = _gated(mem, bt, 0.9, known=mem.topk(bt, 1))
     assert np.array_equal(keep, want_keep) and np.array_equal(row_of, want_row_of)
     assert len(mem) == model.total and base < model.total - cap          # ... and that row is gone now
@@ -294,14 +289,14 @@ def test_non_ring_capacity():
     distinct = np.unique(x, axis=0)[:40]
     assert distinct.shape[0] == 40
     mem = _memory("plain", 32, D, dtype)
-    mem.append(_t(distinct[:10], dtype))
+    mem.append(from_bits(distinct[:10], dtype))
     with pytest.raises(_lib.VidmemError) as e:       # 10 + 23 > 32: refused on the worst case, whatever would be kept
-        mem.enqueue_append_novel(_t(distinct[:23], dtype), 0.5)
+        mem.enqueue_append_novel(from_bits(distinct[:23], dtype), 0.5)
     assert e.value.code == _lib.VM_ERR_NOMEM and mem.sync() == 10
     # a stale mirror (two enqueued calls without a sync between them) must still never write past the capacity
-    keep1, _, c1 = mem.enqueue_append_novel(_t(distinct[10:30], dtype), 0.5)
+    keep1, _, c1 = mem.enqueue_append_novel(from_bits(distinct[10:30], dtype), 0.5)
     assert int(c1.item()) == 20
-    keep2, _, c2 = mem.enqueue_append_novel(_t(distinct[20:40], dtype), 0.5)     # mirror still says 10
+    keep2, _, c2 = mem.enqueue_append_novel(from_bits(distinct[20:40], dtype), 0.5)     # mirror still says 10
     assert mem.sync() == 32 and len(mem) == 32
     pad = _tensor_from_ptr(mem.L.vm_memory_rows(mem.handle), (64, D), torch.int16, mem.device)
     assert np.array_equal(pad[:30].cpu().numpy().view(np.uint16), distinct[:30])
@@ -317,7 +312,7 @@ def test_capture_topk_redo_and_gated_append_in_one_graph():
     mem = _memory("tagged_grouped", cap, D, dtype, ring=True)
     model = N.GatedMemory(D, dtype, capacity=cap)
     seed_keys = np.arange(40, dtype=np.int64) // 8
-    mem.append(_t(x[:40], dtype), group=torch.from_numpy(seed_keys), tag=torch.arange(40))
+    mem.append(from_bits(x[:40], dtype), group=torch.from_numpy(seed_keys), tag=torch.arange(40))
     model.rows, model.keys, model.tags = x[:40].copy(), seed_keys.copy(), np.arange(40, dtype=np.int64)
     rows_in = torch.zeros((B, D), dtype=torch.float16, device="cuda")
     tags_in = torch.zeros(B, dtype=torch.int64, device="cuda")
@@ -333,7 +328,7 @@ def test_capture_topk_redo_and_gated_append_in_one_graph():
 
     with torch.cuda.stream(stream):
         warm = _memory("tagged_grouped", cap, D, dtype, ring=True)
-        warm.append(_t(x[:4], dtype), group=0, tag=0)
+        warm.append(from_bits(x[:4], dtype), group=0, tag=0)
         real = mem
         mem = warm
         body()
@@ -353,7 +348,7 @@ def test_capture_topk_redo_and_gated_append_in_one_graph():
         want_keep, want_row_of = model.append_novel(batch, 0.9, known=(want_ks, want_kr), tags=tags, keys=keys)
         _in_band(want_keep)
         with torch.cuda.stream(stream):
-            rows_in.copy_(_t(batch, dtype))
+            rows_in.copy_(from_bits(batch, dtype))
             tags_in.copy_(torch.from_numpy(tags))
             keys_in.copy_(torch.from_numpy(keys))
             graph.replay()
@@ -377,23 +372,23 @@ def test_against_a_scope_against_none_and_the_eager_tables():
     _in_band(want_keep)
     n0 = int(want_keep.sum())
     ids = [f"a_{i}" for i in range(48)]
-    nov = mem.append_novel(_t(x, dtype), 0.9, ids=ids, meta=[{"i": i} for i in range(48)],
+    nov = mem.append_novel(from_bits(x, dtype), 0.9, ids=ids, meta=[{"i": i} for i in range(48)],
                            tag=[make_tag(0, i) for i in range(48)])
     assert nov.kept == n0 == len(mem) == len(mem.ids)
     assert nov.keep.dtype == torch.bool and np.array_equal(nov.keep.cpu().numpy(), want_keep)
     assert np.array_equal(nov.row_of.cpu().numpy(), want_row_of)
     assert mem.ids == [ids[i] for i in np.nonzero(want_keep)[0]] and mem.meta_of(0) == {"i": 0}
     # the same frames again: nothing is new for the whole memory or for source 0 ...
-    assert mem.append_novel(_t(x, dtype), 0.9, tag=make_tag(0, 99)).kept == 0
-    assert mem.append_novel(_t(x, dtype), 0.9, against=scope_of(0), tag=make_tag(0, 99)).kept == 0
+    assert mem.append_novel(from_bits(x, dtype), 0.9, tag=make_tag(0, 99)).kept == 0
+    assert mem.append_novel(from_bits(x, dtype), 0.9, against=scope_of(0), tag=make_tag(0, 99)).kept == 0
     # ... but they are new for source 1, although source 0 holds them
-    nov1 = mem.append_novel(_t(x, dtype), 0.9, against=scope_of(1), tag=make_tag(1, 0))
+    nov1 = mem.append_novel(from_bits(x, dtype), 0.9, against=scope_of(1), tag=make_tag(1, 0))
     assert nov1.kept == n0 and np.array_equal(nov1.keep.cpu().numpy(), want_keep)
     assert np.array_equal(nov1.row_of.cpu().numpy(), N.gate(x, 0.9, dtype, n0)[1])
     assert len(mem) == 2 * n0 and (mem.tags_host()[n0:] == make_tag(1, 0)).all()
     # and a second time they are known to source 1 too
-    assert mem.append_novel(_t(x, dtype), 0.9, against=scope_of(1), tag=make_tag(1, 1)).kept == 0
+    assert mem.append_novel(from_bits(x, dtype), 0.9, against=scope_of(1), tag=make_tag(1, 1)).kept == 0
     # against=None: among the batch only, whatever is stored
-    nov2 = mem.append_novel(_t(x, dtype), 0.9, against=None)
+    nov2 = mem.append_novel(from_bits(x, dtype), 0.9, against=None)
     assert nov2.kept == n0 and np.array_equal(nov2.row_of.cpu().numpy(), N.gate(x, 0.9, dtype, 2 * n0)[1])
     assert (mem.tags_host()[2 * n0:] == -(1 << 63)).all() and len(mem.ids) == 3 * n0 == len(mem)

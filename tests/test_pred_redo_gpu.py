@@ -14,7 +14,7 @@ import pytest
 import torch
 
 from tests import scope_ref as S
-from tests.test_group_topk_gpu import _bits
+from tests.support import bits
 
 pytestmark = pytest.mark.gpu
 
@@ -48,7 +48,7 @@ def test_tag_range_mask_and_one_row_groups_agree_bit_for_bit(dtype):
     scopes[9] = (250, 249)                   # empty
     for lo, hi in scopes[:9] + scopes[10:]:
         assert lo <= 199 and hi >= 200
-    want_r, want_s = S.scoped_topk(_bits(q), host_rows, tags, scopes, K, dtype=dtype, base=base)
+    want_r, want_s = S.scoped_topk(bits(q), host_rows, tags, scopes, K, dtype=dtype, base=base)
     assert (want_r[9] == -1).all() and (np.delete(want_r, 9, axis=0) >= 0).all()
 
     sc = torch.tensor(scopes, dtype=torch.int64, device="cuda")
@@ -67,6 +67,6 @@ def test_tag_range_mask_and_one_row_groups_agree_bit_for_bit(dtype):
     s_mk, r_mk = mem.topk_masked(q, K, ~mem.new_mask(), exact=True)
     for s, r in ((s_sc, r_sc), (s_mk, r_mk)):
         assert torch.equal(r_all, r) and np.array_equal(_bits64(s_all), _bits64(s))
-    want_r, want_s = S.scoped_topk(_bits(q), host_rows, tags, ALL, K, dtype=dtype, base=base)
+    want_r, want_s = S.scoped_topk(bits(q), host_rows, tags, ALL, K, dtype=dtype, base=base)
     assert np.array_equal(r_all.cpu().numpy(), want_r) and np.array_equal(_bits64(s_all), want_s.view(np.int64))
     mem.close()

@@ -15,10 +15,10 @@ import pytest
 import torch
 
 from tests import preprocess_ref as P
+from tests.support import TD
 
 SMALL = [c.name for c in P.CASES if P.is_small(c)]
 MEDIUM = [c for c in P.CASES if P.n_out(c) <= 40000]  # what the defects are planted in: every branch, a few ms each
-TD = {"f16": torch.float16, "bf16": torch.bfloat16}
 
 
 @pytest.mark.parametrize("dtype", ["f16", "bf16"])

@@ -23,10 +23,10 @@ import pytest
 import torch
 
 from tests import preprocess_ref as P
+from tests.support import TD
 
 pytestmark = pytest.mark.gpu
 
-TD = {"f16": torch.float16, "bf16": torch.bfloat16}
 GUARD = 256                      # bytes before and after the output (and after the frames)
 SENT16 = 0x5AA5                  # the guards' int16 pattern
 SENT8 = 0xA5

@@ -5,7 +5,7 @@ import pytest
 import torch
 
 from tests import range_ref as R
-from tests.test_group_topk_gpu import _bits
+from tests.support import bits
 
 pytestmark = pytest.mark.gpu
 
@@ -36,7 +36,7 @@ def build(gap_inside=False):
 
 def oracle(mem, query, scope):
     base, host = mem.rows_host()
-    return R.range_hits(_bits(query), host, TAU, tags=mem.tags_host(), scopes=scope, dtype="f16", base=base)[0]
+    return R.range_hits(bits(query), host, TAU, tags=mem.tags_host(), scopes=scope, dtype="f16", base=base)[0]
 
 
 def test_a_scene_comes_back_as_one_moment_of_its_video():

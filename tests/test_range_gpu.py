@@ -4,7 +4,6 @@ Bar: rows, fp64 score bits, padding and counts identical to the oracle, for the 
 case.  The oracle's score matrix of a data set is computed once (``dataset``) and shared: a fresh memory and a wrapped
 ring over the same rows differ only in which columns are live.
 """
-import ctypes as C
 import functools
 
 import numpy as np
@@ -12,75 +11,10 @@ import pytest
 import torch
 
 from tests import range_ref as R
-from tests import scope_ref as S
-from tests.test_group_topk_gpu import TD, _bits, clustered, queries_near
-from tests.test_scope_topk_gpu import ALL, contiguous_tags, mixed_scopes, scope_of, tagged_memory
+from tests.search_checks import range_check, range_memory, raw_range
+from tests.support import ALL, bits, clustered, contiguous_tags, mixed_scopes, queries_near, scope_of, tagged_memory
 
 pytestmark = pytest.mark.gpu
-
-SENT_ROW, SENT_SCORE, SENT_COUNT = -7, 123.0, -9      # what the output buffers hold before a call
-
-
-def plain_memory(rows, dtype, capacity=None, ring=False, grouped=False, step=8192):
-    from vidmem.memory import EmbeddingMemory
-    mem = EmbeddingMemory(capacity or max(rows.shape[0], 16), rows.shape[1], dtype, ring=ring, grouped=grouped)
-    step = min(step, mem.capacity)
-    for c0 in range(0, rows.shape[0], step):
-        mem.append(rows[c0:c0 + step])
-    return mem
-
-
-def raw_call(mem, q, min_score, scopes=None, score_mode=0, max_hits=0, exact=False, stride=1, offset=0,
-             null_out=False, lo_hi=None):
-    """One call of the C entry on sentinel-filled buffers -> (rc, rows [Q, max_hits], scores, counts [Q], rescored [Q])
-    as numpy arrays.  ``lo_hi``: explicit (lo, hi) pointers (tensors or None) instead of ``scopes``."""
-    from vidmem import _lib
-    Q = q.shape[0]
-    need = int(mem.L.vm_range_workspace_bytes(mem.handle, Q))
-    assert 0 < need <= 16 * Q * ((mem.capacity + 63) // 64 * 64) + (1 << 16), need
-    ws = torch.empty(max(need, 256), dtype=torch.uint8, device="cuda")
-    rows = torch.full((Q, max(max_hits, 1)), SENT_ROW, dtype=torch.int64, device="cuda")
-    scores = torch.full((Q, max(max_hits, 1)), SENT_SCORE, dtype=torch.float64, device="cuda")
-    counts = torch.full((Q,), SENT_COUNT, dtype=torch.int64, device="cuda")
-    rescored = torch.full((Q,), SENT_COUNT, dtype=torch.int64, device="cuda")
-    p = lambda t: C.c_void_p(t.data_ptr() if t is not None else 0)
-    if lo_hi is None:
-        lo_hi = (None, None)
-        if scopes is not None:
-            lo, hi = S.scope_arrays(scopes, Q)
-            lo_hi = (torch.from_numpy(lo).cuda(), torch.from_numpy(hi).cuda())
-    out_r, out_s = (None, None) if null_out else (rows, scores)
-    head = (mem.handle, p(q), Q, float(min_score), int(score_mode), p(lo_hi[0]), p(lo_hi[1]), int(stride), int(offset),
-            int(max_hits), p(out_r), p(out_s), p(counts))
-    tail = (p(ws), ws.numel(), _lib.current_stream_ptr())
-    if exact:
-        rc = mem.L.vm_range_cosine_exact(*head, *tail)
-    else:
-        rc = mem.L.vm_range_cosine(*head, p(rescored), *tail)
-    torch.cuda.synchronize()
-    return (rc, rows.cpu().numpy()[:, :max_hits], scores.cpu().numpy()[:, :max_hits], counts.cpu().numpy(),
-            rescored.cpu().numpy())
-
-
-def check(mem, q, min_score, want, max_hits=None, scopes=None, score_mode=0, stride=1, offset=0, label=""):
-    """Fast and exhaustive entry against ``want`` (range_ref's per-query hits): padded rows, score bits and counts.
-    ``max_hits=None``: three more slots than the longest list, so that every hit and some padding is seen.
-    -> (counts, rescored) of the fast call."""
-    width = max([c for _, _, c in want] + [0]) + 3 if max_hits is None else max_hits
-    want_r, want_s, want_c = R.padded(want, width)
-    want_r = np.where(want_r >= 0, want_r * stride + offset, -1)
-    out = None
-    for exact in (False, True):
-        rc, r, s, c, resc = raw_call(mem, q, min_score, scopes, score_mode, width, exact, stride, offset,
-                                     null_out=width == 0)
-        assert rc == 0, (rc, mem.L.vm_last_error(mem.ctx.handle))
-        assert np.array_equal(c, want_c), (label, exact, c[:8], want_c[:8])
-        assert np.array_equal(r, want_r), (label, exact, np.argwhere(r != want_r)[:5])
-        assert np.array_equal(s.view(np.int64), want_s.view(np.int64)), f"{label}: scores differ (bit-exact bar) exact={exact}"
-        if not exact:
-            assert (resc >= c).all(), (label, resc[:8], c[:8])
-            out = (c, resc)
-    return out
 
 
 @functools.lru_cache(maxsize=None)
@@ -93,7 +27,7 @@ def dataset(name):
     sizes = [size] * (n // size) + ([n % size] if n % size else [])
     rows, _ = clustered(sizes, D, name, seed=seed)
     q = queries_near(rows, Q, seed + 1, name)
-    return rows, q, R.cref.cosine_matrix(_bits(q), _bits(rows), dtype=name)
+    return rows, q, R.cref.cosine_matrix(bits(q), bits(rows), dtype=name)
 
 
 # ---- 1. clean gap --------------------------------------------------------------------------------------------------
@@ -106,10 +40,10 @@ def test_clean_gap(name, ring):
     rows, q_all, matrix = dataset(name)
     n, D = rows.shape
     cap = None if not ring else (30011 if name == "f16" else 4001)        # below the rows appended: a wrapped ring
-    mem = plain_memory(rows, name, capacity=cap, ring=ring)
+    mem = range_memory(rows, name, capacity=cap, ring=ring)
     base, host = mem.rows_host()
     assert host.shape[0] == (cap or n) and base == n - host.shape[0]
-    assert np.array_equal(host[:3], _bits(rows[base:base + 3]))
+    assert np.array_equal(host[:3], bits(rows[base:base + 3]))
     live = matrix[:, base:]
     gap = np.abs(live - 0.2).min()
     print(f"{name} ring={ring}: nearest score to 0.2 is {gap / R.cert_eps(D):.0f} x cert_eps away")
@@ -117,12 +51,12 @@ def test_clean_gap(name, ring):
     for Q in (1, 17, 49) + ((130,) if name == "bf16" else ()):
         q = q_all[:Q].contiguous()
         want = R.range_from_scores(live[:Q], 0.2, base=base)
-        counts, resc = check(mem, q, 0.2, want, label=f"{name} Q={Q} 0.2")
+        counts, resc = range_check(mem, q, 0.2, want, label=f"{name} Q={Q} 0.2")
         assert counts.sum() > 0 and np.array_equal(resc, counts), (resc[:8], counts[:8])
         everything = R.range_from_scores(live[:Q], -1.0, base=base)
-        counts, _ = check(mem, q, -1.0, everything, max_hits=100, label=f"{name} Q={Q} -1")
+        counts, _ = range_check(mem, q, -1.0, everything, max_hits=100, label=f"{name} Q={Q} -1")
         assert (counts == host.shape[0]).all()
-        check(mem, q, 2.0, R.range_from_scores(live[:Q], 2.0, base=base), max_hits=5, label=f"{name} Q={Q} 2.0")
+        range_check(mem, q, 2.0, R.range_from_scores(live[:Q], 2.0, base=base), max_hits=5, label=f"{name} Q={Q} 2.0")
     # the Python entry on the same memory: trimmed lists, the full count, -inf = everything
     found = mem.range_search(q_all[:17], 0.2)
     for (r, s, c), got in zip(R.range_from_scores(live[:17], 0.2, base=base), found):
@@ -145,13 +79,13 @@ def test_threshold_inside_the_fp32_bound():
     tight = (tight / tight.norm(dim=1, keepdim=True)).to(torch.float16)
     rows = torch.cat([others[:1700], tight, others[1700:]]).contiguous()
     q = (tight[:1].float() + 0.1 * torch.randn(1, D, generator=g, device="cuda")).to(torch.float16)
-    m = R.cref.cosine_matrix(_bits(q), _bits(rows), dtype="f16")
+    m = R.cref.cosine_matrix(bits(q), bits(rows), dtype="f16")
     inside = m[0, 1700:3700]
     tau = float(np.median(inside))
     spread = np.abs(inside - tau).max() / R.cert_eps(D)
-    mem = plain_memory(rows, "f16")
+    mem = range_memory(rows, "f16")
     want = R.range_from_scores(m, tau)
-    counts, resc = check(mem, q, tau, want, label="inside the bound")
+    counts, resc = range_check(mem, q, tau, want, label="inside the bound")
     print(f"inside the bound: counts={counts.tolist()} rescored={resc.tolist()} spread={spread:.2f} x cert_eps")
     assert 0 < counts[0] < 2000 and (resc >= counts).all()
 
@@ -168,27 +102,27 @@ def test_strict_threshold_duplicates_and_zero_vectors():
     q = queries_near(rows, 4, 3, "f16").clone()
     q[1] = rows[40]
     q[3] = 0                                          # a zero query
-    mem = plain_memory(rows, "f16")
-    m = R.cref.cosine_matrix(_bits(q), _bits(rows), dtype="f16")
+    mem = range_memory(rows, "f16")
+    m = R.cref.cosine_matrix(bits(q), bits(rows), dtype="f16")
     for mode in (0, 1):
         for qi, r in ((0, 123), (1, 40), (2, 2999)):
             s = float(R.shown(m[qi, r], mode))
             for tau, present in ((s, False), (float(np.nextafter(s, -np.inf)), True)):
                 want = R.range_from_scores(m, tau, score_mode=mode)
                 assert (r in want[qi][0].tolist()) == present
-                check(mem, q, tau, want, score_mode=mode, label=f"strict mode={mode} q={qi}")
+                range_check(mem, q, tau, want, score_mode=mode, label=f"strict mode={mode} q={qi}")
                 if r == 40:                           # the copies are all in or all out together, in row order
                     got = [x for x in want[1][0].tolist() if x in set(dup + [40])]
                     assert got == ([40] + dup if present else [])
     want = R.range_from_scores(m, -0.5)
-    check(mem, q, -0.5, want, label="zero row")
+    range_check(mem, q, -0.5, want, label="zero row")
     for qi in range(3):
         i = want[qi][0].tolist().index(77)
         assert want[qi][1][i] == 0.0
     assert want[3][0].tolist() == list(range(3000)) and (want[3][1] == 0.0).all()
     assert R.range_from_scores(m, 0.0)[3][2] == 0
-    check(mem, q, 0.0, R.range_from_scores(m, 0.0), label="zero query at 0.0")
-    check(mem, q, 0.4, R.range_from_scores(m, 0.4, score_mode=1), score_mode=1, label="zero query, unit interval")
+    range_check(mem, q, 0.0, R.range_from_scores(m, 0.0), label="zero query at 0.0")
+    range_check(mem, q, 0.4, R.range_from_scores(m, 0.4, score_mode=1), score_mode=1, label="zero query, unit interval")
 
 
 # ---- 4. scopes ---------------------------------------------------------------------------------------------------------
@@ -198,56 +132,56 @@ def test_scopes_mixed_null_and_refused():
     tags = contiguous_tags(4000, 8)
     mem = tagged_memory(rows, tags, "f16")
     q = queries_near(rows, 16, 7, "f16")
-    m = R.cref.cosine_matrix(_bits(q), _bits(rows), dtype="f16")
+    m = R.cref.cosine_matrix(bits(q), bits(rows), dtype="f16")
     scopes = mixed_scopes(tags, 16, 10)
     for tau in (0.2, -1.0):
         want = R.range_from_scores(m, tau, tags=tags, scopes=scopes)
-        counts, _ = check(mem, q, tau, want, scopes=scopes, label=f"mixed scopes {tau}")
+        counts, _ = range_check(mem, q, tau, want, scopes=scopes, label=f"mixed scopes {tau}")
         assert counts[0] == 0 and counts[1] == 0 and counts[6] > 0
-    assert check(mem, q, -1.0, R.range_from_scores(m, -1.0, tags=tags, scopes=scopes), scopes=scopes)[0][2] == 1
+    assert range_check(mem, q, -1.0, R.range_from_scores(m, -1.0, tags=tags, scopes=scopes), scopes=scopes)[0][2] == 1
     # both scopes NULL = [INT64_MIN, INT64_MAX]
     whole = R.range_from_scores(m, 0.2)
-    check(mem, q, 0.2, whole, scopes=None, label="null scopes")
-    check(mem, q, 0.2, whole, scopes=ALL, label="whole scope")
+    range_check(mem, q, 0.2, whole, scopes=None, label="null scopes")
+    range_check(mem, q, 0.2, whole, scopes=ALL, label="whole scope")
     # the Python entry takes what topk_scoped takes
     got = mem.range_search(q, 0.2, scope=scopes)
     for (r, _, c), g in zip(R.range_from_scores(m, 0.2, tags=tags, scopes=scopes), got):
         assert g.count == c and g.rows.tolist() == r.tolist()
     # refusals of the C entry
     lo = torch.zeros(16, dtype=torch.int64, device="cuda")
-    plain = plain_memory(rows, "f16")
+    plain = range_memory(rows, "f16")
     for exact in (False, True):
-        assert raw_call(plain, q, 0.2, lo_hi=(lo, lo), exact=exact)[0] == _lib.VM_ERR_INVALID
-        assert raw_call(mem, q, 0.2, lo_hi=(lo, None), exact=exact)[0] == _lib.VM_ERR_INVALID
-        assert raw_call(mem, q, 0.2, lo_hi=(None, lo), exact=exact)[0] == _lib.VM_ERR_INVALID
+        assert raw_range(plain, q, 0.2, lo_hi=(lo, lo), exact=exact)[0] == _lib.VM_ERR_INVALID
+        assert raw_range(mem, q, 0.2, lo_hi=(lo, None), exact=exact)[0] == _lib.VM_ERR_INVALID
+        assert raw_range(mem, q, 0.2, lo_hi=(None, lo), exact=exact)[0] == _lib.VM_ERR_INVALID
     with pytest.raises(ValueError, match="tagged"):
         plain.range_search(q, 0.2, scope=ALL)
     # a plain and a grouped memory answer the unscoped call
-    check(plain, q, 0.2, whole, label="plain")
-    check(plain_memory(rows, "f16", grouped=True), q, 0.2, whole, label="grouped")
+    range_check(plain, q, 0.2, whole, label="plain")
+    range_check(range_memory(rows, "f16", grouped=True), q, 0.2, whole, label="grouped")
 
 
 # ---- 5. truncation and independence -------------------------------------------------------------------------------------
 def test_truncation_stride_and_independence_of_the_other_queries():
     from vidmem import _lib
     rows, q_all, matrix = dataset("bf16")
-    mem = plain_memory(rows, "bf16")
+    mem = range_memory(rows, "bf16")
     q = q_all[:49].contiguous()
     want = R.range_from_scores(matrix[:49], 0.2)
     full = np.array([c for _, _, c in want])
     assert full.max() > 1
     for max_hits in (0, 1, 7):                        # 0: a count-only call on NULL output pointers
-        counts, _ = check(mem, q, 0.2, want, max_hits=max_hits, label=f"max_hits={max_hits}")
+        counts, _ = range_check(mem, q, 0.2, want, max_hits=max_hits, label=f"max_hits={max_hits}")
         assert np.array_equal(counts, full)
-    check(mem, q, 0.2, want, stride=8, offset=3, label="stride 8 offset 3")
+    range_check(mem, q, 0.2, want, stride=8, offset=3, label="stride 8 offset 3")
     # one query alone returns the bits it returns as the 31st of 49
     width = int(full.max()) + 3
-    _, r49, s49, c49, x49 = raw_call(mem, q, 0.2, max_hits=width)
-    _, r1, s1, c1, x1 = raw_call(mem, q[30:31].contiguous(), 0.2, max_hits=width)
+    _, r49, s49, c49, x49 = raw_range(mem, q, 0.2, max_hits=width)
+    _, r1, s1, c1, x1 = raw_range(mem, q[30:31].contiguous(), 0.2, max_hits=width)
     assert c1[0] == c49[30] and x1[0] == x49[30]
     assert np.array_equal(r1[0], r49[30]) and np.array_equal(s1[0].view(np.int64), s49[30].view(np.int64))
     for exact in (False, True):
-        assert raw_call(mem, q, float("nan"), max_hits=4, exact=exact)[0] == _lib.VM_ERR_INVALID
+        assert raw_range(mem, q, float("nan"), max_hits=4, exact=exact)[0] == _lib.VM_ERR_INVALID
     with pytest.raises(ValueError, match="NaN"):
         mem.range_search(q, float("nan"))
 
@@ -286,7 +220,7 @@ def test_graph_capture_append_and_range_search_replayed():
         torch.cuda.synchronize()
         assert mem.sync() == 256 + (rep + 1) * B
         base, host_rows = mem.rows_host()
-        want = R.range_hits(_bits(q), host_rows, 0.2, tags=mem.tags_host(), scopes=windows, dtype="f16", base=base)
+        want = R.range_hits(bits(q), host_rows, 0.2, tags=mem.tags_host(), scopes=windows, dtype="f16", base=base)
         want_r, want_s, want_c = R.padded(want, H)
         assert np.array_equal(hits.counts.cpu().numpy(), want_c)
         assert np.array_equal(hits.rows.cpu().numpy(), want_r)

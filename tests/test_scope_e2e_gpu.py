@@ -10,23 +10,14 @@ import pytest
 import torch
 
 from tests import scope_ref as S
+from tests.search_checks import e2e_extractor
+from tests.support import Embedder, bits
 
 pytestmark = pytest.mark.gpu
 
 
-def _bits(t):
-    return t.contiguous().view(torch.int16).cpu().numpy().view(np.uint16)
-
-
 def _extractor(enc, tag_by, look_ahead, group_by=None):
-    from vidmem import config as C
-    from vidmem.extractor import FrameEmbeddingExtractor
-    cfg = C.from_dict({
-        "video": {"chunk_size_seconds": 1.0, "frames_per_chunk": 5},
-        "encoder": {"arch": "vit_b16_2l", "dtype": "f16", "seed": 3, "top_k": 4, "look_ahead_chunks": look_ahead},
-        "memory": {"capacity": 512, "tag_by": tag_by, "group_by": group_by},
-    })
-    return FrameEmbeddingExtractor(cfg, encoder=enc)
+    return e2e_extractor(enc, {"tag_by": tag_by, "group_by": group_by}, look_ahead)
 
 
 def _process(ex, clip, path, earlier=()):
@@ -43,14 +34,6 @@ def _process(ex, clip, path, earlier=()):
     out["metadata"].pop("run_id")
     out["metadata"]["config"]["memory"].pop("tag_by")
     return res, out["metadata"], rid
-
-
-class _Embedder:
-    def __init__(self, vec):
-        self.vec = vec
-
-    async def aembed_query(self, text):
-        return self.vec
 
 
 def _seconds(time_str):
@@ -93,11 +76,11 @@ def test_two_clips_one_tagged_memory(tmp_path, monkeypatch, look_ahead):
     stored = mem.rows_tensor()
     noise = torch.randn(stored.shape[1], device="cuda", generator=torch.Generator("cuda").manual_seed(1))
     q16 = (stored[7].float() + 0.02 * noise).to(torch.float16)
-    emb = _Embedder(q16.double().cpu().tolist())
+    emb = Embedder(q16.double().cpu().tolist())
     cfg = SimpleNamespace(top_k_chunks=6)
     vs = HipVectorSearch(mem, emb, cfg, min_score=-1.0, score_mode=_lib.VM_SCORE_RAW, scope=scope_of(1))
     got = asyncio.run(vs._vector_search_chunks(None, "q"))
-    want_r, want_s = S.scoped_topk(_bits(q16[None]), _bits(stored), tags, scope_of(1), 6, min_score=-1.0)
+    want_r, want_s = S.scoped_topk(bits(q16[None]), bits(stored), tags, scope_of(1), 6, min_score=-1.0)
     assert len(got) == 6 and all(c["id"].startswith(rids[1]) for c in got)
     assert [c["id"] for c in got] == [mem.id_of(int(r)) for r in want_r[0]]
     assert [c["score"] for c in got] == want_s[0].tolist()
@@ -108,7 +91,7 @@ def test_two_clips_one_tagged_memory(tmp_path, monkeypatch, look_ahead):
     win = scope_of(0, 2000, 4000)
     vs = HipVectorSearch(mem, emb, cfg, min_score=-1.0, score_mode=_lib.VM_SCORE_RAW, scope=win)
     got = asyncio.run(vs._vector_search_chunks(None, "q"))
-    want_r, want_s = S.scoped_topk(_bits(q16[None]), _bits(stored), tags, win, 6, min_score=-1.0)
+    want_r, want_s = S.scoped_topk(bits(q16[None]), bits(stored), tags, win, 6, min_score=-1.0)
     assert [c["id"] for c in got] == [mem.id_of(int(r)) for r in want_r[0]]
     assert [c["score"] for c in got] == want_s[0].tolist()
     assert len(got) == 6 and all(c["id"].startswith(rids[0]) for c in got)
@@ -117,7 +100,7 @@ def test_two_clips_one_tagged_memory(tmp_path, monkeypatch, look_ahead):
     # the pre-LLM similarity, scoped the same way; a wrong-length query lists the first in-scope rows
     sim = HipPreLLMSimilarity(mem, SimpleNamespace(top_k_chunk_with_batch_similarity=3), scope=scope_of(1))
     got = asyncio.run(sim._calculate_batch_similarities([q16, [0.0] * 5, stored[50]]))
-    want_r, want_s = S.scoped_topk(_bits(torch.stack([q16, stored[50]])), _bits(stored), tags, scope_of(1), 3)
+    want_r, want_s = S.scoped_topk(bits(torch.stack([q16, stored[50]])), bits(stored), tags, scope_of(1), 3)
     assert [i for i, _ in got[0]] == [mem.id_of(int(r)) for r in want_r[0]]
     assert [s for _, s in got[0]] == want_s[0].tolist()
     assert [i for i, _ in got[2]] == [mem.id_of(int(r)) for r in want_r[1]] and got[2][0][0] == mem.id_of(50)

@@ -1,7 +1,7 @@
 """GPU: scoped top-k (vm_topk_cosine_scoped, csrc/topk_scope.hip) against tests/scope_ref.py.
 
 Bar: rows, fp64 scores and padding bit-identical to the oracle, for the fast and the ``exact=True`` entry on every case.
-Certified condition: on the clustered data of tests/test_group_topk_gpu.py (a centre per cluster plus 0.05 noise, queries =
+Certified condition: on the clustered data of tests/support.py (a centre per cluster plus 0.05 noise, queries =
 stored in-scope rows plus 0.1 noise) every query must be answered by the fast path, flag 0.  The reference alone stays
 inside that condition: in fp64 on the rounded 16-bit values the smallest gap between the exact k-th and the (M+1)-th
 in-scope score was >= 9.2 x cert_eps(D) on set (i) (4,000 rows, clusters of 1 and 5 at k in {1, 10, 20}, of 16 at k in
@@ -13,44 +13,16 @@ import pytest
 import torch
 
 from tests import scope_ref as S
-from tests.test_group_topk_gpu import TD, _bits, clustered, queries_near
+from tests.support import ALL, MS, TD, bits, clustered, contiguous_tags, make_tag, mixed_scopes, queries_near, scope_of, tagged_memory
 
 pytestmark = pytest.mark.gpu
-
-ALL = (S.INT64_MIN, S.INT64_MAX)
-MS = 33  # milliseconds between the rows of one source
-
-
-def make_tag(source, ms):
-    return (int(source) << 40) | int(ms)
-
-
-def scope_of(source, t0=None, t1=None):
-    return make_tag(source, 0 if t0 is None else t0), make_tag(source, (1 << 40) - 1 if t1 is None else t1)
-
-
-def contiguous_tags(n, sources):
-    """n rows in `sources` contiguous videos of n / sources rows, MS apart."""
-    per = n // sources
-    i = np.arange(n, dtype=np.int64)
-    return ((i // per) << 40) | ((i % per) * MS)
-
-
-def tagged_memory(rows, tags, dtype, capacity=None, ring=False, step=65536):
-    from vidmem.memory import EmbeddingMemory
-    mem = EmbeddingMemory(capacity or max(rows.shape[0], 16), rows.shape[1], dtype, ring=ring, tagged=True)
-    tags = torch.as_tensor(np.asarray(tags, dtype=np.int64), device=rows.device)
-    step = min(step, mem.capacity)
-    for c0 in range(0, rows.shape[0], step):
-        mem.append(rows[c0:c0 + step], tag=tags[c0:c0 + step])
-    return mem
 
 
 def check(mem, q, k, dtype, scopes, min_score=None, score_mode=0, certified=False, label=""):
     """Fast and exact entry against the oracle.  certified=True: the fast path answered every query (flag 0)."""
     base, host_rows = mem.rows_host()
     tags = mem.tags_host()
-    want_r, want_s = S.scoped_topk(_bits(q), host_rows, tags, scopes, k, dtype=dtype, score_mode=score_mode,
+    want_r, want_s = S.scoped_topk(bits(q), host_rows, tags, scopes, k, dtype=dtype, score_mode=score_mode,
                                    min_score=min_score, base=base)
     out = None
     for exact in (False, True):
@@ -74,15 +46,6 @@ def queries_in_scope(rows, tags, Q, seed, dtype):
     q = rows[pick].float() + 0.1 * torch.randn(Q, rows.shape[1], generator=g, device=rows.device)
     scopes = [scope_of(int(tags[int(p)]) >> 40) for p in pick.cpu()]
     return q.to(TD[dtype]), scopes
-
-
-def mixed_scopes(tags, Q, k):
-    """At least 5 distinct scopes in one call: no row at all, lo > hi, one row, fewer than k rows, a sub-window of a
-    video, a whole video, everything."""
-    one = int(tags[len(tags) // 3])
-    pool = [scope_of(100), (10, 5), (one, one), scope_of(5, 0, MS * max(k - 2, 0)), scope_of(3, MS * 100, MS * 300),
-            scope_of(6), ALL]
-    return [pool[i % len(pool)] for i in range(Q)]
 
 
 # ---- 1. whole-memory scope = the row search -------------------------------------------------------------------
@@ -297,7 +260,7 @@ def test_graph_capture_append_and_scoped_search_replayed_with_new_windows():
         torch.cuda.synchronize()
         assert mem.sync() == 256 + (rep + 1) * B
         base, host_rows = mem.rows_host()
-        want_r, want_s = S.scoped_topk(_bits(q), host_rows, mem.tags_host(), windows, k, dtype="f16", base=base)
+        want_r, want_s = S.scoped_topk(bits(q), host_rows, mem.tags_host(), windows, k, dtype="f16", base=base)
         assert np.array_equal(out_r.cpu().numpy(), want_r)
         assert np.array_equal(out_s.cpu().numpy().view(np.int64), want_s.view(np.int64))
         assert (out_r[0] >= 256 + rep * B).all() and (out_r[3] == -1).all()

@@ -22,14 +22,10 @@ from oracle import cref
 from tests import fold_ref as FR
 from tests import mask_ref as MR
 from tests import mix_ref as XR
-from tests.test_fold_gpu import check as fold_check
-from tests.test_group_topk_gpu import _bits, clustered, queries_near
-from tests.test_mask_gpu import plain_memory
-from tests.test_mix_gpu import check as mix_check
+from tests.search_checks import fold_check, mix_check
+from tests.support import TD, bits, clustered, plain_memory, queries_near
 
 pytestmark = pytest.mark.gpu
-
-TD = {"f16": torch.float16, "bf16": torch.bfloat16}
 
 
 # ---- 1. overflow ----------------------------------------------------------------------------------------------------
@@ -43,14 +39,14 @@ def test_overflow_is_redone_for_the_mixed_and_the_fold_search():
     base, host_rows = mem.rows_host()
     assert base == 0 and host_rows.shape[0] == 8192 + 300
     w = [1.0, -0.5, 0.25]
-    want = XR.mix_topk(_bits(terms), [w], host_rows, None, 5)
+    want = XR.mix_topk(bits(terms), [w], host_rows, None, 5)
     before = mem.mix_uncertified_count
     got_r, got_s, flags = mix_check(mem, terms, w, 5, "f16", want=want, label="8,492 equal rows")
     assert flags.tolist() == [_lib.VM_FLAG_OVERFLOW] and got_r.tolist() == [[0, 1, 2, 3, 4]]
     assert mem.mix_uncertified_count == before + 1
     same = terms[:, :1].expand(1, 3, -1).contiguous()                          # one term three times: every product ties
     for op in FR.OPS:
-        want = FR.fold_topk(_bits(same), [[1.0] * 3], host_rows, None, 5, op)
+        want = FR.fold_topk(bits(same), [[1.0] * 3], host_rows, None, 5, op)
         assert (want[2] == 0).all()                                            # ... and the first term wins
         before = mem.fold_uncertified_count
         got_r, got_s, flags = fold_check(mem, same, [1.0] * 3, 5, op, "f16", want=want, label="8,492 equal rows")
@@ -98,7 +94,7 @@ def big_case(dtype, J):
     keep1 = (set(live[live % 2 == 0]) - set(PLANTED[1])) | {134, 150}
     masks = np.stack([MR.pack_rows(sorted(keep0), CAP), MR.pack_rows(sorted(keep1), CAP)])
     sels = {"none": np.ones((C, CAP), dtype=bool), "masks": MR.selection(masks, None, C, BASE, CAP, CAP)}
-    e = cref.cosine_matrix(_bits(terms).reshape(C * J, D), _bits(rows[BASE:]), dtype=dtype).reshape(C, J, CAP)
+    e = cref.cosine_matrix(bits(terms).reshape(C * J, D), bits(rows[BASE:]), dtype=dtype).reshape(C, J, CAP)
     wm = [MIX_W[j % 3] for j in range(J)]
     wf = [FOLD_W[j % 4] for j in range(J)]
     W = np.stack([XR.mix_scores_loop(e[c], wm) for c in range(C)])
@@ -135,7 +131,7 @@ def test_terms_that_need_more_dynamic_lds_than_a_launch_gets_by_default(dtype, J
     rows, terms, masks, want = big_case(dtype, J)
     assert J * D * 2 + 16384 > 65536
     mem = plain_memory(rows.cuda(), dtype, capacity=CAP, ring=True, step=19)
-    assert mem.rows_host()[0] == BASE and np.array_equal(mem.rows_host()[1], _bits(rows[BASE:]))
+    assert mem.rows_host()[0] == BASE and np.array_equal(mem.rows_host()[1], bits(rows[BASE:]))
     t = terms.cuda()
     for name in ("none", "masks"):
         m = None if name == "none" else masks

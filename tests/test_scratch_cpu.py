@@ -4,16 +4,7 @@ memory operation shares."""
 import pytest
 import torch
 
-from tests.host_memory import host_memory
-
-
-class SizingLibrary:
-    """Every ``vm_*_workspace_bytes`` entry: 1,000 bytes plus 64 per unit of its arguments.  Nothing else exists."""
-
-    def __getattr__(self, name):
-        if not name.endswith("_workspace_bytes"):
-            raise AssertionError(f"library call {name}: the owner rule only sizes")
-        return lambda handle, *args: 1000 + 64 * sum(int(a) for a in args)
+from tests.host_memory import SizingLibrary, host_memory, scratch_buffers
 
 
 def _memory(capacity=16):
@@ -40,24 +31,20 @@ def _kinds():
 KINDS = ["topk", "grouped", "scoped", "grouped_scoped", "clip", "novelty", "range", "events", "summary", "erase"]
 
 
-def _buffers(scratch):
-    return {name: (t.data_ptr(), t.numel()) for name, t in vars(scratch).items() if isinstance(t, torch.Tensor)}
-
-
 @pytest.mark.parametrize("name", KINDS)
 def test_own_scratch_is_kept_while_it_fits_and_replaced_to_grow(name):
     kind, prepare, shape, larger = _kinds()[name]
     mem = _memory()
     first = getattr(mem, prepare)(*shape)
     assert isinstance(first, kind) and first.fits(mem, *shape)
-    before = _buffers(first)
+    before = scratch_buffers(first)
     assert "ws" in before and before["ws"][1] >= 256
     assert getattr(mem, prepare)(*shape) is first                       # it fits: the same object
     assert mem._resolve(kind, None, *shape) is first
     grown = getattr(mem, prepare)(*larger)
     assert grown is not first and isinstance(grown, kind) and grown.fits(mem, *larger)
-    assert _buffers(first) == before                                    # replaced, never resized in place
-    assert set(_buffers(grown)) == set(before)
+    assert scratch_buffers(first) == before                                    # replaced, never resized in place
+    assert set(scratch_buffers(grown)) == set(before)
     assert getattr(mem, prepare)(*larger) is grown
 
 
@@ -66,15 +53,15 @@ def test_caller_owned_scratch_must_fit(name):
     kind, prepare, shape, larger = _kinds()[name]
     mem = _memory()
     own = getattr(mem, prepare)(*shape)
-    before = _buffers(own)
+    before = scratch_buffers(own)
     if name == "erase":       # any segment size serves an erase call: too small = made for a smaller memory
         small, call = kind.for_(_memory(capacity=8)), ()
     else:
         small, call = kind.for_(mem, *shape), larger
-    theirs = _buffers(small)
+    theirs = scratch_buffers(small)
     with pytest.raises(ValueError, match="too small"):
         mem._resolve(kind, small, *call)
-    assert getattr(mem, prepare)(*shape) is own and _buffers(own) == before and _buffers(small) == theirs
+    assert getattr(mem, prepare)(*shape) is own and scratch_buffers(own) == before and scratch_buffers(small) == theirs
     fitting = kind.for_(mem, *larger)
     assert mem._resolve(kind, fitting, *call) is fitting                # a caller-owned one that fits is used as it is
     assert getattr(mem, prepare)(*shape) is own
@@ -102,7 +89,7 @@ def test_buffers_keep_their_names_types_and_fills():
     for kind, (shape, buffers) in want.items():
         s = kind.for_(mem, *shape)
         assert s.ws.dtype == torch.uint8 and s.ws.numel() == 1000 + 64 * sum(s._sized_by(*s.shape))
-        assert set(_buffers(s)) == set(buffers) | {"ws"}
+        assert set(scratch_buffers(s)) == set(buffers) | {"ws"}
         for name, (dtype, fill) in buffers.items():
             t = getattr(s, name)
             assert t.dtype == dtype and (fill is None or (t == fill).all()), (kind.__name__, name)
@@ -118,11 +105,11 @@ def test_topk_fit_returns_a_new_object_and_carries_the_counter():
     mem = _memory()
     first = TopkScratch.for_(mem, 4, 10)
     first.uncert.fill_(7)
-    before = _buffers(first)
+    before = scratch_buffers(first)
     assert first.fit(mem, 4, 10) is first and first.fit(mem, 2, 5) is first
     grown = first.fit(mem, 64, 32)
     assert grown is not first and grown.fits(mem, 64, 32) and grown.fits(mem, 4, 10)
-    assert grown.uncert.item() == 7 and first.uncert.item() == 7 and _buffers(first) == before
+    assert grown.uncert.item() == 7 and first.uncert.item() == 7 and scratch_buffers(first) == before
     assert grown.flags.numel() >= 64 and grown.ws.numel() >= first.ws.numel()
     # the memory's own scratch grows the same way: uncertified_count survives the growth
     assert mem.uncertified_count == 0

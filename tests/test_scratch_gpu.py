@@ -16,8 +16,7 @@ import torch
 from tests import group_ref as G
 from tests import group_scope_ref as GS
 from tests import scope_ref as S
-from tests.test_group_topk_gpu import _bits, clustered, queries_near
-from tests.test_scope_topk_gpu import MS, make_tag, scope_of
+from tests.support import MS, bits, clustered, make_tag, queries_near, scope_of
 
 pytestmark = pytest.mark.gpu
 
@@ -48,12 +47,12 @@ def oracle(name, mem, q, k, scopes):
     """-> the arrays in the order the search returns them: scores, rows (, keys)."""
     base, host_rows = mem.rows_host()
     if name == "topk_scoped":
-        r, s = S.scoped_topk(_bits(q), host_rows, mem.tags_host(), scopes, k, dtype="f16", base=base)
+        r, s = S.scoped_topk(bits(q), host_rows, mem.tags_host(), scopes, k, dtype="f16", base=base)
         return s, r
     if name == "topk_grouped":
-        r, s, kk = G.grouped_topk(_bits(q), host_rows, mem.group_keys_host(), k, dtype="f16", base=base)
+        r, s, kk = G.grouped_topk(bits(q), host_rows, mem.group_keys_host(), k, dtype="f16", base=base)
     else:
-        r, s, kk = GS.group_scoped_topk(_bits(q), host_rows, mem.group_keys_host(), mem.tags_host(), scopes, k,
+        r, s, kk = GS.group_scoped_topk(bits(q), host_rows, mem.group_keys_host(), mem.tags_host(), scopes, k,
                                         dtype="f16", base=base)
     return s, r, kk
 

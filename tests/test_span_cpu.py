@@ -11,8 +11,7 @@ import torch
 
 from tests import mask_ref as MR
 from tests import span_ref as SR
-from tests.host_memory import host_memory
-from tests.test_scratch_cpu import SizingLibrary, _buffers
+from tests.host_memory import host_memory, owner_rule_holds
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MIN, MAX = SR.INT64_MIN, SR.INT64_MAX
@@ -101,22 +100,10 @@ def test_links_loop_against_both_statements():
     assert np.array_equal(lr, full[40:50])
 
 
-# ---- the scratch owner rule for the new kind (tests/test_scratch_cpu.py's stand-in sizing library) -------------------
+# ---- the scratch owner rule for the new kind (tests/host_memory.py's stand-in sizing library) -------------------
 def test_span_scratch_follows_the_owner_rule():
     from vidmem import memory as M
-    mem = host_memory(capacity=16, library=SizingLibrary())
-    first = mem.prepare_topk_span(4, 10)
-    assert isinstance(first, M.SpanTopkScratch) and first.fits(mem, 4, 10)
-    assert first.ws.numel() == 1000 + 64 * 14 and first.flags.dtype == torch.int32 and (first.flags == 0).all()
-    assert set(_buffers(first)) == {"ws", "flags"}
-    before = _buffers(first)
-    assert mem.prepare_topk_span(4, 10) is first and mem._resolve(M.SpanTopkScratch, None, 2, 5) is first
-    grown = mem.prepare_topk_span(64, 32)
-    assert grown is not first and grown.fits(mem, 64, 32) and _buffers(first) == before   # replaced, never resized
-    with pytest.raises(ValueError, match="too small"):
-        mem._resolve(M.SpanTopkScratch, M.SpanTopkScratch.for_(mem, 4, 10), 64, 32)
-    theirs = M.SpanTopkScratch.for_(mem, 64, 32)
-    assert mem._resolve(M.SpanTopkScratch, theirs, 64, 32) is theirs
+    mem = owner_rule_holds("SpanTopkScratch", "prepare_topk_span")
     assert mem.last_span_flags is None and mem.span_uncertified_count == 0
     assert M.SpanTopkScratch.workspaces == (("ws", "vm_topk_span_workspace_bytes"),)
 

@@ -2,7 +2,7 @@
 tests/span_ref.py.
 
 Bar: rows, fp64 score bits and padding identical to statement (A) of the oracle, for the fast and the ``exact=True``
-entry.  The scan test runs the shapes at which the shared tile scan can go wrong (tests/test_tile_scan_gpu.py's data) under
+entry.  The scan test runs the shapes at which the shared tile scan can go wrong (tests/tile_scan_data.py) under
 every span set of tests/span_ref.py and demands flag 0 of every query: the redo would hide a broken scan.  That the data
 allows it is asserted from the oracle's scores before any search, and proven without a GPU in tests/test_span_cpu.py; so
 is the same condition of the link test.
@@ -13,10 +13,9 @@ import torch
 
 from tests import mask_ref as MR
 from tests import span_ref as SR
-from tests.test_group_topk_gpu import _bits, clustered, grouped_memory, queries_near
-from tests.test_mask_gpu import _planted, plain_memory
-from tests.test_scope_topk_gpu import tagged_memory
-from tests.test_tile_scan_gpu import dataset
+from tests.support import (bits, check_entries, clustered, grouped_memory, plain_memory, planted_duplicates, queries_near,
+                           scan_memory, tagged_memory)
+from tests.tile_scan_data import dataset
 
 pytestmark = pytest.mark.gpu
 
@@ -30,25 +29,18 @@ def _bits64(a):
 def want_of(mem, q, k, dtype, spans, **kw):
     """Statement (A) for the memory as it is."""
     base, host_rows = mem.rows_host()
-    return SR.span_topk(_bits(q), host_rows, spans, k, dtype=dtype, base=base, **kw)
+    return SR.span_topk(bits(q), host_rows, spans, k, dtype=dtype, base=base, **kw)
 
 
 def check(mem, q, k, dtype, spans, certified=False, label="", stride=(1, 0), **kw):
     """Fast and exact entry against (A).  certified=True: the fast path answered every query (flag 0)."""
     want_r, want_s = want_of(mem, q, k, dtype, spans, **kw)
     want_r = np.where(want_r >= 0, want_r * stride[0] + stride[1], -1)
-    out = None
-    for exact in (False, True):
+
+    def call(exact):
         s, r = mem.topk_span(q, k, spans, exact=exact, stride=stride, **kw)
-        got_r, got_s = r.cpu().numpy(), s.cpu().numpy()
-        if not exact:
-            flags = mem.last_span_flags[:q.shape[0]].cpu().numpy()
-            out = (got_r, got_s, flags)
-        assert np.array_equal(got_r, want_r), (label, exact, np.argwhere(got_r != want_r)[:5], got_r[:2], want_r[:2])
-        assert np.array_equal(got_s.view(np.int64), want_s.view(np.int64)), f"{label}: scores differ (bit-exact) exact={exact}"
-        if certified and not exact:
-            assert (flags == 0).all(), f"{label}: the scan left queries to the redo: {flags}"
-    return out
+        return r, s
+    return check_entries(call, lambda: mem.last_span_flags[:q.shape[0]], (want_r, want_s), certified or None, label)
 
 
 # ---- 1. the scan ------------------------------------------------------------------------------------------------------
@@ -56,12 +48,7 @@ def check(mem, q, k, dtype, spans, certified=False, label="", stride=(1, 0), **k
 @pytest.mark.parametrize("D,dtype", [(128, "f16"), (128, "bf16"), (384, "f16"), (384, "bf16")])
 def test_scan(D, dtype, shape):
     SR.scan_precondition(D, dtype, shape)            # from oracle scores, before any search
-    rows, q_all, base, live = dataset(D, dtype, shape)
-    hrows, hq, hbase, _ = MR.host_dataset(D, dtype, shape)
-    assert hbase == base and np.array_equal(_bits(rows), _bits(hrows)) and np.array_equal(_bits(q_all), _bits(hq))
-    total, cap = MR.SHAPES[shape]
-    mem = plain_memory(rows, dtype, capacity=cap, ring=cap is not None, step=19)
-    assert mem.rows_host()[0] == base
+    mem, q_all, base, live, total, cap = scan_memory(D, dtype, shape)
     n = live.shape[1]
     for Q in MR.QS:
         q = q_all[:Q].contiguous()
@@ -118,7 +105,7 @@ def test_open_span_equals_topk_and_spans_equal_scopes_and_masks():
 # ---- 3. the redo --------------------------------------------------------------------------------------------------------
 def test_more_duplicates_than_slack_inside_the_span_is_flagged_and_redone():
     from vidmem import _lib
-    rows, planted, dup = _planted()
+    rows, planted, dup = planted_duplicates()
     mem = plain_memory(rows, "f16")
     before = mem.span_uncertified_count
     got_r, _, flags = check(mem, planted[None].contiguous(), 10, "f16", (1000, 1999), label="ties inside")
@@ -127,11 +114,11 @@ def test_more_duplicates_than_slack_inside_the_span_is_flagged_and_redone():
 
 
 def test_the_same_duplicates_outside_the_span_leave_flag_zero():
-    rows, planted, dup = _planted()
+    rows, planted, dup = planted_duplicates()
     mem = plain_memory(rows, "f16")
     q = planted[None].contiguous()
     assert min(dup) >= 1010 and max(dup) < 2000
-    exact = np.sort(MR.cref.cosine_matrix(_bits(q), mem.rows_host()[1])[0][2000:3000])[::-1]
+    exact = np.sort(MR.cref.cosine_matrix(bits(q), mem.rows_host()[1])[0][2000:3000])[::-1]
     assert exact[9] - exact[18] > 4 * MR.cert_eps(768), "precondition: rank k and rank M + 1 too close in the oracle"
     before = mem.span_uncertified_count
     got_r, _, _ = check(mem, q, 10, "f16", (2000, None), certified=True, label="ties outside")

@@ -4,12 +4,9 @@ import pytest
 import torch
 
 from oracle import cref
+from tests.support import bits
 
 pytestmark = pytest.mark.gpu
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int16).cpu().numpy().view(np.uint16)
 
 
 def test_snapshot_restore_roundtrip(tmp_path):
@@ -53,7 +50,7 @@ def test_streaming_graph_matches_eager_and_oracle():
         assert torch.equal(emb, want_emb)
         allrows = torch.cat(hist)
         lo = max(0, allrows.shape[0] - cap)
-        want_r, want_s = cref.cosine_topk(_bits(emb), _bits(allrows[lo:]), k, dtype="f16")
+        want_r, want_s = cref.cosine_topk(bits(emb), bits(allrows[lo:]), k, dtype="f16")
         want_r = np.where(want_r >= 0, want_r + lo, -1)
         assert sess.uncertified_last_push == 0
         assert np.array_equal(rows.cpu().numpy(), want_r)
@@ -66,7 +63,7 @@ def test_streaming_graph_matches_eager_and_oracle():
     allrows = torch.cat(hist)
     q = allrows[[45, 103]]
     s_e, r_e = mem.topk(q, 3, exact=True)
-    want_r, want_s = cref.cosine_topk(_bits(q), _bits(allrows[-cap:]), 3, dtype="f16")
+    want_r, want_s = cref.cosine_topk(bits(q), bits(allrows[-cap:]), 3, dtype="f16")
     assert np.array_equal(r_e.cpu().numpy(), want_r + (allrows.shape[0] - cap))
     assert np.array_equal(s_e.cpu().numpy(), want_s)
     first = mem.append(seed_rows[:2], ids=["a", "b"])
@@ -96,7 +93,7 @@ def test_streaming_redoes_uncertified_queries_inside_the_replay():
         emb, scores, rows = sess.push(frames)
         counts.append(sess.uncertified_last_push)
         allrows = torch.cat(hist)
-        want_r, want_s = cref.cosine_topk(_bits(emb), _bits(allrows), k, dtype="f16")
+        want_r, want_s = cref.cosine_topk(bits(emb), bits(allrows), k, dtype="f16")
         assert np.array_equal(rows.cpu().numpy(), want_r), step
         assert np.array_equal(scores.cpu().numpy(), want_s), step
         hist.append(emb.clone())
@@ -130,6 +127,6 @@ def test_session_survives_larger_eager_calls_on_the_same_encoder_and_memory():
     torch.cuda.synchronize()
     assert torch.equal(emb1, enc.embed_frames(f1))
     allrows = torch.cat([seed_rows.cuda(), emb0])
-    want_r, want_s = cref.cosine_topk(_bits(emb1), _bits(allrows), k, dtype="f16")
+    want_r, want_s = cref.cosine_topk(bits(emb1), bits(allrows), k, dtype="f16")
     assert np.array_equal(r1.cpu().numpy(), want_r) and np.array_equal(s1.cpu().numpy(), want_s)
     del junk

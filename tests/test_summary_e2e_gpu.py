@@ -10,10 +10,10 @@ pytestmark = pytest.mark.gpu
 
 
 def test_consolidate_into_a_summary_memory_and_search_it():
-    from tests.test_group_topk_gpu import _sizes, clustered
+    from tests.support import clustered, group_sizes
     from vidmem.memory import EmbeddingMemory, make_tag, scope_of
     D, dtype = 768, "f16"
-    sizes = _sizes(40, "ragged", 8)
+    sizes = group_sizes(40, "ragged", 8)
     rows, gid = clustered(sizes, D, dtype, seed=41, device="cpu")
     n = rows.shape[0]
     starts = np.concatenate([[0], np.cumsum(sizes)])

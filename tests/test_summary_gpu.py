@@ -13,7 +13,8 @@ import torch
 
 from tests import events_ref as E
 from tests import summary_ref as S
-from tests.test_events_gpu import RING_CAP, TD, _p, _t, raw_regroup
+from tests.search_checks import RING_CAP, ptr, raw_regroup
+from tests.support import from_bits, same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -28,11 +29,11 @@ def grouped_memory(bits, keys, dtype, capacity=None, ring=False, tags=None, step
     mem = EmbeddingMemory(capacity or max(n, 1), bits.shape[1], dtype, ring=ring, grouped=True, tagged=tags is not None)
     step = min(step, mem.capacity)
     for c0 in range(0, n, step):
-        rows = _t(bits[c0:c0 + step], dtype)
+        rows = from_bits(bits[c0:c0 + step], dtype)
         if keys is None:
             first = C.c_int64(0)
             from vidmem import _lib
-            mem.ctx.check(mem.L.vm_memory_append(mem.handle, _p(rows), rows.shape[0], C.byref(first),
+            mem.ctx.check(mem.L.vm_memory_append(mem.handle, ptr(rows), rows.shape[0], C.byref(first),
                                                  _lib.current_stream_ptr()))
             mem.ids.extend([None] * rows.shape[0])
             mem.meta.extend([None] * rows.shape[0])
@@ -71,10 +72,10 @@ class Raw:
         if first_group is not None:
             frm = first_group if isinstance(first_group, torch.Tensor) else \
                 torch.tensor([int(first_group)], dtype=torch.int64).cuda()
-        arg = lambda name: _p(None if name in skip else buf[name])
-        self.rc = mem.L.vm_memory_summaries(mem.handle, _p(frm), int(max_groups), arg("centroids"), arg("first_rows"),
-                                            arg("n_rows"), arg("keys"), arg("key_rows"), arg("key_scores"), _p(cnt),
-                                            _p(ws), need if ws_bytes is None else ws_bytes, _lib.current_stream_ptr())
+        arg = lambda name: ptr(None if name in skip else buf[name])
+        self.rc = mem.L.vm_memory_summaries(mem.handle, ptr(frm), int(max_groups), arg("centroids"), arg("first_rows"),
+                                            arg("n_rows"), arg("keys"), arg("key_rows"), arg("key_scores"), ptr(cnt),
+                                            ptr(ws), need if ws_bytes is None else ws_bytes, _lib.current_stream_ptr())
         torch.cuda.synchronize()
         self.count = int(cnt.item())
         self.max_groups = max_groups
@@ -92,10 +93,6 @@ class Raw:
             if not (a == sent).all():
                 return False
         return True
-
-
-def same_bits(a, b):
-    return np.array_equal(np.asarray(a, np.float64).view(np.int64), np.asarray(b, np.float64).view(np.int64))
 
 
 def check(mem, want: S.Summary, first_group=None, max_groups=None, skip=(), label=""):
@@ -289,9 +286,9 @@ def test_four_thousand_groups_of_one_row():
 def test_refusals():
     from vidmem import _lib
     from vidmem.memory import EmbeddingMemory
-    from tests.test_events_gpu import memory
+    from tests.search_checks import raw_append_memory
     dtype, bits, _, _ = E.dataset("f16_128")
-    plain = memory(bits[:64], dtype)                          # not grouped
+    plain = raw_append_memory(bits[:64], dtype)                          # not grouped
     got = Raw(plain, 0, 8)
     assert got.rc == _lib.VM_ERR_INVALID and got.count == SENT_I and got.untouched(start=0)
     with pytest.raises(ValueError, match="grouped"):
@@ -322,9 +319,9 @@ def test_graph_capture_append_and_summaries_replayed():
     keys_all = scene_keys(name)
     B, H = 128, 64
     mem = EmbeddingMemory(1024, 768, dtype, grouped=True)
-    mem.append(_t(bits_ro[:256], dtype), group=torch.from_numpy(keys_all[:256]))
+    mem.append(from_bits(bits_ro[:256], dtype), group=torch.from_numpy(keys_all[:256]))
     scratch = mem.prepare_summaries(H)
-    src = _t(bits_ro[256:256 + B], dtype).clone()
+    src = from_bits(bits_ro[256:256 + B], dtype).clone()
     src_keys = torch.from_numpy(keys_all[256:256 + B]).cuda()
     frm = torch.zeros(1, dtype=torch.int64, device="cuda")
     torch.cuda.synchronize()
@@ -340,7 +337,7 @@ def test_graph_capture_append_and_summaries_replayed():
     assert len(mem) == 256
     for rep in range(3):
         n = 256 + (rep + 1) * B
-        src.copy_(_t(bits_ro[n - B:n], dtype))
+        src.copy_(from_bits(bits_ro[n - B:n], dtype))
         src_keys.copy_(torch.from_numpy(keys_all[n - B:n]))
         frm.fill_(rep * 5)         # the window pages between replays
         graph.replay()

@@ -13,63 +13,19 @@ scan, so the fast entries must also answer alone: every per-query flag 0 (groupe
 best and 10th exact in-scope score (group maxima for grouped) lie more than 4 x cert_eps(D) apart, and no exact score
 lies within 4 x cert_eps(D) of the range threshold.  The certificate needs 2 x.
 """
-import functools
-
 import numpy as np
 import pytest
-import torch
 
 from tests import group_ref as G
 from tests import range_ref as R
 from tests import scope_ref as S
-from tests.test_group_topk_gpu import _bits, clustered, grouped_memory, queries_near
-from tests.test_range_gpu import check as range_check
-from tests.test_scope_topk_gpu import ALL, make_tag, tagged_memory
+from tests.search_checks import range_check
+from tests.support import grouped_memory, tagged_memory
+from tests.tile_scan_data import K, QS, SHAPES, dataset, gap_ok, scope_sets, tags_of
 
 pytestmark = pytest.mark.gpu
 
-K, M1 = 1, 10                       # k, and the rank M + 1 = k + 8 + 1 that bounds the rows not re-scored
 TAU = 0.29                          # range threshold: between the cross-cluster and the in-cluster scores
-QS = (1, 16, 17, 33)
-SHAPES = {"n17": (17, None), "n33": (33, None), "n47": (47, None), "ring40": (57, 40)}   # rows appended, ring capacity
-CLUSTERS = (5, 3, 4, 1, 2)          # cluster sizes, repeated: at most 5 rows resemble one another
-
-
-@functools.lru_cache(maxsize=None)
-def dataset(D, dtype, shape):
-    """(rows, queries, base, oracle score matrix [33, live rows]) of one shape, made once on the host."""
-    total, cap = SHAPES[shape]
-    sizes, left = [], total
-    while left:
-        sizes.append(min(CLUSTERS[len(sizes) % len(CLUSTERS)], left))
-        left -= sizes[-1]
-    rows, _ = clustered(sizes, D, dtype, seed=D + total, device="cpu")
-    base = total - cap if cap else 0
-    q = queries_near(rows[base:].contiguous(), max(QS), D + total + 1, dtype)
-    live = R.cref.cosine_matrix(_bits(q), _bits(rows[base:]), dtype=dtype)
-    return rows.cuda(), q.cuda(), base, live
-
-
-def tags_of(total):
-    """Two sources interleaved row by row: tag = (row id % 2) << 40 | row id."""
-    r = np.arange(total, dtype=np.int64)
-    return ((r % 2) << 40) | r
-
-
-def scope_sets(Q, base, cap):
-    """name -> Q scopes.  `first_tile`: source 0's rows of physical slots 0 .. 15 - every other tile has no in-scope
-    row and takes the skip path."""
-    r0 = cap if cap else 0          # the row id in physical slot 0 (a ring of capacity cap after cap + 17 rows: cap)
-    return {"all": [ALL] * Q,
-            "half_per_query": [(make_tag(i % 2, 0), make_tag(i % 2, (1 << 40) - 1)) for i in range(Q)],
-            "one_empty": [(10, 5) if i == Q // 2 else ALL for i in range(Q)],
-            "first_tile": [(make_tag(0, r0), make_tag(0, r0 + 15))] * Q}
-
-
-def gap_ok(best_first, D):
-    """best_first: one query's exact scores, descending.  True when rank k and rank M + 1 are more than 4 x cert_eps
-    apart, or when there is no rank M + 1 (everything is re-scored exactly)."""
-    return best_first.size < M1 or best_first[K - 1] - best_first[M1 - 1] > 4 * R.cert_eps(D)
 
 
 @pytest.mark.parametrize("shape", list(SHAPES))

@@ -26,6 +26,7 @@ from tests import domain_ref as DR
 from tests import group_ref as G
 from tests import range_ref as R
 from tests import scope_ref as S
+from tests import support
 from tests import topk_plan as TP
 from tests.topk_ref import oracle_rows_parallel
 
@@ -94,18 +95,6 @@ ROW_CASES = [("list-QT1", "small", 5, 5, "list"), ("list-QT2", "small", 33, 12, 
              ("emit-NG2", "large", 200, 10, "cascade"), ("gscan", "large", None, 10, "cascade")]
 
 
-def _launches(mem, fn):
-    ctx = mem.ctx
-    ctx.profile_mask(None)
-    ctx.profile_enable(256)
-    try:
-        out = fn()
-        prof = ctx.profile_read()
-    finally:
-        ctx.profile_enable(0)
-    return out, {c: prof[c][1] for c in ("topk_scan", "topk_finalize")}
-
-
 @pytest.mark.parametrize("case", ROW_CASES, ids=lambda c: c[0])
 @pytest.mark.parametrize("name", CLASS_NAMES)
 def test_row_search(name, case):
@@ -128,7 +117,7 @@ def test_row_search(name, case):
     assert q_exact == cls.exact or cls.rnorm_plants
     es, er = _np(*mem.topk(qs, k, exact=True))
     scratch = TopkScratch.for_(mem, Q, k)
-    (s0, r0), launches = _launches(mem, lambda: mem.topk(qs, k, redo=False, scratch=scratch))
+    (s0, r0), launches = support.launches(mem, lambda: mem.topk(qs, k, redo=False, scratch=scratch), ("topk_scan", "topk_finalize"))
     assert launches == plan.launches, (path, launches, plan.launches)
     flags = scratch.flags[:Q].cpu().numpy()
     s0, r0 = _np(s0, r0)
@@ -160,7 +149,7 @@ def test_row_search(name, case):
 
 # ---- grouped, scoped, range: n = 4,099 ------------------------------------------------------------------------------
 def _grouped(rows, dtype):
-    from tests.test_group_topk_gpu import grouped_memory
+    from tests.support import grouped_memory
     sizes = [5] * 819 + [4]
     return grouped_memory(rows, sizes, dtype)
 
@@ -199,7 +188,7 @@ def test_grouped(name):
 
 @pytest.mark.parametrize("name", CLASS_NAMES)
 def test_scoped(name):
-    from tests.test_scope_topk_gpu import contiguous_tags, mixed_scopes, tagged_memory
+    from tests.support import contiguous_tags, mixed_scopes, tagged_memory
     Q, k = 16, 10
     cls = DR.CLASSES[name]
     ds, _, live = dataset(name, "small")
@@ -233,8 +222,8 @@ def test_scoped(name):
 
 @pytest.mark.parametrize("name", CLASS_NAMES)
 def test_range(name):
-    from tests.test_group_topk_gpu import clustered
-    from tests.test_range_gpu import plain_memory, raw_call
+    from tests.support import clustered
+    from tests.search_checks import range_memory, raw_range
     Q = 17
     cls = DR.CLASSES[name]
     rows, _ = clustered([5] * 819 + [4], D, cls.dtype, seed=5)
@@ -242,7 +231,7 @@ def test_range(name):
     assert ds.rows_exact == cls.exact or cls.rnorm_plants
     qb, qs, q_exact, _, zero = ds.queries(Q, seed=79, near=True)
     assert q_exact == cls.exact or cls.rnorm_plants
-    mem = plain_memory(ds.rows, cls.dtype)
+    mem = range_memory(ds.rows, cls.dtype)
     matrix = R.cref.cosine_matrix(DR.bits(qs), DR.bits(ds.rows), dtype=cls.dtype)
     problems = []
     for tau in (0.2, -1.0):
@@ -251,7 +240,7 @@ def test_range(name):
         want_r, want_s, want_c = R.padded(want, width)
         got = {}
         for exact in (False, True):
-            rc, r, s, c, resc = raw_call(mem, qs, tau, max_hits=width, exact=exact)
+            rc, r, s, c, resc = raw_range(mem, qs, tau, max_hits=width, exact=exact)
             assert rc == 0, (rc, mem.L.vm_last_error(mem.ctx.handle))
             got[exact] = (r, s, c)
             ok = np.array_equal(c, want_c) and np.array_equal(r, want_r) and np.array_equal(s.view(np.int64), want_s.view(np.int64))
@@ -270,8 +259,8 @@ def test_range(name):
         if tau == -1.0 and cls.inside:
             assert (want_c == ds.n).all()
         if cls.exact:
-            base = plain_memory(ds.base, cls.dtype)
-            rc, ur, us, uc, _ = raw_call(base, qb, tau, max_hits=width, exact=True)
+            base = range_memory(ds.base, cls.dtype)
+            rc, ur, us, uc, _ = raw_range(base, qb, tau, max_hits=width, exact=True)
             base.close()
             r, s, c = got[False]
             if not (rc == 0 and np.array_equal(c, uc) and np.array_equal(r, ur) and np.array_equal(s.view(np.int64), us.view(np.int64))):

@@ -14,19 +14,14 @@ from oracle import cref
 from oracle import similarity_ref as S
 from tests.golden.make_similarity_golden import CASES, make_inputs
 from tests.topk_ref import oracle_rows_parallel as _oracle_rows_parallel
+from tests.support import TD, bits
 
 pytestmark = pytest.mark.gpu
-
-TD = {"f16": torch.float16, "bf16": torch.bfloat16}
 
 
 def _mem(case_or_dtype, capacity, dim, ring=False):
     from vidmem.memory import EmbeddingMemory
     return EmbeddingMemory(capacity, dim, dtype=case_or_dtype, ring=ring)
-
-
-def _bits(t: torch.Tensor) -> np.ndarray:
-    return t.contiguous().view(torch.int16).cpu().numpy().view(np.uint16)
 
 
 @pytest.fixture(scope="module")
@@ -57,7 +52,7 @@ def test_all_pairs_exact_matches_c_oracle():
         q[3] = 0
         mem = _mem(dtype, 16, D)
         got = mem.cosine_exact(q.cuda(), m.cuda()).cpu().numpy()
-        want = cref.cosine_matrix(_bits(q), _bits(m), dtype=dtype)
+        want = cref.cosine_matrix(bits(q), bits(m), dtype=dtype)
         assert np.array_equal(got, want)  # bit for bit, including the zero-norm guards
 
 
@@ -87,7 +82,7 @@ def test_ragged_shapes(M, Q, k):
     if M:
         mem.append(m)
     s, r = mem.topk(q, k)
-    want_r, want_s = cref.cosine_topk(_bits(q), _bits(m) if M else np.zeros((0, D), np.uint16), k, dtype="f16")
+    want_r, want_s = cref.cosine_topk(bits(q), bits(m) if M else np.zeros((0, D), np.uint16), k, dtype="f16")
     assert np.array_equal(r.cpu().numpy(), want_r)
     assert np.array_equal(s.cpu().numpy(), want_s)
 
@@ -104,7 +99,7 @@ def test_ring_memory_overwrites_oldest():
         assert first == done
         done += step
         lo = max(0, done - cap)
-        want_r, want_s = cref.cosine_topk(_bits(q), _bits(allrows[lo:done]), 6, dtype="f16")
+        want_r, want_s = cref.cosine_topk(bits(q), bits(allrows[lo:done]), 6, dtype="f16")
         want_r = np.where(want_r >= 0, want_r + lo, -1)
         for exact in (False, True):
             s, r = mem.topk(q, 6, exact=exact)
@@ -125,7 +120,7 @@ def test_many_exact_ties_fall_back_to_exhaustive():
     s, r = mem.topk(base, 10)
     assert r.cpu().numpy().tolist() == [list(range(100, 110))]
     assert mem.uncertified_count == 1
-    want_r, want_s = cref.cosine_topk(_bits(base), _bits(m), 10, dtype="f16")
+    want_r, want_s = cref.cosine_topk(bits(base), bits(m), 10, dtype="f16")
     assert np.array_equal(s.cpu().numpy(), want_s)
     # the scan alone (redo=False) is NOT the reference answer here: that is what the flags are for
     s0, r0 = mem.topk(base, 10, redo=False)
@@ -146,9 +141,9 @@ def test_the_shape_that_must_redo_near_ties_around_rank_k():
 
     def variants(n):      # rows one fp16 ulp away from `base` in one element each: cosines within ~1e-7 of 1, all different
         v = base.repeat(n, 1).clone()
-        bits = v.view(torch.int16)
+        raw = v.view(torch.int16)
         for j in range(n):
-            bits[j, 3 * j + 1] += 1
+            raw[j, 3 * j + 1] += 1
         return v
     for near, must_redo in ((20, True), (5, False)):
         m = torch.tensor(rng.standard_normal((500, D)), dtype=torch.float32).to(torch.float16)
@@ -159,12 +154,12 @@ def test_the_shape_that_must_redo_near_ties_around_rank_k():
         q = torch.stack([base, m[7]])                         # query 1 is an ordinary one
         s, r = mem.topk(q, k)
         flags = mem.last_flags[:2].cpu().tolist()
-        want_r, want_s = cref.cosine_topk(_bits(q), _bits(m), k, dtype="f16")
+        want_r, want_s = cref.cosine_topk(bits(q), bits(m), k, dtype="f16")
         assert np.array_equal(r.cpu().numpy(), want_r) and np.array_equal(s.cpu().numpy(), want_s)
         assert flags[1] == 0
         if must_redo:
             assert flags[0] == _lib.VM_FLAG_GAP and mem.uncertified_count == 1
-            gap = float(want_s[0, k - 1] - np.sort(cref.cosine_matrix(_bits(q[:1]), _bits(m), dtype="f16")[0])[::-1][16])
+            gap = float(want_s[0, k - 1] - np.sort(cref.cosine_matrix(bits(q[:1]), bits(m), dtype="f16")[0])[::-1][16])
             assert 0.0 <= gap < 2.0 * (D + 8) * 2.0 ** -24       # that is WHY: rank k and rank KL + 1 within the bound
         else:
             assert flags[0] == 0 and mem.uncertified_count == 0
@@ -191,7 +186,7 @@ def test_flagged_redo_only_touches_flagged_queries(dtype, D):
     for kw in (dict(), dict(min_score=0.05, score_mode=S.SCORE_UNIT_INTERVAL)):
         mem.reset_uncertified()
         s, r = mem.topk(q, k, **kw)
-        want_r, want_s = cref.cosine_topk(_bits(q), _bits(live), k, dtype=dtype)
+        want_r, want_s = cref.cosine_topk(bits(q), bits(live), k, dtype=dtype)
         if kw:
             shown = (1.0 + want_s) / 2.0
             keep = (want_r >= 0) & (shown > 0.05)
@@ -216,7 +211,7 @@ def test_100k_rows_against_c_oracle():
         mem.append(m[lo:lo + 25_000])
     s, r = mem.topk(q, k)
     assert mem.uncertified_count == 0
-    want_r, want_s = cref.cosine_topk(_bits(q), _bits(m), k, dtype="f16")
+    want_r, want_s = cref.cosine_topk(bits(q), bits(m), k, dtype="f16")
     assert np.array_equal(r.cpu().numpy(), want_r)
     assert np.array_equal(s.cpu().numpy(), want_s)
 
@@ -274,7 +269,7 @@ def test_sampled_cut_path_many_queries_bit_exact(M):
     mem = _mem("f16", M, D)
     mem.append(m)
     s, r = mem.topk(q, k)
-    want_r, want_s = cref.cosine_topk(_bits(q), _bits(m), k, dtype="f16")
+    want_r, want_s = cref.cosine_topk(bits(q), bits(m), k, dtype="f16")
     assert np.array_equal(r.cpu().numpy(), want_r)
     assert np.array_equal(s.cpu().numpy(), want_s)
 
@@ -294,7 +289,7 @@ def test_many_query_groups_bit_exact():
     mem.append(m)
     s, r = mem.topk(q, k)
     assert mem.uncertified_count == 0
-    want_r, want_s = cref.cosine_topk(_bits(q), _bits(m), k, dtype="f16")
+    want_r, want_s = cref.cosine_topk(bits(q), bits(m), k, dtype="f16")
     assert np.array_equal(r.cpu().numpy(), want_r)
     assert np.array_equal(s.cpu().numpy(), want_s)
     assert r[199, :2].tolist() == [12, 65_000]
@@ -323,7 +318,7 @@ def test_emit_scan_many_queries_bit_exact(dtype, D, M, Q, k):
         mem.append(hist[lo:lo + 26_000])
     mem.reset_uncertified()
     s, r = mem.topk(q, k)
-    want_r, want_s = cref.cosine_topk(_bits(q), _bits(hist[live_lo:]), k, dtype=dtype)
+    want_r, want_s = cref.cosine_topk(bits(q), bits(hist[live_lo:]), k, dtype=dtype)
     want_r = np.where(want_r >= 0, want_r + live_lo, -1)
     assert np.array_equal(r.cpu().numpy(), want_r)
     assert np.array_equal(s.cpu().numpy(), want_s)
@@ -349,7 +344,7 @@ def test_emit_scan_overflow_and_tie_floods_fall_back_to_the_exhaustive_redo():
     mem.append(m)
     mem.reset_uncertified()
     s, r = mem.topk(q, k)
-    want_r, want_s = cref.cosine_topk(_bits(q), _bits(m), k, dtype="f16")
+    want_r, want_s = cref.cosine_topk(bits(q), bits(m), k, dtype="f16")
     assert np.array_equal(r.cpu().numpy(), want_r)
     assert np.array_equal(s.cpu().numpy(), want_s)
     assert r[7].tolist() == sorted(flood.tolist())[:k]
@@ -433,7 +428,7 @@ def test_gemm_class_scan_7040_queries_bit_exact():
     picks = np.unique(np.concatenate([np.arange(0, Q, 53), [401, 402, 500, 6911, 6912, 7000, 7039],
                                       256 * np.arange(28) + 17 * (np.arange(28) % 15)]))
     picks = picks[picks < Q]
-    want_r, want_s = _oracle_rows_parallel(_bits(q), _bits(m), k, "f16", picks)
+    want_r, want_s = _oracle_rows_parallel(bits(q), bits(m), k, "f16", picks)
     assert np.array_equal(r_np[picks], want_r)
     assert np.array_equal(s_np[picks], want_s)
     assert redone <= 8, redone                 # the zero query ties with everything; nothing else may need the redo
@@ -462,7 +457,7 @@ def test_gemm_class_scan_bf16_ring_ragged_bit_exact():
     s2, r2 = mem.topk(q, k, exact=True)
     assert np.array_equal(r2.cpu().numpy(), r_np) and np.array_equal(s2.cpu().numpy(), s_np)
     picks = np.unique(np.concatenate([np.arange(0, Q, 11), [51, 511, 512, 599]]))
-    want_r, want_s = _oracle_rows_parallel(_bits(q), _bits(hist[extra:]), k, "bf16", picks)
+    want_r, want_s = _oracle_rows_parallel(bits(q), bits(hist[extra:]), k, "bf16", picks)
     want_r = np.where(want_r >= 0, want_r + extra, -1)
     assert np.array_equal(r_np[picks], want_r)
     assert np.array_equal(s_np[picks], want_s)
@@ -490,7 +485,7 @@ def test_gemm_class_scan_tie_flood_marks_and_redoes():
     s2, r2 = mem.topk(q, k, exact=True)
     assert np.array_equal(r2.cpu().numpy(), r.cpu().numpy()) and np.array_equal(s2.cpu().numpy(), s.cpu().numpy())
     assert r[7].tolist() == sorted(flood.tolist())[:k]
-    want_r, want_s = cref.cosine_topk(_bits(q[[7, 9, 100]]), _bits(m), k, dtype="f16")
+    want_r, want_s = cref.cosine_topk(bits(q[[7, 9, 100]]), bits(m), k, dtype="f16")
     assert np.array_equal(r[[7, 9, 100]].cpu().numpy(), want_r) and np.array_equal(s[[7, 9, 100]].cpu().numpy(), want_s)
 
 
@@ -582,7 +577,7 @@ def test_gemm_class_scan_two_k_tiles(M, Q):
     s2, r2 = mem.topk(q, k, exact=True)
     assert np.array_equal(r2.cpu().numpy(), r.cpu().numpy()) and np.array_equal(s2.cpu().numpy(), s.cpu().numpy())
     picks = np.unique(np.concatenate([np.arange(0, Q, 23), [Q - 9, Q - 8, Q - 1]]))
-    want_r, want_s = cref.cosine_topk(_bits(q[picks]), _bits(m), k, dtype="f16")
+    want_r, want_s = cref.cosine_topk(bits(q[picks]), bits(m), k, dtype="f16")
     assert np.array_equal(r[picks].cpu().numpy(), want_r) and np.array_equal(s[picks].cpu().numpy(), want_s)
     assert mem.uncertified_count <= 2
 

@@ -21,12 +21,13 @@ import numpy as np
 import pytest
 import torch
 
+from tests import support
 from tests import topk_plan as TP
-from tests.topk_ref import bits, oracle_rows_parallel
+from tests.support import TD, bits
+from tests.topk_ref import oracle_rows_parallel
 
 pytestmark = pytest.mark.gpu
 
-TD = {"f16": torch.float16, "bf16": torch.bfloat16}
 THREADS = min(16, os.cpu_count() or 1)
 CHUNKS = (977, 20_011, 4_099, 31_337, 12_289, 65_521)   # uneven append sizes, cycled
 
@@ -317,18 +318,6 @@ FLAGGED = {}
 # ---------------------------------------------------------------------------------------------------------------------
 # the check
 # ---------------------------------------------------------------------------------------------------------------------
-def _launches(mem, fn):
-    ctx = mem.ctx
-    ctx.profile_mask(None)
-    ctx.profile_enable(256)
-    try:
-        out = fn()
-        prof = ctx.profile_read()
-    finally:
-        ctx.profile_enable(0)
-    return out, {c: prof[c][1] for c in ("topk_scan", "topk_finalize", "topk_exact")}
-
-
 def _same(a_s, a_r, b_s, b_r) -> bool:
     return np.array_equal(a_r, b_r) and np.array_equal(a_s.view(np.int64), b_s.view(np.int64))
 
@@ -362,13 +351,13 @@ def run_case(case: Case, score_mode: int = 0, thr: Optional[str] = None):
     es, er = es.cpu().numpy(), er.cpu().numpy()
 
     if plan.family == "exact":
-        (s1, r1), launches = _launches(mem, lambda: mem.topk(q, k, **kw))
+        (s1, r1), launches = support.launches(mem, lambda: mem.topk(q, k, **kw))
         assert launches["topk_scan"] == 0 and launches["topk_finalize"] == 0 and launches["topk_exact"] >= 1, launches
         s1, r1 = s1.cpu().numpy(), r1.cpu().numpy()
         assert _same(s1, r1, es, er)
     else:
         scratch = TopkScratch.for_(mem, Q, k)
-        (s0, r0), launches = _launches(mem, lambda: mem.topk(q, k, redo=False, scratch=scratch, **kw))
+        (s0, r0), launches = support.launches(mem, lambda: mem.topk(q, k, redo=False, scratch=scratch, **kw))
         want = (plan.launches["topk_scan"], plan.launches["topk_finalize"])
         assert (launches["topk_scan"], launches["topk_finalize"]) == want, (plan.family, launches, want)
         flags = scratch.flags[:Q].cpu().numpy()
@@ -450,7 +439,8 @@ def test_large_k_exhaustive(case):
 @pytest.mark.parametrize("D", [256, 512])
 @pytest.mark.parametrize("groups", [0, 3, 500])
 def test_grouped_fresh_memory(groups, D, dtype):
-    from tests.test_group_topk_gpu import check, clustered, grouped_memory, queries_near
+    from tests.search_checks import grouped_check
+    from tests.support import clustered, grouped_memory, queries_near
     from vidmem.memory import EmbeddingMemory
     if groups == 0:
         mem = EmbeddingMemory(100_000, D, dtype, grouped=True)
@@ -462,7 +452,7 @@ def test_grouped_fresh_memory(groups, D, dtype):
         mem = grouped_memory(rows, sizes, dtype, capacity=100_000)
         q = queries_near(rows, 16, 5, dtype)
     for k in (1, 10):
-        r, s, kk = check(mem, q, k, dtype)
+        r, s, kk = grouped_check(mem, q, k, dtype)
         n_groups = groups
         assert (r[:, min(n_groups, k):] == -1).all() and (s[:, min(n_groups, k):] == 0.0).all()
         assert (r[:, :min(n_groups, k)] >= 0).all()
@@ -471,7 +461,8 @@ def test_grouped_fresh_memory(groups, D, dtype):
 
 @pytest.mark.parametrize("dtype", ["f16", "bf16"])
 def test_grouped_ring_wraps_mid_group(dtype):
-    from tests.test_group_topk_gpu import check, clustered, grouped_memory, queries_near
+    from tests.search_checks import grouped_check
+    from tests.support import clustered, grouped_memory, queries_near
     D, cap = 128, 100_000
     sizes = [int(x) for x in np.random.default_rng(7).integers(1, 40, 5_200)]
     while sum(sizes) <= cap + 20:
@@ -482,6 +473,6 @@ def test_grouped_ring_wraps_mid_group(dtype):
     cut = total - cap                       # the oldest live row: make sure it sits inside a group
     starts = np.concatenate([[0], np.cumsum(sizes)[:-1]])
     assert cut not in set(starts.tolist())
-    check(mem, queries_near(rows[-cap:], 8, 9, dtype), 10, dtype)
-    check(mem, queries_near(rows[cut - 50:cut + 50], 8, 11, dtype), 5, dtype)
+    grouped_check(mem, queries_near(rows[-cap:], 8, 9, dtype), 10, dtype)
+    grouped_check(mem, queries_near(rows[cut - 50:cut + 50], 8, 11, dtype), 5, dtype)
     mem.close()

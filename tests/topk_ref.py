@@ -1,13 +1,7 @@
-"""Host-side helpers shared by the top-k GPU tests: bit patterns of 16-bit rows and the C oracle on a thread pool."""
+"""Host-side helpers shared by the top-k GPU tests: merging per-chunk answers and the C oracle on a thread pool."""
 import numpy as np
 
 from oracle import cref
-
-
-def bits(t) -> np.ndarray:
-    """uint16 bit patterns of a 16-bit torch tensor (host copy)."""
-    import torch
-    return t.contiguous().view(torch.int16).cpu().numpy().view(np.uint16)
 
 
 def merge_topk(parts, k):
