@@ -822,6 +822,43 @@ __global__ void __launch_bounds__(NW * 64, 1)
     }
 }
 
+// The launches of launch_long, one per kernel family: lds = the K | V image, ql = query tiles wanted (<= NT).
+template <int DT, int NT, bool EXACT, int NWV, int ABL = 0>   // ABL: developer ablations of the 12-wave build
+int launch_pair(vm_ctx *ctx, const uint16_t *qkv, uint16_t *out, int items, int T, int heads, hipStream_t st, int ql,
+                size_t lds) {
+    auto kern = attention_pair_kernel<DT, NT, EXACT, NWV, ABL>;
+    if (int r = vm_lds_opt_in(ctx, kern, lds, "vm_attention")) return r;
+    kern<<<items, NWV * 64, lds, st>>>(qkv, out, T, heads, ql);
+    VM_LAUNCH_CHECK(ctx);
+    return VM_OK;
+}
+template <int DT, int NT, bool EXACT, int PF>
+int launch_persist(vm_ctx *ctx, const uint16_t *qkv, uint16_t *out, int items, int T, int heads, hipStream_t st, int ql,
+                   size_t lds) {
+    auto kern = attention_pair_persist_kernel<DT, NT, EXACT, 12, PF>;
+    if (int r = vm_lds_opt_in(ctx, kern, lds, "vm_attention")) return r;
+    kern<<<items < ctx->num_cus ? items : ctx->num_cus, 12 * 64, lds, st>>>(qkv, out, T, heads, ql, items);
+    VM_LAUNCH_CHECK(ctx);
+    return VM_OK;
+}
+template <int DT, int NT, bool EXACT, bool ONLINE>
+int launch_long16(vm_ctx *ctx, const uint16_t *qkv, uint16_t *out, int items, int T, int heads, hipStream_t st, int ql,
+                  size_t lds) {
+    auto kern = attention_long_kernel<DT, NT, EXACT, 16, ONLINE>;
+    if (int r = vm_lds_opt_in(ctx, kern, lds, "vm_attention")) return r;
+    kern<<<items, 1024, lds, st>>>(qkv, out, T, heads, ql);
+    VM_LAUNCH_CHECK(ctx);
+    return VM_OK;
+}
+#ifdef VM_DEV_SWITCHES
+// VIDMEM_ATTN_ABL = one of As: that ablation of the 12-wave pair kernel, its status in *rc; false = none of them asked for
+template <int DT, int NT, bool EXACT, int... As>
+bool launch_pair_abl(int abl, int *rc, vm_ctx *ctx, const uint16_t *qkv, uint16_t *out, int items, int T, int heads,
+                     hipStream_t st, int ql, size_t lds) {
+    return ((abl == As && ((*rc = launch_pair<DT, NT, EXACT, 12, As>(ctx, qkv, out, items, T, heads, st, ql, lds)), true)) || ...);
+}
+#endif
+
 template <int DT, int NT, bool EXACT>
 int launch_long(vm_ctx *ctx, const uint16_t *qkv, uint16_t *out, int B, int T, int heads, hipStream_t st, int qt_lim) {
     const size_t lds = (size_t)NT * 16 * 128 * 2;
@@ -830,80 +867,38 @@ int launch_long(vm_ctx *ctx, const uint16_t *qkv, uint16_t *out, int B, int T, i
     static const int online_env = (int)VM_DEV_ENV("ATTN_ONLINE", 1);
     static const int pair_env = (int)VM_DEV_ENV("ATTN_PAIR", 12);   // waves of the two-tiles-per-walk kernel; 0 = one tile per walk
     vm_prof_scope prof(ctx, VM_PROF_ATTENTION, st);
-    if (online_env && pair_env > 0) {
-        const int ql = qt_lim < NT ? qt_lim : NT;
-#define VM_PAIR_GO(NWV)                                                                                              \
-    {                                                                                                                \
-        auto kern = attention_pair_kernel<DT, NT, EXACT, NWV>;                                                       \
-        static unsigned long long attr_set = 0; /* one bit per device */                                              \
-        if (!((attr_set >> (ctx->device & 63)) & 1ull)) {                                                                                             \
-            VM_HIP(ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-            attr_set |= 1ull << (ctx->device & 63);                                                                                         \
-        }                                                                                                            \
-        kern<<<B * heads, NWV * 64, lds, st>>>(qkv, out, T, heads, ql);                                              \
-    }
+    const int ql = qt_lim < NT ? qt_lim : NT, items = B * heads;
+    if (!online_env) return launch_long16<DT, NT, EXACT, false>(ctx, qkv, out, items, T, heads, st, ql, lds);
+    if (pair_env <= 0) return launch_long16<DT, NT, EXACT, true>(ctx, qkv, out, items, T, heads, st, ql, lds);
 #ifdef VM_DEV_SWITCHES
-        static const int abl_env = (int)VM_DEV_ENV("ATTN_ABL", 0);
-#define VM_PAIR_ABL(A)                                                                                               \
-    if (abl_env == (A)) {                                                                                            \
-        auto kern = attention_pair_kernel<DT, NT, EXACT, 12, (A)>;                                                   \
-        (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);        \
-        kern<<<B * heads, 12 * 64, lds, st>>>(qkv, out, T, heads, ql);                                               \
-        VM_LAUNCH_CHECK(ctx);                                                                                        \
-        return VM_OK;                                                                                                \
+    static const int abl_env = (int)VM_DEV_ENV("ATTN_ABL", 0);
+    if constexpr (NT == 37 && DT == VM_BF16) {
+        int rc = VM_OK;
+        if (launch_pair_abl<DT, NT, EXACT, 1, 2, 4, 8, 16, 32, 3, 10, 48, 63>(abl_env, &rc, ctx, qkv, out, items, T, heads, st,
+                                                                              ql, lds))
+            return rc;
     }
-        if constexpr (NT == 37 && DT == VM_BF16) {
-            VM_PAIR_ABL(1) VM_PAIR_ABL(2) VM_PAIR_ABL(4) VM_PAIR_ABL(8) VM_PAIR_ABL(16) VM_PAIR_ABL(32) VM_PAIR_ABL(3)
-            VM_PAIR_ABL(10) VM_PAIR_ABL(48) VM_PAIR_ABL(63)
-        }
-#undef VM_PAIR_ABL
 #endif
-        // persistent walk with the next item's rows prefetched into the idle waves' registers: when their share fits
-        static const int persist_env = (int)VM_DEV_ENV("ATTN_PERSIST", 1);
-        const int npairs = (ql + 1) / 2, maxc = (npairs + 11) / 12;
-        int w0 = npairs - (maxc - 1) * 12;
-        if (w0 >= 12) w0 = 0;
-        constexpr int GROUPS = 2 * NT * 16 / 8;             // 8-row groups of the K | V image
-        constexpr int PF_FEW = (GROUPS + 4) / 5;            // 16-byte registers per lane with five prefetching waves
-        constexpr int PF_MANY = (GROUPS + 10) / 11;         // ... with eleven (one pair to walk: the last layer's CLS rows)
-        const int pf = (GROUPS + (12 - w0) - 1) / (12 - w0);
-        const int items = B * heads;
-#define VM_PERSIST_GO(PF)                                                                                            \
-    {                                                                                                                \
-        auto kern = attention_pair_persist_kernel<DT, NT, EXACT, 12, PF>;                                            \
-        static unsigned long long attr_set = 0; /* one bit per device */                                              \
-        if (!((attr_set >> (ctx->device & 63)) & 1ull)) {                                                            \
-            VM_HIP(ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-            attr_set |= 1ull << (ctx->device & 63);                                                                  \
-        }                                                                                                            \
-        kern<<<items < ctx->num_cus ? items : ctx->num_cus, 12 * 64, lds, st>>>(qkv, out, T, heads, ql, items);      \
-    }
-        if (persist_env && pair_env == 12 && pf <= PF_MANY) VM_PERSIST_GO(PF_MANY)
-        else if (persist_env && pair_env == 12 && pf <= PF_FEW) VM_PERSIST_GO(PF_FEW)
-#undef VM_PERSIST_GO
-        else if (pair_env == 8) VM_PAIR_GO(8)
-        else if (pair_env == 10) VM_PAIR_GO(10)
-        else VM_PAIR_GO(12)
-#undef VM_PAIR_GO
-    } else if (online_env) {
-        auto kern = attention_long_kernel<DT, NT, EXACT, 16, true>;
-        static unsigned long long attr_set = 0;   // one bit per device
-        if (!((attr_set >> (ctx->device & 63)) & 1ull)) {
-            VM_HIP(ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            attr_set |= 1ull << (ctx->device & 63);
-        }
-        kern<<<B * heads, 1024, lds, st>>>(qkv, out, T, heads, qt_lim < NT ? qt_lim : NT);
+    // persistent walk with the next item's rows prefetched into the idle waves' registers: when their share fits
+    static const int persist_env = (int)VM_DEV_ENV("ATTN_PERSIST", 1);
+    const int npairs = (ql + 1) / 2, maxc = (npairs + 11) / 12;
+    int w0 = npairs - (maxc - 1) * 12;
+    if (w0 >= 12) w0 = 0;
+    constexpr int GROUPS = 2 * NT * 16 / 8;             // 8-row groups of the K | V image
+    constexpr int PF_FEW = (GROUPS + 4) / 5;            // 16-byte registers per lane with five prefetching waves
+    constexpr int PF_MANY = (GROUPS + 10) / 11;         // ... with eleven (one pair to walk: the last layer's CLS rows)
+    const int pf = (GROUPS + (12 - w0) - 1) / (12 - w0);
+    if (persist_env && pair_env == 12 && pf <= PF_MANY) {
+        return launch_persist<DT, NT, EXACT, PF_MANY>(ctx, qkv, out, items, T, heads, st, ql, lds);
+    } else if (persist_env && pair_env == 12 && pf <= PF_FEW) {
+        return launch_persist<DT, NT, EXACT, PF_FEW>(ctx, qkv, out, items, T, heads, st, ql, lds);
+    } else if (pair_env == 8) {
+        return launch_pair<DT, NT, EXACT, 8>(ctx, qkv, out, items, T, heads, st, ql, lds);
+    } else if (pair_env == 10) {
+        return launch_pair<DT, NT, EXACT, 10>(ctx, qkv, out, items, T, heads, st, ql, lds);
     } else {
-        auto kern = attention_long_kernel<DT, NT, EXACT, 16, false>;
-        static unsigned long long attr_set = 0;   // one bit per device
-        if (!((attr_set >> (ctx->device & 63)) & 1ull)) {
-            VM_HIP(ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            attr_set |= 1ull << (ctx->device & 63);
-        }
-        kern<<<B * heads, 1024, lds, st>>>(qkv, out, T, heads, qt_lim < NT ? qt_lim : NT);
+        return launch_pair<DT, NT, EXACT, 12>(ctx, qkv, out, items, T, heads, st, ql, lds);
     }
-    VM_LAUNCH_CHECK(ctx);
-    return VM_OK;
 }
 
 // NT = key tiles of 16 (13 for 197 tokens, 37 for 577).  EXACT: T > 16*(NT-1), so only the last tile has masked keys
@@ -1053,11 +1048,7 @@ template <int DT, int NT, bool EXACT, int CW>
 int launch_stream_cw(vm_ctx *ctx, const uint16_t *qkv, uint16_t *out, int B, int T, int heads, hipStream_t st, int qt_lim) {
     const size_t lds = (size_t)NT * 16 * 128 * 6;
     auto kern = attention_stream_kernel<DT, NT, EXACT, CW>;
-    static unsigned long long attr_set = 0;   // one bit per device
-    if (!((attr_set >> (ctx->device & 63)) & 1ull)) {
-        VM_HIP(ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_set |= 1ull << (ctx->device & 63);
-    }
+    if (int r = vm_lds_opt_in(ctx, kern, lds, "vm_attention")) return r;
     const int items = B * heads;
     const int grid = items < ctx->num_cus ? items : ctx->num_cus;
     vm_prof_scope prof(ctx, VM_PROF_ATTENTION, st);
@@ -1082,11 +1073,7 @@ template <int DT, int NT, bool EXACT, int OCC = (NT <= 13 ? 2 : 1), bool CAUSAL 
 int launch(vm_ctx *ctx, const uint16_t *qkv, uint16_t *out, int B, int T, int heads, hipStream_t st, int qt_lim) {
     const size_t lds = (size_t)NT * 16 * 128 * 2;
     auto kern = attention_kernel<DT, NT, EXACT, OCC, CAUSAL>;
-    static unsigned long long attr_set = 0;   // one bit per device
-    if (!((attr_set >> (ctx->device & 63)) & 1ull)) {
-        VM_HIP(ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_set |= 1ull << (ctx->device & 63);
-    }
+    if (int r = vm_lds_opt_in(ctx, kern, lds, "vm_attention")) return r;
     vm_prof_scope prof(ctx, VM_PROF_ATTENTION, st);
     kern<<<B * heads, 256, lds, st>>>(qkv, out, T, heads, qt_lim < NT ? qt_lim : NT);
     VM_LAUNCH_CHECK(ctx);

@@ -9,6 +9,7 @@
 #include "vm_kernels.h"
 
 #include <type_traits>
+#include <vector>
 
 // ---------------------------------------------------------------------------------------------------------
 // HBM-bound kernels between the GEMMs
@@ -402,14 +403,24 @@ __global__ void __launch_bounds__(256) text_embed_kernel(const int32_t *__restri
 
 }  // namespace
 
-#define VM_VPL_SWITCH(H, CALL)                                                                     \
-    switch ((H) / 256) {                                                                           \
-        case 1: CALL(1); break;                                                                    \
-        case 2: CALL(2); break;                                                                    \
-        case 3: CALL(3); break;                                                                    \
-        case 4: CALL(4); break;                                                                    \
-        default: return vm_fail(ctx, VM_ERR_UNSUPPORTED, "row width %d (need 256..1024, %%256)", H); \
+// Host dispatch of the kernels' two compile-time operands: f(std::integral_constant<int, V>{}) for a row width of
+// H = 256 V floats, f(std::integral_constant<int, DT>{}) for the 16-bit type.  f returns a vm_status.
+template <class F>
+int vpl_dispatch(vm_ctx *ctx, int H, F f) {
+    using std::integral_constant;
+    switch (H / 256) {
+        case 1: return f(integral_constant<int, 1>{});
+        case 2: return f(integral_constant<int, 2>{});
+        case 3: return f(integral_constant<int, 3>{});
+        case 4: return f(integral_constant<int, 4>{});
+        default: return vm_fail(ctx, VM_ERR_UNSUPPORTED, "row width %d (need 256..1024, %%256)", H);
     }
+}
+template <class F>
+int dtype_dispatch(int dtype, F f) {
+    using std::integral_constant;
+    return dtype == VM_F16 ? f(integral_constant<int, VM_F16>{}) : f(integral_constant<int, VM_BF16>{});
+}
 
 int vm_resid_layernorm(vm_ctx *ctx, int dtype, float *x32, const uint16_t *delta16, const uint16_t *deltaB16,
                        int write_x, const float *gamma, const float *beta, float eps, uint16_t *out16, int rows, int H,
@@ -420,34 +431,23 @@ int vm_resid_layernorm(vm_ctx *ctx, int dtype, float *x32, const uint16_t *delta
     vm_prof_scope prof(ctx, VM_PROF_LAYERNORM, st);
     static const int lowreg_env = (int)VM_DEV_ENV("LN_LOWREG", 1);   // developer A/B: 0 = the ordinary kernel on two streams as well
     // (round 4, three alternating pairs: ViT-B/16 26.78-26.84 k against 27.23-27.25 k frames/s with this one, CLIP-L 2,691 / 2,804)
-    if (lowreg != 0 && lowreg_env != 0) {   // two-stream mode: the variant that fits beside the persistent GEMM (always the streaming policy)
-        const int blk = (rows + 3) / 4;
-#define RLNL(V)                                                                                                          \
-    if (dtype == VM_F16)                                                                                                 \
-        resid_layernorm_lowreg_kernel<VM_F16, V, true><<<blk, 256, 0, st>>>(x32, delta16, deltaB16, write_x, gamma, beta, eps, out16, rows, H, rstride); \
-    else                                                                                                                 \
-        resid_layernorm_lowreg_kernel<VM_BF16, V, true><<<blk, 256, 0, st>>>(x32, delta16, deltaB16, write_x, gamma, beta, eps, out16, rows, H, rstride)
-        VM_VPL_SWITCH(H, RLNL)
-#undef RLNL
-        VM_LAUNCH_CHECK(ctx);
-        return VM_OK;
-    }
+    const bool low = lowreg != 0 && lowreg_env != 0;   // two-stream mode: the variant that fits beside the persistent GEMM (always the streaming policy)
     // rows that together exceed the 32 MiB of L2 several times over stream through with the non-temporal policy
     static const int nt_env = (int)VM_DEV_ENV("LN_NT", 1);
     const bool nt = nt_env && (size_t)rows * H * 4 > ((size_t)64 << 20);
-#define RLN16(V) resid_layernorm_kernel<VM_F16, V, RPW, false><<<blocks, 256, 0, st>>>(x32, delta16, deltaB16, write_x, gamma, beta, eps, out16, rows, H, rstride)
-#define RLNB16(V) resid_layernorm_kernel<VM_BF16, V, RPW, false><<<blocks, 256, 0, st>>>(x32, delta16, deltaB16, write_x, gamma, beta, eps, out16, rows, H, rstride)
-#define RLN16N(V) resid_layernorm_kernel<VM_F16, V, RPW, true><<<blocks, 256, 0, st>>>(x32, delta16, deltaB16, write_x, gamma, beta, eps, out16, rows, H, rstride)
-#define RLNB16N(V) resid_layernorm_kernel<VM_BF16, V, RPW, true><<<blocks, 256, 0, st>>>(x32, delta16, deltaB16, write_x, gamma, beta, eps, out16, rows, H, rstride)
-    if (dtype == VM_F16) {
-        if (nt) { VM_VPL_SWITCH(H, RLN16N) } else { VM_VPL_SWITCH(H, RLN16) }
-    } else {
-        if (nt) { VM_VPL_SWITCH(H, RLNB16N) } else { VM_VPL_SWITCH(H, RLNB16) }
-    }
-#undef RLN16
-#undef RLNB16
-#undef RLN16N
-#undef RLNB16N
+    const int rc = vpl_dispatch(ctx, H, [&](auto V) {
+        return dtype_dispatch(dtype, [&](auto DT) {
+            auto go = [&](auto kern, int grid) {
+                kern<<<grid, 256, 0, st>>>(x32, delta16, deltaB16, write_x, gamma, beta, eps, out16, rows, H, rstride);
+                return VM_OK;
+            };
+            constexpr int dt = decltype(DT)::value, vpl = decltype(V)::value;
+            if (low) return go(resid_layernorm_lowreg_kernel<dt, vpl, true>, (rows + 3) / 4);
+            return nt ? go(resid_layernorm_kernel<dt, vpl, RPW, true>, blocks)
+                      : go(resid_layernorm_kernel<dt, vpl, RPW, false>, blocks);
+        });
+    });
+    if (rc != VM_OK) return rc;
     VM_LAUNCH_CHECK(ctx);
     return VM_OK;
 }
@@ -457,15 +457,14 @@ int vm_embed(vm_ctx *ctx, int dtype, const uint16_t *patch16, const float *cls, 
     const int rows = B * T, blocks = (rows + 3) / 4;
     if (H % 256 != 0) return vm_fail(ctx, VM_ERR_UNSUPPORTED, "row width %d", H);
     vm_prof_scope prof(ctx, VM_PROF_LAYERNORM, st);
-#define EMB16(V) embed_kernel<VM_F16, V><<<blocks, 256, 0, st>>>(patch16, cls, pos, pre_g, pre_b, eps, pre_ln, x32, rows, T, H)
-#define EMBB16(V) embed_kernel<VM_BF16, V><<<blocks, 256, 0, st>>>(patch16, cls, pos, pre_g, pre_b, eps, pre_ln, x32, rows, T, H)
-    if (dtype == VM_F16) {
-        VM_VPL_SWITCH(H, EMB16)
-    } else {
-        VM_VPL_SWITCH(H, EMBB16)
-    }
-#undef EMB16
-#undef EMBB16
+    const int rc = vpl_dispatch(ctx, H, [&](auto V) {
+        return dtype_dispatch(dtype, [&](auto DT) {
+            embed_kernel<decltype(DT)::value, decltype(V)::value><<<blocks, 256, 0, st>>>(patch16, cls, pos, pre_g, pre_b, eps,
+                                                                                          pre_ln, x32, rows, T, H);
+            return VM_OK;
+        });
+    });
+    if (rc != VM_OK) return rc;
     VM_LAUNCH_CHECK(ctx);
     return VM_OK;
 }
@@ -475,16 +474,13 @@ int vm_pool(vm_ctx *ctx, int dtype, const float *x, const uint16_t *delta16, con
             int B, int T, int H, hipStream_t st, const int32_t *pool_row) {
     const size_t lds = (size_t)(H + (proj_dim > 0 ? proj_dim : 0)) * 4;
     vm_prof_scope prof(ctx, VM_PROF_POOL, st);
-    if (pool_row) {
-        if (dtype == VM_F16)
-            pool_kernel<VM_F16, true><<<B, 256, lds, st>>>(x, delta16, deltaB16, gamma, beta, eps, proj_w, proj_dim, l2, out, T, H, pool_row);
-        else
-            pool_kernel<VM_BF16, true><<<B, 256, lds, st>>>(x, delta16, deltaB16, gamma, beta, eps, proj_w, proj_dim, l2, out, T, H, pool_row);
-    } else if (dtype == VM_F16) {
-        pool_kernel<VM_F16><<<B, 256, lds, st>>>(x, delta16, deltaB16, gamma, beta, eps, proj_w, proj_dim, l2, out, T, H);
-    } else {
-        pool_kernel<VM_BF16><<<B, 256, lds, st>>>(x, delta16, deltaB16, gamma, beta, eps, proj_w, proj_dim, l2, out, T, H);
-    }
+    dtype_dispatch(dtype, [&](auto DT) {
+        auto go = [&](auto kern) {   // AT_ROW reads pool_row; the other build is handed its default, null
+            kern<<<B, 256, lds, st>>>(x, delta16, deltaB16, gamma, beta, eps, proj_w, proj_dim, l2, out, T, H, pool_row);
+            return VM_OK;
+        };
+        return pool_row ? go(pool_kernel<decltype(DT)::value, true>) : go(pool_kernel<decltype(DT)::value>);
+    });
     VM_LAUNCH_CHECK(ctx);
     return VM_OK;
 }
@@ -494,9 +490,12 @@ int vm_text_embed(vm_ctx *ctx, const int32_t *ids, const float *tok, const float
     const int rows = B * T, blocks = (rows + 3) / 4;
     if (H % 256 != 0) return vm_fail(ctx, VM_ERR_UNSUPPORTED, "row width %d", H);
     vm_prof_scope prof(ctx, VM_PROF_LAYERNORM, st);   // the embedding stage's category, as vm_embed's
-#define TEMB(V) text_embed_kernel<V><<<blocks, 256, 0, st>>>(ids, tok, pos, vocab, eot_id, x32, pool_row, flags, rows, T, H)
-    VM_VPL_SWITCH(H, TEMB)
-#undef TEMB
+    const int rc = vpl_dispatch(ctx, H, [&](auto V) {
+        text_embed_kernel<decltype(V)::value><<<blocks, 256, 0, st>>>(ids, tok, pos, vocab, eot_id, x32, pool_row, flags, rows,
+                                                                      T, H);
+        return VM_OK;
+    });
+    if (rc != VM_OK) return rc;
     VM_LAUNCH_CHECK(ctx);
     return VM_OK;
 }
@@ -529,6 +528,38 @@ static void bind_layer(LayerW &w, char *b, const size_t o[12]) {
     w.fc2_w = (uint16_t *)(b + o[10]);
     w.fc2_b = (float *)(b + o[11]);
 }
+// Host-side builder of a tower's weight blob, one device allocation with every weight at a 256-byte aligned offset:
+// take() lays it out, alloc() allocates it, copy() fills it.  The first copy that fails sticks in `err` and the later
+// ones do nothing, so a create function copies everything and asks once.
+struct WeightBlob {
+    size_t total = 0;
+    char *base = nullptr;
+    hipError_t err = hipSuccess;
+    size_t lsz[12];
+    std::vector<size_t> layer_off;   // 12 per layer, header order
+    size_t take(size_t bytes) {
+        const size_t off = total;
+        total += vm_align_up(bytes, 256);
+        return off;
+    }
+    void take_layers(size_t H, size_t M, int layers) {
+        layer_sizes(H, M, lsz);
+        for (int i = 0; i < 12 * layers; ++i) layer_off.push_back(take(lsz[i % 12]));
+    }
+    hipError_t alloc() { return hipMalloc((void **)&base, total); }
+    // a weight of zero bytes has nothing to copy; a null source of one that has bytes is an error
+    void copy(size_t off, const void *src, size_t bytes) {
+        if (err != hipSuccess || bytes == 0) return;
+        err = src ? hipMemcpy(base + off, src, bytes, hipMemcpyDeviceToDevice) : hipErrorInvalidValue;
+    }
+    // the layers' weights wp[first + 12 l + i] and each layer's pointers into the blob
+    void copy_layers(const void *const *wp, int first, int layers, LayerW *lw) {
+        for (int l = 0; l < layers; ++l) {
+            for (int i = 0; i < 12; ++i) copy(layer_off[12 * l + i], wp[first + 12 * l + i], lsz[i]);
+            bind_layer(lw[l], base, &layer_off[12 * l]);
+        }
+    }
+};
 struct vm_encoder {
     vm_ctx *ctx;
     vm_encoder_desc d;
@@ -563,20 +594,16 @@ extern "C" int vm_encoder_create(vm_ctx *ctx, const vm_encoder_desc *desc, const
     if (n_weights != 9 + 12 * d.layers)
         return vm_fail(ctx, VM_ERR_INVALID, "expected %d weight pointers, got %d", 9 + 12 * d.layers, n_weights);
     VM_HIP(ctx, hipSetDevice(ctx->device));
+    const int g = d.image / d.patch, tokens = g * g + 1;
+    if (tokens > 592) return vm_fail(ctx, VM_ERR_UNSUPPORTED, "%d tokens per frame > 592", tokens);
     vm_encoder *e = new vm_encoder();
     memset(e, 0, sizeof(*e));
     e->ctx = ctx;
     e->d = d;
-    const int g = d.image / d.patch;
     e->patches = g * g;
-    e->tokens = e->patches + 1;
+    e->tokens = tokens;
     e->patch_k = round_up(3 * d.patch * d.patch, 64);
     e->out_dim = d.proj_dim ? d.proj_dim : d.hidden;
-    if (e->tokens > 592) {
-        const int tokens = e->tokens;
-        delete e;
-        return vm_fail(ctx, VM_ERR_UNSUPPORTED, "%d tokens per frame > 592", tokens);
-    }
     e->micro_batch = 0;
     e->cls_last = 3;
     e->schedule = VM_SCHED_AUTO;
@@ -594,57 +621,34 @@ extern "C" int vm_encoder_create(vm_ctx *ctx, const vm_encoder_desc *desc, const
         }
     }
     const size_t H = d.hidden, M = d.mlp;
-    // byte sizes in header order
-    auto a256 = [](size_t b) { return vm_align_up(b, 256); };
-    size_t total = 0;
-    auto take = [&](size_t bytes) {
-        size_t off = total;
-        total += a256(bytes);
-        return off;
-    };
-    const size_t o_patch_w = take(H * e->patch_k * 2), o_patch_b = take(H * 4), o_cls = take(H * 4),
-                 o_pos = take((size_t)e->tokens * H * 4), o_pre_g = take(H * 4), o_pre_b = take(H * 4),
-                 o_ln_g = take(H * 4), o_ln_b = take(H * 4), o_proj = take((size_t)(d.proj_dim ? d.proj_dim : 0) * H * 2);
-    struct LO {
-        size_t o[12];
-    };
-    LO *lo = new LO[d.layers];
-    size_t lsz[12];
-    layer_sizes(H, M, lsz);
-    for (int l = 0; l < d.layers; ++l)
-        for (int i = 0; i < 12; ++i) lo[l].o[i] = take(lsz[i]);
-    hipError_t er = hipMalloc((void **)&e->blob, total);
-    if (er != hipSuccess) {
-        delete[] lo;
-        delete e;
-        return vm_fail(ctx, VM_ERR_NOMEM, "encoder weights: hipMalloc(%zu) failed", total);
+    WeightBlob wb;   // byte sizes in header order
+    const size_t o_patch_w = wb.take(H * e->patch_k * 2), o_patch_b = wb.take(H * 4), o_cls = wb.take(H * 4),
+                 o_pos = wb.take((size_t)e->tokens * H * 4), o_pre_g = wb.take(H * 4), o_pre_b = wb.take(H * 4),
+                 o_ln_g = wb.take(H * 4), o_ln_b = wb.take(H * 4),
+                 o_proj = wb.take((size_t)(d.proj_dim ? d.proj_dim : 0) * H * 2);
+    wb.take_layers(H, M, d.layers);
+    if (wb.alloc() != hipSuccess) {
+        vm_encoder_destroy(e);
+        return vm_fail(ctx, VM_ERR_NOMEM, "encoder weights: hipMalloc(%zu) failed", wb.total);
     }
-    auto copy = [&](size_t off, const void *src, size_t bytes) -> hipError_t {
-        if (bytes == 0) return hipSuccess;
-        if (!src) return hipErrorInvalidValue;
-        return hipMemcpy(e->blob + off, src, bytes, hipMemcpyDeviceToDevice);
-    };
-    er = copy(o_patch_w, wp[0], H * e->patch_k * 2);
-    if (er == hipSuccess) er = d.patch_bias ? copy(o_patch_b, wp[1], H * 4) : hipMemset(e->blob + o_patch_b, 0, H * 4);
-    if (er == hipSuccess) er = copy(o_cls, wp[2], H * 4);
-    if (er == hipSuccess) er = copy(o_pos, wp[3], (size_t)e->tokens * H * 4);
-    if (er == hipSuccess && d.pre_ln) er = copy(o_pre_g, wp[4], H * 4);
-    if (er == hipSuccess && d.pre_ln) er = copy(o_pre_b, wp[5], H * 4);
-    if (er == hipSuccess) er = copy(o_ln_g, wp[6], H * 4);
-    if (er == hipSuccess) er = copy(o_ln_b, wp[7], H * 4);
-    if (er == hipSuccess && d.proj_dim) er = copy(o_proj, wp[8], (size_t)d.proj_dim * H * 2);
+    char *b = e->blob = wb.base;
+    wb.copy(o_patch_w, wp[0], H * e->patch_k * 2);
+    if (d.patch_bias) wb.copy(o_patch_b, wp[1], H * 4);
+    else if (wb.err == hipSuccess) wb.err = hipMemset(b + o_patch_b, 0, H * 4);
+    wb.copy(o_cls, wp[2], H * 4);
+    wb.copy(o_pos, wp[3], (size_t)e->tokens * H * 4);
+    if (d.pre_ln) wb.copy(o_pre_g, wp[4], H * 4);
+    if (d.pre_ln) wb.copy(o_pre_b, wp[5], H * 4);
+    wb.copy(o_ln_g, wp[6], H * 4);
+    wb.copy(o_ln_b, wp[7], H * 4);
+    if (d.proj_dim) wb.copy(o_proj, wp[8], (size_t)d.proj_dim * H * 2);
     e->layers = new LayerW[d.layers];
-    for (int l = 0; l < d.layers && er == hipSuccess; ++l) {
-        for (int i = 0; i < 12 && er == hipSuccess; ++i) er = copy(lo[l].o[i], wp[9 + 12 * l + i], lsz[i]);
-        bind_layer(e->layers[l], e->blob, lo[l].o);
-    }
-    delete[] lo;
-    if (er != hipSuccess) {
+    wb.copy_layers(wp, 9, d.layers, e->layers);
+    if (wb.err != hipSuccess) {
         vm_encoder_destroy(e);
         return vm_fail(ctx, VM_ERR_HIP, "encoder weight copy failed: %s (null or short weight pointer?)",
-                       hipGetErrorString(er));
+                       hipGetErrorString(wb.err));
     }
-    char *b = e->blob;
     e->patch_w = (uint16_t *)(b + o_patch_w);
     e->patch_b = (float *)(b + o_patch_b);
     e->cls = (float *)(b + o_cls);
@@ -776,6 +780,12 @@ struct Tower {
     bool dual;       // two-stream schedule: low-register LayerNorms
     int causal;      // text tower: causal attention
     hipStream_t st;  // the stream the stages launch on
+    // D: vm_encoder_desc or vm_text_encoder_desc
+    template <class D>
+    Tower(vm_ctx *c, const D &d, int tokens, const LayerW *w, int cls_bits, bool two_streams, int causal_mask, hipStream_t s)
+        : ctx(c), dt(d.dtype), H(d.hidden), heads(d.heads), mlp(d.mlp),
+          act_epi(d.act == VM_ACT_QUICK_GELU ? EPI_QGELU16 : EPI_GELU16), layers(d.layers), T(tokens), eps(d.ln_eps), lw(w),
+          cls_env(cls_bits), dual(two_streams), causal(causal_mask), st(s) {}
     bool cls_only() const { return (cls_env & 1) != 0; }
     int gemm16(const uint16_t *X, int ldx, const uint16_t *W, const float *bias, uint16_t *out, int M, int N, int K,
                int epi, int cat, int ldo = 0, int head_major = 0, int hm_rows = 0, int hm_stride = 0) const {
@@ -877,7 +887,6 @@ extern "C" int vm_encode(vm_encoder *e, const void *patches, int B, void *out_em
     hipStream_t st = (hipStream_t)stream;
     const vm_encoder_desc &d = e->d;
     const int H = d.hidden, T = e->tokens, P = e->patches, dt = d.dtype;
-    const int act_epi = d.act == VM_ACT_QUICK_GELU ? EPI_QGELU16 : EPI_GELU16;
     // VM_ENC_OPT_LAST_LAYER: bit 0 = projection / LN2 / MLP of the last layer on the CLS rows only, bit 1 = also only
     // the CLS rows' queries and query tile in its attention; 0 = everything on every row (same embeddings, tests)
     const int cls_env = e->cls_last;
@@ -903,9 +912,7 @@ extern "C" int vm_encode(vm_encoder *e, const void *patches, int B, void *out_em
         VM_HIP(ctx, hipEventRecord(e->ev_fork, st0));
         for (int i = 0; i < 2; ++i) VM_HIP(ctx, hipStreamWaitEvent(e->side[i], e->ev_fork, 0));
     }
-    Tower tw;
-    tw.ctx = ctx; tw.dt = dt; tw.H = H; tw.heads = d.heads; tw.mlp = d.mlp; tw.act_epi = act_epi; tw.layers = d.layers;
-    tw.T = T; tw.eps = d.ln_eps; tw.lw = e->layers; tw.cls_env = cls_env; tw.dual = dual; tw.causal = 0; tw.st = st;
+    Tower tw(ctx, d, T, e->layers, cls_env, dual, 0, st);
     // ---- the stages of one pass (the layer stages are Tower's) ----
     auto embed = [&](Pass &p) -> int {
         // patch embedding: [nb*P, patch_k] x [H, patch_k]^T (+bias) -> 16-bit rows; then x32 = rows + pos (+cls) [+pre-LN]
@@ -920,7 +927,6 @@ extern "C" int vm_encode(vm_encoder *e, const void *patches, int B, void *out_em
         return vm_pool(ctx, dt, p.ws.x32, p.pend_proj, p.pend_fc2, e->ln_g, e->ln_b, d.ln_eps, e->proj_w, d.proj_dim,
                        l2_normalise, dst, p.nb, T, H, st);
     };
-#define VM_TRY(x) do { if ((rc = (x)) != VM_OK) return rc; } while (0)
     auto run_passes = [&]() -> int {
         int pass = 0;
         for (int b0 = 0; b0 < B; ++pass) {
@@ -935,24 +941,23 @@ extern "C" int vm_encode(vm_encoder *e, const void *patches, int B, void *out_em
             static const int phase_env = (int)VM_DEV_ENV("ENC_PHASE", 0);
             const bool mark = dual && phase_env > 0 && pass == 0;
             if (dual && phase_env > 0 && pass == 1) (void)hipStreamWaitEvent(st, e->ev_phase, 0);
-            VM_TRY(embed(A));
+            if ((rc = embed(A)) != VM_OK) return rc;
             for (int l = 0; l < d.layers; ++l) {
-                VM_TRY(tw.ln1(A, l));
+                if ((rc = tw.ln1(A, l)) != VM_OK) return rc;
                 if (mark && l == 0 && phase_env == 1) (void)hipEventRecord(e->ev_phase, st);
-                VM_TRY(tw.attn_block(A, l));
+                if ((rc = tw.attn_block(A, l)) != VM_OK) return rc;
                 if (mark && l == 0 && phase_env == 2) (void)hipEventRecord(e->ev_phase, st);
-                VM_TRY(tw.ln2(A, l));
+                if ((rc = tw.ln2(A, l)) != VM_OK) return rc;
                 if (mark && l == 0 && phase_env == 3) (void)hipEventRecord(e->ev_phase, st);
-                VM_TRY(tw.mlp_block(A, l));
+                if ((rc = tw.mlp_block(A, l)) != VM_OK) return rc;
                 if (mark && l == 0 && phase_env == 4) (void)hipEventRecord(e->ev_phase, st);
                 if (mark && l == 1 && phase_env == 5) (void)hipEventRecord(e->ev_phase, st);   // a layer and a half... (after layer 1's MLP)
             }
-            VM_TRY(pool(A));
+            if ((rc = pool(A)) != VM_OK) return rc;
             b0 += A.nb;
         }
         return VM_OK;
     };
-#undef VM_TRY
     rc = run_passes();
     if (dual) {
         // join, ALSO after a failed launch: kernels already queued on the side streams still use the workspaces, so the
@@ -1003,48 +1008,25 @@ extern "C" int vm_text_encoder_create(vm_ctx *ctx, const vm_text_encoder_desc *d
     e->d = d;
     e->out_dim = d.proj_dim ? d.proj_dim : d.hidden;
     const size_t H = d.hidden, M = d.mlp;
-    size_t total = 0;
-    auto take = [&](size_t bytes) {
-        size_t off = total;
-        total += vm_align_up(bytes, 256);
-        return off;
-    };
     const size_t head_sz[5] = {(size_t)d.vocab * H * 4, (size_t)d.context * H * 4, H * 4, H * 4,
                                (size_t)d.proj_dim * H * 2};
+    WeightBlob wb;
     size_t head_off[5];
-    for (int i = 0; i < 5; ++i) head_off[i] = take(head_sz[i]);
-    size_t lsz[12];
-    layer_sizes(H, M, lsz);
-    struct LO {
-        size_t o[12];
-    };
-    LO *lo = new LO[d.layers];
-    for (int l = 0; l < d.layers; ++l)
-        for (int i = 0; i < 12; ++i) lo[l].o[i] = take(lsz[i]);
-    hipError_t er = hipMalloc((void **)&e->blob, total);
-    if (er != hipSuccess) {
-        delete[] lo;
-        delete e;
-        return vm_fail(ctx, VM_ERR_NOMEM, "text encoder weights: hipMalloc(%zu) failed", total);
+    for (int i = 0; i < 5; ++i) head_off[i] = wb.take(head_sz[i]);
+    wb.take_layers(H, M, d.layers);
+    if (wb.alloc() != hipSuccess) {
+        vm_text_encoder_destroy(e);
+        return vm_fail(ctx, VM_ERR_NOMEM, "text encoder weights: hipMalloc(%zu) failed", wb.total);
     }
-    auto copy = [&](size_t off, const void *src, size_t bytes) -> hipError_t {
-        if (bytes == 0) return hipSuccess;
-        if (!src) return hipErrorInvalidValue;
-        return hipMemcpy(e->blob + off, src, bytes, hipMemcpyDeviceToDevice);
-    };
-    for (int i = 0; i < 5 && er == hipSuccess; ++i) er = copy(head_off[i], wp[i], head_sz[i]);
+    char *b = e->blob = wb.base;
+    for (int i = 0; i < 5; ++i) wb.copy(head_off[i], wp[i], head_sz[i]);
     e->layers = new LayerW[d.layers];
-    for (int l = 0; l < d.layers && er == hipSuccess; ++l) {
-        for (int i = 0; i < 12 && er == hipSuccess; ++i) er = copy(lo[l].o[i], wp[5 + 12 * l + i], lsz[i]);
-        bind_layer(e->layers[l], e->blob, lo[l].o);
-    }
-    delete[] lo;
-    if (er != hipSuccess) {
+    wb.copy_layers(wp, 5, d.layers, e->layers);
+    if (wb.err != hipSuccess) {
         vm_text_encoder_destroy(e);
         return vm_fail(ctx, VM_ERR_HIP, "text encoder weight copy failed: %s (null or short weight pointer?)",
-                       hipGetErrorString(er));
+                       hipGetErrorString(wb.err));
     }
-    char *b = e->blob;
     e->tok = (float *)(b + head_off[0]);
     e->pos = (float *)(b + head_off[1]);
     e->ln_g = (float *)(b + head_off[2]);
@@ -1094,10 +1076,7 @@ extern "C" int vm_text_encode(vm_text_encoder *e, const int32_t *token_ids, int 
     p.ws = carve_rows((size_t)p.rows, d.hidden, d.mlp, workspace);
     p.pend_proj = p.pend_fc2 = nullptr;
     int32_t *pool_row = (int32_t *)((char *)workspace + text_ws_layers(e, B, T));
-    Tower tw;
-    tw.ctx = ctx; tw.dt = d.dtype; tw.H = d.hidden; tw.heads = d.heads; tw.mlp = d.mlp;
-    tw.act_epi = d.act == VM_ACT_QUICK_GELU ? EPI_QGELU16 : EPI_GELU16; tw.layers = d.layers; tw.T = T;
-    tw.eps = d.ln_eps; tw.lw = e->layers; tw.cls_env = 0; tw.dual = false; tw.causal = 1; tw.st = st;
+    const Tower tw(ctx, d, T, e->layers, 0, false, 1, st);
     int rc = vm_text_embed(ctx, token_ids, e->tok, e->pos, d.vocab, d.eot_id, p.ws.x32, pool_row, out_flags, B, T,
                            d.hidden, st);
     for (int l = 0; l < d.layers && rc == VM_OK; ++l) {

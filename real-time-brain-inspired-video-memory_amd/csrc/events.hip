@@ -381,7 +381,7 @@ int events_run(vm_memory *m, bool regroup, double threshold, int64_t max_gap_ms,
                                                           ccount, clast);
     } else {
         auto kern = events_link_stream_kernel<DT>;
-        VM_HIP(ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * EV_BUF));
+        if (int rc = vm_lds_opt_in(ctx, kern, 2 * EV_BUF, "vm_memory_events")) return rc;
         kern<<<p.nch, EV_CHUNK, 2 * EV_BUF, st>>>(m->rows, m->norm64, m->tag, m->d_total, m->cap, m->ring, m->D, from_row,
                                                  threshold, max_gap_ms, out_links, flags, ccount, clast);
     }

@@ -988,6 +988,25 @@ __global__ void __launch_bounds__(256, 2) gemm128_kernel(GemmArgs g) {
 
 int g_variant = 0;  // 0 auto, 1 force 128^2, 2 force 256^2 one tile per block, 3 force 256^2 persistent (tools/gemm_bench, VIDMEM_GEMM)
 
+// One launch of launch_epi: the kernel is granted `grant` bytes of dynamic LDS (vm_lds_opt_in) and started with `lds`.
+template <class K>
+int launch_gemm(vm_ctx *ctx, K kern, int grid, int threads, size_t lds, size_t grant, const GemmArgs &g, hipStream_t st) {
+    if (int r = vm_lds_opt_in(ctx, kern, grant, "vm_gemm")) return r;
+    kern<<<grid, threads, lds, st>>>(g);
+    VM_LAUNCH_CHECK(ctx);
+    return VM_OK;
+}
+#ifdef VM_GEMM_ABLATE
+template <int EPI, int A>   // persistent-kernel ablation A
+int launch_ablp(vm_ctx *ctx, int grid, size_t lds, const GemmArgs &g, hipStream_t st) {
+    return launch_gemm(ctx, gemm256p_kernel<VM_F16, EPI, A>, grid, 512, lds, lds, g, st);
+}
+template <int A>   // one-tile-per-block ablation A
+int launch_ablgo(vm_ctx *ctx, int grid, size_t lds, const GemmArgs &g, hipStream_t st) {
+    return launch_gemm(ctx, gemm256_kernel<VM_F16, EPI_STORE16, A>, grid, 512, lds, lds, g, st);
+}
+#endif
+
 template <int DT, int EPI>
 int launch_epi(vm_ctx *ctx, const GemmArgs &g, hipStream_t st) {
     static const int env_variant = (int)VM_DEV_ENV("GEMM", 0);
@@ -998,79 +1017,43 @@ int launch_epi(vm_ctx *ctx, const GemmArgs &g, hipStream_t st) {
     const bool big_ok = g.N % 256 == 0 && vm_gemm256_tile_addressable(g.K, g.ldx);
     // a 256^2 grid must give (nearly) every CU a tile; below that the 128^2 kernel fills the chip better
     const bool use256 = (variant == 2 || variant == 3) ? big_ok : (variant == 1 ? false : (big_ok && tiles256 * 10 >= ctx->num_cus * 8));
+    const size_t lds_p = 8 * HALF_BYTES + 2048 + 16384 + TAB_LDS;  // persistent: staging + bias slots + epilogue scratch (+ table)
+    const int grid_p = tiles256 < ctx->num_cus ? tiles256 : ctx->num_cus;
 #ifdef VM_GEMM_ABLATE
     if (variant >= 1024 && DT == VM_F16) {  // persistent-kernel ablations: 1024 + ABL bits: 1024 + 8 (no stores) / + 16 (no epilogue)
-        const size_t lds = 8 * HALF_BYTES + 2048 + 16384 + TAB_LDS;
-        const int grid = tiles256 < ctx->num_cus ? tiles256 : ctx->num_cus;
-#define ABLP(A)                                                                                                   \
-    if (variant == 1024 + (A)) {                                                                                  \
-        auto k = gemm256p_kernel<VM_F16, EPI, (A)>;                                                               \
-        (void)hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);        \
-        k<<<grid, 512, lds, st>>>(g);                                                                             \
-        VM_LAUNCH_CHECK(ctx);                                                                                     \
-        return VM_OK;                                                                                             \
-    }
-        ABLP(32) ABLP(64) ABLP(96) ABLP(96 + 16) ABLP(256)
-#undef ABLP
-        if (variant == 1024 + 8) {
-            auto k = gemm256p_kernel<VM_F16, EPI, 8>;
-            (void)hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            k<<<grid, 512, lds, st>>>(g);
-        } else {
-            auto k = gemm256p_kernel<VM_F16, EPI, 16>;
-            (void)hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            k<<<grid, 512, lds, st>>>(g);
+        switch (variant - 1024) {
+            case 32: return launch_ablp<EPI, 32>(ctx, grid_p, lds_p, g, st);
+            case 64: return launch_ablp<EPI, 64>(ctx, grid_p, lds_p, g, st);
+            case 96: return launch_ablp<EPI, 96>(ctx, grid_p, lds_p, g, st);
+            case 96 + 16: return launch_ablp<EPI, 96 + 16>(ctx, grid_p, lds_p, g, st);
+            case 256: return launch_ablp<EPI, 256>(ctx, grid_p, lds_p, g, st);
+            case 8: return launch_ablp<EPI, 8>(ctx, grid_p, lds_p, g, st);
+            default: return launch_ablp<EPI, 16>(ctx, grid_p, lds_p, g, st);
         }
-        VM_LAUNCH_CHECK(ctx);
-        return VM_OK;
     }
     if (variant >= 16 && EPI == EPI_STORE16 && DT == VM_F16) {
         const size_t lds = 8 * HALF_BYTES;
-        const int abl = variant >> 4;
-#define ABLGO(A)                                                                                                  \
-    case A: {                                                                                                     \
-        auto k = gemm256_kernel<VM_F16, EPI_STORE16, A>;                                                          \
-        (void)hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);        \
-        k<<<tiles256, 512, lds, st>>>(g);                                                                         \
-    } break;
-        switch (abl) { ABLGO(1) ABLGO(2) ABLGO(3) ABLGO(4) ABLGO(5) ABLGO(6) ABLGO(7) ABLGO(8) default: break; }
-#undef ABLGO
-        VM_LAUNCH_CHECK(ctx);
-        return VM_OK;
+        switch (variant >> 4) {
+            case 1: return launch_ablgo<1>(ctx, tiles256, lds, g, st);
+            case 2: return launch_ablgo<2>(ctx, tiles256, lds, g, st);
+            case 3: return launch_ablgo<3>(ctx, tiles256, lds, g, st);
+            case 4: return launch_ablgo<4>(ctx, tiles256, lds, g, st);
+            case 5: return launch_ablgo<5>(ctx, tiles256, lds, g, st);
+            case 6: return launch_ablgo<6>(ctx, tiles256, lds, g, st);
+            case 7: return launch_ablgo<7>(ctx, tiles256, lds, g, st);
+            case 8: return launch_ablgo<8>(ctx, tiles256, lds, g, st);
+            default: return VM_OK;
+        }
     }
 #endif
-    if (use256 && variant != 2 && g.N <= 4096) {
-        auto kern = gemm256p_kernel<DT, EPI>;
-        static unsigned long long attr_set_p = 0;   // one bit per device
-        const size_t lds = 8 * HALF_BYTES + 2048 + 16384 + TAB_LDS;  // staging + bias slots + epilogue scratch (+ table)
-        if (!((attr_set_p >> (ctx->device & 63)) & 1ull)) {
-            VM_HIP(ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            163840));
-            attr_set_p |= 1ull << (ctx->device & 63);
-        }
-        const int grid = tiles256 < ctx->num_cus ? tiles256 : ctx->num_cus;
-        kern<<<grid, 512, lds, st>>>(g);
-    } else if (use256) {
-        auto kern = gemm256_kernel<DT, EPI>;
-        static unsigned long long attr_set = 0;   // one bit per device
+    if (use256 && variant != 2 && g.N <= 4096)   // granted the whole 160 KiB, whatever this epilogue's table adds
+        return launch_gemm(ctx, gemm256p_kernel<DT, EPI>, grid_p, 512, lds_p, 163840, g, st);
+    if (use256) {
         const size_t lds = 8 * HALF_BYTES + TAB_LDS;
-        if (!((attr_set >> (ctx->device & 63)) & 1ull)) {
-            VM_HIP(ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            attr_set |= 1ull << (ctx->device & 63);
-        }
-        kern<<<tiles256, 512, lds, st>>>(g);
-    } else {
-        auto kern = gemm128_kernel<DT, EPI>;
-        static unsigned long long attr_set = 0;   // one bit per device
-        const size_t lds = 4 * HALF_BYTES + TAB_LDS;
-        if (!((attr_set >> (ctx->device & 63)) & 1ull)) {
-            VM_HIP(ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            attr_set |= 1ull << (ctx->device & 63);
-        }
-        kern<<<((g.M + 127) / 128) * (g.N / 128), 256, lds, st>>>(g);
+        return launch_gemm(ctx, gemm256_kernel<DT, EPI>, tiles256, 512, lds, lds, g, st);
     }
-    VM_LAUNCH_CHECK(ctx);
-    return VM_OK;
+    const size_t lds = 4 * HALF_BYTES + TAB_LDS;
+    return launch_gemm(ctx, gemm128_kernel<DT, EPI>, ((g.M + 127) / 128) * (g.N / 128), 256, lds, lds, g, st);
 }
 
 template <int DT>

@@ -401,7 +401,7 @@ int summary_run(vm_memory *m, const int64_t *first_group, int64_t max_groups, ui
         const unsigned grid = (unsigned)(p.slots < most ? p.slots : most);
         auto kern = summary_sum_kernel<DT>;
         const size_t lds = (size_t)(m->D + 1) * 16;
-        VM_HIP(ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        if (int rc = vm_lds_opt_in(ctx, kern, lds, "vm_memory_summaries")) return rc;
         kern<<<grid, nt, lds, st>>>(m->rows, m->gord, m->d_total, m->cap, m->ring, m->D, first_group, max_groups, first,
                                    cent, out_n_rows);
         VM_LAUNCH_CHECK(ctx);
@@ -412,7 +412,7 @@ int summary_run(vm_memory *m, const int64_t *first_group, int64_t max_groups, ui
                                                             m->D, first_group, max_groups, first, cent, scores);
     } else {
         auto kern = summary_score_stream_kernel<DT>;
-        VM_HIP(ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * SM_BUF));
+        if (int rc = vm_lds_opt_in(ctx, kern, 2 * SM_BUF, "vm_memory_summaries")) return rc;
         kern<<<p.nch, SM_CHUNK, 2 * SM_BUF, st>>>(m->rows, m->norm64, m->gord, m->d_total, m->cap, m->ring, m->D,
                                                  first_group, max_groups, first, cent, scores);
     }

@@ -748,11 +748,7 @@ int launch_scan(vm_memory *m, const ScanPlan &p, int nblk, int64_t row_limit, co
         if (lb_env == 24) kern = topk_scan_kernel<DT, KL, QT, 24>;
     }
 #endif
-    if (p.lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)p.lds);
-        if (e != hipSuccess) return vm_fail(m->ctx, VM_ERR_HIP, "LDS opt-in %zu: %s", p.lds, hipGetErrorString(e));
-    }
+    if (int rc = vm_lds_opt_in(m->ctx, kern, p.lds, "vm_topk_cosine scan")) return rc;
     const dim3 grid = p.qgroups > 1 ? dim3(nblk * p.qgroups) : dim3(nblk);
     static const int nt_env = (int)VM_DEV_ENV("TOPK_NT", 1);
     const int nt_flag = nt_env && row_limit >= m->cap;  // full passes only: the sampling pre-pass's rows are read again
@@ -861,12 +857,8 @@ int run_topk_kl(vm_memory *m, const ScanPlan &p, const void *queries, int Q, int
         if (with_rows <= 96 * 1024) {
             fin_lds = with_rows;
             stage_rows = 1;
-            if (fin_lds > 48 * 1024) {
-                hipError_t e = hipFuncSetAttribute((const void *)topk_finalize_kernel<DT, KL, false>,
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)fin_lds);
-                if (e != hipSuccess)
-                    return vm_fail(m->ctx, VM_ERR_HIP, "LDS opt-in %zu: %s", fin_lds, hipGetErrorString(e));
-            }
+            if (int rc = vm_lds_opt_in(m->ctx, topk_finalize_kernel<DT, KL, false>, fin_lds, "vm_topk_cosine finalize"))
+                return rc;
         }
     }
     topk_finalize_kernel<DT, KL, false><<<Q, FIN_THREADS, fin_lds, st>>>(

@@ -237,8 +237,8 @@ int diverse_pick(vm_memory *m, const DiverseCall &c, const DPlan &p) {
     const int T = (c.pool + DV_TILE - 1) / DV_TILE;
     const size_t lds = (size_t)DV_TILE * m->D * 2;
     auto kern = diverse_pair_kernel<DT>;
-    if (lds + 16384 > 65536)  // above what a launch gets without the attribute from D = 2,048 on
-        VM_HIP(m->ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    // above what a launch gets without the attribute from D = 2,048 on
+    if (int rc = vm_lds_opt_in(m->ctx, kern, lds, "vm_topk_cosine_diverse")) return rc;
     kern<<<dim3(c.Q, T * (T + 1) / 2), DV_THREADS, lds, c.stream>>>(m->rows, m->norm64, m->d_total, m->cap, m->ring,
                                                                     m->D, c.pool, prow, S);
     VM_LAUNCH_CHECK(m->ctx);

@@ -460,12 +460,7 @@ int vm_topk_gscan(vm_memory *m, const void *queries, int Q, int q_thr, const flo
     static const int qx_env = (int)VM_DEV_ENV("GSCAN_QX", 0);
     g.QX = (qx_env == 1 || qx_env == 2 || qx_env == 4 || qx_env == 8) ? qx_env : best_qx;
     auto kern = m->dtype == VM_F16 ? topk_gscan_kernel<VM_F16> : topk_gscan_kernel<VM_BF16>;
-    static unsigned long long attr_set[2] = {0, 0};   // per dtype, one bit per device
-    if (!((attr_set[m->dtype == VM_F16 ? 0 : 1] >> (m->ctx->device & 63)) & 1ull)) {
-        hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, GS_LDS);
-        if (e != hipSuccess) return vm_fail(m->ctx, VM_ERR_HIP, "gscan LDS opt-in %d: %s", GS_LDS, hipGetErrorString(e));
-        attr_set[m->dtype == VM_F16 ? 0 : 1] |= 1ull << (m->ctx->device & 63);
-    }
+    if (int rc = vm_lds_opt_in(m->ctx, kern, GS_LDS, "gscan")) return rc;
     vm_prof_scope prof(m->ctx, VM_PROF_TOPK_SCAN, st);
     kern<<<m->ctx->num_cus, 512, GS_LDS, st>>>(g);
     VM_LAUNCH_CHECK(m->ctx);

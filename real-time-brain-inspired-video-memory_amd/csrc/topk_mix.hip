@@ -609,23 +609,14 @@ int mix_pack(vm_memory *m, const MixCall &c, const MixBufs &b) {
     return VM_OK;
 }
 
-// the J terms in dynamic LDS: above the 64 KiB a launch gets without the attribute only at J = 16, D = 2,048 (with the
-// kernel's static arrays)
-template <class K>
-int mix_lds_attr(vm_memory *m, K kern, size_t lds) {
-    if (lds + 16384 > 65536)
-        VM_HIP(m->ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    return VM_OK;
-}
-
 template <int DT, int OP, class P>
 int mix_redo(vm_memory *m, const MPlan &p, const MixCall &c, const MixBufs &b, const P &pred) {
     vm_prof_scope prof(m->ctx, VM_PROF_TOPK_EXACT, c.stream);
     double *part_s = (double *)(c.ws + p.off_ps);
     int64_t *part_o = (int64_t *)(c.ws + p.off_po);
-    const size_t lds = (size_t)c.J * m->D * 2;
+    const size_t lds = (size_t)c.J * m->D * 2;   // the J terms in dynamic LDS (the kernels' static arrays beside them)
     auto kern = mix_redo_scan_kernel<DT, OP, P>;
-    if (int rc = mix_lds_attr(m, kern, lds)) return rc;
+    if (int rc = vm_lds_opt_in(m->ctx, kern, lds, "vm_topk_cosine_mix")) return rc;
     kern<<<p.nblk, MIX_THREADS, lds, c.stream>>>(b.tiles, c.weights, b.qn, m->rows, m->norm64, m->d_total, m->cap,
                                                  m->ring, m->D, c.Q, c.J, c.k, b.flags, part_s, part_o, pred);
     VM_LAUNCH_CHECK(m->ctx);
@@ -640,7 +631,7 @@ int fold_terms_out(vm_memory *m, const MixCall &c, const MixBufs &b) {
         if (!c.out_terms) return VM_OK;
         const size_t lds = (size_t)c.J * m->D * 2;
         auto kern = fold_terms_kernel<DT, OP>;
-        if (int rc = mix_lds_attr(m, kern, lds)) return rc;
+        if (int rc = vm_lds_opt_in(m->ctx, kern, lds, "vm_topk_cosine_mix")) return rc;
         kern<<<c.Q, MIX_THREADS, lds, c.stream>>>(m->rows, m->norm64, b.tiles, c.weights, b.qn, m->d_total, m->cap,
                                                   m->ring, m->D, c.J, c.k, c.row_stride, c.row_offset, c.out_rows,
                                                   c.out_terms);
@@ -678,7 +669,7 @@ int mix_run(vm_memory *m, const MixCall &c, bool exact) {
             if (int rc = vm_key_image_select(m, p, F, C, ws, st)) return rc;
             const size_t lds = (size_t)c.J * m->D * 2;
             auto kern = mix_finalize_kernel<DT, OP>;
-            if (int rc = mix_lds_attr(m, kern, lds)) return rc;
+            if (int rc = vm_lds_opt_in(m->ctx, kern, lds, "vm_topk_cosine_mix")) return rc;
             kern<<<C, MIX_THREADS, lds, st>>>(m->rows, m->norm64, b.tiles, c.weights, b.qn, b.A, b.dom, m->d_total,
                                               m->cap, m->ring, m->D, c.J, (const int *)(ws + p.off_co),
                                               (const uint32_t *)(ws + p.off_ck), (const int *)(ws + p.off_cn), p.M, c.k,

@@ -131,17 +131,13 @@ __global__ void __launch_bounds__(TS_THREADS)
 }
 
 // The one launcher.  The kernel's LDS is the query tile (dynamic) plus the policy's per-query state (static); the
-// attribute is set exactly when the two exceed the 64 KiB a launch gets without it.  D is a multiple of 128, so the query
-// tile is a multiple of 4 KiB and the state is below that: with a state the limit is reached at a tile of 64 KiB, without
-// one above it - at every shape the host calls each search made when it had a launcher of its own.
+// context grants the dynamic part (vm_lds_opt_in).
 template <int DT, int QT, class P>
 int vm_tile_scan_qt(vm_memory *m, const ScanGeom &g, const void *queries, int Q, const typename P::Args &a,
                     hipStream_t st) {
-    using QS = typename P::template QState<QT>;
     const size_t lds = (size_t)QT * 16 * m->D * 2;
     auto kern = tile_scan_kernel<DT, QT, P>;
-    if (lds + (std::is_empty<QS>::value ? 0 : sizeof(QS)) > 65536)
-        VM_HIP(m->ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (int rc = vm_lds_opt_in(m->ctx, kern, lds, "tile scan")) return rc;
     kern<<<dim3(g.nbx, g.qgroups), TS_THREADS, lds, st>>>(m->rows, m->rnorm32, (const uint16_t *)queries, m->d_total,
                                                          m->cap, m->ring, m->D, Q, a);
     VM_LAUNCH_CHECK(m->ctx);

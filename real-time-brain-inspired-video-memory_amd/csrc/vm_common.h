@@ -24,10 +24,22 @@ static inline long vm_dev_env_(const char *name, long dflt) {
 #define VM_DEV_ENV(name, dflt) ((long)(dflt))
 #endif
 
+// One dynamic-LDS grant (vm_lds_opt_in, below): the host address of a kernel instantiation and the bytes this context
+// has raised its hipFuncAttributeMaxDynamicSharedMemorySize to.
+struct vm_lds_grant {
+    const void *kern;
+    int bytes;
+};
+// Slots of the open-addressed table, a power of two.  The library holds well over 200 instantiations that opt in (every
+// dtype, epilogue, attention shape, scan plan and search policy); 512 slots, 8 KiB of the context, keep them all, so the
+// full-table path below stays an exception.
+constexpr int VM_LDS_GRANTS = 512;
+
 struct vm_ctx {
     int device;
     int num_cus;
     char err[512];
+    vm_lds_grant lds_grant[VM_LDS_GRANTS];   // all zero = empty, so vm_init's memset builds it
     // optional per-kernel timing (vm_profile_enable): event pool, 2 events + 1 category per launch
     hipEvent_t *prof_ev;
     int *prof_cat;
@@ -85,6 +97,32 @@ inline int vm_fail(vm_ctx *ctx, int code, const char *fmt, ...) {
             return vm_fail((ctx), VM_ERR_HIP, "kernel launch failed: %s (%s:%d)", hipGetErrorString(e_), \
                            __FILE__, __LINE__);                                                        \
     } while (0)
+
+// The one dynamic-LDS opt-in: a launch with `bytes` of dynamic LDS calls this first.  The runtime is asked only when
+// `bytes` exceeds what this context already granted the kernel, so a kernel costs one call at its first use and one more
+// whenever its size grows; a grant is never lowered (it caps launch validation, it is no occupancy input).  The key is
+// the host address of the instantiation and the table is the context's: a context belongs to one device and, like its
+// err buffer, to one thread at a time.  A full table only means the attribute is set on every call.  The runtime keeps
+// one value per kernel and device: a second context on the same device would start from its own empty table and could
+// set a smaller one under the first (the Python layer keeps one context per device and process).
+inline int vm_lds_opt_in_(vm_ctx *ctx, const void *kern, size_t bytes, const char *who) {
+    vm_lds_grant *g = nullptr;
+    const size_t h = ((uintptr_t)kern >> 4) * (size_t)0x9E3779B97F4A7C15ull >> 32;
+    for (int i = 0; i < VM_LDS_GRANTS && !g; ++i) {
+        vm_lds_grant *s = &ctx->lds_grant[(h + i) & (VM_LDS_GRANTS - 1)];
+        if (s->kern == kern || !s->kern) g = s;
+    }
+    if (g && g->kern == kern && (size_t)g->bytes >= bytes) return VM_OK;
+    const hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e != hipSuccess)
+        return vm_fail(ctx, VM_ERR_HIP, "%s: LDS opt-in %zu: %s", who, bytes, hipGetErrorString(e));
+    if (g) *g = {kern, (int)bytes};
+    return VM_OK;
+}
+template <class K>
+int vm_lds_opt_in(vm_ctx *ctx, K kern, size_t bytes, const char *who) {
+    return vm_lds_opt_in_(ctx, (const void *)kern, bytes, who);
+}
 
 static inline size_t vm_align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
