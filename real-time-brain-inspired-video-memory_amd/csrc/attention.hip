@@ -149,224 +149,27 @@ __device__ __forceinline__ void attend_tile(const char *kl, const char *vl, type
     }
 }
 
-// Long rows (577 tokens: 37 key tiles): the whole score row does not fit in registers next to the accumulators
-// (148 VGPRs of scores alone; the single-pass tile spilled ~100 registers).  Two builds: the default ONLINE one
-// (attend_tile_pass2<..., true>: one walk over the keys, lazily raised reference) and, behind VIDMEM_ATTN_ONLINE=0,
-// the two-pass one - this pass 1 computes the scores and keeps only the row maximum, pass 2 recomputes them 32 keys
-// at a time against the known maximum (+50 % QK^T MFMAs, no rescaling).
-template <int DT, int NT, bool EXACT>
-__device__ __forceinline__ float attend_rowmax(const char *kl, typename vm_elem<DT>::vec8 qa,
-                                               typename vm_elem<DT>::vec8 qb, int T, int lane) {
-    using E = vm_elem<DT>;
-    using vec8 = typename E::vec8;
-    const int r16 = lane & 15, h = lane >> 4;
-    // (key & 7) == (r16 & 7) for every key tile: the two swizzled chunk addresses advance by 2 KiB per tile
-    const char *p0 = kl + r16 * 128 + ((h ^ (r16 & 7)) << 4);
-    const char *p1 = kl + r16 * 128 + (((h + 4) ^ (r16 & 7)) << 4);
-    auto tile = [&](int kt, bool masked) {
-        const vec8 k0 = *reinterpret_cast<const vec8 *>(p0 + kt * 2048);
-        const vec8 k1 = *reinterpret_cast<const vec8 *>(p1 + kt * 2048);
-        f32x4 a = f32x4{0.f, 0.f, 0.f, 0.f};
-        a = E::mfma16(k0, qa, a);
-        a = E::mfma16(k1, qb, a);
-        if (masked) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) a[j] = (kt * 16 + 4 * h + j < T) ? a[j] : -INFINITY;
-        }
-        return fmaxf(fmaxf(a[0], a[1]), fmaxf(a[2], a[3]));
-    };
-    float mx0 = -INFINITY, mx1 = -INFINITY;
-    constexpr int FULL = EXACT ? NT - 1 : 0;   // tiles known to lie wholly below T
-    int kt = 0;
-#pragma unroll 1
-    for (; kt + 1 < FULL; kt += 2) {           // a real loop (two independent tiles per trip): unrolled, the
-        mx0 = fmaxf(mx0, tile(kt, false));     // scheduler hoists every K fragment read and spills ~240 registers
-        mx1 = fmaxf(mx1, tile(kt + 1, false));
-    }
-#pragma unroll 1
-    for (; kt < NT; ++kt) mx0 = fmaxf(mx0, tile(kt, kt >= FULL));
-    float mx = fmaxf(mx0, mx1);
-    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    return mx;
-}
-
-// ONLINE: no first pass - a reference value per row is raised step by step and the running sums are rescaled (a
-// wave-uniform branch, taken only in the steps where some row's scores break out of the reference's slack).  Same
-// softmax: exp2((s - m_ref) c) / sum of the same is shift-invariant; only fp32 / 16-bit roundings differ.
-template <int DT, int NT, bool EXACT, bool ONLINE = false>
-__device__ __forceinline__ void attend_tile_pass2(const char *kl, const char *vl, typename vm_elem<DT>::vec8 qa,
-                                                  typename vm_elem<DT>::vec8 qb, float mx, int T, int lane,
-                                                  bool qvalid, uint16_t *dst_row) {
-    using E = vm_elem<DT>;
-    using vec8 = typename E::vec8;
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
-    typedef short s8v __attribute__((__vector_size__(8 * sizeof(short))));
-    constexpr int NS = (NT + 1) / 2;
-    const int r16 = lane & 15, h = lane >> 4;
-    const int tq = r16 >> 2, tp = r16 & 3;
-    const float scale_log2e = 0.125f * 1.44269504088896340736f;
-    constexpr float ONLINE_SLACK = 6.0f;   // scores may exceed the reference by 2^6 in the exponent before a rescale
-    float run_m = ONLINE ? -1e30f : mx;    // reference (ONLINE: lazily raised) or known row maximum
-    float run_hi = -1e30f;                 // ONLINE: run_m + the slack, in score units
-    float neg_mxc = -run_m * scale_log2e;
-    const f32x2 c2 = {scale_log2e, scale_log2e};
-    f32x2 n2 = {neg_mxc, neg_mxc};
-    const char *p0 = kl + r16 * 128 + ((h ^ (r16 & 7)) << 4);
-    const char *p1 = kl + r16 * 128 + (((h + 4) ^ (r16 & 7)) << 4);
-    // V fragments: rows 32*ks + 4h + tq (+16); (row & 7) == ((4h + tq) & 7) for every step -> per-lane constants
-    const int vsw = (4 * h + tq) & 7;
-    const char *vrow = vl + (4 * h + tq) * 128 + (tp & 1) * 8;
-    int voff[4];
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) voff[dt] = ((2 * dt + (tp >> 1)) ^ vsw) << 4;
-    f32x2 sum2 = {0.f, 0.f};
-    f32x4 o[4];
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    // running LDS pointers, advanced by one 32-key step (4 KiB) per trip: every read of a step is base + a small
-    // immediate (the V image sits 74 KiB behind K: as `index * stride + image offset` each of the eight V reads cost
-    // two address instructions per step)
-    lds_cptr kp0 = (lds_cptr)p0, kp1 = (lds_cptr)p1;
-    lds_cptr vp[4];
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) vp[dt] = (lds_cptr)(vrow + voff[dt]);
-    auto step = [&](int ks, bool masked0, bool has1, bool masked1) {
-        // every LDS read of the step is issued up front - the K fragments of both key tiles and the eight transposed V
-        // fragments (they do not depend on P) - so one LDS latency is exposed per 32 keys instead of six
-        const int hi_off = has1 ? 16 * 128 : 0;  // odd NT: the last half step re-reads valid rows against P = 0
-        typedef const __attribute__((address_space(3))) vec8 *lds_vec8_ptr;
-        const vec8 ka0 = *(lds_vec8_ptr)(kp0);
-        const vec8 ka1 = *(lds_vec8_ptr)(kp1);
-        const vec8 kb0 = *(lds_vec8_ptr)(kp0 + (has1 ? 2048 : 0));
-        const vec8 kb1 = *(lds_vec8_ptr)(kp1 + (has1 ? 2048 : 0));
-        s4v vlo[4], vhi[4];
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt) {
-            vlo[dt] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4v_ptr)(vp[dt]));
-            vhi[dt] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4v_ptr)(vp[dt] + hi_off));
-        }
-        kp0 += 4096;
-        kp1 += 4096;
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt) vp[dt] += 4096;
-        // keep them as six loop-carried registers (the compiler otherwise re-derives every address from one induction
-        // variable plus the image offset, which does not fit a ds_read immediate: 14 adds per step instead of 6)
-        asm volatile("" : "+v"(kp0), "+v"(kp1), "+v"(vp[0]), "+v"(vp[1]), "+v"(vp[2]), "+v"(vp[3]));
-        f32x4 a[2];
-        a[0] = E::mfma16(ka0, qa, f32x4{0.f, 0.f, 0.f, 0.f});
-        a[0] = E::mfma16(ka1, qb, a[0]);
-        a[1] = E::mfma16(kb0, qa, f32x4{0.f, 0.f, 0.f, 0.f});
-        a[1] = E::mfma16(kb1, qb, a[1]);
-        if (masked0) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) a[0][j] = ((2 * ks) * 16 + 4 * h + j < T) ? a[0][j] : -INFINITY;
-        }
-        if (!has1) {
-            a[1] = f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-        } else if (masked1) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) a[1][j] = ((2 * ks + 1) * 16 + 4 * h + j < T) ? a[1][j] : -INFINITY;
-        }
-        if (ONLINE) {
-            // LAZY reference: run_m is not the running maximum but a reference the scores may exceed by up to
-            // ONLINE_SLACK (in units of the exponent, i.e. probabilities up to 2^ONLINE_SLACK before the final division:
-            // harmless in fp32 sums and in a 16-bit P, whose relative precision does not depend on its magnitude).
-            // The common step therefore needs no cross-lane traffic at all: every lane tests its OWN eight scores
-            // against the shared reference (one ballot); only when some score breaks out - the first step, and the few
-            // later ones where the row maximum grows by more than the slack - are the two shuffles, the rescale of
-            // the sums and the new reference paid.  (With the reference tied to the exact running maximum every step
-            // carried a dependent chain max -> shuffle -> max -> shuffle -> ballot of ~300 cycles.)
-            if (__ballot(any_above(a[0], a[1], run_hi)) != 0ull) {  // wave-uniform
-                const float lm_own = fmaxf(fmaxf(fmaxf(a[0][0], a[0][1]), fmaxf(a[0][2], a[0][3])),
-                                           fmaxf(fmaxf(a[1][0], a[1][1]), fmaxf(a[1][2], a[1][3])));
-                float lm = fmaxf(lm_own, __shfl_xor(lm_own, 16, 64));
-                lm = fmaxf(lm, __shfl_xor(lm, 32, 64));
-                const float m_new = fmaxf(run_m, lm);  // rows whose scores stayed below keep their reference (f = 1)
-                const float f = __builtin_amdgcn_exp2f((run_m - m_new) * scale_log2e);
-                sum2 *= f32x2{f, f};
-#pragma unroll
-                for (int dt = 0; dt < 4; ++dt) o[dt] *= f32x4{f, f, f, f};
-                run_m = m_new;
-                run_hi = run_m + ONLINE_SLACK / scale_log2e;
-                neg_mxc = -run_m * scale_log2e;
-                n2 = f32x2{neg_mxc, neg_mxc};
-            }
-        }
-        uint16_t pe[8];
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            f32x2 p01 = __builtin_elementwise_fma(f32x2{a[u][0], a[u][1]}, c2, n2);
-            f32x2 p23 = __builtin_elementwise_fma(f32x2{a[u][2], a[u][3]}, c2, n2);
-            p01 = f32x2{__builtin_amdgcn_exp2f(p01.x), __builtin_amdgcn_exp2f(p01.y)};
-            p23 = f32x2{__builtin_amdgcn_exp2f(p23.x), __builtin_amdgcn_exp2f(p23.y)};
-            sum2 += p01 + p23;
-            pe[4 * u + 0] = E::from_float(p01.x);
-            pe[4 * u + 1] = E::from_float(p01.y);
-            pe[4 * u + 2] = E::from_float(p23.x);
-            pe[4 * u + 3] = E::from_float(p23.y);
-        }
-        vec8 pf;
-        __builtin_memcpy(&pf, pe, 16);
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt) {
-            const s8v av = __builtin_shufflevector(vlo[dt], vhi[dt], 0, 1, 2, 3, 4, 5, 6, 7);
-            o[dt] = E::mfma16(__builtin_bit_cast(vec8, av), pf, o[dt]);
-        }
-    };
-    constexpr int FULL_STEPS = EXACT ? (NT - 1) / 2 : 0;  // 32-key steps whose two tiles lie wholly below T
-    int ks = 0;
-#pragma unroll 1
-    for (; ks < FULL_STEPS; ++ks) step(ks, false, true, false);
-#pragma unroll 1
-    for (; ks < NS; ++ks) step(ks, true, 2 * ks + 1 < NT, true);
-
-    float sum = sum2.x + sum2.y;
-    sum += __shfl_xor(sum, 16, 64);
-    sum += __shfl_xor(sum, 32, 64);
-    const float inv = 1.0f / sum;
-    if (qvalid) {
-        uint16_t *dst = dst_row + 4 * h;
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt) {
-            uint16_t oe[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) oe[j] = ctx_value<E>(o[dt][j], inv);
-            uint2 pk;
-            __builtin_memcpy(&pk, oe, 8);
-            *reinterpret_cast<uint2 *>(dst + dt * 16) = pk;
-        }
-    }
-}
-
+// Long rows (577 tokens: 37 key tiles): the whole score row does not fit in registers next to the accumulators (148 VGPRs
+// of scores alone), so the keys are walked once, 32 at a time, with an ONLINE softmax: exp2((s - m_ref) c) / sum of the
+// same is shift-invariant, so any reference m_ref gives the same result up to fp32 / 16-bit roundings.
+// LAZY reference: m_ref is not the running maximum but a value the scores may exceed by up to ONLINE_SLACK (in units of
+// the exponent, i.e. probabilities up to 2^ONLINE_SLACK before the final division: harmless in fp32 sums and in a 16-bit
+// P, whose relative precision does not depend on its magnitude).  The common step therefore needs no cross-lane traffic
+// at all: every lane tests its OWN scores against the shared reference (one ballot); only when some score breaks out -
+// the first step, and the few later ones where the row maximum grows by more than the slack - are the two shuffles, the
+// rescale of the sums and the new reference paid.  (With the reference tied to the exact running maximum every step
+// carried a dependent chain max -> shuffle -> max -> shuffle -> ballot of ~300 cycles.)
+// Every LDS read of a step is issued up front - the K fragments of both key tiles and the eight transposed V fragments
+// (they do not depend on P) - so one LDS latency is exposed per 32 keys instead of six.
 // TWO query tiles per wave and walk (32 queries): the K and V fragments of a 32-key step are read from LDS once and feed
 // both tiles' MFMAs, and the two tiles' softmax chains (MFMA -> max test -> exp2 -> pack -> MFMA) are independent
-// instruction streams inside one wave, so one chain's latencies are covered by the other's work.  Same lazily raised
-// reference per tile as the one-tile walk.  Measured (CLIP-L/14-336 bf16, 448 frames, ms of attention): one tile per
-// walk, 16 waves 26.0; pairs, 8 / 10 / 12 waves 27.4 (before the address trimming) / 28.3 / 24.9 - a 4 % gain, i.e.
-// the walk is not latency-bound; what it IS bound by has not been found (matrix pipe 24 % busy, LDS ~27 %, the
-// vector port ~65 % by instruction count; the K/V fill of a workgroup is 17 % of its life and overlaps nothing).
-// ABL (developer library only, VIDMEM_ATTN_ABL): COMPILE-TIME ablations of the walk - 1 no exponentials, 2 no P.V MFMAs,
-// 4 no K/V fill (kernel), 8 no Q.K MFMAs, 16 no V fragment reads, 32 no K fragment reads.  (A first probe with RUNTIME
-// switches perturbed the kernel by 20 % with every switch off)  Results are garbage under any of them.
-// ABL (developer library only, VIDMEM_ATTN_ABL): COMPILE-TIME ablations of the walk - 1 no exponentials, 2 no P.V MFMAs,
-// 4 no K/V fill (kernel), 8 no Q.K MFMAs, 16 no V fragment reads, 32 no K fragment reads.  (A first probe with RUNTIME
-// switches perturbed the kernel by 20 % with every switch off)  Results are garbage under any of them.
-// s_waitcnt vmcnt(n) for a wave-uniform n known only at run time (the count field is an immediate)
-__device__ __forceinline__ void wait_vmcnt_dyn(int n) {
-#define VM_W(N) case N: asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory"); break;
-    switch (n) {
-        VM_W(1) VM_W(2) VM_W(3) VM_W(4) VM_W(5) VM_W(6) VM_W(7) VM_W(8) VM_W(9) VM_W(10) VM_W(11) VM_W(12) VM_W(13)
-        VM_W(14) VM_W(15) VM_W(16) VM_W(17) VM_W(18) VM_W(19) VM_W(20) VM_W(21) VM_W(22) VM_W(23) VM_W(24) VM_W(25)
-        VM_W(26) VM_W(27) VM_W(28) VM_W(29) VM_W(30) VM_W(31) VM_W(32) VM_W(33) VM_W(34) VM_W(35) VM_W(36) VM_W(37)
-        VM_W(38) VM_W(39) VM_W(40) VM_W(41) VM_W(42) VM_W(43) VM_W(44) VM_W(45) VM_W(46) VM_W(47) VM_W(48)
-        default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;   // 0, and anything unexpected: wait for all
-    }
-#undef VM_W
-}
-
-template <int DT, int NT, bool EXACT, int ABL = 0>
+// instruction streams inside one wave, so one chain's latencies are covered by the other's work.  Measured (CLIP-L/14-336
+// bf16, 448 frames, ms of attention): one tile per walk, 16 waves 26.0; pairs, 8 / 10 / 12 waves 27.4 (before the address
+// trimming) / 28.3 / 24.9 - a 4 % gain, i.e. the walk is not latency-bound; what it IS bound by has not been found
+// (matrix pipe 24 % busy, LDS ~27 %, the vector port ~65 % by instruction count; the K/V fill of a workgroup is 17 % of
+// its life and overlaps nothing).  The one-tile walk, the two-pass softmax before it, the 8- and 10-wave builds and the
+// compile-time ablations of this walk are patches now: tools/experiments/attention_retired_variants.patch, DESIGN.md 4.3.
+template <int DT, int NT, bool EXACT>
 __device__ __forceinline__ void attend_pair_online(const char *kl, const char *vl,
                                                    const typename vm_elem<DT>::vec8 (&qa)[2],
                                                    const typename vm_elem<DT>::vec8 (&qb)[2], int T, int lane,
@@ -403,25 +206,15 @@ __device__ __forceinline__ void attend_pair_online(const char *kl, const char *v
     auto step = [&](int ks, bool masked0, bool has1, bool masked1) {
         const int hi_off = has1 ? 16 * 128 : 0;
         typedef const __attribute__((address_space(3))) vec8 *lds_vec8_ptr;
-        vec8 ka0, ka1, kb0, kb1;
-        if (ABL & 32) {
-            ka0 = ka1 = qa[0];
-            kb0 = kb1 = qb[0];
-        } else {
-            ka0 = *(lds_vec8_ptr)(kp0);
-            ka1 = *(lds_vec8_ptr)(kp1);
-            kb0 = *(lds_vec8_ptr)(kp0 + (has1 ? 2048 : 0));
-            kb1 = *(lds_vec8_ptr)(kp1 + (has1 ? 2048 : 0));
-        }
+        const vec8 ka0 = *(lds_vec8_ptr)(kp0);
+        const vec8 ka1 = *(lds_vec8_ptr)(kp1);
+        const vec8 kb0 = *(lds_vec8_ptr)(kp0 + (has1 ? 2048 : 0));
+        const vec8 kb1 = *(lds_vec8_ptr)(kp1 + (has1 ? 2048 : 0));
         s4v vlo[4], vhi[4];
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt) {
-            if (ABL & 16) {
-                vlo[dt] = vhi[dt] = __builtin_bit_cast(s4v, (unsigned long long)(0x3c003c003c003c00ull + dt));
-            } else {
-                vlo[dt] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4v_ptr)(vp[dt]));
-                vhi[dt] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4v_ptr)(vp[dt] + hi_off));
-            }
+            vlo[dt] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4v_ptr)(vp[dt]));
+            vhi[dt] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4v_ptr)(vp[dt] + hi_off));
         }
         kp0 += 4096;
         kp1 += 4096;
@@ -434,17 +227,10 @@ __device__ __forceinline__ void attend_pair_online(const char *kl, const char *v
         bool out_of_slack = false;
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
-            if (ABL & 8) {   // scores without the matrix pipe: something data-dependent and finite, one move each
-                const f32x4 ua = __builtin_bit_cast(f32x4, ka0), ub = __builtin_bit_cast(f32x4, kb0);
-                a[t][0] = f32x4{1.f, 2.f, 3.f, 4.f} + f32x4{ua[0] * 0.f, 0.f, 0.f, 0.f};
-                a[t][1] = f32x4{4.f, 3.f, 2.f, 1.f} + f32x4{ub[0] * 0.f, 0.f, 0.f, 0.f};
-                asm volatile("" : "+v"(a[t][0]), "+v"(a[t][1]) : "v"(ka1), "v"(kb1));
-            } else {
-                a[t][0] = E::mfma16(ka0, qa[t], f32x4{0.f, 0.f, 0.f, 0.f});
-                a[t][0] = E::mfma16(ka1, qb[t], a[t][0]);
-                a[t][1] = E::mfma16(kb0, qa[t], f32x4{0.f, 0.f, 0.f, 0.f});
-                a[t][1] = E::mfma16(kb1, qb[t], a[t][1]);
-            }
+            a[t][0] = E::mfma16(ka0, qa[t], f32x4{0.f, 0.f, 0.f, 0.f});
+            a[t][0] = E::mfma16(ka1, qb[t], a[t][0]);
+            a[t][1] = E::mfma16(kb0, qa[t], f32x4{0.f, 0.f, 0.f, 0.f});
+            a[t][1] = E::mfma16(kb1, qb[t], a[t][1]);
         }
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
@@ -489,10 +275,8 @@ __device__ __forceinline__ void attend_pair_online(const char *kl, const char *v
             for (int u = 0; u < 2; ++u) {
                 f32x2 p01 = __builtin_elementwise_fma(f32x2{a[t][u][0], a[t][u][1]}, c2, n2[t]);
                 f32x2 p23 = __builtin_elementwise_fma(f32x2{a[t][u][2], a[t][u][3]}, c2, n2[t]);
-                if (!(ABL & 1)) {
-                    p01 = f32x2{__builtin_amdgcn_exp2f(p01.x), __builtin_amdgcn_exp2f(p01.y)};
-                    p23 = f32x2{__builtin_amdgcn_exp2f(p23.x), __builtin_amdgcn_exp2f(p23.y)};
-                }
+                p01 = f32x2{__builtin_amdgcn_exp2f(p01.x), __builtin_amdgcn_exp2f(p01.y)};
+                p23 = f32x2{__builtin_amdgcn_exp2f(p23.x), __builtin_amdgcn_exp2f(p23.y)};
                 sum2[t] += p01 + p23;
                 pe[4 * u + 0] = E::from_float(p01.x);
                 pe[4 * u + 1] = E::from_float(p01.y);
@@ -508,19 +292,11 @@ __device__ __forceinline__ void attend_pair_online(const char *kl, const char *v
         for (int dt = 0; dt < 4; ++dt)
             av[dt] = __builtin_bit_cast(vec8, __builtin_shufflevector(vlo[dt], vhi[dt], 0, 1, 2, 3, 4, 5, 6, 7));
         const vec8 pf0 = softmax_pack(0);
-        if (ABL & 2) {
-            asm volatile("" ::"v"(pf0), "v"(av[0]), "v"(av[1]), "v"(av[2]), "v"(av[3]));
-        } else {
 #pragma unroll
-            for (int dt = 0; dt < 4; ++dt) o[0][dt] = E::mfma16(av[dt], pf0, o[0][dt]);
-        }
+        for (int dt = 0; dt < 4; ++dt) o[0][dt] = E::mfma16(av[dt], pf0, o[0][dt]);
         const vec8 pf1 = softmax_pack(1);
-        if (ABL & 2) {
-            asm volatile("" ::"v"(pf1));
-        } else {
 #pragma unroll
-            for (int dt = 0; dt < 4; ++dt) o[1][dt] = E::mfma16(av[dt], pf1, o[1][dt]);
-        }
+        for (int dt = 0; dt < 4; ++dt) o[1][dt] = E::mfma16(av[dt], pf1, o[1][dt]);
         // schedule of the region above: (1 MFMA, 2 transcendentals) x 4 - tile 0's MFMAs over tile 1's exponentials
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -559,7 +335,7 @@ __device__ __forceinline__ void attend_pair_online(const char *kl, const char *v
 // One workgroup of NW waves per (frame, head), every wave walks PAIRS of query tiles (attend_pair_online): pairs wave,
 // wave + NW, ...  With 37 tiles = 19 pairs and 12 waves seven waves take two pairs and five take one (16 waves with
 // one tile per walk: five waves take three tiles while eleven take two).
-template <int DT, int NT, bool EXACT, int NW, int ABL = 0>
+template <int DT, int NT, bool EXACT, int NW>
 __global__ void __launch_bounds__(NW * 64, 1)
     attention_pair_kernel(const uint16_t *__restrict__ qkv, uint16_t *__restrict__ ctx_out, int T, int heads,
                           int qt_lim) {
@@ -604,10 +380,8 @@ __global__ void __launch_bounds__(NW * 64, 1)
         load_q(2 * wave, qa[0], qb[0]);
         load_q(2 * wave + 1, qa[1], qb[1]);
     }
-    if (!(ABL & 4)) {
-        stage(1, kl);
-        stage(2, vl);
-    }
+    stage(1, kl);
+    stage(2, vl);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     for (int pr = wave; pr < npairs; pr += NW) {
@@ -625,7 +399,7 @@ __global__ void __launch_bounds__(NW * 64, 1)
             load_q(2 * (pr + NW), qa[0], qb[0]);
             load_q(2 * (pr + NW) + 1, qa[1], qb[1]);
         }
-        attend_pair_online<DT, NT, EXACT, ABL>(kl, vl, ca, cb, T, lane, qvalid, dst);
+        attend_pair_online<DT, NT, EXACT>(kl, vl, ca, cb, T, lane, qvalid, dst);
     }
 }
 
@@ -719,7 +493,7 @@ __global__ void __launch_bounds__(NW * 64, 1)
                 load_q(next, 2 * wave, qa[0], qb[0]);   // (a prefetching wave loads it behind its LDS writes instead:
                 load_q(next, 2 * wave + 1, qa[1], qb[1]);   // 16 registers it needs for the rows, latency it can afford)
             }
-            attend_pair_online<DT, NT, EXACT, 0>(kl, vl, ca, cb, T, lane, qvalid, dst);
+            attend_pair_online<DT, NT, EXACT>(kl, vl, ca, cb, T, lane, qvalid, dst);
         }
         if (!has_next) break;
         // the waves that are done early fetch the next item's rows into registers while the others still walk.  A wave
@@ -765,70 +539,14 @@ __global__ void __launch_bounds__(NW * 64, 1)
     }
 }
 
-// One workgroup of NW waves per (frame, head): K rows by LDS-DMA, barrier; the V rows' LDS-DMA is issued next and
-// lands while every wave runs pass 1 of its first query tile; then tiles wave, wave + NW, ...
-template <int DT, int NT, bool EXACT, int NW, bool ONLINE>
-__global__ void __launch_bounds__(NW * 64, 1)
-    attention_long_kernel(const uint16_t *__restrict__ qkv, uint16_t *__restrict__ ctx_out, int T, int heads,
-                          int qt_lim) {
-    using E = vm_elem<DT>;
-    using vec8 = typename E::vec8;
-    constexpr int ROWS = NT * 16;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    char *kl = smem, *vl = smem + (size_t)ROWS * 128;
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int r16 = lane & 15, h = lane >> 4;
-    const int b = blockIdx.x / heads, head = blockIdx.x - b * heads;
-    const int H = heads * 64;
-    const size_t M = (size_t)(gridDim.x / heads) * T;
-    auto block = [&](int part) { return qkv + ((size_t)(part * heads + head) * M + (size_t)b * T) * 64; };
-    auto load_q = [&](int qt, vec8 &q0, vec8 &q1) {
-        int qtok = qt * 16 + r16;
-        if (qtok > T - 1) qtok = T - 1;
-        const uint16_t *qp = block(0) + (size_t)qtok * 64;
-        q0 = __builtin_bit_cast(vec8, *reinterpret_cast<const uint4 *>(qp + 8 * h));
-        q1 = __builtin_bit_cast(vec8, *reinterpret_cast<const uint4 *>(qp + 32 + 8 * h));
-    };
-    const int srow = lane >> 3, scp = lane & 7;
-    auto stage = [&](int part, char *dst) {  // rows past T re-read row T-1 (masked / P = 0 later)
-        const char *src = reinterpret_cast<const char *>(block(part));
-#pragma unroll 4
-        for (int grp = wave; grp < ROWS / 8; grp += NW) {
-            int key = grp * 8 + srow;
-            key = key > T - 1 ? T - 1 : key;
-            __builtin_amdgcn_global_load_lds((gbl_ptr_t)(src + (size_t)key * 128 + ((scp ^ srow) << 4)),
-                                             (lds_ptr_t)(dst + grp * 1024), 16, 0, 2);  // nt: read once
-        }
-    };
-    vec8 q0, q1;
-    load_q(wave, q0, q1);
-    stage(1, kl);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    stage(2, vl);
-    float mx = 0.f;
-    if (!ONLINE && wave < qt_lim) mx = attend_rowmax<DT, NT, EXACT>(kl, q0, q1, T, lane);  // needs K only: overlaps the V fill
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    for (int qt = wave; qt < qt_lim; qt += NW) {
-        const int qtok = qt * 16 + r16;
-        const bool qvalid = qtok < T;
-        const vec8 qa = q0, qb = q1;
-        if (qt + NW < qt_lim) load_q(qt + NW, q0, q1);
-        if (!ONLINE && qt != wave) mx = attend_rowmax<DT, NT, EXACT>(kl, qa, qb, T, lane);
-        attend_tile_pass2<DT, NT, EXACT, ONLINE>(kl, vl, qa, qb, mx, T, lane, qvalid,
-                                         ctx_out + ((size_t)b * T + (qvalid ? qtok : 0)) * H + head * 64);
-    }
-}
-
-// The launches of launch_long, one per kernel family: lds = the K | V image, ql = query tiles wanted (<= NT).
-template <int DT, int NT, bool EXACT, int NWV, int ABL = 0>   // ABL: developer ablations of the 12-wave build
+// The launches of launch_long, one per kernel: lds = the K | V image, ql = query tiles wanted (<= NT).  Twelve waves, three
+// per SIMD (NW stays a template parameter of the kernels, whose fill and pair loops are written for any count).
+template <int DT, int NT, bool EXACT>
 int launch_pair(vm_ctx *ctx, const uint16_t *qkv, uint16_t *out, int items, int T, int heads, hipStream_t st, int ql,
                 size_t lds) {
-    auto kern = attention_pair_kernel<DT, NT, EXACT, NWV, ABL>;
+    auto kern = attention_pair_kernel<DT, NT, EXACT, 12>;
     if (int r = vm_lds_opt_in(ctx, kern, lds, "vm_attention")) return r;
-    kern<<<items, NWV * 64, lds, st>>>(qkv, out, T, heads, ql);
+    kern<<<items, 12 * 64, lds, st>>>(qkv, out, T, heads, ql);
     VM_LAUNCH_CHECK(ctx);
     return VM_OK;
 }
@@ -841,44 +559,12 @@ int launch_persist(vm_ctx *ctx, const uint16_t *qkv, uint16_t *out, int items, i
     VM_LAUNCH_CHECK(ctx);
     return VM_OK;
 }
-template <int DT, int NT, bool EXACT, bool ONLINE>
-int launch_long16(vm_ctx *ctx, const uint16_t *qkv, uint16_t *out, int items, int T, int heads, hipStream_t st, int ql,
-                  size_t lds) {
-    auto kern = attention_long_kernel<DT, NT, EXACT, 16, ONLINE>;
-    if (int r = vm_lds_opt_in(ctx, kern, lds, "vm_attention")) return r;
-    kern<<<items, 1024, lds, st>>>(qkv, out, T, heads, ql);
-    VM_LAUNCH_CHECK(ctx);
-    return VM_OK;
-}
-#ifdef VM_DEV_SWITCHES
-// VIDMEM_ATTN_ABL = one of As: that ablation of the 12-wave pair kernel, its status in *rc; false = none of them asked for
-template <int DT, int NT, bool EXACT, int... As>
-bool launch_pair_abl(int abl, int *rc, vm_ctx *ctx, const uint16_t *qkv, uint16_t *out, int items, int T, int heads,
-                     hipStream_t st, int ql, size_t lds) {
-    return ((abl == As && ((*rc = launch_pair<DT, NT, EXACT, 12, As>(ctx, qkv, out, items, T, heads, st, ql, lds)), true)) || ...);
-}
-#endif
 
 template <int DT, int NT, bool EXACT>
 int launch_long(vm_ctx *ctx, const uint16_t *qkv, uint16_t *out, int B, int T, int heads, hipStream_t st, int qt_lim) {
     const size_t lds = (size_t)NT * 16 * 128 * 2;
-    // 16 waves (4 per SIMD; the kernel needs ~80 VGPRs).  Measured on the two-pass build: 21.1 ms vs 27.0 ms with 8
-    // waves per 256-frame CLIP-L pass
-    static const int online_env = (int)VM_DEV_ENV("ATTN_ONLINE", 1);
-    static const int pair_env = (int)VM_DEV_ENV("ATTN_PAIR", 12);   // waves of the two-tiles-per-walk kernel; 0 = one tile per walk
     vm_prof_scope prof(ctx, VM_PROF_ATTENTION, st);
     const int ql = qt_lim < NT ? qt_lim : NT, items = B * heads;
-    if (!online_env) return launch_long16<DT, NT, EXACT, false>(ctx, qkv, out, items, T, heads, st, ql, lds);
-    if (pair_env <= 0) return launch_long16<DT, NT, EXACT, true>(ctx, qkv, out, items, T, heads, st, ql, lds);
-#ifdef VM_DEV_SWITCHES
-    static const int abl_env = (int)VM_DEV_ENV("ATTN_ABL", 0);
-    if constexpr (NT == 37 && DT == VM_BF16) {
-        int rc = VM_OK;
-        if (launch_pair_abl<DT, NT, EXACT, 1, 2, 4, 8, 16, 32, 3, 10, 48, 63>(abl_env, &rc, ctx, qkv, out, items, T, heads, st,
-                                                                              ql, lds))
-            return rc;
-    }
-#endif
     // persistent walk with the next item's rows prefetched into the idle waves' registers: when their share fits
     static const int persist_env = (int)VM_DEV_ENV("ATTN_PERSIST", 1);
     const int npairs = (ql + 1) / 2, maxc = (npairs + 11) / 12;
@@ -888,17 +574,9 @@ int launch_long(vm_ctx *ctx, const uint16_t *qkv, uint16_t *out, int B, int T, i
     constexpr int PF_FEW = (GROUPS + 4) / 5;            // 16-byte registers per lane with five prefetching waves
     constexpr int PF_MANY = (GROUPS + 10) / 11;         // ... with eleven (one pair to walk: the last layer's CLS rows)
     const int pf = (GROUPS + (12 - w0) - 1) / (12 - w0);
-    if (persist_env && pair_env == 12 && pf <= PF_MANY) {
-        return launch_persist<DT, NT, EXACT, PF_MANY>(ctx, qkv, out, items, T, heads, st, ql, lds);
-    } else if (persist_env && pair_env == 12 && pf <= PF_FEW) {
-        return launch_persist<DT, NT, EXACT, PF_FEW>(ctx, qkv, out, items, T, heads, st, ql, lds);
-    } else if (pair_env == 8) {
-        return launch_pair<DT, NT, EXACT, 8>(ctx, qkv, out, items, T, heads, st, ql, lds);
-    } else if (pair_env == 10) {
-        return launch_pair<DT, NT, EXACT, 10>(ctx, qkv, out, items, T, heads, st, ql, lds);
-    } else {
-        return launch_pair<DT, NT, EXACT, 12>(ctx, qkv, out, items, T, heads, st, ql, lds);
-    }
+    if (persist_env && pf <= PF_MANY) return launch_persist<DT, NT, EXACT, PF_MANY>(ctx, qkv, out, items, T, heads, st, ql, lds);
+    if (persist_env && pf <= PF_FEW) return launch_persist<DT, NT, EXACT, PF_FEW>(ctx, qkv, out, items, T, heads, st, ql, lds);
+    return launch_pair<DT, NT, EXACT>(ctx, qkv, out, items, T, heads, st, ql, lds);
 }
 
 // NT = key tiles of 16 (13 for 197 tokens, 37 for 577).  EXACT: T > 16*(NT-1), so only the last tile has masked keys
@@ -1044,8 +722,12 @@ __global__ void __launch_bounds__((CW + 1) * 64, 1)
     }
 }
 
-template <int DT, int NT, bool EXACT, int CW>
-int launch_stream_cw(vm_ctx *ctx, const uint16_t *qkv, uint16_t *out, int B, int T, int heads, hipStream_t st, int qt_lim) {
+// 13 compute waves (one query tile each, four waves per SIMD at <= 128 registers) + the loader.  (Eight compute waves
+// with up to two tiles each, 168 registers, were the first shape: DESIGN.md 4.3.  CW stays a template parameter of the
+// kernel, whose QT loop is written for any count.)
+template <int DT, int NT, bool EXACT>
+int launch_stream(vm_ctx *ctx, const uint16_t *qkv, uint16_t *out, int B, int T, int heads, hipStream_t st, int qt_lim) {
+    constexpr int CW = 13;
     const size_t lds = (size_t)NT * 16 * 128 * 6;
     auto kern = attention_stream_kernel<DT, NT, EXACT, CW>;
     if (int r = vm_lds_opt_in(ctx, kern, lds, "vm_attention")) return r;
@@ -1058,16 +740,6 @@ int launch_stream_cw(vm_ctx *ctx, const uint16_t *qkv, uint16_t *out, int B, int
     VM_LAUNCH_CHECK(ctx);
     return VM_OK;
 }
-
-template <int DT, int NT, bool EXACT>
-int launch_stream(vm_ctx *ctx, const uint16_t *qkv, uint16_t *out, int B, int T, int heads, hipStream_t st, int qt_lim) {
-    // 13 compute waves (one query tile each, four waves per SIMD at <= 128 registers) + the loader; VIDMEM_ATTN_CW=8:
-    // eight compute waves with up to two tiles each (168 registers)
-    static const int cw_env = (int)VM_DEV_ENV("ATTN_CW", 13);
-    if (cw_env == 8) return launch_stream_cw<DT, NT, EXACT, 8>(ctx, qkv, out, B, T, heads, st, qt_lim);
-    return launch_stream_cw<DT, NT, EXACT, 13>(ctx, qkv, out, B, T, heads, st, qt_lim);
-}
-
 
 template <int DT, int NT, bool EXACT, int OCC = (NT <= 13 ? 2 : 1), bool CAUSAL = false>
 int launch(vm_ctx *ctx, const uint16_t *qkv, uint16_t *out, int B, int T, int heads, hipStream_t st, int qt_lim) {

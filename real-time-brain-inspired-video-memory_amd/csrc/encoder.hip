@@ -575,7 +575,7 @@ struct vm_encoder {
     // matrix-bound GEMMs of the other; see vm_encode.  AUTO = two streams unless per-kernel timing is on.
     int schedule;
     hipStream_t side[2];
-    hipEvent_t ev_fork, ev_join[2], ev_phase;   // ev_phase: developer experiment (start offset of the second stream)
+    hipEvent_t ev_fork, ev_join[2];
 };
 
 static int round_up(int x, int a) { return (x + a - 1) / a * a; }
@@ -614,7 +614,6 @@ extern "C" int vm_encoder_create(vm_ctx *ctx, const vm_encoder_desc *desc, const
             if (he == hipSuccess) he = hipEventCreateWithFlags(&e->ev_join[i], hipEventDisableTiming);
         }
         if (he == hipSuccess) he = hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming);
-        if (he == hipSuccess) he = hipEventCreateWithFlags(&e->ev_phase, hipEventDisableTiming);
         if (he != hipSuccess) {
             vm_encoder_destroy(e);   // destroys whatever was created so far
             return vm_fail(ctx, VM_ERR_HIP, "encoder streams: %s", hipGetErrorString(he));
@@ -669,7 +668,6 @@ extern "C" void vm_encoder_destroy(vm_encoder *e) {
         if (e->ev_join[i]) (void)hipEventDestroy(e->ev_join[i]);
     }
     if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
-    if (e->ev_phase) (void)hipEventDestroy(e->ev_phase);
     if (e->blob) (void)hipFree(e->blob);
     delete[] e->layers;
     delete e;
@@ -936,22 +934,12 @@ extern "C" int vm_encode(vm_encoder *e, const void *patches, int B, void *out_em
             A.rows = A.nb * T;
             A.ws = dual && (pass & 1) ? ws1 : ws0;
             st = tw.st = dual ? e->side[pass & 1] : st0;    // the stages launch on `st`
-            // developer experiment (VIDMEM_ENC_PHASE = n, measured null: DESIGN.md 4.6): the second stream starts behind
-            // the n-th stage of the first pass's first layer instead of together with it
-            static const int phase_env = (int)VM_DEV_ENV("ENC_PHASE", 0);
-            const bool mark = dual && phase_env > 0 && pass == 0;
-            if (dual && phase_env > 0 && pass == 1) (void)hipStreamWaitEvent(st, e->ev_phase, 0);
             if ((rc = embed(A)) != VM_OK) return rc;
             for (int l = 0; l < d.layers; ++l) {
                 if ((rc = tw.ln1(A, l)) != VM_OK) return rc;
-                if (mark && l == 0 && phase_env == 1) (void)hipEventRecord(e->ev_phase, st);
                 if ((rc = tw.attn_block(A, l)) != VM_OK) return rc;
-                if (mark && l == 0 && phase_env == 2) (void)hipEventRecord(e->ev_phase, st);
                 if ((rc = tw.ln2(A, l)) != VM_OK) return rc;
-                if (mark && l == 0 && phase_env == 3) (void)hipEventRecord(e->ev_phase, st);
                 if ((rc = tw.mlp_block(A, l)) != VM_OK) return rc;
-                if (mark && l == 0 && phase_env == 4) (void)hipEventRecord(e->ev_phase, st);
-                if (mark && l == 1 && phase_env == 5) (void)hipEventRecord(e->ev_phase, st);   // a layer and a half... (after layer 1's MLP)
             }
             if ((rc = pool(A)) != VM_OK) return rc;
             b0 += A.nb;

@@ -97,10 +97,12 @@ __device__ __forceinline__ EvScan ev_block_scan(int v, int last, int *s_sum, int
 }
 
 // ---- link, the simple form -----------------------------------------------------------------------------------------
-// Every lane runs ref_dot on global memory, as range.hip's rescore does.  Kept as the yardstick of the streamed form:
-// reached through a developer switch only (VIDMEM_EVENTS_SIMPLE=1 in libvidmem_dev.so, tools/event_probe.py).
+// Every lane runs ref_dot on global memory, as range.hip's rescore does.  Kept as the yardstick of the streamed form and
+// compiled into the developer library only (vm_common.h, VM_DEV_ENV): VIDMEM_EVENTS_SIMPLE=1 in libvidmem_dev.so,
+// tools/event_probe.py.
 // Block c owns the age orders [256 c, 256 c + 256).  flags[o] = row o opens an event; ccount[c] / clast[c] = the
 // chunk's flags and its last flagged age order (-1: none), over the covered rows only.
+#ifdef VM_DEV_SWITCHES
 template <int DT>
 __global__ void __launch_bounds__(EV_CHUNK)
     events_link_kernel(const uint16_t *__restrict__ rows, const double *__restrict__ norm64,
@@ -133,6 +135,7 @@ __global__ void __launch_bounds__(EV_CHUNK)
         clast[blockIdx.x] = r.last;
     }
 }
+#endif  // VM_DEV_SWITCHES
 
 // ---- link, streamed through LDS ------------------------------------------------------------------------------------
 // LDS row j of a buffer holds the slice of age order 256 c - 1 + j (row 0: the halo); lane t sums rows t and t + 1.
@@ -375,11 +378,14 @@ int events_run(vm_memory *m, bool regroup, double threshold, int64_t max_gap_ms,
     int32_t *ccount = (int32_t *)(ws + p.off_cc), *clast = (int32_t *)(ws + p.off_cl);
     int32_t *cbase = (int32_t *)(ws + p.off_cb), *cprev = (int32_t *)(ws + p.off_cp);
     vm_prof_scope prof(ctx, VM_PROF_TOPK_EXACT, st);
+#ifdef VM_DEV_SWITCHES
     if (VM_DEV_ENV("EVENTS_SIMPLE", 0)) {
         events_link_kernel<DT><<<p.nch, EV_CHUNK, 0, st>>>(m->rows, m->norm64, m->tag, m->d_total, m->cap, m->ring,
                                                           m->D, from_row, threshold, max_gap_ms, out_links, flags,
                                                           ccount, clast);
-    } else {
+    } else
+#endif
+    {
         auto kern = events_link_stream_kernel<DT>;
         if (int rc = vm_lds_opt_in(ctx, kern, 2 * EV_BUF, "vm_memory_events")) return rc;
         kern<<<p.nch, EV_CHUNK, 2 * EV_BUF, st>>>(m->rows, m->norm64, m->tag, m->d_total, m->cap, m->ring, m->D, from_row,

@@ -217,8 +217,10 @@ __global__ void __launch_bounds__(1024)
 }
 
 // ---- score, the simple form -----------------------------------------------------------------------------------------
-// Every lane runs ref_dot and ref_sumsq on global memory.  Kept as the yardstick of the streamed form: reached through
-// a developer switch only (VIDMEM_SUMMARY_SIMPLE=1 in libvidmem_dev.so, tools/summary_probe.py).
+// Every lane runs ref_dot and ref_sumsq on global memory.  Kept as the yardstick of the streamed form and compiled into
+// the developer library only (vm_common.h, VM_DEV_ENV): VIDMEM_SUMMARY_SIMPLE=1 in libvidmem_dev.so,
+// tools/summary_probe.py.
+#ifdef VM_DEV_SWITCHES
 template <int DT>
 __global__ void __launch_bounds__(SM_CHUNK)
     summary_score_kernel(const uint16_t *__restrict__ rows, const double *__restrict__ norm64,
@@ -235,6 +237,7 @@ __global__ void __launch_bounds__(SM_CHUNK)
     const double cn = __dsqrt_rn(ref_sumsq<DT>(c, D));
     scores[o] = ref_cosine(ref_dot<DT>(c, rows + (size_t)slot * D, D), cn, norm64[slot]);
 }
+#endif  // VM_DEV_SWITCHES
 
 // ---- score, streamed through LDS -------------------------------------------------------------------------------------
 // LDS row t of a buffer holds the slice of age order 256 c + t; lane t sums its own row against its group's centroid.
@@ -407,10 +410,13 @@ int summary_run(vm_memory *m, const int64_t *first_group, int64_t max_groups, ui
         VM_LAUNCH_CHECK(ctx);
     }
     if (!keys) return VM_OK;  // no second pass over the rows
+#ifdef VM_DEV_SWITCHES
     if (VM_DEV_ENV("SUMMARY_SIMPLE", 0)) {
         summary_score_kernel<DT><<<p.nch, SM_CHUNK, 0, st>>>(m->rows, m->norm64, m->gord, m->d_total, m->cap, m->ring,
                                                             m->D, first_group, max_groups, first, cent, scores);
-    } else {
+    } else
+#endif
+    {
         auto kern = summary_score_stream_kernel<DT>;
         if (int rc = vm_lds_opt_in(ctx, kern, 2 * SM_BUF, "vm_memory_summaries")) return rc;
         kern<<<p.nch, SM_CHUNK, 2 * SM_BUF, st>>>(m->rows, m->norm64, m->gord, m->d_total, m->cap, m->ring, m->D,

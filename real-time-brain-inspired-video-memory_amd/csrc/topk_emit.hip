@@ -534,19 +534,13 @@ int launch_emit(vm_memory *m, const void *queries, int Q, const float *thr_s, co
 template <int DT, int KS>
 int launch_emit_ng(vm_memory *m, const void *queries, int Q, const float *thr_s, const int *thr_o, int *cand_cnt,
                    float *cand_s, int *cand_o, int64_t row_begin, int64_t row_limit, hipStream_t st) {
-    // bit 0: one group per wave (<= 128 queries), bit 1: two groups per wave.  Measured on 1 M x 768 (A/B on one box):
-    // 256 queries 0.547 -> 0.528 ms with the deep schedule, 64 queries 0.312 -> 0.327 ms (a bandwidth-bound scan is not
-    // short of bytes in flight; the second barrier only costs)
-    static const int deep_env = (int)VM_DEV_ENV("EMIT_DEEP", 2);
+    // The deep schedule for two groups per wave only, not for one (<= 128 queries).  Measured on 1 M x 768 (A/B on one
+    // box): 256 queries 0.547 -> 0.528 ms with the deep schedule, 64 queries 0.312 -> 0.327 ms (a bandwidth-bound scan is
+    // not short of bytes in flight; the second barrier only costs)
     if constexpr (KS <= 6) {  // two query groups per wave need 2 x 16 KS registers for the queries alone (192 of 256 at
-        if (Q > EM_QPB) {     // D = 768: checked spill-free with -Rpass-analysis=kernel-resource-usage)
-            if (deep_env & 2)
-                return launch_emit<DT, KS, 2, true>(m, queries, Q, thr_s, thr_o, cand_cnt, cand_s, cand_o, row_begin, row_limit, st);
-            return launch_emit<DT, KS, 2, false>(m, queries, Q, thr_s, thr_o, cand_cnt, cand_s, cand_o, row_begin, row_limit, st);
-        }
+        if (Q > EM_QPB)       // D = 768: checked spill-free with -Rpass-analysis=kernel-resource-usage)
+            return launch_emit<DT, KS, 2, true>(m, queries, Q, thr_s, thr_o, cand_cnt, cand_s, cand_o, row_begin, row_limit, st);
     }
-    if (deep_env & 1)
-        return launch_emit<DT, KS, 1, true>(m, queries, Q, thr_s, thr_o, cand_cnt, cand_s, cand_o, row_begin, row_limit, st);
     return launch_emit<DT, KS, 1, false>(m, queries, Q, thr_s, thr_o, cand_cnt, cand_s, cand_o, row_begin, row_limit, st);
 }
 

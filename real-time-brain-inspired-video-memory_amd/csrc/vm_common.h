@@ -14,6 +14,12 @@
 // default: no environment variable selects which kernel produces product results, and no VIDMEM_* name appears in
 // libvidmem.so.  tools/dev_build.sh builds with -DVM_DEV_SWITCHES, where each is read from the environment once per
 // process.  What a deployment may choose is an explicit per-handle option (vm_encoder_set_option, include/vidmem.h).
+//
+// The rule: the release library contains exactly the kernels a release call can launch.  A VM_DEV_ENV
+// switch may steer between paths the release dispatch reaches as well, or set a number.  A kernel that only a
+// non-default value reaches is instantiated by an ordinary `if` on the switch all the same, so it is either compiled,
+// with its launch branch, under #ifdef VM_DEV_SWITCHES (events.hip and summary.hip, the simple forms; topk.hip, SCAN_LB),
+// or, once the measurement is settled, retired to a patch under tools/experiments/ together with its switch.
 #ifdef VM_DEV_SWITCHES
 static inline long vm_dev_env_(const char *name, long dflt) {
     const char *e = getenv(name);

@@ -341,15 +341,16 @@ def test_bench_size_batches_take_the_big_kernels_and_agree(name, dtype, n):
 
 
 def test_long_attention_variants_agree(tmp_path):
-    """The 577-token attention has four builds (csrc/attention.hip): two query tiles per walk with a lazily raised
-    softmax reference, as a PERSISTENT workgroup per CU whose idle waves fetch the next (frame, head)'s K / V rows into
-    registers during the walk (what the release library runs); the same walk with one workgroup per item and an LDS-DMA
-    fill (VIDMEM_ATTN_PERSIST=0) - identical bits required, on a batch that gives some CUs two items and in both the
-    all-rows and the CLS-rows-only layer; one tile per walk (VIDMEM_ATTN_PAIR=0); and the two-pass softmax
-    against the exact row maximum (VIDMEM_ATTN_ONLINE=0).  Same softmax in all of them: the embeddings may differ by the
-    rounding of the 16-bit probabilities only.  The other builds are reachable only in the DEVELOPER library
-    (make -C csrc dev: -DVM_DEV_SWITCHES; the release library reads no environment variable), where the switches are
-    read once per process, hence one child process per variant; skipped when that library has not been built."""
+    """The 577-token attention has two builds (csrc/attention.hip), both of which the release dispatch reaches: two query
+    tiles per walk with a lazily raised softmax reference, as a PERSISTENT workgroup per CU whose idle waves fetch the
+    next (frame, head)'s K / V rows into registers during the walk (what the release library runs when the idle waves'
+    share fits); and the same walk with one workgroup per item and an LDS-DMA fill, its fallback, forced here by
+    VIDMEM_ATTN_PERSIST=0 - identical bits required, on a batch that gives some CUs two items and in both the all-rows
+    and the CLS-rows-only layer.  The switch exists only in the DEVELOPER library (make -C csrc dev: -DVM_DEV_SWITCHES;
+    the release library reads no environment variable), where it is read once per process, hence one child process per
+    variant; skipped when that library has not been built.  (The one-tile walk and the two-pass softmax this test also
+    compared are retired: tools/experiments/attention_retired_variants.patch.  The online softmax is pinned to fp64 by
+    the long37_* arms of tests/stage_cases.py.)"""
     import subprocess
     import sys
     from vidmem import _lib
@@ -372,17 +373,9 @@ np.save(sys.argv[2], enc.encode_patches(enc.patches_from_pixels(torch.from_numpy
 '''
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     outs = {}
-    for name, env in (("pair", {}), ("one_item", {"VIDMEM_ATTN_PERSIST": "0"}), ("single", {"VIDMEM_ATTN_PAIR": "0"}),
-                      ("two_pass", {"VIDMEM_ATTN_ONLINE": "0"})):
+    for name, env in (("pair", {}), ("one_item", {"VIDMEM_ATTN_PERSIST": "0"})):
         path = str(tmp_path / f"{name}.npy")
         subprocess.check_call([sys.executable, "-c", prog, root, path], env=dict(os.environ, **env))
         outs[name] = np.load(path)
     assert np.isfinite(outs["pair"]).all()
     assert np.array_equal(outs["one_item"], outs["pair"]), rel(outs["one_item"], outs["pair"])
-    for name in ("single", "two_pass"):
-        d = rel(outs[name], outs["pair"])
-        print(f"{name} vs pair: {d:.2e}")
-        # one tile per walk is the same arithmetic (measured: bit-identical); the two-pass build exponentiates against a
-        # different reference, so every 16-bit probability rounds independently (fp16: 2^-11 = 4.9e-4 per value;
-        # measured 3.5e-4 on the embedding of this two-layer stack)
-        assert d < (1e-6 if name == "single" else 6e-4), (name, d)
