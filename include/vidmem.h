@@ -901,6 +901,63 @@ int vm_topk_cosine_clip_exact(vm_memory *mem, const void *clips, int C, int L, i
                               const int64_t *scope_lo, const int64_t *scope_hi, int use_min_score, double min_score,
                               int score_mode, double *out_scores, int64_t *out_rows, void *workspace,
                               size_t workspace_bytes, void *stream);
+/* Sequence search: where do J ORDERED steps occur in the memory, each at most max_step rows after the one before -
+ * "someone opens the door, THEN sits down, THEN picks up the phone".  The clip search scores step i against row r + i
+ * exactly; here the steps may be text embeddings (no frame rate), the scene may play faster or slower, and the novelty gate
+ * may have thinned the rows: the alignment is a dynamic programme over the rows, and a hit is reported by its END row.
+ * steps [C, J, D] dtype, 1 <= J <= 16, 1 <= max_step = G <= 16, 1 <= k <= 64, 1 <= min_sep <= 32, C >= 1 (VM_ERR_INVALID
+ * outside); any memory (plain, grouped, tagged, ring).  max_gap_ms as in vm_topk_cosine_clip; >= 0 on an untagged memory:
+ * VM_ERR_INVALID.  masks / n_masks / mask_index: exactly vm_topk_cosine_masked's operand, one mask per sequence; masks NULL
+ * = every live row (n_masks and mask_index are then ignored).
+ * Eligibility: row r is ELIGIBLE for sequence c iff it is live and c's mask selects it.
+ * Step score: e_j(r) = the raw reference cosine of step j and row r, vm_topk_cosine's fp64 value, 0.0 when either norm is 0.
+ * Chains: rows r_0 < r_1 < ... < r_{J-1}, every r_j eligible, 1 <= r_j - r_{j-1} <= G and, on a tagged memory, no row in
+ *   r_{j-1}+1 .. r_j with a TAG BREAK against its predecessor (vm_topk_cosine_clip's rule, max_gap_ms between ADJACENT rows
+ *   included).  A chain never spans two videos; it may step over rows that the mask does not select.
+ * Score, in fp64, one rounding per operation, never fused:
+ *   P_0(r) = 0.0 + e_0(r) for eligible r;
+ *   for j >= 1 and eligible r: among the d in 1 .. G for which P_{j-1}(r - d) exists and the tag rule allows the step, the
+ *   largest P_{j-1}(r - d), ties to the SMALLEST d; pred_j(r) = r - d; P_j(r) = that value + e_j(r).  P_j(r) does not exist
+ *   when r is not eligible or no such d exists;
+ *   A(r) = P_{J-1}(r) / (double)J; r is an END iff A(r) exists.
+ *   Rounding is monotone, so A(r) is the maximum over all chains ending at r of the left-to-right rounded sum of the chain's
+ *   step scores, divided by J; and A(r) does not decrease when G grows (the chains of G are chains of G + 1).
+ * Peaks: a COMPETITOR of r is an END r' != r with |r' - r| < min_sep; r is a PEAK iff it ranks before every competitor in
+ *   (raw A descending, end row ascending): local-maximum suppression, not greedy, as in the clip search.
+ * Result per sequence: the peaks in that order, the score_mode mapping, the strict > min_score filter on the shown score,
+ *   first k.  out_scores [C,k] the shown fp64 value bit for bit; out_rows [C,k] the END row ids (no stride or offset);
+ *   out_step_rows [C,k,J] int64 (may be NULL) the chain r_0 .. r_{J-1} obtained by following pred back from the end;
+ *   out_step_scores [C,k,J] fp64 (may be NULL) e_j(r_j) bit for bit.  Padding 0.0 / -1 / -1 / 0.0.  The result depends on the
+ *   memory, the sequence, its mask and its own arguments only.
+ * Identities: J = 1, min_sep = 1 is vm_topk_cosine (with a mask: vm_topk_cosine_masked); G = 1 without a mask is
+ *   vm_topk_cosine_clip with L = J and the same min_sep, max_gap_ms, score mode and filter, out_rows = its rows + J - 1;
+ *   G = 1 with the mask of a scope (vm_mask_from_scopes) is the clip search with that scope.
+ * ALWAYS the exhaustive answer: the clip search's fp32 scan of the 16 C steps, the J layers in fp64 over those scores per
+ *   segment of end rows (each layer moves no more than its most-moved argument: the fp32 image of A lies within eps_seq =
+ *   2 (D + 8) 2^-24 + 2^-23 of A), the clip search's possible-peak filter and selection, the exact layers on the cone of each
+ *   of the best k + slack candidates, and a sequence whose result cannot be proven is counted in *out_uncertified (may be
+ *   NULL; accumulates), marked in out_query_flags [C] (vm_topk_flag; may be NULL) and redone exhaustively on the device
+ *   inside the same call - exact layers over all rows -, as is every sequence with a step norm, or a stored row's norm,
+ *   neither 0 nor in [2^-40, 2^40].  Every live row is scanned: a mask does not skip tiles.
+ * No allocation, no synchronisation, no host read-back; the row count, the steps and the masks are read on the device and
+ * the grids are sized from the capacity: capturable.  Errors are reported before any launch, the outputs untouched:
+ * VM_ERR_INVALID for a count out of range, NULL steps / out_scores / out_rows, a NaN min_score with use_min_score, a mask
+ * operand vm_topk_cosine_mix refuses, a workspace not 256-byte or steps not 16-byte aligned; VM_ERR_NOMEM for a workspace
+ * below vm_topk_seq_workspace_bytes (0 for arguments out of range); VM_ERR_UNSUPPORTED above 2^30 words of masks.
+ * Workspace: 64 x C x capacity bytes of fp32 scores + 24 x C x capacity of end scores, keys and the two exact layers of
+ *   the redo + 64 KiB x C and a few MB. */
+size_t vm_topk_seq_workspace_bytes(const vm_memory *mem, int C, int J, int k);
+int vm_topk_cosine_seq(vm_memory *mem, const void *steps, int C, int J, int k, int max_step, int min_sep,
+                       int64_t max_gap_ms, const uint32_t *masks, int n_masks, const int32_t *mask_index,
+                       int use_min_score, double min_score, int score_mode, double *out_scores, int64_t *out_rows,
+                       int64_t *out_step_rows, double *out_step_scores, int32_t *out_uncertified,
+                       int32_t *out_query_flags, void *workspace, size_t workspace_bytes, void *stream);
+/* The same contract, exhaustive only: the exact layers over all rows for every sequence (slow; tests, and a checker). */
+int vm_topk_cosine_seq_exact(vm_memory *mem, const void *steps, int C, int J, int k, int max_step, int min_sep,
+                             int64_t max_gap_ms, const uint32_t *masks, int n_masks, const int32_t *mask_index,
+                             int use_min_score, double min_score, int score_mode, double *out_scores, int64_t *out_rows,
+                             int64_t *out_step_rows, double *out_step_scores, void *workspace, size_t workspace_bytes,
+                             void *stream);
 /* Range search: EVERY row above a threshold, in time order - "which frames of this video show X?" has no k.  The
  * threshold is the reference's own notion of relevance (`vector.similarity.cosine(...) > 0.3`,
  * src/pipeline/retriever_hybrid.py:296-298; `>= compression_threshold`, :494-504); this call returns all of what passes

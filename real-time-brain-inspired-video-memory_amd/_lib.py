@@ -52,6 +52,7 @@ SYMBOLS = [
     "vm_bias_from_rows", "vm_bias_from_tags",
     "vm_topk_diverse_workspace_bytes", "vm_topk_cosine_diverse", "vm_topk_cosine_diverse_exact",
     "vm_topk_clip_workspace_bytes", "vm_topk_cosine_clip", "vm_topk_cosine_clip_exact",
+    "vm_topk_seq_workspace_bytes", "vm_topk_cosine_seq", "vm_topk_cosine_seq_exact",
     "vm_range_workspace_bytes", "vm_range_cosine", "vm_range_cosine_exact",
     "vm_memory_events_workspace_bytes", "vm_memory_events", "vm_memory_regroup_events", "vm_memory_group_ordinals",
     "vm_memory_summaries_workspace_bytes", "vm_memory_summaries",
@@ -181,6 +182,11 @@ def lib() -> C.CDLL:
         "vm_topk_clip_workspace_bytes": (sz, [vp, i32, i32, i32]),
         "vm_topk_cosine_clip": (i32, [vp, vp, i32, i32, i32, i32, i64, vp, vp, i32, f64, i32, vp, vp, vp, vp, vp, sz, vp]),
         "vm_topk_cosine_clip_exact": (i32, [vp, vp, i32, i32, i32, i32, i64, vp, vp, i32, f64, i32, vp, vp, vp, sz, vp]),
+        "vm_topk_seq_workspace_bytes": (sz, [vp, i32, i32, i32]),
+        "vm_topk_cosine_seq": (i32, [vp, vp, i32, i32, i32, i32, i32, i64, vp, i32, vp, i32, f64, i32, vp, vp, vp, vp, vp,
+                                     vp, vp, sz, vp]),
+        "vm_topk_cosine_seq_exact": (i32, [vp, vp, i32, i32, i32, i32, i32, i64, vp, i32, vp, i32, f64, i32, vp, vp, vp, vp,
+                                           vp, sz, vp]),
         "vm_range_workspace_bytes": (sz, [vp, i32]),
         "vm_range_cosine": (i32, [vp, vp, i32, f64, i32, vp, vp, i64, i64, i64, vp, vp, vp, vp, vp, sz, vp]),
         "vm_range_cosine_exact": (i32, [vp, vp, i32, f64, i32, vp, vp, i64, i64, i64, vp, vp, vp, vp, sz, vp]),

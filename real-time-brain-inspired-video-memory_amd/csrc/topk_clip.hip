@@ -25,7 +25,7 @@
 //   redo     : flagged clips: exact W of every valid in-scope window into an fp64 array, the exact peak test on that array,
 //              a stable top-k of peaks per slice, then vm_topk_redo_merge.  Near-empty when nothing is flagged.
 // Every launch reads the row count and the scopes from the device and sizes its grid from the capacity: capturable.
-#include "topk_scope_select.h"
+#include "topk_clip_parts.h"
 #include "topk_tile_scan.h"
 
 #include <climits>
@@ -33,25 +33,13 @@
 
 namespace {
 
-constexpr int CLIP_LMAX = 16;      // frames per clip = queries per scan tile
-constexpr int CLIP_SEPMAX = 32;    // min_sep
 constexpr int CLIP_NDMAX = 2 * CLIP_SEPMAX - 1;  // a candidate and its competitors
 constexpr int CW_THREADS = 256;    // one thread per start row
 constexpr int CR_CHUNK = 1024;     // windows per selection pass of the redo
-constexpr int64_t CLIP_MS_MASK = ((int64_t)1 << 40) - 1;  // a tag = source << 40 | milliseconds
 
 // |Bf(r) - W(r)| <= eps_w inside the certificate's domain: cert_eps(D) per term and so for their mean,
 // below 2^-24 * 1.001 for the one fp32 rounding of |B| <= 1 + eps, below 2^-47 for the fp64 roundings of both sums
 __device__ __forceinline__ double clip_eps_w(int D) { return cert_eps(D) + 1.1920928955078125e-07; }
-
-// the tag part of vm_memory_events' opening rule (events.hip ev_opens) between a row and its successor
-__device__ __forceinline__ bool clip_tag_break(int64_t tp, int64_t tc, int64_t max_gap_ms) {
-    const bool up = tp == LLONG_MIN, uc = tc == LLONG_MIN;
-    if (up != uc) return true;
-    if (up) return false;
-    const int64_t step = (tc & CLIP_MS_MASK) - (tp & CLIP_MS_MASK);
-    return (tp >> 40) != (tc >> 40) || (max_gap_ms >= 0 && (step < 0 || step > max_gap_ms));
-}
 
 // window o (age order of its start row) is valid and in scope: all L rows live, no tag break inside, every tag in [lo, hi]
 __device__ __forceinline__ bool clip_window_ok(const RingView &rv, const int64_t *__restrict__ tag, int64_t o, int L,
@@ -501,12 +489,8 @@ struct ClipCall {
     int64_t *out_rows;
 };
 
-template <int DT>
 int clip_pack(vm_memory *m, const CPlan &p, const ClipCall &a, char *ws, hipStream_t st) {
-    clip_pack_kernel<DT><<<dim3(CLIP_LMAX, a.C), 64, 0, st>>>((const uint16_t *)a.clips, a.L, m->D,
-                                                             (uint16_t *)(ws + p.off_qt), (double *)(ws + p.off_qn));
-    VM_LAUNCH_CHECK(m->ctx);
-    return VM_OK;
+    return vm_clip_pack(m, a.clips, a.C, a.L, (uint16_t *)(ws + p.off_qt), (double *)(ws + p.off_qn), st);
 }
 
 template <int DT>
@@ -522,9 +506,7 @@ int clip_redo(vm_memory *m, const CPlan &p, const ClipCall &a, char *ws, hipStre
         m->rows, m->norm64, (const uint16_t *)(ws + p.off_qt), (const double *)(ws + p.off_qn), m->d_total, m->cap,
         m->ring, m->D, a.L, m->tag, a.scope_lo, a.scope_hi, a.max_gap_ms, flags, p.fstride, W64);
     VM_LAUNCH_CHECK(ctx);
-    clip_redo_slice_kernel<<<dim3(p.nblk, a.C), CW_THREADS, 0, st>>>(m->d_total, m->cap, m->ring, a.min_sep, a.C, a.k,
-                                                                     flags, p.fstride, W64, part_s, part_o);
-    VM_LAUNCH_CHECK(ctx);
+    if (int rc = vm_clip_redo_slices(m, p.nblk, a.C, a.k, a.min_sep, flags, p.fstride, W64, part_s, part_o, st)) return rc;
     return vm_topk_redo_merge(m, part_s, part_o, p.nblk, a.C, a.k, flags, a.use_min, a.min_score, a.score_mode, 1, 0,
                               a.out_scores, a.out_rows, nullptr, nullptr, st);
 }
@@ -547,10 +529,8 @@ int clip_topk(vm_memory *m, const ClipCall &a, int32_t *out_uncertified, int32_t
     int *flags = (int *)(ws + p.off_flags);
     {
         vm_prof_scope prof(ctx, VM_PROF_TOPK_SCAN, st);
-        if (int rc = clip_pack<DT>(m, p, a, ws, st)) return rc;
-        const int rc = vm_tile_scan<DT, ClipScan>(m, p, qt, a.C * CLIP_LMAX,
-                                                  {m->tag, a.scope_lo, a.scope_hi, p.fstride, S}, st);
-        if (rc != VM_OK) return rc;
+        if (int rc = clip_pack(m, p, a, ws, st)) return rc;
+        if (int rc = vm_clip_scan(m, p, qt, a.C, a.scope_lo, a.scope_hi, p.fstride, S, st)) return rc;
     }
     {
         vm_prof_scope prof(ctx, VM_PROF_TOPK_FINALIZE, st);
@@ -558,18 +538,16 @@ int clip_topk(vm_memory *m, const ClipCall &a, int32_t *out_uncertified, int32_t
         clip_window_kernel<<<wgrid, CW_THREADS, 0, st>>>(m->d_total, m->cap, m->ring, m->tag, a.scope_lo, a.scope_hi,
                                                         a.max_gap_ms, a.L, S, p.fstride, qn, Bf);
         VM_LAUNCH_CHECK(ctx);
-        clip_peak_kernel<<<wgrid, CW_THREADS, 0, st>>>(m->d_total, m->cap, m->ring, m->D, a.min_sep, Bf, p.fstride, key);
-        VM_LAUNCH_CHECK(ctx);
+        if (int rc = vm_clip_peaks(m, a.C, a.min_sep, Bf, p.fstride, key, st)) return rc;
         if (int rc = vm_key_image_select(m, p, key, a.C, ws, st)) return rc;
         clip_rescore_kernel<DT><<<dim3(p.M + 1, a.C), CW_THREADS, 0, st>>>(
             m->rows, m->norm64, qt, qn, m->d_total, m->cap, m->ring, m->D, a.L, a.min_sep, Bf, p.fstride, cand_o, cand_n,
             cand_w, cand_p);
         VM_LAUNCH_CHECK(ctx);
-        clip_rank_kernel<DT><<<a.C, SF_THREADS, 0, st>>>(m->d_total, m->cap, m->ring, m->D, a.L, qn, cand_o, cand_k,
-                                                        cand_n, cand_w, cand_p, p.M, a.k, a.use_min, a.min_score,
-                                                        a.score_mode, a.out_scores, a.out_rows, out_uncertified, flags,
-                                                        out_query_flags);
-        VM_LAUNCH_CHECK(ctx);
+        if (int rc = vm_clip_rank(m, a.C, a.L, qn, cand_o, cand_k, cand_n, cand_w, cand_p, p.M, a.k, a.use_min,
+                                  a.min_score, a.score_mode, a.out_scores, a.out_rows, out_uncertified, flags,
+                                  out_query_flags, st))
+            return rc;
     }
     return clip_redo<DT>(m, p, a, ws, st);
 }
@@ -577,12 +555,57 @@ int clip_topk(vm_memory *m, const ClipCall &a, int32_t *out_uncertified, int32_t
 template <int DT>
 int clip_exact(vm_memory *m, const ClipCall &a, char *ws, hipStream_t st) {
     const CPlan p = clip_plan(m, a.C, a.k);
-    if (int rc = clip_pack<DT>(m, p, a, ws, st)) return rc;
+    if (int rc = clip_pack(m, p, a, ws, st)) return rc;
     if (int rc = vm_fill_flags(m, (int32_t *)(ws + p.off_flags), a.C, st)) return rc;
     return clip_redo<DT>(m, p, a, ws, st);
 }
 
 }  // namespace
+
+// ---- the launchers of topk_clip_parts.h ----------------------------------------------------------------------
+int vm_clip_pack(vm_memory *m, const void *vectors, int C, int L, uint16_t *qt, double *qn, hipStream_t st) {
+    return vm_by_dtype(m, [&](auto dt) -> int {
+        clip_pack_kernel<decltype(dt)::value><<<dim3(CLIP_LMAX, C), 64, 0, st>>>((const uint16_t *)vectors, L, m->D, qt, qn);
+        VM_LAUNCH_CHECK(m->ctx);
+        return VM_OK;
+    });
+}
+
+int vm_clip_scan(vm_memory *m, const ScanGeom &g, const uint16_t *qt, int C, const int64_t *scope_lo,
+                 const int64_t *scope_hi, int64_t fstride, float *S, hipStream_t st) {
+    return vm_by_dtype(m, [&](auto dt) -> int {
+        return vm_tile_scan<decltype(dt)::value, ClipScan>(m, g, qt, C * CLIP_LMAX,
+                                                           {m->tag, scope_lo, scope_hi, fstride, S}, st);
+    });
+}
+
+int vm_clip_peaks(vm_memory *m, int C, int min_sep, const float *Bf, int64_t fstride, uint32_t *key, hipStream_t st) {
+    const dim3 wgrid((unsigned)((m->cap + CW_THREADS - 1) / CW_THREADS), C);
+    clip_peak_kernel<<<wgrid, CW_THREADS, 0, st>>>(m->d_total, m->cap, m->ring, m->D, min_sep, Bf, fstride, key);
+    VM_LAUNCH_CHECK(m->ctx);
+    return VM_OK;
+}
+
+int vm_clip_rank(vm_memory *m, int C, int L, const double *qn, const int *cand_o, const uint32_t *cand_k,
+                 const int *cand_n, const double *cand_w, const int *cand_p, int M, int k, int use_min, double min_score,
+                 int score_mode, double *out_scores, int64_t *out_rows, int32_t *uncertified, int32_t *flags,
+                 int32_t *user_flags, hipStream_t st) {
+    return vm_by_dtype(m, [&](auto dt) -> int {
+        clip_rank_kernel<decltype(dt)::value><<<C, SF_THREADS, 0, st>>>(
+            m->d_total, m->cap, m->ring, m->D, L, qn, cand_o, cand_k, cand_n, cand_w, cand_p, M, k, use_min, min_score,
+            score_mode, out_scores, out_rows, uncertified, flags, user_flags);
+        VM_LAUNCH_CHECK(m->ctx);
+        return VM_OK;
+    });
+}
+
+int vm_clip_redo_slices(vm_memory *m, int nblk, int C, int k, int min_sep, const int32_t *flags, int64_t fstride,
+                        const double *W64, double *part_s, int64_t *part_o, hipStream_t st) {
+    clip_redo_slice_kernel<<<dim3(nblk, C), CW_THREADS, 0, st>>>(m->d_total, m->cap, m->ring, min_sep, C, k, flags,
+                                                                 fstride, W64, part_s, part_o);
+    VM_LAUNCH_CHECK(m->ctx);
+    return VM_OK;
+}
 
 extern "C" size_t vm_topk_clip_workspace_bytes(const vm_memory *m, int C, int L, int k) {
     if (!m || !clip_shape_ok(C, L, k)) return 0;
@@ -600,7 +623,7 @@ extern "C" int vm_topk_cosine_clip(vm_memory *m, const void *clips, int C, int L
     if (rc != VM_OK) return rc;
     const ClipCall a = {clips,    C,        L,        k,          min_sep,       max_gap_ms, scope_lo,
                         scope_hi, use_min_score, min_score, score_mode, out_scores, out_rows};
-    return vm_by_dtype(m, [&](auto dt) {
+    return vm_by_dtype(m, [&](auto dt) -> int {
         return clip_topk<decltype(dt)::value>(m, a, out_uncertified, out_query_flags, (char *)workspace,
                                               (hipStream_t)stream);
     });
@@ -616,7 +639,7 @@ extern "C" int vm_topk_cosine_clip_exact(vm_memory *m, const void *clips, int C,
     if (rc != VM_OK) return rc;
     const ClipCall a = {clips,    C,        L,        k,          min_sep,       max_gap_ms, scope_lo,
                         scope_hi, use_min_score, min_score, score_mode, out_scores, out_rows};
-    return vm_by_dtype(m, [&](auto dt) {
+    return vm_by_dtype(m, [&](auto dt) -> int {
         return clip_exact<decltype(dt)::value>(m, a, (char *)workspace, (hipStream_t)stream);
     });
 }

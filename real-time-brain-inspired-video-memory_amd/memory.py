@@ -43,7 +43,7 @@ from . import _lib
 from .scratch import (NOVEL_MAX_ROWS, BiasTopkScratch, ClipScratch, DiverseTopkScratch, EraseScratch, EventsScratch,  # noqa: F401
                       FoldTopkScratch,
                       GroupedScopedTopkScratch, GroupedTopkScratch, MaskedTopkScratch, MixTopkScratch, NoveltyScratch, RangeScratch,
-                      ScopedTopkScratch, Scratch, SpanTopkScratch, SummaryScratch, TopkScratch)
+                      ScopedTopkScratch, Scratch, SeqScratch, SpanTopkScratch, SummaryScratch, TopkScratch)
 
 
 INT64_MIN, INT64_MAX = -(1 << 63), (1 << 63) - 1
@@ -1613,6 +1613,103 @@ class EmbeddingMemory:
                                               min_score=min_score, score_mode=score_mode, exact=exact)
         return scores.clone(), rows.clone()
 
+    # ---- sequence search (include/vidmem.h vm_topk_cosine_seq) --------------------------------------
+    def prepare_topk_seq(self, C: int, J: int, k: int) -> "SeqScratch":
+        """Size this memory's own sequence-search buffers for ``C`` sequences of ``J`` steps and ``k`` hits each now
+        (before a graph capture: a capture must not allocate)."""
+        self._counter(SeqScratch)
+        return self._resolve(SeqScratch, None, int(C), int(J), int(k))
+
+    def _seq_args(self, steps, k, max_step, min_sep, mask, mask_index, max_gap_ms, min_score, score_mode):
+        if not isinstance(steps, torch.Tensor):
+            steps = torch.tensor(steps, dtype=torch.float32)
+        if steps.dim() == 2:
+            steps = steps.unsqueeze(0)
+        if steps.dim() != 3 or steps.shape[-1] != self.dim:
+            raise ValueError(f"steps must be [C, J, {self.dim}] or [J, {self.dim}], got {tuple(steps.shape)}")
+        Cn, J = int(steps.shape[0]), int(steps.shape[1])
+        if Cn < 1:
+            raise ValueError("no sequence")
+        if not 1 <= J <= 16:
+            raise ValueError(f"sequence search supports 1 <= J <= 16 steps, got {J}")
+        if not 1 <= int(k) <= 64:
+            raise ValueError(f"sequence search supports 1 <= k <= 64, got {k}")
+        G = int(max_step)
+        if not 1 <= G <= 16:
+            raise ValueError(f"sequence search supports 1 <= max_step <= 16, got {G}")
+        sep = min(32, (J - 1) * G + 1) if min_sep is None else int(min_sep)
+        if not 1 <= sep <= 32:
+            raise ValueError(f"sequence search supports 1 <= min_sep <= 32, got {sep}")
+        if score_mode not in (_lib.VM_SCORE_RAW, _lib.VM_SCORE_UNIT_INTERVAL):
+            raise ValueError("score_mode must be VM_SCORE_RAW or VM_SCORE_UNIT_INTERVAL")
+        if max_gap_ms is not None and int(max_gap_ms) >= 0 and not self.tagged:
+            raise ValueError("max_gap_ms needs a tagged memory (EmbeddingMemory(..., tagged=True))")
+        if min_score is not None and math.isnan(float(min_score)):
+            raise ValueError("min_score is NaN")
+        masks = self._masks(mask) if mask is not None else None
+        if masks is None and mask_index is not None:
+            raise ValueError("a mask_index needs a mask")
+        idx = self._mask_index(mask_index, masks.shape[0], Cn) if masks is not None else None
+        q = steps.to(device=self.device, dtype=self.dtype).contiguous()
+        gap = -1 if max_gap_ms is None else int(max_gap_ms)
+        return q, Cn, J, G, sep, masks, idx, gap
+
+    def enqueue_topk_seq(self, steps, k: int, max_step: int = 4, min_sep: Optional[int] = None, mask=None,
+                         mask_index=None, max_gap_ms: Optional[int] = None, min_score: Optional[float] = None,
+                         score_mode: int = _lib.VM_SCORE_RAW, scratch: Optional["SeqScratch"] = None,
+                         exact: bool = False) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+        """The capturable sequence search -> ``(scores [C,k] float64, rows [C,k] int64, step_rows [C,k,J] int64,
+        step_scores [C,k,J] float64)``: views of the buffers of ``scratch`` (default: this memory's own,
+        ``prepare_topk_seq``), valid until the next sequence call on it.  Arguments as in ``topk_seq``.  Enqueues
+        ``vm_topk_cosine_seq`` on the current stream: nothing is read on the host.  Inside a graph capture pass ``steps``
+        as a device tensor of the memory's dtype and ``mask`` / ``mask_index`` as device tensors (all rewritten in place
+        between replays) and a ``scratch`` the session owns, or call ``prepare_topk_seq`` first."""
+        q, Cn, J, G, sep, masks, idx, gap = self._seq_args(steps, k, max_step, min_sep, mask, mask_index, max_gap_ms,
+                                                           min_score, score_mode)
+        k = int(k)
+        scratch = self._resolve(SeqScratch, scratch, Cn, J, k)
+        scores = scratch.scores[:Cn * k].view(Cn, k)
+        rows = scratch.rows[:Cn * k].view(Cn, k)
+        step_rows = scratch.step_rows[:Cn * k * J].view(Cn, k, J)
+        step_scores = scratch.step_scores[:Cn * k * J].view(Cn, k, J)
+        head = (self.handle, _ptr(q), Cn, J, k, G, sep, gap, _ptr(masks), 0 if masks is None else masks.shape[0],
+                _ptr(idx), *_min_score_args(min_score), int(score_mode), _ptr(scores), _ptr(rows), _ptr(step_rows),
+                _ptr(step_scores))
+        tail = (_ptr(scratch.ws), scratch.ws.numel(), _lib.current_stream_ptr())
+        if exact:
+            self.ctx.check(self.L.vm_topk_cosine_seq_exact(*head, *tail))
+        else:
+            self.ctx.check(self.L.vm_topk_cosine_seq(*head, _ptr(self._counter(SeqScratch)), _ptr(scratch.flags),
+                                                     *tail))
+        _keep_alive(q, masks, idx)
+        self._last[SeqScratch] = scratch
+        return scores, rows, step_rows, step_scores
+
+    def topk_seq(self, steps, k: int, max_step: int = 4, min_sep: Optional[int] = None, mask=None, mask_index=None,
+                 max_gap_ms: Optional[int] = None, min_score: Optional[float] = None,
+                 score_mode: int = _lib.VM_SCORE_RAW, exact: bool = False
+                 ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+        """-> (scores [C,k] float64, rows [C,k] int64, step_rows [C,k,J] int64, step_scores [C,k,J] float64): where each
+        sequence of J <= 16 ORDERED steps - ``steps`` ``[C,J,D]`` or ``[J,D]``, frame or text embeddings - occurs in the
+        memory, step j at most ``max_step`` <= 16 rows after step j-1.  ``rows`` are END row ids: the row of the last
+        step of the best chain ``r_0 < ... < r_{J-1}`` ending there; ``step_rows`` is that chain and ``step_scores`` the
+        reference cosine of each step with its row; ``scores`` their mean (summed left to right in fp64, bit for bit).
+
+        Every row of a chain must be live and selected by ``mask`` (``mask`` / ``mask_index`` as in ``topk_masked``, one
+        mask per sequence, default every live row); a chain may step over unselected rows.  On a tagged memory a chain
+        stays within one video (no change of source between its first and last row; ``max_gap_ms``: no clock step
+        backwards or above it between adjacent rows either).  Ties between predecessors go to the nearest row.  The k
+        answers are PEAKS: end rows that rank before every other end row closer than ``min_sep`` rows (default
+        ``min(32, (J-1) * max_step + 1)``) in (score desc, end row asc) - local-maximum suppression.  Score mapping and
+        strict ``> min_score`` filter as in ``topk``; 0.0 / -1 / -1 / 0.0 padded.  ``J = 1, min_sep = 1`` is ``topk``
+        (``topk_masked``); ``max_step = 1`` is ``topk_clip`` with its rows + J - 1.  Always the exhaustive answer: the fp32
+        fast path redoes the sequences it cannot certify on the device, in the same call (csrc/topk_seq.hip).
+        ``exact=True`` runs the exact layers over all rows (slow).  The per-sequence flags of the last call are in
+        ``last_seq_flags``."""
+        out = self.enqueue_topk_seq(steps, k, max_step=max_step, min_sep=min_sep, mask=mask, mask_index=mask_index,
+                                    max_gap_ms=max_gap_ms, min_score=min_score, score_mode=score_mode, exact=exact)
+        return tuple(t.clone() for t in out)
+
     # ---- range search (include/vidmem.h vm_range_cosine, DESIGN.md 15) ---------------------------------------------
     def prepare_range(self, Q: int, max_hits: int) -> "RangeScratch":
         """Size this memory's own range-search buffers for ``Q`` queries and ``max_hits`` hits each now (before a graph
@@ -1903,6 +2000,8 @@ class EmbeddingMemory:
                                             "last fast `topk_grouped_scoped` call redid a query, 0 = certified")
     last_clip_flags = _last_property(ClipScratch, "flags", "int32 per clip (vm_topk_flag): why the last fast clip call "
                                      "redid a clip, 0 = certified")
+    last_seq_flags = _last_property(SeqScratch, "flags", "int32 per sequence (vm_topk_flag): why the last fast sequence "
+                                    "call redid a sequence, 0 = certified")
     last_range_rescored = _last_property(RangeScratch, "rescored", "int64 per query: the pairs the last fast range call "
                                          "scored exactly")
     last_mask_flags = _last_property(MaskedTopkScratch, "flags", "int32 per query (vm_topk_flag): why the last fast masked "
@@ -1927,6 +2026,7 @@ class EmbeddingMemory:
     scoped_uncertified_count = _count_property(ScopedTopkScratch, "Queries the scoped fast path")
     group_scoped_uncertified_count = _count_property(GroupedScopedTopkScratch, "Queries the scoped grouped fast path")
     clip_uncertified_count = _count_property(ClipScratch, "Clips the clip search's fast path")
+    seq_uncertified_count = _count_property(SeqScratch, "Sequences the sequence search's fast path")
 
     @property
     def uncertified_count(self) -> int:

@@ -176,6 +176,20 @@ class ClipScratch(Scratch):
                 ("rows", torch.int64, _rows(C * k), -1))
 
 
+class SeqScratch(Scratch):
+    """The sequence search for up to ``C`` sequences of ``J`` steps with ``k`` hits each: the workspace (query tiles, fp32
+    score columns, end scores and keys, candidates, the redo's two exact layers), ``flags`` (int32 [C]) and the ``scores``
+    / ``rows`` (C x k) and ``step_rows`` / ``step_scores`` (C x k x J) outputs."""
+
+    workspaces = (("ws", "vm_topk_seq_workspace_bytes"),)
+
+    @staticmethod
+    def _buffers(C, J, k):
+        return (("flags", torch.int32, _rows(C), 0), ("scores", torch.float64, _rows(C * k), 0.0),
+                ("rows", torch.int64, _rows(C * k), -1), ("step_rows", torch.int64, _rows(C * k * J), -1),
+                ("step_scores", torch.float64, _rows(C * k * J), 0.0))
+
+
 class NoveltyScratch(Scratch):
     """The gated append for batches of up to ``B`` rows (at most 4,096 reach the library at a time): the workspace
     (norms and pair bits), ``keep`` (int32 [B]), ``row_of`` (int64 [B]) and ``count`` (int32 [1])."""

@@ -235,6 +235,46 @@ def clip_similarities(memory: EmbeddingMemory, chunks_of_frame_embeddings: Seque
     return out
 
 
+def seq_similarities(memory: EmbeddingMemory, sequences_of_step_embeddings: Sequence, top_k: int, max_step: int = 4,
+                     min_sep: Optional[int] = None, mask=None, max_gap_ms: Optional[int] = None,
+                     min_score: Optional[float] = None
+                     ) -> Tuple[List[List[Tuple[str, float]]], List[List[Tuple[str, str]]]]:
+    """The ordered counterpart of ``clip_similarities``: each entry of ``sequences_of_step_embeddings`` is the steps of one
+    question in order (``[J, D]``, 1 <= J <= 16; tensor or lists - frame embeddings, or one text embedding per sentence),
+    and its hits are the stored moments where the steps occur in that order, each at most ``max_step`` rows after the one
+    before (EmbeddingMemory.topk_seq: the mean of the J cosines along the best chain, one hit per moment).
+
+    Returns ``(hits, spans)``.  ``hits`` has the reference's list shape (src/components/pre_llm_injector.py:346-372): per
+    sequence ``[(id, score), ...]`` with ``id = memory.id_of(end_row)``; an Exception or ``None`` entry yields ``[]``
+    (:357-359); ``merge_batch_similarities`` consumes it unchanged.  ``spans`` holds, hit for hit, ``(start_id, end_id)``:
+    the ids of the rows of the first and of the last step.  Sequences of one length share one launch.  ``min_sep``,
+    ``mask`` (one mask for every sequence), ``max_gap_ms`` and ``min_score`` as in ``topk_seq``."""
+    hits: List[List[Tuple[str, float]]] = [[] for _ in sequences_of_step_embeddings]
+    spans: List[List[Tuple[str, str]]] = [[] for _ in sequences_of_step_embeddings]
+    if memory.searchable == 0 or top_k <= 0:
+        return hits, spans
+    by_len: Dict[int, List[int]] = {}
+    seqs: Dict[int, torch.Tensor] = {}
+    for i, e in enumerate(sequences_of_step_embeddings):
+        if isinstance(e, Exception) or e is None:
+            continue
+        t = e if isinstance(e, torch.Tensor) else torch.tensor([list(f) for f in e], dtype=torch.float32)
+        if t.dim() != 2 or t.shape[-1] != memory.dim:
+            raise ValueError(f"sequence {i}: steps must be [J, {memory.dim}], got {tuple(t.shape)}")
+        seqs[i] = t
+        by_len.setdefault(int(t.shape[0]), []).append(i)
+    for J, idx in by_len.items():
+        q = torch.stack([seqs[i].to(memory.device) for i in idx])
+        scores, rows, step_rows, _ = memory.topk_seq(q, top_k, max_step=max_step, min_sep=min_sep, mask=mask,
+                                                     max_gap_ms=max_gap_ms, min_score=min_score)
+        scores, rows, first = scores.cpu().tolist(), rows.cpu().tolist(), step_rows[:, :, 0].cpu().tolist()
+        for slot, i in enumerate(idx):
+            keep = [h for h, r in enumerate(rows[slot]) if r >= 0]
+            hits[i] = [(memory.id_of(rows[slot][h]), float(scores[slot][h])) for h in keep]
+            spans[i] = [(memory.id_of(first[slot][h]), memory.id_of(rows[slot][h])) for h in keep]
+    return hits, spans
+
+
 MIX_MAX_TERMS = 16   # terms of one mixed query (EmbeddingMemory.topk_mix)
 
 
