@@ -17,6 +17,9 @@ exactly when no other row can enter the answer, which ``Sparse`` asserts from th
 score is at least FLOOR, and every row left out is noise, bounded by NOISE_BOUND x the query's weight.  Construction
 parameters, asserted on every run, never tuned.  tests/test_bigmem_cpu.py proves the reasoning on a layout small enough for
 the dense oracle.
+
+The biased search adds what a bias column may hold on the rows left out (``Column``: known at the candidates' slots, bounded
+everywhere else), the sequence search how far a chain reaches into a run (``Sparse.seq``).
 """
 from __future__ import annotations
 
@@ -25,17 +28,21 @@ from typing import NamedTuple
 import numpy as np
 
 from oracle import cref
+from tests import bias_ref as BR
 from tests import clip_ref as CL
 from tests import diverse_ref as DR
+from tests import fold_ref as FR
 from tests import group_ref as G
 from tests import group_scope_ref as GS
 from tests import mask_ref as MR
 from tests import mix_ref as XR
 from tests import range_ref as R
 from tests import scope_ref as S
+from tests import seq_ref as SQ
 from tests import span_ref as SP
 from tests import summary_ref as M
 from tests import events_ref as V
+from tests.scored_ref import slack_m
 from tests.support import to_bits
 
 NOISE_SCALE, NOISE_BOUND, FLOOR, SPACING = 0.05, 0.06, 0.5, 0.05
@@ -215,7 +222,8 @@ def cut_hoods(L: Layout, start, x, into: dict):
 # ---- the model -----------------------------------------------------------------------------------------------------------
 class Sparse:
     """The candidate rows of a memory of ``total`` live rows: ``gid`` their row ids (ascending), ``rows`` their bits,
-    ``keys`` and ``tags``; ``planted`` bool: which of them are planted (the others must satisfy the noise bound)."""
+    ``keys`` and ``tags``; ``planted`` bool: which of them are planted (the others must satisfy the noise bound);
+    ``newest_ms`` the largest clock of any row, candidate or not."""
 
     def __init__(self, L: Layout, cand: dict, total=None, base=0, dtype=DTYPE):
         self.L, self.D, self.dtype = L, L.D, dtype
@@ -227,6 +235,7 @@ class Sparse:
         self.planted = np.array([int(r) in pos for r in self.gid])
         self.total = L.N if total is None else total
         self.base = base
+        self.newest_ms = self.total - 1       # tag_of: the clock of a row of the recipe is the row id it is appended with
         self.check_noise()
 
     def check_noise(self):
@@ -257,6 +266,7 @@ class Sparse:
         self.tags = np.concatenate([self.tags, np.asarray(tags, np.int64)])
         self.planted = np.concatenate([self.planted, np.ones(n, bool)])
         self.total += n
+        self.newest_ms = max(self.newest_ms, int((np.asarray(tags, np.int64) & BR.TAG_MS_MASK).max()))
 
     def drop_below(self, base):
         """A ring overwrote every row below ``base``."""
@@ -479,6 +489,141 @@ class Sparse:
             assert DR.flag0_ok(best, pool, self.D), f"diverse: query {i} may be left to the redo"
         return self._ids(r), s, v
 
+    # ---- the biased search: a column is known at the candidates' slots and bounded everywhere else
+    def col_of_rows(self, ids, values, capacity) -> "Column":
+        """``bias_of_rows(ids, values)``: bias_ref.bias_from_rows_ref, read at the candidates' slots.  Every id must be a
+        candidate, so every other live slot holds 0."""
+        live = [int(r) for r in ids if self.base <= int(r) < self.total]
+        assert np.isin(live, self.gid).all(), "the model only knows a boost of candidate rows"
+        col = BR.bias_from_rows_ref(ids, values, self.base, self.total - self.base, capacity)
+        return Column(col[self.gid % capacity], 0.0, 0.0)
+
+    def col_of_age(self, now_ms, per_ms, fill, capacity) -> "Column":
+        """``bias_of_age(now_ms, per_ms, fill)``: bias_ref.bias_from_tags_ref per run, read at the candidates' slots.
+        Everywhere else, in closed form: a row that is not a candidate was appended by the layout's recipe, so its clock
+        is the row id it was appended with, in [0, newest]; with per_ms > 0 and now_ms >= newest its entry
+        fl32(per_ms (clock - now_ms)) lies in [fl32(-per_ms now_ms), 0] (rounding is monotone)."""
+        assert per_ms > 0 and now_ms >= self.newest_ms >= int((self.tags & BR.TAG_MS_MASK).max())
+        at = np.zeros(self.gid.size, np.float32)
+        for a, b in self.segments():
+            col = BR.bias_from_tags_ref(self.tags[a:b], int(self.gid[a]), capacity, now_ms, per_ms, fill)
+            at[a:b] = col[self.gid[a:b] % capacity]
+        assert (at <= 0).all()
+        return Column(at, float(np.float32(float(per_ms) * float(-int(now_ms)))), 0.0)
+
+    def biased(self, q, cols, bias_index, betas, k, sel=None):
+        """bias_ref.bias_topk_from_cosines on the candidates.  A row that is not a candidate scores at most
+        NOISE_BOUND + max(beta lo, beta hi) of its query's column (an index out of range is the zero column): that must
+        lie below the worst returned S.  The fast path must then certify every query whose ranks k and M + 1 stand
+        bias_ref.flag0_ok apart, the rows left out taken at that bound (asserted: ``_flags0`` holds for all)."""
+        Q, n = q.shape[0], self.gid.size
+        assert first_half_only(q), "biased: an operand has a nonzero second half"
+        e = self.scores(q)
+        b, out = np.zeros((Q, n), np.float32), np.zeros(Q)
+        for i, c in enumerate(bias_index):
+            if 0 <= int(c) < len(cols):
+                b[i] = cols[int(c)].at
+                out[i] = max(float(betas[i]) * cols[int(c)].lo, float(betas[i]) * cols[int(c)].hi)
+        r, s = BR.bias_topk_from_cosines(e, list(betas), b, sel, k)
+        assert (r >= 0).all(), "biased: the candidates do not fill the answer"
+        for i in range(Q):
+            bound = NOISE_BOUND + out[i]
+            assert bound < s[i].min(), f"biased: a row outside the candidates may score {bound}, query {i} returns {s[i].min()}"
+            S = BR.bias_scores_loop(e[i], betas[i], b[i])
+            best = np.sort(np.concatenate([S if sel is None else S[sel[i]], np.full(slack_m(k) + 1, bound)]))[::-1]
+            assert BR.flag0_ok(best, k, self.D), f"biased: query {i} may be left to the redo"
+        return self._ids(r), s
+
+    # ---- the any/all search
+    def fold(self, terms, weights, k, op, sel=None):
+        """``mix``'s proof for fold_ref.fold_topk: |w_j e_j| <= A x NOISE_BOUND on a noise row for every term, so its
+        max and its min are; every returned F is at least FLOOR.  For ``min`` that needs every term of a query to be a
+        family with a member in the answer's rows: a term of another family scores about 0 there and the floor says so."""
+        C, J = terms.shape[0], terms.shape[1]
+        r, s, t = FR.fold_topk(terms, weights, self.rows, sel, k, op, dtype=self.dtype)
+        self._safe(terms, r, s, "fold " + op, weight=max(FR.abs_max(w) for w in weights))
+        e = cref.cosine_matrix(terms.reshape(C * J, self.D), np.ascontiguousarray(self.rows), dtype=self.dtype).reshape(C, J, -1)
+        for c in range(C):
+            A = FR.abs_max(weights[c])
+            F, _ = FR.fold_scores_loop(e[c], weights[c], op)
+            best = np.sort(np.concatenate([F if sel is None else F[sel[c]], np.full(slack_m(k) + 1, A * NOISE_BOUND)]))[::-1]
+            assert FR.flag0_ok(best, k, self.D, A), f"fold {op}: query {c} may be left to the redo"
+        return self._ids(r), s, t
+
+    # ---- the sequence search
+    def seq(self, steps, k, G, min_sep, sel=None, min_score=None, max_gap_ms=-1):
+        """-> (end rows [C,k], scores [C,k], step rows [C,k,J], step scores [C,k,J], must bool [C]).  seq_ref.seq_topk per
+        run of consecutive candidates, merged by (score desc, end row asc).
+
+        Sound when every planted row a sequence may use (``sel`` [C, candidates]: its mask; rows that are no candidates
+        count as selected) lies at least (J-1) G rows inside its run on both sides, unless the run ends where the memory
+        does (asserted).  A chain reaches back (J-1) G rows at the most, so a chain that ends outside a run, or in a run's
+        first (J-1) G rows, holds noise rows only and its A is at most NOISE_BOUND; inside, a run computes an end row's A
+        from the whole chain or, in those first rows, from fewer chains of noise rows: at most NOISE_BOUND either way.
+        Such an end row neither enters an answer whose scores are all above NOISE_BOUND (asserted; above ``min_score``
+        when there is one) nor suppresses one.
+
+        ``must``: seq_ref.margin's condition over the merged runs with the end rows left out bounded by NOISE_BOUND - among
+        the best M possible peaks are k exact peaks, and the k-th clears max(the (M+1)-th best possible end row,
+        NOISE_BOUND) by more than 4 eps_seq (the rule of tests/test_seq_gpu.py).  The fast path must then certify."""
+        C, J = steps.shape[0], steps.shape[1]
+        n, reach = self.gid.size, (J - 1) * G
+        assert first_half_only(steps) and (min_score is None or NOISE_BOUND < min_score)
+        el = SQ.eligible(n, C, sel)
+        segs = self.segments()
+        for a, b in segs:
+            for c in range(C):
+                p = self.planted[a:b] & el[c, a:b]
+                if self.gid[a] != self.base:
+                    assert not p[:reach].any(), f"sequence {c}: a planted row within {reach} rows above {self.gid[a]}"
+                if self.gid[b - 1] != self.total - 1:
+                    assert not p[max(b - a - reach, 0):].any(), f"sequence {c}: a planted row within {reach} rows below {self.gid[b - 1]}"
+        parts = [SQ.seq_topk(steps, self.rows[a:b], k, G, min_sep, dtype=self.dtype, tags=self.tags[a:b], sel=el[:, a:b],
+                             max_gap_ms=max_gap_ms, min_score=min_score, base=0) + (a,) for a, b in segs]
+        out_r, out_s = np.full((C, k), -1, np.int64), np.zeros((C, k), np.float64)
+        out_sr, out_ss = np.full((C, k, J), -1, np.int64), np.zeros((C, k, J), np.float64)
+        must = np.zeros(C, bool)
+        M, e = slack_m(k), SQ.eps_seq(self.D, J)
+        for c in range(C):
+            hit = [p[0][c] >= 0 for p in parts]
+            r = np.concatenate([self.gid[p[0][c][h] + p[4]] for p, h in zip(parts, hit)])
+            s = np.concatenate([p[1][c][h] for p, h in zip(parts, hit)])
+            sr = np.concatenate([self.gid[p[2][c][h] + p[4]] for p, h in zip(parts, hit)])
+            ss = np.concatenate([p[3][c][h] for p, h in zip(parts, hit)])
+            order = np.lexsort((r, -s))[:k]
+            m = order.size
+            out_r[c, :m], out_s[c, :m], out_sr[c, :m], out_ss[c, :m] = r[order], s[order], sr[order], ss[order]
+            if min_score is None:
+                assert m == k and (s[order] > NOISE_BOUND).all(), "seq: an end row of noise chains could enter the answer"
+            else:
+                assert (s[order] > min_score).all()
+            As, poss, peaks = [], [], []
+            for a, b in segs:                            # seq_ref.margin's sets, run by run
+                A, ok, _ = SQ.end_scores(CL.frame_scores(steps[c], self.rows[a:b], self.dtype), el[c, a:b],
+                                         CL.tag_breaks(self.tags[a:b], max_gap_ms), G)
+                far = np.zeros(b - a, bool)
+                with np.errstate(invalid="ignore"):
+                    for d in range(1, min(min_sep, b - a)):
+                        far[d:] |= ok[:-d] & (A[:-d] > A[d:] + 4 * e)
+                        far[:-d] |= ok[d:] & (A[d:] > A[:-d] + 4 * e)
+                As.append(A), poss.append(ok & ~far), peaks.append(CL.peak_mask(A, ok, min_sep))
+            A, pos, pk = np.concatenate(As), np.concatenate(poss), np.concatenate(peaks)
+            ids = np.nonzero(pos)[0]                     # run order = row order
+            ranked = ids[np.lexsort((ids, -A[ids]))]
+            exact = ranked[:M][pk[ranked[:M]]]
+            if exact.size >= k:
+                rest = max(A[ranked[M]] if ranked.size > M else -np.inf, NOISE_BOUND)
+                must[c] = (A[exact[k - 1]] - rest) / e > 4
+        return out_r, out_s, out_sr, out_ss, must
+
+
+class Column(NamedTuple):
+    """One bias column as the model knows it: ``at`` fp32 [candidates] its entries at the candidates' slots; every entry of
+    a live slot that is no candidate lies in [lo, hi]."""
+    at: np.ndarray
+    lo: float
+    hi: float
+
 
 def dense(L: Layout, seed=77):
     """The whole memory of a small layout on the host, by the recipe of the large one -> (bits [N, D], Sparse)."""
@@ -552,3 +697,84 @@ def mix_terms(L: Layout, seed=40):
     """bits [16, 3, D]: query c mixes families c, c + 1, c + 2."""
     q = [queries(L, FAMILIES, seed + j) for j in range(3)]
     return np.stack([np.stack([q[j][(c + j) % FAMILIES] for j in range(3)]) for c in ALL16])
+
+
+# the biased search: column 0 boosts planted rows, column 1 is the age of every row, any other index the zero column
+BIAS_K, AGE_FILL = 5, 1.0e6
+BOOST = {4: 0.3, 5: 0.22}     # level 4 (0.75, just below b2) + 0.3 outranks level 0 (0.95, just above it) and level 5 (0.70,
+                              # at b1 and above) + 0.22 outranks level 1 (0.90, just below b1)
+BIAS_INDEX = (0, 1, 2, 0, 1, 0, 1, 0, 1, 0, 1, -1, 0, 1, 0, 1)
+AGE_BETAS = (1.0, 0.3, 2.0 ** -12, 0.0)     # never negative: every entry of an age column is <= 0, so no noise row gains
+
+
+def boost_rows(L: Layout):
+    """(row ids, values) of ``bias_of_rows``: every family's members at the levels of BOOST."""
+    pos = positions(L)
+    rows = sorted(r for r, (_, j) in pos.items() if j in BOOST)
+    return rows, [BOOST[pos[r][1]] for r in rows]
+
+
+def age_per_ms(L: Layout) -> float:
+    """The oldest row loses 0.2: the member at the tail (level 2, 0.85) then outranks the one below b1 (level 1, 0.90)."""
+    return 0.2 / L.N
+
+
+def bias_weights():
+    """One weight per query of BIAS_INDEX: bias_ref.BETAS in turn (0.0, a negative and a tiny one among them) for the boost
+    and the zero column, AGE_BETAS in turn for the age column."""
+    out, seen = [], [0, 0]
+    for c in BIAS_INDEX:
+        pool = AGE_BETAS if c == 1 else BR.BETAS
+        out.append(pool[seen[c == 1] % len(pool)])
+        seen[c == 1] += 1
+    return out
+
+
+# the any/all search
+FOLD_K, FOLD_W = 5, [1.0, 1.0, 0.9]
+
+
+def fold_cases(L: Layout, seed=45):
+    """op -> (terms bits [16, 3, D], weights).  ``max``: families c, c + 1, c + 2, so that every term names some of the five
+    best rows; ``min``: three perturbed copies of family c - a row of family c scores about 0 against any other family, and
+    so would the minimum."""
+    same = np.stack([queries(L, FAMILIES, seed + j) for j in range(3)], axis=1)
+    return {"max": (mix_terms(L), [FOLD_W] * FAMILIES), "min": (same, [[1.0] * 3] * FAMILIES)}
+
+
+# the sequence search
+SEQ_J, SEQ_G, SEQ_K, SEQ_MIN, SEQ_F = 3, 4, 3, 0.3, 3
+SEQ_SEP = (SEQ_J - 1) * SEQ_G + 1         # topk_seq's default min_sep
+
+
+def seq_cases(L: Layout):
+    """group -> [(name, the planted chain's rows, cut: a source change lies inside it, the row its mask excludes or None)].
+    One call per group (at most 8 sequences: the workspace grows with C x capacity).  b1 and b2 begin a source, so the
+    chains across them are no chains on the tagged memory; the chains at gaps of 2 need max_step >= 2."""
+    f = SEQ_F
+    out = {}
+    for name, b, gap2 in (("b2", L.b2, (L.b2 + 2 * f, L.b2 + 2 * f + 2, L.b2 + 2 * f + 4)),
+                          ("b1", L.b1, (L.b1 + f, L.b1 + f + 2, L.b1 + f + 4))):
+        out[name] = [(f"gaps of 2 above {name}", gap2, False, None),
+                     (f"ends below {name}", (b - 3, b - 2, b - 1), False, None),
+                     (f"begins at {name}", (b, b + 1, b + 2), False, None),
+                     (f"across {name}", (b - 2, b - 1, b), True, None)]
+    out["b2"] += [("tail", (L.N - 3, L.N - 2, L.N - 1), False, None),
+                  ("control", (L.ctrl + 4, L.ctrl + 6, L.ctrl + 7), False, None),
+                  # under a mask: without the chain's middle row (the families stand in the same order at every site, so
+                  # the answer moves to another site), and without the row the chain steps over (the answer stays)
+                  ("middle row masked", out["b2"][0][1], False, out["b2"][0][1][1]),
+                  ("stepped-over row masked", out["b2"][0][1], False, out["b2"][0][1][1] - 1)]
+    assert all(len(v) <= 8 for v in out.values())
+    return out
+
+
+def seq_steps(L: Layout, cases, seed=70):
+    """bits [C, J, D]: noisy copies of each case's planted chain."""
+    plant = planted_rows(L)
+    return np.stack([noisy_copy(np.stack([plant[r] for r in chain]), seed + c) for c, (_, chain, _, _) in enumerate(cases)])
+
+
+def seq_sel(model: Sparse, cases):
+    """bool [C, candidates]: what each case's mask selects (all ones, but for the excluded row)."""
+    return np.stack([np.ones(model.gid.size, bool) if x is None else model.gid != x for _, _, _, x in cases])

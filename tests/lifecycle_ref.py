@@ -2,21 +2,25 @@
 
 Every feature of the memory has its own oracle; this file composes them into ONE model that is carried through a whole
 life - keyed, tagged and gated appends, erases, whole and tail regroups, the ring overwrite, reset, snapshot / restore -
-and says after every step what all fourteen readers must return (torch only where the existing data generators use it,
+and says after every step what all seventeen readers must return (torch only where the existing data generators use it,
 ``pool`` and ``noisy``).  The readers: ``topk``, ``topk_grouped``, ``topk_scoped``, ``topk_grouped_scoped``, ``topk_clip``,
-``range_search``, ``events``, ``summaries``, each top-k one with an exact form, and the five whose operands speak about row
+``range_search``, ``events``, ``summaries``, each top-k one with an exact form, the five whose operands speak about row
 ids and slots - ``topk_masked``, ``topk_span``, ``topk_mix``, ``topk_diverse`` (with ``last_diverse_mmr``) and
 ``recall_links`` - fed by the mask builders ``mask_of_rows``, ``mask_of_scope``, ``mask_where`` and read back through
-``rows_of_mask``.  It defines no cosine and no ranking of its own: every
+``rows_of_mask``, and the three newest: ``topk_biased`` over columns built by ``bias_of_rows`` and ``bias_of_age`` (a
+column speaks about physical slots, as a mask does), ``topk_fold`` (max and min, with its term indices) and ``topk_seq``
+(which walks predecessors through the slots and applies the tag-break rule between adjacent rows).  It defines no cosine
+and no ranking of its own: every
 mutator restates the header's rule by calling the oracle that already states it (novelty_ref.gate, erase_ref.erase,
 events_ref.regroup / regroup_tail), every expectation is the feature's own oracle over the live window (mask_ref,
-span_ref, mix_ref and diverse_ref for the five newer readers).
+span_ref, mix_ref, diverse_ref, bias_ref, fold_ref and seq_ref for the eight newer readers).
 
 ``Model``       the state, in row-id order, and the mutators.
 ``checkpoint``  compares an ``EmbeddingMemory`` (or anything with its surface) with the model through the public
-                accessors and all fourteen readers, each top-k reader in its default and its ``exact`` form; bit equality.
+                accessors and all seventeen readers, each top-k reader in its default and its ``exact`` form; bit equality.
                 Where a feature's own oracle condition says that the fast path must certify a query of the masked, span,
-                mixed or diverse search, its flag of the default call must be 0: the redo may not hide a broken scan.
+                mixed, diverse, biased, any/all or sequence search, its flag of the default call must be 0: the redo may
+                not hide a broken scan.
 ``Driver``      applies one step to the model and to the memory, compares what the step returns, builds the probes.
 ``linear_script`` / ``ring_script``  the two lives of tests/test_lifecycle_gpu.py; tests/test_lifecycle_cpu.py runs the
                 same scripts against a fake memory, proves the conditions they must meet and plants defects.
@@ -29,10 +33,12 @@ from typing import NamedTuple
 import numpy as np
 
 from oracle import cref
+from tests import bias_ref as BR
 from tests import clip_ref as CL
 from tests import diverse_ref as DR
 from tests import erase_ref as E
 from tests import events_ref as V
+from tests import fold_ref as FR
 from tests import group_ref as G
 from tests import group_scope_ref as GS
 from tests import mask_ref as MR
@@ -40,6 +46,7 @@ from tests import mix_ref as XR
 from tests import novelty_ref as N
 from tests import range_ref as R
 from tests import scope_ref as S
+from tests import seq_ref as SQ
 from tests import span_ref as SP
 from tests import summary_ref as M
 
@@ -59,6 +66,19 @@ POOL, LAM = 16, (1.0, 0.5, 0.5, 0.3, 0.7, 0.0)                # the diverse sear
 LINK_ROWS, LINK_K, LINK_GAP, LINK_BLOCK = 300, 3, 2, 128      # recall links of the newest 300 rows: pages of 128, 128, 44
 LINK_CALLS = ((None, True), (200, False))                     # (max_back, exclude_group)
 DOMAIN = (2.0 ** -40, 2.0 ** 40)       # the norms inside which the fp32 stage's bound holds (include/vidmem.h)
+# the biased search: four columns - (0) zeros, (1) bias_of_rows of the rows topk just showed, (2) bias_of_age, (3) column
+# (1) as the previous checkpoint built it, searched again, stale, after the mutation.  Query i reads column BIAS_INDEX[i]
+# (9: out of range = the zero column) with weight BIAS_W[i] (bias_ref.BETAS: 0.0, a negative and a tiny one among them)
+BIAS_INDEX = (0, 1, 2, 3, 9, 1)
+BIAS_W = (BR.BETAS[0], BR.BETAS[2], BR.BETAS[3], BR.BETAS[0], BR.BETAS[4], BR.BETAS[1])
+BIAS_PLAIN = (0, 4, 5)                 # the zero column, the index out of range, the weight 0.0: these queries are topk's
+AGE_PER_MS, AGE_FILL = 1.0e-3, 1.0e6   # a frame (33 ms) of age costs 0.033 x the weight; the fill would win every ranking
+FOLD_CALLS = tuple((op, w, m) for op in FR.OPS for w in (False, True) for m in (False, True))   # (op, WEIGHTS?, masks?)
+SEQ_J, SEQ_G = 4, 3                    # the six sequences: four steps, at most three rows apart
+SEQ_MASK_INDEX = (0, 1, 2, 3, 6, 4)    # (a) .. (d) under the checkpoint's masks (a) .. (d), (e) under its own mask (the
+                                       # seventh: every row but the chain's second), (f) under the carried exclusion
+# name -> (min_sep, max_gap_ms, masks?)
+SEQ_CALLS = {"seq": (1, None, False), "seq_masked": (4, None, True), "seq_gap": (4, GAP_MS, False)}
 
 
 def make_tag(source, ms):
@@ -85,6 +105,10 @@ class Probes(NamedTuple):
     carried_span: tuple    # (lo + 10, total - 10) of the previous checkpoint, or None
     terms: np.ndarray      # uint16 [6, 3, D]: the mixed queries
     links: tuple           # (first_row, n_rows) of the recall links
+    bias_now: int          # now_ms of bias_of_age: the newest live tag's clock
+    carried_bias: object   # the model's column (1) of the previous checkpoint, fp32 [S] by slot, or None
+    seqs: np.ndarray       # uint16 [6, 4, D]: the sequences (a) .. (f)
+    seq_excluded: int      # the row id the mask of sequence (e) leaves out, -1 when there is none
     k: int = K
     max_hits: int = MAX_HITS
     threshold: float = THRESHOLD
@@ -287,6 +311,32 @@ class Model:
         lo, live = self.window()
         return DR.diverse_topk(q, live.rows, sel, k, pool, list(lam), dtype=self.dtype, base=lo)
 
+    def exp_biased(self, q, cols, sel, k):
+        """``cols`` fp32 [4, S] by slot; bias_ref.row_bias maps slots to rows: the header's rule - the entry names whichever
+        row lives in the slot now."""
+        lo, live = self.window()
+        return BR.bias_topk(q, live.rows, cols, list(BIAS_INDEX), list(BIAS_W), sel, k, dtype=self.dtype, base=lo,
+                            capacity=self.capacity)
+
+    def exp_fold(self, terms, weights, sel, k, op):
+        lo, live = self.window()
+        return FR.fold_topk(terms, _fold_weights(weights, terms), live.rows, sel, k, op, dtype=self.dtype, base=lo)
+
+    def exp_seq(self, steps, sel, k, G, min_sep, max_gap_ms=None, tags=True):
+        lo, live = self.window()
+        return SQ.seq_topk(steps, live.rows, k, G, min_sep, dtype=self.dtype, tags=live.tags if tags else None, sel=sel,
+                           max_gap_ms=-1 if max_gap_ms is None else max_gap_ms, base=lo)
+
+    def bias_columns(self, p: "Probes", shown):
+        """fp32 [4, S] by slot, from the model alone: zeros, bias_ref.bias_from_rows_ref of the rows shown with
+        ``boost_values``, bias_ref.bias_from_tags_ref, and the carried column as it was (zeros when there is none)."""
+        lo, live = self.window()
+        n, S = live.rows.shape[0], BR.bias_stride(self.capacity)
+        shown = np.asarray(shown, np.int64).ravel()
+        carried = np.zeros(S, np.float32) if p.carried_bias is None else p.carried_bias
+        return np.stack([np.zeros(S, np.float32), BR.bias_from_rows_ref(shown, boost_values(shown), lo, n, self.capacity),
+                         BR.bias_from_tags_ref(live.tags, lo, self.capacity, p.bias_now, AGE_PER_MS, AGE_FILL), carried])
+
     def exp_links(self, first, count, k, min_gap, max_back, exclude_group):
         """span_ref.links_ref wants ``group_of`` as the group of every live row in row order, indexed by r - base, and
         only compares neighbours: the model's ordinals as they are, a cut first group included."""
@@ -334,8 +384,18 @@ class Model:
         exp["mix"], exp["mix_masked"] = self.exp_mix(p.terms, WEIGHTS, None, k), self.exp_mix(p.terms, WEIGHTS, sel, k)
         exp["diverse"] = self.exp_diverse(q, sel, k, POOL, LAM)
         exp["links"] = [self.exp_links(*p.links, LINK_K, LINK_GAP, back, own) for back, own in LINK_CALLS]
+        cols = exp["bias_cols"] = self.bias_columns(p, exp["topk"][0])
+        exp["biased"], exp["biased_masked"] = self.exp_biased(q, cols, None, k), self.exp_biased(q, cols, sel, k)
+        for op, w, m in FOLD_CALLS:
+            exp[fold_name(op, w, m)] = self.exp_fold(p.terms, WEIGHTS if w else None, sel if m else None, op=op, k=k)
+        ids = lo + np.arange(n, dtype=np.int64)
+        seq_sel = exp["seq_sel"] = np.stack([np.concatenate([sels, (ids != p.seq_excluded)[None]])[i] for i in SEQ_MASK_INDEX])
+        for name, (sep, gap, m) in SEQ_CALLS.items():
+            exp[name] = self.exp_seq(p.seqs, seq_sel if m else None, k, SEQ_G, sep, gap)
+        exp["seq_one"] = self.exp_seq(q[:, None, :], None, k, SEQ_G, 1)
         # where the fast path must certify: each feature's own condition, on the oracle's scores (never on the device's)
-        must = {name: [False] * 6 for name in ("masked", "masked2", "mix", "mix_masked", "diverse", *span_sets)}
+        new = ("biased", "biased_masked", *(fold_name(*c) for c in FOLD_CALLS), *SEQ_CALLS, "seq_one")
+        must = {name: [False] * 6 for name in ("masked", "masked2", "mix", "mix_masked", "diverse", *span_sets, *new)}
         if n and not self.outside:
             sc = cref.cosine_matrix(np.ascontiguousarray(q), np.ascontiguousarray(live.rows), dtype=self.dtype)
             e = cref.cosine_matrix(np.ascontiguousarray(p.terms.reshape(-1, self.D)), np.ascontiguousarray(live.rows),
@@ -351,8 +411,42 @@ class Model:
                 must["diverse"][i] = bool(q_in[i] and sel[i].any() and DR.flag0_ok(best(sc[i], sel[i]), POOL, self.D))
                 for name, s in (("mix", np.ones(n, bool)), ("mix_masked", sel[i])):
                     must[name][i] = bool(t_in[i] and s.any() and XR.flag0_ok(best(W[i], s), k, self.D, XR.abs_sum(WEIGHTS[i])))
+                Sb = BR.bias_scores_loop(sc[i], BIAS_W[i], BR.row_bias(cols, list(BIAS_INDEX), 6, lo, n, self.capacity)[i])
+                for name, s in (("biased", np.ones(n, bool)), ("biased_masked", sel[i])):
+                    must[name][i] = bool(q_in[i] and s.any() and BR.flag0_ok(best(Sb, s), k, self.D))
+                for op, w, m in FOLD_CALLS:
+                    wts = _fold_weights(WEIGHTS if w else None, p.terms)[i]
+                    F, s = FR.fold_scores_loop(e[i], wts, op)[0], sel[i] if m else np.ones(n, bool)
+                    must[fold_name(op, w, m)][i] = bool(t_in[i] and s.any() and FR.flag0_ok(best(F, s), k, self.D, FR.abs_max(wts)))
+            s_in = in_domain(p.seqs.reshape(-1, self.D), self.dtype).reshape(6, -1).all(axis=1)
+            for name, (sep, gap, m) in (*SEQ_CALLS.items(), ("seq_one", (1, None, False))):
+                steps, ok = (q[:, None, :], q_in) if name == "seq_one" else (p.seqs, s_in)
+                for i in range(6):          # seq_ref.margin above 4 eps_seq with the k exact peaks held
+                    s = seq_sel[i:i + 1] if m else None
+                    worst, held = SQ.margin(steps[i:i + 1], live.rows, k, SEQ_G, sep, self.dtype, tags=live.tags, sel=s,
+                                            max_gap_ms=-1 if gap is None else gap)
+                    must[name][i] = bool(ok[i] and (s is None or s.any()) and held and worst > 4)
         exp["must_certify"] = must
         return exp
+
+
+def fold_name(op, weighted, masked):
+    return f"fold_{op}{'_w' if weighted else ''}{'_masked' if masked else ''}"
+
+
+def _fold_weights(weights, terms):
+    return [[1.0] * terms.shape[1]] * terms.shape[0] if weights is None else weights
+
+
+def boost_values(shown):
+    """fp32 [len]: the values ``bias_of_rows`` is given for the rows ``shown`` (flat, -1 padded): 2.0 - 0.02 x the place
+    where the row first occurs - distinct per row, descending, large enough to decide a ranking on their own; a row shown
+    twice carries one value, so the order of the builder's stores does not matter."""
+    shown = np.asarray(shown, np.int64).ravel()
+    first = {}
+    for i, r in enumerate(shown.tolist()):
+        first.setdefault(r, i)
+    return np.array([2.0 - 0.02 * first[r] for r in shown.tolist()], np.float32)
 
 
 @functools.lru_cache(maxsize=8)
@@ -395,7 +489,8 @@ def _same(got, want, what):
 
 UNCERT = ("uncertified_count", "grouped_uncertified_count", "scoped_uncertified_count",
           "group_scoped_uncertified_count", "clip_uncertified_count", "masked_uncertified_count", "span_uncertified_count",
-          "mix_uncertified_count", "diverse_uncertified_count")
+          "mix_uncertified_count", "diverse_uncertified_count", "bias_uncertified_count", "fold_uncertified_count",
+          "seq_uncertified_count")
 
 
 def _pair(got_s, got_r, want, what):
@@ -427,14 +522,46 @@ def _masks(mem, io, p: Probes, exp, shown, carry, at):
     return io.stack(built)
 
 
+def _bias(mem, io, model: Model, p: Probes, exp, shown, carry, at):
+    """The four bias columns of a checkpoint as one stack ``[4, S]`` on ``mem``: zeros, ``bias_of_rows`` of the rows
+    ``topk`` just returned (the device tensor, -1 padding and all), ``bias_of_age``, and the carried column.  The two the
+    memory builds must be the model's arrays bit for bit at the slots of live rows (the other entries of ``bias_of_rows``
+    are unspecified), and ``bias_of_age`` must leave its fill in every other slot."""
+    lo, live = model.window()
+    cols = mem.new_bias(4)
+    mem.bias_of_rows(shown, [float(v) for v in boost_values(exp["topk"][0])], out=cols[1])
+    mem.bias_of_age(p.bias_now, AGE_PER_MS, fill=AGE_FILL, out=cols[2])
+    if carry.get("bias") is not None:
+        cols[3][...] = carry["bias"]
+    slots = (lo + np.arange(live.rows.shape[0], dtype=np.int64)) % model.capacity
+    for i, name in ((1, "bias_of_rows"), (2, "bias_of_age")):
+        got = np.ascontiguousarray(io.col_at(cols[i], slots), np.float32)
+        assert np.array_equal(got.view(np.uint32), exp["bias_cols"][i][slots].view(np.uint32)), \
+            f"{at}{name}: the column differs from the model's at the slots of live rows"
+    dead = np.setdiff1d(np.arange(exp["bias_cols"].shape[1]), slots)
+    assert (np.asarray(io.col_at(cols[2], dead)) == np.float32(AGE_FILL)).all(), at + "bias_of_age: a slot without a live row is not the fill"
+    carry["built_bias"] = io.keep(cols[1])
+    return cols
+
+
+def _seq_answer(got, want, what):
+    """(scores, rows, step_rows, step_scores) of the memory against the oracle's (rows, scores, step_rows, step_scores)."""
+    s, r, sr, ss = got
+    _pair(s, r, want, what)
+    _same(sr, want[2], what + " step rows")
+    assert _bits_equal(ss, want[3]), what + " step scores (bit-exact bar)"
+
+
 def checkpoint(mem, model: Model, p: Probes, io, exp=None, label="", carry=None):
-    """``mem`` against ``model``: the accessors, then the fourteen readers; -> the ``*_uncertified_count`` of every
+    """``mem`` against ``model``: the accessors, then the seventeen readers; -> the ``*_uncertified_count`` of every
     reader.  ``io`` carries what is not part of the memory's surface: ``t(bits)`` (bit patterns -> what the memory takes
     as rows), ``ordinals(mem)`` (the ordinal column of the live rows in row-id order, vm_memory_group_ordinals),
     ``raw(mem, n)`` (rows, tags, keys, ordinals over slots [0, n) in slot order), ``stack(masks)``, ``f64(x)`` and
-    ``i64d(x)`` (what the memory takes as stacked masks, as a device fp64 and as a device int64 tensor).  ``carry``: a
-    dict; ``carry["masks"]`` are the previous checkpoint's exclusion mask and its complement as this memory built them
-    (searched again now, stale), ``carry["built"]`` receives this checkpoint's."""
+    ``i64d(x)`` (what the memory takes as stacked masks, as a device fp64 and as a device int64 tensor), ``col_at(col,
+    slots)`` (a bias column read back at the given slots) and ``keep(col)`` (a copy of a column that outlives its stack).
+    ``carry``: a dict; ``carry["masks"]`` are the previous checkpoint's exclusion mask and its complement and
+    ``carry["bias"]`` its ``bias_of_rows`` column as this memory built them (searched again now, stale), ``carry["built"]``
+    and ``carry["built_bias"]`` receive this checkpoint's."""
     carry = {} if carry is None else carry
     exp = model.expect(p) if exp is None else exp
     lo, live = model.window()
@@ -472,6 +599,15 @@ def checkpoint(mem, model: Model, p: Probes, io, exp=None, label="", carry=None)
             f"{at}model: query 0 of {name} is not topk's"
     assert np.array_equal(exp["diverse"][0][0], exp["masked"][0][0]) and _bits_equal(exp["diverse"][1][0], exp["masked"][1][0]), \
         at + "model: lam = 1 is not topk_masked"
+    # the zero column, a column index out of range and a weight of 0.0 are topk (with the masks: topk_masked); one step
+    # with min_sep = 1 is topk
+    assert BIAS_INDEX[0] == 0 and not 0 <= BIAS_INDEX[4] < 4 and BIAS_W[5] == 0.0 and BIAS_PLAIN == (0, 4, 5)
+    for name, plain in (("biased", "topk"), ("biased_masked", "masked")):
+        for i in BIAS_PLAIN:
+            assert np.array_equal(exp[name][0][i], exp[plain][0][i]) and _bits_equal(exp[name][1][i], exp[plain][1][i]), \
+                f"{at}model: query {i} of {name} is not {plain}'s"
+    assert np.array_equal(exp["seq_one"][0], exp["topk"][0]) and _bits_equal(exp["seq_one"][1], exp["topk"][1]) and \
+        np.array_equal(exp["seq_one"][2][:, :, 0], exp["topk"][0]), at + "model: J = 1, min_sep = 1 is not topk"
     must = exp["must_certify"]
     q, terms, lam, shown = io.t(p.queries), io.t(p.terms), io.f64(LAM), None
     for exact in (False, True):
@@ -531,6 +667,29 @@ def checkpoint(mem, model: Model, p: Probes, io, exp=None, label="", carry=None)
             s, r = mem.recall_links(p.links[0], p.links[1], k=LINK_K, min_gap=LINK_GAP, max_back=back, exclude_group=own,
                                     block=LINK_BLOCK, exact=exact)
             _pair(s, r, want, form + f"recall_links max_back={back} exclude_group={own}")
+        # ---- the biased, the any/all and the sequence search
+        if not exact:
+            bias = _bias(mem, io, model, p, exp, shown, carry, at)
+            seq_masks = io.stack([*masks, ~mem.mask_of_rows([p.seq_excluded])])
+            seqs, ones = io.t(p.seqs), io.t(p.queries[:, None, :])
+        with_masks = {"mask": masks, "mask_index": list(MASK_INDEX)}
+        for name, kw in (("biased", {}), ("biased_masked", with_masks)):
+            s, r = mem.topk_biased(q, p.k, bias, weight=list(BIAS_W), bias_index=list(BIAS_INDEX), exact=exact, **kw)
+            _pair(s, r, exp[name], form + f"topk_biased {name}")
+            fast("last_bias_flags", name)
+        for op, w, m in FOLD_CALLS:
+            name = fold_name(op, w, m)
+            s, r, t = mem.topk_fold(terms, p.k, op=op, weights=WEIGHTS if w else None, exact=exact, **(with_masks if m else {}))
+            _pair(s, r, exp[name], form + f"topk_fold {name}")
+            _same(t, exp[name][2], form + f"topk_fold {name} term indices")
+            fast("last_fold_flags", name)
+        for name, (sep, gap, m) in SEQ_CALLS.items():
+            kw = {"mask": seq_masks, "mask_index": list(SEQ_MASK_INDEX)} if m else {}
+            _seq_answer(mem.topk_seq(seqs, p.k, max_step=SEQ_G, min_sep=sep, max_gap_ms=gap, exact=exact, **kw), exp[name],
+                        form + f"topk_seq {name}")
+            fast("last_seq_flags", name)
+        _seq_answer(mem.topk_seq(ones, p.k, max_step=SEQ_G, min_sep=1, exact=exact), exp["seq_one"], form + "topk_seq J=1")
+        fast("last_seq_flags", "seq_one")
     link, seg = exp["events"]
     ev = mem.events(p.threshold, max_gap_ms=p.gap_ms, with_links=True)
     assert ev.count == seg.count, f"{at}events count {ev.count} != {seg.count}"
@@ -607,9 +766,10 @@ class Driver:
         self.seq = 0
         self.stored = 0                  # rows that ever became live
         self.restored = []               # the drivers ``restore`` made: their memories are the caller's to close
-        self.carry = {}                  # the last checkpoint's exclusion masks (the memory's, and the model's words) and
-                                         # span: searched again, stale, after the next mutation; a restored memory is a
-                                         # new object and starts without them, a reset or an erase keeps them
+        self.carry = {}                  # the last checkpoint's exclusion masks (the memory's, and the model's words), its
+                                         # boost column (the memory's, and the model's array) and span: searched again,
+                                         # stale, after the next mutation; a restored memory is a new object and starts
+                                         # without them, a reset or an erase keeps them
         self.last_erase = None           # new_row_of of the erase since the last checkpoint
 
     # -- data
@@ -788,8 +948,40 @@ class Driver:
                for c in range(6)]
         terms = np.stack([np.stack([q[c], q[(c + 1) % 6], far[c]]) for c in range(6)])
         w = min(n, LINK_ROWS)
+        seqs, excluded = self.sequences(live, rnd)
+        now = int(live.tags[-1]) & ((1 << MS_BITS) - 1) if n else 0
         return Probes(q, scopes, clips, range_min, mask_scopes=[one, window], carried=self.carry.get("words"), spans=spans,
-                      carried_span=self.carry.get("span"), terms=terms, links=(total - w, w))
+                      carried_span=self.carry.get("span"), terms=terms, links=(total - w, w), bias_now=now,
+                      carried_bias=self.carry.get("bias_col"), seqs=seqs, seq_excluded=excluded)
+
+    def chains(self, live, rnd):
+        """int64 [6, 4]: the live indices of the rows the six sequences are noisy copies of, from the model alone.
+        (a) across the driver's ``join`` - rows j - 1 and j became adjacent in an erase - when there is one; (b) ends at
+        the newest row; (c) begins at the oldest live row - in a wrapped ring whose slot 0 lies inside the window (every
+        wrapped checkpoint but the one at exactly twice the capacity) around the row in slot 0 instead, so that its rows
+        straddle slots capacity - 1 and 0; (d) around the first change of source, where no chain may hold them all; (e)
+        four adjacent rows of one event, of which the sequence's mask leaves out the second; (f) around the probe query's
+        row, searched under the carried mask."""
+        n, m = live.rows.shape[0], self.model
+        at = lambda first, gaps=(2, 1, 2): min(max(int(first), 0), n - 1 - sum(gaps)) + np.cumsum([0, *gaps])
+        j = self.join if self.join is not None and 3 <= self.join <= n - 3 else n // 2
+        w = (-m.base) % m.capacity                           # the live index of the row in slot 0
+        cuts = np.nonzero((live.tags[1:] >> MS_BITS) != (live.tags[:-1] >> MS_BITS))[0] + 1
+        starts = np.nonzero(np.concatenate([[True], live.keys[1:] != live.keys[:-1]]))[0]
+        long = [int(s) for s, e in zip(starts, np.concatenate([starts[1:], [n]])) if e - s >= 6 and s >= n // 3]
+        return np.stack([at(j - 3), at(n - 6), at(w - 3) if m.wrapped and 3 <= w <= n - 3 else at(0),
+                         at(cuts[0] - 3) if cuts.size else at(n // 4), at((long[0] if long else n // 3) + 1, (1, 1, 1)),
+                         at(rnd - 2)])
+
+    def sequences(self, live, rnd):
+        """-> (uint16 [6, 4, D] the sequences, the row id the mask of (e) leaves out or -1): seq_ref.steps_at of
+        ``chains``; never-stored rows when fewer than 16 rows are live."""
+        n = live.rows.shape[0]
+        if n < 16:
+            spare = self.bits[-6:]
+            return np.stack([spare[[(i + j) % 6 for j in range(SEQ_J)]] for i in range(6)]), -1
+        chains = self.chains(live, rnd)
+        return SQ.steps_at(live.rows, self.dtype, chains, 7), self.model.base + int(chains[4, 1])
 
     def check(self, label):
         n = self.model.total - self.model.base
@@ -798,12 +990,13 @@ class Driver:
         exp = self.model.expect(p)
         for hook in self.hooks:
             hook(label, self, p, exp)
-        carry = {"masks": self.carry.get("masks")}
+        carry = {"masks": self.carry.get("masks"), "bias": self.carry.get("bias")}
         self.log.append((label, checkpoint(self.mem, self.model, p, self.io, exp, label, carry)))
         shown = exp["topk"][0]
         words = MR.pack_rows(shown[shown >= 0], self.model.capacity)         # mask_of_rows of the rows shown, by the model
         self.carry = {"masks": carry["built"], "words": (~words, words),
-                      "span": (self.model.base + 10, self.model.total - 10)}
+                      "span": (self.model.base + 10, self.model.total - 10),
+                      "bias": carry["built_bias"], "bias_col": exp["bias_cols"][1]}   # the memory's column, and the model's
         self.last_erase = None
 
 

@@ -3,7 +3,9 @@
 The small layout (6,000 rows, D = 128, pretend boundaries at rows 2,048 and 4,096) is built by the recipe of the large one;
 for every search family of tests/test_bigmem_gpu.py the oracle over the neighbourhood rows, mapped to row ids, must equal
 the same oracle over all 6,000 rows, rows and scores, on the very cases the GPU test runs.  The noise bound must hold for
-every row, and an erase must move the model as it moves the dense array.
+every row, and an erase must move the model as it moves the dense array.  For the biased, the any/all and the sequence
+search the same, with term indices, chains and the sparse ``must`` against ``seq_ref.margin``; one negative per method: an
+operand that breaks the proof trips its assertion and no answer comes back.
 """
 from __future__ import annotations
 
@@ -11,9 +13,12 @@ import numpy as np
 import pytest
 
 from oracle import cref
+from tests import bias_ref as BR
 from tests import bigmem_ref as B
 from tests import clip_ref as CL
 from tests import diverse_ref as DR
+from tests import fold_ref as FR
+from tests import seq_ref as SQ
 from tests import events_ref as V
 from tests import summary_ref as M
 from tests import group_ref as G
@@ -194,6 +199,107 @@ def test_mix_and_diverse(mem):
     _eq(sparse.diverse(q, B.DIV_K, B.POOL, lam), DR.diverse_topk(q, bits, None, B.DIV_K, B.POOL, lam), "diverse")
 
 
+CAP = L.N + L.spare
+
+
+def _bias_columns(sparse, tags):
+    """-> (the model's two columns, the same columns whole: fp32 [2, S] by the builders' restatements over all rows)."""
+    rows, values = B.boost_rows(L)
+    now = L.N - 1
+    cols = [sparse.col_of_rows(rows, values, CAP), sparse.col_of_age(now, B.age_per_ms(L), B.AGE_FILL, CAP)]
+    whole = np.stack([BR.bias_from_rows_ref(rows, values, 0, L.N, CAP),
+                      BR.bias_from_tags_ref(tags, 0, CAP, now, B.age_per_ms(L), B.AGE_FILL)])
+    return cols, whole
+
+
+def test_biased(mem):
+    bits, _, tags, sparse = mem
+    cols, whole = _bias_columns(sparse, tags)
+    for col, w in zip(cols, whole):         # the model's entries are the builders', and its bounds hold on every other slot
+        assert np.array_equal(col.at.view(np.uint32), w[sparse.gid % CAP].view(np.uint32))
+        rest = np.delete(w[:L.N], sparse.gid)
+        assert (col.lo <= rest).all() and (rest <= col.hi).all()
+    assert (whole[1][L.N:] == np.float32(B.AGE_FILL)).all()
+    q, betas = B.queries(L, 16, 13), B.bias_weights()
+    assert {0.0, -0.5, 2.0 ** -12} <= set(betas) and min(b for b, c in zip(betas, B.BIAS_INDEX) if c == 1) >= 0
+    got = sparse.biased(q, cols, B.BIAS_INDEX, betas, B.BIAS_K)
+    _eq(got, BR.bias_topk(q, bits, whole, list(B.BIAS_INDEX), betas, None, B.BIAS_K, capacity=CAP), "biased")
+    plain = cref.cosine_topk(q, bits, B.BIAS_K, dtype="f16")
+    for f, (c, beta) in enumerate(zip(B.BIAS_INDEX, betas)):
+        m = B.members(L, f)
+        if c not in (0, 1) or beta == 0.0:           # the zero column, a weight of 0: topk bit for bit
+            _eq((got[0][f:f + 1], got[1][f:f + 1]), (plain[0][f:f + 1], plain[1][f:f + 1]), f"biased query {f}")
+        elif c == 0 and beta == 1.0:                  # a lower level below b2 outranks the higher one above it
+            assert got[0][f, 0] == m[4] < L.b2 <= m[0] and m[0] in got[0][f] and plain[0][f, 0] != m[4]
+        elif c == 1 and beta == 1.0:                  # age: the tail's member passes the one below b1
+            assert got[0][f].tolist().index(m[2]) < got[0][f].tolist().index(m[1])
+    assert any(c == 0 and b == 1.0 for c, b in zip(B.BIAS_INDEX, betas)) and any(c == 1 and b == 1.0 for c, b in zip(B.BIAS_INDEX, betas))
+    # negative: one positive entry on a noise slot that is no candidate breaks the proof, and no answer comes back
+    with pytest.raises(AssertionError, match="outside the candidates"):
+        sparse.biased(q, [cols[0]._replace(hi=1.0), cols[1]], B.BIAS_INDEX, betas, B.BIAS_K)
+
+
+@pytest.mark.parametrize("op", ["max", "min"])
+def test_fold(mem, op):
+    bits, _, _, sparse = mem
+    terms, w = B.fold_cases(L)[op]
+    got = sparse.fold(terms, w, B.FOLD_K, op)
+    _eq(got, FR.fold_topk(terms, w, bits, None, B.FOLD_K, op), "fold " + op)
+    if op == "max":       # more than one term names a query's five best rows; where rows 0 and 1 do not crowd in, all three
+        assert all(len(set(t.tolist())) > 1 for t in got[2]) and all(set(t.tolist()) == {0, 1, 2} for t in got[2][2:14]), got[2]
+    else:                 # three copies of one family: which one is the worst differs from row to row
+        assert set(got[2].ravel().tolist()) == {0, 1, 2}
+    assert (got[0] >= L.b2).any(1).all() and (got[0] < L.b1).any(1).all()
+
+
+def test_fold_min_of_an_absent_family_trips_the_floor(mem):
+    _, _, _, sparse = mem
+    terms, _ = B.fold_cases(L)["max"]                 # families c, c + 1, c + 2: no row resembles all three
+    with pytest.raises(AssertionError, match="fold min"):
+        sparse.fold(terms, [[1.0] * 3] * 16, B.FOLD_K, "min")
+
+
+def _dense_sel(cases):
+    return np.stack([np.ones(L.N, bool) if x is None else np.arange(L.N) != x for _, _, _, x in cases])
+
+
+@pytest.mark.parametrize("group", ["b2", "b1"])
+def test_seq(mem, group):
+    bits, _, tags, sparse = mem
+    cases = B.seq_cases(L)[group]
+    steps, sel, dsel = B.seq_steps(L, cases), B.seq_sel(sparse, cases), _dense_sel(cases)
+    for k, ms in ((1, None), (B.SEQ_K, B.SEQ_MIN)):
+        got = sparse.seq(steps, k, B.SEQ_G, B.SEQ_SEP, sel=sel, min_score=ms)
+        _eq(got[:4], SQ.seq_topk(steps, bits, k, B.SEQ_G, B.SEQ_SEP, tags=tags, sel=dsel, min_score=ms), f"seq k={k}")
+        for c in np.flatnonzero(got[4]):       # where the sparse condition says "must certify", the dense margin agrees
+            worst, held = SQ.margin(steps[c:c + 1], bits, k, B.SEQ_G, B.SEQ_SEP, tags=tags, sel=dsel[c:c + 1])
+            assert held and worst > 4, (c, worst, held)
+        if k == 1:
+            assert got[4].all(), got[4]
+        for c, (name, chain, cut, excluded) in enumerate(cases):
+            if cut:           # no chain across the source change; without tags it is the answer
+                assert got[0][c, 0] != chain[-1] and not any(got[2][c, i].tolist() == list(chain) for i in range(k)), name
+                free = SQ.seq_topk(steps[c:c + 1], bits, 1, B.SEQ_G, B.SEQ_SEP)
+                assert free[2][0, 0].tolist() == list(chain) and free[1][0, 0] > got[1][c, 0], name
+            elif excluded is None:
+                assert got[2][c, 0].tolist() == list(chain), (name, got[2][c, 0])
+            elif excluded in chain:       # no returned chain holds the excluded row: the answer is another site's
+                assert excluded not in got[2][c] and got[2][c, 0].tolist() != list(chain), name
+            else:             # a chain may step over a row its mask does not select
+                assert got[2][c, 0].tolist() == list(chain) and chain[0] < excluded < chain[-1], name
+    # the chain at gaps of 2 needs max_step >= 2: with max_step = 1 another one is the answer
+    one = sparse.seq(steps[:1], 1, 1, B.SEQ_SEP, min_score=B.SEQ_MIN)
+    _eq(one[:4], SQ.seq_topk(steps[:1], bits, 1, 1, B.SEQ_SEP, tags=tags, min_score=B.SEQ_MIN), "seq max_step=1")
+    assert one[2][0, 0].tolist() != list(cases[0][1])
+
+
+def test_seq_reach_beyond_the_inset_trips(mem):
+    _, _, _, sparse = mem
+    cases = B.seq_cases(L)["b2"]
+    with pytest.raises(AssertionError, match="a planted row within 32 rows"):
+        sparse.seq(B.seq_steps(L, cases), 1, 16, B.SEQ_SEP)
+
+
 def test_erase_moves_the_model(mem):
     bits, keys, tags, _ = mem
     _, sparse = B.dense(L)
@@ -228,6 +334,30 @@ def test_a_wrapped_offset_would_show(mem, boundary):
     above = {f: B.members(L, f)[0 if boundary == "b2" else 5] for f in range(B.FAMILIES)}
     for f in range(2, B.FAMILIES):      # (families 0 and 1 would find their copies of rows 0 and 1 there instead)
         assert above[f] in good[f] and above[f] not in bad[f]
+    # the three newer searches: every family has a member in [b, b + 48), and each expectation over all of a family's
+    # members changes when those rows are read from r - b
+    differ = lambda a, b_: ((a[0] != b_[0]) | (a[1].view(np.int64) != b_[1].view(np.int64))).any(axis=1)
+    tags = B.tag_of(L, np.arange(L.N))
+    cols, _ = _bias_columns(sparse, tags)
+    betas = B.bias_weights()
+    good = sparse.biased(q, cols, B.BIAS_INDEX, betas, B.LEVELS)
+    e = cref.cosine_matrix(q, np.ascontiguousarray(wrong.rows), dtype="f16")
+    b_at = np.stack([cols[c].at if c in (0, 1) else np.zeros_like(cols[0].at) for c in B.BIAS_INDEX])
+    bad = BR.bias_topk_from_cosines(e, betas, b_at, None, B.LEVELS)
+    assert differ(good, (wrong._ids(bad[0]), bad[1])).all()
+    terms, w = B.fold_cases(L)["min"]       # three copies of one family for both ops: all nine members are returned
+    for op in ("max", "min"):
+        good = sparse.fold(terms, w, B.LEVELS, op)
+        bad = FR.fold_topk(terms, w, wrong.rows, None, B.LEVELS, op)
+        assert differ(good, (wrong._ids(bad[0]), bad[1])).all(), op
+    cases = B.seq_cases(L)[boundary]
+    steps, sel = B.seq_steps(L, cases), B.seq_sel(sparse, cases)
+    good = sparse.seq(steps, 1, B.SEQ_G, B.SEQ_SEP, sel=sel, min_score=B.SEQ_MIN)
+    bad = wrong.seq(steps, 1, B.SEQ_G, B.SEQ_SEP, sel=sel, min_score=B.SEQ_MIN)
+    for c, (name, chain, cut, _) in enumerate(cases):       # every case whose answer has a row at or above the boundary
+        if b <= good[0][c, 0] < b + B.HOOD:
+            assert good[2][c, 0].tolist() != bad[2][c, 0].tolist(), name
+    assert sum(b <= r < b + B.HOOD for r in good[0][:, 0]) >= 2
 
 
 def test_bf16_recipe():

@@ -8,6 +8,14 @@ numbers alone (tests/test_bigmem_cpu.py: equal to the dense oracle on a small la
 where the oracle's gap condition holds the fast path must certify the query itself (flag 0): a wrong scan may not hide
 behind the redo.  No tolerance anywhere.
 
+The biased, the any/all and the sequence search run on the same memory (``test_biased``, ``test_fold``, ``test_seq``, and once
+more each behind the erase and in the ring; one biased call in bf16): the two bias columns as ``bias_of_rows`` and
+``bias_of_age`` build them must equal their restatements bit for bit at the sites, the fold's term indices and the
+sequences' step rows and step score bits must be the oracle's.  ``test_biased`` and ``test_fold`` demand flag 0 of all 16
+queries (the model asserts ``bias_ref.flag0_ok`` / ``fold_ref.flag0_ok`` for each); ``test_seq`` demands it wherever
+``seq_ref.margin``'s condition holds over the merged runs above 4 eps_seq - of every sequence at k = 1 (asserted) - and
+prints how many sequences were flagged and how many had to be certified.
+
 Read-only tests first, then the gated append, the erase and the ring; the mutating tests update the model, so every test
 derives its expectation from the model as it is.  One memory at a time: the ring test closes the first one.
 With BIGMEM_JSON set, the wall time of the build and of every test and the device memory the fixture took are written to
@@ -179,14 +187,15 @@ def test_topk_exact_and_exhaustive(st):
     _pair(s, r, want, "topk k=59")
 
 
-def _both(call, want, flags, Q, what, keys=None):
-    """One filtered search in its fast and its exact form; ``flags``: a callable -> the fast call's flags."""
+def _both(call, want, flags, Q, what, keys=None, third="keys"):
+    """One filtered search in its fast and its exact form; ``flags``: a callable -> the fast call's flags.  ``keys``: what
+    the call's third output must be, named ``third`` in the failure."""
     for exact in (False, True):
         out = call(exact)
         form = what + (" exact" if exact else "")
         _pair(out[0], out[1], want, form)
         if keys is not None:
-            assert np.array_equal(np_of(out[2]), keys), form + " keys"
+            assert np.array_equal(np_of(out[2]), keys), f"{form} {third}"
         if not exact:
             _flags0(flags(), Q, form)
 
@@ -352,6 +361,114 @@ def test_events(st):
     assert np.array_equal(ev.first_rows[torch.from_numpy(event_of).cuda()].cpu().numpy(), first), "first_rows at the sites"
 
 
+# ---- the three newer searches: biased, any/all, sequence -------------------------------------------------------------------
+def _bias_columns(mem, model, what=""):
+    """The two columns as the device builds them -> (device fp32 [2, S], the model's columns).  At the sites each must be
+    the builder's restatement bit for bit (read by slot: ``model.gid % capacity``)."""
+    rows, values = B.boost_rows(L)
+    now, per_ms = model.newest_ms, B.age_per_ms(L)
+    want = [model.col_of_rows(rows, values, mem.capacity), model.col_of_age(now, per_ms, B.AGE_FILL, mem.capacity)]
+    cols = mem.new_bias(2)
+    mem.bias_of_rows(torch.tensor(rows, dtype=torch.int64).cuda(), values, out=cols[0])
+    mem.bias_of_age(now, per_ms, fill=B.AGE_FILL, out=cols[1])
+    slots = torch.from_numpy(model.gid % mem.capacity).cuda()
+    for name, col, w in zip(("bias_of_rows", "bias_of_age"), cols, want):
+        got = col[slots].cpu().numpy()
+        assert np.array_equal(got.view(np.uint32), w.at.view(np.uint32)), f"{what}{name}: the column differs at the sites"
+    if mem.searchable < mem.capacity:       # slots without a live row hold the fill
+        assert bool((cols[1][mem.searchable:mem.capacity] == B.AGE_FILL).all()), what + "bias_of_age: fill"
+    return cols, want
+
+
+def _biased(mem, model, what=""):
+    dtype = model.dtype
+    q, betas, index = B.queries(L, 16, 13, dtype=dtype), B.bias_weights(), list(B.BIAS_INDEX)
+    cols, at = _bias_columns(mem, model, what)
+    want = model.biased(q, at, index, betas, B.BIAS_K)
+    _both(lambda e: mem.topk_biased(from_bits(q, dtype), B.BIAS_K, cols, weight=betas, bias_index=index, exact=e), want,
+          lambda: mem.last_bias_flags, 16, what + "biased")
+    return want
+
+
+def test_biased(st):
+    want = _biased(st.mem, st.model)
+    rows = want[0]
+    assert (rows >= L.b2).any() and (rows < L.b1).any() and ((rows >= L.b1) & (rows < L.b2)).any()
+    for f, (c, beta) in enumerate(zip(B.BIAS_INDEX, B.bias_weights())):
+        m = B.members(L, f)
+        if c == 0 and beta == 1.0:          # the boosted member below 4 GiB outranks the better one above it
+            assert rows[f, 0] == m[4] and m[0] in rows[f]
+        if c == 1 and beta == 1.0:          # age: the member at the tail, past 4 GiB, passes the one below 2 GiB
+            assert rows[f].tolist().index(m[2]) < rows[f].tolist().index(m[1])
+
+
+def _fold(mem, model, op, what=""):
+    terms, w = B.fold_cases(L)[op]
+    want = model.fold(terms, w, B.FOLD_K, op)
+    _both(lambda e: mem.topk_fold(from_bits(terms), B.FOLD_K, op=op, weights=w, exact=e), want, lambda: mem.last_fold_flags, 16,
+          f"{what}fold {op}", want[2], third="term indices")
+    return want
+
+
+@pytest.mark.parametrize("op", ["max", "min"])
+def test_fold(st, op):
+    rows = _fold(st.mem, st.model, op)[0]
+    assert (rows >= L.b2).any(1).all() and (rows < L.b1).any(1).all()      # every query: rows on both sides of both boundaries
+
+
+def _seq(mem, model, group, k, min_score, what, G=B.SEQ_G, first=None, without=()):
+    """One group of tests/bigmem_ref.seq_cases (``first``: only that many of them), fast and exact: end rows, score bits,
+    step rows and step score bits; where the model's margin condition holds the fast path must certify the sequence.
+    ``without``: rows no sequence may use (``~mask_of_rows``), beside the row a case excludes itself."""
+    cases = B.seq_cases(L)[group][:first]
+    steps = B.seq_steps(L, cases)
+    sel = B.seq_sel(model, cases) & ~np.isin(model.gid, list(without))
+    masks, index = None, None
+    if without or any(x is not None for _, _, _, x in cases):
+        sets = sorted({x for _, _, _, x in cases}, key=lambda x: -1 if x is None else x)
+        drop = [list(without) + ([] if x is None else [x]) for x in sets]
+        masks = torch.stack([~mem.mask_of_rows(d) if d else ~mem.new_mask()[0] for d in drop])
+        index = [sets.index(x) for _, _, _, x in cases]
+    want = model.seq(steps, k, G, B.SEQ_SEP, sel=sel, min_score=min_score)
+    for exact in (False, True):
+        s, r, sr, ss = mem.topk_seq(from_bits(steps), k, max_step=G, min_sep=B.SEQ_SEP, mask=masks, mask_index=index,
+                                    min_score=min_score, exact=exact)
+        form = what + (" exact" if exact else "")
+        _pair(s, r, want, form)
+        assert np.array_equal(np_of(sr), want[2]), form + " step rows"
+        assert np.array_equal(np.ascontiguousarray(np_of(ss), np.float64).view(np.int64), want[3].view(np.int64)), form + " step scores"
+        if not exact:
+            flags = np_of(mem.last_seq_flags)[:len(cases)]
+            bad = np.flatnonzero(want[4] & (flags != 0))
+            print(f"{form}: flagged={int((flags != 0).sum())} must={int(want[4].sum())} of {len(cases)}")
+            assert bad.size == 0, f"{form}: the fast path left sequences {bad.tolist()} to the redo, flags {flags.tolist()}"
+    return cases, want
+
+
+@pytest.mark.parametrize("group", ["b2", "b1"])
+def test_seq(st, group):
+    mem, model = st.mem, st.model
+    b = getattr(L, group)
+    cases, want = _seq(mem, model, group, 1, None, f"seq {group} k=1")
+    assert want[4].all(), want[4]           # k = 1: every case meets seq_ref.margin's condition
+    for c, (name, chain, cut, excluded) in enumerate(cases):
+        if cut:                             # b1 and b2 begin a source: no chain across them
+            assert want[0][c, 0] != chain[-1] and want[2][c, 0].tolist() != list(chain), name
+        elif excluded in chain:
+            assert excluded not in want[2][c, 0], name
+        else:
+            assert want[2][c, 0].tolist() == list(chain), (name, want[2][c, 0])
+    ends = want[0][:4, 0]                   # the cases at the boundary: answers on both sides of it
+    assert (ends >= b).any() and (ends < b).any()
+    cases, want = _seq(mem, model, group, B.SEQ_K, B.SEQ_MIN, f"seq {group} k=3")
+    for c, (name, chain, cut, excluded) in enumerate(cases):
+        if not cut and excluded not in chain:
+            assert want[2][c, 0].tolist() == list(chain), (name, want[2][c, 0])
+    # the chain at gaps of 2 is no chain with max_step = 1
+    cases, want = _seq(mem, model, group, 1, B.SEQ_MIN, f"seq {group} max_step=1", G=1, first=1)
+    assert want[2][0, 0].tolist() != list(cases[0][1])
+
+
 # ---- mutations: each updates the model -------------------------------------------------------------------------------------
 def test_append_novel(st):
     mem, model = st.mem, st.model
@@ -400,6 +517,9 @@ def test_erase(st):
     _plain(mem, model, 4, "after erase: ")
     _plain(mem, model, 160, "after erase: ")
     _scoped_and_grouped(mem, model, "after erase: ")
+    _biased(mem, model, "after erase: ")        # the columns are built anew: the rows behind the erased ones moved a slot
+    _fold(mem, model, "max", "after erase: ")
+    _seq(mem, model, "b1", 1, None, "after erase: seq b1 k=1")
 
 
 def test_ring(st):
@@ -424,6 +544,15 @@ def test_ring(st):
     _spans(mem, model, "ring: ")
     want = _range(mem, model, "ring: ")
     assert all(w[0].min() >= 300 for w in want)
+    # the three newer searches: the columns are read by slot (row id - 300 would be another entry), rows 0 and 1 are gone
+    want = _biased(mem, model, "ring: ")
+    assert want[0].min() >= 300
+    assert _fold(mem, model, "min", "ring: ")[0].min() >= 300
+    # the memory goes on for 300 rows behind the last neighbourhood, so the members at its end are no sound chain rows:
+    # every sequence's mask leaves them out
+    tail = [L.N - 16 + f for f in range(B.FAMILIES)]
+    _, want = _seq(mem, model, "b2", 1, None, "ring: seq b2 k=1", without=tail)
+    assert want[0][want[0] >= 0].min() >= 300 and not np.isin(want[2], tail).any()
 
 
 def test_bf16(st):
@@ -442,3 +571,4 @@ def test_bf16(st):
     for name, (scope, k, _) in B.scope_cases(L).items():
         _both(lambda e: mem.topk_scoped(from_bits(q, "bf16"), k, scope, exact=e), model.scoped(q, scope, k),
               lambda: mem.last_scope_flags, 16, f"bf16: scoped {name}")
+    _biased(mem, model, "bf16: ")

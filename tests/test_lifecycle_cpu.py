@@ -5,9 +5,15 @@
    nine older readers, and that the probes of the five newer ones (``topk_masked``, ``topk_span``, ``topk_mix``,
    ``topk_diverse``, ``recall_links``, fed by ``mask_of_rows`` / ``mask_of_scope`` / ``mask_where``) are not vacuous: the
    masks select some and not all, a stale mask is not a remapped one, dead slots lie under the all-ones mask after a
-   reset, the ring cuts a span, W and lam change a ranking, ``exclude_group`` changes a link;
-3. planted defects: a fake memory answers ``checkpoint`` from a second model instance, all fourteen readers and the mask
-   builders in numpy; the unplanted fake passes, every defect planted in that instance fails with its reader's name.
+   reset, the ring cuts a span, W and lam change a ranking, ``exclude_group`` changes a link; and those of the three newest
+   (``topk_biased`` with ``bias_of_rows`` / ``bias_of_age``, ``topk_fold``, ``topk_seq``): the boost and the age column
+   change a ranking, a stale column is not a remapped one, in the wrapped ring the column by slot is not the column by
+   row - base, dead slots lie under the fill, max and min rank different rows, the sequence across a change of source
+   loses to its untagged self, the masked sequence ends where the unmasked one does over another chain, and in the
+   wrapped ring a chain has rows on both sides of the physical wrap;
+3. planted defects: a fake memory answers ``checkpoint`` from a second model instance, all seventeen readers, the mask and
+   the column builders in numpy; the unplanted fake passes, every defect planted in that instance fails with its reader's
+   name.
 """
 import weakref
 from types import SimpleNamespace
@@ -16,15 +22,18 @@ import numpy as np
 import pytest
 
 from oracle import cref
+from tests import bias_ref as BR
 from tests import clip_ref as CL
 from tests import diverse_ref as DR
 from tests import erase_ref as E
 from tests import events_ref as V
+from tests import fold_ref as FR
 from tests import group_ref as G
 from tests import lifecycle_ref as LC
 from tests import mask_ref as MR
 from tests import mix_ref as XR
 from tests import scope_ref as S
+from tests import seq_ref as SQ
 from tests import span_ref as SP
 
 DTYPES = ["f16", "bf16"]
@@ -48,7 +57,16 @@ class _Mask(np.ndarray):
         _Mask.made = [r for r in _Mask.made if r() is not None] + [weakref.ref(self)]
 
 
-STALE_NORMS = ("stale_norm", "mix_stale_norm", "diverse_stale_norm")
+class _Col(np.ndarray):
+    """A bias column (or a stack of them) of the fake memory, remembered weakly as the masks are: the defect
+    "bias_remapped" has to find the columns a caller kept."""
+    made = []
+
+    def __array_finalize__(self, obj):
+        _Col.made = [r for r in _Col.made if r() is not None] + [weakref.ref(self)]
+
+
+STALE_NORMS = ("stale_norm", "mix_stale_norm", "diverse_stale_norm", "bias_stale_norm", "fold_stale_norm")
 
 
 class FakeMemory:
@@ -65,6 +83,7 @@ class FakeMemory:
         self.ghost = None          # rows an erase left in the slots it vacated (defect "ghost")
         self.stale = None          # the norms an erase left behind in slots [0, n') (defect "stale_norm")
         self.memo = {}             # reader answers since the last mutation: checkpoint asks for both forms of each
+        self.join = None           # the live index where the last erase made two rows adjacent (defect "seq_spans_sources")
 
     # -- accessors
     def __len__(self):
@@ -147,6 +166,19 @@ class FakeMemory:
                 seen.add(mask.__array_interface__["data"][0])
                 was = np.nonzero(MR.selected(np.array(mask).view(np.uint32), 0, keep.size, m.capacity))[0]
                 mask[...] = MR.pack_rows(out.new_row_of[was][keep[was]], m.capacity).view(np.int32)
+        if self.defect == "bias_remapped":                  # every column anybody holds follows its rows
+            seen = set()
+            for ref in _Col.made:
+                col = ref()
+                if col is None or col.shape != (BR.bias_stride(m.capacity),) or col.__array_interface__["data"][0] in seen:
+                    continue
+                seen.add(col.__array_interface__["data"][0])
+                was = np.array(col)
+                col[...] = 0
+                col[out.new_row_of[keep]] = was[np.nonzero(keep)[0]]
+        gone = np.nonzero(~keep)[0]
+        if gone.size and keep[gone[0]:].any():
+            self.join = int(out.new_row_of[gone[0] + np.nonzero(keep[gone[0]:])[0][0]])
         self._sync()
         if self.defect == "tags_not_moved":
             m.tags = old.tags[:n]
@@ -178,7 +210,7 @@ class FakeMemory:
     def reset(self):
         last = self.m.state[1]
         self.m.reset()
-        self.ghost = self.stale = self.old_ids = None
+        self.ghost = self.stale = self.old_ids = self.join = None
         if self.defect == "reset_keeps_open":
             self.m.state = (0, last, 1)
 
@@ -327,8 +359,13 @@ class FakeMemory:
                                   dtype=self.m.dtype, base=lo, sim=sim)
         return s, r, v
 
+    def _aged(self):
+        """A wrapped ring, or a linear memory after an erase: where the defects that need no stale operand are planted, so
+        that the script gets going before they show."""
+        return self.m.wrapped or self.m.total < self.m.used
+
     def recall_links(self, first_row, n_rows, k=10, min_gap=1, max_back=None, exclude_group=False, block=256, exact=False):
-        aged = self.m.wrapped or self.m.total < self.m.used                 # the links go wrong on an aged memory only:
+        aged = self._aged()                                                 # the links go wrong on an aged memory only:
         own = exclude_group and not (aged and self.defect == "links_own_group")     # a wrapped ring, or after an erase
         r, s = self._once(self.m.exp_links, first_row, n_rows, k, min_gap, max_back, own)
         done = n_rows // block * block
@@ -337,7 +374,88 @@ class FakeMemory:
             r[done:], s[done:] = -1, 0.0
         return s, r
 
+    # -- bias columns: fp32 [S] by slot as on the device
+    def new_bias(self, n=1):
+        return np.zeros((n, BR.bias_stride(self.m.capacity)), np.float32).view(_Col)
+
+    def bias_of_rows(self, rows, values, out=None, clear=True):
+        lo, live = self.m.window()
+        col = self.new_bias()[0] if out is None else out
+        col[...] = BR.bias_from_rows_ref(np.asarray(rows, np.int64).ravel(), values, lo, live.rows.shape[0], self.m.capacity,
+                                         start=None if clear else col)
+        return col
+
+    def bias_of_age(self, now_ms, per_ms, fill=0.0, out=None):
+        lo, live = self.m.window()
+        col = self.new_bias()[0] if out is None else out
+        col[...] = BR.bias_from_tags_ref(live.tags, lo, self.m.capacity, now_ms, per_ms, fill)
+        return col
+
+    def topk_biased(self, q, k, bias, weight=None, bias_index=None, mask=None, mask_index=None, exact=False):
+        return self._once(self._topk_biased, q, k, np.array(bias), tuple(weight), tuple(bias_index),
+                          None if mask is None else np.array(mask), mask_index)
+
+    def _topk_biased(self, q, k, bias, weight, bias_index, mask, mask_index):
+        m = self.m
+        lo, live = m.window()
+        rows, Q = live.rows, q.shape[0]
+        n, hi = rows.shape[0], m.written
+        sel = None if mask is None else self._selection(mask, mask_index, Q)
+        b = BR.row_bias(bias, list(bias_index), Q, lo, n, m.capacity)
+        if self.defect == "bias_by_row" and m.wrapped:      # the entry at row - base, not at the slot
+            b = BR.row_bias(bias, list(bias_index), Q, 0, n, m.capacity)
+        if self.defect == "bias_sees_dead_slots" and not m.ring and hi > n:      # the slots past the live count rank too
+            rows, b = self.slots[:hi], BR.row_bias(bias, list(bias_index), Q, 0, hi, m.capacity)
+            sel = None if mask is None else MR.selection(mask.view(np.uint32).reshape(-1, self.W), mask_index, Q, 0, hi, m.capacity)
+        e = cref.cosine_matrix(np.ascontiguousarray(q), np.ascontiguousarray(rows), dtype=m.dtype) if rows.shape[0] else np.zeros((Q, 0))
+        if self.defect == "bias_stale_norm" and self.stale is not None and n:
+            e = e * self._stale_scale()
+        r, s = BR.bias_topk_from_cosines(e, list(weight), b, sel, k, base=lo)
+        return s, r
+
+    def topk_fold(self, terms, k, op="max", weights=None, mask=None, mask_index=None, exact=False):
+        return self._once(self._topk_fold, terms, k, op, weights, None if mask is None else np.array(mask), mask_index)
+
+    def _topk_fold(self, terms, k, op, weights, mask, mask_index):
+        lo, live = self.m.window()
+        sel = None if mask is None else self._selection(mask, mask_index, terms.shape[0])
+        scores = FR.fold_scores_loop
+        if self.defect == "fold_stale_norm" and self.stale is not None and live.rows.shape[0]:
+            scale = self._stale_scale()
+            scores = lambda e, w, o: FR.fold_scores_loop(e * scale, w, o)
+        if self.defect == "fold_term_of_max" and op == "min" and self._aged():      # the right score, the other op's term
+            scores = lambda e, w, o: (FR.fold_scores_loop(e, w, "min")[0], FR.fold_scores_loop(e, w, "max")[1])
+        weights = [[1.0] * terms.shape[1]] * terms.shape[0] if weights is None else weights
+        r, s, t = FR.fold_topk(terms, weights, live.rows, sel, k, op, dtype=self.m.dtype, base=lo, scores=scores)
+        return s, r, t
+
+    def topk_seq(self, steps, k, max_step=4, min_sep=None, mask=None, mask_index=None, max_gap_ms=None, exact=False):
+        return self._once(self._topk_seq, steps, k, max_step, min_sep, None if mask is None else np.array(mask), mask_index,
+                          max_gap_ms)
+
+    def _topk_seq(self, steps, k, G, min_sep, mask, mask_index, max_gap_ms):
+        m = self.m
+        lo, live = m.window()
+        C, J, n = steps.shape[0], steps.shape[1], live.rows.shape[0]
+        out = (np.zeros((C, k)), np.full((C, k), -1, np.int64), np.full((C, k, J), -1, np.int64), np.zeros((C, k, J)))
+        if n == 0:
+            return out
+        el = SQ.eligible(n, C, None if mask is None else self._selection(mask, mask_index, C))
+        brk = CL.tag_breaks(live.tags, -1 if max_gap_ms is None else max_gap_ms)
+        w = (-lo) % m.capacity                              # the live index of the row in slot 0
+        if self.defect == "seq_wrong_side" and m.wrapped and 0 < w < n:
+            brk[w] = True       # its predecessors are read from the other side of the wrap: no chain continues into slot 0
+        if self.defect == "seq_spans_sources" and self.join is not None and self.join < n:
+            brk[self.join] = False                          # the break between the two rows an erase made adjacent
+        for c in range(C):
+            b = brk | ~el[c] if self.defect == "seq_mask_blocks" and self._aged() else brk     # an unselected row ends a chain
+            r, s, sr, ss = SQ.from_scores(CL.frame_scores(steps[c], live.rows, m.dtype), el[c], b, k, G, min_sep, base=lo)
+            out[0][c], out[1][c], out[2][c], out[3][c] = s, r, sr, ss
+        return out
+
     last_mask_flags = last_span_flags = last_mix_flags = last_diverse_flags = np.zeros(6, np.int32)
+    last_bias_flags = last_fold_flags = last_seq_flags = np.zeros(6, np.int32)
+    bias_uncertified_count = fold_uncertified_count = seq_uncertified_count = 0
     uncertified_count = grouped_uncertified_count = scoped_uncertified_count = 0
     group_scoped_uncertified_count = clip_uncertified_count = 0
     masked_uncertified_count = span_uncertified_count = mix_uncertified_count = diverse_uncertified_count = 0
@@ -351,6 +469,8 @@ class FakeIO:
     stack = staticmethod(lambda masks: np.stack([np.asarray(m) for m in masks]))
     f64 = staticmethod(lambda x: np.asarray(x, np.float64))
     i64d = staticmethod(lambda x: np.asarray(x, np.int64))
+    col_at = staticmethod(lambda col, slots: np.asarray(col)[slots])
+    keep = staticmethod(lambda col: col.copy())
     ordinals = staticmethod(lambda mem: mem.m.window()[1].ords)
     raw = staticmethod(lambda mem, n: mem.raw(n))
     restore = staticmethod(lambda mem, capacity: FakeMemory(mem.m.restored(capacity), mem.defect))
@@ -421,7 +541,19 @@ def test_append_follows_the_open_group_rule_and_reset_forgets_it():
 # ---- 2. the conditions of the scripts ----------------------------------------------------------------------------------
 ONCE = ("stale mask differs from a remapped one", "W ranks other rows than term 0", "a lam < 1 query leaves its pool's first k",
         "a link row with an empty past, or live rows before the window", "exclude_group changes a link",
-        "the flag-0 demand is made of every reader")
+        "the flag-0 demand is made of every reader",
+        # the biased, the any/all and the sequence search
+        "the boost column changes a query's rows", "the age column changes a query's rows",
+        "a stale bias column selects other rows than a remapped one", "max and min rank different rows",
+        "sequence (d) scores lower on the tagged window than without tags",
+        "sequence (e) ends at the same row under its mask, over another chain",
+        "the flag-0 demand is made of topk_biased", "the flag-0 demand is made of topk_fold",
+        "the flag-0 demand is made of topk_seq")
+ONCE_WRAPPED = ("the bias column read by slot is not the column read by row - base",
+                "sequence (c) has step rows on both sides of the physical wrap")
+OLDER = ("masked", "masked2", "span", "span_carried", "mix", "mix_masked", "diverse")     # the readers ``must_certify`` had
+DEAD_SLOTS = ("5 erase scope", "6 erase top-k rows, whole regroup", "9 empty", "9 append after erase-to-empty",
+              "10 reset, append", "2 erase scope", "8 reset, append")
 
 
 def _new_reader_conditions(label, d, p, exp, once, at):
@@ -433,8 +565,11 @@ def _new_reader_conditions(label, d, p, exp, once, at):
     sels, sel = [r.size for r in exp["mask_rows"]], exp["sel"]
     if n == 0:
         assert all(c == 0 for c in sels) and not sel.any(), at
-        for name in ("masked", "masked2", "span", "mix", "mix_masked", "diverse"):
+        newer = ("biased", "biased_masked", *(LC.fold_name(*c) for c in LC.FOLD_CALLS), *LC.SEQ_CALLS, "seq_one")
+        for name in ("masked", "masked2", "span", "mix", "mix_masked", "diverse", *newer):
             assert (exp[name][0] == -1).all() and not exp[name][1].any(), at + name
+            assert all((x == -1).all() if x.dtype.kind == "i" else not x.any() for x in exp[name][2:]), at + name
+        assert (exp["bias_cols"][2] == np.float32(LC.AGE_FILL)).all(), at + "bias_of_age of the empty memory is not all fill"
         assert not exp["diverse"][2].any() and all(r.shape == (0, LC.LINK_K) for r, _ in exp["links"]), at
         assert not any(any(v) for v in exp["must_certify"].values()), at
         return
@@ -480,12 +615,57 @@ def _new_reader_conditions(label, d, p, exp, once, at):
     assert not (must["masked"][5] or must["mix_masked"][5] or must["diverse"][5] or must["span"][4]), at + "an empty query"
     if m.outside:
         assert not any(any(v) for v in must.values()), at + "the sticky word is set: every query goes to the redo"
-    once["the flag-0 demand is made of every reader"] += all(any(v) for name, v in must.items())
+    once["the flag-0 demand is made of every reader"] += all(any(v) for name, v in must.items() if name in OLDER)
+    _newest_reader_conditions(label, d, p, exp, once, at)
+
+
+def _newest_reader_conditions(label, d, p, exp, once, at):
+    """The probes of the biased, the any/all and the sequence search are not vacuous, from the oracle's values alone."""
+    m = d.model
+    lo, live = m.window()
+    n, k, cap = live.rows.shape[0], p.k, m.capacity
+    q, cols, index, W = p.queries, exp["bias_cols"], list(LC.BIAS_INDEX), list(LC.BIAS_W)
+    once["the boost column changes a query's rows"] += not np.array_equal(exp["biased"][0][1], exp["topk"][0][1])
+    once["the age column changes a query's rows"] += not np.array_equal(exp["biased"][0][2], exp["topk"][0][2])
+    if d.last_erase is not None and p.carried_bias is not None:     # stale: the entry names whichever row lives in the slot now
+        new = d.last_erase
+        kept = np.nonzero(new >= 0)[0]
+        remapped = cols.copy()
+        remapped[3] = 0
+        remapped[3][new[kept] % cap] = p.carried_bias[kept % cap]
+        once["a stale bias column selects other rows than a remapped one"] += not np.array_equal(
+            m.exp_biased(q, remapped, None, k)[0][3], exp["biased"][0][3])
+    slots = (lo + np.arange(n)) % cap
+    dead = np.setdiff1d(np.arange(cols.shape[1]), slots)
+    assert (cols[2][dead] == np.float32(LC.AGE_FILL)).all() and (np.abs(cols[2][slots]) < 2.0 ** 40).all(), at
+    assert np.abs(LC.AGE_FILL * max(W)) > 2 + np.abs(cols[:, slots]).max() * max(np.abs(W)), at + "the fill would not win"
+    if label in DEAD_SLOTS:         # a slot that held a row once and holds none now lies under the fill
+        assert m.written > n and (cols[2][n:m.written] == np.float32(LC.AGE_FILL)).all(), at + "no dead slot under the fill"
+    e = cref.cosine_matrix(np.ascontiguousarray(q), np.ascontiguousarray(live.rows), dtype=m.dtype)
+    if m.wrapped:
+        by_row = BR.bias_topk_from_cosines(e, W, BR.row_bias(cols, index, 6, 0, n, cap), None, k, base=lo)
+        once[ONCE_WRAPPED[0]] += not np.array_equal(by_row[0], exp["biased"][0])
+        step_slots = exp["seq"][2][2, 0] % cap
+        once[ONCE_WRAPPED[1]] += bool(exp["seq"][0][2, 0] >= 0 and step_slots.max() >= cap - 3 and step_slots.min() <= 2)
+    once["max and min rank different rows"] += not np.array_equal(exp["fold_max"][0], exp["fold_min"][0])
+    assert all(((exp[LC.fold_name(*c)][2] >= 0) == (exp[LC.fold_name(*c)][0] >= 0)).all() for c in LC.FOLD_CALLS), at
+    free = m.exp_seq(p.seqs[3:4], None, k, LC.SEQ_G, 1, tags=False)
+    once["sequence (d) scores lower on the tagged window than without tags"] += bool(free[1][0, 0] > exp["seq"][1][3, 0])
+    plain = m.exp_seq(p.seqs[4:5], None, k, LC.SEQ_G, LC.SEQ_CALLS["seq_masked"][0])
+    under = exp["seq_masked"]
+    assert p.seq_excluded not in under[2][4], at + "a chain of sequence (e) holds the row its mask leaves out"
+    once["sequence (e) ends at the same row under its mask, over another chain"] += bool(
+        under[0][4, 0] == plain[0][0, 0] >= 0 and not np.array_equal(under[2][4, 0], plain[2][0, 0]))
+    must = exp["must_certify"]
+    # as for the older readers: every named call of the reader is asked for flag 0 at one checkpoint
+    once["the flag-0 demand is made of topk_biased"] += any(must["biased"]) and any(must["biased_masked"])
+    once["the flag-0 demand is made of topk_fold"] += all(any(must[LC.fold_name(*c)]) for c in LC.FOLD_CALLS)
+    once["the flag-0 demand is made of topk_seq"] += all(any(must[name]) for name in (*LC.SEQ_CALLS, "seq_one"))
 
 
 def _conditions(seen, once=None):
     once = {} if once is None else once
-    once.update({name: 0 for name in ONCE})
+    once.update({name: 0 for name in ONCE + ONCE_WRAPPED})
 
     def hook(label, d, p, exp):
         lo, live = d.model.window()
@@ -563,7 +743,7 @@ def test_ring_script_conditions_and_the_unplanted_fake(dtype):
     once = {}
     d = _driver("ring", dtype, hooks=[_conditions(seen, once), wrap_hook])
     LC.ring_script(d)
-    assert all(once[name] >= 1 for name in ONCE), once
+    assert all(once[name] >= 1 for name in ONCE + ONCE_WRAPPED), once
     labels = [s[0] for s in seen]
     assert labels.count("wrapped twice") == 2 and "7 restored linear" in labels and labels[-1] == "8 reset, append"
     assert all(0.2 <= g <= 0.8 for g in d.gated) and len(d.gated) == 1, d.gated
@@ -580,7 +760,12 @@ DEFECTS = [("stale_norm", "linear", "default topk"), ("tags_not_moved", "linear"
            ("where_ids_stale", "linear", "mask_where"), ("span_by_slot", "ring", "topk_span"),
            ("mix_stale_norm", "linear", "topk_mix"), ("diverse_stale_norm", "linear", "last_diverse_mmr"),
            ("links_own_group", "linear", "recall_links max_back=None exclude_group=True"),
-           ("links_page_edge", "ring", "recall_links")]
+           ("links_page_edge", "ring", "recall_links"),
+           ("bias_remapped", "linear", "topk_biased"), ("bias_by_row", "ring", "topk_biased"),
+           ("bias_sees_dead_slots", "linear", "topk_biased"), ("bias_stale_norm", "linear", "topk_biased"),
+           ("fold_stale_norm", "linear", "topk_fold"), ("fold_term_of_max", "linear", "term indices"),
+           ("seq_wrong_side", "ring", "topk_seq"), ("seq_spans_sources", "linear", "topk_seq seq_gap"),
+           ("seq_mask_blocks", "linear", "topk_seq seq_masked")]
 
 
 @pytest.mark.parametrize("defect,script,message", DEFECTS, ids=[d[0] for d in DEFECTS])
@@ -590,6 +775,25 @@ def test_planted_defect_fails_the_checkpoint(defect, script, message):
         SCRIPTS[script][0](d)
     assert message in str(e.value), str(e.value)[:300]
     assert d.log, "the defect showed before the first checkpoint passed: the script did not get going"
+
+
+def test_fewer_live_rows_than_steps_is_padding():
+    """No script checkpoint has between 1 and 3 live rows (below 16 the probes are never-stored rows and the window is
+    empty), so the rule is held here directly: with fewer live rows than the sequence has steps there is no chain, and the
+    model, the oracle's loop statement and the fake all return padding; with exactly J rows the one chain is the answer."""
+    bits, _ = LC.pool("f16")
+    for n in (1, LC.SEQ_J - 1, LC.SEQ_J):
+        m, _ = _filled(n=n, capacity=8)
+        steps = SQ.steps_at(bits, "f16", np.arange(LC.SEQ_J)[None], 3)
+        want = m.exp_seq(steps, None, LC.K, LC.SEQ_G, 1)
+        loop = SQ.seq_topk_loop(steps, m.rows, LC.K, LC.SEQ_G, 1, "f16", tags=m.tags)
+        s, r, sr, ss = FakeMemory(m).topk_seq(steps, LC.K, max_step=LC.SEQ_G, min_sep=1)
+        for got in (loop, (r, s, sr, ss)):
+            assert all(np.array_equal(a, b) for a, b in zip(got, want)), n
+        if n < LC.SEQ_J:
+            assert (want[0] == -1).all() and not want[1].any() and (want[2] == -1).all() and not want[3].any(), n
+        else:
+            assert want[0][0].tolist() == [n - 1] + [-1] * (LC.K - 1) and want[2][0, 0].tolist() == list(range(n))
 
 
 def test_ghost_rows_are_seen_by_the_next_gated_append():

@@ -2,18 +2,28 @@
 
 Two scripts - a linear memory of 1,600 rows and a ring of 600, grouped and tagged - apply every mutator in turn: keyed,
 tagged and gated appends, erases by scope and by rows, whole and tail regroups, the ring overwrite, reset, snapshot /
-restore.  After every step ``lifecycle_ref.checkpoint`` compares the accessors, the raw columns and all fourteen readers
+restore.  After every step ``lifecycle_ref.checkpoint`` compares the accessors, the raw columns and all seventeen readers
 - ``topk``, ``topk_grouped``, ``topk_scoped``, ``topk_grouped_scoped``, ``topk_clip``, ``range_search``, ``events``,
-``summaries``, ``topk_masked``, ``topk_span``, ``topk_mix``, ``topk_diverse`` with ``last_diverse_mmr`` and
-``recall_links``, the mask builders ``mask_of_rows`` / ``mask_of_scope`` / ``mask_where`` through ``rows_of_mask``; each
-top-k reader in its default and its exact form - with the model: rows, keys and fp64 score bits equal.  The masks are
+``summaries``, ``topk_masked``, ``topk_span``, ``topk_mix``, ``topk_diverse`` with ``last_diverse_mmr``,
+``recall_links``, ``topk_biased``, ``topk_fold`` (max and min, with its term indices) and ``topk_seq`` (with its step
+rows and step scores), the mask builders ``mask_of_rows`` / ``mask_of_scope`` / ``mask_where`` through ``rows_of_mask``
+and the column builders ``bias_of_rows`` / ``bias_of_age`` read back at the slots of the live rows; each top-k reader in
+its default and its exact form - with the model: rows, keys and fp64 score bits equal.  The masks are
 all ones, a scope mask, the exclusion of the rows just shown, a metadata filter and the previous checkpoint's exclusion
-mask searched again, stale, after the mutation; the spans include one carried over in the same way.  Where a feature's
-own oracle condition says that the fast path of the masked, span, mixed or diverse search must certify a query, its flag
-must be 0.  tests/test_lifecycle_cpu.py proves the scripts' conditions and that the checkpoint fails on planted defects.
+mask searched again, stale, after the mutation; the spans include one carried over in the same way, and so do the bias
+columns (zeros, a boost of the rows just shown, age with a fill that would win every ranking, and the previous
+checkpoint's boost).  The six sequences lie across an erase join, at the newest and the oldest row (in the wrapped ring:
+across slots capacity - 1 and 0), across a change of source, over a row their mask leaves out, and under the carried mask.
+Where a feature's own oracle condition says that the fast path of the masked, span, mixed, diverse, biased, any/all or
+sequence search must certify a query, its flag must be 0.  tests/test_lifecycle_cpu.py proves the scripts' conditions and
+that the checkpoint fails on planted defects.
 
-Measured on one MI355X (profiles/lifecycle.json): 1.0 - 2.3 s per script and dtype (0.3 - 0.8 s with the
-nine readers of the parent commit, same session), 3.3 s for the first case under pytest, which builds the data pools.
+Measured on one MI355X (profiles/lifecycle.json): 1.6 - 4.3 s per script and dtype (1.0 - 2.3 s with the
+fourteen readers of the parent commit, same session), 4.4 s for the slowest case under pytest; most of the added time is
+the host oracles', the fold oracle's first.  Flag 0 is demanded of the biased, the any/all and the sequence search for
+nearly every query of every fp16 checkpoint and was met; it is not demanded on the empty memory, of a query without a
+selected row, of the `min` queries under WEIGHTS for which fold_ref.flag0_ok does not hold, and in bf16 once the sticky
+word is set.
 """
 import time
 
@@ -58,6 +68,16 @@ class IO:
     def i64d(x):
         """-> device int64 tensor (the spans as ``[Q, 2]``)."""
         return torch.tensor(x, dtype=torch.int64).cuda()
+
+    @staticmethod
+    def col_at(col, slots):
+        """A device fp32 bias column read back at the given slots -> numpy."""
+        return col[torch.from_numpy(np.ascontiguousarray(slots, dtype=np.int64)).to(col.device)].cpu().numpy()
+
+    @staticmethod
+    def keep(col):
+        """A copy of a column that outlives the stack it was built in: the next checkpoint searches it again."""
+        return col.clone()
 
     @staticmethod
     def _col(mem, fn, n, width=None):
@@ -109,6 +129,9 @@ def run_life(script, dtype, capacity, ring, tmp_path):
     record = {"seconds": round(seconds, 2), "checkpoints": len(d.log),
               "uncertified": [{"checkpoint": label, **counts} for label, counts in d.log]}
     print(f"{script.__name__} {dtype}: {len(d.log)} checkpoints in {seconds:.1f} s")
+    worst = {name: max(counts[name] for _, counts in d.log) for name in LC.UNCERT}
+    print(f"{script.__name__} {dtype}: most queries sent to the redo by one memory: "
+          + ", ".join(f"{name[:-len('_count')]}={n}" for name, n in worst.items()))
     return d, end, record
 
 

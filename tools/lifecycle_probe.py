@@ -4,8 +4,8 @@ checkpoint sent to the exhaustive redo.
   python tools/lifecycle_probe.py [--out profiles/lifecycle.json] [--parent parent.json]
 
 Per script and dtype: the wall time from the memory's creation to its close, the number of checkpoints, and after every
-checkpoint the ``*_uncertified_count`` of each reader (cumulative per memory) - the masked, span, mixed and diverse
-searches included; the span counter also counts the pages of ``recall_links``.  The counts are recorded, not asserted;
+checkpoint the ``*_uncertified_count`` of each reader (cumulative per memory) - the masked, span, mixed, diverse, biased,
+any/all and sequence searches included; the span counter also counts the pages of ``recall_links``.  The counts are recorded, not asserted;
 what the checkpoint asserts is the per-query flag wherever a feature's oracle condition says the fast path must certify.
 ``--parent``: the file this tool wrote at the parent commit on the same machine in the same session; its seconds are
 recorded beside the new ones as ``parent_seconds``.
@@ -49,9 +49,9 @@ def main():
     out = {"device": torch.cuda.get_device_name(0),
            "note": "uncertified = queries (clips) each reader's fp32 stage sent to the exhaustive redo since the memory "
                    "was created, read after every checkpoint; recorded, not asserted (the checkpoint asserts the "
-                   "per-query flags of the masked, span, mixed and diverse searches where their oracle conditions say "
-                   "the fast path must certify).  seconds = one warm run of the script, memory creation to close, the "
-                   "host oracle's time included; parent_seconds = the same at the parent commit (nine readers), same "
+                   "per-query flags of the masked, span, mixed, diverse, biased, any/all and sequence searches where "
+                   "their oracle conditions say the fast path must certify).  seconds = one warm run of the script, memory creation to close, the "
+                   "host oracle's time included; parent_seconds = the same at the parent commit (fourteen readers), same "
                    "machine, same session.",
            "tests": tests}
     with open(args.out, "w") as f:
